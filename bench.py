@@ -18,6 +18,7 @@ and merged in rank order on every rank.
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (bare: starts the N ranks itself, as children, and relays rank 0's line;
                                          refuses -- non-zero exit -- when the machine has fewer than N GPUs)
+    python bench.py ... --dump-outputs DIR   (also writes what the last timed step returned: dump_outputs below)
 """
 import argparse
 import json
@@ -54,16 +55,16 @@ def reference_cpu_baseline(sample_rows, seed):
     cargo = shutil.which("cargo")
     if not cargo:
         return None, "no cargo on PATH"
-    ref = os.environ.get("TGX_TERM_GUARD_PATH", "/root/reference/term-guard")
-    if not os.path.exists(os.path.join(ref, "Cargo.toml")):
+    ref = os.environ.get("TGX_TERM_GUARD_PATH")
+    if not ref or not os.path.exists(os.path.join(ref, "Cargo.toml")):
         return None, "term-guard sources not found (TGX_TERM_GUARD_PATH)"
     home = os.environ.get("TGX_CARGO_HOME", os.environ.get("CARGO_HOME", os.path.expanduser("~/.cargo")))
     if not (os.path.isdir(os.path.join(crate, "vendor")) or os.path.isdir(os.path.join(home, "registry", "cache"))):
         return None, "no offline crate registry (vendor/ or $CARGO_HOME/registry)"
     env = dict(os.environ, CARGO_HOME=home)
     cmd = [cargo, "build", "--release", "--offline", "--manifest-path", os.path.join(crate, "Cargo.toml")]
-    if ref != "/root/reference/term-guard":
-        cmd += ["--config", 'patch.crates-io.term-guard.path="%s"' % ref]
+    if os.path.realpath(ref) != os.path.realpath(os.path.join(crate, "..", "..", "..", "reference", "term-guard")):
+        cmd += ["--config", 'patch.crates-io.term-guard.path="%s"' % ref]  # (Cargo.toml's path is the default)
     try:
         b = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800)
         if b.returncode != 0:
@@ -117,6 +118,41 @@ def cpu_baseline(torch, layout, unique_cols, table, sample_rows):
             "sample": "first %d rows x %d cols of the same table, oracle/suite_mt.c on %d threads (best of %d runs, "
                       "%.2f s each); single thread on the first %d rows (%.1f s)"
                       % (sample_rows, len(layout), cores, runs, best, one_rows, dt1)}
+
+
+def dump_outputs(out_dir, specs, res):
+    """--dump-outputs DIR: what the last timed step returned to its caller -- one tgx_result per check of the plan --
+    as DIR/<field>.npy, one float64 array per field of the result, indexed by the check's position in the plan;
+    check_kind.npy and check_column.npy say which check each position is.  A NUMERIC_STATS field that its result
+    declares SQL NULL (include/tgx.h: has_value / has_variance == 0; the library leaves NaN there) is written as 0, and
+    has_value.npy / has_variance.npy say which entries those are.  A float64 holds integers exactly only up to 2^53, so
+    every 64-bit integer field is also written exactly as <field>_hi32.npy (v >> 32) and <field>_lo32.npy
+    (v & 0xFFFFFFFF).  A few KB in all, whatever --rows is."""
+    import ctypes
+
+    import numpy as np
+    from term_amd._lib import NUMERIC_STATS
+
+    null_unless = {f: "has_value" for f in ("min_i", "max_i", "min_f", "max_f", "sum_i", "sum_f", "mean")}
+    null_unless.update(var_samp="has_variance", stddev_samp="has_variance")
+
+    def value(r, field):
+        gate = null_unless.get(field)
+        if r.kind == NUMERIC_STATS and gate is not None and not getattr(r, gate):
+            return 0
+        return getattr(r, field)
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"check_kind": [s.kind for s in specs], "check_column": [s.column for s in specs]}
+    for field, ctype in type(res[0])._fields_:
+        vals = [value(r, field) for r in res]
+        arrays[field] = vals
+        if ctype in (ctypes.c_int64, ctypes.c_uint64):
+            arrays[field + "_hi32"] = [v >> 32 for v in vals]
+            arrays[field + "_lo32"] = [v & 0xFFFFFFFF for v in vals]
+    for name, vals in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.array(vals, dtype=np.float64))
+    return sorted(arrays)
 
 
 def launcher_command(n_gpus, port, script_args):
@@ -219,6 +255,8 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the other BASELINE.json configs (C2, C3, C4 on one GPU, C5) and the cold-step measurement "
                          "that follow the headline's timed region at N = 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (every check's result) as DIR/<name>.npy")
     ap.add_argument("--force-distributed", action="store_true",
                     help="run the N>1 code path (range agreement, bitmap-slice exchange, all-gather merge) even "
                          "with one rank: a self-test of the multi-GPU step on a 1-GPU box")
@@ -226,6 +264,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     # Every rank, however it was launched (by launch_ranks below or by `python -m torch.distributed.run ... bench.py`),
     # before its first GPU call: the host driver of this pool only supports dmabuf IPC, and with the legacy mode RCCL /
     # device-memory sharing across processes fails with `hipIpcGetMemHandle: invalid argument` (stated by the pool's
@@ -356,6 +396,9 @@ def main():
         ok &= by_col[0][T.NUMERIC_STATS].sum_i == n_total * (n_total - 1) // 2
         ok &= 0 < d_k.distinct <= max(1, n_total // 10)
         verified = bool(ok)
+
+    if rank == 0 and args.dump_outputs:  # (every rank holds the whole table's results: rank 0 writes them)
+        dump_outputs(args.dump_outputs, specs, res)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3

@@ -1,0 +1,83 @@
+"""bench.py --dump-outputs DIR: what the last timed step returned (one result per check of the plan) as DIR/<name>.npy,
+float64, so that two builds can be compared output for output; --steps is the number of timed steps."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def test_dump_writes_every_result_field_and_64_bit_integers_exactly(tmp_path):
+    import bench
+    from term_amd._lib import COUNT, DISTINCT, NUMERIC_STATS, Result, spec
+
+    specs = [spec(COUNT, 0), spec(NUMERIC_STATS, 0), spec(DISTINCT, 1), spec(NUMERIC_STATS, 2), spec(NUMERIC_STATS, 3)]
+    res = [Result() for _ in specs]
+    big = (1 << 62) + 3  # not a float64: only the hi / lo halves keep it
+    nan = float("nan")
+    res[0].kind, res[0].total, res[0].non_null = COUNT, big, big - 1
+    res[1].kind, res[1].min_i, res[1].max_i, res[1].sum_i, res[1].mean = NUMERIC_STATS, -(1 << 40) - 7, 99, -big, 1.25
+    res[1].has_value, res[1].var_samp, res[1].stddev_samp = 1, nan, nan  # no variance asked for: SQL NULL
+    res[2].kind, res[2].distinct, res[2].kll_n = DISTINCT, 12345, (1 << 64) - 1
+    # no non-NULL rows: MIN / MAX / AVG and the variance are SQL NULL, left as NaN by the library
+    res[3].kind, res[3].total = NUMERIC_STATS, 7
+    res[3].min_f = res[3].max_f = res[3].mean = res[3].var_samp = res[3].stddev_samp = nan
+    res[4].kind, res[4].has_value, res[4].has_variance, res[4].var_samp, res[4].stddev_samp = NUMERIC_STATS, 1, 1, 4.0, 2.0
+    names = bench.dump_outputs(str(tmp_path / "out"), specs, res)
+
+    files = sorted(f[:-4] for f in os.listdir(tmp_path / "out"))
+    assert files == names
+    assert {f for f, _ in Result._fields_} <= set(files) and {"check_kind", "check_column"} <= set(files)
+    load = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 and a.shape == (5,) and np.isfinite(a).all() for a in load.values())
+    assert load["check_kind"].tolist() == [COUNT, NUMERIC_STATS, DISTINCT, NUMERIC_STATS, NUMERIC_STATS]
+    assert load["check_column"].tolist() == [0, 0, 1, 2, 3]
+    assert load["mean"][1] == 1.25 and load["distinct"][2] == 12345 and load["total"][3] == 7
+    assert load["has_value"].tolist() == [0, 1, 0, 0, 1] and load["has_variance"].tolist() == [0, 0, 0, 0, 1]
+    assert (load["min_f"][3], load["mean"][3], load["var_samp"][1], load["var_samp"][3]) == (0, 0, 0, 0)
+    assert (load["var_samp"][4], load["stddev_samp"][4]) == (4.0, 2.0)
+
+    def exact(field, i):
+        return int(load[field + "_hi32"][i]) * (1 << 32) + int(load[field + "_lo32"][i])
+
+    assert exact("total", 0) == big and exact("non_null", 0) == big - 1
+    assert (exact("min_i", 1), exact("max_i", 1), exact("sum_i", 1)) == (-(1 << 40) - 7, 99, -big)
+    assert exact("kll_n", 2) == (1 << 64) - 1
+    assert sum(os.path.getsize(tmp_path / "out" / (n + ".npy")) for n in names) < 64 << 20
+
+
+def _bench(out_dir, steps):
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    rows = 1 << 22
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", "1", "--rows", str(rows), "--no-cpu-baseline", "--no-secondary",
+                        "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    return rows, line, {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_step_and_the_same_arguments_give_the_same_outputs(tmp_path):
+    import term_amd as T
+
+    rows, line, got = _bench(tmp_path / "a", 3)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["verified"] is True
+    kinds, cols = got["check_kind"].astype(int).tolist(), got["check_column"].astype(int).tolist()
+    assert len(kinds) == 16 * 2 + 2 and (got["total"] == rows).all()
+    assert all(np.isfinite(a).all() for a in got.values()), [n for n, a in got.items() if not np.isfinite(a).all()]
+    i_id = [i for i, (k, c) in enumerate(zip(kinds, cols)) if k == T.NUMERIC_STATS and c == 0][0]
+    d_id = [i for i, (k, c) in enumerate(zip(kinds, cols)) if k == T.DISTINCT and c == 0][0]
+    sum_id = int(got["sum_i_hi32"][i_id]) * (1 << 32) + int(got["sum_i_lo32"][i_id])
+    assert sum_id == rows * (rows - 1) // 2 and got["distinct"][d_id] == rows  # the id column is a permutation
+    _, line2, again = _bench(tmp_path / "b", 2)
+    assert line2["steps"] == 2 and sorted(again) == sorted(got)
+    for name in got:
+        np.testing.assert_array_equal(again[name], got[name], err_msg=name)
