@@ -425,7 +425,7 @@ extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_com
   // stream for the two phases (StreamLoan) and the two are joined by an event before the states are packed.
   const bool has_spearman_tasks = plan->spearman && spearman_num_tasks(plan) > 0;
   const bool overlap = comm->ops.device_buffers && st->device_ready && st->keys_ready_recorded && nd > 0 &&
-                       !has_spearman_tasks && getenv("TGX_NO_EXCHANGE_OVERLAP") == nullptr;
+                       !has_spearman_tasks;
   st->exchange_expected = comm->ops.device_buffers != 0 && nd > 0;
   struct StreamLoan {
     tgx_state *st;

@@ -1001,15 +1001,11 @@ tgx_status tgx::coalesce_flush(tgx_state *st, tgx_error *err) {
   co.deferred_bytes = 0;
   if (co.arena_used) {
     // (the arena's device twin is free: whoever read it last was waited for when the arena's first window was noted)
-    static const bool own_stream = !(getenv("TGX_COALESCE_COPY_STREAM") && atoi(getenv("TGX_COALESCE_COPY_STREAM")) == 0);
-    if (own_stream && !co.copy_stream) HIP_TRY(stream_acquire(&co.copy_stream, false));
-    if (own_stream && !co.upload_done[ar]) HIP_TRY(hipEventCreateWithFlags(&co.upload_done[ar], hipEventDisableTiming));
-    hipStream_t up = own_stream ? co.copy_stream : st->stream;
-    HIP_TRY(hipMemcpyAsync(co.arena_dev[ar].p, co.arena_host[ar], co.arena_used, hipMemcpyHostToDevice, up));
-    if (own_stream) {
-      HIP_TRY(hipEventRecord(co.upload_done[ar], up));
-      HIP_TRY(hipStreamWaitEvent(st->stream, co.upload_done[ar], 0));
-    }
+    if (!co.copy_stream) HIP_TRY(stream_acquire(&co.copy_stream, false));
+    if (!co.upload_done[ar]) HIP_TRY(hipEventCreateWithFlags(&co.upload_done[ar], hipEventDisableTiming));
+    HIP_TRY(hipMemcpyAsync(co.arena_dev[ar].p, co.arena_host[ar], co.arena_used, hipMemcpyHostToDevice, co.copy_stream));
+    HIP_TRY(hipEventRecord(co.upload_done[ar], co.copy_stream));
+    HIP_TRY(hipStreamWaitEvent(st->stream, co.upload_done[ar], 0));
     co.host_flushes++;
   }
   HIP_TRY(hipMemcpyAsync(co.desc_dev[ar].p, gs, g * sizeof(GatherSeg), hipMemcpyHostToDevice, st->stream));

@@ -527,14 +527,10 @@ void bitmap_shape(const DistinctState &ds, int64_t length, bool mult, uint32_t *
   // buckets, as ever.  Without (round 5): <= 256 -- a list entry is then 2 bytes where a bucket holds <= 2^16 keys, else
   // 20 bits (three to an 8-byte word: distinct_run_numeric, `pack20`).  Measured at 1 G keys over 10^8 values: 1526
   // buckets of 2-byte entries 3.26 ms, 763 / 382 / 191 / 96 buckets of 20-bit entries 3.09 / 3.07 / 2.93 / 3.36 ms.
-  // (TGX_BUCKET_TARGET overrides the aim, TGX_KEY16=0 forbids 2-byte entries: experiments)
-  const char *bt = getenv("TGX_BUCKET_TARGET");
-  const uint64_t bucket_target = bt ? std::max<uint64_t>(1, strtoull(bt, nullptr, 10)) : (mult ? 1024 : 256);
-  const char *k16 = getenv("TGX_KEY16");
-  const bool allow_key16 = !(k16 && atoi(k16) == 0);
+  const uint64_t bucket_target = mult ? 1024 : 256;
   uint32_t sub_bits = 14;
   while (sub_bits < (mult ? 19u : 20u) && ((ds.range + (1ull << sub_bits) - 1) >> sub_bits) > bucket_target) sub_bits++;
-  const bool key16 = allow_key16 && !mult && sub_bits <= 16;
+  const bool key16 = !mult && sub_bits <= 16;
   const uint64_t n_buckets = (ds.range + (1ull << sub_bits) - 1) >> sub_bits;
   uint64_t cap_slots = (uint64_t)length / std::max<uint64_t>(n_buckets, 1);
   cap_slots = cap_slots + cap_slots / 4 + 16 * (((uint64_t)length >> 15) + 1) + 4096;
@@ -864,14 +860,11 @@ tgx_status distinct_run_numeric(tgx_state *st, size_t slot, const tgx_column &c,
       if (pp.cap >= (1ull << 32) - 64) return fail(err, TGX_INTERNAL, "distinct: list capacity out of range");
       pp.want_multiplicity = mult ? 1 : 0;
       pp.key16 = prep.key16 ? 1 : pack20 ? 2 : 0;
-      static const bool no_probe = getenv("TGX_NO_CLUSTERED_PROBE") && atoi(getenv("TGX_NO_CLUSTERED_PROBE")) != 0;
-      pp.probe = no_probe ? 0 : 1;
       // Only the form the column's last batch took is launched (PartitionParams::force_form; either form is correct on
       // any keys, the probe still runs and the next finalize remembers what it said): the form that would leave at once
       // still costs its dispatch, 1024 threads x a workgroup per CU -- C2 over 40 steps, three runs each: 1.594 against
-      // 1.606 ms.  TGX_FORM_MEMORY=0 launches both again.
-      static const bool form_memory = !(getenv("TGX_FORM_MEMORY") && atoi(getenv("TGX_FORM_MEMORY")) == 0);
-      pp.force_form = (form_memory && !no_probe) ? ds.remembered_form : 0;
+      // 1.606 ms.
+      pp.force_form = ds.remembered_form;
       HIP_TRY(ds.lists.reserve(prep.key16 ? (uint64_t)pp.n_lists * pp.cap * sizeof(uint16_t)
                                : pack20   ? (uint64_t)pp.n_lists * pp.cap / 3 * 8
                                           : (uint64_t)pp.n_lists * pp.cap * sizeof(uint32_t)));

@@ -172,6 +172,8 @@ struct ScanTask {
   int column;
   bool variance;
   bool stats_needed = false;  // a NUMERIC_STATS spec or a key set's range reads its MIN / MAX / SUM (else COUNT only)
+  bool stats_spec = false;    // a NUMERIC_STATS spec is bound to the task
+  bool read_by_spec = false;  // a NUMERIC_STATS spec or a COUNT spec that rides on the scan reads the task
 };
 struct CountTask {
   int column;
@@ -636,11 +638,6 @@ struct tgx_state {
   // state's own stream is still scanning, and joins the two with `aux_done`
   hipStream_t aux_stream = nullptr;
   hipEvent_t keys_ready = nullptr, aux_done = nullptr;
-  // the key columns' uniqueness passes BESIDE the scan (update.cpp, round 6): they are queued on `key_stream` behind
-  // `batch_in` (what the state's stream held when the update began) and the state's stream waits for `keys_ready`
-  // once the scan is queued
-  hipStream_t key_stream = nullptr;
-  hipEvent_t batch_in = nullptr;
   bool keys_ready_recorded = false;  // since the last reset, and standing for EVERY key set of the plan
   int64_t passes = 0;                // fused passes (batches or flushes) with rows since the last reset
   bool exchange_expected = false;    // the state has been through tgx_allreduce: its scans leave room for the exchange

@@ -80,13 +80,7 @@ struct BitmapView {
 constexpr uint32_t kMaxPartitions = 2048;
 constexpr uint32_t kListPad = 0xFFFFFFFFu;  // filler of the padded runs in the bucket lists
 // a (tile, bucket) run is padded to a whole number of these many slots: 4-byte entries / 2-byte entries
-#ifndef TGX_RUN_PAD4
-#define TGX_RUN_PAD4 16
-#endif
-#ifndef TGX_RUN_PAD2
-#define TGX_RUN_PAD2 32
-#endif
-constexpr int kRunPad4 = TGX_RUN_PAD4, kRunPad2 = TGX_RUN_PAD2;
+constexpr int kRunPad4 = 16, kRunPad2 = 32;
 constexpr int kPartitionThreads = 1024;
 constexpr int kPartitionKeysPerThread = 32;
 constexpr int kPartitionTile = kPartitionThreads * kPartitionKeysPerThread;  // 32768 keys
@@ -120,7 +114,6 @@ struct PartitionParams {
   // a stream whose keys grow covers a few slices of a bitmap that has grown with the stream): lists are laid out and
   // sized for these only; a key that lands in another bucket after all takes the spill path (exact, slow)
   uint32_t bucket0, n_lists;
-  int32_t probe;  // 0: partition_init_kernel leaves the clustered flag at 0 (TGX_NO_CLUSTERED_PROBE=1: for A/B runs)
   // 0: the probe's flag picks the form and BOTH forms of partition_kernel are launched (the other one leaves at once:
   // ~5 us of a 1.6 ms step); 1 / 2: the host remembers which form the column's last batch took (counters[kCntForm]) and
   // launches only that one -- plain / CLUSTERED -- whatever the probe says: both forms are exact for any keys, a wrong

@@ -745,12 +745,8 @@ void launch_regex(const RegexColDesc &d, const DfaView &dfa, unsigned long long 
   // the limit was kRegexLdsEntries (32 KiB: five to seven workgroups a CU) and bigger automata were walked from L2 by
   // seven; round 6 measured the 316-state automaton of `^[\w.@+-]*$` (61 KiB: TWO workgroups a CU) at 1.90 ms per
   // 100 M x 28 B from LDS against 2.96 ms from L2 -- the dependent table read is what a walk waits for.
-  // TGX_REGEX_LDS_ENTRIES overrides (16384: the old rule).
-  static const uint64_t lds_entries = [] {
-    const char *e = getenv("TGX_REGEX_LDS_ENTRIES");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : (uint64_t)32767;
-  }();
-  const bool in_lds = direct || (entries <= lds_entries && entries * 2 <= 65535);
+  constexpr uint64_t kLdsEntries = 32767;
+  const bool in_lds = direct || (entries <= kLdsEntries && entries * 2 <= 65535);
   const RegexLds lds = regex_lds_layout(dfa.n_states, dfa.n_classes, in_lds);
   const bool view = d.views != nullptr;
   // persistent grid: exactly the workgroups that stay resident (LDS, and 7 rather than 8 waves per SIMD at this
@@ -774,7 +770,6 @@ void launch_regex(const RegexColDesc &d, const DfaView &dfa, unsigned long long 
     constexpr uint32_t kLdsGranule = 1280;
     const int by_lds = (int)((160u << 10) / ((lds.total + kLdsGranule - 1) / kLdsGranule * kLdsGranule));
     if (by_lds >= 1 && occ > by_lds) occ = by_lds;
-    if (const char *e = getenv("TGX_REGEX_RESIDENT")) occ = std::max(1, atoi(e));  // (experiments: workgroups per CU)
     cache[{id, lds.total}] = occ;
     return occ;
   };

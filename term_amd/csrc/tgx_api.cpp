@@ -343,6 +343,12 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     plan->bind[i].slot = slot;
     plan->bind[i].count_src = Source::kCount;
   }
+  for (size_t i = 0; i < n_specs; i++) {
+    const SpecBinding &b = plan->bind[i];
+    if (b.kind == TGX_CHECK_NUMERIC_STATS) plan->scan[b.slot].stats_spec = true;
+    if (b.kind == TGX_CHECK_NUMERIC_STATS || (b.kind == TGX_CHECK_COUNT && b.count_src == Source::kScan))
+      plan->scan[b.slot].read_by_spec = true;
+  }
   plan->n_columns_needed = max_col + 1;
   regex_plan_finish(plan.get());
   // which columns the plan touches, whose values it reads, and which 4-byte numeric columns a pass needs widened
@@ -620,8 +626,6 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   if (st->aux_done) (void)hipEventDestroy(st->aux_done);
   // (idle: the device has been waited for above) back to the pool -- hipStreamDestroy costs ~0.5 ms
   if (st->aux_stream) stream_release(st->aux_stream, true);
-  if (st->batch_in) (void)hipEventDestroy(st->batch_in);
-  if (st->key_stream) stream_release(st->key_stream, false);
   if (st->coalesce.copy_stream) stream_release(st->coalesce.copy_stream, false);
   if (st->own_stream && st->stream) stream_release(st->stream, false);
   delete st;

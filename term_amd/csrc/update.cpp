@@ -34,9 +34,7 @@ inline void update_mark(const char *what) {
 // ------------------------------------------------------------------------------------------------
 // update
 
-// copies a HOST column's buffers to the device; `out` is the device view
-
-
+// copies a HOST column's buffers to the device; `out` is the device view.
 // `widen32`: a TGX_INT32 / TGX_FLOAT32 column is needed as 8-byte values (DISTINCT, KLL, co-moments, Spearman); the
 // scan alone reads 4-byte values as they are
 tgx_status stage_column(tgx_state *st, const tgx_column &c, tgx_column *out, tgx_error *err,
@@ -365,26 +363,73 @@ extern "C" tgx_status tgx_update(const tgx_plan *plan, tgx_state *st, const tgx_
   return tgx::abi_exception(err);
 }
 
-// one batch through the fused pass: device views of its columns, then every kernel of the plan
-tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, int64_t nrows,
-                              tgx_error *err) {
-  TGX_TRY(state_init_device(st, err));
-  const std::vector<char> &used = plan->used;
+// ---- the phases of one batch through the fused pass (update_impl) ----
+namespace {
 
-  // device views of every used column
+struct StagedBatch {
+  std::vector<tgx_column> dev;  // device views of the plan's columns (unused ones left empty)
+  bool any_host = false;        // a used HOST column has rows
+  bool arena_in_use = false;    // small HOST buffers travelled in the pinned arena
+};
+
+// A COMOMENTS pair whose columns are scanned by ONE workgroup per tile pair (scan_pair_kernel)
+struct FusedPair {
+  int como, x, y;
+  ScanColDesc dx, dy;
+};
+
+// What the phases of one batch decide and hand on: which task rides on which launch, and what ran before `keys_ready`
+struct BatchFusion {
+  std::vector<int> kll_on_col, pair_of_col, hll_on_col;  // per column: its KLL task / fused pair / HLL task, or -1
+  std::vector<char> kll_fused, como_fused;                // per KLL / COMOMENTS task: it rides on the scan
+  std::vector<char> distinct_idle;                        // per key set: the HLL lane answers for it
+  std::vector<FusedPair> fused_pairs;
+  std::vector<NumericPrep> dprep;        // per key set: the shape of its numeric pass
+  std::vector<int> stats_by_partition;   // per scan task: the key set whose pass brings its aggregates, or -1
+  std::vector<char> distinct_done;       // per key set: updated before `keys_ready`
+
+  // the scan task whose aggregates key set q's pass produces, or -1
+  int stats_slot(const tgx_plan *plan, size_t q) const {
+    const int s = plan->distinct[q].scan_slot;
+    return (s >= 0 && stats_by_partition[s] == (int)q) ? s : -1;
+  }
+};
+
+int scan_slot_of(const tgx_plan *plan, int col) {
+  for (size_t q = 0; q < plan->scan.size(); q++)
+    if (plan->scan[q].column == col) return (int)q;
+  return -1;
+}
+
+// waves of a fused launch and the most rows one of them sees (sizes the sampler's buffers)
+int fused_blocks(const ScanColDesc &d, int n_tasks) {
+  const int64_t units = d.n_tiles > 0 ? d.n_tiles : (d.length + 63) / 64;
+  int64_t want = (units + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
+  const int64_t cap = std::max(32, (g_ctx.n_cu * 3) / std::max(1, n_tasks));
+  return (int)std::max<int64_t>(1, std::min(want, cap));
+}
+
+int64_t rows_per_wave(const ScanColDesc &d, int blocks) {
+  const int64_t waves = (int64_t)blocks * kWavesPerBlock;
+  if (d.n_tiles > 0) return (d.n_tiles + waves - 1) / waves * kTileRows;
+  return ((d.length + 63) / 64 + waves - 1) / waves * 64;
+}
+
+// device views of every used column; the pinned arena uploaded and the pending widenings queued behind it
+tgx_status stage_batch(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, StagedBatch *b, tgx_error *err) {
   st->staging_used = 0;
   if (st->arena_used) (void)hipStreamSynchronize(st->stream);  // an update that failed half way left it in use
   st->arena_used = 0;
   st->host_direct = false;
   st->dict_views.clear();
   st->pending_widen.clear();
-  std::vector<tgx_column> dev(plan->n_columns_needed);
+  std::vector<tgx_column> &dev = b->dev;
+  dev.assign(plan->n_columns_needed, tgx_column());
   // 4-byte numeric columns are widened to 8-byte values only for the passes that need them so
   const std::vector<char> &needs_wide = plan->needs_wide;
-  bool any_host = false;
   for (int i = 0; i < plan->n_columns_needed; i++) {
-    if (!used[i]) continue;
-    if (columns[i].mem == TGX_MEM_HOST && columns[i].length > 0) any_host = true;
+    if (!plan->used[i]) continue;
+    if (columns[i].mem == TGX_MEM_HOST && columns[i].length > 0) b->any_host = true;
     if (columns[i].length == 0) {
       dev[i] = columns[i];
       if ((is_numeric32(dev[i].type) && needs_wide[i]) || is_narrow_int(dev[i].type)) dev[i].type = widened_type(dev[i].type);
@@ -404,518 +449,454 @@ tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *co
     TGX_TRY(stage_column(st, columns[i], &dev[i], err, widen));
   }
   update_mark("staged");
-  const bool arena_in_use = st->arena_used != 0;
-  if (arena_in_use)
+  b->arena_in_use = st->arena_used != 0;
+  if (b->arena_in_use)
     HIP_TRY(hipMemcpyAsync(st->arena_dev[st->arena_cur].p, st->arena_host[st->arena_cur], st->arena_used,
                            hipMemcpyHostToDevice, st->stream));
   for (const auto &w : st->pending_widen) launch_widen32(w.src, w.dst, w.n, w.mode, g_ctx.n_cu, st->stream);
   st->pending_widen.clear();
+  return TGX_OK;
+}
 
-  if (nrows > 0) {
-    // ---- what rides on the numeric scan of this batch (kernels/scan.hip) ----
-    // A COMOMENTS pair whose columns are plain 8-byte numerics is scanned by ONE workgroup per tile pair
-    // (scan_pair_kernel): both columns' own aggregates and the co-moments from one read.  A KLL task of a batch big
-    // enough to be sampled hands its sampler to the scan of its column (scan_kll_kernel / the pair kernel).  So a
-    // suite with range, quantile and correlation checks on the same columns reads them once.
-    const int n_plan_cols = plan->n_columns_needed;
-    std::vector<int> kll_on_col(n_plan_cols, -1), pair_of_col(n_plan_cols, -1);
-    std::vector<char> kll_fused(plan->kll.size(), 0), como_fused(plan->como.size(), 0);
-    auto scan_slot_of = [&](int col) -> int {
-      for (size_t q = 0; q < plan->scan.size(); q++)
-        if (plan->scan[q].column == col) return (int)q;
-      return -1;
-    };
-    auto plain8 = [&](int col) { return is_numeric(dev[col].type) && dev[col].values != nullptr; };
-    struct FusedPair {
-      int como, x, y;
-      ScanColDesc dx, dy;
-    };
-    std::vector<FusedPair> fused_pairs;
-    // ---- APPROX_DISTINCT: the HyperLogLog lane of the scan for numeric columns; the exact key set elsewhere ----
-    // (decided by the first batch's column type; a column whose scan also carries variance lanes keeps the exact set)
-    std::vector<int> hll_on_col(n_plan_cols, -1);
-    std::vector<char> distinct_is_idle(plan->distinct.size(), 0);
-    for (size_t q = 0; q < plan->hll.size(); q++) {
-      const HllTask &t = plan->hll[q];
-      const int type = dev[t.column].type;
-      const bool numeric = is_numeric(type) || is_numeric32(type);
-      const bool lane = numeric && plan->distinct[t.distinct_slot].approx_only && !plan->scan[t.scan_slot].variance;
-      if (st->hll_mode[q] == 0) st->hll_mode[q] = lane ? 1 : 2;
-      if (st->hll_mode[q] == 1) {
-        if (dev[t.column].values) hll_on_col[t.column] = (int)q;
-        distinct_is_idle[t.distinct_slot] = 1;  // (its approx_only key set has nothing to do)
-      }
+// What rides on the numeric scan of this batch (kernels/scan.hip), decided on the host.  A COMOMENTS pair whose
+// columns are plain 8-byte numerics is scanned by ONE workgroup per tile pair (scan_pair_kernel): both columns' own
+// aggregates and the co-moments from one read.  A KLL task of a batch big enough to be sampled hands its sampler to the
+// scan of its column (scan_kll_kernel / the pair kernel).  So a suite with range, quantile and correlation checks on
+// the same columns reads them once.
+BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows) {
+  const int n_plan_cols = plan->n_columns_needed;
+  BatchFusion f;
+  f.kll_on_col.assign(n_plan_cols, -1);
+  f.pair_of_col.assign(n_plan_cols, -1);
+  f.hll_on_col.assign(n_plan_cols, -1);
+  f.kll_fused.assign(plan->kll.size(), 0);
+  f.como_fused.assign(plan->como.size(), 0);
+  f.distinct_idle.assign(plan->distinct.size(), 0);
+  f.dprep.resize(plan->distinct.size());
+  f.stats_by_partition.assign(plan->scan.size(), -1);
+  f.distinct_done.assign(plan->distinct.size(), 0);
+  auto plain8 = [&](int col) { return is_numeric(dev[col].type) && dev[col].values != nullptr; };
+  // ---- APPROX_DISTINCT: the HyperLogLog lane of the scan for numeric columns; the exact key set elsewhere ----
+  // (decided by the first batch's column type; a column whose scan also carries variance lanes keeps the exact set)
+  for (size_t q = 0; q < plan->hll.size(); q++) {
+    const HllTask &t = plan->hll[q];
+    const int type = dev[t.column].type;
+    const bool numeric = is_numeric(type) || is_numeric32(type);
+    const bool lane = numeric && plan->distinct[t.distinct_slot].approx_only && !plan->scan[t.scan_slot].variance;
+    if (st->hll_mode[q] == 0) st->hll_mode[q] = lane ? 1 : 2;
+    if (st->hll_mode[q] == 1) {
+      if (dev[t.column].values) f.hll_on_col[t.column] = (int)q;
+      f.distinct_idle[t.distinct_slot] = 1;  // (its approx_only key set has nothing to do)
     }
-    auto distinct_idle = [&](size_t q) { return distinct_is_idle[q] != 0; };
-    auto has_hll = [&](int col) { return hll_on_col[col] >= 0; };  // its own scan launch: fuses with nothing else
-    if (nrows >= (1 << 20)) {
-      for (size_t q = 0; q < plan->kll.size(); q++) {
-        const int col = plan->kll[q].column;
-        if (plain8(col) && !has_hll(col) && kll_on_col[col] < 0 && kll_scan_eligible(nrows)) {
-          kll_on_col[col] = (int)q;
-          kll_fused[q] = 1;
-        }
-      }
-      for (size_t q = 0; q < plan->como.size() && fused_pairs.size() < (size_t)kMaxPairsPerLaunch; q++) {
-        const int x = plan->como[q].col_x, y = plan->como[q].col_y;
-        if (x == y || !plain8(x) || !plain8(y) || pair_of_col[x] >= 0 || pair_of_col[y] >= 0) continue;
-        if (has_hll(x) || has_hll(y)) continue;
-        const int sx = scan_slot_of(x), sy = scan_slot_of(y);
-        if ((sx >= 0 && plan->scan[sx].variance) || (sy >= 0 && plan->scan[sy].variance)) continue;
-        FusedPair fp;
-        fp.como = (int)q;
-        fp.x = x;
-        fp.y = y;
-        fill_scan_desc(dev[x], false, nullptr, &fp.dx);
-        fill_scan_desc(dev[y], false, nullptr, &fp.dy);
-        if (fp.dx.head != fp.dy.head || fp.dx.n_tiles != fp.dy.n_tiles) continue;  // tiles must line up
-        pair_of_col[x] = pair_of_col[y] = (int)fused_pairs.size();
-        como_fused[q] = 1;
-        fused_pairs.push_back(fp);
-      }
-    }
-    // waves of a fused launch and the most rows one of them sees (sizes the sampler's buffers)
-    auto fused_blocks = [&](const ScanColDesc &d, int n_tasks) -> int {
-      const int64_t units = d.n_tiles > 0 ? d.n_tiles : (d.length + 63) / 64;
-      int64_t want = (units + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
-      const int64_t cap = std::max(32, (g_ctx.n_cu * 3) / std::max(1, n_tasks));
-      return (int)std::max<int64_t>(1, std::min(want, cap));
-    };
-    auto rows_per_wave = [&](const ScanColDesc &d, int blocks) -> int64_t {
-      const int64_t waves = (int64_t)blocks * kWavesPerBlock;
-      if (d.n_tiles > 0) return (d.n_tiles + waves - 1) / waves * kTileRows;
-      return ((d.length + 63) / 64 + waves - 1) / waves * 64;
-    };
-    // ---- exact uniqueness over dense Int64 keys takes the column's range aggregates along (kernels/distinct.hip,
-    // partition_kernel<.., STATS>): such a column is not scanned at all -- it crosses HBM once for MIN / MAX / SUM /
-    // COUNT and COUNT(DISTINCT) together.  Decided here, before the scan is queued, from a sample of the batch.
-    std::vector<NumericPrep> dprep(plan->distinct.size());
-    std::vector<int> stats_by_partition(plan->scan.size(), -1);
-    update_mark("fused");
-    TGX_TRY(distinct_sample_all(st, dev.data(), err));
-    update_mark("sampled");
-    for (size_t q = 0; q < plan->distinct.size(); q++) {
-      const DistinctTask &t = plan->distinct[q];
-      if (!t.tuple.empty() || !is_numeric(dev[t.column].type) || dev[t.column].length == 0 || distinct_idle(q)) continue;
-      TGX_TRY(distinct_prepare_numeric(st, q, dev[t.column], &dprep[q], err));
-      if (dprep[q].partitioned && dev[t.column].type == TGX_INT64 && t.scan_slot >= 0 &&
-          !plan->scan[t.scan_slot].variance && pair_of_col[t.column] < 0 && kll_on_col[t.column] < 0)
-        stats_by_partition[t.scan_slot] = (int)q;
-    }
-    // ---- the key columns' uniqueness passes go FIRST (numeric keys: everything they need is decided) and an event
-    // marks their end: across ranks the exchange of the key sets (tgx_allreduce) can then run on a second stream
-    // while the scan of the other columns below is still running (the >= 6x target is set by the exchange)
-    std::vector<char> distinct_done(plan->distinct.size(), 0);
-    update_mark("prepared");
-    // BESIDE the scan (round 6, an experiment that stays OFF: TGX_KEYS_BESIDE_SCAN=1 turns it on): the key passes
-    // queued on a stream of their own in front of the scan, which then runs next to them instead of behind them.  The
-    // key stream starts behind everything the state's stream held when the update began (`batch_in`), and the state's
-    // stream waits for `keys_ready` once the scan is queued, so whatever follows the update sees both.  Measured on
-    // MI355X: 1 G rows x 16 columns 24.9 ms against 23.7 one after the other (both kernels stretch: the partition pass
-    // -- one 1024-thread workgroup a CU with 152 KiB of LDS -- and the scan's waves contend for the same CUs and for
-    // HBM the scan alone already saturates); one rank's shard of 125 M rows 3.44 against 3.43 ms.
-    bool any_key_pass = false;
-    for (size_t q = 0; q < plan->distinct.size(); q++) {
-      const DistinctTask &t = plan->distinct[q];
-      any_key_pass |= t.tuple.empty() && !distinct_idle(q) && is_numeric(dev[t.column].type) && dev[t.column].length > 0 &&
-                      dprep[q].partitioned;
-    }
-    static const bool beside_on = [] {
-      const char *e = getenv("TGX_KEYS_BESIDE_SCAN");
-      return e && e[0] == '1';
-    }();
-    const bool beside = beside_on && any_key_pass && nrows >= (1 << 22) && !plan->scan.empty();
-    struct KeyStreamLoan {
-      tgx_state *st;
-      hipStream_t own;
-      bool on = false;
-      ~KeyStreamLoan() {
-        if (on) st->stream = own;
-      }
-    } key_loan{st, st->stream};
-    if (beside) {
-      if (!st->key_stream) {
-        HIP_TRY(stream_acquire(&st->key_stream, false));
-        HIP_TRY(hipEventCreateWithFlags(&st->batch_in, hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventRecord(st->batch_in, st->stream));
-      HIP_TRY(hipStreamWaitEvent(st->key_stream, st->batch_in, 0));
-      st->stream = st->key_stream;
-      key_loan.on = true;
-    }
-    for (size_t q = 0; q < plan->distinct.size(); q++) {
-      const DistinctTask &t = plan->distinct[q];
-      if (!t.tuple.empty() || distinct_idle(q) || !is_numeric(dev[t.column].type) || dev[t.column].length == 0) continue;
-      const int stats_slot = (t.scan_slot >= 0 && stats_by_partition[t.scan_slot] == (int)q) ? t.scan_slot : -1;
-      TGX_TRY(distinct_update(st, q, dev[t.column], err, nullptr, &dprep[q], stats_slot, &columns[t.column]));
-      distinct_done[q] = 1;
-    }
-    update_mark("keys_queued");
-    if (!st->keys_ready) HIP_TRY(hipEventCreateWithFlags(&st->keys_ready, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(st->keys_ready, st->stream));
-    update_mark("event");
-    if (beside) {
-      st->stream = key_loan.own;
-      key_loan.on = false;
-    }
-    // (the event stands for the key sets only when every key set of the plan was touched before it: string,
-    //  dictionary and tuple sets are updated further down, behind the scan)
-    bool all_early = true;
-    for (size_t q = 0; q < plan->distinct.size(); q++) all_early &= distinct_done[q] || distinct_idle(q);
-    // ... and for the running MIN / MAX the facts round reads (allreduce.cpp tightens a bitmap's range with them) only
-    // when they, too, were produced before it: a key column whose aggregates come from the scan below -- a pass that is
-    // not partitioned, variance / pair / KLL / HLL lanes on the key column -- would have its ScanAcc read on the second
-    // stream while the scan is still writing it
-    for (size_t q = 0; q < plan->distinct.size(); q++) {
-      const DistinctTask &t = plan->distinct[q];
-      if (!distinct_done[q] || t.scan_slot < 0 || st->distinct[q].has_hint) continue;
-      all_early &= stats_by_partition[t.scan_slot] == (int)q;
-    }
-    st->keys_ready_recorded = all_early && (st->passes == 0 || st->keys_ready_recorded);
-    st->passes++;
-    // (a state that takes part in exchanges leaves two workgroup slots per CU to the second stream's kernels: the
-    //  scan is HBM-bound from 4 workgroups per CU upwards)
-    const int scan_per_cu = (st->exchange_expected || beside) ? 6 : 8;
-    // ---- numeric scan: all columns of the batch in launches of <= kMaxColsPerLaunch ----
-    {
-      std::vector<ScanColDesc> descs, kll_descs, hll_descs;
-      std::vector<int32_t> index, kll_index, hll_index;
-      std::vector<int> kll_slots;
-      for (size_t s = 0; s < plan->scan.size(); s++) {
-        const tgx_column &c = dev[plan->scan[s].column];
-        if (!is_numeric(c.type) && !is_numeric32(c.type)) {
-          // a scan task that only exists for DISTINCT's range decision does not apply to strings
-          bool needed_by_stats = false;
-          for (size_t i = 0; i < plan->specs.size(); i++)
-            if (plan->specs[i].kind == TGX_CHECK_NUMERIC_STATS && plan->bind[i].slot == (int)s) needed_by_stats = true;
-          if (needed_by_stats)
-            return fail(err, TGX_INVALID_ARGUMENT, "NUMERIC_STATS on non-numeric column %d (type %d)",
-                        plan->scan[s].column, c.type);
-          continue;
-        }
-        if (pair_of_col[plan->scan[s].column] >= 0) continue;  // scanned with its partner below
-        if (stats_by_partition[s] >= 0) continue;                // its DISTINCT pass brings the aggregates
-        if (kll_on_col[plan->scan[s].column] < 0 && hll_on_col[plan->scan[s].column] < 0) {
-          // a scan that only feeds DISTINCT's range decision is not needed once the range is declared
-          bool bound = false, all_hinted = true, any_distinct = false;
-          for (size_t i = 0; i < plan->specs.size(); i++) {
-            const SpecBinding &b = plan->bind[i];
-            if (b.slot == (int)s && (b.kind == TGX_CHECK_NUMERIC_STATS || (b.kind == TGX_CHECK_COUNT && b.count_src == Source::kScan)))
-              bound = true;
-          }
-          for (size_t dd = 0; dd < plan->distinct.size(); dd++)
-            if (plan->distinct[dd].scan_slot == (int)s) {
-              any_distinct = true;
-              all_hinted &= st->distinct[dd].has_hint;
-            }
-          if (!bound && any_distinct && all_hinted) continue;
-        }
-        ScanColDesc d;
-        fill_scan_desc(c, plan->scan[s].variance, st->d_pivots.as<double>() + s, &d);
-        if (hll_on_col[plan->scan[s].column] >= 0 && !plan->scan[s].variance) {
-          d.skip_stats = plan->scan[s].stats_needed ? 0 : 1;
-          d.hll_regs = st->d_hll.as<uint8_t>() + (size_t)hll_on_col[plan->scan[s].column] * kHllRegisters;
-          hll_descs.push_back(d);
-          hll_index.push_back((int32_t)s);
-          hll_on_col[plan->scan[s].column] = -2;  // taken
-          continue;
-        }
-        if (kll_on_col[plan->scan[s].column] >= 0) {
-          kll_descs.push_back(d);
-          kll_index.push_back((int32_t)s);
-          kll_slots.push_back(kll_on_col[plan->scan[s].column]);
-        } else {
-          descs.push_back(d);
-          index.push_back((int32_t)s);
-        }
-      }
-      // sampled columns without a scan task of their own (a KLL check alone): scanned all the same, their column
-      // aggregates are dropped (acc_index -1)
-      for (size_t q = 0; q < plan->kll.size(); q++) {
-        const int col = plan->kll[q].column;
-        if (!kll_fused[q] || pair_of_col[col] >= 0 || scan_slot_of(col) >= 0) continue;
-        ScanColDesc d;
-        fill_scan_desc(dev[col], false, nullptr, &d);
-        kll_descs.push_back(d);
-        kll_index.push_back(-1);
-        kll_slots.push_back((int)q);
-      }
-      // launches of <= kMaxColsPerLaunch columns; descriptors travel in the kernel arguments
-      for (size_t c0 = 0; c0 < descs.size(); c0 += kMaxColsPerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxColsPerLaunch, descs.size() - c0);
-        ScanLaunch L;
-        memset(&L, 0, sizeof(L));
-        int blocks = 1;
-        uint64_t chunk_bytes = 0;
-        bool chunk_var = false;
-        for (int k = 0; k < n; k++) {
-          L.cols[k] = descs[c0 + k];
-          L.acc_index[k] = index[c0 + k];
-          blocks = std::max(blocks, scan_blocks_for(L.cols[k], n, scan_per_cu));
-          chunk_bytes += (uint64_t)L.cols[k].length * (L.cols[k].elem32 ? 4 : 8) +
-                         (L.cols[k].validity ? (uint64_t)(L.cols[k].length + 7) / 8 : 0);
-          chunk_var |= L.cols[k].want_variance != 0;
-        }
-        HIP_TRY(st->d_scan_partials.reserve((size_t)n * blocks * sizeof(ScanPartial)));
-        if (chunk_var) launch_scan_pivot(L, n, st->d_pivots.as<double>(), st->d_pivot_set.as<int32_t>(), st->stream);
-        {
-          ProfScope ps(st, "scan", chunk_bytes);
-          launch_scan_main_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
-                                st->stream);
-        }
-        if (blocks > 1)  // one workgroup per column folds into the running state itself (small batches: one launch)
-          launch_scan_reduce_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
-                                  st->stream);
-      }
-      // columns whose KLL samplers ride on the scan: columns of one launch share the sampling level (same rows)
-      for (size_t c0 = 0; c0 < kll_descs.size(); c0 += kMaxColsPerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxColsPerLaunch, kll_descs.size() - c0);
-        ScanLaunch L;
-        memset(&L, 0, sizeof(L));
-        int blocks = 1;
-        uint64_t chunk_bytes = 0;
-        bool chunk_var = false;
-        for (int k = 0; k < n; k++) {
-          L.cols[k] = kll_descs[c0 + k];
-          L.acc_index[k] = kll_index[c0 + k];
-          blocks = std::max(blocks, fused_blocks(L.cols[k], n));
-          chunk_bytes += (uint64_t)L.cols[k].length * 8 + (L.cols[k].validity ? (uint64_t)(L.cols[k].length + 7) / 8 : 0);
-          chunk_var |= L.cols[k].want_variance != 0;
-        }
-        size_t lds = 0;
-        for (int k = 0; k < n; k++) {
-          TGX_TRY(kll_scan_prepare(st, (size_t)kll_slots[c0 + k], nrows, blocks * kWavesPerBlock,
-                                   rows_per_wave(L.cols[k], blocks), &L.cols[k].kll, err));
-          lds = std::max(lds, (size_t)kWavesPerBlock * (((size_t)1 << L.cols[k].kll.top) + kTileRows) * sizeof(double));
-        }
-        HIP_TRY(st->d_scan_partials.reserve((size_t)n * blocks * sizeof(ScanPartial)));
-        if (chunk_var) launch_scan_pivot(L, n, st->d_pivots.as<double>(), st->d_pivot_set.as<int32_t>(), st->stream);
-        {
-          ProfScope ps(st, "scan", chunk_bytes);
-          launch_scan_kll(L, n, blocks, lds, st->d_scan_partials.as<ScanPartial>(), st->stream);
-        }
-        launch_scan_reduce_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
-                                st->stream);
-      }
-      // columns with the HyperLogLog lane on (APPROX_DISTINCT)
-      for (size_t c0 = 0; c0 < hll_descs.size(); c0 += kMaxColsPerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxColsPerLaunch, hll_descs.size() - c0);
-        ScanLaunch L;
-        memset(&L, 0, sizeof(L));
-        int blocks = 1;
-        uint64_t chunk_bytes = 0;
-        for (int k = 0; k < n; k++) {
-          L.cols[k] = hll_descs[c0 + k];
-          L.acc_index[k] = hll_index[c0 + k];
-          blocks = std::max(blocks, scan_blocks_for(L.cols[k], n));
-          chunk_bytes += (uint64_t)L.cols[k].length * (L.cols[k].elem32 ? 4 : 8) +
-                         (L.cols[k].validity ? (uint64_t)(L.cols[k].length + 7) / 8 : 0);
-        }
-        HIP_TRY(st->d_scan_partials.reserve((size_t)n * blocks * sizeof(ScanPartial)));
-        HIP_TRY(st->d_hll_rows.reserve((size_t)n * blocks * kHllRegisters));
-        for (int k = 0; k < n; k++) L.cols[k].hll = st->d_hll_rows.as<uint8_t>() + (size_t)k * blocks * kHllRegisters;
-        {
-          ProfScope ps(st, "scan", chunk_bytes), ps_hll(st, "scan_hll", chunk_bytes);
-          launch_scan_hll(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->stream);
-        }
-        launch_scan_reduce_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
-                                st->stream);
-      }
-      // COMOMENTS pairs: both columns and their co-moments from one read
-      if (!fused_pairs.empty()) {
-        const int n = (int)fused_pairs.size();
-        // grouped by (x type, y type): one launch of the kernel instance of each combination (kernels/scan.hip)
-        std::stable_sort(fused_pairs.begin(), fused_pairs.end(), [](const FusedPair &a, const FusedPair &b) {
-          return 2 * a.dx.is_float + a.dy.is_float > 2 * b.dx.is_float + b.dy.is_float;
-        });
-        ScanPairLaunch PL;
-        ScanLaunch RL;  // the same columns as the reduce kernel wants them: [2 k] = x, [2 k + 1] = y
-        ComomentLaunch CL;
-        memset(&PL, 0, sizeof(PL));
-        memset(&RL, 0, sizeof(RL));
-        memset(&CL, 0, sizeof(CL));
-        int blocks = 1;
-        uint64_t chunk_bytes = 0;
-        for (int k = 0; k < n; k++) blocks = std::max(blocks, fused_blocks(fused_pairs[k].dx, n));
-        size_t lds = 0;
-        for (int k = 0; k < n; k++) {
-          FusedPair &fp = fused_pairs[k];
-          ScanPairDesc &P = PL.pairs[k];
-          P.x = fp.dx;
-          P.y = fp.dy;
-          P.x_acc = scan_slot_of(fp.x);
-          P.y_acc = scan_slot_of(fp.y);
-          P.como_acc = fp.como;
-          size_t rings = 0;
-          for (int side = 0; side < 2; side++) {
-            ScanColDesc &d = side ? P.y : P.x;
-            const int col = side ? fp.y : fp.x;
-            if (kll_on_col[col] >= 0) {
-              TGX_TRY(kll_scan_prepare(st, (size_t)kll_on_col[col], nrows, blocks * kWavesPerBlock,
-                                       rows_per_wave(d, blocks), &d.kll, err));
-              rings += ((size_t)1 << d.kll.top) + kTileRows;
-            }
-            chunk_bytes += (uint64_t)d.length * 8 + (d.validity ? (uint64_t)(d.length + 7) / 8 : 0);
-          }
-          lds = std::max(lds, (size_t)kWavesPerBlock * rings * sizeof(double));
-          RL.cols[2 * k] = P.x;
-          RL.cols[2 * k + 1] = P.y;
-          RL.acc_index[2 * k] = P.x_acc;
-          RL.acc_index[2 * k + 1] = P.y_acc;
-          const tgx_column &xc = dev[fp.x], &yc = dev[fp.y];
-          CL.pairs[k].x = xc.values;
-          CL.pairs[k].y = yc.values;
-          CL.pairs[k].xv = xc.validity;
-          CL.pairs[k].yv = yc.validity;
-          CL.pairs[k].xoff = xc.offset;
-          CL.pairs[k].yoff = yc.offset;
-          CL.pairs[k].length = P.x.length;
-          CL.pairs[k].x_is_float = xc.type == TGX_FLOAT64;
-          CL.pairs[k].y_is_float = yc.type == TGX_FLOAT64;
-          CL.acc_index[k] = fp.como;
-        }
-        TGX_TRY(como_pivots(st, CL, n, err));
-        HIP_TRY(st->d_scan_partials.reserve((size_t)2 * n * blocks * sizeof(ScanPartial)));
-        HIP_TRY(st->d_como_partials.reserve((size_t)n * blocks * comoments_partial_bytes()));
-        {
-          ProfScope ps(st, "scan", chunk_bytes);
-          launch_scan_pairs(PL, n, blocks, lds, st->d_scan_partials.as<ScanPartial>(), st->d_como_partials.p,
-                            st->d_como_acc.as<ComomentAcc>(), st->stream);
-        }
-        launch_scan_reduce_only(RL, 2 * n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
-                                st->stream);
-        launch_comoments_reduce(CL, n, blocks, st->d_como_partials.p, st->d_como_acc.as<ComomentAcc>(), st->stream);
-      }
-    }
-    // ---- validity-only columns ----
-    {
-      std::vector<CountColDesc> descs;
-      std::vector<int32_t> index;
-      uint64_t bytes = 0;
-      int64_t max_words = 0;
-      for (size_t s = 0; s < plan->count.size(); s++) {
-        const tgx_column &c = dev[plan->count[s].column];
-        if (c.type == TGX_DICT32_UTF8 && c.dictionary->validity && c.dictionary->length > 0) {
-          // a row whose dictionary VALUE is NULL is a NULL row (Arrow's logical nulls): count through the indices
-          launch_dict_count((const int32_t *)c.values, c.validity, c.offset, c.length, c.dictionary->validity,
-                            c.dictionary->offset, c.dictionary->length, st->d_count_acc.as<CountAcc>() + s, g_ctx.n_cu,
-                            st->stream);
-          continue;
-        }
-        if (!c.validity) {  // no validity buffer: COUNT(col) = COUNT(*) = length, no kernel needed
-          st->h_count[s].total += c.length;
-          st->h_count[s].non_null += c.length;
-          continue;
-        }
-        descs.push_back({c.validity, c.offset, c.length});
-        index.push_back((int32_t)s);
-        bytes += (uint64_t)(c.length + 7) / 8;
-        max_words = std::max<int64_t>(max_words, (c.length + 63) / 64 + 1);
-      }
-      for (size_t c0 = 0; c0 < descs.size(); c0 += kMaxColsPerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxColsPerLaunch, descs.size() - c0);
-        CountLaunch L;
-        memset(&L, 0, sizeof(L));
-        uint64_t chunk_bytes = 0;
-        for (int k = 0; k < n; k++) {
-          L.cols[k] = descs[c0 + k];
-          L.acc_index[k] = index[c0 + k];
-          chunk_bytes += (uint64_t)(L.cols[k].length + 7) / 8;
-        }
-        int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (max_words + 256 * 4 - 1) / (256 * 4)),
-                                            std::max(8, (g_ctx.n_cu * 8) / n));
-        HIP_TRY(st->d_count_blocks.reserve((size_t)n * blocks * sizeof(unsigned long long)));
-        ProfScope ps(st, "count", chunk_bytes);
-        launch_count(L, n, blocks, st->d_count_blocks.as<unsigned long long>(), st->d_count_acc.as<CountAcc>(), st->stream);
-      }
-      (void)bytes;
-    }
-    // ---- co-moments ----
-    if (!plan->como.empty()) {
-      std::vector<ComomentColDesc> descs;
-      std::vector<int32_t> index;
-      uint64_t bytes = 0;
-      for (size_t s = 0; s < plan->como.size(); s++) {
-        if (como_fused[s]) continue;  // rode on the scan of its columns
-        const tgx_column &x = dev[plan->como[s].col_x], &y = dev[plan->como[s].col_y];
-        if (!is_numeric(x.type) || !is_numeric(y.type))
-          return fail(err, TGX_INVALID_ARGUMENT, "COMOMENTS needs numeric columns (%d, %d)", x.type, y.type);
-        ComomentColDesc d;
-        d.x = x.values;
-        d.y = y.values;
-        d.xv = x.validity;
-        d.yv = y.validity;
-        d.xoff = x.offset;
-        d.yoff = y.offset;
-        d.length = x.length;
-        d.x_is_float = x.type == TGX_FLOAT64;
-        d.y_is_float = y.type == TGX_FLOAT64;
-        descs.push_back(d);
-        index.push_back((int32_t)s);
-        bytes += (uint64_t)x.length * 16 + (x.validity ? (uint64_t)(x.length + 7) / 8 : 0) +
-                 (y.validity ? (uint64_t)(y.length + 7) / 8 : 0);
-      }
-      for (size_t c0 = 0; c0 < descs.size(); c0 += kMaxColsPerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxColsPerLaunch, descs.size() - c0);
-        ComomentLaunch L;
-        memset(&L, 0, sizeof(L));
-        for (int k = 0; k < n; k++) {
-          L.pairs[k] = descs[c0 + k];
-          L.acc_index[k] = index[c0 + k];
-        }
-        int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nrows + 256 * 16 - 1) / (256 * 16)),
-                                            std::max(32, (g_ctx.n_cu * 12) / n));  // 4/5/6/8/12 per CU: 6.8/6.4/6.2/6.5/6.0 ms (2 pairs, 1 G rows)
-        HIP_TRY(st->d_como_partials.reserve((size_t)n * blocks * comoments_partial_bytes()));
-        TGX_TRY(como_pivots(st, L, n, err));
-        ProfScope ps(st, "comoments", bytes * n / std::max<size_t>(descs.size(), 1));
-        launch_comoments(L, n, blocks, st->d_como_partials.p, st->d_como_acc.as<ComomentAcc>(), st->stream);
-      }
-    }
-    // (the key passes that ran beside the scan: whatever follows on the state's stream sees them done)
-    if (beside) HIP_TRY(hipStreamWaitEvent(st->stream, st->keys_ready, 0));
-    // ---- exact distinct ----
-    // dictionary columns with a DISTINCT check and pattern / length checks: the patterns are matched on the
-    // dictionary ENTRIES first (regex_update), their per-row gathers then ride on the DISTINCT pass
-    DictFuse fuse;
-    for (size_t s = 0; s < plan->distinct.size(); s++) {
-      const DistinctTask &t = plan->distinct[s];
-      if (!t.tuple.empty()) continue;
-      const tgx_column &c = dev[t.column];
-      if (c.type != TGX_DICT32_UTF8 || c.length == 0 || c.dictionary->length == 0 || c.dictionary->validity) continue;
-      if (dict_usage_scratch_bytes(c.length, c.dictionary->length, t.multiplicity ? 1 : 0, g_ctx.n_cu) == 0) continue;
-      const int cap = dict_fuse_capacity(c.length, c.dictionary->length, t.multiplicity ? 1 : 0, g_ctx.n_cu);
-      if (cap > 0 && !fuse.capacity.count(t.column)) fuse.capacity[t.column] = cap;
-    }
-    TGX_TRY(regex_update(st, dev.data(), err, &fuse));
-    std::map<int, bool> fuse_done;
-    for (size_t s = 0; s < plan->distinct.size(); s++)
-      if (distinct_idle(s) || distinct_done[s]) {
-        continue;
-      } else if (plan->distinct[s].tuple.empty()) {
-        const int col = plan->distinct[s].column;
-        const std::vector<DictGather> *g = nullptr;
-        auto it = fuse.by_column.find(col);
-        if (it != fuse.by_column.end() && !fuse_done[col]) {
-          g = &it->second;
-          fuse_done[col] = true;
-        }
-        const int stats_slot = (plan->distinct[s].scan_slot >= 0 && stats_by_partition[plan->distinct[s].scan_slot] == (int)s)
-                                   ? plan->distinct[s].scan_slot
-                                   : -1;
-        TGX_TRY(distinct_update(st, s, dev[col], err, g, &dprep[s], stats_slot, &columns[col]));
-      } else {
-        TGX_TRY(distinct_tuple_update(st, s, dev.data(), err, columns));
-      }
-    // (gathers handed out but not consumed -- cannot happen: every fusable column has exactly one DISTINCT task)
-    // ---- KLL ----
-    TGX_TRY(kll_scan_finish(st, err));  // sketches the picks the scan left for the tasks that rode on it
-    for (size_t s = 0; s < plan->kll.size(); s++)
-      if (!kll_fused[s]) TGX_TRY(kll_update(st, s, dev[plan->kll[s].column], err));
-    // ---- Spearman: keep the pairs, rank at finalize ----
-    TGX_TRY(spearman_update(st, dev.data(), columns, !st->coalesce.flushing && !g_ctx.no_coalesce, err));
   }
+  auto has_hll = [&](int col) { return f.hll_on_col[col] >= 0; };  // its own scan launch: fuses with nothing else
+  if (nrows >= (1 << 20)) {
+    for (size_t q = 0; q < plan->kll.size(); q++) {
+      const int col = plan->kll[q].column;
+      if (plain8(col) && !has_hll(col) && f.kll_on_col[col] < 0 && kll_scan_eligible(nrows)) {
+        f.kll_on_col[col] = (int)q;
+        f.kll_fused[q] = 1;
+      }
+    }
+    for (size_t q = 0; q < plan->como.size() && f.fused_pairs.size() < (size_t)kMaxPairsPerLaunch; q++) {
+      const int x = plan->como[q].col_x, y = plan->como[q].col_y;
+      if (x == y || !plain8(x) || !plain8(y) || f.pair_of_col[x] >= 0 || f.pair_of_col[y] >= 0) continue;
+      if (has_hll(x) || has_hll(y)) continue;
+      const int sx = scan_slot_of(plan, x), sy = scan_slot_of(plan, y);
+      if ((sx >= 0 && plan->scan[sx].variance) || (sy >= 0 && plan->scan[sy].variance)) continue;
+      FusedPair fp;
+      fp.como = (int)q;
+      fp.x = x;
+      fp.y = y;
+      fill_scan_desc(dev[x], false, nullptr, &fp.dx);
+      fill_scan_desc(dev[y], false, nullptr, &fp.dy);
+      if (fp.dx.head != fp.dy.head || fp.dx.n_tiles != fp.dy.n_tiles) continue;  // tiles must line up
+      f.pair_of_col[x] = f.pair_of_col[y] = (int)f.fused_pairs.size();
+      f.como_fused[q] = 1;
+      f.fused_pairs.push_back(fp);
+    }
+  }
+  return f;
+}
+
+// The key columns' uniqueness passes go FIRST (numeric keys: everything they need is decided) and an event marks
+// their end: across ranks the exchange of the key sets (tgx_allreduce) can then run on a second stream while the scan
+// of the other columns is still running (the >= 6x target is set by the exchange).
+//
+// Exact uniqueness over dense Int64 keys takes the column's range aggregates along (kernels/distinct.hip,
+// partition_kernel<.., STATS>): such a column is not scanned at all -- it crosses HBM once for MIN / MAX / SUM / COUNT
+// and COUNT(DISTINCT) together.  Decided here, before the scan is queued, from a sample of the batch.
+tgx_status early_key_passes(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, const tgx_column *columns,
+                            BatchFusion *f, tgx_error *err) {
+  update_mark("fused");
+  TGX_TRY(distinct_sample_all(st, dev, err));
+  update_mark("sampled");
+  auto numeric_pass = [&](size_t q) {
+    const DistinctTask &t = plan->distinct[q];
+    return t.tuple.empty() && !f->distinct_idle[q] && is_numeric(dev[t.column].type) && dev[t.column].length > 0;
+  };
+  for (size_t q = 0; q < plan->distinct.size(); q++) {
+    const DistinctTask &t = plan->distinct[q];
+    if (!numeric_pass(q)) continue;
+    TGX_TRY(distinct_prepare_numeric(st, q, dev[t.column], &f->dprep[q], err));
+    if (f->dprep[q].partitioned && dev[t.column].type == TGX_INT64 && t.scan_slot >= 0 &&
+        !plan->scan[t.scan_slot].variance && f->pair_of_col[t.column] < 0 && f->kll_on_col[t.column] < 0)
+      f->stats_by_partition[t.scan_slot] = (int)q;
+  }
+  update_mark("prepared");
+  for (size_t q = 0; q < plan->distinct.size(); q++) {
+    const DistinctTask &t = plan->distinct[q];
+    if (!numeric_pass(q)) continue;
+    TGX_TRY(distinct_update(st, q, dev[t.column], err, nullptr, &f->dprep[q], f->stats_slot(plan, q),
+                            &columns[t.column]));
+    f->distinct_done[q] = 1;
+  }
+  update_mark("keys_queued");
+  if (!st->keys_ready) HIP_TRY(hipEventCreateWithFlags(&st->keys_ready, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(st->keys_ready, st->stream));
+  update_mark("event");
+  // (the event stands for the key sets only when every key set of the plan was touched before it: string,
+  //  dictionary and tuple sets are updated further down, behind the scan)
+  bool all_early = true;
+  for (size_t q = 0; q < plan->distinct.size(); q++) all_early &= f->distinct_done[q] || f->distinct_idle[q];
+  // ... and for the running MIN / MAX the facts round reads (allreduce.cpp tightens a bitmap's range with them) only
+  // when they, too, were produced before it: a key column whose aggregates come from the scan below -- a pass that is
+  // not partitioned, variance / pair / KLL / HLL lanes on the key column -- would have its ScanAcc read on the second
+  // stream while the scan is still writing it
+  for (size_t q = 0; q < plan->distinct.size(); q++) {
+    const DistinctTask &t = plan->distinct[q];
+    if (!f->distinct_done[q] || t.scan_slot < 0 || st->distinct[q].has_hint) continue;
+    all_early &= f->stats_by_partition[t.scan_slot] == (int)q;
+  }
+  st->keys_ready_recorded = all_early && (st->passes == 0 || st->keys_ready_recorded);
+  st->passes++;
+  return TGX_OK;
+}
+
+// The columns of one scan launch flavour: the plain scan, the scan with KLL samplers, the scan with the HLL lane
+enum class ScanLane { kPlain, kKll, kHll };
+struct LaneColumns {
+  std::vector<ScanColDesc> descs;
+  std::vector<int32_t> acc_index;  // running-state slot of each column (-1: its aggregates are dropped)
+  std::vector<int> kll_slots;      // kKll: the KLL task of each column
+  void add(const ScanColDesc &d, int32_t acc, int kll = -1) {
+    descs.push_back(d);
+    acc_index.push_back(acc);
+    if (kll >= 0) kll_slots.push_back(kll);
+  }
+};
+
+// launches of <= kMaxColsPerLaunch columns of one lane; descriptors travel in the kernel arguments
+tgx_status launch_scan_lane(tgx_state *st, ScanLane lane, const LaneColumns &cols, int64_t nrows, int scan_per_cu,
+                            tgx_error *err) {
+  for (size_t c0 = 0; c0 < cols.descs.size(); c0 += kMaxColsPerLaunch) {
+    const int n = (int)std::min<size_t>(kMaxColsPerLaunch, cols.descs.size() - c0);
+    ScanLaunch L;
+    memset(&L, 0, sizeof(L));
+    int blocks = 1;
+    uint64_t chunk_bytes = 0;
+    bool chunk_var = false;  // (never with the HLL lane: it takes no variance lanes)
+    for (int k = 0; k < n; k++) {
+      L.cols[k] = cols.descs[c0 + k];
+      L.acc_index[k] = cols.acc_index[c0 + k];
+      // (the HLL lane at the default 8 workgroups per CU, exchange or not)
+      const int want = lane == ScanLane::kKll    ? fused_blocks(L.cols[k], n)
+                       : lane == ScanLane::kHll ? scan_blocks_for(L.cols[k], n)
+                                                : scan_blocks_for(L.cols[k], n, scan_per_cu);
+      blocks = std::max(blocks, want);
+      chunk_bytes += (uint64_t)L.cols[k].length * (L.cols[k].elem32 ? 4 : 8) +
+                     (L.cols[k].validity ? (uint64_t)(L.cols[k].length + 7) / 8 : 0);
+      chunk_var |= L.cols[k].want_variance != 0;
+    }
+    // columns whose KLL samplers ride on the scan: columns of one launch share the sampling level (same rows)
+    size_t lds = 0;
+    if (lane == ScanLane::kKll)
+      for (int k = 0; k < n; k++) {
+        TGX_TRY(kll_scan_prepare(st, (size_t)cols.kll_slots[c0 + k], nrows, blocks * kWavesPerBlock,
+                                 rows_per_wave(L.cols[k], blocks), &L.cols[k].kll, err));
+        lds = std::max(lds, (size_t)kWavesPerBlock * (((size_t)1 << L.cols[k].kll.top) + kTileRows) * sizeof(double));
+      }
+    HIP_TRY(st->d_scan_partials.reserve((size_t)n * blocks * sizeof(ScanPartial)));
+    if (lane == ScanLane::kHll) {
+      HIP_TRY(st->d_hll_rows.reserve((size_t)n * blocks * kHllRegisters));
+      for (int k = 0; k < n; k++) L.cols[k].hll = st->d_hll_rows.as<uint8_t>() + (size_t)k * blocks * kHllRegisters;
+    }
+    if (chunk_var) launch_scan_pivot(L, n, st->d_pivots.as<double>(), st->d_pivot_set.as<int32_t>(), st->stream);
+    {
+      ProfScope ps(st, "scan", chunk_bytes);
+      if (lane == ScanLane::kPlain) {
+        launch_scan_main_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
+                              st->stream);
+      } else if (lane == ScanLane::kKll) {
+        launch_scan_kll(L, n, blocks, lds, st->d_scan_partials.as<ScanPartial>(), st->stream);
+      } else {
+        ProfScope ps_hll(st, "scan_hll", chunk_bytes);
+        launch_scan_hll(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->stream);
+      }
+    }
+    // (the plain scan's single workgroup per column folds into the running state itself: small batches, one launch)
+    if (lane != ScanLane::kPlain || blocks > 1)
+      launch_scan_reduce_only(L, n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
+                              st->stream);
+  }
+  return TGX_OK;
+}
+
+ComomentColDesc como_desc(const tgx_column &x, const tgx_column &y) {
+  ComomentColDesc d;
+  d.x = x.values;
+  d.y = y.values;
+  d.xv = x.validity;
+  d.yv = y.validity;
+  d.xoff = x.offset;
+  d.yoff = y.offset;
+  d.length = x.length;
+  d.x_is_float = x.type == TGX_FLOAT64;
+  d.y_is_float = y.type == TGX_FLOAT64;
+  return d;
+}
+
+// COMOMENTS pairs: both columns and their co-moments from one read
+tgx_status launch_fused_pairs(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows,
+                              const BatchFusion &f, tgx_error *err) {
+  std::vector<FusedPair> pairs = f.fused_pairs;
+  const int n = (int)pairs.size();
+  // grouped by (x type, y type): one launch of the kernel instance of each combination (kernels/scan.hip)
+  std::stable_sort(pairs.begin(), pairs.end(), [](const FusedPair &a, const FusedPair &b) {
+    return 2 * a.dx.is_float + a.dy.is_float > 2 * b.dx.is_float + b.dy.is_float;
+  });
+  ScanPairLaunch PL;
+  ScanLaunch RL;  // the same columns as the reduce kernel wants them: [2 k] = x, [2 k + 1] = y
+  ComomentLaunch CL;
+  memset(&PL, 0, sizeof(PL));
+  memset(&RL, 0, sizeof(RL));
+  memset(&CL, 0, sizeof(CL));
+  int blocks = 1;
+  uint64_t chunk_bytes = 0;
+  for (int k = 0; k < n; k++) blocks = std::max(blocks, fused_blocks(pairs[k].dx, n));
+  size_t lds = 0;
+  for (int k = 0; k < n; k++) {
+    FusedPair &fp = pairs[k];
+    ScanPairDesc &P = PL.pairs[k];
+    P.x = fp.dx;
+    P.y = fp.dy;
+    P.x_acc = scan_slot_of(plan, fp.x);
+    P.y_acc = scan_slot_of(plan, fp.y);
+    P.como_acc = fp.como;
+    size_t rings = 0;
+    for (int side = 0; side < 2; side++) {
+      ScanColDesc &d = side ? P.y : P.x;
+      const int col = side ? fp.y : fp.x;
+      if (f.kll_on_col[col] >= 0) {
+        TGX_TRY(kll_scan_prepare(st, (size_t)f.kll_on_col[col], nrows, blocks * kWavesPerBlock,
+                                 rows_per_wave(d, blocks), &d.kll, err));
+        rings += ((size_t)1 << d.kll.top) + kTileRows;
+      }
+      chunk_bytes += (uint64_t)d.length * 8 + (d.validity ? (uint64_t)(d.length + 7) / 8 : 0);
+    }
+    lds = std::max(lds, (size_t)kWavesPerBlock * rings * sizeof(double));
+    RL.cols[2 * k] = P.x;
+    RL.cols[2 * k + 1] = P.y;
+    RL.acc_index[2 * k] = P.x_acc;
+    RL.acc_index[2 * k + 1] = P.y_acc;
+    CL.pairs[k] = como_desc(dev[fp.x], dev[fp.y]);
+    CL.acc_index[k] = fp.como;
+  }
+  TGX_TRY(como_pivots(st, CL, n, err));
+  HIP_TRY(st->d_scan_partials.reserve((size_t)2 * n * blocks * sizeof(ScanPartial)));
+  HIP_TRY(st->d_como_partials.reserve((size_t)n * blocks * comoments_partial_bytes()));
+  {
+    ProfScope ps(st, "scan", chunk_bytes);
+    launch_scan_pairs(PL, n, blocks, lds, st->d_scan_partials.as<ScanPartial>(), st->d_como_partials.p,
+                      st->d_como_acc.as<ComomentAcc>(), st->stream);
+  }
+  launch_scan_reduce_only(RL, 2 * n, blocks, st->d_scan_partials.as<ScanPartial>(), st->d_scan_acc.as<ScanAcc>(),
+                          st->stream);
+  launch_comoments_reduce(CL, n, blocks, st->d_como_partials.p, st->d_como_acc.as<ComomentAcc>(), st->stream);
+  return TGX_OK;
+}
+
+// numeric scan: every column whose aggregates no other pass brings, in launches of <= kMaxColsPerLaunch columns
+tgx_status scan_columns(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows,
+                        const BatchFusion &f, tgx_error *err) {
+  // (a state that takes part in exchanges leaves two workgroup slots per CU to the second stream's kernels: the
+  //  scan is HBM-bound from 4 workgroups per CU upwards)
+  const int scan_per_cu = st->exchange_expected ? 6 : 8;
+  LaneColumns plain, kll, hll;
+  for (size_t s = 0; s < plan->scan.size(); s++) {
+    const ScanTask &t = plan->scan[s];
+    const tgx_column &c = dev[t.column];
+    if (!is_numeric(c.type) && !is_numeric32(c.type)) {
+      // a scan task that only exists for DISTINCT's range decision does not apply to strings
+      if (t.stats_spec)
+        return fail(err, TGX_INVALID_ARGUMENT, "NUMERIC_STATS on non-numeric column %d (type %d)", t.column, c.type);
+      continue;
+    }
+    if (f.pair_of_col[t.column] >= 0) continue;  // scanned with its partner below
+    if (f.stats_by_partition[s] >= 0) continue;  // its DISTINCT pass brings the aggregates
+    if (f.kll_on_col[t.column] < 0 && f.hll_on_col[t.column] < 0 && !t.read_by_spec) {
+      // a scan that only feeds DISTINCT's range decision is not needed once the range is declared
+      bool all_hinted = true, any_distinct = false;
+      for (size_t dd = 0; dd < plan->distinct.size(); dd++)
+        if (plan->distinct[dd].scan_slot == (int)s) {
+          any_distinct = true;
+          all_hinted &= st->distinct[dd].has_hint;
+        }
+      if (any_distinct && all_hinted) continue;
+    }
+    ScanColDesc d;
+    fill_scan_desc(c, t.variance, st->d_pivots.as<double>() + s, &d);
+    if (f.hll_on_col[t.column] >= 0 && !t.variance) {
+      d.skip_stats = t.stats_needed ? 0 : 1;
+      d.hll_regs = st->d_hll.as<uint8_t>() + (size_t)f.hll_on_col[t.column] * kHllRegisters;
+      hll.add(d, (int32_t)s);
+    } else if (f.kll_on_col[t.column] >= 0) {
+      kll.add(d, (int32_t)s, f.kll_on_col[t.column]);
+    } else {
+      plain.add(d, (int32_t)s);
+    }
+  }
+  // sampled columns without a scan task of their own (a KLL check alone): scanned all the same, their column
+  // aggregates are dropped (acc_index -1)
+  for (size_t q = 0; q < plan->kll.size(); q++) {
+    const int col = plan->kll[q].column;
+    if (!f.kll_fused[q] || f.pair_of_col[col] >= 0 || scan_slot_of(plan, col) >= 0) continue;
+    ScanColDesc d;
+    fill_scan_desc(dev[col], false, nullptr, &d);
+    kll.add(d, -1, (int)q);
+  }
+  TGX_TRY(launch_scan_lane(st, ScanLane::kPlain, plain, nrows, scan_per_cu, err));
+  TGX_TRY(launch_scan_lane(st, ScanLane::kKll, kll, nrows, scan_per_cu, err));
+  TGX_TRY(launch_scan_lane(st, ScanLane::kHll, hll, nrows, scan_per_cu, err));
+  if (!f.fused_pairs.empty()) TGX_TRY(launch_fused_pairs(plan, st, dev, nrows, f, err));
+  return TGX_OK;
+}
+
+// validity-only columns
+tgx_status count_validity(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, tgx_error *err) {
+  std::vector<CountColDesc> descs;
+  std::vector<int32_t> index;
+  int64_t max_words = 0;
+  for (size_t s = 0; s < plan->count.size(); s++) {
+    const tgx_column &c = dev[plan->count[s].column];
+    if (c.type == TGX_DICT32_UTF8 && c.dictionary->validity && c.dictionary->length > 0) {
+      // a row whose dictionary VALUE is NULL is a NULL row (Arrow's logical nulls): count through the indices
+      launch_dict_count((const int32_t *)c.values, c.validity, c.offset, c.length, c.dictionary->validity,
+                        c.dictionary->offset, c.dictionary->length, st->d_count_acc.as<CountAcc>() + s, g_ctx.n_cu,
+                        st->stream);
+      continue;
+    }
+    if (!c.validity) {  // no validity buffer: COUNT(col) = COUNT(*) = length, no kernel needed
+      st->h_count[s].total += c.length;
+      st->h_count[s].non_null += c.length;
+      continue;
+    }
+    descs.push_back({c.validity, c.offset, c.length});
+    index.push_back((int32_t)s);
+    max_words = std::max<int64_t>(max_words, (c.length + 63) / 64 + 1);
+  }
+  for (size_t c0 = 0; c0 < descs.size(); c0 += kMaxColsPerLaunch) {
+    const int n = (int)std::min<size_t>(kMaxColsPerLaunch, descs.size() - c0);
+    CountLaunch L;
+    memset(&L, 0, sizeof(L));
+    uint64_t chunk_bytes = 0;
+    for (int k = 0; k < n; k++) {
+      L.cols[k] = descs[c0 + k];
+      L.acc_index[k] = index[c0 + k];
+      chunk_bytes += (uint64_t)(L.cols[k].length + 7) / 8;
+    }
+    int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (max_words + 256 * 4 - 1) / (256 * 4)),
+                                        std::max(8, (g_ctx.n_cu * 8) / n));
+    HIP_TRY(st->d_count_blocks.reserve((size_t)n * blocks * sizeof(unsigned long long)));
+    ProfScope ps(st, "count", chunk_bytes);
+    launch_count(L, n, blocks, st->d_count_blocks.as<unsigned long long>(), st->d_count_acc.as<CountAcc>(), st->stream);
+  }
+  return TGX_OK;
+}
+
+// co-moments of the pairs that did not ride on the scan
+tgx_status unfused_comoments(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows,
+                             const BatchFusion &f, tgx_error *err) {
+  std::vector<ComomentColDesc> descs;
+  std::vector<int32_t> index;
+  uint64_t bytes = 0;
+  for (size_t s = 0; s < plan->como.size(); s++) {
+    if (f.como_fused[s]) continue;  // rode on the scan of its columns
+    const tgx_column &x = dev[plan->como[s].col_x], &y = dev[plan->como[s].col_y];
+    if (!is_numeric(x.type) || !is_numeric(y.type))
+      return fail(err, TGX_INVALID_ARGUMENT, "COMOMENTS needs numeric columns (%d, %d)", x.type, y.type);
+    descs.push_back(como_desc(x, y));
+    index.push_back((int32_t)s);
+    bytes += (uint64_t)x.length * 16 + (x.validity ? (uint64_t)(x.length + 7) / 8 : 0) +
+             (y.validity ? (uint64_t)(y.length + 7) / 8 : 0);
+  }
+  for (size_t c0 = 0; c0 < descs.size(); c0 += kMaxColsPerLaunch) {
+    const int n = (int)std::min<size_t>(kMaxColsPerLaunch, descs.size() - c0);
+    ComomentLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int k = 0; k < n; k++) {
+      L.pairs[k] = descs[c0 + k];
+      L.acc_index[k] = index[c0 + k];
+    }
+    int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nrows + 256 * 16 - 1) / (256 * 16)),
+                                        std::max(32, (g_ctx.n_cu * 12) / n));  // 4/5/6/8/12 per CU: 6.8/6.4/6.2/6.5/6.0 ms (2 pairs, 1 G rows)
+    HIP_TRY(st->d_como_partials.reserve((size_t)n * blocks * comoments_partial_bytes()));
+    TGX_TRY(como_pivots(st, L, n, err));
+    ProfScope ps(st, "comoments", bytes * n / std::max<size_t>(descs.size(), 1));
+    launch_comoments(L, n, blocks, st->d_como_partials.p, st->d_como_acc.as<ComomentAcc>(), st->stream);
+  }
+  return TGX_OK;
+}
+
+// the pattern / length checks and the key sets not updated before `keys_ready` (strings, dictionaries, tuples):
+// dictionary columns with a DISTINCT check and pattern / length checks have the patterns matched on the dictionary
+// ENTRIES first (regex_update), their per-row gathers then ride on the DISTINCT pass
+tgx_status late_key_sets(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, const tgx_column *columns,
+                         const BatchFusion &f, tgx_error *err) {
+  DictFuse fuse;
+  for (size_t s = 0; s < plan->distinct.size(); s++) {
+    const DistinctTask &t = plan->distinct[s];
+    if (!t.tuple.empty()) continue;
+    const tgx_column &c = dev[t.column];
+    if (c.type != TGX_DICT32_UTF8 || c.length == 0 || c.dictionary->length == 0 || c.dictionary->validity) continue;
+    if (dict_usage_scratch_bytes(c.length, c.dictionary->length, t.multiplicity ? 1 : 0, g_ctx.n_cu) == 0) continue;
+    const int cap = dict_fuse_capacity(c.length, c.dictionary->length, t.multiplicity ? 1 : 0, g_ctx.n_cu);
+    if (cap > 0 && !fuse.capacity.count(t.column)) fuse.capacity[t.column] = cap;
+  }
+  TGX_TRY(regex_update(st, dev, err, &fuse));
+  std::map<int, bool> fuse_done;
+  for (size_t s = 0; s < plan->distinct.size(); s++)
+    if (f.distinct_idle[s] || f.distinct_done[s]) {
+      continue;
+    } else if (plan->distinct[s].tuple.empty()) {
+      const int col = plan->distinct[s].column;
+      const std::vector<DictGather> *g = nullptr;
+      auto it = fuse.by_column.find(col);
+      if (it != fuse.by_column.end() && !fuse_done[col]) {
+        g = &it->second;
+        fuse_done[col] = true;
+      }
+      TGX_TRY(distinct_update(st, s, dev[col], err, g, &f.dprep[s], f.stats_slot(plan, s), &columns[col]));
+    } else {
+      TGX_TRY(distinct_tuple_update(st, s, dev, err, columns));
+    }
+  // (gathers handed out but not consumed -- cannot happen: every fusable column has exactly one DISTINCT task)
+  return TGX_OK;
+}
+
+// KLL sketches and Spearman's pairs (kept, ranked at finalize)
+tgx_status sketches(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, const tgx_column *columns,
+                    const BatchFusion &f, tgx_error *err) {
+  TGX_TRY(kll_scan_finish(st, err));  // sketches the picks the scan left for the tasks that rode on it
+  for (size_t s = 0; s < plan->kll.size(); s++)
+    if (!f.kll_fused[s]) TGX_TRY(kll_update(st, s, dev[plan->kll[s].column], err));
+  return spearman_update(st, dev, columns, !st->coalesce.flushing && !g_ctx.no_coalesce, err);
+}
+
+// the arena handed back, HOST memory borrowed from the caller released
+tgx_status finish_batch(tgx_state *st, const StagedBatch &b, tgx_error *err) {
   st->batches++;
-  if (arena_in_use) {
+  if (b.arena_in_use) {
     // the arena (and its device twin) are free again once everything this update queued has run
     HIP_TRY(hipEventRecord(st->arena_event[st->arena_cur], st->stream));
     st->arena_busy[st->arena_cur] = true;
@@ -923,10 +904,30 @@ tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *co
     st->arena_used = 0;
   }
   // HOST buffers copied straight from the caller's memory are borrowed only until tgx_update returns
-  if (any_host && st->host_direct) HIP_TRY(hipStreamSynchronize(st->stream));
+  if (b.any_host && st->host_direct) HIP_TRY(hipStreamSynchronize(st->stream));
   // a sampled-range key set keeps views of its batches for a later repair: staged copies of HOST batches do not
   // live that long
-  if (any_host) TGX_TRY(distinct_resolve_all(st, err));
+  if (b.any_host) TGX_TRY(distinct_resolve_all(st, err));
   return TGX_OK;
 }
 
+}  // namespace
+
+// one batch through the fused pass: device views of its columns, then every kernel of the plan
+tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, int64_t nrows,
+                       tgx_error *err) {
+  TGX_TRY(state_init_device(st, err));
+  StagedBatch b;
+  TGX_TRY(stage_batch(plan, st, columns, &b, err));
+  if (nrows > 0) {
+    const tgx_column *dev = b.dev.data();
+    BatchFusion f = decide_fusion(plan, st, dev, nrows);
+    TGX_TRY(early_key_passes(plan, st, dev, columns, &f, err));
+    TGX_TRY(scan_columns(plan, st, dev, nrows, f, err));
+    TGX_TRY(count_validity(plan, st, dev, err));
+    TGX_TRY(unfused_comoments(plan, st, dev, nrows, f, err));
+    TGX_TRY(late_key_sets(plan, st, dev, columns, f, err));
+    TGX_TRY(sketches(plan, st, dev, columns, f, err));
+  }
+  return finish_batch(st, b, err);
+}
