@@ -60,12 +60,32 @@ struct Context {
 };
 extern TGX_HIDDEN Context g_ctx;
 
+// What the host knows about one key column of the batch about to run: a coalesced flush counted and bounded its
+// windows as they were noted (coalesce_flush); a batch handed to tgx_update directly comes with nothing known
+struct BatchKeyFacts {
+  // an Int64 column's value range: the flush's HOST windows (the host saw every value on its way into the arena), or
+  // its DEVICE windows once the device has taken their MIN / MAX (distinct_sample_all)
+  bool range_known = false;
+  int64_t lo = 0, hi = 0;
+  // an Int64 column whose flush windows were DEVICE memory: the host has not seen its values, so -- while that can
+  // still keep the key set on the bitmap -- the device takes the flush's exact MIN / MAX before the pass (one wait,
+  // the one a sample would cost)
+  bool device_keys = false;
+  // a Utf8 column's value bytes, or a dictionary column's dictionary's (-1: not known)
+  int64_t data_bytes = -1;
+  // the batch's sample (distinct_sample_all reads the samples of all key columns at once)
+  bool sampled = false;
+  DistinctSample sample;
+};
+
 struct NumericPrep {
   bool prepared = false;
   bool partitioned = false;  // the batch goes through partition_kernel / bucket_apply_kernel
   uint32_t sub_bits = 0;
   bool key16 = false;
   uint64_t n_buckets = 0;
+  bool range_known = false;  // the batch's own value range (BatchKeyFacts): the buckets its keys can land in
+  int64_t lo = 0, hi = 0;
 };
 
 struct BatchTraits {
@@ -159,50 +179,22 @@ TGX_HIDDEN tgx_status como_pivots(tgx_state *st, const ComomentLaunch &L, int n_
 TGX_HIDDEN tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, size_t n_columns,
                                   int64_t *nrows_out, BatchTraits *traits, tgx_error *err);
 TGX_HIDDEN tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, int64_t nrows,
-                              tgx_error *err);
+                              tgx_error *err, const std::vector<BatchKeyFacts> *facts = nullptr);
 TGX_HIDDEN tgx_status coalesce_append(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, int64_t nrows,
                                   const BatchTraits &traits, bool *taken, tgx_error *err);
-TGX_HIDDEN uint64_t next_pow2(uint64_t x);
 TGX_HIDDEN tgx_status distinct_read_counters(tgx_state *st, DistinctState &ds, unsigned long long *out,
                                          tgx_error *err);
-TGX_HIDDEN HashSetView hash_view(const DistinctState &ds);
-TGX_HIDDEN BitmapView bitmap_view(const DistinctState &ds);
-TGX_HIDDEN tgx_status hash_alloc(tgx_state *st, DevBuf &keys, DevBuf &dup, uint64_t capacity, bool mult,
-                             bool wide, tgx_error *err);
-TGX_HIDDEN tgx_status hash_ensure(tgx_state *st, DistinctState &ds, bool mult, uint64_t incoming,
-                              tgx_error *err);
-TGX_HIDDEN tgx_status bitmap_to_hash(tgx_state *st, DistinctState &ds, bool mult, uint64_t incoming,
-                                 tgx_error *err);
-TGX_HIDDEN tgx_status tuple_desc_of(const std::vector<const tgx_column *> &cols, bool mult, TupleDesc *d, tgx_error *err);
-TGX_HIDDEN bool fp_lists_fit_rows(int64_t rows);
-TGX_HIDDEN tgx_status fp_lists_tuple_update(tgx_state *st, size_t slot, const TupleDesc &d,
-                                        const std::vector<const tgx_column *> &cols, tgx_error *err);
 TGX_HIDDEN tgx_status distinct_tuple_update(tgx_state *st, size_t slot, const tgx_column *dev, tgx_error *err,
                                         const tgx_column *orig = nullptr);
-TGX_HIDDEN tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column &c, NumericPrep *prep,
-                                           tgx_error *err);
-TGX_HIDDEN tgx_status distinct_run_numeric(tgx_state *st, size_t slot, const tgx_column &c, const NumericPrep &prep,
-                                       int stats_slot, tgx_error *err, const tgx_column *orig = nullptr);
-TGX_HIDDEN uint64_t fp_list_cap(int64_t rows, uint64_t lists);
-TGX_HIDDEN bool fp_lists_fit(const tgx_column &c);
-TGX_HIDDEN void fp_views(const DistinctState &ds, FpLists *l1, FpLists *l2);
-TGX_HIDDEN tgx_status fp_lists_prepare(tgx_state *st, DistinctState &ds, int64_t rows, size_t rec_bytes, tgx_error *err);
-TGX_HIDDEN tgx_status fp_lists_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error *err);
-TGX_HIDDEN tgx_status distinct_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error *err,
-                                  const std::vector<DictGather> *gathers = nullptr, const NumericPrep *ready = nullptr,
-                                  int stats_slot = -1, const tgx_column *orig = nullptr);
-TGX_HIDDEN void bitmap_shape(const DistinctState &ds, int64_t length, bool mult, uint32_t *sub_bits_out, bool *key16_out,
-                         uint64_t *n_buckets_out, bool *partitioned_out);
+TGX_HIDDEN tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column &c,
+                                           const BatchKeyFacts &facts, NumericPrep *prep, tgx_error *err);
+TGX_HIDDEN tgx_status distinct_update(tgx_state *st, size_t slot, const tgx_column &c, const BatchKeyFacts &facts,
+                                  const NumericPrep &prep, tgx_error *err,
+                                  const std::vector<DictGather> *gathers = nullptr, int stats_slot = -1,
+                                  const tgx_column *orig = nullptr);
 TGX_HIDDEN tgx_status pinned_readback(tgx_state *st, size_t bytes, tgx_error *err);
-TGX_HIDDEN bool distinct_wants_sample(const DistinctState &ds, const tgx_column &c);
-TGX_HIDDEN bool distinct_wants_exact_range(const DistinctState &ds, const tgx_column &c);
-TGX_HIDDEN tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, tgx_error *err);
-TGX_HIDDEN tgx_status bitmap_grow(tgx_state *st, DistinctState &ds, bool mult, int64_t lo, int64_t hi, int64_t incoming,
-                              tgx_error *err);
-TGX_HIDDEN tgx_status retained_numeric_view(tgx_state *st, const tgx_column &col, std::vector<std::unique_ptr<DevBuf>> &tmp,
-                                        tgx_column *out, tgx_error *err);
-TGX_HIDDEN tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot,
-                                   tgx_error *err);
+TGX_HIDDEN tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, std::vector<BatchKeyFacts> &facts,
+                                      tgx_error *err);
 TGX_HIDDEN void stream_copy(void *dst, const void *src, size_t bytes);
 TGX_HIDDEN void host_minmax_i64_plain(const int64_t *v, const uint8_t *validity, int64_t bit0, int64_t n, int64_t *lo,
                                   int64_t *hi);

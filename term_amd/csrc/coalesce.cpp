@@ -1022,30 +1022,26 @@ tgx_status tgx::coalesce_flush(tgx_state *st, tgx_error *err) {
   co.arena_busy[ar] = true;
   co.arena_cur ^= 1;
   co.arena_used = 0;
-  // Int64 key columns whose pending windows were all HOST: the flush's value range is known exactly
+  // what the host knows of each key column of the flush
+  std::vector<BatchKeyFacts> facts(plan->distinct.size());
   for (size_t q = 0; q < plan->distinct.size(); q++) {
     const DistinctTask &t = plan->distinct[q];
-    DistinctState &ds = st->distinct[q];
-    ds.batch_range_known = false;
-    ds.batch_bytes_known = false;
     if (!t.tuple.empty() || t.approx_only) continue;
     const CoalesceColumn &cc = co.cols[t.column];
-    ds.flush_device_keys = false;
+    BatchKeyFacts &kf = facts[q];
     // a string key column: the flush's value bytes were added up as its windows were noted (an exact key set sizes its
     // key store from them without asking the device); a dictionary column: the bytes of the flush's dictionary
-    if (is_string(cc.type) && !cc.segs.empty()) {
-      ds.batch_bytes_known = true;
-      ds.batch_data_bytes = cc.data_bytes;
-    } else if (cc.type == TGX_DICT32_UTF8 && cc.dict && !cc.segs.empty()) {
-      ds.batch_bytes_known = true;
-      ds.batch_data_bytes = cc.dict->data_bytes;
-    }
+    if (is_string(cc.type) && !cc.segs.empty())
+      kf.data_bytes = cc.data_bytes;
+    else if (cc.type == TGX_DICT32_UTF8 && cc.dict && !cc.segs.empty())
+      kf.data_bytes = cc.dict->data_bytes;
+    // an Int64 key column whose pending windows were all HOST: the flush's value range is known exactly
     if (cc.type == TGX_INT64 && cc.range_known && cc.range_lo <= cc.range_hi && !cc.segs.empty()) {
-      ds.batch_range_known = true;
-      ds.batch_lo = cc.range_lo;
-      ds.batch_hi = cc.range_hi;
+      kf.range_known = true;
+      kf.lo = cc.range_lo;
+      kf.hi = cc.range_hi;
     } else if (cc.type == TGX_INT64 && !cc.range_known && !cc.segs.empty()) {
-      ds.flush_device_keys = true;  // (DEVICE windows: the device will say, distinct_sample_all)
+      kf.device_keys = true;  // (DEVICE windows: the device will say, distinct_sample_all)
     }
   }
   // the pending list is empty from here on (update_impl may come back to tgx::coalesce_flush through a resolve)
@@ -1072,13 +1068,8 @@ tgx_status tgx::coalesce_flush(tgx_state *st, tgx_error *err) {
   std::vector<size_t> kept_before(st->distinct.size());
   for (size_t q = 0; q < st->distinct.size(); q++) kept_before[q] = st->distinct[q].retained.size();
   st->batches -= batches_of_flush;  // update_impl counts the flush as one batch: keep the caller's count
-  tgx_status rc = update_impl(plan, st, views.data(), rows, err);
+  tgx_status rc = update_impl(plan, st, views.data(), rows, err, &facts);
   st->batches += batches_of_flush - 1;
-  for (auto &ds : st->distinct) {
-    ds.batch_range_known = false;
-    ds.flush_device_keys = false;
-    ds.batch_bytes_known = false;
-  }
   // views the key sets kept of this flush point into region set `set` -- also when the pass failed half-way: a view
   // that kept the tag of "the caller's memory" would dangle once the set is used again
   for (size_t q = 0; q < st->distinct.size(); q++) {

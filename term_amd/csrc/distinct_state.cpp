@@ -2,12 +2,6 @@
 // the sampled range and its repair, export / import / adopt, tgx_merge.  Split off tgx_api.cpp in round 4.
 #include "api_internal.h"
 
-uint64_t next_pow2(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
 tgx_status distinct_read_counters(tgx_state *st, DistinctState &ds, unsigned long long *out,
                                          tgx_error *err) {
   memset(out, 0, kNumDistinctCounters * sizeof(unsigned long long));
@@ -16,6 +10,25 @@ tgx_status distinct_read_counters(tgx_state *st, DistinctState &ds, unsigned lon
                          hipMemcpyDeviceToHost, st->stream));
   HIP_TRY(hipStreamSynchronize(st->stream));
   return TGX_OK;
+}
+
+tgx_status pinned_readback(tgx_state *st, size_t bytes, tgx_error *err) {
+  if (bytes <= st->h_pinned_cap) return TGX_OK;
+  pinned_free(st->h_pinned, st->h_pinned_cap);
+  st->h_pinned = nullptr;
+  st->h_pinned_cap = 0;
+  const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
+  HIP_TRY(pinned_alloc(&st->h_pinned, want));
+  st->h_pinned_cap = want;
+  return TGX_OK;
+}
+
+namespace {
+
+uint64_t next_pow2(uint64_t x) {
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
 }
 
 HashSetView hash_view(const DistinctState &ds) {
@@ -33,6 +46,18 @@ HashSetView hash_view(const DistinctState &ds) {
   v.pending_waves = exact ? ds.key_pending_waves : 0;
   v.pad_ = 0;
   return v;
+}
+
+// the kernels' view of a numeric key column
+DistinctColDesc numeric_desc(const tgx_column &c, bool mult) {
+  DistinctColDesc d;
+  d.values = c.values;
+  d.validity = c.validity;
+  d.offset = c.offset;
+  d.length = c.length;
+  d.want_multiplicity = mult ? 1 : 0;
+  d.pad = 0;
+  return d;
 }
 
 // ---- the key store of an exact set ----
@@ -104,14 +129,17 @@ tgx_status key_store_measure_begin(tgx_state *st, DistinctState &ds, uint64_t it
   HIP_TRY(hipMemsetAsync(ds.key_cursor.as<unsigned long long>() + 1, 0, 3 * sizeof(unsigned long long), st->stream));
   return TGX_OK;
 }
-// room for the keys of a string column batch (every valid row a new key at worst)
-tgx_status key_store_reserve_utf8(tgx_state *st, DistinctState &ds, const tgx_column &c, tgx_error *err) {
+// room for the keys of a string column (every valid row a new key at worst; `used`: a dictionary's entries that the
+// batch refers to, or nullptr).  `data_bytes` >= 0: the column's value bytes, which a coalesced flush counted as its
+// windows were noted -- the host bounds the fill itself; otherwise (-1) the device measures it
+tgx_status key_store_reserve_utf8(tgx_state *st, DistinctState &ds, const tgx_column &c, const uint32_t *used,
+                                  int64_t data_bytes, tgx_error *err) {
   TGX_TRY(key_store_measure_begin(st, ds, (uint64_t)c.length, err));
-  if (ds.batch_bytes_known && c.type != TGX_UTF8_VIEW)  // (an entry: two words + ceil(len / 8) <= len / 8 + 3 words)
-    return key_store_reserve_bound(st, ds, 3 * (uint64_t)c.length + (uint64_t)ds.batch_data_bytes / 8, err);
+  if (data_bytes >= 0 && c.type != TGX_UTF8_VIEW)  // (an entry: two words + ceil(len / 8) <= len / 8 + 3 words)
+    return key_store_reserve_bound(st, ds, 3 * (uint64_t)c.length + (uint64_t)data_bytes / 8, err);
   const bool view = c.type == TGX_UTF8_VIEW;
   launch_exact_measure_utf8(c.offsets, c.data, view ? c.values : nullptr, view ? c.variadic : nullptr, c.validity, c.offset,
-                            c.length, c.type == TGX_LARGE_UTF8, nullptr, ds.key_cursor.as<unsigned long long>() + 1,
+                            c.length, c.type == TGX_LARGE_UTF8, used, ds.key_cursor.as<unsigned long long>() + 1,
                             st->stream);
   return key_store_reserve_measured(st, ds, err);
 }
@@ -204,13 +232,28 @@ tgx_status bitmap_to_hash(tgx_state *st, DistinctState &ds, bool mult, uint64_t 
   return TGX_OK;
 }
 
+// a string column's keys into the table (`data_bytes`: see key_store_reserve_utf8)
+tgx_status table_insert_utf8(tgx_state *st, size_t slot, const tgx_column &c, int64_t data_bytes, tgx_error *err) {
+  DistinctState &ds = st->distinct[slot];
+  const bool mult = st->plan->distinct[slot].multiplicity;
+  TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)c.length, err));
+  if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, c, nullptr, data_bytes, err));
+  const bool view = c.type == TGX_UTF8_VIEW;
+  launch_distinct_utf8(c.offsets, c.data, view ? c.values : nullptr, view ? c.variadic : nullptr, c.validity, c.offset,
+                       c.length, c.type == TGX_LARGE_UTF8, mult ? 1 : 0, hash_view(ds), st->plan->fp_key,
+                       ds.counters.as<unsigned long long>(), st->stream);
+  return TGX_OK;
+}
+
 // COUNT(DISTINCT (a, b, ...)): every row's tuple goes into the 128-bit fingerprint set (kernels/distinct128.hip)
 // the kernels' view of a tuple of columns; cols[k] = the k-th component
-tgx_status tuple_desc_of(const std::vector<const tgx_column *> &cols, bool mult, TupleDesc *d, tgx_error *err) {
+tgx_status tuple_desc_of(const tgx_state *st, const std::vector<const tgx_column *> &cols, bool mult, TupleDesc *d,
+                         tgx_error *err) {
   memset(d, 0, sizeof(*d));
   d->n_cols = (int32_t)cols.size();
   d->want_multiplicity = mult ? 1 : 0;
   d->length = cols[0]->length;
+  d->key = st->plan->fp_key;
   for (size_t k = 0; k < cols.size(); k++) {
     const tgx_column &c = *cols[k];
     TupleCol &tc = d->cols[k];
@@ -245,48 +288,18 @@ tgx_status tuple_desc_of(const std::vector<const tgx_column *> &cols, bool mult,
   return TGX_OK;
 }
 
-
-// COUNT(DISTINCT (a, b, ...)): every row's tuple goes into the 128-bit fingerprint set (kernels/distinct128.hip)
-tgx_status distinct_tuple_update(tgx_state *st, size_t slot, const tgx_column *dev, tgx_error *err,
-                                        const tgx_column *orig) {
-  const DistinctTask &task = st->plan->distinct[slot];
+// a tuple batch's keys into the table
+tgx_status table_insert_tuple(tgx_state *st, size_t slot, const TupleDesc &d, tgx_error *err) {
   DistinctState &ds = st->distinct[slot];
-  std::vector<const tgx_column *> cols;
-  bool any_view = false;  // a component whose device view lives in per-update scratch: never retained (no lists)
-  for (int c2 : task.tuple) {
-    cols.push_back(&dev[c2]);
-    any_view |= dev[c2].type == TGX_UTF8_VIEW || (orig && is_widened(orig[c2].type));
-  }
-  TupleDesc d;
-  TGX_TRY(tuple_desc_of(cols, task.multiplicity, &d, err));
-  d.key = st->plan->fp_key;
-  ds.col_type = TGX_UTF8;  // a 128-bit fingerprint set, like a string column's
-  ds.total_rows += d.length;
-  if (d.length == 0) return TGX_OK;
-  if (ds.fp_staged) TGX_TRY(distinct_resolve(st, slot, err));  // a second batch: the table takes over
-  // the first big batch: through the partitioned lists (views read their buffers through a table staged per update)
-  // (an exact set takes the lists only over the caller's own DEVICE buffers, which outlive the update: its records refer
-  //  to rows, and what turns the lists into a table later needs the rows' bytes)
-  bool exact_lists_ok = orig != nullptr && d.length < (int64_t)1 << 32;
-  if (orig)
-    for (int c2 : task.tuple) exact_lists_ok &= orig[c2].mem == TGX_MEM_DEVICE && !is_widened(orig[c2].type);
-  if (ds.mode == DistinctMode::kUndecided && !any_view && (!ds.exact || exact_lists_ok) && fp_lists_fit_rows(d.length))
-    return fp_lists_tuple_update(st, slot, d, cols, err);
-  if (ds.mode == DistinctMode::kUndecided) {
-    ds.mode = DistinctMode::kHash;
-    ds.wide = true;
-  }
-  TGX_TRY(hash_ensure(st, ds, task.multiplicity, (uint64_t)d.length, err));
+  TGX_TRY(hash_ensure(st, ds, st->plan->distinct[slot].multiplicity, (uint64_t)d.length, err));
   if (ds.exact) {
     TGX_TRY(key_store_measure_begin(st, ds, (uint64_t)d.length, err));
     launch_exact_measure_tuple(d, ds.key_cursor.as<unsigned long long>() + 1, st->stream);
     TGX_TRY(key_store_reserve_measured(st, ds, err));
   }
-  ProfScope ps(st, "distinct", 0);
   launch_distinct_tuple(d, hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
   return TGX_OK;
 }
-
 
 // ---- big Utf8 batches: partitioned fingerprint lists (kernels/distinct128.hip, fp_*) ----
 // records a list is sized for when `rows` values are spread over `lists` lists: the mean, twelve standard deviations
@@ -312,10 +325,15 @@ void fp_views(const DistinctState &ds, FpLists *l1, FpLists *l2) {
   l2->offered = ds.fp_offered.as<uint32_t>() + kFpXcds * kFpFan;
   l2->cap = ds.fp_cap2;
 }
-// sizes and clears the two levels of lists for a batch of `rows` records of `rec_bytes` bytes
-tgx_status fp_lists_prepare(tgx_state *st, DistinctState &ds, int64_t rows, size_t rec_bytes, tgx_error *err) {
+// The first big batch of a key set goes onto two levels of partitioned lists, which are the set until the table is
+// needed (distinct_resolve): sizes and clears them for `rows` records -- 128-bit fingerprints (`wide`) or 8-byte keys
+// -- and marks the set as staged there.  An exact set's records carry their row: the other half of the second
+// fingerprint word waits in `*fb_lo` for the day the batch is released while the lists are still the key set.
+tgx_status fp_lists_stage(tgx_state *st, DistinctState &ds, int64_t rows, bool wide, FpLists *l1, FpLists *l2,
+                          uint32_t **fb_lo, tgx_error *err) {
   constexpr uint64_t kLists2 = (uint64_t)kFpFan * kFpFan;
   constexpr uint64_t kLists1 = (uint64_t)kFpXcds * kFpFan;
+  const size_t rec_bytes = wide ? 16 : 8;
   ds.fp_cap1 = fp_list_cap(rows, kLists1);
   ds.fp_cap2 = fp_list_cap(rows, kLists2);
   // TGX_FP_LIST_CAPS="cap1:cap2" (tests): room for longer lists than the batch's size asks for, so that a batch of a
@@ -332,23 +350,25 @@ tgx_status fp_lists_prepare(tgx_state *st, DistinctState &ds, int64_t rows, size
   HIP_TRY(ds.fp_offered.reserve((kLists1 + kLists2) * sizeof(uint32_t)));
   HIP_TRY(ds.fp_per_list.reserve(kLists2 * sizeof(uint2)));
   HIP_TRY(hipMemsetAsync(ds.fp_offered.p, 0, (kLists1 + kLists2) * sizeof(uint32_t), st->stream));
+  const bool exact = ds.exact && wide;
+  *fb_lo = nullptr;
+  if (exact) {
+    HIP_TRY(ds.fp_fb_lo.reserve((size_t)rows * sizeof(uint32_t) + 16));
+    *fb_lo = ds.fp_fb_lo.as<uint32_t>();
+  }
+  fp_views(ds, l1, l2);
+  ds.mode = DistinctMode::kHash;
+  ds.wide = wide;
+  ds.capacity = 0;  // no table yet
+  ds.rows_upper_bound = 0;
+  ds.fp_staged = true;
+  ds.fp_exact_lists = exact;
   return TGX_OK;
 }
 
 tgx_status fp_lists_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error *err) {
   DistinctState &ds = st->distinct[slot];
   const bool mult = st->plan->distinct[slot].multiplicity;
-  TGX_TRY(fp_lists_prepare(st, ds, c.length, 16, err));
-  FpLists l1, l2;
-  fp_views(ds, &l1, &l2);
-  ProfScope ps(st, "distinct", 0), ps_lists(st, "distinct_lists", 0);
-  unsigned long long *counters = ds.counters.as<unsigned long long>();
-  // an exact set: records carry their row, the count settles equal fingerprints on the rows' bytes
-  uint32_t *fb_lo = nullptr;
-  if (ds.exact) {
-    HIP_TRY(ds.fp_fb_lo.reserve((size_t)c.length * sizeof(uint32_t) + 16));
-    fb_lo = ds.fp_fb_lo.as<uint32_t>();
-  }
   tgx_column kept = c;
   const bool view = c.type == TGX_UTF8_VIEW;
   if (view) {
@@ -359,25 +379,26 @@ tgx_status fp_lists_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_
       HIP_TRY(hipMemcpyAsync(ds.fp_buffers.p, c.variadic, (size_t)c.n_variadic * sizeof(void *), hipMemcpyDeviceToDevice,
                              st->stream));
     kept.variadic = (const uint8_t *const *)ds.fp_buffers.p;
+  }
+  FpLists l1, l2;
+  uint32_t *fb_lo = nullptr;
+  TGX_TRY(fp_lists_stage(st, ds, c.length, true, &l1, &l2, &fb_lo, err));
+  ProfScope ps(st, "distinct", 0), ps_lists(st, "distinct_lists", 0);
+  unsigned long long *counters = ds.counters.as<unsigned long long>();
+  if (view)
     launch_fp_partition_views(c.values, kept.variadic, c.validity, c.offset, c.length, l1, st->plan->fp_key, fb_lo, counters,
                               st->stream);
-  } else {
+  else
     launch_fp_partition_strings(c.offsets, c.data, c.validity, c.offset, c.length, c.type == TGX_LARGE_UTF8, l1,
                                 st->plan->fp_key, fb_lo, counters, st->stream);
-  }
   launch_fp_partition_lists(l1, l2, counters, st->stream);
+  // an exact set: records carry their row, the count settles equal fingerprints on the rows' bytes
   if (ds.exact)
     launch_fp_count_exact_utf8(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), l1.offered, c.offsets, c.data,
                                view ? c.values : nullptr, view ? kept.variadic : nullptr, c.offset, c.length,
                                c.type == TGX_LARGE_UTF8, counters, st->stream);
   else
     launch_fp_count(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), l1.offered, counters, st->stream);
-  ds.mode = DistinctMode::kHash;
-  ds.wide = true;
-  ds.capacity = 0;  // no table yet
-  ds.rows_upper_bound = 0;
-  ds.fp_staged = true;
-  ds.fp_exact_lists = ds.exact;
   ds.retained.push_back(kept);  // (a DEVICE view, or a staged one looked at before the update returns)
   return TGX_OK;
 }
@@ -387,131 +408,57 @@ tgx_status fp_lists_tuple_update(tgx_state *st, size_t slot, const TupleDesc &d,
                                         const std::vector<const tgx_column *> &cols, tgx_error *err) {
   DistinctState &ds = st->distinct[slot];
   const bool mult = st->plan->distinct[slot].multiplicity;
-  TGX_TRY(fp_lists_prepare(st, ds, d.length, 16, err));
   FpLists l1, l2;
-  fp_views(ds, &l1, &l2);
+  uint32_t *fb_lo = nullptr;
+  TGX_TRY(fp_lists_stage(st, ds, d.length, true, &l1, &l2, &fb_lo, err));
   ProfScope ps(st, "distinct", 0), ps_lists(st, "distinct_lists", 0);
   unsigned long long *counters = ds.counters.as<unsigned long long>();
-  uint32_t *fb_lo = nullptr;
-  if (ds.exact) {
-    HIP_TRY(ds.fp_fb_lo.reserve((size_t)d.length * sizeof(uint32_t) + 16));
-    fb_lo = ds.fp_fb_lo.as<uint32_t>();
-  }
   launch_fp_partition_tuples(d, l1, fb_lo, counters, st->stream);
   launch_fp_partition_lists(l1, l2, counters, st->stream);
   if (ds.exact)
     launch_fp_count_exact_tuple(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), d, counters, st->stream);
   else
     launch_fp_count(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), nullptr, counters, st->stream);  // (valid rows: level 1)
-  ds.mode = DistinctMode::kHash;
-  ds.wide = true;
-  ds.capacity = 0;  // no table yet
-  ds.rows_upper_bound = 0;
-  ds.fp_staged = true;
-  ds.fp_exact_lists = ds.exact;
   for (const tgx_column *c : cols) ds.retained.push_back(*c);
   return TGX_OK;
 }
 
-// `orig`: the caller's own view of the column when `c` is a per-update staging copy of a DEVICE column (a 4-byte
-// numeric column widened for this pass): what a key set retains for a later repair must outlive the update
-tgx_status distinct_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error *err,
-                                  const std::vector<DictGather> *gathers, const NumericPrep *ready,
-                                  int stats_slot, const tgx_column *orig) {
+}  // namespace
+
+// COUNT(DISTINCT (a, b, ...)): every row's tuple goes into the 128-bit fingerprint set (kernels/distinct128.hip)
+tgx_status distinct_tuple_update(tgx_state *st, size_t slot, const tgx_column *dev, tgx_error *err,
+                                        const tgx_column *orig) {
   const DistinctTask &task = st->plan->distinct[slot];
   DistinctState &ds = st->distinct[slot];
-  const bool mult = task.multiplicity;
-  if (is_any_string(c.type)) {
-    // values are reduced to 128-bit fingerprints on the fly (kernels/distinct128.hip)
-    ds.col_type = c.type;
-    ds.total_rows += c.length;
-    if (c.length == 0) return TGX_OK;
-    if (ds.fp_staged) TGX_TRY(distinct_resolve(st, slot, err));  // a second batch: the table takes over
-    // (an exact set takes the lists only over the caller's own DEVICE buffers, which outlive the update: its records
-    //  refer to rows, and what turns the lists into a table later needs the rows' bytes)
-    const bool exact_lists_ok = orig && orig->mem == TGX_MEM_DEVICE && c.length < (int64_t)1 << 32;
-    if (ds.mode == DistinctMode::kUndecided && (!ds.exact || exact_lists_ok) && fp_lists_fit(c))
-      return fp_lists_update(st, slot, c, err);
-    if (ds.mode == DistinctMode::kUndecided) {
-      ds.mode = DistinctMode::kHash;
-      ds.wide = true;
-    }
-    TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)c.length, err));
-    if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, c, err));
-    ProfScope ps(st, "distinct", 0);
-    const bool view = c.type == TGX_UTF8_VIEW;
-    launch_distinct_utf8(c.offsets, c.data, view ? c.values : nullptr, view ? c.variadic : nullptr, c.validity,
-                         c.offset, c.length, c.type == TGX_LARGE_UTF8, mult ? 1 : 0, hash_view(ds), st->plan->fp_key,
-                         ds.counters.as<unsigned long long>(), st->stream);
-    return TGX_OK;
+  std::vector<const tgx_column *> cols;
+  bool any_view = false;  // a component whose device view lives in per-update scratch: never retained (no lists)
+  for (int c2 : task.tuple) {
+    cols.push_back(&dev[c2]);
+    any_view |= dev[c2].type == TGX_UTF8_VIEW || (orig && is_widened(orig[c2].type));
   }
-  if (c.type == TGX_DICT32_UTF8) {
-    // string work once per dictionary entry: count references per entry, then insert the fingerprints of the
-    // referenced entries -- identical set contents to the plain Utf8 path (kernels/dict.hip)
-    const tgx_column &dict = *c.dictionary;
-    ds.col_type = c.type;
-    ds.total_rows += c.length;
-    if (c.length == 0 || dict.length == 0) return TGX_OK;
-    if (ds.mode == DistinctMode::kUndecided) {
-      ds.mode = DistinctMode::kHash;
-      ds.wide = true;
-    }
-    TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)std::min<int64_t>(c.length, dict.length), err));
-    const size_t uw = dict_usage_words(dict.length);
-    HIP_TRY(ds.dict_usage.reserve(2 * uw * 4 + 16));
-    const size_t scratch = dict_usage_scratch_bytes(c.length, dict.length, mult ? 1 : 0, g_ctx.n_cu);
-    if (scratch)
-      HIP_TRY(ds.dict_scratch.reserve(scratch));
-    else
-      HIP_TRY(hipMemsetAsync(ds.dict_usage.p, 0, 2 * uw * 4, st->stream));  // the global-atomics path accumulates
-    uint32_t *u_seen = ds.dict_usage.as<uint32_t>(), *u_twice = u_seen + uw;
-    ProfScope ps(st, "distinct", 0);
-    if (gathers && !gathers->empty() && scratch) {
-      // the column's pattern / length checks ride on this pass: the indices are read once
-      const uint8_t *hits[4];
-      unsigned long long *pc[4];
-      int32_t niv[4];
-      const int k = (int)std::min<size_t>(gathers->size(), 4);
-      for (int i = 0; i < k; i++) {
-        hits[i] = (*gathers)[i].hits;
-        pc[i] = (*gathers)[i].counters;
-        niv[i] = (*gathers)[i].null_is_valid;
-      }
-      launch_dict_usage_fused((const int32_t *)c.values, c.validity, c.offset, c.length, dict.length, mult ? 1 : 0, k,
-                              hits, pc, niv, u_seen, u_twice, ds.dict_scratch.as<uint32_t>(),
-                              ds.counters.as<unsigned long long>(), g_ctx.n_cu, st->stream);
-    } else {
-      launch_dict_usage((const int32_t *)c.values, c.validity, c.offset, c.length, dict.validity, dict.offset,
-                        dict.length, mult ? 1 : 0, u_seen, u_twice, ds.dict_scratch.as<uint32_t>(),
-                        ds.counters.as<unsigned long long>(), g_ctx.n_cu, st->stream);
-    }
-    if (ds.exact) {  // room for the referenced entries
-      TGX_TRY(key_store_measure_begin(st, ds, (uint64_t)dict.length, err));
-      if (ds.batch_bytes_known) {
-        TGX_TRY(key_store_reserve_bound(st, ds, 3 * (uint64_t)dict.length + (uint64_t)ds.batch_data_bytes / 8, err));
-      } else {
-      launch_exact_measure_utf8(dict.offsets, dict.data, nullptr, nullptr, dict.validity, dict.offset, dict.length,
-                                dict.type == TGX_LARGE_UTF8, u_seen, ds.key_cursor.as<unsigned long long>() + 1, st->stream);
-      TGX_TRY(key_store_reserve_measured(st, ds, err));
-      }
-    }
-    launch_dict_insert(dict.offsets, dict.data, dict.validity, dict.offset, dict.length,
-                       dict.type == TGX_LARGE_UTF8, mult ? 1 : 0, u_seen, u_twice, hash_view(ds), st->plan->fp_key,
-                       ds.counters.as<unsigned long long>(), st->stream);
-    return TGX_OK;
+  TupleDesc d;
+  TGX_TRY(tuple_desc_of(st, cols, task.multiplicity, &d, err));
+  ds.col_type = TGX_UTF8;  // a 128-bit fingerprint set, like a string column's
+  ds.total_rows += d.length;
+  if (d.length == 0) return TGX_OK;
+  if (ds.fp_staged) TGX_TRY(distinct_resolve(st, slot, err));  // a second batch: the table takes over
+  // the first big batch: through the partitioned lists (views read their buffers through a table staged per update)
+  // (an exact set takes the lists only over the caller's own DEVICE buffers, which outlive the update: its records refer
+  //  to rows, and what turns the lists into a table later needs the rows' bytes)
+  bool exact_lists_ok = orig != nullptr && d.length < (int64_t)1 << 32;
+  if (orig)
+    for (int c2 : task.tuple) exact_lists_ok &= orig[c2].mem == TGX_MEM_DEVICE && !is_widened(orig[c2].type);
+  if (ds.mode == DistinctMode::kUndecided && !any_view && (!ds.exact || exact_lists_ok) && fp_lists_fit_rows(d.length))
+    return fp_lists_tuple_update(st, slot, d, cols, err);
+  if (ds.mode == DistinctMode::kUndecided) {
+    ds.mode = DistinctMode::kHash;
+    ds.wide = true;
   }
-  if (!is_numeric(c.type))
-    return fail(err, TGX_UNSUPPORTED, "DISTINCT on column type %d is not supported yet", c.type);
-  ds.col_type = c.type;
-  ds.total_rows += c.length;
-  if (c.length == 0) return TGX_OK;
-  NumericPrep prep;
-  if (ready && ready->prepared)
-    prep = *ready;  // decided before the scan of this batch was queued (tgx_update)
-  else
-    TGX_TRY(distinct_prepare_numeric(st, slot, c, &prep, err));
-  return distinct_run_numeric(st, slot, c, prep, stats_slot, err, orig);
+  ProfScope ps(st, "distinct", 0);
+  return table_insert_tuple(st, slot, d, err);
 }
+
+namespace {
 
 // How the keys of one batch of an Int64 / Float64 column enter the set.
 //   * a set that is a range bitmap takes every batch as it is: keys outside its range are counted, never inserted,
@@ -544,47 +491,39 @@ void bitmap_shape(const DistinctState &ds, int64_t length, bool mult, uint32_t *
                      cap_slots < (1ull << 32) - 64;
 }
 
-tgx_status pinned_readback(tgx_state *st, size_t bytes, tgx_error *err) {
-  if (bytes <= st->h_pinned_cap) return TGX_OK;
-  pinned_free(st->h_pinned, st->h_pinned_cap);
-  st->h_pinned = nullptr;
-  st->h_pinned_cap = 0;
-  const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-  HIP_TRY(pinned_alloc(&st->h_pinned, want));
-  st->h_pinned_cap = want;
-  return TGX_OK;
-}
-
 // does this batch of an undecided Int64 key set get its range from a sample? (see distinct_prepare_numeric)
-bool distinct_wants_sample(const DistinctState &ds, const tgx_column &c) {
-  return ds.mode == DistinctMode::kUndecided && c.type == TGX_INT64 && !ds.has_hint && !ds.batch_range_known &&
+bool distinct_wants_sample(const DistinctState &ds, const BatchKeyFacts &facts, const tgx_column &c) {
+  return ds.mode == DistinctMode::kUndecided && c.type == TGX_INT64 && !ds.has_hint && !facts.range_known &&
          !ds.remembered && c.length >= (1 << 16);
 }
 // ... or the exact MIN / MAX of a coalesced flush whose key windows were DEVICE memory?  While the key set is undecided,
 // or a bitmap no batch can have left outliers under: the flush then lays the bitmap out / grows it like a HOST flush
 // (a stream of DEVICE batches of growing ids stays on the bitmap instead of going through the repair, flush after flush)
-bool distinct_wants_exact_range(const DistinctState &ds, const tgx_column &c) {
-  if (!ds.flush_device_keys || c.type != TGX_INT64 || ds.has_hint || ds.batch_range_known || c.length < (1 << 16))
+bool distinct_wants_exact_range(const DistinctState &ds, const BatchKeyFacts &facts, const tgx_column &c) {
+  if (!facts.device_keys || c.type != TGX_INT64 || ds.has_hint || facts.range_known || c.length < (1 << 16))
     return false;
   return ds.mode == DistinctMode::kUndecided ||
          (ds.mode == DistinctMode::kBitmap && ds.speculative && !ds.partitioned && !ds.outliers_possible);
 }
 
+}  // namespace
+
 // The samples of ALL key columns of the batch, queued together and read back with ONE wait: a read-back costs the
 // stream's latency (~50 us) whatever its size -- two key columns sampled one after the other were 6 % of a
-// 100 M-row step.
-tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, tgx_error *err) {
+// 100 M-row step.  What they say goes into `facts`: a sample, or the exact range of a flush's DEVICE windows.
+tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, std::vector<BatchKeyFacts> &facts,
+                               tgx_error *err) {
   const tgx_plan *plan = st->plan;
   std::vector<size_t> who;
   for (size_t q = 0; q < plan->distinct.size(); q++) {
     const DistinctTask &t = plan->distinct[q];
-    st->distinct[q].sample_ready = false;
     if (!t.tuple.empty() || !is_numeric(dev[t.column].type) || dev[t.column].length == 0) continue;
     bool lane = false;  // (the HyperLogLog lane has the column: its approx_only key set stays idle)
     for (size_t h = 0; h < plan->hll.size(); h++)
       lane |= plan->hll[h].distinct_slot == (int)q && st->hll_mode[h] == 1;
     if (lane) continue;
-    if (distinct_wants_sample(st->distinct[q], dev[t.column]) || distinct_wants_exact_range(st->distinct[q], dev[t.column]))
+    if (distinct_wants_sample(st->distinct[q], facts[q], dev[t.column]) ||
+        distinct_wants_exact_range(st->distinct[q], facts[q], dev[t.column]))
       who.push_back(q);
   }
   if (who.empty()) return TGX_OK;
@@ -593,13 +532,8 @@ tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, tgx_error *
   for (size_t k = 0; k < who.size(); k++) {
     DistinctState &ds = st->distinct[who[k]];
     const tgx_column &c = dev[plan->distinct[who[k]].column];
-    DistinctColDesc d;
-    d.values = c.values;
-    d.validity = c.validity;
-    d.offset = c.offset;
-    d.length = c.length;
-    d.want_multiplicity = 0;
-    d.pad = distinct_wants_exact_range(ds, c) ? 1 : 0;  // every row, not a sample
+    DistinctColDesc d = numeric_desc(c, false);
+    d.pad = distinct_wants_exact_range(ds, facts[who[k]], c) ? 1 : 0;  // every row, not a sample
     HIP_TRY(ds.sample.reserve(sizeof(DistinctSample)));
     launch_distinct_init(ds.sample.as<DistinctSample>(), nullptr, st->stream);
     launch_distinct_sample(d, ds.sample.as<DistinctSample>(), st->stream);
@@ -607,20 +541,22 @@ tgx_status distinct_sample_all(tgx_state *st, const tgx_column *dev, tgx_error *
   }
   HIP_TRY(hipStreamSynchronize(st->stream));  // (the stream holds nothing but the samples when a step starts)
   for (size_t k = 0; k < who.size(); k++) {
-    DistinctState &ds = st->distinct[who[k]];
-    if (distinct_wants_exact_range(ds, dev[plan->distinct[who[k]].column])) {
+    BatchKeyFacts &kf = facts[who[k]];
+    if (distinct_wants_exact_range(st->distinct[who[k]], kf, dev[plan->distinct[who[k]].column])) {
       if (got[k].count) {  // the flush's range, as if the host had seen the values
-        ds.batch_range_known = true;
-        ds.batch_lo = got[k].min_v;
-        ds.batch_hi = got[k].max_v;
+        kf.range_known = true;
+        kf.lo = got[k].min_v;
+        kf.hi = got[k].max_v;
       }
       continue;
     }
-    ds.sample_host = got[k];
-    ds.sample_ready = true;
+    kf.sample = got[k];
+    kf.sampled = true;
   }
   return TGX_OK;
 }
+
+namespace {
 
 // Extends a sampled-range bitmap so that it covers [lo, hi] as well: whole 2^20-bit slices are added below and / or
 // above (the old words move by whole slices, a device copy), generously in the direction of growth -- at least the
@@ -687,13 +623,18 @@ tgx_status bitmap_grow(tgx_state *st, DistinctState &ds, bool mult, int64_t lo, 
   return TGX_OK;
 }
 
-tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column &c, NumericPrep *prep,
-                                           tgx_error *err) {
+}  // namespace
+
+tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column &c, const BatchKeyFacts &facts,
+                                    NumericPrep *prep, tgx_error *err) {
   const DistinctTask &task = st->plan->distinct[slot];
   DistinctState &ds = st->distinct[slot];
   const bool mult = task.multiplicity;
   prep->prepared = true;
   prep->partitioned = false;
+  prep->range_known = facts.range_known;
+  prep->lo = facts.lo;
+  prep->hi = facts.hi;
   if (ds.mode == DistinctMode::kUndecided) {
     bool have_range = false;
     int64_t lo = 0, hi = 0;
@@ -701,32 +642,22 @@ tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column
       have_range = true;  // the caller vouches for [lo, hi]; keys outside it are counted and reported
       lo = ds.hint_lo;
       hi = ds.hint_hi;
-    } else if (c.type == TGX_INT64 && ds.batch_range_known) {
+    } else if (c.type == TGX_INT64 && facts.range_known) {
       have_range = true;  // a coalesced flush of HOST windows: the host saw every value on its way into the arena
-      lo = ds.batch_lo;
-      hi = ds.batch_hi;
+      lo = facts.lo;
+      hi = facts.hi;
     } else if (c.type == TGX_INT64 && ds.remembered && c.length >= (1 << 16)) {
       have_range = true;  // what the column's sample said before the state was reset; outliers are repaired as ever
       lo = ds.remembered_lo;
       hi = ds.remembered_hi;
-    } else if (distinct_wants_sample(ds, c)) {
+    } else if (distinct_wants_sample(ds, facts, c)) {
       // (a stream of small batches -- DataFusion hands out 8192 rows at a time -- goes straight to the hash set:
       // its inserts need no range, and the read-back of a sample would cost one stream synchronisation per batch)
-      DistinctSample got;
-      if (ds.sample_ready) {  // tgx_update has read the samples of all key columns at once
-        got = ds.sample_host;
-        ds.sample_ready = false;
-      } else {
-        DistinctColDesc d;
-        d.values = c.values;
-        d.validity = c.validity;
-        d.offset = c.offset;
-        d.length = c.length;
-        d.want_multiplicity = 0;
-        d.pad = 0;
+      DistinctSample got = facts.sample;
+      if (!facts.sampled) {  // (tgx_update reads the samples of all key columns at once: distinct_sample_all)
         HIP_TRY(ds.sample.reserve(sizeof(DistinctSample)));
         launch_distinct_init(ds.sample.as<DistinctSample>(), nullptr, st->stream);
-        launch_distinct_sample(d, ds.sample.as<DistinctSample>(), st->stream);
+        launch_distinct_sample(numeric_desc(c, false), ds.sample.as<DistinctSample>(), st->stream);
         HIP_TRY(hipMemcpyAsync(&got, ds.sample.p, sizeof(got), hipMemcpyDeviceToHost, st->stream));
         HIP_TRY(hipStreamSynchronize(st->stream));
       }
@@ -767,7 +698,7 @@ tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column
       }
       ds.mode = DistinctMode::kBitmap;
       ds.speculative = !ds.has_hint;
-      if (ds.speculative && !ds.batch_range_known) {
+      if (ds.speculative && !facts.range_known) {
         ds.remembered = true;
         ds.remembered_lo = lo;
         ds.remembered_hi = hi;
@@ -779,14 +710,13 @@ tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column
   }
   // a later batch whose range the host knows and the bitmap does not cover (ids that grow from batch to batch): the
   // bitmap grows instead of counting the batch's keys as outliers and repairing them through the hash set afterwards
-  if (ds.mode == DistinctMode::kBitmap && ds.speculative && !ds.partitioned && ds.batch_range_known &&
+  if (ds.mode == DistinctMode::kBitmap && ds.speculative && !ds.partitioned && facts.range_known &&
       !ds.outliers_possible)
-    TGX_TRY(bitmap_grow(st, ds, mult, ds.batch_lo, ds.batch_hi, c.length, err));
+    TGX_TRY(bitmap_grow(st, ds, mult, facts.lo, facts.hi, c.length, err));
   if (ds.mode == DistinctMode::kBitmap && ds.speculative) {
     // can this batch leave keys outside the range?  Not when the host saw every value and the bitmap covers them.
     auto u = [](int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; };
-    const bool covered = ds.batch_range_known && u(ds.batch_lo) >= u(ds.base) &&
-                         u(ds.batch_hi) - u(ds.base) < ds.range;
+    const bool covered = facts.range_known && u(facts.lo) >= u(ds.base) && u(facts.hi) - u(ds.base) < ds.range;
     if (!covered) ds.outliers_possible = true;
   }
   if (ds.mode == DistinctMode::kBitmap) {
@@ -795,6 +725,8 @@ tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column
   }
   return TGX_OK;
 }
+
+namespace {
 
 // `stats_slot` >= 0: the partition pass also produces the column's COUNT / MIN / MAX / SUM into that scan slot (the
 // numeric scan has skipped the column)
@@ -807,13 +739,7 @@ tgx_status distinct_run_numeric(tgx_state *st, size_t slot, const tgx_column &c,
   const tgx_column &keep = (orig && orig->mem == TGX_MEM_DEVICE && is_widened(orig->type)) ? *orig : c;
   DistinctState &ds = st->distinct[slot];
   const bool mult = task.multiplicity;
-  DistinctColDesc d;
-  d.values = c.values;
-  d.validity = c.validity;
-  d.offset = c.offset;
-  d.length = c.length;
-  d.want_multiplicity = mult ? 1 : 0;
-  d.pad = 0;
+  const DistinctColDesc d = numeric_desc(c, mult);
   const uint64_t bytes = (uint64_t)c.length * 8 + (c.validity ? (uint64_t)(c.length + 7) / 8 : 0);
   if (ds.mode == DistinctMode::kUndecided) return TGX_OK;  // nothing valid seen yet
   if (ds.mode == DistinctMode::kBitmap) {
@@ -837,11 +763,11 @@ tgx_status distinct_run_numeric(tgx_state *st, size_t slot, const tgx_column &c,
       // stream, and lists sized for an even spread over ALL slices would overflow into the spill path
       pp.bucket0 = 0;
       pp.n_lists = pp.n_buckets;
-      if (ds.batch_range_known) {
+      if (prep.range_known) {
         auto u = [](int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; };
         const uint64_t ub = u(ds.base);
-        const uint64_t rlo = u(ds.batch_lo) > ub ? u(ds.batch_lo) - ub : 0;
-        uint64_t rhi = u(ds.batch_hi) > ub ? u(ds.batch_hi) - ub : 0;
+        const uint64_t rlo = u(prep.lo) > ub ? u(prep.lo) - ub : 0;
+        uint64_t rhi = u(prep.hi) > ub ? u(prep.hi) - ub : 0;
         rhi = std::min(rhi, ds.range - 1);
         if (rlo <= rhi) {
           pp.bucket0 = (uint32_t)(rlo >> pp.sub_bits);
@@ -907,13 +833,12 @@ tgx_status distinct_run_numeric(tgx_state *st, size_t slot, const tgx_column &c,
     if (ds.capacity == 0 && fp_lists_fit(c)) {
       // the first big batch of a key set without a dense range: mixed keys through partitioned lists, deduplicated
       // in LDS (kernels/distinct.hip, key_*) -- no global atomic per key; the lists are the set until the table is needed
-      TGX_TRY(fp_lists_prepare(st, ds, c.length, 8, err));
       FpLists l1, l2;
-      fp_views(ds, &l1, &l2);
+      uint32_t *fb_lo = nullptr;  // (8-byte keys: no rows carried)
+      TGX_TRY(fp_lists_stage(st, ds, c.length, false, &l1, &l2, &fb_lo, err));
       ProfScope ps(st, "distinct", bytes), ps_lists(st, "distinct_lists", 0);
       launch_key_lists(d, l1, l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), ds.counters.as<unsigned long long>(),
                        st->stream);
-      ds.fp_staged = true;
       ds.retained.push_back(keep);  // (a DEVICE view, or a staged one looked at before the update returns)
       return TGX_OK;
     }
@@ -945,6 +870,91 @@ tgx_status retained_numeric_view(tgx_state *st, const tgx_column &col, std::vect
   return TGX_OK;
 }
 
+}  // namespace
+
+// `orig`: the caller's own view of the column when `c` is a per-update staging copy of a DEVICE column (a 4-byte
+// numeric column widened for this pass): what a key set retains for a later repair must outlive the update
+// `facts`: what the host knows of the column in this batch; `prep`: the numeric pass as distinct_prepare_numeric shaped it
+tgx_status distinct_update(tgx_state *st, size_t slot, const tgx_column &c, const BatchKeyFacts &facts,
+                           const NumericPrep &prep, tgx_error *err, const std::vector<DictGather> *gathers,
+                           int stats_slot, const tgx_column *orig) {
+  const DistinctTask &task = st->plan->distinct[slot];
+  DistinctState &ds = st->distinct[slot];
+  const bool mult = task.multiplicity;
+  if (is_any_string(c.type)) {
+    // values are reduced to 128-bit fingerprints on the fly (kernels/distinct128.hip)
+    ds.col_type = c.type;
+    ds.total_rows += c.length;
+    if (c.length == 0) return TGX_OK;
+    if (ds.fp_staged) TGX_TRY(distinct_resolve(st, slot, err));  // a second batch: the table takes over
+    // (an exact set takes the lists only over the caller's own DEVICE buffers, which outlive the update: its records
+    //  refer to rows, and what turns the lists into a table later needs the rows' bytes)
+    const bool exact_lists_ok = orig && orig->mem == TGX_MEM_DEVICE && c.length < (int64_t)1 << 32;
+    if (ds.mode == DistinctMode::kUndecided && (!ds.exact || exact_lists_ok) && fp_lists_fit(c))
+      return fp_lists_update(st, slot, c, err);
+    if (ds.mode == DistinctMode::kUndecided) {
+      ds.mode = DistinctMode::kHash;
+      ds.wide = true;
+    }
+    ProfScope ps(st, "distinct", 0);
+    return table_insert_utf8(st, slot, c, facts.data_bytes, err);
+  }
+  if (c.type == TGX_DICT32_UTF8) {
+    // string work once per dictionary entry: count references per entry, then insert the fingerprints of the
+    // referenced entries -- identical set contents to the plain Utf8 path (kernels/dict.hip)
+    const tgx_column &dict = *c.dictionary;
+    ds.col_type = c.type;
+    ds.total_rows += c.length;
+    if (c.length == 0 || dict.length == 0) return TGX_OK;
+    if (ds.mode == DistinctMode::kUndecided) {
+      ds.mode = DistinctMode::kHash;
+      ds.wide = true;
+    }
+    TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)std::min<int64_t>(c.length, dict.length), err));
+    const size_t uw = dict_usage_words(dict.length);
+    HIP_TRY(ds.dict_usage.reserve(2 * uw * 4 + 16));
+    const size_t scratch = dict_usage_scratch_bytes(c.length, dict.length, mult ? 1 : 0, g_ctx.n_cu);
+    if (scratch)
+      HIP_TRY(ds.dict_scratch.reserve(scratch));
+    else
+      HIP_TRY(hipMemsetAsync(ds.dict_usage.p, 0, 2 * uw * 4, st->stream));  // the global-atomics path accumulates
+    uint32_t *u_seen = ds.dict_usage.as<uint32_t>(), *u_twice = u_seen + uw;
+    ProfScope ps(st, "distinct", 0);
+    if (gathers && !gathers->empty() && scratch) {
+      // the column's pattern / length checks ride on this pass: the indices are read once
+      const uint8_t *hits[4];
+      unsigned long long *pc[4];
+      int32_t niv[4];
+      const int k = (int)std::min<size_t>(gathers->size(), 4);
+      for (int i = 0; i < k; i++) {
+        hits[i] = (*gathers)[i].hits;
+        pc[i] = (*gathers)[i].counters;
+        niv[i] = (*gathers)[i].null_is_valid;
+      }
+      launch_dict_usage_fused((const int32_t *)c.values, c.validity, c.offset, c.length, dict.length, mult ? 1 : 0, k,
+                              hits, pc, niv, u_seen, u_twice, ds.dict_scratch.as<uint32_t>(),
+                              ds.counters.as<unsigned long long>(), g_ctx.n_cu, st->stream);
+    } else {
+      launch_dict_usage((const int32_t *)c.values, c.validity, c.offset, c.length, dict.validity, dict.offset,
+                        dict.length, mult ? 1 : 0, u_seen, u_twice, ds.dict_scratch.as<uint32_t>(),
+                        ds.counters.as<unsigned long long>(), g_ctx.n_cu, st->stream);
+    }
+    if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, dict, u_seen, facts.data_bytes, err));  // the referenced entries
+    launch_dict_insert(dict.offsets, dict.data, dict.validity, dict.offset, dict.length,
+                       dict.type == TGX_LARGE_UTF8, mult ? 1 : 0, u_seen, u_twice, hash_view(ds), st->plan->fp_key,
+                       ds.counters.as<unsigned long long>(), st->stream);
+    return TGX_OK;
+  }
+  if (!is_numeric(c.type))
+    return fail(err, TGX_UNSUPPORTED, "DISTINCT on column type %d is not supported yet", c.type);
+  ds.col_type = c.type;
+  ds.total_rows += c.length;
+  if (c.length == 0) return TGX_OK;
+  NumericPrep ready = prep;  // (decided before the scan of this batch was queued: tgx_update)
+  if (!ready.prepared) TGX_TRY(distinct_prepare_numeric(st, slot, c, facts, &ready, err));
+  return distinct_run_numeric(st, slot, c, ready, stats_slot, err, orig);
+}
+
 // The host is about to look at the key set (counts, export, exchange, merge) or the caller may release the batches:
 // keys that fell outside a sampled range are brought in now.  The bitmap moves into a hash set and the retained
 // batches are walked once more for their outliers only (disjoint from the bitmap's keys, so multiplicities stay right).
@@ -970,36 +980,19 @@ tgx_status tgx::distinct_resolve(tgx_state *st, size_t slot, tgx_error *err) {
         std::vector<const tgx_column *> cols;
         for (const tgx_column &col : ds.retained) cols.push_back(&col);
         TupleDesc d;
-        TGX_TRY(tuple_desc_of(cols, mult, &d, err));
-        d.key = st->plan->fp_key;
-        TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)d.length, err));
-        if (ds.exact) {
-          TGX_TRY(key_store_measure_begin(st, ds, (uint64_t)d.length, err));
-          launch_exact_measure_tuple(d, ds.key_cursor.as<unsigned long long>() + 1, st->stream);
-          TGX_TRY(key_store_reserve_measured(st, ds, err));
+        TGX_TRY(tuple_desc_of(st, cols, mult, &d, err));
+        TGX_TRY(table_insert_tuple(st, slot, d, err));
+      } else {
+        for (const tgx_column &kept : ds.retained) {
+          tgx_column col;
+          TGX_TRY(retained_numeric_view(st, kept, widened, &col, err));
+          if (ds.wide) {  // (no flush's byte count describes a retained batch: an exact set measures it)
+            TGX_TRY(table_insert_utf8(st, slot, col, -1, err));
+            continue;
+          }
+          TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)col.length, err));  // a numeric key column
+          launch_distinct_hash(numeric_desc(col, mult), hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
         }
-        launch_distinct_tuple(d, hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
-      } else
-      for (const tgx_column &kept : ds.retained) {
-        tgx_column col;
-        TGX_TRY(retained_numeric_view(st, kept, widened, &col, err));
-        TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)col.length, err));
-        if (!ds.wide) {  // a numeric key column
-          DistinctColDesc d;
-          d.values = col.values;
-          d.validity = col.validity;
-          d.offset = col.offset;
-          d.length = col.length;
-          d.want_multiplicity = mult ? 1 : 0;
-          d.pad = 0;
-          launch_distinct_hash(d, hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
-          continue;
-        }
-        if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, col, err));
-        const bool view = col.type == TGX_UTF8_VIEW;
-        launch_distinct_utf8(col.offsets, col.data, view ? col.values : nullptr, view ? col.variadic : nullptr,
-                             col.validity, col.offset, col.length, col.type == TGX_LARGE_UTF8, mult ? 1 : 0,
-                             hash_view(ds), st->plan->fp_key, ds.counters.as<unsigned long long>(), st->stream);
       }
     } else if (exact_lists) {
       // the batch is gone (tgx_finalize handed it back): the keys go on as their 128-bit fingerprints
@@ -1051,14 +1044,7 @@ tgx_status tgx::distinct_resolve(tgx_state *st, size_t slot, tgx_error *err) {
   for (const tgx_column &kept : ds.retained) {
     tgx_column col;
     TGX_TRY(retained_numeric_view(st, kept, widened, &col, err));
-    DistinctColDesc d;
-    d.values = col.values;
-    d.validity = col.validity;
-    d.offset = col.offset;
-    d.length = col.length;
-    d.want_multiplicity = mult ? 1 : 0;
-    d.pad = 0;
-    launch_distinct_outliers(d, old_base, old_range, hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
+    launch_distinct_outliers(numeric_desc(col, mult), old_base, old_range, hash_view(ds), ds.counters.as<unsigned long long>(), st->stream);
   }
   HIP_TRY(hipMemsetAsync(ds.counters.as<unsigned long long>() + kCntOutOfRange, 0, sizeof(unsigned long long), st->stream));
   HIP_TRY(hipStreamSynchronize(st->stream));
@@ -1095,6 +1081,7 @@ tgx_status tgx::distinct_resolve_all(tgx_state *st, tgx_error *err) {
   }
   return TGX_OK;
 }
+
 
 // ------------------------------------------------------------------------------------------------
 // distinct: export / import / merge
@@ -1251,6 +1238,7 @@ extern "C" tgx_status tgx_distinct_import(const tgx_plan *plan, tgx_state *st, s
   return tgx::abi_exception(err);
 }
 
+namespace {
 tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot,
                                    tgx_error *err) {
   if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
@@ -1259,6 +1247,7 @@ tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_ind
   *slot = (size_t)plan->bind[spec_index].slot;
   return TGX_OK;
 }
+}  // namespace
 
 extern "C" tgx_status tgx_distinct_range_hint(const tgx_plan *plan, tgx_state *st, size_t spec_index, int64_t lo,
                                               int64_t hi, tgx_error *err) try {
@@ -1433,4 +1422,3 @@ extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state 
 } catch (...) {
   return tgx::abi_exception(err);
 }
-

@@ -348,11 +348,9 @@ struct DistinctState {
   uint64_t key_pending_region = 0;
   uint32_t key_pending_waves = 0;
   // host-side bound on the store's fill (the cursor lives on the device): a batch whose worst case the host can bound --
-  // a coalesced flush of a Utf8 / dictionary column: its bytes were counted as they were noted (`batch_data_bytes`) --
+  // a coalesced flush of a Utf8 / dictionary column: its bytes were counted as they were noted (BatchKeyFacts) --
   // reserves against this bound and waits for nothing; only when the bound no longer fits is the real fill read back
   uint64_t key_words_ub = 0;
-  bool batch_bytes_known = false;
-  int64_t batch_data_bytes = 0;
   uint64_t capacity = 0;         // slots (power of two)
   uint64_t rows_upper_bound = 0; // host-side bound on keys in the table
   // counters (device) + host-side totals
@@ -385,13 +383,6 @@ struct DistinctState {
   // repair walks the retained batches for the keys outside the range, so a bitmap grown over them in the meantime
   // would make it skip them (a stream of HOST and DEVICE batches of growing ids lost a whole batch that way).
   bool outliers_possible = false;
-  // the value range of the batch about to be run, when the host knows it (a coalesced flush of HOST windows)
-  bool batch_range_known = false;
-  int64_t batch_lo = 0, batch_hi = 0;
-  // the batch about to be run is a coalesced flush with DEVICE windows of this Int64 key column: the host has not seen
-  // its values, so -- while that can still keep the key set on the bitmap -- the device takes the flush's exact
-  // MIN / MAX before the pass (distinct_sample_all: one wait, the one a sample would cost)
-  bool flush_device_keys = false;
   // the views, and for each the coalescing region set it points into (-1: the caller's own memory)
   struct Retained {
     std::vector<tgx_column> cols;
@@ -411,8 +402,6 @@ struct DistinctState {
     const tgx_column &operator[](size_t i) const { return cols[i]; }
   } retained;
   DevBuf sample;         // DistinctSample
-  bool sample_ready = false;  // `sample_host` holds this batch's sample (tgx_update reads all tasks' samples at once)
-  DistinctSample sample_host;
   DevBuf stat_partials;  // ScanPartial per workgroup of the partition pass (PartitionParams::stats) + one for outliers
   DevBuf outlier_stats;  // OutlierStats
   // A big first Utf8 batch leaves its key set as partitioned fingerprint lists (kernels/distinct128.hip, fp_*): the

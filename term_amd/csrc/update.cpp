@@ -384,6 +384,7 @@ struct BatchFusion {
   std::vector<char> kll_fused, como_fused;                // per KLL / COMOMENTS task: it rides on the scan
   std::vector<char> distinct_idle;                        // per key set: the HLL lane answers for it
   std::vector<FusedPair> fused_pairs;
+  std::vector<BatchKeyFacts> key_facts;  // per key set: what the host knows of its column in this batch
   std::vector<NumericPrep> dprep;        // per key set: the shape of its numeric pass
   std::vector<int> stats_by_partition;   // per scan task: the key set whose pass brings its aggregates, or -1
   std::vector<char> distinct_done;       // per key set: updated before `keys_ready`
@@ -463,7 +464,8 @@ tgx_status stage_batch(const tgx_plan *plan, tgx_state *st, const tgx_column *co
 // aggregates and the co-moments from one read.  A KLL task of a batch big enough to be sampled hands its sampler to the
 // scan of its column (scan_kll_kernel / the pair kernel).  So a suite with range, quantile and correlation checks on
 // the same columns reads them once.
-BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows) {
+BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, int64_t nrows,
+                          const std::vector<BatchKeyFacts> *facts) {
   const int n_plan_cols = plan->n_columns_needed;
   BatchFusion f;
   f.kll_on_col.assign(n_plan_cols, -1);
@@ -472,6 +474,7 @@ BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column 
   f.kll_fused.assign(plan->kll.size(), 0);
   f.como_fused.assign(plan->como.size(), 0);
   f.distinct_idle.assign(plan->distinct.size(), 0);
+  f.key_facts = facts ? *facts : std::vector<BatchKeyFacts>(plan->distinct.size());
   f.dprep.resize(plan->distinct.size());
   f.stats_by_partition.assign(plan->scan.size(), -1);
   f.distinct_done.assign(plan->distinct.size(), 0);
@@ -529,7 +532,7 @@ BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column 
 tgx_status early_key_passes(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, const tgx_column *columns,
                             BatchFusion *f, tgx_error *err) {
   update_mark("fused");
-  TGX_TRY(distinct_sample_all(st, dev, err));
+  TGX_TRY(distinct_sample_all(st, dev, f->key_facts, err));
   update_mark("sampled");
   auto numeric_pass = [&](size_t q) {
     const DistinctTask &t = plan->distinct[q];
@@ -538,7 +541,7 @@ tgx_status early_key_passes(const tgx_plan *plan, tgx_state *st, const tgx_colum
   for (size_t q = 0; q < plan->distinct.size(); q++) {
     const DistinctTask &t = plan->distinct[q];
     if (!numeric_pass(q)) continue;
-    TGX_TRY(distinct_prepare_numeric(st, q, dev[t.column], &f->dprep[q], err));
+    TGX_TRY(distinct_prepare_numeric(st, q, dev[t.column], f->key_facts[q], &f->dprep[q], err));
     if (f->dprep[q].partitioned && dev[t.column].type == TGX_INT64 && t.scan_slot >= 0 &&
         !plan->scan[t.scan_slot].variance && f->pair_of_col[t.column] < 0 && f->kll_on_col[t.column] < 0)
       f->stats_by_partition[t.scan_slot] = (int)q;
@@ -547,7 +550,7 @@ tgx_status early_key_passes(const tgx_plan *plan, tgx_state *st, const tgx_colum
   for (size_t q = 0; q < plan->distinct.size(); q++) {
     const DistinctTask &t = plan->distinct[q];
     if (!numeric_pass(q)) continue;
-    TGX_TRY(distinct_update(st, q, dev[t.column], err, nullptr, &f->dprep[q], f->stats_slot(plan, q),
+    TGX_TRY(distinct_update(st, q, dev[t.column], f->key_facts[q], f->dprep[q], err, nullptr, f->stats_slot(plan, q),
                             &columns[t.column]));
     f->distinct_done[q] = 1;
   }
@@ -876,7 +879,7 @@ tgx_status late_key_sets(const tgx_plan *plan, tgx_state *st, const tgx_column *
         g = &it->second;
         fuse_done[col] = true;
       }
-      TGX_TRY(distinct_update(st, s, dev[col], err, g, &f.dprep[s], f.stats_slot(plan, s), &columns[col]));
+      TGX_TRY(distinct_update(st, s, dev[col], f.key_facts[s], f.dprep[s], err, g, f.stats_slot(plan, s), &columns[col]));
     } else {
       TGX_TRY(distinct_tuple_update(st, s, dev, err, columns));
     }
@@ -913,15 +916,16 @@ tgx_status finish_batch(tgx_state *st, const StagedBatch &b, tgx_error *err) {
 
 }  // namespace
 
-// one batch through the fused pass: device views of its columns, then every kernel of the plan
+// one batch through the fused pass: device views of its columns, then every kernel of the plan.  `facts`: what a
+// coalesced flush knows of each key set's column (nullptr: nothing)
 tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *columns, int64_t nrows,
-                       tgx_error *err) {
+                       tgx_error *err, const std::vector<BatchKeyFacts> *facts) {
   TGX_TRY(state_init_device(st, err));
   StagedBatch b;
   TGX_TRY(stage_batch(plan, st, columns, &b, err));
   if (nrows > 0) {
     const tgx_column *dev = b.dev.data();
-    BatchFusion f = decide_fusion(plan, st, dev, nrows);
+    BatchFusion f = decide_fusion(plan, st, dev, nrows, facts);
     TGX_TRY(early_key_passes(plan, st, dev, columns, &f, err));
     TGX_TRY(scan_columns(plan, st, dev, nrows, f, err));
     TGX_TRY(count_validity(plan, st, dev, err));

@@ -259,6 +259,23 @@ def test_partners_in_different_batches_and_store_growth(pairs):
     assert res[0].distinct == want.distinct - len(pairs)
 
 
+def test_flush_after_the_lists_sizes_the_store_for_the_retained_batch(monkeypatch):
+    """an exact set on the lists of a big DEVICE batch of long values, then small HOST batches: the flush that brings
+    them moves the retained batch into the table first, and the room for ITS keys is measured on it -- the byte count
+    the flush noted describes the flush only (sized by it, the store filled up and finalize failed)"""
+    monkeypatch.setenv("TGX_FP_LISTS_MIN_ROWS", "1000")
+    rng = np.random.default_rng(29)
+    n = 100_000
+    tails = rng.integers(ord("a"), ord("z") + 1, size=(n, 193), dtype=np.uint8)
+    keys = [i - 3 if i % 10 == 3 else i for i in range(n)]  # (a tenth of the rows repeat one)
+    big = [None if i % 97 == 0 else b"%07d" % k + tails[k].tobytes() for i, k in enumerate(keys)]
+    smalls = [[None if i % 31 == 0 else b"k%d" % rng.integers(0, 6_000) for i in range(8192)] for _ in range(3)]
+    batches = [[column_of(big)[0]]] + [[column_of(s, device=False)[0]] for s in smalls]
+    res, st, _ = run([spec(T.DISTINCT, 0, flags=T.FLAG_MULTIPLICITY | T.FLAG_EXACT_KEYS)], batches, profile=True)
+    assert lists_ran(st) == 1
+    check(res[0], orc.distinct_utf8(*orc.utf8_from_list(big + [v for s in smalls for v in s])))
+
+
 @pytest.mark.parametrize("device", [True, False])
 def test_utf8view(pairs, device):
     from test_gpu_utf8view import view_column
