@@ -42,7 +42,8 @@ inline tgx_status abi_exception(tgx_error *err) {
 }
 
 // ---- kernel launchers (defined in kernels/*.hip) ----------------------------------------------
-void launch_scan_pivot(const ScanLaunch &L, int n_cols, double *d_pivots, int32_t *d_pivot_set, hipStream_t stream);
+void launch_scan_pivot(const ScanLaunch &L, int n_cols, double *d_pivots, int32_t *d_pivot_set, PivotSearch *d_search,
+                       hipStream_t stream);
 void launch_scan_main_only(const ScanLaunch &L, int n_cols, int blocks_per_col, ScanPartial *d_partials,
                            ScanAcc *d_accs, hipStream_t stream);
 void launch_scan_kll(const ScanLaunch &L, int n_cols, int blocks_per_col, size_t lds_bytes, ScanPartial *d_partials,
@@ -51,7 +52,7 @@ void launch_scan_pairs(const ScanPairLaunch &L, int n_pairs, int blocks_per_pair
                        ScanPartial *d_partials, void *d_como_partials, const ComomentAcc *d_como_accs,
                        hipStream_t stream);
 void launch_scan_hll(const ScanLaunch &L, int n_cols, int blocks_per_col, ScanPartial *d_partials, hipStream_t stream);
-void launch_como_pivot(const ComomentLaunch &L, int n_pairs, ComomentAcc *d_accs, hipStream_t stream);
+void launch_como_pivot(const ComomentLaunch &L, int n_pairs, ComomentAcc *d_accs, PivotSearch *d_search, hipStream_t stream);
 void launch_comoments_reduce(const ComomentLaunch &L, int n_pairs, int blocks_per_pair, const void *d_partials,
                              ComomentAcc *d_accs, hipStream_t stream);
 // mode: 0 Int32, 1 Float32, 2 Int8, 3 Int16, 4 UInt8, 5 UInt16, 6 UInt32, 7 Boolean (bits) -> Int64 / Float64
@@ -569,6 +570,7 @@ struct tgx_state {
 
   // device accumulators
   tgx::DevBuf d_scan_acc, d_count_acc, d_como_acc, d_pivots, d_pivot_set;
+  tgx::DevBuf d_pivot_search;  // PivotSearch: [scan slots] then [COMOMENTS tasks]
   tgx::DevBuf d_scan_identity;  // (unused since round 5: state_reset_kernel writes the identities itself)
   struct Widen {
     const void *src;
@@ -576,7 +578,6 @@ struct tgx_state {
     int64_t n;
     int mode;  // widen_mode()
   };
-  std::vector<int> como_pivot_tries;  // per COMOMENTS task: batches that offered the pivot kernel a look (<= 4)
   std::vector<Widen> pending_widen;  // TGX_INT32 / TGX_FLOAT32 windows of the current update (stage_column)
   tgx::DevBuf d_distinct_counters;  // [distinct task][kNumDistinctCounters]: every DistinctState::counters is a slice
   // per-update scratch

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "pivot_search.h"
 
 namespace tgx {
 
@@ -179,55 +180,133 @@ __global__ __launch_bounds__(64) void comoments_reduce_kernel(
 }
 
 // Picks the pivots of a pair: the means of (up to) 4096 evenly spread rows of the batch that have both values, finite.
-// Any finite pivot gives the right answer; one near the data keeps S(x'x') - S(x')^2 / n well conditioned.  Pivots are
-// fixed once rows have been folded in (acc.n > 0): every batch of a state is summed about the same pair.
-__global__ __launch_bounds__(256) void como_pivot_kernel(const ComomentLaunch L, ComomentAcc *__restrict__ accs) {
-  const ComomentColDesc d = L.pairs[blockIdx.x];
-  ComomentAcc &acc = accs[L.acc_index[blockIdx.x]];
-  if (acc.n > 0 || d.length <= 0) return;
+// Any finite pivot gives the right answer; one near the data keeps S(x'x') - S(x')^2 / n well conditioned.  When the
+// sample holds no such row, the batch's first one is searched for by the whole grid (pivot_search.h); a mean that
+// overflows is replaced by one of the pairs it was taken over.  Pivots are fixed once rows have been folded in
+// (acc.n > 0): every batch of a state is summed about the same pair, and the kernel returns at once.
+// grid = (search workgroups, pairs); workgroup 0 of a pair takes the sample.
+__global__ __launch_bounds__(256) void como_pivot_kernel(const ComomentLaunch L, ComomentAcc *__restrict__ accs,
+                                                         PivotSearch *__restrict__ search) {
+  const ComomentColDesc d = L.pairs[blockIdx.y];
+  const int task = L.acc_index[blockIdx.y];
+  ComomentAcc &acc = accs[task];
+  if (acc.n > 0 || d.length <= 0) return;  // (the same in every workgroup of the pair: n moves only in later kernels)
   global_i64_ptr x = (global_i64_ptr)(uintptr_t)((const int64_t *)d.x + d.xoff);
   global_i64_ptr y = (global_i64_ptr)(uintptr_t)((const int64_t *)d.y + d.yoff);
   global_u8_ptr xv = (global_u8_ptr)(uintptr_t)d.xv;
   global_u8_ptr yv = (global_u8_ptr)(uintptr_t)d.yv;
-  const int64_t samples = d.length < 4096 ? d.length : 4096;
-  const int64_t step = d.length / samples;
-  double sx = 0.0, sy = 0.0;
-  int cnt = 0;
-  for (int64_t k = threadIdx.x; k < samples; k += 256) {
-    const int64_t i = k * step;
-    if (!cm_valid(xv, d.xoff + i) || !cm_valid(yv, d.yoff + i)) continue;
-    const double a = d.x_is_float ? __longlong_as_double(x[i]) : (double)x[i];
-    const double b = d.y_is_float ? __longlong_as_double(y[i]) : (double)y[i];
-    if (a - a != 0.0 || b - b != 0.0) continue;  // inf / NaN
-    sx += a;
-    sy += b;
-    cnt++;
-  }
-  __shared__ double s_x[256], s_y[256];
+  auto xval = [&](int64_t i) { return d.x_is_float ? __longlong_as_double(x[i]) : (double)x[i]; };
+  auto yval = [&](int64_t i) { return d.y_is_float ? __longlong_as_double(y[i]) : (double)y[i]; };
+  __shared__ double s_x[256], s_y[256], s_ox[256], s_oy[256];
   __shared__ int s_n[256];
-  s_x[threadIdx.x] = sx;
-  s_y[threadIdx.x] = sy;
-  s_n[threadIdx.x] = cnt;
+  __shared__ int s_done;
+  if (threadIdx.x == 0) s_done = acc.pivot_set;  // (workgroup 0 of this launch may set it while others start)
   __syncthreads();
-  if (threadIdx.x != 0) return;
-  double tx = 0.0, ty = 0.0;
-  int k = 0;
-  for (int i = 0; i < 256; i++) {
-    tx += s_x[i];
-    ty += s_y[i];
-    k += s_n[i];
+  if (blockIdx.x == 0 && !s_done) {
+    const int64_t samples = d.length < 4096 ? d.length : 4096;
+    const int64_t step = d.length / samples;
+    double sx = 0.0, sy = 0.0, ox = 0.0, oy = 0.0;
+    int cnt = 0;
+    for (int64_t k = threadIdx.x; k < samples; k += 256) {
+      const int64_t i = k * step;
+      if (!cm_valid(xv, d.xoff + i) || !cm_valid(yv, d.yoff + i)) continue;
+      const double a = xval(i);
+      const double b = yval(i);
+      if (a - a != 0.0 || b - b != 0.0) continue;  // inf / NaN
+      if (cnt == 0) {
+        ox = a;
+        oy = b;
+      }
+      sx += a;
+      sy += b;
+      cnt++;
+    }
+    s_x[threadIdx.x] = sx;
+    s_y[threadIdx.x] = sy;
+    s_ox[threadIdx.x] = ox;
+    s_oy[threadIdx.x] = oy;
+    s_n[threadIdx.x] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double tx = 0.0, ty = 0.0, fx = 0.0, fy = 0.0;
+      int k = 0;
+      for (int i = 0; i < 256; i++) {
+        if (k == 0 && s_n[i] > 0) {
+          fx = s_ox[i];
+          fy = s_oy[i];
+        }
+        tx += s_x[i];
+        ty += s_y[i];
+        k += s_n[i];
+      }
+      if (k > 0) {
+        tx /= (double)k;
+        ty /= (double)k;
+        if (tx - tx != 0.0 || ty - ty != 0.0) {  // the sample's sum overflowed: one of its pairs
+          tx = fx;
+          ty = fy;
+        }
+        acc.px = tx;
+        acc.py = ty;
+        acc.pivot_set = 1;
+        s_done = 1;
+      }
+    }
+    __syncthreads();
   }
-  if (k == 0) return;
-  tx /= (double)k;
-  ty /= (double)k;
-  if (tx - tx != 0.0 || ty - ty != 0.0) return;  // the sample's sum overflowed: stay with what is there
-  acc.px = tx;
-  acc.py = ty;
+  if (blockIdx.x > 0 && !s_done) {  // one valid finite pair among the sample's rows settles it
+    const int64_t samples = d.length < 4096 ? d.length : 4096;
+    const int64_t k = threadIdx.x, i = k * (d.length / samples);
+    bool hit = false;
+    if (k < samples && cm_valid(xv, d.xoff + i) && cm_valid(yv, d.yoff + i)) {
+      const double a = xval(i), b = yval(i);
+      hit = a - a == 0.0 && b - b == 0.0;
+    }
+    if (__syncthreads_or(hit)) return;
+  }
+  if (!s_done) {
+    int64_t lo, hi;
+    pivot_search_stretch(d.length, &lo, &hi);
+    const int64_t xend = (d.xoff + d.length + 7) >> 3, yend = (d.yoff + d.length + 7) >> 3;
+    const int64_t row = first_valid_finite_row(
+        lo, hi,
+        [&](int64_t r) {
+          return validity_bits64(d.xv, d.xoff + r, xend) & validity_bits64(d.yv, d.yoff + r, yend);
+        },
+        [&](int64_t i) {
+          const double a = xval(i), b = yval(i);
+          return a - a == 0.0 && b - b == 0.0;
+        });
+    pivot_search_offer(&search[task], row);
+  }
+}
+
+// after como_pivot_kernel: a pair the sample left without pivots takes the search's row; the slot is cleared for the
+// next launch.  grid = pairs, one wave each.
+__global__ __launch_bounds__(64) void como_pivot_finish_kernel(const ComomentLaunch L, ComomentAcc *__restrict__ accs,
+                                                               PivotSearch *__restrict__ search) {
+  const ComomentColDesc d = L.pairs[blockIdx.x];
+  const int task = L.acc_index[blockIdx.x];
+  ComomentAcc &acc = accs[task];
+  if (acc.n > 0 || d.length <= 0 || threadIdx.x != 0) return;
+  const unsigned long long best = search[task].best;
+  if (!best) return;
+  search[task].best = 0;
+  if (acc.pivot_set) return;
+  const int64_t i = (int64_t)~best;
+  const int64_t xb = ((const int64_t *)d.x)[d.xoff + i], yb = ((const int64_t *)d.y)[d.yoff + i];
+  acc.px = d.x_is_float ? __longlong_as_double(xb) : (double)xb;
+  acc.py = d.y_is_float ? __longlong_as_double(yb) : (double)yb;
   acc.pivot_set = 1;
 }
 
-void launch_como_pivot(const ComomentLaunch &L, int n_pairs, ComomentAcc *d_accs, hipStream_t stream) {
-  hipLaunchKernelGGL(como_pivot_kernel, dim3(n_pairs), dim3(256), 0, stream, L, d_accs);
+void launch_como_pivot(const ComomentLaunch &L, int n_pairs, ComomentAcc *d_accs, PivotSearch *d_search,
+                       hipStream_t stream) {
+  int64_t longest = 0;
+  for (int k = 0; k < n_pairs; k++) longest = L.pairs[k].length > longest ? L.pairs[k].length : longest;
+  hipLaunchKernelGGL(como_pivot_kernel, dim3(pivot_search_blocks(longest), n_pairs), dim3(256), 0, stream, L, d_accs,
+                     d_search);
+  hipLaunchKernelGGL(como_pivot_finish_kernel, dim3(n_pairs), dim3(64), 0, stream, L, d_accs, d_search);
 }
 
 size_t comoments_partial_bytes() { return sizeof(ComomentPartial); }

@@ -188,6 +188,15 @@ struct StateResetArgs {
   uint32_t n_ident;
 };
 
+// Scratch of the pivot kernels' grid-wide search for a first valid row (kernels/pivot_search.h): one per scan slot and
+// one per COMOMENTS task, zero between launches (the search's finishing kernel clears it again).
+struct PivotSearch {
+  unsigned long long best;  // ~(first row found by this launch); 0: none
+  unsigned long long pad;
+};
+constexpr int64_t kPivotSearchRows = 1 << 18;  // rows per workgroup of the search (grids of at most kPivotSearchBlocks)
+constexpr int kPivotSearchBlocks = 4096;
+
 __host__ __device__ inline int64_t f64_total_key(int64_t bits) {
   return bits ^ (int64_t)(((uint64_t)(bits >> 63)) >> 1);
 }

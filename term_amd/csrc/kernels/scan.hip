@@ -19,6 +19,7 @@
 
 #include "device_types.h"
 #include "distinct_types.h"
+#include "pivot_search.h"
 
 namespace tgx {
 
@@ -481,9 +482,18 @@ __device__ __forceinline__ void scan_fold(ScanAcc &s, const LaneAcc &a, const Sc
     // batch moments about the pivot -> (n, mean, M2), then Chan's pairwise merge
     const double pivot = c.pivot ? *c.pivot : 0.0;
     const double nb = (double)a.cnt;
-    const double mean_b = pivot + a.s1 / nb;
+    double mean_b = pivot + a.s1 / nb;
     double m2_b = a.s2 - a.s1 * a.s1 / nb;
     if (m2_b < 0.0) m2_b = 0.0;
+    if (a.mn == a.mx) {
+      // one value throughout the batch: M2 = 0 whatever the pivot (a pivot a rounding away from values near 1e305
+      // leaves deviations whose squares overflow), as Welford's update gives
+      const double v = c.is_float ? __longlong_as_double(f64_total_key(a.mn)) : (double)a.mn;
+      if (v - v == 0.0) {
+        mean_b = v;
+        m2_b = 0.0;
+      }
+    }
     if (s.var_n == 0) {
       s.var_n = a.cnt;
       s.var_mean = mean_b;
@@ -1194,55 +1204,120 @@ __global__ __launch_bounds__(64) void scan_reduce_kernel(const ScanLaunch L,
   if (lane == 0) scan_fold(accs[L.acc_index[col]], a, c);
 }
 
-// Picks the variance pivot of a column: the mean of (up to) the first 256 valid values of the first
-// batch.  Any finite pivot gives the right answer; one near the data keeps s2 - s1^2/n well
-// conditioned.  A pivot that is already set (later batches) is kept.
+// Picks the variance pivot of a column: the mean of the valid, finite values among the first (up to) 4096 rows of the
+// first batch that has any.  Any finite pivot gives the right answer; one near the data keeps s2 - s1^2/n well
+// conditioned.  When those rows hold none (a column sorted NULLS FIRST), 4096 rows spread evenly over the batch are
+// looked at, and when they hold none either, the batch's first valid finite row is searched for by the whole grid
+// (pivot_search.h).  A mean that overflows is replaced by one of the values it was taken over.  A pivot that is
+// already set (later batches) is kept: the kernel then returns at once.
+// grid = (search workgroups, columns); workgroup 0 of a column takes the two looks.
 __global__ __launch_bounds__(256) void scan_pivot_kernel(const ScanLaunch L,
                                                           double *__restrict__ pivots,
-                                                          int32_t *__restrict__ pivot_set) {
-  const ScanColDesc c = L.cols[blockIdx.x];
-  if (!c.want_variance) return;
-  const int slot = L.acc_index[blockIdx.x];
-  if (pivot_set[slot]) return;
-  __shared__ double s_sum[256];
+                                                          int32_t *__restrict__ pivot_set,
+                                                          PivotSearch *__restrict__ search) {
+  const ScanColDesc c = L.cols[blockIdx.y];
+  if (!c.want_variance || c.length <= 0) return;  // (the same in every workgroup of the column)
+  const int slot = L.acc_index[blockIdx.y];
+  __shared__ double s_sum[256], s_one[256];
   __shared__ int s_cnt[256];
-  const int64_t n = c.length < 4096 ? c.length : 4096;
-  double sum = 0.0;
-  int cnt = 0;
+  __shared__ int s_done;
   global_i64_ptr vals = (global_i64_ptr)(uintptr_t)((const int64_t *)c.values + c.offset);
   global_i32_ptr vals32 = (global_i32_ptr)(uintptr_t)((const int32_t *)c.values + c.offset);
   global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)c.validity;
-  for (int64_t i = threadIdx.x; i < n; i += 256) {
-    bool valid = true;
-    if (c.validity) {
-      int64_t b = c.offset + i;
-      valid = (vbits[b >> 3] >> (b & 7)) & 1;
-    }
-    if (!valid) continue;
-    double x;
-    if (c.elem32)
-      x = c.is_float ? (double)__int_as_float(vals32[i]) : (double)vals32[i];
-    else
-      x = c.is_float ? __longlong_as_double(vals[i]) : (double)vals[i];
-    if (x - x != 0.0) continue;  // skip inf / nan
-    sum += x;
-    cnt++;
-  }
-  s_sum[threadIdx.x] = sum;
-  s_cnt[threadIdx.x] = cnt;
+  auto valid = [&](int64_t i) {
+    if (!c.validity) return true;
+    const int64_t b = c.offset + i;
+    return ((vbits[b >> 3] >> (b & 7)) & 1) != 0;
+  };
+  auto value = [&](int64_t i) {
+    if (c.elem32) return c.is_float ? (double)__int_as_float(vals32[i]) : (double)vals32[i];
+    return c.is_float ? __longlong_as_double(vals[i]) : (double)vals[i];
+  };
+  if (threadIdx.x == 0) s_done = pivot_set[slot];  // (workgroup 0 of this launch may set it while others start)
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    int k = 0;
-    for (int i = 0; i < 256; i++) {
-      t += s_sum[i];
-      k += s_cnt[i];
+  const int64_t n = c.length < 4096 ? c.length : 4096;
+  // look 0: rows 0 .. n - 1; look 1: rows k * step, spread over the batch
+  for (int look = 0; look < 2 && blockIdx.x == 0 && !s_done; look++) {
+    const int64_t step = look == 0 ? 1 : c.length / n;
+    if (look == 1 && step == 1) break;  // (the same rows again)
+    double sum = 0.0, one = 0.0;
+    int cnt = 0;
+    for (int64_t k = threadIdx.x; k < n; k += 256) {
+      const int64_t i = k * step;
+      if (!valid(i)) continue;
+      const double x = value(i);
+      if (x - x != 0.0) continue;  // skip inf / nan
+      if (cnt == 0) one = x;
+      sum += x;
+      cnt++;
     }
-    if (k > 0) {
-      pivots[slot] = t / (double)k;
-      pivot_set[slot] = 1;
+    s_sum[threadIdx.x] = sum;
+    s_one[threadIdx.x] = one;
+    s_cnt[threadIdx.x] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = 0.0, first = 0.0;
+      int k = 0;
+      for (int i = 0; i < 256; i++) {
+        if (k == 0 && s_cnt[i] > 0) first = s_one[i];
+        t += s_sum[i];
+        k += s_cnt[i];
+      }
+      if (k > 0) {
+        double p = t / (double)k;
+        if (p - p != 0.0) p = first;  // the sum overflowed: one of the values, not 0
+        pivots[slot] = p;
+        pivot_set[slot] = 1;
+        s_done = 1;
+      }
     }
+    __syncthreads();
   }
+  if (blockIdx.x > 0 && !s_done) {  // look 0 reads rows 0 .. 4095: one of them valid and finite settles it
+    const int64_t i = threadIdx.x;
+    bool hit = false;
+    if (i < c.length && valid(i)) {
+      const double x = value(i);
+      hit = x - x == 0.0;
+    }
+    if (__syncthreads_or(hit)) return;
+  }
+  if (!s_done) {
+    int64_t lo, hi;
+    pivot_search_stretch(c.length, &lo, &hi);
+    const int64_t end_byte = (c.offset + c.length + 7) >> 3;
+    const int64_t row = first_valid_finite_row(
+        lo, hi, [&](int64_t r) { return validity_bits64((const uint8_t *)c.validity, c.offset + r, end_byte); },
+        [&](int64_t i) {
+          const double x = value(i);
+          return x - x == 0.0;
+        });
+    pivot_search_offer(&search[slot], row);
+  }
+}
+
+// after scan_pivot_kernel: a column the looks left without a pivot takes the value of the search's row; the slot is
+// cleared for the next launch.  grid = columns, one wave each.
+__global__ __launch_bounds__(64) void scan_pivot_finish_kernel(const ScanLaunch L, double *__restrict__ pivots,
+                                                                int32_t *__restrict__ pivot_set,
+                                                                PivotSearch *__restrict__ search) {
+  const ScanColDesc c = L.cols[blockIdx.x];
+  if (!c.want_variance || c.length <= 0 || threadIdx.x != 0) return;
+  const int slot = L.acc_index[blockIdx.x];
+  const unsigned long long best = search[slot].best;
+  if (!best) return;
+  search[slot].best = 0;
+  if (pivot_set[slot]) return;
+  const int64_t i = (int64_t)~best;
+  double x;
+  if (c.elem32)
+    x = c.is_float ? (double)__int_as_float(((const int32_t *)c.values)[c.offset + i])
+                   : (double)((const int32_t *)c.values)[c.offset + i];
+  else
+    x = c.is_float ? __longlong_as_double(((const int64_t *)c.values)[c.offset + i])
+                   : (double)((const int64_t *)c.values)[c.offset + i];
+  pivots[slot] = x;
+  pivot_set[slot] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1363,9 +1438,14 @@ void launch_widen32(const void *src, void *dst, int64_t n, int mode, int n_cu, h
 
 // ---------------------------------------------------------------------------------------------
 // host launchers (called from tgx_api.cpp); `n_cols` <= kMaxColsPerLaunch
-void launch_scan_pivot(const ScanLaunch &L, int n_cols, double *d_pivots, int32_t *d_pivot_set,
+void launch_scan_pivot(const ScanLaunch &L, int n_cols, double *d_pivots, int32_t *d_pivot_set, PivotSearch *d_search,
                        hipStream_t stream) {
-  hipLaunchKernelGGL(scan_pivot_kernel, dim3(n_cols), dim3(256), 0, stream, L, d_pivots, d_pivot_set);
+  int64_t longest = 0;
+  for (int k = 0; k < n_cols; k++)
+    if (L.cols[k].want_variance && L.cols[k].length > longest) longest = L.cols[k].length;
+  hipLaunchKernelGGL(scan_pivot_kernel, dim3(pivot_search_blocks(longest), n_cols), dim3(256), 0, stream, L, d_pivots,
+                     d_pivot_set, d_search);
+  hipLaunchKernelGGL(scan_pivot_finish_kernel, dim3(n_cols), dim3(64), 0, stream, L, d_pivots, d_pivot_set, d_search);
 }
 
 // d_accs != nullptr and blocks_per_col == 1: the kernel folds into the running states itself (no reduce launch)

@@ -535,6 +535,7 @@ static void state_reset_small(tgx_state *st) {
     zero(st->d_pivot_set.p, plan->scan.size() * sizeof(int32_t));
   }
   if (!plan->count.empty()) zero(st->d_count_acc.p, plan->count.size() * sizeof(CountAcc));
+  zero(st->d_pivot_search.p, (plan->scan.size() + plan->como.size()) * sizeof(PivotSearch));
   if (!plan->como.empty()) zero(st->d_como_acc.p, plan->como.size() * sizeof(ComomentAcc));
   zero(st->d_distinct_counters.p, st->distinct.size() * kNumDistinctCounters * sizeof(unsigned long long));
   if (a.n_zero || a.n_ident) launch_state_reset(a, st->stream);
@@ -556,6 +557,8 @@ tgx_status tgx::state_init_device(tgx_state *st, tgx_error *err) {
     HIP_TRY(st->d_pivot_set.reserve(plan->scan.size() * sizeof(int32_t)));
   }
   if (!plan->count.empty()) HIP_TRY(st->d_count_acc.reserve(plan->count.size() * sizeof(CountAcc)));
+  if (!plan->scan.empty() || !plan->como.empty())
+    HIP_TRY(st->d_pivot_search.reserve((plan->scan.size() + plan->como.size()) * sizeof(PivotSearch)));
   if (!plan->como.empty()) HIP_TRY(st->d_como_acc.reserve(plan->como.size() * sizeof(ComomentAcc)));
   if (!plan->hll.empty()) {
     HIP_TRY(st->d_hll.reserve(plan->hll.size() * (size_t)kHllRegisters));
@@ -695,7 +698,6 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   kll_state_reset(st);
   regex_state_reset(st);
   spearman_state_reset(st);
-  st->como_pivot_tries.clear();
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
   st->hll_mode.assign(plan->hll.size(), 0);
   if (st->device_ready && st->d_hll.p)

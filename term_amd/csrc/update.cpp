@@ -217,19 +217,17 @@ int scan_blocks_for(const ScanColDesc &d, int n_cols_in_launch, int per_cu) {
   return (int)want;
 }
 
-// The pivots of the pairs of one launch (kernels/comoments.hip, como_pivot_kernel): picked from the first batches that
-// bring rows -- the kernel leaves a pair alone once rows have been folded into it; after a few batches nothing is
-// launched any more (a stream of 8192-row batches must not pay a launch per batch for a decision long taken).
+// The pivots of the pairs of one launch (kernels/comoments.hip, como_pivot_kernel): launched for every pass that brings
+// rows, like the scan's pivot kernel -- the kernel returns at once for a pair that has rows folded in, so a pair whose
+// first batches are all NULL still gets its pivot from the first batch that has data.  (A stream of 8192-row batches is
+// coalesced: one launch per flush, not per batch.)
 tgx_status como_pivots(tgx_state *st, const ComomentLaunch &L, int n_pairs, tgx_error *err) {
   (void)err;
   bool want = false;
-  if (st->como_pivot_tries.size() < st->plan->como.size()) st->como_pivot_tries.assign(st->plan->como.size(), 0);
-  for (int k = 0; k < n_pairs; k++)
-    if (L.pairs[k].length > 0 && st->como_pivot_tries[L.acc_index[k]] < 4) {
-      st->como_pivot_tries[L.acc_index[k]]++;
-      want = true;
-    }
-  if (want) launch_como_pivot(L, n_pairs, st->d_como_acc.as<ComomentAcc>(), st->stream);
+  for (int k = 0; k < n_pairs; k++) want |= L.pairs[k].length > 0;
+  if (want)
+    launch_como_pivot(L, n_pairs, st->d_como_acc.as<ComomentAcc>(),
+                      st->d_pivot_search.as<PivotSearch>() + st->plan->scan.size(), st->stream);
   return TGX_OK;
 }
 
@@ -624,7 +622,9 @@ tgx_status launch_scan_lane(tgx_state *st, ScanLane lane, const LaneColumns &col
       HIP_TRY(st->d_hll_rows.reserve((size_t)n * blocks * kHllRegisters));
       for (int k = 0; k < n; k++) L.cols[k].hll = st->d_hll_rows.as<uint8_t>() + (size_t)k * blocks * kHllRegisters;
     }
-    if (chunk_var) launch_scan_pivot(L, n, st->d_pivots.as<double>(), st->d_pivot_set.as<int32_t>(), st->stream);
+    if (chunk_var)
+      launch_scan_pivot(L, n, st->d_pivots.as<double>(), st->d_pivot_set.as<int32_t>(), st->d_pivot_search.as<PivotSearch>(),
+                        st->stream);
     {
       ProfScope ps(st, "scan", chunk_bytes);
       if (lane == ScanLane::kPlain) {
