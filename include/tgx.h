@@ -153,8 +153,11 @@ typedef enum tgx_check_kind {
   /* COUNT(CASE WHEN [TRIM(]c[)] ~|~* 'pat' [OR c IS NULL] THEN 1 END), COUNT(*)
    *                                            TG/constraints/format.rs:750-776 */
   TGX_CHECK_REGEX_MATCH = 4,
-  /* KllSketch::update over the column's non-NULL, non-NaN values
-   *                                            TG/analyzers/advanced/kll_sketch.rs:195-229 */
+  /* KllSketch::update over the column's non-NULL, non-NaN values (Int64 CAST AS DOUBLE)
+   *                                            TG/analyzers/advanced/kll_sketch.rs:195-229
+   * The sketch itself does not depend on kll_k (512-item runs, < 1024 raw items): k sets the stated bound
+   * tgx_kll_relative_error_bound(k) = 1.65/sqrt(k) and the merge check only.  Its actual rank error is about
+   * 0.1-0.2 %, so the bound holds up to k = 65536 (0.64 %) but not for k above roughly 10^6. */
   TGX_CHECK_KLL = 5,
   /* n, Sx, Sy, Sxx, Syy, Sxy over rows with both columns non-NULL (CAST AS DOUBLE)
    *                                            TG/analyzers/advanced/correlation.rs:239-249

@@ -193,6 +193,7 @@ void fill_scan_desc(const tgx_column &c, bool variance, const double *pivot, Sca
   d->skip_stats = 0;
   d->hll = nullptr;
   d->hll_regs = nullptr;
+  d->kll = ScanKll();  // no sampler until kll_scan_prepare gives the column one
   const uintptr_t width = d->elem32 ? 4 : 8;  // a lane's pair of rows is one 2 x width load
   int64_t head = (64 - (c.offset & 63)) & 63;
   if (head > c.length) head = c.length;

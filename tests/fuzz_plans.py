@@ -10,6 +10,7 @@ import sys
 
 import numpy as np
 
+import exact_quantiles as Q
 import oracle_binding as orc
 import term_amd as T
 from _lib_spec import spec
@@ -388,8 +389,7 @@ class Case:
 
             on_device = self.device != "host"
             shards_of = lambda rank: self.columns_of(self.cuts[rank], self.cuts[rank + 1], on_device)  # noqa: E731
-            out = _run_ranks(self.world, plan, shards_of)
-            return [r for r, _st in out]  # every rank's view of the whole table
+            return _run_ranks(self.world, plan, shards_of)  # every rank's view of the whole table, and its state
         n_states = int(self.rng.integers(2, 4)) if self.after == "merge" else 1
         states = [T.State(plan) for _ in range(n_states)]
         # a declared value range (tgx_distinct_range_hint: what ranks agree on before a sharded run) for some of the
@@ -417,13 +417,13 @@ class Case:
                 cols = self.columns_of(self.cuts[b], self.cuts[b + 1], on_device)
                 keep.append(cols)
                 states[0].update(cols)
-            self.check_one(states[0].finalize())
+            self.check_one(states[0].finalize(), states[0])
             states[0].reset()
             for k, lo, hi in hints:
                 states[0].distinct_range_hint(k, lo, hi)
         for b in order:
             if b == stop_at:  # the table so far
-                self.prefix_case(self.cuts[b]).check_one(states[0].finalize())
+                self.prefix_case(self.cuts[b]).check_one(states[0].finalize(), states[0])
             if b == blob_at:
                 states[0] = T.State.deserialize(plan, states[0].serialize())
             lo, hi = self.cuts[b], self.cuts[b + 1]
@@ -442,7 +442,7 @@ class Case:
             st = T.State.deserialize(plan, st.serialize())
         res = st.finalize()
         del keep
-        return [res]
+        return [(res, st)]
 
     # ---- the oracle side + comparison ----
     def key_bits(self, ci):
@@ -467,12 +467,13 @@ class Case:
         return offsets.astype(np.int32)
 
     def check(self, all_res):
-        for res in all_res:
-            self.check_one(res)
+        for res, st in all_res:
+            self.check_one(res, st)
 
-    def check_one(self, res):
+    def check_one(self, res, st):
+        """res: the results of the case's table; st: the state that gave them (read for its KLL sketches)"""
         n = self.n
-        for r, e in zip(res, self.expect):
+        for si, (r, e) in enumerate(zip(res, self.expect)):
             what = e[0]
             if what == "tuple":
                 self.check_tuple(r, e)
@@ -510,9 +511,8 @@ class Case:
                 want = rx.count_utf8(self.offsets32(vals), extra[0], vb, n=n, trim=bool(e[3] & T.FLAG_TRIM),
                                      null_is_valid=bool(e[3] & T.FLAG_NULL_IS_VALID))
                 assert (r.total, r.matches) == (n, want.matches), (e, r.matches, want.matches)
-            elif what == "kll":
-                x = vals[mask].astype(np.float64)
-                assert r.kll_n == int((~np.isnan(x)).sum()), (e, r.kll_n)
+            elif what == "kll":  # weight, membership, the query rule, rank error; exact below 1024 values
+                Q.check_sketch(st, si, Q.kept(vals[mask]), self.specs[si].kll_k, result=r)
             elif what == "comoments":
                 _, y, yb, _, _ = self.cols[e[2]]
                 o = orc.comoments(vals, y, vb, yb, n=n)

@@ -13,20 +13,10 @@ import pytest
 import oracle_binding as orc
 import term_amd as T
 from _lib_spec import spec
+from exact_quantiles import rank_error
 from gpu_util import numeric_column, run_plan
 
 pytestmark = pytest.mark.gpu
-
-
-def rank_error(sorted_vals, q, phi):
-    """|rank(q) - phi*n| / n using the closest rank of q in the exact data"""
-    n = len(sorted_vals)
-    lo = np.searchsorted(sorted_vals, q, side="left")
-    hi = np.searchsorted(sorted_vals, q, side="right")
-    target = phi * n
-    if lo <= target <= hi:
-        return 0.0
-    return min(abs(lo - target), abs(hi - target)) / n
 
 
 def total_weight(st, idx):
