@@ -84,7 +84,11 @@ typedef enum tgx_type {
    * accumulators), value-preserving for MIN / MAX / COUNT(DISTINCT): COUNT and NUMERIC_STATS read the 4-byte values
    * in place (widened in registers); for DISTINCT, KLL, COMOMENTS and SPEARMAN the batch's window is widened into a
    * staging buffer on the device first (one extra pass over those columns).  Int64-shaped Arrow types (Timestamp, Date64, Time64, Duration) are passed as
-   * TGX_INT64 as they are. */
+   * TGX_INT64 as they are.
+   * Float32 widens bit-preservingly: normal and subnormal values exactly, a NaN to the Float64 NaN of the same sign and
+   * payload, its quiet bit as it was -- a signalling NaN and the quiet NaN of its payload stay two keys for DISTINCT,
+   * multiplicity and APPROX_DISTINCT, and MIN / MAX order the widened bits.  SPEARMAN ranks CAST(x AS DOUBLE), where
+   * every NaN is quiet. */
   TGX_INT32 = 7,
   TGX_FLOAT32 = 8,
   /* Narrow and unsigned integers (round 5): the reference's completeness / uniqueness SQL takes any column type

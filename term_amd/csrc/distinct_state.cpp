@@ -661,7 +661,18 @@ tgx_status distinct_prepare_numeric(tgx_state *st, size_t slot, const tgx_column
         HIP_TRY(hipMemcpyAsync(&got, ds.sample.p, sizeof(got), hipMemcpyDeviceToHost, st->stream));
         HIP_TRY(hipStreamSynchronize(st->stream));
       }
-      if (got.count == 0) return TGX_OK;          // nothing valid among the sampled rows: decide on a later batch
+      if (got.count == 0 && c.length > 65536) {
+        // the sample (65 536 rows of the batch, kernels/distinct.hip; of one shorter than 131 072 rows its first ones)
+        // saw only NULLs, but other rows may hold keys: an undecided key set drops the batch, so read every row first
+        DistinctColDesc d = numeric_desc(c, false);
+        d.pad = 1;
+        HIP_TRY(ds.sample.reserve(sizeof(DistinctSample)));
+        launch_distinct_init(ds.sample.as<DistinctSample>(), nullptr, st->stream);
+        launch_distinct_sample(d, ds.sample.as<DistinctSample>(), st->stream);
+        HIP_TRY(hipMemcpyAsync(&got, ds.sample.p, sizeof(got), hipMemcpyDeviceToHost, st->stream));
+        HIP_TRY(hipStreamSynchronize(st->stream));
+      }
+      if (got.count == 0) return TGX_OK;          // nothing valid in the batch: decide on a later batch
       have_range = true;
       lo = got.min_v;
       hi = got.max_v;

@@ -126,7 +126,7 @@ struct ComomentColDesc {
   const uint8_t *xv, *yv;
   int64_t xoff, yoff;
   int64_t length;
-  int32_t x_is_float, y_is_float;
+  int32_t x_is_float, y_is_float;  // (SPEARMAN: 2 = a widened Float32 column, whose rank keys quiet their NaNs)
 };
 
 struct ComomentLaunch {
@@ -199,6 +199,16 @@ constexpr int kPivotSearchBlocks = 4096;
 
 __host__ __device__ inline int64_t f64_total_key(int64_t bits) {
   return bits ^ (int64_t)(((uint64_t)(bits >> 63)) >> 1);
+}
+
+// The bits of a Float32 as the bits of the Float64 it stands for, bit-preserving (include/tgx.h, TGX_FLOAT32): the
+// hardware conversion (IEEE mode) quiets a signalling NaN, which would make 0x7F800001 and 0x7FC00001 one key, so a
+// NaN is rebuilt from its own sign and payload, quiet bit as it was.  Subnormals convert exactly (f32 denormals are
+// kept: the kernels' float_denorm_mode_32 is 3).
+__device__ __forceinline__ int64_t f32_widen_bits(uint32_t u) {
+  const int64_t hw = __double_as_longlong((double)__uint_as_float(u));
+  const uint64_t nan = ((uint64_t)(u & 0x80000000u) << 32) | 0x7FF0000000000000ull | ((uint64_t)(u & 0x7FFFFFu) << 29);
+  return (u & 0x7FFFFFFFu) > 0x7F800000u ? (int64_t)nan : hw;
 }
 
 }  // namespace tgx

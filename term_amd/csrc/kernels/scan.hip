@@ -118,7 +118,7 @@ typedef const int32_t __attribute__((address_space(1))) *global_i32_ptr;
 // an Int32 as the Int64 it stands for / the bits of a Float32 as the bits of the Float64 it stands for
 template <bool IS_FLOAT>
 __device__ __forceinline__ int64_t widen32(int32_t raw) {
-  if (IS_FLOAT) return __double_as_longlong((double)__int_as_float(raw));
+  if (IS_FLOAT) return f32_widen_bits((uint32_t)raw);
   return (int64_t)raw;
 }
 
@@ -1404,23 +1404,19 @@ __global__ __launch_bounds__(256) void widen32_kernel(const void *__restrict__ s
   const bool aligned = (((uintptr_t)src) & 15) == 0;
   const int64_t n4 = aligned ? n >> 2 : 0;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
-    if (is_float) {
-      const float4 v = ((const float4 *)src)[q];
-      double2 *o = (double2 *)dst + 2 * q;
-      o[0] = make_double2((double)v.x, (double)v.y);
-      o[1] = make_double2((double)v.z, (double)v.w);
+    const int4 v = ((const int4 *)src)[q];
+    longlong2 *o = (longlong2 *)dst + 2 * q;
+    if (is_float) {  // (bit-preserving: DISTINCT, multiplicity and the key sets read these bits as keys)
+      o[0] = make_longlong2(f32_widen_bits((uint32_t)v.x), f32_widen_bits((uint32_t)v.y));
+      o[1] = make_longlong2(f32_widen_bits((uint32_t)v.z), f32_widen_bits((uint32_t)v.w));
     } else {
-      const int4 v = ((const int4 *)src)[q];
-      longlong2 *o = (longlong2 *)dst + 2 * q;
       o[0] = make_longlong2((long long)v.x, (long long)v.y);
       o[1] = make_longlong2((long long)v.z, (long long)v.w);
     }
   }
   for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (is_float)
-      ((double *)dst)[i] = (double)((const float *)src)[i];
-    else
-      ((long long *)dst)[i] = (long long)((const int *)src)[i];
+    const int v = ((const int *)src)[i];
+    ((long long *)dst)[i] = is_float ? f32_widen_bits((uint32_t)v) : (long long)v;
   }
 }
 

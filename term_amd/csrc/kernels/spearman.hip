@@ -21,7 +21,10 @@ namespace tgx {
 typedef const int64_t __attribute__((address_space(1))) *global_i64_ptr;
 typedef const uint8_t __attribute__((address_space(1))) *global_u8_ptr;
 
+// is_float 2: a Float32 column, widened bit-preservingly (scan.hip, widen32_kernel); its CAST AS DOUBLE is the
+// hardware conversion, which quiets every NaN: a signalling NaN ranks with the quiet NaN of its payload
 __device__ __forceinline__ uint64_t sort_key(int64_t bits, int is_float) {
+  if (is_float == 2 && (bits & 0x7FFFFFFFFFFFFFFFll) > 0x7FF0000000000000ll) bits |= 0x0008000000000000ll;
   const double d = is_float ? __longlong_as_double(bits) : (double)bits;  // CAST(c AS DOUBLE)
   const int64_t k = f64_total_key(__double_as_longlong(d));
   return (uint64_t)k ^ 0x8000000000000000ULL;  // signed total order -> unsigned radix order

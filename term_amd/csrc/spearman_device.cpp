@@ -153,7 +153,7 @@ void spearman_state_reset(tgx_state *st) {
 namespace {
 // the pairs of `length` rows without NULLs behind the pairs the task holds
 tgx_status append_rows(tgx_state *st, SpearmanTaskState &ts, const void *xv, const void *yv, const uint8_t *xval,
-                       const uint8_t *yval, int64_t xoff, int64_t yoff, int64_t length, bool x_is_float, bool y_is_float,
+                       const uint8_t *yval, int64_t xoff, int64_t yoff, int64_t length, int x_is_float, int y_is_float,
                        tgx_error *err) {
   if (!ts.count.p) {
     SHIP(ts.count.reserve(16));
@@ -243,8 +243,10 @@ tgx_status spearman_update(tgx_state *st, const tgx_column *dev, const tgx_colum
       ts.lent.y_is_float = y.type == TGX_FLOAT64;
       continue;
     }
-    STRY(append_rows(st, ts, x.values, y.values, x.validity, y.validity, x.offset, y.offset, x.length,
-                     x.type == TGX_FLOAT64, y.type == TGX_FLOAT64, err));
+    // (a widened Float32 column is never lent: its keys quiet their NaNs as they are made, kernels/spearman.hip)
+    auto fl = [](const tgx_column &c, const tgx_column &o) { return c.type == TGX_FLOAT64 ? (o.type == TGX_FLOAT32 ? 2 : 1) : 0; };
+    STRY(append_rows(st, ts, x.values, y.values, x.validity, y.validity, x.offset, y.offset, x.length, fl(x, ox),
+                     fl(y, oy), err));
   }
   return TGX_OK;
 }

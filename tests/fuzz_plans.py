@@ -11,6 +11,7 @@ import sys
 import numpy as np
 
 import exact_quantiles as Q
+import exact_widening as W
 import oracle_binding as orc
 import term_amd as T
 from _lib_spec import spec
@@ -73,6 +74,22 @@ def float_values(rng, n, shape):
 
 
 FLOAT_SHAPES = ["uniform", "normal", "rounded", "ints", "ascending", "specials"]
+
+
+def f32_bit_patterns(rng, n):
+    """a Float32 column of the patterns no cast of a Float64 gives: NaN payloads, signalling and quiet, of both signs
+    (some payload both ways: two keys of DISTINCT), and subnormals, among ordinary values"""
+    u = (rng.standard_normal(n) * 10).astype(np.float32).view(np.uint32)
+    pick = rng.random(n)
+    sign = rng.integers(0, 2, size=n, dtype=np.uint64) << np.uint64(31)
+    payload = rng.integers(1, 2 ** 23, size=n, dtype=np.uint64)
+    rep = rng.random(n) < 0.5
+    payload[rep] = rng.integers(1, 8, size=int(rep.sum()), dtype=np.uint64)  # a few payloads repeat
+    quiet = np.where(rng.random(n) < 0.5, np.uint64(0x400000), np.uint64(0))
+    nan = (sign | np.uint64(0x7F800000) | quiet | payload).astype(np.uint32)
+    sub = (sign | rng.integers(1, 2 ** 23, size=n, dtype=np.uint64)).astype(np.uint32)
+    u = np.where(pick < 0.06, nan, np.where(pick < 0.12, sub, u))
+    return u.view(np.float32)
 
 
 # ---- strings ----------------------------------------------------------------------------------------------------------
@@ -185,8 +202,9 @@ class Case:
                 vals = int_values(rng, n, str(rng.choice(["permutation", "ascending", "few", "tenth", "constant"])))
                 vals = (vals % (2**31)).astype(np.int32) if rng.random() < 0.5 else vals.astype(np.int32)
             elif kind == "f32":
+                shape = str(rng.choice(["uniform", "rounded", "ints", "specials", "bits"]))
                 with np.errstate(over="ignore"):  # (1e308 becomes inf: one more special value)
-                    vals = float_values(rng, n, str(rng.choice(["uniform", "rounded", "ints", "specials"]))).astype(np.float32)
+                    vals = f32_bit_patterns(rng, n) if shape == "bits" else float_values(rng, n, shape).astype(np.float32)
             else:
                 vocab = int(rng.choice([1, 3, 100, max(1, n // 10), max(1, n)]))
                 vocab = min(vocab, 200_000)
@@ -450,8 +468,8 @@ class Case:
         kind, vals, vb, _, _ = self.cols[ci]
         if kind == "i32":
             return vals.astype(np.int64).view(np.uint64), vb
-        if kind == "f32":
-            return vals.astype(np.float64).view(np.uint64), vb
+        if kind == "f32":  # (bit-preserving: a signalling NaN is a key of its own, exact_widening.py)
+            return W.widen_f32_bits(vals), vb
         return vals.view(np.uint64), vb
 
     def exact_distinct(self, ci):
@@ -479,7 +497,8 @@ class Case:
                 self.check_tuple(r, e)
                 continue
             kind, vals, vb, mask, extra = self.cols[e[1]]
-            wide = vals if kind in ("i", "f", "s") else vals.astype(np.int64 if kind == "i32" else np.float64)
+            wide = (vals if kind in ("i", "f", "s") else W.widen_int(vals, "int32") if kind == "i32"
+                    else W.widen_f32_bits(vals).view(np.float64))
             if what == "count":
                 c = orc.count(vb, n)
                 assert (r.total, r.non_null) == (c.total, c.non_null), (e, r.total, r.non_null)
@@ -512,7 +531,7 @@ class Case:
                                      null_is_valid=bool(e[3] & T.FLAG_NULL_IS_VALID))
                 assert (r.total, r.matches) == (n, want.matches), (e, r.matches, want.matches)
             elif what == "kll":  # weight, membership, the query rule, rank error; exact below 1024 values
-                Q.check_sketch(st, si, Q.kept(vals[mask]), self.specs[si].kll_k, result=r)
+                Q.check_sketch(st, si, Q.kept(wide[mask]), self.specs[si].kll_k, result=r)
             elif what == "comoments":
                 _, y, yb, _, _ = self.cols[e[2]]
                 o = orc.comoments(vals, y, vb, yb, n=n)
