@@ -19,6 +19,12 @@ and merged in rank order on every rank.
     python bench.py --gpus N ...        (bare: starts the N ranks itself, as children, and relays rank 0's line;
                                          refuses -- non-zero exit -- when the machine has fewer than N GPUs)
     python bench.py ... --dump-outputs DIR   (also writes what the last timed step returned: dump_outputs below)
+    python bench.py --gpus 1 --full          (also the CPU baseline and, at the default --rows, the other
+                                              BASELINE.json configs and the cold step: `cpu_baseline`, `secondary`)
+
+A plain run does only what its line's headline needs: set up, warm up, time the steps, verify the last step's results
+against the closed-form facts of the table, write them with --dump-outputs, print the line.  What takes runs of its own
+(the CPU baseline, the secondary configs) waits for --full, after the headline's timed region.
 """
 import argparse
 import json
@@ -248,13 +254,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=1_000_000_000, help="total rows of the table (all ranks)")
     ap.add_argument("--seed", type=int, default=0x7E570004)
-    ap.add_argument("--cpu-sample-rows", type=int, default=1 << 26)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the CPU baseline (`cpu_baseline`) and, at the default "
+                         "--rows, the other BASELINE.json configs and the cold step (`secondary`); N = 1 only")
+    ap.add_argument("--cpu-sample-rows", type=int, default=1 << 26, help="rows of the CPU baseline (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--secondary", action="store_true", help="measure the secondary configs at any --rows")
+    ap.add_argument("--secondary", action="store_true", help="--full: measure the secondary configs at any --rows")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the other BASELINE.json configs (C2, C3, C4 on one GPU, C5) and the cold-step measurement "
-                         "that follow the headline's timed region at N = 1")
+                    help="--full without the other BASELINE.json configs (C2, C3, C4 on one GPU, C5) and the cold-step "
+                         "measurement that follow the headline's timed region at N = 1")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (every check's result) as DIR/<name>.npy")
     ap.add_argument("--force-distributed", action="store_true",
@@ -266,6 +275,8 @@ def main():
         raise SystemExit("--gpus must be at least 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.secondary and not args.full:
+        ap.error("--secondary measures part of --full: add --full")
     # Every rank, however it was launched (by launch_ranks below or by `python -m torch.distributed.run ... bench.py`),
     # before its first GPU call: the host driver of this pool only supports dmabuf IPC, and with the legacy mode RCCL /
     # device-memory sharing across processes fails with `hipIpcGetMemHandle: invalid argument` (stated by the pool's
@@ -452,13 +463,14 @@ def main():
         }
         if breakdown is not None:
             out["config"]["rank_breakdown"] = breakdown
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:  # (timed on rank 0 of the single-GPU run only)
             sample = min(args.cpu_sample_rows, n_local)
             ref_line, why_not = reference_cpu_baseline(sample, args.seed)  # term-guard itself, where it can be built
             out["cpu_baseline"] = ref_line or cpu_baseline(torch, layout, unique_cols, table, sample)
             if ref_line is None:
                 out["cpu_baseline"]["reference_probe"] = why_not
-        if world == 1 and not distributed and not args.no_secondary and (n_total == 1_000_000_000 or args.secondary):
+        if args.full and world == 1 and not distributed and not args.no_secondary and \
+                (n_total == 1_000_000_000 or args.secondary):
             # the other BASELINE.json configs and the cold step, after the headline's timed region (tools/secondary_bench.py);
             # the headline's own keys above are what they always were
             sys.path.insert(0, os.path.join(ROOT, "tools"))

@@ -62,3 +62,9 @@ def test_world_size_that_disagrees_with_gpus_is_refused():
     assert p.returncode != 0 and "--gpus 8 but WORLD_SIZE=1" in p.stderr and '"metric"' not in p.stdout
     p = _run(["--gpus", "1"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "--gpus 1 but WORLD_SIZE=2" in p.stderr
+
+
+def test_secondary_without_full_is_refused():
+    """the secondary configs are part of --full: a plain run never measures them, and says so rather than ignore it"""
+    p = _run(["--gpus", "1", "--secondary"])
+    assert p.returncode == 2 and "add --full" in p.stderr and '"metric"' not in p.stdout

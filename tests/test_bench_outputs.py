@@ -51,16 +51,20 @@ def test_dump_writes_every_result_field_and_64_bit_integers_exactly(tmp_path):
     assert sum(os.path.getsize(tmp_path / "out" / (n + ".npy")) for n in names) < 64 << 20
 
 
-def _bench(out_dir, steps):
+def _run_bench(args):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    rows = 1 << 22
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
-                        "--warmup", "1", "--rows", str(rows), "--no-cpu-baseline", "--no-secondary",
-                        "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args, env=env,
+                       capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
-    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def _bench(out_dir, steps):
+    rows = 1 << 22
+    line = _run_bench(["--steps", str(steps), "--warmup", "1", "--rows", str(rows), "--no-cpu-baseline",
+                       "--no-secondary", "--dump-outputs", str(out_dir)])
     return rows, line, {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
 
 
@@ -81,3 +85,15 @@ def test_bench_dumps_the_last_step_and_the_same_arguments_give_the_same_outputs(
     assert line2["steps"] == 2 and sorted(again) == sorted(got)
     for name in got:
         np.testing.assert_array_equal(again[name], got[name], err_msg=name)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_cpu_baseline_and_secondary_configs_to_full():
+    small = ["--steps", "2", "--warmup", "1", "--rows", str(1 << 22)]
+    plain = _run_bench(small)
+    assert plain["config"]["verified"] is True and plain["ms_per_step"] > 0 and plain["roofline"]["frac"] > 0
+    assert "cpu_baseline" not in plain and "secondary" not in plain
+    full = _run_bench(small + ["--full"])  # (the secondary configs only at the default --rows, or with --secondary)
+    assert full["config"]["verified"] is True and "secondary" not in full
+    assert full["cpu_baseline"]["verified"] is True and full["cpu_baseline"]["value"] > 0
+    assert sorted(k for k in full if k != "cpu_baseline") == sorted(plain)

@@ -3,7 +3,7 @@
 #   gpurun --timeout 1200 -- 'bash tools/bench_all.sh > gpurun_out/bench_all.txt 2>&1'
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 run() { echo "### $*"; timeout -k 5 400 "$@" 2>/dev/null | grep -E '^\{|^rows |ms/step|G rows/s' | cut -c1-400; }
-run python bench.py                                   # headline: 1 G rows x 16 columns, + cpu_baseline
+run python bench.py --full                            # headline: 1 G rows x 16 columns, + cpu_baseline, secondary
 run python bench.py --force-distributed --rows 125000000 --steps 10 --warmup 3 --no-cpu-baseline   # one rank of the 8-way shard
 run python tools/bench_configs.py --steps 3           # C2, C4, C5
 run python tools/bench_regex.py                       # C3 (LargeUtf8)
