@@ -10,7 +10,9 @@ import sys
 
 import numpy as np
 
+import exact_hll as H
 import exact_quantiles as Q
+import exact_ranks as R
 import exact_widening as W
 import oracle_binding as orc
 import term_amd as T
@@ -518,9 +520,11 @@ class Case:
                 assert (r.total, r.non_null) == (c.total, c.non_null), e
                 if e[2]:
                     want = self.exact_distinct(e[1]).distinct
-                else:
+                else:  # (the independent reference: registers of the widened bits, the estimate in doubles)
                     bits, _ = self.key_bits(e[1])
-                    want = orc.hll_estimate(orc.hll_registers(bits.view(np.int64), vb, n=n))
+                    want = H.estimate_double(H.registers(bits, vb, n=n))
+                    true = self.exact_distinct(e[1]).distinct
+                    assert abs(want - true) <= H.rel_bound(true) * true, (e, want, true)
                 assert r.distinct == want, (e, r.distinct, want)
             elif what == "length":
                 want = orc.length_count_utf8(self.offsets32(vals), extra[0], vb, n=n, min_chars=e[2], max_chars=e[3])
@@ -579,10 +583,9 @@ class Case:
                         assert rel_err(got, want) < TOL or abs(got - want) < 1e-6, (e, got, want)
             elif what == "spearman":
                 _, y, yb, _, _ = self.cols[e[2]]
-                o = orc.spearman_state(vals, y, vb, yb, n=n)
+                want = R.spearman(vals, y, vb, yb, n=n)  # RANK() over the totalOrder keys, sums wrapped mod 2^64
                 got = (int(r.non_null), r.sum_x, r.sum_y, r.sum_x2, r.sum_y2, r.sum_xy)
-                want = (int(o.n), o.sum_x, o.sum_y, o.sum_x2, o.sum_y2, o.sum_xy)
-                assert got == want, (e, got, want)
+                assert got == (want.n,) + want.doubles(), (e, got, want.n, want.wrapped)
 
     def check_tuple(self, r, e):
         """COUNT(DISTINCT (a, b, ...)): a tuple is a value of its own, NULL components included"""
