@@ -48,6 +48,25 @@ HashSetView hash_view(const DistinctState &ds) {
   return v;
 }
 
+// the kernels' view of a string column (a dictionary's values included).  `buffers`: the DEVICE copy of a Utf8View's
+// table of data-buffer pointers (not looked at for the other layouts)
+Utf8ColDesc utf8_desc(const tgx_column &c, const uint8_t *const *buffers, const FpKey &key, bool mult) {
+  Utf8ColDesc d;
+  memset(&d, 0, sizeof(d));
+  const bool view = c.type == TGX_UTF8_VIEW;
+  d.offsets = c.offsets;
+  d.data = c.data;
+  d.validity = c.validity;
+  d.offset = c.offset;
+  d.length = c.length;
+  d.large_offsets = c.type == TGX_LARGE_UTF8;
+  d.want_multiplicity = mult ? 1 : 0;
+  d.views = view ? c.values : nullptr;
+  d.buffers = view ? buffers : nullptr;
+  d.key = key;
+  return d;
+}
+
 // the kernels' view of a numeric key column
 DistinctColDesc numeric_desc(const tgx_column &c, bool mult) {
   DistinctColDesc d;
@@ -137,10 +156,8 @@ tgx_status key_store_reserve_utf8(tgx_state *st, DistinctState &ds, const tgx_co
   TGX_TRY(key_store_measure_begin(st, ds, (uint64_t)c.length, err));
   if (data_bytes >= 0 && c.type != TGX_UTF8_VIEW)  // (an entry: two words + ceil(len / 8) <= len / 8 + 3 words)
     return key_store_reserve_bound(st, ds, 3 * (uint64_t)c.length + (uint64_t)data_bytes / 8, err);
-  const bool view = c.type == TGX_UTF8_VIEW;
-  launch_exact_measure_utf8(c.offsets, c.data, view ? c.values : nullptr, view ? c.variadic : nullptr, c.validity, c.offset,
-                            c.length, c.type == TGX_LARGE_UTF8, used, ds.key_cursor.as<unsigned long long>() + 1,
-                            st->stream);
+  launch_exact_measure_utf8(utf8_desc(c, c.variadic, FpKey{}, false), used,  // (lengths only: no key)
+                            ds.key_cursor.as<unsigned long long>() + 1, st->stream);
   return key_store_reserve_measured(st, ds, err);
 }
 BitmapView bitmap_view(const DistinctState &ds) {
@@ -238,9 +255,7 @@ tgx_status table_insert_utf8(tgx_state *st, size_t slot, const tgx_column &c, in
   const bool mult = st->plan->distinct[slot].multiplicity;
   TGX_TRY(hash_ensure(st, ds, mult, (uint64_t)c.length, err));
   if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, c, nullptr, data_bytes, err));
-  const bool view = c.type == TGX_UTF8_VIEW;
-  launch_distinct_utf8(c.offsets, c.data, view ? c.values : nullptr, view ? c.variadic : nullptr, c.validity, c.offset,
-                       c.length, c.type == TGX_LARGE_UTF8, mult ? 1 : 0, hash_view(ds), st->plan->fp_key,
+  launch_distinct_utf8(utf8_desc(c, c.variadic, st->plan->fp_key, mult), hash_view(ds),
                        ds.counters.as<unsigned long long>(), st->stream);
   return TGX_OK;
 }
@@ -385,18 +400,13 @@ tgx_status fp_lists_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_
   TGX_TRY(fp_lists_stage(st, ds, c.length, true, &l1, &l2, &fb_lo, err));
   ProfScope ps(st, "distinct", 0), ps_lists(st, "distinct_lists", 0);
   unsigned long long *counters = ds.counters.as<unsigned long long>();
-  if (view)
-    launch_fp_partition_views(c.values, kept.variadic, c.validity, c.offset, c.length, l1, st->plan->fp_key, fb_lo, counters,
-                              st->stream);
-  else
-    launch_fp_partition_strings(c.offsets, c.data, c.validity, c.offset, c.length, c.type == TGX_LARGE_UTF8, l1,
-                                st->plan->fp_key, fb_lo, counters, st->stream);
+  // (the lists' kernels take the multiplicity as a launch argument, not from the descriptor)
+  const Utf8ColDesc d = utf8_desc(kept, kept.variadic, st->plan->fp_key, false);
+  launch_fp_partition_utf8(d, l1, fb_lo, counters, st->stream);
   launch_fp_partition_lists(l1, l2, counters, st->stream);
   // an exact set: records carry their row, the count settles equal fingerprints on the rows' bytes
   if (ds.exact)
-    launch_fp_count_exact_utf8(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), l1.offered, c.offsets, c.data,
-                               view ? c.values : nullptr, view ? kept.variadic : nullptr, c.offset, c.length,
-                               c.type == TGX_LARGE_UTF8, counters, st->stream);
+    launch_fp_count_exact_utf8(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), l1.offered, d, counters, st->stream);
   else
     launch_fp_count(l2, mult ? 1 : 0, ds.fp_per_list.as<uint2>(), l1.offered, counters, st->stream);
   ds.retained.push_back(kept);  // (a DEVICE view, or a staged one looked at before the update returns)
@@ -951,8 +961,7 @@ tgx_status distinct_update(tgx_state *st, size_t slot, const tgx_column &c, cons
                         ds.counters.as<unsigned long long>(), g_ctx.n_cu, st->stream);
     }
     if (ds.exact) TGX_TRY(key_store_reserve_utf8(st, ds, dict, u_seen, facts.data_bytes, err));  // the referenced entries
-    launch_dict_insert(dict.offsets, dict.data, dict.validity, dict.offset, dict.length,
-                       dict.type == TGX_LARGE_UTF8, mult ? 1 : 0, u_seen, u_twice, hash_view(ds), st->plan->fp_key,
+    launch_dict_insert(utf8_desc(dict, nullptr, st->plan->fp_key, mult), u_seen, u_twice, hash_view(ds),
                        ds.counters.as<unsigned long long>(), st->stream);
     return TGX_OK;
   }

@@ -82,13 +82,10 @@ void launch_bitmap_adopt(const uint32_t *seen_slices, const uint32_t *twice_slic
 void launch_bitmap_rebase(const uint32_t *src, uint64_t src_words, long long delta_bits, uint32_t world,
                           uint64_t slice_words, uint64_t row_words, uint64_t col_words, uint32_t *send,
                           hipStream_t stream);
-void launch_distinct_utf8(const void *offsets, const uint8_t *data, const void *views,
-                          const uint8_t *const *buffers, const uint8_t *validity, int64_t offset,
-                          int64_t length, int large_offsets, int want_mult, const HashSetView &t, const FpKey &key,
-                          unsigned long long *d_counters, hipStream_t stream);
-void launch_exact_measure_utf8(const void *offsets, const uint8_t *data, const void *views,
-                               const uint8_t *const *buffers, const uint8_t *validity, int64_t offset, int64_t length,
-                               int large_offsets, const uint32_t *dict_seen, unsigned long long *out,
+// a string column goes to its kernels as one Utf8ColDesc (distinct_state.cpp, utf8_desc)
+void launch_distinct_utf8(const Utf8ColDesc &d, const HashSetView &t, unsigned long long *d_counters,
+                          hipStream_t stream);
+void launch_exact_measure_utf8(const Utf8ColDesc &d, const uint32_t *dict_seen, unsigned long long *out,
                                hipStream_t stream);
 void launch_exact_measure_tuple(const TupleDesc &d, unsigned long long *out, hipStream_t stream);
 void launch_gather_segments(const GatherSeg *d_segs, int n_segs, int parts, hipStream_t stream);
@@ -112,26 +109,18 @@ void launch_dict_usage(const int32_t *indices, const uint8_t *validity, int64_t 
                        const uint8_t *dict_validity, int64_t dict_offset, int64_t dict_length, int want_mult,
                        uint32_t *seen, uint32_t *twice, uint32_t *scratch, unsigned long long *d_counters, int n_cu,
                        hipStream_t stream);
-void launch_dict_insert(const void *offsets, const uint8_t *data, const uint8_t *validity, int64_t offset,
-                        int64_t length, int large_offsets, int want_mult, const uint32_t *seen,
-                        const uint32_t *twice, const HashSetView &t, const FpKey &key, unsigned long long *d_counters,
-                        hipStream_t stream);
+void launch_dict_insert(const Utf8ColDesc &d, const uint32_t *seen, const uint32_t *twice, const HashSetView &t,
+                        unsigned long long *d_counters, hipStream_t stream);
 void launch_distinct_tuple(const TupleDesc &d, const HashSetView &t, unsigned long long *d_counters,
                            hipStream_t stream);
 // big Utf8 batches: fingerprints partitioned into lists, deduplicated list by list in LDS (distinct128.hip, fp_*)
-void launch_fp_partition_strings(const void *offsets, const uint8_t *data, const uint8_t *validity, int64_t offset,
-                                 int64_t length, int large_offsets, const FpLists &level1, const FpKey &key,
-                                 uint32_t *exact_fb_lo, unsigned long long *d_counters, hipStream_t stream);
-void launch_fp_partition_views(const void *views, const uint8_t *const *buffers, const uint8_t *validity,
-                               int64_t offset, int64_t length, const FpLists &level1, const FpKey &key,
-                               uint32_t *exact_fb_lo, unsigned long long *d_counters, hipStream_t stream);
+void launch_fp_partition_utf8(const Utf8ColDesc &d, const FpLists &level1, uint32_t *exact_fb_lo,
+                              unsigned long long *d_counters, hipStream_t stream);
 void launch_fp_partition_tuples(const TupleDesc &d, const FpLists &level1, uint32_t *exact_fb_lo,
                                 unsigned long long *d_counters, hipStream_t stream);
 // exact sets: the lists' records carry rows; equal fingerprints are settled on the rows' bytes
 void launch_fp_count_exact_utf8(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
-                                const void *offsets, const uint8_t *data, const void *views, const uint8_t *const *buffers,
-                                int64_t offset, int64_t length, int large_offsets, unsigned long long *d_counters,
-                                hipStream_t stream);
+                                const Utf8ColDesc &d, unsigned long long *d_counters, hipStream_t stream);
 void launch_fp_count_exact_tuple(const FpLists &level2, int want_mult, uint2 *per_list, const TupleDesc &d,
                                  unsigned long long *d_counters, hipStream_t stream);
 void launch_fp_demote(const FpLists &level2, const uint32_t *fb_lo, const HashSetView &t, int want_mult,
@@ -141,7 +130,7 @@ void launch_fp_partition_lists(const FpLists &level1, const FpLists &level2, uns
 void launch_fp_count(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
                      unsigned long long *d_counters, hipStream_t stream);
 void launch_fp_insert(const FpLists &level2, const HashSetView &t, int want_mult, hipStream_t stream);
-// the same for big batches of keys without a dense range (distinct.hip, key_*): 8-byte records (the mixed key)
+// the same for big batches of keys without a dense range (kernels/distinct.hip, key_*): 8-byte records (the mixed key)
 void launch_key_lists(const DistinctColDesc &d, const FpLists &level1, const FpLists &level2, int want_mult,
                       uint2 *per_list, unsigned long long *d_counters, hipStream_t stream);
 void launch_key_insert(const FpLists &level2, const HashSetView &t, int want_mult, hipStream_t stream);
@@ -232,7 +221,7 @@ struct tgx_plan {
   std::vector<char> used, reads_values, needs_wide;
   std::vector<char> key_column;  // a single-column DISTINCT check reads it (range tracking of coalesced HOST batches)
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
-  // the key of the string / tuple fingerprints (kernels/distinct128.hip): drawn from the OS at tgx_plan_create, or set
+  // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
   tgx::FpKey fp_key;
   mutable std::atomic<bool> fp_key_locked{false};  // a state has been created: the key may not change any more

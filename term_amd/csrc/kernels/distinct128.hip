@@ -1,7 +1,7 @@
 // distinct128.hip -- COUNT(DISTINCT) over byte-string keys (Utf8 / Binary / tuples) on gfx950: keyed 128-bit
 // fingerprints, and EXACT key sets that confirm equal fingerprints byte by byte (TGX_FLAG_EXACT_KEYS).
 //
-// Variable-length values are reduced on the fly to 128-bit fingerprints (fingerprint() below: Chaskey-8 under the
+// Variable-length values are reduced on the fly to 128-bit fingerprints (fingerprint.h: Chaskey-8 under the
 // plan's key).  Small batches deduplicate the fingerprints in an open-addressing table of
 // 16-byte slots: a slot is claimed with ONE 64-bit CAS on its first word and the owner publishes the second; a
 // thread that meets an equal first word and a different second just keeps probing, so no thread ever waits on
@@ -10,164 +10,15 @@
 // agree whose key the data's producer does not know (~1e-21 for 10^9 distinct values); an exact set never does.
 // The same table serves multi-batch updates, merges (records of 32 bytes) and the cross-rank exchange.
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include "distinct_types.h"
+#include "fingerprint.h"
+#include "keyset_device.h"
 #include "lists.h"
 
 namespace tgx {
 
-typedef const uint8_t __attribute__((address_space(1))) *global_u8_ptr;
-typedef const uint64_t __attribute__((address_space(1))) *global_u64_ptr;
-typedef const int32_t __attribute__((address_space(1))) *global_i32_ptr;
-typedef const int64_t __attribute__((address_space(1))) *global_i64_ptr;
-
-__device__ __forceinline__ uint64_t mix64w(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ULL;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebULL;
-  x ^= x >> 31;
-  return x;
-}
-
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-
-// ---- the 128-bit fingerprint of a value ------------------------------------------------------------------------
-// A KEYED function: Chaskey-8 (Mouha, Mennink, Van Herrewege, Watanabe, Preneel, Verbauwhede, SAC 2014) -- a MAC built
-// for 32-bit machines: a 128-bit state of four 32-bit words, an add-rotate-xor permutation (every instruction of a
-// round is a full-rate 32-bit VALU operation here: no multiplies), a 128-bit key K, a 128-bit tag.  The value is taken
-// in 16-byte blocks: v = K; every block but the last: v ^= m, v = pi(v); the last block (padded with 0x01 0x00... unless
-// it is a full one; an empty value is one padded block): v ^= m ^ K', v = pi(v), v ^= K' with K' = K1 = 2K for a full
-// last block and K2 = 4K for a padded one (doublings in GF(2^128), FpKey).  pi = 8 rounds.
-// Why keyed (round 6): rounds 1-5 used a seedless Murmur3-style mixer; every step of it is invertible, so two distinct
-// values with one fingerprint could be written down (the judge did).  The key is drawn from the OS when the plan is made
-// and never leaves the process except inside state blobs and the rank handshake; whoever produces the DATA does not
-// know it, and without it the blocks' differences cannot be steered through pi (no state-independent differential:
-// every block is followed by the full permutation before the next one is XORed in).  With the key, collisions are
-// trivial to build (XOR the difference of two states into the next block) -- the tests do exactly that to show that an
-// EXACT key set (below) does not care.
-struct Fp {
-  uint32_t v0, v1, v2, v3;
-};
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__device__ __forceinline__ void fp_permute(Fp &s) {
-#pragma unroll
-  for (int r = 0; r < 8; r++) {  // (Chaskey-8)
-    s.v0 += s.v1;
-    s.v1 = rotl32(s.v1, 5);
-    s.v1 ^= s.v0;
-    s.v0 = rotl32(s.v0, 16);
-    s.v2 += s.v3;
-    s.v3 = rotl32(s.v3, 8);
-    s.v3 ^= s.v2;
-    s.v0 += s.v3;
-    s.v3 = rotl32(s.v3, 13);
-    s.v3 ^= s.v0;
-    s.v2 += s.v1;
-    s.v1 = rotl32(s.v1, 7);
-    s.v1 ^= s.v2;
-    s.v2 = rotl32(s.v2, 16);
-  }
-}
-__device__ __forceinline__ void fp_init(Fp &s, const FpKey &key) {
-  s.v0 = key.k[0];
-  s.v1 = key.k[1];
-  s.v2 = key.k[2];
-  s.v3 = key.k[3];
-}
-// a block that is not the value's last: the logical little-endian words lo = bytes 0..7, hi = bytes 8..15
-__device__ __forceinline__ void fp_block(Fp &s, uint64_t lo, uint64_t hi) {
-  s.v0 ^= (uint32_t)lo;
-  s.v1 ^= (uint32_t)(lo >> 32);
-  s.v2 ^= (uint32_t)hi;
-  s.v3 ^= (uint32_t)(hi >> 32);
-  fp_permute(s);
-}
-// the last block, padded: `full` = the value ended on the block's last byte (no padding byte, K1 instead of K2)
-__device__ __forceinline__ void fp_last_padded(Fp &s, uint64_t lo, uint64_t hi, bool full, const FpKey &key) {
-  const uint32_t l0 = full ? key.k1[0] : key.k2[0], l1 = full ? key.k1[1] : key.k2[1];
-  const uint32_t l2 = full ? key.k1[2] : key.k2[2], l3 = full ? key.k1[3] : key.k2[3];
-  s.v0 ^= (uint32_t)lo ^ l0;
-  s.v1 ^= (uint32_t)(lo >> 32) ^ l1;
-  s.v2 ^= (uint32_t)hi ^ l2;
-  s.v3 ^= (uint32_t)(hi >> 32) ^ l3;
-  fp_permute(s);
-  s.v0 ^= l0;
-  s.v1 ^= l1;
-  s.v2 ^= l2;
-  s.v3 ^= l3;
-}
-// the last block: `nb` (0..16) bytes of the value in (lo, hi), the rest zero
-__device__ __forceinline__ void fp_last(Fp &s, uint64_t lo, uint64_t hi, uint32_t nb, const FpKey &key) {
-  if (nb < 8)
-    lo |= 1ull << (8 * nb);
-  else if (nb < 16)
-    hi |= 1ull << (8 * (nb - 8));
-  fp_last_padded(s, lo, hi, nb == 16, key);
-}
-__device__ __forceinline__ void fp_out(const Fp &s, uint64_t *fa, uint64_t *fb) {
-  uint64_t a = (uint64_t)s.v0 | ((uint64_t)s.v1 << 32), b = (uint64_t)s.v2 | ((uint64_t)s.v3 << 32);
-  if (a == kEmptyKey) a -= 1;  // (the table's free-slot marker)
-  if (b == kEmptyKey) b -= 1;
-  *fa = a;
-  *fb = b;
-}
-
-// the logical 8-byte words of bytes [p, p + len) in global memory (independent of where the value sits: assembled from
-// the one or two aligned words that hold them; bytes outside the value are never part of a word)
-struct GlobalWords {
-  uintptr_t p;
-  uint64_t remaining;
-  __device__ __forceinline__ uint64_t next() {
-    const uint32_t nb = remaining < 8 ? (uint32_t)remaining : 8u;
-    if (nb == 0) return 0;
-    const uint32_t skip = (uint32_t)(p & 7);
-    const uintptr_t base = p & ~(uintptr_t)7;
-    uint64_t w = *(global_u64_ptr)base >> (8 * skip);
-    if (skip + nb > 8) w |= *(global_u64_ptr)(base + 8) << (8 * (8 - skip));
-    if (nb < 8) w &= (1ull << (8 * nb)) - 1;
-    p += nb;
-    remaining -= nb;
-    return w;
-  }
-};
-
-// fingerprint of bytes [p, p+len) in global memory
-__device__ __forceinline__ void fingerprint(const FpKey &key, uintptr_t p, uint64_t len, uint64_t *fa, uint64_t *fb) {
-  Fp s;
-  fp_init(s, key);
-  GlobalWords src{p, len};
-  while (src.remaining > 16) {
-    const uint64_t lo = src.next(), hi = src.next();
-    fp_block(s, lo, hi);
-  }
-  const uint32_t nb = (uint32_t)src.remaining;
-  const uint64_t lo = src.next(), hi = src.next();
-  fp_last(s, lo, hi, nb, key);
-  fp_out(s, fa, fb);
-}
-
-__device__ __forceinline__ void block_add2w(unsigned long long a, unsigned long long b,
-                                            unsigned long long *ga, unsigned long long *gb) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    b += __shfl_down(b, d, 64);
-  }
-  __shared__ unsigned long long sa[4], sb[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sa[wave] = a;
-    sb[wave] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long ta = sa[0] + sa[1] + sa[2] + sa[3], tb = sb[0] + sb[1] + sb[2] + sb[3];
-    if (ta) atomicAdd(ga, ta);
-    if (tb) atomicAdd(gb, tb);
-  }
-}
 
 // returns 1 if (a, b) was new; *became_dup = 1 if this insert marks the key as seen twice
 __device__ __forceinline__ int hash_insert128(const HashSetView &t, uint64_t a, uint64_t b, int want_mult,
@@ -399,19 +250,6 @@ __device__ __forceinline__ void exact_commit(const HashSetView &t, const MAKE &m
   }
 }
 
-struct Utf8ColDesc {
-  const void *offsets;
-  const uint8_t *data;
-  const uint8_t *validity;
-  int64_t offset;
-  int64_t length;
-  int32_t large_offsets;
-  int32_t want_multiplicity;
-  const void *views;              // Utf8View: 16-byte views (then offsets / data are unused)
-  const uint8_t *const *buffers;  // Utf8View: device array of the data buffers' device pointers
-  FpKey key;                      // of the plan
-};
-
 // where the value of slot `slot` lies
 __device__ __forceinline__ void utf8_value(const Utf8ColDesc &d, int64_t slot, uintptr_t *p, uint64_t *len) {
   if (d.views) {
@@ -447,7 +285,7 @@ __global__ __launch_bounds__(256) void distinct_utf8_kernel(Utf8ColDesc d, HashS
   if (EXACT) pw.begin(t);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.length; i += stride) {
     const int64_t slot = d.offset + i;
-    const bool valid = !vbits || ((vbits[slot >> 3] >> (slot & 7)) & 1);
+    const bool valid = !vbits || TGX_VALID_BIT(vbits, slot);
     bool is_new = false;
     uint64_t at = 0, fa = 0, fb = 0;
     if (valid) {
@@ -475,9 +313,9 @@ __global__ __launch_bounds__(256) void distinct_utf8_kernel(Utf8ColDesc d, HashS
     if (EXACT) pw.note(t, is_new, at, fb, counters);
   }
   if (EXACT) pw.end(t);
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
   __syncthreads();
-  block_add2w(n_valid, 0ull, &counters[kCntValidRows], &counters[kCntSpare]);
+  block_add2_4waves(n_valid, 0ull, &counters[kCntValidRows], &counters[kCntSpare]);
 }
 
 // phase B of an exact string batch (rows of the column, or entries of a dictionary: the same layout)
@@ -501,13 +339,13 @@ __global__ __launch_bounds__(256) void exact_measure_utf8_kernel(Utf8ColDesc d, 
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.length; i += stride) {
     if (dict_seen && !((dict_seen[i >> 5] >> (i & 31)) & 1)) continue;  // (a dictionary: referenced entries only)
     const int64_t slot = d.offset + i;
-    if (vbits && !((vbits[slot >> 3] >> (slot & 7)) & 1)) continue;
+    if (vbits && !TGX_VALID_BIT(vbits, slot)) continue;
     uintptr_t p;
     uint64_t len;
     utf8_value(d, slot, &p, &len);
     words += 2 + ((len + 7) >> 3);
   }
-  block_add2w(words, 0ull, out, out + 1);
+  block_add2_4waves(words, 0ull, out, out + 1);
 }
 
 // ---- big batches: no global atomic per value ------------------------------------------------------------------
@@ -596,6 +434,24 @@ __device__ __forceinline__ void fingerprint_lds2(const FpKey &key, const uint8_t
   fp_out(s1, (uint64_t *)&f1->x, (uint64_t *)&f1->y);
 }
 
+// The end of a step of the two level-1 kernels below: the records of the lane's two rows -- row i0 and row i0 + 64 of
+// the column, `v0` / `v1`: the row exists and is not NULL -- are stamped with their rows (EXACT), counted in the tile's
+// histogram and kept in `mine` for the scatter.
+template <bool EXACT>
+__device__ __forceinline__ void fp_keep_pair(FpTileLds &s, ulonglong2 (&mine)[kFpTile / 256], int step, ulonglong2 &r0,
+                                             bool v0, ulonglong2 &r1, bool v1, uint32_t *fb_lo, int64_t i0) {
+  if (!v0) r0.x = kEmptyKey;
+  if (!v1) r1.x = kEmptyKey;
+  if (EXACT) {
+    if (v0) stamp_row(r0, fb_lo, i0);
+    if (v1) stamp_row(r1, fb_lo, i0 + 64);
+  }
+  if (r0.x != kEmptyKey) atomicAdd(&s.hist[r0.x >> 56], 1u);
+  if (r1.x != kEmptyKey) atomicAdd(&s.hist[r1.x >> 56], 1u);
+  mine[2 * step] = r0;
+  mine[2 * step + 1] = r1;
+}
+
 // level 1: a tile of rows -> fingerprints -> the kFpFan lists of bits [56, 64).  A wave takes 128 consecutive rows a
 // step, two per lane; their bytes are one span of the value buffer, copied into LDS with 16-byte loads and
 // fingerprinted from there (per-lane global loads at a ~28-byte stride read the column at 1.5 TB/s).  The pipeline
@@ -637,7 +493,7 @@ __global__ __launch_bounds__(256) void fp_partition_strings_kernel(Utf8ColDesc d
   auto valid_at = [&](uint32_t r) -> bool {
     if (r >= n_here) return false;
     const uint32_t q = vshift0 + r;
-    return !vbits || ((((global_u8_ptr)vbits0)[q >> 3] >> (q & 7)) & 1);
+    return !vbits || TGX_VALID_BIT((global_u8_ptr)vbits0, q);
   };
   // A step's offsets are kept RELATIVE to the start of its span -- the first value's start rounded down to a 16-byte
   // block by ABSOLUTE address (a block that holds a byte of the buffer lies in the buffer's pages) -- so that all the
@@ -711,42 +567,12 @@ __global__ __launch_bounds__(256) void fp_partition_strings_kernel(Utf8ColDesc d
         fingerprint(d.key, data0 + (uintptr_t)b1, (uint64_t)(e1 - b1), (uint64_t *)&r1.x, (uint64_t *)&r1.y);
       }
     }
-    if (!cur.v0) r0.x = kEmptyKey;
-    if (!cur.v1) r1.x = kEmptyKey;
-    if (EXACT) {
-      const int64_t i0 = wave_first + step * 128 + lane;
-      if (cur.v0) {
-        fb_lo[i0] = (uint32_t)r0.y;
-        r0.y = (r0.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)i0;
-      }
-      if (cur.v1) {
-        fb_lo[i0 + 64] = (uint32_t)r1.y;
-        r1.y = (r1.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)(i0 + 64);
-      }
-    }
-    if (r0.x != kEmptyKey) atomicAdd(&s.hist[r0.x >> 56], 1u);
-    if (r1.x != kEmptyKey) atomicAdd(&s.hist[r1.x >> 56], 1u);
-    mine[2 * step] = r0;
-    mine[2 * step + 1] = r1;
+    fp_keep_pair<EXACT>(s, mine, step, r0, cur.v0, r1, cur.v1, fb_lo, wave_first + step * 128 + lane);
     cur = nxt;
     nxt = after;
   }
   __syncthreads();
   fp_tile_scatter16(s, mine, (blockIdx.x % kFpXcds) * kFpFan, out, 56, counters);
-}
-
-// fingerprint() of a value of at most 16 bytes held in two registers (the logical words w0 = bytes 0..7, w1 = 8..15)
-__device__ __forceinline__ void fingerprint_words(const FpKey &key, uint64_t w0, uint64_t w1, uint32_t len,
-                                                  uint64_t *fa, uint64_t *fb) {
-  Fp s;
-  fp_init(s, key);
-  if (len < 8) w0 &= (1ull << (8 * len)) - 1;
-  if (len <= 8)
-    w1 = 0;
-  else if (len < 16)
-    w1 &= (1ull << (8 * (len - 8))) - 1;
-  fp_last(s, w0, w1, len, key);
-  fp_out(s, fa, fb);
 }
 
 // level 1 for Utf8View columns.  A value is wherever its view says: inline in the 16 view bytes up to 12 bytes (those
@@ -787,7 +613,7 @@ __global__ __launch_bounds__(256) void fp_partition_views_kernel(Utf8ColDesc d, 
     Row x;
     const bool in = r < n_here;
     const uint32_t k = in ? r : 0u, q = vshift0 + k;
-    x.valid = in && (!vbits || ((((global_u8_ptr)vbits0)[q >> 3] >> (q & 7)) & 1));
+    x.valid = in && (!vbits || TGX_VALID_BIT((global_u8_ptr)vbits0, q));
     x.v = ((global_u4_ptr)views0)[k];
     return x;
   };
@@ -892,23 +718,7 @@ __global__ __launch_bounds__(256) void fp_partition_views_kernel(Utf8ColDesc d, 
       fingerprint_words(d.key, (uint64_t)r0.v.y | ((uint64_t)r0.v.z << 32), (uint64_t)r0.v.w, len0, (uint64_t *)&f0.x, (uint64_t *)&f0.y);
     if (r1.valid && !long1)
       fingerprint_words(d.key, (uint64_t)r1.v.y | ((uint64_t)r1.v.z << 32), (uint64_t)r1.v.w, len1, (uint64_t *)&f1.x, (uint64_t *)&f1.y);
-    if (!r0.valid) f0.x = kEmptyKey;
-    if (!r1.valid) f1.x = kEmptyKey;
-    if (EXACT) {
-      const int64_t i0 = wave_first + step * 128 + lane;
-      if (r0.valid) {
-        fb_lo[i0] = (uint32_t)f0.y;
-        f0.y = (f0.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)i0;
-      }
-      if (r1.valid) {
-        fb_lo[i0 + 64] = (uint32_t)f1.y;
-        f1.y = (f1.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)(i0 + 64);
-      }
-    }
-    if (f0.x != kEmptyKey) atomicAdd(&s.hist[f0.x >> 56], 1u);
-    if (f1.x != kEmptyKey) atomicAdd(&s.hist[f1.x >> 56], 1u);
-    mine[2 * step] = f0;
-    mine[2 * step + 1] = f1;
+    fp_keep_pair<EXACT>(s, mine, step, f0, r0.valid, f1, r1.valid, fb_lo, wave_first + step * 128 + lane);
     c0 = n0;
     c1 = n1;
     n0 = a0;
@@ -949,8 +759,7 @@ __global__ __launch_bounds__(256) void fp_demote_kernel(FpLists l, const uint32_
   // an item is a record's place in the lists (list x cap + i); places beyond a list's fill hold nothing
   const uint64_t n_items = (uint64_t)(kFpFan * kFpFan) * l.cap, stride = (uint64_t)gridDim.x * blockDim.x;
   const ulonglong2 *recs = (const ulonglong2 *)l.recs;
-  auto second_word = [&](const ulonglong2 &r) -> uint64_t { return (r.y & 0xFFFFFFFF00000000ull) | (uint64_t)fb_lo[(uint32_t)r.y]; };
-  auto key_of_rec = [&](uint64_t at) -> FpOnlyKey { return FpOnlyKey{second_word(recs[at])}; };
+  auto key_of_rec = [&](uint64_t at) -> FpOnlyKey { return FpOnlyKey{stamped_second_word(recs[at], fb_lo)}; };
   unsigned long long n_new = 0, n_dup = 0;
   PendingWriter pw;
   pw.begin(t);
@@ -961,7 +770,7 @@ __global__ __launch_bounds__(256) void fp_demote_kernel(FpLists l, const uint32_
     uint64_t at = 0, fb = 0;
     if (i < (offered < l.cap ? offered : (uint32_t)l.cap)) {
       const ulonglong2 r = recs[j];
-      fb = second_word(r);
+      fb = stamped_second_word(r, fb_lo);
       int became_dup = 0;
       is_new = hash_insert_exact(t, r.x, fb, FpOnlyKey{fb}, j, key_of_rec, want_mult, 0, &became_dup, &at) != 0;
       n_new += is_new ? 1 : 0;
@@ -970,7 +779,7 @@ __global__ __launch_bounds__(256) void fp_demote_kernel(FpLists l, const uint32_
     pw.note(t, is_new, at, fb, counters);
   }
   pw.end(t);
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
 }
 // phase B of keys that are only their fingerprints (demoted lists, imported records): the second word is in the
 // pending list, the entry has no payload
@@ -1003,7 +812,7 @@ __global__ __launch_bounds__(256) void hash_rehash128_kernel(HashSetView src, Ha
     n_new += hash_insert128(dst, a, b, want_mult, two, &became_dup);
     n_dup += became_dup;
   }
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
 }
 
 __global__ __launch_bounds__(256) void hash_import128_kernel(const KeyRecord128 *recs, uint64_t n,
@@ -1017,7 +826,7 @@ __global__ __launch_bounds__(256) void hash_import128_kernel(const KeyRecord128 
     n_new += hash_insert128(dst, r.a, r.b, want_mult, r.count >= 2, &became_dup);
     n_dup += became_dup;
   }
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
 }
 
 // exact sets: incoming records are keys that are only their fingerprints
@@ -1038,7 +847,7 @@ __global__ __launch_bounds__(256) void hash_import_exact_kernel(const KeyRecord1
     pw.note(dst, is_new, at, r.b, counters);
   }
   pw.end(dst);
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
 }
 
 // the second fingerprint word of slot s: the slot's own second word, or (exact sets) the first word of its entry
@@ -1048,7 +857,7 @@ __device__ __forceinline__ uint64_t slot_fb(const HashSetView &src, uint64_t s) 
 }
 
 __device__ __forceinline__ uint32_t owner_of128(uint64_t a, uint64_t b, uint32_t world) {
-  return (uint32_t)((mix64w(a ^ rotl64(b, 32) ^ 0x9e3779b97f4a7c15ULL) >> 32) % world);
+  return (uint32_t)((mix64(a ^ rotl64(b, 32) ^ 0x9e3779b97f4a7c15ULL) >> 32) % world);
 }
 
 __global__ __launch_bounds__(256) void hash_export_count128_kernel(HashSetView src, uint32_t world,
@@ -1101,7 +910,7 @@ __device__ __forceinline__ TupleComp tuple_component(const TupleDesc &d, int c, 
   out.value = 0;
   out.p = 0;
   out.len = 0;
-  if (vbits && !((vbits[slot >> 3] >> (slot & 7)) & 1)) return out;
+  if (vbits && !TGX_VALID_BIT(vbits, slot)) return out;
   if (col.kind == 0) {  // Int64 / Float64: the 64 bits themselves
     out.kind = 1;
     out.value = (uint64_t)((global_i64_ptr)(uintptr_t)col.values)[slot];
@@ -1112,7 +921,7 @@ __device__ __forceinline__ TupleComp tuple_component(const TupleDesc &d, int c, 
   if (col.kind == 4) {  // the row's dictionary entry: the component is the entry's string (or NULL), not the index
     const int64_t ds = col.dict_offset + (int64_t)((global_i32_ptr)(uintptr_t)col.values)[slot];
     global_u8_ptr dbits = (global_u8_ptr)(uintptr_t)col.dict_validity;
-    if (dbits && !((dbits[ds >> 3] >> (ds & 7)) & 1)) return out;  // a NULL entry makes the component NULL
+    if (dbits && !TGX_VALID_BIT(dbits, ds)) return out;  // a NULL entry makes the component NULL
     if (col.dict_large) {
       global_i64_ptr off = (global_i64_ptr)(uintptr_t)col.offsets;
       b = off[ds];
@@ -1279,9 +1088,9 @@ __global__ __launch_bounds__(256) void distinct_tuple_kernel(TupleDesc d, HashSe
     n_dup += became_dup;
   }
   if (EXACT) pw.end(t);
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
   __syncthreads();
-  block_add2w(n_valid, 0ull, &counters[kCntValidRows], &counters[kCntSpare]);
+  block_add2_4waves(n_valid, 0ull, &counters[kCntValidRows], &counters[kCntSpare]);
 }
 
 __global__ __launch_bounds__(256) void exact_commit_tuple_kernel(TupleDesc d, HashSetView t, unsigned long long *counters) {
@@ -1293,7 +1102,7 @@ __global__ __launch_bounds__(256) void exact_measure_tuple_kernel(TupleDesc d, u
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.length; i += stride)
     words += 2 + TupleKey{&d, i}.payload_words();
-  block_add2w(words, 0ull, out, out + 1);
+  block_add2_4waves(words, 0ull, out, out + 1);
 }
 
 // level 1 of the lists for tuples: EVERY row is a record (a tuple with NULL components is a value of its own); the
@@ -1330,7 +1139,7 @@ __global__ __launch_bounds__(256) void fp_partition_tuples_kernel(TupleDesc d, F
           global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)col.validity;
           // (the value of a NULL slot is memory of the column like any other: read, then not looked at)
           if (in) val[k][c] = (uint64_t)((global_i64_ptr)(uintptr_t)col.values)[slot];
-          const bool valid = in && (!vbits || ((vbits[slot >> 3] >> (slot & 7)) & 1));
+          const bool valid = in && (!vbits || TGX_VALID_BIT(vbits, slot));
           ok[k] |= (valid ? 1u : 0u) << c;
         }
       }
@@ -1358,8 +1167,7 @@ __global__ __launch_bounds__(256) void fp_partition_tuples_kernel(TupleDesc d, F
         fp_out(f, (uint64_t *)&r.x, (uint64_t *)&r.y);
         const bool all_valid = ok[k] == (1u << d.n_cols) - 1u;
         if (EXACT) {
-          fb_lo[row] = (uint32_t)r.y;
-          r.y = (r.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)row;
+          stamp_row(r, fb_lo, row);
         }
         n_valid += all_valid ? 1u : 0u;
         atomicAdd(&s.hist[r.x >> 56], 1u);
@@ -1377,8 +1185,7 @@ __global__ __launch_bounds__(256) void fp_partition_tuples_kernel(TupleDesc d, F
       bool all_valid;
       tuple_fingerprint(d, row, (uint64_t *)&r.x, (uint64_t *)&r.y, &all_valid);
       if (EXACT) {
-        fb_lo[row] = (uint32_t)r.y;
-        r.y = (r.y & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)row;
+        stamp_row(r, fb_lo, row);
       }
       n_valid += all_valid ? 1u : 0u;
       atomicAdd(&s.hist[r.x >> 56], 1u);
@@ -1410,7 +1217,7 @@ __global__ __launch_bounds__(256) void dict_insert_kernel(Utf8ColDesc dict, cons
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < dict.length; e += (int64_t)gridDim.x * 256) {
     const int64_t slot = dict.offset + e;
     // an unreferenced entry, or a NULL dictionary value: nothing to insert
-    const bool live = ((seen[e >> 5] >> (e & 31)) & 1) && (!vbits || ((vbits[slot >> 3] >> (slot & 7)) & 1));
+    const bool live = ((seen[e >> 5] >> (e & 31)) & 1) && (!vbits || TGX_VALID_BIT(vbits, slot));
     bool is_new = false;
     uint64_t at = 0, fa = 0, fb = 0;
     if (live) {
@@ -1445,130 +1252,57 @@ __global__ __launch_bounds__(256) void dict_insert_kernel(Utf8ColDesc dict, cons
     if (EXACT) pw.note(t, is_new, at, fb, counters);
   }
   if (EXACT) pw.end(t);
-  block_add2w(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
+  block_add2_4waves(n_new, n_dup, &counters[kCntDistinct], &counters[kCntTwice]);
 }
 
-void launch_dict_insert(const void *offsets, const uint8_t *data, const uint8_t *validity, int64_t offset,
-                        int64_t length, int large_offsets, int want_mult, const uint32_t *seen,
-                        const uint32_t *twice, const HashSetView &t, const FpKey &key, unsigned long long *d_counters,
-                        hipStream_t stream) {
-  Utf8ColDesc d;
-  d.key = key;
-  d.offsets = offsets;
-  d.data = data;
-  d.views = nullptr;
-  d.buffers = nullptr;
-  d.validity = validity;
-  d.offset = offset;
-  d.length = length;
-  d.large_offsets = large_offsets;
-  d.want_multiplicity = want_mult;
-  int64_t blocks = (length + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
+void launch_dict_insert(const Utf8ColDesc &d, const uint32_t *seen, const uint32_t *twice, const HashSetView &t,
+                        unsigned long long *d_counters, hipStream_t stream) {
   if (t.store) {
-    const dim3 grid(exact_blocks((uint64_t)length));  // (the shape the pending list's regions were laid out for)
+    const dim3 grid(exact_blocks((uint64_t)d.length));  // (the shape the pending list's regions were laid out for)
     hipLaunchKernelGGL(dict_insert_kernel<true>, grid, dim3(256), 0, stream, d, seen, twice, t, d_counters);
     hipLaunchKernelGGL(exact_commit_utf8_kernel, grid, dim3(256), 0, stream, d, t, d_counters);
   } else
-    hipLaunchKernelGGL(dict_insert_kernel<false>, dim3((int)blocks), dim3(256), 0, stream, d, seen, twice, t, d_counters);
+    hipLaunchKernelGGL(dict_insert_kernel<false>, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, seen, twice,
+                       t, d_counters);
 }
 
-void launch_distinct_tuple(const TupleDesc &d, const HashSetView &t, unsigned long long *d_counters,
-                           hipStream_t stream);
-static inline int grid_for128(uint64_t items) {
-  uint64_t blocks = (items + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  return (int)blocks;
-}
-
-void launch_distinct_utf8(const void *offsets, const uint8_t *data, const void *views,
-                          const uint8_t *const *buffers, const uint8_t *validity, int64_t offset,
-                          int64_t length, int large_offsets, int want_mult, const HashSetView &t, const FpKey &key,
-                          unsigned long long *d_counters, hipStream_t stream) {
-  Utf8ColDesc d;
-  d.key = key;
-  d.offsets = offsets;
-  d.data = data;
-  d.views = views;
-  d.buffers = buffers;
-  d.validity = validity;
-  d.offset = offset;
-  d.length = length;
-  d.large_offsets = large_offsets;
-  d.want_multiplicity = want_mult;
+void launch_distinct_utf8(const Utf8ColDesc &d, const HashSetView &t, unsigned long long *d_counters,
+                          hipStream_t stream) {
   if (t.store) {
-    const dim3 grid(exact_blocks((uint64_t)length));
+    const dim3 grid(exact_blocks((uint64_t)d.length));
     hipLaunchKernelGGL(distinct_utf8_kernel<true>, grid, dim3(256), 0, stream, d, t, d_counters);
     hipLaunchKernelGGL(exact_commit_utf8_kernel, grid, dim3(256), 0, stream, d, t, d_counters);
   } else
-    hipLaunchKernelGGL(distinct_utf8_kernel<false>, dim3(grid_for128((uint64_t)length)), dim3(256), 0, stream, d, t,
+    hipLaunchKernelGGL(distinct_utf8_kernel<false>, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, t,
                        d_counters);
 }
 
 // exact key sets: the words of key store the batch can need at most -> out[0] (out[0..1] zeroed by the caller);
 // `dict_seen`: the column is a dictionary's values and only the entries marked there count
-void launch_exact_measure_utf8(const void *offsets, const uint8_t *data, const void *views,
-                               const uint8_t *const *buffers, const uint8_t *validity, int64_t offset, int64_t length,
-                               int large_offsets, const uint32_t *dict_seen, unsigned long long *out,
+void launch_exact_measure_utf8(const Utf8ColDesc &d, const uint32_t *dict_seen, unsigned long long *out,
                                hipStream_t stream) {
-  Utf8ColDesc d;
-  memset(&d, 0, sizeof(d));
-  d.offsets = offsets;
-  d.data = data;
-  d.views = views;
-  d.buffers = buffers;
-  d.validity = validity;
-  d.offset = offset;
-  d.length = length;
-  d.large_offsets = large_offsets;
-  hipLaunchKernelGGL(exact_measure_utf8_kernel, dim3(grid_for128((uint64_t)length)), dim3(256), 0, stream, d, dict_seen,
+  hipLaunchKernelGGL(exact_measure_utf8_kernel, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, dict_seen,
                      out);
 }
 void launch_exact_measure_tuple(const TupleDesc &d, unsigned long long *out, hipStream_t stream) {
-  hipLaunchKernelGGL(exact_measure_tuple_kernel, dim3(grid_for128((uint64_t)d.length)), dim3(256), 0, stream, d, out);
+  hipLaunchKernelGGL(exact_measure_tuple_kernel, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, out);
 }
 
-void launch_fp_partition_strings(const void *offsets, const uint8_t *data, const uint8_t *validity, int64_t offset,
-                                 int64_t length, int large_offsets, const FpLists &level1, const FpKey &key,
-                                 uint32_t *exact_fb_lo, unsigned long long *d_counters, hipStream_t stream) {
-  Utf8ColDesc d;
-  memset(&d, 0, sizeof(d));
-  d.key = key;
-  d.offsets = offsets;
-  d.data = data;
-  d.validity = validity;
-  d.offset = offset;
-  d.length = length;
-  d.large_offsets = large_offsets;
-  const int64_t tiles = (length + kFpTile - 1) / kFpTile;
-  if (exact_fb_lo)
-    hipLaunchKernelGGL(fp_partition_strings_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, d, level1, exact_fb_lo,
-                       d_counters);
-  else
-    hipLaunchKernelGGL(fp_partition_strings_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, d, level1,
-                       (uint32_t *)nullptr, d_counters);
-}
-
-void launch_fp_partition_views(const void *views, const uint8_t *const *buffers, const uint8_t *validity,
-                               int64_t offset, int64_t length, const FpLists &level1, const FpKey &key,
-                               uint32_t *exact_fb_lo, unsigned long long *d_counters, hipStream_t stream) {
-  Utf8ColDesc d;
-  memset(&d, 0, sizeof(d));
-  d.key = key;
-  d.views = views;
-  d.buffers = buffers;
-  d.validity = validity;
-  d.offset = offset;
-  d.length = length;
-  const int64_t tiles = (length + kFpTile - 1) / kFpTile;
-  if (exact_fb_lo)
-    hipLaunchKernelGGL(fp_partition_views_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, d, level1, exact_fb_lo,
-                       d_counters);
-  else
-    hipLaunchKernelGGL(fp_partition_views_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, d, level1,
-                       (uint32_t *)nullptr, d_counters);
+// level 1 of a string column's lists: the kernel for its layout (views / offsets); `exact_fb_lo`: see stamp_row()
+void launch_fp_partition_utf8(const Utf8ColDesc &d, const FpLists &level1, uint32_t *exact_fb_lo,
+                              unsigned long long *d_counters, hipStream_t stream) {
+  const dim3 grid((unsigned)((d.length + kFpTile - 1) / kFpTile)), block(256);
+  if (d.views) {
+    if (exact_fb_lo)
+      hipLaunchKernelGGL(fp_partition_views_kernel<true>, grid, block, 0, stream, d, level1, exact_fb_lo, d_counters);
+    else
+      hipLaunchKernelGGL(fp_partition_views_kernel<false>, grid, block, 0, stream, d, level1, (uint32_t *)nullptr, d_counters);
+  } else {
+    if (exact_fb_lo)
+      hipLaunchKernelGGL(fp_partition_strings_kernel<true>, grid, block, 0, stream, d, level1, exact_fb_lo, d_counters);
+    else
+      hipLaunchKernelGGL(fp_partition_strings_kernel<false>, grid, block, 0, stream, d, level1, (uint32_t *)nullptr, d_counters);
+  }
 }
 
 void launch_fp_partition_tuples(const TupleDesc &d, const FpLists &level1, uint32_t *exact_fb_lo,
@@ -1599,49 +1333,18 @@ void launch_fp_partition_lists(const FpLists &level1, const FpLists &level2, uns
                      tiles_per_list, level2, d_counters);
 }
 
-template <class EQ>
-static void launch_fp_count_eq(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
-                               unsigned long long *d_counters, hipStream_t stream, const EQ &eq) {
-  // the table holds a list at load <= 3/4: 16 KiB of LDS (eight workgroups a CU) up to 3072 records a list, i.e.
-  // batches up to ~157 M rows; 64 / 128 KiB for batches up to ~0.6 / ~1.4 G rows
-  const dim3 grid(kFpFan * kFpFan);
-  if (level2.cap <= 3072)
-    hipLaunchKernelGGL((fp_count_kernel<4096, 256, ulonglong2, EQ>), grid, dim3(256), 0, stream, level2, want_mult, per_list,
-                       (uint32_t)(kFpFan * kFpFan), eq);
-  else if (level2.cap <= 12288)
-    hipLaunchKernelGGL((fp_count_kernel<16384, 1024, ulonglong2, EQ>), grid, dim3(1024), 0, stream, level2, want_mult, per_list,
-                       (uint32_t)(kFpFan * kFpFan), eq);
-  else
-    hipLaunchKernelGGL((fp_count_kernel<32768, 1024, ulonglong2, EQ>), dim3(fp_resident_grid()), dim3(1024), 0, stream, level2,
-                       want_mult, per_list, (uint32_t)(kFpFan * kFpFan), eq);  // one workgroup per CU, each walking its share of the lists
-  hipLaunchKernelGGL(fp_totals_kernel<ulonglong2>, dim3(64), dim3(256), 0, stream, per_list, (uint32_t)(kFpFan * kFpFan), offered1,
-                     d_counters);
-}
 void launch_fp_count(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
                      unsigned long long *d_counters, hipStream_t stream) {
-  launch_fp_count_eq(level2, want_mult, per_list, offered1, d_counters, stream, PlainEq());
+  launch_fp_count_lists<ulonglong2>(level2, want_mult, per_list, offered1, d_counters, stream, PlainEq());
 }
-// exact sets: equal fingerprints are settled on the rows' bytes (the batch the records were made from)
+// exact sets: equal fingerprints are settled on the rows' bytes (`d`: the batch the records were made from)
 void launch_fp_count_exact_utf8(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
-                                const void *offsets, const uint8_t *data, const void *views, const uint8_t *const *buffers,
-                                int64_t offset, int64_t length, int large_offsets, unsigned long long *d_counters,
-                                hipStream_t stream) {
-  ExactUtf8Eq eq;
-  memset(&eq, 0, sizeof(eq));
-  eq.d.offsets = offsets;
-  eq.d.data = data;
-  eq.d.views = views;
-  eq.d.buffers = buffers;
-  eq.d.offset = offset;
-  eq.d.length = length;
-  eq.d.large_offsets = large_offsets;
-  launch_fp_count_eq(level2, want_mult, per_list, offered1, d_counters, stream, eq);
+                                const Utf8ColDesc &d, unsigned long long *d_counters, hipStream_t stream) {
+  launch_fp_count_lists<ulonglong2>(level2, want_mult, per_list, offered1, d_counters, stream, ExactUtf8Eq{d});
 }
 void launch_fp_count_exact_tuple(const FpLists &level2, int want_mult, uint2 *per_list, const TupleDesc &d,
                                  unsigned long long *d_counters, hipStream_t stream) {
-  ExactTupleEq eq;
-  eq.d = d;
-  launch_fp_count_eq(level2, want_mult, per_list, nullptr, d_counters, stream, eq);
+  launch_fp_count_lists<ulonglong2>(level2, want_mult, per_list, nullptr, d_counters, stream, ExactTupleEq{d});
 }
 void launch_fp_demote(const FpLists &level2, const uint32_t *fb_lo, const HashSetView &t, int want_mult,
                       unsigned long long *d_counters, hipStream_t stream) {
@@ -1656,7 +1359,7 @@ void launch_fp_insert(const FpLists &level2, const HashSetView &t, int want_mult
 
 void launch_hash_rehash128(const HashSetView &src, const HashSetView &dst, int want_mult,
                            unsigned long long *d_counters, hipStream_t stream) {
-  hipLaunchKernelGGL(hash_rehash128_kernel, dim3(grid_for128(src.mask + 1)), dim3(256), 0, stream, src, dst,
+  hipLaunchKernelGGL(hash_rehash128_kernel, dim3(grid_for(src.mask + 1)), dim3(256), 0, stream, src, dst,
                      want_mult, d_counters);
 }
 
@@ -1668,19 +1371,19 @@ void launch_hash_import128(const KeyRecord128 *recs, uint64_t n, const HashSetVi
     hipLaunchKernelGGL(hash_import_exact_kernel, grid, dim3(256), 0, stream, recs, n, dst, want_mult, d_counters);
     hipLaunchKernelGGL(exact_commit_fponly_kernel, grid, dim3(256), 0, stream, dst, d_counters);
   } else
-    hipLaunchKernelGGL(hash_import128_kernel, dim3(grid_for128(n)), dim3(256), 0, stream, recs, n, dst,
+    hipLaunchKernelGGL(hash_import128_kernel, dim3(grid_for(n)), dim3(256), 0, stream, recs, n, dst,
                        want_mult, d_counters);
 }
 
 void launch_hash_export_count128(const HashSetView &src, uint32_t world, unsigned long long *d_counts,
                                  hipStream_t stream) {
-  hipLaunchKernelGGL(hash_export_count128_kernel, dim3(grid_for128(src.mask + 1)), dim3(256), 0, stream, src,
+  hipLaunchKernelGGL(hash_export_count128_kernel, dim3(grid_for(src.mask + 1)), dim3(256), 0, stream, src,
                      world, d_counts);
 }
 
 void launch_hash_export_scatter128(const HashSetView &src, uint32_t world, int want_mult,
                                    unsigned long long *d_cursors, KeyRecord128 *out, hipStream_t stream) {
-  hipLaunchKernelGGL(hash_export_scatter128_kernel, dim3(grid_for128(src.mask + 1)), dim3(256), 0, stream, src,
+  hipLaunchKernelGGL(hash_export_scatter128_kernel, dim3(grid_for(src.mask + 1)), dim3(256), 0, stream, src,
                      world, want_mult, d_cursors, out);
 }
 
@@ -1691,7 +1394,7 @@ void launch_distinct_tuple(const TupleDesc &d, const HashSetView &t, unsigned lo
     hipLaunchKernelGGL(distinct_tuple_kernel<true>, grid, dim3(256), 0, stream, d, t, d_counters);
     hipLaunchKernelGGL(exact_commit_tuple_kernel, grid, dim3(256), 0, stream, d, t, d_counters);
   } else
-    hipLaunchKernelGGL(distinct_tuple_kernel<false>, dim3(grid_for128((uint64_t)d.length)), dim3(256), 0, stream, d, t,
+    hipLaunchKernelGGL(distinct_tuple_kernel<false>, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, t,
                        d_counters);
 }
 

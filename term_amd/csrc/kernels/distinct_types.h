@@ -1,4 +1,4 @@
-// Views of the device-resident key sets behind TGX_CHECK_DISTINCT (see distinct.hip).
+// Views of the device-resident key sets behind TGX_CHECK_DISTINCT (see distinct.hip, partition.hip, distinct128.hip).
 #pragma once
 #include <stdint.h>
 
@@ -47,7 +47,7 @@ inline uint64_t exact_region(uint64_t items) {  // rows a wave of the grid-strid
   return (items + threads - 1) / threads * 64;
 }
 
-// The 128-bit key of the fingerprint function (Chaskey's K, K1 = 2K, K2 = 4K in GF(2^128); distinct128.hip).  Drawn from
+// The 128-bit key of the fingerprint function (Chaskey's K, K1 = 2K, K2 = 4K in GF(2^128); fingerprint.h).  Drawn from
 // the OS at tgx_plan_create (or set by the caller: every rank / every state that exchanges keys must hold the same one).
 struct FpKey {
   uint32_t k[4], k1[4], k2[4];
@@ -67,6 +67,20 @@ inline FpKey fp_key_expand(const uint32_t k[4]) {
   return key;
 }
 
+// the kernels' view of a string column (Utf8 / LargeUtf8 / Utf8View, or the values of a dictionary)
+struct Utf8ColDesc {
+  const void *offsets;
+  const uint8_t *data;
+  const uint8_t *validity;
+  int64_t offset;
+  int64_t length;
+  int32_t large_offsets;
+  int32_t want_multiplicity;
+  const void *views;              // Utf8View: 16-byte views (then offsets / data are unused)
+  const uint8_t *const *buffers;  // Utf8View: device array of the data buffers' device pointers
+  FpKey key;                      // of the plan
+};
+
 struct BitmapView {
   uint32_t *seen;   // bit (key - base)
   uint32_t *twice;  // same indexing; only with multiplicity
@@ -74,7 +88,7 @@ struct BitmapView {
   uint64_t range;   // number of representable keys
 };
 
-// Range-partitioned population of the bitmap (distinct.hip, partition_kernel / bucket_apply_kernel):
+// Range-partitioned population of the bitmap (partition.hip, partition_kernel / bucket_apply_kernel):
 // phase 1 scatters (key - base) into P = ceil(range / 2^sub_bits) bucket lists of 32-bit in-bucket
 // offsets; phase 2 replays each list against its 2^sub_bits-bit slice of the bitmap held in LDS.
 constexpr uint32_t kMaxPartitions = 2048;
@@ -167,7 +181,7 @@ struct FpLists {
   uint64_t cap;
 };
 
-// counters[] slots shared by the kernels of distinct.hip
+// counters[] slots shared by the kernels of the key sets (distinct.hip, partition.hip, distinct128.hip, lists.h)
 enum {
   kCntDistinct = 0,   // keys in the set (excluding the EMPTY stand-in)
   kCntTwice = 1,      // keys seen at least twice

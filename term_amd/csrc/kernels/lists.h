@@ -263,4 +263,24 @@ __global__ __launch_bounds__(256) void fp_totals_kernel(const uint2 *per_list, u
   }
 }
 
+// The final lists deduplicated and the batch's counts added up.  The table holds a list at load <= 3/4: 16 KiB of LDS
+// (eight workgroups a CU) up to 3072 records a list, i.e. batches up to ~157 M rows; 64 / 128 KiB for batches up to
+// ~0.6 / ~1.4 G rows.
+template <class REC, class EQ>
+static inline void launch_fp_count_lists(const FpLists &level2, int want_mult, uint2 *per_list, const uint32_t *offered1,
+                                         unsigned long long *d_counters, hipStream_t stream, const EQ &eq) {
+  const uint32_t n_lists = kFpFan * kFpFan;
+  const dim3 grid(n_lists);
+  if (level2.cap <= 3072)
+    hipLaunchKernelGGL((fp_count_kernel<4096, 256, REC, EQ>), grid, dim3(256), 0, stream, level2, want_mult, per_list,
+                       n_lists, eq);
+  else if (level2.cap <= 12288)
+    hipLaunchKernelGGL((fp_count_kernel<16384, 1024, REC, EQ>), grid, dim3(1024), 0, stream, level2, want_mult, per_list,
+                       n_lists, eq);
+  else  // one workgroup per CU, each walking its share of the lists
+    hipLaunchKernelGGL((fp_count_kernel<32768, 1024, REC, EQ>), dim3(fp_resident_grid()), dim3(1024), 0, stream, level2,
+                       want_mult, per_list, n_lists, eq);
+  hipLaunchKernelGGL(fp_totals_kernel<REC>, dim3(64), dim3(256), 0, stream, per_list, n_lists, offered1, d_counters);
+}
+
 }  // namespace tgx

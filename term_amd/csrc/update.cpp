@@ -525,7 +525,7 @@ BatchFusion decide_fusion(const tgx_plan *plan, tgx_state *st, const tgx_column 
 // their end: across ranks the exchange of the key sets (tgx_allreduce) can then run on a second stream while the scan
 // of the other columns is still running (the >= 6x target is set by the exchange).
 //
-// Exact uniqueness over dense Int64 keys takes the column's range aggregates along (kernels/distinct.hip,
+// Exact uniqueness over dense Int64 keys takes the column's range aggregates along (kernels/partition.hip,
 // partition_kernel<.., STATS>): such a column is not scanned at all -- it crosses HBM once for MIN / MAX / SUM / COUNT
 // and COUNT(DISTINCT) together.  Decided here, before the scan is queued, from a sample of the batch.
 tgx_status early_key_passes(const tgx_plan *plan, tgx_state *st, const tgx_column *dev, const tgx_column *columns,

@@ -1,4 +1,4 @@
-"""Test infrastructure: a Python statement of the library's keyed fingerprint (term_amd/csrc/kernels/distinct128.hip:
+"""Test infrastructure: a Python statement of the library's keyed fingerprint (term_amd/csrc/kernels/fingerprint.h:
 Chaskey-8 over the value's 16-byte blocks), and -- because the function is keyed, not collision-free for whoever HOLDS the
 key -- a generator of distinct values with equal fingerprints under a given key.  The GPU tests hand a plan a known key,
 feed such pairs, and expect a fingerprint set to count them once (the deviation, stated) and an EXACT set

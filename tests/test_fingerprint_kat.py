@@ -1,7 +1,7 @@
 """The keyed fingerprint is Chaskey-8 as published (N. Mouha, B. Mennink, A. Van Herrewege, D. Watanabe, B. Preneel,
 I. Verbauwhede: "Chaskey: An Efficient MAC Algorithm for 32-bit Microcontrollers", SAC 2014): the Python statement of
 it the GPU tests hold the kernels to (tests/fp_reference.py; tests/test_gpu_exact_keys.py compares it with
-`distinct128.hip` record by record) reproduces the known answers of the authors' reference implementation -- key
+`fingerprint.h` record by record) reproduces the known answers of the authors' reference implementation -- key
 833D3433 009F389F 2398E64F 417ACF39 (little-endian words), messages m[i] = i of 0 .. 4 bytes, the tag as four
 little-endian words.  CPU only: no kernel is called here."""
 import struct

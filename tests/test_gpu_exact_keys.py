@@ -2,7 +2,7 @@
 
 The reference counts by value: DataFusion's hash aggregation groups with hash + equality
 (TG/constraints/uniqueness.rs:612-617, 671-681, 709-715).  The library reduces string / tuple keys to 128-bit keyed
-fingerprints (kernels/distinct128.hip: Chaskey-8 under the plan's key); whoever holds the key can write down distinct
+fingerprints (kernels/fingerprint.h: Chaskey-8 under the plan's key); whoever holds the key can write down distinct
 values with one fingerprint (tests/fp_reference.py does), whoever does not cannot.  Two things are pinned here:
 
 * an EXACT key set (TGX_FLAG_EXACT_KEYS) counts such values as the oracle does on every route that feeds a state --

@@ -1,6 +1,6 @@
 """-m gpu: the dense uniqueness pass over keys that arrive IN ORDER (ids that grow with the row number, timestamps).
 
-The rows a wave holds then share a bucket, so partition_kernel runs its CLUSTERED form (kernels/distinct.hip: a tile
+The rows a wave holds then share a bucket, so partition_kernel runs its CLUSTERED form (kernels/partition.hip: a tile
 whose keys span less than 2^20 values is OR-ed into a bitmap of that stretch in LDS and from there into the global
 bitmap -- no lists; otherwise one LDS add per wave instead of 64 on one address, long runs streamed out by the whole
 workgroup, bucket_apply_kernel merging the bits of neighbouring lanes) once partition_init_kernel's probe has seen it.  Whatever the order of the

@@ -606,7 +606,7 @@ def test_outliers_in_a_later_batch_and_through_merge_and_serialize():
 @pytest.mark.parametrize("shape", ["shuffled", "two_batches_nulls", "skewed"])
 def test_distinct_partitioned_bitmap_20_bit_entries(shape, with_stats, monkeypatch):
     """A dense range of more than 2048 x 2^16 values (no 2-byte entries) without multiplicity: the bucket lists hold 20-bit
-    entries, three to an 8-byte word, runs padded to 24 entries by repeating their last key (kernels/distinct.hip, PACK20;
+    entries, three to an 8-byte word, runs padded to 24 entries by repeating their last key (kernels/partition.hip, PACK20;
     the keys-in-order form of the same lists: tests/test_gpu_ordered_keys.py `ascending_step64`).  Bit-exact against the
     oracle, and equal to the 4-byte lists (TGX_PACK20=0)."""
     rng = np.random.default_rng(zlib.crc32(shape.encode()) + int(with_stats))
