@@ -181,7 +181,25 @@ typedef enum tgx_check_kind {
    * reference's own tests allow 3 %), total, non_null.  Int64 / Float64 / Int32 / Float32 columns (Float64 by bit
    * pattern, like DISTINCT); on string and dictionary columns -- and whenever the plan also holds an exact DISTINCT
    * check of the column -- the exact count answers (it satisfies every bound the estimate does). */
-  TGX_CHECK_APPROX_DISTINCT = 9
+  TGX_CHECK_APPROX_DISTINCT = 9,
+  /* The joint bin counts behind MutualInformationAnalyzer's numeric x numeric branch
+   *                                            TG/analyzers/advanced/mutual_information.rs:143-248
+   * over the pair (`column`, `column2`), every value CAST AS DOUBLE, in TWO PHASES -- the bin edges depend on the whole
+   * table, so the reference scans twice and so does the caller here:
+   *   range phase (no binning set on the spec): n and MIN / MAX of both columns over the rows where both sides are
+   *     non-NULL and finite; read with tgx_joint_range_get;
+   *   count phase (tgx_plan_set_joint_binning was called for the spec): per such row
+   *     i = FLOOR((x - x_origin) / x_width), j = FLOOR((y - y_origin) / y_width), evaluated in IEEE double arithmetic
+   *     exactly as written (the division is correctly rounded), and cell (i, j) of a (bins + 1) x (bins + 1) table of
+   *     64-bit counts goes up by one (the column's maximum lands in bin `bins` or `bins - 1`); read with
+   *     tgx_joint_counts.
+   * A row with a NULL on either side is dropped (as COMOMENTS does).  A row with a NaN or an infinity on either side
+   * is left out of n, the range and the cells and counted as `non_finite` (the reference's own behaviour there is an
+   * accident of FLOOR(NaN) and pinned by nothing).  tgx_result carries total (rows seen) and non_null (n).
+   * Columns: Int64, Float64, and Int32 / Float32 / Int8 .. UInt32 through the widening staging; UInt64, Boolean and every
+   * string layout are TGX_UNSUPPORTED.  The state is additive: tgx_merge, state blobs and tgx_allreduce combine the
+   * extremes by MIN / MAX and n and the cells by addition. */
+  TGX_CHECK_JOINT_BINS = 10
 } tgx_check_kind;
 
 enum {
@@ -211,7 +229,7 @@ enum {
 typedef struct tgx_check_spec {
   int32_t kind;         /* tgx_check_kind */
   int32_t column;       /* index into the columns array handed to tgx_update */
-  int32_t column2;      /* COMOMENTS / SPEARMAN: second column; otherwise -1 */
+  int32_t column2;      /* COMOMENTS / SPEARMAN / JOINT_BINS: second column; otherwise -1 */
   uint32_t flags;
   const char *pattern;  /* REGEX: pattern bytes (Rust `regex` syntax), not NUL-terminated */
   uint64_t pattern_len;
@@ -323,6 +341,22 @@ size_t tgx_plan_num_specs(const tgx_plan *plan);
 tgx_status tgx_plan_set_fingerprint_key(tgx_plan *plan, const uint8_t key[16], tgx_error *err);
 tgx_status tgx_plan_get_fingerprint_key(const tgx_plan *plan, uint8_t key_out[16]);
 
+/* TGX_CHECK_JOINT_BINS: the binning of spec `spec_index`, which puts the spec into its COUNT phase.  Like the
+ * fingerprint key it can be set until the plan's first state exists; afterwards (and for a spec of another kind) the
+ * call is refused with TGX_INVALID_ARGUMENT.  `bins` runs from 2 to TGX_JOINT_MAX_BINS: the (bins + 1)^2 cells are
+ * counted in a workgroup's LDS with 32-bit counters (128^2 x 4 B = 64 KiB); more bins are TGX_UNSUPPORTED (there is no
+ * global-memory path).  Origins must be finite and widths finite and positive: a range whose difference MAX - MIN
+ * overflows to infinity has no bin width and is an error (TGX_INVALID_ARGUMENT) here.  The reference's values are
+ * origin = MIN, width = (MAX - MIN) > 0 ? (MAX - MIN) / bins : 1.0 (mutual_information.rs:219-233). */
+#define TGX_JOINT_MAX_BINS 127
+typedef struct tgx_joint_binning {
+  double x_origin, x_width, y_origin, y_width;
+  uint32_t bins;
+  uint32_t reserved;
+} tgx_joint_binning;
+tgx_status tgx_plan_set_joint_binning(tgx_plan *plan, size_t spec_index, const tgx_joint_binning *binning,
+                                      tgx_error *err);
+
 /* State = `Analyzer::State` for every spec of the plan (TG/analyzers/traits.rs:154-179).
  * `hip_stream` is a hipStream_t (NULL = a stream the library creates).  Everything the state does on the device is
  * queued on that stream and nowhere else: a DEVICE buffer handed to tgx_update has to be COMPLETE as far as that
@@ -414,6 +448,24 @@ tgx_status tgx_kll_level_items(const tgx_plan *plan, tgx_state *state, size_t sp
                                tgx_error *err);
 double tgx_kll_relative_error_bound(uint32_t k);
 
+/* ---- joint bin counts (TGX_CHECK_JOINT_BINS; TG/analyzers/advanced/mutual_information.rs:143-248) --------------- */
+typedef struct tgx_joint_range {
+  uint64_t total;       /* rows seen */
+  uint64_t n;           /* rows with both sides non-NULL and finite */
+  uint64_t non_finite;  /* rows with both sides non-NULL and a NaN or an infinity on either side */
+  double x_min, x_max, y_min, y_max; /* over the n rows; NaN when n == 0 */
+} tgx_joint_range;
+/* a spec in its range phase; a spec in its count phase answers total, n (the sum of its cells) and non_finite and
+ * leaves the extremes NaN */
+tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_joint_range *out,
+                               tgx_error *err);
+/* a spec in its count phase: the (bins + 1)^2 cell counts, row-major (cell (i, j) at i * (bins + 1) + j), into the
+ * caller's `cells` (`cap` entries; NULL / too small: only *n_cells is written and the call returns
+ * TGX_INVALID_ARGUMENT when cells is non-NULL).  *out_of_range = rows whose index fell outside [0, bins] on either
+ * side -- a table that changed between the two passes; they are in no cell. */
+tgx_status tgx_joint_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, uint64_t *cells, uint64_t cap,
+                            uint64_t *n_cells, uint64_t *out_of_range, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -503,7 +555,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments"; "distinct_lists" is the share of
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);
 tgx_status tgx_profile_get(tgx_state *state, const char *kernel, double *total_ms,

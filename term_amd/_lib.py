@@ -9,6 +9,8 @@ _ROOT = os.path.dirname(_HERE)
 # enums of include/tgx.h
 COUNT, NUMERIC_STATS, DISTINCT, REGEX_MATCH, KLL, COMOMENTS, SPEARMAN, LENGTH = 1, 2, 3, 4, 5, 6, 7, 8
 APPROX_DISTINCT = 9
+JOINT_BINS = 10  # joint bin counts of a numeric pair, in two phases (Plan.set_joint_binning)
+JOINT_MAX_BINS = 127
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -64,6 +66,18 @@ class Result(C.Structure):
         ("co_mean_x", C.c_double), ("co_mean_y", C.c_double), ("co_m2_x", C.c_double), ("co_m2_y", C.c_double),
         ("co_c_xy", C.c_double),
     ]
+
+
+class JointBinning(C.Structure):
+    """tgx_joint_binning (include/tgx.h)"""
+    _fields_ = [("x_origin", C.c_double), ("x_width", C.c_double), ("y_origin", C.c_double), ("y_width", C.c_double),
+                ("bins", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class JointRange(C.Structure):
+    """tgx_joint_range (include/tgx.h)"""
+    _fields_ = [("total", C.c_uint64), ("n", C.c_uint64), ("non_finite", C.c_uint64), ("x_min", C.c_double),
+                ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double)]
 
 
 class _Options(C.Structure):
@@ -173,6 +187,9 @@ def lib():
         L.tgx_regex_is_match.argtypes = [C.c_char_p, sz, C.c_uint32, C.c_char_p, sz, C.POINTER(C.c_int32), E]
         L.tgx_cache_stats_get.argtypes = [C.POINTER(CacheStats)]
         L.tgx_state_pending.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.tgx_plan_set_joint_binning.argtypes = [vp, sz, C.POINTER(JointBinning), E]
+        L.tgx_joint_range_get.argtypes = [vp, vp, sz, C.POINTER(JointRange), E]
+        L.tgx_joint_counts.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), C.POINTER(u64), E]
         _LIB = L
     return _LIB
 
@@ -559,6 +576,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_fingerprint_key(self.h, key, C.byref(err)), err)
 
+    def set_joint_binning(self, spec_index, x_origin, x_width, y_origin, y_width, bins):
+        """tgx_plan_set_joint_binning: puts a JOINT_BINS spec into its count phase (before the plan's first state)"""
+        b = JointBinning(x_origin, x_width, y_origin, y_width, bins, 0)
+        err = _Error()
+        _check(lib().tgx_plan_set_joint_binning(self.h, spec_index, C.byref(b), C.byref(err)), err)
+
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
         lib().tgx_plan_get_fingerprint_key(self.h, out)
@@ -692,6 +715,24 @@ class State:
         _check(lib().tgx_kll_level_items(self.plan.h, self.h, spec_index, level, out.ctypes.data, cnt.value,
                                          C.byref(cnt), C.byref(err)), err)
         return out[: cnt.value]
+
+    # joint bin counts
+    def joint_range(self, spec_index):
+        """tgx_joint_range_get: dict(total, n, non_finite, x_min, x_max, y_min, y_max)"""
+        out = JointRange()
+        err = _Error()
+        _check(lib().tgx_joint_range_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return {name: getattr(out, name) for name, _ in JointRange._fields_}
+
+    def joint_counts(self, spec_index):
+        """tgx_joint_counts: (the (bins + 1)^2 cell counts, row-major, as a list of ints; rows outside [0, bins])"""
+        n, outside = C.c_uint64(), C.c_uint64()
+        err = _Error()
+        _check(lib().tgx_joint_counts(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, C.byref(err)), err)
+        cells = (C.c_uint64 * max(1, n.value))()
+        _check(lib().tgx_joint_counts(self.plan.h, self.h, spec_index, cells, n.value, C.byref(n), C.byref(outside),
+                                      C.byref(err)), err)
+        return list(cells)[: n.value], outside.value
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "internal.h"
+#include "jointbins_device.h"
 #include "kll_device.h"
 #include "regex_device.h"
 #include "spearman_device.h"

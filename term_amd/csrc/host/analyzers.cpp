@@ -405,6 +405,154 @@ class CorrelationAnalyzer : public Analyzer {  // advanced/correlation.rs
   Type t_;
 };
 
+// advanced/mutual_information.rs, numeric x numeric branch (:143-248): two passes -- MIN / MAX of both columns over the
+// rows with both sides non-NULL, then COUNT(*) GROUP BY FLOOR((x - x_min) / x_width), FLOOR((y - y_min) / y_width) --
+// both on the device (TGX_CHECK_JOINT_BINS).  Categorical columns (the reference's other three branches group by the
+// string value) are outside the path: the library answers TGX_UNSUPPORTED and that is this analyzer's error.
+//
+// State: the reference's struct is {n, joint_counts: HashMap<(String, String), u64>, x_counts, y_counts, bins} -- and
+// serde_json cannot write a map with tuple keys at all ("key must be a string"), so there is no reference format to
+// match for `joint_counts`: here it is a list of [x_label, y_label, count], non-empty cells only, in row-major order.
+// `n` and `bins` are integer tokens, x_counts / y_counts maps keyed by the bin label.  A label is the Float64 bin
+// index as Arrow casts it to text ("0.0", "1.0", ...: CAST(FLOOR(..) AS VARCHAR)).
+class MutualInformationAnalyzer : public Analyzer {
+ public:
+  MutualInformationAnalyzer(std::string a, std::string b, uint64_t bins)
+      : a_(std::move(a)), b_(std::move(b)), bins_(std::max<uint64_t>(bins, 2)) {}  // :96-104
+  std::string name() const override { return "mutual_information"; }
+  std::string metric_key() const override { return "mutual_information_" + a_ + "_" + b_; }  // :413-415
+  std::vector<std::string> columns() const override { return {a_, b_}; }
+  std::vector<SpecRequest> plan() const override {
+    SpecRequest r = req(TGX_CHECK_JOINT_BINS, a_);
+    r.column2 = b_;
+    return {r};
+  }
+  bool two_pass() const override { return true; }
+  std::optional<tgx_joint_binning> follow_up(const tgx_joint_range &range) const override {
+    if (range.n == 0) return std::nullopt;
+    if (bins_ > TGX_JOINT_MAX_BINS)
+      throw AnalyzerError::query("TGX_UNSUPPORTED: " + std::to_string(bins_) + " bins: at most " +
+                                 std::to_string(TGX_JOINT_MAX_BINS) + " are supported");
+    tgx_joint_binning b;
+    memset(&b, 0, sizeof(b));
+    // :219-233, in the same double arithmetic
+    const double x_range = range.x_max - range.x_min, y_range = range.y_max - range.y_min;
+    if (!std::isfinite(x_range) || !std::isfinite(y_range))
+      throw AnalyzerError::invalid_data("the range of " + (std::isfinite(x_range) ? b_ : a_) +
+                                        " overflows a double: no bin width");
+    b.x_origin = range.x_min;
+    b.x_width = x_range > 0.0 ? x_range / (double)bins_ : 1.0;
+    b.y_origin = range.y_min;
+    b.y_width = y_range > 0.0 ? y_range / (double)bins_ : 1.0;
+    b.bins = (uint32_t)bins_;
+    return b;
+  }
+  json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
+    return state_from_follow_up(tgx_joint_range(), nullptr);
+  }
+  json::Value state_from_follow_up(const tgx_joint_range &, const JointCounts *counts) const override {
+    std::vector<Cell> cells;
+    uint64_t n = 0;
+    if (counts) {
+      if (counts->out_of_range)
+        throw AnalyzerError::query("the table changed between the two passes: " + std::to_string(counts->out_of_range) +
+                                   " rows fell outside the bins");
+      const uint32_t side = counts->bins + 1;
+      for (uint32_t i = 0; i < side; i++)
+        for (uint32_t j = 0; j < side; j++)
+          if (const uint64_t c = counts->cells[(size_t)i * side + j]) {
+            cells.push_back({label(i), label(j), c});
+            n += c;
+          }
+    }
+    return state(n, cells, bins_);
+  }
+  json::Value merge_states(const std::vector<json::Value> &states) const override {  // :31-75
+    if (states.empty()) throw AnalyzerError::state_merge("Cannot merge empty states");
+    const uint64_t bins = u(states[0], "bins");
+    uint64_t n = 0;
+    std::vector<Cell> cells;
+    for (const json::Value &s : states) {
+      if (u(s, "bins") != bins) throw AnalyzerError::state_merge("Cannot merge states with different bin counts");
+      n += u(s, "n");
+      for (const Cell &c : cells_of(s)) {
+        bool found = false;
+        for (Cell &m : cells)
+          if (m.x == c.x && m.y == c.y) {
+            m.count += c.count;
+            found = true;
+          }
+        if (!found) cells.push_back(c);
+      }
+    }
+    // (the marginals of the reference's states are the sums of their cells, and stay so under addition)
+    return state(n, cells, bins);
+  }
+  MetricValue metric_from_state(const json::Value &s) const override {  // :378-407
+    const uint64_t nn = u(s, "n");
+    if (nn == 0) return MetricValue::of_double(0.0);
+    const double n = (double)nn;
+    const json::Value *xc = s.get("x_counts"), *yc = s.get("y_counts");
+    double mi = 0.0;
+    for (const Cell &c : cells_of(s)) {  // in the state's order: row-major
+      const double p_xy = (double)c.count / n;
+      const uint64_t x_count = xc ? xc->get_u64(c.x, 0) : 0, y_count = yc ? yc->get_u64(c.y, 0) : 0;
+      if (x_count > 0 && y_count > 0) {
+        const double p_x = (double)x_count / n, p_y = (double)y_count / n;
+        if (p_xy > 0.0) mi += p_xy * log(p_xy / (p_x * p_y));
+      }
+    }
+    return MetricValue::of_double(mi / 0.6931471805599453);  // std::f64::consts::LN_2
+  }
+
+ private:
+  struct Cell {
+    std::string x, y;
+    uint64_t count;
+  };
+  static std::string label(uint32_t i) { return std::to_string(i) + ".0"; }
+  static std::vector<Cell> cells_of(const json::Value &s) {
+    std::vector<Cell> out;
+    const json::Value *j = s.get("joint_counts");
+    if (!j || j->type != json::Value::Array) return out;
+    for (const json::Value &e : j->arr) {
+      if (e.type != json::Value::Array || e.arr.size() != 3 || e.arr[0].type != json::Value::String ||
+          e.arr[1].type != json::Value::String)
+        throw AnalyzerError::invalid_data("joint_counts entries are [x_label, y_label, count]");
+      out.push_back({e.arr[0].str, e.arr[1].str, e.arr[2].as_u64()});
+    }
+    return out;
+  }
+  static json::Value state(uint64_t n, const std::vector<Cell> &cells, uint64_t bins) {
+    json::Value joint;
+    joint.type = json::Value::Array;
+    std::vector<std::pair<std::string, uint64_t>> xs, ys;
+    auto add = [](std::vector<std::pair<std::string, uint64_t>> &m, const std::string &k, uint64_t c) {
+      for (auto &kv : m)
+        if (kv.first == k) {
+          kv.second += c;
+          return;
+        }
+      m.push_back({k, c});
+    };
+    for (const Cell &c : cells) {
+      json::Value e;
+      e.type = json::Value::Array;
+      e.arr = {jstr(c.x), jstr(c.y), jcount(c.count)};
+      joint.arr.push_back(e);
+      add(xs, c.x, c.count);
+      add(ys, c.y, c.count);
+    }
+    std::vector<std::pair<std::string, json::Value>> xo, yo;
+    for (auto &kv : xs) xo.push_back({kv.first, jcount(kv.second)});
+    for (auto &kv : ys) yo.push_back({kv.first, jcount(kv.second)});
+    return jobj({{"n", jcount(n)}, {"joint_counts", joint}, {"x_counts", jobj(xo)}, {"y_counts", jobj(yo)},
+                 {"bins", jcount(bins)}});
+  }
+  std::string a_, b_;
+  uint64_t bins_;
+};
+
 struct Handles {
   tgx_plan *plan = nullptr;
   tgx_state *state = nullptr;
@@ -447,6 +595,11 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
     if (v.get_str("column1").empty() || v.get_str("column2").empty())
       throw TermError{TermError::Internal, "correlation needs column1 and column2"};
     return std::make_shared<CorrelationAnalyzer>(v.get_str("column1"), v.get_str("column2"), ct);
+  }
+  if (t == "mutual_information") {
+    if (v.get_str("column1").empty() || v.get_str("column2").empty())
+      throw TermError{TermError::Internal, "mutual_information needs column1 and column2"};
+    return std::make_shared<MutualInformationAnalyzer>(v.get_str("column1"), v.get_str("column2"), v.get_u64("bins", 10));
   }
   throw TermError{TermError::Internal, "unknown analyzer type '" + t + "'"};
 }
@@ -526,11 +679,15 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
   Handles h;
   std::vector<tgx_result> results;
   std::optional<std::string> run_error;
-  auto pass = [&](Handles &hh, size_t max_rows, tgx_status *status) -> std::optional<std::string> {
+  // `binnings`: the follow-up pass -- spec i is a JOINT_BINS check in its count phase
+  auto pass = [&](Handles &hh, size_t max_rows, tgx_status *status,
+                  const std::vector<tgx_joint_binning> *binnings = nullptr) -> std::optional<std::string> {
     tgx_error err;
     memset(&err, 0, sizeof(err));
     tgx_status s = tgx_init(nullptr, &err);
     if (s == TGX_OK) s = tgx_plan_create(specs.data(), specs.size(), &hh.plan, &err);
+    for (size_t i = 0; s == TGX_OK && binnings && i < binnings->size(); i++)
+      s = tgx_plan_set_joint_binning(hh.plan, i, &(*binnings)[i], &err);
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
     for (size_t b = 0; s == TGX_OK && b < table->batches.size(); b++) {
@@ -588,6 +745,64 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       }
     }
   }
+  // The second pass (analyzers.h, Analyzer::follow_up): the analyzers whose first-pass results are in say what their
+  // follow-up request is; all of those run as ONE more pass over the table.  A run without such an analyzer makes one pass.
+  struct Followed {
+    tgx_joint_range range;
+    bool counted = false;
+    JointCounts counts;
+  };
+  std::vector<Followed> followed(analyzers_.size());
+  if (!run_error && h.state) {
+    std::vector<size_t> owners;
+    std::vector<tgx_joint_binning> binnings;
+    std::vector<tgx_check_spec> first_specs = specs;
+    for (size_t a = 0; a < analyzers_.size(); a++) {
+      if (!analyzers_[a]->two_pass() || planned[a].error || planned[a].spec_index.empty()) continue;
+      tgx_error err;
+      memset(&err, 0, sizeof(err));
+      const tgx_status s = tgx_joint_range_get(h.plan, h.state, planned[a].spec_index[0], &followed[a].range, &err);
+      if (s != TGX_OK) {
+        planned[a].error = AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg).text;
+        continue;
+      }
+      try {
+        if (const std::optional<tgx_joint_binning> b = analyzers_[a]->follow_up(followed[a].range)) {
+          owners.push_back(a);
+          binnings.push_back(*b);
+        }
+      } catch (const AnalyzerError &e) {
+        planned[a].error = e.text;
+      }
+    }
+    if (!owners.empty()) {
+      specs.clear();
+      for (size_t a : owners) specs.push_back(first_specs[planned[a].spec_index[0]]);
+      Handles second;
+      tgx_status status = TGX_OK;
+      const std::vector<tgx_result> first_results = results;
+      std::optional<std::string> second_error = pass(second, SIZE_MAX, &status, &binnings);
+      results = first_results;
+      for (size_t k = 0; k < owners.size(); k++) {
+        Followed &fo = followed[owners[k]];
+        tgx_error err;
+        memset(&err, 0, sizeof(err));
+        if (!second_error) {
+          uint64_t n_cells = 0;
+          fo.counts.bins = binnings[k].bins;
+          fo.counts.cells.assign((size_t)(binnings[k].bins + 1) * (binnings[k].bins + 1), 0);
+          const tgx_status s = tgx_joint_counts(second.plan, second.state, k, fo.counts.cells.data(),
+                                                fo.counts.cells.size(), &n_cells, &fo.counts.out_of_range, &err);
+          if (s != TGX_OK) second_error = AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg).text;
+        }
+        if (second_error)
+          planned[owners[k]].error = second_error;
+        else
+          fo.counted = true;
+      }
+      specs = first_specs;
+    }
+  }
   for (size_t a = 0; a < analyzers_.size(); a++) {
     const Analyzer &an = *analyzers_[a];
     std::optional<std::string> error = planned[a].error ? planned[a].error : run_error;
@@ -595,7 +810,9 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       try {
         std::vector<const tgx_result *> r;
         for (size_t si : planned[a].spec_index) r.push_back(&results[si]);
-        json::Value st = an.state_from_results(r, planned[a].column_types);
+        json::Value st = an.two_pass()
+                             ? an.state_from_follow_up(followed[a].range, followed[a].counted ? &followed[a].counts : nullptr)
+                             : an.state_from_results(r, planned[a].column_types);
         MetricValue m = an.metric_from_state(st);
         out.states.push_back({an.metric_key(), st});
         // context.rs:71-73: a later analyzer with the same key replaces the earlier metric

@@ -48,6 +48,13 @@ struct AnalyzerError {
   static AnalyzerError custom(const std::string &m) { return {m}; }
 };
 
+// what a two-pass analyzer is handed once both passes are through (AnalysisRunner::run)
+struct JointCounts {
+  uint32_t bins = 0;
+  std::vector<uint64_t> cells;  // (bins + 1)^2, row-major (tgx_joint_counts)
+  uint64_t out_of_range = 0;
+};
+
 class Analyzer {
  public:
   virtual ~Analyzer() {}
@@ -60,6 +67,15 @@ class Analyzer {
   // column_types: tgx_type of columns() in order (the reference's downcasts depend on the SQL result type).
   virtual json::Value state_from_results(const std::vector<const tgx_result *> &r,
                                          const std::vector<int> &column_types) const = 0;
+  // A SECOND PASS over the table, for aggregates whose parameters depend on the first pass's results (bin edges from
+  // the table's MIN / MAX: the reference's MutualInformationAnalyzer runs two queries, mutual_information.rs:143-248).
+  // An analyzer that overrides follow_up() has ONE TGX_CHECK_JOINT_BINS request as plan()[0]; once the first pass is
+  // in, the runner hands it that request's range and gets the binning of the follow-up request back (nullopt: no rows,
+  // no second pass; throws AnalyzerError when the range has no binning), runs all follow-up requests as one more fused
+  // pass and builds the state with state_from_follow_up (`counts` == nullptr when there was no second pass).
+  virtual bool two_pass() const { return false; }
+  virtual std::optional<tgx_joint_binning> follow_up(const tgx_joint_range &) const { return std::nullopt; }
+  virtual json::Value state_from_follow_up(const tgx_joint_range &, const JointCounts *) const { return json::Value(); }
   virtual json::Value merge_states(const std::vector<json::Value> &states) const = 0;      // AnalyzerState::merge
   virtual MetricValue metric_from_state(const json::Value &state) const = 0;              // throws AnalyzerError
 };

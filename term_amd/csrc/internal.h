@@ -195,6 +195,12 @@ struct KllTask {
   int column;
   uint32_t k;
 };
+// TGX_CHECK_JOINT_BINS (jointbins_device.cpp): one task per spec; `binned` once tgx_plan_set_joint_binning was called
+struct JointTask {
+  int col_x, col_y;
+  bool binned;
+  JointBinning binning;
+};
 
 enum class Source { kScan, kCount };
 
@@ -216,10 +222,12 @@ struct tgx_plan {
   std::vector<tgx::ComomentTask> como;
   std::vector<tgx::KllTask> kll;
   std::vector<tgx::HllTask> hll;
+  std::vector<tgx::JointTask> joint;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
   std::vector<char> key_column;  // a single-column DISTINCT check reads it (range tracking of coalesced HOST batches)
+  std::vector<char> joint_on;    // a JOINT_BINS check reads it (numeric columns only: strings are TGX_UNSUPPORTED)
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
   // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
@@ -609,6 +617,7 @@ struct tgx_state {
   void *kll = nullptr;    // tgx::KllDeviceState (kll_device.cpp)
   void *regex = nullptr;  // tgx::RegexState (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
+  void *joint = nullptr;  // tgx::JointState (jointbins_device.cpp)
 
   tgx::Coalescer coalesce;
   std::vector<tgx::DevBuf> parked;  // buffers replaced while the stream may still read them; freed once it has drained

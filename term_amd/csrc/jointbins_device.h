@@ -1,0 +1,18 @@
+// jointbins_device.h -- TGX_CHECK_JOINT_BINS tasks of a state (range / count phase on the device, additive host part);
+// see jointbins_device.cpp.
+#pragma once
+#include "internal.h"
+
+namespace tgx {
+tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+void joint_state_init(tgx_state *st);
+void joint_state_free(tgx_state *st);
+tgx_status joint_state_reset(tgx_state *st, tgx_error *err);
+// one batch (device views of the plan's columns) through the tasks' kernels
+tgx_status joint_update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err);
+tgx_status joint_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err);
+tgx_status joint_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err);
+// the blob's section: present only when the plan has such tasks (blobs of other plans keep their bytes)
+tgx_status joint_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err);
+tgx_status joint_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err);
+}  // namespace tgx

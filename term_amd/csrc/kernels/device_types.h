@@ -150,6 +150,30 @@ struct ComomentAcc {
   int32_t pad;
 };
 
+// Joint bin counts of two numeric columns (kernels/jointbins.hip; TGX_CHECK_JOINT_BINS).  The pairs of a launch travel as
+// ComomentColDesc (same loads as the co-moment kernel); `acc_index` is the task's slot.
+// Range phase: n, rows with a NaN / infinity, and the extremes over the rows with both sides non-NULL and finite.
+struct JointRangeAcc {
+  int64_t n, non_finite;
+  double x_min, x_max, y_min, y_max;  // identities: +inf / -inf
+};
+// Count phase: the task's binning; its global counters are [cells][kJointOutOfRange][kJointNonFinite] 64-bit words.
+struct JointBinning {
+  double x_origin, x_width, y_origin, y_width;
+  uint32_t bins;
+  uint32_t pad;
+};
+constexpr uint32_t kJointMaxBins = 127;  // (bins + 1)^2 32-bit LDS counters: 64 KiB
+constexpr int kJointBlock = 512;         // threads of a workgroup of the two kernels
+constexpr int kMaxJointPerLaunch = 8;
+struct JointLaunch {
+  ComomentColDesc pairs[kMaxJointPerLaunch];
+  JointBinning binning[kMaxJointPerLaunch];
+  unsigned long long *counters[kMaxJointPerLaunch];  // count phase: the task's global counters
+  int32_t acc_index[kMaxJointPerLaunch];             // range phase: the task's JointRangeAcc
+};
+__host__ __device__ inline uint32_t joint_cells(uint32_t bins) { return (bins + 1) * (bins + 1); }
+
 // One (column, batch) window of the library-side batch coalescing (kernels/gather.hip): where the window lives and
 // where it lands in the coalesced column.  A table of these is uploaded per flush; one workgroup per entry.
 struct GatherSeg {

@@ -303,6 +303,13 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
+      case TGX_CHECK_JOINT_BINS: {
+        int slot = -1;
+        TGX_TRY(joint_plan_add(plan.get(), (int)i, &slot, err));
+        max_col = std::max(max_col, sp.column2);
+        plan->bind[i].slot = slot;
+        break;
+      }
       case TGX_CHECK_SPEARMAN: {
         max_col = std::max(max_col, sp.column2);
         int slot = -1;
@@ -359,6 +366,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     P->needs_wide.assign(P->n_columns_needed, 0);
     P->key_column.assign(P->n_columns_needed, 0);
     P->stats_on.assign(P->n_columns_needed, 0);
+    P->joint_on.assign(P->n_columns_needed, 0);
     for (auto &t : P->distinct)
       if (t.tuple.empty() && !t.approx_only) P->key_column[t.column] = 1;
     // (by what was ASKED: a key column has a scan task of its own for the range decisions of its key set)
@@ -380,6 +388,9 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       P->used[t.col_x] = P->used[t.col_y] = P->reads_values[t.col_x] = P->reads_values[t.col_y] =
           P->needs_wide[t.col_x] = P->needs_wide[t.col_y] = 1;
     for (auto &t : P->kll) P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = 1;
+    for (auto &t : P->joint)
+      for (int c : {t.col_x, t.col_y})
+        P->used[c] = P->reads_values[c] = P->needs_wide[c] = P->stats_on[c] = P->joint_on[c] = 1;
     regex_mark_used(P, P->used);
     std::vector<char> sp_used(P->n_columns_needed, 0), sp_vals(P->n_columns_needed, 0);
     spearman_mark_used(P, sp_used, sp_vals);
@@ -514,6 +525,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   regex_state_init(st);
   kll_state_init(st);
   spearman_state_init(st);
+  joint_state_init(st);
 }
 
 // one launch for all the small accumulators of a state (fresh, or reset): the scan accumulators to their identities,
@@ -612,6 +624,7 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   regex_state_free(st);
   kll_state_free(st);
   spearman_state_free(st);
+  joint_state_free(st);
   coalesce_drop(st);  // (copy threads that are still filling an arena let go of it first)
   for (int k = 0; k < 2; k++) {
     if (st->arena_event[k]) (void)hipEventDestroy(st->arena_event[k]);
@@ -698,6 +711,7 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   kll_state_reset(st);
   regex_state_reset(st);
   spearman_state_reset(st);
+  TGX_TRY(joint_state_reset(st, err));
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
   st->hll_mode.assign(plan->hll.size(), 0);
   if (st->device_ready && st->d_hll.p)
@@ -1081,6 +1095,9 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
         break;
       case TGX_CHECK_SPEARMAN:
         TGX_TRY(spearman_fill_result(st, b.slot, r, err));
+        break;
+      case TGX_CHECK_JOINT_BINS:
+        TGX_TRY(joint_fill_result(st, b.slot, r, err));
         break;
       default:
         break;

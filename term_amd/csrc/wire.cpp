@@ -97,6 +97,8 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
     w.pod((uint32_t)(g.hll[k].empty() ? 0 : 1));
     if (!g.hll[k].empty()) w.put(g.hll[k].data(), kHllRegisters);
   }
+  // (behind everything else, and only for plans with such checks: blobs of every other plan keep their bytes)
+  TGX_TRY(joint_serialize(st, &w.len, w.buf, w.cap, err));
   *len = w.len;
   if (buf && w.len > cap) return fail(err, TGX_INVALID_ARGUMENT, "buffer too small: need %zu bytes", w.len);
   return TGX_OK;
@@ -200,6 +202,10 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
         st->h_hll[k].resize(kHllRegisters);
         r.get(st->h_hll[k].data(), kHllRegisters);
       }
+    }
+    if (r.ok) {
+      s = joint_deserialize(st.get(), r.buf, r.len, &r.pos, err);
+      if (s != TGX_OK) return s;
     }
   }
   if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");

@@ -675,6 +675,8 @@ class _Analyzer:
             return t
         if t == "correlation":
             return "correlation_%s_%s_%s" % (self.spec.get("method", "pearson"), self.spec["column1"], self.spec["column2"])
+        if t == "mutual_information":
+            return "mutual_information_%s_%s" % (self.spec["column1"], self.spec["column2"])
         return "%s.%s" % (t, self.spec["column"])
 
     def merge_states(self, states):
@@ -715,6 +717,12 @@ def StandardDeviationAnalyzer(column): return _Analyzer({"type": "standard_devia
 
 def CorrelationAnalyzer(column1, column2, method="pearson"):
     return _Analyzer({"type": "correlation", "column1": column1, "column2": column2, "method": method})
+
+
+def MutualInformationAnalyzer(column1, column2, bins=10):
+    """TG/analyzers/advanced/mutual_information.rs, numeric x numeric pairs: two passes on the device (the range of
+    both columns, then the joint bin counts); `bins` = max(bins, 2), at most JOINT_MAX_BINS (include/tgx.h)"""
+    return _Analyzer({"type": "mutual_information", "column1": column1, "column2": column2, "bins": max(int(bins), 2)})
 
 
 class AnalyzerContext:

@@ -19,6 +19,13 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
     n_regex     x { u64 total, u64 matches }
     n_hll       x { u32 mode (0 nothing seen, 1 registers, 2 the exact key set answers), u32 has_registers;
                     has_registers x 16384 u8 HyperLogLog registers (rank 0 .. 33) }
+    and ONLY for plans with JOINT_BINS checks (blobs of every other plan keep the bytes they had):
+    u32 magic 'JNTB', u32 n_joint
+    n_joint     x { u32 binned, u32 bins; f64 x_origin, x_width, y_origin, y_width      (the plan's binning; zeros in the
+                    i64 total, n, non_finite; f64 x_min, x_max, y_min, y_max              range phase; extremes: +inf / -inf
+                    u64 n_words; u64 words[n_words] }                                     when n = 0 and in the count phase)
+                               n_words = (bins + 1)^2 + 1 in the count phase: the cells, row-major, then the rows whose
+                               index fell outside [0, bins]; 0 in the range phase.  n = the sum of the cells there.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -26,6 +33,7 @@ min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys o
 import struct
 
 MAGIC, VERSION = 0x53584754, 3
+JOINT_MAGIC = 0x42544E4A  # 'JNTB'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -88,9 +96,29 @@ def hll_state(registers=None, mode=1):
     return struct.pack("<II", mode, 1) + bytes(registers)
 
 
-def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=()):
+def joint_range_state(total, n, non_finite=0, x_min=None, x_max=None, y_min=None, y_max=None):
+    """a JOINT_BINS task in its range phase (extremes None: no rows)"""
+    inf = float("inf")
+    ext = [inf if x_min is None else x_min, -inf if x_max is None else x_max, inf if y_min is None else y_min,
+           -inf if y_max is None else y_max]
+    return struct.pack("<II4d3q4dQ", 0, 0, 0.0, 0.0, 0.0, 0.0, total, n, non_finite, *ext, 0)
+
+
+def joint_count_state(binning, total, cells, outside=0, non_finite=0):
+    """a JOINT_BINS task in its count phase: binning = (x_origin, x_width, y_origin, y_width, bins), `cells` the
+    (bins + 1)^2 counts, row-major"""
+    x0, xw, y0, yw, bins = binning
+    assert len(cells) == (bins + 1) ** 2
+    inf = float("inf")
+    words = list(cells) + [outside]
+    return (struct.pack("<II4d3q4dQ", 1, bins, x0, xw, y0, yw, total, sum(cells), non_finite, inf, -inf, inf, -inf,
+                        len(words)) + struct.pack("<%dQ" % len(words), *words))
+
+
+def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
+    tail = struct.pack("<II", JOINT_MAGIC, len(joint)) + b"".join(joint) if joint else b""
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
-            b"".join(regex) + b"".join(hll))
+            b"".join(regex) + b"".join(hll) + tail)
