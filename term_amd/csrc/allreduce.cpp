@@ -9,34 +9,11 @@
 // RCCL is bound at run time (dlopen of librccl.so.1 -- the copy already in the process when the host is PyTorch), so
 // libtgx.so itself links against HIP only.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include <algorithm>
 #include <chrono>
-#include <mutex>
-#include <thread>
-#include <vector>
 
-#include "internal.h"
-#include "spearman_device.h"
-
-using namespace tgx;
-
-#define HIP_TRY(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess)                                                                                 \
-      return fail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR, "%s failed: %s", \
-                  #expr, hipGetErrorString(e_));                                                          \
-  } while (0)
-#define TGX_TRY(expr)            \
-  do {                           \
-    tgx_status s_ = (expr);      \
-    if (s_ != TGX_OK) return s_; \
-  } while (0)
+#include "api_internal.h"
 
 // ------------------------------------------------------------------------------------------------ RCCL binding
 namespace {
@@ -384,9 +361,76 @@ struct Header {
 constexpr uint64_t kFactsMagic = 0x5447584641435453ull;  // "TGXFACTS"
 
 uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
-}  // namespace
 
-namespace {
+// rank r's block of an all-gathered buffer begins with its Header
+const Header &header_of(const uint8_t *blocks, size_t stride, int32_t r) {
+  return *(const Header *)(blocks + (size_t)r * stride);
+}
+
+// the all-gathered facts: per rank a Header and one TaskFacts per DISTINCT task
+struct GatheredFacts {
+  std::vector<uint8_t> all;
+  size_t stride = 0;
+  const Header &header(int32_t r) const { return header_of(all.data(), stride, r); }
+  const TaskFacts &task(int32_t r, size_t k) const {
+    return ((const TaskFacts *)(all.data() + (size_t)r * stride + sizeof(Header)))[k];
+  }
+};
+
+// a DISTINCT task whose key sets travel as slices of one global range bitmap: rank r owns words
+// [r * slice_words, (r + 1) * slice_words) over the values from `glo` on; the task's slices start at word `col_words`
+// of every peer's row of the send buffer (`seen`, then `twice` for a multiplicity set)
+struct BitmapPart {
+  size_t task;
+  int64_t glo;
+  uint64_t slice_words, col_words;
+  bool mult;
+};
+struct ExchangePlan {
+  std::vector<BitmapPart> parts;
+  std::vector<size_t> by_records;  // tasks whose keys travel as records to their hash owners
+  uint64_t row_words = 0;          // words every peer receives in the one all-to-all of the bitmap slices
+  bool empty() const { return parts.empty() && by_records.empty(); }
+};
+
+// How each task's key sets travel.  EVERY RANK MUST COMPUTE THE SAME ANSWER -- the collectives that follow are sized
+// by it -- so this is a pure function of what all ranks hold alike: the all-gathered facts, the world size and the
+// plan's tasks.  Nothing rank-local (the state, the rank's number, its buffers, the environment) may reach it.
+ExchangePlan plan_exchange(const GatheredFacts &facts, int32_t W, const std::vector<DistinctTask> &tasks) {
+  ExchangePlan xp;
+  for (size_t k = 0; k < tasks.size(); k++) {
+    int64_t glo = INT64_MAX, ghi = INT64_MIN;
+    bool any_set = false, all_bitmap = true, wide = false;
+    uint64_t rows = 0;
+    for (int32_t r = 0; r < W; r++) {
+      const TaskFacts &f = facts.task(r, k);
+      glo = std::min(glo, f.lo);
+      ghi = std::max(ghi, f.hi);
+      any_set |= f.kind != kKindNone;
+      all_bitmap &= f.kind != kKindHash;
+      wide |= f.wide != 0;
+      rows += (uint64_t)f.rows;
+    }
+    if (!any_set) continue;  // nobody holds keys on a device (already partitioned, host-only or empty states)
+    // range bitmaps everywhere, and a global range that is still dense (at most 16 bits per row of the whole table,
+    // below 2^34 values)
+    bool use_bitmap = all_bitmap && !wide && glo <= ghi;
+    if (use_bitmap) {
+      const uint64_t width = (uint64_t)ghi - (uint64_t)glo;
+      use_bitmap = width < (1ull << 34) && width / 16 <= std::max<uint64_t>(rows, 4096);
+    }
+    if (use_bitmap) {
+      const uint64_t words = (((uint64_t)ghi - (uint64_t)glo) >> 5) + 1;
+      const BitmapPart p{k, glo, round_up((words + W - 1) / W, 4), xp.row_words, tasks[k].multiplicity};
+      xp.row_words += p.slice_words * (p.mult ? 2 : 1);
+      xp.parts.push_back(p);
+    } else {
+      xp.by_records.push_back(k);
+    }
+  }
+  return xp;
+}
+
 // host-clock phases of the step, for a profiling state (tgx_profile_get: "xr_facts" -- local preparation + the facts
 // round, i.e. mostly the wait for the shard's key passes --, "xr_exchange", "xr_pack" -- reading the state back, which
 // waits for the scan --, "xr_gather", "xr_merge"): `total_ms` is wall time on this rank, `launches` the calls
@@ -404,154 +448,213 @@ struct HostPhase {
   }
   ~HostPhase() { end(); }
 };
-}  // namespace
 
-extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_comm *comm, tgx_error *err) try {
-  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (!comm) return fail(err, TGX_INVALID_ARGUMENT, "comm is NULL");
-  bind_thread();  // (a tokio worker / any thread: HIP's current device is per thread)
-  TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
-  const int32_t W = comm->ops.world, R = comm->ops.rank;
-  const size_t nd = plan->distinct.size();
-  if (comm->ops.device_buffers) {
-    TGX_TRY(need_device(err));
-    TGX_TRY(state_init_device(st, err));
+// the state works on a borrowed stream while `on` (Step::borrow_stream); however the step ends, it gets its own back
+struct StreamLoan {
+  tgx_state *st;
+  hipStream_t own;
+  bool on = false;
+  ~StreamLoan() {
+    if (on) st->stream = own;
   }
-  hipStream_t s = st->device_ready ? st->stream : nullptr;
-  // Facts and key sets travel on a SECOND stream that waits only for the key columns' uniqueness passes
-  // (tgx_update records `keys_ready` right after them and queues the scan of the other columns behind): the exchange
-  // -- range / 8 bytes per rank and dense key column over xGMI, three collective latencies -- then runs while the
-  // state's own stream is still scanning.  Every helper below works on `st->stream`, so the state borrows the second
-  // stream for the two phases (StreamLoan) and the two are joined by an event before the states are packed.
-  const bool has_spearman_tasks = plan->spearman && spearman_num_tasks(plan) > 0;
-  const bool overlap = comm->ops.device_buffers && st->device_ready && st->keys_ready_recorded && nd > 0 &&
-                       !has_spearman_tasks;
-  st->exchange_expected = comm->ops.device_buffers != 0 && nd > 0;
-  struct StreamLoan {
-    tgx_state *st;
-    hipStream_t own;
-    bool on = false;
-    ~StreamLoan() {
-      if (on) st->stream = own;
-    }
-  } loan{st, st->stream};
-  if (overlap) {
-    if (!st->aux_stream) {
-      HIP_TRY(stream_acquire(&st->aux_stream, true));  // (the most urgent priority; from the library's pool)
-      HIP_TRY(hipEventCreateWithFlags(&st->aux_done, hipEventDisableTiming));
-    }
-    HIP_TRY(hipStreamWaitEvent(st->aux_stream, st->keys_ready, 0));
-    st->stream = st->aux_stream;
-    loan.on = true;
-    s = st->aux_stream;
-  }
+};
 
-  // ---- 0. SPEARMAN: ranks over the union of the ranks' pairs (a distributed sort, spearman_device.cpp) -----------
-  // Rank-based states do not merge (the reference's neither: analyzers/advanced/correlation.rs:103-109), so their
-  // results are computed here and carried past the reset + merge below by hand.
-  std::vector<SpearmanResolved> spearman_results;
-  const bool has_spearman = has_spearman_tasks;
-  if (has_spearman) {
-    SpearmanExchange X;
-    X.rank = R;
-    X.world = W;
-    X.allgather_host = [&](const void *h_send, void *h_recv, size_t bytes) {
-      return do_allgather_host(comm, st->device_ready ? st->stream : nullptr, h_send, h_recv, bytes, err);
-    };
-    X.alltoallv = [&](const void *d_send, const uint64_t *sc, void *d_recv, const uint64_t *rc, size_t elem) {
-      return do_alltoallv(comm, st->device_ready ? st->stream : nullptr, d_send, sc, d_recv, rc, elem, err);
-    };
-    TGX_TRY(spearman_allreduce(st, X, &spearman_results, err));
-    s = st->device_ready ? st->stream : nullptr;
-    spearman_set_reducing(st, true);  // (the state's own blob does not carry these tasks)
+struct ReducingGuard {
+  tgx_state *st;
+  bool on;
+  ~ReducingGuard() {
+    if (on) spearman_set_reducing(st, false);
   }
-  struct ReducingGuard {
-    tgx_state *st;
-    bool on;
-    ~ReducingGuard() {
-      if (on) spearman_set_reducing(st, false);
-    }
-  } reducing_guard{st, has_spearman};
+};
 
-  HostPhase ph_facts(st, "xr_facts");
-  // ---- 1. facts --------------------------------------------------------------------------------------------
+// What the phases of one step share; tgx_allreduce, at the end of this file, is the list of the phases.
+struct Step {
+  const tgx_plan *plan;
+  tgx_state *st;
+  tgx_comm *comm;
+  tgx_error *err;  // the caller's
+  const int32_t W, R;
+  // the stream in use: the state's own, or the borrowed one from borrow_stream to join_streams (null: the state has no
+  // device part yet).  The helpers of the other files work on st->stream, which is the same stream throughout.
+  hipStream_t s;
   // A rank that fails ON ITS OWN between two collectives must not return: its peers would wait in the next one for
   // ever.  It notes the failure in `local`, keeps taking part with what it has, and the next status word the ranks
-  // exchange anyway (facts header, the "ready" rounds below, the blob header) makes ALL ranks return an error from the
-  // same point.  TGX_FAULT_INJECT="rank:site" makes that rank fail at site 1..7 (tests/test_gpu_distributed_sim.py).
-  int fault_rank = -1, fault_site = 0;
-  if (const char *fi = getenv("TGX_FAULT_INJECT")) (void)sscanf(fi, "%d:%d", &fault_rank, &fault_site);
+  // exchange anyway (facts header, the "ready" rounds of the exchange, the blob header) makes ALL ranks return an error
+  // from the same point.  So: what needs no peer goes through attempt(); what a collective or a peer's status word
+  // says is returned.  TGX_FAULT_INJECT="rank:site" makes that rank fail at site 1..7 -- an error status from host
+  // code, nothing else (tests/test_gpu_distributed_sim.py).
   tgx_status local = TGX_OK;
   tgx_error local_err;
-  memset(&local_err, 0, sizeof(local_err));
-  auto note = [&](tgx_status sdone, const tgx_error &e) {
-    if (local == TGX_OK && sdone != TGX_OK) {
-      local = sdone;
-      local_err = e;
-    }
-  };
-  auto injected = [&](int site, tgx_error *e) -> tgx_status {
+  int fault_rank = -1, fault_site = 0;
+  GatheredFacts facts;
+
+  Step(const tgx_plan *p, tgx_state *state, tgx_comm *c, tgx_error *e)
+      : plan(p), st(state), comm(c), err(e), W(c->ops.world), R(c->ops.rank),
+        s(state->device_ready ? state->stream : nullptr) {
+    memset(&local_err, 0, sizeof(local_err));
+    if (const char *fi = getenv("TGX_FAULT_INJECT")) (void)sscanf(fi, "%d:%d", &fault_rank, &fault_site);
+  }
+
+  tgx_status injected(int site, tgx_error *e) const {
     if (fault_rank == R && fault_site == site) return fail(e, TGX_OUT_OF_MEMORY, "injected failure at site %d", site);
     return TGX_OK;
-  };
-  std::vector<ScanAcc> scan(plan->scan.size());
-  auto local_prep = [&](tgx_error *err) -> tgx_status {
-    TGX_TRY(injected(1, err));
-    // (the small staging buffers of the record exchange: allocated here, where a failure still travels in the facts)
-    if (st->device_ready || comm->ops.device_buffers) {
-      HIP_TRY(comm->d_small_send.reserve((size_t)W * 16 + 16));
-      HIP_TRY(comm->d_small_recv.reserve((size_t)W * 16 + 16));
-    }
-    if (st->device_ready && !scan.empty()) {
-      // (queued in front of the resolve's own read-back, into pinned memory: the two come back with one wait)
-      TGX_TRY(pinned_reserve(&comm->h_a, &comm->h_a_cap, scan.size() * sizeof(ScanAcc), err));
-      HIP_TRY(hipMemcpyAsync(comm->h_a, st->d_scan_acc.p, scan.size() * sizeof(ScanAcc), hipMemcpyDeviceToHost, s));
-    }
-    TGX_TRY(distinct_resolve_all(st, err));  // keys outside a sampled bitmap range are brought in first
-    if (st->device_ready) {
-      HIP_TRY(hipStreamSynchronize(s));
-      if (!scan.empty()) memcpy(scan.data(), comm->h_a, scan.size() * sizeof(ScanAcc));
-    }
-    return TGX_OK;
-  };
-  {
+  }
+  // runs something this rank does on its own, with an error record of its own, and notes the first failure
+  template <class F>
+  void attempt(F &&f) {
     tgx_error e;
     memset(&e, 0, sizeof(e));
-    note(local_prep(&e), e);
-  }
-  if (local != TGX_OK || !st->device_ready) {
-    for (auto &a : scan) {
-      memset(&a, 0, sizeof(a));
-      a.min_k = INT64_MAX;
-      a.max_k = INT64_MIN;
+    const tgx_status done = f(&e);
+    if (local == TGX_OK && done != TGX_OK) {
+      local = done;
+      local_err = e;
     }
   }
   // every rank learns of a peer's local failure from a status word it was about to receive anyway
-  auto report = [&](int32_t r, uint64_t status, const char *where) -> tgx_status {
+  tgx_status report(int32_t r, uint64_t status, const char *where) const {
     if (r == R && local != TGX_OK) {
       if (err) *err = local_err;
       return local;
     }
     return fail(err, (tgx_status)status, "tgx_allreduce: rank %d failed %s (%s); no rank went on", r, where,
                 tgx_status_name((int32_t)status));
-  };
-  auto peers_ok = [&](const uint8_t *blocks, size_t stride, const char *where) -> tgx_status {
-    for (int32_t r = 0; r < W; r++) {
-      const Header *hr = (const Header *)(blocks + (size_t)r * stride);
-      if (hr->status != 0) return report(r, hr->status, where);
-    }
+  }
+  tgx_status peers_ok(const uint8_t *blocks, size_t stride, const char *where) const {
+    for (int32_t r = 0; r < W; r++)
+      if (header_of(blocks, stride, r).status != 0) return report(r, header_of(blocks, stride, r).status, where);
     return TGX_OK;
-  };
+  }
   // one word per rank, all-gathered: "did what you just did on your own succeed?"
-  auto status_round = [&](const char *where) -> tgx_status {
+  tgx_status status_round(const char *where) {
     std::vector<uint64_t> mine_w(1, (uint64_t)local), all_w((size_t)W, 0);
     TGX_TRY(do_allgather_host(comm, s, mine_w.data(), all_w.data(), sizeof(uint64_t), err));
     for (int32_t r = 0; r < W; r++)
       if (all_w[r] != 0) return report(r, all_w[r], where);
     return TGX_OK;
+  }
+
+  tgx_status borrow_stream(StreamLoan *loan, bool has_spearman);
+  tgx_status spearman(std::vector<SpearmanResolved> *results);
+  void prepare(std::vector<ScanAcc> *scan);
+  TaskFacts local_facts(size_t k, const std::vector<ScanAcc> &scan) const;
+  tgx_status facts_round(const std::vector<ScanAcc> &scan);
+  void need_device_state();
+  tgx_status exchange_bitmap_slices(const ExchangePlan &xp);
+  tgx_status exchange_records(size_t k);
+  tgx_status join_streams(StreamLoan *loan);
+  void pack(bool exchanged, std::vector<uint8_t> *blob);
+  tgx_status gather_blobs(const std::vector<uint8_t> &blob, std::vector<uint8_t> *gathered);
+  tgx_status reset_and_fold(const std::vector<uint8_t> &gathered);
+};
+
+// Facts and key sets travel on a SECOND stream that waits only for the key columns' uniqueness passes (tgx_update
+// records `keys_ready` right after them and queues the scan of the other columns behind): the exchange -- range / 8
+// bytes per rank and dense key column over xGMI, three collective latencies -- then runs while the state's own stream
+// is still scanning.  Every helper works on `st->stream`, so the state borrows the second stream for the two phases
+// and the two are joined by an event before the states are packed (join_streams).
+tgx_status Step::borrow_stream(StreamLoan *loan, bool has_spearman) {
+  const size_t nd = plan->distinct.size();
+  const bool overlap = comm->ops.device_buffers && st->device_ready && st->keys_ready_recorded && nd > 0 && !has_spearman;
+  st->exchange_expected = comm->ops.device_buffers != 0 && nd > 0;
+  if (!overlap) return TGX_OK;
+  if (!st->aux_stream) {
+    HIP_TRY(stream_acquire(&st->aux_stream, true));  // (the most urgent priority; from the library's pool)
+    HIP_TRY(hipEventCreateWithFlags(&st->aux_done, hipEventDisableTiming));
+  }
+  HIP_TRY(hipStreamWaitEvent(st->aux_stream, st->keys_ready, 0));
+  st->stream = st->aux_stream;
+  loan->on = true;
+  s = st->aux_stream;
+  return TGX_OK;
+}
+
+// SPEARMAN: ranks over the union of the ranks' pairs (a distributed sort, spearman_device.cpp).  Rank-based states do
+// not merge (the reference's neither: analyzers/advanced/correlation.rs:103-109), so their results are computed here
+// and carried past the reset + merge of reset_and_fold by hand (spearman_install).
+tgx_status Step::spearman(std::vector<SpearmanResolved> *results) {
+  SpearmanExchange X;
+  X.rank = R;
+  X.world = W;
+  X.allgather_host = [this](const void *h_send, void *h_recv, size_t bytes) {
+    return do_allgather_host(comm, st->device_ready ? st->stream : nullptr, h_send, h_recv, bytes, err);
   };
-  const size_t facts_bytes = sizeof(Header) + nd * sizeof(TaskFacts);
-  std::vector<uint8_t> mine(facts_bytes), all(facts_bytes * (size_t)W);
+  X.alltoallv = [this](const void *d_send, const uint64_t *sc, void *d_recv, const uint64_t *rc, size_t elem) {
+    return do_alltoallv(comm, st->device_ready ? st->stream : nullptr, d_send, sc, d_recv, rc, elem, err);
+  };
+  TGX_TRY(spearman_allreduce(st, X, results, err));
+  s = st->device_ready ? st->stream : nullptr;
+  spearman_set_reducing(st, true);  // (the state's own blob does not carry these tasks)
+  return TGX_OK;
+}
+
+// what this rank does before it has anything to tell: its key sets resolved, its scan accumulators read back (`scan`:
+// the facts take the key columns' MIN / MAX from them; identities where there is nothing to read)
+void Step::prepare(std::vector<ScanAcc> *scan) {
+  attempt([this, scan](tgx_error *err) -> tgx_status {
+    TGX_TRY(injected(1, err));
+    // (the small staging buffers of the record exchange: allocated here, where a failure still travels in the facts)
+    if (st->device_ready || comm->ops.device_buffers) {
+      HIP_TRY(comm->d_small_send.reserve((size_t)W * 16 + 16));
+      HIP_TRY(comm->d_small_recv.reserve((size_t)W * 16 + 16));
+    }
+    if (st->device_ready && !scan->empty()) {
+      // (queued in front of the resolve's own read-back, into pinned memory: the two come back with one wait)
+      TGX_TRY(pinned_reserve(&comm->h_a, &comm->h_a_cap, scan->size() * sizeof(ScanAcc), err));
+      HIP_TRY(hipMemcpyAsync(comm->h_a, st->d_scan_acc.p, scan->size() * sizeof(ScanAcc), hipMemcpyDeviceToHost, s));
+    }
+    TGX_TRY(distinct_resolve_all(st, err));  // keys outside a sampled bitmap range are brought in first
+    if (st->device_ready) {
+      HIP_TRY(hipStreamSynchronize(s));
+      if (!scan->empty()) memcpy(scan->data(), comm->h_a, scan->size() * sizeof(ScanAcc));
+    }
+    return TGX_OK;
+  });
+  if (local != TGX_OK || !st->device_ready) {
+    for (auto &a : *scan) {
+      memset(&a, 0, sizeof(a));
+      a.min_k = INT64_MAX;
+      a.max_k = INT64_MIN;
+    }
+  }
+}
+
+TaskFacts Step::local_facts(size_t k, const std::vector<ScanAcc> &scan) const {
+  const DistinctTask &task = plan->distinct[k];
+  const DistinctState &ds = st->distinct[k];
+  TaskFacts f{INT64_MAX, INT64_MIN, kKindNone, (ds.wide || !task.tuple.empty()) ? 1 : 0, ds.total_rows,
+              task.multiplicity ? std::min(ds.spare_seen.cap, ds.spare_twice.cap) : ds.spare_seen.cap};
+  if (has_key_set(ds) && !ds.partitioned && st->device_ready)
+    f.kind = ds.mode == DistinctMode::kBitmap ? kKindBitmap : kKindHash;
+  if (f.kind == kKindBitmap) {
+    // tightest range known: the declared one, the scan's running MIN / MAX, else what the bitmap can represent
+    f.lo = ds.base;
+    f.hi = (int64_t)((uint64_t)ds.base + (ds.range - 1));
+    if (ds.has_hint) {
+      f.lo = ds.hint_lo;
+      f.hi = ds.hint_hi;
+    } else if (task.scan_slot >= 0) {
+      ScanAcc a = scan[task.scan_slot];
+      const ScanAcc &h = st->h_scan[task.scan_slot];
+      if (h.non_null > 0) {
+        a.min_k = std::min(a.min_k, h.min_k);
+        a.max_k = std::max(a.max_k, h.max_k);
+        a.non_null += h.non_null;
+      }
+      if (a.non_null > 0 && !a.is_float && a.min_k >= f.lo && a.max_k <= f.hi) {
+        f.lo = a.min_k;
+        f.hi = a.max_k;
+      }
+    }
+  }
+  return f;
+}
+
+// one all-gather of Header + TaskFacts; every rank sees the same block and returns the same from here
+tgx_status Step::facts_round(const std::vector<ScanAcc> &scan) {
+  const size_t nd = plan->distinct.size();
+  facts.stride = sizeof(Header) + nd * sizeof(TaskFacts);
+  std::vector<uint8_t> mine(facts.stride);
+  facts.all.resize(facts.stride * (size_t)W);
   Header *hd = (Header *)mine.data();
   hd->magic = kFactsMagic ^ (uint64_t)nd;
   hd->blob_len = hd->blob_need = 0;
@@ -559,318 +662,202 @@ extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_com
   hd->xchg_cap = st->device_ready ? std::min(comm->d_send.cap, comm->d_recv.cap) : 0;  // (0: "I will have to allocate")
   memcpy(hd->fp_key, plan->fp_key.k, 16);
   TaskFacts *tf = (TaskFacts *)(mine.data() + sizeof(Header));
-  for (size_t k = 0; k < nd; k++) {
-    const DistinctTask &task = plan->distinct[k];
-    const DistinctState &ds = st->distinct[k];
-    TaskFacts f;
-    f.lo = INT64_MAX;
-    f.hi = INT64_MIN;
-    f.kind = kKindNone;
-    f.wide = (ds.wide || !task.tuple.empty()) ? 1 : 0;
-    f.rows = ds.total_rows;
-    f.spare_cap = task.multiplicity ? std::min(ds.spare_seen.cap, ds.spare_twice.cap) : ds.spare_seen.cap;
-    if (!ds.partitioned && st->device_ready) {
-      if (ds.mode == DistinctMode::kBitmap) f.kind = kKindBitmap;
-      if (ds.mode == DistinctMode::kHash) f.kind = kKindHash;
-    }
-    if (f.kind == kKindBitmap) {
-      // tightest range known: the declared one, the scan's running MIN / MAX, else what the bitmap can represent
-      f.lo = ds.base;
-      f.hi = (int64_t)((uint64_t)ds.base + (ds.range - 1));
-      if (ds.has_hint) {
-        f.lo = ds.hint_lo;
-        f.hi = ds.hint_hi;
-      } else if (task.scan_slot >= 0) {
-        ScanAcc a = scan[task.scan_slot];
-        const ScanAcc &h = st->h_scan[task.scan_slot];
-        if (h.non_null > 0) {
-          a.min_k = std::min(a.min_k, h.min_k);
-          a.max_k = std::max(a.max_k, h.max_k);
-          a.non_null += h.non_null;
-        }
-        if (a.non_null > 0 && !a.is_float && a.min_k >= f.lo && a.max_k <= f.hi) {
-          f.lo = a.min_k;
-          f.hi = a.max_k;
-        }
-      }
-    }
-    tf[k] = f;
-  }
-  TGX_TRY(do_allgather_host(comm, s, mine.data(), all.data(), facts_bytes, err));
+  for (size_t k = 0; k < nd; k++) tf[k] = local_facts(k, scan);
+  TGX_TRY(do_allgather_host(comm, s, mine.data(), facts.all.data(), facts.stride, err));
   for (int32_t r = 0; r < W; r++)
-    if (((const Header *)(all.data() + (size_t)r * facts_bytes))->magic != hd->magic)
+    if (facts.header(r).magic != hd->magic)
       return fail(err, TGX_INVALID_ARGUMENT, "rank %d runs a different plan (or the transport mixed up the blocks)", r);
-  TGX_TRY(peers_ok(all.data(), facts_bytes, "while preparing its key sets"));
-  auto facts_of = [&](int32_t r, size_t k) -> const TaskFacts & {
-    return ((const TaskFacts *)(all.data() + (size_t)r * facts_bytes + sizeof(Header)))[k];
-  };
-  // string / tuple key sets: one fingerprint key on all ranks (every rank sees the same facts and returns the same)
-  {
-    bool any_wide = false;
-    for (size_t k = 0; k < nd; k++)
-      for (int32_t r = 0; r < W; r++) any_wide |= facts_of(r, k).wide != 0 && facts_of(r, k).rows > 0;
-    if (any_wide)
-      for (int32_t r = 0; r < W; r++)
-        if (memcmp(((const Header *)(all.data() + (size_t)r * facts_bytes))->fp_key, hd->fp_key, 16) != 0)
-          return fail(err, TGX_INVALID_ARGUMENT,
-                      "rank %d holds another fingerprint key than rank %d: string / tuple keys cannot be united -- give "
-                      "every rank's plan one key (tgx_plan_set_fingerprint_key) before its first state", r, R);
-  }
+  TGX_TRY(peers_ok(facts.all.data(), facts.stride, "while preparing its key sets"));
+  // string / tuple key sets: one fingerprint key on all ranks
+  bool any_wide = false;
+  for (size_t k = 0; k < nd; k++)
+    for (int32_t r = 0; r < W; r++) any_wide |= facts.task(r, k).wide != 0 && facts.task(r, k).rows > 0;
+  if (any_wide)
+    for (int32_t r = 0; r < W; r++)
+      if (memcmp(facts.header(r).fp_key, hd->fp_key, 16) != 0)
+        return fail(err, TGX_INVALID_ARGUMENT,
+                    "rank %d holds another fingerprint key than rank %d: string / tuple keys cannot be united -- give "
+                    "every rank's plan one key (tgx_plan_set_fingerprint_key) before its first state", r, R);
+  return TGX_OK;
+}
 
-  ph_facts.end();
-  HostPhase ph_exchange(st, "xr_exchange");
-  // ---- 2. exact DISTINCT: one exchange of key sets ----------------------------------------------------------------
-  struct BitmapPart {
-    size_t task;
-    int64_t glo;
-    uint64_t slice_words, col_words;
-    bool mult;
-  };
-  std::vector<BitmapPart> parts;
-  std::vector<size_t> by_records;
-  uint64_t row_words = 0;
-  for (size_t k = 0; k < nd; k++) {
-    int64_t glo = INT64_MAX, ghi = INT64_MIN;
-    bool any_set = false, all_bitmap = true, wide = false;
-    uint64_t rows = 0;
-    for (int32_t r = 0; r < W; r++) {
-      const TaskFacts &f = facts_of(r, k);
-      glo = std::min(glo, f.lo);
-      ghi = std::max(ghi, f.hi);
-      any_set |= f.kind != kKindNone;
-      all_bitmap &= f.kind != kKindHash;
-      wide |= f.wide != 0;
-      rows += (uint64_t)f.rows;
-    }
-    if (!any_set) continue;  // nobody holds keys on a device (already partitioned, host-only or empty states)
-    // a pure function of agreed values, so every rank takes the same branch: range bitmaps everywhere, and a global
-    // range that is still dense (at most 16 bits per row of the whole table, below 2^34 values)
-    bool use_bitmap = all_bitmap && !wide && glo <= ghi;
-    if (use_bitmap) {
-      const uint64_t width = (uint64_t)ghi - (uint64_t)glo;
-      use_bitmap = width < (1ull << 34) && width / 16 <= std::max<uint64_t>(rows, 4096);
-    }
-    if (use_bitmap) {
-      const uint64_t words = (((uint64_t)ghi - (uint64_t)glo) >> 5) + 1;
-      BitmapPart p;
-      p.task = k;
-      p.glo = glo;
-      p.slice_words = round_up((words + W - 1) / W, 4);
-      p.col_words = row_words;
-      p.mult = plan->distinct[k].multiplicity;
-      row_words += p.slice_words * (p.mult ? 2 : 1);
-      parts.push_back(p);
-    } else {
-      by_records.push_back(k);
-    }
+// a rank that saw no batch still owns a slice / a share of the keys: it needs its device state now (whether a rank
+// gets here is a function of the facts, and a failure travels in the next status word)
+void Step::need_device_state() {
+  if (st->device_ready) return;
+  attempt([this](tgx_error *e) -> tgx_status {
+    TGX_TRY(need_device(e));
+    TGX_TRY(state_init_device(st, e));
+    hipError_t he = comm->d_small_send.reserve((size_t)W * 16 + 16);
+    if (he == hipSuccess) he = comm->d_small_recv.reserve((size_t)W * 16 + 16);
+    if (he != hipSuccess) return fail(e, TGX_OUT_OF_MEMORY, "exchange staging: %s", hipGetErrorString(he));
+    return TGX_OK;
+  });
+  if (st->device_ready) s = st->stream;
+}
+
+// ONE all-to-all for all dense Int64 columns together: every rank re-bases its bitmaps on the agreed global ranges
+// while it copies them into the send buffer, and adopts the OR of what it receives for the slices it owns
+tgx_status Step::exchange_bitmap_slices(const ExchangePlan &xp) {
+  const size_t total_bytes = (size_t)W * xp.row_words * 4;
+  // does ANY rank have to allocate for this exchange?  (a function of the facts: every rank answers alike)
+  bool any_alloc = false;
+  for (int32_t r = 0; r < W; r++) {
+    any_alloc |= facts.header(r).xchg_cap < total_bytes + 16;
+    for (const BitmapPart &p : xp.parts) any_alloc |= facts.task(r, p.task).spare_cap < p.slice_words * 4 + 16;
   }
-  if ((!parts.empty() || !by_records.empty()) && !st->device_ready) {
-    // (a rank that saw no batch still owns a slice / a share of the keys: it needs its device state now; whether a
-    //  rank gets here is a function of the facts, and a failure travels in the next status word)
-    tgx_error e;
-    memset(&e, 0, sizeof(e));
-    tgx_status sd = need_device(&e);
-    if (sd == TGX_OK) sd = state_init_device(st, &e);
-    if (sd == TGX_OK) {
-      hipError_t he = comm->d_small_send.reserve((size_t)W * 16 + 16);
-      if (he == hipSuccess) he = comm->d_small_recv.reserve((size_t)W * 16 + 16);
-      if (he != hipSuccess) sd = fail(&e, TGX_OUT_OF_MEMORY, "exchange staging: %s", hipGetErrorString(he));
-    }
-    note(sd, e);
-    if (st->device_ready) s = st->stream;
-  }
-  if (!parts.empty()) {
-    const size_t total_bytes = (size_t)W * row_words * 4;
-    // does ANY rank have to allocate for this exchange?  (a function of the facts: every rank answers alike)
-    bool any_alloc = false;
-    for (int32_t r = 0; r < W; r++) {
-      any_alloc |= ((const Header *)(all.data() + (size_t)r * facts_bytes))->xchg_cap < total_bytes + 16;
-      for (const BitmapPart &p : parts) any_alloc |= facts_of(r, p.task).spare_cap < p.slice_words * 4 + 16;
-    }
-    if (fault_site == 2 || fault_site == 3) any_alloc = true;  // (every rank reads the same environment)
-    auto alloc = [&](tgx_error *err) -> tgx_status {
+  if (fault_site == 2 || fault_site == 3) any_alloc = true;  // (every rank reads the same environment)
+  if (local == TGX_OK)
+    attempt([this, &xp, total_bytes](tgx_error *err) -> tgx_status {
       TGX_TRY(injected(2, err));
       HIP_TRY(comm->d_send.reserve(total_bytes + 16));
       HIP_TRY(comm->d_recv.reserve(total_bytes + 16));
-      for (const BitmapPart &p : parts) {
+      for (const BitmapPart &p : xp.parts) {
         DistinctState &ds = st->distinct[p.task];
         TGX_TRY(injected(3, err));
         HIP_TRY(ds.spare_seen.reserve(p.slice_words * 4 + 16));
         if (p.mult) HIP_TRY(ds.spare_twice.reserve(p.slice_words * 4 + 16));
       }
       return TGX_OK;
-    };
-    if (local == TGX_OK) {
-      tgx_error e;
-      memset(&e, 0, sizeof(e));
-      note(alloc(&e), e);
-    }
-    if (any_alloc) TGX_TRY(status_round("while allocating the buffers of the key-set exchange"));
-    // (from here to the blob round nothing of this branch can fail on its own but a queueing call of the runtime: it is
-    //  noted and the blob header carries it)
-    uint32_t *send = comm->d_send.as<uint32_t>();
-    for (const BitmapPart &p : parts) {
-      DistinctState &ds = st->distinct[p.task];
-      const bool have = ds.mode == DistinctMode::kBitmap && !ds.partitioned;
-      // a rank without keys sends zeros (src_words = 0)
-      const long long delta = have ? (long long)((uint64_t)p.glo - (uint64_t)ds.base) : 0;
-      const uint64_t src_words = have ? ds.bitmap_words : 0;
-      launch_bitmap_rebase(have ? ds.seen.as<uint32_t>() : nullptr, src_words, delta, (uint32_t)W, p.slice_words,
-                           row_words, p.col_words, send, s);
-      if (p.mult)
-        launch_bitmap_rebase(have ? ds.twice.as<uint32_t>() : nullptr, src_words, delta, (uint32_t)W, p.slice_words,
-                             row_words, p.col_words + p.slice_words, send, s);
-    }
-    TGX_TRY(do_alltoall(comm, s, comm->d_send.p, comm->d_recv.p, (size_t)row_words * 4, err));
-    const uint32_t *recv = comm->d_recv.as<uint32_t>();
-    for (const BitmapPart &p : parts) {
-      DistinctState &ds = st->distinct[p.task];
-      // the owned slice: OR of what every rank sent for it; the key counters are recounted from it, the row counters
-      // stay (the old bitmap becomes the spare of the next round, so a state that is reset and refilled every step
-      // neither frees nor allocates)
-      const hipError_t me = hipMemsetAsync(ds.counters.as<unsigned long long>() + kCntDistinct, 0,
-                                           2 * sizeof(unsigned long long), s);
-      if (me != hipSuccess) {
-        tgx_error e;
-        note(fail(&e, TGX_DEVICE_ERROR, "hipMemsetAsync failed: %s", hipGetErrorString(me)), e);
-        continue;
-      }
-      launch_bitmap_adopt(recv + p.col_words, p.mult ? recv + p.col_words + p.slice_words : nullptr, (uint32_t)W,
-                          p.slice_words, row_words, ds.spare_seen.as<uint32_t>(),
-                          p.mult ? ds.spare_twice.as<uint32_t>() : nullptr, ds.counters.as<unsigned long long>(), s);
-      std::swap(ds.seen, ds.spare_seen);
-      std::swap(ds.twice, ds.spare_twice);
-      ds.capacity = 0;
-      ds.mode = DistinctMode::kBitmap;
-      ds.col_type = TGX_INT64;
-      ds.base = (int64_t)((uint64_t)p.glo + (uint64_t)R * p.slice_words * 32);
-      ds.range = p.slice_words * 32;
-      ds.bitmap_words = p.slice_words;
-      ds.partitioned = true;
-    }
+    });
+  if (any_alloc) TGX_TRY(status_round("while allocating the buffers of the key-set exchange"));
+  // (from here to the blob round nothing of this phase can fail on its own but a queueing call of the runtime: it is
+  //  noted and the blob header carries it)
+  uint32_t *send = comm->d_send.as<uint32_t>();
+  for (const BitmapPart &p : xp.parts) {
+    DistinctState &ds = st->distinct[p.task];
+    const bool have = ds.mode == DistinctMode::kBitmap && !ds.partitioned;
+    // a rank without keys sends zeros (src_words = 0)
+    const long long delta = have ? (long long)((uint64_t)p.glo - (uint64_t)ds.base) : 0;
+    const uint64_t src_words = have ? ds.bitmap_words : 0;
+    launch_bitmap_rebase(have ? ds.seen.as<uint32_t>() : nullptr, src_words, delta, (uint32_t)W, p.slice_words,
+                         xp.row_words, p.col_words, send, s);
+    if (p.mult)
+      launch_bitmap_rebase(have ? ds.twice.as<uint32_t>() : nullptr, src_words, delta, (uint32_t)W, p.slice_words,
+                           xp.row_words, p.col_words + p.slice_words, send, s);
   }
-  for (size_t k : by_records) {
-    DistinctState &ds = st->distinct[k];
-    bool wide = false;
-    for (int32_t r = 0; r < W; r++) wide |= facts_of(r, k).wide != 0;
-    if (ds.mode == DistinctMode::kUndecided) ds.wide = wide;  // a rank that saw no rows still receives keys
-    const void *recs = nullptr;
-    std::vector<uint64_t> sc((size_t)W, 0), rc((size_t)W, 0);
-    if (!ds.partitioned && local == TGX_OK) {
-      tgx_error e;
-      memset(&e, 0, sizeof(e));
-      tgx_status se = injected(4, &e);
-      if (se == TGX_OK) se = distinct_export_impl(st, k, (uint32_t)W, &recs, sc.data(), &e);
-      note(se, e);
-      if (local != TGX_OK) {  // keep taking part with nothing to send; the status beside the counts tells everybody
-        recs = nullptr;
-        std::fill(sc.begin(), sc.end(), 0);
-      }
-    }
-    // counts first -- 16 bytes per peer: how many records, and whether this rank is still well -- then the records
-    std::vector<uint64_t> cs((size_t)W * 2, 0), cr((size_t)W * 2, 0);
-    for (int32_t r = 0; r < W; r++) {
-      cs[2 * r] = sc[r];
-      cs[2 * r + 1] = (uint64_t)local;
-    }
-    HIP_TRY(hipMemcpyAsync(comm->d_small_send.p, cs.data(), (size_t)W * 16, hipMemcpyHostToDevice, s));
-    TGX_TRY(do_alltoall(comm, s, comm->d_small_send.p, comm->d_small_recv.p, 16, err));
-    HIP_TRY(hipMemcpyAsync(cr.data(), comm->d_small_recv.p, (size_t)W * 16, hipMemcpyDeviceToHost, s));
-    TGX_TRY(deadline_sync(comm, s, "the all-to-all of record counts", err));
-    for (int32_t r = 0; r < W; r++) {
-      rc[r] = cr[2 * r];
-      if (cr[2 * r + 1] != 0) return report(r, cr[2 * r + 1], "while exporting its keys");
-    }
-    const size_t rec_bytes = wide ? sizeof(KeyRecord128) : sizeof(KeyRecord);
-    uint64_t n_recv = 0;
-    for (int32_t r = 0; r < W; r++) n_recv += rc[r];
-    {  // the receive buffer: sized by what the peers announced, so its allocation is this rank's own business --
-       // and the ranks tell each other how it went before anybody sends
-      tgx_error e;
-      memset(&e, 0, sizeof(e));
-      tgx_status sa = injected(5, &e);
-      if (sa == TGX_OK) {
-        const hipError_t he = comm->d_recv.reserve(std::max<size_t>((size_t)n_recv * rec_bytes, 16));
-        if (he != hipSuccess)
-          sa = fail(&e, he == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR,
-                    "receive buffer of %llu key records: %s", (unsigned long long)n_recv, hipGetErrorString(he));
-      }
-      note(sa, e);
-    }
-    TGX_TRY(status_round("while allocating the receive buffer of its keys"));
-    static const uint64_t nothing = 0;
-    TGX_TRY(do_alltoallv(comm, s, recs ? recs : (const void *)&nothing, sc.data(), comm->d_recv.p, rc.data(), rec_bytes, err));
-    // keep the row counters, replace the key set by the owned keys of all ranks (what fails from here on is noted: the
-    // blob round's header carries it, and nothing below needs a peer)
-    {
-      tgx_error e;
-      memset(&e, 0, sizeof(e));
-      tgx_status si = injected(6, &e);
-      if (si == TGX_OK) {
-        const hipError_t me = hipMemsetAsync(ds.counters.as<unsigned long long>() + kCntDistinct, 0,
-                                             3 * sizeof(unsigned long long), s);
-        if (me != hipSuccess) si = fail(&e, TGX_DEVICE_ERROR, "hipMemsetAsync failed: %s", hipGetErrorString(me));
-      }
-      if (si == TGX_OK) {
-        ds.capacity = 0;
-        ds.rows_upper_bound = 0;
-        ds.mode = DistinctMode::kHash;
-        ds.wide = wide;
-        si = distinct_import_records(st, k, comm->d_recv.p, n_recv, wide, &e);
-      }
-      note(si, e);
-    }
-    // (d_recv is reused by the next column's exchange: queued behind the import on the same stream -- the host does
-    //  not wait here; a transport that takes HOST buffers has waited in do_alltoallv)
-    ds.partitioned = true;
-  }
+  TGX_TRY(do_alltoall(comm, s, comm->d_send.p, comm->d_recv.p, (size_t)xp.row_words * 4, err));
+  const uint32_t *recv = comm->d_recv.as<uint32_t>();
+  for (const BitmapPart &p : xp.parts)
+    // the owned slice: OR of what every rank sent for it (a state that is reset and refilled every step neither frees
+    // nor allocates: the spare pair was sized above)
+    attempt([this, &xp, &p, recv](tgx_error *e) -> tgx_status {
+      TGX_TRY(distinct_replace_by_slices(st, p.task, (int64_t)((uint64_t)p.glo + (uint64_t)R * p.slice_words * 32),
+                                         recv + p.col_words, recv + p.col_words + p.slice_words, (uint32_t)W,
+                                         p.slice_words, xp.row_words, e));
+      st->distinct[p.task].col_type = TGX_INT64;
+      return TGX_OK;
+    });
+  return TGX_OK;
+}
 
-  if (loan.on) {  // the state's own stream goes on only after the exchange; the host has not waited for either
-    HIP_TRY(hipEventRecord(st->aux_done, st->aux_stream));
-    st->stream = loan.own;
-    loan.on = false;
-    s = st->stream;
-    HIP_TRY(hipStreamWaitEvent(st->stream, st->aux_done, 0));
-  }
-  ph_exchange.end();
-  HostPhase ph_pack(st, "xr_pack");
-  // ---- 3. the packed partial states: one all-gather, folded in rank order ----------------------------------------
-  size_t len = 0;
-  std::vector<uint8_t> blob;
-  if (local == TGX_OK) {
-    tgx_error e;
-    memset(&e, 0, sizeof(e));
-    tgx_status ss = injected(7, &e);
-    // (packing reads the state back: it waits for the exchange queued above -- with a deadline, like every wait
-    //  behind a collective)
-    if (ss == TGX_OK && comm->ops.device_buffers && st->device_ready && (!parts.empty() || !by_records.empty()))
-      ss = deadline_sync(comm, s, "the exchange of the key sets", &e);
-    // (packing reads every accumulator back: once -- into a buffer of the capacity the ranks last agreed on -- and a
-    //  second time only if the state has outgrown that)
-    if (ss == TGX_OK) {
-      blob.resize(std::max<size_t>(comm->blob_plan == plan ? comm->blob_cap : 0, 4096));
-      ss = tgx_state_serialize(plan, st, blob.data(), blob.size(), &len, &e);
-      if (ss == TGX_INVALID_ARGUMENT && len > blob.size()) {  // ("buffer too small": len says how much it takes)
-        blob.resize(len);
-        memset(&e, 0, sizeof(e));
-        ss = tgx_state_serialize(plan, st, blob.data(), blob.size(), &len, &e);
-      }
-      if (ss == TGX_OK) blob.resize(len);
+// one task's keys as records to their hash owners: counts, then the records (an all-to-all-v), then the import
+tgx_status Step::exchange_records(size_t k) {
+  DistinctState &ds = st->distinct[k];
+  bool wide = false;
+  for (int32_t r = 0; r < W; r++) wide |= facts.task(r, k).wide != 0;
+  if (ds.mode == DistinctMode::kUndecided) ds.wide = wide;  // a rank that saw no rows still receives keys
+  const void *recs = nullptr;
+  std::vector<uint64_t> sc((size_t)W, 0), rc((size_t)W, 0);
+  if (!ds.partitioned && local == TGX_OK) {
+    attempt([this, k, &recs, &sc](tgx_error *e) -> tgx_status {
+      TGX_TRY(injected(4, e));
+      return distinct_export_impl(st, k, (uint32_t)W, &recs, sc.data(), e);
+    });
+    if (local != TGX_OK) {  // keep taking part with nothing to send; the status beside the counts tells everybody
+      recs = nullptr;
+      std::fill(sc.begin(), sc.end(), 0);
     }
-    note(ss, e);
-    if (local != TGX_OK) len = 0;
   }
+  // counts first -- 16 bytes per peer: how many records, and whether this rank is still well -- then the records
+  std::vector<uint64_t> cs((size_t)W * 2, 0), cr((size_t)W * 2, 0);
+  for (int32_t r = 0; r < W; r++) {
+    cs[2 * r] = sc[r];
+    cs[2 * r + 1] = (uint64_t)local;
+  }
+  HIP_TRY(hipMemcpyAsync(comm->d_small_send.p, cs.data(), (size_t)W * 16, hipMemcpyHostToDevice, s));
+  TGX_TRY(do_alltoall(comm, s, comm->d_small_send.p, comm->d_small_recv.p, 16, err));
+  HIP_TRY(hipMemcpyAsync(cr.data(), comm->d_small_recv.p, (size_t)W * 16, hipMemcpyDeviceToHost, s));
+  TGX_TRY(deadline_sync(comm, s, "the all-to-all of record counts", err));
+  for (int32_t r = 0; r < W; r++) {
+    rc[r] = cr[2 * r];
+    if (cr[2 * r + 1] != 0) return report(r, cr[2 * r + 1], "while exporting its keys");
+  }
+  const size_t rec_bytes = wide ? sizeof(KeyRecord128) : sizeof(KeyRecord);
+  uint64_t n_recv = 0;
+  for (int32_t r = 0; r < W; r++) n_recv += rc[r];
+  // the receive buffer: sized by what the peers announced, so its allocation is this rank's own business -- and the
+  // ranks tell each other how it went before anybody sends
+  attempt([this, n_recv, rec_bytes](tgx_error *e) -> tgx_status {
+    TGX_TRY(injected(5, e));
+    const hipError_t he = comm->d_recv.reserve(std::max<size_t>((size_t)n_recv * rec_bytes, 16));
+    if (he != hipSuccess)
+      return fail(e, he == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR,
+                  "receive buffer of %llu key records: %s", (unsigned long long)n_recv, hipGetErrorString(he));
+    return TGX_OK;
+  });
+  TGX_TRY(status_round("while allocating the receive buffer of its keys"));
+  static const uint64_t nothing = 0;
+  TGX_TRY(do_alltoallv(comm, s, recs ? recs : (const void *)&nothing, sc.data(), comm->d_recv.p, rc.data(), rec_bytes, err));
+  // keep the row counters, replace the key set by the owned keys of all ranks (what fails from here on is noted: the
+  // blob round's header carries it, and nothing below needs a peer)
+  attempt([this, k, n_recv, wide](tgx_error *e) -> tgx_status {
+    TGX_TRY(injected(6, e));
+    return distinct_replace_by_records(st, k, comm->d_recv.p, n_recv, wide, e);
+  });
+  // (d_recv is reused by the next column's exchange: queued behind the import on the same stream -- the host does
+  //  not wait here; a transport that takes HOST buffers has waited in do_alltoallv)
+  ds.partitioned = true;  // (also where the import failed: this rank's keys have gone to their owners)
+  return TGX_OK;
+}
+
+// the state's own stream goes on only after the exchange; the host has not waited for either
+tgx_status Step::join_streams(StreamLoan *loan) {
+  if (!loan->on) return TGX_OK;
+  HIP_TRY(hipEventRecord(st->aux_done, st->aux_stream));
+  st->stream = loan->own;
+  loan->on = false;
+  s = st->stream;
+  HIP_TRY(hipStreamWaitEvent(st->stream, st->aux_done, 0));
+  return TGX_OK;
+}
+
+// this rank's partial state as a blob (left empty where the rank has failed: the blob round's header says so)
+void Step::pack(bool exchanged, std::vector<uint8_t> *blob) {
+  if (local == TGX_OK)
+    attempt([this, exchanged, blob](tgx_error *e) -> tgx_status {
+      TGX_TRY(injected(7, e));
+      // (packing reads the state back: it waits for the exchange queued above -- with a deadline, like every wait
+      //  behind a collective)
+      if (comm->ops.device_buffers && st->device_ready && exchanged)
+        TGX_TRY(deadline_sync(comm, s, "the exchange of the key sets", e));
+      // (packing reads every accumulator back: once -- into a buffer of the capacity the ranks last agreed on -- and a
+      //  second time only if the state has outgrown that)
+      size_t len = 0;
+      blob->resize(std::max<size_t>(comm->blob_plan == plan ? comm->blob_cap : 0, 4096));
+      tgx_status ss = tgx_state_serialize(plan, st, blob->data(), blob->size(), &len, e);
+      if (ss == TGX_INVALID_ARGUMENT && len > blob->size()) {  // ("buffer too small": len says how much it takes)
+        blob->resize(len);
+        memset(e, 0, sizeof(*e));
+        ss = tgx_state_serialize(plan, st, blob->data(), blob->size(), &len, e);
+      }
+      if (ss == TGX_OK) blob->resize(len);
+      return ss;
+    });
+  if (local != TGX_OK) blob->clear();
   if (comm->blob_plan != plan) {
     comm->blob_plan = plan;
     comm->blob_cap = 0;
   }
-  ph_pack.end();
-  HostPhase ph_gather(st, "xr_gather");
-  std::vector<uint8_t> sendbuf, recvbuf;
+}
+
+// all-gathers the blobs.  Every rank sends header + payload in a buffer of the agreed capacity; a rank whose payload
+// has outgrown it says so in the header, every rank sees that and all repeat the round with the larger capacity (the
+// first round of a plan only carries the sizes)
+tgx_status Step::gather_blobs(const std::vector<uint8_t> &blob, std::vector<uint8_t> *gathered) {
+  const size_t len = blob.size();
+  std::vector<uint8_t> sendbuf;
   for (int round = 0;; round++) {
-    // every rank sends header + payload in a buffer of the agreed capacity; a rank whose payload has outgrown it says
-    // so in the header, every rank sees that and all repeat the round with the larger capacity (the first round of a
-    // plan only carries the sizes)
     const size_t cap = comm->blob_cap;
     const bool fits = cap > 0 && len <= cap;
     sendbuf.assign(sizeof(Header) + cap, 0);
@@ -881,36 +868,80 @@ extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_com
     h.status = (uint64_t)local;
     memcpy(sendbuf.data(), &h, sizeof(h));
     if (fits) memcpy(sendbuf.data() + sizeof(Header), blob.data(), len);
-    recvbuf.resize(sendbuf.size() * (size_t)W);
-    TGX_TRY(do_allgather_host(comm, s, sendbuf.data(), recvbuf.data(), sendbuf.size(), err));
+    gathered->resize(sendbuf.size() * (size_t)W);
+    TGX_TRY(do_allgather_host(comm, s, sendbuf.data(), gathered->data(), sendbuf.size(), err));
     size_t need = 0;
     bool all_fit = cap > 0;
     for (int32_t r = 0; r < W; r++) {
-      const Header *hr = (const Header *)(recvbuf.data() + (size_t)r * sendbuf.size());
-      if (hr->magic != kFactsMagic) return fail(err, TGX_INTERNAL, "state gather: bad header from rank %d", r);
-      need = std::max<size_t>(need, hr->blob_need);
-      all_fit &= hr->blob_need <= cap;
+      const Header &hr = header_of(gathered->data(), sendbuf.size(), r);
+      if (hr.magic != kFactsMagic) return fail(err, TGX_INTERNAL, "state gather: bad header from rank %d", r);
+      need = std::max<size_t>(need, hr.blob_need);
+      all_fit &= hr.blob_need <= cap;
     }
-    TGX_TRY(peers_ok(recvbuf.data(), sendbuf.size(), "while exchanging its key sets or packing its state"));
-    if (all_fit) break;
+    TGX_TRY(peers_ok(gathered->data(), sendbuf.size(), "while exchanging its key sets or packing its state"));
+    if (all_fit) return TGX_OK;
     if (round >= 3) return fail(err, TGX_INTERNAL, "state gather: the ranks cannot agree on a capacity");
     comm->blob_cap = round_up(need + need / 2 + 64, 256);  // the same on every rank: all saw the same headers
   }
-  ph_gather.end();
-  HostPhase ph_merge(st, "xr_merge");
-  // the local contribution travels in its own blob like everybody else's: empty this state (device buffers are kept)
-  // and fold all W blobs in rank order -- identical arithmetic, hence bit-identical results, on every rank
+}
+
+// the local contribution travels in its own blob like everybody else's: empty this state (device buffers are kept)
+// and fold all W blobs in rank order -- identical arithmetic, hence bit-identical results, on every rank
+tgx_status Step::reset_and_fold(const std::vector<uint8_t> &gathered) {
   TGX_TRY(tgx_state_reset(plan, st, err));
   const size_t stride = sizeof(Header) + comm->blob_cap;
   for (int32_t r = 0; r < W; r++) {
-    const uint8_t *p = recvbuf.data() + (size_t)r * stride;
-    const Header *hr = (const Header *)p;
+    const Header &hr = header_of(gathered.data(), stride, r);
     tgx_state *part = nullptr;
-    TGX_TRY(tgx_state_deserialize(plan, p + sizeof(Header), (size_t)hr->blob_len, &part, err));
+    TGX_TRY(tgx_state_deserialize(plan, (const uint8_t *)(&hr + 1), (size_t)hr.blob_len, &part, err));
     tgx_status ms = tgx_merge(plan, st, &part, 1, err);
     tgx_state_destroy(part);
     if (ms != TGX_OK) return ms;
   }
+  return TGX_OK;
+}
+}  // namespace
+
+extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_comm *comm, tgx_error *err) try {
+  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
+  if (!comm) return fail(err, TGX_INVALID_ARGUMENT, "comm is NULL");
+  bind_thread();  // (a tokio worker / any thread: HIP's current device is per thread)
+  TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
+  if (comm->ops.device_buffers) {
+    TGX_TRY(need_device(err));
+    TGX_TRY(state_init_device(st, err));
+  }
+  Step X(plan, st, comm, err);
+  const bool has_spearman = plan->spearman && spearman_num_tasks(plan) > 0;
+  StreamLoan loan{st, st->stream};
+  TGX_TRY(X.borrow_stream(&loan, has_spearman));
+  std::vector<SpearmanResolved> spearman_results;
+  if (has_spearman) TGX_TRY(X.spearman(&spearman_results));
+  ReducingGuard reducing_guard{st, has_spearman};
+
+  HostPhase ph_facts(st, "xr_facts");
+  std::vector<ScanAcc> scan(plan->scan.size());
+  X.prepare(&scan);
+  TGX_TRY(X.facts_round(scan));
+  ph_facts.end();
+
+  HostPhase ph_exchange(st, "xr_exchange");  // exact DISTINCT: one exchange of key sets
+  const ExchangePlan xp = plan_exchange(X.facts, X.W, plan->distinct);
+  if (!xp.empty()) X.need_device_state();
+  if (!xp.parts.empty()) TGX_TRY(X.exchange_bitmap_slices(xp));
+  for (size_t k : xp.by_records) TGX_TRY(X.exchange_records(k));
+  TGX_TRY(X.join_streams(&loan));
+  ph_exchange.end();
+
+  HostPhase ph_pack(st, "xr_pack");  // the packed partial states: one all-gather, folded in rank order
+  std::vector<uint8_t> blob, gathered;
+  X.pack(!xp.empty(), &blob);
+  ph_pack.end();
+  HostPhase ph_gather(st, "xr_gather");
+  TGX_TRY(X.gather_blobs(blob, &gathered));
+  ph_gather.end();
+  HostPhase ph_merge(st, "xr_merge");
+  TGX_TRY(X.reset_and_fold(gathered));
   if (has_spearman) spearman_install(st, spearman_results);
   return TGX_OK;
 } catch (...) {

@@ -1,7 +1,8 @@
 // api_internal.h -- what the translation units behind include/tgx.h share: tgx_api.cpp (handles, plans, states,
 // profiling, finalize), update.cpp (staging and the fused pass of a batch), distinct_state.cpp (the key sets' host-side
-// bookkeeping, export / import / merge), coalesce.cpp (small batches noted and gathered, the copy pool) and wire.cpp
-// (state blobs).  The helpers declared here are shared between those files only (hidden visibility).
+// bookkeeping, export / import / adopt), merge.cpp (tgx_merge), coalesce.cpp (small batches noted and gathered, the copy
+// pool), wire.cpp (state blobs) and allreduce.cpp (the cross-rank step).  The helpers declared here are shared between
+// those files only (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -99,6 +100,15 @@ struct BatchTraits {
 struct DistinctTotals {
   uint64_t total = 0, non_null = 0, distinct = 0, twice = 0, empty_rows = 0;
 };
+// adds an owner-partitioned (or count-only) partial's totals to the host-side part of `d`.  The +1s distinct_totals()
+// put in for the EMPTY stand-in come off again: they are re-derived from h_empty_rows
+static inline void distinct_fold_totals(DistinctState &d, const DistinctTotals &t) {
+  d.h_total += t.total;
+  d.h_non_null += t.non_null;
+  d.h_distinct += t.distinct - (t.empty_rows > 0 ? 1 : 0);
+  d.h_twice += t.twice - (t.empty_rows > 1 ? 1 : 0);
+  d.h_empty_rows += t.empty_rows;
+}
 struct Gathered {
   std::vector<ScanAcc> scan;
   std::vector<CountAcc> count;

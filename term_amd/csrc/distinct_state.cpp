@@ -1,5 +1,5 @@
 // distinct_state.cpp -- the host side of the exact key sets: bitmaps / hash sets / partitioned lists per DISTINCT task,
-// the sampled range and its repair, export / import / adopt, tgx_merge.  Split off tgx_api.cpp in round 4.
+// the sampled range and its repair, export / import / adopt (tgx_merge is merge.cpp).  Split off tgx_api.cpp in round 4.
 #include "api_internal.h"
 
 tgx_status distinct_read_counters(tgx_state *st, DistinctState &ds, unsigned long long *out,
@@ -1104,7 +1104,26 @@ tgx_status tgx::distinct_resolve_all(tgx_state *st, tgx_error *err) {
 
 
 // ------------------------------------------------------------------------------------------------
-// distinct: export / import / merge
+// distinct: export / import / adopt
+namespace {
+// the rank that owns `key`: must equal owner_of (kernels/distinct.hip), which the export kernels apply to the keys in
+// the table -- the EMPTY key's owner is taken here, on the host
+uint32_t host_owner_of(uint64_t key, uint32_t world) {
+  uint64_t x = key ^ 0x9e3779b97f4a7c15ULL;
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
+  return (uint32_t)((x >> 32) % world);
+}
+
+tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot,
+                                   tgx_error *err) {
+  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
+  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a DISTINCT check", spec_index);
+  *slot = (size_t)plan->bind[spec_index].slot;
+  return TGX_OK;
+}
+}  // namespace
+
 tgx_status tgx::distinct_export_impl(tgx_state *st, size_t slot, uint32_t world,
                                        const void **device_records, uint64_t *counts, tgx_error *err) {
   TGX_TRY(coalesce_flush(st, err));
@@ -1115,7 +1134,6 @@ tgx_status tgx::distinct_export_impl(tgx_state *st, size_t slot, uint32_t world,
   std::vector<unsigned long long> h_counts(world, 0);
   unsigned long long c[kNumDistinctCounters];
   TGX_TRY(distinct_read_counters(st, ds, c, err));
-  const uint64_t n_keys = c[kCntDistinct];
   const uint64_t empty_rows = c[kCntEmptyRows];
   HIP_TRY(ds.export_counts.reserve(2 * world * sizeof(unsigned long long)));
   unsigned long long *d_counts = ds.export_counts.as<unsigned long long>();
@@ -1132,10 +1150,7 @@ tgx_status tgx::distinct_export_impl(tgx_state *st, size_t slot, uint32_t world,
   // the all-ones key lives in a side counter; it travels as one extra record to its owner
   uint32_t empty_owner = 0;
   if (empty_rows > 0) {
-    // same owner function as the kernels (distinct.hip owner_of)
-    uint64_t x = kEmptyKey ^ 0x9e3779b97f4a7c15ULL;
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
-    empty_owner = (uint32_t)((x >> 32) % world);
+    empty_owner = host_owner_of(kEmptyKey, world);
     h_counts[empty_owner] += 1;
   }
   std::vector<unsigned long long> starts(world, 0);
@@ -1144,7 +1159,6 @@ tgx_status tgx::distinct_export_impl(tgx_state *st, size_t slot, uint32_t world,
     starts[r] = total;
     total += h_counts[r];
   }
-  (void)n_keys;
   const size_t rec_bytes = ds.wide ? sizeof(KeyRecord128) : sizeof(KeyRecord);
   HIP_TRY(ds.export_records.reserve(std::max<uint64_t>(total, 1) * rec_bytes));
   HIP_TRY(hipMemcpyAsync(d_cursors, starts.data(), world * sizeof(unsigned long long), hipMemcpyHostToDevice, st->stream));
@@ -1171,22 +1185,19 @@ extern "C" size_t tgx_distinct_record_bytes(const tgx_plan *plan, const tgx_stat
   if (!plan || !st || st->plan != plan || spec_index >= plan->specs.size() ||
       plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
     return 0;
-  const DistinctState &ds = st->distinct[plan->bind[spec_index].slot];
-  const bool wide = ds.wide || is_any_string(ds.col_type) || ds.col_type == TGX_DICT32_UTF8;
-  return wide ? sizeof(KeyRecord128) : sizeof(KeyRecord);
+  return records_are_wide(st->distinct[plan->bind[spec_index].slot]) ? sizeof(KeyRecord128) : sizeof(KeyRecord);
 }
 
 extern "C" tgx_status tgx_distinct_export(const tgx_plan *plan, tgx_state *st, size_t spec_index,
                                           uint32_t world, const void **device_records, uint64_t *counts,
                                           tgx_error *err) try {
   bind_thread();
-  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a DISTINCT check", spec_index);
+  size_t slot = 0;
+  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
   if (world == 0 || world > 256 || !device_records || !counts)
     return fail(err, TGX_INVALID_ARGUMENT, "bad arguments (world must be 1..256)");
   TGX_TRY(need_device(err));
-  return distinct_export_impl(st, plan->bind[spec_index].slot, world, device_records, counts, err);
+  return distinct_export_impl(st, slot, world, device_records, counts, err);
 } catch (...) {
   return tgx::abi_exception(err);
 }
@@ -1222,52 +1233,48 @@ tgx_status tgx::distinct_import_records(tgx_state *st, size_t slot, const void *
   return TGX_OK;
 }
 
+tgx_status tgx::distinct_replace_by_records(tgx_state *st, size_t slot, const void *d_recs, uint64_t n, bool wide,
+                                            tgx_error *err) {
+  DistinctState &ds = st->distinct[slot];
+  static_assert(kCntDistinct == 0 && kCntTwice == 1 && kCntEmptyRows == 2, "the three totals of the keys lie together");
+  HIP_TRY(hipMemsetAsync(ds.counters.as<unsigned long long>() + kCntDistinct, 0, 3 * sizeof(unsigned long long),
+                         st->stream));
+  ds.capacity = 0;  // (the table's memory stays the state's: hash_ensure takes it again if it is large enough)
+  ds.rows_upper_bound = 0;
+  ds.mode = DistinctMode::kHash;
+  ds.wide = wide;
+  TGX_TRY(distinct_import_records(st, slot, d_recs, n, wide, err));
+  ds.partitioned = true;
+  return TGX_OK;
+}
+
 extern "C" tgx_status tgx_distinct_import(const tgx_plan *plan, tgx_state *st, size_t spec_index,
                                           const void *device_records, uint64_t n_records, tgx_error *err) try {
   bind_thread();
-  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a DISTINCT check", spec_index);
+  size_t slot = 0;
+  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
   TGX_TRY(need_device(err));
   TGX_TRY(coalesce_flush(st, err));
-  const size_t slot = plan->bind[spec_index].slot;
   DistinctState &ds = st->distinct[slot];
   TGX_TRY(state_init_device(st, err));
-  // keep the row counts, replace the key set
-  unsigned long long c[kNumDistinctCounters];
-  TGX_TRY(distinct_read_counters(st, ds, c, err));
-  const unsigned long long valid_rows = c[kCntValidRows];
-  const bool wide = ds.wide || is_any_string(ds.col_type) || ds.col_type == TGX_DICT32_UTF8;
+  const bool wide = records_are_wide(ds);  // (before the import below settles ds.wide)
+  // the old set may be of any kind and size: its memory goes back to the cache once the stream is through with it
+  HIP_TRY(hipStreamSynchronize(st->stream));
   ds.seen.release();
   ds.twice.release();
   ds.keys.release();
   ds.dup.release();
-  ds.capacity = 0;
-  ds.rows_upper_bound = 0;
-  ds.mode = DistinctMode::kHash;
-  unsigned long long zero[kNumDistinctCounters];
-  memset(zero, 0, sizeof(zero));
-  zero[kCntValidRows] = valid_rows;
-  HIP_TRY(hipMemcpyAsync(ds.counters.p, zero, sizeof(zero), hipMemcpyHostToDevice, st->stream));
-  HIP_TRY(hipStreamSynchronize(st->stream));  // `zero` is on this stack frame
-  TGX_TRY(distinct_import_records(st, slot, device_records, n_records, wide, err));
+  // of the counters only kCntValidRows outlives an import: the shared form clears the keys' totals in front of it, the
+  // words behind it (outliers, key-store overflow, the partition pass's form) described the old set
+  static_assert(kCntValidRows + 1 == kCntOutOfRange, "the words behind the row counter");
+  HIP_TRY(hipMemsetAsync(ds.counters.as<unsigned long long>() + kCntOutOfRange, 0,
+                         (kNumDistinctCounters - kCntOutOfRange) * sizeof(unsigned long long), st->stream));
+  TGX_TRY(distinct_replace_by_records(st, slot, device_records, n_records, wide, err));
   HIP_TRY(hipStreamSynchronize(st->stream));
-  ds.partitioned = true;
   return TGX_OK;
 } catch (...) {
   return tgx::abi_exception(err);
 }
-
-namespace {
-tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot,
-                                   tgx_error *err) {
-  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a DISTINCT check", spec_index);
-  *slot = (size_t)plan->bind[spec_index].slot;
-  return TGX_OK;
-}
-}  // namespace
 
 extern "C" tgx_status tgx_distinct_range_hint(const tgx_plan *plan, tgx_state *st, size_t spec_index, int64_t lo,
                                               int64_t hi, tgx_error *err) try {
@@ -1307,6 +1314,28 @@ extern "C" tgx_status tgx_distinct_bitmap_view(const tgx_plan *plan, tgx_state *
   return tgx::abi_exception(err);
 }
 
+tgx_status tgx::distinct_replace_by_slices(tgx_state *st, size_t slot, int64_t base, const uint32_t *seen_slices,
+                                           const uint32_t *twice_slices, uint32_t n_slices, uint64_t slice_words,
+                                           uint64_t stride_words, tgx_error *err) {
+  DistinctState &ds = st->distinct[slot];
+  const bool mult = st->plan->distinct[slot].multiplicity;
+  unsigned long long *cnt = ds.counters.as<unsigned long long>();
+  // the keys' two totals are recounted from the owned slice
+  static_assert(kCntDistinct == 0 && kCntTwice == 1, "launch_bitmap_adopt adds to the two totals");
+  HIP_TRY(hipMemsetAsync(cnt + kCntDistinct, 0, 2 * sizeof(unsigned long long), st->stream));
+  launch_bitmap_adopt(seen_slices, mult ? twice_slices : nullptr, n_slices, slice_words, stride_words,
+                      ds.spare_seen.as<uint32_t>(), mult ? ds.spare_twice.as<uint32_t>() : nullptr, cnt, st->stream);
+  std::swap(ds.seen, ds.spare_seen);  // the old bitmap stays around as the spare of the next round
+  std::swap(ds.twice, ds.spare_twice);
+  ds.capacity = 0;
+  ds.mode = DistinctMode::kBitmap;
+  ds.base = base;
+  ds.range = slice_words * 32;
+  ds.bitmap_words = slice_words;
+  ds.partitioned = true;
+  return TGX_OK;
+}
+
 extern "C" tgx_status tgx_distinct_adopt_slices(const tgx_plan *plan, tgx_state *st, size_t spec_index,
                                                 int64_t slice_base, const void *seen_slices,
                                                 const void *twice_slices, uint32_t n_slices, uint64_t slice_words,
@@ -1324,121 +1353,17 @@ extern "C" tgx_status tgx_distinct_adopt_slices(const tgx_plan *plan, tgx_state 
   if (slice_stride_words < slice_words) return fail(err, TGX_INVALID_ARGUMENT, "slice stride shorter than a slice");
   if (mult && !twice_slices) return fail(err, TGX_INVALID_ARGUMENT, "this check needs the 'twice' slices too");
   if (ds.wide) return fail(err, TGX_INVALID_ARGUMENT, "Utf8 key sets have no range bitmap");
-  unsigned long long c[kNumDistinctCounters];
-  TGX_TRY(distinct_read_counters(st, ds, c, err));
-  DevBuf &new_seen = ds.spare_seen, &new_twice = ds.spare_twice;
-  HIP_TRY(new_seen.reserve(slice_words * 4 + 16));
-  if (mult) HIP_TRY(new_twice.reserve(slice_words * 4 + 16));
-  unsigned long long zero[kNumDistinctCounters];
-  memset(zero, 0, sizeof(zero));
-  zero[kCntValidRows] = c[kCntValidRows];
-  zero[kCntOutOfRange] = c[kCntOutOfRange];
-  HIP_TRY(hipMemcpyAsync(ds.counters.p, zero, sizeof(zero), hipMemcpyHostToDevice, st->stream));
-  launch_bitmap_adopt((const uint32_t *)seen_slices, mult ? (const uint32_t *)twice_slices : nullptr, n_slices,
-                      slice_words, slice_stride_words, new_seen.as<uint32_t>(), mult ? new_twice.as<uint32_t>() : nullptr,
-                      ds.counters.as<unsigned long long>(), st->stream);
+  HIP_TRY(hipStreamSynchronize(st->stream));  // (a spare that has to grow goes back to the cache first)
+  HIP_TRY(ds.spare_seen.reserve(slice_words * 4 + 16));
+  if (mult) HIP_TRY(ds.spare_twice.reserve(slice_words * 4 + 16));
+  // kCntValidRows and kCntOutOfRange outlive an adoption: the shared form clears the two totals in front, and the
+  // state handed in here may be of any kind, so the EMPTY stand-in's rows and the words behind go as well
+  unsigned long long *cnt = ds.counters.as<unsigned long long>();
+  HIP_TRY(hipMemsetAsync(cnt + kCntEmptyRows, 0, sizeof(unsigned long long), st->stream));
+  HIP_TRY(hipMemsetAsync(cnt + kCntSpare, 0, (kNumDistinctCounters - kCntSpare) * sizeof(unsigned long long), st->stream));
+  TGX_TRY(distinct_replace_by_slices(st, slot, slice_base, (const uint32_t *)seen_slices,
+                                     (const uint32_t *)twice_slices, n_slices, slice_words, slice_stride_words, err));
   HIP_TRY(hipStreamSynchronize(st->stream));
-  std::swap(ds.seen, ds.spare_seen);  // the old bitmap stays around as the spare of the next round
-  std::swap(ds.twice, ds.spare_twice);
-  ds.capacity = 0;
-  ds.mode = DistinctMode::kBitmap;
-  ds.base = slice_base;
-  ds.range = slice_words * 32;
-  ds.bitmap_words = slice_words;
-  ds.partitioned = true;
-  return TGX_OK;
-} catch (...) {
-  return tgx::abi_exception(err);
-}
-
-extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state *const *srcs, size_t n_srcs,
-                                tgx_error *err) try {
-  bind_thread();
-  if (!plan || !dst || dst->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "dst does not belong to plan");
-  TGX_TRY(coalesce_flush(dst, err));
-  {  // what can refuse a source is checked for ALL sources before dst takes anything of any of them
-    std::vector<int> mode(dst->hll_mode.begin(), dst->hll_mode.end());
-    for (size_t i = 0; i < n_srcs; i++) {
-      tgx_state *src = srcs ? srcs[i] : nullptr;
-      if (!src || src->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "src %zu does not belong to plan", i);
-      if (src == dst) return fail(err, TGX_INVALID_ARGUMENT, "src %zu is dst", i);
-      TGX_TRY(spearman_check_mergeable(src, err));
-      TGX_TRY(coalesce_flush(src, err));  // (its noted batches decide which form an APPROX_DISTINCT task takes)
-      for (size_t k = 0; k < plan->hll.size(); k++) {
-        if (src->hll_mode[k] == 0) continue;
-        if (mode[k] == 0) mode[k] = src->hll_mode[k];
-        if (mode[k] != src->hll_mode[k])
-          return fail(err, TGX_INVALID_ARGUMENT,
-                      "APPROX_DISTINCT task %zu: one state holds registers, the other a key set (src %zu); nothing was merged",
-                      k, i);
-      }
-    }
-  }
-  for (size_t i = 0; i < n_srcs; i++) {
-    tgx_state *src = srcs[i];
-    Gathered g;
-    // distinct totals are handled set-wise below; gather the fixed-size parts
-    {
-      std::vector<DistinctState> hold;  // gather() reads distinct counters too; harmless
-      TGX_TRY(gather(src, &g, err));
-    }
-    for (size_t k = 0; k < g.scan.size(); k++) scan_acc_merge(dst->h_scan[k], g.scan[k]);
-    for (size_t k = 0; k < g.count.size(); k++) {
-      dst->h_count[k].total += g.count[k].total;
-      dst->h_count[k].non_null += g.count[k].non_null;
-    }
-    for (size_t k = 0; k < g.como.size(); k++) como_acc_merge(dst->h_como[k], g.como[k]);
-    for (size_t k = 0; k < plan->hll.size(); k++) {
-      if (src->hll_mode[k] == 0) continue;
-      if (dst->hll_mode[k] == 0) dst->hll_mode[k] = src->hll_mode[k];
-      if (dst->hll_mode[k] != src->hll_mode[k])
-        return fail(err, TGX_INVALID_ARGUMENT, "APPROX_DISTINCT task %zu: one state holds registers, the other a key set", k);
-      if (g.hll[k].empty()) continue;
-      std::vector<uint8_t> &out = dst->h_hll[k];
-      if (out.empty()) {
-        out = g.hll[k];
-      } else {
-        for (int r = 0; r < kHllRegisters; r++) out[r] = std::max(out[r], g.hll[k][r]);
-      }
-    }
-    for (size_t k = 0; k < plan->distinct.size(); k++) {
-      DistinctState &s = src->distinct[k];
-      DistinctState &d = dst->distinct[k];
-      const bool src_has_set = s.mode == DistinctMode::kBitmap || s.mode == DistinctMode::kHash;
-      if (s.partitioned || !src_has_set) {
-        // owner-partitioned (or count-only) partial: key sets are disjoint by construction
-        if (src_has_set && !s.partitioned)
-          return fail(err, TGX_INTERNAL, "distinct merge: unexpected state");
-        const DistinctTotals &t = g.distinct[k];
-        // remove the +1 adjustments distinct_totals() made for the EMPTY stand-in: they are re-derived
-        d.h_total += t.total;
-        d.h_non_null += t.non_null;
-        d.h_distinct += t.distinct - (t.empty_rows > 0 ? 1 : 0);
-        d.h_twice += t.twice - (t.empty_rows > 1 ? 1 : 0);
-        d.h_empty_rows += t.empty_rows;
-        if (s.partitioned) d.partitioned = true;
-      } else {
-        // exact set union on the device
-        TGX_TRY(need_device(err));
-        const void *recs = nullptr;
-        uint64_t cnt = 0;
-        TGX_TRY(distinct_export_impl(src, k, 1, &recs, &cnt, err));
-        TGX_TRY(state_init_device(dst, err));
-        TGX_TRY(distinct_import_records(dst, k, recs, cnt, s.wide, err));
-        HIP_TRY(hipStreamSynchronize(dst->stream));
-        d.h_total += (uint64_t)s.total_rows + s.h_total;
-        unsigned long long c[kNumDistinctCounters];
-        TGX_TRY(distinct_read_counters(src, s, c, err));
-        d.h_non_null += c[kCntValidRows] + s.h_non_null;
-        d.h_distinct += s.h_distinct;
-        d.h_twice += s.h_twice;
-        d.h_empty_rows += s.h_empty_rows;
-      }
-    }
-    TGX_TRY(kll_merge_states(dst, src, err));
-    TGX_TRY(regex_merge_states(dst, src, err));
-    TGX_TRY(joint_merge_states(dst, src, err));
-  }
   return TGX_OK;
 } catch (...) {
   return tgx::abi_exception(err);

@@ -418,6 +418,16 @@ struct DistinctState {
   DevBuf spare_seen, spare_twice;
 };
 
+// the state holds keys on the device (not only counts: undecided, host-only)
+inline bool has_key_set(const DistinctState &ds) {
+  return ds.mode == DistinctMode::kBitmap || ds.mode == DistinctMode::kHash;
+}
+// its exported / imported records are KeyRecord128 (fingerprints of a string, dictionary or tuple key)
+inline bool records_are_wide(const DistinctState &ds) {
+  const int t = ds.col_type;
+  return ds.wide || t == TGX_UTF8 || t == TGX_LARGE_UTF8 || t == TGX_UTF8_VIEW || t == TGX_DICT32_UTF8;
+}
+
 // pattern checks of a dictionary column whose row gather rides on the column's DISTINCT pass (kernels/dict.hip)
 struct DictGather {
   const uint8_t *hits;          // per-entry verdict bytes
@@ -568,7 +578,6 @@ struct tgx_state {
   // device accumulators
   tgx::DevBuf d_scan_acc, d_count_acc, d_como_acc, d_pivots, d_pivot_set;
   tgx::DevBuf d_pivot_search;  // PivotSearch: [scan slots] then [COMOMENTS tasks]
-  tgx::DevBuf d_scan_identity;  // (unused since round 5: state_reset_kernel writes the identities itself)
   struct Widen {
     const void *src;
     void *dst;
@@ -645,6 +654,21 @@ tgx_status distinct_export_impl(tgx_state *st, size_t slot, uint32_t world, cons
 // unites `n` device records into the task's set (switching it to hash mode)
 tgx_status distinct_import_records(tgx_state *st, size_t slot, const void *d_recs, uint64_t n, bool wide,
                                    tgx_error *err);
+// The two ways a state's key set is REPLACED (by the share of the keys this rank owns) while its row counters stay.
+// Both only queue work on the state's stream: they wait for nothing and release nothing -- tgx_allreduce calls them
+// between two collectives; the ABI entry points put their own waits and releases around them.  (Hidden: they are no
+// part of what the library exports.)
+//   bitmap: the OR of `n_slices` slices of `slice_words` words, `stride_words` apart, becomes the set over
+//           [base, base + 32 * slice_words).  It is built in the spare pair (the caller has reserved slice_words * 4 + 16
+//           bytes there) and swapped in, so the old bitmap is the spare of the next round.
+//   records: the current set is forgotten, `n` records are imported and the state is marked partitioned.
+__attribute__((visibility("hidden")))
+tgx_status distinct_replace_by_slices(tgx_state *st, size_t slot, int64_t base, const uint32_t *seen_slices,
+                                      const uint32_t *twice_slices, uint32_t n_slices, uint64_t slice_words,
+                                      uint64_t stride_words, tgx_error *err);
+__attribute__((visibility("hidden")))
+tgx_status distinct_replace_by_records(tgx_state *st, size_t slot, const void *d_recs, uint64_t n, bool wide,
+                                       tgx_error *err);
 // brings in the keys that fell outside a sampled bitmap range (see DistinctState::speculative); a no-op otherwise
 tgx_status distinct_resolve(tgx_state *st, size_t slot, tgx_error *err);
 tgx_status distinct_resolve_all(tgx_state *st, tgx_error *err);

@@ -58,8 +58,7 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
   uint32_t keyed = 0;
   for (size_t k = 0; k < g.distinct.size(); k++) {
     const DistinctState &ds = st->distinct[k];
-    const bool has_set = ds.mode == DistinctMode::kBitmap || ds.mode == DistinctMode::kHash;
-    if (has_set && !ds.partitioned && ds.wide) keyed = 1;
+    if (has_key_set(ds) && !ds.partitioned && ds.wide) keyed = 1;
   }
   w.pod(keyed);
   uint32_t key_words[4] = {0, 0, 0, 0};
@@ -71,8 +70,7 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
   for (size_t k = 0; k < g.distinct.size(); k++) {
     DistinctState &ds = st->distinct[k];
     const DistinctTotals &t = g.distinct[k];
-    const bool has_set = ds.mode == DistinctMode::kBitmap || ds.mode == DistinctMode::kHash;
-    uint32_t partitioned = (ds.partitioned || !has_set) ? 1 : 0;
+    uint32_t partitioned = (ds.partitioned || !has_key_set(ds)) ? 1 : 0;
     w.pod(partitioned);
     w.pod((uint32_t)(ds.wide ? 1 : 0));
     w.pod(t);
@@ -160,11 +158,7 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
     if (!r.ok) break;
     if (partitioned) {
       ds.partitioned = true;
-      ds.h_total = t.total;
-      ds.h_non_null = t.non_null;
-      ds.h_distinct = t.distinct - (t.empty_rows > 0 ? 1 : 0);
-      ds.h_twice = t.twice - (t.empty_rows > 1 ? 1 : 0);
-      ds.h_empty_rows = t.empty_rows;
+      distinct_fold_totals(ds, t);  // (into a fresh state: adding is assigning)
     } else {
       // rebuild the key set on the device from the records.  n_records comes from the blob: bound it by the bytes
       // that are really there BEFORE multiplying (a crafted count would wrap the product past the check)
