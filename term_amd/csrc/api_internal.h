@@ -2,7 +2,9 @@
 // profiling, finalize), update.cpp (staging and the fused pass of a batch), distinct_state.cpp (the key sets' host-side
 // bookkeeping, export / import / adopt), merge.cpp (tgx_merge), coalesce.cpp (small batches noted and gathered, the copy
 // pool), wire.cpp (state blobs) and allreduce.cpp (the cross-rank step).  The helpers declared here are shared between
-// those files only (hidden visibility).
+// those files only (hidden visibility).  What the check modules (kll_device.cpp, regex_device.cpp, spearman_device.cpp,
+// jointbins_device.cpp) need as well -- fail(), HIP_TRY / TGX_TRY, ProfScope, spec_slot -- is in internal.h; the blob's
+// Writer / Reader are in wire_io.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -24,22 +26,6 @@
 #include "spearman_device.h"
 
 using namespace tgx;
-
-#define TGX_HIDDEN __attribute__((visibility("hidden")))
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      return fail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR,      \
-                  "%s failed: %s", #expr, hipGetErrorString(e_));                             \
-  } while (0)
-
-#define TGX_TRY(expr)                  \
-  do {                                 \
-    tgx_status s_ = (expr);            \
-    if (s_ != TGX_OK) return s_;       \
-  } while (0)
 
 typedef long double xdouble;
 constexpr size_t kArenaBytes = 8u << 20;        // pinned staging arena per state
@@ -170,8 +156,6 @@ TGX_HIDDEN void como_store(ComomentAcc &a, int k, xdouble v);
 TGX_HIDDEN void como_rebase(ComomentAcc &b, double px, double py);
 TGX_HIDDEN void como_acc_merge(ComomentAcc &a, const ComomentAcc &b_in);
 TGX_HIDDEN void state_init_host(tgx_state *st, const tgx_plan *plan);
-TGX_HIDDEN void prof_begin(tgx_state *st, const char *name, uint64_t bytes, hipEvent_t *e0, hipEvent_t *e1);
-TGX_HIDDEN void prof_end(tgx_state *st, const char *name, hipEvent_t e0, hipEvent_t e1);
 TGX_HIDDEN void prof_resolve(tgx_state *st);
 TGX_HIDDEN tgx_status distinct_totals(tgx_state *st, size_t slot, DistinctTotals *t, tgx_error *err,
                                   const unsigned long long *pre = nullptr);
@@ -216,12 +200,3 @@ TGX_HIDDEN tgx_status coalesce_prepare_window(const tgx_column &c, int64_t nrows
 TGX_HIDDEN size_t coalesce_host_bytes(const tgx_plan *plan, const tgx_column *columns, int64_t nrows,
                                   const std::vector<WindowPrep> &prep);
 TGX_HIDDEN tgx_status coalesce_release_set(tgx_state *st, int set, tgx_error *err);
-
-struct ProfScope {
-  tgx_state *st;
-  const char *name;
-  hipEvent_t e0, e1;
-  ProfScope(tgx_state *s, const char *n, uint64_t bytes) : st(s), name(n) { prof_begin(s, n, bytes, &e0, &e1); }
-  ~ProfScope() { prof_end(st, name, e0, e1); }
-};
-

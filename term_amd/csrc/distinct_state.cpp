@@ -1113,15 +1113,6 @@ uint32_t host_owner_of(uint64_t key, uint32_t world) {
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
   return (uint32_t)((x >> 32) % world);
 }
-
-tgx_status distinct_slot_of(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot,
-                                   tgx_error *err) {
-  if (!plan || !st || st->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_DISTINCT)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a DISTINCT check", spec_index);
-  *slot = (size_t)plan->bind[spec_index].slot;
-  return TGX_OK;
-}
 }  // namespace
 
 tgx_status tgx::distinct_export_impl(tgx_state *st, size_t slot, uint32_t world,
@@ -1193,7 +1184,7 @@ extern "C" tgx_status tgx_distinct_export(const tgx_plan *plan, tgx_state *st, s
                                           tgx_error *err) try {
   bind_thread();
   size_t slot = 0;
-  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_DISTINCT, "DISTINCT", &slot, err));
   if (world == 0 || world > 256 || !device_records || !counts)
     return fail(err, TGX_INVALID_ARGUMENT, "bad arguments (world must be 1..256)");
   TGX_TRY(need_device(err));
@@ -1252,7 +1243,7 @@ extern "C" tgx_status tgx_distinct_import(const tgx_plan *plan, tgx_state *st, s
                                           const void *device_records, uint64_t n_records, tgx_error *err) try {
   bind_thread();
   size_t slot = 0;
-  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_DISTINCT, "DISTINCT", &slot, err));
   TGX_TRY(need_device(err));
   TGX_TRY(coalesce_flush(st, err));
   DistinctState &ds = st->distinct[slot];
@@ -1279,7 +1270,7 @@ extern "C" tgx_status tgx_distinct_import(const tgx_plan *plan, tgx_state *st, s
 extern "C" tgx_status tgx_distinct_range_hint(const tgx_plan *plan, tgx_state *st, size_t spec_index, int64_t lo,
                                               int64_t hi, tgx_error *err) try {
   size_t slot = 0;
-  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_DISTINCT, "DISTINCT", &slot, err));
   TGX_TRY(coalesce_flush(st, err));
   DistinctState &ds = st->distinct[slot];
   if (ds.mode != DistinctMode::kUndecided)
@@ -1298,7 +1289,7 @@ extern "C" tgx_status tgx_distinct_bitmap_view(const tgx_plan *plan, tgx_state *
                                                tgx_error *err) try {
   bind_thread();
   size_t slot = 0;
-  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_DISTINCT, "DISTINCT", &slot, err));
   TGX_TRY(coalesce_flush(st, err));
   TGX_TRY(distinct_resolve(st, slot, err));
   DistinctState &ds = st->distinct[slot];
@@ -1342,7 +1333,7 @@ extern "C" tgx_status tgx_distinct_adopt_slices(const tgx_plan *plan, tgx_state 
                                                 uint64_t slice_stride_words, tgx_error *err) try {
   bind_thread();
   size_t slot = 0;
-  TGX_TRY(distinct_slot_of(plan, st, spec_index, &slot, err));
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_DISTINCT, "DISTINCT", &slot, err));
   TGX_TRY(need_device(err));
   TGX_TRY(coalesce_flush(st, err));
   TGX_TRY(state_init_device(st, err));

@@ -642,9 +642,40 @@ struct tgx_state {
   std::map<std::string, tgx::ProfileEntry> profile;
 };
 
-// ---- shared between tgx_api.cpp and allreduce.cpp ------------------------------------------------
+// ---- shared by every translation unit of the library ---------------------------------------------
+#define TGX_HIDDEN __attribute__((visibility("hidden")))
+
+// inside a function that has `tgx_error *err` and returns tgx_status: leave with the failure of a HIP call (the text
+// names the expression as written) or of a call that has already filled `err`
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess)                                                                     \
+      return tgx::fail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR, \
+                       "%s failed: %s", #expr, hipGetErrorString(e_));                        \
+  } while (0)
+
+#define TGX_TRY(expr)                  \
+  do {                                 \
+    tgx_status s_ = (expr);            \
+    if (s_ != TGX_OK) return s_;       \
+  } while (0)
+
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
+// the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
+// `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the
+// call is about the plan alone and has checked it
+TGX_HIDDEN inline tgx_status spec_slot(const tgx_plan *plan, const tgx_state *st, size_t spec_index, int kind,
+                                       const char *kind_name, size_t *slot, tgx_error *err,
+                                       const char *foreign = "state does not belong to plan") {
+  if (foreign && (!plan || !st || st->plan != plan)) return fail(err, TGX_INVALID_ARGUMENT, "%s", foreign);
+  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != kind)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a %s check", spec_index, kind_name);
+  *slot = (size_t)plan->bind[spec_index].slot;
+  return TGX_OK;
+}
+
 tgx_status need_device(tgx_error *err);
 tgx_status state_init_device(tgx_state *st, tgx_error *err);
 // partitions the task's key set by owner = mix(key) % world into runs of KeyRecord / KeyRecord128 (device memory
@@ -680,3 +711,13 @@ int device_id();
 void bind_thread();  // hipSetDevice(the device tgx_init selected) for the calling thread
 }  // namespace tgx
 
+// a "name" entry of tgx_profile_get around the launches queued while the scope lives (nothing when profiling is off)
+TGX_HIDDEN void prof_begin(tgx_state *st, const char *name, uint64_t bytes, hipEvent_t *e0, hipEvent_t *e1);
+TGX_HIDDEN void prof_end(tgx_state *st, const char *name, hipEvent_t e0, hipEvent_t e1);
+struct ProfScope {
+  tgx_state *st;
+  const char *name;
+  hipEvent_t e0, e1;
+  ProfScope(tgx_state *s, const char *n, uint64_t bytes) : st(s), name(n) { prof_begin(s, n, bytes, &e0, &e1); }
+  ~ProfScope() { prof_end(st, name, e0, e1); }
+};

@@ -113,13 +113,6 @@ tgx_status joint_gather(tgx_state *st, std::vector<JointHost> *out, tgx_error *e
   return TGX_OK;
 }
 
-tgx_status task_of_spec(const tgx_plan *plan, size_t spec_index, int *slot, tgx_error *err) {
-  if (spec_index >= plan->specs.size() || plan->bind[spec_index].kind != TGX_CHECK_JOINT_BINS)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a JOINT_BINS check", spec_index);
-  *slot = plan->bind[spec_index].slot;
-  return TGX_OK;
-}
-
 }  // namespace
 
 tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err) {
@@ -257,72 +250,55 @@ tgx_status joint_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err) {
 // section: { u32 magic "JNTB", u32 tasks; per task { u32 binned, u32 bins, f64 x_origin, x_width, y_origin, y_width,
 //   i64 total, n, non_finite, f64 x_min, x_max, y_min, y_max, u64 n_words, u64 words[n_words] } }
 // n_words = (bins + 1)^2 + 1 in the count phase (the cells, row-major, then the rows outside [0, bins]), else 0
-tgx_status joint_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err) {
+tgx_status joint_serialize(tgx_state *st, Writer &w, tgx_error *err) {
   const tgx_plan *plan = st->plan;
   if (plan->joint.empty()) return TGX_OK;
   std::vector<JointHost> g;
   TGX_TRY(joint_gather(st, &g, err));
-  auto put = [&](const void *p, size_t n) {
-    if (buf && *len + n <= cap) memcpy(buf + *len, p, n);
-    *len += n;
-  };
-  const uint32_t head[2] = {kJointWireMagic, (uint32_t)plan->joint.size()};
-  put(head, sizeof(head));
+  w.pod(kJointWireMagic);
+  w.pod((uint32_t)plan->joint.size());
   for (size_t k = 0; k < g.size(); k++) {
     const JointTask &t = plan->joint[k];
     const uint32_t phase[2] = {t.binned ? 1u : 0u, t.binning.bins};
-    put(phase, sizeof(phase));
+    w.pod(phase);
     const double edges[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
-    put(edges, sizeof(edges));
+    w.pod(edges);
     const int64_t counts[3] = {g[k].total, g[k].range.n, g[k].range.non_finite};
-    put(counts, sizeof(counts));
+    w.pod(counts);
     const double ext[4] = {g[k].range.x_min, g[k].range.x_max, g[k].range.y_min, g[k].range.y_max};
-    put(ext, sizeof(ext));
-    const uint64_t n_words = g[k].words.size();
-    put(&n_words, sizeof(n_words));
-    put(g[k].words.data(), n_words * sizeof(uint64_t));
+    w.pod(ext);
+    w.pod((uint64_t)g[k].words.size());
+    w.put(g[k].words.data(), g[k].words.size() * sizeof(uint64_t));
   }
   return TGX_OK;
 }
 
-tgx_status joint_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err) {
+tgx_status joint_deserialize(tgx_state *st, Reader &r, tgx_error *err) {
   const tgx_plan *plan = st->plan;
   JointState *js = js_of(st);
   if (!js) return TGX_OK;
-  bool ok = true;
-  auto get = [&](void *p, size_t n) {
-    if (!ok || n > len - *pos) {
-      ok = false;
-      memset(p, 0, n);
-      return;
-    }
-    memcpy(p, buf + *pos, n);
-    *pos += n;
-  };
-  if (*pos > len) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
-  uint32_t head[2];
-  get(head, sizeof(head));
-  if (!ok || head[0] != kJointWireMagic || head[1] != plan->joint.size())
+  const uint32_t magic = r.pod<uint32_t>(), tasks = r.pod<uint32_t>();
+  if (!r.ok || magic != kJointWireMagic || tasks != plan->joint.size())
     return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan (JOINT_BINS section)");
   for (size_t k = 0; k < plan->joint.size(); k++) {
     const JointTask &t = plan->joint[k];
     uint32_t phase[2];
     double edges[4], ext[4];
     int64_t counts[3];
-    uint64_t n_words = 0;
-    get(phase, sizeof(phase));
-    get(edges, sizeof(edges));
-    get(counts, sizeof(counts));
-    get(ext, sizeof(ext));
-    get(&n_words, sizeof(n_words));
-    if (!ok) break;
+    r.get(phase, sizeof(phase));
+    r.get(edges, sizeof(edges));
+    r.get(counts, sizeof(counts));
+    r.get(ext, sizeof(ext));
+    const uint64_t n_words = r.pod<uint64_t>();
+    if (!r.ok) break;
     const double mine[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
     if (phase[0] != (t.binned ? 1u : 0u) || phase[1] != t.binning.bins || memcmp(edges, mine, sizeof(mine)) != 0)
       return fail(err, TGX_INVALID_ARGUMENT,
                   "JOINT_BINS task %zu: the blob was counted under another binning (bins %u) than the plan's (bins %u)", k,
                   phase[1], t.binning.bins);
     JointHost &h = js->host[k];
-    if (n_words != h.words.size() || n_words > (len - *pos) / sizeof(uint64_t))
+    size_t bytes = 0;
+    if (n_words != h.words.size() || !r.fits(n_words, sizeof(uint64_t), &bytes))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (JOINT_BINS task %zu)", k);
     h.total = counts[0];
     h.range.n = counts[1];
@@ -331,9 +307,9 @@ tgx_status joint_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size
     h.range.x_max = ext[1];
     h.range.y_min = ext[2];
     h.range.y_max = ext[3];
-    get(h.words.data(), (size_t)n_words * sizeof(uint64_t));
+    r.get(h.words.data(), bytes);
   }
-  if (!ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
+  if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
   return TGX_OK;
 }
 
@@ -344,8 +320,8 @@ using namespace tgx;
 extern "C" tgx_status tgx_plan_set_joint_binning(tgx_plan *plan, size_t spec_index, const tgx_joint_binning *b,
                                                  tgx_error *err) try {
   if (!plan || !b) return fail(err, TGX_INVALID_ARGUMENT, "plan/binning is NULL");
-  int slot = -1;
-  TGX_TRY(task_of_spec(plan, spec_index, &slot, err));
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_JOINT_BINS, "JOINT_BINS", &slot, err, nullptr));
   if (plan->fp_key_locked.load())
     return fail(err, TGX_INVALID_ARGUMENT, "the binning of a JOINT_BINS check is fixed once a state of the plan exists");
   if (b->bins < 2) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: bins must be at least 2", spec_index);
@@ -374,9 +350,9 @@ extern "C" tgx_status tgx_plan_set_joint_binning(tgx_plan *plan, size_t spec_ind
 extern "C" tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *st, size_t spec_index, tgx_joint_range *out,
                                           tgx_error *err) try {
   bind_thread();
-  if (!plan || !st || st->plan != plan || !out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
-  int slot = -1;
-  TGX_TRY(task_of_spec(plan, spec_index, &slot, err));
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_JOINT_BINS, "JOINT_BINS", &slot, err, "bad arguments"));
   std::vector<JointHost> g;
   TGX_TRY(joint_gather(st, &g, err));
   const JointHost &h = g[slot];
@@ -396,9 +372,9 @@ extern "C" tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *st, s
 extern "C" tgx_status tgx_joint_counts(const tgx_plan *plan, tgx_state *st, size_t spec_index, uint64_t *cells,
                                        uint64_t cap, uint64_t *n_cells, uint64_t *out_of_range, tgx_error *err) try {
   bind_thread();
-  if (!plan || !st || st->plan != plan || !n_cells) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
-  int slot = -1;
-  TGX_TRY(task_of_spec(plan, spec_index, &slot, err));
+  if (!n_cells) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_JOINT_BINS, "JOINT_BINS", &slot, err, "bad arguments"));
   const JointTask &t = plan->joint[slot];
   if (!t.binned)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu is in its range phase: no binning was set (tgx_plan_set_joint_binning)",

@@ -2,6 +2,7 @@
 // see jointbins_device.cpp.
 #pragma once
 #include "internal.h"
+#include "wire_io.h"
 
 namespace tgx {
 tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
@@ -13,6 +14,6 @@ tgx_status joint_update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx
 tgx_status joint_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err);
 tgx_status joint_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err);
 // the blob's section: present only when the plan has such tasks (blobs of other plans keep their bytes)
-tgx_status joint_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err);
-tgx_status joint_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err);
+TGX_HIDDEN tgx_status joint_serialize(tgx_state *st, Writer &w, tgx_error *err);
+TGX_HIDDEN tgx_status joint_deserialize(tgx_state *st, Reader &r, tgx_error *err);
 }  // namespace tgx

@@ -1,9 +1,8 @@
-// kll_device.cpp -- KLL tasks of a state: device sketching (kernels/kll.hip) + host-side merge/query.
+// kll_device.cpp -- KLL tasks of a state: device sketching (kernels/kll.hip) + host-side merge/query.  Errors, profile
+// entries ("kll") and the blob section go through the library's shared helpers (internal.h, wire_io.h).
 #include "kll_device.h"
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -38,24 +37,6 @@ struct KllDeviceState {
   DevBuf scratch;              // per-workgroup sketches of the batch being processed
   uint64_t salt = 0x6b6c6c5f74677821ULL;
 };
-
-tgx_status kfail(tgx_error *err, tgx_status code, const char *fmt, ...) {
-  if (err) {
-    err->code = code;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err->msg, sizeof(err->msg), fmt, ap);
-    va_end(ap);
-  }
-  return code;
-}
-#define KHIP(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess)                                                                            \
-      return kfail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR, "%s failed: %s", \
-                   #expr, hipGetErrorString(e_));                                                    \
-  } while (0)
 
 KllDeviceState *dev(tgx_state *st) { return (KllDeviceState *)st->kll; }
 }  // namespace
@@ -113,9 +94,9 @@ tgx_status kll_scan_prepare(tgx_state *st, size_t slot, int64_t rows, int n_wave
   b.top = top;
   b.n_picks = (int64_t)n_waves * cap;
   b.n_left = (int64_t)n_waves << top;
-  KHIP(b.picks.reserve((size_t)b.n_picks * 8 + 64));
-  KHIP(b.left.reserve((size_t)b.n_left * 8 + 64));
-  KHIP(b.meta.reserve((size_t)n_waves * sizeof(KllWaveMeta)));
+  HIP_TRY(b.picks.reserve((size_t)b.n_picks * 8 + 64));
+  HIP_TRY(b.left.reserve((size_t)b.n_left * 8 + 64));
+  HIP_TRY(b.meta.reserve((size_t)n_waves * sizeof(KllWaveMeta)));
   k->salt = k->salt * 6364136223846793005ULL + 1442695040888963407ULL;
   out->picks = b.picks.as<double>();
   out->left = b.left.as<double>();
@@ -136,27 +117,25 @@ tgx_status kll_scan_finish(tgx_state *st, tgx_error *err) {
   for (size_t i = 0; i < k->scan.size(); i++)
     if (k->scan[i].pending) slots.push_back(i);
   if (slots.empty()) return TGX_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (st->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
-    (void)hipEventRecord(e0, st->stream);
+  uint64_t bytes = 0;  // what the jobs below read: every pending task's picks and leftovers
+  for (size_t slot : slots) bytes += (uint64_t)(k->scan[slot].n_picks + k->scan[slot].n_left) * 8;
+  ProfScope ps(st, "kll", bytes);
   std::vector<KllJob> jobs;
   std::vector<int64_t> scratch_at;
   int64_t scratch_total = 0;
-  uint64_t bytes = 0;
   for (size_t slot : slots) {
     KllScanBuffers &b = k->scan[slot];
     b.pending = false;
     if (!k->sketch[slot].p) {
-      KHIP(k->sketch[slot].reserve(sizeof(KllDeviceSketch)));
+      HIP_TRY(k->sketch[slot].reserve(sizeof(KllDeviceSketch)));
       launch_kll_init(k->sketch[slot].as<KllDeviceSketch>(), st->stream, 0);
     }
     if (k->sketch_hi[slot].p && k->dirty_hi[slot] && k->hi_shift[slot] != b.top) {
       // a batch of another size class: its picks weigh differently -- hand the old ones to the host first
-      tgx_status s = kll_flush(st, err);
-      if (s != TGX_OK) return s;
+      TGX_TRY(kll_flush(st, err));
     }
     if (!k->sketch_hi[slot].p || k->hi_shift[slot] != b.top) {
-      KHIP(k->sketch_hi[slot].reserve(sizeof(KllDeviceSketch)));
+      HIP_TRY(k->sketch_hi[slot].reserve(sizeof(KllDeviceSketch)));
       k->hi_shift[slot] = b.top;
       launch_kll_init(k->sketch_hi[slot].as<KllDeviceSketch>(), st->stream, b.top);
     }
@@ -177,11 +156,10 @@ tgx_status kll_scan_finish(tgx_state *st, tgx_error *err) {
       scratch_at.push_back(scratch_total);
       scratch_total += groups;
       jobs.push_back(job);
-      bytes += (uint64_t)job.d.length * 8;
     }
     k->dirty[slot] = k->dirty_hi[slot] = 1;
   }
-  KHIP(k->scratch.reserve((size_t)scratch_total * sizeof(KllDeviceSketch)));
+  HIP_TRY(k->scratch.reserve((size_t)scratch_total * sizeof(KllDeviceSketch)));
   for (size_t j = 0; j < jobs.size(); j++) jobs[j].sketches = k->scratch.as<KllDeviceSketch>() + scratch_at[j];
   launch_kll_jobs(jobs.data(), (int)jobs.size(), st->stream);
   for (size_t slot : slots) {
@@ -191,22 +169,16 @@ tgx_status kll_scan_finish(tgx_state *st, tgx_error *err) {
     launch_kll_meta(b.meta.as<KllWaveMeta>(), b.n_waves, k->sketch[slot].as<KllDeviceSketch>(), st->stream);
     launch_kll_meta(b.meta.as<KllWaveMeta>(), b.n_waves, k->sketch_hi[slot].as<KllDeviceSketch>(), st->stream);
   }
-  if (st->profiling && e0 && e1) {
-    (void)hipEventRecord(e1, st->stream);
-    ProfileEntry &pe = st->profile["kll"];
-    pe.pending.emplace_back(e0, e1);
-    pe.pending_bytes.push_back(bytes);
-  }
   return TGX_OK;
 }
 
 tgx_status kll_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error *err) {
   KllDeviceState *k = dev(st);
   if (c.type != TGX_INT64 && c.type != TGX_FLOAT64)
-    return kfail(err, TGX_UNSUPPORTED, "KLL needs a numeric column (type %d)", c.type);
+    return fail(err, TGX_UNSUPPORTED, "KLL needs a numeric column (type %d)", c.type);
   if (c.length == 0) return TGX_OK;
   if (!k->sketch[slot].p) {
-    KHIP(k->sketch[slot].reserve(sizeof(KllDeviceSketch)));
+    HIP_TRY(k->sketch[slot].reserve(sizeof(KllDeviceSketch)));
     launch_kll_init(k->sketch[slot].as<KllDeviceSketch>(), st->stream, 0);
   }
   // one workgroup per >= 64 Ki rows, at most 1024 of them (235 MiB of scratch sketches)
@@ -215,7 +187,7 @@ tgx_status kll_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error
   int64_t chunk = (c.length + groups - 1) / groups;
   chunk = (chunk + 4095) / 4096 * 4096;
   groups = (c.length + chunk - 1) / chunk;
-  KHIP(k->scratch.reserve((size_t)groups * sizeof(KllDeviceSketch)));
+  HIP_TRY(k->scratch.reserve((size_t)groups * sizeof(KllDeviceSketch)));
   KllColDesc d;
   d.values = c.values;
   d.validity = c.validity;
@@ -224,10 +196,6 @@ tgx_status kll_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error
   d.is_float = c.type == TGX_FLOAT64;
   d.pad = 0;
   k->salt = k->salt * 6364136223846793005ULL + 1442695040888963407ULL;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (st->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-    (void)hipEventRecord(e0, st->stream);
-  }
   KllJob job;
   memset(&job, 0, sizeof(job));
   job.d = d;
@@ -237,12 +205,9 @@ tgx_status kll_update(tgx_state *st, size_t slot, const tgx_column &c, tgx_error
   job.salt = k->salt;
   job.top = kll_top_for(d.length);
   job.groups = (int32_t)groups;
-  launch_kll_jobs(&job, 1, st->stream);
-  if (st->profiling && e0 && e1) {
-    (void)hipEventRecord(e1, st->stream);
-    ProfileEntry &pe = st->profile["kll"];
-    pe.pending.emplace_back(e0, e1);
-    pe.pending_bytes.push_back((uint64_t)c.length * 8 + (c.validity ? (uint64_t)(c.length + 7) / 8 : 0));
+  {
+    ProfScope ps(st, "kll", (uint64_t)c.length * 8 + (c.validity ? (uint64_t)(c.length + 7) / 8 : 0));
+    launch_kll_jobs(&job, 1, st->stream);
   }
   k->dirty[slot] = 1;
   return TGX_OK;
@@ -257,8 +222,8 @@ tgx_status kll_flush(tgx_state *st, tgx_error *err) {
       char &dirty = hi ? k->dirty_hi[i] : k->dirty[i];
       if (!dirty) continue;
       std::vector<uint8_t> raw(sizeof(KllDeviceSketch));
-      KHIP(hipMemcpyAsync(raw.data(), buf.p, raw.size(), hipMemcpyDeviceToHost, st->stream));
-      KHIP(hipStreamSynchronize(st->stream));
+      HIP_TRY(hipMemcpyAsync(raw.data(), buf.p, raw.size(), hipMemcpyDeviceToHost, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));
       const KllDeviceSketch *s = (const KllDeviceSketch *)raw.data();
       KllHost part;
       part.k = st->h_kll[i].k;
@@ -269,7 +234,7 @@ tgx_status kll_flush(tgx_state *st, tgx_error *err) {
       if (s->lv0_count) part.add_level_items(s->shift, s->lv0, s->lv0_count);
       for (int l = 1; l < kKllMaxLevels; l++)
         if ((s->level_mask >> l) & 1) part.add_level_items((size_t)l, s->runs[l], kKllRunItems);
-      if (!st->h_kll[i].merge(part)) return kfail(err, TGX_INTERNAL, "KLL merge failed");
+      if (!st->h_kll[i].merge(part)) return fail(err, TGX_INTERNAL, "KLL merge failed");
       launch_kll_init(buf.as<KllDeviceSketch>(), st->stream, hi ? k->hi_shift[i] : 0);
       dirty = 0;
     }
@@ -278,80 +243,65 @@ tgx_status kll_flush(tgx_state *st, tgx_error *err) {
 }
 
 tgx_status kll_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) {
-  tgx_status s = kll_flush(st, err);
-  if (s != TGX_OK) return s;
+  TGX_TRY(kll_flush(st, err));
   r->kll_n = st->h_kll[slot].n;
   r->non_null = (int64_t)st->h_kll[slot].n;
   return TGX_OK;
 }
 
 tgx_status kll_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err) {
-  tgx_status s = kll_flush(dst, err);
-  if (s != TGX_OK) return s;
-  s = kll_flush(src, err);
-  if (s != TGX_OK) return s;
+  TGX_TRY(kll_flush(dst, err));
+  TGX_TRY(kll_flush(src, err));
   for (size_t i = 0; i < dst->h_kll.size(); i++)
     if (!dst->h_kll[i].merge(src->h_kll[i]))
-      return kfail(err, TGX_INVALID_ARGUMENT, "Cannot merge sketches with different k values: %u vs %u",
+      return fail(err, TGX_INVALID_ARGUMENT, "Cannot merge sketches with different k values: %u vs %u",
                    dst->h_kll[i].k, src->h_kll[i].k);
   return TGX_OK;
 }
 
 // wire: per task  u32 k, u32 n_levels, u64 n, f64 min, f64 max, then per level u32 count + items
-tgx_status kll_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err) {
-  tgx_status s = kll_flush(st, err);
-  if (s != TGX_OK) return s;
-  auto put = [&](const void *p, size_t n) {
-    if (n && buf && *len + n <= cap) memcpy(buf + *len, p, n);  // (an empty level has no items: p may be null)
-    *len += n;
-  };
+tgx_status kll_serialize(tgx_state *st, Writer &w, tgx_error *err) {
+  TGX_TRY(kll_flush(st, err));
   for (auto &h : st->h_kll) {
-    uint32_t k = h.k, nl = (uint32_t)h.levels.size();
-    put(&k, 4);
-    put(&nl, 4);
-    put(&h.n, 8);
-    put(&h.min_v, 8);
-    put(&h.max_v, 8);
+    w.pod(h.k);
+    w.pod((uint32_t)h.levels.size());
+    w.pod(h.n);
+    w.pod(h.min_v);
+    w.pod(h.max_v);
     for (auto &lv : h.levels) {
-      uint32_t c = (uint32_t)lv.size();
-      put(&c, 4);
-      put(lv.data(), (size_t)c * 8);
+      w.pod((uint32_t)lv.size());
+      w.put(lv.data(), lv.size() * 8);
     }
   }
   return TGX_OK;
 }
 
-tgx_status kll_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err) {
-  auto get = [&](void *p, size_t n) -> bool {
-    if (*pos + n > len) return false;
-    if (n) memcpy(p, buf + *pos, n);  // (an empty level: p may be null)
-    *pos += n;
-    return true;
-  };
+// (the section's own texts; `r.ok` is looked at before a count from the blob sizes anything)
+tgx_status kll_deserialize(tgx_state *st, Reader &r, tgx_error *err) {
   for (auto &h : st->h_kll) {
-    uint32_t k = 0, nl = 0;
-    if (!get(&k, 4) || !get(&nl, 4) || !get(&h.n, 8) || !get(&h.min_v, 8) || !get(&h.max_v, 8))
-      return kfail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
-    if (k != h.k) return kfail(err, TGX_INVALID_ARGUMENT, "state blob was produced with k=%u, plan has k=%u", k, h.k);
-    if (nl > 64) return kfail(err, TGX_INVALID_ARGUMENT, "corrupt state blob (kll levels)");
+    const uint32_t k = r.pod<uint32_t>(), nl = r.pod<uint32_t>();
+    h.n = r.pod<uint64_t>();
+    h.min_v = r.pod<double>();
+    h.max_v = r.pod<double>();
+    if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
+    if (k != h.k) return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced with k=%u, plan has k=%u", k, h.k);
+    if (nl > 64) return fail(err, TGX_INVALID_ARGUMENT, "corrupt state blob (kll levels)");
     h.levels.assign(nl, {});
     for (uint32_t l = 0; l < nl; l++) {
-      uint32_t c = 0;
-      if (!get(&c, 4) || c > (1u << 20)) return kfail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
+      const uint32_t c = r.pod<uint32_t>();
+      if (!r.ok || c > (1u << 20)) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
       h.levels[l].resize(c);
-      if (!get(h.levels[l].data(), (size_t)c * 8)) return kfail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
+      r.get(h.levels[l].data(), (size_t)c * 8);
+      if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob (kll)");
     }
   }
   return TGX_OK;
 }
 
-static tgx_status kll_slot(const tgx_plan *plan, tgx_state *st, size_t spec_index, int *slot, tgx_error *err) {
-  if (!plan || !st || st->plan != plan) return kfail(err, TGX_INVALID_ARGUMENT, "state does not belong to plan");
-  if (spec_index >= plan->specs.size() || plan->specs[spec_index].kind != TGX_CHECK_KLL)
-    return kfail(err, TGX_INVALID_ARGUMENT, "spec %zu is not a KLL check", spec_index);
-  *slot = plan->bind[spec_index].slot;
-  tgx_status cs = coalesce_flush(st, err);  // batches tgx_update has only noted so far
-  if (cs != TGX_OK) return cs;
+// the task behind a KLL spec, with everything the state has been given folded into h_kll
+static tgx_status kll_slot(const tgx_plan *plan, tgx_state *st, size_t spec_index, size_t *slot, tgx_error *err) {
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_KLL, "KLL", slot, err));
+  TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
   return kll_flush(st, err);
 }
 
@@ -362,14 +312,13 @@ using namespace tgx;
 extern "C" tgx_status tgx_kll_quantile(const tgx_plan *plan, tgx_state *st, size_t spec_index, double phi,
                                        double *out, tgx_error *err) try {
   bind_thread();
-  int slot = 0;
-  tgx_status s = kll_slot(plan, st, spec_index, &slot, err);
-  if (s != TGX_OK) return s;
-  if (!out) return kfail(err, TGX_INVALID_ARGUMENT, "out is NULL");
+  size_t slot = 0;
+  TGX_TRY(kll_slot(plan, st, spec_index, &slot, err));
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "out is NULL");
   int rc = st->h_kll[slot].quantile(phi, out);
   // messages of KllSketch::get_quantile (kll_sketch.rs:247-257)
-  if (rc == 1) return kfail(err, TGX_INVALID_ARGUMENT, "Cannot compute quantile on empty sketch");
-  if (rc == 2) return kfail(err, TGX_INVALID_ARGUMENT, "Quantile phi must be in [0, 1], got %g", phi);
+  if (rc == 1) return fail(err, TGX_INVALID_ARGUMENT, "Cannot compute quantile on empty sketch");
+  if (rc == 2) return fail(err, TGX_INVALID_ARGUMENT, "Quantile phi must be in [0, 1], got %g", phi);
   return TGX_OK;
 } catch (...) {
   return tgx::abi_exception(err);
@@ -379,9 +328,8 @@ extern "C" tgx_status tgx_kll_summary(const tgx_plan *plan, tgx_state *st, size_
                                       double *min_value, double *max_value, uint64_t *num_levels,
                                       uint64_t *num_retained, tgx_error *err) try {
   bind_thread();
-  int slot = 0;
-  tgx_status s = kll_slot(plan, st, spec_index, &slot, err);
-  if (s != TGX_OK) return s;
+  size_t slot = 0;
+  TGX_TRY(kll_slot(plan, st, spec_index, &slot, err));
   const KllHost &h = st->h_kll[slot];
   if (n) *n = h.n;
   if (min_value) *min_value = h.min_v;
@@ -397,9 +345,8 @@ extern "C" tgx_status tgx_kll_level_items(const tgx_plan *plan, tgx_state *st, s
                                           uint64_t level, double *out, uint64_t cap, uint64_t *count,
                                           tgx_error *err) try {
   bind_thread();
-  int slot = 0;
-  tgx_status s = kll_slot(plan, st, spec_index, &slot, err);
-  if (s != TGX_OK) return s;
+  size_t slot = 0;
+  TGX_TRY(kll_slot(plan, st, spec_index, &slot, err));
   const KllHost &h = st->h_kll[slot];
   uint64_t c = level < h.levels.size() ? h.levels[level].size() : 0;
   if (count) *count = c;

@@ -1,6 +1,7 @@
 // kll_device.h -- KLL sketch tasks of a state (device sketching + host merge); see kll_device.cpp.
 #pragma once
 #include "internal.h"
+#include "wire_io.h"
 
 namespace tgx {
 void kll_state_init(tgx_state *st);
@@ -19,6 +20,6 @@ tgx_status kll_scan_finish(tgx_state *st, tgx_error *err);  // every prepared ta
 tgx_status kll_flush(tgx_state *st, tgx_error *err);
 tgx_status kll_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err);
 tgx_status kll_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err);
-tgx_status kll_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err);
-tgx_status kll_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err);
+TGX_HIDDEN tgx_status kll_serialize(tgx_state *st, Writer &w, tgx_error *err);
+TGX_HIDDEN tgx_status kll_deserialize(tgx_state *st, Reader &r, tgx_error *err);
 }  // namespace tgx

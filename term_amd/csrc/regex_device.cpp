@@ -1,11 +1,11 @@
 // regex_device.cpp -- REGEX_MATCH tasks: pattern validation + DFA compilation at plan time, the match
-// kernel at update time (kernels/regex.hip), counts merged like any other additive state.
+// kernel at update time (kernels/regex.hip), counts merged like any other additive state.  Errors, profile entries and
+// the blob section go through the library's shared helpers (internal.h, wire_io.h).
 #include "regex_device.h"
 
-#include <vector>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "kernels/regex_types.h"
 #include "regex/regex_compile.h"
@@ -57,37 +57,13 @@ struct RegexState {
   bool fetched_ok = false;
 };
 
-tgx_status rfail(tgx_error *err, tgx_status code, const char *fmt, ...) {
-  if (err) {
-    err->code = code;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err->msg, sizeof(err->msg), fmt, ap);
-    va_end(ap);
-  }
-  return code;
-}
-#define RHIP(expr)                                                                                         \
-  do {                                                                                                     \
-    hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess)                                                                                  \
-      return rfail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR, "%s failed: %s", \
-                   #expr, hipGetErrorString(e_));                                                          \
-  } while (0)
-
-#define TGX_TRY_R(expr)          \
-  do {                           \
-    tgx_status s_ = (expr);      \
-    if (s_ != TGX_OK) return s_; \
-  } while (0)
-
 const RegexPlan *rplan(const tgx_plan *p) { return (const RegexPlan *)p->regex; }
 RegexState *rstate(tgx_state *s) { return (RegexState *)s->regex; }
 
 tgx_status compile_checked(const char *pattern, size_t len, uint32_t flags, rx::Dfa *dfa, tgx_error *err) {
   std::string msg;
   rx::CompileStatus rs = rx::validate_pattern_rules(pattern, len, &msg);
-  if (rs != rx::kOk) return rfail(err, TGX_INVALID_ARGUMENT, "%s", msg.c_str());
+  if (rs != rx::kOk) return fail(err, TGX_INVALID_ARGUMENT, "%s", msg.c_str());
   // a pattern is compiled by validate, by plan_create and by every is_match / match_group of a host-side check: the
   // last few automata of the thread are kept (a pattern with Unicode word boundaries takes 15-100 ms to build)
   struct Cached {
@@ -103,8 +79,8 @@ tgx_status compile_checked(const char *pattern, size_t len, uint32_t flags, rx::
       return TGX_OK;
     }
   rs = rx::compile(pattern, len, fold, dfa, &msg);
-  if (rs == rx::kInvalid) return rfail(err, TGX_INVALID_ARGUMENT, "%s", msg.c_str());
-  if (rs != rx::kOk) return rfail(err, TGX_UNSUPPORTED, "%s", msg.c_str());
+  if (rs == rx::kInvalid) return fail(err, TGX_INVALID_ARGUMENT, "%s", msg.c_str());
+  if (rs != rx::kOk) return fail(err, TGX_UNSUPPORTED, "%s", msg.c_str());
   if (cache.size() >= 8) cache.erase(cache.begin());
   cache.push_back({std::string(pattern, len), fold, *dfa});
   return TGX_OK;
@@ -116,7 +92,7 @@ tgx_status regex_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *
   RegexPlan *rp = (RegexPlan *)plan->regex;
   const tgx_check_spec &sp = plan->specs[spec_index];
   if (sp.kind == TGX_CHECK_LENGTH) {
-    if (sp.length_min > sp.length_max) return rfail(err, TGX_INVALID_ARGUMENT, "LENGTH: length_min > length_max");
+    if (sp.length_min > sp.length_max) return fail(err, TGX_INVALID_ARGUMENT, "LENGTH: length_min > length_max");
     for (size_t i = 0; i < rp->tasks.size(); i++)
       if (rp->tasks[i].is_length && rp->tasks[i].column == sp.column && rp->tasks[i].len_min == sp.length_min &&
           rp->tasks[i].len_max == sp.length_max) {
@@ -145,8 +121,7 @@ tgx_status regex_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *
   t.column = sp.column;
   t.flags = flags;
   t.pattern = pat;
-  tgx_status s = compile_checked(pat.data(), pat.size(), flags, &t.dfa, err);
-  if (s != TGX_OK) return s;
+  TGX_TRY(compile_checked(pat.data(), pat.size(), flags, &t.dfa, err));
   rp->tasks.push_back(std::move(t));
   *slot = (int)rp->tasks.size() - 1;
   return TGX_OK;
@@ -254,12 +229,12 @@ static tgx_status upload_dfa(uint32_t n_states, uint32_t n_classes, const uint8_
       for (uint32_t b = 0; b < 256; b++) table[(size_t)s2 * 256 + b] = src[(size_t)s2 * n_classes + byte_class[b]];
     for (uint32_t b = 0; b < 256; b++) cls[b] = (uint8_t)b;
   }
-  RHIP(d_table.reserve(table.size() * sizeof(uint16_t) + 16));
-  RHIP(d_class.reserve(256));
-  RHIP(d_accept.reserve(accept.size() + 16));
-  RHIP(hipMemcpy(d_table.p, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  RHIP(hipMemcpy(d_class.p, cls, 256, hipMemcpyHostToDevice));
-  RHIP(hipMemcpy(d_accept.p, accept.data(), accept.size(), hipMemcpyHostToDevice));
+  HIP_TRY(d_table.reserve(table.size() * sizeof(uint16_t) + 16));
+  HIP_TRY(d_class.reserve(256));
+  HIP_TRY(d_accept.reserve(accept.size() + 16));
+  HIP_TRY(hipMemcpy(d_table.p, table.data(), table.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_class.p, cls, 256, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_accept.p, accept.data(), accept.size(), hipMemcpyHostToDevice));
   return TGX_OK;
 }
 
@@ -269,33 +244,17 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
   RegexState *rs = rstate(st);
   rs->fetched_ok = false;
   const int n_cu = tgx_num_cus();
-  struct Timer {  // one "regex" profile entry per launch
-    tgx_state *st;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit Timer(tgx_state *s) : st(s) {
-      if (st->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess)
-        (void)hipEventRecord(e0, st->stream);
-    }
-    ~Timer() {
-      if (st->profiling && e0 && e1) {
-        (void)hipEventRecord(e1, st->stream);
-        ProfileEntry &pe = st->profile["regex"];
-        pe.pending.emplace_back(e0, e1);
-        pe.pending_bytes.push_back(0);  // value bytes are data dependent; bench.py prices them itself
-      }
-    }
-  };
   for (size_t i = 0; i < rp->tasks.size(); i++) {
     const RegexTask &t = rp->tasks[i];
     const tgx_column &c = dev[t.column];
     if (c.type != TGX_UTF8 && c.type != TGX_LARGE_UTF8 && c.type != TGX_DICT32_UTF8 && c.type != TGX_UTF8_VIEW)
-      return rfail(err, TGX_UNSUPPORTED, "%s needs a Utf8 column (column %d has type %d)",
+      return fail(err, TGX_UNSUPPORTED, "%s needs a Utf8 column (column %d has type %d)",
                    t.is_length ? "LENGTH" : "REGEX_MATCH", t.column, c.type);
   }
   if (!rs->counter_pool.p && !rs->tasks.empty()) {
-    RHIP(rs->counter_pool.reserve(rs->tasks.size() * 16));
+    HIP_TRY(rs->counter_pool.reserve(rs->tasks.size() * 16));
     // zero-filled on the state's (non-blocking) stream: ordered with the kernels that add to the counters
-    RHIP(hipMemsetAsync(rs->counter_pool.p, 0, rs->tasks.size() * 16, st->stream));
+    HIP_TRY(hipMemsetAsync(rs->counter_pool.p, 0, rs->tasks.size() * 16, st->stream));
     for (size_t k = 0; k < rs->tasks.size(); k++)
       rs->tasks[k].counters.borrow((char *)rs->counter_pool.p + 16 * k, 16);
   }
@@ -309,8 +268,8 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
     const tgx_column &sc = is_dict ? *c.dictionary : c;
     if (c.length == 0 || sc.length == 0) continue;
     if (!gs.uploaded) {
-      TGX_TRY_R(upload_dfa(grp.dfa.n_states, grp.dfa.n_classes, grp.dfa.byte_class, grp.dfa.table, grp.dfa.accept_mask,
-                           gs.table, gs.byte_class, gs.accept_end, &gs.direct, err));
+      TGX_TRY(upload_dfa(grp.dfa.n_states, grp.dfa.n_classes, grp.dfa.byte_class, grp.dfa.table, grp.dfa.accept_mask,
+                         gs.table, gs.byte_class, gs.accept_end, &gs.direct, err));
       gs.uploaded = true;
     }
     RegexColDesc d;
@@ -320,7 +279,7 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
       const RegexTask &t = rp->tasks[grp.members[k]];
       RegexTaskState &ts = rs->tasks[grp.members[k]];
       if (t.flags & TGX_FLAG_NULL_IS_VALID) d.null_mask |= 1u << k;
-      if (is_dict) RHIP(ts.dict_hits.reserve((size_t)sc.length + 32));
+      if (is_dict) HIP_TRY(ts.dict_hits.reserve((size_t)sc.length + 32));
       d.hits_k[k] = is_dict ? ts.dict_hits.as<uint8_t>() : nullptr;
       // dictionary columns: counters[1] soaks up the per-entry match count, counters[0] receives the per-row one
       d.counters_k[k] = ts.counters.as<unsigned long long>() + (is_dict ? 1 : 0);
@@ -335,7 +294,7 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
     v.start = grp.dfa.start;
     v.direct = gs.direct ? 1 : 0;
     v.n_final = grp.dfa.n_final;
-    Timer timer(st);
+    ProfScope ps(st, "regex", 0);  // (value bytes are data dependent; bench.py prices them itself)
     launch_regex(d, v, nullptr, n_cu, st->stream);
   }
   // ---- single patterns, LENGTH checks, and the per-row gathers of dictionary columns
@@ -345,12 +304,12 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
     const tgx_column &c = dev[t.column];
     const bool is_dict = c.type == TGX_DICT32_UTF8;
     if (!t.is_length && !ts.table.p && !walked[i])
-      TGX_TRY_R(upload_dfa(t.dfa.n_states, t.dfa.n_classes, t.dfa.byte_class, t.dfa.table, t.dfa.accept_at_end, ts.table,
-                           ts.byte_class, ts.accept_end, &ts.direct, err));
+      TGX_TRY(upload_dfa(t.dfa.n_states, t.dfa.n_classes, t.dfa.byte_class, t.dfa.table, t.dfa.accept_at_end, ts.table,
+                         ts.byte_class, ts.accept_end, &ts.direct, err));
     ts.total += (uint64_t)c.length;
     if (c.length == 0) continue;
     const tgx_column &sc = is_dict ? *c.dictionary : c;
-    if (is_dict) RHIP(ts.dict_hits.reserve((size_t)sc.length + 32));
+    if (is_dict) HIP_TRY(ts.dict_hits.reserve((size_t)sc.length + 32));
     RegexColDesc d;
     fill_col_desc(c, t.flags, &d);
     d.hits = is_dict ? ts.dict_hits.as<uint8_t>() : nullptr;
@@ -363,7 +322,7 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
     v.start = t.dfa.start;
     v.direct = ts.direct ? 1 : 0;
     v.n_final = 2;
-    Timer timer(st);
+    ProfScope ps(st, "regex", 0);  // (value bytes are data dependent; bench.py prices them itself)
     const LengthBounds lb{t.len_min, t.len_max};
     // an automaton with a character count (`^C{m,n}$`, regex_compile.h): the walk leaves a byte per row, a second pass
     // takes the rows whose length is outside the bounds out of the matches and counts
@@ -373,7 +332,7 @@ tgx_status regex_update(tgx_state *st, const tgx_column *dev, tgx_error *err, Di
       if (t.is_length) {
         launch_length(d, lb, ts.counters.as<unsigned long long>(), n_cu, st->stream);
       } else if (!walked[i] && bounded) {
-        RHIP(ts.dict_hits.reserve((size_t)c.length + 32));
+        HIP_TRY(ts.dict_hits.reserve((size_t)c.length + 32));
         d.hits = ts.dict_hits.as<uint8_t>();
         launch_regex(d, v, ts.counters.as<unsigned long long>() + 1, n_cu, st->stream);  // (counters[1]: scratch)
         launch_length_filter(d, lbb, ts.counters.as<unsigned long long>(), n_cu, st->stream);
@@ -417,9 +376,9 @@ tgx_status regex_fetch_begin(tgx_state *st, tgx_error *err) {
   RegexState *rs = rstate(st);
   if (!rs || !rs->counter_pool.p) return TGX_OK;
   rs->fetched.resize(rs->tasks.size() * 2);
-  RHIP(hipMemcpyAsync(rs->fetched.data(), rs->counter_pool.p, rs->tasks.size() * 16, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(rs->fetched.data(), rs->counter_pool.p, rs->tasks.size() * 16, hipMemcpyDeviceToHost,
                       st->stream));  // ordered on the state's stream: no wait for the rest of the device
-  RHIP(hipStreamSynchronize(st->stream));
+  HIP_TRY(hipStreamSynchronize(st->stream));
   rs->fetched_ok = true;
   return TGX_OK;
 }
@@ -435,8 +394,8 @@ static tgx_status regex_totals(tgx_state *st, size_t i, uint64_t *total, uint64_
   if (rs->fetched_ok) {
     dev_matches = rs->fetched[2 * i];
   } else if (ts.counters.p) {
-    RHIP(hipMemcpyAsync(&dev_matches, ts.counters.p, 8, hipMemcpyDeviceToHost, st->stream));
-    RHIP(hipStreamSynchronize(st->stream));
+    HIP_TRY(hipMemcpyAsync(&dev_matches, ts.counters.p, 8, hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
   }
   *total = ts.total + ts.h_total;
   *matches = dev_matches + ts.h_matches;
@@ -445,8 +404,7 @@ static tgx_status regex_totals(tgx_state *st, size_t i, uint64_t *total, uint64_
 
 tgx_status regex_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) {
   uint64_t total = 0, matches = 0;
-  tgx_status s = regex_totals(st, (size_t)slot, &total, &matches, err);
-  if (s != TGX_OK) return s;
+  TGX_TRY(regex_totals(st, (size_t)slot, &total, &matches, err));
   r->total = (int64_t)total;
   r->matches = (int64_t)matches;
   return TGX_OK;
@@ -454,8 +412,7 @@ tgx_status regex_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *
 
 tgx_status regex_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err) {
   if (!dst->regex) return TGX_OK;
-  tgx_status fs = regex_fetch_begin(src, err);
-  if (fs != TGX_OK) return fs;
+  TGX_TRY(regex_fetch_begin(src, err));
   for (size_t i = 0; i < rstate(dst)->tasks.size(); i++) {
     uint64_t total = 0, matches = 0;
     tgx_status s = regex_totals(src, i, &total, &matches, err);
@@ -470,10 +427,9 @@ tgx_status regex_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err) {
   return TGX_OK;
 }
 
-tgx_status regex_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err) {
+tgx_status regex_serialize(tgx_state *st, Writer &w, tgx_error *err) {
   if (!st->regex) return TGX_OK;
-  tgx_status fs = regex_fetch_begin(st, err);
-  if (fs != TGX_OK) return fs;
+  TGX_TRY(regex_fetch_begin(st, err));
   for (size_t i = 0; i < rstate(st)->tasks.size(); i++) {
     uint64_t v[2] = {0, 0};
     tgx_status s = regex_totals(st, i, &v[0], &v[1], err);
@@ -481,22 +437,18 @@ tgx_status regex_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap,
       regex_fetch_end(st);
       return s;
     }
-    if (buf && *len + 16 <= cap) memcpy(buf + *len, v, 16);
-    *len += 16;
+    w.put(v, 16);
   }
   regex_fetch_end(st);
   return TGX_OK;
 }
 
-tgx_status regex_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err) {
+tgx_status regex_deserialize(tgx_state *st, Reader &r, tgx_error *err) {
   if (!st->regex) return TGX_OK;
   for (auto &t : rstate(st)->tasks) {
-    if (*pos + 16 > len) return rfail(err, TGX_INVALID_ARGUMENT, "truncated state blob (regex)");
-    uint64_t v[2];
-    memcpy(v, buf + *pos, 16);
-    *pos += 16;
-    t.h_total = v[0];
-    t.h_matches = v[1];
+    t.h_total = r.pod<uint64_t>();
+    t.h_matches = r.pod<uint64_t>();
+    if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob (regex)");
   }
   return TGX_OK;
 }
@@ -506,7 +458,7 @@ tgx_status regex_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size
 using namespace tgx;
 
 extern "C" tgx_status tgx_regex_validate(const char *pattern, size_t len, uint32_t flags, tgx_error *err) try {
-  if (!pattern && len) return rfail(err, TGX_INVALID_ARGUMENT, "pattern is NULL");
+  if (!pattern && len) return fail(err, TGX_INVALID_ARGUMENT, "pattern is NULL");
   rx::Dfa dfa;
   return compile_checked(pattern ? pattern : "", len, flags, &dfa, err);
 } catch (...) {
@@ -517,10 +469,9 @@ extern "C" tgx_status tgx_regex_validate(const char *pattern, size_t len, uint32
 // mean what I think), never used by tgx_update.
 extern "C" tgx_status tgx_regex_is_match(const char *pattern, size_t plen, uint32_t flags, const uint8_t *value,
                                          size_t vlen, int32_t *matched, tgx_error *err) try {
-  if ((!pattern && plen) || (!value && vlen) || !matched) return rfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  if ((!pattern && plen) || (!value && vlen) || !matched) return fail(err, TGX_INVALID_ARGUMENT, "NULL argument");
   rx::Dfa dfa;
-  tgx_status s = compile_checked(pattern ? pattern : "", plen, flags, &dfa, err);
-  if (s != TGX_OK) return s;
+  TGX_TRY(compile_checked(pattern ? pattern : "", plen, flags, &dfa, err));
   size_t b = 0, e = vlen;
   if (flags & TGX_FLAG_TRIM) {
     while (b < e && value[b] == 0x20) b++;
@@ -536,14 +487,13 @@ extern "C" tgx_status tgx_regex_match_group(const char *const *patterns, const s
                                             const uint32_t *flags, size_t n_patterns, const uint8_t *value, size_t vlen,
                                             uint32_t *mask, int32_t *grouped, tgx_error *err) try {
   if (!patterns || !pattern_lens || !mask || (!value && vlen) || n_patterns == 0 || n_patterns > (size_t)kMaxRegexGroup)
-    return rfail(err, TGX_INVALID_ARGUMENT, "bad arguments (1..%d patterns)", kMaxRegexGroup);
+    return fail(err, TGX_INVALID_ARGUMENT, "bad arguments (1..%d patterns)", kMaxRegexGroup);
   std::vector<rx::Dfa> dfas(n_patterns);
   std::vector<const rx::Dfa *> parts;
   bool same_trim = true;
   for (size_t k = 0; k < n_patterns; k++) {
     const uint32_t f = flags ? flags[k] : 0;
-    tgx_status s = compile_checked(patterns[k] ? patterns[k] : "", pattern_lens[k], f, &dfas[k], err);
-    if (s != TGX_OK) return s;
+    TGX_TRY(compile_checked(patterns[k] ? patterns[k] : "", pattern_lens[k], f, &dfas[k], err));
     parts.push_back(&dfas[k]);
     same_trim &= ((f ^ (flags ? flags[0] : 0)) & TGX_FLAG_TRIM) == 0;
   }

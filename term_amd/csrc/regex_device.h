@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "wire_io.h"
 
 namespace tgx {
 tgx_status regex_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
@@ -21,6 +22,6 @@ tgx_status regex_fetch_begin(tgx_state *st, tgx_error *err);
 void regex_fetch_end(tgx_state *st);
 tgx_status regex_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err);
 tgx_status regex_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err);
-tgx_status regex_serialize(tgx_state *st, size_t *len, uint8_t *buf, size_t cap, tgx_error *err);
-tgx_status regex_deserialize(tgx_state *st, const uint8_t *buf, size_t len, size_t *pos, tgx_error *err);
+TGX_HIDDEN tgx_status regex_serialize(tgx_state *st, Writer &w, tgx_error *err);
+TGX_HIDDEN tgx_status regex_deserialize(tgx_state *st, Reader &r, tgx_error *err);
 }  // namespace tgx

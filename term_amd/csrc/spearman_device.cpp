@@ -1,10 +1,9 @@
-// spearman_device.cpp -- keeps the (x, y) pairs of every batch on the device and ranks them at finalize.
+// spearman_device.cpp -- keeps the (x, y) pairs of every batch on the device and ranks them at finalize.  (No blob
+// section: spearman_check_mergeable refuses.)  Errors go through fail / HIP_TRY / TGX_TRY of internal.h.
 #include "spearman_device.h"
 
 #include "kernels/sortrank.h"
 
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -64,30 +63,6 @@ struct SpearmanState {
   bool reducing = false;
 };
 
-tgx_status sfail(tgx_error *err, tgx_status code, const char *fmt, ...) {
-  if (err) {
-    err->code = code;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err->msg, sizeof(err->msg), fmt, ap);
-    va_end(ap);
-  }
-  return code;
-}
-#define SHIP(expr)                                                                                         \
-  do {                                                                                                     \
-    hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess)                                                                                  \
-      return sfail(err, e_ == hipErrorOutOfMemory ? TGX_OUT_OF_MEMORY : TGX_DEVICE_ERROR, "%s failed: %s", \
-                   #expr, hipGetErrorString(e_));                                                          \
-  } while (0)
-
-#define STRY(expr)               \
-  do {                           \
-    tgx_status s_ = (expr);      \
-    if (s_ != TGX_OK) return s_; \
-  } while (0)
-
 const SpearmanPlan *splan(const tgx_plan *p) { return (const SpearmanPlan *)p->spearman; }
 SpearmanState *sstate(tgx_state *s) { return (SpearmanState *)s->spearman; }
 
@@ -100,7 +75,7 @@ tgx_status spearman_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_erro
   if (!plan->spearman) plan->spearman = new SpearmanPlan();
   SpearmanPlan *sp = (SpearmanPlan *)plan->spearman;
   const tgx_check_spec &s = plan->specs[spec_index];
-  if (s.column2 < 0) return sfail(err, TGX_INVALID_ARGUMENT, "spec %d: SPEARMAN needs column2", spec_index);
+  if (s.column2 < 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %d: SPEARMAN needs column2", spec_index);
   const bool exact = (s.flags & TGX_FLAG_EXACT_RANK_SUMS) != 0;
   for (size_t i = 0; i < sp->tasks.size(); i++)
     if (sp->tasks[i].col_x == s.column && sp->tasks[i].col_y == s.column2 && sp->tasks[i].exact_sums == exact) {
@@ -156,19 +131,19 @@ tgx_status append_rows(tgx_state *st, SpearmanTaskState &ts, const void *xv, con
                        const uint8_t *yval, int64_t xoff, int64_t yoff, int64_t length, int x_is_float, int y_is_float,
                        tgx_error *err) {
   if (!ts.count.p) {
-    SHIP(ts.count.reserve(16));
-    SHIP(hipMemsetAsync(ts.count.p, 0, 16, st->stream));
+    HIP_TRY(ts.count.reserve(16));
+    HIP_TRY(hipMemsetAsync(ts.count.p, 0, 16, st->stream));
   }
   const uint64_t need = ts.rows_upper + (uint64_t)length;
   if (need > ts.capacity) {
     const uint64_t cap = std::max<uint64_t>(need, ts.capacity * 2);
     DevBuf nx, ny;
-    SHIP(nx.reserve(cap * 8));
-    SHIP(ny.reserve(cap * 8));
+    HIP_TRY(nx.reserve(cap * 8));
+    HIP_TRY(ny.reserve(cap * 8));
     if (ts.capacity && ts.rows_upper) {
-      SHIP(hipMemcpyAsync(nx.p, ts.kx.p, ts.rows_upper * 8, hipMemcpyDeviceToDevice, st->stream));
-      SHIP(hipMemcpyAsync(ny.p, ts.ky.p, ts.rows_upper * 8, hipMemcpyDeviceToDevice, st->stream));
-      SHIP(hipStreamSynchronize(st->stream));
+      HIP_TRY(hipMemcpyAsync(nx.p, ts.kx.p, ts.rows_upper * 8, hipMemcpyDeviceToDevice, st->stream));
+      HIP_TRY(hipMemcpyAsync(ny.p, ts.ky.p, ts.rows_upper * 8, hipMemcpyDeviceToDevice, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));
     }
     ts.kx = std::move(nx);
     ts.ky = std::move(ny);
@@ -195,10 +170,10 @@ tgx_status resolve_lent(tgx_state *st, SpearmanTaskState &ts, tgx_error *err) {
     ts.capacity = std::min(ts.kx.cap, ts.ky.cap) / 8;
     ts.rows_upper = ts.work_pairs;
     ts.work_x = ts.work_y = nullptr;
-    if (!ts.count.p) SHIP(ts.count.reserve(16));
+    if (!ts.count.p) HIP_TRY(ts.count.reserve(16));
     ts.count_seed[0] = ts.work_pairs;
     ts.count_seed[1] = 0;
-    SHIP(hipMemcpyAsync(ts.count.p, ts.count_seed, 16, hipMemcpyHostToDevice, st->stream));
+    HIP_TRY(hipMemcpyAsync(ts.count.p, ts.count_seed, 16, hipMemcpyHostToDevice, st->stream));
   }
   if (!ts.lent.length) return TGX_OK;
   const LentBatch b = ts.lent;
@@ -209,7 +184,7 @@ tgx_status resolve_lent(tgx_state *st, SpearmanTaskState &ts, tgx_error *err) {
 
 tgx_status spearman_resolve_all(tgx_state *st, tgx_error *err) {
   if (!st->spearman) return TGX_OK;
-  for (auto &ts : sstate(st)->tasks) STRY(resolve_lent(st, ts, err));
+  for (auto &ts : sstate(st)->tasks) TGX_TRY(resolve_lent(st, ts, err));
   return TGX_OK;
 }
 
@@ -224,13 +199,13 @@ tgx_status spearman_update(tgx_state *st, const tgx_column *dev, const tgx_colum
     SpearmanTaskState &ts = ss->tasks[i];
     auto numeric = [](int t) { return t == TGX_INT64 || t == TGX_FLOAT64; };
     if (!numeric(x.type) || !numeric(y.type))
-      return sfail(err, TGX_INVALID_ARGUMENT, "SPEARMAN needs numeric columns (%d, %d)", x.type, y.type);
+      return fail(err, TGX_INVALID_ARGUMENT, "SPEARMAN needs numeric columns (%d, %d)", x.type, y.type);
     if (ts.resolved)
-      return sfail(err, TGX_UNSUPPORTED, "SPEARMAN: the state holds the result of a cross-rank reduction; reset it first");
+      return fail(err, TGX_UNSUPPORTED, "SPEARMAN: the state holds the result of a cross-rank reduction; reset it first");
     ts.total_rows += x.length;
     if (x.length == 0) continue;
     ts.cached = false;
-    STRY(resolve_lent(st, ts, err));  // (a second batch: the first becomes pairs of the state's own)
+    TGX_TRY(resolve_lent(st, ts, err));  // (a second batch: the first becomes pairs of the state's own)
     // the first batch, in the caller's own DEVICE buffers, without NULLs, large enough for the ranking to take it
     const bool lend = lendable && ts.rows_upper == 0 && !x.validity && !y.validity && ox.mem == TGX_MEM_DEVICE &&
                       oy.mem == TGX_MEM_DEVICE && x.values == ox.values && y.values == oy.values &&
@@ -245,8 +220,8 @@ tgx_status spearman_update(tgx_state *st, const tgx_column *dev, const tgx_colum
     }
     // (a widened Float32 column is never lent: its keys quiet their NaNs as they are made, kernels/spearman.hip)
     auto fl = [](const tgx_column &c, const tgx_column &o) { return c.type == TGX_FLOAT64 ? (o.type == TGX_FLOAT32 ? 2 : 1) : 0; };
-    STRY(append_rows(st, ts, x.values, y.values, x.validity, y.validity, x.offset, y.offset, x.length, fl(x, ox),
-                     fl(y, oy), err));
+    TGX_TRY(append_rows(st, ts, x.values, y.values, x.validity, y.validity, x.offset, y.offset, x.length, fl(x, ox),
+                        fl(y, oy), err));
   }
   return TGX_OK;
 }
@@ -284,12 +259,12 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
   if (lent) {
     m = (unsigned long long)ts.lent.length;  // (no NULLs: every row is a pair)
   } else if (ts.count.p) {
-    SHIP(hipMemcpyAsync(&m, ts.count.p, 8, hipMemcpyDeviceToHost, st->stream));
-    SHIP(hipStreamSynchronize(st->stream));
+    HIP_TRY(hipMemcpyAsync(&m, ts.count.p, 8, hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
   }
   r->non_null = (int64_t)m;
   if (m == 0) return TGX_OK;
-  if (m > 0xFFFFFFF0ull) return sfail(err, TGX_UNSUPPORTED, "SPEARMAN over more than 2^32 rows is not supported");
+  if (m > 0xFFFFFFF0ull) return fail(err, TGX_UNSUPPORTED, "SPEARMAN over more than 2^32 rows is not supported");
   SpearmanState *ws = sstate(st);
   // RANK(x) with y as the payload, then RANK(y) with RANK(x) as the payload, the five sums taken where the second
   // ranking ends: no rank is ever scattered back to its row and nothing is laid out in order (kernels/sortrank.hip).
@@ -297,11 +272,11 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
          &temp = ws->temp, &partials = ws->partials, &kc = ws->rx, &pc = ws->ry;
   const int blocks = sr_partials_count();
   const size_t sums_bytes = (size_t)blocks * spearman_rank_sums_bytes();
-  SHIP(partials.reserve(sums_bytes + 64));
+  HIP_TRY(partials.reserve(sums_bytes + 64));
   uint32_t *d_status = (uint32_t *)((char *)partials.p + sums_bytes);  // [0] the first ranking's, [1] the second's
   const size_t temp_bytes = sr_workspace_bytes(m);
-  SHIP(temp.reserve(temp_bytes));
-  SHIP(rank32.reserve(m * 4));
+  HIP_TRY(temp.reserve(temp_bytes));
+  HIP_TRY(rank32.reserve(m * 4));
   // Bucket sizes from the sample instead of a counting read per pass (kernels/sortrank.h): the passes' buckets then lie
   // apart, in arrays a third larger, none of them the state's own (a pass that finds a bucket full leaves nothing
   // valid behind: the pairs have to be intact for the second try, with counted buckets).  Taken when the device has
@@ -316,20 +291,20 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
       optimistic = false;
   }
   if (lent && !optimistic) {  // (no room for a ranking that leaves its input alone: pairs of the state's own first)
-    STRY(resolve_lent(st, ts, err));
+    TGX_TRY(resolve_lent(st, ts, err));
     lent = false;
   }
   std::vector<RankSumsHost> h(blocks);
   SrPlaced at;
   for (int attempt = 0; attempt < 2; attempt++) {
     const uint64_t elems = optimistic ? roomy : m;
-    SHIP(ka.reserve(elems * 8));
-    SHIP(pa.reserve(elems * 8));
-    SHIP(ra.reserve(elems * 4));
-    SHIP(rb.reserve(elems * 4));
+    HIP_TRY(ka.reserve(elems * 8));
+    HIP_TRY(pa.reserve(elems * 8));
+    HIP_TRY(ra.reserve(elems * 4));
+    HIP_TRY(rb.reserve(elems * 4));
     if (optimistic) {
-      SHIP(kc.reserve(elems * 8));
-      SHIP(pc.reserve(elems * 8));
+      HIP_TRY(kc.reserve(elems * 8));
+      HIP_TRY(pc.reserve(elems * 8));
     }
     SrJob jx;
     jx.keys = lent ? (const uint64_t *)ts.lent.x : ts.kx.as<uint64_t>();
@@ -351,7 +326,7 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
     jx.status = d_status;
     jx.sink = kSrRank32;
     jx.rank32 = rank32.as<uint32_t>();
-    SHIP(sr_run(jx, temp.p, temp_bytes, st->stream, &at));
+    HIP_TRY(sr_run(jx, temp.p, temp_bytes, st->stream, &at));
     SrJob jy;
     jy.keys = (const uint64_t *)at.pay;  // the y keys, slot for slot beside rank32
     jy.pay = rank32.p;
@@ -372,17 +347,17 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
     jy.status = d_status + 1;
     jy.sink = kSrSums;
     jy.partials = (RankSums *)partials.p;
-    SHIP(sr_run(jy, temp.p, temp_bytes, st->stream, nullptr));
+    HIP_TRY(sr_run(jy, temp.p, temp_bytes, st->stream, nullptr));
     uint32_t status[2] = {0, 0};
-    SHIP(hipMemcpyAsync(h.data(), partials.p, blocks * sizeof(RankSumsHost), hipMemcpyDeviceToHost, st->stream));
-    SHIP(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st->stream));
-    SHIP(hipStreamSynchronize(st->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), partials.p, blocks * sizeof(RankSumsHost), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
     if ((status[0] | status[1]) == 0) break;
-    if (!optimistic) return sfail(err, TGX_INTERNAL, "SPEARMAN: the ranking failed with counted buckets (status %u, %u)",
-                                  status[0], status[1]);
+    if (!optimistic) return fail(err, TGX_INTERNAL, "SPEARMAN: the ranking failed with counted buckets (status %u, %u)",
+                                 status[0], status[1]);
     optimistic = false;  // a bucket outgrew the room its share of the sample gave it: once more, counting
     if (lent) {
-      STRY(resolve_lent(st, ts, err));
+      TGX_TRY(resolve_lent(st, ts, err));
       lent = false;
     }
     if (getenv("TGX_SORT_DEBUG")) fprintf(stderr, "tgx sort: a bucket was full (status %u, %u): again with counted buckets\n", status[0], status[1]);
@@ -395,14 +370,14 @@ tgx_status spearman_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_erro
       if (b->p == (const void *)at.keys) bx = b;
       if (b->p == at.pay) by = b;
     }
-    if (!bx || !by || bx == by) return sfail(err, TGX_INTERNAL, "SPEARMAN: the ranking's output is not where it was expected");
+    if (!bx || !by || bx == by) return fail(err, TGX_INTERNAL, "SPEARMAN: the ranking's output is not where it was expected");
     ts.work_x = bx;
     ts.work_y = by;
     ts.work_pairs = m;
     ts.rows_upper = m;
     ts.lent = LentBatch();
     // (another task ranks in the same arrays next)
-    if (sstate(st)->tasks.size() > 1) STRY(resolve_lent(st, ts, err));
+    if (sstate(st)->tasks.size() > 1) TGX_TRY(resolve_lent(st, ts, err));
   }
   double out[5];
   for (int k = 0; k < 5; k++) {
@@ -429,9 +404,9 @@ tgx_status spearman_check_mergeable(tgx_state *st, tgx_error *err) {
   if (!st->spearman || sstate(st)->reducing) return TGX_OK;
   for (auto &t : sstate(st)->tasks)
     if (t.rows_upper > 0 || t.total_rows > 0 || t.resolved)
-      return sfail(err, TGX_UNSUPPORTED,
-                   "Spearman states hold ranks of one data set and cannot be merged or serialized "
-                   "(as in the reference, analyzers/advanced/correlation.rs:103-109)");
+      return fail(err, TGX_UNSUPPORTED,
+                  "Spearman states hold ranks of one data set and cannot be merged or serialized "
+                  "(as in the reference, analyzers/advanced/correlation.rs:103-109)");
   return TGX_OK;
 }
 
@@ -448,14 +423,14 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
   // (a) this rank's keys in order, with the permutation that leads back to the rows (the keys' positions travel as the
   //     payload; the state's own arrays are only read: x and y must stay side by side)
   if (m) {
-    SHIP(ws->loc_sorted.reserve(m * 8));
-    SHIP(ws->loc_perm.reserve(m * 4));
-    SHIP(ws->keys_sorted.reserve(m * 8));
-    SHIP(ws->heads.reserve(m * 8));
-    SHIP(ws->idx.reserve(m * 4));
-    SHIP(ws->idx_sorted.reserve(m * 4));
+    HIP_TRY(ws->loc_sorted.reserve(m * 8));
+    HIP_TRY(ws->loc_perm.reserve(m * 4));
+    HIP_TRY(ws->keys_sorted.reserve(m * 8));
+    HIP_TRY(ws->heads.reserve(m * 8));
+    HIP_TRY(ws->idx.reserve(m * 4));
+    HIP_TRY(ws->idx_sorted.reserve(m * 4));
     tb = sr_workspace_bytes(m);
-    SHIP(ws->temp.reserve(tb));
+    HIP_TRY(ws->temp.reserve(tb));
     SrJob j;
     j.keys = keys;
     j.n = m;
@@ -467,23 +442,23 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
     j.sink = kSrSorted;
     j.out_keys = ws->loc_sorted.as<uint64_t>();
     j.out_pay = ws->loc_perm.p;
-    SHIP(sr_run(j, ws->temp.p, tb, s, nullptr));
+    HIP_TRY(sr_run(j, ws->temp.p, tb, s, nullptr));
   }
   // (b) regular samples of every rank -> the same world-1 splitters everywhere
   std::vector<uint64_t> mine(1 + kSamplesPerRank, 0), all((size_t)W * (1 + kSamplesPerRank), 0);
   const uint32_t ns = (uint32_t)std::min<uint64_t>(m, kSamplesPerRank);
   mine[0] = ns;
   if (ns) {
-    SHIP(ws->small.reserve((2 * kSamplesPerRank + 512) * 8));
+    HIP_TRY(ws->small.reserve((2 * kSamplesPerRank + 512) * 8));
     launch_sample_sorted(ws->loc_sorted.as<uint64_t>(), m, ns, ws->small.as<uint64_t>(), s);
-    SHIP(hipMemcpyAsync(&mine[1], ws->small.p, ns * 8, hipMemcpyDeviceToHost, s));
-    SHIP(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(&mine[1], ws->small.p, ns * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
-  STRY(X.allgather_host(mine.data(), all.data(), mine.size() * 8));
+  TGX_TRY(X.allgather_host(mine.data(), all.data(), mine.size() * 8));
   std::vector<uint64_t> pool;
   for (int32_t r = 0; r < W; r++) {
     const uint64_t *p = &all[(size_t)r * (1 + kSamplesPerRank)];
-    if (p[0] > kSamplesPerRank) return sfail(err, TGX_INTERNAL, "SPEARMAN exchange: bad sample header from rank %d", r);
+    if (p[0] > kSamplesPerRank) return fail(err, TGX_INTERNAL, "SPEARMAN exchange: bad sample header from rank %d", r);
     pool.insert(pool.end(), p + 1, p + 1 + p[0]);
   }
   std::sort(pool.begin(), pool.end());
@@ -493,12 +468,12 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
   std::vector<uint64_t> sc((size_t)W, 0);
   if (m && W > 1) {
     uint64_t *d_split = ws->small.as<uint64_t>() + kSamplesPerRank, *d_bound = d_split + 256;
-    if (W - 1 > 256) return sfail(err, TGX_UNSUPPORTED, "SPEARMAN across more than 257 ranks");
+    if (W - 1 > 256) return fail(err, TGX_UNSUPPORTED, "SPEARMAN across more than 257 ranks");
     std::vector<uint64_t> bound((size_t)W - 1);
-    SHIP(hipMemcpyAsync(d_split, split.data(), split.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_split, split.data(), split.size() * 8, hipMemcpyHostToDevice, s));
     launch_lower_bounds(ws->loc_sorted.as<uint64_t>(), m, d_split, (uint32_t)(W - 1), d_bound, s);
-    SHIP(hipMemcpyAsync(bound.data(), d_bound, bound.size() * 8, hipMemcpyDeviceToHost, s));
-    SHIP(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(bound.data(), d_bound, bound.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     uint64_t prev = 0;
     for (int32_t j = 0; j + 1 < W; j++) {
       sc[j] = bound[j] - prev;
@@ -509,7 +484,7 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
     sc[0] = m;
   }
   std::vector<uint64_t> mat((size_t)W * W, 0), rc((size_t)W, 0);
-  STRY(X.allgather_host(sc.data(), mat.data(), (size_t)W * 8));  // mat[p * W + q]: p sends q
+  TGX_TRY(X.allgather_host(sc.data(), mat.data(), (size_t)W * 8));  // mat[p * W + q]: p sends q
   uint64_t M = 0, base = 0, everywhere = 0;
   for (int32_t p = 0; p < W; p++) {
     rc[p] = mat[(size_t)p * W + R];
@@ -519,26 +494,26 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
   }
   if (everywhere == 0) return TGX_OK;  // no rank holds a pair (every rank sees that): nothing to exchange
   if (M > 0xFFFFFFF0ull)
-    return sfail(err, TGX_UNSUPPORTED, "SPEARMAN: more than 2^32 keys fall to one rank (heavily repeated values)");
+    return fail(err, TGX_UNSUPPORTED, "SPEARMAN: more than 2^32 keys fall to one rank (heavily repeated values)");
   if (M || m) {  // (a rank that saw no batch may still own a value range)
-    STRY(need_device(err));
-    STRY(state_init_device(st, err));
+    TGX_TRY(need_device(err));
+    TGX_TRY(state_init_device(st, err));
     s = st->stream;
   }
   // (d) the keys to their owners, ranked there, the ranks back
-  SHIP(ws->recv.reserve(std::max<uint64_t>(M, 1) * 8));
-  SHIP(ws->loc_sorted.reserve(8));  // (a rank without keys still names a buffer)
-  STRY(X.alltoallv(ws->loc_sorted.p, sc.data(), ws->recv.p, rc.data(), 8));
-  SHIP(ws->recv_ranks.reserve(std::max<uint64_t>(M, 1) * 8));
+  HIP_TRY(ws->recv.reserve(std::max<uint64_t>(M, 1) * 8));
+  HIP_TRY(ws->loc_sorted.reserve(8));  // (a rank without keys still names a buffer)
+  TGX_TRY(X.alltoallv(ws->loc_sorted.p, sc.data(), ws->recv.p, rc.data(), 8));
+  HIP_TRY(ws->recv_ranks.reserve(std::max<uint64_t>(M, 1) * 8));
   if (M) {
     // RANK() of a received key = the keys lower ranks own + its rank among the keys owned here, written to the slot
     // the key arrived in
-    SHIP(ws->keys_sorted.reserve(M * 8));
-    SHIP(ws->heads.reserve(M * 8));
-    SHIP(ws->idx.reserve(M * 4));
-    SHIP(ws->idx_sorted.reserve(M * 4));
+    HIP_TRY(ws->keys_sorted.reserve(M * 8));
+    HIP_TRY(ws->heads.reserve(M * 8));
+    HIP_TRY(ws->idx.reserve(M * 4));
+    HIP_TRY(ws->idx_sorted.reserve(M * 4));
     tb = sr_workspace_bytes(M);
-    SHIP(ws->temp.reserve(tb));
+    HIP_TRY(ws->temp.reserve(tb));
     SrJob j;
     j.keys = ws->recv.as<uint64_t>();
     j.n = M;
@@ -550,10 +525,10 @@ tgx_status rank_across(tgx_state *st, SpearmanState *ws, const SpearmanExchange 
     j.sink = kSrRankScatter;
     j.rank_out = ws->recv_ranks.as<uint64_t>();
     j.ext_base = base;
-    SHIP(sr_run(j, ws->temp.p, tb, s, nullptr));
+    HIP_TRY(sr_run(j, ws->temp.p, tb, s, nullptr));
   }
-  SHIP(ws->back.reserve(std::max<uint64_t>(m, 1) * 8));
-  STRY(X.alltoallv(ws->recv_ranks.p, rc.data(), ws->back.p, sc.data(), 8));
+  HIP_TRY(ws->back.reserve(std::max<uint64_t>(m, 1) * 8));
+  TGX_TRY(X.alltoallv(ws->recv_ranks.p, rc.data(), ws->back.p, sc.data(), 8));
   if (m) launch_unsort(ws->back.as<uint64_t>(), ws->loc_perm.as<uint32_t>(), m, out, s);
   return TGX_OK;
 }
@@ -563,7 +538,7 @@ tgx_status spearman_allreduce(tgx_state *st, const SpearmanExchange &X, std::vec
                               tgx_error *err) {
   out->clear();
   if (!st->plan->spearman) return TGX_OK;
-  STRY(spearman_resolve_all(st, err));  // (the exchange reads the state's own pairs)
+  TGX_TRY(spearman_resolve_all(st, err));  // (the exchange reads the state's own pairs)
   const SpearmanPlan *sp = splan(st->plan);
   SpearmanState *ws = sstate(st);
   hipStream_t s = st->device_ready ? st->stream : nullptr;
@@ -575,29 +550,29 @@ tgx_status spearman_allreduce(tgx_state *st, const SpearmanExchange &X, std::vec
   for (size_t t = 0; t < sp->tasks.size(); t++) {
     SpearmanTaskState &ts = ws->tasks[t];
     if (ts.resolved)
-      return sfail(err, TGX_UNSUPPORTED, "SPEARMAN: the state already holds the result of a cross-rank reduction");
+      return fail(err, TGX_UNSUPPORTED, "SPEARMAN: the state already holds the result of a cross-rank reduction");
     unsigned long long m = 0;
     if (ts.count.p) {
-      SHIP(hipMemcpyAsync(&m, ts.count.p, 8, hipMemcpyDeviceToHost, s));
-      SHIP(hipStreamSynchronize(s));
+      HIP_TRY(hipMemcpyAsync(&m, ts.count.p, 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
     }
-    if (m > 0xFFFFFFF0ull) return sfail(err, TGX_UNSUPPORTED, "SPEARMAN over more than 2^32 rows per rank is not supported");
+    if (m > 0xFFFFFFF0ull) return fail(err, TGX_UNSUPPORTED, "SPEARMAN over more than 2^32 rows per rank is not supported");
     if (m) {
-      SHIP(ws->rx.reserve(m * 8));
-      SHIP(ws->ry.reserve(m * 8));
+      HIP_TRY(ws->rx.reserve(m * 8));
+      HIP_TRY(ws->ry.reserve(m * 8));
     }
-    STRY(rank_across(st, ws, X, ts.kx.as<uint64_t>(), m, ws->rx.as<uint64_t>(), err));
-    STRY(rank_across(st, ws, X, ts.ky.as<uint64_t>(), m, ws->ry.as<uint64_t>(), err));
+    TGX_TRY(rank_across(st, ws, X, ts.kx.as<uint64_t>(), m, ws->rx.as<uint64_t>(), err));
+    TGX_TRY(rank_across(st, ws, X, ts.ky.as<uint64_t>(), m, ws->ry.as<uint64_t>(), err));
     Wire mine;
     memset(&mine, 0, sizeof(mine));
     mine.total_rows = ts.total_rows;
     mine.pairs = m;
     if (m) {
-      SHIP(ws->partials.reserve(2048 * spearman_rank_sums_bytes()));
+      HIP_TRY(ws->partials.reserve(2048 * spearman_rank_sums_bytes()));
       const int blocks = launch_rank_sums(ws->rx.as<uint64_t>(), ws->ry.as<uint64_t>(), m, 0, ws->partials.p, s);
       std::vector<RankSumsHost> h(blocks);
-      SHIP(hipMemcpyAsync(h.data(), ws->partials.p, blocks * sizeof(RankSumsHost), hipMemcpyDeviceToHost, s));
-      SHIP(hipStreamSynchronize(s));
+      HIP_TRY(hipMemcpyAsync(h.data(), ws->partials.p, blocks * sizeof(RankSumsHost), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
       for (int k = 0; k < 5; k++) {
         unsigned __int128 e = 0;
         for (auto &p : h) {
@@ -609,7 +584,7 @@ tgx_status spearman_allreduce(tgx_state *st, const SpearmanExchange &X, std::vec
       }
     }
     std::vector<Wire> all((size_t)X.world);
-    STRY(X.allgather_host(&mine, all.data(), sizeof(Wire)));
+    TGX_TRY(X.allgather_host(&mine, all.data(), sizeof(Wire)));
     SpearmanResolved res;
     memset(&res, 0, sizeof(res));
     for (auto &w : all) {

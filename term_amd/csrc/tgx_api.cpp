@@ -289,8 +289,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       }
       case TGX_CHECK_LENGTH: {
         int slot = -1;
-        tgx_status st = regex_plan_add(plan.get(), (int)i, &slot, err);
-        if (st != TGX_OK) return st;
+        TGX_TRY(regex_plan_add(plan.get(), (int)i, &slot, err));
         plan->bind[i].slot = slot;
         break;
       }
@@ -298,8 +297,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         if (!sp.pattern && sp.pattern_len) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: pattern is NULL", i);
         plan->patterns[i].assign(sp.pattern ? sp.pattern : "", sp.pattern_len);
         int slot = -1;
-        tgx_status st = regex_plan_add(plan.get(), (int)i, &slot, err);
-        if (st != TGX_OK) return st;
+        TGX_TRY(regex_plan_add(plan.get(), (int)i, &slot, err));
         plan->bind[i].slot = slot;
         break;
       }
@@ -313,8 +311,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       case TGX_CHECK_SPEARMAN: {
         max_col = std::max(max_col, sp.column2);
         int slot = -1;
-        tgx_status st = spearman_plan_add(plan.get(), (int)i, &slot, err);
-        if (st != TGX_OK) return st;
+        TGX_TRY(spearman_plan_add(plan.get(), (int)i, &slot, err));
         plan->bind[i].slot = slot;
         break;
       }

@@ -1,41 +1,8 @@
-// wire.cpp -- tgx_state_serialize / tgx_state_deserialize (blobs v3; term_amd/wire.py documents the layout).
-// Split off tgx_api.cpp in round 4.
+// wire.cpp -- tgx_state_serialize / tgx_state_deserialize (blobs v3; term_amd/wire.py documents the layout).  The
+// sections of the check modules (KLL, pattern checks, JOINT_BINS) are written and read by the modules themselves, through
+// the Writer / Reader of wire_io.h.  Split off tgx_api.cpp in round 4.
 #include "api_internal.h"
-
-// ------------------------------------------------------------------------------------------------
-// wire form
-namespace {
-struct Writer {
-  uint8_t *buf;
-  size_t cap, len = 0;
-  void put(const void *p, size_t n) {
-    if (buf && len + n <= cap) memcpy(buf + len, p, n);
-    len += n;
-  }
-  template <class T>
-  void pod(const T &v) { put(&v, sizeof(T)); }
-};
-struct Reader {
-  const uint8_t *buf;
-  size_t len, pos = 0;
-  bool ok = true;
-  void get(void *p, size_t n) {
-    if (pos + n > len) {
-      ok = false;
-      memset(p, 0, n);
-      return;
-    }
-    memcpy(p, buf + pos, n);
-    pos += n;
-  }
-  template <class T>
-  T pod() {
-    T v;
-    get(&v, sizeof(T));
-    return v;
-  }
-};
-}  // namespace
+#include "wire_io.h"
 
 extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, uint8_t *buf, size_t cap,
                                           size_t *len, tgx_error *err) try {
@@ -88,15 +55,15 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
       w.pod(n_records);
     }
   }
-  TGX_TRY(kll_serialize(st, &w.len, w.buf, w.cap, err));
-  TGX_TRY(regex_serialize(st, &w.len, w.buf, w.cap, err));
+  TGX_TRY(kll_serialize(st, w, err));
+  TGX_TRY(regex_serialize(st, w, err));
   for (size_t k = 0; k < plan->hll.size(); k++) {  // { u32 mode, u32 has_registers; registers }
     w.pod((uint32_t)st->hll_mode[k]);
     w.pod((uint32_t)(g.hll[k].empty() ? 0 : 1));
     if (!g.hll[k].empty()) w.put(g.hll[k].data(), kHllRegisters);
   }
   // (behind everything else, and only for plans with such checks: blobs of every other plan keep their bytes)
-  TGX_TRY(joint_serialize(st, &w.len, w.buf, w.cap, err));
+  TGX_TRY(joint_serialize(st, w, err));
   *len = w.len;
   if (buf && w.len > cap) return fail(err, TGX_INVALID_ARGUMENT, "buffer too small: need %zu bytes", w.len);
   return TGX_OK;
@@ -160,34 +127,24 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
       ds.partitioned = true;
       distinct_fold_totals(ds, t);  // (into a fresh state: adding is assigning)
     } else {
-      // rebuild the key set on the device from the records.  n_records comes from the blob: bound it by the bytes
-      // that are really there BEFORE multiplying (a crafted count would wrap the product past the check)
-      const size_t rec_bytes = wide ? sizeof(KeyRecord128) : sizeof(KeyRecord);
-      if (n_records > (r.len - r.pos) / rec_bytes) {
-        r.ok = false;
-        break;
-      }
-      size_t bytes = (size_t)n_records * rec_bytes;
-      tgx_status s = need_device(err);
-      if (s != TGX_OK) return s;
-      s = state_init_device(st.get(), err);
-      if (s != TGX_OK) return s;
+      // rebuild the key set on the device from the records
+      size_t bytes = 0;
+      if (!r.fits(n_records, wide ? sizeof(KeyRecord128) : sizeof(KeyRecord), &bytes)) break;
+      TGX_TRY(need_device(err));
+      TGX_TRY(state_init_device(st.get(), err));
       DevBuf tmp;
       HIP_TRY(tmp.reserve(std::max<size_t>(bytes, 16)));
       HIP_TRY(hipMemcpy(tmp.p, r.buf + r.pos, bytes, hipMemcpyHostToDevice));
       r.pos += bytes;
-      s = distinct_import_records(st.get(), k, tmp.p, n_records, wide, err);
-      if (s != TGX_OK) return s;
+      TGX_TRY(distinct_import_records(st.get(), k, tmp.p, n_records, wide, err));
       HIP_TRY(hipStreamSynchronize(st->stream));
       ds.h_total = t.total;
       ds.h_non_null = t.non_null;
     }
   }
   if (r.ok) {
-    tgx_status s = kll_deserialize(st.get(), r.buf, r.len, &r.pos, err);
-    if (s != TGX_OK) return s;
-    s = regex_deserialize(st.get(), r.buf, r.len, &r.pos, err);
-    if (s != TGX_OK) return s;
+    TGX_TRY(kll_deserialize(st.get(), r, err));
+    TGX_TRY(regex_deserialize(st.get(), r, err));
     for (size_t k = 0; k < plan->hll.size() && r.ok; k++) {
       const uint32_t mode = r.pod<uint32_t>(), has = r.pod<uint32_t>();
       if (mode > 2 || has > 1) return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (APPROX_DISTINCT task)");
@@ -197,10 +154,7 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
         r.get(st->h_hll[k].data(), kHllRegisters);
       }
     }
-    if (r.ok) {
-      s = joint_deserialize(st.get(), r.buf, r.len, &r.pos, err);
-      if (s != TGX_OK) return s;
-    }
+    if (r.ok) TGX_TRY(joint_deserialize(st.get(), r, err));
   }
   if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
   *out = st.release();

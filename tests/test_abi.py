@@ -146,3 +146,35 @@ def test_fingerprint_key_of_a_plan(monkeypatch):
     assert st.finalize()[0].total == 10
     with pytest.raises(T.TgxError):
         T.blob_fingerprint_key(b"garbage")
+
+
+def test_getters_name_what_is_wrong_with_plan_state_and_spec():
+    """the getters of a check kind look at (plan, state, spec_index) before anything else -- no device is needed to be
+    told that the state is another plan's, or that the spec is of another kind or does not exist"""
+    lib = T.lib()
+    sp = [spec(T.KLL, 0, kll_k=8), spec(T.JOINT_BINS, 0, column2=1), spec(T.DISTINCT, 0)]
+    plan, other = T.Plan(sp), T.Plan(sp)
+    st, foreign = T.State(plan), T.State(other)
+    d, u, p, i64 = C.c_double(), C.c_uint64(), C.c_void_p(), C.c_int64()
+    rng = T._lib.JointRange()
+    getters = {
+        "KLL": (0, "state does not belong to plan", [
+            lambda s, i, e: lib.tgx_kll_quantile(plan.h, s, i, 0.5, C.byref(d), e),
+            lambda s, i, e: lib.tgx_kll_summary(plan.h, s, i, C.byref(u), None, None, None, None, e),
+            lambda s, i, e: lib.tgx_kll_level_items(plan.h, s, i, 0, None, 0, C.byref(u), e)]),
+        "JOINT_BINS": (1, "bad arguments", [
+            lambda s, i, e: lib.tgx_joint_range_get(plan.h, s, i, C.byref(rng), e),
+            lambda s, i, e: lib.tgx_joint_counts(plan.h, s, i, None, 0, C.byref(u), None, e)]),
+        "DISTINCT": (2, "state does not belong to plan", [
+            lambda s, i, e: lib.tgx_distinct_export(plan.h, s, i, 1, C.byref(p), C.byref(u), e),
+            lambda s, i, e: lib.tgx_distinct_range_hint(plan.h, s, i, 0, 9, e),
+            lambda s, i, e: lib.tgx_distinct_bitmap_view(plan.h, s, i, C.byref(i64), C.byref(u), C.byref(p), None, e)]),
+    }
+    for kind, (own, foreign_text, calls) in getters.items():
+        for call in calls:
+            for state, index, want in ((st, (own + 1) % 3, "spec %d is not a %s check" % ((own + 1) % 3, kind)),
+                                       (foreign, own, foreign_text),
+                                       (st, 3, "spec 3 is not a %s check" % kind)):
+                err = _Error()
+                assert call(state.h, index, C.byref(err)) == 1, (kind, want)  # TGX_INVALID_ARGUMENT
+                assert (err.code, err.msg.decode()) == (1, want)

@@ -327,3 +327,18 @@ def test_pair_scan_min_max_are_exact_in_total_order(case):
                 assert abs(r.sum_f - o.sum_hi) <= 1e-9 * max(1.0, abs(o.sum_hi))
         else:
             assert (r.min_i, r.max_i, r.sum_i) == (o.min_i, o.max_i, o.sum_i_wrapping)
+
+
+def test_profile_entry_of_one_update():
+    """with profiling on, a batch sketched by its own launch is one "kll" entry that prices the column's values and
+    its validity bits"""
+    n = 5001
+    rng = np.random.default_rng(7)
+    vals = rng.standard_normal(n)
+    validity = orc.pack_validity(rng.random(n) >= 0.1)
+    T.init()
+    st = T.State(T.Plan([spec(T.KLL, 0, kll_k=64)]))
+    st.profile_enable(True)
+    st.update([numeric_column(vals, validity, True)])
+    got = st.profile_get("kll")
+    assert got["launches"] >= 1 and got["bytes"] == n * 8 + (n + 7) // 8

@@ -301,3 +301,15 @@ def test_counted_unicode_classes_on_gpu(layout):
     for (p, f), r in zip(checks, res):
         want = orc.Regex(p).count_utf8(offs, data, validity, trim=bool(f & T.FLAG_TRIM), null_is_valid=bool(f & T.FLAG_NULL_IS_VALID))
         assert (r.total, r.matches) == (want.total, want.matches), (p, f)
+
+
+def test_profile_entry_of_one_update():
+    """with profiling on, every launch of a pattern check is a "regex" entry; it prices no bytes (how many value bytes a
+    walk reads depends on the data)"""
+    offs, data, validity = orc.utf8_from_list(synth_strings(np.random.default_rng(3), 2000, "email"))
+    T.init()
+    st = T.State(T.Plan([spec(T.REGEX_MATCH, 0, pattern="@"), spec(T.LENGTH, 0, length_max=20)]))
+    st.profile_enable(True)
+    st.update([utf8_column(offs, data, validity, True)])
+    got = st.profile_get("regex")
+    assert got["launches"] >= 1 and got["bytes"] == 0
