@@ -199,7 +199,17 @@ typedef enum tgx_check_kind {
    * Columns: Int64, Float64, and Int32 / Float32 / Int8 .. UInt32 through the widening staging; UInt64, Boolean and every
    * string layout are TGX_UNSUPPORTED.  The state is additive: tgx_merge, state blobs and tgx_allreduce combine the
    * extremes by MIN / MAX and n and the cells by addition. */
-  TGX_CHECK_JOINT_BINS = 10
+  TGX_CHECK_JOINT_BINS = 10,
+  /* The row predicates behind TemporalOrderingConstraint's three pure-scan modes
+   *                                            TG/constraints/temporal_ordering.rs:346-453
+   * each a SELECT COUNT(*), SUM(CASE WHEN <predicate> THEN 0 ELSE 1 END) FROM t WHERE ... over one or two Int64-shaped
+   * columns (Timestamp / Date64 / Int64), everything in the column's own ticks.  `column` is the timestamp column, or the
+   * BEFORE column in order mode; `column2` is the AFTER column in order mode and -1 otherwise.  The mode and its
+   * parameters come with tgx_plan_set_temporal (below); a spec without them makes tgx_state_create fail.  Read with
+   * tgx_temporal_get; tgx_result carries total = rows seen, non_null = rows considered, matches = considered -
+   * violations.  Every other column type is TGX_UNSUPPORTED from tgx_update.  The state is three counters: tgx_merge,
+   * state blobs and tgx_allreduce add them. */
+  TGX_CHECK_TEMPORAL = 11
 } tgx_check_kind;
 
 enum {
@@ -229,7 +239,7 @@ enum {
 typedef struct tgx_check_spec {
   int32_t kind;         /* tgx_check_kind */
   int32_t column;       /* index into the columns array handed to tgx_update */
-  int32_t column2;      /* COMOMENTS / SPEARMAN / JOINT_BINS: second column; otherwise -1 */
+  int32_t column2;      /* COMOMENTS / SPEARMAN / JOINT_BINS / TEMPORAL (order mode): second column; otherwise -1 */
   uint32_t flags;
   const char *pattern;  /* REGEX: pattern bytes (Rust `regex` syntax), not NUL-terminated */
   uint64_t pattern_len;
@@ -357,6 +367,35 @@ typedef struct tgx_joint_binning {
 tgx_status tgx_plan_set_joint_binning(tgx_plan *plan, size_t spec_index, const tgx_joint_binning *binning,
                                       tgx_error *err);
 
+/* TGX_CHECK_TEMPORAL: the mode and parameters of spec `spec_index`.  Like the fingerprint key they can be set until the
+ * plan's first state exists; afterwards, and for a spec of another kind, the call is refused with
+ * TGX_INVALID_ARGUMENT.
+ *   TGX_TEMPORAL_ORDER        the row passes iff after - before >= delta, the difference taken without wrap-around
+ *                             (INT64_MAX - INT64_MIN is a large positive number, not -1).  The reference's four comparisons
+ *                             (temporal_ordering.rs:352-368) are delta = tolerance for >= and tolerance + 1 for >.
+ *   TGX_TEMPORAL_TIME_OF_DAY  the row passes iff tod_lo <= floormod(t, 86400 * ticks_per_second) <= tod_hi (floor forms:
+ *                             timestamps before 1970 are negative).  ticks_per_second is 1, 10^3, 10^6 or 10^9.
+ *   TGX_TEMPORAL_RANGE        the row passes iff lo <= t <= hi; INT64_MIN / INT64_MAX mean "no bound".
+ * Flags:
+ *   TGX_TEMPORAL_KEEP_NULLS     the reference's allow_nulls(true): the IS NOT NULL terms leave the WHERE clause.  A NULL row
+ *                               (either side, in order mode) is then CONSIDERED, its predicate is SQL NULL, it lands in the
+ *                               ELSE 1 branch: a violation.  Without the flag a NULL row is seen and not considered.
+ *   TGX_TEMPORAL_WEEKDAYS_ONLY  time-of-day mode only: the WHERE term EXTRACT(DOW FROM t) BETWEEN 1 AND 5, with
+ *                               dow = floormod(floordiv(t, ticks per day) + 4, 7) (1970-01-01 is a Thursday, DOW 0 is
+ *                               Sunday).  It takes rows out of `considered`; it does not make them violations.  A NULL
+ *                               row never passes this filter, with or without KEEP_NULLS. */
+enum { TGX_TEMPORAL_ORDER = 1, TGX_TEMPORAL_TIME_OF_DAY = 2, TGX_TEMPORAL_RANGE = 3 };
+enum { TGX_TEMPORAL_KEEP_NULLS = 1u << 0, TGX_TEMPORAL_WEEKDAYS_ONLY = 1u << 1 };
+typedef struct tgx_temporal_params {
+  int32_t mode;             /* TGX_TEMPORAL_ORDER / _TIME_OF_DAY / _RANGE */
+  uint32_t flags;           /* TGX_TEMPORAL_KEEP_NULLS | TGX_TEMPORAL_WEEKDAYS_ONLY */
+  int64_t delta;            /* ORDER */
+  int64_t ticks_per_second; /* TIME_OF_DAY */
+  int64_t tod_lo, tod_hi;   /* TIME_OF_DAY: ticks into the day, both ends inclusive */
+  int64_t lo, hi;           /* RANGE: both ends inclusive */
+} tgx_temporal_params;
+tgx_status tgx_plan_set_temporal(tgx_plan *plan, size_t spec_index, const tgx_temporal_params *params, tgx_error *err);
+
 /* State = `Analyzer::State` for every spec of the plan (TG/analyzers/traits.rs:154-179).
  * `hip_stream` is a hipStream_t (NULL = a stream the library creates).  Everything the state does on the device is
  * queued on that stream and nowhere else: a DEVICE buffer handed to tgx_update has to be COMPLETE as far as that
@@ -466,6 +505,15 @@ tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *state, size_t sp
 tgx_status tgx_joint_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, uint64_t *cells, uint64_t cap,
                             uint64_t *n_cells, uint64_t *out_of_range, tgx_error *err);
 
+/* ---- temporal row predicates (TGX_CHECK_TEMPORAL; TG/constraints/temporal_ordering.rs:346-453) -------------------- */
+typedef struct tgx_temporal_counts {
+  uint64_t seen;        /* rows handed to tgx_update */
+  uint64_t considered;  /* the SQL's COUNT(*): rows the WHERE clause lets through */
+  uint64_t violations;  /* the SQL's SUM(CASE WHEN <predicate> THEN 0 ELSE 1 END); 0 when nothing was considered */
+} tgx_temporal_counts;
+tgx_status tgx_temporal_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_temporal_counts *out,
+                            tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -555,7 +603,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins"; "distinct_lists" is the share of
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);
 tgx_status tgx_profile_get(tgx_state *state, const char *kernel, double *total_ms,

@@ -53,6 +53,16 @@ tgx_status tgx_host_run_suite_json(const char *suite_json, const char *const *co
 /* The aggregates one constraint asks for (its half of the fused plan), as a JSON array. */
 tgx_status tgx_host_constraint_plan_json(const char *constraint_json, char **out_json, tgx_error *err);
 
+/* A "temporal_ordering" constraint ({"type": "temporal_ordering", "table": t, "validation": "before_after |
+ * business_hours | date_range | max_time_gap | event_sequence", the builder calls' arguments by name, "allow_nulls",
+ * "tolerance_seconds"}) + the Arrow DataType names of its columns ({"created_at": "Timestamp(Nanosecond, None)", ..})
+ * -> the tgx_temporal_params the suite runner hands to tgx_plan_set_temporal, in the column's ticks:
+ * {"column", "column2", "mode", "flags", "delta", "ticks_per_second", "tod_lo", "tod_hi", "lo", "hi"}.  What the GPU path
+ * does not take (a unit it cannot know, a time zone other than UTC, MaxTimeGap, EventSequence, an unreadable literal) is
+ * TGX_INVALID_ARGUMENT with the constraint's error text: hand such a constraint to the stock path.  Needs no device. */
+tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char *arrow_types_json, char **out_json,
+                                         tgx_error *err);
+
 /* `Constraint::evaluate`'s verdict half on given aggregates: results_json is an array of objects with
  * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}).
  * Returns {"status": "success|failure|skipped", "metric": x|null, "message": s|null}.  Needs no device.

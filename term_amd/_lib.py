@@ -11,6 +11,9 @@ COUNT, NUMERIC_STATS, DISTINCT, REGEX_MATCH, KLL, COMOMENTS, SPEARMAN, LENGTH = 
 APPROX_DISTINCT = 9
 JOINT_BINS = 10  # joint bin counts of a numeric pair, in two phases (Plan.set_joint_binning)
 JOINT_MAX_BINS = 127
+TEMPORAL = 11  # row predicates over timestamp columns (Plan.set_temporal)
+TEMPORAL_ORDER, TEMPORAL_TIME_OF_DAY, TEMPORAL_RANGE = 1, 2, 3
+TEMPORAL_KEEP_NULLS, TEMPORAL_WEEKDAYS_ONLY = 1, 2
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -78,6 +81,17 @@ class JointRange(C.Structure):
     """tgx_joint_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("n", C.c_uint64), ("non_finite", C.c_uint64), ("x_min", C.c_double),
                 ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double)]
+
+
+class TemporalParams(C.Structure):
+    """tgx_temporal_params (include/tgx.h)"""
+    _fields_ = [("mode", C.c_int32), ("flags", C.c_uint32), ("delta", C.c_int64), ("ticks_per_second", C.c_int64),
+                ("tod_lo", C.c_int64), ("tod_hi", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+class TemporalCounts(C.Structure):
+    """tgx_temporal_counts (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("violations", C.c_uint64)]
 
 
 class _Options(C.Structure):
@@ -190,6 +204,8 @@ def lib():
         L.tgx_plan_set_joint_binning.argtypes = [vp, sz, C.POINTER(JointBinning), E]
         L.tgx_joint_range_get.argtypes = [vp, vp, sz, C.POINTER(JointRange), E]
         L.tgx_joint_counts.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), C.POINTER(u64), E]
+        L.tgx_plan_set_temporal.argtypes = [vp, sz, C.POINTER(TemporalParams), E]
+        L.tgx_temporal_get.argtypes = [vp, vp, sz, C.POINTER(TemporalCounts), E]
         _LIB = L
     return _LIB
 
@@ -582,6 +598,13 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_joint_binning(self.h, spec_index, C.byref(b), C.byref(err)), err)
 
+    def set_temporal(self, spec_index, mode, flags=0, delta=0, ticks_per_second=0, tod_lo=0, tod_hi=0,
+                     lo=-(1 << 63), hi=(1 << 63) - 1):
+        """tgx_plan_set_temporal: the mode and parameters of a TEMPORAL spec (before the plan's first state)"""
+        p = TemporalParams(mode, flags, delta, ticks_per_second, tod_lo, tod_hi, lo, hi)
+        err = _Error()
+        _check(lib().tgx_plan_set_temporal(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
         lib().tgx_plan_get_fingerprint_key(self.h, out)
@@ -733,6 +756,14 @@ class State:
         _check(lib().tgx_joint_counts(self.plan.h, self.h, spec_index, cells, n.value, C.byref(n), C.byref(outside),
                                       C.byref(err)), err)
         return list(cells)[: n.value], outside.value
+
+    # temporal row predicates
+    def temporal_counts(self, spec_index):
+        """tgx_temporal_get: (seen, considered, violations)"""
+        out = TemporalCounts()
+        err = _Error()
+        _check(lib().tgx_temporal_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return out.seen, out.considered, out.violations
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -7,6 +7,7 @@
 #include "../../../include/tgx_host.h"
 #include "json.h"
 #include "analyzers.h"
+#include "temporal.h"
 #include "term_guard.h"
 
 using namespace term_guard;
@@ -84,7 +85,18 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
       if (i) o += ", ";
       o += "{\"kind\": " + std::to_string(r.kind) + ", \"column\": " + json::quote(r.column) + ", \"column2\": " +
            json::quote(r.column2) + ", \"flags\": " + std::to_string(r.flags) + ", \"pattern\": " + json::quote(r.pattern) +
-           ", \"kll_k\": " + std::to_string(r.kll_k) + "}";
+           ", \"kll_k\": " + std::to_string(r.kll_k);
+      if (r.temporal) {
+        const TemporalRequest &t = *r.temporal;
+        auto text = [](const std::optional<std::string> &s) { return s ? json::quote(*s) : std::string("null"); };
+        o += std::string(", \"temporal\": {\"mode\": ") + std::to_string(t.mode) + ", \"allow_equal\": " +
+             (t.allow_equal ? "true" : "false") + ", \"allow_nulls\": " + (t.allow_nulls ? "true" : "false") +
+             ", \"weekdays_only\": " + (t.weekdays_only ? "true" : "false") + ", \"tolerance_seconds\": " +
+             std::to_string(t.tolerance_seconds) + ", \"start_time\": " + json::quote(t.start_time) +
+             ", \"end_time\": " + json::quote(t.end_time) + ", \"min_date\": " + text(t.min_date) +
+             ", \"max_date\": " + text(t.max_date) + "}";
+      }
+      o += "}";
     }
     o += "]}";
     *out_json = dup_string(o);
@@ -198,6 +210,38 @@ extern "C" tgx_status tgx_host_constraint_verdict_json(const char *constraint_js
     o += ", \"message\": " + (cr.message ? json::quote(*cr.message) : std::string("null")) + ", \"name\": " +
          json::quote(c->name()) + "}";
     *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char *arrow_types_json,
+                                                    char **out_json, tgx_error *err) {
+  if (!constraint_json || !arrow_types_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto c = constraint_from_json_text(constraint_json);
+    json::Value types;
+    std::string perr;
+    if (!json::parse(arrow_types_json, &types, &perr) || !types.is(json::Value::Object))
+      return hfail(err, TGX_INVALID_ARGUMENT, "arrow types JSON must be an object {column: DataType}: " + perr);
+    const std::vector<SpecRequest> reqs = c->plan();
+    if (reqs.size() != 1 || !reqs[0].temporal)
+      return hfail(err, TGX_INVALID_ARGUMENT, "not a temporal_ordering constraint");
+    const SpecRequest &r = reqs[0];
+    const tgx_temporal_params p = temporal_params(*r.temporal, types.get_str(r.column), types.get_str(r.column2));
+    auto n = [](int64_t v) { return std::to_string(v); };
+    *out_json = dup_string("{\"column\": " + json::quote(r.column) + ", \"column2\": " + json::quote(r.column2) +
+                           ", \"mode\": " + n(p.mode) + ", \"flags\": " + n(p.flags) + ", \"delta\": " + n(p.delta) +
+                           ", \"ticks_per_second\": " + n(p.ticks_per_second) + ", \"tod_lo\": " + n(p.tod_lo) +
+                           ", \"tod_hi\": " + n(p.tod_hi) + ", \"lo\": " + n(p.lo) + ", \"hi\": " + n(p.hi) + "}");
     return TGX_OK;
   } catch (const TermError &e) {
     return hfail(err, TGX_INVALID_ARGUMENT, e.display());

@@ -12,6 +12,7 @@
 #include <chrono>
 
 #include "json.h"
+#include "temporal.h"
 
 namespace term_guard {
 
@@ -30,6 +31,7 @@ std::string TermError::display() const {
     case DataFusion: return "DataFusion error: " + message;
     case NotSupported: return "Operation not supported: " + message;
     case Configuration: return "Configuration error: " + message;
+    case ConstraintEvaluation: return "Constraint evaluation failed for " + message;  // error.rs:28
     case TypeMismatch: return "Type mismatch: " + message;  // error.rs:81 ("expected {expected}, found {found}")
     default: return "Internal error: " + message;
   }
@@ -1301,7 +1303,8 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           if (r.column.empty() && r.kind == TGX_CHECK_COUNT && !table->column_names.empty())
             r.column = table->column_names[0];
           std::vector<const std::string *> named = {&r.column};
-          if (r.kind == TGX_CHECK_COMOMENTS) named.push_back(&r.column2);
+          if (r.kind == TGX_CHECK_COMOMENTS || (r.kind == TGX_CHECK_TEMPORAL && !r.column2.empty()))
+            named.push_back(&r.column2);
           for (const std::string &c2 : r.columns) named.push_back(&c2);
           for (const std::string *col : named) {
             if (column_index(*col) < 0) {
@@ -1310,6 +1313,14 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
             }
           }
           if (p.error) break;
+          if (r.temporal) {  // the unit rules (host/temporal.cpp): what is missing is this constraint's error
+            try {
+              (void)temporal_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
+            } catch (const TermError &e) {
+              p.error = e.display();
+              break;
+            }
+          }
         }
       }
       planned.push_back(std::move(p));
@@ -1330,7 +1341,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           const SpecRequest &q = spec_requests[i];
           if (q.kind == r.kind && q.column == r.column && q.column2 == r.column2 && q.columns == r.columns &&
               q.flags == r.flags && q.pattern == r.pattern && q.kll_k == r.kll_k && q.length_min == r.length_min &&
-              q.length_max == r.length_max)
+              q.length_max == r.length_max && q.temporal == r.temporal)
             found = i;
         }
         if (found == spec_requests.size()) spec_requests.push_back(r);
@@ -1342,7 +1353,9 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       memset(&s, 0, sizeof(s));
       s.kind = r.kind;
       s.column = column_index(r.column);
-      s.column2 = r.kind == TGX_CHECK_COMOMENTS ? column_index(r.column2) : -1;
+      s.column2 = r.kind == TGX_CHECK_COMOMENTS || (r.kind == TGX_CHECK_TEMPORAL && !r.column2.empty())
+                      ? column_index(r.column2)
+                      : -1;
       s.flags = r.flags;
       // COUNT(DISTINCT) by VALUE, as DataFusion groups (hash + equality): string / tuple keys are kept with their bytes
       if (r.kind == TGX_CHECK_DISTINCT && exact_keys_) s.flags |= TGX_FLAG_EXACT_KEYS;
@@ -1370,6 +1383,12 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
     memset(&err, 0, sizeof(err));
     tgx_status s = tgx_init(nullptr, &err);
     if (s == TGX_OK) s = tgx_plan_create(specs.data(), specs.size(), &hh.plan, &err);
+    for (size_t i = 0; s == TGX_OK && i < spec_requests.size(); i++) {
+      const SpecRequest &r = spec_requests[i];
+      if (!r.temporal) continue;
+      const tgx_temporal_params tp = temporal_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
+      s = tgx_plan_set_temporal(hh.plan, i, &tp, &err);
+    }
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
     for (size_t b = 0; s == TGX_OK && b < table->batches.size(); b++) {
@@ -1721,6 +1740,8 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     v.max = c.get_num("max", 0.0);
     v.max_correlation = c.get_num("max_correlation", 0.0);
     b.correlation(std::move(v));
+  } else if (type == "temporal_ordering") {
+    b.constraint(temporal_ordering_from_json(c));
   } else {
     throw TermError{TermError::Internal, "unknown constraint type '" + type + "'"};
   }

@@ -46,7 +46,8 @@ struct ConstraintResult {
 
 // TermError (error.rs:14-145): only the variants this path produces
 struct TermError {
-  enum Kind { Internal, SecurityError, DataFusion, NotSupported, Configuration, TypeMismatch } kind = Internal;
+  // ConstraintEvaluation: `message` starts with the quoted constraint name ("'temporal_ordering': ..", error.rs:28)
+  enum Kind { Internal, SecurityError, DataFusion, NotSupported, Configuration, TypeMismatch, ConstraintEvaluation } kind = Internal;
   std::string message;
   std::string display() const;  // thiserror Display strings, e.g. "Security error: ..."
 };
@@ -145,6 +146,21 @@ struct CorrelationValidation {
   std::vector<std::string> columns;           // MultiColumn (needs >= 2)
 };
 
+// The unit-free parameters of a TGX_CHECK_TEMPORAL request (host/temporal.h turns them, with the columns' Arrow types,
+// into tgx_temporal_params): seconds, "HH:MM", TIMESTAMP literal texts
+struct TemporalRequest {
+  int mode = 0;  // TGX_TEMPORAL_ORDER / _TIME_OF_DAY / _RANGE
+  bool allow_equal = false, allow_nulls = false, weekdays_only = false;
+  int64_t tolerance_seconds = 0;
+  std::string start_time, end_time;          // "HH:MM"
+  std::optional<std::string> min_date, max_date;
+  bool operator==(const TemporalRequest &o) const {
+    return mode == o.mode && allow_equal == o.allow_equal && allow_nulls == o.allow_nulls &&
+           weekdays_only == o.weekdays_only && tolerance_seconds == o.tolerance_seconds && start_time == o.start_time &&
+           end_time == o.end_time && min_date == o.min_date && max_date == o.max_date;
+  }
+};
+
 // One aggregate a constraint needs; the suite runner resolves column names and fuses all requests.
 struct SpecRequest {
   int kind = 0;  // tgx_check_kind
@@ -154,6 +170,7 @@ struct SpecRequest {
   std::string pattern;
   uint32_t kll_k = 0;
   uint64_t length_min = 0, length_max = ~0ull;  // LENGTH: inclusive character-count bounds
+  std::optional<TemporalRequest> temporal;      // TEMPORAL (`column2`: the after column in order mode)
 };
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:
@@ -297,6 +314,9 @@ class Check::Builder {
   Builder &multi_statistic(std::string column, std::vector<std::pair<StatisticType, Assertion>> statistics);
   Builder &quantile_validation(std::string column, QuantileValidation validation);
   Builder &correlation(CorrelationValidation validation);
+  // core/check.rs:2125-2179: pushes TemporalOrderingConstraint::new(table) -- empty column names, so evaluating it
+  // fails identifier validation, as in the reference; configured objects come through constraint(..) (host/temporal.h)
+  Builder &temporal_ordering(std::string table);
   Check build() { return check_; }
 
  private:

@@ -322,7 +322,7 @@ extern "C" tgx_status tgx_plan_set_joint_binning(tgx_plan *plan, size_t spec_ind
   if (!plan || !b) return fail(err, TGX_INVALID_ARGUMENT, "plan/binning is NULL");
   size_t slot = 0;
   TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_JOINT_BINS, "JOINT_BINS", &slot, err, nullptr));
-  if (plan->fp_key_locked.load())
+  if (plan_has_state(plan))
     return fail(err, TGX_INVALID_ARGUMENT, "the binning of a JOINT_BINS check is fixed once a state of the plan exists");
   if (b->bins < 2) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: bins must be at least 2", spec_index);
   if (b->bins > kJointMaxBins)

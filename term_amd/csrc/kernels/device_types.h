@@ -174,6 +174,26 @@ struct JointLaunch {
 };
 __host__ __device__ inline uint32_t joint_cells(uint32_t bins) { return (bins + 1) * (bins + 1); }
 
+// Temporal row predicates over one or two Int64-shaped columns (kernels/temporal.hip; TGX_CHECK_TEMPORAL).  The tasks of
+// a launch travel as ComomentColDesc (ORDER: x = before, y = after; the single-column modes read x only).  Per task two
+// 64-bit global counters: [0] rows that are non-NULL (both sides in ORDER mode) and pass the weekday filter, [1] those
+// of them that pass the predicate.  What a NULL row counts as is decided on the host from these and the rows seen.
+enum { kTemporalOrder = 1, kTemporalTimeOfDay = 2, kTemporalRange = 3 };
+struct TemporalParams {
+  int32_t mode;
+  int32_t weekdays_only;
+  int64_t delta;             // ORDER: passes iff after - before >= delta (no wrap-around)
+  int64_t ticks_per_second;  // TIME_OF_DAY: 1, 10^3, 10^6 or 10^9
+  int64_t lo, hi;            // TIME_OF_DAY: ticks into the day; RANGE: the bounds; both ends inclusive
+};
+constexpr int kTemporalBlock = 512;
+constexpr int kMaxTemporalPerLaunch = 8;
+struct TemporalLaunch {
+  ComomentColDesc cols[kMaxTemporalPerLaunch];
+  TemporalParams params[kMaxTemporalPerLaunch];
+  unsigned long long *counters[kMaxTemporalPerLaunch];
+};
+
 // One (column, batch) window of the library-side batch coalescing (kernels/gather.hip): where the window lives and
 // where it lands in the coalesced column.  A table of these is uploaded per flush; one workgroup per entry.
 struct GatherSeg {

@@ -5,7 +5,8 @@
 //   joint_bins_kernel   per such row i = FLOOR((x - x_origin) / x_width), j likewise, cell (i, j) += 1
 //
 // Both read what comoments_kernel reads (16 B + 2 validity bits per row) the way it does: one row per lane per load,
-// row pairs as one 16-byte load per column where the addresses allow, four loads in flight per column per lane.
+// row pairs as one 16-byte load per column where the addresses allow, four loads in flight per column per lane
+// (jb_for_rows, row_walk.h).
 //
 // The cells of a workgroup are 32-bit counters in LDS (a workgroup's share of the rows stays below 2^32), flushed to the
 // task's 64-bit global counters with vector atomics once, at the end, non-zero cells only.  What decides the design is
@@ -18,82 +19,11 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "row_walk.h"
 
 namespace tgx {
 
 namespace {
-
-typedef const int64_t __attribute__((address_space(1))) *jb_i64_ptr;
-typedef const uint8_t __attribute__((address_space(1))) *jb_u8_ptr;
-
-__device__ __forceinline__ bool jb_valid(jb_u8_ptr v, int64_t bit) {
-  return v == nullptr ? true : ((v[bit >> 3] >> (bit & 7)) & 1) != 0;
-}
-
-// every row of the pair's window once: fold(x bits, y bits, row is in the window and both sides are non-NULL)
-template <class Fold>
-__device__ __forceinline__ void jb_for_rows(const ComomentColDesc &d, Fold fold) {
-  jb_i64_ptr x = (jb_i64_ptr)(uintptr_t)((const int64_t *)d.x + d.xoff);
-  jb_i64_ptr y = (jb_i64_ptr)(uintptr_t)((const int64_t *)d.y + d.yoff);
-  jb_u8_ptr xv = (jb_u8_ptr)(uintptr_t)d.xv;
-  jb_u8_ptr yv = (jb_u8_ptr)(uintptr_t)d.yv;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const bool wide =
-      ((((uintptr_t)((const int64_t *)d.x + d.xoff)) | ((uintptr_t)((const int64_t *)d.y + d.yoff))) & 15) == 0;
-  int64_t done = 0;  // rows [0, done) are handled by the wide path
-  if (wide) {
-    typedef long long i64x2 __attribute__((ext_vector_type(2)));
-    typedef const i64x2 __attribute__((address_space(1))) *jb_i64x2_ptr;
-    jb_i64x2_ptr x2 = (jb_i64x2_ptr)x, y2 = (jb_i64x2_ptr)y;
-    const int64_t n_pairs = d.length >> 1;
-    done = 2 * n_pairs;
-    const bool x_even = (d.xoff & 1) == 0, y_even = (d.yoff & 1) == 0;
-    for (int64_t p0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p0 < n_pairs; p0 += 4 * stride) {
-      i64x2 xq[4], yq[4];
-      bool ok[8];
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int64_t p = p0 + u * stride;
-        const bool in = p < n_pairs;
-        const int64_t q = in ? p : 0;
-        uint32_t xb2 = 3, yb2 = 3;  // both rows of a pair share a validity byte when the Arrow offset is even
-        if (xv) {
-          const int64_t b = d.xoff + 2 * q;
-          xb2 = x_even ? ((uint32_t)xv[b >> 3] >> (b & 7)) & 3u
-                       : (uint32_t)jb_valid(xv, b) | ((uint32_t)jb_valid(xv, b + 1) << 1);
-        }
-        if (yv) {
-          const int64_t b = d.yoff + 2 * q;
-          yb2 = y_even ? ((uint32_t)yv[b >> 3] >> (b & 7)) & 3u
-                       : (uint32_t)jb_valid(yv, b) | ((uint32_t)jb_valid(yv, b + 1) << 1);
-        }
-        ok[2 * u] = in && (xb2 & yb2 & 1u);
-        ok[2 * u + 1] = in && ((xb2 & yb2) >> 1);
-        xq[u] = __builtin_nontemporal_load(x2 + q);
-        yq[u] = __builtin_nontemporal_load(y2 + q);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        fold(xq[u].x, yq[u].x, ok[2 * u]);
-        fold(xq[u].y, yq[u].y, ok[2 * u + 1]);
-      }
-    }
-  }
-  for (int64_t i0 = done + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < d.length; i0 += 4 * stride) {
-    int64_t xb[4], yb[4];
-    bool ok[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int64_t i = i0 + u * stride;
-      const bool in = i < d.length;
-      xb[u] = in ? x[i] : 0;
-      yb[u] = in ? y[i] : 0;
-      ok[u] = in && jb_valid(xv, d.xoff + (in ? i : 0)) && jb_valid(yv, d.yoff + (in ? i : 0));
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) fold(xb[u], yb[u], ok[u]);
-  }
-}
 
 struct JointRangePartial {
   int64_t n, non_finite;

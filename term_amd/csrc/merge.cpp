@@ -78,6 +78,7 @@ extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state 
     TGX_TRY(kll_merge_states(dst, src, err));
     TGX_TRY(regex_merge_states(dst, src, err));
     TGX_TRY(joint_merge_states(dst, src, err));
+    TGX_TRY(temporal_merge_states(dst, src, err));
   }
   return TGX_OK;
 } catch (...) {

@@ -1,0 +1,21 @@
+// temporal_device.h -- TGX_CHECK_TEMPORAL tasks of a state (two additive counters per task on the device, additive host
+// part); see temporal_device.cpp.
+#pragma once
+#include "internal.h"
+#include "wire_io.h"
+
+namespace tgx {
+tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+// every task has its parameters (tgx_plan_set_temporal)?  Asked by tgx_state_create
+tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
+void temporal_state_init(tgx_state *st);
+void temporal_state_free(tgx_state *st);
+tgx_status temporal_state_reset(tgx_state *st, tgx_error *err);
+// one batch (device views of the plan's columns) through the tasks' kernel
+tgx_status temporal_update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err);
+tgx_status temporal_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err);
+tgx_status temporal_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err);
+// the blob's section: present only when the plan has such tasks (blobs of other plans keep their bytes)
+TGX_HIDDEN tgx_status temporal_serialize(tgx_state *st, Writer &w, tgx_error *err);
+TGX_HIDDEN tgx_status temporal_deserialize(tgx_state *st, Reader &r, tgx_error *err);
+}  // namespace tgx

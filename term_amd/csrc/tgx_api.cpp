@@ -308,6 +308,13 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
+      case TGX_CHECK_TEMPORAL: {
+        int slot = -1;
+        TGX_TRY(temporal_plan_add(plan.get(), (int)i, &slot, err));
+        max_col = std::max(max_col, sp.column2);
+        plan->bind[i].slot = slot;
+        break;
+      }
       case TGX_CHECK_SPEARMAN: {
         max_col = std::max(max_col, sp.column2);
         int slot = -1;
@@ -364,6 +371,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     P->key_column.assign(P->n_columns_needed, 0);
     P->stats_on.assign(P->n_columns_needed, 0);
     P->joint_on.assign(P->n_columns_needed, 0);
+    P->temporal_on.assign(P->n_columns_needed, 0);
     for (auto &t : P->distinct)
       if (t.tuple.empty() && !t.approx_only) P->key_column[t.column] = 1;
     // (by what was ASKED: a key column has a scan task of its own for the range decisions of its key set)
@@ -388,6 +396,9 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     for (auto &t : P->joint)
       for (int c : {t.col_x, t.col_y})
         P->used[c] = P->reads_values[c] = P->needs_wide[c] = P->stats_on[c] = P->joint_on[c] = 1;
+    for (auto &t : P->temporal)
+      for (int c : {t.column, t.column2})
+        if (c >= 0) P->used[c] = P->reads_values[c] = P->temporal_on[c] = 1;
     regex_mark_used(P, P->used);
     std::vector<char> sp_used(P->n_columns_needed, 0), sp_vals(P->n_columns_needed, 0);
     spearman_mark_used(P, sp_used, sp_vals);
@@ -523,6 +534,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   kll_state_init(st);
   spearman_state_init(st);
   joint_state_init(st);
+  temporal_state_init(st);
 }
 
 // one launch for all the small accumulators of a state (fresh, or reset): the scan accumulators to their identities,
@@ -588,6 +600,7 @@ extern "C" tgx_status tgx_state_create(const tgx_plan *plan, void *hip_stream, t
                                        tgx_error *err) try {
   if (!plan || !out) return fail(err, TGX_INVALID_ARGUMENT, "plan/out is NULL");
   *out = nullptr;
+  TGX_TRY(temporal_plan_ready(plan, err));  // (before the plan is locked: the parameters can still follow)
   tgx_state *st = new tgx_state();
   state_init_host(st, plan);
   st->stream = (hipStream_t)hip_stream;
@@ -622,6 +635,7 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   kll_state_free(st);
   spearman_state_free(st);
   joint_state_free(st);
+  temporal_state_free(st);
   coalesce_drop(st);  // (copy threads that are still filling an arena let go of it first)
   for (int k = 0; k < 2; k++) {
     if (st->arena_event[k]) (void)hipEventDestroy(st->arena_event[k]);
@@ -709,6 +723,7 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   regex_state_reset(st);
   spearman_state_reset(st);
   TGX_TRY(joint_state_reset(st, err));
+  TGX_TRY(temporal_state_reset(st, err));
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
   st->hll_mode.assign(plan->hll.size(), 0);
   if (st->device_ready && st->d_hll.p)
@@ -1095,6 +1110,9 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
         break;
       case TGX_CHECK_JOINT_BINS:
         TGX_TRY(joint_fill_result(st, b.slot, r, err));
+        break;
+      case TGX_CHECK_TEMPORAL:
+        TGX_TRY(temporal_fill_result(st, b.slot, r, err));
         break;
       default:
         break;

@@ -263,6 +263,11 @@ class CheckBuilder:
     def has_correlation(self, column1, column2, assertion):
         return self._add(type="correlation", column1=column1, column2=column2, assertion=assertion.to_json())
 
+    def temporal_ordering(self, table_name):
+        """core/check.rs:2125-2179: pushes TemporalOrderingConstraint::new(table) as it stands -- empty column names, so
+        evaluating it fails identifier validation, as in the reference; a configured object goes through constraint()"""
+        return self.constraint(TemporalOrderingConstraint(table_name))
+
     def constraint(self, c):
         """core/check.rs:263: a constraint object (MultiStatisticalConstraint, QuantileConstraint,
         CorrelationConstraint below) instead of a builder shorthand"""
@@ -373,6 +378,60 @@ class CorrelationConstraint:
     @staticmethod
     def multi_column(columns, correlation_type=CorrelationType.Pearson):
         return CorrelationConstraint(validation="multi_column", columns=list(columns), correlation_type=correlation_type)
+
+
+class TemporalOrderingConstraint:
+    """constraints/temporal_ordering.rs:106-288, one method per builder call of the reference.  BeforeAfter,
+    BusinessHours and DateRange run on the device (TGX_CHECK_TEMPORAL); MaxTimeGap and EventSequence evaluate to an
+    error"""
+
+    def __init__(self, table_name):
+        self.spec = {"type": "temporal_ordering", "table": table_name, "allow_nulls": False, "tolerance_seconds": 0}
+
+    def _type(self, validation, **fields):
+        keep = {k: self.spec[k] for k in ("type", "table", "allow_nulls", "tolerance_seconds")}
+        self.spec = dict(keep, validation=validation, **fields)
+        return self
+
+    def before_after(self, before_column, after_column):
+        return self._type("before_after", before_column=before_column, after_column=after_column, allow_equal=False)
+
+    def before_or_equal(self, before_column, after_column):
+        return self._type("before_after", before_column=before_column, after_column=after_column, allow_equal=True)
+
+    def business_hours(self, timestamp_column, start_time, end_time):
+        return self._type("business_hours", timestamp_column=timestamp_column, start_time=start_time,
+                          end_time=end_time, weekdays_only=False, timezone=None)
+
+    def weekdays_only(self, weekdays_only):
+        if self.spec.get("validation") == "business_hours":
+            self.spec["weekdays_only"] = bool(weekdays_only)
+        return self
+
+    def with_timezone(self, timezone):
+        if self.spec.get("validation") == "business_hours":
+            self.spec["timezone"] = timezone
+        return self
+
+    def date_range(self, timestamp_column, min_date=None, max_date=None):
+        return self._type("date_range", timestamp_column=timestamp_column, min_date=min_date, max_date=max_date)
+
+    def max_time_gap(self, timestamp_column, max_gap_seconds):
+        return self._type("max_time_gap", timestamp_column=timestamp_column, max_gap_seconds=int(max_gap_seconds),
+                          group_by_column=None)
+
+    def group_by(self, column):
+        if self.spec.get("validation") == "max_time_gap":
+            self.spec["group_by_column"] = column
+        return self
+
+    def allow_nulls(self, allow):
+        self.spec["allow_nulls"] = bool(allow)
+        return self
+
+    def tolerance_seconds(self, seconds):
+        self.spec["tolerance_seconds"] = int(seconds)
+        return self
 
 
 class Check:
@@ -788,6 +847,7 @@ def _host():
                                               C.c_size_t, C.POINTER(C.c_char_p), E]
         L.tgx_host_constraint_plan_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_constraint_verdict_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_temporal_params_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_validate_identifier.argtypes = [C.c_char_p, E]
         L.tgx_host_assertion_json.argtypes = [C.c_char_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), E]
         L.tgx_host_run_analysis_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_Column),
@@ -825,6 +885,16 @@ def constraint_verdict(constraint, results):
     err = _Error()
     _host_check(_host().tgx_host_constraint_verdict_json(json.dumps(constraint).encode(), json.dumps(results).encode(),
                                                          C.byref(out), C.byref(err)), err)
+    return json.loads(_take(out))
+
+
+def temporal_params(constraint, arrow_types):
+    """a temporal_ordering constraint (its dict) + {column: Arrow DataType name} -> the tgx_temporal_params of its
+    TEMPORAL spec as a dict (tgx_host_temporal_params_json); TgxError with the constraint's error text otherwise"""
+    out = C.c_char_p()
+    err = _Error()
+    _host_check(_host().tgx_host_temporal_params_json(json.dumps(constraint).encode(), json.dumps(arrow_types).encode(),
+                                                      C.byref(out), C.byref(err)), err)
     return json.loads(_take(out))
 
 

@@ -26,6 +26,12 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                     u64 n_words; u64 words[n_words] }                                     when n = 0 and in the count phase)
                                n_words = (bins + 1)^2 + 1 in the count phase: the cells, row-major, then the rows whose
                                index fell outside [0, bins]; 0 in the range phase.  n = the sum of the cells there.
+    and ONLY for plans with TEMPORAL checks, behind the JOINT_BINS section if there is one:
+    u32 magic 'TMPR', u32 n_temporal
+    n_temporal  x { i32 mode, u32 flags; i64 delta, ticks_per_second, lo, hi     (the plan's parameters: tod_lo / tod_hi
+                    u64 seen, live, passed }                                      travel as lo / hi; fields of other modes 0)
+                               live = rows that are non-NULL (both sides in order mode) and through the weekday filter,
+                               passed = those of them that satisfy the predicate: passed <= live <= seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -34,6 +40,7 @@ import struct
 
 MAGIC, VERSION = 0x53584754, 3
 JOINT_MAGIC = 0x42544E4A  # 'JNTB'
+TEMPORAL_MAGIC = 0x52504D54  # 'TMPR'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -115,10 +122,18 @@ def joint_count_state(binning, total, cells, outside=0, non_finite=0):
                         len(words)) + struct.pack("<%dQ" % len(words), *words))
 
 
-def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=()):
+def temporal_state(mode, flags, seen, live, passed, delta=0, ticks_per_second=0, lo=0, hi=0):
+    """a TEMPORAL task: the plan's parameters as the device holds them (time of day: lo / hi = tod_lo / tod_hi; the
+    fields of other modes 0) and its three counters"""
+    return struct.pack("<iI4q3Q", mode, flags, delta, ticks_per_second, lo, hi, seen, live, passed)
+
+
+def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
     tail = struct.pack("<II", JOINT_MAGIC, len(joint)) + b"".join(joint) if joint else b""
+    if temporal:
+        tail += struct.pack("<II", TEMPORAL_MAGIC, len(temporal)) + b"".join(temporal)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
