@@ -209,7 +209,24 @@ typedef enum tgx_check_kind {
    * tgx_temporal_get; tgx_result carries total = rows seen, non_null = rows considered, matches = considered -
    * violations.  Every other column type is TGX_UNSUPPORTED from tgx_update.  The state is three counters: tgx_merge,
    * state blobs and tgx_allreduce add them. */
-  TGX_CHECK_TEMPORAL = 11
+  TGX_CHECK_TEMPORAL = 11,
+  /* The two scans behind HistogramAnalyzer         TG/analyzers/advanced/histogram.rs:184-330
+   * over `column`, every value CAST AS DOUBLE, in TWO PHASES -- the bucket edges depend on the whole table, so the
+   * reference scans twice and so does the caller here:
+   *   range phase (no edges set on the spec): n, MIN, MAX, SUM(c) and SUM(c * c) over the rows that are non-NULL and
+   *     finite; the sums are plain double sums (they carry the reference's own cancellation; nothing is pivoted); read
+   *     with tgx_histogram_range_get;
+   *   count phase (tgx_plan_set_histogram_edges was called for the spec, with buckets + 1 edges): per such row x the
+   *     bucket is the first i in 0 .. buckets-1 with edges[i] <= x < edges[i+1], else buckets-1 -- the reference's
+   *     CASE WHEN .. ELSE num_buckets (histogram.rs:262-294) taken literally, including for rows below edges[0] or at
+   *     or above edges[buckets]; read with tgx_histogram_counts.
+   * A NULL row is dropped (WHERE c IS NOT NULL).  A NaN or an infinity is left out of n, the range, the sums and the
+   * buckets and counted as `non_finite` (the reference's own behaviour there is an accident of comparisons with NaN and
+   * pinned by nothing).  tgx_result carries total (rows seen) and non_null (the non-NULL rows: n + non_finite).
+   * Columns: Int64, Float64, and Int32 / Float32 / Int8 .. UInt32 through the widening staging; UInt64, Boolean and every
+   * string layout are TGX_UNSUPPORTED.  The state is additive: tgx_merge, state blobs and tgx_allreduce combine the
+   * extremes by MIN / MAX and n, the sums and the buckets by addition. */
+  TGX_CHECK_HISTOGRAM = 12
 } tgx_check_kind;
 
 enum {
@@ -396,6 +413,18 @@ typedef struct tgx_temporal_params {
 } tgx_temporal_params;
 tgx_status tgx_plan_set_temporal(tgx_plan *plan, size_t spec_index, const tgx_temporal_params *params, tgx_error *err);
 
+/* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
+ * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
+ * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
+ * and edges[0 .. buckets-1] non-decreasing (TGX_INVALID_ARGUMENT otherwise).  edges[buckets] MAY lie below
+ * edges[buckets-1]: the reference's own formula produces that on a range a few ulps wide, where max + width * 0.001
+ * rounds to max while min + (buckets-1) * width has rounded up.  The reference's values are
+ * width = (MAX - MIN) > 0 && buckets > 1 ? (MAX - MIN) / buckets : 1.0, edges[i] = MIN + i * width for i < buckets and
+ * edges[buckets] = MAX + width * 0.001 (histogram.rs:253-275). */
+#define TGX_HISTOGRAM_MAX_BUCKETS 1000
+tgx_status tgx_plan_set_histogram_edges(tgx_plan *plan, size_t spec_index, const double *edges, uint32_t buckets,
+                                        tgx_error *err);
+
 /* State = `Analyzer::State` for every spec of the plan (TG/analyzers/traits.rs:154-179).
  * `hip_stream` is a hipStream_t (NULL = a stream the library creates).  Everything the state does on the device is
  * queued on that stream and nowhere else: a DEVICE buffer handed to tgx_update has to be COMPLETE as far as that
@@ -505,6 +534,26 @@ tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *state, size_t sp
 tgx_status tgx_joint_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, uint64_t *cells, uint64_t cap,
                             uint64_t *n_cells, uint64_t *out_of_range, tgx_error *err);
 
+/* ---- histogram of a numeric column (TGX_CHECK_HISTOGRAM; TG/analyzers/advanced/histogram.rs:184-330) ------------- */
+typedef struct tgx_histogram_range {
+  uint64_t total;       /* rows seen */
+  uint64_t nulls;       /* NULL rows */
+  uint64_t non_finite;  /* non-NULL rows holding a NaN or an infinity */
+  uint64_t n;           /* non-NULL, finite rows */
+  double min, max;      /* over the n rows; NaN when n == 0 */
+  double sum, sum_squared; /* SUM(x), SUM(x * x) over the n rows as plain double sums; 0 when n == 0 */
+} tgx_histogram_range;
+/* a spec in its range phase; a spec in its count phase answers total, nulls, non_finite and n (the sum of its buckets)
+ * and leaves the extremes and the sums NaN */
+tgx_status tgx_histogram_range_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_histogram_range *out,
+                                   tgx_error *err);
+/* a spec in its count phase: its `buckets` counts into the caller's `counts` (`cap` entries; fewer than `buckets`:
+ * TGX_INVALID_ARGUMENT).  *else_rows = the rows that reached the last bucket through ELSE rather than through its own
+ * WHEN (below edges[0], or at or above edges[buckets]); they are part of counts[buckets-1].  *non_finite as above;
+ * either may be NULL. */
+tgx_status tgx_histogram_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, uint64_t *counts, size_t cap,
+                                uint64_t *else_rows, uint64_t *non_finite, tgx_error *err);
+
 /* ---- temporal row predicates (TGX_CHECK_TEMPORAL; TG/constraints/temporal_ordering.rs:346-453) -------------------- */
 typedef struct tgx_temporal_counts {
   uint64_t seen;        /* rows handed to tgx_update */
@@ -603,7 +652,8 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal"; "distinct_lists" is the share of
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "hist_range",
+ * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);
 tgx_status tgx_profile_get(tgx_state *state, const char *kernel, double *total_ms,

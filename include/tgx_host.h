@@ -81,11 +81,12 @@ tgx_status tgx_host_assertion_json(const char *assertion_json, double value, int
  * Analysis JSON: {"table_name": "data", "continue_on_error": true, "analyzers": [
  *     {"type": "size"}, {"type": "completeness|distinctness|approx_count_distinct|mean|min|max|sum|standard_deviation", "column": "c"},
  *     {"type": "correlation", "column1": "a", "column2": "b", "method": "pearson|spearman|covariance"},
- *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10}]}
- * AnalysisRunner::run: every analyzer's aggregates planned into ONE tgx_plan, one pass over the table; a
- * mutual_information analyzer (numeric pairs; bin edges depend on the whole table) adds a second pass for its joint bin
- * counts, shared by all such analyzers of the run.  Returns
- *   {"metrics": {metric_key: {"type": "Double|Long|Map", "value": ..}},      (MetricValue's serde form, types.rs:11-35)
+ *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10},
+ *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true}]}
+ * AnalysisRunner::run: every analyzer's aggregates planned into ONE tgx_plan, one pass over the table; the
+ * mutual_information and histogram analyzers (bin edges depend on the whole table) add a second pass for their counts,
+ * shared by all such analyzers of the run.  Returns
+ *   {"metrics": {metric_key: {"type": "Double|Long|Map|Histogram", "value": ..}},   (MetricValue's serde form, types.rs:11-35)
  *    "states":  {metric_key: {..the AnalyzerState's serde fields..}},
  *    "errors":  [{"analyzer_name": "..", "error": ".."}]}                        (context.rs:118-123)
  * With continue_on_error false the first failing analyzer makes the call fail with "Analyzer {name} failed". */

@@ -14,6 +14,8 @@ JOINT_MAX_BINS = 127
 TEMPORAL = 11  # row predicates over timestamp columns (Plan.set_temporal)
 TEMPORAL_ORDER, TEMPORAL_TIME_OF_DAY, TEMPORAL_RANGE = 1, 2, 3
 TEMPORAL_KEEP_NULLS, TEMPORAL_WEEKDAYS_ONLY = 1, 2
+HISTOGRAM = 12  # the histogram of a numeric column, in two phases (Plan.set_histogram_edges)
+HISTOGRAM_MAX_BUCKETS = 1000
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -92,6 +94,12 @@ class TemporalParams(C.Structure):
 class TemporalCounts(C.Structure):
     """tgx_temporal_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("violations", C.c_uint64)]
+
+
+class HistogramRange(C.Structure):
+    """tgx_histogram_range (include/tgx.h)"""
+    _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
+                ("min", C.c_double), ("max", C.c_double), ("sum", C.c_double), ("sum_squared", C.c_double)]
 
 
 class _Options(C.Structure):
@@ -206,6 +214,9 @@ def lib():
         L.tgx_joint_counts.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), C.POINTER(u64), E]
         L.tgx_plan_set_temporal.argtypes = [vp, sz, C.POINTER(TemporalParams), E]
         L.tgx_temporal_get.argtypes = [vp, vp, sz, C.POINTER(TemporalCounts), E]
+        L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
+        L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
+        L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
         _LIB = L
     return _LIB
 
@@ -582,6 +593,7 @@ class Plan:
         _check(lib().tgx_plan_create(arr, len(self._specs), C.byref(h), C.byref(err)), err)
         self.h = h
         self.n = len(self._specs)
+        self.histogram_buckets = {}  # spec index -> buckets, once set_histogram_edges was called
         if fingerprint_key is not None:
             self.set_fingerprint_key(fingerprint_key)
 
@@ -597,6 +609,18 @@ class Plan:
         b = JointBinning(x_origin, x_width, y_origin, y_width, bins, 0)
         err = _Error()
         _check(lib().tgx_plan_set_joint_binning(self.h, spec_index, C.byref(b), C.byref(err)), err)
+
+    def set_histogram_edges(self, spec_index, edges):
+        """tgx_plan_set_histogram_edges: puts a HISTOGRAM spec into its count phase (before the plan's first state);
+        `edges` are the buckets + 1 edges, lowest first"""
+        edges = [float(e) for e in edges]
+        if not edges:
+            raise ValueError("a histogram needs at least two edges")
+        buckets = len(edges) - 1
+        arr = (C.c_double * len(edges))(*edges)
+        err = _Error()
+        _check(lib().tgx_plan_set_histogram_edges(self.h, spec_index, arr, buckets, C.byref(err)), err)
+        self.histogram_buckets[spec_index] = buckets
 
     def set_temporal(self, spec_index, mode, flags=0, delta=0, ticks_per_second=0, tod_lo=0, tod_hi=0,
                      lo=-(1 << 63), hi=(1 << 63) - 1):
@@ -756,6 +780,24 @@ class State:
         _check(lib().tgx_joint_counts(self.plan.h, self.h, spec_index, cells, n.value, C.byref(n), C.byref(outside),
                                       C.byref(err)), err)
         return list(cells)[: n.value], outside.value
+
+    # histogram of a numeric column
+    def histogram_range(self, spec_index):
+        """tgx_histogram_range_get: dict(total, nulls, non_finite, n, min, max, sum, sum_squared)"""
+        out = HistogramRange()
+        err = _Error()
+        _check(lib().tgx_histogram_range_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return {name: getattr(out, name) for name, _ in HistogramRange._fields_}
+
+    def histogram_counts(self, spec_index):
+        """tgx_histogram_counts: (the bucket counts as a list of ints, else_rows, non_finite)"""
+        n = self.plan.histogram_buckets.get(spec_index, 0)
+        counts = (C.c_uint64 * max(1, n))()
+        else_rows, non_finite = C.c_uint64(), C.c_uint64()
+        err = _Error()
+        _check(lib().tgx_histogram_counts(self.plan.h, self.h, spec_index, counts, n, C.byref(else_rows),
+                                          C.byref(non_finite), C.byref(err)), err)
+        return list(counts)[:n], else_rows.value, non_finite.value
 
     # temporal row predicates
     def temporal_counts(self, spec_index):

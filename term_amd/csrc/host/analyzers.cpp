@@ -1,6 +1,6 @@
 // analyzers.cpp -- see analyzers.h.  Reference: TG/analyzers/{traits,runner,context,types,errors}.rs,
 // TG/analyzers/basic/{size,completeness,distinctness,mean,min_max,sum}.rs,
-// TG/analyzers/advanced/{standard_deviation,correlation}.rs.
+// TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram}.rs.
 #include "analyzers.h"
 
 #include <math.h>
@@ -95,6 +95,18 @@ std::string MetricValue::to_json() const {
       std::string o = "{\"type\": \"Map\", \"value\": {";
       for (size_t i = 0; i < map.size(); i++) o += (i ? ", " : "") + json::quote(map[i].first) + ": " + map[i].second.to_json();
       return o + "}}";
+    }
+    case Histogram: {  // MetricDistribution's serde form (types.rs:95-169)
+      auto optional = [](const std::optional<double> &v) { return v ? num_text(*v) : std::string("null"); };
+      std::string o = "{\"type\": \"Histogram\", \"value\": {\"buckets\": [";
+      for (size_t i = 0; i < histogram.buckets.size(); i++) {
+        const HistogramBucket &b = histogram.buckets[i];
+        o += std::string(i ? ", " : "") + "{\"lower_bound\": " + num_text(b.lower_bound) + ", \"upper_bound\": " +
+             num_text(b.upper_bound) + ", \"count\": " + std::to_string((unsigned long long)b.count) + "}";
+      }
+      return o + "], \"total_count\": " + std::to_string((unsigned long long)histogram.total_count) + ", \"min\": " +
+             optional(histogram.min) + ", \"max\": " + optional(histogram.max) + ", \"mean\": " +
+             optional(histogram.mean) + ", \"std_dev\": " + optional(histogram.std_dev) + "}}";
     }
   }
   return "null";
@@ -428,13 +440,14 @@ class MutualInformationAnalyzer : public Analyzer {
     return {r};
   }
   bool two_pass() const override { return true; }
-  std::optional<tgx_joint_binning> follow_up(const tgx_joint_range &range) const override {
+  std::optional<FollowUp> follow_up(const FirstPass &first) const override {
+    const tgx_joint_range &range = first.joint;
     if (range.n == 0) return std::nullopt;
     if (bins_ > TGX_JOINT_MAX_BINS)
       throw AnalyzerError::query("TGX_UNSUPPORTED: " + std::to_string(bins_) + " bins: at most " +
                                  std::to_string(TGX_JOINT_MAX_BINS) + " are supported");
-    tgx_joint_binning b;
-    memset(&b, 0, sizeof(b));
+    FollowUp out;
+    tgx_joint_binning &b = out.binning;
     // :219-233, in the same double arithmetic
     const double x_range = range.x_max - range.x_min, y_range = range.y_max - range.y_min;
     if (!std::isfinite(x_range) || !std::isfinite(y_range))
@@ -445,12 +458,13 @@ class MutualInformationAnalyzer : public Analyzer {
     b.y_origin = range.y_min;
     b.y_width = y_range > 0.0 ? y_range / (double)bins_ : 1.0;
     b.bins = (uint32_t)bins_;
-    return b;
+    return out;
   }
   json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
-    return state_from_follow_up(tgx_joint_range(), nullptr);
+    return state_from_follow_up(FirstPass(), nullptr);
   }
-  json::Value state_from_follow_up(const tgx_joint_range &, const JointCounts *counts) const override {
+  json::Value state_from_follow_up(const FirstPass &, const SecondPass *second) const override {
+    const JointCounts *counts = second ? &second->joint : nullptr;
     std::vector<Cell> cells;
     uint64_t n = 0;
     if (counts) {
@@ -553,6 +567,142 @@ class MutualInformationAnalyzer : public Analyzer {
   uint64_t bins_;
 };
 
+// The reference's arithmetic on the first query's results, in IEEE doubles exactly as written: every product rounds
+// before the sum that takes it.  (The library's build does not contract; the pragma keeps it so under any flags.)
+struct HistogramArithmetic {
+  // histogram.rs:253-275: width = range > 0 && B > 1 ? range / B : 1.0; lower_i = min + (i as f64 * width);
+  // the last upper edge = max + width * 0.001
+  static std::vector<double> edges(double min, double max, uint64_t buckets) {
+#pragma clang fp contract(off)
+    const double range = max - min;
+    const double width = range > 0.0 && buckets > 1 ? range / (double)buckets : 1.0;
+    std::vector<double> e(buckets + 1);
+    for (uint64_t i = 0; i < buckets; i++) {
+      const double step = (double)i * width;
+      e[i] = min + step;
+    }
+    const double tail = width * 0.001;
+    e[buckets] = max + tail;
+    return e;
+  }
+  // histogram.rs:107-115: sqrt(sum_squared / n - mean * mean), NaN when the difference is negative
+  static double std_dev(double sum_squared, double n, double mean) {
+#pragma clang fp contract(off)
+    const double mean_squared = mean * mean;
+    const double variance = sum_squared / n - mean_squared;
+    return sqrt(variance);
+  }
+};
+
+// advanced/histogram.rs: two passes -- MIN, MAX, COUNT, SUM, SUM(c * c) WHERE c IS NOT NULL, then COUNT(*) GROUP BY a
+// CASE chain over `num_buckets` equal-width buckets whose edges come from the first -- both on the device
+// (TGX_CHECK_HISTOGRAM).  The reference downcasts MIN to Float64Array, so a column of another type is
+// "Expected Float64 for min" there; with "strict_reference_types": false on the analyzer such a column runs CAST AS
+// DOUBLE instead.  Rows holding a NaN or an infinity are left out of everything, as MutualInformationAnalyzer does.
+class HistogramAnalyzer : public ColumnAnalyzer {
+ public:
+  HistogramAnalyzer(std::string c, uint64_t num_buckets, bool strict_types)
+      : ColumnAnalyzer(std::move(c)), buckets_(std::min<uint64_t>(std::max<uint64_t>(num_buckets, 1), 1000)),  // :61-66
+        strict_types_(strict_types) {}
+  std::string name() const override { return "histogram"; }
+  std::string metric_key() const override { return name(); }  // the reference does not add the column (traits.rs:133-135)
+  std::vector<SpecRequest> plan() const override { return {req(TGX_CHECK_HISTOGRAM, column_)}; }
+  bool two_pass() const override { return true; }
+  std::optional<FollowUp> follow_up(const FirstPass &first) const override {
+    const tgx_histogram_range &r = first.histogram;
+    if (r.n == 0) return std::nullopt;  // :237-246: the empty state, no second query
+    if (strict_types_ && !first.column_types.empty() && first.column_types[0] != TGX_FLOAT64)
+      throw AnalyzerError::invalid_data("Expected Float64 for min");  // :205-210
+    if (!std::isfinite(r.max - r.min))
+      throw AnalyzerError::invalid_data("the range of " + column_ + " overflows a double: no bucket width");
+    FollowUp out;
+    out.edges = HistogramArithmetic::edges(r.min, r.max, buckets_);
+    for (double e : out.edges)
+      if (!std::isfinite(e))
+        throw AnalyzerError::invalid_data("the bucket edges of " + column_ + " overflow a double");
+    return out;
+  }
+  json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
+    return state_from_follow_up(FirstPass(), nullptr);
+  }
+  json::Value state_from_follow_up(const FirstPass &first, const SecondPass *second) const override {
+    State s;
+    if (!second) return dump(s);  // no rows
+    const tgx_histogram_range &r = first.histogram;
+    const std::vector<double> e = HistogramArithmetic::edges(r.min, r.max, buckets_);
+    for (size_t i = 0; i < second->buckets.size() && i + 1 < e.size(); i++)
+      s.buckets.push_back({e[i], e[i + 1], second->buckets[i]});
+    s.min = r.min;
+    s.max = r.max;
+    s.total = r.n;
+    s.sum = r.sum;
+    s.sum_squared = r.sum_squared;
+    return dump(s);
+  }
+  json::Value merge_states(const std::vector<json::Value> &states) const override {  // :120-171
+    if (states.empty()) throw AnalyzerError::state_merge("No states to merge");
+    State m = parse(states[0]);  // the first state's bucket structure
+    for (size_t k = 1; k < states.size(); k++) {
+      const State s = parse(states[k]);
+      if (s.buckets.size() == m.buckets.size())
+        for (size_t i = 0; i < s.buckets.size(); i++) m.buckets[i].count += s.buckets[i].count;
+      // min_by / max_by over partial_cmp, Equal when unordered: a later value replaces only when it compares below / not below
+      if (s.min < m.min) m.min = s.min;
+      if (!(s.max < m.max)) m.max = s.max;
+      m.total += s.total;
+      m.sum += s.sum;
+      m.sum_squared += s.sum_squared;
+    }
+    return dump(m);
+  }
+  MetricValue metric_from_state(const json::Value &state) const override {  // :333-342
+    const State s = parse(state);
+    MetricValue m;
+    m.kind = MetricValue::Histogram;
+    m.histogram.buckets = s.buckets;
+    for (const HistogramBucket &b : s.buckets) m.histogram.total_count += b.count;  // from_buckets (types.rs:130-140)
+    const double n = (double)s.total;
+    const std::optional<double> mean = s.total > 0 ? std::optional<double>(s.sum / n) : std::nullopt;  // :96-103
+    const std::optional<double> sd =
+        s.total > 1 ? std::optional<double>(HistogramArithmetic::std_dev(s.sum_squared, n, *mean)) : std::nullopt;
+    m.histogram.min = s.min;
+    m.histogram.max = s.max;
+    m.histogram.mean = mean.value_or(0.0);
+    m.histogram.std_dev = sd.value_or(0.0);
+    return m;
+  }
+
+ private:
+  struct State {  // HistogramState (:79-93)
+    std::vector<HistogramBucket> buckets;
+    double min = 0, max = 0, sum = 0, sum_squared = 0;
+    uint64_t total = 0;
+  };
+  static State parse(const json::Value &v) {
+    State s;
+    if (const json::Value *b = v.get("buckets"))
+      if (b->type == json::Value::Array)
+        for (const json::Value &e : b->arr) s.buckets.push_back({f(e, "lower_bound"), f(e, "upper_bound"), u(e, "count")});
+    s.min = f(v, "min_value");
+    s.max = f(v, "max_value");
+    s.total = u(v, "total_count");
+    s.sum = f(v, "sum");
+    s.sum_squared = f(v, "sum_squared");
+    return s;
+  }
+  static json::Value dump(const State &s) {
+    json::Value buckets;
+    buckets.type = json::Value::Array;
+    for (const HistogramBucket &b : s.buckets)
+      buckets.arr.push_back(jobj({{"lower_bound", jnum(b.lower_bound)}, {"upper_bound", jnum(b.upper_bound)},
+                                  {"count", jcount(b.count)}}));
+    return jobj({{"buckets", buckets}, {"min_value", jnum(s.min)}, {"max_value", jnum(s.max)},
+                 {"total_count", jcount(s.total)}, {"sum", jnum(s.sum)}, {"sum_squared", jnum(s.sum_squared)}});
+  }
+  uint64_t buckets_;
+  bool strict_types_;
+};
+
 struct Handles {
   tgx_plan *plan = nullptr;
   tgx_state *state = nullptr;
@@ -601,6 +751,8 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
       throw TermError{TermError::Internal, "mutual_information needs column1 and column2"};
     return std::make_shared<MutualInformationAnalyzer>(v.get_str("column1"), v.get_str("column2"), v.get_u64("bins", 10));
   }
+  if (t == "histogram")
+    return std::make_shared<HistogramAnalyzer>(col(), v.get_u64("num_buckets", 10), v.get_bool("strict_reference_types", true));
   throw TermError{TermError::Internal, "unknown analyzer type '" + t + "'"};
 }
 
@@ -679,15 +831,19 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
   Handles h;
   std::vector<tgx_result> results;
   std::optional<std::string> run_error;
-  // `binnings`: the follow-up pass -- spec i is a JOINT_BINS check in its count phase
+  // `follow_ups`: the follow-up pass -- spec i is a two-phase check that these parameters put into its count phase
   auto pass = [&](Handles &hh, size_t max_rows, tgx_status *status,
-                  const std::vector<tgx_joint_binning> *binnings = nullptr) -> std::optional<std::string> {
+                  const std::vector<FollowUp> *follow_ups = nullptr) -> std::optional<std::string> {
     tgx_error err;
     memset(&err, 0, sizeof(err));
     tgx_status s = tgx_init(nullptr, &err);
     if (s == TGX_OK) s = tgx_plan_create(specs.data(), specs.size(), &hh.plan, &err);
-    for (size_t i = 0; s == TGX_OK && binnings && i < binnings->size(); i++)
-      s = tgx_plan_set_joint_binning(hh.plan, i, &(*binnings)[i], &err);
+    for (size_t i = 0; s == TGX_OK && follow_ups && i < follow_ups->size(); i++) {
+      const FollowUp &fu = (*follow_ups)[i];
+      s = specs[i].kind == TGX_CHECK_HISTOGRAM
+              ? tgx_plan_set_histogram_edges(hh.plan, i, fu.edges.data(), (uint32_t)(fu.edges.size() - 1), &err)
+              : tgx_plan_set_joint_binning(hh.plan, i, &fu.binning, &err);
+    }
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
     for (size_t b = 0; s == TGX_OK && b < table->batches.size(); b++) {
@@ -748,28 +904,33 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
   // The second pass (analyzers.h, Analyzer::follow_up): the analyzers whose first-pass results are in say what their
   // follow-up request is; all of those run as ONE more pass over the table.  A run without such an analyzer makes one pass.
   struct Followed {
-    tgx_joint_range range;
+    FirstPass first;
     bool counted = false;
-    JointCounts counts;
+    SecondPass second;
   };
   std::vector<Followed> followed(analyzers_.size());
   if (!run_error && h.state) {
     std::vector<size_t> owners;
-    std::vector<tgx_joint_binning> binnings;
+    std::vector<FollowUp> follow_ups;
     std::vector<tgx_check_spec> first_specs = specs;
     for (size_t a = 0; a < analyzers_.size(); a++) {
       if (!analyzers_[a]->two_pass() || planned[a].error || planned[a].spec_index.empty()) continue;
       tgx_error err;
       memset(&err, 0, sizeof(err));
-      const tgx_status s = tgx_joint_range_get(h.plan, h.state, planned[a].spec_index[0], &followed[a].range, &err);
+      FirstPass &first = followed[a].first;
+      first.kind = specs[planned[a].spec_index[0]].kind;
+      first.column_types = planned[a].column_types;
+      const tgx_status s = first.kind == TGX_CHECK_HISTOGRAM
+                               ? tgx_histogram_range_get(h.plan, h.state, planned[a].spec_index[0], &first.histogram, &err)
+                               : tgx_joint_range_get(h.plan, h.state, planned[a].spec_index[0], &first.joint, &err);
       if (s != TGX_OK) {
         planned[a].error = AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg).text;
         continue;
       }
       try {
-        if (const std::optional<tgx_joint_binning> b = analyzers_[a]->follow_up(followed[a].range)) {
+        if (std::optional<FollowUp> fu = analyzers_[a]->follow_up(first)) {
           owners.push_back(a);
-          binnings.push_back(*b);
+          follow_ups.push_back(std::move(*fu));
         }
       } catch (const AnalyzerError &e) {
         planned[a].error = e.text;
@@ -781,18 +942,26 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       Handles second;
       tgx_status status = TGX_OK;
       const std::vector<tgx_result> first_results = results;
-      std::optional<std::string> second_error = pass(second, SIZE_MAX, &status, &binnings);
+      std::optional<std::string> second_error = pass(second, SIZE_MAX, &status, &follow_ups);
       results = first_results;
       for (size_t k = 0; k < owners.size(); k++) {
         Followed &fo = followed[owners[k]];
         tgx_error err;
         memset(&err, 0, sizeof(err));
         if (!second_error) {
-          uint64_t n_cells = 0;
-          fo.counts.bins = binnings[k].bins;
-          fo.counts.cells.assign((size_t)(binnings[k].bins + 1) * (binnings[k].bins + 1), 0);
-          const tgx_status s = tgx_joint_counts(second.plan, second.state, k, fo.counts.cells.data(),
-                                                fo.counts.cells.size(), &n_cells, &fo.counts.out_of_range, &err);
+          tgx_status s;
+          if (fo.first.kind == TGX_CHECK_HISTOGRAM) {
+            fo.second.buckets.assign(follow_ups[k].edges.size() - 1, 0);
+            s = tgx_histogram_counts(second.plan, second.state, k, fo.second.buckets.data(), fo.second.buckets.size(),
+                                     nullptr, nullptr, &err);
+          } else {
+            JointCounts &jc = fo.second.joint;
+            uint64_t n_cells = 0;
+            jc.bins = follow_ups[k].binning.bins;
+            jc.cells.assign((size_t)(jc.bins + 1) * (jc.bins + 1), 0);
+            s = tgx_joint_counts(second.plan, second.state, k, jc.cells.data(), jc.cells.size(), &n_cells,
+                                 &jc.out_of_range, &err);
+          }
           if (s != TGX_OK) second_error = AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg).text;
         }
         if (second_error)
@@ -811,7 +980,7 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
         std::vector<const tgx_result *> r;
         for (size_t si : planned[a].spec_index) r.push_back(&results[si]);
         json::Value st = an.two_pass()
-                             ? an.state_from_follow_up(followed[a].range, followed[a].counted ? &followed[a].counts : nullptr)
+                             ? an.state_from_follow_up(followed[a].first, followed[a].counted ? &followed[a].second : nullptr)
                              : an.state_from_results(r, planned[a].column_types);
         MetricValue m = an.metric_from_state(st);
         out.states.push_back({an.metric_key(), st});

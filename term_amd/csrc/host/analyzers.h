@@ -18,11 +18,21 @@
 namespace term_guard {
 
 // TG/analyzers/types.rs:13-35 (serde: {"type": "Double", "value": 0.8})
+struct HistogramBucket {  // types.rs:158-169
+  double lower_bound = 0, upper_bound = 0;
+  uint64_t count = 0;
+};
+struct MetricDistribution {  // types.rs:95-157; the statistics are Options there (null when absent)
+  std::vector<HistogramBucket> buckets;
+  uint64_t total_count = 0;
+  std::optional<double> min, max, mean, std_dev;
+};
 struct MetricValue {
-  enum Kind { Double, Long, Map } kind = Double;
+  enum Kind { Double, Long, Map, Histogram } kind = Double;
   double d = 0;
   int64_t l = 0;
   std::vector<std::pair<std::string, MetricValue>> map;  // insertion ordered (the reference's HashMap is unordered)
+  MetricDistribution histogram;
   static MetricValue of_double(double v) {
     MetricValue m;
     m.kind = Double;
@@ -48,11 +58,26 @@ struct AnalyzerError {
   static AnalyzerError custom(const std::string &m) { return {m}; }
 };
 
-// what a two-pass analyzer is handed once both passes are through (AnalysisRunner::run)
+// The two passes of a two-pass analyzer (AnalysisRunner::run).  Its plan()[0] is ONE request of a two-phase check kind
+// -- TGX_CHECK_JOINT_BINS or TGX_CHECK_HISTOGRAM -- and the members that belong to that kind are the ones in use.
 struct JointCounts {
   uint32_t bins = 0;
   std::vector<uint64_t> cells;  // (bins + 1)^2, row-major (tgx_joint_counts)
   uint64_t out_of_range = 0;
+};
+struct FirstPass {  // what the request's range phase found
+  int kind = 0;                   // the kind of plan()[0]
+  std::vector<int> column_types;  // tgx_type of columns() in order
+  tgx_joint_range joint = {};
+  tgx_histogram_range histogram = {};
+};
+struct FollowUp {  // the parameters that put the request into its count phase
+  tgx_joint_binning binning = {};  // JOINT_BINS (tgx_plan_set_joint_binning)
+  std::vector<double> edges;       // HISTOGRAM (tgx_plan_set_histogram_edges): buckets + 1
+};
+struct SecondPass {  // what the request's count phase found
+  JointCounts joint;
+  std::vector<uint64_t> buckets;  // HISTOGRAM (tgx_histogram_counts)
 };
 
 class Analyzer {
@@ -68,14 +93,15 @@ class Analyzer {
   virtual json::Value state_from_results(const std::vector<const tgx_result *> &r,
                                          const std::vector<int> &column_types) const = 0;
   // A SECOND PASS over the table, for aggregates whose parameters depend on the first pass's results (bin edges from
-  // the table's MIN / MAX: the reference's MutualInformationAnalyzer runs two queries, mutual_information.rs:143-248).
-  // An analyzer that overrides follow_up() has ONE TGX_CHECK_JOINT_BINS request as plan()[0]; once the first pass is
-  // in, the runner hands it that request's range and gets the binning of the follow-up request back (nullopt: no rows,
-  // no second pass; throws AnalyzerError when the range has no binning), runs all follow-up requests as one more fused
-  // pass and builds the state with state_from_follow_up (`counts` == nullptr when there was no second pass).
+  // the table's MIN / MAX: the reference's MutualInformationAnalyzer and HistogramAnalyzer run two queries,
+  // mutual_information.rs:143-248, histogram.rs:184-330).  An analyzer that overrides follow_up() has ONE request of a
+  // two-phase kind as plan()[0]; once the first pass is in, the runner hands it that request's range and gets the
+  // parameters of the follow-up request back (nullopt: no rows, no second pass; throws AnalyzerError when the range
+  // has none), runs ALL follow-up requests of the run as one more fused pass and builds the state with
+  // state_from_follow_up (the SecondPass is nullptr when there was no second pass).
   virtual bool two_pass() const { return false; }
-  virtual std::optional<tgx_joint_binning> follow_up(const tgx_joint_range &) const { return std::nullopt; }
-  virtual json::Value state_from_follow_up(const tgx_joint_range &, const JointCounts *) const { return json::Value(); }
+  virtual std::optional<FollowUp> follow_up(const FirstPass &) const { return std::nullopt; }
+  virtual json::Value state_from_follow_up(const FirstPass &, const SecondPass *) const { return json::Value(); }
   virtual json::Value merge_states(const std::vector<json::Value> &states) const = 0;      // AnalyzerState::merge
   virtual MetricValue metric_from_state(const json::Value &state) const = 0;              // throws AnalyzerError
 };

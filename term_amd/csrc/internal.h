@@ -208,6 +208,13 @@ struct TemporalTask {
   uint32_t flags;  // TGX_TEMPORAL_*
   TemporalParams params;
 };
+// TGX_CHECK_HISTOGRAM (histogram_device.cpp): one task per spec; `counted` once tgx_plan_set_histogram_edges was called
+struct HistTask {
+  int column;
+  bool counted = false;
+  std::vector<double> edges;  // count phase: buckets + 1
+  uint32_t buckets() const { return counted ? (uint32_t)edges.size() - 1 : 0; }
+};
 
 enum class Source { kScan, kCount };
 
@@ -231,12 +238,14 @@ struct tgx_plan {
   std::vector<tgx::HllTask> hll;
   std::vector<tgx::JointTask> joint;
   std::vector<tgx::TemporalTask> temporal;
+  std::vector<tgx::HistTask> hist;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
   std::vector<char> key_column;  // a single-column DISTINCT check reads it (range tracking of coalesced HOST batches)
   std::vector<char> joint_on;    // a JOINT_BINS check reads it (numeric columns only: strings are TGX_UNSUPPORTED)
   std::vector<char> temporal_on; // a TEMPORAL check reads it (Int64-shaped columns only)
+  std::vector<char> hist_on;     // a HISTOGRAM check reads it (numeric columns only, as JOINT_BINS)
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
   // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
@@ -637,6 +646,7 @@ struct tgx_state {
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
   void *joint = nullptr;  // tgx::JointState (jointbins_device.cpp)
   void *temporal = nullptr;  // tgx::TemporalState (temporal_device.cpp)
+  void *hist = nullptr;  // tgx::HistState (histogram_device.cpp)
 
   tgx::Coalescer coalesce;
   std::vector<tgx::DevBuf> parked;  // buffers replaced while the stream may still read them; freed once it has drained
@@ -674,7 +684,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

@@ -194,6 +194,31 @@ struct TemporalLaunch {
   unsigned long long *counters[kMaxTemporalPerLaunch];
 };
 
+// Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
+// ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
+// Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.
+struct HistRangeAcc {
+  int64_t n, non_finite;
+  double min, max;          // identities: +inf / -inf
+  double sum, sum_squared;  // plain sums of x and of the rounded squares x * x
+};
+// Count phase: the task's `buckets + 1` edges in device memory; its global counters are
+// [buckets][kHistElse][kHistNonFinite] 64-bit words.
+constexpr uint32_t kHistMaxBuckets = 1000;
+constexpr int kHistBlock = 512;  // threads of a workgroup of the two kernels
+constexpr int kMaxHistPerLaunch = 8;
+struct HistLaunch {
+  ComomentColDesc cols[kMaxHistPerLaunch];
+  const double *edges[kMaxHistPerLaunch];           // count phase
+  uint32_t buckets[kMaxHistPerLaunch];              // count phase
+  unsigned long long *counters[kMaxHistPerLaunch];  // count phase: the task's global counters
+  int32_t acc_index[kMaxHistPerLaunch];             // range phase: the task's HistRangeAcc
+};
+// dynamic LDS of a count-phase workgroup: the edges, then 32-bit bucket counters
+__host__ __device__ inline size_t hist_lds_bytes(uint32_t buckets) {
+  return (size_t)(buckets + 1) * sizeof(double) + (size_t)buckets * sizeof(unsigned int);
+}
+
 // One (column, batch) window of the library-side batch coalescing (kernels/gather.hip): where the window lives and
 // where it lands in the coalesced column.  A table of these is uploaded per flush; one workgroup per entry.
 struct GatherSeg {

@@ -315,6 +315,12 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
+      case TGX_CHECK_HISTOGRAM: {
+        int slot = -1;
+        TGX_TRY(hist_plan_add(plan.get(), (int)i, &slot, err));
+        plan->bind[i].slot = slot;
+        break;
+      }
       case TGX_CHECK_SPEARMAN: {
         max_col = std::max(max_col, sp.column2);
         int slot = -1;
@@ -372,6 +378,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     P->stats_on.assign(P->n_columns_needed, 0);
     P->joint_on.assign(P->n_columns_needed, 0);
     P->temporal_on.assign(P->n_columns_needed, 0);
+    P->hist_on.assign(P->n_columns_needed, 0);
     for (auto &t : P->distinct)
       if (t.tuple.empty() && !t.approx_only) P->key_column[t.column] = 1;
     // (by what was ASKED: a key column has a scan task of its own for the range decisions of its key set)
@@ -399,6 +406,8 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     for (auto &t : P->temporal)
       for (int c : {t.column, t.column2})
         if (c >= 0) P->used[c] = P->reads_values[c] = P->temporal_on[c] = 1;
+    for (auto &t : P->hist)
+      P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->stats_on[t.column] = P->hist_on[t.column] = 1;
     regex_mark_used(P, P->used);
     std::vector<char> sp_used(P->n_columns_needed, 0), sp_vals(P->n_columns_needed, 0);
     spearman_mark_used(P, sp_used, sp_vals);
@@ -535,6 +544,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   spearman_state_init(st);
   joint_state_init(st);
   temporal_state_init(st);
+  hist_state_init(st);
 }
 
 // one launch for all the small accumulators of a state (fresh, or reset): the scan accumulators to their identities,
@@ -636,6 +646,7 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   spearman_state_free(st);
   joint_state_free(st);
   temporal_state_free(st);
+  hist_state_free(st);
   coalesce_drop(st);  // (copy threads that are still filling an arena let go of it first)
   for (int k = 0; k < 2; k++) {
     if (st->arena_event[k]) (void)hipEventDestroy(st->arena_event[k]);
@@ -724,6 +735,7 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   spearman_state_reset(st);
   TGX_TRY(joint_state_reset(st, err));
   TGX_TRY(temporal_state_reset(st, err));
+  TGX_TRY(hist_state_reset(st, err));
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
   st->hll_mode.assign(plan->hll.size(), 0);
   if (st->device_ready && st->d_hll.p)
@@ -1113,6 +1125,9 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
         break;
       case TGX_CHECK_TEMPORAL:
         TGX_TRY(temporal_fill_result(st, b.slot, r, err));
+        break;
+      case TGX_CHECK_HISTOGRAM:
+        TGX_TRY(hist_fill_result(st, b.slot, r, err));
         break;
       default:
         break;

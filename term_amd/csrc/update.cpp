@@ -254,6 +254,8 @@ tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column
                   c.type == TGX_BOOL ? "Boolean" : "UInt64");
     if (plan->joint_on[i] && !is_numeric(c.type) && !is_widened(c.type))
       return fail(err, TGX_UNSUPPORTED, "column %d: JOINT_BINS takes numeric columns (type %d)", i, c.type);
+    if (plan->hist_on[i] && !is_numeric(c.type) && !is_widened(c.type))
+      return fail(err, TGX_UNSUPPORTED, "column %d: HISTOGRAM takes numeric columns (type %d)", i, c.type);
     if (plan->temporal_on[i] && c.type != TGX_INT64)
       return fail(err, TGX_UNSUPPORTED, "column %d: TEMPORAL takes Int64-shaped columns (type %d)", i, c.type);
     if (c.mem != TGX_MEM_HOST && c.mem != TGX_MEM_DEVICE)
@@ -937,6 +939,7 @@ tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *co
     TGX_TRY(unfused_comoments(plan, st, dev, nrows, f, err));
     TGX_TRY(joint_update(st, dev, nrows, err));
     TGX_TRY(temporal_update(st, dev, nrows, err));
+    TGX_TRY(hist_update(st, dev, nrows, err));
     TGX_TRY(late_key_sets(plan, st, dev, columns, f, err));
     TGX_TRY(sketches(plan, st, dev, columns, f, err));
   }

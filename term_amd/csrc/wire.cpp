@@ -65,6 +65,7 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
   // (behind everything else, and only for plans with such checks: blobs of every other plan keep their bytes)
   TGX_TRY(joint_serialize(st, w, err));
   TGX_TRY(temporal_serialize(st, w, err));
+  TGX_TRY(hist_serialize(st, w, err));
   *len = w.len;
   if (buf && w.len > cap) return fail(err, TGX_INVALID_ARGUMENT, "buffer too small: need %zu bytes", w.len);
   return TGX_OK;
@@ -158,6 +159,7 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
     }
     if (r.ok) TGX_TRY(joint_deserialize(st.get(), r, err));
     if (r.ok) TGX_TRY(temporal_deserialize(st.get(), r, err));
+    if (r.ok) TGX_TRY(hist_deserialize(st.get(), r, err));
   }
   if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
   *out = st.release();

@@ -730,7 +730,7 @@ class _Analyzer:
 
     def metric_key(self):
         t = self.spec["type"]
-        if t in ("size", "standard_deviation"):  # standard_deviation.rs does not override metric_key
+        if t in ("size", "standard_deviation", "histogram"):  # (these analyzers do not override metric_key)
             return t
         if t == "correlation":
             return "correlation_%s_%s_%s" % (self.spec.get("method", "pearson"), self.spec["column1"], self.spec["column2"])
@@ -782,6 +782,17 @@ def MutualInformationAnalyzer(column1, column2, bins=10):
     """TG/analyzers/advanced/mutual_information.rs, numeric x numeric pairs: two passes on the device (the range of
     both columns, then the joint bin counts); `bins` = max(bins, 2), at most JOINT_MAX_BINS (include/tgx.h)"""
     return _Analyzer({"type": "mutual_information", "column1": column1, "column2": column2, "bins": max(int(bins), 2)})
+
+
+def HistogramAnalyzer(column, num_buckets=10, strict_reference_types=True):
+    """TG/analyzers/advanced/histogram.rs: two passes on the device (MIN / MAX / COUNT / SUM / SUM of squares, then the
+    counts of `num_buckets` equal-width buckets, clamped to 1..1000); the metric is a MetricValue of type "Histogram".
+    The reference reads MIN as Float64 only, so a column of another type is the analyzer's error unless
+    `strict_reference_types` is off (then it runs CAST AS DOUBLE)"""
+    spec = {"type": "histogram", "column": column, "num_buckets": min(max(int(num_buckets), 1), _lib.HISTOGRAM_MAX_BUCKETS)}
+    if not strict_reference_types:
+        spec["strict_reference_types"] = False
+    return _Analyzer(spec)
 
 
 class AnalyzerContext:

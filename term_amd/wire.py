@@ -32,6 +32,13 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                     u64 seen, live, passed }                                      travel as lo / hi; fields of other modes 0)
                                live = rows that are non-NULL (both sides in order mode) and through the weekday filter,
                                passed = those of them that satisfy the predicate: passed <= live <= seen.
+    and ONLY for plans with HISTOGRAM checks, behind the TEMPORAL section if there is one:
+    u32 magic 'HIST', u32 n_hist
+    n_hist      x { u32 counted, u32 buckets; f64 edges[buckets + 1]   (the plan's edges; count phase only)
+                    i64 total, n, non_finite; f64 min, max, sum, sum_squared   (extremes +inf / -inf when n = 0 and in
+                    u64 n_words; u64 words[n_words] }                           the count phase, where the sums are 0)
+                               n_words = buckets + 1 in the count phase: the buckets, then the rows that reached the
+                               last bucket through ELSE; 0 in the range phase.  n = the sum of the buckets there.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -41,6 +48,7 @@ import struct
 MAGIC, VERSION = 0x53584754, 3
 JOINT_MAGIC = 0x42544E4A  # 'JNTB'
 TEMPORAL_MAGIC = 0x52504D54  # 'TMPR'
+HIST_MAGIC = 0x54534948  # 'HIST'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -128,12 +136,31 @@ def temporal_state(mode, flags, seen, live, passed, delta=0, ticks_per_second=0,
     return struct.pack("<iI4q3Q", mode, flags, delta, ticks_per_second, lo, hi, seen, live, passed)
 
 
-def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=()):
+def hist_range_state(total, n, non_finite=0, min=None, max=None, sum=0.0, sum_squared=0.0):
+    """a HISTOGRAM task in its range phase (extremes None: no rows)"""
+    inf = float("inf")
+    return struct.pack("<II3q4dQ", 0, 0, total, n, non_finite, inf if min is None else min, -inf if max is None else max,
+                       sum, sum_squared, 0)
+
+
+def hist_count_state(edges, total, counts, else_rows=0, non_finite=0):
+    """a HISTOGRAM task in its count phase: the plan's buckets + 1 `edges` and the bucket `counts`"""
+    buckets = len(edges) - 1
+    assert len(counts) == buckets
+    inf = float("inf")
+    words = list(counts) + [else_rows]
+    return (struct.pack("<II%dd3q4dQ" % len(edges), 1, buckets, *edges, total, sum(counts), non_finite, inf, -inf, 0.0, 0.0,
+                        len(words)) + struct.pack("<%dQ" % len(words), *words))
+
+
+def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
     tail = struct.pack("<II", JOINT_MAGIC, len(joint)) + b"".join(joint) if joint else b""
     if temporal:
         tail += struct.pack("<II", TEMPORAL_MAGIC, len(temporal)) + b"".join(temporal)
+    if hist:
+        tail += struct.pack("<II", HIST_MAGIC, len(hist)) + b"".join(hist)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
