@@ -124,3 +124,46 @@ def merge_states(states):
             for k, c in s[name].items():
                 out[name][k] = out[name].get(k, 0) + c
     return out
+
+
+# ---- the same over numpy arrays (the differential tester's tables: 400 000 rows a case) ---------------------------
+# x, y: the two columns CAST AS DOUBLE as float64 arrays; valid: rows with both sides non-NULL.  numpy's float64
+# subtract, divide and floor are the IEEE operations the walks above do one row at a time; tests/test_exact_joint.py
+# holds each of these to its walk.
+def live_rows_np(x, y, valid):
+    import numpy as np
+
+    x, y = np.asarray(x, np.float64)[valid], np.asarray(y, np.float64)[valid]
+    live = np.isfinite(x) & np.isfinite(y)
+    return x[live], y[live], int(len(x) - live.sum())
+
+
+def pair_range_np(x, y, valid):
+    a, b, non_finite = live_rows_np(x, y, valid)
+    out = dict(n=len(a), non_finite=non_finite, x_min=None, x_max=None, y_min=None, y_max=None)
+    if len(a):
+        out.update(x_min=float(a.min()), x_max=float(a.max()), y_min=float(b.min()), y_max=float(b.max()))
+    return out
+
+
+def binning_of_range(r, bins):
+    """binning_of from a pair_range"""
+    bins = max(bins, 2)
+    if r["n"] == 0:
+        return None
+    return (r["x_min"], bin_width(r["x_min"], r["x_max"], bins), r["y_min"], bin_width(r["y_min"], r["y_max"], bins), bins)
+
+
+def joint_counts_np(x, y, valid, binning):
+    import numpy as np
+
+    x0, xw, y0, yw, bins = binning
+    a, b, _ = live_rows_np(x, y, valid)
+    with np.errstate(over="ignore", invalid="ignore"):
+        fi, fj = (a - x0) / xw, (b - y0) / yw
+        inside = np.isfinite(fi) & np.isfinite(fj)
+        i, j = np.floor(fi[inside]), np.floor(fj[inside])
+    ok = (i >= 0) & (i <= bins) & (j >= 0) & (j <= bins)
+    flat = i[ok].astype(np.int64) * (bins + 1) + j[ok].astype(np.int64)
+    cells = {(int(k) // (bins + 1), int(k) % (bins + 1)): int(c) for k, c in zip(*np.unique(flat, return_counts=True))}
+    return cells, int(len(a) - ok.sum())

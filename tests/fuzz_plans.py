@@ -4,13 +4,23 @@ tools/fuzz_device.py any range).  One seed fixes everything: columns (type, shap
 how the rows are cut into tgx_update calls (one batch, ragged cuts, a stream of DataFusion-sized batches; DEVICE or
 HOST buffers; Arrow offsets), and what happens to the state before it is read (finalize / blob round trip / several
 states merged).  Bit-exact wherever the reference is (counts, MIN / MAX, integer sums, DISTINCT, HyperLogLog
-registers -> estimate); 1e-6 relative for floating-point aggregates (north star)."""
+registers -> estimate); 1e-6 relative for floating-point aggregates (north star).
+
+The two-phase kinds (HISTOGRAM, JOINT_BINS) make a case run TWICE: pass one has their specs in the range phase, pass
+two is a fresh plan with edges / binnings set -- derived from the exact references' ranges, never from what the device
+said in pass one -- fed the same table through the same batching and state sequence.  TEMPORAL is complete in pass
+one.  These three are compared with tests/exact_histogram.py, exact_joint.py and exact_temporal.py: every count, extreme
+and counter for equality, the histogram's two plain double sums within exact_histogram.sum_bounds (or by its overflow
+rule, sum_rules).  tests/test_fuzz_cases.py tests this tester without a device."""
 import math
 import sys
 
 import numpy as np
 
+import exact_histogram as EH
 import exact_hll as H
+import exact_joint as EJ
+import exact_temporal as ET
 import exact_quantiles as Q
 import exact_ranks as R
 import exact_widening as W
@@ -342,12 +352,70 @@ class Case:
                 self.present[ci] = np.uint64
             elif fits:
                 self.present[ci] = fits[int(rng5.integers(0, len(fits)))]
+        self.draw_two_phase_and_temporal(np.random.default_rng([seed, 8]))
+
+    HISTOGRAM_BUCKETS = [1, 2, 5, 10, 100, 999, 1000]
+    JOINT_BINS = [2, 5, 10, 127]
+    NEW_KINDS_MAX_ROWS = 400_000  # (the references walk the table in Python and numpy; the limit of the tuples)
+
+    def draw_two_phase_and_temporal(self, rng8):
+        """HISTOGRAM, JOINT_BINS and TEMPORAL checks, from a stream of their own: every earlier draw of the seed -- rng5's
+        presentations above included, which saw the older expectations only -- is what it was.  A column presented as
+        UInt64 or Boolean is TGX_UNSUPPORTED for the two-phase kinds and is not drawn for them (Int8 .. UInt32 are
+        widened and stay); a column a TEMPORAL check reads arrives as Int64 whatever rng5 drew for it."""
+        self.phase, self.pass_two, self._cache = 1, {}, {}
+        n = self.n
+        if n > self.NEW_KINDS_MAX_ROWS:
+            return
+        numeric = [ci for ci, c in enumerate(self.cols) if c[0] in ("i", "f", "i32", "f32")
+                   and not (self.present[ci] == "bool" or self.present[ci] is np.uint64)]
+        ints = [ci for ci, c in enumerate(self.cols) if c[0] == "i"]
+        if numeric and rng8.random() < 0.45:
+            for _ in range(1 + int(rng8.random() < 0.3)):
+                ci = numeric[int(rng8.integers(0, len(numeric)))]
+                buckets = int(rng8.choice(self.HISTOGRAM_BUCKETS))
+                edges = str(rng8.choice(["exact", "shifted", "uneven"]))
+                # (the last field seeds the sample of the uneven edges, drawn when pass two knows the finite values)
+                self.add(spec(T.HISTOGRAM, ci), ("histogram", ci, buckets, edges, int(rng8.integers(0, 2**31))))
+        if len(numeric) >= 2 and rng8.random() < 0.5:
+            cx, cy = (int(c) for c in rng8.permutation(numeric)[:2])
+            self.add(spec(T.JOINT_BINS, cx, column2=cy),
+                     ("joint", cx, cy, int(rng8.choice(self.JOINT_BINS)), bool(rng8.integers(0, 2))))
+        if ints and rng8.random() < 0.5:
+            modes = ["time_of_day", "range"] + (["order", "order"] if len(ints) >= 2 else [])
+            mode = modes[int(rng8.integers(0, len(modes)))]
+            cols = [int(c) for c in rng8.permutation(ints)]
+            ci, cj = cols[0], (cols[1] if mode == "order" else -1)
+            keep, weekdays = bool(rng8.integers(0, 2)), bool(rng8.integers(0, 2))
+            delta = [0, 1, -1, int(rng8.integers(-(2**39), 2**39)), ET.I64_MAX, ET.I64_MIN][int(rng8.integers(0, 6))]
+            tps = [1, 10**3, 10**6, 10**9][int(rng8.integers(0, 4))]
+            tod_lo, tod_hi = sorted(int(x) for x in rng8.integers(0, 86400 * tps, size=2))
+            vals = self.cols[ci][1]
+            lo, hi = ((int(vals[int(rng8.integers(0, n))]) if n and rng8.random() < 0.7 else None) for _ in range(2))
+            flags = (T.TEMPORAL_KEEP_NULLS if keep else 0) | (T.TEMPORAL_WEEKDAYS_ONLY if weekdays and mode == "time_of_day" else 0)
+            if mode == "order":
+                params = dict(mode=T.TEMPORAL_ORDER, flags=flags, delta=delta)
+            elif mode == "time_of_day":
+                params = dict(mode=T.TEMPORAL_TIME_OF_DAY, flags=flags, ticks_per_second=tps, tod_lo=tod_lo, tod_hi=tod_hi)
+            else:
+                params = dict(mode=T.TEMPORAL_RANGE, flags=flags)
+                if lo is not None:
+                    params["lo"] = lo
+                if hi is not None:
+                    params["hi"] = hi
+            self.add(spec(T.TEMPORAL, ci, column2=cj), ("temporal", ci, cj, mode, params))
+        for e in self.expect:
+            if e[0] == "temporal":
+                for ci in self.columns_of_expect(e):
+                    self.present[ci] = None
+            if e[0] in ("histogram", "joint"):
+                assert not any(self.present[ci] == "bool" or self.present[ci] is np.uint64 for ci in self.columns_of_expect(e))
 
     @staticmethod
     def columns_of_expect(e):
         if e[0] == "tuple":
             return tuple(e[1])
-        if e[0] in ("comoments", "spearman"):
+        if e[0] in ("comoments", "spearman", "joint") or (e[0] == "temporal" and e[2] >= 0):
             return (e[1], e[2])
         return (e[1],)
 
@@ -358,6 +426,7 @@ class Case:
         c = copy.copy(self)
         c.n = m
         c.cols = [(k, (v[:m + 1] if k == "s" else v[:m]), vb, mask[:m], extra) for k, v, vb, mask, extra in self.cols]
+        c._cache = {}  # (the references of the prefix; pass two's edges and binnings stay the whole table's)
         return c
 
     def tuple_columns(self):
@@ -371,8 +440,9 @@ class Case:
     def describe(self):
         cols = ", ".join("%s%s/nulls=%d" % (c[0], "" if p is None else "as" + (p if isinstance(p, str) else p.__name__),
                                             int((~c[3]).sum())) for c, p in zip(self.cols, self.present))
-        return "seed %d: n=%d cols=[%s] checks=%s batching=%s(%d) buffers=%s after=%s env=%s" % (
-            self.seed, self.n, cols, [e[0] for e in self.expect], self.mode, len(self.cuts) - 1, self.device,
+        checks = [e[0] if e[0] not in ("histogram", "joint", "temporal") else "%s%r" % (e[0], e[1:]) for e in self.expect]
+        return "seed %d: n=%d cols=[%s] checks=%s pass=%d batching=%s(%d) buffers=%s after=%s env=%s" % (
+            self.seed, self.n, cols, checks, self.phase, self.mode, len(self.cuts) - 1, self.device,
             self.after + ("" if self.seq == "plain" else "/" + self.seq) + (" kept" if self.retain else "") +
             (" exact-keys" if self.exact_keys else ""), self.env)
 
@@ -404,6 +474,7 @@ class Case:
     def run_device_inner(self):
         T.init()
         plan = T.Plan(self.specs)
+        self.set_parameters(plan)
         if self.after == "ranks":
             from test_gpu_distributed_sim import _run_ranks
 
@@ -464,6 +535,167 @@ class Case:
         del keep
         return [(res, st)]
 
+    # ---- the two-phase kinds and TEMPORAL: parameters, references ----
+    def set_parameters(self, plan):
+        """what goes into a plan before its first state: TEMPORAL parameters, and in pass two the edges and binnings"""
+        for si, e in enumerate(self.expect):
+            if e[0] == "temporal":
+                plan.set_temporal(si, **e[4])
+            elif self.phase == 2 and e[0] == "histogram":
+                plan.set_histogram_edges(si, self.pass_two[si])
+            elif self.phase == 2 and e[0] == "joint":
+                b = self.pass_two[si]
+                if all(math.isfinite(v) for v in b[:4]) and b[1] > 0.0 and b[3] > 0.0:
+                    plan.set_joint_binning(si, *b)
+                    continue
+                # a range without a finite positive width: refused, as include/tgx.h promises; the spec stays in its
+                # range phase and is compared as in pass one
+                try:
+                    plan.set_joint_binning(si, *b)
+                except T.TgxError as err:
+                    assert "TGX_INVALID_ARGUMENT" in str(err), err
+                else:
+                    raise AssertionError("%r: set_joint_binning took %r" % (e, b))
+                self.pass_two[si] = None
+
+    def has_two_phases(self):
+        return any(e[0] in ("histogram", "joint") for e in self.expect)
+
+    def enter_pass_two(self):
+        """edges and binnings for every HISTOGRAM / JOINT_BINS spec, from the exact references' ranges of the whole table"""
+        for si, e in enumerate(self.expect):
+            if e[0] == "histogram":
+                self.pass_two[si] = self.histogram_edges(e)
+            elif e[0] == "joint":
+                b = EJ.binning_of_range(self.reference(("joint_range", e[1], e[2])), e[3])
+                if b is None:  # no live row: counts over nothing
+                    b = (0.0, 1.0, 0.0, 1.0, e[3])
+                elif e[4]:  # the origin half a width up: the rows of the lowest half bin fall outside
+                    b = (b[0] + b[1] / 2, b[1], b[2] + b[3] / 2, b[3], b[4])
+                self.pass_two[si] = b
+        self.phase = 2
+
+    def histogram_edges(self, e):
+        _, ci, buckets, how, sample_seed = e
+        r = self.reference(("histogram_range", ci))
+        if r["n"] == 0:
+            return [float(i) for i in range(buckets + 1)]  # 0.0 .. float(buckets)
+        exact = EH.edges_of(r["min"], r["max"], buckets)
+        assert all(math.isfinite(x) for x in exact), (e, r["min"], r["max"])
+        if how == "shifted":  # another table's edges: rows below the first edge take ELSE
+            w = EH.bucket_width(r["min"], r["max"], buckets)
+            lo, w = r["min"] + 0.37 * w, w * 1.9
+            edges = [lo + float(i) * w for i in range(buckets + 1)]
+            return edges if all(math.isfinite(x) for x in edges) else exact  # (1e308 in the column: the stretch overflows)
+        if how == "uneven":  # a sorted sample of the column's finite values, repeats included: the fallback search
+            d = self.doubles_of(ci)[self.cols[ci][3]]
+            d = d[np.isfinite(d)]
+            return sorted(np.random.default_rng(sample_seed).choice(d, size=buckets + 1).tolist())
+        return exact
+
+    def wide_of(self, ci):
+        """the 8-byte values the device widens column ci to (exact_widening.py: nothing converted by a float unit)"""
+        kind, vals = self.cols[ci][0], self.cols[ci][1]
+        return (vals if kind in ("i", "f", "s") else W.widen_int(vals, "int32") if kind == "i32"
+                else W.widen_f32_bits(vals).view(np.float64))
+
+    def doubles_of(self, ci):
+        """column ci CAST AS DOUBLE (an Int64 beyond 2^53 rounds to nearest even)"""
+        return self.wide_of(ci).astype(np.float64)
+
+    def reference(self, key):
+        """the exact modules' answers for this case's table, computed once per table"""
+        if key not in self._cache:
+            what = key[0]
+            if what == "histogram_range":
+                ci = key[1]
+                self._cache[key] = EH.value_range_np(self.doubles_of(ci), self.cols[ci][3])
+            elif what == "histogram_counts":
+                ci = key[1]
+                self._cache[key] = EH.counts_of_np(self.doubles_of(ci), self.cols[ci][3], list(key[2]))
+            elif what == "joint_range":
+                self._cache[key] = EJ.pair_range_np(self.doubles_of(key[1]), self.doubles_of(key[2]),
+                                                    self.cols[key[1]][3] & self.cols[key[2]][3])
+            elif what == "joint_counts":
+                self._cache[key] = EJ.joint_counts_np(self.doubles_of(key[1]), self.doubles_of(key[2]),
+                                                      self.cols[key[1]][3] & self.cols[key[2]][3], key[3])
+            elif what == "both_zeros":  # does the column hold +0.0 AND -0.0 among the rows `key[2]` names?
+                d = self.doubles_of(key[1])[self.live_mask(key[2])]
+                z = d[d == 0.0]
+                self._cache[key] = bool(len(z)) and bool(np.signbit(z).any()) and not bool(np.signbit(z).all())
+        return self._cache[key]
+
+    def live_mask(self, cols):
+        m = np.ones(self.n, bool)
+        for ci in cols:
+            m &= self.cols[ci][3] & np.isfinite(self.doubles_of(ci))
+        return m
+
+    def same_extreme(self, e, name, got, want, ci, live_cols):
+        """an extreme bit for bit (float.hex: -0.0 is not 0.0).  Only where +0.0 and -0.0 both occur among the rows it
+        runs over and it IS zero, either zero stands: they compare equal, and no MIN / MAX is pinned on which it keeps"""
+        if want is None:
+            assert math.isnan(got), (e, name, got)
+        elif want == 0.0 and got == 0.0 and self.reference(("both_zeros", ci, tuple(live_cols))):
+            pass
+        else:
+            assert float(got).hex() == float(want).hex(), (e, name, got, want)
+
+    def check_histogram(self, e, si, r, st):
+        _, ci, buckets, _, _ = e
+        want = self.reference(("histogram_range", ci))
+        assert (r.total, r.non_null) == (want["total"], want["n"] + want["non_finite"]), (e, r.total, r.non_null, want["total"])
+        got = st.histogram_range(si)
+        for k in ("total", "nulls", "non_finite"):
+            assert got[k] == want[k], (e, k, got[k], want[k])
+        if self.phase == 2:
+            edges = self.pass_two[si]
+            counts = self.reference(("histogram_counts", ci, tuple(edges)))
+            have = st.histogram_counts(si)
+            if have[0] != counts[0]:
+                bad = [(i, a, b) for i, (a, b) in enumerate(zip(have[0], counts[0])) if a != b]
+                raise AssertionError((e, "buckets (index, device, exact)", bad[:8], "edges", edges[:4], "..", edges[-2:]))
+            assert have[1:] == counts[1:], (e, "else_rows, non_finite", have[1:], counts[1:])
+            assert got["n"] == sum(counts[0]) == want["n"], (e, got["n"], want["n"])
+            return
+        assert got["n"] == want["n"], (e, "n", got["n"], want["n"])
+        for k in ("min", "max"):
+            self.same_extreme(e, k, got[k], want[k], ci, (ci,))
+        bounds, rules = EH.sum_bounds(want), EH.sum_rules(want)
+        for k, bound, rule in zip(("sum", "sum_squared"), bounds, rules):
+            why = EH.sum_failure(got[k], want[k], bound, rule)
+            assert why is None, (e, k, why)
+
+    def check_joint(self, e, si, r, st):
+        _, cx, cy, bins, _ = e
+        want = self.reference(("joint_range", cx, cy))
+        assert r.total == self.n, (e, r.total)
+        if self.phase == 2 and self.pass_two[si] is not None:
+            cells, outside = self.reference(("joint_counts", cx, cy, self.pass_two[si]))
+            have, have_outside = st.joint_counts(si)
+            dense = EJ.dense(cells, max(bins, 2))
+            if have != dense:
+                side = max(bins, 2) + 1
+                bad = [((k // side, k % side), a, b) for k, (a, b) in enumerate(zip(have, dense)) if a != b]
+                raise AssertionError((e, "cells ((i, j), device, exact)", bad[:8], "binning", self.pass_two[si], len(have)))
+            assert have_outside == outside, (e, "outside", have_outside, outside)
+            return
+        got = st.joint_range(si)
+        assert (got["total"], got["n"], got["non_finite"]) == (self.n, want["n"], want["non_finite"]), (e, got, want)
+        assert r.non_null == want["n"], (e, r.non_null, want["n"])
+        for k, ci in (("x_min", cx), ("x_max", cx), ("y_min", cy), ("y_max", cy)):
+            self.same_extreme(e, k, got[k], want[k], ci, (cx, cy))
+
+    def check_temporal(self, e, si, r, st):
+        _, ci, cj, _, params = e
+        p = dict(params)
+        mode = p.pop("mode")
+        want = ET.counts_np(mode, p, self.cols[ci][1], self.cols[cj][1] if cj >= 0 else None, self.cols[ci][3],
+                            self.cols[cj][3] if cj >= 0 else None)
+        got = tuple(st.temporal_counts(si))
+        assert got == want, (e, "seen, considered, violations", got, want)
+        assert (r.total, r.non_null, r.matches) == (want[0], want[1], want[1] - want[2]), (e, r.total, r.non_null, r.matches, want)
+
     # ---- the oracle side + comparison ----
     def key_bits(self, ci):
         """(values as the 64-bit patterns DISTINCT compares, validity) of a numeric column"""
@@ -497,6 +729,9 @@ class Case:
             what = e[0]
             if what == "tuple":
                 self.check_tuple(r, e)
+                continue
+            if what in ("histogram", "joint", "temporal"):
+                {"histogram": self.check_histogram, "joint": self.check_joint, "temporal": self.check_temporal}[what](e, si, r, st)
                 continue
             kind, vals, vb, mask, extra = self.cols[e[1]]
             wide = (vals if kind in ("i", "f", "s") else W.widen_int(vals, "int32") if kind == "i32"
@@ -647,6 +882,9 @@ def run_seed(seed, max_rows=2_600_000, host_only=False):
     case = Case(seed, max_rows, host_only)
     try:
         case.check(case.run_device())
+        if case.has_two_phases():  # the count phases: the same table through the same machinery, on a fresh plan
+            case.enter_pass_two()
+            case.check(case.run_device())
     except AssertionError as err:
         raise AssertionError("%s\n%s" % (case.describe(), err)) from None
     except T.TgxError as err:

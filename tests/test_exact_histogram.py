@@ -101,3 +101,70 @@ def test_both_walks_of_the_chain_agree():
                 counts[b] += 1
                 else_rows += e
         assert eh.counts_of_columnwise(values, edges) == (counts, else_rows, 1)
+
+
+# ---- the numpy fast paths of the differential tester, against the plain walks -----------------------------------------
+def _special_column(rng, n, pool):
+    import numpy as np
+
+    v = np.round(rng.standard_normal(n) * 10, 1)
+    m = rng.random(n) < 0.1
+    v[m] = np.array(pool, np.float64)[rng.integers(0, len(pool), int(m.sum()))]
+    valid = rng.random(n) >= 0.1
+    return v, valid, [x if ok else None for x, ok in zip(v.tolist(), valid.tolist())]
+
+
+@pytest.mark.parametrize("n", [0, 1, 7, 255, 256, 257, 5000])
+@pytest.mark.parametrize("pool", [[0.0], [float("nan"), float("inf"), -float("inf"), 0.0, -0.0, 5e-324, -5e-324, 1e308],
+                                  [1e154, -1e154, 1.5e-162, 2.0 ** -537, 2.0 ** 1023]], ids=["plain", "specials", "limits"])
+def test_numpy_range_and_counts_equal_the_walks(n, pool):
+    """value_range_np (the exact sums in segments of int64) and counts_of_np (binary search) over specials, squares
+    that overflow or underflow, repeated edges, and a last edge below the one before"""
+    import numpy as np
+
+    rng = np.random.default_rng(n)
+    v, valid, xs = _special_column(rng, n, pool)
+    r = eh.value_range(xs)
+    assert eh.value_range_np(v, valid) == r
+    if r["n"] == 0:
+        return
+    finite = v[np.isfinite(v)]
+    sample = sorted(rng.choice(finite, 12).tolist())
+    for edges in (eh.edges_of(r["min"], r["max"], 7), eh.edges_of(-3.0, 4.0, 1000), [0.0, 1.0], sample,
+                  sample[:6] + sample[5:6] * 3 + sample[6:], sample[:-1] + [sample[3]]):
+        assert eh.counts_of_np(v, valid, edges) == eh.counts_of(xs, edges) == eh.counts_of_columnwise(xs, edges)
+
+
+def test_numpy_exact_sum_of_integers_beyond_2_53():
+    import numpy as np
+
+    v = np.random.default_rng(1).integers(-2**62, 2**62, 3000).astype(np.float64)
+    assert eh.exact_sum_np(v) == sum(int(x) for x in v.tolist()) == eh.exact_sum(v.tolist())
+    assert eh.exact_sum_np(v, 2) == sum(int(x) ** 2 for x in v.tolist()) == eh.exact_sum(v.tolist(), 2)
+
+
+def test_sum_rules_and_infinite_squares():
+    """1e308: its rounded square is infinite (sum_squared must be +inf), and two of them overflow a plain sum in some
+    order (an infinity of the exact sum's sign, or within the bound); a NaN passes neither"""
+    inf, nan = math.inf, math.nan
+    r = eh.value_range([1e308, 1e308, -2.0, None, nan])
+    assert r["infinite_squares"] == 2 and r["abs_sum_squared"] == 4 and r["sum_squared"] == 2 * Fraction(1e308) ** 2 + 4
+    rule_sum, rule_sq = eh.sum_rules(r)
+    assert (rule_sum, rule_sq) == (("either", 1.0), ("infinite", 1.0))
+    bound_sum, bound_sq = eh.sum_bounds(r)
+    assert eh.sum_failure(inf, r["sum"], bound_sum, rule_sum) is None
+    assert eh.sum_failure(-inf, r["sum"], bound_sum, rule_sum) is not None
+    assert eh.sum_failure(nan, r["sum"], bound_sum, rule_sum) is not None
+    assert eh.sum_failure(1e308, r["sum"], bound_sum, rule_sum) is not None  # finite, and far outside the bound
+    assert eh.sum_failure(inf, r["sum_squared"], bound_sq, rule_sq) is None
+    assert eh.sum_failure(1e308, r["sum_squared"], bound_sq, rule_sq) is not None
+    assert eh.sum_failure(nan, r["sum_squared"], bound_sq, rule_sq) is not None
+    small = eh.value_range([1.5, -2.0, 4.0])
+    assert eh.sum_rules(small) == (("bound", 1.0), ("bound", 1.0))
+    assert eh.sum_failure(3.5, small["sum"], eh.sum_bounds(small)[0], ("bound", 1.0)) is None
+    assert eh.sum_failure(inf, small["sum"], eh.sum_bounds(small)[0], ("bound", 1.0)) is not None
+    negative = eh.value_range([-1e308, -1e308, 3.0])
+    assert eh.sum_rules(negative)[0] == ("either", -1.0)
+    # 2^1023 is where a partial sum may first pass DBL_MAX
+    assert eh.sum_rules(eh.value_range([2.0 ** 1022, 2.0 ** 1021]))[0][0] == "bound"
+    assert eh.sum_rules(eh.value_range([2.0 ** 1022, 2.0 ** 1022]))[0][0] == "either"

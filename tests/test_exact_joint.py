@@ -82,3 +82,31 @@ def test_non_finite_and_null_rows_are_left_out():
     assert cells == {(0, 0): 1} and outside == 0
     assert ej.binning_of([None], [1.0], 5) is None
     assert float(ej.mutual_information({}, 0)[0]) == 0.0
+
+
+# ---- the numpy fast paths of the differential tester, against the plain walks -----------------------------------------
+def test_numpy_range_and_counts_equal_the_walks():
+    import numpy as np
+
+    for n in (0, 1, 6, 4000):
+        rng = np.random.default_rng(n)
+        x = np.round(rng.standard_normal(n) * 10, 1)
+        m = rng.random(n) < 0.1
+        pool = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 5e-324, 1e308])
+        x[m] = pool[rng.integers(0, len(pool), int(m.sum()))]
+        y = rng.integers(-2**62, 2**62, n)
+        xv, yv = rng.random(n) >= 0.1, rng.random(n) >= 0.3
+        xs = [v if ok else None for v, ok in zip(x.tolist(), xv.tolist())]
+        ys = [v if ok else None for v, ok in zip(y.tolist(), yv.tolist())]
+        yd = y.astype(np.float64)
+        r = ej.pair_range(xs, ys)
+        assert ej.pair_range_np(x, yd, xv & yv) == r
+        for bins in (2, 5, 127):
+            b = ej.binning_of(xs, ys, bins)
+            assert ej.binning_of_range(r, bins) == b
+            if b is None:
+                continue
+            moved = (b[0] + b[1] / 2, b[1], b[2] + b[3] / 2, b[3], bins)
+            tiny = (b[0], 5e-324, b[2], b[3], bins)  # (a quotient that overflows: outside)
+            for binning in (b, moved, tiny):
+                assert ej.joint_counts_np(x, yd, xv & yv, binning) == ej.joint_counts(xs, ys, binning)

@@ -130,3 +130,28 @@ def test_reference_unit_tests_as_data():
         status, metric, message = et.verdict("before_after", considered, violations, before_col, after_col)
         assert status == case["status"] and (message is not None) == case["message_is_some"], case["source"]
         assert seen == considered == 2
+
+
+# ---- the numpy fast path of the differential tester, against the plain walk -------------------------------------------
+def test_numpy_counts_equal_the_walk():
+    import numpy as np
+
+    for n in (0, 1, 9, 3000):
+        rng = np.random.default_rng(n)
+        for make in (lambda: rng.integers(-2**62, 2**62, n), lambda: rng.integers(-10**6, 10**6, n),
+                     lambda: rng.integers(-2 * 10**18, 2 * 10**18, n)):
+            b, a = make(), make()
+            if n > 2:
+                b[0], a[0], b[1], a[1] = et.I64_MIN, et.I64_MAX, et.I64_MAX, et.I64_MIN
+            vb, va = rng.random(n) >= 0.2, rng.random(n) >= 0.2
+            for delta in (0, 1, -1, 2**39 + 5, et.I64_MAX, et.I64_MIN):
+                for flags in (0, et.KEEP_NULLS):
+                    p = dict(delta=delta, flags=flags)
+                    assert et.counts_np(et.ORDER, p, b, a, vb, va) == et.counts(et.ORDER, p, b.tolist(), a.tolist(), vb.tolist(), va.tolist())
+            for tps in et.TICKS.values():
+                for flags in (0, 1, 2, 3):
+                    p = dict(ticks_per_second=tps, tod_lo=3 * tps, tod_hi=50_000 * tps, flags=flags)
+                    assert et.counts_np(et.TIME_OF_DAY, p, b, None, vb) == et.counts(et.TIME_OF_DAY, p, b.tolist(), None, vb.tolist())
+            for p in (dict(), dict(lo=-5, flags=1), dict(hi=10**5), dict(lo=-(2**61), hi=2**61, flags=1)):
+                assert et.counts_np(et.RANGE, p, b, None, vb) == et.counts(et.RANGE, p, b.tolist(), None, vb.tolist())
+            assert et.counts_np(et.RANGE, dict(lo=0), b) == et.counts(et.RANGE, dict(lo=0), b.tolist())
