@@ -666,6 +666,12 @@ tgx_status tgx_regex_validate(const char *pattern, size_t len, uint32_t flags, t
 /* Host-side `is_match` of the compiled automaton for one value (debug / small inputs). */
 tgx_status tgx_regex_is_match(const char *pattern, size_t plen, uint32_t flags, const uint8_t *value,
                               size_t vlen, int32_t *matched, tgx_error *err);
+/* What the device's launch decides from, for one pattern: the size of the compiled automaton (states x byte classes
+ * picks the table's place: byte-indexed, in LDS, or in global memory) and its character count -- *len_min / *len_max
+ * are -1 unless the pattern is an automaton AND a count (`^C{m,n}$`).  The same compile as tgx_plan_create's; launches
+ * and allocates nothing on the device. */
+tgx_status tgx_regex_table_info(const char *pattern, size_t len, uint32_t flags, uint32_t *n_states,
+                                uint32_t *n_classes, int64_t *len_min, int64_t *len_max, tgx_error *err);
 
 /* Host-side walk of the PRODUCT automaton of up to 4 patterns -- the form in which several pattern checks of one
  * column are evaluated on the device (one walk over the value decides all of them).  Bit k of *mask: pattern k

@@ -207,6 +207,10 @@ def lib():
         L.tgx_profile_reset.argtypes = [vp]
         L.tgx_regex_validate.argtypes = [C.c_char_p, sz, C.c_uint32, E]
         L.tgx_regex_is_match.argtypes = [C.c_char_p, sz, C.c_uint32, C.c_char_p, sz, C.POINTER(C.c_int32), E]
+        L.tgx_regex_match_group.argtypes = [C.POINTER(C.c_char_p), C.POINTER(sz), C.POINTER(C.c_uint32), sz, C.c_char_p, sz,
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int32), E]
+        L.tgx_regex_table_info.argtypes = [C.c_char_p, sz, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), E]
         L.tgx_cache_stats_get.argtypes = [C.POINTER(CacheStats)]
         L.tgx_state_pending.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
         L.tgx_plan_set_joint_binning.argtypes = [vp, sz, C.POINTER(JointBinning), E]

@@ -483,6 +483,23 @@ extern "C" tgx_status tgx_regex_is_match(const char *pattern, size_t plen, uint3
   return tgx::abi_exception(err);
 }
 
+// What launch_regex decides from, for ONE pattern: the automaton's size (table class) and its character count
+// (-1, -1: none).  The same compile as the plan's; nothing is launched or allocated on the device.
+extern "C" tgx_status tgx_regex_table_info(const char *pattern, size_t len, uint32_t flags, uint32_t *n_states,
+                                           uint32_t *n_classes, int64_t *len_min, int64_t *len_max, tgx_error *err) try {
+  if ((!pattern && len) || !n_states || !n_classes || !len_min || !len_max)
+    return fail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  rx::Dfa dfa;
+  TGX_TRY(compile_checked(pattern ? pattern : "", len, flags, &dfa, err));
+  *n_states = dfa.n_states;
+  *n_classes = dfa.n_classes;
+  *len_min = dfa.len_max >= 0 ? dfa.len_min : -1;
+  *len_max = dfa.len_max >= 0 ? dfa.len_max : -1;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
 extern "C" tgx_status tgx_regex_match_group(const char *const *patterns, const size_t *pattern_lens,
                                             const uint32_t *flags, size_t n_patterns, const uint8_t *value, size_t vlen,
                                             uint32_t *mask, int32_t *grouped, tgx_error *err) try {

@@ -90,6 +90,37 @@ def test_plan_validation_needs_no_device():
     assert T.lib().tgx_plan_num_specs(p.h) == 3
 
 
+def test_regex_table_info_arguments():
+    """tgx_regex_table_info: NULL arguments and invalid patterns are told apart from an answer; nothing is written then"""
+    lib = T.lib()
+    ns, nc, lo, hi = C.c_uint32(77), C.c_uint32(77), C.c_int64(77), C.c_int64(77)
+    outs = [C.byref(ns), C.byref(nc), C.byref(lo), C.byref(hi)]
+    for k in range(4):  # each out pointer NULL in turn
+        err = _Error()
+        args = list(outs)
+        args[k] = None
+        assert lib.tgx_regex_table_info(b"a+", 2, 0, *args, C.byref(err)) == 1  # TGX_INVALID_ARGUMENT
+        assert (err.code, err.msg.decode()) == (1, "NULL argument")
+    err = _Error()
+    assert lib.tgx_regex_table_info(None, 2, 0, *outs, C.byref(err)) == 1 and err.msg.decode() == "NULL argument"
+    assert lib.tgx_regex_table_info(b"a+", 2, 0, *outs, None) == 0  # (err itself may be NULL)
+    assert (ns.value, nc.value, lo.value, hi.value) == (3, 2, -1, -1)
+    assert lib.tgx_regex_table_info(None, 0, 0, *outs, C.byref(err)) == 0  # (the empty pattern, as tgx_regex_validate takes it)
+    before = (ns.value, nc.value, lo.value, hi.value)
+    for pat, status in ((b"(", 1), (b"a{2,1}", 1), (b"[z-a]", 1), (rb"\b{start}word", 2)):  # TGX_INVALID_ARGUMENT; TGX_UNSUPPORTED
+        err = _Error()
+        verr = _Error()
+        assert lib.tgx_regex_table_info(pat, len(pat), 0, *outs, C.byref(err)) == status, pat
+        assert lib.tgx_regex_validate(pat, len(pat), 0, C.byref(verr)) == status  # (the same compile, the same refusal)
+        assert err.msg == verr.msg and err.msg
+        assert (ns.value, nc.value, lo.value, hi.value) == before
+    pat = rb"^\w{1,64}$"  # an automaton and a character count
+    assert lib.tgx_regex_table_info(pat, len(pat), 0, *outs, None) == 0
+    assert (lo.value, hi.value) == (1, 64) and ns.value * nc.value > 4096
+    assert lib.tgx_regex_table_info(pat, len(pat), T.FLAG_TRIM | T.FLAG_NULL_IS_VALID, *outs, None) == 0  # (flags of the walk: no part of the compile)
+    assert (lo.value, hi.value) == (1, 64)
+
+
 def test_blob_roundtrip_without_device():
     from term_amd import wire
 

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""The pattern kernels on the GPU against RE2 (pyarrow.compute): random valid patterns (tools/fuzz_regex_diff.py's
-grammar), each counted by regex_match_kernel over a column of a few thousand random values -- short and long ones
-(a value may span several staging steps), NULLs, as Utf8 on the device, as Utf8View, as a dictionary column; up to
-four patterns per plan, so that they share ONE walk (product automaton) where their tables fit -- and by RE2 value by
-value.  Counts must be equal.
+"""The pattern kernels on the GPU against RE2 (pyarrow.compute), seed by seed: the cases of tests/regex_cases.py -- one
+string column (Utf8, LargeUtf8, Utf8View, dictionary) with value lengths that force each way a wave step is fed, one to
+six patterns from tools/fuzz_regex_diff.py's grammar and templates with TRIM / NULL-is-valid / case flags, LENGTH checks,
+fed as one batch, ragged Arrow slices, 8192-row batches, from DEVICE / HOST buffers or as two merged states -- over any
+range of seeds.  Counts must be equal; a spec that disagrees is printed with its route (table class, single walk or
+product automaton, layout, feeds), and its seed can go into tests/regex_cases.py's SEEDS.  Seeds whose draw RE2 or the
+engine refuses are counted and passed over: nothing to compare.
 
-    python tools/fuzz_regex_device.py [--seconds 120] [--seed 1]"""
+    python tools/fuzz_regex_device.py [--first S] [--count K] [--seconds T] [--seed S]
+
+A run covers the seeds --first .. --first + --count - 1 and says which it ran.  --seed is the earlier name of --first;
+--seconds (default 0: no limit) stops starting new cases after that long, and the last line then says that the clock,
+not the count, ended the run; --rows is accepted and ignored (a case draws its own row count)."""
 import argparse
 import os
-import random
 import sys
 import time
 
@@ -20,64 +25,51 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=120)
+    ap.add_argument("--seconds", type=float, default=0, help="stop starting new cases after this long (0: run them all)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--rows", type=int, default=6000)
+    ap.add_argument("--first", type=int, default=None)
+    ap.add_argument("--count", type=int, default=200)
     args = ap.parse_args()
-    import ctypes as C
+    import pyarrow  # noqa: F401
 
-    import numpy as np
-    import pyarrow as pa
-    import pyarrow.compute as pc
-
-    import fuzz_regex_diff as F
+    import regex_cases as R
     import term_amd as T
-    from term_amd._lib import spec
 
     T.init()
-    rng = random.Random(args.seed)
+    first = args.seed if args.first is None else args.first
     t0 = time.time()
-    plans = cmps = bad = 0
-    err = T._lib._Error()
-    while time.time() - t0 < args.seconds:
-        ascii_only = rng.random() < 0.5
-        pats = []
-        while len(pats) < rng.randint(1, 4):
-            p = F.pattern(rng, ascii_only)
-            pb = p.encode()
-            if T.lib().tgx_regex_validate(pb, len(pb), 0, C.byref(err)) == 0:
-                pats.append(p)
-        vals = []
-        for _ in range(args.rows):
-            r = rng.random()
-            if r < 0.06:
-                vals.append(None)
-            elif r < 0.85:
-                vals.append(F.subject(rng, ascii_only))
-            else:  # long values: several staging steps, multi-byte characters across their borders
-                vals.append("".join(F.subject(rng, ascii_only) for _ in range(rng.randint(5, 60))))
-        layout = rng.choice(["utf8", "large", "view", "dict"])
-        arr = pa.array(vals, pa.large_string() if layout == "large" else pa.string())
-        if layout == "view":
-            fed = arr.cast(pa.string_view())
-        elif layout == "dict":
-            fed = arr.dictionary_encode()
-        else:
-            fed = arr
-        col = T.Column.from_arrow(fed)
-        plan = T.Plan([spec(T.REGEX_MATCH, 0, pattern=p) for p in pats])
-        st = T.State(plan)
-        st.update([col])
-        res = st.finalize()
-        plans += 1
-        for p, r in zip(pats, res):
-            want = pc.sum(pc.match_substring_regex(arr, p)).as_py() or 0
-            cmps += 1
-            if r.matches != want or r.total != len(vals):
-                bad += 1
-                print("DISAGREE %s pattern %r: device %d RE2 %d (of %d rows, with %r)" % (layout, p, r.matches, want, len(vals), pats))
-        del st, plan
-    print("%d plans, %d pattern counts, %d disagreements, %.0f s" % (plans, cmps, bad, time.time() - t0))
+    cases = specs = bad = refused = 0
+    routes = set()
+    last, cut_short = None, False
+    for seed in range(first, first + args.count):
+        if args.seconds > 0 and time.time() - t0 > args.seconds:
+            cut_short = True
+            break
+        last = seed
+        try:
+            case = R.Case(seed)
+        except RuntimeError as e:  # (no pattern of the stratum's table class in the generator's draws)
+            print("seed %d: %s" % (seed, e))
+            refused += 1
+            continue
+        if case.refused():
+            refused += 1
+            continue
+        got = case.run()
+        cases += 1
+        specs += len(got)
+        for r in case.routes():
+            if r and r["kind"] == "regex":
+                routes.update((r["table"], r["layout"], r["group"], f) for f in r["feeds"])
+        for line in R.disagreements(case, got):
+            bad += 1
+            print("DISAGREE", line, flush=True)
+            for ref in case.reference_disagreements()[:5]:  # (a host walk that agrees with RE2 puts the fault in the kernel)
+                print("         references:", ref, flush=True)
+    print("seeds %d .. %s%s: %d cases, %d specs compared over %d routes, %d disagreements, %d seeds refused, %.0f s"
+          % (first, last, " (ended by --seconds, %d asked for)" % args.count if cut_short else "", cases, specs, len(routes),
+             bad, refused, time.time() - t0))
     return 1 if bad else 0
 
 

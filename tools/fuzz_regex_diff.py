@@ -71,6 +71,38 @@ def pattern(rng, ascii_only):
     return p
 
 
+# ---- templates: the shapes real format checks have, which the grammar above rarely draws.  All inside the common subset:
+# ASCII classes and literals, counted NEGATED ASCII classes (both engines count code points), and -- over ASCII subjects
+# only -- \w \S \d and word boundaries.  tgx_regex_table_info says where each lands: `tiny` is a byte-indexed table
+# (and so is the product of two to four of them), `counted_ascii` / `stacked` a table in LDS, `counted` the automaton
+# with a character count (`^C*$` + LENGTH bounds; \w: LDS), `word` the Unicode-aware boundary automaton (global memory).
+TEMPLATES = ["tiny", "counted_ascii", "stacked", "counted", "word"]
+WORDS = ["ab", "a", "zz", "A9", "x.y", "c0", "Z"]
+
+
+def template(rng, ascii_only, kind=None):
+    kind = kind or rng.choice(TEMPLATES)
+    if kind == "tiny":
+        a = rng.choice(["a", "b", "z", "A", "Z", "0", "1", "9", "@", r"\.", "-", "_", "/", ":", " ", "[0-9]", "[a-c]", "[^a-c]", "[A-Za-z]", "[^@]"])
+        return rng.choice(["%s", "^%s", "%s$", "%s%s"]).replace("%s", a)
+    if kind == "counted_ascii":
+        m = rng.choice([0, 1, 2, 3, 5])
+        return "^%s{%d,%d}$" % (rng.choice(["[a-z0-9._-]", "[A-Za-z0-9@. /:_-]", "[abcxyz019]"]), m, m + rng.choice([1, 4, 9, 30, 64]))
+    if kind == "stacked":
+        parts = rng.sample(["[a-z]{1,%d}", "[0-9]{1,%d}", "[A-Z]{1,%d}", "[@. /:_-]{1,%d}"], rng.randint(2, 3))
+        return "^(?:%s){1,%d}$" % ("".join(q % rng.choice([3, 10, 40]) for q in parts), rng.randint(1, 3))
+    if kind == "counted":
+        m = rng.choice([0, 1, 2, 5, 12])
+        n = m + rng.choice([0, 3, 8, 30, 70])
+        classes = ["[^@]", "[^a-c]", "[^[:space:]]", "[^0-9]"] + ([r"\w", r"\S", r"\D", r"[\w.@-]"] if ascii_only else ["."])
+        return "^%s{%d,%d}$" % (rng.choice(classes), m, n)
+    if kind == "word":
+        if not ascii_only:  # (no \b over non-ASCII subjects: a literal between the ends of two non-ASCII-aware classes)
+            return "(?:^|[^A-Za-z0-9_])%s(?:[^A-Za-z0-9_]|$)" % rng.choice(WORDS).replace(".", r"\.")
+        return rng.choice([r"\b%s\b", r"\b%s", r"%s\b", r"\B%s"]) % rng.choice(WORDS).replace(".", r"\.")
+    raise ValueError(kind)
+
+
 def subject(rng, ascii_only):
     pool = LITERALS_ASCII + (["\t", "\n", "\n"] if rng.random() < 0.3 else []) + ([] if ascii_only else LITERALS_UNI + ["Ж", "漢", "😀"])
     return "".join(rng.choice(pool) for _ in range(rng.randint(0, 10)))
@@ -135,7 +167,7 @@ def main():
         print("%d counted-class patterns" % n_counted)
     while time.time() - t0 < args.seconds:
         ascii_only = args.ascii or rng.random() < 0.5
-        pat = pattern(rng, ascii_only)
+        pat = pattern(rng, ascii_only) if rng.random() < 0.8 else template(rng, ascii_only)
         subs = [subject(rng, ascii_only) for _ in range(args.subjects)]
         try:
             want = pc.match_substring_regex(pa.array(subs, pa.large_string()), pat).to_pylist()
