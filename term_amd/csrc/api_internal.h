@@ -2,9 +2,9 @@
 // profiling, finalize), update.cpp (staging and the fused pass of a batch), distinct_state.cpp (the key sets' host-side
 // bookkeeping, export / import / adopt), merge.cpp (tgx_merge), coalesce.cpp (small batches noted and gathered, the copy
 // pool), wire.cpp (state blobs) and allreduce.cpp (the cross-rank step).  The helpers declared here are shared between
-// those files only (hidden visibility).  What the check modules (kll_device.cpp, regex_device.cpp, spearman_device.cpp,
-// jointbins_device.cpp, temporal_device.cpp, histogram_device.cpp) need as well -- fail(), HIP_TRY / TGX_TRY, ProfScope, spec_slot -- is in internal.h; the blob's
-// Writer / Reader are in wire_io.h.
+// those files only (hidden visibility).  What the check modules (kll_device.cpp, regex_device.cpp, spearman_device.cpp
+// and the three kinds of side_check.h) need as well -- fail(), HIP_TRY / TGX_TRY, ProfScope, spec_slot -- is in
+// internal.h; the blob's Writer / Reader are in wire_io.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,13 +19,11 @@
 #include <mutex>
 #include <thread>
 
-#include "histogram_device.h"
 #include "internal.h"
-#include "jointbins_device.h"
 #include "kll_device.h"
 #include "regex_device.h"
+#include "side_check.h"
 #include "spearman_device.h"
-#include "temporal_device.h"
 
 using namespace tgx;
 

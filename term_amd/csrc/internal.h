@@ -195,6 +195,7 @@ struct KllTask {
   int column;
   uint32_t k;
 };
+// The three kinds of side_check.h.
 // TGX_CHECK_JOINT_BINS (jointbins_device.cpp): one task per spec; `binned` once tgx_plan_set_joint_binning was called
 struct JointTask {
   int col_x, col_y;
@@ -215,6 +216,9 @@ struct HistTask {
   std::vector<double> edges;  // count phase: buckets + 1
   uint32_t buckets() const { return counted ? (uint32_t)edges.size() - 1 : 0; }
 };
+
+struct SideCheck;            // side_check.h: the state of one kind's tasks
+constexpr int kNumSide = 3;  // JOINT_BINS, TEMPORAL, HISTOGRAM
 
 enum class Source { kScan, kCount };
 
@@ -644,9 +648,8 @@ struct tgx_state {
   void *kll = nullptr;    // tgx::KllDeviceState (kll_device.cpp)
   void *regex = nullptr;  // tgx::RegexState (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
-  void *joint = nullptr;  // tgx::JointState (jointbins_device.cpp)
-  void *temporal = nullptr;  // tgx::TemporalState (temporal_device.cpp)
-  void *hist = nullptr;  // tgx::HistState (histogram_device.cpp)
+  // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms
+  std::unique_ptr<tgx::SideCheck> side[tgx::kNumSide];
 
   tgx::Coalescer coalesce;
   std::vector<tgx::DevBuf> parked;  // buffers replaced while the stream may still read them; freed once it has drained

@@ -5,113 +5,176 @@
 // 64-bit counters in the count phase (the cells, the rows outside [0, bins], the non-finite rows) -- and is folded by
 // kernels/jointbins.hip; rows seen are counted on the host.  What is merged in from other states or read from a blob
 // is kept on the host and added when the state is read: extremes by MIN / MAX, everything else by addition.
-#include "jointbins_device.h"
-
 #include "api_internal.h"
 
 namespace tgx {
-size_t joint_range_partial_bytes();
-void launch_pair_range(const JointLaunch &L, int n_pairs, int blocks_per_pair, void *d_partials, JointRangeAcc *d_accs,
-                       hipStream_t stream);
+void launch_pair_range(const JointLaunch &L, int n_pairs, int blocks_per_pair, JointRangeAcc *d_partials,
+                       JointRangeAcc *d_accs, hipStream_t stream);
 void launch_joint_bins(const JointLaunch &L, int n_pairs, int blocks_per_pair, size_t lds_bytes, hipStream_t stream);
 
 namespace {
 
-constexpr uint32_t kJointWireMagic = 0x42544e4a;  // "JNTB"
-
-JointRangeAcc range_identity() {
-  JointRangeAcc a;
-  a.n = a.non_finite = 0;
-  a.x_min = a.y_min = INFINITY;
-  a.x_max = a.y_max = -INFINITY;
-  return a;
-}
-
 // one task's state as the host sees it
 struct JointHost {
   int64_t total = 0;
-  JointRangeAcc range = range_identity();  // count phase: n and non_finite only
-  std::vector<uint64_t> words;             // count phase: the cells, then the rows outside [0, bins]
+  JointRangeAcc range;          // count phase: n and non_finite only
+  std::vector<uint64_t> words;  // count phase: the cells, then the rows outside [0, bins]
 };
 
-struct JointState {
-  std::vector<JointHost> host;        // merged in / deserialized
-  std::vector<int64_t> device_total;  // rows the device part has seen
-  std::vector<size_t> word_off;       // per task: first of its counters in d_counts (count phase)
-  size_t n_words = 0;
-  bool device_ready = false;
-  DevBuf d_range, d_counts, d_partials;
-  std::vector<JointRangeAcc> identity;  // (kept alive: uploaded asynchronously)
-};
+struct JointKind {
+  typedef JointTask Task;
+  typedef JointHost Host;
+  typedef JointRangeAcc Range;
+  static constexpr bool kRanged = true;
+  static constexpr int kIndex = kSideJoint;
+  static constexpr const char *kName = "JOINT_BINS", *kDiffers = "binnings";
+  static constexpr uint32_t kMagic = 0x42544e4a;  // "JNTB"
 
-JointState *js_of(tgx_state *st) { return (JointState *)st->joint; }
+  static const std::vector<JointTask> &tasks(const tgx_plan *plan) { return plan->joint; }
+  static size_t words(const JointTask &t) { return t.binned ? (size_t)joint_cells(t.binning.bins) + 2 : 0; }
+  static JointRangeAcc range_identity() {
+    JointRangeAcc a;
+    a.n = a.non_finite = 0;
+    a.x_min = a.y_min = INFINITY;
+    a.x_max = a.y_max = -INFINITY;
+    return a;
+  }
+  static JointHost fresh(const JointTask &t) {
+    JointHost h;
+    h.range = range_identity();
+    if (t.binned) h.words.assign(joint_cells(t.binning.bins) + 1, 0);
+    return h;
+  }
+  static size_t shape(const JointHost &h) { return h.words.size(); }
 
-size_t task_words(const JointTask &t) { return t.binned ? (size_t)joint_cells(t.binning.bins) + 2 : 0; }
-
-void merge_host(JointHost &a, const JointHost &b) {
-  a.total += b.total;
-  a.range.n += b.range.n;
-  a.range.non_finite += b.range.non_finite;
-  a.range.x_min = std::min(a.range.x_min, b.range.x_min);
-  a.range.x_max = std::max(a.range.x_max, b.range.x_max);
-  a.range.y_min = std::min(a.range.y_min, b.range.y_min);
-  a.range.y_max = std::max(a.range.y_max, b.range.y_max);
-  for (size_t i = 0; i < a.words.size() && i < b.words.size(); i++) a.words[i] += b.words[i];
-}
-
-tgx_status device_clear(tgx_state *st, tgx_error *err) {
-  JointState *js = js_of(st);
-  if (!js->identity.empty())
-    HIP_TRY(hipMemcpyAsync(js->d_range.p, js->identity.data(), js->identity.size() * sizeof(JointRangeAcc),
-                           hipMemcpyHostToDevice, st->stream));
-  if (js->n_words) HIP_TRY(hipMemsetAsync(js->d_counts.p, 0, js->n_words * sizeof(unsigned long long), st->stream));
-  return TGX_OK;
-}
-
-tgx_status device_init(tgx_state *st, tgx_error *err) {
-  JointState *js = js_of(st);
-  if (js->device_ready) return TGX_OK;
-  const size_t n = st->plan->joint.size();
-  js->identity.assign(n, range_identity());
-  HIP_TRY(js->d_range.reserve(n * sizeof(JointRangeAcc)));
-  if (js->n_words) HIP_TRY(js->d_counts.reserve(js->n_words * sizeof(unsigned long long)));
-  TGX_TRY(device_clear(st, err));
-  js->device_ready = true;
-  return TGX_OK;
-}
-
-// host part + device part of every task (the device part stays where it is)
-tgx_status joint_gather(tgx_state *st, std::vector<JointHost> *out, tgx_error *err) {
-  JointState *js = js_of(st);
-  const tgx_plan *plan = st->plan;
-  TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
-  *out = js->host;
-  if (!js->device_ready) return TGX_OK;
-  std::vector<JointRangeAcc> ranges(plan->joint.size());
-  std::vector<unsigned long long> words(js->n_words);
-  HIP_TRY(hipMemcpyAsync(ranges.data(), js->d_range.p, ranges.size() * sizeof(JointRangeAcc), hipMemcpyDeviceToHost,
-                         st->stream));
-  if (js->n_words)
-    HIP_TRY(hipMemcpyAsync(words.data(), js->d_counts.p, words.size() * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, st->stream));
-  HIP_TRY(hipStreamSynchronize(st->stream));
-  for (size_t k = 0; k < plan->joint.size(); k++) {
-    const JointTask &t = plan->joint[k];
-    JointHost d;
-    d.total = js->device_total[k];
+  static JointHost from_device(const JointTask &t, int64_t rows, const JointRangeAcc &range,
+                               const unsigned long long *w) {
+    JointHost d = fresh(t);
+    d.total = rows;
     if (!t.binned) {
-      d.range = ranges[k];
+      d.range = range;
     } else {
       const size_t cells = joint_cells(t.binning.bins);
-      const unsigned long long *w = words.data() + js->word_off[k];
       d.words.assign(w, w + cells + 1);
       for (size_t c = 0; c < cells; c++) d.range.n += (int64_t)w[c];
       d.range.non_finite = (int64_t)w[cells + 1];
     }
-    merge_host((*out)[k], d);
+    return d;
   }
-  return TGX_OK;
-}
+
+  static void merge_host(JointHost &a, const JointHost &b) {
+    a.total += b.total;
+    a.range.n += b.range.n;
+    a.range.non_finite += b.range.non_finite;
+    a.range.x_min = std::min(a.range.x_min, b.range.x_min);
+    a.range.x_max = std::max(a.range.x_max, b.range.x_max);
+    a.range.y_min = std::min(a.range.y_min, b.range.y_min);
+    a.range.y_max = std::max(a.range.y_max, b.range.y_max);
+    for (size_t i = 0; i < a.words.size() && i < b.words.size(); i++) a.words[i] += b.words[i];
+  }
+
+  // per task { u32 binned, u32 bins, f64 x_origin, x_width, y_origin, y_width, i64 total, n, non_finite,
+  //   f64 x_min, x_max, y_min, y_max, u64 n_words, u64 words[n_words] }
+  // n_words = (bins + 1)^2 + 1 in the count phase (the cells, row-major, then the rows outside [0, bins]), else 0
+  static void write(const JointTask &t, const JointHost &h, Writer &w) {
+    const uint32_t phase[2] = {t.binned ? 1u : 0u, t.binning.bins};
+    w.pod(phase);
+    const double edges[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
+    w.pod(edges);
+    const int64_t counts[3] = {h.total, h.range.n, h.range.non_finite};
+    w.pod(counts);
+    const double ext[4] = {h.range.x_min, h.range.x_max, h.range.y_min, h.range.y_max};
+    w.pod(ext);
+    w.pod((uint64_t)h.words.size());
+    w.put(h.words.data(), h.words.size() * sizeof(uint64_t));
+  }
+
+  static tgx_status read(const JointTask &t, JointHost &h, Reader &r, size_t k, tgx_error *err) {
+    uint32_t phase[2];
+    double edges[4], ext[4];
+    int64_t counts[3];
+    r.get(phase, sizeof(phase));
+    r.get(edges, sizeof(edges));
+    r.get(counts, sizeof(counts));
+    r.get(ext, sizeof(ext));
+    const uint64_t n_words = r.pod<uint64_t>();
+    if (!r.ok) return TGX_OK;
+    const double mine[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
+    if (phase[0] != (t.binned ? 1u : 0u) || phase[1] != t.binning.bins || memcmp(edges, mine, sizeof(mine)) != 0)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "JOINT_BINS task %zu: the blob was counted under another binning (bins %u) than the plan's (bins %u)", k,
+                  phase[1], t.binning.bins);
+    size_t bytes = 0;
+    if (n_words != h.words.size() || !r.fits(n_words, sizeof(uint64_t), &bytes))
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (JOINT_BINS task %zu)", k);
+    h.total = counts[0];
+    h.range.n = counts[1];
+    h.range.non_finite = counts[2];
+    h.range.x_min = ext[0];
+    h.range.x_max = ext[1];
+    h.range.y_min = ext[2];
+    h.range.y_max = ext[3];
+    r.get(h.words.data(), bytes);
+    return TGX_OK;
+  }
+};
+
+struct JointCheck final : SideState<JointKind> {
+  using SideState::SideState;
+
+  tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
+    const tgx_plan *plan = st->plan;
+    if (nrows <= 0) return TGX_OK;
+    TGX_TRY(device_init(st, err));
+    for (int phase = 0; phase < 2; phase++) {
+      auto launch = [&](const int *slots, int n) -> tgx_status {
+        JointLaunch L;
+        memset(&L, 0, sizeof(L));
+        uint64_t bytes = 0;
+        uint32_t max_cells = 0;
+        for (int k = 0; k < n; k++) {
+          const int slot = slots[k];
+          const JointTask &t = plan->joint[slot];
+          const tgx_column &x = dev[t.col_x], &y = dev[t.col_y];
+          if (!is_numeric(x.type) || !is_numeric(y.type))
+            return fail(err, TGX_UNSUPPORTED, "JOINT_BINS takes numeric columns (%d, %d)", x.type, y.type);
+          bytes += side_fill_x(L.pairs[k], x) + side_fill_y(L.pairs[k], y);
+          L.binning[k] = t.binning;
+          L.counters[k] = t.binned ? d_counts.as<unsigned long long>() + word_off[slot] : nullptr;
+          L.acc_index[k] = slot;
+          max_cells = std::max(max_cells, t.binned ? joint_cells(t.binning.bins) : 0u);
+          device_rows[slot] += nrows;
+        }
+        // 8 waves a workgroup, up to 4 workgroups a CU; the count phase as many as its LDS counters leave room for
+        const size_t lds = (size_t)max_cells * sizeof(unsigned int);
+        const int per_cu = phase == 0 ? 4 : (int)std::max<size_t>(1, std::min<size_t>(4, (160u << 10) / std::max<size_t>(lds, 1)));
+        const int blocks = side_blocks(nrows, kJointBlock, g_ctx.n_cu, per_cu, n);
+        TGX_TRY(side_rows_fit("JOINT_BINS", nrows, blocks, err));
+        (void)hipGetLastError();  // (what the launches below leave is theirs: a 64 KiB LDS request can be refused)
+        if (phase == 0) {
+          HIP_TRY(d_partials.reserve((size_t)n * blocks * sizeof(JointRangeAcc)));
+          ProfScope ps(st, "joint_range", bytes);
+          launch_pair_range(L, n, blocks, d_partials.as<JointRangeAcc>(), d_range.as<JointRangeAcc>(), st->stream);
+        } else {
+          ProfScope ps(st, "joint_bins", bytes);
+          launch_joint_bins(L, n, blocks, lds, st->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        return TGX_OK;
+      };
+      TGX_TRY(side_launches(plan->joint, [&](const JointTask &t) { return (int)t.binned == phase; }, launch));
+    }
+    return TGX_OK;
+  }
+
+  tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) override {
+    std::vector<JointHost> g;
+    TGX_TRY(gather(st, &g, err));
+    r->total = g[slot].total;
+    r->non_null = g[slot].range.n;
+    return TGX_OK;
+  }
+};
 
 }  // namespace
 
@@ -127,191 +190,7 @@ tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *
   return TGX_OK;
 }
 
-void joint_state_init(tgx_state *st) {
-  joint_state_free(st);
-  const tgx_plan *plan = st->plan;
-  if (plan->joint.empty()) return;
-  JointState *js = new JointState();
-  js->host.resize(plan->joint.size());
-  js->device_total.assign(plan->joint.size(), 0);
-  js->word_off.assign(plan->joint.size(), 0);
-  for (size_t k = 0; k < plan->joint.size(); k++) {
-    js->word_off[k] = js->n_words;
-    js->n_words += task_words(plan->joint[k]);
-    if (plan->joint[k].binned) js->host[k].words.assign(joint_cells(plan->joint[k].binning.bins) + 1, 0);
-  }
-  st->joint = js;
-}
-
-void joint_state_free(tgx_state *st) {
-  delete js_of(st);
-  st->joint = nullptr;
-}
-
-// (the caller has waited for the stream)
-tgx_status joint_state_reset(tgx_state *st, tgx_error *err) {
-  JointState *js = js_of(st);
-  if (!js) return TGX_OK;
-  for (JointHost &h : js->host) {
-    h.total = 0;
-    h.range = range_identity();
-    std::fill(h.words.begin(), h.words.end(), 0);
-  }
-  std::fill(js->device_total.begin(), js->device_total.end(), 0);
-  if (js->device_ready) TGX_TRY(device_clear(st, err));
-  return TGX_OK;
-}
-
-tgx_status joint_update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) {
-  const tgx_plan *plan = st->plan;
-  JointState *js = js_of(st);
-  if (!js || nrows <= 0) return TGX_OK;
-  TGX_TRY(device_init(st, err));
-  // the tasks of each phase in launches of up to kMaxJointPerLaunch pairs (grid.y)
-  for (int phase = 0; phase < 2; phase++) {
-    std::vector<int> tasks;
-    for (size_t k = 0; k < plan->joint.size(); k++)
-      if ((int)plan->joint[k].binned == phase) tasks.push_back((int)k);
-    for (size_t t0 = 0; t0 < tasks.size(); t0 += kMaxJointPerLaunch) {
-      const int n = (int)std::min<size_t>(kMaxJointPerLaunch, tasks.size() - t0);
-      JointLaunch L;
-      memset(&L, 0, sizeof(L));
-      uint64_t bytes = 0;
-      uint32_t max_cells = 0;
-      for (int k = 0; k < n; k++) {
-        const int slot = tasks[t0 + k];
-        const JointTask &t = plan->joint[slot];
-        const tgx_column &x = dev[t.col_x], &y = dev[t.col_y];
-        if (!is_numeric(x.type) || !is_numeric(y.type))
-          return fail(err, TGX_UNSUPPORTED, "JOINT_BINS takes numeric columns (%d, %d)", x.type, y.type);
-        ComomentColDesc &d = L.pairs[k];
-        d.x = x.values;
-        d.y = y.values;
-        d.xv = x.validity;
-        d.yv = y.validity;
-        d.xoff = x.offset;
-        d.yoff = y.offset;
-        d.length = x.length;
-        d.x_is_float = x.type == TGX_FLOAT64;
-        d.y_is_float = y.type == TGX_FLOAT64;
-        L.binning[k] = t.binning;
-        L.counters[k] = t.binned ? js->d_counts.as<unsigned long long>() + js->word_off[slot] : nullptr;
-        L.acc_index[k] = slot;
-        max_cells = std::max(max_cells, t.binned ? joint_cells(t.binning.bins) : 0u);
-        bytes += (uint64_t)x.length * 16 + (x.validity ? (uint64_t)(x.length + 7) / 8 : 0) +
-                 (y.validity ? (uint64_t)(y.length + 7) / 8 : 0);
-        js->device_total[slot] += nrows;
-      }
-      // 8 waves a workgroup, up to 4 workgroups a CU; the count phase as many as its LDS counters leave room for
-      const size_t lds = (size_t)max_cells * sizeof(unsigned int);
-      const int per_cu = phase == 0 ? 4 : (int)std::max<size_t>(1, std::min<size_t>(4, (160u << 10) / std::max<size_t>(lds, 1)));
-      const int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, (nrows + kJointBlock * 16 - 1) / (kJointBlock * 16)),
-                                                std::max(32, (g_ctx.n_cu * per_cu) / n));
-      // (a workgroup's cells are 32-bit counters)
-      if (nrows / blocks >= ((int64_t)1 << 32))
-        return fail(err, TGX_UNSUPPORTED, "JOINT_BINS: a batch of %lld rows is too long", (long long)nrows);
-      (void)hipGetLastError();  // (what the launches below leave is theirs: a 64 KiB LDS request can be refused)
-      if (phase == 0) {
-        HIP_TRY(js->d_partials.reserve((size_t)n * blocks * joint_range_partial_bytes()));
-        ProfScope ps(st, "joint_range", bytes);
-        launch_pair_range(L, n, blocks, js->d_partials.p, js->d_range.as<JointRangeAcc>(), st->stream);
-      } else {
-        ProfScope ps(st, "joint_bins", bytes);
-        launch_joint_bins(L, n, blocks, lds, st->stream);
-      }
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return TGX_OK;
-}
-
-tgx_status joint_fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) {
-  std::vector<JointHost> g;
-  TGX_TRY(joint_gather(st, &g, err));
-  r->total = g[slot].total;
-  r->non_null = g[slot].range.n;
-  return TGX_OK;
-}
-
-tgx_status joint_merge_states(tgx_state *dst, tgx_state *src, tgx_error *err) {
-  JointState *jd = js_of(dst);
-  if (!jd) return TGX_OK;
-  std::vector<JointHost> g;
-  TGX_TRY(joint_gather(src, &g, err));
-  for (size_t k = 0; k < g.size(); k++) {
-    // (states of one plan share its binning; a blob made under another one was refused by tgx_state_deserialize)
-    if (g[k].words.size() != jd->host[k].words.size())
-      return fail(err, TGX_INVALID_ARGUMENT, "JOINT_BINS task %zu: the states were counted under different binnings", k);
-    merge_host(jd->host[k], g[k]);
-  }
-  return TGX_OK;
-}
-
-// section: { u32 magic "JNTB", u32 tasks; per task { u32 binned, u32 bins, f64 x_origin, x_width, y_origin, y_width,
-//   i64 total, n, non_finite, f64 x_min, x_max, y_min, y_max, u64 n_words, u64 words[n_words] } }
-// n_words = (bins + 1)^2 + 1 in the count phase (the cells, row-major, then the rows outside [0, bins]), else 0
-tgx_status joint_serialize(tgx_state *st, Writer &w, tgx_error *err) {
-  const tgx_plan *plan = st->plan;
-  if (plan->joint.empty()) return TGX_OK;
-  std::vector<JointHost> g;
-  TGX_TRY(joint_gather(st, &g, err));
-  w.pod(kJointWireMagic);
-  w.pod((uint32_t)plan->joint.size());
-  for (size_t k = 0; k < g.size(); k++) {
-    const JointTask &t = plan->joint[k];
-    const uint32_t phase[2] = {t.binned ? 1u : 0u, t.binning.bins};
-    w.pod(phase);
-    const double edges[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
-    w.pod(edges);
-    const int64_t counts[3] = {g[k].total, g[k].range.n, g[k].range.non_finite};
-    w.pod(counts);
-    const double ext[4] = {g[k].range.x_min, g[k].range.x_max, g[k].range.y_min, g[k].range.y_max};
-    w.pod(ext);
-    w.pod((uint64_t)g[k].words.size());
-    w.put(g[k].words.data(), g[k].words.size() * sizeof(uint64_t));
-  }
-  return TGX_OK;
-}
-
-tgx_status joint_deserialize(tgx_state *st, Reader &r, tgx_error *err) {
-  const tgx_plan *plan = st->plan;
-  JointState *js = js_of(st);
-  if (!js) return TGX_OK;
-  const uint32_t magic = r.pod<uint32_t>(), tasks = r.pod<uint32_t>();
-  if (!r.ok || magic != kJointWireMagic || tasks != plan->joint.size())
-    return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan (JOINT_BINS section)");
-  for (size_t k = 0; k < plan->joint.size(); k++) {
-    const JointTask &t = plan->joint[k];
-    uint32_t phase[2];
-    double edges[4], ext[4];
-    int64_t counts[3];
-    r.get(phase, sizeof(phase));
-    r.get(edges, sizeof(edges));
-    r.get(counts, sizeof(counts));
-    r.get(ext, sizeof(ext));
-    const uint64_t n_words = r.pod<uint64_t>();
-    if (!r.ok) break;
-    const double mine[4] = {t.binning.x_origin, t.binning.x_width, t.binning.y_origin, t.binning.y_width};
-    if (phase[0] != (t.binned ? 1u : 0u) || phase[1] != t.binning.bins || memcmp(edges, mine, sizeof(mine)) != 0)
-      return fail(err, TGX_INVALID_ARGUMENT,
-                  "JOINT_BINS task %zu: the blob was counted under another binning (bins %u) than the plan's (bins %u)", k,
-                  phase[1], t.binning.bins);
-    JointHost &h = js->host[k];
-    size_t bytes = 0;
-    if (n_words != h.words.size() || !r.fits(n_words, sizeof(uint64_t), &bytes))
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (JOINT_BINS task %zu)", k);
-    h.total = counts[0];
-    h.range.n = counts[1];
-    h.range.non_finite = counts[2];
-    h.range.x_min = ext[0];
-    h.range.x_max = ext[1];
-    h.range.y_min = ext[2];
-    h.range.y_max = ext[3];
-    r.get(h.words.data(), bytes);
-  }
-  if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
-  return TGX_OK;
-}
+SideCheck *joint_state_new(const tgx_plan *plan) { return plan->joint.empty() ? nullptr : new JointCheck(plan); }
 
 }  // namespace tgx
 
@@ -354,7 +233,7 @@ extern "C" tgx_status tgx_joint_range_get(const tgx_plan *plan, tgx_state *st, s
   size_t slot = 0;
   TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_JOINT_BINS, "JOINT_BINS", &slot, err, "bad arguments"));
   std::vector<JointHost> g;
-  TGX_TRY(joint_gather(st, &g, err));
+  TGX_TRY(JointCheck::of(st)->gather(st, &g, err));
   const JointHost &h = g[slot];
   out->total = (uint64_t)h.total;
   out->n = (uint64_t)h.range.n;
@@ -385,7 +264,7 @@ extern "C" tgx_status tgx_joint_counts(const tgx_plan *plan, tgx_state *st, size
   if (cap < n) return fail(err, TGX_INVALID_ARGUMENT, "cells has room for %llu of %llu counts", (unsigned long long)cap,
                            (unsigned long long)n);
   std::vector<JointHost> g;
-  TGX_TRY(joint_gather(st, &g, err));
+  TGX_TRY(JointCheck::of(st)->gather(st, &g, err));
   memcpy(cells, g[slot].words.data(), (size_t)n * sizeof(uint64_t));
   if (out_of_range) *out_of_range = g[slot].words[n];
   return TGX_OK;

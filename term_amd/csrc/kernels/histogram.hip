@@ -26,14 +26,14 @@
 
 namespace tgx {
 
-namespace {
+static __device__ __forceinline__ void range_clear(HistRangeAcc &a) {
+  a.n = a.non_finite = 0;
+  a.min = INFINITY;
+  a.max = -INFINITY;
+  a.sum = a.sum_squared = 0.0;
+}
 
-struct HistRangePartial {
-  int64_t n, non_finite;
-  double min, max, sum, sum_squared;
-};
-
-__device__ __forceinline__ void hist_range_fold(HistRangePartial &a, const HistRangePartial &b) {
+static __device__ __forceinline__ void range_fold(HistRangeAcc &a, const HistRangeAcc &b) {
   a.n += b.n;
   a.non_finite += b.non_finite;
   a.min = fmin(a.min, b.min);
@@ -42,28 +42,17 @@ __device__ __forceinline__ void hist_range_fold(HistRangePartial &a, const HistR
   a.sum_squared += b.sum_squared;
 }
 
-__device__ __forceinline__ void hist_range_wave_reduce(HistRangePartial &r) {
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-    HistRangePartial o;
-    o.n = __shfl_down(r.n, dlt, 64);
-    o.non_finite = __shfl_down(r.non_finite, dlt, 64);
-    o.min = __shfl_down(r.min, dlt, 64);
-    o.max = __shfl_down(r.max, dlt, 64);
-    o.sum = __shfl_down(r.sum, dlt, 64);
-    o.sum_squared = __shfl_down(r.sum_squared, dlt, 64);
-    hist_range_fold(r, o);
-  }
-}
+}  // namespace tgx
 
-constexpr int kHistWaves = kHistBlock / 64;
+#include "bin_count.h"
 
-}  // namespace
+namespace tgx {
 
-__global__ __launch_bounds__(kHistBlock) void hist_range_kernel(const HistLaunch L,
-                                                                 HistRangePartial *__restrict__ partials) {
+static __global__ __launch_bounds__(kHistBlock) void hist_range_kernel(const HistLaunch L,
+                                                                        HistRangeAcc *__restrict__ partials) {
   const ComomentColDesc d = L.cols[blockIdx.y];
-  HistRangePartial r = {0, 0, INFINITY, -INFINITY, 0.0, 0.0};
+  HistRangeAcc r;
+  range_clear(r);
   jb_for_rows_single(d, [&](int64_t xb, bool ok) {
     const double a = d.x_is_float ? __longlong_as_double(xb) : (double)xb;
     const bool finite = a - a == 0.0;
@@ -76,34 +65,7 @@ __global__ __launch_bounds__(kHistBlock) void hist_range_kernel(const HistLaunch
       r.sum_squared += a * a;  // (the square rounds on its own: the build does not contract)
     }
   });
-  hist_range_wave_reduce(r);
-  __shared__ HistRangePartial sh[kHistWaves];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) sh[wave] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    HistRangePartial t = sh[0];
-    for (int w = 1; w < kHistWaves; w++) hist_range_fold(t, sh[w]);
-    partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-  }
-}
-
-// the per-workgroup partials of a launch into the tasks' running states.  grid = tasks, one wave each.
-__global__ __launch_bounds__(64) void hist_range_reduce_kernel(const HistLaunch L,
-                                                               const HistRangePartial *__restrict__ partials,
-                                                               int blocks_per_task, HistRangeAcc *__restrict__ accs) {
-  const int task = blockIdx.x;
-  HistRangePartial r = {0, 0, INFINITY, -INFINITY, 0.0, 0.0};
-  for (int i = threadIdx.x; i < blocks_per_task; i += 64) hist_range_fold(r, partials[(size_t)task * blocks_per_task + i]);
-  hist_range_wave_reduce(r);
-  if (threadIdx.x != 0) return;
-  HistRangeAcc &acc = accs[L.acc_index[task]];
-  acc.n += r.n;
-  acc.non_finite += r.non_finite;
-  acc.min = fmin(acc.min, r.min);
-  acc.max = fmax(acc.max, r.max);
-  acc.sum += r.sum;
-  acc.sum_squared += r.sum_squared;
+  range_block_store<kHistBlock>(r, partials);
 }
 
 // dynamic LDS: hist_lds_bytes(buckets) of the task this workgroup works on -- B + 1 edges, then B 32-bit counters
@@ -118,7 +80,6 @@ __global__ __launch_bounds__(kHistBlock) void hist_counts_kernel(const HistLaunc
   for (uint32_t c = threadIdx.x; c <= B; c += kHistBlock) edges[c] = g_edges[c];
   for (uint32_t c = threadIdx.x; c < B; c += kHistBlock) cells[c] = 0;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
   const uint32_t last = B - 1;  // the last bucket, and the last interior edge (B >= 1)
   const double e0 = edges[0], e_end = edges[B];
   const double span = edges[last] - e0;
@@ -156,40 +117,18 @@ __global__ __launch_bounds__(kHistBlock) void hist_counts_kernel(const HistLaunc
     const bool below = !(x >= e0);
     const uint32_t cell = live ? (below ? last : k) : 0u;  // <= last: k counts at most `last` edges
     else_rows += live && (below || (k == last && !(x < e_end))) ? 1u : 0u;
-    const unsigned long long todo = __ballot(live);
-    if (todo == 0) return;
-    const int leader = __ffsll((long long)todo) - 1;
-    const uint32_t first = (uint32_t)__shfl((int)cell, leader, 64);
-    const unsigned long long same = __ballot(live && cell == first);
-    if (lane == leader)
-      atomicAdd(&cells[first], (unsigned int)__popcll(same));
-    else if (live && cell != first)
-      atomicAdd(&cells[cell], 1u);
+    bin_add(cells, live, cell);
   });
   __syncthreads();
-  for (uint32_t c = threadIdx.x; c < B; c += kHistBlock) {
-    const unsigned int v = cells[c];
-    if (v) atomicAdd(&out[c], (unsigned long long)v);
-  }
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-    else_rows += __shfl_down(else_rows, dlt, 64);
-    non_finite += __shfl_down(non_finite, dlt, 64);
-  }
-  if (lane == 0) {
-    if (else_rows) atomicAdd(&out[B], (unsigned long long)else_rows);
-    if (non_finite) atomicAdd(&out[B + 1], (unsigned long long)non_finite);
-  }
+  bin_flush<kHistBlock>(cells, B, out);
+  tail_flush(else_rows, non_finite, out + B);
 }
 
-size_t hist_range_partial_bytes() { return sizeof(HistRangePartial); }
-
-void launch_hist_range(const HistLaunch &L, int n_tasks, int blocks_per_task, void *d_partials, HistRangeAcc *d_accs,
-                       hipStream_t stream) {
-  hipLaunchKernelGGL(hist_range_kernel, dim3(blocks_per_task, n_tasks), dim3(kHistBlock), 0, stream, L,
-                     (HistRangePartial *)d_partials);
-  hipLaunchKernelGGL(hist_range_reduce_kernel, dim3(n_tasks), dim3(64), 0, stream, L,
-                     (const HistRangePartial *)d_partials, blocks_per_task, d_accs);
+void launch_hist_range(const HistLaunch &L, int n_tasks, int blocks_per_task, HistRangeAcc *d_partials,
+                       HistRangeAcc *d_accs, hipStream_t stream) {
+  hipLaunchKernelGGL(hist_range_kernel, dim3(blocks_per_task, n_tasks), dim3(kHistBlock), 0, stream, L, d_partials);
+  hipLaunchKernelGGL((range_reduce_kernel<HistLaunch, HistRangeAcc>), dim3(n_tasks), dim3(64), 0, stream, L,
+                     (const HistRangeAcc *)d_partials, blocks_per_task, d_accs);
 }
 
 // `lds_bytes`: hist_lds_bytes of the launch's largest task

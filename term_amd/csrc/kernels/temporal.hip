@@ -18,6 +18,7 @@
 // 1970 are negative.
 #include <hip/hip_runtime.h>
 
+#include "bin_count.h"
 #include "device_types.h"
 #include "row_walk.h"
 
@@ -42,19 +43,6 @@ __device__ __forceinline__ bool tp_time_of_day(int64_t t, int64_t lo, int64_t hi
   return lo <= tod && tod <= hi;
 }
 
-// the wave's two counters into the task's
-__device__ __forceinline__ void tp_flush(uint32_t considered, uint32_t passed, unsigned long long *__restrict__ out) {
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-    considered += __shfl_down(considered, dlt, 64);
-    passed += __shfl_down(passed, dlt, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (considered) atomicAdd(&out[0], (unsigned long long)considered);
-    if (passed) atomicAdd(&out[1], (unsigned long long)passed);
-  }
-}
-
 template <int64_t kTicksPerSecond>
 __device__ __forceinline__ void tp_scan_time_of_day(const ComomentColDesc &d, const TemporalParams &P,
                                                     unsigned long long *__restrict__ out) {
@@ -75,7 +63,7 @@ __device__ __forceinline__ void tp_scan_time_of_day(const ComomentColDesc &d, co
       passed += ok && pass ? 1u : 0u;
     });
   }
-  tp_flush(considered, passed, out);
+  tail_flush(considered, passed, out);
 }
 
 }  // namespace
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(const Temporal
       considered += ok ? 1u : 0u;
       passed += ok && pass ? 1u : 0u;
     });
-    tp_flush(considered, passed, out);
+    tail_flush(considered, passed, out);
   } else if (P.mode == kTemporalRange) {
     uint32_t considered = 0, passed = 0;
     const int64_t lo = P.lo, hi = P.hi;
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(const Temporal
       considered += ok ? 1u : 0u;
       passed += ok && lo <= t && t <= hi ? 1u : 0u;
     });
-    tp_flush(considered, passed, out);
+    tail_flush(considered, passed, out);
   } else {
     switch (P.ticks_per_second) {  // (one of the four: tgx_plan_set_temporal)
       case 1: tp_scan_time_of_day<1>(d, P, out); break;

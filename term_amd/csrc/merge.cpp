@@ -1,5 +1,5 @@
 // merge.cpp -- tgx_merge: folds partial states of one plan into another, every aggregate kind (scan, count,
-// co-moments, HyperLogLog, exact key sets, KLL, regex, joint bins, temporal, histograms).  Split off distinct_state.cpp.
+// co-moments, HyperLogLog, exact key sets, KLL, regex, the kinds of side_check.h).  Split off distinct_state.cpp.
 #include "api_internal.h"
 
 extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state *const *srcs, size_t n_srcs,
@@ -77,9 +77,8 @@ extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state 
     }
     TGX_TRY(kll_merge_states(dst, src, err));
     TGX_TRY(regex_merge_states(dst, src, err));
-    TGX_TRY(joint_merge_states(dst, src, err));
-    TGX_TRY(temporal_merge_states(dst, src, err));
-    TGX_TRY(hist_merge_states(dst, src, err));
+    for (auto &side : dst->side)
+      if (side) TGX_TRY(side->merge_from(dst, src, err));
   }
   return TGX_OK;
 } catch (...) {

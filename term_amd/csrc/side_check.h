@@ -1,0 +1,221 @@
+// side_check.h -- the check kinds that run beside the fused pass and share one shape: TGX_CHECK_JOINT_BINS
+// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp) and TGX_CHECK_HISTOGRAM (histogram_device.cpp).
+//
+// A task is one spec.  Its running state is a few 64-bit counters on the device, plus a small range accumulator for the
+// kinds that have a range phase; rows seen are counted on the host.  What is merged in from other states or read from a
+// blob is kept on the host (`host`) and added when the state is read (`gather`).  The rest of the library sees a
+// SideCheck per kind in tgx_state::side, in the order of the blob's sections (null: the plan has no task of the kind);
+// SideState<K> is everything the kinds have in common, a kind K adds what its tasks count and how they are launched.
+#pragma once
+#include <memory>
+
+#include "internal.h"
+#include "wire_io.h"
+
+namespace tgx {
+
+enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2 };  // (kNumSide: internal.h)
+TGX_HIDDEN inline int side_index(int kind) {
+  return kind == TGX_CHECK_JOINT_BINS ? kSideJoint : kind == TGX_CHECK_TEMPORAL ? kSideTemporal : kSideHist;
+}
+
+struct TGX_HIDDEN SideCheck {
+  virtual ~SideCheck() {}
+  // (the caller has waited for the stream)
+  virtual tgx_status reset(tgx_state *st, tgx_error *err) = 0;
+  // one batch (device views of the plan's columns) through the tasks' kernels
+  virtual tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) = 0;
+  virtual tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) = 0;
+  virtual tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) = 0;
+  // the blob's section: present only when the plan has such tasks (blobs of other plans keep their bytes)
+  virtual tgx_status serialize(tgx_state *st, Writer &w, tgx_error *err) = 0;
+  virtual tgx_status deserialize(tgx_state *st, Reader &r, tgx_error *err) = 0;
+};
+
+tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+// every task has its parameters (tgx_plan_set_temporal)?  Asked by tgx_state_create
+tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
+TGX_HIDDEN SideCheck *joint_state_new(const tgx_plan *plan);
+TGX_HIDDEN SideCheck *temporal_state_new(const tgx_plan *plan);
+TGX_HIDDEN SideCheck *hist_state_new(const tgx_plan *plan);
+// the fresh state of the plan's tasks of kind `index`, or null when it has none
+TGX_HIDDEN inline SideCheck *side_state_new(int index, const tgx_plan *plan) {
+  SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new};
+  return make[index](plan);
+}
+
+// ---- what the kinds' updates share -----------------------------------------------------------------------------------
+constexpr int kSidePerLaunch = 8;  // tasks of one launch (grid.y)
+static_assert(kMaxJointPerLaunch == kSidePerLaunch && kMaxTemporalPerLaunch == kSidePerLaunch &&
+                  kMaxHistPerLaunch == kSidePerLaunch, "the kinds' launch descriptors hold kSidePerLaunch tasks");
+
+// the tasks that are `in_phase`, in launches of up to kSidePerLaunch: launch(slots, n)
+template <class Task, class InPhase, class Launch>
+TGX_HIDDEN inline tgx_status side_launches(const std::vector<Task> &tasks, InPhase in_phase, Launch launch) {
+  std::vector<int> slots;
+  for (size_t k = 0; k < tasks.size(); k++)
+    if (in_phase(tasks[k])) slots.push_back((int)k);
+  for (size_t t0 = 0; t0 < slots.size(); t0 += kSidePerLaunch)
+    TGX_TRY(launch(slots.data() + t0, (int)std::min<size_t>(kSidePerLaunch, slots.size() - t0)));
+  return TGX_OK;
+}
+
+// workgroups per task: 16 rows a lane before another workgroup is worth its launch; `per_cu` workgroups a CU, shared by
+// the `n_tasks` tasks of the launch
+TGX_HIDDEN inline int side_blocks(int64_t nrows, int block, int n_cu, int per_cu, int n_tasks) {
+  return (int)std::min<int64_t>(std::max<int64_t>(1, (nrows + block * 16 - 1) / (block * 16)),
+                                std::max(32, (n_cu * per_cu) / n_tasks));
+}
+
+// (a lane's, a wave's and a workgroup's counters are 32-bit)
+TGX_HIDDEN inline tgx_status side_rows_fit(const char *kind, int64_t nrows, int blocks, tgx_error *err) {
+  if (nrows / blocks >= ((int64_t)1 << 32))
+    return fail(err, TGX_UNSUPPORTED, "%s: a batch of %lld rows is too long", kind, (long long)nrows);
+  return TGX_OK;
+}
+
+// a column as the x / y side of a launch's descriptor; what reading it moves (the profile's bytes figure)
+TGX_HIDDEN inline uint64_t side_fill_x(ComomentColDesc &d, const tgx_column &x) {
+  d.x = x.values;
+  d.xv = x.validity;
+  d.xoff = x.offset;
+  d.length = x.length;
+  d.x_is_float = x.type == TGX_FLOAT64;
+  return (uint64_t)x.length * 8 + (x.validity ? (uint64_t)(x.length + 7) / 8 : 0);
+}
+TGX_HIDDEN inline uint64_t side_fill_y(ComomentColDesc &d, const tgx_column &y) {
+  d.y = y.values;
+  d.yv = y.validity;
+  d.yoff = y.offset;
+  d.y_is_float = y.type == TGX_FLOAT64;
+  return (uint64_t)y.length * 8 + (y.validity ? (uint64_t)(y.length + 7) / 8 : 0);
+}
+
+// ---- the state of one kind's tasks -----------------------------------------------------------------------------------
+// K gives: Task, Host (one task's state as the host sees it), Range (the device's range accumulator; kRanged: whether
+// there is one), kIndex, kName, kMagic, kDiffers (what two states of one plan can still differ in, or null), and
+//   tasks(plan)                         the plan's tasks of the kind
+//   words(task)                         64-bit device counters of the task
+//   range_identity()
+//   fresh(task)                         the identity of `Host`
+//   shape(host)                         what must agree before two hosts are merged
+//   from_device(task, rows, range, w)   the device part as a Host
+//   merge_host(a, b)
+//   write(task, host, w)                the task's part of the blob's section
+//   read(task, host, r, k, err)         ... read back into a fresh `host`; returns TGX_OK when the blob has run out
+template <class K>
+struct TGX_HIDDEN SideState : SideCheck {
+  typedef typename K::Host Host;
+  typedef typename K::Range Range;
+
+  std::vector<Host> host;            // merged in / deserialized
+  std::vector<int64_t> device_rows;  // rows the device part has seen
+  std::vector<size_t> word_off;      // per task: first of its counters in d_counts
+  size_t n_words = 0;
+  bool device_ready = false;
+  DevBuf d_range, d_counts, d_partials;
+  std::vector<Range> identity;  // (kept alive: uploaded asynchronously)
+
+  explicit SideState(const tgx_plan *plan) {
+    const auto &tasks = K::tasks(plan);
+    device_rows.assign(tasks.size(), 0);
+    for (const auto &t : tasks) {
+      host.push_back(K::fresh(t));
+      word_off.push_back(n_words);
+      n_words += K::words(t);
+    }
+  }
+
+  static SideState *of(tgx_state *st) { return static_cast<SideState *>(st->side[K::kIndex].get()); }
+
+  // what a kind uploads once per state
+  virtual tgx_status device_init_extra(tgx_state *, tgx_error *) { return TGX_OK; }
+
+  tgx_status device_clear(tgx_state *st, tgx_error *err) {
+    if (!identity.empty())
+      HIP_TRY(hipMemcpyAsync(d_range.p, identity.data(), identity.size() * sizeof(Range), hipMemcpyHostToDevice,
+                             st->stream));
+    if (n_words) HIP_TRY(hipMemsetAsync(d_counts.p, 0, n_words * sizeof(unsigned long long), st->stream));
+    return TGX_OK;
+  }
+
+  tgx_status device_init(tgx_state *st, tgx_error *err) {
+    if (device_ready) return TGX_OK;
+    if (K::kRanged) {
+      identity.assign(host.size(), K::range_identity());
+      HIP_TRY(d_range.reserve(identity.size() * sizeof(Range)));
+    }
+    if (n_words) HIP_TRY(d_counts.reserve(n_words * sizeof(unsigned long long)));
+    TGX_TRY(device_init_extra(st, err));
+    TGX_TRY(device_clear(st, err));
+    device_ready = true;
+    return TGX_OK;
+  }
+
+  // host part + device part of every task (the device part stays where it is)
+  tgx_status gather(tgx_state *st, std::vector<Host> *out, tgx_error *err) {
+    const auto &tasks = K::tasks(st->plan);
+    TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
+    *out = host;
+    if (!device_ready) return TGX_OK;
+    std::vector<Range> ranges(identity.size());
+    std::vector<unsigned long long> words(n_words);
+    if (!ranges.empty())
+      HIP_TRY(hipMemcpyAsync(ranges.data(), d_range.p, ranges.size() * sizeof(Range), hipMemcpyDeviceToHost, st->stream));
+    if (n_words)
+      HIP_TRY(hipMemcpyAsync(words.data(), d_counts.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    for (size_t k = 0; k < tasks.size(); k++)
+      K::merge_host((*out)[k], K::from_device(tasks[k], device_rows[k], K::kRanged ? ranges[k] : Range(),
+                                              words.data() + word_off[k]));
+    return TGX_OK;
+  }
+
+  tgx_status reset(tgx_state *st, tgx_error *err) override {
+    const auto &tasks = K::tasks(st->plan);
+    for (size_t k = 0; k < tasks.size(); k++) host[k] = K::fresh(tasks[k]);
+    std::fill(device_rows.begin(), device_rows.end(), 0);
+    if (device_ready) TGX_TRY(device_clear(st, err));
+    return TGX_OK;
+  }
+
+  tgx_status merge_from(tgx_state *, tgx_state *src, tgx_error *err) override {
+    std::vector<Host> g;
+    TGX_TRY(of(src)->gather(src, &g, err));
+    for (size_t k = 0; k < g.size(); k++) {
+      // (states of one plan share what the plan fixes; a blob made under something else was refused by
+      // tgx_state_deserialize)
+      if (K::shape(g[k]) != K::shape(host[k]))
+        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", K::kName, k,
+                    K::kDiffers);
+      K::merge_host(host[k], g[k]);
+    }
+    return TGX_OK;
+  }
+
+  // section: { u32 magic, u32 tasks; per task what K::write writes }
+  tgx_status serialize(tgx_state *st, Writer &w, tgx_error *err) override {
+    const auto &tasks = K::tasks(st->plan);
+    std::vector<Host> g;
+    TGX_TRY(gather(st, &g, err));
+    w.pod(K::kMagic);
+    w.pod((uint32_t)tasks.size());
+    for (size_t k = 0; k < g.size(); k++) K::write(tasks[k], g[k], w);
+    return TGX_OK;
+  }
+
+  tgx_status deserialize(tgx_state *st, Reader &r, tgx_error *err) override {
+    const auto &tasks = K::tasks(st->plan);
+    const uint32_t magic = r.pod<uint32_t>(), n = r.pod<uint32_t>();
+    if (!r.ok || magic != K::kMagic || n != tasks.size())
+      return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan (%s section)", K::kName);
+    for (size_t k = 0; k < tasks.size() && r.ok; k++) TGX_TRY(K::read(tasks[k], host[k], r, k, err));
+    if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
+    return TGX_OK;
+  }
+};
+
+}  // namespace tgx

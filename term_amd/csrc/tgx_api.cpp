@@ -301,23 +301,14 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
-      case TGX_CHECK_JOINT_BINS: {
+      case TGX_CHECK_JOINT_BINS:
+      case TGX_CHECK_TEMPORAL:
+      case TGX_CHECK_HISTOGRAM: {  // the kinds of side_check.h, in its order
+        tgx_status (*const add[kNumSide])(tgx_plan *, int, int *, tgx_error *) = {joint_plan_add, temporal_plan_add,
+                                                                                  hist_plan_add};
         int slot = -1;
-        TGX_TRY(joint_plan_add(plan.get(), (int)i, &slot, err));
-        max_col = std::max(max_col, sp.column2);
-        plan->bind[i].slot = slot;
-        break;
-      }
-      case TGX_CHECK_TEMPORAL: {
-        int slot = -1;
-        TGX_TRY(temporal_plan_add(plan.get(), (int)i, &slot, err));
-        max_col = std::max(max_col, sp.column2);
-        plan->bind[i].slot = slot;
-        break;
-      }
-      case TGX_CHECK_HISTOGRAM: {
-        int slot = -1;
-        TGX_TRY(hist_plan_add(plan.get(), (int)i, &slot, err));
+        TGX_TRY(add[side_index(sp.kind)](plan.get(), (int)i, &slot, err));
+        if (sp.kind != TGX_CHECK_HISTOGRAM) max_col = std::max(max_col, sp.column2);
         plan->bind[i].slot = slot;
         break;
       }
@@ -542,9 +533,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   regex_state_init(st);
   kll_state_init(st);
   spearman_state_init(st);
-  joint_state_init(st);
-  temporal_state_init(st);
-  hist_state_init(st);
+  for (int i = 0; i < kNumSide; i++) st->side[i].reset(side_state_new(i, plan));
 }
 
 // one launch for all the small accumulators of a state (fresh, or reset): the scan accumulators to their identities,
@@ -644,9 +633,7 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   regex_state_free(st);
   kll_state_free(st);
   spearman_state_free(st);
-  joint_state_free(st);
-  temporal_state_free(st);
-  hist_state_free(st);
+  for (auto &side : st->side) side.reset();  // (their device blocks: inside the scope, as everything above)
   coalesce_drop(st);  // (copy threads that are still filling an arena let go of it first)
   for (int k = 0; k < 2; k++) {
     if (st->arena_event[k]) (void)hipEventDestroy(st->arena_event[k]);
@@ -733,9 +720,8 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   kll_state_reset(st);
   regex_state_reset(st);
   spearman_state_reset(st);
-  TGX_TRY(joint_state_reset(st, err));
-  TGX_TRY(temporal_state_reset(st, err));
-  TGX_TRY(hist_state_reset(st, err));
+  for (auto &side : st->side)
+    if (side) TGX_TRY(side->reset(st, err));
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
   st->hll_mode.assign(plan->hll.size(), 0);
   if (st->device_ready && st->d_hll.p)
@@ -1121,13 +1107,9 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
         TGX_TRY(spearman_fill_result(st, b.slot, r, err));
         break;
       case TGX_CHECK_JOINT_BINS:
-        TGX_TRY(joint_fill_result(st, b.slot, r, err));
-        break;
       case TGX_CHECK_TEMPORAL:
-        TGX_TRY(temporal_fill_result(st, b.slot, r, err));
-        break;
       case TGX_CHECK_HISTOGRAM:
-        TGX_TRY(hist_fill_result(st, b.slot, r, err));
+        TGX_TRY(st->side[side_index(b.kind)]->fill_result(st, b.slot, r, err));
         break;
       default:
         break;

@@ -937,9 +937,8 @@ tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *co
     TGX_TRY(scan_columns(plan, st, dev, nrows, f, err));
     TGX_TRY(count_validity(plan, st, dev, err));
     TGX_TRY(unfused_comoments(plan, st, dev, nrows, f, err));
-    TGX_TRY(joint_update(st, dev, nrows, err));
-    TGX_TRY(temporal_update(st, dev, nrows, err));
-    TGX_TRY(hist_update(st, dev, nrows, err));
+    for (auto &side : st->side)
+      if (side) TGX_TRY(side->update(st, dev, nrows, err));
     TGX_TRY(late_key_sets(plan, st, dev, columns, f, err));
     TGX_TRY(sketches(plan, st, dev, columns, f, err));
   }

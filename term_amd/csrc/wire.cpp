@@ -1,6 +1,6 @@
 // wire.cpp -- tgx_state_serialize / tgx_state_deserialize (blobs v3; term_amd/wire.py documents the layout).  The
-// sections of the check modules (KLL, pattern checks, JOINT_BINS) are written and read by the modules themselves, through
-// the Writer / Reader of wire_io.h.  Split off tgx_api.cpp in round 4.
+// sections of the check modules (KLL, pattern checks, the kinds of side_check.h) are written and read by the modules
+// themselves, through the Writer / Reader of wire_io.h.  Split off tgx_api.cpp in round 4.
 #include "api_internal.h"
 #include "wire_io.h"
 
@@ -63,9 +63,8 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
     if (!g.hll[k].empty()) w.put(g.hll[k].data(), kHllRegisters);
   }
   // (behind everything else, and only for plans with such checks: blobs of every other plan keep their bytes)
-  TGX_TRY(joint_serialize(st, w, err));
-  TGX_TRY(temporal_serialize(st, w, err));
-  TGX_TRY(hist_serialize(st, w, err));
+  for (auto &side : st->side)
+    if (side) TGX_TRY(side->serialize(st, w, err));
   *len = w.len;
   if (buf && w.len > cap) return fail(err, TGX_INVALID_ARGUMENT, "buffer too small: need %zu bytes", w.len);
   return TGX_OK;
@@ -157,9 +156,8 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
         r.get(st->h_hll[k].data(), kHllRegisters);
       }
     }
-    if (r.ok) TGX_TRY(joint_deserialize(st.get(), r, err));
-    if (r.ok) TGX_TRY(temporal_deserialize(st.get(), r, err));
-    if (r.ok) TGX_TRY(hist_deserialize(st.get(), r, err));
+    for (auto &side : st->side)
+      if (side && r.ok) TGX_TRY(side->deserialize(st.get(), r, err));
   }
   if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
   *out = st.release();
