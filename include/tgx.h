@@ -226,7 +226,31 @@ typedef enum tgx_check_kind {
    * Columns: Int64, Float64, and Int32 / Float32 / Int8 .. UInt32 through the widening staging; UInt64, Boolean and every
    * string layout are TGX_UNSUPPORTED.  The state is additive: tgx_merge, state blobs and tgx_allreduce combine the
    * extremes by MIN / MAX and n, the sums and the buckets by addition. */
-  TGX_CHECK_HISTOGRAM = 12
+  TGX_CHECK_HISTOGRAM = 12,
+  /* The window query behind TemporalOrderingConstraint's MaxTimeGap mode
+   *                                            TG/constraints/temporal_ordering.rs:454-481
+   *   SELECT ts - LAG(ts) OVER ([PARTITION BY g] ORDER BY ts) FROM t WHERE ts IS NOT NULL
+   * `column` is the timestamp column t (Int64-shaped: Timestamp / Date64 / Duration / Int64, in its own ticks), `column2`
+   * the group column g or -1.  The threshold comes with tgx_plan_set_time_gap (below); a spec without it makes
+   * tgx_state_create fail.  The rules:
+   *   - a row whose t is NULL is seen and otherwise ignored (the query's WHERE clause; there is no flag that keeps it);
+   *   - without g the remaining rows form one partition; with g there is one partition per value of g, and ALL rows
+   *     whose g is NULL form one partition of their own (SQL's PARTITION BY);
+   *   - within a partition the timestamps are put in non-decreasing order; every row but the first has a gap
+   *     t_i - t_(i-1), taken as an unsigned 64-bit value (INT64_MAX - INT64_MIN is 2^64 - 1, not -1); equal timestamps
+   *     give gap 0, so the answer depends only on the multiset of (g, t), never on tie order or batching;
+   *   - gaps = non-NULL rows - non-empty partitions; violations = gaps with gap > max_gap (a negative max_gap makes every
+   *     gap a violation, a gap equal to max_gap is none); largest_gap = the maximum gap, unsigned, 0 when there is none.
+   * The reference compares EXTRACT(EPOCH FROM ts - LAG(ts)), a Float64 number of seconds, with the literal; this check
+   * compares ticks exactly (the two agree for every gap below 2^53 ticks).
+   * Read with tgx_time_gap_get; tgx_result carries total = rows seen, non_null = gaps, matches = gaps - violations.
+   * Group columns: Int64-shaped, and Int32 / Date32 / Int8 .. UInt32 through the widening staging; UInt64, Boolean, floats
+   * and every string or binary layout are TGX_UNSUPPORTED from tgx_update, as is every timestamp column that is not
+   * Int64-shaped.  The state RETAINS its rows on the device until it is reset (8 B per row, 16 B with a group) and sorts
+   * them when it is read; specs on the same (t, g) that differ only in max_gap share one copy and one sort.  More than
+   * 2^32 - 1 retained rows in a task are TGX_UNSUPPORTED.  Such a state is not additive: tgx_merge, tgx_state_serialize
+   * and tgx_allreduce on a state whose TIME_GAP task holds rows return TGX_UNSUPPORTED (an empty one passes). */
+  TGX_CHECK_TIME_GAP = 13
 } tgx_check_kind;
 
 enum {
@@ -413,6 +437,15 @@ typedef struct tgx_temporal_params {
 } tgx_temporal_params;
 tgx_status tgx_plan_set_temporal(tgx_plan *plan, size_t spec_index, const tgx_temporal_params *params, tgx_error *err);
 
+/* TGX_CHECK_TIME_GAP: the threshold of spec `spec_index`, in the timestamp column's ticks.  Like the TEMPORAL parameters
+ * it can be set until the plan's first state exists; afterwards, and for a spec of another kind, the call is refused
+ * with TGX_INVALID_ARGUMENT.  `flags` must be 0. */
+typedef struct tgx_time_gap_params {
+  int64_t max_gap; /* a gap is a violation iff gap > max_gap (negative: every gap is one) */
+  uint32_t flags;  /* 0 */
+} tgx_time_gap_params;
+tgx_status tgx_plan_set_time_gap(tgx_plan *plan, size_t spec_index, const tgx_time_gap_params *params, tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -561,6 +594,18 @@ typedef struct tgx_temporal_counts {
   uint64_t violations;  /* the SQL's SUM(CASE WHEN <predicate> THEN 0 ELSE 1 END); 0 when nothing was considered */
 } tgx_temporal_counts;
 tgx_status tgx_temporal_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_temporal_counts *out,
+                            tgx_error *err);
+
+/* ---- time gaps between neighbouring timestamps (TGX_CHECK_TIME_GAP; TG/constraints/temporal_ordering.rs:454-481) -- */
+typedef struct tgx_time_gap_counts {
+  uint64_t seen;        /* rows handed to tgx_update */
+  uint64_t rows;        /* of them, rows whose timestamp is not NULL */
+  uint64_t gaps;        /* rows - non-empty partitions */
+  uint64_t violations;  /* gaps above the spec's max_gap */
+  uint64_t largest_gap; /* unsigned ticks; 0 when there is no gap */
+} tgx_time_gap_counts;
+/* Sorts the retained rows (the answer is kept until the next batch or reset: a second read does not sort again). */
+tgx_status tgx_time_gap_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_time_gap_counts *out,
                             tgx_error *err);
 
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------

@@ -59,7 +59,10 @@ tgx_status tgx_host_constraint_plan_json(const char *constraint_json, char **out
  * -> the tgx_temporal_params the suite runner hands to tgx_plan_set_temporal, in the column's ticks:
  * {"column", "column2", "mode", "flags", "delta", "ticks_per_second", "tod_lo", "tod_hi", "lo", "hi"}.  What the GPU path
  * does not take (a unit it cannot know, a time zone other than UTC, MaxTimeGap, EventSequence, an unreadable literal) is
- * TGX_INVALID_ARGUMENT with the constraint's error text: hand such a constraint to the stock path.  Needs no device. */
+ * TGX_INVALID_ARGUMENT with the constraint's error text: hand such a constraint to the stock path.  Needs no device.
+ * A max_time_gap constraint that carries "window_on_device": true plans a TGX_CHECK_TIME_GAP spec instead, and the
+ * answer is the tgx_time_gap_params of that spec: {"column", "column2" (the group column or ""), "kind": 13, "max_gap"
+ * (max_gap_seconds x the column's ticks per second), "flags"}.  Its timestamp column must be a Timestamp (any zone). */
 tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char *arrow_types_json, char **out_json,
                                          tgx_error *err);
 

@@ -16,6 +16,7 @@ TEMPORAL_ORDER, TEMPORAL_TIME_OF_DAY, TEMPORAL_RANGE = 1, 2, 3
 TEMPORAL_KEEP_NULLS, TEMPORAL_WEEKDAYS_ONLY = 1, 2
 HISTOGRAM = 12  # the histogram of a numeric column, in two phases (Plan.set_histogram_edges)
 HISTOGRAM_MAX_BUCKETS = 1000
+TIME_GAP = 13  # gaps between neighbouring timestamps, whole table or per group (Plan.set_time_gap)
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -94,6 +95,17 @@ class TemporalParams(C.Structure):
 class TemporalCounts(C.Structure):
     """tgx_temporal_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("violations", C.c_uint64)]
+
+
+class TimeGapParams(C.Structure):
+    """tgx_time_gap_params (include/tgx.h)"""
+    _fields_ = [("max_gap", C.c_int64), ("flags", C.c_uint32)]
+
+
+class TimeGapCounts(C.Structure):
+    """tgx_time_gap_counts (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("rows", C.c_uint64), ("gaps", C.c_uint64), ("violations", C.c_uint64),
+                ("largest_gap", C.c_uint64)]
 
 
 class HistogramRange(C.Structure):
@@ -218,6 +230,8 @@ def lib():
         L.tgx_joint_counts.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), C.POINTER(u64), E]
         L.tgx_plan_set_temporal.argtypes = [vp, sz, C.POINTER(TemporalParams), E]
         L.tgx_temporal_get.argtypes = [vp, vp, sz, C.POINTER(TemporalCounts), E]
+        L.tgx_plan_set_time_gap.argtypes = [vp, sz, C.POINTER(TimeGapParams), E]
+        L.tgx_time_gap_get.argtypes = [vp, vp, sz, C.POINTER(TimeGapCounts), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -633,6 +647,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_temporal(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_time_gap(self, spec_index, max_gap, flags=0):
+        """tgx_plan_set_time_gap: the threshold of a TIME_GAP spec, in the column's ticks (before the plan's first state)"""
+        p = TimeGapParams(max_gap, flags)
+        err = _Error()
+        _check(lib().tgx_plan_set_time_gap(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
         lib().tgx_plan_get_fingerprint_key(self.h, out)
@@ -810,6 +830,14 @@ class State:
         err = _Error()
         _check(lib().tgx_temporal_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.considered, out.violations
+
+    # time gaps
+    def time_gap_counts(self, spec_index):
+        """tgx_time_gap_get: (seen, rows, gaps, violations, largest_gap)"""
+        out = TimeGapCounts()
+        err = _Error()
+        _check(lib().tgx_time_gap_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return out.seen, out.rows, out.gaps, out.violations, out.largest_gap
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -907,6 +907,7 @@ extern "C" tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *st, tgx_com
   if (!comm) return fail(err, TGX_INVALID_ARGUMENT, "comm is NULL");
   bind_thread();  // (a tokio worker / any thread: HIP's current device is per thread)
   TGX_TRY(coalesce_flush(st, err));  // batches tgx_update has only noted so far
+  TGX_TRY(timegap_check_mergeable(st, "tgx_allreduce", err));  // (before anything is exchanged)
   if (comm->ops.device_buffers) {
     TGX_TRY(need_device(err));
     TGX_TRY(state_init_device(st, err));

@@ -24,6 +24,7 @@
 #include "regex_device.h"
 #include "side_check.h"
 #include "spearman_device.h"
+#include "timegap_device.h"
 
 using namespace tgx;
 

@@ -94,7 +94,9 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
              ", \"weekdays_only\": " + (t.weekdays_only ? "true" : "false") + ", \"tolerance_seconds\": " +
              std::to_string(t.tolerance_seconds) + ", \"start_time\": " + json::quote(t.start_time) +
              ", \"end_time\": " + json::quote(t.end_time) + ", \"min_date\": " + text(t.min_date) +
-             ", \"max_date\": " + text(t.max_date) + "}";
+             ", \"max_date\": " + text(t.max_date) +
+             (t.mode == kTemporalTimeGapMode ? ", \"max_gap_seconds\": " + std::to_string(t.max_gap_seconds) : std::string()) +
+             "}";
       }
       o += "}";
     }
@@ -236,6 +238,13 @@ extern "C" tgx_status tgx_host_temporal_params_json(const char *constraint_json,
     if (reqs.size() != 1 || !reqs[0].temporal)
       return hfail(err, TGX_INVALID_ARGUMENT, "not a temporal_ordering constraint");
     const SpecRequest &r = reqs[0];
+    if (r.kind == TGX_CHECK_TIME_GAP) {  // MaxTimeGap with window_on_device: the tgx_time_gap_params of its spec
+      const tgx_time_gap_params g = time_gap_params(*r.temporal, types.get_str(r.column), types.get_str(r.column2));
+      *out_json = dup_string("{\"column\": " + json::quote(r.column) + ", \"column2\": " + json::quote(r.column2) +
+                             ", \"kind\": " + std::to_string(r.kind) + ", \"max_gap\": " + std::to_string(g.max_gap) +
+                             ", \"flags\": " + std::to_string(g.flags) + "}");
+      return TGX_OK;
+    }
     const tgx_temporal_params p = temporal_params(*r.temporal, types.get_str(r.column), types.get_str(r.column2));
     auto n = [](int64_t v) { return std::to_string(v); };
     *out_json = dup_string("{\"column\": " + json::quote(r.column) + ", \"column2\": " + json::quote(r.column2) +

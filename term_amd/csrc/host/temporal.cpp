@@ -172,7 +172,12 @@ TemporalOrderingConstraint &TemporalOrderingConstraint::max_time_gap(std::string
   validation_ = Validation::MaxTimeGap;
   column_ = std::move(column);
   group_by_.reset();
+  window_on_device_ = false;
   max_gap_seconds_ = max_gap_seconds;
+  return *this;
+}
+TemporalOrderingConstraint &TemporalOrderingConstraint::window_on_device(bool on) {
+  if (validation_ == Validation::MaxTimeGap) window_on_device_ = on;  // (ignored on every other type, as weekdays_only)
   return *this;
 }
 TemporalOrderingConstraint &TemporalOrderingConstraint::group_by(std::string column) {
@@ -224,7 +229,13 @@ std::vector<SpecRequest> TemporalOrderingConstraint::plan() const {
     case Validation::MaxTimeGap:
       require_identifier(column_);
       if (group_by_) require_identifier(*group_by_);
-      evaluation_error("MaxTimeGap validation is a LAG() OVER (ORDER BY ..) window query and is not on the GPU path");
+      if (!window_on_device_)
+        evaluation_error("MaxTimeGap validation is a LAG() OVER (ORDER BY ..) window query and is not on the GPU path");
+      r.kind = TGX_CHECK_TIME_GAP;  // (allow_nulls is not read: the query's WHERE ts IS NOT NULL stands either way)
+      if (group_by_) r.column2 = *group_by_;
+      t.mode = kTemporalTimeGapMode;
+      t.max_gap_seconds = max_gap_seconds_;
+      break;
     case Validation::EventSequence:
       require_identifier(column2_);
       require_identifier(column_);
@@ -235,6 +246,7 @@ std::vector<SpecRequest> TemporalOrderingConstraint::plan() const {
 }
 
 // :521-602.  The result carries total = rows seen, non_null = the query's COUNT(*), matches = COUNT(*) - violations
+// (MaxTimeGap, :551-601: COUNT(*) is the number of gaps; no gaps at all is a Success with metric 1.0)
 ConstraintResult TemporalOrderingConstraint::evaluate(const Inputs &in) const {
   const tgx_result &r = *in.results.at(0);
   const int64_t total_rows = r.non_null, violations = r.non_null - r.matches;
@@ -310,12 +322,29 @@ tgx_temporal_params temporal_params(const TemporalRequest &req, const std::strin
   return p;
 }
 
+tgx_time_gap_params time_gap_params(const TemporalRequest &req, const std::string &type, const std::string &group_type) {
+  if (req.mode != kTemporalTimeGapMode) evaluation_error("unknown temporal mode " + std::to_string(req.mode));
+  const ArrowTimestamp a = need_timestamp(type, "max time gap validation on the device", false);
+  static const char *const kGroupTypes[] = {"Int8", "Int16", "Int32", "Int64", "UInt8", "UInt16", "UInt32", "Date32", "Date64"};
+  bool group_ok = group_type.empty() || parse_arrow_type(group_type).is_timestamp;
+  for (const char *g : kGroupTypes) group_ok = group_ok || group_type == g;
+  if (!group_ok)
+    evaluation_error("max time gap validation on the device needs a group column of Int8 .. Int64, UInt8 .. UInt32, a date "
+                     "or a timestamp; the column is " + group_type + " (not on the GPU path)");
+  tgx_time_gap_params p;
+  memset(&p, 0, sizeof(p));
+  if (__builtin_mul_overflow(req.max_gap_seconds, a.ticks_per_second, &p.max_gap))
+    evaluation_error("Temporal validation query failed: the maximum gap overflows the column's unit");
+  return p;
+}
+
 Check::Builder &Check::Builder::temporal_ordering(std::string table) {
   return constraint(std::make_shared<TemporalOrderingConstraint>(std::move(table)));
 }
 
 // {"type": "temporal_ordering", "table": t, "validation": "before_after|business_hours|date_range|max_time_gap|
-//  event_sequence" (absent: the default object of TemporalOrderingConstraint::new), .. the builder calls' arguments ..}
+//  event_sequence" (absent: the default object of TemporalOrderingConstraint::new), .. the builder calls' arguments ..;
+//  "window_on_device": true with max_time_gap only}
 std::shared_ptr<Constraint> temporal_ordering_from_json(const json::Value &c) {
   auto t = std::make_shared<TemporalOrderingConstraint>(c.get_str("table", "data"));
   const std::string v = c.get_str("validation");
@@ -335,6 +364,7 @@ std::shared_ptr<Constraint> temporal_ordering_from_json(const json::Value &c) {
   } else if (v == "max_time_gap") {
     t->max_time_gap(c.get_str("timestamp_column"), c.get_i64("max_gap_seconds"));
     if (auto g = opt("group_by_column")) t->group_by(*g);
+    t->window_on_device(c.get_bool("window_on_device"));
   } else if (v == "event_sequence") {
     std::vector<std::string> seq;
     if (const json::Value *s = c.get("expected_sequence"))

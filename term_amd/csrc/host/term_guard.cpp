@@ -1303,7 +1303,8 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           if (r.column.empty() && r.kind == TGX_CHECK_COUNT && !table->column_names.empty())
             r.column = table->column_names[0];
           std::vector<const std::string *> named = {&r.column};
-          if (r.kind == TGX_CHECK_COMOMENTS || (r.kind == TGX_CHECK_TEMPORAL && !r.column2.empty()))
+          if (r.kind == TGX_CHECK_COMOMENTS ||
+              ((r.kind == TGX_CHECK_TEMPORAL || r.kind == TGX_CHECK_TIME_GAP) && !r.column2.empty()))
             named.push_back(&r.column2);
           for (const std::string &c2 : r.columns) named.push_back(&c2);
           for (const std::string *col : named) {
@@ -1315,7 +1316,10 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           if (p.error) break;
           if (r.temporal) {  // the unit rules (host/temporal.cpp): what is missing is this constraint's error
             try {
-              (void)temporal_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
+              if (r.kind == TGX_CHECK_TIME_GAP)
+                (void)time_gap_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
+              else
+                (void)temporal_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
             } catch (const TermError &e) {
               p.error = e.display();
               break;
@@ -1353,7 +1357,8 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       memset(&s, 0, sizeof(s));
       s.kind = r.kind;
       s.column = column_index(r.column);
-      s.column2 = r.kind == TGX_CHECK_COMOMENTS || (r.kind == TGX_CHECK_TEMPORAL && !r.column2.empty())
+      s.column2 = r.kind == TGX_CHECK_COMOMENTS ||
+                          ((r.kind == TGX_CHECK_TEMPORAL || r.kind == TGX_CHECK_TIME_GAP) && !r.column2.empty())
                       ? column_index(r.column2)
                       : -1;
       s.flags = r.flags;
@@ -1386,6 +1391,11 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
     for (size_t i = 0; s == TGX_OK && i < spec_requests.size(); i++) {
       const SpecRequest &r = spec_requests[i];
       if (!r.temporal) continue;
+      if (r.kind == TGX_CHECK_TIME_GAP) {
+        const tgx_time_gap_params gp = time_gap_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
+        s = tgx_plan_set_time_gap(hh.plan, i, &gp, &err);
+        continue;
+      }
       const tgx_temporal_params tp = temporal_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
       s = tgx_plan_set_temporal(hh.plan, i, &tp, &err);
     }

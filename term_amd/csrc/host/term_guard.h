@@ -147,17 +147,21 @@ struct CorrelationValidation {
 };
 
 // The unit-free parameters of a TGX_CHECK_TEMPORAL request (host/temporal.h turns them, with the columns' Arrow types,
-// into tgx_temporal_params): seconds, "HH:MM", TIMESTAMP literal texts
+// into tgx_temporal_params): seconds, "HH:MM", TIMESTAMP literal texts.  A TGX_CHECK_TIME_GAP request (MaxTimeGap with
+// window_on_device) carries kTemporalTimeGapMode and max_gap_seconds; host/temporal.h turns them into tgx_time_gap_params
+constexpr int kTemporalTimeGapMode = 4;  // (host side only: not a mode of tgx_temporal_params)
 struct TemporalRequest {
-  int mode = 0;  // TGX_TEMPORAL_ORDER / _TIME_OF_DAY / _RANGE
+  int mode = 0;  // TGX_TEMPORAL_ORDER / _TIME_OF_DAY / _RANGE, or kTemporalTimeGapMode
   bool allow_equal = false, allow_nulls = false, weekdays_only = false;
   int64_t tolerance_seconds = 0;
+  int64_t max_gap_seconds = 0;               // kTemporalTimeGapMode
   std::string start_time, end_time;          // "HH:MM"
   std::optional<std::string> min_date, max_date;
   bool operator==(const TemporalRequest &o) const {
     return mode == o.mode && allow_equal == o.allow_equal && allow_nulls == o.allow_nulls &&
            weekdays_only == o.weekdays_only && tolerance_seconds == o.tolerance_seconds && start_time == o.start_time &&
-           end_time == o.end_time && min_date == o.min_date && max_date == o.max_date;
+           end_time == o.end_time && min_date == o.min_date && max_date == o.max_date &&
+           max_gap_seconds == o.max_gap_seconds;
   }
 };
 
@@ -170,7 +174,8 @@ struct SpecRequest {
   std::string pattern;
   uint32_t kll_k = 0;
   uint64_t length_min = 0, length_max = ~0ull;  // LENGTH: inclusive character-count bounds
-  std::optional<TemporalRequest> temporal;      // TEMPORAL (`column2`: the after column in order mode)
+  std::optional<TemporalRequest> temporal;      // TEMPORAL (`column2`: the after column in order mode) and TIME_GAP
+                                                // (`column2`: the group column, or empty)
 };
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:

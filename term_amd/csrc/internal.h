@@ -257,6 +257,8 @@ struct tgx_plan {
   mutable std::atomic<bool> fp_key_locked{false};  // a state has been created: the key may not change any more
   void *regex = nullptr;     // tgx::RegexPlan (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanPlan (spearman_device.cpp)
+  void *timegap = nullptr;   // tgx::TimeGapPlan (timegap_device.cpp)
+  std::vector<char> timegap_on;  // a TIME_GAP check reads it: bit 0 as its timestamps, bit 1 as its group keys
 };
 
 namespace tgx {
@@ -648,6 +650,7 @@ struct tgx_state {
   void *kll = nullptr;    // tgx::KllDeviceState (kll_device.cpp)
   void *regex = nullptr;  // tgx::RegexState (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
+  void *timegap = nullptr;   // tgx::TimeGapState (timegap_device.cpp)
   // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms
   std::unique_ptr<tgx::SideCheck> side[tgx::kNumSide];
 

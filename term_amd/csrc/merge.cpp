@@ -14,6 +14,7 @@ extern "C" tgx_status tgx_merge(const tgx_plan *plan, tgx_state *dst, tgx_state 
       if (!src || src->plan != plan) return fail(err, TGX_INVALID_ARGUMENT, "src %zu does not belong to plan", i);
       if (src == dst) return fail(err, TGX_INVALID_ARGUMENT, "src %zu is dst", i);
       TGX_TRY(spearman_check_mergeable(src, err));
+      TGX_TRY(timegap_check_mergeable(src, "tgx_merge", err));
       TGX_TRY(coalesce_flush(src, err));  // (its noted batches decide which form an APPROX_DISTINCT task takes)
       for (size_t k = 0; k < plan->hll.size(); k++) {
         if (src->hll_mode[k] == 0) continue;

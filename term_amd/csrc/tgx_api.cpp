@@ -319,6 +319,13 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
+      case TGX_CHECK_TIME_GAP: {
+        max_col = std::max(max_col, sp.column2);
+        int slot = -1;
+        TGX_TRY(timegap_plan_add(plan.get(), (int)i, &slot, err));
+        plan->bind[i].slot = slot;
+        break;
+      }
       default:
         return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: unknown check kind %d", i, sp.kind);
     }
@@ -408,6 +415,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       P->needs_wide[i] |= sp_used[i];
       P->stats_on[i] |= sp_used[i];
     }
+    timegap_mark_used(P);
   }
   // re-point pattern pointers at the plan-owned copies
   for (size_t i = 0; i < n_specs; i++) {
@@ -424,6 +432,7 @@ extern "C" void tgx_plan_destroy(tgx_plan *plan) {
   if (!plan) return;
   regex_plan_free(plan);
   spearman_plan_free(plan);
+  timegap_plan_free(plan);
   delete plan;
 }
 extern "C" size_t tgx_plan_num_specs(const tgx_plan *plan) { return plan ? plan->specs.size() : 0; }
@@ -533,6 +542,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   regex_state_init(st);
   kll_state_init(st);
   spearman_state_init(st);
+  timegap_state_init(st);
   for (int i = 0; i < kNumSide; i++) st->side[i].reset(side_state_new(i, plan));
 }
 
@@ -600,6 +610,7 @@ extern "C" tgx_status tgx_state_create(const tgx_plan *plan, void *hip_stream, t
   if (!plan || !out) return fail(err, TGX_INVALID_ARGUMENT, "plan/out is NULL");
   *out = nullptr;
   TGX_TRY(temporal_plan_ready(plan, err));  // (before the plan is locked: the parameters can still follow)
+  TGX_TRY(timegap_plan_ready(plan, err));
   tgx_state *st = new tgx_state();
   state_init_host(st, plan);
   st->stream = (hipStream_t)hip_stream;
@@ -633,6 +644,7 @@ extern "C" void tgx_state_destroy(tgx_state *st) {
   regex_state_free(st);
   kll_state_free(st);
   spearman_state_free(st);
+  timegap_state_free(st);
   for (auto &side : st->side) side.reset();  // (their device blocks: inside the scope, as everything above)
   coalesce_drop(st);  // (copy threads that are still filling an arena let go of it first)
   for (int k = 0; k < 2; k++) {
@@ -720,6 +732,7 @@ extern "C" tgx_status tgx_state_reset(const tgx_plan *plan, tgx_state *st, tgx_e
   kll_state_reset(st);
   regex_state_reset(st);
   spearman_state_reset(st);
+  timegap_state_reset(st);
   for (auto &side : st->side)
     if (side) TGX_TRY(side->reset(st, err));
   st->h_hll.assign(plan->hll.size(), std::vector<uint8_t>());
@@ -1110,6 +1123,9 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
       case TGX_CHECK_TEMPORAL:
       case TGX_CHECK_HISTOGRAM:
         TGX_TRY(st->side[side_index(b.kind)]->fill_result(st, b.slot, r, err));
+        break;
+      case TGX_CHECK_TIME_GAP:
+        TGX_TRY(timegap_fill_result(st, (int)i, r, err));
         break;
       default:
         break;

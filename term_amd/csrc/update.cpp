@@ -258,6 +258,7 @@ tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column
       return fail(err, TGX_UNSUPPORTED, "column %d: HISTOGRAM takes numeric columns (type %d)", i, c.type);
     if (plan->temporal_on[i] && c.type != TGX_INT64)
       return fail(err, TGX_UNSUPPORTED, "column %d: TEMPORAL takes Int64-shaped columns (type %d)", i, c.type);
+    if (plan->timegap_on[i]) TGX_TRY(timegap_check_type(plan, i, c.type, err));
     if (c.mem != TGX_MEM_HOST && c.mem != TGX_MEM_DEVICE)
       return fail(err, TGX_INVALID_ARGUMENT, "column %d: unknown memory space %d", i, c.mem);
     if (st->col_types[i] == 0) st->col_types[i] = c.type;
@@ -941,6 +942,7 @@ tgx_status update_impl(const tgx_plan *plan, tgx_state *st, const tgx_column *co
       if (side) TGX_TRY(side->update(st, dev, nrows, err));
     TGX_TRY(late_key_sets(plan, st, dev, columns, f, err));
     TGX_TRY(sketches(plan, st, dev, columns, f, err));
+    TGX_TRY(timegap_update(st, dev, nrows, err));  // the time-gap checks' rows (kept, sorted at finalize)
   }
   return finish_batch(st, b, err);
 }

@@ -9,6 +9,7 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
   bind_thread();
   if (!plan || !st || st->plan != plan || !len) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   TGX_TRY(spearman_check_mergeable(st, err));
+  TGX_TRY(timegap_check_mergeable(st, "tgx_state_serialize", err));
   Gathered g;
   TGX_TRY(gather(st, &g, err));
   Writer w{buf, cap};

@@ -382,8 +382,8 @@ class CorrelationConstraint:
 
 class TemporalOrderingConstraint:
     """constraints/temporal_ordering.rs:106-288, one method per builder call of the reference.  BeforeAfter,
-    BusinessHours and DateRange run on the device (TGX_CHECK_TEMPORAL); MaxTimeGap and EventSequence evaluate to an
-    error"""
+    BusinessHours and DateRange run on the device (TGX_CHECK_TEMPORAL); MaxTimeGap evaluates to an error unless
+    window_on_device(True) asks for it (TGX_CHECK_TIME_GAP); EventSequence evaluates to an error"""
 
     def __init__(self, table_name):
         self.spec = {"type": "temporal_ordering", "table": table_name, "allow_nulls": False, "tolerance_seconds": 0}
@@ -423,6 +423,14 @@ class TemporalOrderingConstraint:
     def group_by(self, column):
         if self.spec.get("validation") == "max_time_gap":
             self.spec["group_by_column"] = column
+        return self
+
+    def window_on_device(self, on):
+        """MaxTimeGap only (this layer's own call): run the LAG() window on the device.  Off by default -- the check
+        keeps 8 B per row (16 B with a group) on the device until the verdict, and its state cannot be merged,
+        serialized or reduced across ranks"""
+        if self.spec.get("validation") == "max_time_gap":
+            self.spec["window_on_device"] = bool(on)
         return self
 
     def allow_nulls(self, allow):
@@ -901,7 +909,9 @@ def constraint_verdict(constraint, results):
 
 def temporal_params(constraint, arrow_types):
     """a temporal_ordering constraint (its dict) + {column: Arrow DataType name} -> the tgx_temporal_params of its
-    TEMPORAL spec as a dict (tgx_host_temporal_params_json); TgxError with the constraint's error text otherwise"""
+    TEMPORAL spec as a dict (tgx_host_temporal_params_json) -- for max_time_gap with window_on_device, the
+    tgx_time_gap_params of its TIME_GAP spec ({column, column2, kind, max_gap, flags}); TgxError with the constraint's
+    error text otherwise"""
     out = C.c_char_p()
     err = _Error()
     _host_check(_host().tgx_host_temporal_params_json(json.dumps(constraint).encode(), json.dumps(arrow_types).encode(),
