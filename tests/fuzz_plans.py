@@ -11,7 +11,14 @@ two is a fresh plan with edges / binnings set -- derived from the exact referenc
 said in pass one -- fed the same table through the same batching and state sequence.  TEMPORAL is complete in pass
 one.  These three are compared with tests/exact_histogram.py, exact_joint.py and exact_temporal.py: every count, extreme
 and counter for equality, the histogram's two plain double sums within exact_histogram.sum_bounds (or by its overflow
-rule, sum_rules).  tests/test_fuzz_cases.py tests this tester without a device."""
+rule, sum_rules).
+
+TIME_GAP (the one kind that keeps rows on the device between batches) is drawn last, from a stream of its own, for cases
+that are simply finalized: one or two tasks (timestamp column, group column or none -- any Int64-shaped or widened
+integer column, the timestamp column itself included), each with 1 to 3 thresholds (sometimes more than one neighbour
+pass compares) taken from the gaps tests/exact_time_gap.py finds in the whole table, some under one of the environments
+of tests/test_gpu_time_gap.py that force the sort's other routes.  It changes nothing an earlier stream drew.  All five
+counters of every spec are compared for equality.  tests/test_fuzz_cases.py tests this tester without a device."""
 import math
 import sys
 
@@ -21,6 +28,7 @@ import exact_histogram as EH
 import exact_hll as H
 import exact_joint as EJ
 import exact_temporal as ET
+import exact_time_gap as EG
 import exact_quantiles as Q
 import exact_ranks as R
 import exact_widening as W
@@ -202,12 +210,15 @@ class Case:
              "medium": int(rng.integers(20_000, 400_000)), "big": int(rng.integers(min(1_050_000, max_rows - 1), max_rows))}[size_class]
         self.n = n
         self.cols = []  # (kind 'i'/'f', values, validity bytes or None, mask)
+        self.shapes = []  # per column: the shape of an Int64 column's values (INT_SHAPES), None for the other kinds
         for _ in range(int(rng.integers(1, 4))):
             rate = float(rng.choice([0.0, 0.0, 0.02, 0.3, 1.0], p=[0.3, 0.2, 0.25, 0.2, 0.05]))
             kind = str(rng.choice(["i", "f", "i32", "f32", "s"], p=[0.45, 0.25, 0.08, 0.07, 0.15]))
             extra = None
+            self.shapes.append(None)
             if kind == "i":
-                vals = int_values(rng, n, str(rng.choice(INT_SHAPES)))
+                self.shapes[-1] = str(rng.choice(INT_SHAPES))
+                vals = int_values(rng, n, self.shapes[-1])
             elif kind == "f":
                 vals = np.ascontiguousarray(float_values(rng, n, str(rng.choice(FLOAT_SHAPES))), dtype=np.float64)
             elif kind == "i32":
@@ -353,6 +364,7 @@ class Case:
             elif fits:
                 self.present[ci] = fits[int(rng5.integers(0, len(fits)))]
         self.draw_two_phase_and_temporal(np.random.default_rng([seed, 8]))
+        self.draw_time_gap(np.random.default_rng([seed, 9]))
 
     HISTOGRAM_BUCKETS = [1, 2, 5, 10, 100, 999, 1000]
     JOINT_BINS = [2, 5, 10, 127]
@@ -411,10 +423,52 @@ class Case:
             if e[0] in ("histogram", "joint"):
                 assert not any(self.present[ci] == "bool" or self.present[ci] is np.uint64 for ci in self.columns_of_expect(e))
 
+    FORCED_SORT_ROUTES = ("two_passes", "three_passes", "chunked_last_pass", "many_stretches")
+
+    def draw_time_gap(self, rng9):
+        """TIME_GAP checks, from a stream of their own and without touching anything drawn before (no presentation
+        changes: a group column keeps its narrow type, the widened route).  Only for a case that is simply finalized -- a
+        state that holds rows refuses blob, merge and allreduce -- and has an Int64 column to serve as timestamps."""
+        self.sort_env, self.sort_route = {}, "shipped"
+        stamps = [ci for ci, c in enumerate(self.cols) if c[0] == "i" and self.present[ci] is None]
+        if self.after != "finalize" or self.n > self.NEW_KINDS_MAX_ROWS or not stamps or rng9.random() >= 0.7:
+            return
+        groups = [ci for ci, c in enumerate(self.cols) if c[0] == "i32" or (
+            c[0] == "i" and not (self.present[ci] == "bool" or self.present[ci] is np.uint64))]
+
+        def pick(a):
+            return a[int(rng9.integers(0, len(a)))]
+
+        def group():  # (the timestamp columns are group columns too: `groups` is never empty)
+            return pick(groups) if rng9.random() < 0.65 else -1
+
+        t = pick(stamps)
+        if rng9.random() < 0.5:
+            tasks = [(t, group())]
+        elif len(stamps) < 2 or rng9.random() < 0.6:  # the whole table and per group, over one retained column
+            tasks = [(t, -1), (t, pick(groups))]
+        else:
+            tasks = [(t, group()), (pick([ci for ci in stamps if ci != t]), group())]
+        many = int(rng9.integers(0, len(tasks))) if rng9.random() < 0.1 else -1  # more than kTimeGapThresholds (8)
+        for k, (ct, cg) in enumerate(tasks):
+            _, _, gaps = self.reference(("time_gap", ct, cg))
+            for _ in range(int(rng9.integers(9, 12)) if k == many else int(rng9.integers(1, 4))):
+                how = int(rng9.integers(0, 5)) if len(gaps) else int(rng9.integers(2, 4))
+                some = int(gaps[int(rng9.integers(0, len(gaps)))]) if how < 2 else 0  # a gap that occurs (up to 2^64 - 1)
+                max_gap = [min(some, EG.I64_MAX), min(some, EG.I64_MAX) - 1, 0, -1, EG.I64_MAX][how]
+                self.add(spec(T.TIME_GAP, ct, column2=cg), ("time_gap", ct, cg, max_gap))
+        if rng9.random() < 1 / 3:
+            from test_gpu_time_gap import SORT_SHAPES  # (the hand tests' forcing environments: read per sort call)
+
+            self.sort_route = pick(self.FORCED_SORT_ROUTES)
+            self.sort_env = dict(SORT_SHAPES[self.sort_route][1])
+
     @staticmethod
     def columns_of_expect(e):
         if e[0] == "tuple":
             return tuple(e[1])
+        if e[0] == "time_gap":
+            return (e[1],) if e[2] < 0 or e[2] == e[1] else (e[1], e[2])
         if e[0] in ("comoments", "spearman", "joint") or (e[0] == "temporal" and e[2] >= 0):
             return (e[1], e[2])
         return (e[1],)
@@ -440,11 +494,12 @@ class Case:
     def describe(self):
         cols = ", ".join("%s%s/nulls=%d" % (c[0], "" if p is None else "as" + (p if isinstance(p, str) else p.__name__),
                                             int((~c[3]).sum())) for c, p in zip(self.cols, self.present))
-        checks = [e[0] if e[0] not in ("histogram", "joint", "temporal") else "%s%r" % (e[0], e[1:]) for e in self.expect]
-        return "seed %d: n=%d cols=[%s] checks=%s pass=%d batching=%s(%d) buffers=%s after=%s env=%s" % (
+        checks = [e[0] if e[0] not in ("histogram", "joint", "temporal", "time_gap") else "%s%r" % (e[0], e[1:]) for e in self.expect]
+        return "seed %d: n=%d cols=[%s] checks=%s pass=%d batching=%s(%d) buffers=%s after=%s env=%s%s" % (
             self.seed, self.n, cols, checks, self.phase, self.mode, len(self.cuts) - 1, self.device,
             self.after + ("" if self.seq == "plain" else "/" + self.seq) + (" kept" if self.retain else "") +
-            (" exact-keys" if self.exact_keys else ""), self.env)
+            (" exact-keys" if self.exact_keys else ""), self.env,
+            " sort=%s%s" % (self.sort_route, self.sort_env) if self.sort_env else "")
 
     # ---- the device side ----
     def columns_of(self, lo, hi, on_device):
@@ -463,12 +518,12 @@ class Case:
     def run_device(self):
         import os
 
-        for k, v in self.env.items():
+        for k, v in list(self.env.items()) + list(self.sort_env.items()):
             os.environ[k] = v
         try:
             return self.run_device_inner()
         finally:
-            for k in self.env:
+            for k in list(self.env) + list(self.sort_env):
                 os.environ.pop(k, None)
 
     def run_device_inner(self):
@@ -541,6 +596,8 @@ class Case:
         for si, e in enumerate(self.expect):
             if e[0] == "temporal":
                 plan.set_temporal(si, **e[4])
+            elif e[0] == "time_gap":
+                plan.set_time_gap(si, e[3])
             elif self.phase == 2 and e[0] == "histogram":
                 plan.set_histogram_edges(si, self.pass_two[si])
             elif self.phase == 2 and e[0] == "joint":
@@ -619,6 +676,10 @@ class Case:
             elif what == "joint_counts":
                 self._cache[key] = EJ.joint_counts_np(self.doubles_of(key[1]), self.doubles_of(key[2]),
                                                       self.cols[key[1]][3] & self.cols[key[2]][3], key[3])
+            elif what == "time_gap":  # (seen, rows, the task's gaps in order): shared by all its thresholds
+                ct, cg = key[1], key[2]
+                self._cache[key] = EG.gaps_np(self.cols[ct][1], self.cols[ct][3], *(
+                    (self.cols[cg][1], self.cols[cg][3]) if cg >= 0 else (None, None)))
             elif what == "both_zeros":  # does the column hold +0.0 AND -0.0 among the rows `key[2]` names?
                 d = self.doubles_of(key[1])[self.live_mask(key[2])]
                 z = d[d == 0.0]
@@ -696,6 +757,15 @@ class Case:
         assert got == want, (e, "seen, considered, violations", got, want)
         assert (r.total, r.non_null, r.matches) == (want[0], want[1], want[1] - want[2]), (e, r.total, r.non_null, r.matches, want)
 
+    def check_time_gap(self, e, si, r, st):
+        _, ct, cg, max_gap = e
+        want = EG.counts_of_gaps(max_gap, *self.reference(("time_gap", ct, cg)))
+        for read in ("first read", "cached read"):
+            got = tuple(st.time_gap_counts(si))
+            assert got == want, (e, read, "seen, rows, gaps, violations, largest_gap", got, want)
+        seen, _, gaps, violations, _ = want
+        assert (r.total, r.non_null, r.matches) == (seen, gaps, gaps - violations), (e, r.total, r.non_null, r.matches, want)
+
     # ---- the oracle side + comparison ----
     def key_bits(self, ci):
         """(values as the 64-bit patterns DISTINCT compares, validity) of a numeric column"""
@@ -730,8 +800,9 @@ class Case:
             if what == "tuple":
                 self.check_tuple(r, e)
                 continue
-            if what in ("histogram", "joint", "temporal"):
-                {"histogram": self.check_histogram, "joint": self.check_joint, "temporal": self.check_temporal}[what](e, si, r, st)
+            if what in ("histogram", "joint", "temporal", "time_gap"):
+                {"histogram": self.check_histogram, "joint": self.check_joint, "temporal": self.check_temporal,
+                 "time_gap": self.check_time_gap}[what](e, si, r, st)
                 continue
             kind, vals, vb, mask, extra = self.cols[e[1]]
             wide = (vals if kind in ("i", "f", "s") else W.widen_int(vals, "int32") if kind == "i32"

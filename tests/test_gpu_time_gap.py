@@ -17,7 +17,8 @@ from gpu_util import pad_validity, to_device
 pytestmark = pytest.mark.gpu
 
 I64_MIN, I64_MAX = eg.I64_MIN, eg.I64_MAX
-NP_TYPES = {T.INT64: np.int64, T.INT32: np.int32, T.UINT8: np.uint8}
+NP_TYPES = {T.INT64: np.int64, T.INT32: np.int32, T.UINT8: np.uint8, T.INT8: np.int8, T.INT16: np.int16,
+            T.UINT16: np.uint16, T.UINT32: np.uint32}
 
 
 def column(vals, mask, mem=T.MEM_DEVICE, type_id=T.INT64):
@@ -174,12 +175,16 @@ def test_interleaved_groups_with_overlapping_timestamps():
     assert want[0][2] == n - 3 and want[0][3] >= 1 and want[1][3] > want[0][3]
 
 
-@pytest.mark.parametrize("gtype,lo,hi", [(T.INT32, -2**31, 2**31), (T.UINT8, 0, 256)])
+@pytest.mark.parametrize("gtype,lo,hi", [(T.INT32, -2**31, 2**31), (T.UINT8, 0, 256), (T.INT8, -2**7, 2**7),
+                                         (T.INT16, -2**15, 2**15), (T.UINT16, 0, 2**16), (T.UINT32, 0, 2**32)])
 def test_widened_group_columns(gtype, lo, hi):
+    """every type the staging widens for the group column: the type's minimum, its maximum and a value next to each
+    (an unsigned maximum read as signed, or a sign not extended, would merge or split partitions)"""
     rng = np.random.default_rng(7 + gtype)
     n = 25_000
     t = rng.integers(0, 10**6, n, dtype=np.int64)
     g = rng.choice(np.array([lo, lo + 1, -1 if lo < 0 else 128, hi - 2, hi - 1]), n)
+    assert (g.astype(NP_TYPES[gtype]).astype(np.int64) == g).all() and {lo, lo + 1, hi - 2, hi - 1} <= set(g.tolist())
     for mem in (T.MEM_DEVICE, T.MEM_HOST):
         check([50], t, rng.random(n) >= 0.05, g, rng.random(n) >= 0.2, mem=mem, gtype=gtype)
 
@@ -387,6 +392,72 @@ def test_beside_other_checks_on_the_same_column(batch_table):
             ctypes.string_at(ctypes.addressof(ref), ctypes.sizeof(ref))
     with pytest.raises(T.TgxError, match="TGX_INVALID_ARGUMENT.*not a TIME_GAP"):
         st.time_gap_counts(2)
+
+
+# ---- four tasks over three columns: every column in both roles, one task grouped by its own timestamps ---------------
+FOUR_N = 30_011
+FOUR_SPECS = [(0, 1, 5), (2, 2, 0), (0, -1, 0), (1, 0, 1), (0, 1, -1), (0, -1, 7), (2, 2, -1), (0, 1, 100), (1, 0, 40)]
+FOUR_TASKS = [(0, -1), (0, 1), (1, 0), (2, 2)]
+FOUR_CUTS = [1, 64, 65, 4097, 4100, 12_288, 20_481, 29_999]
+
+
+@pytest.fixture(scope="module")
+def four_tasks_table():
+    """three Int64 columns a, b, c with NULLs in all of them, and the exact counters of every spec of FOUR_SPECS"""
+    rng = np.random.default_rng(10)
+    vals = [rng.integers(-1500, 1500, FOUR_N, dtype=np.int64) * 7, rng.integers(0, 400, FOUR_N, dtype=np.int64) - 200,
+            rng.integers(-(2**40), 2**40, FOUR_N, dtype=np.int64)]
+    vals[2][rng.random(FOUR_N) < 0.4] = vals[2][0]  # (one value of c many times over, the rest nearly distinct)
+    masks = [rng.random(FOUR_N) >= rate for rate in (0.05, 0.1, 0.2)]
+    want = [eg.counts(m, lst(vals[ct]), lst(masks[ct]), *((lst(vals[cg]), lst(masks[cg])) if cg >= 0 else (None, None)))
+            for ct, cg, m in FOUR_SPECS]
+    return vals, masks, want
+
+
+def four_tasks_plan(specs):
+    plan = T.Plan([spec(T.TIME_GAP, ct, column2=cg) for ct, cg, _ in specs])
+    for i, (_, _, m) in enumerate(specs):
+        plan.set_time_gap(i, m)
+    return plan
+
+
+@pytest.mark.parametrize("order", ["as_planned", "backwards"])
+@pytest.mark.parametrize("mem", [T.MEM_DEVICE, T.MEM_HOST], ids=["device", "host"])
+def test_four_tasks_over_three_columns(four_tasks_table, mem, order):
+    """(a, -), (a, b), (b, a), (c, c) in one plan, their specs interleaved: every spec's counters are the reference's
+    and what its task gives in a plan of its own -- the tasks share the sort's work buffers and are answered one after
+    the other, in the order they are first read"""
+    vals, masks, want = four_tasks_table
+    T.init()
+    cols = [column(v, m, mem) for v, m in zip(vals, masks)]
+    batches = batches_of(cols, FOUR_N, FOUR_CUTS)
+    st = feed(four_tasks_plan(FOUR_SPECS), batches)
+    reads = list(range(len(FOUR_SPECS)))
+    if order == "backwards":
+        reads.reverse()
+    got = {i: st.time_gap_counts(i) for i in reads}
+    assert [got[i] for i in range(len(FOUR_SPECS))] == want
+    assert [st.time_gap_counts(i) for i in range(len(FOUR_SPECS))] == want  # the cached answers
+    for r, (seen, _, gaps, violations, _) in zip(st.finalize(), want):
+        assert (r.total, r.non_null, r.matches) == (seen, gaps, gaps - violations)
+    for task in FOUR_TASKS:
+        mine = [i for i, sp in enumerate(FOUR_SPECS) if sp[:2] == task]
+        assert mine, task
+        alone = feed(four_tasks_plan([FOUR_SPECS[i] for i in mine]), batches)
+        assert [alone.time_gap_counts(k) for k in range(len(mine))] == [got[i] for i in mine], task
+
+
+def test_grouped_by_its_own_timestamps(four_tasks_table):
+    """(c, c): every partition holds one instant, so every gap is 0, there are as many gaps as rows beyond the first of
+    each distinct value, and a NULL c is a NULL timestamp: dropped, never a NULL group"""
+    vals, masks, want = four_tasks_table
+    c, cm = vals[2], masks[2]
+    rows, distinct = int(cm.sum()), len(set(c[cm].tolist()))
+    assert rows - distinct > FOUR_N // 4
+    for (ct, cg, max_gap), w in zip(FOUR_SPECS, want):
+        if (ct, cg) == (2, 2):
+            assert w == (FOUR_N, rows, rows - distinct, rows - distinct if max_gap < 0 else 0, 0)
+    check([0, -1], c, cm, c, cm, cuts=FOUR_CUTS, want=[want[1], want[6]])
 
 
 def test_merge_and_serialize_are_refused_on_a_state_that_holds_rows():
