@@ -250,7 +250,19 @@ typedef enum tgx_check_kind {
    * them when it is read; specs on the same (t, g) that differ only in max_gap share one copy and one sort.  More than
    * 2^32 - 1 retained rows in a task are TGX_UNSUPPORTED.  Such a state is not additive: tgx_merge, tgx_state_serialize
    * and tgx_allreduce on a state whose TIME_GAP task holds rows return TGX_UNSUPPORTED (an empty one passes). */
-  TGX_CHECK_TIME_GAP = 13
+  TGX_CHECK_TIME_GAP = 13,
+  /* The numeric row predicates behind DataTypeConstraint
+   *                                            TG/constraints/datatype.rs:144-160, 383-439
+   *   SELECT COUNT(*) AS total, SUM(CASE WHEN <predicate> THEN 1 ELSE 0 END) AS valid FROM t WHERE col IS NOT NULL
+   * over one numeric column: `column` names it, `column2` is -1.  The rule and its bounds come with
+   * tgx_plan_set_value_rule (below, which also holds the rules' exact semantics); a spec without them makes
+   * tgx_state_create fail.  Read with tgx_value_rule_get; tgx_result carries total = rows seen, non_null = rows
+   * considered (the non-NULL rows), matches = valid rows, distinct = cast errors (INTEGER mode).
+   * Columns: the Int64-shaped ones (Int64 / Timestamp / Date64 / Duration), Float64, and Int32 / Date32 / Float32 /
+   * Int8 .. UInt32 through the widening staging; UInt64, Boolean and every string layout are TGX_UNSUPPORTED from
+   * tgx_update, and the state stays usable afterwards.  The state is four counters: tgx_merge, state blobs and
+   * tgx_allreduce add them.  A blob counted under other parameters is refused. */
+  TGX_CHECK_VALUE_RULE = 14
 } tgx_check_kind;
 
 enum {
@@ -446,6 +458,48 @@ typedef struct tgx_time_gap_params {
 } tgx_time_gap_params;
 tgx_status tgx_plan_set_time_gap(tgx_plan *plan, size_t spec_index, const tgx_time_gap_params *params, tgx_error *err);
 
+/* TGX_CHECK_VALUE_RULE: the rule of spec `spec_index`.  Like the TEMPORAL parameters it can be set until the plan's
+ * first state exists; afterwards, and for a spec of another kind, the call is refused with TGX_INVALID_ARGUMENT.
+ *
+ * A row's value is an int64 when the column's Arrow type is an integer type (Int8 .. Int64, UInt8 .. UInt32, Date32,
+ * Date64, Timestamp, Duration) and a double when it is Float32 or Float64; widening preserves both (a Float32 NaN keeps
+ * its sign and payload).  A NULL row is seen and never considered.
+ *
+ * The semantics are DataFusion 50 / arrow 56 as the reference's query reaches them.  arrow-ord's comparison kernels
+ * order floats by IEEE totalOrder, for `=` as well:
+ *     -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN
+ * so every float comparison below is a comparison of totalOrder keys, key(x) = b ^ ((b >> 63) & 0x7fffffffffffffff)
+ * over the bits b of x taken as an int64 (arithmetic shift) -- not `<` / `==` on doubles.  (This rests on arrow-ord's
+ * documented behaviour: the reference cannot be built beside this library.  INTEGRATION.md lists it as unverified.)
+ *
+ *   TGX_RULE_GE_ZERO   col >= 0.  Integer column: v >= 0.  Float column: key(x) >= key(+0.0).
+ *   TGX_RULE_GT_ZERO   col > 0.   Integer column: v > 0.   Float column: key(x) > key(+0.0).
+ *                      So -0.0 fails both, +0.0 passes GE_ZERO and fails GT_ZERO, +NaN passes both, -NaN fails both.
+ *   TGX_RULE_BETWEEN   col BETWEEN lo AND hi, the three operands coerced to one type.  Integer column without
+ *                      TGX_RULE_BOUNDS_AS_DOUBLE: lo_i <= v <= hi_i as int64.  With the flag, or on a float column
+ *                      (where the flag changes nothing): key(lo_f) <= key((double)v) <= key(hi_f), an int64 converted
+ *                      round-to-nearest-even as CAST(col AS DOUBLE) does.  lo > hi is allowed and matches nothing.
+ *                      lo_i / hi_i are read only without the flag on an integer column, lo_f / hi_f only otherwise.
+ *   TGX_RULE_INTEGER   col = CAST(col AS INT), INT being Int32.  SQL CAST is not TRY_CAST: a value that does not fit
+ *                      fails the whole query, so such rows are COUNTED as cast_errors (never raised; the caller turns
+ *                      cast_errors > 0 into its error).  A row is a cast error when it is an integer value outside
+ *                      [-2^31, 2^31 - 1], a float that is NaN or +-inf, or a float whose truncation toward zero lies
+ *                      outside that range (num-traits' rule: -2147483648.9 is in range, 2147483648.0 is not).  A row
+ *                      that casts is valid iff v == (int32)v for integers (always), and
+ *                      key(x) == key((double)(int32)trunc(x)) for floats: 2.0 is valid, 2.5 is not, and -0.0 is not
+ *                      (its cast gives +0.0).  A cast error is considered and not valid.
+ * Flags: TGX_RULE_BOUNDS_AS_DOUBLE, BETWEEN only (TGX_INVALID_ARGUMENT with another mode). */
+enum { TGX_RULE_GE_ZERO = 1, TGX_RULE_GT_ZERO = 2, TGX_RULE_BETWEEN = 3, TGX_RULE_INTEGER = 4 };
+enum { TGX_RULE_BOUNDS_AS_DOUBLE = 1u << 0 };
+typedef struct tgx_value_rule_params {
+  int32_t mode;       /* TGX_RULE_* */
+  uint32_t flags;     /* TGX_RULE_BOUNDS_AS_DOUBLE */
+  int64_t lo_i, hi_i; /* BETWEEN, int64 domain: both ends inclusive */
+  double lo_f, hi_f;  /* BETWEEN, double domain: both ends inclusive, by totalOrder (a NaN bound is a key like any other) */
+} tgx_value_rule_params;
+tgx_status tgx_plan_set_value_rule(tgx_plan *plan, size_t spec_index, const tgx_value_rule_params *params,
+                                   tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -608,6 +662,16 @@ typedef struct tgx_time_gap_counts {
 tgx_status tgx_time_gap_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_time_gap_counts *out,
                             tgx_error *err);
 
+/* ---- numeric value rules (TGX_CHECK_VALUE_RULE; TG/constraints/datatype.rs:383-439) ----------------------------- */
+typedef struct tgx_value_rule_counts {
+  uint64_t seen;        /* rows handed to tgx_update */
+  uint64_t considered;  /* the SQL's COUNT(*): the non-NULL rows */
+  uint64_t valid;       /* the SQL's SUM(CASE WHEN <predicate> THEN 1 ELSE 0 END): considered rows that pass */
+  uint64_t cast_errors; /* INTEGER mode: considered rows on which CAST(col AS INT) fails the reference's query; else 0 */
+} tgx_value_rule_counts;
+tgx_status tgx_value_rule_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_value_rule_counts *out,
+                              tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -697,7 +761,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

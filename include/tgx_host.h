@@ -66,6 +66,16 @@ tgx_status tgx_host_constraint_plan_json(const char *constraint_json, char **out
 tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char *arrow_types_json, char **out_json,
                                          tgx_error *err);
 
+/* A "datatype" constraint with a numeric validation ({"type": "datatype", "column": c, "validation": "numeric",
+ * "numeric": "non_negative | positive | integer | range", "min", "max"}) -> the tgx_value_rule_params the suite runner
+ * hands to tgx_plan_set_value_rule: {"column", "kind": 14, "mode", "flags", "lo_i", "hi_i", "lo_f", "hi_f"}.  A range's
+ * bounds are read as DataFusion reads what the reference prints with `{}`: a finite integral bound with |b| <= 2^53 is an
+ * Int64 literal, any other finite bound a Float64 literal, and one Float64 literal sets TGX_RULE_BOUNDS_AS_DOUBLE.  What
+ * the GPU path does not take (finite, a bound that is not finite or an integer beyond 2^53, every string, temporal and
+ * custom validation) is TGX_INVALID_ARGUMENT with the constraint's error text: hand such a constraint to the stock path.
+ * Needs no device. */
+tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **out_json, tgx_error *err);
+
 /* `Constraint::evaluate`'s verdict half on given aggregates: results_json is an array of objects with
  * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}).
  * Returns {"status": "success|failure|skipped", "metric": x|null, "message": s|null}.  Needs no device.

@@ -17,6 +17,9 @@ TEMPORAL_KEEP_NULLS, TEMPORAL_WEEKDAYS_ONLY = 1, 2
 HISTOGRAM = 12  # the histogram of a numeric column, in two phases (Plan.set_histogram_edges)
 HISTOGRAM_MAX_BUCKETS = 1000
 TIME_GAP = 13  # gaps between neighbouring timestamps, whole table or per group (Plan.set_time_gap)
+VALUE_RULE = 14  # numeric value rules: >= 0, > 0, between, whole (Plan.set_value_rule)
+RULE_GE_ZERO, RULE_GT_ZERO, RULE_BETWEEN, RULE_INTEGER = 1, 2, 3, 4
+RULE_BOUNDS_AS_DOUBLE = 1
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -106,6 +109,17 @@ class TimeGapCounts(C.Structure):
     """tgx_time_gap_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("rows", C.c_uint64), ("gaps", C.c_uint64), ("violations", C.c_uint64),
                 ("largest_gap", C.c_uint64)]
+
+
+class ValueRuleParams(C.Structure):
+    """tgx_value_rule_params (include/tgx.h)"""
+    _fields_ = [("mode", C.c_int32), ("flags", C.c_uint32), ("lo_i", C.c_int64), ("hi_i", C.c_int64),
+                ("lo_f", C.c_double), ("hi_f", C.c_double)]
+
+
+class ValueRuleCounts(C.Structure):
+    """tgx_value_rule_counts (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("valid", C.c_uint64), ("cast_errors", C.c_uint64)]
 
 
 class HistogramRange(C.Structure):
@@ -232,6 +246,8 @@ def lib():
         L.tgx_temporal_get.argtypes = [vp, vp, sz, C.POINTER(TemporalCounts), E]
         L.tgx_plan_set_time_gap.argtypes = [vp, sz, C.POINTER(TimeGapParams), E]
         L.tgx_time_gap_get.argtypes = [vp, vp, sz, C.POINTER(TimeGapCounts), E]
+        L.tgx_plan_set_value_rule.argtypes = [vp, sz, C.POINTER(ValueRuleParams), E]
+        L.tgx_value_rule_get.argtypes = [vp, vp, sz, C.POINTER(ValueRuleCounts), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -653,6 +669,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_time_gap(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_value_rule(self, spec_index, mode, flags=0, lo_i=0, hi_i=0, lo_f=0.0, hi_f=0.0):
+        """tgx_plan_set_value_rule: the rule of a VALUE_RULE spec (before the plan's first state)"""
+        p = ValueRuleParams(mode, flags, lo_i, hi_i, lo_f, hi_f)
+        err = _Error()
+        _check(lib().tgx_plan_set_value_rule(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
         lib().tgx_plan_get_fingerprint_key(self.h, out)
@@ -838,6 +860,14 @@ class State:
         err = _Error()
         _check(lib().tgx_time_gap_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.rows, out.gaps, out.violations, out.largest_gap
+
+    # numeric value rules
+    def value_rule_counts(self, spec_index):
+        """tgx_value_rule_get: (seen, considered, valid, cast_errors)"""
+        out = ValueRuleCounts()
+        err = _Error()
+        _check(lib().tgx_value_rule_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return out.seen, out.considered, out.valid, out.cast_errors
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -7,6 +7,7 @@
 #include "../../../include/tgx_host.h"
 #include "json.h"
 #include "analyzers.h"
+#include "datatype.h"
 #include "temporal.h"
 #include "term_guard.h"
 
@@ -73,6 +74,22 @@ static std::shared_ptr<Constraint> constraint_from_json_text(const char *text) {
   return c.constraints().at(0);
 }
 
+// a double as JSON: 17 significant digits round-trip; a NaN or an infinity (a BETWEEN bound may be one at the C ABI,
+// never from this layer) as a string
+static std::string json_f64(double v) {
+  if (std::isnan(v)) return "\"NaN\"";
+  if (std::isinf(v)) return v > 0 ? "\"inf\"" : "\"-inf\"";
+  char buf[64];
+  snprintf(buf, sizeof(buf), "%.17g", v);
+  return buf;
+}
+
+static std::string value_rule_json(const tgx_value_rule_params &p) {
+  return "{\"mode\": " + std::to_string(p.mode) + ", \"flags\": " + std::to_string(p.flags) + ", \"lo_i\": " +
+         std::to_string(p.lo_i) + ", \"hi_i\": " + std::to_string(p.hi_i) + ", \"lo_f\": " + json_f64(p.lo_f) +
+         ", \"hi_f\": " + json_f64(p.hi_f) + "}";
+}
+
 extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json, char **out_json, tgx_error *err) {
   if (!constraint_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
   *out_json = nullptr;
@@ -98,6 +115,7 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
              (t.mode == kTemporalTimeGapMode ? ", \"max_gap_seconds\": " + std::to_string(t.max_gap_seconds) : std::string()) +
              "}";
       }
+      if (r.value_rule) o += ", \"value_rule\": " + value_rule_json(*r.value_rule);
       o += "}";
     }
     o += "]}";
@@ -251,6 +269,29 @@ extern "C" tgx_status tgx_host_temporal_params_json(const char *constraint_json,
                            ", \"mode\": " + n(p.mode) + ", \"flags\": " + n(p.flags) + ", \"delta\": " + n(p.delta) +
                            ", \"ticks_per_second\": " + n(p.ticks_per_second) + ", \"tod_lo\": " + n(p.tod_lo) +
                            ", \"tod_hi\": " + n(p.tod_hi) + ", \"lo\": " + n(p.lo) + ", \"hi\": " + n(p.hi) + "}");
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **out_json, tgx_error *err) {
+  if (!constraint_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto c = constraint_from_json_text(constraint_json);
+    const std::vector<SpecRequest> reqs = c->plan();
+    if (reqs.size() != 1 || !reqs[0].value_rule)
+      return hfail(err, TGX_INVALID_ARGUMENT, "not a numeric datatype constraint");
+    const std::string rule = value_rule_json(*reqs[0].value_rule);
+    *out_json = dup_string("{\"column\": " + json::quote(reqs[0].column) + ", \"kind\": " + std::to_string(reqs[0].kind) +
+                           ", " + rule.substr(1));
     return TGX_OK;
   } catch (const TermError &e) {
     return hfail(err, TGX_INVALID_ARGUMENT, e.display());

@@ -12,6 +12,7 @@
 #include <chrono>
 
 #include "json.h"
+#include "datatype.h"
 #include "temporal.h"
 
 namespace term_guard {
@@ -1345,7 +1346,9 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           const SpecRequest &q = spec_requests[i];
           if (q.kind == r.kind && q.column == r.column && q.column2 == r.column2 && q.columns == r.columns &&
               q.flags == r.flags && q.pattern == r.pattern && q.kll_k == r.kll_k && q.length_min == r.length_min &&
-              q.length_max == r.length_max && q.temporal == r.temporal)
+              q.length_max == r.length_max && q.temporal == r.temporal &&
+              q.value_rule.has_value() == r.value_rule.has_value() &&
+              (!r.value_rule || memcmp(&*q.value_rule, &*r.value_rule, sizeof(tgx_value_rule_params)) == 0))
             found = i;
         }
         if (found == spec_requests.size()) spec_requests.push_back(r);
@@ -1390,6 +1393,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
     if (s == TGX_OK) s = tgx_plan_create(specs.data(), specs.size(), &hh.plan, &err);
     for (size_t i = 0; s == TGX_OK && i < spec_requests.size(); i++) {
       const SpecRequest &r = spec_requests[i];
+      if (r.value_rule) s = tgx_plan_set_value_rule(hh.plan, i, &*r.value_rule, &err);
       if (!r.temporal) continue;
       if (r.kind == TGX_CHECK_TIME_GAP) {
         const tgx_time_gap_params gp = time_gap_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
@@ -1752,6 +1756,8 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     b.correlation(std::move(v));
   } else if (type == "temporal_ordering") {
     b.constraint(temporal_ordering_from_json(c));
+  } else if (type == "datatype") {
+    b.constraint(datatype_from_json(c));
   } else {
     throw TermError{TermError::Internal, "unknown constraint type '" + type + "'"};
   }

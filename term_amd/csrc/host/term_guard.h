@@ -176,6 +176,7 @@ struct SpecRequest {
   uint64_t length_min = 0, length_max = ~0ull;  // LENGTH: inclusive character-count bounds
   std::optional<TemporalRequest> temporal;      // TEMPORAL (`column2`: the after column in order mode) and TIME_GAP
                                                 // (`column2`: the group column, or empty)
+  std::optional<tgx_value_rule_params> value_rule;  // VALUE_RULE: the rule as the device takes it (host/datatype.h)
 };
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:
@@ -322,6 +323,10 @@ class Check::Builder {
   // core/check.rs:2125-2179: pushes TemporalOrderingConstraint::new(table) -- empty column names, so evaluating it
   // fails identifier validation, as in the reference; configured objects come through constraint(..) (host/temporal.h)
   Builder &temporal_ordering(std::string table);
+  // core/check.rs:651-657: pushes DataTypeConstraint::type_consistency(column, threshold); throws TermError where the
+  // reference's constructor returns Err and the builder panics on it (a threshold outside [0, 1]: Configuration).  The other validations come
+  // as configured objects through constraint(..) (host/datatype.h)
+  Builder &has_consistent_data_type(std::string column, double threshold);
   Check build() { return check_; }
 
  private:

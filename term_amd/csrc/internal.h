@@ -195,7 +195,7 @@ struct KllTask {
   int column;
   uint32_t k;
 };
-// The three kinds of side_check.h.
+// The four kinds of side_check.h.
 // TGX_CHECK_JOINT_BINS (jointbins_device.cpp): one task per spec; `binned` once tgx_plan_set_joint_binning was called
 struct JointTask {
   int col_x, col_y;
@@ -217,8 +217,17 @@ struct HistTask {
   uint32_t buckets() const { return counted ? (uint32_t)edges.size() - 1 : 0; }
 };
 
+// TGX_CHECK_VALUE_RULE (valuerule_device.cpp): one task per spec; `set` once tgx_plan_set_value_rule was called.  The
+// tasks of a column are launched in groups of up to eight, in plan order: `leader` is the first task of this one's group
+// (`slot`: the task's own index), whose counters hold the group's count of non-NULL rows
+struct ValueRuleTask {
+  int column, spec_index, slot, leader;
+  bool set;
+  tgx_value_rule_params params;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 3;  // JOINT_BINS, TEMPORAL, HISTOGRAM
+constexpr int kNumSide = 4;  // JOINT_BINS, TEMPORAL, HISTOGRAM, VALUE_RULE
 
 enum class Source { kScan, kCount };
 
@@ -243,6 +252,7 @@ struct tgx_plan {
   std::vector<tgx::JointTask> joint;
   std::vector<tgx::TemporalTask> temporal;
   std::vector<tgx::HistTask> hist;
+  std::vector<tgx::ValueRuleTask> rules;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
@@ -250,6 +260,7 @@ struct tgx_plan {
   std::vector<char> joint_on;    // a JOINT_BINS check reads it (numeric columns only: strings are TGX_UNSUPPORTED)
   std::vector<char> temporal_on; // a TEMPORAL check reads it (Int64-shaped columns only)
   std::vector<char> hist_on;     // a HISTOGRAM check reads it (numeric columns only, as JOINT_BINS)
+  std::vector<char> rule_on;     // a VALUE_RULE check reads it (numeric columns, Boolean and UInt64 excepted)
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
   // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
@@ -651,7 +662,8 @@ struct tgx_state {
   void *regex = nullptr;  // tgx::RegexState (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
   void *timegap = nullptr;   // tgx::TimeGapState (timegap_device.cpp)
-  // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms
+  // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms,
+  // value rules
   std::unique_ptr<tgx::SideCheck> side[tgx::kNumSide];
 
   tgx::Coalescer coalesce;
@@ -690,7 +702,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE parameters -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

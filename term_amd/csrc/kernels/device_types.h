@@ -194,6 +194,30 @@ struct TemporalLaunch {
   unsigned long long *counters[kMaxTemporalPerLaunch];
 };
 
+// Numeric value rules over one column (kernels/valuerule.hip; TGX_CHECK_VALUE_RULE).  A launch's tasks are COLUMN
+// GROUPS: one walk of a column (ComomentColDesc, the x side only) evaluates up to kValueRulesPerGroup rules of it.  The
+// host has reduced every comparison mode to one inclusive range test lo <= k <= hi on a key it names -- the int64 value
+// itself, or the IEEE totalOrder key (f64_total_key below) of the value as a double -- so GE_ZERO is [key(+0.0), max],
+// GT_ZERO [key(+0.0) + 1, max] and BETWEEN its own bounds, in either domain.  Per rule three 64-bit global counters at
+// counts[word]: [0] valid rows, [1] cast errors (kRuleInteger), [2] non-NULL rows -- counted once per group, in the
+// counters of its first rule.
+enum { kRuleRangeValue = 0, kRuleRangeKey = 1, kRuleInteger = 2 };
+struct ValueRule {
+  int64_t lo, hi;  // the two range kinds: both ends inclusive, in the key's domain
+  uint32_t word;   // first of the rule's three counters
+  int32_t kind;
+};
+constexpr int kValueRuleBlock = 512;
+constexpr int kMaxValueRuleGroupsPerLaunch = 8;
+constexpr int kValueRulesPerGroup = 8;
+constexpr int kValueRuleWords = 3;
+struct ValueRuleLaunch {
+  ComomentColDesc cols[kMaxValueRuleGroupsPerLaunch];
+  ValueRule rules[kMaxValueRuleGroupsPerLaunch][kValueRulesPerGroup];
+  int32_t n_rules[kMaxValueRuleGroupsPerLaunch];
+  unsigned long long *counts;
+};
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

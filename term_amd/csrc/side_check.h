@@ -1,5 +1,6 @@
 // side_check.h -- the check kinds that run beside the fused pass and share one shape: TGX_CHECK_JOINT_BINS
-// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp) and TGX_CHECK_HISTOGRAM (histogram_device.cpp).
+// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp), TGX_CHECK_HISTOGRAM (histogram_device.cpp) and
+// TGX_CHECK_VALUE_RULE (valuerule_device.cpp).
 //
 // A task is one spec.  Its running state is a few 64-bit counters on the device, plus a small range accumulator for the
 // kinds that have a range phase; rows seen are counted on the host.  What is merged in from other states or read from a
@@ -14,9 +15,12 @@
 
 namespace tgx {
 
-enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2 };  // (kNumSide: internal.h)
+enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3 };  // (kNumSide: internal.h)
 TGX_HIDDEN inline int side_index(int kind) {
-  return kind == TGX_CHECK_JOINT_BINS ? kSideJoint : kind == TGX_CHECK_TEMPORAL ? kSideTemporal : kSideHist;
+  return kind == TGX_CHECK_JOINT_BINS ? kSideJoint
+         : kind == TGX_CHECK_TEMPORAL ? kSideTemporal
+         : kind == TGX_CHECK_HISTOGRAM ? kSideHist
+                                       : kSideRule;
 }
 
 struct TGX_HIDDEN SideCheck {
@@ -35,21 +39,26 @@ struct TGX_HIDDEN SideCheck {
 tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-// every task has its parameters (tgx_plan_set_temporal)?  Asked by tgx_state_create
+tgx_status valuerule_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule)?  Asked by tgx_state_create
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
+tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
 TGX_HIDDEN SideCheck *joint_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *temporal_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *hist_state_new(const tgx_plan *plan);
+TGX_HIDDEN SideCheck *valuerule_state_new(const tgx_plan *plan);
 // the fresh state of the plan's tasks of kind `index`, or null when it has none
 TGX_HIDDEN inline SideCheck *side_state_new(int index, const tgx_plan *plan) {
-  SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new};
+  SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new,
+                                                          valuerule_state_new};
   return make[index](plan);
 }
 
 // ---- what the kinds' updates share -----------------------------------------------------------------------------------
 constexpr int kSidePerLaunch = 8;  // tasks of one launch (grid.y)
 static_assert(kMaxJointPerLaunch == kSidePerLaunch && kMaxTemporalPerLaunch == kSidePerLaunch &&
-                  kMaxHistPerLaunch == kSidePerLaunch, "the kinds' launch descriptors hold kSidePerLaunch tasks");
+                  kMaxHistPerLaunch == kSidePerLaunch && kMaxValueRuleGroupsPerLaunch == kSidePerLaunch,
+              "the kinds' launch descriptors hold kSidePerLaunch tasks");
 
 // the tasks that are `in_phase`, in launches of up to kSidePerLaunch: launch(slots, n)
 template <class Task, class InPhase, class Launch>

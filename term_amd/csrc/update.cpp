@@ -258,6 +258,8 @@ tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column
       return fail(err, TGX_UNSUPPORTED, "column %d: HISTOGRAM takes numeric columns (type %d)", i, c.type);
     if (plan->temporal_on[i] && c.type != TGX_INT64)
       return fail(err, TGX_UNSUPPORTED, "column %d: TEMPORAL takes Int64-shaped columns (type %d)", i, c.type);
+    if (plan->rule_on[i] && !is_numeric(c.type) && !(is_widened(c.type) && c.type != TGX_BOOL))
+      return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_RULE takes numeric columns other than UInt64 (type %d)", i, c.type);
     if (plan->timegap_on[i]) TGX_TRY(timegap_check_type(plan, i, c.type, err));
     if (c.mem != TGX_MEM_HOST && c.mem != TGX_MEM_DEVICE)
       return fail(err, TGX_INVALID_ARGUMENT, "column %d: unknown memory space %d", i, c.mem);

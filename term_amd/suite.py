@@ -268,6 +268,10 @@ class CheckBuilder:
         evaluating it fails identifier validation, as in the reference; a configured object goes through constraint()"""
         return self.constraint(TemporalOrderingConstraint(table_name))
 
+    def has_consistent_data_type(self, column, threshold):
+        """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
+        return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
+
     def constraint(self, c):
         """core/check.rs:263: a constraint object (MultiStatisticalConstraint, QuantileConstraint,
         CorrelationConstraint below) instead of a builder shorthand"""
@@ -440,6 +444,78 @@ class TemporalOrderingConstraint:
     def tolerance_seconds(self, seconds):
         self.spec["tolerance_seconds"] = int(seconds)
         return self
+
+
+class NumericValidation:
+    """constraints/datatype.rs:42-59"""
+    NonNegative, Positive, Integer, Finite = ({"numeric": k} for k in ("non_negative", "positive", "integer", "finite"))
+
+    @staticmethod
+    def Range(min, max):
+        # (JSON has no inf / NaN: such a bound travels as text and is the constraint's error when it is evaluated)
+        def text(b):
+            b = float(b)
+            return b if b == b and abs(b) != float("inf") else ("NaN" if b != b else "inf" if b > 0 else "-inf")
+        return {"numeric": "range", "min": text(min), "max": text(max)}
+
+
+class StringTypeValidation:
+    """constraints/datatype.rs:61-75"""
+    NotEmpty, ValidUtf8, NotBlank = ({"string": k} for k in ("not_empty", "valid_utf8", "not_blank"))
+
+    @staticmethod
+    def MaxBytes(n): return {"string": "max_bytes", "max_bytes": int(n)}
+
+
+class TemporalValidation:
+    """constraints/datatype.rs:77-91"""
+    PastDate, FutureDate, ValidTimezone = ({"temporal": k} for k in ("past_date", "future_date", "valid_timezone"))
+
+    @staticmethod
+    def DateRange(start, end): return {"temporal": "date_range", "start": start, "end": end}
+
+
+class DataTypeValidation:
+    """constraints/datatype.rs:21-40"""
+
+    @staticmethod
+    def SpecificType(data_type): return {"validation": "specific_type", "data_type": data_type}
+    @staticmethod
+    def Consistency(threshold): return {"validation": "consistency", "threshold": float(threshold)}
+    @staticmethod
+    def Numeric(v): return dict(v, validation="numeric")
+    @staticmethod
+    def String(v): return dict(v, validation="string")
+    @staticmethod
+    def Temporal(v): return dict(v, validation="temporal")
+    @staticmethod
+    def Custom(sql_predicate): return {"validation": "custom", "sql_predicate": sql_predicate}
+
+
+class DataTypeConstraint:
+    """constraints/datatype.rs:233-288.  The numeric NonNegative / Positive / Integer / Range validations run on the
+    device (TGX_CHECK_VALUE_RULE); SpecificType reads the column's Arrow type, Consistency is the reference's placeholder;
+    Finite and every String, Temporal and Custom validation evaluate to the constraint's own error.  The constructor
+    raises what DataTypeConstraint::new returns as Err: a column name that is no identifier, a consistency threshold
+    outside [0, 1]"""
+
+    def __init__(self, column, validation):
+        validate_identifier(column)
+        if validation.get("validation") == "consistency" and not 0.0 <= validation["threshold"] <= 1.0:
+            raise TgxError(1, "Configuration error: Threshold must be between 0.0 and 1.0")
+        self.spec = dict(validation, type="datatype", column=column)
+
+    @staticmethod
+    def non_negative(column):
+        return DataTypeConstraint(column, DataTypeValidation.Numeric(NumericValidation.NonNegative))
+
+    @staticmethod
+    def type_consistency(column, threshold):
+        return DataTypeConstraint(column, DataTypeValidation.Consistency(threshold))
+
+    @staticmethod
+    def specific_type(column, data_type):
+        return DataTypeConstraint(column, DataTypeValidation.SpecificType(data_type))
 
 
 class Check:
@@ -867,6 +943,7 @@ def _host():
         L.tgx_host_constraint_plan_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_constraint_verdict_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_temporal_params_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_value_rule_params_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_validate_identifier.argtypes = [C.c_char_p, E]
         L.tgx_host_assertion_json.argtypes = [C.c_char_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), E]
         L.tgx_host_run_analysis_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_Column),
@@ -916,6 +993,16 @@ def temporal_params(constraint, arrow_types):
     err = _Error()
     _host_check(_host().tgx_host_temporal_params_json(json.dumps(constraint).encode(), json.dumps(arrow_types).encode(),
                                                       C.byref(out), C.byref(err)), err)
+    return json.loads(_take(out))
+
+
+def value_rule_params(constraint):
+    """a datatype constraint with a numeric validation (its dict) -> the tgx_value_rule_params of its VALUE_RULE spec as
+    a dict ({column, kind, mode, flags, lo_i, hi_i, lo_f, hi_f}; tgx_host_value_rule_params_json); TgxError with the
+    constraint's error text for what stays off the device"""
+    out = C.c_char_p()
+    err = _Error()
+    _host_check(_host().tgx_host_value_rule_params_json(json.dumps(constraint).encode(), C.byref(out), C.byref(err)), err)
     return json.loads(_take(out))
 
 

@@ -39,6 +39,12 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                     u64 n_words; u64 words[n_words] }                           the count phase, where the sums are 0)
                                n_words = buckets + 1 in the count phase: the buckets, then the rows that reached the
                                last bucket through ELSE; 0 in the range phase.  n = the sum of the buckets there.
+    and ONLY for plans with VALUE_RULE checks, behind the HISTOGRAM section if there is one:
+    u32 magic 'VVRL', u32 n_rules
+    n_rules     x { i32 mode, u32 flags; i64 lo_i, hi_i; f64 lo_f, hi_f    (the plan's parameters as they were set: the
+                    u64 seen, considered, valid, cast_errors }              bounds are zeros outside the between mode)
+                               considered = the non-NULL rows, valid = those of them that pass, cast_errors = those of
+                               them CAST(col AS INT) fails on: valid + cast_errors <= considered <= seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -49,6 +55,7 @@ MAGIC, VERSION = 0x53584754, 3
 JOINT_MAGIC = 0x42544E4A  # 'JNTB'
 TEMPORAL_MAGIC = 0x52504D54  # 'TMPR'
 HIST_MAGIC = 0x54534948  # 'HIST'
+VALUE_RULE_MAGIC = 0x4C525656  # 'VVRL'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -153,7 +160,13 @@ def hist_count_state(edges, total, counts, else_rows=0, non_finite=0):
                         len(words)) + struct.pack("<%dQ" % len(words), *words))
 
 
-def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=()):
+def value_rule_state(mode, flags, seen, considered, valid, cast_errors=0, lo_i=0, hi_i=0, lo_f=0.0, hi_f=0.0):
+    """a VALUE_RULE task: the plan's parameters as they were set and its four counters"""
+    return struct.pack("<iI2q2d4Q", mode, flags, lo_i, hi_i, lo_f, hi_f, seen, considered, valid, cast_errors)
+
+
+def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
+         value_rules=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -162,5 +175,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", TEMPORAL_MAGIC, len(temporal)) + b"".join(temporal)
     if hist:
         tail += struct.pack("<II", HIST_MAGIC, len(hist)) + b"".join(hist)
+    if value_rules:
+        tail += struct.pack("<II", VALUE_RULE_MAGIC, len(value_rules)) + b"".join(value_rules)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
