@@ -262,7 +262,28 @@ typedef enum tgx_check_kind {
    * Int8 .. UInt32 through the widening staging; UInt64, Boolean and every string layout are TGX_UNSUPPORTED from
    * tgx_update, and the state stays usable afterwards.  The state is four counters: tgx_merge, state blobs and
    * tgx_allreduce add them.  A blob counted under other parameters is refused. */
-  TGX_CHECK_VALUE_RULE = 14
+  TGX_CHECK_VALUE_RULE = 14,
+  /* How often each value of one column occurs: the GROUP BY behind HistogramConstraint and EntropyAnalyzer
+   *                          TG/constraints/histogram.rs:205-391, TG/analyzers/advanced/entropy.rs:192-335
+   *   SELECT col, COUNT(*) FROM t WHERE col IS NOT NULL GROUP BY col
+   * for a BOUNDED number of distinct values: `column` names the column, `column2` is -1, the bounds come with
+   * tgx_plan_set_value_counts (below); a spec without them makes tgx_state_create fail.  Read with
+   * tgx_value_counts_get and tgx_value_counts_entries; tgx_result carries total = rows seen, non_null, distinct = values
+   * held, matches = rows counted in them.
+   * The counts are exact.  Everything beyond the bounds is reported, never approximated: a non-NULL row is in exactly
+   * one of an entry, overflow_rows (its value found no slot in the table) and long_rows (a string longer than
+   * max_value_bytes), so counted + overflow_rows + long_rows == non_null always holds.
+   * Columns: the Int64-shaped ones, Int32 / Date32 and Int8 .. UInt32 through the widening staging (the value is the
+   * widened int64), Utf8, LargeUtf8, Utf8View and Dictionary<Int32, Utf8> (the value is the string's bytes; the empty
+   * string is a value; rows whose dictionary entry is NULL, or whose index lies outside the dictionary, are NULL rows).
+   * The value of a string layout is its BYTES: a Binary column handed over in a string layout is counted as well, and
+   * what its values read as is the caller's business (the host layer refuses columns declared Binary).  Float32 / Float64, UInt64 and Boolean are
+   * TGX_UNSUPPORTED from tgx_update, and the state stays usable afterwards.
+   * Within one state strings are grouped by their 128-bit keyed fingerprint -- the guarantee the library gives for keys
+   * that cross a state boundary (TGX_CHECK_DISTINCT without TGX_FLAG_EXACT_KEYS) -- and every entry keeps its bytes;
+   * across states, blobs and ranks entries are united by their bytes.  Integer and dictionary-index counts are exact by
+   * construction.  tgx_merge, state blobs and tgx_allreduce unite by value and add the counters. */
+  TGX_CHECK_VALUE_COUNTS = 15
 } tgx_check_kind;
 
 enum {
@@ -500,6 +521,20 @@ typedef struct tgx_value_rule_params {
 tgx_status tgx_plan_set_value_rule(tgx_plan *plan, size_t spec_index, const tgx_value_rule_params *params,
                                    tgx_error *err);
 
+/* TGX_CHECK_VALUE_COUNTS: the bounds of spec `spec_index`.  Like the VALUE_RULE parameters they can be set until the
+ * plan's first state exists; afterwards, and for a spec of another kind, the call is refused with TGX_INVALID_ARGUMENT.
+ * max_distinct (1 .. TGX_VALUE_COUNTS_MAX_DISTINCT) sizes the task's table on the device: a power of two of at least
+ * 2 * max_distinct slots, so a column with up to max_distinct values is counted without overflow; a column with more may
+ * still fit (the caller compares `distinct` with its bound) or leave rows in overflow_rows.  max_value_bytes
+ * (1 .. TGX_VALUE_COUNTS_MAX_VALUE_BYTES) is read for string columns only: longer rows are counted in long_rows. */
+enum { TGX_VALUE_COUNTS_MAX_DISTINCT = 65536, TGX_VALUE_COUNTS_MAX_VALUE_BYTES = 256 };
+typedef struct tgx_value_counts_params {
+  uint32_t max_distinct;
+  uint32_t max_value_bytes;
+} tgx_value_counts_params;
+tgx_status tgx_plan_set_value_counts(tgx_plan *plan, size_t spec_index, const tgx_value_counts_params *params,
+                                     tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -672,6 +707,33 @@ typedef struct tgx_value_rule_counts {
 tgx_status tgx_value_rule_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_value_rule_counts *out,
                               tgx_error *err);
 
+/* ---- value counts (TGX_CHECK_VALUE_COUNTS; TG/constraints/histogram.rs:205-391) ----------------------------------- */
+typedef struct tgx_value_counts_summary {
+  uint64_t seen;          /* rows handed to tgx_update */
+  uint64_t non_null;      /* non-NULL rows (a row whose dictionary entry is NULL is a NULL row) */
+  uint64_t distinct;      /* values held; may exceed max_distinct: the caller compares */
+  uint64_t counted;       /* rows counted in the entries: the sum of their counts */
+  uint64_t overflow_rows; /* non-NULL rows whose value found no slot */
+  uint64_t long_rows;     /* string rows longer than max_value_bytes: they are in no entry */
+} tgx_value_counts_summary; /* counted + overflow_rows + long_rows == non_null */
+tgx_status tgx_value_counts_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                tgx_value_counts_summary *out, tgx_error *err);
+/* One value and its count.  Integer columns: `value`; string columns: bytes [offset, offset + length) of the caller's
+ * byte buffer (value is 0 there; offset and length are 0 for integers). */
+typedef struct tgx_value_count_entry {
+  int64_t value;
+  uint64_t offset, length;
+  uint64_t count;
+} tgx_value_count_entry;
+/* Copies the entries, ascending by value: int64 order for integer columns, bytewise (unsigned bytes, a prefix first) for
+ * strings, so two reads of equal states are byte-identical.  The convention of tgx_joint_counts: *n_entries and *n_bytes
+ * always receive what is needed; `entries` (cap entries) and `bytes` (bytes_cap bytes) may be NULL for a size query; a
+ * non-NULL buffer that is too small makes the call return TGX_INVALID_ARGUMENT with nothing copied.  *is_bytes = 1 when
+ * the values are strings, 0 when they are integers or the state has seen no value yet. */
+tgx_status tgx_value_counts_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                    tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
+                                    uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -761,7 +823,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

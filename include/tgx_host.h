@@ -77,7 +77,14 @@ tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char
 tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **out_json, tgx_error *err);
 
 /* `Constraint::evaluate`'s verdict half on given aggregates: results_json is an array of objects with
- * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}).
+ * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}, a
+ * VALUE_COUNTS entry {"total", "non_null", "value_counts": {"entries": {value text: count}, "overflow_rows",
+ * "long_rows"}}).
+ * A "histogram" constraint is {"type": "histogram", "column": c, "measures": [{"measure": "most_common_ratio |
+ * least_common_ratio | bucket_count | entropy | null_ratio | top_n_ratio | value_ratio", "assertion": {..}, "n"
+ * (top_n_ratio), "value" (value_ratio)}, ..], "description" (optional), "max_distinct" (default 10000)}: every measure
+ * must hold; it plans one TGX_CHECK_VALUE_COUNTS request ({"kind": 15, "value_counts": {"max_distinct",
+ * "max_value_bytes"}}).
  * Returns {"status": "success|failure|skipped", "metric": x|null, "message": s|null}.  Needs no device.
  * The constraint JSON may carry "column_type" (the column's Arrow DataType) and "strict_reference_types" as above. */
 tgx_status tgx_host_constraint_verdict_json(const char *constraint_json, const char *results_json, char **out_json,
@@ -95,11 +102,14 @@ tgx_status tgx_host_assertion_json(const char *assertion_json, double value, int
  *     {"type": "size"}, {"type": "completeness|distinctness|approx_count_distinct|mean|min|max|sum|standard_deviation", "column": "c"},
  *     {"type": "correlation", "column1": "a", "column2": "b", "method": "pearson|spearman|covariance"},
  *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10},
- *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true}]}
+ *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true},
+ *     {"type": "value_entropy", "column": "c", "max_unique_values": 10000, "arrow_type": "Int64" (optional)}]}
+ * "value_entropy" is the tag of EntropyAnalyzer (TG/analyzers/advanced/entropy.rs; name() "entropy", metric key
+ * "entropy.<column>"): the tag "entropy" is not taken, it stays an unknown analyzer type.
  * AnalysisRunner::run: every analyzer's aggregates planned into ONE tgx_plan, one pass over the table; the
  * mutual_information and histogram analyzers (bin edges depend on the whole table) add a second pass for their counts,
  * shared by all such analyzers of the run.  Returns
- *   {"metrics": {metric_key: {"type": "Double|Long|Map|Histogram", "value": ..}},   (MetricValue's serde form, types.rs:11-35)
+ *   {"metrics": {metric_key: {"type": "Double|Long|Boolean|Map|Histogram", "value": ..}},   (MetricValue's serde form, types.rs:11-35)
  *    "states":  {metric_key: {..the AnalyzerState's serde fields..}},
  *    "errors":  [{"analyzer_name": "..", "error": ".."}]}                        (context.rs:118-123)
  * With continue_on_error false the first failing analyzer makes the call fail with "Analyzer {name} failed". */

@@ -20,6 +20,8 @@ TIME_GAP = 13  # gaps between neighbouring timestamps, whole table or per group 
 VALUE_RULE = 14  # numeric value rules: >= 0, > 0, between, whole (Plan.set_value_rule)
 RULE_GE_ZERO, RULE_GT_ZERO, RULE_BETWEEN, RULE_INTEGER = 1, 2, 3, 4
 RULE_BOUNDS_AS_DOUBLE = 1
+VALUE_COUNTS = 15  # how often each value of a column occurs, for a bounded number of values (Plan.set_value_counts)
+VALUE_COUNTS_MAX_DISTINCT, VALUE_COUNTS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -120,6 +122,22 @@ class ValueRuleParams(C.Structure):
 class ValueRuleCounts(C.Structure):
     """tgx_value_rule_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("valid", C.c_uint64), ("cast_errors", C.c_uint64)]
+
+
+class ValueCountsParams(C.Structure):
+    """tgx_value_counts_params (include/tgx.h)"""
+    _fields_ = [("max_distinct", C.c_uint32), ("max_value_bytes", C.c_uint32)]
+
+
+class ValueCountsSummary(C.Structure):
+    """tgx_value_counts_summary (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("non_null", C.c_uint64), ("distinct", C.c_uint64), ("counted", C.c_uint64),
+                ("overflow_rows", C.c_uint64), ("long_rows", C.c_uint64)]
+
+
+class ValueCountEntry(C.Structure):
+    """tgx_value_count_entry (include/tgx.h)"""
+    _fields_ = [("value", C.c_int64), ("offset", C.c_uint64), ("length", C.c_uint64), ("count", C.c_uint64)]
 
 
 class HistogramRange(C.Structure):
@@ -248,6 +266,10 @@ def lib():
         L.tgx_time_gap_get.argtypes = [vp, vp, sz, C.POINTER(TimeGapCounts), E]
         L.tgx_plan_set_value_rule.argtypes = [vp, sz, C.POINTER(ValueRuleParams), E]
         L.tgx_value_rule_get.argtypes = [vp, vp, sz, C.POINTER(ValueRuleCounts), E]
+        L.tgx_plan_set_value_counts.argtypes = [vp, sz, C.POINTER(ValueCountsParams), E]
+        L.tgx_value_counts_get.argtypes = [vp, vp, sz, C.POINTER(ValueCountsSummary), E]
+        L.tgx_value_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
+                                               C.POINTER(C.c_int32), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -675,6 +697,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_value_rule(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_value_counts(self, spec_index, max_distinct=10000, max_value_bytes=256):
+        """tgx_plan_set_value_counts: the bounds of a VALUE_COUNTS spec (before the plan's first state)"""
+        p = ValueCountsParams(max_distinct, max_value_bytes)
+        err = _Error()
+        _check(lib().tgx_plan_set_value_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
         lib().tgx_plan_get_fingerprint_key(self.h, out)
@@ -868,6 +896,28 @@ class State:
         err = _Error()
         _check(lib().tgx_value_rule_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.considered, out.valid, out.cast_errors
+
+    # value counts
+    def value_counts(self, spec_index):
+        """tgx_value_counts_get + tgx_value_counts_entries: (summary, counts) -- summary a dict of the six counters
+        (seen, non_null, distinct, counted, overflow_rows, long_rows), counts a dict value -> count in the library's
+        order (ascending by value); its keys are ints for an integer column and bytes for a string column"""
+        L, err = lib(), _Error()
+        s = ValueCountsSummary()
+        _check(L.tgx_value_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        n, nb, is_bytes = C.c_uint64(), C.c_uint64(), C.c_int32()
+        _check(L.tgx_value_counts_entries(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, 0, C.byref(nb),
+                                          C.byref(is_bytes), C.byref(err)), err)
+        entries = (ValueCountEntry * max(n.value, 1))()
+        buf = (C.c_uint8 * max(nb.value, 1))()
+        _check(L.tgx_value_counts_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), buf, nb.value,
+                                          C.byref(nb), C.byref(is_bytes), C.byref(err)), err)
+        raw = bytes(buf)
+        counts = {}
+        for e in entries[:n.value]:
+            counts[raw[e.offset:e.offset + e.length] if is_bytes.value else e.value] = e.count
+        summary = {f: getattr(s, f) for f, _ in ValueCountsSummary._fields_}
+        return summary, counts
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -1,6 +1,6 @@
 // analyzers.cpp -- see analyzers.h.  Reference: TG/analyzers/{traits,runner,context,types,errors}.rs,
 // TG/analyzers/basic/{size,completeness,distinctness,mean,min_max,sum}.rs,
-// TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram}.rs.
+// TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram,entropy}.rs.
 #include "analyzers.h"
 
 #include <math.h>
@@ -91,6 +91,7 @@ std::string MetricValue::to_json() const {
   switch (kind) {
     case Double: return "{\"type\": \"Double\", \"value\": " + num_text(d) + "}";
     case Long: return "{\"type\": \"Long\", \"value\": " + std::to_string(l) + "}";
+    case Boolean: return std::string("{\"type\": \"Boolean\", \"value\": ") + (b ? "true" : "false") + "}";
     case Map: {
       std::string o = "{\"type\": \"Map\", \"value\": {";
       for (size_t i = 0; i < map.size(); i++) o += (i ? ", " : "") + json::quote(map[i].first) + ": " + map[i].second.to_json();
@@ -703,6 +704,76 @@ class HistogramAnalyzer : public ColumnAnalyzer {
   bool strict_types_;
 };
 
+// advanced/entropy.rs: SELECT CAST(col AS VARCHAR), COUNT(*) .. WHERE col IS NOT NULL GROUP BY .. as one
+// TGX_CHECK_VALUE_COUNTS request bounded by max_unique_values.  The state is EntropyState's serde form; beyond the bound
+// the analyzer fails with the numbers (the reference's truncated top-N sampling is not reproduced: `truncated` is only
+// ever true in a state that was handed in).  Its JSON tag is "value_entropy"; name() is the reference's "entropy".
+class EntropyAnalyzer : public ColumnAnalyzer {
+ public:
+  EntropyAnalyzer(std::string c, uint64_t max_unique_values, std::string arrow_type)
+      : ColumnAnalyzer(std::move(c)), max_unique_(std::max<uint64_t>(max_unique_values, 10)),  // entropy.rs:66-71
+        arrow_type_(std::move(arrow_type)) {}
+  std::string name() const override { return "entropy"; }
+  std::vector<SpecRequest> plan() const override { return {value_counts_request(column_, max_unique_)}; }
+  bool reads_value_counts() const override { return true; }
+  std::string value_text_refusal(int type) const override {
+    const std::string t = !arrow_type_.empty()      ? arrow_type_
+                          : type == TGX_FLOAT64     ? "Float64"
+                          : type == TGX_FLOAT32     ? "Float32"
+                          : type == TGX_BOOL        ? "Boolean"
+                                                    : "";
+    return term_guard::value_text_refusal(column_, t);
+  }
+  json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
+    throw AnalyzerError::invalid_data("the entropy state is built from value counts");
+  }
+  json::Value state_from_value_counts(const ValueCounts &vc) const override {
+    const std::string beyond = value_counts_out_of_bound(vc, max_unique_);
+    if (!beyond.empty()) throw AnalyzerError::invalid_data(beyond);
+    return entropy_state(vc);
+  }
+  json::Value merge_states(const std::vector<json::Value> &states) const override { return entropy_merge(states); }
+  MetricValue metric_from_state(const json::Value &s) const override {  // :337-395
+    const json::Value *vc = s.get("value_counts");
+    const size_t unique = vc && vc->is(json::Value::Object) ? vc->obj.size() : 0;
+    const uint64_t total = u(s, "total_count");
+    const double h = entropy_bits(s);
+    MetricValue m;
+    m.kind = MetricValue::Map;
+    m.map.push_back({"entropy", MetricValue::of_double(h)});
+    m.map.push_back({"normalized_entropy", MetricValue::of_double(unique <= 1 ? 0.0 : h / log2((double)unique))});
+    m.map.push_back({"gini_impurity", MetricValue::of_double(entropy_gini(s))});
+    m.map.push_back({"effective_values", MetricValue::of_double(pow(2.0, h))});
+    m.map.push_back({"unique_values", MetricValue::of_long((int64_t)unique)});
+    m.map.push_back({"total_count", MetricValue::of_long((int64_t)total)});
+    m.map.push_back({"truncated", MetricValue::of_bool(s.get_bool("truncated", false))});
+    if (unique <= 100) {  // the ten most frequent values (ties by text: the reference's HashMap order is arbitrary)
+      std::vector<std::pair<std::string, uint64_t>> top;
+      if (unique)
+        for (const auto &kv : vc->obj) top.emplace_back(kv.first, kv.second.as_u64());
+      std::sort(top.begin(), top.end(), [](const std::pair<std::string, uint64_t> &a, const std::pair<std::string, uint64_t> &b) {
+        return a.second != b.second ? a.second > b.second : a.first < b.first;
+      });
+      if (top.size() > 10) top.resize(10);
+      MetricValue tv;
+      tv.kind = MetricValue::Map;
+      for (const auto &e : top) {
+        MetricValue one;
+        one.kind = MetricValue::Map;
+        one.map.push_back({"count", MetricValue::of_long((int64_t)e.second)});
+        one.map.push_back({"probability", MetricValue::of_double((double)e.second / (double)total)});
+        tv.map.push_back({e.first, one});
+      }
+      m.map.push_back({"top_values", tv});
+    }
+    return m;
+  }
+
+ private:
+  uint64_t max_unique_;
+  std::string arrow_type_;
+};
+
 struct Handles {
   tgx_plan *plan = nullptr;
   tgx_state *state = nullptr;
@@ -753,6 +824,9 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
   }
   if (t == "histogram")
     return std::make_shared<HistogramAnalyzer>(col(), v.get_u64("num_buckets", 10), v.get_bool("strict_reference_types", true));
+  // ("entropy" stays an unknown type: the tag of EntropyAnalyzer is "value_entropy")
+  if (t == "value_entropy")
+    return std::make_shared<EntropyAnalyzer>(col(), v.get_u64("max_unique_values", 10000), v.get_str("arrow_type"));
   throw TermError{TermError::Internal, "unknown analyzer type '" + t + "'"};
 }
 
@@ -798,6 +872,10 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
           if (type == 0) type = b.columns[ci].type;
       p.column_types.push_back(type);
     }
+    if (!p.error && analyzers_[a]->reads_value_counts()) {
+      const std::string refusal = analyzers_[a]->value_text_refusal(p.column_types.empty() ? 0 : p.column_types[0]);
+      if (!refusal.empty()) p.error = AnalyzerError::invalid_data(refusal).text;
+    }
   }
   // one pass over the table for every analyzer that is still in the run: their requests fused and de-duplicated
   std::vector<tgx_check_spec> specs;
@@ -811,7 +889,7 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
         size_t found = requests.size();
         for (size_t i = 0; i < requests.size(); i++)
           if (requests[i].kind == r.kind && requests[i].column == r.column && requests[i].column2 == r.column2 &&
-              requests[i].flags == r.flags)
+              requests[i].flags == r.flags && requests[i].same_parameters(r))
             found = i;
         if (found == requests.size()) requests.push_back(r);
         p.spec_index.push_back(found);
@@ -844,6 +922,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
               ? tgx_plan_set_histogram_edges(hh.plan, i, fu.edges.data(), (uint32_t)(fu.edges.size() - 1), &err)
               : tgx_plan_set_joint_binning(hh.plan, i, &fu.binning, &err);
     }
+    for (size_t i = 0; s == TGX_OK && !follow_ups && i < requests.size(); i++)
+      if (requests[i].value_counts) s = tgx_plan_set_value_counts(hh.plan, i, &*requests[i].value_counts, &err);
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
     for (size_t b = 0; s == TGX_OK && b < table->batches.size(); b++) {
@@ -979,9 +1059,18 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       try {
         std::vector<const tgx_result *> r;
         for (size_t si : planned[a].spec_index) r.push_back(&results[si]);
-        json::Value st = an.two_pass()
-                             ? an.state_from_follow_up(followed[a].first, followed[a].counted ? &followed[a].second : nullptr)
-                             : an.state_from_results(r, planned[a].column_types);
+        json::Value st;
+        if (an.reads_value_counts()) {
+          try {
+            st = an.state_from_value_counts(read_value_counts(h.plan, h.state, planned[a].spec_index[0]));
+          } catch (const TermError &e) {
+            throw AnalyzerError::query(e.display());
+          }
+        } else {
+          st = an.two_pass()
+                   ? an.state_from_follow_up(followed[a].first, followed[a].counted ? &followed[a].second : nullptr)
+                   : an.state_from_results(r, planned[a].column_types);
+        }
         MetricValue m = an.metric_from_state(st);
         out.states.push_back({an.metric_key(), st});
         // context.rs:71-73: a later analyzer with the same key replaces the earlier metric

@@ -14,6 +14,7 @@
 
 #include "json.h"
 #include "term_guard.h"
+#include "value_counts.h"
 
 namespace term_guard {
 
@@ -28,15 +29,22 @@ struct MetricDistribution {  // types.rs:95-157; the statistics are Options ther
   std::optional<double> min, max, mean, std_dev;
 };
 struct MetricValue {
-  enum Kind { Double, Long, Map, Histogram } kind = Double;
+  enum Kind { Double, Long, Map, Histogram, Boolean } kind = Double;
   double d = 0;
   int64_t l = 0;
+  bool b = false;
   std::vector<std::pair<std::string, MetricValue>> map;  // insertion ordered (the reference's HashMap is unordered)
   MetricDistribution histogram;
   static MetricValue of_double(double v) {
     MetricValue m;
     m.kind = Double;
     m.d = v;
+    return m;
+  }
+  static MetricValue of_bool(bool v) {
+    MetricValue m;
+    m.kind = Boolean;
+    m.b = v;
     return m;
   }
   static MetricValue of_long(int64_t v) {
@@ -99,6 +107,12 @@ class Analyzer {
   // parameters of the follow-up request back (nullopt: no rows, no second pass; throws AnalyzerError when the range
   // has none), runs ALL follow-up requests of the run as one more fused pass and builds the state with
   // state_from_follow_up (the SecondPass is nullptr when there was no second pass).
+  // An analyzer whose plan()[0] is a TGX_CHECK_VALUE_COUNTS request (EntropyAnalyzer) builds its state from the entries
+  // the device counted, not from a tgx_result (host/value_counts.h).  value_text_refusal(): what is wrong with reading
+  // the column's values as text, asked before the device sees the column ("" when nothing is)
+  virtual bool reads_value_counts() const { return false; }
+  virtual std::string value_text_refusal(int /*tgx_type of the column*/) const { return std::string(); }
+  virtual json::Value state_from_value_counts(const ValueCounts &) const { return json::Value(); }
   virtual bool two_pass() const { return false; }
   virtual std::optional<FollowUp> follow_up(const FirstPass &) const { return std::nullopt; }
   virtual json::Value state_from_follow_up(const FirstPass &, const SecondPass *) const { return json::Value(); }

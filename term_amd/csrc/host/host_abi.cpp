@@ -8,6 +8,7 @@
 #include "json.h"
 #include "analyzers.h"
 #include "datatype.h"
+#include "value_counts.h"
 #include "temporal.h"
 #include "term_guard.h"
 
@@ -116,6 +117,9 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
              "}";
       }
       if (r.value_rule) o += ", \"value_rule\": " + value_rule_json(*r.value_rule);
+      if (r.value_counts)
+        o += ", \"value_counts\": {\"max_distinct\": " + std::to_string(r.value_counts->max_distinct) +
+             ", \"max_value_bytes\": " + std::to_string(r.value_counts->max_value_bytes) + "}";
       o += "}";
     }
     o += "]}";
@@ -135,7 +139,13 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
 namespace {
 struct FakeQuantiles {
   std::vector<std::vector<std::pair<double, double>>> per_request;
+  std::vector<std::optional<ValueCounts>> value_counts;  // per request: what a VALUE_COUNTS entry of results_json carries
 };
+void fake_value_counts(const void *ctx, size_t idx, ValueCounts *out) {
+  const FakeQuantiles *f = (const FakeQuantiles *)ctx;
+  if (!f->value_counts.at(idx)) throw TermError{TermError::Internal, "results_json has no value_counts for this request"};
+  *out = *f->value_counts[idx];
+}
 double fake_quantile(const void *ctx, size_t idx, double phi) {
   const FakeQuantiles *f = (const FakeQuantiles *)ctx;
   for (auto &kv : f->per_request.at(idx))
@@ -157,6 +167,7 @@ extern "C" tgx_status tgx_host_constraint_verdict_json(const char *constraint_js
     std::vector<tgx_result> results(rv.arr.size());
     FakeQuantiles fq;
     fq.per_request.resize(rv.arr.size());
+    fq.value_counts.resize(rv.arr.size());
     for (size_t i = 0; i < rv.arr.size(); i++) {
       const json::Value &o = rv.arr[i];
       tgx_result &r = results[i];
@@ -200,6 +211,20 @@ extern "C" tgx_status tgx_host_constraint_verdict_json(const char *constraint_js
       r.kll_n = o.get_u64("kll_n");
       if (const json::Value *q = o.get("quantiles"))
         for (auto &kv : q->obj) fq.per_request[i].emplace_back(atof(kv.first.c_str()), kv.second.num);
+      if (const json::Value *vc = o.get("value_counts")) {  // {"entries": {text: count}, "overflow_rows", "long_rows"}
+        ValueCounts v;
+        v.summary.seen = (uint64_t)r.total;
+        v.summary.non_null = (uint64_t)r.non_null;
+        v.summary.overflow_rows = vc->get_u64("overflow_rows");
+        v.summary.long_rows = vc->get_u64("long_rows");
+        if (const json::Value *e = vc->get("entries"))
+          for (auto &kv : e->obj) {
+            v.entries.emplace_back(kv.first, kv.second.as_u64());
+            v.summary.counted += kv.second.as_u64();
+          }
+        v.summary.distinct = vc->get("distinct") ? vc->get_u64("distinct") : v.entries.size();
+        fq.value_counts[i] = std::move(v);
+      }
     }
     const size_t want = c->plan().size();
     if (results.size() != want)
@@ -209,6 +234,7 @@ extern "C" tgx_status tgx_host_constraint_verdict_json(const char *constraint_js
     for (auto &r : results) in.results.push_back(&r);
     in.ctx = &fq;
     in.quantile = fake_quantile;
+    in.value_counts = fake_value_counts;
     {  // the reference's result-type rule (term_guard.h reference_extracts): "column_type" = the column's Arrow DataType
       json::Value cv;
       std::string cerr;

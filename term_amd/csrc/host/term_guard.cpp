@@ -13,6 +13,7 @@
 
 #include "json.h"
 #include "datatype.h"
+#include "value_counts.h"
 #include "temporal.h"
 
 namespace term_guard {
@@ -1222,6 +1223,10 @@ double quantile_cb(const void *ctx, size_t request_index, double phi) {
     throw TermError{TermError::Internal, err.msg};
   return out;
 }
+void value_counts_cb(const void *ctx, size_t request_index, ValueCounts *out) {
+  const QuantileCtx *q = (const QuantileCtx *)ctx;
+  *out = read_value_counts(q->plan, q->state, q->spec_of_request[request_index]);
+}
 std::string now_rfc3339() {
   using namespace std::chrono;
   auto now = system_clock::now();
@@ -1315,6 +1320,13 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
             }
           }
           if (p.error) break;
+          if (r.value_counts) {  // a value text the device does not reproduce is this constraint's error, before the scan
+            const std::string refusal = value_text_refusal(r.column, arrow_type_of(r.column));
+            if (!refusal.empty()) {
+              p.error = TermError{TermError::ConstraintEvaluation, "'" + c->name() + "': " + refusal}.display();
+              break;
+            }
+          }
           if (r.temporal) {  // the unit rules (host/temporal.cpp): what is missing is this constraint's error
             try {
               if (r.kind == TGX_CHECK_TIME_GAP)
@@ -1346,9 +1358,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
           const SpecRequest &q = spec_requests[i];
           if (q.kind == r.kind && q.column == r.column && q.column2 == r.column2 && q.columns == r.columns &&
               q.flags == r.flags && q.pattern == r.pattern && q.kll_k == r.kll_k && q.length_min == r.length_min &&
-              q.length_max == r.length_max && q.temporal == r.temporal &&
-              q.value_rule.has_value() == r.value_rule.has_value() &&
-              (!r.value_rule || memcmp(&*q.value_rule, &*r.value_rule, sizeof(tgx_value_rule_params)) == 0))
+              q.length_max == r.length_max && q.temporal == r.temporal && q.same_parameters(r))
             found = i;
         }
         if (found == spec_requests.size()) spec_requests.push_back(r);
@@ -1394,6 +1404,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
     for (size_t i = 0; s == TGX_OK && i < spec_requests.size(); i++) {
       const SpecRequest &r = spec_requests[i];
       if (r.value_rule) s = tgx_plan_set_value_rule(hh.plan, i, &*r.value_rule, &err);
+      if (r.value_counts && s == TGX_OK) s = tgx_plan_set_value_counts(hh.plan, i, &*r.value_counts, &err);
       if (!r.temporal) continue;
       if (r.kind == TGX_CHECK_TIME_GAP) {
         const tgx_time_gap_params gp = time_gap_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
@@ -1479,6 +1490,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       in.strict_reference_types = strict_types_;
       in.ctx = &qctx;
       in.quantile = quantile_cb;
+      in.value_counts = value_counts_cb;
       try {
         cr = p.constraint->evaluate(in);
       } catch (const TermError &e) {
@@ -1758,6 +1770,24 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     b.constraint(temporal_ordering_from_json(c));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
+  } else if (type == "histogram") {
+    // {"type": "histogram", "column", "measures": [{"measure", "assertion", "n"?, "value"?}, ..], "description"?,
+    //  "max_distinct"? (default 10000)}: every measure must hold
+    std::vector<HistogramMeasure> measures;
+    if (const json::Value *mv = c.get("measures"))
+      if (mv->is(json::Value::Array))
+        for (const json::Value &e : mv->arr) {
+          HistogramMeasure m;
+          m.measure = e.get_str("measure");
+          m.assertion = assertion_from(*need(e, "assertion"));
+          m.n = (size_t)e.get_u64("n", 0);
+          m.value = e.get_str("value");
+          measures.push_back(std::move(m));
+        }
+    std::optional<std::string> description;
+    if (c.get("description") && c.get("description")->is(json::Value::String)) description = c.get_str("description");
+    b.constraint(std::make_shared<HistogramConstraint>(c.get_str("column"), std::move(measures), description,
+                                                       c.get_u64("max_distinct", HistogramConstraint::kDefaultMaxDistinct)));
   } else {
     throw TermError{TermError::Internal, "unknown constraint type '" + type + "'"};
   }

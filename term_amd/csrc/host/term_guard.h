@@ -14,6 +14,8 @@
 // constraint apply its own verdict to the shared results.  The DataFusion SessionContext is replaced by
 // `Context`, a registry of named tables whose batches are Arrow-layout column views (host or device).
 #pragma once
+#include <string.h>
+
 #include <functional>
 #include <map>
 #include <memory>
@@ -177,7 +179,18 @@ struct SpecRequest {
   std::optional<TemporalRequest> temporal;      // TEMPORAL (`column2`: the after column in order mode) and TIME_GAP
                                                 // (`column2`: the group column, or empty)
   std::optional<tgx_value_rule_params> value_rule;  // VALUE_RULE: the rule as the device takes it (host/datatype.h)
+  std::optional<tgx_value_counts_params> value_counts;  // VALUE_COUNTS: the bounds (host/value_counts.h)
+  // do two requests ask the device for the same thing (what the runners' fusing compares beside kind and columns)?
+  bool same_parameters(const SpecRequest &o) const {
+    return value_rule.has_value() == o.value_rule.has_value() &&
+           (!value_rule || memcmp(&*value_rule, &*o.value_rule, sizeof(tgx_value_rule_params)) == 0) &&
+           value_counts.has_value() == o.value_counts.has_value() &&
+           (!value_counts || (value_counts->max_distinct == o.value_counts->max_distinct &&
+                              value_counts->max_value_bytes == o.value_counts->max_value_bytes));
+  }
 };
+struct ValueCounts;  // host/value_counts.h
+class Histogram;
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:
 // plan() says which aggregates are needed, evaluate() turns them into the verdict.
@@ -193,6 +206,8 @@ class Constraint {
     std::vector<const tgx_result *> results;
     const void *ctx = nullptr;
     double (*quantile)(const void *ctx, size_t request_index, double phi) = nullptr;
+    // reads a VALUE_COUNTS request (index into plan()): the counters and the entries, values as text; throws TermError
+    void (*value_counts)(const void *ctx, size_t request_index, ValueCounts *out) = nullptr;
     // the Arrow DataType of the column request i reads, as the caller holds it ("Int64", "Int32", "Date32",
     // "Timestamp", "Float32", "UInt16", ...; empty = unknown, taken for Int64 / Float64), and whether the verdict
     // follows the reference's own extraction rule for it (reference_extracts below)
@@ -327,6 +342,11 @@ class Check::Builder {
   // reference's constructor returns Err and the builder panics on it (a threshold outside [0, 1]: Configuration).  The other validations come
   // as configured objects through constraint(..) (host/datatype.h)
   Builder &has_consistent_data_type(std::string column, double threshold);
+  // core/check.rs has_histogram / has_histogram_with_description: pushes HistogramConstraint::new[_with_description]
+  // (host/value_counts.h; max_distinct bounds the values the device counts, default 10000)
+  Builder &has_histogram(std::string column, std::function<bool(const Histogram &)> assertion);
+  Builder &has_histogram_with_description(std::string column, std::function<bool(const Histogram &)> assertion,
+                                          std::string description);
   Check build() { return check_; }
 
  private:

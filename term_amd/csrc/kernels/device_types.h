@@ -218,6 +218,34 @@ struct ValueRuleLaunch {
   unsigned long long *counts;
 };
 
+// Value counts of one column (kernels/valuecounts.hip; TGX_CHECK_VALUE_COUNTS): a bounded GROUP BY.  A task's running
+// state on the device is one open-addressing table of `mask + 1` slots (a power of two >= 2 * max_distinct) in one
+// allocation, plus kValueCountsWords 64-bit counters.
+//   numeric keys: keys[slot] (the int64 value; all-ones = free, the VALUE -1 is counted in a word of its own),
+//                 counts[slot]
+//   string keys:  keys[slot] / keys2[slot] (the two fingerprint words; fingerprint.h never produces all-ones),
+//                 counts[slot], lens[slot] and the value's bytes at store + slot * max_value_bytes, written by the lane
+//                 that claimed the slot
+// A key that finds no slot within kValueCountsProbes probes adds its weight to the overflow word.
+// (kVcLong is not the last word: the kernels flush it as the first of a pair of counters, bin_count.h's tail_flush)
+enum { kVcNonNull = 0, kVcMarker = 1, kVcLong = 2, kVcOverflow = 3, kValueCountsWords = 4 };
+constexpr int kValueCountsBlock = 1024;       // numeric route: 16 waves share one LDS table
+constexpr uint32_t kValueCountsLdsSlots = 8192;  // 8-byte keys + 4-byte counts: 96 KiB of LDS a workgroup
+constexpr uint32_t kValueCountsLdsProbes = 8;
+constexpr uint32_t kValueCountsStrLdsSlots = 1024;   // string route: two key words, a row and a count: 28 KiB
+constexpr uint32_t kValueCountsDictLdsCells = 16384;  // dictionary route: 32-bit cells in LDS up to this many entries
+constexpr uint32_t kValueCountsProbes = 256;
+struct ValueCountsTable {
+  unsigned long long *keys, *keys2, *counts;
+  uint32_t *lens;
+  uint8_t *store;
+  unsigned long long *words;  // kValueCountsWords counters
+  uint64_t mask;
+  uint64_t salt;  // numeric keys are mixed with it before they are hashed (from the plan's fingerprint key)
+  uint32_t max_value_bytes;
+  uint32_t pad;
+};
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

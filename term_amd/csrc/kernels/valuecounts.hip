@@ -1,0 +1,348 @@
+// valuecounts.hip -- value counts for gfx950 (TGX_CHECK_VALUE_COUNTS): how often each value of one column occurs,
+//   SELECT col, COUNT(*) FROM t WHERE col IS NOT NULL GROUP BY col
+// for a BOUNDED number of distinct values (the GROUP BY behind the reference's HistogramConstraint and EntropyAnalyzer:
+// TG/constraints/histogram.rs:205-391, TG/analyzers/advanced/entropy.rs:192-335).
+//
+// One open-addressing table primitive (vc_claim / vc_insert), used at two places: in LDS per workgroup with 32-bit counts
+// (a workgroup sees fewer than 2^32 rows: side_rows_fit) and in global memory per task with 64-bit counts
+// (ValueCountsTable, device_types.h).  A slot is claimed by CAS on its key word; a string key (two fingerprint words)
+// claims the first word by CAS and then settles the second by CAS: the slot is the key's when both come back free or
+// equal, otherwise probing goes on.  A probe sequence that runs out adds the key's weight to the overflow counter, so
+// every non-NULL row ends up in exactly one of: an entry, the overflow counter, the long-rows counter.
+//
+//   numeric route     value_counts_i64_kernel walks the column once (row_walk.h's single-column form: 8 B + 1 bit per row).
+//                     Equal keys are combined within the wave before the LDS atomic (the wave's first live key is
+//                     broadcast, its lanes are counted with a ballot: a constant column is one LDS atomic per wave and
+//                     64 rows).  The table has 8192 slots (96 KiB: one 1024-thread workgroup a CU; 4096 slots and two
+//                     512-thread workgroups measured the same up to 16 values and 1.2 - 2.5 times slower from 1000
+//                     values on).  A key that finds the workgroup's LDS table full goes to the global table directly; at the
+//                     end every occupied LDS slot is one global insert with its count.
+//   string route      value_counts_utf8_kernel: a row per lane (Utf8 / LargeUtf8 / Utf8View through utf8_value's three
+//                     layouts).  Rows longer than max_value_bytes are counted as long rows; the others are reduced to
+//                     their keyed fingerprint, equal fingerprints are combined within the wave (up to four rounds), and
+//                     the leaders insert into the workgroup's LDS table, whose slots also remember a row that holds
+//                     the value (a full table: straight into the global one).  At the end every occupied LDS slot is
+//                     one global insert with its count.  The lane that claims a GLOBAL slot copies the value's bytes
+//                     and length into the slot's place in the value store -- on the device, in the same stream.
+//   dictionary route  value_counts_dict_count_kernel counts the INDICES into one 64-bit cell per dictionary entry (up to
+//                     16384 entries through 32-bit cells in LDS, bin_count.h's idiom; above that with global atomics);
+//                     value_counts_dict_insert_kernel then takes a lane per entry with a non-zero count, fingerprints the
+//                     entry and inserts it with its count (rows of NULL entries are counted nowhere: they are NULLs).
+//                     Entries that repeat a value, and the dictionaries of different batches, unite by value.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "bin_count.h"
+#include "device_types.h"
+#include "fingerprint.h"
+#include "row_walk.h"
+
+namespace tgx {
+
+namespace {
+
+// ---- the table primitive ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long vc_peek(const unsigned long long *word) {
+  return __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// probes from slot `h` for `key`: the slot that holds it, claimed if need be, or -1 when `probes` slots held other keys
+template <class Slot>
+__device__ __forceinline__ int64_t vc_claim(unsigned long long *keys, Slot mask, Slot h, unsigned long long key,
+                                            uint32_t probes) {
+  for (uint32_t p = 0; p < probes; p++) {
+    // (a key word never changes once it is set: a plain look spares the hot keys their CAS)
+    unsigned long long old = vc_peek(&keys[h]);
+    if (old == kEmptyKey) old = atomicCAS(&keys[h], (unsigned long long)kEmptyKey, key);
+    if (old == kEmptyKey || old == key) return (int64_t)h;
+    h = (h + 1) & mask;
+  }
+  return -1;
+}
+
+// a numeric key with its weight into the task's global table
+__device__ __forceinline__ void vc_insert_global(const ValueCountsTable &t, unsigned long long key,
+                                                 unsigned long long weight) {
+  const int64_t s = vc_claim<uint64_t>(t.keys, t.mask, mix64(key ^ t.salt) & t.mask, key, kValueCountsProbes);
+  if (s >= 0) atomicAdd(&t.counts[s], weight);
+  else atomicAdd(&t.words[kVcOverflow], weight);
+}
+
+// a string key (fa, fb) whose bytes are [p, p + len), with its weight
+__device__ __forceinline__ void vc_insert_global128(const ValueCountsTable &t, unsigned long long fa,
+                                                    unsigned long long fb, unsigned long long weight, uintptr_t p,
+                                                    uint32_t len) {
+  uint64_t h = fa & t.mask;
+  for (uint32_t probe = 0; probe < kValueCountsProbes; probe++) {
+    unsigned long long a = vc_peek(&t.keys[h]);
+    if (a == kEmptyKey) a = atomicCAS(&t.keys[h], (unsigned long long)kEmptyKey, fa);
+    if (a == kEmptyKey || a == fa) {
+      unsigned long long b = vc_peek(&t.keys2[h]);
+      const bool made = b == kEmptyKey && (b = atomicCAS(&t.keys2[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
+      if (made) {  // this lane made the entry: its bytes go to the slot's place in the store
+        global_u8_ptr src = (global_u8_ptr)p;
+        uint8_t *dst = t.store + h * (uint64_t)t.max_value_bytes;
+        for (uint32_t i = 0; i < len; i++) dst[i] = src[i];
+        t.lens[h] = len;
+      }
+      if (made || b == fb) {
+        atomicAdd(&t.counts[h], weight);
+        return;
+      }
+    }
+    h = (h + 1) & t.mask;
+  }
+  atomicAdd(&t.words[kVcOverflow], weight);
+}
+
+// the workgroup's table of string keys: the two fingerprint words, a 32-bit count and a row that holds the value
+struct VcLdsStrings {
+  unsigned long long fa[kValueCountsStrLdsSlots], fb[kValueCountsStrLdsSlots], row[kValueCountsStrLdsSlots];
+  unsigned int count[kValueCountsStrLdsSlots];
+};
+// false: the slots around the key's place hold other keys
+__device__ __forceinline__ bool vc_insert_lds128(VcLdsStrings &l, unsigned long long fa, unsigned long long fb,
+                                                 uint32_t weight, unsigned long long row) {
+  uint32_t h = (uint32_t)fa & (kValueCountsStrLdsSlots - 1);
+  for (uint32_t probe = 0; probe < kValueCountsLdsProbes; probe++) {
+    unsigned long long a = vc_peek(&l.fa[h]);
+    if (a == kEmptyKey) a = atomicCAS(&l.fa[h], (unsigned long long)kEmptyKey, fa);
+    if (a == kEmptyKey || a == fa) {
+      unsigned long long b = vc_peek(&l.fb[h]);
+      const bool made = b == kEmptyKey && (b = atomicCAS(&l.fb[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
+      if (made) l.row[h] = row;  // (read after the workgroup's barrier)
+      if (made || b == fb) {
+        atomicAdd(&l.count[h], weight);
+        return true;
+      }
+    }
+    h = (h + 1) & (kValueCountsStrLdsSlots - 1);
+  }
+  return false;
+}
+
+// where the value of slot `slot` of a string column lies (the three layouts: int32 offsets, int64 offsets, views)
+__device__ __forceinline__ void utf8_value_of(const Utf8ColDesc &d, int64_t slot, uintptr_t *p, uint64_t *len) {
+  if (d.views) {
+    global_i32_ptr vw = (global_i32_ptr)((uintptr_t)d.views + (uintptr_t)slot * 16);
+    const int32_t n = vw[0];
+    *len = (uint64_t)(uint32_t)n;
+    if (n <= 12) *p = (uintptr_t)d.views + (uintptr_t)slot * 16 + 4;
+    else *p = (uintptr_t)d.buffers[vw[2]] + (uintptr_t)(uint32_t)vw[3];
+  } else if (d.large_offsets) {
+    global_i64_ptr off = (global_i64_ptr)(uintptr_t)d.offsets;
+    const int64_t b = off[slot];
+    *p = (uintptr_t)d.data + (uintptr_t)b;
+    *len = (uint64_t)(off[slot + 1] - b);
+  } else {
+    global_i32_ptr off = (global_i32_ptr)(uintptr_t)d.offsets;
+    const int32_t b = off[slot];
+    *p = (uintptr_t)d.data + (uintptr_t)b;
+    *len = (uint64_t)(off[slot + 1] - b);
+  }
+}
+
+__device__ __forceinline__ unsigned long long vc_shfl64(unsigned long long v, int lane) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+}  // namespace
+
+// ---- numeric route ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kValueCountsBlock) void value_counts_i64_kernel(const ComomentColDesc d,
+                                                                             const ValueCountsTable t) {
+  __shared__ unsigned long long lkeys[kValueCountsLdsSlots];
+  __shared__ unsigned int lcounts[kValueCountsLdsSlots];
+  for (uint32_t s = threadIdx.x; s < kValueCountsLdsSlots; s += kValueCountsBlock) {
+    lkeys[s] = kEmptyKey;
+    lcounts[s] = 0;
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  uint32_t non_null = 0, marker = 0;  // (a workgroup sees fewer than 2^32 rows: side_rows_fit)
+  jb_for_rows_single(d, [&](int64_t v, bool ok) {
+    const unsigned long long key = (unsigned long long)v;
+    non_null += ok ? 1u : 0u;
+    const bool is_marker = ok && key == kEmptyKey;  // (the value whose bits are the free-slot marker)
+    marker += is_marker ? 1u : 0u;
+    const bool live = ok && !is_marker;
+    const unsigned long long todo = __ballot(live);
+    if (todo == 0) return;
+    // the wave's first live key is counted once for all the lanes that hold it; the others add for themselves
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned long long first = vc_shfl64(key, leader);
+    const unsigned long long same = __ballot(live && key == first);
+    const bool adds = lane == leader || (live && key != first);
+    if (!adds) return;
+    const uint32_t weight = lane == leader ? (uint32_t)__popcll(same) : 1u;
+    const int64_t s = vc_claim<uint32_t>(lkeys, kValueCountsLdsSlots - 1,
+                                         (uint32_t)mix64(key ^ t.salt) & (kValueCountsLdsSlots - 1), key,
+                                         kValueCountsLdsProbes);
+    if (s >= 0) atomicAdd(&lcounts[s], weight);
+    else vc_insert_global(t, key, weight);  // (the workgroup's table is full around there)
+  });
+  tail_flush(non_null, marker, t.words);  // kVcNonNull, kVcMarker
+  __syncthreads();
+  for (uint32_t s = threadIdx.x; s < kValueCountsLdsSlots; s += kValueCountsBlock) {
+    const unsigned long long key = lkeys[s];
+    if (key != kEmptyKey) vc_insert_global(t, key, lcounts[s]);
+  }
+}
+
+// ---- string route -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void value_counts_utf8_kernel(const Utf8ColDesc d, const ValueCountsTable t) {
+  global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)d.validity;
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  uint32_t non_null = 0, too_long = 0;
+  __shared__ VcLdsStrings lds;
+  for (uint32_t s = threadIdx.x; s < kValueCountsStrLdsSlots; s += 256) {
+    lds.fa[s] = lds.fb[s] = kEmptyKey;
+    lds.count[s] = 0;
+  }
+  __syncthreads();
+  // (the loop is uniform within the wave: every lane takes part in the ballots of every round)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < d.length; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t slot = d.offset + i;
+    const bool valid = i < d.length && (!vbits || TGX_VALID_BIT(vbits, slot));
+    uintptr_t p = 0;
+    uint64_t len = 0;
+    unsigned long long fa = 0, fb = 0;
+    bool live = false;
+    if (valid) {
+      non_null++;
+      utf8_value_of(d, slot, &p, &len);
+      if (len > t.max_value_bytes) {
+        too_long++;
+      } else {
+        uint64_t a, b;
+        fingerprint(d.key, p, len, &a, &b);
+        fa = a;
+        fb = b;
+        live = true;
+      }
+    }
+    unsigned long long todo = __ballot(live);
+    bool pending = live;
+    for (int round = 0; round < 4 && todo != 0; round++) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const unsigned long long la = vc_shfl64(fa, leader), lb = vc_shfl64(fb, leader);
+      const bool mine = pending && fa == la && fb == lb;
+      const unsigned long long same = __ballot(mine);
+      if (lane == leader && !vc_insert_lds128(lds, fa, fb, (uint32_t)__popcll(same), (unsigned long long)i))
+        vc_insert_global128(t, fa, fb, (unsigned long long)__popcll(same), p, (uint32_t)len);
+      pending = pending && !mine;
+      todo &= ~same;
+    }
+    if (pending && !vc_insert_lds128(lds, fa, fb, 1u, (unsigned long long)i))
+      vc_insert_global128(t, fa, fb, 1ull, p, (uint32_t)len);
+  }
+  __syncthreads();
+  // every occupied LDS slot is one global insert with its count; its bytes are those of the row it remembers
+  for (uint32_t s = threadIdx.x; s < kValueCountsStrLdsSlots; s += 256) {
+    const unsigned long long fa = lds.fa[s], fb = lds.fb[s];
+    const unsigned int n = lds.count[s];
+    if (fa == kEmptyKey || fb == kEmptyKey || n == 0) continue;
+    uintptr_t p;
+    uint64_t len;
+    utf8_value_of(d, d.offset + (int64_t)lds.row[s], &p, &len);
+    vc_insert_global128(t, fa, fb, (unsigned long long)n, p, (uint32_t)len);
+  }
+  // (tail_flush adds to out[0] and out[1], non-zero sums only: both pairs lie within the task's four words)
+  tail_flush(non_null, 0u, t.words + kVcNonNull);
+  tail_flush(too_long, 0u, t.words + kVcLong);
+}
+
+// ---- dictionary route ---------------------------------------------------------------------------------------------------
+// the rows' indices into cells[dict_length]; an index outside the dictionary is a row without a value: it is counted
+// as a NULL row (include/tgx.h says so), never read
+template <bool kLds>
+__global__ __launch_bounds__(256) void value_counts_dict_count_kernel(const int32_t *__restrict__ indices,
+                                                                      const uint8_t *__restrict__ validity,
+                                                                      int64_t offset, int64_t length, int64_t dict_length,
+                                                                      unsigned long long *__restrict__ cells) {
+  global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)validity;
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // up to kValueCountsDictLdsCells entries: the workgroup's cells are 32-bit counters in LDS (bin_count.h), flushed once
+  __shared__ unsigned int lcells[kLds ? kValueCountsDictLdsCells : 1];
+  if (kLds) {
+    for (uint32_t c = threadIdx.x; c < (uint32_t)dict_length; c += 256) lcells[c] = 0;
+    __syncthreads();
+  }
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < length; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t slot = offset + i;
+    bool live = i < length && (!vbits || TGX_VALID_BIT(vbits, slot));
+    int32_t idx = live ? indices[slot] : 0;
+    live = live && idx >= 0 && (int64_t)idx < dict_length;
+    if (kLds) {
+      bin_add(lcells, live, (uint32_t)idx);
+      continue;
+    }
+    const unsigned long long todo = __ballot(live);
+    if (todo == 0) continue;
+    const int leader = __ffsll((long long)todo) - 1;
+    const int32_t first = __shfl(idx, leader, 64);
+    const unsigned long long same = __ballot(live && idx == first);
+    if (lane == leader) atomicAdd(&cells[first], (unsigned long long)__popcll(same));
+    else if (live && idx != first) atomicAdd(&cells[idx], 1ull);
+  }
+  if (kLds) {
+    __syncthreads();
+    bin_flush<256>(lcells, (uint32_t)dict_length, cells);
+  }
+}
+
+// `d`: the dictionary's values as a string column; a lane per entry with a non-zero count
+__global__ __launch_bounds__(256) void value_counts_dict_insert_kernel(const Utf8ColDesc d,
+                                                                       const unsigned long long *__restrict__ cells,
+                                                                       const ValueCountsTable t) {
+  global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)d.validity;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < d.length; e += stride) {
+    const unsigned long long n = cells[e];
+    const int64_t slot = d.offset + e;
+    if (n == 0 || (vbits && !TGX_VALID_BIT(vbits, slot))) continue;
+    atomicAdd(&t.words[kVcNonNull], n);
+    uintptr_t p;
+    uint64_t len;
+    utf8_value_of(d, slot, &p, &len);
+    if (len > t.max_value_bytes) {
+      atomicAdd(&t.words[kVcLong], n);
+      continue;
+    }
+    uint64_t fa, fb;
+    fingerprint(d.key, p, len, &fa, &fb);
+    vc_insert_global128(t, fa, fb, n, p, (uint32_t)len);
+  }
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------
+void launch_value_counts_i64(const ComomentColDesc &d, const ValueCountsTable &t, int blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(value_counts_i64_kernel, dim3(blocks), dim3(kValueCountsBlock), 0, stream, d, t);
+}
+
+void launch_value_counts_utf8(const Utf8ColDesc &d, const ValueCountsTable &t, hipStream_t stream) {
+  hipLaunchKernelGGL(value_counts_utf8_kernel, dim3(grid_for((uint64_t)d.length)), dim3(256), 0, stream, d, t);
+}
+
+void launch_value_counts_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
+                              const Utf8ColDesc &dict, unsigned long long *cells, const ValueCountsTable &t,
+                              hipStream_t stream) {
+  if (dict.length <= (int64_t)kValueCountsDictLdsCells)  // (fewer workgroups: each one flushes its cells once)
+    hipLaunchKernelGGL(value_counts_dict_count_kernel<true>, dim3(std::min(grid_for((uint64_t)length), 1024)), dim3(256),
+                       0, stream, indices, validity, offset, length, dict.length, cells);
+  else
+    hipLaunchKernelGGL(value_counts_dict_count_kernel<false>, dim3(grid_for((uint64_t)length)), dim3(256), 0, stream,
+                       indices, validity, offset, length, dict.length, cells);
+  hipLaunchKernelGGL(value_counts_dict_insert_kernel, dim3(grid_for((uint64_t)dict.length)), dim3(256), 0, stream, dict,
+                     cells, t);
+}
+
+}  // namespace tgx

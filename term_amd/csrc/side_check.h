@@ -1,12 +1,14 @@
 // side_check.h -- the check kinds that run beside the fused pass and share one shape: TGX_CHECK_JOINT_BINS
-// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp), TGX_CHECK_HISTOGRAM (histogram_device.cpp) and
-// TGX_CHECK_VALUE_RULE (valuerule_device.cpp).
+// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp), TGX_CHECK_HISTOGRAM (histogram_device.cpp),
+// TGX_CHECK_VALUE_RULE (valuerule_device.cpp) and TGX_CHECK_VALUE_COUNTS (valuecounts_device.cpp).
 //
 // A task is one spec.  Its running state is a few 64-bit counters on the device, plus a small range accumulator for the
 // kinds that have a range phase; rows seen are counted on the host.  What is merged in from other states or read from a
 // blob is kept on the host (`host`) and added when the state is read (`gather`).  The rest of the library sees a
 // SideCheck per kind in tgx_state::side, in the order of the blob's sections (null: the plan has no task of the kind);
 // SideState<K> is everything the kinds have in common, a kind K adds what its tasks count and how they are launched.
+// A kind whose tasks keep more on the device than counters (VALUE_COUNTS: a table per task, and a host part of variable
+// size) clears and reads that through device_clear_extra / gather_extra; the other kinds leave both alone.
 #pragma once
 #include <memory>
 
@@ -15,12 +17,13 @@
 
 namespace tgx {
 
-enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3 };  // (kNumSide: internal.h)
+enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3, kSideCounts = 4 };  // (kNumSide: internal.h)
 TGX_HIDDEN inline int side_index(int kind) {
   return kind == TGX_CHECK_JOINT_BINS ? kSideJoint
          : kind == TGX_CHECK_TEMPORAL ? kSideTemporal
          : kind == TGX_CHECK_HISTOGRAM ? kSideHist
-                                       : kSideRule;
+         : kind == TGX_CHECK_VALUE_RULE ? kSideRule
+                                        : kSideCounts;
 }
 
 struct TGX_HIDDEN SideCheck {
@@ -40,17 +43,23 @@ tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *
 tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status valuerule_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule)?  Asked by tgx_state_create
+tgx_status valuecounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule, tgx_plan_set_value_counts)?  Asked by
+// tgx_state_create
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
+tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err);
+// may a column of tgx_type `type` feed a VALUE_COUNTS check?  Asked by tgx_update of column `column`
+tgx_status valuecounts_check_type(int column, int type, tgx_error *err);
 TGX_HIDDEN SideCheck *joint_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *temporal_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *hist_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *valuerule_state_new(const tgx_plan *plan);
+TGX_HIDDEN SideCheck *valuecounts_state_new(const tgx_plan *plan);
 // the fresh state of the plan's tasks of kind `index`, or null when it has none
 TGX_HIDDEN inline SideCheck *side_state_new(int index, const tgx_plan *plan) {
   SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new,
-                                                          valuerule_state_new};
+                                                          valuerule_state_new, valuecounts_state_new};
   return make[index](plan);
 }
 
@@ -141,13 +150,17 @@ struct TGX_HIDDEN SideState : SideCheck {
 
   // what a kind uploads once per state
   virtual tgx_status device_init_extra(tgx_state *, tgx_error *) { return TGX_OK; }
+  // device memory of the kind's own: back to empty (queued on the stream) / folded into the gathered hosts (the stream
+  // has been waited for, the counters are already in `out`)
+  virtual tgx_status device_clear_extra(tgx_state *, tgx_error *) { return TGX_OK; }
+  virtual tgx_status gather_extra(tgx_state *, std::vector<Host> *, tgx_error *) { return TGX_OK; }
 
   tgx_status device_clear(tgx_state *st, tgx_error *err) {
     if (!identity.empty())
       HIP_TRY(hipMemcpyAsync(d_range.p, identity.data(), identity.size() * sizeof(Range), hipMemcpyHostToDevice,
                              st->stream));
     if (n_words) HIP_TRY(hipMemsetAsync(d_counts.p, 0, n_words * sizeof(unsigned long long), st->stream));
-    return TGX_OK;
+    return device_clear_extra(st, err);
   }
 
   tgx_status device_init(tgx_state *st, tgx_error *err) {
@@ -180,7 +193,7 @@ struct TGX_HIDDEN SideState : SideCheck {
     for (size_t k = 0; k < tasks.size(); k++)
       K::merge_host((*out)[k], K::from_device(tasks[k], device_rows[k], K::kRanged ? ranges[k] : Range(),
                                               words.data() + word_off[k]));
-    return TGX_OK;
+    return gather_extra(st, out, err);
   }
 
   tgx_status reset(tgx_state *st, tgx_error *err) override {

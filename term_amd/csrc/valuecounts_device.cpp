@@ -1,0 +1,500 @@
+// valuecounts_device.cpp -- TGX_CHECK_VALUE_COUNTS: how often each value of one column occurs, for a bounded number of
+// distinct values (the GROUP BY behind the reference's HistogramConstraint, TG/constraints/histogram.rs:205-391, and
+// EntropyAnalyzer, TG/analyzers/advanced/entropy.rs:192-335; include/tgx.h has the exact semantics).
+//
+// A task is one spec.  Its running state on the device is four 64-bit counters (non-NULL rows, rows holding the value
+// whose bits are the free-slot marker, overflow rows, long rows) and one open-addressing table filled by
+// kernels/valuecounts.hip: integer keys with their counts, or string keys (two fingerprint words) with their counts,
+// lengths and bytes.  The table is allocated at the task's first batch, when the column's kind is known.  The host part
+// is a map from value (int64, or bytes) to count plus the same counters: what was merged in or read from a blob, and
+// what the device part is folded into whenever the state is read (gather_extra) -- so merges, blobs and the cross-rank
+// step unite by VALUE, never by fingerprint.  Rows seen are counted on the host.
+#include <map>
+#include <string>
+
+#include "api_internal.h"
+
+namespace tgx {
+void launch_value_counts_i64(const ComomentColDesc &d, const ValueCountsTable &t, int blocks, hipStream_t stream);
+void launch_value_counts_utf8(const Utf8ColDesc &d, const ValueCountsTable &t, hipStream_t stream);
+void launch_value_counts_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
+                              const Utf8ColDesc &dict, unsigned long long *cells, const ValueCountsTable &t,
+                              hipStream_t stream);
+
+namespace {
+
+enum { kNoValues = 0, kIntValues = 1, kByteValues = 2 };
+
+// one task's state as the host sees it
+struct CountsHost {
+  int kind = kNoValues;
+  uint64_t seen = 0, non_null = 0, overflow_rows = 0, long_rows = 0;
+  std::map<int64_t, uint64_t> ints;      // ascending int64
+  std::map<std::string, uint64_t> strs;  // ascending bytewise (std::string compares as unsigned bytes)
+  uint64_t distinct() const { return ints.size() + strs.size(); }
+  uint64_t counted() const {
+    uint64_t n = 0;
+    for (const auto &e : ints) n += e.second;
+    for (const auto &e : strs) n += e.second;
+    return n;
+  }
+};
+
+// the kernels' view of a string column (a dictionary's values included); `buffers`: the device copy of a Utf8View's
+// table of data-buffer pointers
+Utf8ColDesc string_desc(const tgx_column &c, const uint8_t *const *buffers, const FpKey &key) {
+  Utf8ColDesc d;
+  memset(&d, 0, sizeof(d));
+  const bool view = c.type == TGX_UTF8_VIEW;
+  d.offsets = c.offsets;
+  d.data = c.data;
+  d.validity = c.validity;
+  d.offset = c.offset;
+  d.length = c.length;
+  d.large_offsets = c.type == TGX_LARGE_UTF8;
+  d.views = view ? c.values : nullptr;
+  d.buffers = view ? buffers : nullptr;
+  d.key = key;
+  return d;
+}
+
+struct NoRange {};
+
+struct CountsKind {
+  typedef ValueCountsTask Task;
+  typedef CountsHost Host;
+  typedef NoRange Range;
+  static constexpr bool kRanged = false;
+  static constexpr int kIndex = kSideCounts;
+  static constexpr const char *kName = "VALUE_COUNTS", *kDiffers = "column types";
+  static constexpr uint32_t kMagic = 0x544e4356;  // "VCNT"
+
+  static const std::vector<ValueCountsTask> &tasks(const tgx_plan *plan) { return plan->value_counts; }
+  static size_t words(const ValueCountsTask &) { return kValueCountsWords; }
+  static NoRange range_identity() { return NoRange(); }
+  static CountsHost fresh(const ValueCountsTask &) { return CountsHost(); }
+  static size_t shape(const CountsHost &) { return 0; }  // (integer against string values: CountsCheck::merge_from)
+  // the counters; the table's entries follow in gather_extra
+  static CountsHost from_device(const ValueCountsTask &, int64_t rows, const NoRange &, const unsigned long long *w) {
+    CountsHost d;
+    d.seen = (uint64_t)rows;
+    d.non_null = w[kVcNonNull];
+    d.overflow_rows = w[kVcOverflow];
+    d.long_rows = w[kVcLong];
+    if (w[kVcMarker]) {
+      d.kind = kIntValues;
+      d.ints[(int64_t)kEmptyKey] = w[kVcMarker];
+    }
+    return d;
+  }
+  static void merge_host(CountsHost &a, const CountsHost &b) {
+    if (a.kind == kNoValues) a.kind = b.kind;
+    a.seen += b.seen;
+    a.non_null += b.non_null;
+    a.overflow_rows += b.overflow_rows;
+    a.long_rows += b.long_rows;
+    for (const auto &e : b.ints) a.ints[e.first] += e.second;
+    for (const auto &e : b.strs) a.strs[e.first] += e.second;
+  }
+
+  // per task { u32 max_distinct, max_value_bytes (the plan's parameters), u32 kind (0 no values, 1 int64, 2 bytes), u32 0,
+  //   u64 seen, non_null, overflow_rows, long_rows, u64 n_entries,
+  //   n_entries x { i64 value, u64 count }  or  { u32 length, u8 bytes[length], u64 count }, ascending by value }
+  static void write(const ValueCountsTask &t, const CountsHost &h, Writer &w) {
+    w.pod(t.params);
+    w.pod((uint32_t)h.kind);
+    w.pod((uint32_t)0);
+    const uint64_t counts[5] = {h.seen, h.non_null, h.overflow_rows, h.long_rows, h.distinct()};
+    w.pod(counts);
+    for (const auto &e : h.ints) {
+      w.pod(e.first);
+      w.pod(e.second);
+    }
+    for (const auto &e : h.strs) {
+      w.pod((uint32_t)e.first.size());
+      w.put(e.first.data(), e.first.size());
+      w.pod(e.second);
+    }
+  }
+
+  static tgx_status read(const ValueCountsTask &t, CountsHost &h, Reader &r, size_t k, tgx_error *err) {
+    tgx_value_counts_params p;
+    r.get(&p, sizeof(p));
+    const uint32_t kind = r.pod<uint32_t>(), pad = r.pod<uint32_t>();
+    uint64_t counts[5];
+    r.get(counts, sizeof(counts));
+    if (!r.ok) return TGX_OK;
+    if (p.max_distinct != t.params.max_distinct || p.max_value_bytes != t.params.max_value_bytes)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "VALUE_COUNTS task %zu: the blob was counted under other parameters (max_distinct %u, max_value_bytes "
+                  "%u) than the plan's (%u, %u)",
+                  k, p.max_distinct, p.max_value_bytes, t.params.max_distinct, t.params.max_value_bytes);
+    const uint64_t n = counts[4];
+    if (kind > kByteValues || pad != 0 || (kind == kNoValues && n != 0))
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: kind)", k);
+    size_t least = 0;  // (held against the bytes that are left before anything is allocated)
+    if (!r.fits(n, kind == kIntValues ? 16 : 12, &least)) return TGX_OK;
+    uint64_t counted = 0;
+    for (uint64_t i = 0; i < n; i++) {
+      uint64_t c = 0;
+      bool ascending = true;
+      if (kind == kIntValues) {
+        const int64_t v = r.pod<int64_t>();
+        c = r.pod<uint64_t>();
+        if (!r.ok) return TGX_OK;
+        ascending = h.ints.empty() || h.ints.rbegin()->first < v;
+        if (ascending) h.ints.emplace_hint(h.ints.end(), v, c);
+      } else {
+        const uint32_t len = r.pod<uint32_t>();
+        if (!r.ok) return TGX_OK;
+        if (len > t.params.max_value_bytes)
+          return fail(err, TGX_INVALID_ARGUMENT,
+                      "malformed state blob (VALUE_COUNTS task %zu: a value of %u bytes, max_value_bytes is %u)", k, len,
+                      t.params.max_value_bytes);
+        std::string v(len, '\0');
+        r.get(&v[0], len);
+        c = r.pod<uint64_t>();
+        if (!r.ok) return TGX_OK;
+        ascending = h.strs.empty() || h.strs.rbegin()->first < v;
+        if (ascending) h.strs.emplace_hint(h.strs.end(), std::move(v), c);
+      }
+      if (!ascending)
+        return fail(err, TGX_INVALID_ARGUMENT,
+                    "malformed state blob (VALUE_COUNTS task %zu: entry %llu is out of order or repeated)", k,
+                    (unsigned long long)i);
+      if (c == 0)
+        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: entry %llu has a zero count)",
+                    k, (unsigned long long)i);
+      if (c > UINT64_MAX - counted)
+        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: counts)", k);
+      counted += c;
+    }
+    // counted + overflow_rows + long_rows == non_null <= seen (no sum can wrap: each term is held against non_null)
+    const uint64_t non_null = counts[1];
+    if (non_null > counts[0] || counted > non_null || counts[2] > non_null - counted ||
+        counts[3] != non_null - counted - counts[2])
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "malformed state blob (VALUE_COUNTS task %zu: counted + overflow_rows + long_rows != non_null)", k);
+    h.kind = (int)kind;
+    h.seen = counts[0];
+    h.non_null = non_null;
+    h.overflow_rows = counts[2];
+    h.long_rows = counts[3];
+    return TGX_OK;
+  }
+};
+
+uint64_t table_slots(uint32_t max_distinct) {
+  uint64_t s = 2;
+  while (s < 2 * (uint64_t)max_distinct) s <<= 1;
+  return s;
+}
+
+struct CountsCheck final : SideState<CountsKind> {
+  // the device part of a task: its table (allocated at the first batch, for the kind of value the column holds) and the
+  // per-entry cells of the dictionary route
+  struct Dev {
+    int kind = kNoValues;
+    uint64_t slots = 0;
+    uint32_t max_value_bytes = 0;
+    DevBuf table, cells;
+    size_t key_bytes() const { return (size_t)slots * 8 * (kind == kByteValues ? 2 : 1); }
+    size_t counts_at() const { return key_bytes(); }
+    size_t lens_at() const { return counts_at() + (size_t)slots * 8; }
+    size_t store_at() const { return lens_at() + (size_t)slots * 4; }
+    size_t bytes() const { return kind == kByteValues ? store_at() + (size_t)slots * max_value_bytes : lens_at(); }
+  };
+  std::vector<Dev> dev_part;
+  // what the tables held when they were last read back: a read of the state costs the copy once, until the next batch
+  // or reset (tgx_value_counts_get, the two calls of tgx_value_counts_entries and tgx_finalize all gather)
+  std::vector<CountsHost> table_cache;
+  bool table_cache_ok = false;
+
+  explicit CountsCheck(const tgx_plan *plan) : SideState(plan), dev_part(plan->value_counts.size()) {}
+
+  ValueCountsTable view(const tgx_state *st, size_t k) const {
+    const Dev &d = dev_part[k];
+    uint8_t *base = d.table.as<uint8_t>();
+    ValueCountsTable t;
+    memset(&t, 0, sizeof(t));
+    t.keys = (unsigned long long *)base;
+    t.keys2 = d.kind == kByteValues ? t.keys + d.slots : nullptr;
+    t.counts = (unsigned long long *)(base + d.counts_at());
+    t.lens = d.kind == kByteValues ? (uint32_t *)(base + d.lens_at()) : nullptr;
+    t.store = d.kind == kByteValues ? base + d.store_at() : nullptr;
+    t.words = d_counts.as<unsigned long long>() + word_off[k];
+    t.mask = d.slots - 1;
+    t.salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
+    t.max_value_bytes = d.max_value_bytes;
+    return t;
+  }
+
+  tgx_status clear_table(tgx_state *st, size_t k, tgx_error *err) {
+    const Dev &d = dev_part[k];
+    if (d.kind == kNoValues) return TGX_OK;
+    uint8_t *base = d.table.as<uint8_t>();
+    HIP_TRY(hipMemsetAsync(base, 0xFF, d.key_bytes(), st->stream));  // (every key word: kEmptyKey)
+    HIP_TRY(hipMemsetAsync(base + d.counts_at(), 0, (size_t)d.slots * 8, st->stream));
+    return TGX_OK;
+  }
+
+  tgx_status device_clear_extra(tgx_state *st, tgx_error *err) override {
+    table_cache_ok = false;
+    for (size_t k = 0; k < dev_part.size(); k++) TGX_TRY(clear_table(st, k, err));
+    return TGX_OK;
+  }
+
+  tgx_status ensure_table(tgx_state *st, size_t k, int kind, tgx_error *err) {
+    Dev &d = dev_part[k];
+    if (d.kind == kind) return TGX_OK;
+    if (d.kind != kNoValues && device_rows[k] > 0)
+      return fail(err, TGX_INVALID_ARGUMENT, "VALUE_COUNTS task %zu: the column changed between integer and string values",
+                  k);
+    const tgx_value_counts_params &p = st->plan->value_counts[k].params;
+    d.kind = kind;
+    d.slots = table_slots(p.max_distinct);
+    d.max_value_bytes = p.max_value_bytes;
+    HIP_TRY(d.table.reserve(d.bytes()));
+    return clear_table(st, k, err);
+  }
+
+  tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
+    const tgx_plan *plan = st->plan;
+    if (nrows <= 0) return TGX_OK;
+    TGX_TRY(device_init(st, err));
+    table_cache_ok = false;
+    for (size_t k = 0; k < plan->value_counts.size(); k++) {
+      const tgx_column &x = dev[plan->value_counts[k].column];
+      const bool strings = is_any_string(x.type), dict = x.type == TGX_DICT32_UTF8;
+      // (an Int64 view: update_validate refuses what is neither a string layout nor widened to one)
+      if (x.type != TGX_INT64 && !strings && !dict)
+        return fail(err, TGX_UNSUPPORTED, "VALUE_COUNTS takes integer and string columns (%d)", x.type);
+      TGX_TRY(ensure_table(st, k, x.type == TGX_INT64 ? kIntValues : kByteValues, err));
+      const ValueCountsTable t = view(st, k);
+      if (x.type == TGX_INT64) {
+        ComomentColDesc d;
+        memset(&d, 0, sizeof(d));
+        const uint64_t bytes = side_fill_x(d, x);
+        // 16 waves a workgroup and 96 KiB of LDS: one workgroup a CU
+        const int blocks = side_blocks(nrows, kValueCountsBlock, g_ctx.n_cu, 1, 1);
+        TGX_TRY(side_rows_fit("VALUE_COUNTS", nrows, blocks, err));
+        ProfScope ps(st, "value_counts", bytes);
+        launch_value_counts_i64(d, t, blocks, st->stream);
+      } else if (strings) {
+        // (per-lane and LDS counters are 32-bit here too: the launchers take up to 2048 workgroups, 1024 for the
+        //  dictionary's indices, so a batch would need 2^42 rows to wrap one; refused all the same)
+        TGX_TRY(side_rows_fit("VALUE_COUNTS", nrows, 1024, err));
+        ProfScope ps(st, "value_counts", 0);
+        launch_value_counts_utf8(string_desc(x, x.variadic, plan->fp_key), t, st->stream);
+      } else {
+        const tgx_column *dc = x.dictionary;
+        if (!dc || !is_string(dc->type)) return fail(err, TGX_INVALID_ARGUMENT, "VALUE_COUNTS: malformed dictionary");
+        TGX_TRY(side_rows_fit("VALUE_COUNTS", nrows, 1024, err));
+        if (dc->length > 0) {  // (without entries every row is a row without a value)
+          Dev &d = dev_part[k];
+          HIP_TRY(d.cells.reserve_roomy((size_t)dc->length * 8));
+          HIP_TRY(hipMemsetAsync(d.cells.p, 0, (size_t)dc->length * 8, st->stream));
+          ProfScope ps(st, "value_counts", (uint64_t)x.length * 4);
+          launch_value_counts_dict((const int32_t *)x.values, x.validity, x.offset, x.length,
+                                   string_desc(*dc, nullptr, plan->fp_key), d.cells.as<unsigned long long>(), t,
+                                   st->stream);
+        }
+      }
+      HIP_TRY(hipGetLastError());
+      device_rows[k] += nrows;
+    }
+    return TGX_OK;
+  }
+
+  // the tables' entries into the gathered hosts (the counters are already there)
+  tgx_status gather_extra(tgx_state *st, std::vector<CountsHost> *out, tgx_error *err) override {
+    std::vector<uint8_t> h;
+    if (!table_cache_ok) table_cache.assign(dev_part.size(), CountsHost());
+    for (size_t k = 0; k < dev_part.size() && !table_cache_ok; k++) {
+      const Dev &d = dev_part[k];
+      if (d.kind == kNoValues || device_rows[k] == 0) continue;
+      h.resize(d.bytes());
+      HIP_TRY(hipMemcpyAsync(h.data(), d.table.p, h.size(), hipMemcpyDeviceToHost, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));
+      const uint64_t *keys = (const uint64_t *)h.data();
+      const uint64_t *counts = (const uint64_t *)(h.data() + d.counts_at());
+      CountsHost &o = table_cache[k];
+      for (uint64_t s = 0; s < d.slots; s++) {
+        if (keys[s] == kEmptyKey || counts[s] == 0) continue;
+        if (o.kind == kNoValues) o.kind = d.kind;
+        if (d.kind == kIntValues) {
+          o.ints[(int64_t)keys[s]] += counts[s];
+        } else {
+          const uint32_t len = std::min(((const uint32_t *)(h.data() + d.lens_at()))[s], d.max_value_bytes);
+          o.strs[std::string((const char *)h.data() + d.store_at() + (size_t)s * d.max_value_bytes, len)] += counts[s];
+        }
+      }
+    }
+    table_cache_ok = true;
+    for (size_t k = 0; k < dev_part.size(); k++) {  // (only the entries: the counters came with the words)
+      CountsHost &o = (*out)[k];
+      if (o.kind == kNoValues) o.kind = table_cache[k].kind;
+      for (const auto &e : table_cache[k].ints) o.ints[e.first] += e.second;
+      for (const auto &e : table_cache[k].strs) o.strs[e.first] += e.second;
+    }
+    return TGX_OK;
+  }
+
+  // (integer values and string values do not unite: SideState's merge knows one shape per kind)
+  tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) override {
+    std::vector<CountsHost> theirs, mine;
+    TGX_TRY(of(src)->gather(src, &theirs, err));
+    TGX_TRY(gather(st, &mine, err));
+    for (size_t k = 0; k < theirs.size(); k++)
+      if (theirs[k].kind != kNoValues && mine[k].kind != kNoValues && theirs[k].kind != mine[k].kind)
+        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", CountsKind::kName,
+                    k, CountsKind::kDiffers);
+    for (size_t k = 0; k < theirs.size(); k++) CountsKind::merge_host(host[k], theirs[k]);
+    return TGX_OK;
+  }
+
+  // one task, read; a state that was fed integers under one column type and strings under another holds both
+  tgx_status read_task(tgx_state *st, size_t slot, CountsHost *out, tgx_error *err) {
+    std::vector<CountsHost> g;
+    TGX_TRY(gather(st, &g, err));
+    if (!g[slot].ints.empty() && !g[slot].strs.empty())
+      return fail(err, TGX_INVALID_ARGUMENT, "VALUE_COUNTS task %zu holds integer and string values", slot);
+    *out = std::move(g[slot]);
+    return TGX_OK;
+  }
+
+  tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) override {
+    CountsHost h;
+    TGX_TRY(read_task(st, (size_t)slot, &h, err));
+    r->total = (int64_t)h.seen;
+    r->non_null = (int64_t)h.non_null;
+    r->distinct = (int64_t)h.distinct();
+    r->matches = (int64_t)h.counted();
+    return TGX_OK;
+  }
+};
+
+const char *type_name(int type) {
+  switch (type) {
+    case TGX_FLOAT64: return "Float64";
+    case TGX_FLOAT32: return "Float32";
+    case TGX_UINT64: return "UInt64";
+    case TGX_BOOL: return "Boolean";
+    default: return "this type";
+  }
+}
+
+}  // namespace
+
+tgx_status valuecounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err) {
+  const tgx_check_spec &sp = plan->specs[spec_index];
+  if (sp.column2 != -1)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %d: VALUE_COUNTS reads one column: column2 must be -1 (%d)", spec_index,
+                sp.column2);
+  ValueCountsTask t;
+  memset(&t, 0, sizeof(t));
+  t.column = sp.column;
+  t.spec_index = spec_index;
+  plan->value_counts.push_back(t);
+  *slot = (int)plan->value_counts.size() - 1;
+  return TGX_OK;
+}
+
+tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err) {
+  for (const ValueCountsTask &t : plan->value_counts)
+    if (!t.set)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "spec %d: a VALUE_COUNTS check needs its parameters (tgx_plan_set_value_counts)", t.spec_index);
+  return TGX_OK;
+}
+
+tgx_status valuecounts_check_type(int column, int type, tgx_error *err) {
+  if (type == TGX_FLOAT64 || type == TGX_FLOAT32 || type == TGX_UINT64 || type == TGX_BOOL)
+    return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_COUNTS takes integer and string columns, not %s (type %d)", column,
+                type_name(type), type);
+  return TGX_OK;
+}
+
+SideCheck *valuecounts_state_new(const tgx_plan *plan) {
+  return plan->value_counts.empty() ? nullptr : new CountsCheck(plan);
+}
+
+}  // namespace tgx
+
+using namespace tgx;
+
+extern "C" tgx_status tgx_plan_set_value_counts(tgx_plan *plan, size_t spec_index, const tgx_value_counts_params *p,
+                                                tgx_error *err) try {
+  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_VALUE_COUNTS, "VALUE_COUNTS", &slot, err, nullptr));
+  if (plan_has_state(plan))
+    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a VALUE_COUNTS check are fixed once a state of the plan exists");
+  if (p->max_distinct < 1 || p->max_distinct > TGX_VALUE_COUNTS_MAX_DISTINCT)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_distinct must be 1 .. %d (%u)", spec_index,
+                (int)TGX_VALUE_COUNTS_MAX_DISTINCT, p->max_distinct);
+  if (p->max_value_bytes < 1 || p->max_value_bytes > TGX_VALUE_COUNTS_MAX_VALUE_BYTES)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
+                (int)TGX_VALUE_COUNTS_MAX_VALUE_BYTES, p->max_value_bytes);
+  ValueCountsTask &t = plan->value_counts[slot];
+  t.params = *p;
+  t.set = true;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_value_counts_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                           tgx_value_counts_summary *out, tgx_error *err) try {
+  bind_thread();
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_VALUE_COUNTS, "VALUE_COUNTS", &slot, err, "bad arguments"));
+  CountsHost h;
+  TGX_TRY(static_cast<CountsCheck *>(CountsCheck::of(st))->read_task(st, slot, &h, err));
+  out->seen = h.seen;
+  out->non_null = h.non_null;
+  out->distinct = h.distinct();
+  out->counted = h.counted();
+  out->overflow_rows = h.overflow_rows;
+  out->long_rows = h.long_rows;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_value_counts_entries(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                               tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries,
+                                               uint8_t *bytes, uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes,
+                                               tgx_error *err) try {
+  bind_thread();
+  if (!n_entries || !n_bytes || !is_bytes) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_VALUE_COUNTS, "VALUE_COUNTS", &slot, err, "bad arguments"));
+  CountsHost h;
+  TGX_TRY(static_cast<CountsCheck *>(CountsCheck::of(st))->read_task(st, slot, &h, err));
+  uint64_t need_bytes = 0;
+  for (const auto &e : h.strs) need_bytes += e.first.size();
+  *n_entries = h.distinct();
+  *n_bytes = need_bytes;
+  *is_bytes = h.kind == kByteValues ? 1 : 0;
+  if (entries && cap < *n_entries)
+    return fail(err, TGX_INVALID_ARGUMENT, "entries holds %llu entries, %llu are needed", (unsigned long long)cap,
+                (unsigned long long)*n_entries);
+  if (bytes && bytes_cap < need_bytes)
+    return fail(err, TGX_INVALID_ARGUMENT, "bytes holds %llu bytes, %llu are needed", (unsigned long long)bytes_cap,
+                (unsigned long long)need_bytes);
+  if (!entries) return TGX_OK;
+  if (need_bytes && !bytes) return fail(err, TGX_INVALID_ARGUMENT, "string values need a byte buffer");
+  size_t i = 0;
+  uint64_t at = 0;
+  for (const auto &e : h.ints) entries[i++] = tgx_value_count_entry{e.first, 0, 0, e.second};
+  for (const auto &e : h.strs) {
+    if (!e.first.empty()) memcpy(bytes + at, e.first.data(), e.first.size());
+    entries[i++] = tgx_value_count_entry{0, at, (uint64_t)e.first.size(), e.second};
+    at += e.first.size();
+  }
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}

@@ -272,6 +272,14 @@ class CheckBuilder:
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
 
+    def has_histogram(self, column, measures, max_distinct=10000):
+        """Check::has_histogram: HistogramConstraint.new(column, measures) -- `measures` is what stands for the
+        reference's assertion function here: a list of HistogramMeasure entries that must all hold"""
+        return self.constraint(HistogramConstraint(column, measures, max_distinct=max_distinct))
+
+    def has_histogram_with_description(self, column, measures, description, max_distinct=10000):
+        return self.constraint(HistogramConstraint(column, measures, description, max_distinct))
+
     def constraint(self, c):
         """core/check.rs:263: a constraint object (MultiStatisticalConstraint, QuantileConstraint,
         CorrelationConstraint below) instead of a builder shorthand"""
@@ -518,6 +526,44 @@ class DataTypeConstraint:
         return DataTypeConstraint(column, DataTypeValidation.SpecificType(data_type))
 
 
+class HistogramMeasure:
+    """One named measure of a column's value histogram held to an Assertion (constraints/histogram.rs:37-127): the form a
+    histogram assertion takes where no function can travel (JSON, Python)"""
+
+    @staticmethod
+    def _of(measure, assertion, **extra):
+        return dict(extra, measure=measure, assertion=assertion.to_json())
+
+    @staticmethod
+    def most_common_ratio(assertion): return HistogramMeasure._of("most_common_ratio", assertion)
+    @staticmethod
+    def least_common_ratio(assertion): return HistogramMeasure._of("least_common_ratio", assertion)
+    @staticmethod
+    def bucket_count(assertion): return HistogramMeasure._of("bucket_count", assertion)
+    @staticmethod
+    def entropy(assertion): return HistogramMeasure._of("entropy", assertion)
+    @staticmethod
+    def null_ratio(assertion): return HistogramMeasure._of("null_ratio", assertion)
+    @staticmethod
+    def top_n_ratio(n, assertion): return HistogramMeasure._of("top_n_ratio", assertion, n=int(n))
+    @staticmethod
+    def value_ratio(value, assertion): return HistogramMeasure._of("value_ratio", assertion, value=value)
+
+
+class HistogramConstraint:
+    """constraints/histogram.rs:154-410 over TGX_CHECK_VALUE_COUNTS: the column's value -> count map is counted on the
+    device for at most `max_distinct` values (a column beyond that, or with strings above 256 bytes, is the constraint's
+    error, with the numbers).  Buckets are ordered by count descending, then by the value's text; ratio = count / (total
+    - nulls); the metric is the histogram's entropy in nats; no non-NULL row is Skipped ("No data to analyze").  Every
+    measure must hold.  Value text is the string itself or the decimal text of an integer: a date, time, timestamp,
+    duration, float, decimal, boolean or binary column is the constraint's error ("... not on the GPU path")"""
+
+    def __init__(self, column, measures, description=None, max_distinct=10000):
+        self.spec = {"type": "histogram", "column": column, "measures": list(measures), "max_distinct": int(max_distinct)}
+        if description is not None:
+            self.spec["description"] = description
+
+
 class Check:
     def __init__(self, spec):
         self.spec = spec
@@ -683,6 +729,9 @@ def _arrow_type_names(table):
             out[f.name] = "Timestamp(%s, %s)" % (unit, "None" if t.tz is None else 'Some("%s")' % t.tz)
         elif pa.types.is_time(t) or pa.types.is_duration(t) or pa.types.is_decimal(t):
             out[f.name] = str(t)
+        elif pa.types.is_binary(t) or pa.types.is_large_binary(t) or pa.types.is_fixed_size_binary(t) or \
+                (hasattr(pa.types, "is_binary_view") and pa.types.is_binary_view(t)):
+            out[f.name] = "Binary"
     return out
 
 
@@ -810,10 +859,11 @@ class _Analyzer:
         self.spec = spec
 
     def name(self):
-        return self.spec["type"]
+        t = self.spec["type"]
+        return "entropy" if t == "value_entropy" else t  # (the tag "entropy" was taken: see EntropyAnalyzer)
 
     def metric_key(self):
-        t = self.spec["type"]
+        t = self.name()
         if t in ("size", "standard_deviation", "histogram"):  # (these analyzers do not override metric_key)
             return t
         if t == "correlation":
@@ -879,6 +929,19 @@ def HistogramAnalyzer(column, num_buckets=10, strict_reference_types=True):
     return _Analyzer(spec)
 
 
+def EntropyAnalyzer(column, max_unique_values=10000, arrow_type=None):
+    """TG/analyzers/advanced/entropy.rs over TGX_CHECK_VALUE_COUNTS: entropy (bits), normalized entropy, Gini impurity,
+    effective and unique values, the ten most frequent values; the state is {value_counts, total_count, truncated}.
+    name() is "entropy"; the JSON tag is "value_entropy" ("entropy" is what the tests of unknown analyzer types use).
+    A column with more than max(max_unique_values, 10) values is the analyzer's error, with the numbers: the reference's
+    truncated top-N sampling is not reproduced.  `arrow_type`: the column's Arrow DataType where the table is not a
+    pyarrow one (a date, time, float, decimal, boolean or binary column is the analyzer's error)"""
+    spec = {"type": "value_entropy", "column": column, "max_unique_values": max(int(max_unique_values), 10)}
+    if arrow_type:
+        spec["arrow_type"] = arrow_type
+    return _Analyzer(spec)
+
+
 class AnalyzerContext:
     """TG/analyzers/context.rs: metrics by key, errors; plus the analyzers' states (for merges across shards)"""
 
@@ -919,8 +982,11 @@ class AnalysisRunner:
         return len(self._analyzers)
 
     def run(self, table):
-        spec = {"table_name": self._table, "continue_on_error": self._continue,
-                "analyzers": [a.spec for a in self._analyzers]}
+        declared = _arrow_type_names(table)  # (analyzers that read a column's values as text need its Arrow type)
+        specs = [dict(a.spec, arrow_type=declared[a.spec["column"]])
+                 if a.spec["type"] == "value_entropy" and "arrow_type" not in a.spec and a.spec["column"] in declared
+                 else a.spec for a in self._analyzers]
+        spec = {"table_name": self._table, "continue_on_error": self._continue, "analyzers": specs}
         name_arr, n_cols, col_arr, n_batches, _keep = _flatten_table(table)
         out = C.c_char_p()
         err = _Error()

@@ -45,6 +45,15 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                     u64 seen, considered, valid, cast_errors }              bounds are zeros outside the between mode)
                                considered = the non-NULL rows, valid = those of them that pass, cast_errors = those of
                                them CAST(col AS INT) fails on: valid + cast_errors <= considered <= seen.
+    and ONLY for plans with VALUE_COUNTS checks, behind the VALUE_RULE section if there is one:
+    u32 magic 'VCNT', u32 n_tasks
+    n_tasks     x { u32 max_distinct, max_value_bytes            (the plan's parameters)
+                    u32 kind (0 no values, 1 int64, 2 bytes), u32 0
+                    u64 seen, non_null, overflow_rows, long_rows, n_entries
+                    n_entries x { i64 value; u64 count }                      kind 1, ascending int64
+                             or { u32 length; u8 bytes[length]; u64 count } } kind 2, ascending bytewise
+                               every count > 0, every length <= max_value_bytes, no value twice, and
+                               sum(counts) + overflow_rows + long_rows == non_null <= seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -56,6 +65,7 @@ JOINT_MAGIC = 0x42544E4A  # 'JNTB'
 TEMPORAL_MAGIC = 0x52504D54  # 'TMPR'
 HIST_MAGIC = 0x54534948  # 'HIST'
 VALUE_RULE_MAGIC = 0x4C525656  # 'VVRL'
+VALUE_COUNTS_MAGIC = 0x544E4356  # 'VCNT'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -165,8 +175,27 @@ def value_rule_state(mode, flags, seen, considered, valid, cast_errors=0, lo_i=0
     return struct.pack("<iI2q2d4Q", mode, flags, lo_i, hi_i, lo_f, hi_f, seen, considered, valid, cast_errors)
 
 
+def value_counts_state(max_distinct, max_value_bytes, seen, counts, nulls=0, overflow_rows=0, long_rows=0,
+                       ordered=True):
+    """a VALUE_COUNTS task: the plan's parameters, the counters and the entries of `counts` (value -> count; every key an
+    int, or every key bytes).  non_null is what the invariant makes it: sum(counts) + overflow_rows + long_rows, and
+    seen - nulls must equal it.  `ordered=False` keeps the entries in the order given (for a blob that is to be refused)."""
+    items = list(counts.items()) if hasattr(counts, "items") else list(counts)
+    is_bytes = bool(items) and isinstance(items[0][0], (bytes, bytearray))
+    if ordered:
+        items.sort(key=lambda kv: kv[0])
+    non_null = sum(c for _, c in items) + overflow_rows + long_rows
+    if seen - nulls != non_null:
+        raise ValueError("seen - nulls must be sum(counts) + overflow_rows + long_rows")
+    out = struct.pack("<4I5Q", max_distinct, max_value_bytes, (2 if is_bytes else 1) if items else 0, 0, seen, non_null,
+                      overflow_rows, long_rows, len(items))
+    for v, c in items:
+        out += (struct.pack("<I", len(v)) + bytes(v) + struct.pack("<Q", c)) if is_bytes else struct.pack("<qQ", v, c)
+    return out
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=()):
+         value_rules=(), value_counts=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -177,5 +206,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", HIST_MAGIC, len(hist)) + b"".join(hist)
     if value_rules:
         tail += struct.pack("<II", VALUE_RULE_MAGIC, len(value_rules)) + b"".join(value_rules)
+    if value_counts:
+        tail += struct.pack("<II", VALUE_COUNTS_MAGIC, len(value_counts)) + b"".join(value_counts)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
