@@ -283,7 +283,41 @@ typedef enum tgx_check_kind {
    * that cross a state boundary (TGX_CHECK_DISTINCT without TGX_FLAG_EXACT_KEYS) -- and every entry keeps its bytes;
    * across states, blobs and ranks entries are united by their bytes.  Integer and dictionary-index counts are exact by
    * construction.  tgx_merge, state blobs and tgx_allreduce unite by value and add the counters. */
-  TGX_CHECK_VALUE_COUNTS = 15
+  TGX_CHECK_VALUE_COUNTS = 15,
+  /* How often each PAIR of cells of two columns occurs: the GROUP BY behind MutualInformationAnalyzer's three
+   * categorical branches (string x string, numeric x string, string x numeric)
+   *                          TG/analyzers/advanced/mutual_information.rs:249-293
+   *   SELECT cell(x), cell(y), COUNT(*) FROM t WHERE x IS NOT NULL AND y IS NOT NULL GROUP BY 1, 2
+   * for a BOUNDED number of distinct pairs: `column` is x, `column2` is y, the bounds and what a cell is on either side
+   * come with tgx_plan_set_pair_counts (below); a spec without them makes tgx_state_create fail.  A side is
+   *   TGX_PAIR_SIDE_VALUE   a string column (Utf8, LargeUtf8, Utf8View, Dictionary<Int32, Utf8>): the cell is the string's
+   *                         bytes, the empty string is a value; a row whose dictionary entry is NULL, or whose index lies
+   *                         outside the dictionary, is a NULL row (the rules of TGX_CHECK_VALUE_COUNTS);
+   *   TGX_PAIR_SIDE_BINNED  a numeric column (the types JOINT_BINS takes): the cell is the integer
+   *                         FLOOR((CAST(v AS DOUBLE) - origin) / width) in IEEE double arithmetic as written (the one
+   *                         index function of JOINT_BINS); a row holding a NaN or an infinity is counted in non_finite, a
+   *                         row whose index falls outside [0, bins] in out_of_range;
+   *   TGX_PAIR_SIDE_RANGE   a numeric column, and the spec is in its RANGE phase: nothing is counted into a table; the
+   *                         state is n, MIN, MAX (as doubles) and non_finite of that side over the rows where BOTH sides
+   *                         are non-NULL (rows with a NaN or an infinity left out, as JOINT_BINS does); read with
+   *                         tgx_pair_range_get.
+   * Two numeric sides are refused by tgx_plan_set_pair_counts: that is TGX_CHECK_JOINT_BINS.  A side whose mode does
+   * not fit its column, and a UInt64, Boolean, binary, decimal or validity-only column on either side, are
+   * TGX_UNSUPPORTED from tgx_update, and the state stays usable afterwards.
+   * Read with tgx_pair_counts_get and tgx_pair_counts_entries; tgx_result carries total = rows seen, non_null = rows
+   * with both sides non-NULL, distinct = pairs held, matches = rows counted in them.
+   * The counts are exact.  Everything beyond the bounds is reported, never approximated: a row with both sides non-NULL
+   * is in exactly one of an entry, overflow_rows (its pair found no slot in the table), long_rows (a string on either
+   * side longer than max_value_bytes), non_finite and out_of_range, so
+   *   counted + overflow_rows + long_rows + non_finite + out_of_range == both_non_null
+   * always holds.
+   * The grouping guarantee is the one of TGX_CHECK_VALUE_COUNTS: within one state pairs are grouped by a 128-bit keyed
+   * fingerprint of the PAIR (each string side reduced to its fingerprint, a binned side to its index, the two cells
+   * chained as the components of a tuple key are -- never a concatenation of the bytes: ("ab", "c") and ("a", "bc") are
+   * different pairs) and every entry keeps its bytes; across states, blobs and ranks entries are united by their bytes
+   * (and bin indices).  tgx_merge, state blobs and tgx_allreduce unite by value and add the counters; a range-phase
+   * state merges MIN / MAX / counters as JOINT_BINS's does. */
+  TGX_CHECK_PAIR_COUNTS = 16
 } tgx_check_kind;
 
 enum {
@@ -535,6 +569,30 @@ typedef struct tgx_value_counts_params {
 tgx_status tgx_plan_set_value_counts(tgx_plan *plan, size_t spec_index, const tgx_value_counts_params *params,
                                      tgx_error *err);
 
+/* TGX_CHECK_PAIR_COUNTS: the bounds of spec `spec_index` and what a cell is on either side.  Like the VALUE_COUNTS
+ * parameters they can be set until the plan's first state exists; afterwards, and for a spec of another kind, the call is
+ * refused with TGX_INVALID_ARGUMENT.  max_pairs (1 .. TGX_PAIR_COUNTS_MAX_PAIRS) sizes the task's table on the device: a
+ * power of two of at least 2 * max_pairs slots, probed as VALUE_COUNTS's is; max_value_bytes
+ * (1 .. TGX_PAIR_COUNTS_MAX_VALUE_BYTES) holds per string side.  A TGX_PAIR_SIDE_BINNED side gives origin (finite),
+ * width (finite, positive) and bins (2 .. TGX_JOINT_MAX_BINS); the other modes leave the three zero.  Two numeric sides
+ * (any two of BINNED and RANGE) are refused with TGX_INVALID_ARGUMENT: joint bins of two numeric columns are
+ * TGX_CHECK_JOINT_BINS.  The reference's values are origin = MIN, width = (MAX - MIN) > 0 ? (MAX - MIN) / bins : 1.0
+ * (mutual_information.rs:219-233), with MIN / MAX from a first pass in the RANGE mode. */
+enum { TGX_PAIR_SIDE_VALUE = 0, TGX_PAIR_SIDE_RANGE = 1, TGX_PAIR_SIDE_BINNED = 2 };
+enum { TGX_PAIR_COUNTS_MAX_PAIRS = 65536, TGX_PAIR_COUNTS_MAX_VALUE_BYTES = 256 };
+typedef struct tgx_pair_side {
+  int32_t mode;  /* TGX_PAIR_SIDE_* */
+  uint32_t bins; /* BINNED */
+  double origin, width; /* BINNED */
+} tgx_pair_side;
+typedef struct tgx_pair_counts_params {
+  uint32_t max_pairs;
+  uint32_t max_value_bytes;
+  tgx_pair_side x, y;
+} tgx_pair_counts_params;
+tgx_status tgx_plan_set_pair_counts(tgx_plan *plan, size_t spec_index, const tgx_pair_counts_params *params,
+                                    tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -734,6 +792,48 @@ tgx_status tgx_value_counts_entries(const tgx_plan *plan, tgx_state *state, size
                                     tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
                                     uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
 
+/* ---- pair counts (TGX_CHECK_PAIR_COUNTS; TG/analyzers/advanced/mutual_information.rs:249-293) -------------------- */
+typedef struct tgx_pair_counts_summary {
+  uint64_t seen;          /* rows handed to tgx_update */
+  uint64_t both_non_null; /* rows with both sides non-NULL (a row whose dictionary entry is NULL is a NULL row) */
+  uint64_t distinct;      /* pairs held; may exceed max_pairs: the caller compares */
+  uint64_t counted;       /* rows counted in the entries: the sum of their counts */
+  uint64_t overflow_rows; /* rows whose pair found no slot */
+  uint64_t long_rows;     /* rows with a string longer than max_value_bytes on either side: they are in no entry */
+  uint64_t non_finite;    /* rows, not long ones, whose binned side holds a NaN or an infinity */
+  uint64_t out_of_range;  /* rows, neither long nor non-finite, whose bin index fell outside [0, bins] */
+} tgx_pair_counts_summary; /* counted + overflow_rows + long_rows + non_finite + out_of_range == both_non_null */
+/* A spec in its RANGE phase answers seen and both_non_null and leaves the rest zero. */
+tgx_status tgx_pair_counts_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                               tgx_pair_counts_summary *out, tgx_error *err);
+/* A spec in its RANGE phase: the numeric side over the rows with both sides non-NULL.  A spec in its count phase is
+ * refused with TGX_INVALID_ARGUMENT. */
+typedef struct tgx_pair_range {
+  uint64_t seen;          /* rows handed to tgx_update */
+  uint64_t both_non_null; /* rows with both sides non-NULL */
+  uint64_t n;             /* those of them whose numeric side is finite */
+  uint64_t non_finite;    /* those of them whose numeric side is a NaN or an infinity: n + non_finite == both_non_null */
+  double min, max;        /* CAST AS DOUBLE, over the n rows; NaN when n == 0 */
+} tgx_pair_range;
+tgx_status tgx_pair_range_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_pair_range *out,
+                              tgx_error *err);
+/* One pair and its count.  A string side: bytes [offset, offset + length) of the caller's byte buffer (its bin is 0); a
+ * binned side: its bin index (offset and length are 0). */
+typedef struct tgx_pair_count_entry {
+  int64_t x_bin, y_bin;
+  uint64_t x_offset, x_length;
+  uint64_t y_offset, y_length;
+  uint64_t count;
+} tgx_pair_count_entry;
+/* Copies the entries, ascending by (x cell, y cell): strings bytewise (unsigned bytes, a prefix first), bins as
+ * integers, so two reads of equal states are byte-identical.  The convention of tgx_value_counts_entries: *n_entries
+ * and *n_bytes always receive what is needed; `entries` (cap entries) and `bytes` (bytes_cap bytes) may be NULL for a
+ * size query; a non-NULL buffer that is too small makes the call return TGX_INVALID_ARGUMENT with nothing copied.  A
+ * spec in its RANGE phase has no entries. */
+tgx_status tgx_pair_counts_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                   tgx_pair_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
+                                   uint64_t bytes_cap, uint64_t *n_bytes, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -823,7 +923,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -101,14 +101,20 @@ tgx_status tgx_host_assertion_json(const char *assertion_json, double value, int
  * Analysis JSON: {"table_name": "data", "continue_on_error": true, "analyzers": [
  *     {"type": "size"}, {"type": "completeness|distinctness|approx_count_distinct|mean|min|max|sum|standard_deviation", "column": "c"},
  *     {"type": "correlation", "column1": "a", "column2": "b", "method": "pearson|spearman|covariance"},
- *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10},
+ *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10, "max_pairs": N (optional),
+ *      "max_value_bytes": 256 (optional), "arrow_types": ["Utf8", "Int64"] (optional)},
  *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true},
  *     {"type": "value_entropy", "column": "c", "max_unique_values": 10000, "arrow_type": "Int64" (optional)}]}
  * "value_entropy" is the tag of EntropyAnalyzer (TG/analyzers/advanced/entropy.rs; name() "entropy", metric key
  * "entropy.<column>"): the tag "entropy" is not taken, it stays an unknown analyzer type.
  * AnalysisRunner::run: every analyzer's aggregates planned into ONE tgx_plan, one pass over the table; the
  * mutual_information and histogram analyzers (bin edges depend on the whole table) add a second pass for their counts,
- * shared by all such analyzers of the run.  Returns
+ * shared by all such analyzers of the run.  "max_pairs" is mutual_information's opt-in for string columns: with it, a
+ * pair with at least one Utf8 / LargeUtf8 / Utf8View / Dictionary column plans ONE TGX_CHECK_PAIR_COUNTS request
+ * (string x string: one pass; a mixed pair: the numeric side's range, then the count, in the shared second pass);
+ * without it the analyzer does what it always did (JOINT_BINS; a string column is its TGX_UNSUPPORTED error).  A pair
+ * beyond the bounds, a column declared binary and a string value that may parse as a number are the
+ * analyzer's own errors.  Returns
  *   {"metrics": {metric_key: {"type": "Double|Long|Boolean|Map|Histogram", "value": ..}},   (MetricValue's serde form, types.rs:11-35)
  *    "states":  {metric_key: {..the AnalyzerState's serde fields..}},
  *    "errors":  [{"analyzer_name": "..", "error": ".."}]}                        (context.rs:118-123)
@@ -123,6 +129,19 @@ tgx_status tgx_host_merge_states_json(const char *analyzer_json, const char *sta
 /* Analyzer::compute_metric_from_state; needs no device.  An AnalyzerError (e.g. NoData) is returned as
  * TGX_INVALID_ARGUMENT with the reference's Display text in err->msg. */
 tgx_status tgx_host_metric_from_state_json(const char *analyzer_json, const char *state_json, char **out_metric_json,
+                                           tgx_error *err);
+
+/* What an analyzer plans for columns of the given tgx_types (column_types_json: an array of tgx_type numbers parallel to
+ * the analyzer's columns; 0 = unknown): {"requests": [{"kind", "column", "column2", "pair_counts": {"max_pairs",
+ * "max_value_bytes", "x_mode", "y_mode"} (TGX_CHECK_PAIR_COUNTS only)}]}.  Needs no device. */
+tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *column_types_json, char **out_json,
+                                       tgx_error *err);
+
+/* The state a mutual_information analyzer builds from given pair counts; needs no device.  pair_counts_json:
+ * {"summary": {tgx_pair_counts_summary's fields; absent ones are 0}, "entries": [[x, y, count], ..]} in the library's
+ * order, a cell being a string (a value), an array of byte values (a value that is no UTF-8) or an integer (a bin).  An
+ * AnalyzerError is returned as TGX_INVALID_ARGUMENT with its text in err->msg. */
+tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json, const char *pair_counts_json, char **out_state_json,
                                            tgx_error *err);
 
 void tgx_host_free(char *s);

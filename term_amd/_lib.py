@@ -22,6 +22,9 @@ RULE_GE_ZERO, RULE_GT_ZERO, RULE_BETWEEN, RULE_INTEGER = 1, 2, 3, 4
 RULE_BOUNDS_AS_DOUBLE = 1
 VALUE_COUNTS = 15  # how often each value of a column occurs, for a bounded number of values (Plan.set_value_counts)
 VALUE_COUNTS_MAX_DISTINCT, VALUE_COUNTS_MAX_VALUE_BYTES = 65536, 256
+PAIR_COUNTS = 16  # how often each pair of cells of two columns occurs, for a bounded number of pairs (Plan.set_pair_counts)
+PAIR_SIDE_VALUE, PAIR_SIDE_RANGE, PAIR_SIDE_BINNED = 0, 1, 2
+PAIR_COUNTS_MAX_PAIRS, PAIR_COUNTS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -138,6 +141,35 @@ class ValueCountsSummary(C.Structure):
 class ValueCountEntry(C.Structure):
     """tgx_value_count_entry (include/tgx.h)"""
     _fields_ = [("value", C.c_int64), ("offset", C.c_uint64), ("length", C.c_uint64), ("count", C.c_uint64)]
+
+
+class PairSide(C.Structure):
+    """tgx_pair_side (include/tgx.h)"""
+    _fields_ = [("mode", C.c_int32), ("bins", C.c_uint32), ("origin", C.c_double), ("width", C.c_double)]
+
+
+class PairCountsParams(C.Structure):
+    """tgx_pair_counts_params (include/tgx.h)"""
+    _fields_ = [("max_pairs", C.c_uint32), ("max_value_bytes", C.c_uint32), ("x", PairSide), ("y", PairSide)]
+
+
+class PairCountsSummary(C.Structure):
+    """tgx_pair_counts_summary (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("both_non_null", C.c_uint64), ("distinct", C.c_uint64), ("counted", C.c_uint64),
+                ("overflow_rows", C.c_uint64), ("long_rows", C.c_uint64), ("non_finite", C.c_uint64),
+                ("out_of_range", C.c_uint64)]
+
+
+class PairRange(C.Structure):
+    """tgx_pair_range (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("both_non_null", C.c_uint64), ("n", C.c_uint64), ("non_finite", C.c_uint64),
+                ("min", C.c_double), ("max", C.c_double)]
+
+
+class PairCountEntry(C.Structure):
+    """tgx_pair_count_entry (include/tgx.h)"""
+    _fields_ = [("x_bin", C.c_int64), ("y_bin", C.c_int64), ("x_offset", C.c_uint64), ("x_length", C.c_uint64),
+                ("y_offset", C.c_uint64), ("y_length", C.c_uint64), ("count", C.c_uint64)]
 
 
 class HistogramRange(C.Structure):
@@ -270,6 +302,10 @@ def lib():
         L.tgx_value_counts_get.argtypes = [vp, vp, sz, C.POINTER(ValueCountsSummary), E]
         L.tgx_value_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
                                                C.POINTER(C.c_int32), E]
+        L.tgx_plan_set_pair_counts.argtypes = [vp, sz, C.POINTER(PairCountsParams), E]
+        L.tgx_pair_counts_get.argtypes = [vp, vp, sz, C.POINTER(PairCountsSummary), E]
+        L.tgx_pair_range_get.argtypes = [vp, vp, sz, C.POINTER(PairRange), E]
+        L.tgx_pair_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -650,6 +686,7 @@ class Plan:
         self.h = h
         self.n = len(self._specs)
         self.histogram_buckets = {}  # spec index -> buckets, once set_histogram_edges was called
+        self.pair_sides = {}  # spec index -> the two sides' modes, once set_pair_counts was called
         if fingerprint_key is not None:
             self.set_fingerprint_key(fingerprint_key)
 
@@ -702,6 +739,25 @@ class Plan:
         p = ValueCountsParams(max_distinct, max_value_bytes)
         err = _Error()
         _check(lib().tgx_plan_set_value_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_pair_counts(self, spec_index, x=None, y=None, max_pairs=10000, max_value_bytes=256):
+        """tgx_plan_set_pair_counts: the bounds and the sides of a PAIR_COUNTS spec (before the plan's first state).  A
+        side is None or "value" (a string column: PAIR_SIDE_VALUE), "range" (a numeric column: the spec is in its range
+        phase) or a binning (origin, width, bins) of a numeric column"""
+        def side(s):
+            if s is None or s == "value":
+                return PairSide(PAIR_SIDE_VALUE, 0, 0.0, 0.0)
+            if s == "range":
+                return PairSide(PAIR_SIDE_RANGE, 0, 0.0, 0.0)
+            if isinstance(s, PairSide):
+                return s
+            origin, width, bins = s
+            return PairSide(PAIR_SIDE_BINNED, bins, origin, width)
+        sx, sy = side(x), side(y)
+        p = PairCountsParams(max_pairs, max_value_bytes, sx, sy)
+        err = _Error()
+        _check(lib().tgx_plan_set_pair_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
+        self.pair_sides[spec_index] = (sx.mode, sy.mode)
 
     def fingerprint_key(self):
         out = (C.c_uint8 * 16)()
@@ -918,6 +974,39 @@ class State:
             counts[raw[e.offset:e.offset + e.length] if is_bytes.value else e.value] = e.count
         summary = {f: getattr(s, f) for f, _ in ValueCountsSummary._fields_}
         return summary, counts
+
+    # pair counts
+    def pair_counts(self, spec_index):
+        """tgx_pair_counts_get + tgx_pair_counts_entries: (summary, counts) -- summary a dict of the eight counters (seen,
+        both_non_null, distinct, counted, overflow_rows, long_rows, non_finite, out_of_range), counts a dict
+        (x cell, y cell) -> count in the library's order (ascending by x cell, then y cell); a cell is bytes for a string
+        side and an int (the bin index) for a binned side"""
+        L, err = lib(), _Error()
+        s = PairCountsSummary()
+        _check(L.tgx_pair_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        n, nb = C.c_uint64(), C.c_uint64()
+        _check(L.tgx_pair_counts_entries(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, 0, C.byref(nb),
+                                         C.byref(err)), err)
+        entries = (PairCountEntry * max(n.value, 1))()
+        buf = (C.c_uint8 * max(nb.value, 1))()
+        _check(L.tgx_pair_counts_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), buf, nb.value,
+                                         C.byref(nb), C.byref(err)), err)
+        raw = bytes(buf)
+        mx, my = self.plan.pair_sides.get(spec_index, (PAIR_SIDE_VALUE, PAIR_SIDE_VALUE))
+        counts = {}
+        for e in entries[:n.value]:
+            cx = raw[e.x_offset:e.x_offset + e.x_length] if mx == PAIR_SIDE_VALUE else e.x_bin
+            cy = raw[e.y_offset:e.y_offset + e.y_length] if my == PAIR_SIDE_VALUE else e.y_bin
+            counts[(cx, cy)] = e.count
+        summary = {f: getattr(s, f) for f, _ in PairCountsSummary._fields_}
+        return summary, counts
+
+    def pair_range(self, spec_index):
+        """tgx_pair_range_get: dict(seen, both_non_null, n, non_finite, min, max) of a spec in its range phase"""
+        out = PairRange()
+        err = _Error()
+        _check(lib().tgx_pair_range_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return {name: getattr(out, name) for name, _ in PairRange._fields_}
 
     # distinct key exchange
     def distinct_export(self, spec_index, world):

@@ -428,10 +428,24 @@ class CorrelationAnalyzer : public Analyzer {  // advanced/correlation.rs
 // match for `joint_counts`: here it is a list of [x_label, y_label, count], non-empty cells only, in row-major order.
 // `n` and `bins` are integer tokens, x_counts / y_counts maps keyed by the bin label.  A label is the Float64 bin
 // index as Arrow casts it to text ("0.0", "1.0", ...: CAST(FLOOR(..) AS VARCHAR)).
+//
+// The other three branches (:249-293: a string column on either side or both) are an OPT-IN, "max_pairs": N (with an
+// optional "max_value_bytes"): the reference's constructor has no bounds, the device's table needs them.  With it, a
+// pair with at least one string column plans ONE TGX_CHECK_PAIR_COUNTS request: string x string is one pass; a mixed
+// pair is two -- the numeric side's range over the rows with both sides non-NULL, then origin = MIN and
+// width = range > 0 ? range / bins : 1.0 (:219-233) and the count.  The state has the same shape: a string side's label
+// is its value, a binned side's the bin label; entries follow the library's order (ascending by x cell, then y cell).
+// Beyond the bounds (overflow rows, long rows, rows outside the bins, more pairs than max_pairs) the analyzer fails
+// with the numbers.  One fidelity guard: the reference takes a column for categorical only when no value of it parses
+// as a double (MIN(TRY_CAST(col AS DOUBLE)) IS NULL); a string column with a value that MAY parse (may_parse_as_number:
+// a deliberately generous superset of any float grammar) is this analyzer's error, not a guess.
 class MutualInformationAnalyzer : public Analyzer {
  public:
-  MutualInformationAnalyzer(std::string a, std::string b, uint64_t bins)
-      : a_(std::move(a)), b_(std::move(b)), bins_(std::max<uint64_t>(bins, 2)) {}  // :96-104
+  MutualInformationAnalyzer(std::string a, std::string b, uint64_t bins, std::optional<uint64_t> max_pairs = std::nullopt,
+                            uint64_t max_value_bytes = TGX_PAIR_COUNTS_MAX_VALUE_BYTES,
+                            std::vector<std::string> arrow_types = {})
+      : a_(std::move(a)), b_(std::move(b)), bins_(std::max<uint64_t>(bins, 2)),  // :96-104
+        max_pairs_(max_pairs), max_value_bytes_(max_value_bytes), arrow_types_(std::move(arrow_types)) {}
   std::string name() const override { return "mutual_information"; }
   std::string metric_key() const override { return "mutual_information_" + a_ + "_" + b_; }  // :413-415
   std::vector<std::string> columns() const override { return {a_, b_}; }
@@ -440,8 +454,62 @@ class MutualInformationAnalyzer : public Analyzer {
     r.column2 = b_;
     return {r};
   }
+  static bool is_text(int type) {
+    return type == TGX_UTF8 || type == TGX_LARGE_UTF8 || type == TGX_UTF8_VIEW || type == TGX_DICT32_UTF8;
+  }
+  std::vector<SpecRequest> plan_for(const std::vector<int> &types, const std::vector<std::string> &declared) const override {
+    if (!max_pairs_ || types.size() != 2 || (!is_text(types[0]) && !is_text(types[1]))) return plan();
+    for (int side = 0; side < 2; side++) {
+      const std::string &given = arrow_types_.size() == 2 && !arrow_types_[side].empty() ? arrow_types_[side]
+                                 : declared.size() == 2                                  ? declared[side]
+                                                                                         : std::string();
+      std::string lower;
+      for (char ch : given) lower += (char)tolower((unsigned char)ch);
+      if (lower.find("binary") != std::string::npos)
+        throw AnalyzerError::invalid_data("column '" + (side ? b_ : a_) + "' is declared " + given +
+                                          ": its values are not text (not on the GPU path)");
+    }
+    if (*max_pairs_ < 1 || *max_pairs_ > TGX_PAIR_COUNTS_MAX_PAIRS || max_value_bytes_ < 1 ||
+        max_value_bytes_ > TGX_PAIR_COUNTS_MAX_VALUE_BYTES)
+      throw AnalyzerError::invalid_data("max_pairs must be 1 .. " + std::to_string(TGX_PAIR_COUNTS_MAX_PAIRS) + " (" +
+                                        std::to_string(*max_pairs_) + ") and max_value_bytes 1 .. " +
+                                        std::to_string(TGX_PAIR_COUNTS_MAX_VALUE_BYTES) + " (" +
+                                        std::to_string(max_value_bytes_) + ")");
+    SpecRequest r = req(TGX_CHECK_PAIR_COUNTS, a_);
+    r.column2 = b_;
+    tgx_pair_counts_params p;
+    memset(&p, 0, sizeof(p));
+    p.max_pairs = (uint32_t)*max_pairs_;
+    p.max_value_bytes = (uint32_t)max_value_bytes_;
+    p.x.mode = is_text(types[0]) ? TGX_PAIR_SIDE_VALUE : TGX_PAIR_SIDE_RANGE;
+    p.y.mode = is_text(types[1]) ? TGX_PAIR_SIDE_VALUE : TGX_PAIR_SIDE_RANGE;
+    r.pair_counts = p;
+    return {r};
+  }
   bool two_pass() const override { return true; }
   std::optional<FollowUp> follow_up(const FirstPass &first) const override {
+    if (first.kind == TGX_CHECK_PAIR_COUNTS) {  // a mixed pair: the numeric side's range is in, the count follows
+      const tgx_pair_range &range = first.pair;
+      if (range.n == 0) return std::nullopt;
+      if (bins_ > TGX_JOINT_MAX_BINS)
+        throw AnalyzerError::query("TGX_UNSUPPORTED: " + std::to_string(bins_) + " bins: at most " +
+                                   std::to_string(TGX_JOINT_MAX_BINS) + " are supported");
+      const bool x_numeric = !is_text(first.column_types.at(0));
+      const double span = range.max - range.min;
+      if (!std::isfinite(span))
+        throw AnalyzerError::invalid_data("the range of " + (x_numeric ? a_ : b_) + " overflows a double: no bin width");
+      FollowUp out;
+      tgx_pair_counts_params &p = out.pair;
+      p.max_pairs = (uint32_t)max_pairs_.value_or(1);
+      p.max_value_bytes = (uint32_t)max_value_bytes_;
+      tgx_pair_side &num = x_numeric ? p.x : p.y, &text = x_numeric ? p.y : p.x;
+      text.mode = TGX_PAIR_SIDE_VALUE;
+      num.mode = TGX_PAIR_SIDE_BINNED;
+      num.bins = (uint32_t)bins_;
+      num.origin = range.min;
+      num.width = span > 0.0 ? span / (double)bins_ : 1.0;  // :219-233, in the same double arithmetic
+      return out;
+    }
     const tgx_joint_range &range = first.joint;
     if (range.n == 0) return std::nullopt;
     if (bins_ > TGX_JOINT_MAX_BINS)
@@ -464,7 +532,88 @@ class MutualInformationAnalyzer : public Analyzer {
   json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
     return state_from_follow_up(FirstPass(), nullptr);
   }
-  json::Value state_from_follow_up(const FirstPass &, const SecondPass *second) const override {
+  // is `v` inside a superset of what a cast of text to a double may take?  Conservative, and unverified against
+  // arrow-cast: after stripping ASCII whitespace, a non-empty text of the characters 0-9 + - . e E _ with a digit in it,
+  // or -- after an optional sign -- nan / inf / infinity in either letter case
+  static bool may_parse_as_number(const std::string &v) {
+    size_t lo = 0, hi = v.size();
+    auto space = [](char ch) { return ch == ' ' || (ch >= '\t' && ch <= '\r'); };
+    while (lo < hi && space(v[lo])) lo++;
+    while (hi > lo && space(v[hi - 1])) hi--;
+    if (lo == hi) return false;
+    bool only = true, digit = false;
+    for (size_t i = lo; i < hi; i++) {
+      const char ch = v[i];
+      digit |= ch >= '0' && ch <= '9';
+      only &= (ch >= '0' && ch <= '9') || ch == '+' || ch == '-' || ch == '.' || ch == 'e' || ch == 'E' || ch == '_';
+    }
+    if (only && digit) return true;
+    if (v[lo] == '+' || v[lo] == '-') lo++;
+    std::string word;
+    for (size_t i = lo; i < hi; i++) word += (char)tolower((unsigned char)v[i]);
+    return word == "nan" || word == "inf" || word == "infinity";
+  }
+  static bool valid_utf8(const std::string &s) {
+    const unsigned char *p = (const unsigned char *)s.data();
+    size_t i = 0, n = s.size();
+    while (i < n) {
+      const unsigned c = p[i];
+      size_t more;
+      unsigned cp, least;
+      if (c < 0x80) { i++; continue; }
+      else if ((c & 0xE0) == 0xC0) { more = 1; cp = c & 0x1F; least = 0x80; }
+      else if ((c & 0xF0) == 0xE0) { more = 2; cp = c & 0x0F; least = 0x800; }
+      else if ((c & 0xF8) == 0xF0) { more = 3; cp = c & 0x07; least = 0x10000; }
+      else return false;
+      if (i + more >= n) return false;  // (cut short)
+      for (size_t k = 1; k <= more; k++) {
+        if ((p[i + k] & 0xC0) != 0x80) return false;
+        cp = (cp << 6) | (p[i + k] & 0x3F);
+      }
+      if (cp < least || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
+      i += more + 1;
+    }
+    return true;
+  }
+  json::Value state_from_pair_counts(const PairCounts &pc) const override {
+    const tgx_pair_counts_summary &s = pc.summary;
+    const uint64_t max_pairs = max_pairs_.value_or(0);
+    if (s.overflow_rows || s.long_rows || s.out_of_range || s.distinct > max_pairs) {
+      char buf[320];
+      snprintf(buf, sizeof(buf),
+               "the pair is beyond the bounds of its pair counts: %llu distinct pairs (max_pairs %llu), %llu overflow "
+               "rows, %llu rows with a value longer than %llu bytes, %llu rows outside the bins (the table changed "
+               "between the two passes)",
+               (unsigned long long)s.distinct, (unsigned long long)max_pairs, (unsigned long long)s.overflow_rows,
+               (unsigned long long)s.long_rows, (unsigned long long)max_value_bytes_, (unsigned long long)s.out_of_range);
+      throw AnalyzerError::invalid_data(buf);
+    }
+    std::vector<Cell> cells;
+    uint64_t n = 0;
+    for (const PairCounts::Entry &e : pc.entries) {
+      std::string labels[2];
+      for (int side = 0; side < 2; side++) {
+        const PairCell &c = side ? e.y : e.x;
+        const std::string &col = side ? b_ : a_;
+        if (c.binned) {
+          labels[side] = label((uint32_t)c.bin);
+          continue;
+        }
+        if (!valid_utf8(c.bytes))
+          throw AnalyzerError::invalid_data("a value of " + col + " is not valid UTF-8: it has no text (not on the GPU path)");
+        if (may_parse_as_number(c.bytes))
+          throw AnalyzerError::invalid_data("a value of " + col + " may parse as a number: the reference would bin this "
+                                            "column (not on the GPU path)");
+        labels[side] = c.bytes;
+      }
+      cells.push_back({labels[0], labels[1], e.count});
+      n += e.count;
+    }
+    return state(n, cells, bins_);
+  }
+  json::Value state_from_follow_up(const FirstPass &first, const SecondPass *second) const override {
+    if (first.kind == TGX_CHECK_PAIR_COUNTS)
+      return second ? state_from_pair_counts(second->pairs) : state(0, std::vector<Cell>(), bins_);
     const JointCounts *counts = second ? &second->joint : nullptr;
     std::vector<Cell> cells;
     uint64_t n = 0;
@@ -566,6 +715,9 @@ class MutualInformationAnalyzer : public Analyzer {
   }
   std::string a_, b_;
   uint64_t bins_;
+  std::optional<uint64_t> max_pairs_;  // the opt-in for string columns (TGX_CHECK_PAIR_COUNTS)
+  uint64_t max_value_bytes_;
+  std::vector<std::string> arrow_types_;  // the two columns' Arrow DataType names where the table does not say
 };
 
 // The reference's arithmetic on the first query's results, in IEEE doubles exactly as written: every product rounds
@@ -774,6 +926,38 @@ class EntropyAnalyzer : public ColumnAnalyzer {
   std::string arrow_type_;
 };
 
+}  // namespace
+
+PairCounts read_pair_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, const tgx_pair_counts_params &params) {
+  PairCounts out;
+  tgx_error err;
+  memset(&err, 0, sizeof(err));
+  auto check = [&](tgx_status s) {
+    if (s != TGX_OK) throw AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg);
+  };
+  check(tgx_pair_counts_get(plan, state, spec_index, &out.summary, &err));
+  uint64_t n = 0, nb = 0;
+  check(tgx_pair_counts_entries(plan, state, spec_index, nullptr, 0, &n, nullptr, 0, &nb, &err));
+  std::vector<tgx_pair_count_entry> entries((size_t)n + 1);
+  std::vector<uint8_t> bytes((size_t)nb + 1);
+  check(tgx_pair_counts_entries(plan, state, spec_index, entries.data(), n, &n, bytes.data(), nb, &nb, &err));
+  for (uint64_t i = 0; i < n; i++) {
+    const tgx_pair_count_entry &e = entries[i];
+    PairCounts::Entry o;
+    o.x.binned = params.x.mode != TGX_PAIR_SIDE_VALUE;
+    o.x.bin = e.x_bin;
+    if (!o.x.binned) o.x.bytes.assign((const char *)bytes.data() + e.x_offset, (size_t)e.x_length);
+    o.y.binned = params.y.mode != TGX_PAIR_SIDE_VALUE;
+    o.y.bin = e.y_bin;
+    if (!o.y.binned) o.y.bytes.assign((const char *)bytes.data() + e.y_offset, (size_t)e.y_length);
+    o.count = e.count;
+    out.entries.push_back(std::move(o));
+  }
+  return out;
+}
+
+namespace {
+
 struct Handles {
   tgx_plan *plan = nullptr;
   tgx_state *state = nullptr;
@@ -820,7 +1004,16 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
   if (t == "mutual_information") {
     if (v.get_str("column1").empty() || v.get_str("column2").empty())
       throw TermError{TermError::Internal, "mutual_information needs column1 and column2"};
-    return std::make_shared<MutualInformationAnalyzer>(v.get_str("column1"), v.get_str("column2"), v.get_u64("bins", 10));
+    std::optional<uint64_t> max_pairs;
+    if (const json::Value *mp = v.get("max_pairs"))
+      if (mp->type != json::Value::Null) max_pairs = mp->as_u64();
+    std::vector<std::string> arrow_types;
+    if (const json::Value *at = v.get("arrow_types"))
+      if (at->type == json::Value::Array)
+        for (const json::Value &e : at->arr) arrow_types.push_back(e.type == json::Value::String ? e.str : std::string());
+    return std::make_shared<MutualInformationAnalyzer>(v.get_str("column1"), v.get_str("column2"), v.get_u64("bins", 10),
+                                                       max_pairs, v.get_u64("max_value_bytes", TGX_PAIR_COUNTS_MAX_VALUE_BYTES),
+                                                       arrow_types);
   }
   if (t == "histogram")
     return std::make_shared<HistogramAnalyzer>(col(), v.get_u64("num_buckets", 10), v.get_bool("strict_reference_types", true));
@@ -854,7 +1047,24 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       p.error = AnalyzerError::query("Error during planning: table 'datafusion.public." + table_name_ + "' not found").text;
       continue;
     }
-    for (SpecRequest r : analyzers_[a]->plan()) {
+    std::vector<std::string> declared;
+    for (const std::string &c : analyzers_[a]->columns()) {
+      int ci = column_index(c);
+      int type = 0;
+      if (ci >= 0)
+        for (const Batch &b : table->batches)
+          if (type == 0) type = b.columns[ci].type;
+      p.column_types.push_back(type);
+      declared.push_back(ci >= 0 && (size_t)ci < table->arrow_types.size() ? table->arrow_types[ci] : std::string());
+    }
+    std::vector<SpecRequest> wanted;
+    try {
+      wanted = analyzers_[a]->plan_for(p.column_types, declared);
+    } catch (const AnalyzerError &e) {
+      p.error = e.text;
+      continue;
+    }
+    for (SpecRequest r : wanted) {
       if (r.column.empty() && !table->column_names.empty()) r.column = table->column_names[0];  // COUNT(*)
       for (const std::string *c : {&r.column, &r.column2}) {
         if (c == &r.column2 && r.column2.empty()) continue;
@@ -863,14 +1073,6 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       }
       if (p.error) break;
       p.reqs.push_back(r);
-    }
-    for (const std::string &c : analyzers_[a]->columns()) {
-      int ci = column_index(c);
-      int type = 0;
-      if (ci >= 0)
-        for (const Batch &b : table->batches)
-          if (type == 0) type = b.columns[ci].type;
-      p.column_types.push_back(type);
     }
     if (!p.error && analyzers_[a]->reads_value_counts()) {
       const std::string refusal = analyzers_[a]->value_text_refusal(p.column_types.empty() ? 0 : p.column_types[0]);
@@ -920,10 +1122,13 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       const FollowUp &fu = (*follow_ups)[i];
       s = specs[i].kind == TGX_CHECK_HISTOGRAM
               ? tgx_plan_set_histogram_edges(hh.plan, i, fu.edges.data(), (uint32_t)(fu.edges.size() - 1), &err)
-              : tgx_plan_set_joint_binning(hh.plan, i, &fu.binning, &err);
+          : specs[i].kind == TGX_CHECK_PAIR_COUNTS ? tgx_plan_set_pair_counts(hh.plan, i, &fu.pair, &err)
+                                                   : tgx_plan_set_joint_binning(hh.plan, i, &fu.binning, &err);
     }
-    for (size_t i = 0; s == TGX_OK && !follow_ups && i < requests.size(); i++)
+    for (size_t i = 0; s == TGX_OK && !follow_ups && i < requests.size(); i++) {
       if (requests[i].value_counts) s = tgx_plan_set_value_counts(hh.plan, i, &*requests[i].value_counts, &err);
+      if (requests[i].pair_counts) s = tgx_plan_set_pair_counts(hh.plan, i, &*requests[i].pair_counts, &err);
+    }
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
     for (size_t b = 0; s == TGX_OK && b < table->batches.size(); b++) {
@@ -1000,8 +1205,23 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       FirstPass &first = followed[a].first;
       first.kind = specs[planned[a].spec_index[0]].kind;
       first.column_types = planned[a].column_types;
+      if (first.kind == TGX_CHECK_PAIR_COUNTS) {
+        // string x string: the first pass counted the pairs, there is no follow-up
+        const tgx_pair_counts_params &pp = *requests[planned[a].spec_index[0]].pair_counts;
+        if (pp.x.mode != TGX_PAIR_SIDE_RANGE && pp.y.mode != TGX_PAIR_SIDE_RANGE) {
+          try {
+            followed[a].second.pairs = read_pair_counts(h.plan, h.state, planned[a].spec_index[0], pp);
+            followed[a].counted = true;
+          } catch (const AnalyzerError &e) {
+            planned[a].error = e.text;
+          }
+          continue;
+        }
+      }
       const tgx_status s = first.kind == TGX_CHECK_HISTOGRAM
                                ? tgx_histogram_range_get(h.plan, h.state, planned[a].spec_index[0], &first.histogram, &err)
+                           : first.kind == TGX_CHECK_PAIR_COUNTS
+                               ? tgx_pair_range_get(h.plan, h.state, planned[a].spec_index[0], &first.pair, &err)
                                : tgx_joint_range_get(h.plan, h.state, planned[a].spec_index[0], &first.joint, &err);
       if (s != TGX_OK) {
         planned[a].error = AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg).text;
@@ -1029,8 +1249,14 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
         tgx_error err;
         memset(&err, 0, sizeof(err));
         if (!second_error) {
-          tgx_status s;
-          if (fo.first.kind == TGX_CHECK_HISTOGRAM) {
+          tgx_status s = TGX_OK;
+          if (fo.first.kind == TGX_CHECK_PAIR_COUNTS) {
+            try {
+              fo.second.pairs = read_pair_counts(second.plan, second.state, k, follow_ups[k].pair);
+            } catch (const AnalyzerError &e) {
+              second_error = e.text;
+            }
+          } else if (fo.first.kind == TGX_CHECK_HISTOGRAM) {
             fo.second.buckets.assign(follow_ups[k].edges.size() - 1, 0);
             s = tgx_histogram_counts(second.plan, second.state, k, fo.second.buckets.data(), fo.second.buckets.size(),
                                      nullptr, nullptr, &err);

@@ -73,19 +73,38 @@ struct JointCounts {
   std::vector<uint64_t> cells;  // (bins + 1)^2, row-major (tgx_joint_counts)
   uint64_t out_of_range = 0;
 };
+// one spec's state as tgx_pair_counts_get / tgx_pair_counts_entries answer it, in the library's order
+struct PairCell {
+  bool binned = false;  // a binned side: `bin`; a string side: `bytes`
+  int64_t bin = 0;
+  std::string bytes;
+};
+struct PairCounts {
+  tgx_pair_counts_summary summary = {};
+  struct Entry {
+    PairCell x, y;
+    uint64_t count = 0;
+  };
+  std::vector<Entry> entries;
+};
+PairCounts read_pair_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                            const tgx_pair_counts_params &params);  // throws AnalyzerError (query)
 struct FirstPass {  // what the request's range phase found
   int kind = 0;                   // the kind of plan()[0]
   std::vector<int> column_types;  // tgx_type of columns() in order
   tgx_joint_range joint = {};
   tgx_histogram_range histogram = {};
+  tgx_pair_range pair = {};       // PAIR_COUNTS with a side in its range phase
 };
 struct FollowUp {  // the parameters that put the request into its count phase
   tgx_joint_binning binning = {};  // JOINT_BINS (tgx_plan_set_joint_binning)
   std::vector<double> edges;       // HISTOGRAM (tgx_plan_set_histogram_edges): buckets + 1
+  tgx_pair_counts_params pair = {};  // PAIR_COUNTS (tgx_plan_set_pair_counts): the range side now binned
 };
 struct SecondPass {  // what the request's count phase found
   JointCounts joint;
   std::vector<uint64_t> buckets;  // HISTOGRAM (tgx_histogram_counts)
+  PairCounts pairs;               // PAIR_COUNTS; a string x string request is counted by the FIRST pass and lands here too
 };
 
 class Analyzer {
@@ -96,6 +115,16 @@ class Analyzer {
   virtual std::vector<std::string> columns() const { return {}; }
   // aggregates this analyzer needs (its half of the fused plan)
   virtual std::vector<SpecRequest> plan() const = 0;
+  // ... where the plan depends on what the columns hold (column_types: tgx_type of columns() in order; 0 = unknown).
+  // MutualInformationAnalyzer with "max_pairs" plans TGX_CHECK_PAIR_COUNTS when a column is a string one.  Throws
+  // AnalyzerError for a column the analyzer refuses before the device sees it.
+  // `declared`: the columns' Arrow DataType names where the caller holds them (Table::arrow_types), else empty strings.
+  virtual std::vector<SpecRequest> plan_for(const std::vector<int> & /*column_types*/,
+                                            const std::vector<std::string> & /*declared*/) const {
+    return plan();
+  }
+  // the state of an analyzer whose request is a TGX_CHECK_PAIR_COUNTS one, from the pairs the device counted
+  virtual json::Value state_from_pair_counts(const PairCounts &) const { return json::Value(); }
   // compute_state_from_data's second half: aggregates (answering plan() in order) -> state (serde field names).
   // column_types: tgx_type of columns() in order (the reference's downcasts depend on the SQL result type).
   virtual json::Value state_from_results(const std::vector<const tgx_result *> &r,

@@ -469,3 +469,98 @@ extern "C" tgx_status tgx_host_metric_from_state_json(const char *analyzer_json,
     return hfail(err, TGX_INTERNAL, "unknown C++ exception");
   }
 }
+
+extern "C" tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *column_types_json,
+                                                  char **out_json, tgx_error *err) {
+  if (!analyzer_json || !column_types_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto a = analyzer_from_json(parse_json_text(analyzer_json, "analyzer"));
+    json::Value types = parse_json_text(column_types_json, "column types");
+    if (types.type != json::Value::Array) return hfail(err, TGX_INVALID_ARGUMENT, "column types must be a JSON array");
+    std::vector<int> column_types;
+    for (const json::Value &t : types.arr) column_types.push_back((int)t.as_u64());
+    std::string o = "{\"requests\": [";
+    const std::vector<SpecRequest> reqs = a->plan_for(column_types, std::vector<std::string>());
+    for (size_t i = 0; i < reqs.size(); i++) {
+      const SpecRequest &r = reqs[i];
+      o += std::string(i ? ", " : "") + "{\"kind\": " + std::to_string(r.kind) + ", \"column\": " + json::quote(r.column) +
+           ", \"column2\": " + json::quote(r.column2);
+      if (r.pair_counts)
+        o += ", \"pair_counts\": {\"max_pairs\": " + std::to_string(r.pair_counts->max_pairs) + ", \"max_value_bytes\": " +
+             std::to_string(r.pair_counts->max_value_bytes) + ", \"x_mode\": " + std::to_string(r.pair_counts->x.mode) +
+             ", \"y_mode\": " + std::to_string(r.pair_counts->y.mode) + "}";
+      o += "}";
+    }
+    o += "]}";
+    *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const AnalyzerError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.text);
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json, const char *pair_counts_json,
+                                                      char **out_state_json, tgx_error *err) {
+  if (!analyzer_json || !pair_counts_json || !out_state_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_state_json = nullptr;
+  try {
+    auto a = analyzer_from_json(parse_json_text(analyzer_json, "analyzer"));
+    json::Value v = parse_json_text(pair_counts_json, "pair counts");
+    PairCounts pc;
+    if (const json::Value *s = v.get("summary")) {
+      pc.summary.seen = s->get_u64("seen", 0);
+      pc.summary.both_non_null = s->get_u64("both_non_null", 0);
+      pc.summary.distinct = s->get_u64("distinct", 0);
+      pc.summary.counted = s->get_u64("counted", 0);
+      pc.summary.overflow_rows = s->get_u64("overflow_rows", 0);
+      pc.summary.long_rows = s->get_u64("long_rows", 0);
+      pc.summary.non_finite = s->get_u64("non_finite", 0);
+      pc.summary.out_of_range = s->get_u64("out_of_range", 0);
+    }
+    if (const json::Value *es = v.get("entries")) {
+      if (es->type != json::Value::Array) return hfail(err, TGX_INVALID_ARGUMENT, "entries must be a JSON array");
+      for (const json::Value &e : es->arr) {
+        if (e.type != json::Value::Array || e.arr.size() != 3)
+          return hfail(err, TGX_INVALID_ARGUMENT, "an entry is [x, y, count]");
+        PairCounts::Entry o;
+        for (int side = 0; side < 2; side++) {
+          PairCell &c = side ? o.y : o.x;
+          const json::Value &j = e.arr[side];
+          if (j.type == json::Value::String) {
+            c.bytes = j.str;
+          } else if (j.type == json::Value::Array) {
+            for (const json::Value &b : j.arr) c.bytes += (char)(unsigned char)b.as_u64();
+          } else if (j.type == json::Value::Number) {
+            c.binned = true;
+            c.bin = (int64_t)j.as_u64();
+          } else {
+            return hfail(err, TGX_INVALID_ARGUMENT, "a cell is a string, an array of bytes or a bin index");
+          }
+        }
+        o.count = e.arr[2].as_u64();
+        pc.entries.push_back(std::move(o));
+      }
+    }
+    *out_state_json = dup_string(json_dump(a->state_from_pair_counts(pc)));
+    return TGX_OK;
+  } catch (const AnalyzerError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.text);
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}

@@ -180,13 +180,16 @@ struct SpecRequest {
                                                 // (`column2`: the group column, or empty)
   std::optional<tgx_value_rule_params> value_rule;  // VALUE_RULE: the rule as the device takes it (host/datatype.h)
   std::optional<tgx_value_counts_params> value_counts;  // VALUE_COUNTS: the bounds (host/value_counts.h)
+  std::optional<tgx_pair_counts_params> pair_counts;    // PAIR_COUNTS: the bounds and the sides (host/analyzers.cpp)
   // do two requests ask the device for the same thing (what the runners' fusing compares beside kind and columns)?
   bool same_parameters(const SpecRequest &o) const {
     return value_rule.has_value() == o.value_rule.has_value() &&
            (!value_rule || memcmp(&*value_rule, &*o.value_rule, sizeof(tgx_value_rule_params)) == 0) &&
            value_counts.has_value() == o.value_counts.has_value() &&
            (!value_counts || (value_counts->max_distinct == o.value_counts->max_distinct &&
-                              value_counts->max_value_bytes == o.value_counts->max_value_bytes));
+                              value_counts->max_value_bytes == o.value_counts->max_value_bytes)) &&
+           pair_counts.has_value() == o.pair_counts.has_value() &&
+           (!pair_counts || memcmp(&*pair_counts, &*o.pair_counts, sizeof(tgx_pair_counts_params)) == 0);
   }
 };
 struct ValueCounts;  // host/value_counts.h

@@ -195,7 +195,7 @@ struct KllTask {
   int column;
   uint32_t k;
 };
-// The five kinds of side_check.h.
+// The six kinds of side_check.h.
 // TGX_CHECK_JOINT_BINS (jointbins_device.cpp): one task per spec; `binned` once tgx_plan_set_joint_binning was called
 struct JointTask {
   int col_x, col_y;
@@ -233,8 +233,15 @@ struct ValueCountsTask {
   tgx_value_counts_params params;
 };
 
+// TGX_CHECK_PAIR_COUNTS (paircounts_device.cpp): one task per spec; `set` once tgx_plan_set_pair_counts was called
+struct PairCountsTask {
+  int col_x, col_y, spec_index;
+  bool set;
+  tgx_pair_counts_params params;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 5;  // JOINT_BINS, TEMPORAL, HISTOGRAM, VALUE_RULE, VALUE_COUNTS
+constexpr int kNumSide = 6;  // JOINT_BINS, TEMPORAL, HISTOGRAM, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS
 
 enum class Source { kScan, kCount };
 
@@ -261,6 +268,7 @@ struct tgx_plan {
   std::vector<tgx::HistTask> hist;
   std::vector<tgx::ValueRuleTask> rules;
   std::vector<tgx::ValueCountsTask> value_counts;
+  std::vector<tgx::PairCountsTask> pair_counts;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
@@ -270,6 +278,7 @@ struct tgx_plan {
   std::vector<char> hist_on;     // a HISTOGRAM check reads it (numeric columns only, as JOINT_BINS)
   std::vector<char> rule_on;     // a VALUE_RULE check reads it (numeric columns, Boolean and UInt64 excepted)
   std::vector<char> counts_on;   // a VALUE_COUNTS check reads it (integer columns below UInt64, and every string layout)
+  std::vector<char> pairs_on;    // a PAIR_COUNTS check reads it (a string layout or a numeric column, by the side's mode)
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
   // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
@@ -672,7 +681,7 @@ struct tgx_state {
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
   void *timegap = nullptr;   // tgx::TimeGapState (timegap_device.cpp)
   // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms,
-  // value rules, value counts
+  // value rules, value counts, pair counts
   std::unique_ptr<tgx::SideCheck> side[tgx::kNumSide];
 
   tgx::Coalescer coalesce;
@@ -711,7 +720,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE and VALUE_COUNTS parameters -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS and PAIR_COUNTS parameters -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

@@ -14,6 +14,10 @@
 
 namespace tgx {
 
+// the bin index of the equal-width binnings (jointbins.hip, paircounts.hip): the reference's expression, in IEEE double
+// arithmetic as written -- subtract, divide (correctly rounded), floor; NaN for a NaN
+__device__ __forceinline__ double bin_index(double v, double origin, double width) { return floor((v - origin) / width); }
+
 // cell `cell` += 1 for every live lane.  Equal cells are combined within the wave: the cell of the wave's first live
 // lane is broadcast, the lanes that hold the same cell are counted with a ballot and their leader adds the count; only
 // the lanes with another cell add for themselves.

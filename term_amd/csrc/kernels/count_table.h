@@ -1,0 +1,86 @@
+// count_table.h -- the open-addressing table primitive of the bounded GROUP BY kernels (valuecounts.hip, paircounts.hip):
+// a slot is claimed by CAS on its key word; a 128-bit key (two fingerprint words) claims the first word by CAS and then
+// settles the second by CAS: the slot is the key's when both come back free or equal, otherwise probing goes on.  Used in
+// LDS per workgroup with 32-bit counts (a workgroup sees fewer than 2^32 rows: side_rows_fit) and in global memory per
+// task with 64-bit counts.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_types.h"
+#include "distinct_types.h"
+#include "keyset_device.h"
+
+namespace tgx {
+
+__device__ __forceinline__ unsigned long long vc_peek(const unsigned long long *word) {
+  return __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// probes from slot `h` for `key`: the slot that holds it, claimed if need be, or -1 when `probes` slots held other keys
+template <class Slot>
+__device__ __forceinline__ int64_t vc_claim(unsigned long long *keys, Slot mask, Slot h, unsigned long long key,
+                                            uint32_t probes) {
+  for (uint32_t p = 0; p < probes; p++) {
+    // (a key word never changes once it is set: a plain look spares the hot keys their CAS)
+    unsigned long long old = vc_peek(&keys[h]);
+    if (old == kEmptyKey) old = atomicCAS(&keys[h], (unsigned long long)kEmptyKey, key);
+    if (old == kEmptyKey || old == key) return (int64_t)h;
+    h = (h + 1) & mask;
+  }
+  return -1;
+}
+
+// the workgroup's table of 128-bit keys: the two fingerprint words, a 32-bit count and a row that holds the key's value
+struct VcLdsStrings {
+  unsigned long long fa[kValueCountsStrLdsSlots], fb[kValueCountsStrLdsSlots], row[kValueCountsStrLdsSlots];
+  unsigned int count[kValueCountsStrLdsSlots];
+};
+// false: the slots around the key's place hold other keys
+__device__ __forceinline__ bool vc_insert_lds128(VcLdsStrings &l, unsigned long long fa, unsigned long long fb,
+                                                 uint32_t weight, unsigned long long row) {
+  uint32_t h = (uint32_t)fa & (kValueCountsStrLdsSlots - 1);
+  for (uint32_t probe = 0; probe < kValueCountsLdsProbes; probe++) {
+    unsigned long long a = vc_peek(&l.fa[h]);
+    if (a == kEmptyKey) a = atomicCAS(&l.fa[h], (unsigned long long)kEmptyKey, fa);
+    if (a == kEmptyKey || a == fa) {
+      unsigned long long b = vc_peek(&l.fb[h]);
+      const bool made = b == kEmptyKey && (b = atomicCAS(&l.fb[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
+      if (made) l.row[h] = row;  // (read after the workgroup's barrier)
+      if (made || b == fb) {
+        atomicAdd(&l.count[h], weight);
+        return true;
+      }
+    }
+    h = (h + 1) & (kValueCountsStrLdsSlots - 1);
+  }
+  return false;
+}
+
+// where the value of slot `slot` of a string column lies (the three layouts: int32 offsets, int64 offsets, views)
+__device__ __forceinline__ void utf8_value_of(const Utf8ColDesc &d, int64_t slot, uintptr_t *p, uint64_t *len) {
+  if (d.views) {
+    global_i32_ptr vw = (global_i32_ptr)((uintptr_t)d.views + (uintptr_t)slot * 16);
+    const int32_t n = vw[0];
+    *len = (uint64_t)(uint32_t)n;
+    if (n <= 12) *p = (uintptr_t)d.views + (uintptr_t)slot * 16 + 4;
+    else *p = (uintptr_t)d.buffers[vw[2]] + (uintptr_t)(uint32_t)vw[3];
+  } else if (d.large_offsets) {
+    global_i64_ptr off = (global_i64_ptr)(uintptr_t)d.offsets;
+    const int64_t b = off[slot];
+    *p = (uintptr_t)d.data + (uintptr_t)b;
+    *len = (uint64_t)(off[slot + 1] - b);
+  } else {
+    global_i32_ptr off = (global_i32_ptr)(uintptr_t)d.offsets;
+    const int32_t b = off[slot];
+    *p = (uintptr_t)d.data + (uintptr_t)b;
+    *len = (uint64_t)(off[slot + 1] - b);
+  }
+}
+
+__device__ __forceinline__ unsigned long long vc_shfl64(unsigned long long v, int lane) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+}  // namespace tgx

@@ -246,6 +246,52 @@ struct ValueCountsTable {
   uint32_t pad;
 };
 
+// Pair counts of two columns (kernels/paircounts.hip; TGX_CHECK_PAIR_COUNTS): a bounded GROUP BY x, y.  A side is a
+// string column (the cell is the value's bytes) or a numeric one (the cell is its bin index).  A task's running state in
+// its count phase is one open-addressing table of `mask + 1` slots (a power of two >= 2 * max_pairs) in one allocation,
+// keyed by the pair's fingerprint (keys / keys2), plus kPairCountsWords 64-bit counters; per slot and side a 32-bit
+// word (a string side: the value's length; a binned side: its bin index) and, for a string side, the value's bytes at
+// store + slot * max_value_bytes, written by the lane that claimed the slot.  In its range phase it is a PairRangeAcc.
+// (the counters are flushed in pairs, bin_count.h's tail_flush: both | long, non-finite | out of range)
+enum { kPcBoth = 0, kPcLong = 1, kPcNonFinite = 2, kPcOutOfRange = 3, kPcOverflow = 4, kPairCountsWords = 5 };
+enum { kPairSideValue = 0, kPairSideRange = 1, kPairSideBinned = 2 };  // (TGX_PAIR_SIDE_*)
+constexpr int kPairCountsBlock = 256;         // 4 waves share one LDS table of kValueCountsStrLdsSlots slots (28 KiB)
+constexpr int64_t kPairCountsRowsPerLane = 16;  // rows a lane takes before another workgroup is worth its flush
+constexpr int kPairCountsMaxBlocks = 2048;
+// one side of a pair as the kernels see it
+struct PairSide {
+  const uint8_t *validity;  // the rows' bitmap or nullptr
+  int64_t offset;           // the rows' Arrow offset
+  const void *values;       // numeric side: 8-byte values (Int64 / Float64 after the widening staging)
+  const int32_t *indices;   // dictionary side: the rows' indices into `str` (then `str` is the dictionary)
+  const void *str_offsets;  // string side: the layout of utf8_value_of (Utf8ColDesc), of the column or its dictionary
+  const uint8_t *str_data;
+  const void *str_views;
+  const uint8_t *const *str_buffers;
+  const uint8_t *dict_validity;  // dictionary side: a NULL entry makes the row a NULL row
+  int64_t dict_offset, dict_length;
+  double origin, width;  // binned side
+  uint32_t bins;
+  int32_t mode;          // kPairSide*
+  int32_t is_float;      // numeric side
+  int32_t large_offsets;
+};
+struct PairCountsTable {
+  unsigned long long *keys, *keys2, *counts;
+  uint32_t *cell[2];  // per side: length or bin index
+  uint8_t *store[2];  // per string side: the bytes
+  unsigned long long *words;  // kPairCountsWords counters
+  uint64_t mask;
+  uint32_t max_value_bytes;
+  uint32_t pad;
+};
+// range phase: the numeric side over the rows with both sides non-NULL; the extremes as IEEE totalOrder keys
+// (f64_total_key: signed order), so that every word is folded with one 64-bit vector atomic
+struct PairRangeAcc {
+  long long both, n, non_finite;
+  long long min_key, max_key;  // identities: INT64_MAX / INT64_MIN
+};
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

@@ -81,9 +81,8 @@ __global__ __launch_bounds__(kJointBlock) void joint_bins_kernel(const JointLaun
     const double b = d.y_is_float ? __longlong_as_double(yb) : (double)yb;
     const bool finite = a - a == 0.0 && b - b == 0.0;
     non_finite += ok && !finite ? 1u : 0u;
-    // the reference's expression, in IEEE double arithmetic as written: subtract, divide (correctly rounded), floor
-    const double fi = floor((a - B.x_origin) / B.x_width);
-    const double fj = floor((b - B.y_origin) / B.y_width);
+    const double fi = bin_index(a, B.x_origin, B.x_width);
+    const double fj = bin_index(b, B.y_origin, B.y_width);
     const bool inside = fi >= 0.0 && fi <= top && fj >= 0.0 && fj <= top;  // (false for NaN)
     outside += ok && finite && !inside ? 1u : 0u;
     const bool live = ok && finite && inside;

@@ -1,14 +1,15 @@
 // side_check.h -- the check kinds that run beside the fused pass and share one shape: TGX_CHECK_JOINT_BINS
 // (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp), TGX_CHECK_HISTOGRAM (histogram_device.cpp),
-// TGX_CHECK_VALUE_RULE (valuerule_device.cpp) and TGX_CHECK_VALUE_COUNTS (valuecounts_device.cpp).
+// TGX_CHECK_VALUE_RULE (valuerule_device.cpp), TGX_CHECK_VALUE_COUNTS (valuecounts_device.cpp) and TGX_CHECK_PAIR_COUNTS
+// (paircounts_device.cpp).
 //
 // A task is one spec.  Its running state is a few 64-bit counters on the device, plus a small range accumulator for the
 // kinds that have a range phase; rows seen are counted on the host.  What is merged in from other states or read from a
 // blob is kept on the host (`host`) and added when the state is read (`gather`).  The rest of the library sees a
 // SideCheck per kind in tgx_state::side, in the order of the blob's sections (null: the plan has no task of the kind);
 // SideState<K> is everything the kinds have in common, a kind K adds what its tasks count and how they are launched.
-// A kind whose tasks keep more on the device than counters (VALUE_COUNTS: a table per task, and a host part of variable
-// size) clears and reads that through device_clear_extra / gather_extra; the other kinds leave both alone.
+// A kind whose tasks keep more on the device than counters (VALUE_COUNTS, PAIR_COUNTS: a table per task, and a host part
+// of variable size) clears and reads that through device_clear_extra / gather_extra; the other kinds leave both alone.
 #pragma once
 #include <memory>
 
@@ -17,13 +18,14 @@
 
 namespace tgx {
 
-enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3, kSideCounts = 4 };  // (kNumSide: internal.h)
+enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3, kSideCounts = 4, kSidePairs = 5 };  // (kNumSide: internal.h)
 TGX_HIDDEN inline int side_index(int kind) {
   return kind == TGX_CHECK_JOINT_BINS ? kSideJoint
          : kind == TGX_CHECK_TEMPORAL ? kSideTemporal
          : kind == TGX_CHECK_HISTOGRAM ? kSideHist
          : kind == TGX_CHECK_VALUE_RULE ? kSideRule
-                                        : kSideCounts;
+         : kind == TGX_CHECK_VALUE_COUNTS ? kSideCounts
+                                          : kSidePairs;
 }
 
 struct TGX_HIDDEN SideCheck {
@@ -44,22 +46,28 @@ tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_erro
 tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status valuerule_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
 tgx_status valuecounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule, tgx_plan_set_value_counts)?  Asked by
-// tgx_state_create
+tgx_status paircounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule, tgx_plan_set_value_counts,
+// tgx_plan_set_pair_counts)?  Asked by tgx_state_create
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 // may a column of tgx_type `type` feed a VALUE_COUNTS check?  Asked by tgx_update of column `column`
 tgx_status valuecounts_check_type(int column, int type, tgx_error *err);
+tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
+// may column `column` of a batch feed the PAIR_COUNTS checks that read it (each side's mode against the column's type)?
+tgx_status paircounts_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err);
 TGX_HIDDEN SideCheck *joint_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *temporal_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *hist_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *valuerule_state_new(const tgx_plan *plan);
 TGX_HIDDEN SideCheck *valuecounts_state_new(const tgx_plan *plan);
+TGX_HIDDEN SideCheck *paircounts_state_new(const tgx_plan *plan);
 // the fresh state of the plan's tasks of kind `index`, or null when it has none
 TGX_HIDDEN inline SideCheck *side_state_new(int index, const tgx_plan *plan) {
   SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new,
-                                                          valuerule_state_new, valuecounts_state_new};
+                                                          valuerule_state_new, valuecounts_state_new,
+                                                          paircounts_state_new};
   return make[index](plan);
 }
 

@@ -305,12 +305,14 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       case TGX_CHECK_TEMPORAL:
       case TGX_CHECK_HISTOGRAM:
       case TGX_CHECK_VALUE_RULE:
-      case TGX_CHECK_VALUE_COUNTS: {  // the kinds of side_check.h, in its order
+      case TGX_CHECK_VALUE_COUNTS:
+      case TGX_CHECK_PAIR_COUNTS: {  // the kinds of side_check.h, in its order
         tgx_status (*const add[kNumSide])(tgx_plan *, int, int *, tgx_error *) = {
-            joint_plan_add, temporal_plan_add, hist_plan_add, valuerule_plan_add, valuecounts_plan_add};
+            joint_plan_add, temporal_plan_add, hist_plan_add, valuerule_plan_add, valuecounts_plan_add,
+            paircounts_plan_add};
         int slot = -1;
         TGX_TRY(add[side_index(sp.kind)](plan.get(), (int)i, &slot, err));
-        if (sp.kind == TGX_CHECK_JOINT_BINS || sp.kind == TGX_CHECK_TEMPORAL) max_col = std::max(max_col, sp.column2);
+        if (sp.kind == TGX_CHECK_JOINT_BINS || sp.kind == TGX_CHECK_TEMPORAL || sp.kind == TGX_CHECK_PAIR_COUNTS) max_col = std::max(max_col, sp.column2);
         plan->bind[i].slot = slot;
         break;
       }
@@ -381,6 +383,7 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     P->hist_on.assign(P->n_columns_needed, 0);
     P->rule_on.assign(P->n_columns_needed, 0);
     P->counts_on.assign(P->n_columns_needed, 0);
+    P->pairs_on.assign(P->n_columns_needed, 0);
     for (auto &t : P->distinct)
       if (t.tuple.empty() && !t.approx_only) P->key_column[t.column] = 1;
     // (by what was ASKED: a key column has a scan task of its own for the range decisions of its key set)
@@ -414,6 +417,8 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->rule_on[t.column] = 1;
     for (auto &t : P->value_counts)
       P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->counts_on[t.column] = 1;
+    for (auto &t : P->pair_counts)
+      for (int c : {t.col_x, t.col_y}) P->used[c] = P->reads_values[c] = P->needs_wide[c] = P->pairs_on[c] = 1;
     regex_mark_used(P, P->used);
     std::vector<char> sp_used(P->n_columns_needed, 0), sp_vals(P->n_columns_needed, 0);
     spearman_mark_used(P, sp_used, sp_vals);
@@ -620,6 +625,7 @@ extern "C" tgx_status tgx_state_create(const tgx_plan *plan, void *hip_stream, t
   TGX_TRY(temporal_plan_ready(plan, err));  // (before the plan is locked: the parameters can still follow)
   TGX_TRY(valuerule_plan_ready(plan, err));
   TGX_TRY(valuecounts_plan_ready(plan, err));
+  TGX_TRY(paircounts_plan_ready(plan, err));
   TGX_TRY(timegap_plan_ready(plan, err));
   tgx_state *st = new tgx_state();
   state_init_host(st, plan);
@@ -1134,6 +1140,7 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
       case TGX_CHECK_HISTOGRAM:
       case TGX_CHECK_VALUE_RULE:
       case TGX_CHECK_VALUE_COUNTS:
+      case TGX_CHECK_PAIR_COUNTS:
         TGX_TRY(st->side[side_index(b.kind)]->fill_result(st, b.slot, r, err));
         break;
       case TGX_CHECK_TIME_GAP:

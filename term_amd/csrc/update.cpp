@@ -261,6 +261,7 @@ tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column
     if (plan->rule_on[i] && !is_numeric(c.type) && !(is_widened(c.type) && c.type != TGX_BOOL))
       return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_RULE takes numeric columns other than UInt64 (type %d)", i, c.type);
     if (plan->counts_on[i]) TGX_TRY(valuecounts_check_type(i, c.type, err));
+    if (plan->pairs_on[i]) TGX_TRY(paircounts_check_column(plan, i, c, err));
     if (plan->timegap_on[i]) TGX_TRY(timegap_check_type(plan, i, c.type, err));
     if (c.mem != TGX_MEM_HOST && c.mem != TGX_MEM_DEVICE)
       return fail(err, TGX_INVALID_ARGUMENT, "column %d: unknown memory space %d", i, c.mem);

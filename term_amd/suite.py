@@ -887,6 +887,26 @@ class _Analyzer:
                                                        C.byref(out), C.byref(err)), err)
         return _take(out)
 
+    def planned_requests(self, column_types):
+        """what the analyzer plans for columns of the given tgx_types (parallel to its columns): a list of dicts with
+        kind, column, column2 and, for a PAIR_COUNTS request, pair_counts"""
+        out = C.c_char_p()
+        err = _Error()
+        _host_check(_host().tgx_host_analyzer_plan_json(json.dumps(self.spec).encode(), json.dumps(list(column_types)).encode(),
+                                                        C.byref(out), C.byref(err)), err)
+        return json.loads(_take(out))["requests"]
+
+    def state_text_from_pair_counts(self, summary, entries):
+        """the state (the bytes the library wrote) a mutual_information analyzer builds from given pair counts: `entries`
+        is a list of (x, y, count) in the library's order, a cell being str / bytes (a value) or int (a bin)"""
+        cell = lambda c: list(c) if isinstance(c, (bytes, bytearray)) else c  # noqa: E731
+        doc = {"summary": summary, "entries": [[cell(x), cell(y), n] for x, y, n in entries]}
+        out = C.c_char_p()
+        err = _Error()
+        _host_check(_host().tgx_host_pair_counts_state_json(json.dumps(self.spec).encode(), json.dumps(doc).encode(),
+                                                            C.byref(out), C.byref(err)), err)
+        return _take(out)
+
     def compute_metric_from_state(self, state):
         """-> MetricValue as {"type": "Double"|"Long"|"Map", "value": ...}; raises TgxError with the
         reference's AnalyzerError text (e.g. 'No data available for analysis')"""
@@ -912,10 +932,23 @@ def CorrelationAnalyzer(column1, column2, method="pearson"):
     return _Analyzer({"type": "correlation", "column1": column1, "column2": column2, "method": method})
 
 
-def MutualInformationAnalyzer(column1, column2, bins=10):
+def MutualInformationAnalyzer(column1, column2, bins=10, max_pairs=None, max_value_bytes=None, arrow_types=None):
     """TG/analyzers/advanced/mutual_information.rs, numeric x numeric pairs: two passes on the device (the range of
-    both columns, then the joint bin counts); `bins` = max(bins, 2), at most JOINT_MAX_BINS (include/tgx.h)"""
-    return _Analyzer({"type": "mutual_information", "column1": column1, "column2": column2, "bins": max(int(bins), 2)})
+    both columns, then the joint bin counts); `bins` = max(bins, 2), at most JOINT_MAX_BINS (include/tgx.h).
+    `max_pairs` opts into the reference's three categorical branches (TGX_CHECK_PAIR_COUNTS): with it a pair with at
+    least one string column is counted by (value, value) or (bin, value) -- string x string in one pass, a mixed pair in
+    two -- for up to max_pairs distinct pairs of values of up to `max_value_bytes` (default 256) bytes; beyond the
+    bounds, for a column declared binary and for a string value that may parse as a number (the reference would bin
+    such a column) the analyzer fails with its own error.  Without it the analyzer does what it always did.
+    `arrow_types`: the two columns' Arrow DataTypes where the table is not a pyarrow one"""
+    spec = {"type": "mutual_information", "column1": column1, "column2": column2, "bins": max(int(bins), 2)}
+    if max_pairs is not None:
+        spec["max_pairs"] = int(max_pairs)
+        if max_value_bytes is not None:
+            spec["max_value_bytes"] = int(max_value_bytes)
+    if arrow_types is not None:
+        spec["arrow_types"] = list(arrow_types)
+    return _Analyzer(spec)
 
 
 def HistogramAnalyzer(column, num_buckets=10, strict_reference_types=True):
@@ -985,6 +1018,8 @@ class AnalysisRunner:
         declared = _arrow_type_names(table)  # (analyzers that read a column's values as text need its Arrow type)
         specs = [dict(a.spec, arrow_type=declared[a.spec["column"]])
                  if a.spec["type"] == "value_entropy" and "arrow_type" not in a.spec and a.spec["column"] in declared
+                 else dict(a.spec, arrow_types=[declared.get(a.spec["column1"], ""), declared.get(a.spec["column2"], "")])
+                 if a.spec["type"] == "mutual_information" and "max_pairs" in a.spec and "arrow_types" not in a.spec
                  else a.spec for a in self._analyzers]
         spec = {"table_name": self._table, "continue_on_error": self._continue, "analyzers": specs}
         name_arr, n_cols, col_arr, n_batches, _keep = _flatten_table(table)
@@ -1016,6 +1051,8 @@ def _host():
                                                  C.c_size_t, C.POINTER(C.c_char_p), E]
         L.tgx_host_merge_states_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_metric_from_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_analyzer_plan_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_pair_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_free.argtypes = [C.c_void_p]
         L.tgx_host_free.restype = None
         _HOST = L

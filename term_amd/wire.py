@@ -54,6 +54,24 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                              or { u32 length; u8 bytes[length]; u64 count } } kind 2, ascending bytewise
                                every count > 0, every length <= max_value_bytes, no value twice, and
                                sum(counts) + overflow_rows + long_rows == non_null <= seen.
+    and ONLY for plans with PAIR_COUNTS checks, behind the VALUE_COUNTS section if there is one:
+    u32 magic 'PCNT', u32 n_tasks
+    n_tasks     x { u32 max_pairs, max_value_bytes                   (the plan's parameters: a blob counted under other
+                    2 x { i32 mode, u32 bins, f64 origin, width }     ones is refused, binnings compared by their bits;
+                                                                      mode 0 value, 1 range, 2 binned; what a mode does
+                                                                      not read is zero)
+                    u64 seen, both_non_null, overflow_rows, long_rows, non_finite, out_of_range
+                    u64 n, f64 min, max                               the range phase (a side of mode 1): the numeric
+                                                                      side over the rows with both sides non-NULL;
+                                                                      n + non_finite == both_non_null, no entries;
+                                                                      min / max are +inf / -inf while n is 0, and n is 0
+                                                                      in a count phase
+                    u64 n_entries
+                    n_entries x { per side { u32 length; u8 bytes[length] }   a value side
+                                        or { i64 bin }                        a binned side, 0 <= bin <= bins
+                                  u64 count } }                      ascending by (x cell, y cell): bytewise, bins as ints
+                               every count > 0, every length <= max_value_bytes, no pair twice, and
+                               sum(counts) + overflow_rows + long_rows + non_finite + out_of_range == both_non_null <= seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -66,6 +84,7 @@ TEMPORAL_MAGIC = 0x52504D54  # 'TMPR'
 HIST_MAGIC = 0x54534948  # 'HIST'
 VALUE_RULE_MAGIC = 0x4C525656  # 'VVRL'
 VALUE_COUNTS_MAGIC = 0x544E4356  # 'VCNT'
+PAIR_COUNTS_MAGIC = 0x544E4350  # 'PCNT'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -194,8 +213,34 @@ def value_counts_state(max_distinct, max_value_bytes, seen, counts, nulls=0, ove
     return out
 
 
+def pair_side(mode=0, bins=0, origin=0.0, width=0.0):
+    """one side of a PAIR_COUNTS task's parameters: mode 0 value, 1 range, 2 binned"""
+    return struct.pack("<iI2d", mode, bins, origin, width)
+
+
+def pair_counts_state(max_pairs, max_value_bytes, x_side, y_side, seen, counts=(), both_non_null=None, overflow_rows=0,
+                      long_rows=0, non_finite=0, out_of_range=0, n=0, lo=float("inf"), hi=float("-inf"), ordered=True):
+    """a PAIR_COUNTS task: the plan's parameters (x_side / y_side from pair_side), the counters and the entries of
+    `counts` ((x cell, y cell) -> count; a cell is bytes on a value side and an int on a binned side).  both_non_null
+    defaults to what the invariant makes it.  n / lo / hi: the range phase.  `ordered=False` keeps the entries in the
+    order given (for a blob that is to be refused)."""
+    items = list(counts.items()) if hasattr(counts, "items") else list(counts)
+    if ordered:
+        items.sort(key=lambda kv: kv[0])
+    if both_non_null is None:
+        both_non_null = sum(c for _, c in items) + overflow_rows + long_rows + non_finite + out_of_range + n
+    out = struct.pack("<2I", max_pairs, max_value_bytes) + x_side + y_side
+    out += struct.pack("<7Q2dQ", seen, both_non_null, overflow_rows, long_rows, non_finite, out_of_range, n, lo, hi,
+                       len(items))
+    for (cx, cy), c in items:
+        for cell in (cx, cy):
+            out += struct.pack("<q", cell) if isinstance(cell, int) else struct.pack("<I", len(cell)) + bytes(cell)
+        out += struct.pack("<Q", c)
+    return out
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=(), value_counts=()):
+         value_rules=(), value_counts=(), pair_counts=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -208,5 +253,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", VALUE_RULE_MAGIC, len(value_rules)) + b"".join(value_rules)
     if value_counts:
         tail += struct.pack("<II", VALUE_COUNTS_MAGIC, len(value_counts)) + b"".join(value_counts)
+    if pair_counts:
+        tail += struct.pack("<II", PAIR_COUNTS_MAGIC, len(pair_counts)) + b"".join(pair_counts)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
