@@ -953,6 +953,18 @@ class State:
         _check(lib().tgx_value_rule_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.considered, out.valid, out.cast_errors
 
+    def _counted_entries(self, call, entry_type, spec_index, *more):
+        """the two calls of a *_entries function: ask for the sizes, allocate, fetch; (the entries, the bytes their
+        offsets point into).  `more`: the call's arguments between n_bytes and the error"""
+        err = _Error()
+        n, nb = C.c_uint64(), C.c_uint64()
+        _check(call(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, 0, C.byref(nb), *more, C.byref(err)), err)
+        entries = (entry_type * max(n.value, 1))()
+        buf = (C.c_uint8 * max(nb.value, 1))()
+        _check(call(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), buf, nb.value, C.byref(nb), *more,
+                    C.byref(err)), err)
+        return entries[:n.value], bytes(buf)
+
     # value counts
     def value_counts(self, spec_index):
         """tgx_value_counts_get + tgx_value_counts_entries: (summary, counts) -- summary a dict of the six counters
@@ -961,16 +973,10 @@ class State:
         L, err = lib(), _Error()
         s = ValueCountsSummary()
         _check(L.tgx_value_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
-        n, nb, is_bytes = C.c_uint64(), C.c_uint64(), C.c_int32()
-        _check(L.tgx_value_counts_entries(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, 0, C.byref(nb),
-                                          C.byref(is_bytes), C.byref(err)), err)
-        entries = (ValueCountEntry * max(n.value, 1))()
-        buf = (C.c_uint8 * max(nb.value, 1))()
-        _check(L.tgx_value_counts_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), buf, nb.value,
-                                          C.byref(nb), C.byref(is_bytes), C.byref(err)), err)
-        raw = bytes(buf)
+        is_bytes = C.c_int32()
+        entries, raw = self._counted_entries(L.tgx_value_counts_entries, ValueCountEntry, spec_index, C.byref(is_bytes))
         counts = {}
-        for e in entries[:n.value]:
+        for e in entries:
             counts[raw[e.offset:e.offset + e.length] if is_bytes.value else e.value] = e.count
         summary = {f: getattr(s, f) for f, _ in ValueCountsSummary._fields_}
         return summary, counts
@@ -984,17 +990,10 @@ class State:
         L, err = lib(), _Error()
         s = PairCountsSummary()
         _check(L.tgx_pair_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
-        n, nb = C.c_uint64(), C.c_uint64()
-        _check(L.tgx_pair_counts_entries(self.plan.h, self.h, spec_index, None, 0, C.byref(n), None, 0, C.byref(nb),
-                                         C.byref(err)), err)
-        entries = (PairCountEntry * max(n.value, 1))()
-        buf = (C.c_uint8 * max(nb.value, 1))()
-        _check(L.tgx_pair_counts_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), buf, nb.value,
-                                         C.byref(nb), C.byref(err)), err)
-        raw = bytes(buf)
+        entries, raw = self._counted_entries(L.tgx_pair_counts_entries, PairCountEntry, spec_index)
         mx, my = self.plan.pair_sides.get(spec_index, (PAIR_SIDE_VALUE, PAIR_SIDE_VALUE))
         counts = {}
-        for e in entries[:n.value]:
+        for e in entries:
             cx = raw[e.x_offset:e.x_offset + e.x_length] if mx == PAIR_SIDE_VALUE else e.x_bin
             cy = raw[e.y_offset:e.y_offset + e.y_length] if my == PAIR_SIDE_VALUE else e.y_bin
             counts[(cx, cy)] = e.count

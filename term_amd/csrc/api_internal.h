@@ -3,7 +3,7 @@
 // bookkeeping, export / import / adopt), merge.cpp (tgx_merge), coalesce.cpp (small batches noted and gathered, the copy
 // pool), wire.cpp (state blobs) and allreduce.cpp (the cross-rank step).  The helpers declared here are shared between
 // those files only (hidden visibility).  What the check modules (kll_device.cpp, regex_device.cpp, spearman_device.cpp
-// and the six kinds of side_check.h) need as well -- fail(), HIP_TRY / TGX_TRY, ProfScope, spec_slot -- is in
+// and the kinds registered in side_check.h) need as well -- fail(), HIP_TRY / TGX_TRY, ProfScope, spec_slot -- is in
 // internal.h; the blob's Writer / Reader are in wire_io.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -28,8 +28,8 @@ struct HistKind {
   typedef HistHost Host;
   typedef HistRangeAcc Range;
   static constexpr bool kRanged = true;
-  static constexpr int kIndex = kSideHist;
-  static constexpr const char *kName = "HISTOGRAM", *kDiffers = "edges";
+  static constexpr int kKind = TGX_CHECK_HISTOGRAM;
+  static constexpr const char *kDiffers = "edges";
   static constexpr uint32_t kMagic = 0x54534948;  // "HIST"
 
   static const std::vector<HistTask> &tasks(const tgx_plan *plan) { return plan->hist; }
@@ -211,6 +211,19 @@ tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *e
   t.column = plan->specs[spec_index].column;
   plan->hist.push_back(t);
   *slot = (int)plan->hist.size() - 1;
+  return TGX_OK;
+}
+
+void hist_mark_columns(tgx_plan *plan) {
+  for (const HistTask &t : plan->hist) {
+    side_mark(plan, HistCheck::kIndex, t.column, true);
+    plan->stats_on[t.column] = 1;
+  }
+}
+
+tgx_status hist_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  if (!is_numeric(c.type) && !is_widened(c.type))
+    return fail(err, TGX_UNSUPPORTED, "column %d: HISTOGRAM takes numeric columns (type %d)", column, c.type);
   return TGX_OK;
 }
 

@@ -195,7 +195,7 @@ struct KllTask {
   int column;
   uint32_t k;
 };
-// The six kinds of side_check.h.
+// The tasks of the kinds of side_check.h (registered there, in kSideKinds).
 // TGX_CHECK_JOINT_BINS (jointbins_device.cpp): one task per spec; `binned` once tgx_plan_set_joint_binning was called
 struct JointTask {
   int col_x, col_y;
@@ -241,7 +241,7 @@ struct PairCountsTask {
 };
 
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 6;  // JOINT_BINS, TEMPORAL, HISTOGRAM, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS
+constexpr int kNumSide = 6;  // the records of side_check.h's kSideKinds
 
 enum class Source { kScan, kCount };
 
@@ -273,12 +273,9 @@ struct tgx_plan {
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
   std::vector<char> key_column;  // a single-column DISTINCT check reads it (range tracking of coalesced HOST batches)
-  std::vector<char> joint_on;    // a JOINT_BINS check reads it (numeric columns only: strings are TGX_UNSUPPORTED)
-  std::vector<char> temporal_on; // a TEMPORAL check reads it (Int64-shaped columns only)
-  std::vector<char> hist_on;     // a HISTOGRAM check reads it (numeric columns only, as JOINT_BINS)
-  std::vector<char> rule_on;     // a VALUE_RULE check reads it (numeric columns, Boolean and UInt64 excepted)
-  std::vector<char> counts_on;   // a VALUE_COUNTS check reads it (integer columns below UInt64, and every string layout)
-  std::vector<char> pairs_on;    // a PAIR_COUNTS check reads it (a string layout or a numeric column, by the side's mode)
+  // a task of kind k of side_check.h reads it: side_on[k], k as in kSideKinds (which types the kind takes: its
+  // check_column)
+  std::vector<char> side_on[tgx::kNumSide];
   std::vector<char> stats_on;    // a statistic, sketch, correlation or ranking reads it (TGX_UINT64 / TGX_BOOL columns may not)
   // the key of the string / tuple fingerprints (kernels/fingerprint.h): drawn from the OS at tgx_plan_create, or set
   // by tgx_plan_set_fingerprint_key before the plan's first state exists
@@ -680,8 +677,7 @@ struct tgx_state {
   void *regex = nullptr;  // tgx::RegexState (regex_device.cpp)
   void *spearman = nullptr;  // tgx::SpearmanState (spearman_device.cpp)
   void *timegap = nullptr;   // tgx::TimeGapState (timegap_device.cpp)
-  // the tasks of the kinds of side_check.h, in the order of their blob sections: joint bins, temporal, histograms,
-  // value rules, value counts, pair counts
+  // the tasks of the kinds of side_check.h, in the order of kSideKinds (that of their blob sections)
   std::unique_ptr<tgx::SideCheck> side[tgx::kNumSide];
 
   tgx::Coalescer coalesce;

@@ -26,8 +26,8 @@ struct JointKind {
   typedef JointHost Host;
   typedef JointRangeAcc Range;
   static constexpr bool kRanged = true;
-  static constexpr int kIndex = kSideJoint;
-  static constexpr const char *kName = "JOINT_BINS", *kDiffers = "binnings";
+  static constexpr int kKind = TGX_CHECK_JOINT_BINS;
+  static constexpr const char *kDiffers = "binnings";
   static constexpr uint32_t kMagic = 0x42544e4a;  // "JNTB"
 
   static const std::vector<JointTask> &tasks(const tgx_plan *plan) { return plan->joint; }
@@ -187,6 +187,20 @@ tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *
   t.col_y = sp.column2;
   plan->joint.push_back(t);
   *slot = (int)plan->joint.size() - 1;
+  return TGX_OK;
+}
+
+void joint_mark_columns(tgx_plan *plan) {
+  for (const JointTask &t : plan->joint)
+    for (int c : {t.col_x, t.col_y}) {
+      side_mark(plan, JointCheck::kIndex, c, true);
+      plan->stats_on[c] = 1;
+    }
+}
+
+tgx_status joint_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  if (!is_numeric(c.type) && !is_widened(c.type))
+    return fail(err, TGX_UNSUPPORTED, "column %d: JOINT_BINS takes numeric columns (type %d)", column, c.type);
   return TGX_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "api_internal.h"
+#include "counted_state.h"
 
 namespace tgx {
 void launch_pair_counts(const PairSide &x, const PairSide &y, const PairCountsTable &t, int64_t length,
@@ -58,8 +59,8 @@ struct PairsKind {
   typedef PairsHost Host;
   typedef PairRangeAcc Range;
   static constexpr bool kRanged = true;
-  static constexpr int kIndex = kSidePairs;
-  static constexpr const char *kName = "PAIR_COUNTS", *kDiffers = "parameters";
+  static constexpr int kKind = TGX_CHECK_PAIR_COUNTS;
+  static constexpr const char *kDiffers = "parameters";
   static constexpr uint32_t kMagic = 0x544e4350;  // "PCNT"
 
   static const std::vector<PairCountsTask> &tasks(const tgx_plan *plan) { return plan->pair_counts; }
@@ -95,6 +96,9 @@ struct PairsKind {
     }
     return d;
   }
+  static void add_entries(PairsHost &a, const PairsHost &b) {
+    for (const auto &e : b.pairs) a.pairs[e.first] += e.second;
+  }
   static void merge_host(PairsHost &a, const PairsHost &b) {
     a.seen += b.seen;
     a.both += b.both;
@@ -105,7 +109,7 @@ struct PairsKind {
     a.n += b.n;
     a.min = std::min(a.min, b.min);
     a.max = std::max(a.max, b.max);
-    for (const auto &e : b.pairs) a.pairs[e.first] += e.second;
+    add_entries(a, b);
   }
 
   // per task { tgx_pair_counts_params (the plan's: u32 max_pairs, max_value_bytes, per side i32 mode, u32 bins, f64
@@ -162,48 +166,32 @@ struct PairsKind {
     } else {
       if (counts[6] != 0 || ext[0] != INFINITY || ext[1] != -INFINITY)
         return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (PAIR_COUNTS task %zu: a count phase with a range)", k);
-      size_t least = 0;  // (held against the bytes that are left before anything is allocated)
-      if (!r.fits(n, 16, &least)) return TGX_OK;
-    }
-    uint64_t counted = 0;
-    for (uint64_t i = 0; i < n; i++) {
-      PairKey key;
-      for (int side = 0; side < 2; side++) {
-        const tgx_pair_side &m = side ? t.params.y : t.params.x;
-        Cell &c = side ? key.second : key.first;
-        c.first = 0;
-        if (m.mode == TGX_PAIR_SIDE_VALUE) {
-          const uint32_t len = r.pod<uint32_t>();
-          if (!r.ok) return TGX_OK;
-          if (len > t.params.max_value_bytes)
-            return fail(err, TGX_INVALID_ARGUMENT,
-                        "malformed state blob (PAIR_COUNTS task %zu: a value of %u bytes, max_value_bytes is %u)", k, len,
-                        t.params.max_value_bytes);
-          c.second.assign(len, '\0');
-          r.get(&c.second[0], len);
-        } else {
-          c.first = r.pod<int64_t>();
-          if (r.ok && (c.first < 0 || c.first > (int64_t)m.bins))
-            return fail(err, TGX_INVALID_ARGUMENT,
-                        "malformed state blob (PAIR_COUNTS task %zu: bin %lld lies outside [0, %u])", k,
-                        (long long)c.first, m.bins);
+      uint64_t counted = 0;
+      TGX_TRY(counted_read_entries("PAIR_COUNTS", k, r, n, 16, h.pairs, &counted, [&](PairKey &key) {
+        for (int side = 0; side < 2; side++) {
+          const tgx_pair_side &m = side ? t.params.y : t.params.x;
+          Cell &c = side ? key.second : key.first;
+          c.first = 0;
+          if (m.mode == TGX_PAIR_SIDE_VALUE) {
+            const uint32_t len = r.pod<uint32_t>();
+            if (!r.ok) return TGX_OK;
+            if (len > t.params.max_value_bytes)
+              return fail(err, TGX_INVALID_ARGUMENT,
+                          "malformed state blob (PAIR_COUNTS task %zu: a value of %u bytes, max_value_bytes is %u)", k,
+                          len, t.params.max_value_bytes);
+            c.second.assign(len, '\0');
+            r.get(&c.second[0], len);
+          } else {
+            c.first = r.pod<int64_t>();
+            if (r.ok && (c.first < 0 || c.first > (int64_t)m.bins))
+              return fail(err, TGX_INVALID_ARGUMENT,
+                          "malformed state blob (PAIR_COUNTS task %zu: bin %lld lies outside [0, %u])", k,
+                          (long long)c.first, m.bins);
+          }
         }
-      }
-      const uint64_t c = r.pod<uint64_t>();
+        return TGX_OK;
+      }, err));
       if (!r.ok) return TGX_OK;
-      if (!h.pairs.empty() && !(h.pairs.rbegin()->first < key))
-        return fail(err, TGX_INVALID_ARGUMENT,
-                    "malformed state blob (PAIR_COUNTS task %zu: entry %llu is out of order or repeated)", k,
-                    (unsigned long long)i);
-      if (c == 0)
-        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (PAIR_COUNTS task %zu: entry %llu has a zero count)",
-                    k, (unsigned long long)i);
-      if (c > UINT64_MAX - counted)
-        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (PAIR_COUNTS task %zu: counts)", k);
-      counted += c;
-      h.pairs.emplace_hint(h.pairs.end(), std::move(key), c);
-    }
-    if (!is_range(t)) {
       // counted + overflow_rows + long_rows + non_finite + out_of_range == both_non_null <= seen (no sum can wrap: each
       // term is held against what is left of both_non_null)
       uint64_t left = both;
@@ -231,80 +219,43 @@ struct PairsKind {
   }
 };
 
-uint64_t table_slots(uint32_t max_pairs) {
-  uint64_t s = 2;
-  while (s < 2 * (uint64_t)max_pairs) s <<= 1;
-  return s;
-}
+struct PairsCheck final : CountedState<PairsKind> {
+  // a count-phase task's table (made at the first batch): two key words a slot, and behind the counts the two sides'
+  // cells (a string's length or a bin index) and the byte stores of the string sides
+  const std::vector<PairCountsTask> &tasks;  // (the plan's: their parameters are fixed once a state exists)
 
-struct PairsCheck final : SideState<PairsKind> {
-  // the device part of a count-phase task: its table, allocated at the first batch
-  struct Dev {
-    bool ready = false;
-    uint64_t slots = 0;
-    uint32_t max_value_bytes = 0;
-    bool strings[2] = {false, false};
-    DevBuf table;
-    size_t key_bytes() const { return (size_t)slots * 16; }
-    size_t counts_at() const { return key_bytes(); }
-    size_t cell_at(int side) const { return counts_at() + (size_t)slots * 8 + (size_t)side * slots * 4; }
-    size_t store_at(int side) const {
-      return cell_at(2) + (side && strings[0] ? (size_t)slots * max_value_bytes : 0);
-    }
-    size_t bytes() const { return cell_at(2) + ((size_t)strings[0] + (size_t)strings[1]) * slots * max_value_bytes; }
-  };
-  std::vector<Dev> dev_part;
-  // what the tables held when they were last read back: a read of the state costs the copy once, until the next batch
-  // or reset
-  std::vector<PairsHost> table_cache;
-  bool table_cache_ok = false;
+  explicit PairsCheck(const tgx_plan *plan) : CountedState(plan), tasks(plan->pair_counts) {}
 
-  explicit PairsCheck(const tgx_plan *plan) : SideState(plan), dev_part(plan->pair_counts.size()) {}
+  uint32_t value_bytes(size_t k) const { return tasks[k].params.max_value_bytes; }
+  bool strings(size_t k, int side) const {
+    return (side ? tasks[k].params.y : tasks[k].params.x).mode == TGX_PAIR_SIDE_VALUE;
+  }
+  size_t cell_at(size_t k, int side) const { return table[k].extra_at() + (size_t)side * table[k].slots * 4; }
+  size_t store_at(size_t k, int side) const {
+    return cell_at(k, 2) + (side && strings(k, 0) ? (size_t)table[k].slots * value_bytes(k) : 0);
+  }
 
   PairCountsTable view(size_t k) const {
-    const Dev &d = dev_part[k];
-    uint8_t *base = d.table.as<uint8_t>();
+    uint8_t *base = table[k].buf.as<uint8_t>();
     PairCountsTable t;
     memset(&t, 0, sizeof(t));
     t.keys = (unsigned long long *)base;
-    t.keys2 = t.keys + d.slots;
-    t.counts = (unsigned long long *)(base + d.counts_at());
+    t.keys2 = t.keys + table[k].slots;
+    t.counts = (unsigned long long *)(base + table[k].counts_at());
     for (int side = 0; side < 2; side++) {
-      t.cell[side] = (uint32_t *)(base + d.cell_at(side));
-      t.store[side] = d.strings[side] ? base + d.store_at(side) : nullptr;
+      t.cell[side] = (uint32_t *)(base + cell_at(k, side));
+      t.store[side] = strings(k, side) ? base + store_at(k, side) : nullptr;
     }
     t.words = d_counts.as<unsigned long long>() + word_off[k];
-    t.mask = d.slots - 1;
-    t.max_value_bytes = d.max_value_bytes;
+    t.mask = table[k].slots - 1;
+    t.max_value_bytes = value_bytes(k);
     return t;
   }
 
-  tgx_status clear_table(tgx_state *st, size_t k, tgx_error *err) {
-    const Dev &d = dev_part[k];
-    if (!d.ready) return TGX_OK;
-    uint8_t *base = d.table.as<uint8_t>();
-    HIP_TRY(hipMemsetAsync(base, 0xFF, d.key_bytes(), st->stream));  // (every key word: kEmptyKey)
-    HIP_TRY(hipMemsetAsync(base + d.counts_at(), 0, (size_t)d.slots * 8, st->stream));
-    return TGX_OK;
-  }
-
-  tgx_status device_clear_extra(tgx_state *st, tgx_error *err) override {
-    table_cache_ok = false;
-    for (size_t k = 0; k < dev_part.size(); k++) TGX_TRY(clear_table(st, k, err));
-    return TGX_OK;
-  }
-
   tgx_status ensure_table(tgx_state *st, size_t k, tgx_error *err) {
-    Dev &d = dev_part[k];
-    if (d.ready) return TGX_OK;
-    const tgx_pair_counts_params &p = st->plan->pair_counts[k].params;
-    d.slots = table_slots(p.max_pairs);
-    d.max_value_bytes = p.max_value_bytes;
-    d.strings[0] = p.x.mode == TGX_PAIR_SIDE_VALUE;
-    d.strings[1] = p.y.mode == TGX_PAIR_SIDE_VALUE;
-    HIP_TRY(d.table.reserve(d.bytes()));
-    d.ready = true;
-    return clear_table(st, k, err);
+    if (table[k].live) return TGX_OK;
+    const size_t stores = (size_t)strings(k, 0) + (size_t)strings(k, 1);
+    return open_table(st, k, tasks[k].params.max_pairs, 2, 8 + stores * value_bytes(k), err);
   }
 
   // column `c` (a device view, widened) as side `m` of a launch
@@ -371,39 +322,19 @@ struct PairsCheck final : SideState<PairsKind> {
     return TGX_OK;
   }
 
-  // the tables' entries into the gathered hosts (the counters are already there)
-  tgx_status gather_extra(tgx_state *st, std::vector<PairsHost> *out, tgx_error *err) override {
-    std::vector<uint8_t> h;
-    if (!table_cache_ok) table_cache.assign(dev_part.size(), PairsHost());
-    for (size_t k = 0; k < dev_part.size() && !table_cache_ok; k++) {
-      const Dev &d = dev_part[k];
-      if (!d.ready || device_rows[k] == 0) continue;
-      h.resize(d.bytes());
-      HIP_TRY(hipMemcpyAsync(h.data(), d.table.p, h.size(), hipMemcpyDeviceToHost, st->stream));
-      HIP_TRY(hipStreamSynchronize(st->stream));
-      const uint64_t *keys = (const uint64_t *)h.data(), *keys2 = keys + d.slots;
-      const uint64_t *counts = (const uint64_t *)(h.data() + d.counts_at());
-      PairsHost &o = table_cache[k];
-      for (uint64_t s = 0; s < d.slots; s++) {
-        if (keys[s] == kEmptyKey || keys2[s] == kEmptyKey || counts[s] == 0) continue;
-        PairKey key;
-        for (int side = 0; side < 2; side++) {
-          Cell &c = side ? key.second : key.first;
-          const uint32_t word = ((const uint32_t *)(h.data() + d.cell_at(side)))[s];
-          c.first = 0;
-          if (d.strings[side])
-            c.second.assign((const char *)h.data() + d.store_at(side) + (size_t)s * d.max_value_bytes,
-                            std::min(word, d.max_value_bytes));
-          else
-            c.first = (int64_t)word;
-        }
-        o.pairs[key] += counts[s];
-      }
+  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, PairsHost &o) const override {
+    if (((const uint64_t *)h)[table[k].slots + s] == kEmptyKey) return;
+    PairKey key;
+    for (int side = 0; side < 2; side++) {
+      Cell &c = side ? key.second : key.first;
+      const uint32_t word = ((const uint32_t *)(h + cell_at(k, side)))[s];
+      c.first = 0;
+      if (strings(k, side))
+        c.second.assign((const char *)h + store_at(k, side) + (size_t)s * value_bytes(k), std::min(word, value_bytes(k)));
+      else
+        c.first = (int64_t)word;
     }
-    table_cache_ok = true;
-    for (size_t k = 0; k < dev_part.size(); k++)  // (only the entries: the counters came with the words)
-      for (const auto &e : table_cache[k].pairs) (*out)[k].pairs[e.first] += e.second;
-    return TGX_OK;
+    o.pairs[key] += count;
   }
 
   tgx_status read_task(tgx_state *st, size_t slot, PairsHost *out, tgx_error *err) {
@@ -447,6 +378,11 @@ tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err) {
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a PAIR_COUNTS check needs its parameters (tgx_plan_set_pair_counts)",
                   t.spec_index);
   return TGX_OK;
+}
+
+void paircounts_mark_columns(tgx_plan *plan) {
+  for (const PairCountsTask &t : plan->pair_counts)
+    for (int c : {t.col_x, t.col_y}) side_mark(plan, PairsCheck::kIndex, c, true);
 }
 
 tgx_status paircounts_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err) {
@@ -580,16 +516,8 @@ extern "C" tgx_status tgx_pair_counts_entries(const tgx_plan *plan, tgx_state *s
   TGX_TRY(static_cast<PairsCheck *>(PairsCheck::of(st))->read_task(st, slot, &h, err));
   uint64_t need_bytes = 0;
   for (const auto &e : h.pairs) need_bytes += e.first.first.second.size() + e.first.second.second.size();
-  *n_entries = h.pairs.size();
-  *n_bytes = need_bytes;
-  if (entries && cap < *n_entries)
-    return fail(err, TGX_INVALID_ARGUMENT, "entries holds %llu entries, %llu are needed", (unsigned long long)cap,
-                (unsigned long long)*n_entries);
-  if (bytes && bytes_cap < need_bytes)
-    return fail(err, TGX_INVALID_ARGUMENT, "bytes holds %llu bytes, %llu are needed", (unsigned long long)bytes_cap,
-                (unsigned long long)need_bytes);
+  TGX_TRY(counted_entries_sizes(h.pairs.size(), need_bytes, entries, cap, n_entries, bytes, bytes_cap, n_bytes, err));
   if (!entries) return TGX_OK;
-  if (need_bytes && !bytes) return fail(err, TGX_INVALID_ARGUMENT, "string values need a byte buffer");
   size_t i = 0;
   uint64_t at = 0;
   for (const auto &e : h.pairs) {

@@ -1,15 +1,14 @@
-// side_check.h -- the check kinds that run beside the fused pass and share one shape: TGX_CHECK_JOINT_BINS
-// (jointbins_device.cpp), TGX_CHECK_TEMPORAL (temporal_device.cpp), TGX_CHECK_HISTOGRAM (histogram_device.cpp),
-// TGX_CHECK_VALUE_RULE (valuerule_device.cpp), TGX_CHECK_VALUE_COUNTS (valuecounts_device.cpp) and TGX_CHECK_PAIR_COUNTS
-// (paircounts_device.cpp).
+// side_check.h -- the check kinds that run beside the fused pass and share one shape.  A kind is registered once, by its
+// record in kSideKinds below; its code is in a *_device.cpp of its own.
 //
 // A task is one spec.  Its running state is a few 64-bit counters on the device, plus a small range accumulator for the
 // kinds that have a range phase; rows seen are counted on the host.  What is merged in from other states or read from a
 // blob is kept on the host (`host`) and added when the state is read (`gather`).  The rest of the library sees a
-// SideCheck per kind in tgx_state::side, in the order of the blob's sections (null: the plan has no task of the kind);
-// SideState<K> is everything the kinds have in common, a kind K adds what its tasks count and how they are launched.
-// A kind whose tasks keep more on the device than counters (VALUE_COUNTS, PAIR_COUNTS: a table per task, and a host part
-// of variable size) clears and reads that through device_clear_extra / gather_extra; the other kinds leave both alone.
+// SideCheck per kind in tgx_state::side, in the order of kSideKinds, which is the order of the blob's sections (null: the
+// plan has no task of the kind); SideState<K> is everything the kinds have in common, a kind K adds what its tasks count
+// and how they are launched.  A kind whose tasks keep more on the device than counters clears and reads that through
+// device_clear_extra / gather_extra (counted_state.h: a table of counted keys per task); the other kinds leave both
+// alone.
 #pragma once
 #include <memory>
 
@@ -17,16 +16,6 @@
 #include "wire_io.h"
 
 namespace tgx {
-
-enum { kSideJoint = 0, kSideTemporal = 1, kSideHist = 2, kSideRule = 3, kSideCounts = 4, kSidePairs = 5 };  // (kNumSide: internal.h)
-TGX_HIDDEN inline int side_index(int kind) {
-  return kind == TGX_CHECK_JOINT_BINS ? kSideJoint
-         : kind == TGX_CHECK_TEMPORAL ? kSideTemporal
-         : kind == TGX_CHECK_HISTOGRAM ? kSideHist
-         : kind == TGX_CHECK_VALUE_RULE ? kSideRule
-         : kind == TGX_CHECK_VALUE_COUNTS ? kSideCounts
-                                          : kSidePairs;
-}
 
 struct TGX_HIDDEN SideCheck {
   virtual ~SideCheck() {}
@@ -41,34 +30,73 @@ struct TGX_HIDDEN SideCheck {
   virtual tgx_status deserialize(tgx_state *st, Reader &r, tgx_error *err) = 0;
 };
 
-tgx_status joint_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-tgx_status temporal_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-tgx_status hist_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-tgx_status valuerule_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-tgx_status valuecounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-tgx_status paircounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
-// every task has its parameters (tgx_plan_set_temporal, tgx_plan_set_value_rule, tgx_plan_set_value_counts,
-// tgx_plan_set_pair_counts)?  Asked by tgx_state_create
+// ---- the kinds ---------------------------------------------------------------------------------------------------------
+struct TGX_HIDDEN SideKind {
+  int kind;  // TGX_CHECK_*
+  const char *name;
+  // spec `spec_index` as a task of the plan; *slot: the task's index within its kind
+  tgx_status (*plan_add)(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);
+  // every task has the parameters of its tgx_plan_set_* call?  Null: the kind's tasks run without any
+  tgx_status (*plan_ready)(const tgx_plan *plan, tgx_error *err);
+  void (*mark_columns)(tgx_plan *plan);  // the per-column flags of the columns its tasks read (side_mark)
+  // may column `column` of a batch feed the kind's tasks?  Asked by tgx_update of the columns they read only
+  tgx_status (*check_column)(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err);
+  SideCheck *(*state_new)(const tgx_plan *plan);  // the fresh state of the plan's tasks, or null when it has none
+  bool reads_column2;                             // a spec's column2 is a column of the batch
+};
+
+// what every kind's *_device.cpp defines (a plan_ready where the kind has parameters)
+#define TGX_SIDE_KIND(prefix)                                                                               \
+  tgx_status prefix##_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err);                  \
+  void prefix##_mark_columns(tgx_plan *plan);                                                               \
+  tgx_status prefix##_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err);  \
+  TGX_HIDDEN SideCheck *prefix##_state_new(const tgx_plan *plan);
+TGX_SIDE_KIND(joint)
+TGX_SIDE_KIND(temporal)
+TGX_SIDE_KIND(hist)
+TGX_SIDE_KIND(valuerule)
+TGX_SIDE_KIND(valuecounts)
+TGX_SIDE_KIND(paircounts)
+#undef TGX_SIDE_KIND
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err);
-// may a column of tgx_type `type` feed a VALUE_COUNTS check?  Asked by tgx_update of column `column`
-tgx_status valuecounts_check_type(int column, int type, tgx_error *err);
 tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
-// may column `column` of a batch feed the PAIR_COUNTS checks that read it (each side's mode against the column's type)?
-tgx_status paircounts_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err);
-TGX_HIDDEN SideCheck *joint_state_new(const tgx_plan *plan);
-TGX_HIDDEN SideCheck *temporal_state_new(const tgx_plan *plan);
-TGX_HIDDEN SideCheck *hist_state_new(const tgx_plan *plan);
-TGX_HIDDEN SideCheck *valuerule_state_new(const tgx_plan *plan);
-TGX_HIDDEN SideCheck *valuecounts_state_new(const tgx_plan *plan);
-TGX_HIDDEN SideCheck *paircounts_state_new(const tgx_plan *plan);
-// the fresh state of the plan's tasks of kind `index`, or null when it has none
-TGX_HIDDEN inline SideCheck *side_state_new(int index, const tgx_plan *plan) {
-  SideCheck *(*const make[kNumSide])(const tgx_plan *) = {joint_state_new, temporal_state_new, hist_state_new,
-                                                          valuerule_state_new, valuecounts_state_new,
-                                                          paircounts_state_new};
-  return make[index](plan);
+
+// in the order of the blob's sections
+inline constexpr SideKind kSideKinds[kNumSide] = {
+    {TGX_CHECK_JOINT_BINS, "JOINT_BINS", joint_plan_add, nullptr, joint_mark_columns, joint_check_column,
+     joint_state_new, true},
+    {TGX_CHECK_TEMPORAL, "TEMPORAL", temporal_plan_add, temporal_plan_ready, temporal_mark_columns,
+     temporal_check_column, temporal_state_new, true},
+    {TGX_CHECK_HISTOGRAM, "HISTOGRAM", hist_plan_add, nullptr, hist_mark_columns, hist_check_column, hist_state_new,
+     false},
+    {TGX_CHECK_VALUE_RULE, "VALUE_RULE", valuerule_plan_add, valuerule_plan_ready, valuerule_mark_columns,
+     valuerule_check_column, valuerule_state_new, false},
+    {TGX_CHECK_VALUE_COUNTS, "VALUE_COUNTS", valuecounts_plan_add, valuecounts_plan_ready, valuecounts_mark_columns,
+     valuecounts_check_column, valuecounts_state_new, false},
+    {TGX_CHECK_PAIR_COUNTS, "PAIR_COUNTS", paircounts_plan_add, paircounts_plan_ready, paircounts_mark_columns,
+     paircounts_check_column, paircounts_state_new, true},
+};
+
+// where `kind` stands in kSideKinds (and in tgx_state::side, tgx_plan::side_on), or -1: not a kind of this file
+constexpr int side_index(int kind) {
+  for (int i = 0; i < kNumSide; i++)
+    if (kSideKinds[i].kind == kind) return i;
+  return -1;
+}
+
+// column `c` feeds a task of kind `index`, which reads its values; `wide`: as 8-byte values (a 4-byte column is widened)
+TGX_HIDDEN inline void side_mark(tgx_plan *plan, int index, int c, bool wide) {
+  plan->used[c] = plan->reads_values[c] = plan->side_on[index][c] = 1;
+  if (wide) plan->needs_wide[c] = 1;
+}
+
+// every task of every kind has its parameters?  Asked before a state of the plan is made
+TGX_HIDDEN inline tgx_status side_plans_ready(const tgx_plan *plan, tgx_error *err) {
+  for (const SideKind &k : kSideKinds)
+    if (k.plan_ready) TGX_TRY(k.plan_ready(plan, err));
+  return TGX_OK;
 }
 
 // ---- what the kinds' updates share -----------------------------------------------------------------------------------
@@ -121,7 +149,7 @@ TGX_HIDDEN inline uint64_t side_fill_y(ComomentColDesc &d, const tgx_column &y) 
 
 // ---- the state of one kind's tasks -----------------------------------------------------------------------------------
 // K gives: Task, Host (one task's state as the host sees it), Range (the device's range accumulator; kRanged: whether
-// there is one), kIndex, kName, kMagic, kDiffers (what two states of one plan can still differ in, or null), and
+// there is one), kKind, kMagic, kDiffers (what two states of one plan can still differ in, or null), and
 //   tasks(plan)                         the plan's tasks of the kind
 //   words(task)                         64-bit device counters of the task
 //   range_identity()
@@ -135,6 +163,9 @@ template <class K>
 struct TGX_HIDDEN SideState : SideCheck {
   typedef typename K::Host Host;
   typedef typename K::Range Range;
+  static constexpr int kIndex = side_index(K::kKind);
+  static_assert(kIndex >= 0, "the kind has a record in kSideKinds");
+  static constexpr const char *kName = kSideKinds[kIndex].name;
 
   std::vector<Host> host;            // merged in / deserialized
   std::vector<int64_t> device_rows;  // rows the device part has seen
@@ -154,7 +185,7 @@ struct TGX_HIDDEN SideState : SideCheck {
     }
   }
 
-  static SideState *of(tgx_state *st) { return static_cast<SideState *>(st->side[K::kIndex].get()); }
+  static SideState *of(tgx_state *st) { return static_cast<SideState *>(st->side[kIndex].get()); }
 
   // what a kind uploads once per state
   virtual tgx_status device_init_extra(tgx_state *, tgx_error *) { return TGX_OK; }
@@ -219,7 +250,7 @@ struct TGX_HIDDEN SideState : SideCheck {
       // (states of one plan share what the plan fixes; a blob made under something else was refused by
       // tgx_state_deserialize)
       if (K::shape(g[k]) != K::shape(host[k]))
-        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", K::kName, k,
+        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", kName, k,
                     K::kDiffers);
       K::merge_host(host[k], g[k]);
     }
@@ -241,7 +272,7 @@ struct TGX_HIDDEN SideState : SideCheck {
     const auto &tasks = K::tasks(st->plan);
     const uint32_t magic = r.pod<uint32_t>(), n = r.pod<uint32_t>();
     if (!r.ok || magic != K::kMagic || n != tasks.size())
-      return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan (%s section)", K::kName);
+      return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan (%s section)", kName);
     for (size_t k = 0; k < tasks.size() && r.ok; k++) TGX_TRY(K::read(tasks[k], host[k], r, k, err));
     if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
     return TGX_OK;

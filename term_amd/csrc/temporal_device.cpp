@@ -36,8 +36,8 @@ struct TemporalKind {
   typedef TemporalHost Host;
   typedef NoRange Range;
   static constexpr bool kRanged = false;
-  static constexpr int kIndex = kSideTemporal;
-  static constexpr const char *kName = "TEMPORAL", *kDiffers = nullptr;  // (every host has the one shape)
+  static constexpr int kKind = TGX_CHECK_TEMPORAL;
+  static constexpr const char *kDiffers = nullptr;  // (every host has the one shape)
   static constexpr uint32_t kMagic = 0x52504d54;  // "TMPR"
 
   static const std::vector<TemporalTask> &tasks(const tgx_plan *plan) { return plan->temporal; }
@@ -156,6 +156,18 @@ tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err) {
     if (!t.set)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a TEMPORAL check needs its parameters (tgx_plan_set_temporal)",
                   t.spec_index);
+  return TGX_OK;
+}
+
+void temporal_mark_columns(tgx_plan *plan) {
+  for (const TemporalTask &t : plan->temporal)
+    for (int c : {t.column, t.column2})
+      if (c >= 0) side_mark(plan, TemporalCheck::kIndex, c, false);  // (Int64-shaped columns only: nothing to widen)
+}
+
+tgx_status temporal_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  if (c.type != TGX_INT64)
+    return fail(err, TGX_UNSUPPORTED, "column %d: TEMPORAL takes Int64-shaped columns (type %d)", column, c.type);
   return TGX_OK;
 }
 

@@ -219,6 +219,11 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     plan->bind[i].kind = sp.kind;
     plan->bind[i].slot = -1;
     plan->bind[i].count_src = Source::kCount;
+    if (const int s = side_index(sp.kind); s >= 0) {  // a kind of side_check.h
+      TGX_TRY(kSideKinds[s].plan_add(plan.get(), (int)i, &plan->bind[i].slot, err));
+      if (kSideKinds[s].reads_column2) max_col = std::max(max_col, sp.column2);
+      continue;
+    }
     switch (sp.kind) {
       case TGX_CHECK_COUNT:
         break;
@@ -301,21 +306,6 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         plan->bind[i].slot = slot;
         break;
       }
-      case TGX_CHECK_JOINT_BINS:
-      case TGX_CHECK_TEMPORAL:
-      case TGX_CHECK_HISTOGRAM:
-      case TGX_CHECK_VALUE_RULE:
-      case TGX_CHECK_VALUE_COUNTS:
-      case TGX_CHECK_PAIR_COUNTS: {  // the kinds of side_check.h, in its order
-        tgx_status (*const add[kNumSide])(tgx_plan *, int, int *, tgx_error *) = {
-            joint_plan_add, temporal_plan_add, hist_plan_add, valuerule_plan_add, valuecounts_plan_add,
-            paircounts_plan_add};
-        int slot = -1;
-        TGX_TRY(add[side_index(sp.kind)](plan.get(), (int)i, &slot, err));
-        if (sp.kind == TGX_CHECK_JOINT_BINS || sp.kind == TGX_CHECK_TEMPORAL || sp.kind == TGX_CHECK_PAIR_COUNTS) max_col = std::max(max_col, sp.column2);
-        plan->bind[i].slot = slot;
-        break;
-      }
       case TGX_CHECK_SPEARMAN: {
         max_col = std::max(max_col, sp.column2);
         int slot = -1;
@@ -378,12 +368,6 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     P->needs_wide.assign(P->n_columns_needed, 0);
     P->key_column.assign(P->n_columns_needed, 0);
     P->stats_on.assign(P->n_columns_needed, 0);
-    P->joint_on.assign(P->n_columns_needed, 0);
-    P->temporal_on.assign(P->n_columns_needed, 0);
-    P->hist_on.assign(P->n_columns_needed, 0);
-    P->rule_on.assign(P->n_columns_needed, 0);
-    P->counts_on.assign(P->n_columns_needed, 0);
-    P->pairs_on.assign(P->n_columns_needed, 0);
     for (auto &t : P->distinct)
       if (t.tuple.empty() && !t.approx_only) P->key_column[t.column] = 1;
     // (by what was ASKED: a key column has a scan task of its own for the range decisions of its key set)
@@ -405,20 +389,10 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       P->used[t.col_x] = P->used[t.col_y] = P->reads_values[t.col_x] = P->reads_values[t.col_y] =
           P->needs_wide[t.col_x] = P->needs_wide[t.col_y] = 1;
     for (auto &t : P->kll) P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = 1;
-    for (auto &t : P->joint)
-      for (int c : {t.col_x, t.col_y})
-        P->used[c] = P->reads_values[c] = P->needs_wide[c] = P->stats_on[c] = P->joint_on[c] = 1;
-    for (auto &t : P->temporal)
-      for (int c : {t.column, t.column2})
-        if (c >= 0) P->used[c] = P->reads_values[c] = P->temporal_on[c] = 1;
-    for (auto &t : P->hist)
-      P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->stats_on[t.column] = P->hist_on[t.column] = 1;
-    for (auto &t : P->rules)
-      P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->rule_on[t.column] = 1;
-    for (auto &t : P->value_counts)
-      P->used[t.column] = P->reads_values[t.column] = P->needs_wide[t.column] = P->counts_on[t.column] = 1;
-    for (auto &t : P->pair_counts)
-      for (int c : {t.col_x, t.col_y}) P->used[c] = P->reads_values[c] = P->needs_wide[c] = P->pairs_on[c] = 1;
+    for (int k = 0; k < kNumSide; k++) {
+      P->side_on[k].assign(P->n_columns_needed, 0);
+      kSideKinds[k].mark_columns(P);
+    }
     regex_mark_used(P, P->used);
     std::vector<char> sp_used(P->n_columns_needed, 0), sp_vals(P->n_columns_needed, 0);
     spearman_mark_used(P, sp_used, sp_vals);
@@ -556,7 +530,7 @@ void state_init_host(tgx_state *st, const tgx_plan *plan) {
   kll_state_init(st);
   spearman_state_init(st);
   timegap_state_init(st);
-  for (int i = 0; i < kNumSide; i++) st->side[i].reset(side_state_new(i, plan));
+  for (int i = 0; i < kNumSide; i++) st->side[i].reset(kSideKinds[i].state_new(plan));
 }
 
 // one launch for all the small accumulators of a state (fresh, or reset): the scan accumulators to their identities,
@@ -622,10 +596,7 @@ extern "C" tgx_status tgx_state_create(const tgx_plan *plan, void *hip_stream, t
                                        tgx_error *err) try {
   if (!plan || !out) return fail(err, TGX_INVALID_ARGUMENT, "plan/out is NULL");
   *out = nullptr;
-  TGX_TRY(temporal_plan_ready(plan, err));  // (before the plan is locked: the parameters can still follow)
-  TGX_TRY(valuerule_plan_ready(plan, err));
-  TGX_TRY(valuecounts_plan_ready(plan, err));
-  TGX_TRY(paircounts_plan_ready(plan, err));
+  TGX_TRY(side_plans_ready(plan, err));  // (before the plan is locked: the parameters can still follow)
   TGX_TRY(timegap_plan_ready(plan, err));
   tgx_state *st = new tgx_state();
   state_init_host(st, plan);
@@ -1049,6 +1020,10 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
     memset(r, 0, sizeof(*r));
     const SpecBinding &b = plan->bind[i];
     r->kind = b.kind;
+    if (const int s = side_index(b.kind); s >= 0) {  // a kind of side_check.h
+      TGX_TRY(st->side[s]->fill_result(st, b.slot, r, err));
+      continue;
+    }
     switch (b.kind) {
       case TGX_CHECK_COUNT:
         if (b.count_src == Source::kScan) {
@@ -1134,14 +1109,6 @@ extern "C" tgx_status tgx_finalize(const tgx_plan *plan, tgx_state *st, tgx_resu
         break;
       case TGX_CHECK_SPEARMAN:
         TGX_TRY(spearman_fill_result(st, b.slot, r, err));
-        break;
-      case TGX_CHECK_JOINT_BINS:
-      case TGX_CHECK_TEMPORAL:
-      case TGX_CHECK_HISTOGRAM:
-      case TGX_CHECK_VALUE_RULE:
-      case TGX_CHECK_VALUE_COUNTS:
-      case TGX_CHECK_PAIR_COUNTS:
-        TGX_TRY(st->side[side_index(b.kind)]->fill_result(st, b.slot, r, err));
         break;
       case TGX_CHECK_TIME_GAP:
         TGX_TRY(timegap_fill_result(st, (int)i, r, err));

@@ -252,16 +252,8 @@ tgx_status update_validate(const tgx_plan *plan, tgx_state *st, const tgx_column
     if (is_keys_only(c.type) && plan->stats_on[i])
       return fail(err, TGX_UNSUPPORTED, "column %d: a %s column takes COUNT and DISTINCT checks only", i,
                   c.type == TGX_BOOL ? "Boolean" : "UInt64");
-    if (plan->joint_on[i] && !is_numeric(c.type) && !is_widened(c.type))
-      return fail(err, TGX_UNSUPPORTED, "column %d: JOINT_BINS takes numeric columns (type %d)", i, c.type);
-    if (plan->hist_on[i] && !is_numeric(c.type) && !is_widened(c.type))
-      return fail(err, TGX_UNSUPPORTED, "column %d: HISTOGRAM takes numeric columns (type %d)", i, c.type);
-    if (plan->temporal_on[i] && c.type != TGX_INT64)
-      return fail(err, TGX_UNSUPPORTED, "column %d: TEMPORAL takes Int64-shaped columns (type %d)", i, c.type);
-    if (plan->rule_on[i] && !is_numeric(c.type) && !(is_widened(c.type) && c.type != TGX_BOOL))
-      return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_RULE takes numeric columns other than UInt64 (type %d)", i, c.type);
-    if (plan->counts_on[i]) TGX_TRY(valuecounts_check_type(i, c.type, err));
-    if (plan->pairs_on[i]) TGX_TRY(paircounts_check_column(plan, i, c, err));
+    for (int k = 0; k < kNumSide; k++)
+      if (plan->side_on[k][i]) TGX_TRY(kSideKinds[k].check_column(plan, i, c, err));
     if (plan->timegap_on[i]) TGX_TRY(timegap_check_type(plan, i, c.type, err));
     if (c.mem != TGX_MEM_HOST && c.mem != TGX_MEM_DEVICE)
       return fail(err, TGX_INVALID_ARGUMENT, "column %d: unknown memory space %d", i, c.mem);

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "api_internal.h"
+#include "counted_state.h"
 
 namespace tgx {
 void launch_value_counts_i64(const ComomentColDesc &d, const ValueCountsTable &t, int blocks, hipStream_t stream);
@@ -65,8 +66,8 @@ struct CountsKind {
   typedef CountsHost Host;
   typedef NoRange Range;
   static constexpr bool kRanged = false;
-  static constexpr int kIndex = kSideCounts;
-  static constexpr const char *kName = "VALUE_COUNTS", *kDiffers = "column types";
+  static constexpr int kKind = TGX_CHECK_VALUE_COUNTS;
+  static constexpr const char *kDiffers = "column types";
   static constexpr uint32_t kMagic = 0x544e4356;  // "VCNT"
 
   static const std::vector<ValueCountsTask> &tasks(const tgx_plan *plan) { return plan->value_counts; }
@@ -87,14 +88,17 @@ struct CountsKind {
     }
     return d;
   }
-  static void merge_host(CountsHost &a, const CountsHost &b) {
+  static void add_entries(CountsHost &a, const CountsHost &b) {
     if (a.kind == kNoValues) a.kind = b.kind;
+    for (const auto &e : b.ints) a.ints[e.first] += e.second;
+    for (const auto &e : b.strs) a.strs[e.first] += e.second;
+  }
+  static void merge_host(CountsHost &a, const CountsHost &b) {
     a.seen += b.seen;
     a.non_null += b.non_null;
     a.overflow_rows += b.overflow_rows;
     a.long_rows += b.long_rows;
-    for (const auto &e : b.ints) a.ints[e.first] += e.second;
-    for (const auto &e : b.strs) a.strs[e.first] += e.second;
+    add_entries(a, b);
   }
 
   // per task { u32 max_distinct, max_value_bytes (the plan's parameters), u32 kind (0 no values, 1 int64, 2 bytes), u32 0,
@@ -132,43 +136,26 @@ struct CountsKind {
     const uint64_t n = counts[4];
     if (kind > kByteValues || pad != 0 || (kind == kNoValues && n != 0))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: kind)", k);
-    size_t least = 0;  // (held against the bytes that are left before anything is allocated)
-    if (!r.fits(n, kind == kIntValues ? 16 : 12, &least)) return TGX_OK;
     uint64_t counted = 0;
-    for (uint64_t i = 0; i < n; i++) {
-      uint64_t c = 0;
-      bool ascending = true;
-      if (kind == kIntValues) {
-        const int64_t v = r.pod<int64_t>();
-        c = r.pod<uint64_t>();
-        if (!r.ok) return TGX_OK;
-        ascending = h.ints.empty() || h.ints.rbegin()->first < v;
-        if (ascending) h.ints.emplace_hint(h.ints.end(), v, c);
-      } else {
+    if (kind == kIntValues) {
+      TGX_TRY(counted_read_entries("VALUE_COUNTS", k, r, n, 16, h.ints, &counted, [&](int64_t &v) {
+        v = r.pod<int64_t>();
+        return TGX_OK;
+      }, err));
+    } else {
+      TGX_TRY(counted_read_entries("VALUE_COUNTS", k, r, n, 12, h.strs, &counted, [&](std::string &v) {
         const uint32_t len = r.pod<uint32_t>();
         if (!r.ok) return TGX_OK;
         if (len > t.params.max_value_bytes)
           return fail(err, TGX_INVALID_ARGUMENT,
                       "malformed state blob (VALUE_COUNTS task %zu: a value of %u bytes, max_value_bytes is %u)", k, len,
                       t.params.max_value_bytes);
-        std::string v(len, '\0');
+        v.assign(len, '\0');
         r.get(&v[0], len);
-        c = r.pod<uint64_t>();
-        if (!r.ok) return TGX_OK;
-        ascending = h.strs.empty() || h.strs.rbegin()->first < v;
-        if (ascending) h.strs.emplace_hint(h.strs.end(), std::move(v), c);
-      }
-      if (!ascending)
-        return fail(err, TGX_INVALID_ARGUMENT,
-                    "malformed state blob (VALUE_COUNTS task %zu: entry %llu is out of order or repeated)", k,
-                    (unsigned long long)i);
-      if (c == 0)
-        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: entry %llu has a zero count)",
-                    k, (unsigned long long)i);
-      if (c > UINT64_MAX - counted)
-        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (VALUE_COUNTS task %zu: counts)", k);
-      counted += c;
+        return TGX_OK;
+      }, err));
     }
+    if (!r.ok) return TGX_OK;
     // counted + overflow_rows + long_rows == non_null <= seen (no sum can wrap: each term is held against non_null)
     const uint64_t non_null = counts[1];
     if (non_null > counts[0] || counted > non_null || counts[2] > non_null - counted ||
@@ -184,64 +171,39 @@ struct CountsKind {
   }
 };
 
-uint64_t table_slots(uint32_t max_distinct) {
-  uint64_t s = 2;
-  while (s < 2 * (uint64_t)max_distinct) s <<= 1;
-  return s;
-}
-
-struct CountsCheck final : SideState<CountsKind> {
-  // the device part of a task: its table (allocated at the first batch, for the kind of value the column holds) and the
-  // per-entry cells of the dictionary route
+struct CountsCheck final : CountedState<CountsKind> {
+  // the device part of a task besides its table (made at the first batch, for the kind of value the column holds: one
+  // key word and nothing behind the counts for integers, two key words, the lengths and the byte store for strings):
+  // the per-entry cells of the dictionary route
   struct Dev {
     int kind = kNoValues;
-    uint64_t slots = 0;
-    uint32_t max_value_bytes = 0;
-    DevBuf table, cells;
-    size_t key_bytes() const { return (size_t)slots * 8 * (kind == kByteValues ? 2 : 1); }
-    size_t counts_at() const { return key_bytes(); }
-    size_t lens_at() const { return counts_at() + (size_t)slots * 8; }
-    size_t store_at() const { return lens_at() + (size_t)slots * 4; }
-    size_t bytes() const { return kind == kByteValues ? store_at() + (size_t)slots * max_value_bytes : lens_at(); }
+    DevBuf cells;
   };
   std::vector<Dev> dev_part;
-  // what the tables held when they were last read back: a read of the state costs the copy once, until the next batch
-  // or reset (tgx_value_counts_get, the two calls of tgx_value_counts_entries and tgx_finalize all gather)
-  std::vector<CountsHost> table_cache;
-  bool table_cache_ok = false;
+  const std::vector<ValueCountsTask> &tasks;  // (the plan's: their parameters are fixed once a state exists)
 
-  explicit CountsCheck(const tgx_plan *plan) : SideState(plan), dev_part(plan->value_counts.size()) {}
+  explicit CountsCheck(const tgx_plan *plan)
+      : CountedState(plan), dev_part(plan->value_counts.size()), tasks(plan->value_counts) {}
+
+  size_t lens_at(size_t k) const { return table[k].extra_at(); }
+  size_t store_at(size_t k) const { return lens_at(k) + (size_t)table[k].slots * 4; }
 
   ValueCountsTable view(const tgx_state *st, size_t k) const {
     const Dev &d = dev_part[k];
-    uint8_t *base = d.table.as<uint8_t>();
+    const uint64_t slots = table[k].slots;
+    uint8_t *base = table[k].buf.as<uint8_t>();
     ValueCountsTable t;
     memset(&t, 0, sizeof(t));
     t.keys = (unsigned long long *)base;
-    t.keys2 = d.kind == kByteValues ? t.keys + d.slots : nullptr;
-    t.counts = (unsigned long long *)(base + d.counts_at());
-    t.lens = d.kind == kByteValues ? (uint32_t *)(base + d.lens_at()) : nullptr;
-    t.store = d.kind == kByteValues ? base + d.store_at() : nullptr;
+    t.keys2 = d.kind == kByteValues ? t.keys + slots : nullptr;
+    t.counts = (unsigned long long *)(base + table[k].counts_at());
+    t.lens = d.kind == kByteValues ? (uint32_t *)(base + lens_at(k)) : nullptr;
+    t.store = d.kind == kByteValues ? base + store_at(k) : nullptr;
     t.words = d_counts.as<unsigned long long>() + word_off[k];
-    t.mask = d.slots - 1;
+    t.mask = slots - 1;
     t.salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
-    t.max_value_bytes = d.max_value_bytes;
+    t.max_value_bytes = tasks[k].params.max_value_bytes;
     return t;
-  }
-
-  tgx_status clear_table(tgx_state *st, size_t k, tgx_error *err) {
-    const Dev &d = dev_part[k];
-    if (d.kind == kNoValues) return TGX_OK;
-    uint8_t *base = d.table.as<uint8_t>();
-    HIP_TRY(hipMemsetAsync(base, 0xFF, d.key_bytes(), st->stream));  // (every key word: kEmptyKey)
-    HIP_TRY(hipMemsetAsync(base + d.counts_at(), 0, (size_t)d.slots * 8, st->stream));
-    return TGX_OK;
-  }
-
-  tgx_status device_clear_extra(tgx_state *st, tgx_error *err) override {
-    table_cache_ok = false;
-    for (size_t k = 0; k < dev_part.size(); k++) TGX_TRY(clear_table(st, k, err));
-    return TGX_OK;
   }
 
   tgx_status ensure_table(tgx_state *st, size_t k, int kind, tgx_error *err) {
@@ -250,12 +212,11 @@ struct CountsCheck final : SideState<CountsKind> {
     if (d.kind != kNoValues && device_rows[k] > 0)
       return fail(err, TGX_INVALID_ARGUMENT, "VALUE_COUNTS task %zu: the column changed between integer and string values",
                   k);
-    const tgx_value_counts_params &p = st->plan->value_counts[k].params;
+    const tgx_value_counts_params &p = tasks[k].params;
+    const bool strings = kind == kByteValues;
+    TGX_TRY(open_table(st, k, p.max_distinct, strings ? 2 : 1, strings ? 4 + (size_t)p.max_value_bytes : 0, err));
     d.kind = kind;
-    d.slots = table_slots(p.max_distinct);
-    d.max_value_bytes = p.max_value_bytes;
-    HIP_TRY(d.table.reserve(d.bytes()));
-    return clear_table(st, k, err);
+    return TGX_OK;
   }
 
   tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
@@ -306,38 +267,15 @@ struct CountsCheck final : SideState<CountsKind> {
     return TGX_OK;
   }
 
-  // the tables' entries into the gathered hosts (the counters are already there)
-  tgx_status gather_extra(tgx_state *st, std::vector<CountsHost> *out, tgx_error *err) override {
-    std::vector<uint8_t> h;
-    if (!table_cache_ok) table_cache.assign(dev_part.size(), CountsHost());
-    for (size_t k = 0; k < dev_part.size() && !table_cache_ok; k++) {
-      const Dev &d = dev_part[k];
-      if (d.kind == kNoValues || device_rows[k] == 0) continue;
-      h.resize(d.bytes());
-      HIP_TRY(hipMemcpyAsync(h.data(), d.table.p, h.size(), hipMemcpyDeviceToHost, st->stream));
-      HIP_TRY(hipStreamSynchronize(st->stream));
-      const uint64_t *keys = (const uint64_t *)h.data();
-      const uint64_t *counts = (const uint64_t *)(h.data() + d.counts_at());
-      CountsHost &o = table_cache[k];
-      for (uint64_t s = 0; s < d.slots; s++) {
-        if (keys[s] == kEmptyKey || counts[s] == 0) continue;
-        if (o.kind == kNoValues) o.kind = d.kind;
-        if (d.kind == kIntValues) {
-          o.ints[(int64_t)keys[s]] += counts[s];
-        } else {
-          const uint32_t len = std::min(((const uint32_t *)(h.data() + d.lens_at()))[s], d.max_value_bytes);
-          o.strs[std::string((const char *)h.data() + d.store_at() + (size_t)s * d.max_value_bytes, len)] += counts[s];
-        }
-      }
+  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, CountsHost &o) const override {
+    const Dev &d = dev_part[k];
+    if (o.kind == kNoValues) o.kind = d.kind;
+    if (d.kind == kIntValues) {
+      o.ints[(int64_t)((const uint64_t *)h)[s]] += count;
+    } else {
+      const uint32_t most = tasks[k].params.max_value_bytes, len = std::min(((const uint32_t *)(h + lens_at(k)))[s], most);
+      o.strs[std::string((const char *)h + store_at(k) + (size_t)s * most, len)] += count;
     }
-    table_cache_ok = true;
-    for (size_t k = 0; k < dev_part.size(); k++) {  // (only the entries: the counters came with the words)
-      CountsHost &o = (*out)[k];
-      if (o.kind == kNoValues) o.kind = table_cache[k].kind;
-      for (const auto &e : table_cache[k].ints) o.ints[e.first] += e.second;
-      for (const auto &e : table_cache[k].strs) o.strs[e.first] += e.second;
-    }
-    return TGX_OK;
   }
 
   // (integer values and string values do not unite: SideState's merge knows one shape per kind)
@@ -347,8 +285,8 @@ struct CountsCheck final : SideState<CountsKind> {
     TGX_TRY(gather(st, &mine, err));
     for (size_t k = 0; k < theirs.size(); k++)
       if (theirs[k].kind != kNoValues && mine[k].kind != kNoValues && theirs[k].kind != mine[k].kind)
-        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", CountsKind::kName,
-                    k, CountsKind::kDiffers);
+        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", kName, k,
+                    CountsKind::kDiffers);
     for (size_t k = 0; k < theirs.size(); k++) CountsKind::merge_host(host[k], theirs[k]);
     return TGX_OK;
   }
@@ -408,7 +346,12 @@ tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err) {
   return TGX_OK;
 }
 
-tgx_status valuecounts_check_type(int column, int type, tgx_error *err) {
+void valuecounts_mark_columns(tgx_plan *plan) {
+  for (const ValueCountsTask &t : plan->value_counts) side_mark(plan, CountsCheck::kIndex, t.column, true);
+}
+
+tgx_status valuecounts_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  const int type = c.type;
   if (type == TGX_FLOAT64 || type == TGX_FLOAT32 || type == TGX_UINT64 || type == TGX_BOOL)
     return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_COUNTS takes integer and string columns, not %s (type %d)", column,
                 type_name(type), type);
@@ -475,17 +418,9 @@ extern "C" tgx_status tgx_value_counts_entries(const tgx_plan *plan, tgx_state *
   TGX_TRY(static_cast<CountsCheck *>(CountsCheck::of(st))->read_task(st, slot, &h, err));
   uint64_t need_bytes = 0;
   for (const auto &e : h.strs) need_bytes += e.first.size();
-  *n_entries = h.distinct();
-  *n_bytes = need_bytes;
   *is_bytes = h.kind == kByteValues ? 1 : 0;
-  if (entries && cap < *n_entries)
-    return fail(err, TGX_INVALID_ARGUMENT, "entries holds %llu entries, %llu are needed", (unsigned long long)cap,
-                (unsigned long long)*n_entries);
-  if (bytes && bytes_cap < need_bytes)
-    return fail(err, TGX_INVALID_ARGUMENT, "bytes holds %llu bytes, %llu are needed", (unsigned long long)bytes_cap,
-                (unsigned long long)need_bytes);
+  TGX_TRY(counted_entries_sizes(h.distinct(), need_bytes, entries, cap, n_entries, bytes, bytes_cap, n_bytes, err));
   if (!entries) return TGX_OK;
-  if (need_bytes && !bytes) return fail(err, TGX_INVALID_ARGUMENT, "string values need a byte buffer");
   size_t i = 0;
   uint64_t at = 0;
   for (const auto &e : h.ints) entries[i++] = tgx_value_count_entry{e.first, 0, 0, e.second};

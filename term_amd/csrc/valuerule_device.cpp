@@ -60,8 +60,8 @@ struct RuleKind {
   typedef RuleHost Host;
   typedef NoRange Range;
   static constexpr bool kRanged = false;
-  static constexpr int kIndex = kSideRule;
-  static constexpr const char *kName = "VALUE_RULE", *kDiffers = nullptr;  // (every host has the one shape)
+  static constexpr int kKind = TGX_CHECK_VALUE_RULE;
+  static constexpr const char *kDiffers = nullptr;  // (every host has the one shape)
   static constexpr uint32_t kMagic = 0x4c525656;  // "VVRL"
 
   static const std::vector<ValueRuleTask> &tasks(const tgx_plan *plan) { return plan->rules; }
@@ -200,6 +200,17 @@ tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err) {
     if (!t.set)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a VALUE_RULE check needs its parameters (tgx_plan_set_value_rule)",
                   t.spec_index);
+  return TGX_OK;
+}
+
+void valuerule_mark_columns(tgx_plan *plan) {
+  for (const ValueRuleTask &t : plan->rules) side_mark(plan, RuleCheck::kIndex, t.column, true);
+}
+
+tgx_status valuerule_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  if (!is_numeric(c.type) && !(is_widened(c.type) && c.type != TGX_BOOL))
+    return fail(err, TGX_UNSUPPORTED, "column %d: VALUE_RULE takes numeric columns other than UInt64 (type %d)", column,
+                c.type);
   return TGX_OK;
 }
 

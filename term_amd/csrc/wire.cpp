@@ -113,10 +113,7 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
                   "that key (tgx_plan_set_fingerprint_key) before its first state", hex);
     }
   }
-  TGX_TRY(temporal_plan_ready(plan, err));
-  TGX_TRY(valuerule_plan_ready(plan, err));
-  TGX_TRY(valuecounts_plan_ready(plan, err));
-  TGX_TRY(paircounts_plan_ready(plan, err));
+  TGX_TRY(side_plans_ready(plan, err));
   std::unique_ptr<tgx_state, void (*)(tgx_state *)> st(new tgx_state(), tgx_state_destroy);
   state_init_host(st.get(), plan);
   for (auto &a : st->h_scan) a = r.pod<ScanAcc>();

@@ -3,11 +3,15 @@ every kind's second launch, its slot arithmetic and its share of the counter buf
 (three workgroups of 8192 rows), 10 % NULLs, one column at Arrow offset 1, DEVICE memory, every batch launched as it
 arrives.  The references are tests/exact_histogram.py, exact_joint.py and exact_temporal.py (plain Python, neither the
 library nor the oracle); every count is compared for equality, the histogram's two sums are held to
-exact_histogram.sum_bounds.  Then reset and the first half alone; then two half-states merged and sent through a blob."""
+exact_histogram.sum_bounds.  Then reset and the first half alone; then two half-states merged and sent through a blob.
+
+Below that, all six kinds of side_check.h in one plan, held against plans of one kind each; and the refusals of a
+column that two kinds read, with their texts."""
 import math
 from fractions import Fraction
 
 import numpy as np
+import pyarrow as pa
 import pytest
 
 import exact_histogram as eh
@@ -193,3 +197,186 @@ def test_nine_tasks_of_each_kind_against_the_exact_references(tasks):
     back = T.State.deserialize(plan, blob)
     tasks.check(back, 0, N)
     assert back.serialize() == blob
+
+
+# ---- all six kinds of the skeleton in one plan ---------------------------------------------------------------------------
+ROWS, FIRST = 1000, 600
+
+
+class SixKinds:
+    """1 000 rows in HOST memory and two specs of each of the six kinds, the kinds interleaved; each kind's two tasks differ
+    in their parameters, so a task that reads its neighbour's counters, range slot or table answers wrongly (no table
+    overflows: which keys an overflowing table keeps is decided by the order in which the lanes arrive).  The shapes
+    are small because what is held here is host plumbing (word offsets, slot binding, the order of the blob's sections,
+    the per-column flags); the kernels have their own tests on large shapes."""
+
+    def __init__(self):
+        rng = np.random.default_rng(46)
+        x = rng.standard_normal(ROWS) * 50.0
+        x[17], x[701] = np.nan, np.inf
+        a = rng.integers(-30 * 365 * MS_DAY, 30 * 365 * MS_DAY, ROWS, dtype=np.int64)
+        b = a + rng.integers(-3000, 30000, ROWS, dtype=np.int64)
+        k = rng.integers(0, 20, ROWS, dtype=np.int64) * 3 - 7
+        words = ["w%02d" % i + "x" * (i % 5) for i in range(20)]
+        s = [words[i] for i in rng.integers(0, 20, ROWS)]
+        self.x = [v if ok else None for v, ok in zip(x.tolist(), (rng.random(ROWS) >= 0.1).tolist())]
+        arrays = [pa.array(self.x, pa.float64()), pa.array(a), pa.array(b), pa.array(k), pa.array(s, pa.string())]
+        self.columns = []
+        for arr in arrays:
+            col = T.Column.from_arrow(arr)
+            col.c.mem = T.MEM_HOST
+            self.columns.append(col)
+        self.edges = eh.edges_of(-100.0, 100.0, 6)
+        # (kind, column, column2, how the plan is told the task's parameters)
+        self.tasks = [
+            (T.JOINT_BINS, 0, 1, lambda p, i: p.set_joint_binning(i, -150.0, 30.0, float(a.min()), 2e11, 10)),
+            (T.TEMPORAL, 1, 2, lambda p, i: p.set_temporal(i, et.ORDER, delta=0)),
+            (T.HISTOGRAM, 0, -1, lambda p, i: p.set_histogram_edges(i, self.edges)),
+            (T.VALUE_RULE, 0, -1, lambda p, i: p.set_value_rule(i, T.RULE_GE_ZERO)),
+            (T.VALUE_COUNTS, 3, -1, lambda p, i: p.set_value_counts(i, max_distinct=100, max_value_bytes=8)),
+            (T.PAIR_COUNTS, 4, 3, lambda p, i: p.set_pair_counts(i, x="value", y=(-7.0, 6.0, 10), max_pairs=1000)),
+            (T.JOINT_BINS, 2, 1, lambda p, i: None),  # stays in its range phase
+            (T.TEMPORAL, 2, -1, lambda p, i: p.set_temporal(i, et.RANGE, flags=et.KEEP_NULLS, lo=0)),
+            (T.HISTOGRAM, 0, -1, lambda p, i: None),  # stays in its range phase
+            (T.VALUE_RULE, 3, -1, lambda p, i: p.set_value_rule(i, T.RULE_BETWEEN, lo_i=-1, hi_i=20)),
+            (T.VALUE_COUNTS, 4, -1, lambda p, i: p.set_value_counts(i, max_distinct=16, max_value_bytes=5)),
+            (T.PAIR_COUNTS, 3, 4, lambda p, i: p.set_pair_counts(i, x=(-7.0, 20.0, 3), y="value", max_pairs=64,
+                                                                 max_value_bytes=5)),
+        ]
+        self.exact = {}
+
+    def batch(self, lo, hi):
+        return [c.sliced(lo, hi - lo) for c in self.columns]
+
+    def plan(self, which):
+        plan = T.Plan([spec(self.tasks[t][0], self.tasks[t][1], column2=self.tasks[t][2]) for t in which])
+        for i, t in enumerate(which):
+            self.tasks[t][3](plan, i)
+        return plan
+
+    def read(self, st, which, lo, hi):
+        """per task of `which`: everything its kind's getters give (NaNs as text: they compare unequal to themselves);
+        a ranged histogram's two sums are held to the exact sums' bounds here and left out"""
+        results = st.finalize()
+        out = {}
+        for i, t in enumerate(which):
+            kind, r = self.tasks[t][0], results[i]
+            got = [(r.kind, r.total, r.non_null, r.distinct, r.matches)]
+            if kind == T.JOINT_BINS:
+                got += [st.joint_range(i), st.joint_counts(i) if t == 0 else None]
+            elif kind == T.TEMPORAL:
+                got.append(st.temporal_counts(i))
+            elif kind == T.HISTOGRAM:
+                rng = st.histogram_range(i)
+                sums = [rng.pop("sum"), rng.pop("sum_squared")]
+                if t == 8:
+                    if (lo, hi) not in self.exact:
+                        self.exact[(lo, hi)] = eh.value_range(self.x[lo:hi])
+                    want = self.exact[(lo, hi)]
+                    for name, have, bound in zip(("sum", "sum_squared"), sums, eh.sum_bounds(want)):
+                        diff = abs(Fraction(have) - want[name])
+                        print("rows [%d, %d) %s: got %.17g, |diff| %.3g, bound %.3g" % (lo, hi, name, have, float(diff),
+                                                                                       float(bound)))
+                        assert diff <= bound, (lo, hi, name)
+                got += [rng, st.histogram_counts(i) if t == 2 else None]
+            elif kind == T.VALUE_RULE:
+                got.append(st.value_rule_counts(i))
+            elif kind == T.VALUE_COUNTS:
+                summary, counts = st.value_counts(i)
+                got += [summary, list(counts.items())]
+            else:
+                summary, counts = st.pair_counts(i)
+                got += [summary, list(counts.items())]
+            out[t] = repr(got)
+        return out
+
+    def walk(self, which):
+        """the four ways a state comes to its answer, each read through `read`: both batches; reset and the first batch
+        alone; two states of one batch each, merged; that state through a blob (which must serialize to itself)"""
+        plan = self.plan(which)
+        st = T.State(plan)
+        st.update(self.batch(0, FIRST))
+        st.update(self.batch(FIRST, ROWS))
+        out = {"both": self.read(st, which, 0, ROWS)}
+        st.reset()
+        st.update(self.batch(0, FIRST))
+        out["first"] = self.read(st, which, 0, FIRST)
+        other = T.State(plan)
+        other.update(self.batch(FIRST, ROWS))
+        out["second"] = self.read(other, which, FIRST, ROWS)
+        st.merge([other])
+        out["merged"] = self.read(st, which, 0, ROWS)
+        blob = st.serialize()
+        back = T.State.deserialize(plan, blob)
+        out["blob"] = self.read(back, which, 0, ROWS)
+        assert back.serialize() == blob
+        return out
+
+
+def test_six_kinds_in_one_plan_answer_as_each_kind_alone():
+    T.init()
+    six = SixKinds()
+    together = six.walk(list(range(12)))
+    assert together["both"] == together["merged"] == together["blob"]
+    assert together["both"] != together["first"]
+    for first in range(6):  # the two tasks of one kind, alone in a plan
+        alone = six.walk([first, first + 6])
+        for step, answers in alone.items():
+            for t, answer in answers.items():
+                assert together[step][t] == answer, (step, t)
+    # the comparison is worth something: the two tasks of a kind answer differently
+    assert all(together["both"][t] != together["both"][t + 6] for t in range(6))
+
+
+# ---- refusals where two kinds read one column ----------------------------------------------------------------------------
+def host_column(values, type):
+    col = T.Column.from_arrow(pa.array(values, type))
+    col.c.mem = T.MEM_HOST
+    return col
+
+
+WORDS8 = ["a", "b", "c", "a", "b", "a", "d", "a"]
+FLOATS8 = [0.5, 1.5, 2.5, 3.5, 4.5, 5.5, 6.5, 7.5]
+INTS8 = list(range(8))
+
+
+def refused(plan, batch, text):
+    st = T.State(plan)
+    with pytest.raises(T.TgxError) as e:
+        st.update(batch)
+    assert e.value.status == "TGX_UNSUPPORTED" and str(e.value) == "TGX_UNSUPPORTED: " + text
+    return st  # (the refused batch went to the very state that is read afterwards)
+
+
+def test_a_string_column_under_joint_bins_and_histogram_is_refused_by_joint_bins():
+    T.init()
+    plan = T.Plan([spec(T.JOINT_BINS, 0, column2=1), spec(T.HISTOGRAM, 0)])
+    st = refused(plan, [host_column(WORDS8, pa.string()), host_column(FLOATS8, pa.float64())],
+                 "column 0: JOINT_BINS takes numeric columns (type 3)")
+    st.update([host_column(FLOATS8, pa.float64()), host_column(FLOATS8, pa.float64())])
+    assert st.joint_range(0)["n"] == 8 and st.histogram_range(1)["n"] == 8
+
+
+def test_a_string_column_under_histogram_and_temporal_is_refused_by_temporal():
+    T.init()
+    plan = T.Plan([spec(T.HISTOGRAM, 0), spec(T.TEMPORAL, 0, column2=-1)])
+    plan.set_temporal(1, et.RANGE, lo=2)
+    # (the kinds are asked in the order of their registration, TEMPORAL before HISTOGRAM; before there was one, HISTOGRAM
+    # was asked first and this read "column 0: HISTOGRAM takes numeric columns (type 3)")
+    st = refused(plan, [host_column(WORDS8, pa.string())], "column 0: TEMPORAL takes Int64-shaped columns (type 3)")
+    st.update([host_column(INTS8, pa.int64())])
+    assert st.histogram_range(0)["n"] == 8
+    assert st.temporal_counts(1) == et.counts(et.RANGE, {"lo": 2}, INTS8, None, [True] * 8, None) == (8, 8, 2)
+
+
+def test_a_float_column_under_value_counts_and_a_binned_pair_side_is_refused_by_value_counts():
+    T.init()
+    plan = T.Plan([spec(T.VALUE_COUNTS, 0), spec(T.PAIR_COUNTS, 0, column2=1)])
+    plan.set_value_counts(0)
+    plan.set_pair_counts(1, x=(0.0, 2.0, 4), y="value")
+    st = refused(plan, [host_column(FLOATS8, pa.float64()), host_column(WORDS8, pa.string())],
+                 "column 0: VALUE_COUNTS takes integer and string columns, not Float64 (type 2)")
+    st.update([host_column(INTS8, pa.int64()), host_column(WORDS8, pa.string())])
+    assert st.value_counts(0)[1] == {v: 1 for v in range(8)}
+    assert st.pair_counts(1)[1] == {(0, b"a"): 1, (0, b"b"): 1, (1, b"c"): 1, (1, b"a"): 1, (2, b"b"): 1, (2, b"a"): 1,
+                                    (3, b"d"): 1, (3, b"a"): 1}
