@@ -317,7 +317,32 @@ typedef enum tgx_check_kind {
    * different pairs) and every entry keeps its bytes; across states, blobs and ranks entries are united by their bytes
    * (and bin indices).  tgx_merge, state blobs and tgx_allreduce unite by value and add the counters; a range-phase
    * state merges MIN / MAX / counters as JOINT_BINS's does. */
-  TGX_CHECK_PAIR_COUNTS = 16
+  TGX_CHECK_PAIR_COUNTS = 16,
+  /* Completeness per group, "metrics per segment": the GROUP BY behind CompletenessAnalyzer::with_grouping
+   *                          TG/analyzers/grouped.rs, TG/analyzers/basic/grouped_completeness.rs:160-200
+   *   SELECT g, COUNT(*) AS total_count, COUNT(col) AS non_null_count FROM t GROUP BY g
+   * for a BOUNDED number of groups: `column` is the value column col, of which only the validity is read (every type
+   * TGX_CHECK_COUNT takes, validity-only columns included), `column2` is the group column g; the bounds come with
+   * tgx_plan_set_group_counts (below); a spec without them makes tgx_state_create fail.
+   * Rows with a NULL group key are a group, as in SQL: they are counted apart (null_group_rows, null_group_non_null),
+   * not in the table.  A row whose dictionary entry is NULL, or whose index lies outside the dictionary, is a NULL-key
+   * row (the rule of TGX_CHECK_VALUE_COUNTS).
+   * Group columns: those of TGX_CHECK_VALUE_COUNTS -- the Int64-shaped ones, Int32 / Date32 and Int8 .. UInt32 through
+   * the widening staging, Utf8, LargeUtf8, Utf8View and Dictionary<Int32, Utf8>.  Float32 / Float64, UInt64, Boolean
+   * and validity-only group columns are TGX_UNSUPPORTED from tgx_update, and the state stays usable afterwards.
+   * Nothing is approximated: every row is in exactly one of an entry, the NULL group, overflow_rows (its key found no
+   * slot in the table) and long_rows (a string key longer than max_value_bytes), and so is every row with a non-NULL
+   * value:
+   *   counted + null_group_rows + overflow_rows + long_rows == seen
+   *   counted_non_null + null_group_non_null + overflow_non_null + long_non_null == COUNT(col)
+   * Specs that share the group column and both bounds share one walk of the group column and one table on the device
+   * (up to eight value columns a walk, each adding one validity bit a row); the walk's shared counters are reported in
+   * every member's summary.  The grouping guarantee is the one of TGX_CHECK_VALUE_COUNTS: within one state string keys
+   * are grouped by their 128-bit keyed fingerprint and every entry keeps its bytes; across states, blobs and ranks
+   * entries are united by their bytes.  tgx_merge, state blobs and tgx_allreduce unite by value and add every counter.
+   * Read with tgx_group_counts_get and tgx_group_counts_entries; tgx_result carries total = rows seen, non_null =
+   * COUNT(col), distinct = groups held (the NULL group not among them), matches = rows counted in them. */
+  TGX_CHECK_GROUP_COUNTS = 17
 } tgx_check_kind;
 
 enum {
@@ -593,6 +618,19 @@ typedef struct tgx_pair_counts_params {
 tgx_status tgx_plan_set_pair_counts(tgx_plan *plan, size_t spec_index, const tgx_pair_counts_params *params,
                                     tgx_error *err);
 
+/* TGX_CHECK_GROUP_COUNTS: the bounds of spec `spec_index`.  Lifetime and refusals are those of
+ * tgx_plan_set_value_counts.  max_groups (1 .. TGX_GROUP_COUNTS_MAX_GROUPS) sizes the walk's table on the device: a
+ * power of two of at least 2 * max_groups slots, probed as VALUE_COUNTS's is; max_value_bytes
+ * (1 .. TGX_GROUP_COUNTS_MAX_VALUE_BYTES) is read for string group columns only: rows with a longer key are counted in
+ * long_rows / long_non_null. */
+enum { TGX_GROUP_COUNTS_MAX_GROUPS = 65536, TGX_GROUP_COUNTS_MAX_VALUE_BYTES = 256 };
+typedef struct tgx_group_counts_params {
+  uint32_t max_groups;
+  uint32_t max_value_bytes;
+} tgx_group_counts_params;
+tgx_status tgx_plan_set_group_counts(tgx_plan *plan, size_t spec_index, const tgx_group_counts_params *params,
+                                     tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -834,6 +872,36 @@ tgx_status tgx_pair_counts_entries(const tgx_plan *plan, tgx_state *state, size_
                                    tgx_pair_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
                                    uint64_t bytes_cap, uint64_t *n_bytes, tgx_error *err);
 
+/* ---- group counts (TGX_CHECK_GROUP_COUNTS; TG/analyzers/basic/grouped_completeness.rs:160-200) ----------------------- */
+typedef struct tgx_group_counts_summary {
+  uint64_t seen;                /* rows handed to tgx_update */
+  uint64_t groups;              /* non-NULL keys held; may exceed max_groups: the caller compares */
+  uint64_t counted;             /* rows counted in the entries: the sum of their totals */
+  uint64_t counted_non_null;    /* ... of them with a non-NULL value: the sum of the entries' non_null */
+  uint64_t null_group_rows;     /* rows whose group key is NULL */
+  uint64_t null_group_non_null; /* ... of them with a non-NULL value */
+  uint64_t overflow_rows;       /* rows whose key found no slot */
+  uint64_t overflow_non_null;
+  uint64_t long_rows;           /* rows whose string key is longer than max_value_bytes: they are in no entry */
+  uint64_t long_non_null;
+} tgx_group_counts_summary; /* counted + null_group_rows + overflow_rows + long_rows == seen, and the same of the
+                             * *_non_null counters == COUNT(value column) */
+tgx_status tgx_group_counts_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                tgx_group_counts_summary *out, tgx_error *err);
+/* One group: its key and its two counts.  Integer keys: `value`; string keys: bytes [offset, offset + length) of the
+ * caller's byte buffer (value is 0 there; offset and length are 0 for integers). */
+typedef struct tgx_group_count_entry {
+  int64_t value;
+  uint64_t offset, length;
+  uint64_t total;    /* COUNT(*) of the group */
+  uint64_t non_null; /* COUNT(col) of the group */
+} tgx_group_count_entry;
+/* Copies the entries, ascending by key, in the convention of tgx_value_counts_entries (order, size query, a too-small
+ * buffer is TGX_INVALID_ARGUMENT with nothing copied, *is_bytes).  The NULL group is not an entry: it is in the summary. */
+tgx_status tgx_group_counts_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                    tgx_group_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
+                                    uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -923,7 +991,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

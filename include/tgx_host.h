@@ -133,7 +133,8 @@ tgx_status tgx_host_metric_from_state_json(const char *analyzer_json, const char
 
 /* What an analyzer plans for columns of the given tgx_types (column_types_json: an array of tgx_type numbers parallel to
  * the analyzer's columns; 0 = unknown): {"requests": [{"kind", "column", "column2", "pair_counts": {"max_pairs",
- * "max_value_bytes", "x_mode", "y_mode"} (TGX_CHECK_PAIR_COUNTS only)}]}.  Needs no device. */
+ * "max_value_bytes", "x_mode", "y_mode"} (TGX_CHECK_PAIR_COUNTS only), "group_counts": {"max_groups", "max_value_bytes"}
+ * (TGX_CHECK_GROUP_COUNTS only)}]}.  Needs no device. */
 tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *column_types_json, char **out_json,
                                        tgx_error *err);
 
@@ -143,6 +144,13 @@ tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *co
  * AnalyzerError is returned as TGX_INVALID_ARGUMENT with its text in err->msg. */
 tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json, const char *pair_counts_json, char **out_state_json,
                                            tgx_error *err);
+
+/* The state a grouped_completeness analyzer builds from given group counts; needs no device.  group_counts_json:
+ * {"summary": {tgx_group_counts_summary's fields; absent ones are 0}, "entries": [[key, total, non_null], ..]} in the
+ * library's order, a key being a string, an array of byte values (a key that is no UTF-8) or an integer.  An
+ * AnalyzerError is returned as TGX_INVALID_ARGUMENT with its text in err->msg. */
+tgx_status tgx_host_group_counts_state_json(const char *analyzer_json, const char *group_counts_json,
+                                            char **out_state_json, tgx_error *err);
 
 void tgx_host_free(char *s);
 

@@ -25,6 +25,8 @@ VALUE_COUNTS_MAX_DISTINCT, VALUE_COUNTS_MAX_VALUE_BYTES = 65536, 256
 PAIR_COUNTS = 16  # how often each pair of cells of two columns occurs, for a bounded number of pairs (Plan.set_pair_counts)
 PAIR_SIDE_VALUE, PAIR_SIDE_RANGE, PAIR_SIDE_BINNED = 0, 1, 2
 PAIR_COUNTS_MAX_PAIRS, PAIR_COUNTS_MAX_VALUE_BYTES = 65536, 256
+GROUP_COUNTS = 17  # COUNT(*) and COUNT(col) per group of a second column, for a bounded number of groups (Plan.set_group_counts)
+GROUP_COUNTS_MAX_GROUPS, GROUP_COUNTS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -172,6 +174,24 @@ class PairCountEntry(C.Structure):
                 ("y_offset", C.c_uint64), ("y_length", C.c_uint64), ("count", C.c_uint64)]
 
 
+class GroupCountsParams(C.Structure):
+    """tgx_group_counts_params (include/tgx.h)"""
+    _fields_ = [("max_groups", C.c_uint32), ("max_value_bytes", C.c_uint32)]
+
+
+class GroupCountsSummary(C.Structure):
+    """tgx_group_counts_summary (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("groups", C.c_uint64), ("counted", C.c_uint64), ("counted_non_null", C.c_uint64),
+                ("null_group_rows", C.c_uint64), ("null_group_non_null", C.c_uint64), ("overflow_rows", C.c_uint64),
+                ("overflow_non_null", C.c_uint64), ("long_rows", C.c_uint64), ("long_non_null", C.c_uint64)]
+
+
+class GroupCountEntry(C.Structure):
+    """tgx_group_count_entry (include/tgx.h)"""
+    _fields_ = [("value", C.c_int64), ("offset", C.c_uint64), ("length", C.c_uint64), ("total", C.c_uint64),
+                ("non_null", C.c_uint64)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -306,6 +326,10 @@ def lib():
         L.tgx_pair_counts_get.argtypes = [vp, vp, sz, C.POINTER(PairCountsSummary), E]
         L.tgx_pair_range_get.argtypes = [vp, vp, sz, C.POINTER(PairRange), E]
         L.tgx_pair_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
+        L.tgx_plan_set_group_counts.argtypes = [vp, sz, C.POINTER(GroupCountsParams), E]
+        L.tgx_group_counts_get.argtypes = [vp, vp, sz, C.POINTER(GroupCountsSummary), E]
+        L.tgx_group_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
+                                               C.POINTER(C.c_int32), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -740,6 +764,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_value_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_group_counts(self, spec_index, max_groups=10000, max_value_bytes=256):
+        """tgx_plan_set_group_counts: the bounds of a GROUP_COUNTS spec (before the plan's first state)"""
+        p = GroupCountsParams(max_groups, max_value_bytes)
+        err = _Error()
+        _check(lib().tgx_plan_set_group_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def set_pair_counts(self, spec_index, x=None, y=None, max_pairs=10000, max_value_bytes=256):
         """tgx_plan_set_pair_counts: the bounds and the sides of a PAIR_COUNTS spec (before the plan's first state).  A
         side is None or "value" (a string column: PAIR_SIDE_VALUE), "range" (a numeric column: the spec is in its range
@@ -999,6 +1029,23 @@ class State:
             counts[(cx, cy)] = e.count
         summary = {f: getattr(s, f) for f, _ in PairCountsSummary._fields_}
         return summary, counts
+
+    # group counts
+    def group_counts(self, spec_index):
+        """tgx_group_counts_get + tgx_group_counts_entries: (summary, groups) -- summary a dict of the ten counters (seen,
+        groups, counted, counted_non_null, null_group_rows, null_group_non_null, overflow_rows, overflow_non_null,
+        long_rows, long_non_null), groups a dict key -> (total, non_null) in the library's order (ascending by key); its
+        keys are ints for an integer group column and bytes for a string one.  The NULL group is in the summary"""
+        L, err = lib(), _Error()
+        s = GroupCountsSummary()
+        _check(L.tgx_group_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        is_bytes = C.c_int32()
+        entries, raw = self._counted_entries(L.tgx_group_counts_entries, GroupCountEntry, spec_index, C.byref(is_bytes))
+        groups = {}
+        for e in entries:
+            groups[raw[e.offset:e.offset + e.length] if is_bytes.value else e.value] = (e.total, e.non_null)
+        summary = {f: getattr(s, f) for f, _ in GroupCountsSummary._fields_}
+        return summary, groups
 
     def pair_range(self, spec_index):
         """tgx_pair_range_get: dict(seen, both_non_null, n, non_finite, min, max) of a spec in its range phase"""

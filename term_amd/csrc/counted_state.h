@@ -1,4 +1,4 @@
-// counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS: the
+// counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS: the
 // bounded GROUP BY of kernels/count_table.h): the table's size and layout, clearing it, reading it back once between
 // batches, and the two places where sizes come from outside -- a blob's entries and the buffers of the *_entries calls.
 #pragma once
@@ -14,13 +14,14 @@ TGX_HIDDEN inline uint64_t table_slots(uint32_t bound) {
 }
 
 // one task's table: `key_words` arrays of `slots` 64-bit key words (kEmptyKey: free), the slots' 64-bit counts, then
-// `extra` bytes a slot that the kind lays out (arrays of `slots` elements, from extra_at() on)
+// `extra` bytes a slot that the kind lays out (arrays of `slots` elements, from extra_at() on); the first
+// `extra_counters` bytes a slot of them are further counters of the slot, cleared with its count
 struct TGX_HIDDEN CountedTable {
   DevBuf buf;
   bool live = false;  // allocated (at the task's first batch) and cleared
   uint64_t slots = 0;
   int key_words = 0;
-  size_t extra = 0;
+  size_t extra = 0, extra_counters = 0;
   size_t key_bytes() const { return (size_t)slots * 8 * key_words; }
   size_t counts_at() const { return key_bytes(); }
   size_t extra_at() const { return counts_at() + (size_t)slots * 8; }
@@ -49,7 +50,7 @@ struct TGX_HIDDEN CountedState : SideState<K> {
     if (!t.live) return TGX_OK;
     uint8_t *base = t.buf.template as<uint8_t>();
     HIP_TRY(hipMemsetAsync(base, 0xFF, t.key_bytes(), st->stream));  // (every key word: kEmptyKey)
-    HIP_TRY(hipMemsetAsync(base + t.counts_at(), 0, (size_t)t.slots * 8, st->stream));
+    HIP_TRY(hipMemsetAsync(base + t.counts_at(), 0, (size_t)t.slots * (8 + t.extra_counters), st->stream));
     return TGX_OK;
   }
 
@@ -60,11 +61,13 @@ struct TGX_HIDDEN CountedState : SideState<K> {
   }
 
   // task k's table made for up to `bound` keys in the given layout, and cleared
-  tgx_status open_table(tgx_state *st, size_t k, uint32_t bound, int key_words, size_t extra, tgx_error *err) {
+  tgx_status open_table(tgx_state *st, size_t k, uint32_t bound, int key_words, size_t extra, tgx_error *err,
+                        size_t extra_counters = 0) {
     CountedTable &t = table[k];
     t.slots = table_slots(bound);
     t.key_words = key_words;
     t.extra = extra;
+    t.extra_counters = extra_counters;
     HIP_TRY(t.buf.reserve(t.bytes()));
     t.live = true;
     return clear_table(st, k, err);
@@ -90,6 +93,24 @@ struct TGX_HIDDEN CountedState : SideState<K> {
   }
 };
 
+// the kernels' view of a string column (a dictionary's values included); `buffers`: the device copy of a Utf8View's
+// table of data-buffer pointers
+TGX_HIDDEN inline Utf8ColDesc string_desc(const tgx_column &c, const uint8_t *const *buffers, const FpKey &key) {
+  Utf8ColDesc d;
+  memset(&d, 0, sizeof(d));
+  const bool view = c.type == TGX_UTF8_VIEW;
+  d.offsets = c.offsets;
+  d.data = c.data;
+  d.validity = c.validity;
+  d.offset = c.offset;
+  d.length = c.length;
+  d.large_offsets = c.type == TGX_LARGE_UTF8;
+  d.views = view ? c.values : nullptr;
+  d.buffers = view ? buffers : nullptr;
+  d.key = key;
+  return d;
+}
+
 // A task's entries in a blob: n x { key, u64 count }, strictly ascending by key, into the empty map `m`; *counted: the
 // sum of their counts.  `least`: the fewest bytes an entry takes.  read_key(key) reads one key and may refuse it.
 // TGX_OK with r.ok cleared: the blob ran out
@@ -114,6 +135,41 @@ TGX_HIDDEN inline tgx_status counted_read_entries(const char *name, size_t k, Re
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: counts)", name, k);
     *counted += c;
     m.emplace_hint(m.end(), std::move(key), c);
+  }
+  return TGX_OK;
+}
+
+// The sibling for entries with a second counter: n x { key, u64 total, u64 non_null }, non_null <= total, into the map
+// `m` of key -> Counts{total, non_null}; *counted / *counted_non_null: the sums
+template <class Map, class ReadKey>
+TGX_HIDDEN inline tgx_status counted_read_entries2(const char *name, size_t k, Reader &r, uint64_t n, size_t least, Map &m,
+                                                   uint64_t *counted, uint64_t *counted_non_null, ReadKey read_key,
+                                                   tgx_error *err) {
+  size_t bytes = 0;  // (held against the bytes that are left before anything is allocated)
+  if (!r.fits(n, least, &bytes)) return TGX_OK;
+  *counted = *counted_non_null = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    typename Map::key_type key;
+    TGX_TRY(read_key(key));
+    const uint64_t c = r.pod<uint64_t>(), nn = r.pod<uint64_t>();
+    if (!r.ok) return TGX_OK;
+    if (!m.empty() && !(m.rbegin()->first < key))
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu is out of order or repeated)",
+                  name, k, (unsigned long long)i);
+    if (c == 0)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu has a zero count)", name, k,
+                  (unsigned long long)i);
+    if (nn > c)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu has non_null > total)", name,
+                  k, (unsigned long long)i);
+    if (c > UINT64_MAX - *counted)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: counts)", name, k);
+    *counted += c;
+    *counted_non_null += nn;
+    typename Map::mapped_type v;
+    v.total = c;
+    v.non_null = nn;
+    m.emplace_hint(m.end(), std::move(key), v);
   }
   return TGX_OK;
 }

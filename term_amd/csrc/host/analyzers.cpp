@@ -92,6 +92,7 @@ std::string MetricValue::to_json() const {
     case Double: return "{\"type\": \"Double\", \"value\": " + num_text(d) + "}";
     case Long: return "{\"type\": \"Long\", \"value\": " + std::to_string(l) + "}";
     case Boolean: return std::string("{\"type\": \"Boolean\", \"value\": ") + (b ? "true" : "false") + "}";
+    case String: return "{\"type\": \"String\", \"value\": " + json::quote(s) + "}";
     case Map: {
       std::string o = "{\"type\": \"Map\", \"value\": {";
       for (size_t i = 0; i < map.size(); i++) o += (i ? ", " : "") + json::quote(map[i].first) + ": " + map[i].second.to_json();
@@ -926,6 +927,263 @@ class EntropyAnalyzer : public ColumnAnalyzer {
   std::string arrow_type_;
 };
 
+// basic/grouped_completeness.rs + grouped.rs: CompletenessAnalyzer::with_grouping, "completeness per segment",
+//   SELECT g, COUNT(*) AS total_count, COUNT(col) AS non_null_count FROM t GROUP BY g
+//   ORDER BY COUNT(col) * 1.0 / COUNT(*) DESC LIMIT max_groups + 1                    (grouped_completeness.rs:119-150)
+// as one TGX_CHECK_GROUP_COUNTS request.  name() stays "completeness"; metric_key() is
+// "completeness.<col>_grouped_by_<g>" (grouped.rs:288-294); the JSON tag is "grouped_completeness".
+// The reference's rules, restated:
+//   - rows come ordered by completeness descending; the first max_groups are kept; total_groups counts the rows the
+//     LIMIT let through, min(actual, max_groups + 1); `overall` sums the kept rows only (:160-200).  The order among
+//     rows of equal completeness is unspecified there: here by key ascending, the NULL group last.
+//   - a NULL key reads as "" (StringArray::value, :258-262).  When a "" group exists as well, the later of the two rows
+//     overwrites the earlier in the map, yet both count in total_groups and `overall`, so `truncated` comes out true.
+//   - included_groups is the map's size, truncated = total_groups > included_groups (grouped.rs:179-188).
+//   - a group column that is no StringArray makes the reference push the {:?} of the WHOLE key array for every row
+//     (:263-268): with strict_reference_types (the default) such a column is this analyzer's error; without, strings
+//     of every layout group by value and integers print as decimal text.
+// More than one group column, or none, is the analyzer's error: TGX_CHECK_GROUP_COUNTS groups by one column.
+// The state is ours -- the reference's BTreeMap<Vec<String>, _> does not pass through serde_json, whose map keys must
+// be strings: {"groups": [{"key": [..], "total_count", "non_null_count"}, ..ascending by key], "null_group": {..}|null,
+// "overall": {..}|null, "metadata": GroupedMetadata}.  Beyond the device's bounds the analyzer fails with the numbers.
+class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
+ public:
+  GroupedCompletenessAnalyzer(std::string c, GroupingConfig config, bool strict, std::string group_arrow_type)
+      : ColumnAnalyzer(std::move(c)), config_(std::move(config)), strict_(strict),
+        group_arrow_type_(std::move(group_arrow_type)) {}
+  std::string name() const override { return "completeness"; }
+  std::string metric_key() const override {
+    std::string joined;
+    for (size_t i = 0; i < config_.columns.size(); i++) joined += (i ? "_" : "") + config_.columns[i];
+    return "completeness." + column_ + "_grouped_by_" + joined;
+  }
+  std::vector<std::string> columns() const override {
+    std::vector<std::string> cols = {column_};
+    cols.insert(cols.end(), config_.columns.begin(), config_.columns.end());
+    return cols;
+  }
+  // the table bound on the device: max_groups, capped at what the kind takes
+  uint32_t device_bound() const {
+    const uint64_t most = TGX_GROUP_COUNTS_MAX_GROUPS;
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(config_.max_groups.value_or(most), 1), most);
+  }
+  std::vector<SpecRequest> plan() const override {
+    if (config_.columns.size() != 1)
+      throw AnalyzerError::invalid_data("grouped completeness groups by exactly one column on the GPU path (" +
+                                        std::to_string(config_.columns.size()) + " given)");
+    SpecRequest r = req(TGX_CHECK_GROUP_COUNTS, column_);
+    r.column2 = config_.columns[0];
+    r.group_counts = tgx_group_counts_params{device_bound(), TGX_GROUP_COUNTS_MAX_VALUE_BYTES};
+    return {r};
+  }
+  std::vector<SpecRequest> plan_for(const std::vector<int> &types, const std::vector<std::string> &declared) const override {
+    std::vector<SpecRequest> reqs = plan();
+    if (!strict_) return reqs;
+    const int type = types.size() > 1 ? types[1] : 0;
+    std::string t = !group_arrow_type_.empty() ? group_arrow_type_ : declared.size() > 1 ? declared[1] : std::string();
+    if (t.empty())
+      t = type == TGX_UTF8 ? "Utf8" : type == TGX_LARGE_UTF8 ? "LargeUtf8" : type == TGX_UTF8_VIEW ? "Utf8View"
+          : type == TGX_DICT32_UTF8 ? "Dictionary(Int32, Utf8)" : type == 0 ? "" : "tgx type " + std::to_string(type);
+    if (!t.empty() && t != "Utf8")
+      throw AnalyzerError::invalid_data(
+          "group column '" + config_.columns[0] + "' is " + t + ": the reference reads only a Utf8 group column by value "
+          "and pushes the {:?} of the whole key array for every row of any other (grouped_completeness.rs:263-268); "
+          "strict_reference_types=false groups strings of every layout by value and prints integers as decimal text");
+    return reqs;
+  }
+  bool reads_group_counts() const override { return true; }
+  json::Value state_from_results(const std::vector<const tgx_result *> &, const std::vector<int> &) const override {
+    throw AnalyzerError::invalid_data("the grouped completeness state is built from group counts");
+  }
+
+  struct Row {
+    bool null_key = false;
+    int64_t value = 0;
+    std::string bytes, text;
+    uint64_t total = 0, non_null = 0;
+  };
+  static double completeness(uint64_t total, uint64_t non_null) {  // CompletenessState::completeness, completeness.rs:67-73
+    return total == 0 ? 1.0 : (double)non_null / (double)total;
+  }
+  static json::Value counts(uint64_t total, uint64_t non_null) {
+    return jobj({{"total_count", jcount(total)}, {"non_null_count", jcount(non_null)}});
+  }
+  json::Value metadata(uint64_t total_groups, uint64_t included) const {
+    json::Value cols;
+    cols.type = json::Value::Array;
+    for (const std::string &c : config_.columns) cols.arr.push_back(jstr(c));
+    return jobj({{"group_columns", cols}, {"total_groups", jcount(total_groups)}, {"included_groups", jcount(included)},
+                 {"truncated", jbool(total_groups > included)}, {"overflow_strategy", jnull()}});
+  }
+  // the state's parts -> the state; `groups`: text key -> counts, any order
+  json::Value state_of(std::vector<std::pair<std::string, std::pair<uint64_t, uint64_t>>> groups, const json::Value &null_group,
+                       const json::Value &overall, const json::Value &meta) const {
+    std::sort(groups.begin(), groups.end());
+    json::Value arr;
+    arr.type = json::Value::Array;
+    for (const auto &g : groups) {
+      json::Value key;
+      key.type = json::Value::Array;
+      key.arr.push_back(jstr(g.first));
+      arr.arr.push_back(jobj({{"key", key}, {"total_count", jcount(g.second.first)}, {"non_null_count", jcount(g.second.second)}}));
+    }
+    return jobj({{"groups", arr}, {"null_group", null_group}, {"overall", overall}, {"metadata", meta}});
+  }
+
+  json::Value state_from_group_counts(const GroupCounts &gc) const override {
+    const tgx_group_counts_summary &s = gc.summary;
+    if (s.overflow_rows || s.long_rows)
+      throw AnalyzerError::invalid_data(
+          "column '" + config_.columns[0] + "' has more groups than the table for max_groups " +
+          std::to_string(device_bound()) + " holds, or keys longer than " +
+          std::to_string((int)TGX_GROUP_COUNTS_MAX_VALUE_BYTES) + " bytes: " + std::to_string(s.groups) + " groups held, " +
+          std::to_string(s.overflow_rows) + " overflow rows, " + std::to_string(s.long_rows) + " long rows");
+    std::vector<Row> rows;
+    for (const GroupCounts::Entry &e : gc.entries) {
+      Row r;
+      r.value = e.value;
+      r.bytes = e.bytes;
+      r.text = gc.is_bytes ? e.bytes : std::to_string((long long)e.value);
+      r.total = e.total;
+      r.non_null = e.non_null;
+      rows.push_back(std::move(r));
+    }
+    if (s.null_group_rows) {
+      Row r;
+      r.null_key = true;
+      r.total = s.null_group_rows;
+      r.non_null = s.null_group_non_null;
+      rows.push_back(std::move(r));
+    }
+    // ORDER BY completeness DESC; ties by key ascending (the library's order), the NULL group last
+    std::stable_sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) {
+      const double ca = completeness(a.total, a.non_null), cb = completeness(b.total, b.non_null);
+      if (ca != cb) return ca > cb;
+      return !a.null_key && b.null_key;
+    });
+    const uint64_t limit = config_.max_groups ? *config_.max_groups : UINT64_MAX;
+    const uint64_t total_groups = std::min<uint64_t>(rows.size(), limit == UINT64_MAX ? limit : limit + 1);  // LIMIT max_groups + 1
+    const size_t kept = (size_t)std::min<uint64_t>(rows.size(), limit);
+    std::vector<std::pair<std::string, std::pair<uint64_t, uint64_t>>> groups;
+    json::Value null_group = jnull();
+    uint64_t all = 0, all_non_null = 0;
+    bool empty_text = false, null_kept = false;
+    for (size_t i = 0; i < kept; i++) {
+      const Row &r = rows[i];
+      all += r.total;
+      all_non_null += r.non_null;
+      if (r.null_key) {
+        null_group = counts(r.total, r.non_null);
+        null_kept = true;
+      } else {
+        groups.push_back({r.text, {r.total, r.non_null}});
+        empty_text |= r.text.empty();
+      }
+    }
+    const uint64_t included = groups.size() + (null_kept && !empty_text ? 1 : 0);  // (NULL reads as "": one key with "")
+    return state_of(std::move(groups), null_group, config_.include_overall ? counts(all, all_non_null) : jnull(),
+                    metadata(total_groups, included));
+  }
+
+  // grouped_completeness.rs:37-84: groups by key, their states summed; the overalls summed; the first state's
+  // metadata with total_groups the maximum, included_groups the merged map's size, truncated = total > included
+  json::Value merge_states(const std::vector<json::Value> &states) const override {
+    if (states.empty()) throw AnalyzerError::custom("Invalid configuration: Cannot merge empty states");
+    std::vector<std::pair<std::string, std::pair<uint64_t, uint64_t>>> groups;
+    bool has_null = false, has_overall = false, empty_text = false;
+    uint64_t null_t = 0, null_n = 0, all_t = 0, all_n = 0, total_groups = 0;
+    for (const json::Value &st : states) {
+      if (const json::Value *gs = st.get("groups"))
+        if (gs->type == json::Value::Array)
+          for (const json::Value &g : gs->arr) {
+            const json::Value *key = g.get("key");
+            const std::string text = key && key->type == json::Value::Array && !key->arr.empty() ? key->arr[0].str : std::string();
+            auto it = std::find_if(groups.begin(), groups.end(), [&](const auto &e) { return e.first == text; });
+            if (it == groups.end()) it = groups.insert(groups.end(), {text, {0, 0}});
+            it->second.first += u(g, "total_count");
+            it->second.second += u(g, "non_null_count");
+            empty_text |= text.empty();
+          }
+      if (const json::Value *ng = st.get("null_group"))
+        if (ng->type == json::Value::Object) {
+          has_null = true;
+          null_t += u(*ng, "total_count");
+          null_n += u(*ng, "non_null_count");
+        }
+      if (const json::Value *ov = st.get("overall"))
+        if (ov->type == json::Value::Object) {
+          has_overall = true;
+          all_t += u(*ov, "total_count");
+          all_n += u(*ov, "non_null_count");
+        }
+      if (const json::Value *md = st.get("metadata")) total_groups = std::max(total_groups, u(*md, "total_groups"));
+    }
+    json::Value meta = metadata(0, 0);
+    if (const json::Value *md = states[0].get("metadata"))
+      if (const json::Value *gc = md->get("group_columns")) meta.obj[0].second = *gc;
+    const uint64_t included = groups.size() + (has_null && !empty_text ? 1 : 0);
+    meta.obj[1].second = jcount(total_groups);
+    meta.obj[2].second = jcount(included);
+    meta.obj[3].second = jbool(total_groups > included);
+    return state_of(std::move(groups), has_null ? counts(null_t, null_n) : jnull(),
+                    has_overall ? counts(all_t, all_n) : jnull(), meta);
+  }
+
+  // GroupedMetrics::to_metric_value (grouped.rs:135-156): one Double per group under key.join("_"), then "__overall__",
+  // then "__metadata__", a String holding the serde JSON of GroupedMetadata; a later insert of a key replaces the
+  // earlier, as in the reference's HashMap
+  MetricValue metric_from_state(const json::Value &st) const override {
+    MetricValue m;
+    m.kind = MetricValue::Map;
+    auto put = [&](const std::string &key, MetricValue v) {
+      for (auto &kv : m.map)
+        if (kv.first == key) {
+          kv.second = std::move(v);
+          return;
+        }
+      m.map.push_back({key, std::move(v)});
+    };
+    const json::Value *ng = st.get("null_group");
+    const bool has_null = ng && ng->type == json::Value::Object;
+    const double null_c = has_null ? completeness(u(*ng, "total_count"), u(*ng, "non_null_count")) : 0.0;
+    bool null_done = false;
+    if (const json::Value *gs = st.get("groups"))
+      if (gs->type == json::Value::Array)
+        for (const json::Value &g : gs->arr) {
+          std::string joined;
+          if (const json::Value *key = g.get("key"))
+            for (size_t i = 0; key->type == json::Value::Array && i < key->arr.size(); i++)
+              joined += (i ? "_" : "") + key->arr[i].str;
+          double c = completeness(u(g, "total_count"), u(g, "non_null_count"));
+          if (joined.empty() && has_null) {  // the "" row and the NULL row: the later in the query's order stays
+            if (null_c <= c) c = null_c;
+            null_done = true;
+          }
+          put(joined, MetricValue::of_double(c));
+        }
+    if (has_null && !null_done) put("", MetricValue::of_double(null_c));
+    if (const json::Value *ov = st.get("overall"))
+      if (ov->type == json::Value::Object)
+        put("__overall__", MetricValue::of_double(completeness(u(*ov, "total_count"), u(*ov, "non_null_count"))));
+    std::string meta = "{\"group_columns\":[";
+    const json::Value *md = st.get("metadata");
+    if (md)
+      if (const json::Value *gc = md->get("group_columns"))
+        for (size_t i = 0; gc->type == json::Value::Array && i < gc->arr.size(); i++)
+          meta += (i ? "," : "") + json::quote(gc->arr[i].str);
+    meta += "],\"total_groups\":" + std::to_string((unsigned long long)(md ? u(*md, "total_groups") : 0)) +
+            ",\"included_groups\":" + std::to_string((unsigned long long)(md ? u(*md, "included_groups") : 0)) +
+            ",\"truncated\":" + (md && md->get_bool("truncated", false) ? "true" : "false") + ",\"overflow_strategy\":null}";
+    put("__metadata__", MetricValue::of_string(meta));
+    return m;
+  }
+
+ private:
+  GroupingConfig config_;
+  bool strict_;
+  std::string group_arrow_type_;
+};
+
 }  // namespace
 
 PairCounts read_pair_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index, const tgx_pair_counts_params &params) {
@@ -954,6 +1212,38 @@ PairCounts read_pair_counts(const tgx_plan *plan, tgx_state *state, size_t spec_
     out.entries.push_back(std::move(o));
   }
   return out;
+}
+
+GroupCounts read_group_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index) {
+  GroupCounts out;
+  tgx_error err;
+  memset(&err, 0, sizeof(err));
+  auto check = [&](tgx_status s) {
+    if (s != TGX_OK) throw AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg);
+  };
+  check(tgx_group_counts_get(plan, state, spec_index, &out.summary, &err));
+  uint64_t n = 0, nb = 0;
+  int32_t is_bytes = 0;
+  check(tgx_group_counts_entries(plan, state, spec_index, nullptr, 0, &n, nullptr, 0, &nb, &is_bytes, &err));
+  std::vector<tgx_group_count_entry> entries((size_t)n + 1);
+  std::vector<uint8_t> bytes((size_t)nb + 1);
+  check(tgx_group_counts_entries(plan, state, spec_index, entries.data(), n, &n, bytes.data(), nb, &nb, &is_bytes, &err));
+  out.is_bytes = is_bytes != 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const tgx_group_count_entry &e = entries[i];
+    GroupCounts::Entry o;
+    o.value = e.value;
+    if (out.is_bytes) o.bytes.assign((const char *)bytes.data() + e.offset, (size_t)e.length);
+    o.total = e.total;
+    o.non_null = e.non_null;
+    out.entries.push_back(std::move(o));
+  }
+  return out;
+}
+
+std::shared_ptr<Analyzer> completeness_with_grouping(const std::string &column, const GroupingConfig &config,
+                                                     bool strict_reference_types, const std::string &group_arrow_type) {
+  return std::make_shared<GroupedCompletenessAnalyzer>(column, config, strict_reference_types, group_arrow_type);
 }
 
 namespace {
@@ -1017,6 +1307,18 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
   }
   if (t == "histogram")
     return std::make_shared<HistogramAnalyzer>(col(), v.get_u64("num_buckets", 10), v.get_bool("strict_reference_types", true));
+  if (t == "grouped_completeness") {
+    GroupingConfig cfg;
+    if (const json::Value *g = v.get("group_by"))
+      if (g->type == json::Value::Array)
+        for (const json::Value &e : g->arr) cfg.columns.push_back(e.type == json::Value::String ? e.str : std::string());
+    if (const json::Value *mg = v.get("max_groups")) {
+      if (mg->type == json::Value::Null) cfg.max_groups.reset();
+      else cfg.max_groups = mg->as_u64();
+    }
+    cfg.include_overall = v.get_bool("include_overall", true);
+    return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"));
+  }
   // ("entropy" stays an unknown type: the tag of EntropyAnalyzer is "value_entropy")
   if (t == "value_entropy")
     return std::make_shared<EntropyAnalyzer>(col(), v.get_u64("max_unique_values", 10000), v.get_str("arrow_type"));
@@ -1128,6 +1430,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
     for (size_t i = 0; s == TGX_OK && !follow_ups && i < requests.size(); i++) {
       if (requests[i].value_counts) s = tgx_plan_set_value_counts(hh.plan, i, &*requests[i].value_counts, &err);
       if (requests[i].pair_counts) s = tgx_plan_set_pair_counts(hh.plan, i, &*requests[i].pair_counts, &err);
+      if (s == TGX_OK && requests[i].group_counts)
+        s = tgx_plan_set_group_counts(hh.plan, i, &*requests[i].group_counts, &err);
     }
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;
@@ -1292,6 +1596,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
           } catch (const TermError &e) {
             throw AnalyzerError::query(e.display());
           }
+        } else if (an.reads_group_counts()) {
+          st = an.state_from_group_counts(read_group_counts(h.plan, h.state, planned[a].spec_index[0]));
         } else {
           st = an.two_pass()
                    ? an.state_from_follow_up(followed[a].first, followed[a].counted ? &followed[a].second : nullptr)

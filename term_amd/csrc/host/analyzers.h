@@ -29,8 +29,9 @@ struct MetricDistribution {  // types.rs:95-157; the statistics are Options ther
   std::optional<double> min, max, mean, std_dev;
 };
 struct MetricValue {
-  enum Kind { Double, Long, Map, Histogram, Boolean } kind = Double;
+  enum Kind { Double, Long, Map, Histogram, Boolean, String } kind = Double;
   double d = 0;
+  std::string s;  // String
   int64_t l = 0;
   bool b = false;
   std::vector<std::pair<std::string, MetricValue>> map;  // insertion ordered (the reference's HashMap is unordered)
@@ -45,6 +46,12 @@ struct MetricValue {
     MetricValue m;
     m.kind = Boolean;
     m.b = v;
+    return m;
+  }
+  static MetricValue of_string(std::string v) {
+    MetricValue m;
+    m.kind = String;
+    m.s = std::move(v);
     return m;
   }
   static MetricValue of_long(int64_t v) {
@@ -89,6 +96,37 @@ struct PairCounts {
 };
 PairCounts read_pair_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index,
                             const tgx_pair_counts_params &params);  // throws AnalyzerError (query)
+// one spec's state as tgx_group_counts_get / tgx_group_counts_entries answer it, in the library's order (ascending by
+// key); the NULL group is in the summary
+struct GroupCounts {
+  tgx_group_counts_summary summary = {};
+  bool is_bytes = false;  // string keys: `bytes`; integer keys: `value`
+  struct Entry {
+    int64_t value = 0;
+    std::string bytes;
+    uint64_t total = 0, non_null = 0;
+  };
+  std::vector<Entry> entries;
+};
+GroupCounts read_group_counts(const tgx_plan *plan, tgx_state *state, size_t spec_index);  // throws AnalyzerError (query)
+
+// TG/analyzers/grouped.rs:14-95: how an analyzer's metric is computed per group.  Defaults: GroupingConfig::new
+// (grouped.rs:32-39).  The overflow strategy is carried, not acted on: the reference's query orders by the metric
+// descending and keeps the first max_groups whatever it says (grouped_completeness.rs:130-150).
+enum class OverflowStrategy { TopK, BottomK, Sample, Fail };
+struct GroupingConfig {
+  std::vector<std::string> columns;
+  std::optional<uint64_t> max_groups = 10000;
+  bool include_overall = true;
+  OverflowStrategy overflow_strategy = OverflowStrategy::TopK;
+};
+class Analyzer;
+// CompletenessAnalyzer::with_grouping (grouped.rs:200-210, basic/grouped_completeness.rs): the one grouped analyzer.
+// strict_reference_types: only a group column declared Utf8 is taken (see the class in analyzers.cpp)
+std::shared_ptr<Analyzer> completeness_with_grouping(const std::string &column, const GroupingConfig &config,
+                                                     bool strict_reference_types = true,
+                                                     const std::string &group_arrow_type = std::string());
+
 struct FirstPass {  // what the request's range phase found
   int kind = 0;                   // the kind of plan()[0]
   std::vector<int> column_types;  // tgx_type of columns() in order
@@ -142,6 +180,10 @@ class Analyzer {
   virtual bool reads_value_counts() const { return false; }
   virtual std::string value_text_refusal(int /*tgx_type of the column*/) const { return std::string(); }
   virtual json::Value state_from_value_counts(const ValueCounts &) const { return json::Value(); }
+  // An analyzer whose plan()[0] is a TGX_CHECK_GROUP_COUNTS request (the grouped CompletenessAnalyzer) builds its state
+  // from the groups the device counted
+  virtual bool reads_group_counts() const { return false; }
+  virtual json::Value state_from_group_counts(const GroupCounts &) const { return json::Value(); }
   virtual bool two_pass() const { return false; }
   virtual std::optional<FollowUp> follow_up(const FirstPass &) const { return std::nullopt; }
   virtual json::Value state_from_follow_up(const FirstPass &, const SecondPass *) const { return json::Value(); }

@@ -490,6 +490,9 @@ extern "C" tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, con
         o += ", \"pair_counts\": {\"max_pairs\": " + std::to_string(r.pair_counts->max_pairs) + ", \"max_value_bytes\": " +
              std::to_string(r.pair_counts->max_value_bytes) + ", \"x_mode\": " + std::to_string(r.pair_counts->x.mode) +
              ", \"y_mode\": " + std::to_string(r.pair_counts->y.mode) + "}";
+      if (r.group_counts)
+        o += ", \"group_counts\": {\"max_groups\": " + std::to_string(r.group_counts->max_groups) +
+             ", \"max_value_bytes\": " + std::to_string(r.group_counts->max_value_bytes) + "}";
       o += "}";
     }
     o += "]}";
@@ -551,6 +554,64 @@ extern "C" tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json,
       }
     }
     *out_state_json = dup_string(json_dump(a->state_from_pair_counts(pc)));
+    return TGX_OK;
+  } catch (const AnalyzerError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.text);
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_group_counts_state_json(const char *analyzer_json, const char *group_counts_json,
+                                                       char **out_state_json, tgx_error *err) {
+  if (!analyzer_json || !group_counts_json || !out_state_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_state_json = nullptr;
+  try {
+    auto a = analyzer_from_json(parse_json_text(analyzer_json, "analyzer"));
+    json::Value v = parse_json_text(group_counts_json, "group counts");
+    GroupCounts gc;
+    if (const json::Value *s = v.get("summary")) {
+      gc.summary.seen = s->get_u64("seen", 0);
+      gc.summary.groups = s->get_u64("groups", 0);
+      gc.summary.counted = s->get_u64("counted", 0);
+      gc.summary.counted_non_null = s->get_u64("counted_non_null", 0);
+      gc.summary.null_group_rows = s->get_u64("null_group_rows", 0);
+      gc.summary.null_group_non_null = s->get_u64("null_group_non_null", 0);
+      gc.summary.overflow_rows = s->get_u64("overflow_rows", 0);
+      gc.summary.overflow_non_null = s->get_u64("overflow_non_null", 0);
+      gc.summary.long_rows = s->get_u64("long_rows", 0);
+      gc.summary.long_non_null = s->get_u64("long_non_null", 0);
+    }
+    if (const json::Value *es = v.get("entries")) {
+      if (es->type != json::Value::Array) return hfail(err, TGX_INVALID_ARGUMENT, "entries must be a JSON array");
+      for (const json::Value &e : es->arr) {
+        if (e.type != json::Value::Array || e.arr.size() != 3)
+          return hfail(err, TGX_INVALID_ARGUMENT, "an entry is [key, total, non_null]");
+        GroupCounts::Entry o;
+        const json::Value &j = e.arr[0];
+        if (j.type == json::Value::String) {
+          gc.is_bytes = true;
+          o.bytes = j.str;
+        } else if (j.type == json::Value::Array) {
+          gc.is_bytes = true;
+          for (const json::Value &b : j.arr) o.bytes += (char)(unsigned char)b.as_u64();
+        } else if (j.type == json::Value::Number) {
+          o.value = j.as_i64();
+        } else {
+          return hfail(err, TGX_INVALID_ARGUMENT, "a key is a string, an array of bytes or an integer");
+        }
+        o.total = e.arr[1].as_u64();
+        o.non_null = e.arr[2].as_u64();
+        gc.entries.push_back(std::move(o));
+      }
+    }
+    *out_state_json = dup_string(json_dump(a->state_from_group_counts(gc)));
     return TGX_OK;
   } catch (const AnalyzerError &e) {
     return hfail(err, TGX_INVALID_ARGUMENT, e.text);

@@ -181,6 +181,7 @@ struct SpecRequest {
   std::optional<tgx_value_rule_params> value_rule;  // VALUE_RULE: the rule as the device takes it (host/datatype.h)
   std::optional<tgx_value_counts_params> value_counts;  // VALUE_COUNTS: the bounds (host/value_counts.h)
   std::optional<tgx_pair_counts_params> pair_counts;    // PAIR_COUNTS: the bounds and the sides (host/analyzers.cpp)
+  std::optional<tgx_group_counts_params> group_counts;  // GROUP_COUNTS (`column2`: the group column): the bounds
   // do two requests ask the device for the same thing (what the runners' fusing compares beside kind and columns)?
   bool same_parameters(const SpecRequest &o) const {
     return value_rule.has_value() == o.value_rule.has_value() &&
@@ -189,7 +190,10 @@ struct SpecRequest {
            (!value_counts || (value_counts->max_distinct == o.value_counts->max_distinct &&
                               value_counts->max_value_bytes == o.value_counts->max_value_bytes)) &&
            pair_counts.has_value() == o.pair_counts.has_value() &&
-           (!pair_counts || memcmp(&*pair_counts, &*o.pair_counts, sizeof(tgx_pair_counts_params)) == 0);
+           (!pair_counts || memcmp(&*pair_counts, &*o.pair_counts, sizeof(tgx_pair_counts_params)) == 0) &&
+           group_counts.has_value() == o.group_counts.has_value() &&
+           (!group_counts || (group_counts->max_groups == o.group_counts->max_groups &&
+                              group_counts->max_value_bytes == o.group_counts->max_value_bytes));
   }
 };
 struct ValueCounts;  // host/value_counts.h

@@ -240,8 +240,18 @@ struct PairCountsTask {
   tgx_pair_counts_params params;
 };
 
+// TGX_CHECK_GROUP_COUNTS (groupcounts_device.cpp): one task per spec; `set` once tgx_plan_set_group_counts was called.
+// The set tasks that share the group column and both bounds ride one walk of the group column, up to
+// kGroupCountsMembers of them, in plan order: `leader` is the first task of this one's walk (`slot`: the task's own
+// index), whose table and shared counters hold the walk's; `member`: the task's place in the walk
+struct GroupCountsTask {
+  int column, group, spec_index, slot, leader, member;
+  bool set;
+  tgx_group_counts_params params;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 6;  // the records of side_check.h's kSideKinds
+constexpr int kNumSide = 7;  // the records of side_check.h's kSideKinds
 
 enum class Source { kScan, kCount };
 
@@ -269,6 +279,7 @@ struct tgx_plan {
   std::vector<tgx::ValueRuleTask> rules;
   std::vector<tgx::ValueCountsTask> value_counts;
   std::vector<tgx::PairCountsTask> pair_counts;
+  std::vector<tgx::GroupCountsTask> group_counts;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
@@ -716,7 +727,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS and PAIR_COUNTS parameters -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS and GROUP_COUNTS parameters -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

@@ -30,6 +30,38 @@ __device__ __forceinline__ int64_t vc_claim(unsigned long long *keys, Slot mask,
   return -1;
 }
 
+// the same for a 128-bit key (fa, fb) whose words lie in ka / kb, probing from slot `h`; *made: this lane made the entry
+// (it owes the slot whatever lies behind the key: a row, the value's bytes)
+template <class Slot>
+__device__ __forceinline__ int64_t vc_claim128(unsigned long long *ka, unsigned long long *kb, Slot mask, Slot h,
+                                               unsigned long long fa, unsigned long long fb, uint32_t probes,
+                                               bool *made) {
+  *made = false;
+  for (uint32_t p = 0; p < probes; p++) {
+    unsigned long long a = vc_peek(&ka[h]);
+    if (a == kEmptyKey) a = atomicCAS(&ka[h], (unsigned long long)kEmptyKey, fa);
+    if (a == kEmptyKey || a == fa) {
+      unsigned long long b = vc_peek(&kb[h]);
+      *made = b == kEmptyKey && (b = atomicCAS(&kb[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
+      if (*made || b == fb) return (int64_t)h;
+    }
+    h = (h + 1) & mask;
+  }
+  return -1;
+}
+
+// Where a wave's lanes hold 64 consecutive rows (lane l: row `row`, `in`: the row exists), the validity of another
+// column for the wave as one 64-bit window of its bitmap, whatever its Arrow offset: bit l is set when the row is
+// non-NULL there.  A column without a bitmap: every row that exists.  (One byte load a lane, eight lanes a byte; what
+// a key's lanes `same` count of the column is then popcount(same & window).)
+__device__ __forceinline__ unsigned long long vc_valid_window(const uint8_t *validity, int64_t offset, int64_t row,
+                                                              bool in) {
+  typedef const uint8_t __attribute__((address_space(1))) *u8_ptr;
+  u8_ptr v = (u8_ptr)(uintptr_t)validity;
+  const int64_t bit = offset + row;
+  return __ballot(in && (v == nullptr || ((v[bit >> 3] >> (bit & 7)) & 1) != 0));
+}
+
 // the workgroup's table of 128-bit keys: the two fingerprint words, a 32-bit count and a row that holds the key's value
 struct VcLdsStrings {
   unsigned long long fa[kValueCountsStrLdsSlots], fb[kValueCountsStrLdsSlots], row[kValueCountsStrLdsSlots];

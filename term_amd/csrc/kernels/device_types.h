@@ -292,6 +292,44 @@ struct PairRangeAcc {
   long long min_key, max_key;  // identities: INT64_MAX / INT64_MIN
 };
 
+// Group counts (kernels/groupcounts.hip; TGX_CHECK_GROUP_COUNTS): a bounded GROUP BY g with COUNT(*) and, for up to
+// kGroupCountsMembers value columns that ride the walk, COUNT(col).  The walk's running state is one open-addressing
+// table of `mask + 1` slots in one allocation, laid out as ValueCountsTable's is (keys / keys2, totals, lens, store),
+// with the members' 64-bit non_null counters between the totals and the lengths: member m's counter of slot s is
+// non_null[m * (mask + 1) + s].  Every task has kGroupCountsWords 64-bit counters: the walk's rows with a NULL key,
+// with a key longer than max_value_bytes, whose key found no slot, whose key has the bits of the free-slot marker --
+// those four in the walk's FIRST task only (`shared_word`) -- and behind each the member's rows of that class whose
+// value is non-NULL (GroupMembers::word).
+enum {
+  kGcNullRows = 0, kGcNullNonNull = 1, kGcLongRows = 2, kGcLongNonNull = 3, kGcOverflowRows = 4, kGcOverflowNonNull = 5,
+  kGcMarkerRows = 6, kGcMarkerNonNull = 7, kGroupCountsWords = 8
+};
+constexpr int kGroupCountsMembers = 8;
+constexpr int kGroupCountsBlock = 1024;  // numeric route: 16 waves share one LDS table
+// numeric route: slots of the workgroup's LDS table by member count (8-byte key, 4-byte total, 4 bytes a member):
+// 128 KiB with one member, 80 .. 128 KiB with two to five, 72 .. 88 KiB with six to eight
+__host__ __device__ constexpr uint32_t group_counts_lds_slots(int members) {
+  return members <= 1 ? 8192u : members <= 5 ? 4096u : 2048u;
+}
+constexpr uint32_t kGroupCountsDictLdsCells = 16384;  // dictionary route: 32-bit cells in LDS, (1 + members) an entry
+struct GroupMembers {
+  const uint8_t *validity[kGroupCountsMembers];  // the value column's bitmap, or nullptr: every row is non-NULL
+  int64_t offset[kGroupCountsMembers];           // its Arrow offset, unrelated to the group column's
+  uint32_t word[kGroupCountsMembers];            // first of the member's counters in `words`
+  int32_t n;
+  int32_t pad;
+};
+struct GroupCountsTable {
+  unsigned long long *keys, *keys2, *totals, *non_null;
+  uint32_t *lens;
+  uint8_t *store;
+  unsigned long long *words;  // the state's counters (GroupMembers::word and shared_word index them)
+  uint64_t mask;
+  uint64_t salt;
+  uint32_t max_value_bytes;
+  uint32_t shared_word;  // first of the counters of the walk's first task
+};
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

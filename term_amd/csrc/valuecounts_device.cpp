@@ -41,24 +41,6 @@ struct CountsHost {
   }
 };
 
-// the kernels' view of a string column (a dictionary's values included); `buffers`: the device copy of a Utf8View's
-// table of data-buffer pointers
-Utf8ColDesc string_desc(const tgx_column &c, const uint8_t *const *buffers, const FpKey &key) {
-  Utf8ColDesc d;
-  memset(&d, 0, sizeof(d));
-  const bool view = c.type == TGX_UTF8_VIEW;
-  d.offsets = c.offsets;
-  d.data = c.data;
-  d.validity = c.validity;
-  d.offset = c.offset;
-  d.length = c.length;
-  d.large_offsets = c.type == TGX_LARGE_UTF8;
-  d.views = view ? c.values : nullptr;
-  d.buffers = view ? buffers : nullptr;
-  d.key = key;
-  return d;
-}
-
 struct NoRange {};
 
 struct CountsKind {

@@ -860,6 +860,8 @@ class _Analyzer:
 
     def name(self):
         t = self.spec["type"]
+        if t == "grouped_completeness":  # (the wrapper keeps the analyzer's name: grouped.rs:280-282)
+            return "completeness"
         return "entropy" if t == "value_entropy" else t  # (the tag "entropy" was taken: see EntropyAnalyzer)
 
     def metric_key(self):
@@ -870,7 +872,32 @@ class _Analyzer:
             return "correlation_%s_%s_%s" % (self.spec.get("method", "pearson"), self.spec["column1"], self.spec["column2"])
         if t == "mutual_information":
             return "mutual_information_%s_%s" % (self.spec["column1"], self.spec["column2"])
+        if self.spec["type"] == "grouped_completeness":  # grouped.rs:288-294
+            return "completeness.%s_grouped_by_%s" % (self.spec["column"], "_".join(self.spec["group_by"]))
         return "%s.%s" % (t, self.spec["column"])
+
+    def with_grouping(self, config):
+        """TG/analyzers/grouped.rs GroupedAnalyzer::with_grouping: the analyzer's metric per group of config.columns.  The
+        reference implements it for CompletenessAnalyzer alone (basic/grouped_completeness.rs), and so does this"""
+        if self.spec["type"] != "completeness":
+            raise TypeError("with_grouping: only CompletenessAnalyzer has a grouped form (the reference implements "
+                            "GroupedAnalyzer for it alone), not %s" % self.name())
+        spec = {"type": "grouped_completeness", "column": self.spec["column"], "group_by": list(config.columns),
+                "max_groups": config.max_groups, "include_overall": bool(config.include_overall)}
+        if not config.strict_reference_types:
+            spec["strict_reference_types"] = False
+        return _Analyzer(spec)
+
+    def state_text_from_group_counts(self, summary, entries):
+        """the state (the bytes the library wrote) a grouped_completeness analyzer builds from given group counts:
+        `entries` is a list of (key, total, non_null) in the library's order, a key being str / bytes or int"""
+        key = lambda k: list(k) if isinstance(k, (bytes, bytearray)) else k  # noqa: E731
+        doc = {"summary": summary, "entries": [[key(k), t, n] for k, t, n in entries]}
+        out = C.c_char_p()
+        err = _Error()
+        _host_check(_host().tgx_host_group_counts_state_json(json.dumps(self.spec).encode(), json.dumps(doc).encode(),
+                                                             C.byref(out), C.byref(err)), err)
+        return _take(out)
 
     def merge_states(self, states):
         out = C.c_char_p()
@@ -915,6 +942,32 @@ class _Analyzer:
         _host_check(_host().tgx_host_metric_from_state_json(json.dumps(self.spec).encode(), json.dumps(state).encode(),
                                                             C.byref(out), C.byref(err)), err)
         return json.loads(_take(out))
+
+
+class GroupingConfig:
+    """TG/analyzers/grouped.rs:14-66 GroupingConfig: the group columns, max_groups (default 10000: the first max_groups
+    groups by the metric, descending, are kept; also the bound of the table on the device, capped at
+    GROUP_COUNTS_MAX_GROUPS), include_overall (default true) and the overflow strategy, which the reference carries and
+    never reads.  strict_reference_types (default true): only a group column declared Utf8 is taken, the one type the
+    reference reads by value; off, strings of every layout group by value and integers print as decimal text"""
+
+    def __init__(self, columns, max_groups=10000, include_overall=True, overflow_strategy="TopK",
+                 strict_reference_types=True):
+        self.columns = [columns] if isinstance(columns, str) else list(columns)
+        self.max_groups, self.include_overall = max_groups, include_overall
+        self.overflow_strategy, self.strict_reference_types = overflow_strategy, strict_reference_types
+
+    def with_max_groups(self, n):
+        self.max_groups = int(n)
+        return self
+
+    def with_overall(self, include):
+        self.include_overall = bool(include)
+        return self
+
+    def with_overflow_strategy(self, strategy):
+        self.overflow_strategy = strategy
+        return self
 
 
 def SizeAnalyzer(): return _Analyzer({"type": "size"})
@@ -1020,6 +1073,9 @@ class AnalysisRunner:
                  if a.spec["type"] == "value_entropy" and "arrow_type" not in a.spec and a.spec["column"] in declared
                  else dict(a.spec, arrow_types=[declared.get(a.spec["column1"], ""), declared.get(a.spec["column2"], "")])
                  if a.spec["type"] == "mutual_information" and "max_pairs" in a.spec and "arrow_types" not in a.spec
+                 else dict(a.spec, group_arrow_type=declared[a.spec["group_by"][0]])
+                 if a.spec["type"] == "grouped_completeness" and len(a.spec["group_by"]) == 1 and
+                 a.spec["group_by"][0] in declared and "group_arrow_type" not in a.spec
                  else a.spec for a in self._analyzers]
         spec = {"table_name": self._table, "continue_on_error": self._continue, "analyzers": specs}
         name_arr, n_cols, col_arr, n_batches, _keep = _flatten_table(table)
@@ -1053,6 +1109,7 @@ def _host():
         L.tgx_host_metric_from_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_analyzer_plan_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_pair_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_group_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_free.argtypes = [C.c_void_p]
         L.tgx_host_free.restype = None
         _HOST = L

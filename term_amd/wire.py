@@ -72,6 +72,17 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                                   u64 count } }                      ascending by (x cell, y cell): bytewise, bins as ints
                                every count > 0, every length <= max_value_bytes, no pair twice, and
                                sum(counts) + overflow_rows + long_rows + non_finite + out_of_range == both_non_null <= seen.
+    and ONLY for plans with GROUP_COUNTS checks, behind the PAIR_COUNTS section if there is one:
+    u32 magic 'GCNT', u32 n_tasks
+    n_tasks     x { u32 max_groups, max_value_bytes              (the plan's parameters)
+                    u32 kind (0 no keys, 1 int64, 2 bytes), u32 0
+                    u64 seen, null_group_rows, null_group_non_null, overflow_rows, overflow_non_null, long_rows,
+                        long_non_null, n_entries
+                    n_entries x { i64 key; u64 total, non_null }                      kind 1, ascending int64
+                             or { u32 length; u8 bytes[length]; u64 total, non_null } } kind 2, ascending bytewise
+                               every total > 0, every non_null <= its total (its rows, for the three classes), every
+                               length <= max_value_bytes, no key twice, and
+                               sum(totals) + null_group_rows + overflow_rows + long_rows == seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -85,6 +96,7 @@ HIST_MAGIC = 0x54534948  # 'HIST'
 VALUE_RULE_MAGIC = 0x4C525656  # 'VVRL'
 VALUE_COUNTS_MAGIC = 0x544E4356  # 'VCNT'
 PAIR_COUNTS_MAGIC = 0x544E4350  # 'PCNT'
+GROUP_COUNTS_MAGIC = 0x544E4347  # 'GCNT'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -239,8 +251,27 @@ def pair_counts_state(max_pairs, max_value_bytes, x_side, y_side, seen, counts=(
     return out
 
 
+def group_counts_state(max_groups, max_value_bytes, groups, seen=None, null_group=(0, 0), overflow=(0, 0), long=(0, 0),
+                       ordered=True):
+    """a GROUP_COUNTS task: the plan's parameters, the counters and the entries of `groups` (key -> (total, non_null);
+    every key an int, or every key bytes).  null_group / overflow / long: (rows, non-NULL values among them).  seen
+    defaults to what the invariant makes it.  `ordered=False` keeps the entries in the order given (for a blob that is to
+    be refused)."""
+    items = list(groups.items()) if hasattr(groups, "items") else list(groups)
+    is_bytes = bool(items) and isinstance(items[0][0], (bytes, bytearray))
+    if ordered:
+        items.sort(key=lambda kv: kv[0])
+    if seen is None:
+        seen = sum(t for _, (t, _n) in items) + null_group[0] + overflow[0] + long[0]
+    out = struct.pack("<4I8Q", max_groups, max_value_bytes, (2 if is_bytes else 1) if items else 0, 0, seen, *null_group,
+                      *overflow, *long, len(items))
+    for k, (t, n) in items:
+        out += (struct.pack("<I", len(k)) + bytes(k) if is_bytes else struct.pack("<q", k)) + struct.pack("<QQ", t, n)
+    return out
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=(), value_counts=(), pair_counts=()):
+         value_rules=(), value_counts=(), pair_counts=(), group_counts=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -255,5 +286,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", VALUE_COUNTS_MAGIC, len(value_counts)) + b"".join(value_counts)
     if pair_counts:
         tail += struct.pack("<II", PAIR_COUNTS_MAGIC, len(pair_counts)) + b"".join(pair_counts)
+    if group_counts:
+        tail += struct.pack("<II", GROUP_COUNTS_MAGIC, len(group_counts)) + b"".join(group_counts)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
