@@ -342,7 +342,36 @@ typedef enum tgx_check_kind {
    * entries are united by their bytes.  tgx_merge, state blobs and tgx_allreduce unite by value and add every counter.
    * Read with tgx_group_counts_get and tgx_group_counts_entries; tgx_result carries total = rows seen, non_null =
    * COUNT(col), distinct = groups held (the NULL group not among them), matches = rows counted in them. */
-  TGX_CHECK_GROUP_COUNTS = 17
+  TGX_CHECK_GROUP_COUNTS = 17,
+  /* A sum per group: each side of the reference's CrossTableSumConstraint
+   *                          TG/constraints/cross_table_sum.rs:251-262
+   *   SELECT g, COUNT(*) AS rows, COUNT(col) AS non_null, SUM(col) AS sum FROM t GROUP BY g
+   * for a BOUNDED number of groups: `column` is the value column col, `column2` is the group column g (the same column
+   * is allowed); the bounds come with tgx_plan_set_group_sums (below); a spec without them makes tgx_state_create fail.
+   * Group columns, the NULL group, the NULL-entry and index-outside-the-dictionary rules, the free-slot marker and the
+   * grouping guarantee are those of TGX_CHECK_GROUP_COUNTS.
+   * Value columns and what the sum is:
+   *   Int64-shaped, Int32 / Date32, Int8 .. UInt32 (widened)   a 64-bit WRAPPING integer sum, the sum_i of tgx_result
+   *                         (DataFusion's SUM for these inputs): exact, so independent of batching, association, merge
+   *                         order and rank count.  Reported in sum_i; sum_f is (double)sum_i.
+   *   Float64, Float32 (widened)   a plain IEEE double sum in whatever order the device adds.  NaN and +-inf propagate
+   *                         by IEEE rules; there is no non_finite class.  A group that holds only -0.0 may come out as
+   *                         +0.0.  Reported in sum_f; sum_i is 0.
+   *   UInt64, Boolean, string and validity-only value columns are TGX_UNSUPPORTED from tgx_update (as are the group
+   *   columns TGX_CHECK_GROUP_COUNTS refuses), and the state stays usable afterwards.
+   * Nothing is approximated: every row is in exactly one of an entry, the NULL group, overflow (its key found no slot
+   * in the table) and long rows (a string key longer than max_value_bytes).  Each class carries rows, non_null and sum:
+   *   counted + null_group_rows + overflow_rows + long_rows == seen
+   *   counted_non_null + null_group_non_null + overflow_non_null + long_non_null == COUNT(col)
+   * and, for integer value columns, exact in wrapping arithmetic,
+   *   counted.sum_i + null_group.sum_i + overflow.sum_i + long_rows.sum_i == SUM(col).
+   * One value column a walk: two specs on one group column each walk it.  tgx_merge, state blobs and tgx_allreduce
+   * unite by value; integer sums add with wrap, float sums add in state order and rank order.  A state that summed
+   * integers and one that summed floats do not merge, nor do integer-key and string-key states.
+   * Read with tgx_group_sums_get and tgx_group_sums_entries; tgx_result carries total = rows seen, non_null =
+   * COUNT(col), distinct = groups held, matches = rows counted in them, sum_i / sum_f = the sum over all classes,
+   * has_value = 0 when COUNT(col) is 0. */
+  TGX_CHECK_GROUP_SUMS = 18
 } tgx_check_kind;
 
 enum {
@@ -631,6 +660,16 @@ typedef struct tgx_group_counts_params {
 tgx_status tgx_plan_set_group_counts(tgx_plan *plan, size_t spec_index, const tgx_group_counts_params *params,
                                      tgx_error *err);
 
+/* TGX_CHECK_GROUP_SUMS: the bounds of spec `spec_index`, with the meaning, lifetime and refusals of
+ * tgx_plan_set_group_counts. */
+enum { TGX_GROUP_SUMS_MAX_GROUPS = 65536, TGX_GROUP_SUMS_MAX_VALUE_BYTES = 256 };
+typedef struct tgx_group_sums_params {
+  uint32_t max_groups;
+  uint32_t max_value_bytes;
+} tgx_group_sums_params;
+tgx_status tgx_plan_set_group_sums(tgx_plan *plan, size_t spec_index, const tgx_group_sums_params *params,
+                                   tgx_error *err);
+
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
  * the call is refused with TGX_INVALID_ARGUMENT.  1 <= buckets <= TGX_HISTOGRAM_MAX_BUCKETS; every edge must be finite
@@ -902,6 +941,43 @@ tgx_status tgx_group_counts_entries(const tgx_plan *plan, tgx_state *state, size
                                     tgx_group_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
                                     uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
 
+/* ---- group sums (TGX_CHECK_GROUP_SUMS; TG/constraints/cross_table_sum.rs:251-262) ------------------------------------ */
+/* one class of rows: COUNT(*), COUNT(col) and SUM(col) over it.  Integer value columns: sum_i is the wrapping sum and
+ * sum_f is (double)sum_i; float value columns: sum_f is the sum and sum_i is 0 */
+typedef struct tgx_group_sums_class {
+  uint64_t rows;
+  uint64_t non_null;
+  int64_t sum_i;
+  double sum_f;
+} tgx_group_sums_class;
+typedef struct tgx_group_sums_summary {
+  uint64_t seen;   /* rows handed to tgx_update */
+  uint64_t groups; /* non-NULL keys held; may exceed max_groups: the caller compares */
+  int32_t is_float; /* the sums are doubles (a Float64 / Float32 value column); 0 while no row was seen */
+  int32_t reserved;
+  tgx_group_sums_class counted;    /* the entries together (float sums: added in ascending key order) */
+  tgx_group_sums_class null_group; /* rows whose group key is NULL */
+  tgx_group_sums_class overflow;   /* rows whose key found no slot */
+  tgx_group_sums_class long_rows;  /* rows whose string key is longer than max_value_bytes: they are in no entry */
+} tgx_group_sums_summary; /* the four classes' rows add up to seen, their non_null to COUNT(col), their sum_i (integer
+                           * value columns, wrapping) to SUM(col) */
+tgx_status tgx_group_sums_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_group_sums_summary *out,
+                              tgx_error *err);
+/* One group: its key as in tgx_group_count_entry, its two counts and its sum (sum_i / sum_f as in tgx_group_sums_class;
+ * has no value, in SQL's sense, when non_null is 0: both sums are 0 then) */
+typedef struct tgx_group_sum_entry {
+  int64_t value;
+  uint64_t offset, length;
+  uint64_t rows;     /* COUNT(*) of the group */
+  uint64_t non_null; /* COUNT(col) of the group */
+  int64_t sum_i;
+  double sum_f;
+} tgx_group_sum_entry;
+/* Copies the entries, ascending by key, in the convention of tgx_group_counts_entries. */
+tgx_status tgx_group_sums_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                  tgx_group_sum_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
+                                  uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -991,7 +1067,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -152,6 +152,35 @@ tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json, const char
 tgx_status tgx_host_group_counts_state_json(const char *analyzer_json, const char *group_counts_json,
                                             char **out_state_json, tgx_error *err);
 
+/* ValidationSuite::run over SEVERAL registered tables: what tgx_host_run_suite_json does, with every table of `tables`
+ * registered under its own name (the suite's table among them, under the suite's table_name; a suite whose table is not
+ * registered answers as the reference does for a missing table).  A "cross_table_sum" constraint
+ *   {"type": "cross_table_sum", "left_column": "orders.total", "right_column": "payments.amount", "group_by": ["g"],
+ *    "tolerance": 0.0, "max_violations_reported": 100, "max_groups": 65536}       (TG/constraints/cross_table_sum.rs)
+ * is evaluated beside the suite's fused plan, against the registered tables: each side is walked once, as a
+ * TGX_CHECK_GROUP_SUMS spec (grouped) or a TGX_CHECK_NUMERIC_STATS spec (ungrouped); the outer join of the sides'
+ * groups runs on the host. */
+typedef struct tgx_host_table {
+  const char *name;
+  const char *const *column_names; /* n_columns names */
+  size_t n_columns;
+  const tgx_column *columns;       /* n_batches x n_columns views, batch-major */
+  size_t n_batches;
+} tgx_host_table;
+tgx_status tgx_host_run_suite_tables_json(const char *suite_json, const tgx_host_table *tables, size_t n_tables,
+                                          char **out_json, tgx_error *err);
+
+/* The join and the verdict of a "cross_table_sum" constraint on given sums; needs no device.  sums_json:
+ * {"left": S, "right": S} with S = a number (the ungrouped form: COALESCE(SUM(col), 0.0) of the side) or
+ * {"groups": [[key, sum], ..] ascending by key (a key a string or an integer), "null_group": sum or null,
+ *  "overflow_rows": n, "long_rows": n}; NaN / Infinity / -Infinity are read as Python's json writes them.  Returns
+ * {"status", "metric", "message", "total_groups", "violating_groups", "total_left_sum", "total_right_sum",
+ *  "max_difference", "config": {the constraint as the host layer read it}}; a number that is not finite comes back as
+ * the string "NaN" / "inf" / "-inf".  A side beyond its bounds, sides of different key kinds and an unqualified column
+ * are TGX_INVALID_ARGUMENT with the constraint's error text. */
+tgx_status tgx_host_cross_table_sum_json(const char *constraint_json, const char *sums_json, char **out_json,
+                                         tgx_error *err);
+
 void tgx_host_free(char *s);
 
 #ifdef __cplusplus

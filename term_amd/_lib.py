@@ -27,6 +27,8 @@ PAIR_SIDE_VALUE, PAIR_SIDE_RANGE, PAIR_SIDE_BINNED = 0, 1, 2
 PAIR_COUNTS_MAX_PAIRS, PAIR_COUNTS_MAX_VALUE_BYTES = 65536, 256
 GROUP_COUNTS = 17  # COUNT(*) and COUNT(col) per group of a second column, for a bounded number of groups (Plan.set_group_counts)
 GROUP_COUNTS_MAX_GROUPS, GROUP_COUNTS_MAX_VALUE_BYTES = 65536, 256
+GROUP_SUMS = 18  # COUNT(*), COUNT(col) and SUM(col) per group of a second column, for a bounded number of groups (Plan.set_group_sums)
+GROUP_SUMS_MAX_GROUPS, GROUP_SUMS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
 FLAG_EXACT_RANK_SUMS = 32
 FLAG_EXACT_KEYS = 64  # DISTINCT over string / tuple keys: equal fingerprints confirmed byte by byte
@@ -192,6 +194,29 @@ class GroupCountEntry(C.Structure):
                 ("non_null", C.c_uint64)]
 
 
+class GroupSumsParams(C.Structure):
+    """tgx_group_sums_params (include/tgx.h)"""
+    _fields_ = [("max_groups", C.c_uint32), ("max_value_bytes", C.c_uint32)]
+
+
+class GroupSumsClass(C.Structure):
+    """tgx_group_sums_class (include/tgx.h)"""
+    _fields_ = [("rows", C.c_uint64), ("non_null", C.c_uint64), ("sum_i", C.c_int64), ("sum_f", C.c_double)]
+
+
+class GroupSumsSummary(C.Structure):
+    """tgx_group_sums_summary (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("groups", C.c_uint64), ("is_float", C.c_int32), ("reserved", C.c_int32),
+                ("counted", GroupSumsClass), ("null_group", GroupSumsClass), ("overflow", GroupSumsClass),
+                ("long_rows", GroupSumsClass)]
+
+
+class GroupSumEntry(C.Structure):
+    """tgx_group_sum_entry (include/tgx.h)"""
+    _fields_ = [("value", C.c_int64), ("offset", C.c_uint64), ("length", C.c_uint64), ("rows", C.c_uint64),
+                ("non_null", C.c_uint64), ("sum_i", C.c_int64), ("sum_f", C.c_double)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -328,6 +353,10 @@ def lib():
         L.tgx_pair_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_group_counts.argtypes = [vp, sz, C.POINTER(GroupCountsParams), E]
         L.tgx_group_counts_get.argtypes = [vp, vp, sz, C.POINTER(GroupCountsSummary), E]
+        L.tgx_plan_set_group_sums.argtypes = [vp, sz, C.POINTER(GroupSumsParams), E]
+        L.tgx_group_sums_get.argtypes = [vp, vp, sz, C.POINTER(GroupSumsSummary), E]
+        L.tgx_group_sums_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
+                                             C.POINTER(C.c_int32), E]
         L.tgx_group_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
                                                C.POINTER(C.c_int32), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
@@ -770,6 +799,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_group_counts(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_group_sums(self, spec_index, max_groups=10000, max_value_bytes=256):
+        """tgx_plan_set_group_sums: the bounds of a GROUP_SUMS spec (before the plan's first state)"""
+        p = GroupSumsParams(max_groups, max_value_bytes)
+        err = _Error()
+        _check(lib().tgx_plan_set_group_sums(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def set_pair_counts(self, spec_index, x=None, y=None, max_pairs=10000, max_value_bytes=256):
         """tgx_plan_set_pair_counts: the bounds and the sides of a PAIR_COUNTS spec (before the plan's first state).  A
         side is None or "value" (a string column: PAIR_SIDE_VALUE), "range" (a numeric column: the spec is in its range
@@ -1045,6 +1080,29 @@ class State:
         for e in entries:
             groups[raw[e.offset:e.offset + e.length] if is_bytes.value else e.value] = (e.total, e.non_null)
         summary = {f: getattr(s, f) for f, _ in GroupCountsSummary._fields_}
+        return summary, groups
+
+    # group sums
+    def group_sums(self, spec_index):
+        """tgx_group_sums_get + tgx_group_sums_entries: (summary, groups) -- summary a dict of seen, groups, is_float and
+        the four classes counted, null_group, overflow, long_rows, each a tuple (rows, non_null, sum); groups a dict
+        key -> (rows, non_null, sum) in the library's order (ascending by key), its keys ints for an integer group column
+        and bytes for a string one.  A sum is an int (the wrapping Int64 sum, sum_i) for an integer value column and a
+        float (sum_f) for a float one.  The NULL group is in the summary"""
+        L, err = lib(), _Error()
+        s = GroupSumsSummary()
+        _check(L.tgx_group_sums_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        is_bytes = C.c_int32()
+        entries, raw = self._counted_entries(L.tgx_group_sums_entries, GroupSumEntry, spec_index, C.byref(is_bytes))
+        is_float = bool(s.is_float)
+        groups = {}
+        for e in entries:
+            key = raw[e.offset:e.offset + e.length] if is_bytes.value else e.value
+            groups[key] = (e.rows, e.non_null, e.sum_f if is_float else e.sum_i)
+        summary = {"seen": s.seen, "groups": s.groups, "is_float": is_float}
+        for name in ("counted", "null_group", "overflow", "long_rows"):
+            c = getattr(s, name)
+            summary[name] = (c.rows, c.non_null, c.sum_f if is_float else c.sum_i)
         return summary, groups
 
     def pair_range(self, spec_index):

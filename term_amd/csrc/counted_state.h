@@ -1,4 +1,4 @@
-// counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS: the
+// counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS: the
 // bounded GROUP BY of kernels/count_table.h): the table's size and layout, clearing it, reading it back once between
 // batches, and the two places where sizes come from outside -- a blob's entries and the buffers of the *_entries calls.
 #pragma once

@@ -625,3 +625,110 @@ extern "C" tgx_status tgx_host_group_counts_state_json(const char *analyzer_json
     return hfail(err, TGX_INTERNAL, "unknown C++ exception");
   }
 }
+
+// ---- cross-table constraints ---------------------------------------------------------------------------------------------
+extern "C" tgx_status tgx_host_run_suite_tables_json(const char *suite_json, const tgx_host_table *tables, size_t n_tables,
+                                                     char **out_json, tgx_error *err) {
+  if (!suite_json || !out_json || (n_tables && !tables)) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    ValidationSuite suite = suite_from_json(suite_json);
+    Context ctx;
+    for (size_t k = 0; k < n_tables; k++) {
+      const tgx_host_table &in = tables[k];
+      if (!in.name || (in.n_columns && (!in.column_names || (in.n_batches && !in.columns))))
+        return hfail(err, TGX_INVALID_ARGUMENT, "table " + std::to_string(k) + ": NULL argument");
+      Table t;
+      for (size_t i = 0; i < in.n_columns; i++) t.column_names.push_back(in.column_names[i]);
+      for (size_t b = 0; b < in.n_batches; b++) {
+        Batch batch;
+        batch.columns.assign(in.columns + b * in.n_columns, in.columns + (b + 1) * in.n_columns);
+        t.batches.push_back(std::move(batch));
+      }
+      ctx.register_table(in.name, std::move(t));
+    }
+    ValidationResult r = suite.run(ctx);
+    *out_json = dup_string(r.to_json());
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+static SideSums side_sums_from(const json::Value &v) {
+  SideSums s;
+  if (const json::Value *gs = v.get("groups")) {
+    if (gs->type != json::Value::Array) throw TermError{TermError::Internal, "groups must be a JSON array"};
+    for (const json::Value &e : gs->arr) {
+      if (e.type != json::Value::Array || e.arr.size() != 2 || e.arr[1].type != json::Value::Number)
+        throw TermError{TermError::Internal, "a group is [key, sum]"};
+      SideSums::Group g;
+      const json::Value &j = e.arr[0];
+      if (j.type == json::Value::String) {
+        s.is_bytes = true;
+        g.bytes = j.str;
+      } else if (j.type == json::Value::Number) {
+        g.value = j.as_i64();
+      } else {
+        throw TermError{TermError::Internal, "a key is a string or an integer"};
+      }
+      g.sum = e.arr[1].num;
+      s.groups.push_back(std::move(g));
+    }
+  }
+  if (const json::Value *n = v.get("null_group"))
+    if (n->type == json::Value::Number) s.null_group = n->num;
+  s.overflow_rows = v.get_u64("overflow_rows", 0);
+  s.long_rows = v.get_u64("long_rows", 0);
+  return s;
+}
+
+extern "C" tgx_status tgx_host_cross_table_sum_json(const char *constraint_json, const char *sums_json, char **out_json,
+                                                    tgx_error *err) {
+  if (!constraint_json || !sums_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto c = std::dynamic_pointer_cast<CrossTableSumConstraint>(constraint_from_json_text(constraint_json));
+    if (!c) return hfail(err, TGX_INVALID_ARGUMENT, "not a cross_table_sum constraint");
+    json::Value v;
+    std::string perr;
+    if (!json::parse(sums_json, &v, &perr)) return hfail(err, TGX_INVALID_ARGUMENT, "sums JSON: " + perr);
+    const json::Value *l = v.get("left"), *r = v.get("right");
+    if (!l || !r) return hfail(err, TGX_INVALID_ARGUMENT, "sums JSON needs 'left' and 'right'");
+    (void)CrossTableSumConstraint::parse_qualified_column(c->left_column());
+    (void)CrossTableSumConstraint::parse_qualified_column(c->right_column());
+    const bool ungrouped = l->type == json::Value::Number && r->type == json::Value::Number;
+    if (ungrouped != c->group_by_columns().empty())
+      return hfail(err, TGX_INVALID_ARGUMENT, "a grouped constraint takes two sides of groups, an ungrouped one two numbers");
+    const CrossTableSumRow row = ungrouped ? c->totals(l->num, r->num) : c->join(side_sums_from(*l), side_sums_from(*r));
+    const ConstraintResult cr = c->verdict(row);
+    std::string o = std::string("{\"status\": \"") +
+                    (cr.status == ConstraintStatus::Success ? "success" : cr.status == ConstraintStatus::Failure ? "failure" : "skipped") +
+                    "\", \"metric\": " + (cr.metric ? json_f64(*cr.metric) : "null") + ", \"message\": " +
+                    (cr.message ? json::quote(*cr.message) : "null") + ", \"total_groups\": " +
+                    std::to_string(row.total_groups) + ", \"violating_groups\": " + std::to_string(row.violating_groups) +
+                    ", \"total_left_sum\": " + json_f64(row.total_left_sum) + ", \"total_right_sum\": " +
+                    json_f64(row.total_right_sum) + ", \"max_difference\": " + json_f64(row.max_difference) +
+                    ", \"config\": {\"name\": " + json::quote(c->name()) + ", \"left_column\": " +
+                    json::quote(c->left_column()) + ", \"right_column\": " + json::quote(c->right_column()) + ", \"group_by\": [";
+    for (size_t i = 0; i < c->group_by_columns().size(); i++) o += (i ? ", " : "") + json::quote(c->group_by_columns()[i]);
+    o += "], \"tolerance\": " + json_f64(c->tolerance_value()) + ", \"max_violations_reported\": " +
+         std::to_string(c->violations_reported()) + ", \"max_groups\": " + std::to_string(c->groups_bound()) + "}}";
+    *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}

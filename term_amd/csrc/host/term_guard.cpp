@@ -1293,6 +1293,10 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       Planned p;
       p.check = &check;
       p.constraint = c.get();
+      if (c->reads_context()) {  // (its own tables, its own walks: evaluated with the verdicts below)
+        planned.push_back(std::move(p));
+        continue;
+      }
       if (!table) {
         p.error = TermError{TermError::DataFusion,
                             "Error during planning: table 'datafusion.public." + table_name_ + "' not found"}
@@ -1482,7 +1486,14 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
     metrics.total_checks += 1;
     ConstraintResult cr;
     std::optional<std::string> error = p.error ? p.error : run_error;
-    if (!error) {
+    if (p.constraint->reads_context()) {
+      error.reset();  // (the fused plan's fate is not this constraint's)
+      try {
+        cr = p.constraint->evaluate_context(ctx);
+      } catch (const TermError &e) {
+        error = e.display();
+      }
+    } else if (!error) {
       Constraint::Inputs in;
       QuantileCtx qctx{h.plan, h.state, p.spec_index};
       for (size_t si : p.spec_index) in.results.push_back(&results[si]);
@@ -1768,6 +1779,16 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     b.correlation(std::move(v));
   } else if (type == "temporal_ordering") {
     b.constraint(temporal_ordering_from_json(c));
+  } else if (type == "cross_table_sum") {
+    // {"type": "cross_table_sum", "left_column": "orders.total", "right_column": "payments.amount", "group_by": [..],
+    //  "tolerance": 0.0, "max_violations_reported": 100, "max_groups": 65536}
+    auto x = std::make_shared<CrossTableSumConstraint>(c.get_str("left_column"), c.get_str("right_column"));
+    x->group_by(strings_from(c.get("group_by")));
+    x->tolerance(c.get_num("tolerance", 0.0));
+    x->max_violations_reported((size_t)c.get_u64("max_violations_reported", 100));
+    x->max_groups((uint32_t)std::min<uint64_t>(c.get_u64("max_groups", CrossTableSumConstraint::kDefaultMaxGroups),
+                                               UINT32_MAX));
+    b.constraint(std::move(x));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
   } else if (type == "histogram") {

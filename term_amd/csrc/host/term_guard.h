@@ -198,6 +198,7 @@ struct SpecRequest {
 };
 struct ValueCounts;  // host/value_counts.h
 class Histogram;
+class Context;       // below: the SessionContext stand-in
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:
 // plan() says which aggregates are needed, evaluate() turns them into the verdict.
@@ -222,6 +223,10 @@ class Constraint {
     bool strict_reference_types = true;
   };
   virtual ConstraintResult evaluate(const Inputs &in) const = 0;
+  // A constraint that reads tables of its own (CrossTableSumConstraint) is no part of the suite's fused plan: plan() is
+  // empty and ValidationSuite::run evaluates it beside the plan, against the Context.  Throws TermError as plan() does.
+  virtual bool reads_context() const { return false; }
+  virtual ConstraintResult evaluate_context(const Context &ctx) const;
 };
 
 // What DataFusion 50's aggregate hands back for a column of Arrow type `arrow_type`, and whether the reference can
@@ -236,6 +241,66 @@ enum class StatisticResultKind { Min, Max, Mean, Sum, StandardDeviation, Varianc
 bool reference_extracts(StatisticResultKind stat, const std::string &arrow_type);
 // QuantileConstraint reads Float64, Int64 or Int32 (constraints/quantile.rs:308-324), else TypeMismatch
 bool reference_extracts_quantile(const std::string &arrow_type);
+
+// ---- constraints/cross_table_sum.rs: SUM(left) against SUM(right), over the whole tables or per group of ONE group
+// column.  Each side is one walk of its table on the device -- a TGX_CHECK_GROUP_SUMS spec (grouped) or a
+// TGX_CHECK_NUMERIC_STATS spec (ungrouped) -- and the FULL OUTER JOIN of at most 65 536 groups a side runs on the host.
+// One side's groups as the join takes them: COALESCE(SUM(col), 0.0) as a double per key, ascending by key
+struct SideSums {
+  bool is_bytes = false;                             // string keys (`bytes`), else integer keys (`value`)
+  struct Group {
+    int64_t value = 0;
+    std::string bytes;
+    double sum = 0;
+  };
+  std::vector<Group> groups;                         // ascending by key, as tgx_group_sums_entries gives them
+  std::optional<double> null_group;                  // the rows with a NULL key, when there are any
+  uint64_t overflow_rows = 0, long_rows = 0;         // rows beyond the bounds: no verdict on partial sums
+};
+struct CrossTableSumRow {                            // the reference's result row (:273-279)
+  int64_t total_groups = 0, violating_groups = 0;
+  double total_left_sum = 0, total_right_sum = 0, max_difference = 0;
+};
+class CrossTableSumConstraint : public Constraint {
+ public:
+  static constexpr uint32_t kDefaultMaxGroups = 65536;
+  CrossTableSumConstraint(std::string left_column, std::string right_column)  // "table.column" each (:87-95)
+      : left_(std::move(left_column)), right_(std::move(right_column)) {}
+  CrossTableSumConstraint &group_by(std::vector<std::string> columns) { group_by_ = std::move(columns); return *this; }
+  CrossTableSumConstraint &tolerance(double t) { tolerance_ = t < 0 ? -t : t; return *this; }  // (:129-132: abs)
+  CrossTableSumConstraint &max_violations_reported(size_t n) { max_violations_ = n; return *this; }
+  // this layer's own: the groups a side's table on the device is sized for (1 .. 65 536).  A side with rows beyond it
+  // (overflow) or with keys longer than 256 bytes makes the constraint an error that names the bound
+  CrossTableSumConstraint &max_groups(uint32_t n) { max_groups_ = n; return *this; }
+
+  const std::string &left_column() const { return left_; }
+  const std::string &right_column() const { return right_; }
+  const std::vector<std::string> &group_by_columns() const { return group_by_; }
+  double tolerance_value() const { return tolerance_; }
+  size_t violations_reported() const { return max_violations_; }
+  uint32_t groups_bound() const { return max_groups_; }
+
+  std::string name() const override { return "cross_table_sum"; }
+  std::vector<SpecRequest> plan() const override { return {}; }
+  ConstraintResult evaluate(const Inputs &in) const override;  // throws: the constraint reads the Context
+  bool reads_context() const override { return true; }
+  ConstraintResult evaluate_context(const Context &ctx) const override;
+
+  // (table, column) of a qualified name; throws the reference's errors (:158-175)
+  static std::pair<std::string, std::string> parse_qualified_column(const std::string &qualified);
+  // the join and the result row; throws TermError where a side is beyond its bounds or the key kinds differ
+  CrossTableSumRow join(const SideSums &left, const SideSums &right) const;
+  CrossTableSumRow totals(double left_total, double right_total) const;  // the ungrouped form
+  // the verdict and the message (:572-630); left_total / right_total feed the ungrouped form's example
+  ConstraintResult verdict(const CrossTableSumRow &row) const;
+
+ private:
+  std::string left_, right_;
+  std::vector<std::string> group_by_;
+  double tolerance_ = 0.0;
+  size_t max_violations_ = 100;
+  uint32_t max_groups_ = kDefaultMaxGroups;
+};
 
 // ---- core/check.rs
 class Check {
@@ -354,6 +419,9 @@ class Check::Builder {
   Builder &has_histogram(std::string column, std::function<bool(const Histogram &)> assertion);
   Builder &has_histogram_with_description(std::string column, std::function<bool(const Histogram &)> assertion,
                                           std::string description);
+  // core/check.rs:2054-2065: pushes CrossTableSumConstraint::new(left, right); a configured object comes through
+  // constraint(..)
+  Builder &cross_table_sum(std::string left_column, std::string right_column);
   Check build() { return check_; }
 
  private:

@@ -330,6 +330,39 @@ struct GroupCountsTable {
   uint32_t shared_word;  // first of the counters of the walk's first task
 };
 
+// Group sums (kernels/groupsums.hip; TGX_CHECK_GROUP_SUMS): a bounded GROUP BY g with COUNT(*), COUNT(col) and
+// SUM(col) of ONE value column.  A task's running state is one open-addressing table laid out as GroupCountsTable's
+// is, with two 64-bit counters a slot behind the rows: non_null[s] and sum[s] (the bits of an int64 that wraps, or of a
+// double -- all-zero is +0.0, so clearing is the same).  Every task has kGroupSumsWords 64-bit counters: rows,
+// non_null and sum of each of the four classes of rows that are in no slot.
+enum {
+  kGsNull = 0, kGsLong = 3, kGsOverflow = 6, kGsMarker = 9, kGroupSumsWords = 12  // (+0 rows, +1 non_null, +2 sum)
+};
+constexpr int kGroupSumsBlock = 1024;  // numeric route: 16 waves share one LDS table
+// numeric route: the workgroup's LDS table: 8-byte key, 4-byte rows, 4-byte non_null, 8-byte sum = 24 bytes a slot,
+// 96 KiB of the CU's 160 (8192 slots would not fit): one workgroup a CU
+constexpr uint32_t kGroupSumsLdsSlots = 4096;
+// string route: VcLdsStrings' slots with a non_null and a sum: 40 bytes a slot, 40 KiB
+constexpr uint32_t kGroupSumsStrLdsSlots = kValueCountsStrLdsSlots;
+// dictionary route: entries whose cells (4-byte rows, 4-byte non_null, 8-byte sum) are kept in LDS: 64 KiB
+constexpr uint32_t kGroupSumsDictLdsEntries = 4096;
+// the value column of a walk
+struct GroupSumsValue {
+  const void *values;       // 8-byte values (Int64 / Float64 after the widening staging)
+  const uint8_t *validity;  // or nullptr: every row is non-NULL
+  int64_t offset;           // its Arrow offset, unrelated to the group column's
+};
+struct GroupSumsTable {
+  unsigned long long *keys, *keys2, *rows, *non_null, *sums;
+  uint32_t *lens;
+  uint8_t *store;
+  unsigned long long *words;  // the task's kGroupSumsWords counters
+  uint64_t mask;
+  uint64_t salt;
+  uint32_t max_value_bytes;
+  uint32_t pad;
+};
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

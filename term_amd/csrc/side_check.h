@@ -58,12 +58,14 @@ TGX_SIDE_KIND(valuerule)
 TGX_SIDE_KIND(valuecounts)
 TGX_SIDE_KIND(paircounts)
 TGX_SIDE_KIND(groupcounts)
+TGX_SIDE_KIND(groupsums)
 #undef TGX_SIDE_KIND
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupcounts_plan_ready(const tgx_plan *plan, tgx_error *err);
+tgx_status groupsums_plan_ready(const tgx_plan *plan, tgx_error *err);
 
 // in the order of the blob's sections
 inline constexpr SideKind kSideKinds[kNumSide] = {
@@ -81,6 +83,8 @@ inline constexpr SideKind kSideKinds[kNumSide] = {
      paircounts_check_column, paircounts_state_new, true},
     {TGX_CHECK_GROUP_COUNTS, "GROUP_COUNTS", groupcounts_plan_add, groupcounts_plan_ready, groupcounts_mark_columns,
      groupcounts_check_column, groupcounts_state_new, true},
+    {TGX_CHECK_GROUP_SUMS, "GROUP_SUMS", groupsums_plan_add, groupsums_plan_ready, groupsums_mark_columns,
+     groupsums_check_column, groupsums_state_new, true},
 };
 
 // where `kind` stands in kSideKinds (and in tgx_state::side, tgx_plan::side_on), or -1: not a kind of this file

@@ -268,6 +268,11 @@ class CheckBuilder:
         evaluating it fails identifier validation, as in the reference; a configured object goes through constraint()"""
         return self.constraint(TemporalOrderingConstraint(table_name))
 
+    def cross_table_sum(self, left_column, right_column):
+        """core/check.rs:2054-2065: pushes CrossTableSumConstraint::new(left, right); a configured object goes through
+        constraint()"""
+        return self.constraint(CrossTableSumConstraint(left_column, right_column))
+
     def has_consistent_data_type(self, column, threshold):
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
@@ -452,6 +457,54 @@ class TemporalOrderingConstraint:
     def tolerance_seconds(self, seconds):
         self.spec["tolerance_seconds"] = int(seconds)
         return self
+
+
+class CrossTableSumConstraint:
+    """constraints/cross_table_sum.rs:87-140, one method per builder call of the reference: SUM(left) against SUM(right),
+    `left_column` / `right_column` qualified as "table.column", over the whole tables or per group of ONE group column
+    that both tables have.  Each side is one walk of its table on the device (TGX_CHECK_GROUP_SUMS, or NUMERIC_STATS for
+    the ungrouped form); the outer join runs on the host.  It needs ValidationSuite.run(table, tables={name: table})"""
+
+    def __init__(self, left_column, right_column):
+        self.spec = {"type": "cross_table_sum", "left_column": left_column, "right_column": right_column, "group_by": [],
+                     "tolerance": 0.0, "max_violations_reported": 100, "max_groups": _lib.GROUP_SUMS_MAX_GROUPS}
+
+    def group_by(self, columns):
+        self.spec["group_by"] = _cols(columns)
+        return self
+
+    def tolerance(self, tolerance):
+        self.spec["tolerance"] = abs(float(tolerance))  # (:129-132)
+        return self
+
+    def max_violations_reported(self, n):
+        self.spec["max_violations_reported"] = int(n)
+        return self
+
+    def max_groups(self, n):
+        """this layer's own: the groups a side's table on the device is sized for (1 .. 65 536, the default).  A side
+        with more (overflow rows), or with keys longer than 256 bytes, makes the constraint an error that names the
+        bound -- never a verdict on partial sums"""
+        self.spec["max_groups"] = int(n)
+        return self
+
+    def name(self): return "cross_table_sum"
+    def left_column(self): return self.spec["left_column"]
+    def right_column(self): return self.spec["right_column"]
+    def group_by_columns(self): return list(self.spec["group_by"])
+
+    def verdict_from_sums(self, left, right):
+        """the join and the verdict on given sums (no device): left / right are numbers for the ungrouped form, else
+        dicts {"groups": [[key, sum], ..] ascending by key, "null_group": sum or None, "overflow_rows", "long_rows"}"""
+        out, err = C.c_char_p(), _Error()
+        _host_check(_host().tgx_host_cross_table_sum_json(json.dumps(self.spec).encode(),
+                                                          json.dumps({"left": left, "right": right}).encode(),
+                                                          C.byref(out), C.byref(err)), err)
+        v = json.loads(_take(out))
+        for k in ("metric", "total_left_sum", "total_right_sum", "max_difference"):
+            if isinstance(v[k], str):
+                v[k] = float(v[k])
+        return v
 
 
 class NumericValidation:
@@ -691,9 +744,11 @@ class ValidationSuite:
 
     def name(self): return self.spec["name"]
 
-    def run(self, table):
+    def run(self, table, tables=None):
         """table: dict name -> term_amd.Column (one batch), a list of such dicts (batches), a pyarrow Table /
-        RecordBatch, or None (no table registered)."""
+        RecordBatch, or None (no table registered).  tables: {name: table} of further tables, each registered under its
+        name beside the suite's own (which is registered under the suite's table_name): what cross-table constraints
+        read."""
         name_arr, n_cols, col_arr, n_batches, _keep = _flatten_table(table)
         out = C.c_char_p()
         err = _Error()
@@ -701,9 +756,23 @@ class ValidationSuite:
         declared = _arrow_type_names(table)
         if declared:  # (what the builder declared wins)
             spec = dict(spec, column_types=dict(declared, **spec.get("column_types", {})))
-        _host_check(_host().tgx_host_run_suite_json(json.dumps(spec).encode(), name_arr, n_cols, col_arr,
-                                                    n_batches, C.byref(out), C.byref(err)), err)
-        return ValidationResult(_take(out))
+        if tables is None:
+            _host_check(_host().tgx_host_run_suite_json(json.dumps(spec).encode(), name_arr, n_cols, col_arr,
+                                                        n_batches, C.byref(out), C.byref(err)), err)
+            return ValidationResult(_take(out))
+        flat = [] if n_cols == 0 else [(spec.get("table_name", "data"), name_arr, n_cols, col_arr, n_batches, _keep)]
+        for name, t in tables.items():
+            flat.append((name,) + tuple(_flatten_table(t)))
+        arr = (_HostTable * max(1, len(flat)))()
+        for slot, (name, names, nc, cols, nb, _k) in zip(arr, flat):
+            slot.name = name.encode()
+            slot.column_names = C.cast(names, C.POINTER(C.c_char_p))
+            slot.n_columns = nc
+            slot.columns = C.cast(cols, C.POINTER(_Column))
+            slot.n_batches = nb
+        _host_check(_host().tgx_host_run_suite_tables_json(json.dumps(spec).encode(), arr, len(flat), C.byref(out),
+                                                           C.byref(err)), err)
+        return ValidationResult(_take(out))  # (`flat` kept every table's buffers alive through the call)
 
 
 def _arrow_type_names(table):
@@ -1090,6 +1159,12 @@ class AnalysisRunner:
 _HOST = None
 
 
+class _HostTable(C.Structure):
+    """tgx_host_table (include/tgx_host.h)"""
+    _fields_ = [("name", C.c_char_p), ("column_names", C.POINTER(C.c_char_p)), ("n_columns", C.c_size_t),
+                ("columns", C.POINTER(_Column)), ("n_batches", C.c_size_t)]
+
+
 def _host():
     global _HOST
     if _HOST is None:
@@ -1110,6 +1185,9 @@ def _host():
         L.tgx_host_analyzer_plan_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_pair_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_group_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_run_suite_tables_json.argtypes = [C.c_char_p, C.POINTER(_HostTable), C.c_size_t,
+                                                     C.POINTER(C.c_char_p), E]
+        L.tgx_host_cross_table_sum_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_free.argtypes = [C.c_void_p]
         L.tgx_host_free.restype = None
         _HOST = L

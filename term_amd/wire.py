@@ -83,6 +83,18 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                                every total > 0, every non_null <= its total (its rows, for the three classes), every
                                length <= max_value_bytes, no key twice, and
                                sum(totals) + null_group_rows + overflow_rows + long_rows == seen.
+    and ONLY for plans with GROUP_SUMS checks, behind the GROUP_COUNTS section if there is one:
+    u32 magic 'GSUM', u32 n_tasks
+    n_tasks     x { u32 max_groups, max_value_bytes              (the plan's parameters)
+                    u32 kind (0 no keys, 1 int64, 2 bytes), u32 values (0 no rows, 1 integer sums, 2 double sums)
+                    u64 seen, then { u64 rows, non_null, sum } of the NULL group, of overflow and of the long rows,
+                    u64 n_entries
+                    n_entries x { i64 key; u64 rows, non_null, sum }                      kind 1, ascending int64
+                             or { u32 length; u8 bytes[length]; u64 rows, non_null, sum } } kind 2, ascending bytewise
+                               a sum is the Int64 that wrapped (values 1) or the bits of the double (values 2); every
+                               rows > 0, every non_null <= its rows, a sum of 0 where non_null is 0, every length <=
+                               max_value_bytes, no key twice, values 0 only with seen 0 and no keys, and
+                               sum(rows) + null_group_rows + overflow_rows + long_rows == seen.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -97,6 +109,7 @@ VALUE_RULE_MAGIC = 0x4C525656  # 'VVRL'
 VALUE_COUNTS_MAGIC = 0x544E4356  # 'VCNT'
 PAIR_COUNTS_MAGIC = 0x544E4350  # 'PCNT'
 GROUP_COUNTS_MAGIC = 0x544E4347  # 'GCNT'
+GROUP_SUMS_MAGIC = 0x4D555347  # 'GSUM'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -270,8 +283,34 @@ def group_counts_state(max_groups, max_value_bytes, groups, seen=None, null_grou
     return out
 
 
+def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=None, null_group=(0, 0, 0),
+                     overflow=(0, 0, 0), long=(0, 0, 0), ordered=True, values=None):
+    """a GROUP_SUMS task: the plan's parameters, the classes and the entries of `groups` (key -> (rows, non_null, sum);
+    every key an int, or every key bytes).  null_group / overflow / long: (rows, non-NULL values among them, their sum).
+    A sum is an int (taken modulo 2^64) or, with is_float, a float.  seen defaults to what the invariant makes it, values
+    (the blob's value kind) to what is_float says, 0 for a state without rows.  `ordered=False` keeps the entries in the
+    order given (for a blob that is to be refused)."""
+    items = list(groups.items()) if hasattr(groups, "items") else list(groups)
+    is_bytes = bool(items) and isinstance(items[0][0], (bytes, bytearray))
+    if ordered:
+        items.sort(key=lambda kv: kv[0])
+    if seen is None:
+        seen = sum(v[0] for _, v in items) + null_group[0] + overflow[0] + long[0]
+    if values is None:
+        values = 0 if seen == 0 else (2 if is_float else 1)
+
+    def cls(c):
+        return struct.pack("<QQ", c[0], c[1]) + (struct.pack("<d", c[2]) if is_float else
+                                                  struct.pack("<Q", c[2] & ((1 << 64) - 1)))
+    out = struct.pack("<4IQ", max_groups, max_value_bytes, (2 if is_bytes else 1) if items else 0, values, seen)
+    out += cls(null_group) + cls(overflow) + cls(long) + struct.pack("<Q", len(items))
+    for k, v in items:
+        out += (struct.pack("<I", len(k)) + bytes(k) if is_bytes else struct.pack("<q", k)) + cls(v)
+    return out
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=(), value_counts=(), pair_counts=(), group_counts=()):
+         value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -288,5 +327,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", PAIR_COUNTS_MAGIC, len(pair_counts)) + b"".join(pair_counts)
     if group_counts:
         tail += struct.pack("<II", GROUP_COUNTS_MAGIC, len(group_counts)) + b"".join(group_counts)
+    if group_sums:
+        tail += struct.pack("<II", GROUP_SUMS_MAGIC, len(group_sums)) + b"".join(group_sums)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
