@@ -37,9 +37,9 @@ def float_class(rows, vals):
     """(rows, non_null, fsum, sum of magnitudes); a NaN or opposite infinities make fsum NaN, as IEEE addition does"""
     try:
         exact = math.fsum(vals)
-    except (ValueError, OverflowError):  # (inf - inf; an intermediate overflow cannot happen at the tests' magnitudes)
+    except (ValueError, OverflowError):  # (inf - inf, or partial sums beyond DBL_MAX: float_rule decides such a group)
         exact = math.nan
-    return (rows, len(vals), exact, math.fsum(abs(v) for v in vals) if vals else 0.0)
+    return (rows, len(vals), exact, magnitudes_of(vals))
 
 
 def walk(values, groups, max_value_bytes=256, is_float=False):
@@ -77,6 +77,142 @@ def float_bound(non_null, exact, magnitudes):
     u = 2.0 ** -53
     k = max(non_null - 1, 0)
     return k * u / (1 - k * u) * magnitudes + u * abs(exact)
+
+
+def magnitudes_of(vals):
+    """math.fsum of the magnitudes; inf where an infinity is among them or the exact sum lies beyond DBL_MAX (fsum raises
+    OverflowError there), NaN with a NaN"""
+    try:
+        return math.fsum(abs(v) for v in vals) if len(vals) else 0.0
+    except OverflowError:
+        return math.inf
+
+
+def float_rule(vals):
+    """how a float group's sum is decided, in the manner of exact_histogram.sum_rules.  ("bound", None): finite values
+    whose magnitudes add up to a finite number -- no order of additions overflows, float_bound holds.  Otherwise, by IEEE
+    addition in any order or tree:
+      - a NaN among the values gives NaN: ("is", nan);
+      - infinities of both signs give NaN: ("is", nan);
+      - infinities of ONE sign give that infinity, provided the finite values cannot overflow on their own (their
+        magnitudes add up to a finite number; an overflow to the other infinity would meet this one as NaN):
+        ("is", +-inf);
+      - finite values whose magnitudes add up beyond DBL_MAX (with or without an infinity beside them) overflow in some
+        orders and not in others: ("unpinned", None).  The group's rows and non_null stay pinned.
+    vals: the group's non-NULL values"""
+    pos = neg = False
+    for v in vals:
+        if v != v:
+            return ("is", math.nan)
+        pos |= v == math.inf
+        neg |= v == -math.inf
+    if pos and neg:
+        return ("is", math.nan)
+    if not math.isfinite(magnitudes_of([v for v in vals if math.isfinite(v)])):
+        return ("unpinned", None)
+    if pos or neg:
+        return ("is", math.inf if pos else -math.inf)
+    return ("bound", None)
+
+
+def float_failure(got, rule, non_null, exact, magnitudes):
+    """None, or why `got` is not a double sum of the group; rule: float_rule's answer ("bound" without looking when the
+    magnitudes are finite)"""
+    how, value = rule
+    if how == "unpinned":
+        return None
+    if how == "is":
+        same = (got != got) if value != value else got == value
+        return None if same else "the overflow rule gives %r, got %r" % (value, got)
+    bound = float_bound(non_null, exact, magnitudes)
+    if got == got and abs(got - exact) <= bound:
+        return None
+    return "%r is %r from fsum %r, the bound is %r" % (got, abs(got - exact), exact, bound)
+
+
+# ---- the numpy twin (the differential tester's tables: 400 000 rows a case) ----------------------------------------------
+def _float_class_np(rows, vals):
+    """float_class over a float64 slice"""
+    if len(vals) == 1:
+        v = float(vals[0])
+        return (rows, 1, v, abs(v))
+    return float_class(rows, vals.tolist())
+
+
+def walk_np(values, valid, keys, key_valid=None, words=None, max_value_bytes=256, rules=False):
+    """walk() over arrays: `values` an int64 or float64 array (the value column, widened), `valid` its non-NULL mask,
+    `keys` an int64 array -- the group column's values, or with `words` (a list of distinct bytes) the index of each
+    row's word -- and `key_valid` the group column's mask (None: no NULL keys).  Sorts the rows by key once and sums
+    each group's slice: integers wrapping in uint64, floats with math.fsum as the walk does.
+    rules=True adds, for float values, what a comparison beyond the entries needs: s["all"] and s["counted_class"], the
+    float_class of every non-NULL value and of the entries' values together, and s["rules"], float_rule's answer for
+    every entry (by key) and class (by name: null_group, long_rows, counted_class, all) whose magnitudes are not finite"""
+    import numpy as np
+
+    values, valid, keys = np.asarray(values), np.asarray(valid, bool), np.asarray(keys, np.int64)
+    is_float = values.dtype == np.float64
+    if not is_float and values.dtype != np.int64:
+        raise TypeError("widen first: %s" % values.dtype)
+    n = len(values)
+    key_valid = np.ones(n, bool) if key_valid is None else np.asarray(key_valid, bool)
+
+    def cls(rows_mask):
+        v = values[rows_mask & valid]
+        if is_float:
+            return float_class(int(rows_mask.sum()), v.tolist())
+        return (int(rows_mask.sum()), len(v), wrap(int(v.view(np.uint64).sum(dtype=np.uint64))))
+
+    nothing = float_class(0, []) if is_float else int_class(0, [])
+    s = dict(seen=n, is_float=bool(is_float) and n > 0, null_group=cls(~key_valid) if n else nothing, overflow=nothing)
+    by_rule = {}
+
+    def judged(name, c, vals):
+        if rules and is_float and not math.isfinite(c[3]):
+            by_rule[name] = float_rule(vals.tolist())
+        return c
+    if words is not None:
+        order_of = np.argsort(np.array([bytes(w) for w in words] + [b""], dtype=object)[:-1], kind="stable") \
+            if len(words) else np.zeros(0, np.int64)
+        rank = np.empty(len(words), np.int64)
+        rank[order_of] = np.arange(len(words))
+        is_long = np.array([len(w) > max_value_bytes for w in words], bool)
+        long_rows = key_valid & is_long[np.where(key_valid, keys, 0)] if len(words) else np.zeros(n, bool)
+        sort_keys = rank[np.where(key_valid, keys, 0)] if len(words) else keys
+    else:
+        long_rows, sort_keys = np.zeros(n, bool), keys
+    s["long_rows"] = cls(long_rows) if n else nothing
+    live = key_valid & ~long_rows
+    rows = np.flatnonzero(live)
+    rows = rows[np.argsort(sort_keys[rows], kind="stable")]
+    k_sorted = sort_keys[rows]
+    starts = np.flatnonzero(np.concatenate([[True], k_sorted[1:] != k_sorted[:-1]])) if len(rows) else np.zeros(0, np.int64)
+    ends = np.concatenate([starts[1:], [len(rows)]]).astype(np.int64)
+    v_ok = valid[rows]
+    non_null = np.add.reduceat(v_ok.astype(np.int64), starts) if len(starts) else np.zeros(0, np.int64)
+    entries = {}
+    if is_float:
+        v_sorted = values[rows]
+        for a, b, nn, key in zip(starts.tolist(), ends.tolist(), non_null.tolist(), keys[rows[starts]].tolist()):
+            vals = v_sorted[a:b][v_ok[a:b]] if nn != b - a else v_sorted[a:b]
+            key = bytes(words[key]) if words is not None else key
+            entries[key] = judged(key, _float_class_np(b - a, vals), vals) if nn else (b - a, 0, 0.0, 0.0)
+        s["counted"] = (sum(e[0] for e in entries.values()), sum(e[1] for e in entries.values()))
+    else:
+        masked = np.where(v_ok, values[rows], 0).view(np.uint64)
+        sums = np.add.reduceat(masked, starts) if len(starts) else np.zeros(0, np.uint64)
+        for a, b, nn, t, key in zip(starts.tolist(), ends.tolist(), non_null.tolist(), sums.tolist(),
+                                    keys[rows[starts]].tolist()):
+            entries[bytes(words[key]) if words is not None else key] = (b - a, nn, wrap(t))
+        s["counted"] = (sum(e[0] for e in entries.values()), sum(e[1] for e in entries.values()),
+                        wrap(sum(e[2] for e in entries.values())))
+    if rules and is_float:
+        for name, rows_mask in (("null_group", ~key_valid), ("long_rows", long_rows), ("counted_class", live),
+                                ("all", np.ones(n, bool))):
+            judged(name, s[name] if name in s else s.setdefault(name, cls(rows_mask)), values[rows_mask & valid])
+        s["rules"] = by_rule
+    s["entries"] = entries  # (ascending by key already: the rows were sorted by it)
+    s["groups"] = len(entries)
+    return s
 
 
 # ---- the constraint -------------------------------------------------------------------------------------------------------

@@ -89,6 +89,90 @@ def binning_of(nums, others, bins):
     return (r["min"], ej.bin_width(r["min"], r["max"], bins), bins)
 
 
+# ---- the same over numpy arrays (the differential tester's tables: 400 000 rows a case) ---------------------------------
+# A VALUE side is (codes, words): an int64 array of indices into a list of DISTINCT bytes; a BINNED side is the column
+# CAST AS DOUBLE as a float64 array.  tests/test_exact_pair_counts.py holds each of these to its walk.
+def side_range_np(nums, both_valid):
+    """side_range: nums the numeric side CAST AS DOUBLE, both_valid the rows with both sides non-NULL"""
+    import numpy as np
+
+    both = np.asarray(nums, np.float64)[np.asarray(both_valid, bool)]
+    finite = both[np.isfinite(both)]
+    return dict(seen=len(nums), both_non_null=len(both), n=len(finite), non_finite=len(both) - len(finite),
+                min=float(finite.min()) if len(finite) else None, max=float(finite.max()) if len(finite) else None)
+
+
+def binning_of_range(r, bins):
+    """binning_of from a side_range"""
+    if r["n"] == 0:
+        return None
+    return (r["min"], ej.bin_width(r["min"], r["max"], bins), bins)
+
+
+def _bins_np(v, binning):
+    """per row of a BINNED side: (bin index as int64, non-finite value, index outside [0, bins]), by the arithmetic of
+    exact_joint.joint_counts_np: float64 subtract, divide and floor"""
+    import numpy as np
+
+    origin, width, bins = binning
+    non_finite = ~np.isfinite(v)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = (np.where(non_finite, origin, v) - origin) / width
+        inside = np.isfinite(f)
+        i = np.floor(np.where(inside, f, -1.0))
+    outside = ~inside | (i < 0) | (i > bins)
+    return np.where(outside, 0, i).astype(np.int64), non_finite, outside
+
+
+def _cells_np(words, max_value_bytes):
+    """per word of a VALUE side: (its rank in bytewise order, longer than max_value_bytes)"""
+    import numpy as np
+
+    order = np.argsort(np.array([bytes(w) for w in words] + [b""], dtype=object)[:-1], kind="stable")
+    rank = np.empty(len(words), np.int64)
+    rank[order] = np.arange(len(words))
+    return rank, order, np.array([len(w) > max_value_bytes for w in words] + [False], bool)[:-1]
+
+
+def walk_np(x, y, both_valid, x_side=None, y_side=None, max_value_bytes=256):
+    """walk() over arrays: x / y are (codes, words) for a VALUE side (x_side / y_side None) or a float64 array for a
+    BINNED one; both_valid: the rows with both sides non-NULL"""
+    import numpy as np
+
+    both = np.asarray(both_valid, bool)
+    n = len(both)
+    is_long, non_finite, outside = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool)
+    ranks, cell_of = [], []
+    for col, side in ((x, x_side), (y, y_side)):
+        if side is None:
+            codes, words = np.where(both, np.asarray(col[0], np.int64), 0), col[1]
+            if len(words) == 0:  # (no word: no non-NULL row)
+                ranks.append(np.zeros(n, np.int64))
+                cell_of.append(lambda r: b"")
+                continue
+            rank, order, long_word = _cells_np(words, max_value_bytes)
+            is_long |= both & long_word[codes]
+            ranks.append(rank[codes])
+            cell_of.append(lambda r, words=words, order=order: bytes(words[order[r]]))
+        else:
+            i, nf, out = _bins_np(np.asarray(col, np.float64), side)
+            non_finite |= nf
+            outside |= out
+            ranks.append(i)
+            cell_of.append(lambda r: r)
+    non_finite &= both & ~is_long
+    outside &= both & ~is_long & ~non_finite
+    counted = both & ~is_long & ~non_finite & ~outside
+    out = dict(seen=n, both_non_null=int(both.sum()), distinct=0, counted=int(counted.sum()), overflow_rows=0,
+               long_rows=int(is_long.sum()), non_finite=int(non_finite.sum()), out_of_range=int(outside.sum()))
+    rx, ry = ranks[0][counted], ranks[1][counted]
+    span = int(ry.max()) + 1 if len(ry) else 1
+    flat, c = np.unique(rx * span + ry, return_counts=True)
+    out["counts"] = {(cell_of[0](k // span), cell_of[1](k % span)): cnt for k, cnt in zip(flat.tolist(), c.tolist())}
+    out["distinct"] = len(flat)
+    return out
+
+
 def marginals(counts):
     return ej.marginals(counts)
 

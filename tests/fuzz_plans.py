@@ -18,19 +18,38 @@ that are simply finalized: one or two tasks (timestamp column, group column or n
 integer column, the timestamp column itself included), each with 1 to 3 thresholds (sometimes more than one neighbour
 pass compares) taken from the gaps tests/exact_time_gap.py finds in the whole table, some under one of the environments
 of tests/test_gpu_time_gap.py that force the sort's other routes.  It changes nothing an earlier stream drew.  All five
-counters of every spec are compared for equality.  tests/test_fuzz_cases.py tests this tester without a device."""
+counters of every spec are compared for equality.
+
+VALUE_RULE and the four counting kinds (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS) are drawn after it, from a
+stream of their own again, for tables of at most 400 000 rows and every `after` and `seq` -- the five kinds are additive:
+one to three rules (now and then nine) on a numeric column, BETWEEN with bounds from the column's own values; a key column
+of kind Int64, Int32, a narrow presentation or a string in any layout, with max_value_bytes that sometimes cuts real
+words; one to three GROUP_COUNTS members on one walk; a GROUP_SUMS over integer or float values; a PAIR_COUNTS of two
+string sides or of a string and a numeric one, which makes the case run twice as the two-phase kinds above do (RANGE,
+then BINNED with the binning of the exact range, sometimes moved).  The bounds are drawn against the exact number of keys
+d: with d <= bound include/tgx.h promises no overflow, and the entries, their order and every counter are compared for
+equality with tests/exact_value_counts.py, exact_pair_counts.py, exact_group_counts.py and exact_group_sums.py (float
+sums within exact_group_sums.float_bound, or by its float_rule); so is a table of more keys that reports no overflow;
+one that reports overflow is held to the identities of include/tgx.h, to holding only keys of the table, none counted too
+often, and to the slots it has.  The four VALUE_RULE counters are compared with exact_value_rule.counts_np.
+tests/test_fuzz_cases.py tests this tester without a device."""
 import math
 import sys
 
 import numpy as np
 
+import exact_group_counts as EGC
+import exact_group_sums as EGS
 import exact_histogram as EH
 import exact_hll as H
 import exact_joint as EJ
+import exact_pair_counts as EP
 import exact_temporal as ET
 import exact_time_gap as EG
 import exact_quantiles as Q
 import exact_ranks as R
+import exact_value_counts as EVC
+import exact_value_rule as EV
 import exact_widening as W
 import oracle_binding as orc
 import term_amd as T
@@ -365,6 +384,7 @@ class Case:
                 self.present[ci] = fits[int(rng5.integers(0, len(fits)))]
         self.draw_two_phase_and_temporal(np.random.default_rng([seed, 8]))
         self.draw_time_gap(np.random.default_rng([seed, 9]))
+        self.draw_rules_and_counts(np.random.default_rng([seed, 10]))
 
     HISTOGRAM_BUCKETS = [1, 2, 5, 10, 100, 999, 1000]
     JOINT_BINS = [2, 5, 10, 127]
@@ -375,7 +395,7 @@ class Case:
         presentations above included, which saw the older expectations only -- is what it was.  A column presented as
         UInt64 or Boolean is TGX_UNSUPPORTED for the two-phase kinds and is not drawn for them (Int8 .. UInt32 are
         widened and stay); a column a TEMPORAL check reads arrives as Int64 whatever rng5 drew for it."""
-        self.phase, self.pass_two, self._cache = 1, {}, {}
+        self.phase, self.pass_two, self._cache, self.tables = 1, {}, {}, 1
         n = self.n
         if n > self.NEW_KINDS_MAX_ROWS:
             return
@@ -463,8 +483,140 @@ class Case:
             self.sort_route = pick(self.FORCED_SORT_ROUTES)
             self.sort_env = dict(SORT_SHAPES[self.sort_route][1])
 
+    COUNTING = ("value_counts", "pair_counts", "group_counts", "group_sums")
+    RULES_AND_COUNTS = ("rule",) + COUNTING
+    MAX_VALUE_BYTES = [256, 256, 20, 4, 1]  # (the shorter ones cut real words: those rows are long rows)
+    BOUND_LIMIT = 65536  # TGX_VALUE_COUNTS_MAX_DISTINCT, .._MAX_PAIRS, .._MAX_GROUPS
+    LOW_BOUND = 16  # a bound far below most columns' number of keys: 32 slots
+
+    def unsupported_as_key(self, ci):
+        return self.present[ci] == "bool" or self.present[ci] is np.uint64
+
+    def draw_rules_and_counts(self, rng10):
+        """VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS and GROUP_SUMS checks, from a stream of their own and
+        without touching anything drawn before (no presentation changes: a column presented as UInt64 or Boolean is
+        TGX_UNSUPPORTED as a key or rule column and is not drawn in those roles).  Every `after` and every `seq`: the
+        five kinds are additive.  The bounds are drawn against the exact number of keys d of the references -- d, d + 1,
+        10000, 65536, sometimes LOW_BOUND -- and key columns (pairs) with d <= 65536 are preferred, so that most tasks
+        are compared for full equality (tests/test_fuzz_cases.py holds the share of the others to a quarter)."""
+        n = self.n
+        if n > self.NEW_KINDS_MAX_ROWS:
+            return
+        numeric = [ci for ci, c in enumerate(self.cols) if c[0] in ("i", "f", "i32", "f32") and not self.unsupported_as_key(ci)]
+        keys = [ci for ci, c in enumerate(self.cols) if c[0] == "s" or (c[0] in ("i", "i32") and not self.unsupported_as_key(ci))]
+        strings = [ci for ci, c in enumerate(self.cols) if c[0] == "s"]
+        if not (numeric or keys) or rng10.random() >= 0.55:
+            return
+
+        def pick(a):
+            return a[int(rng10.integers(0, len(a)))]
+
+        def max_value_bytes():
+            return int(pick(self.MAX_VALUE_BYTES))
+
+        def bound_for(d):
+            how = str(rng10.choice(["d", "d+1", "10000", "65536", "low"], p=[0.27, 0.27, 0.09, 0.33, 0.04]))
+            bound = {"d": d, "d+1": d + 1, "10000": 10000, "65536": self.BOUND_LIMIT, "low": self.LOW_BOUND}[how]
+            return min(max(bound, 1), self.BOUND_LIMIT)
+
+        def key_column(mvb):
+            """a key column, one with at most BOUND_LIMIT keys if there is one (nine times in ten)"""
+            ci = pick(keys)
+            fits = [c for c in keys if self.reference(("value_counts", c, mvb))["distinct"] <= self.BOUND_LIMIT]
+            if fits and ci not in fits and rng10.random() < 0.9:
+                ci = pick(fits)
+            return ci
+
+        kinds = [k for k, possible in (("rule", numeric), ("value_counts", keys), ("pair_counts", strings),
+                                       ("group_counts", keys), ("group_sums", keys and numeric)) if possible]
+        # (a table none of whose key columns has at most BOUND_LIMIT keys can only overflow: those tasks are drawn, but
+        #  less often, so that three tasks in four of a kind stay pinned by their references)
+        tight = bool(keys) and all(self.reference(("value_counts", c, 256))["distinct"] > self.BOUND_LIMIT for c in keys)
+        often = {k: 0.12 if tight and k in ("value_counts", "group_counts", "group_sums") else 0.5 for k in kinds}
+        chosen = [k for k in kinds if rng10.random() < often[k]] or [pick([k for k in kinds if often[k] == 0.5] or kinds)]
+        if "rule" in chosen:
+            ci = pick(numeric)
+            is_float = self.cols[ci][0] in ("f", "f32")
+            wide, live = self.wide_of(ci), np.flatnonzero(self.cols[ci][3])
+            for _ in range(9 if rng10.random() < 0.12 else int(rng10.integers(1, 4))):  # (nine: a second launch group)
+                mode = int(pick([T.RULE_GE_ZERO, T.RULE_GT_ZERO, T.RULE_BETWEEN, T.RULE_BETWEEN, T.RULE_INTEGER]))
+                rule = EV.rule(mode)
+                if mode == T.RULE_BETWEEN:
+                    # bounds from the column's own values (NaN and both zeros included on float columns), in order by the
+                    # rule's own comparison three times in four -- lo > hi matches nothing
+                    a, b = ((wide[int(pick(live))] if len(live) and rng10.random() < 0.9 else wide.dtype.type(0)) for _ in range(2))
+                    as_double = is_float or bool(rng10.integers(0, 2))
+                    if as_double:
+                        a, b = float(a), float(b)
+                        ka, kb = EV.key(EV.bits_of(a)), EV.key(EV.bits_of(b))
+                    else:
+                        ka, kb = a, b = int(a), int(b)
+                    if (ka > kb) != (rng10.random() < 0.25):
+                        a, b = b, a
+                    flags = T.RULE_BOUNDS_AS_DOUBLE if as_double and (not is_float or rng10.random() < 0.5) else 0
+                    rule = EV.rule(mode, flags, *((0, 0, a, b) if as_double else (a, b, 0.0, 0.0)))
+                self.add(spec(T.VALUE_RULE, ci), ("rule", ci, rule))
+        if "value_counts" in chosen:
+            mvb = max_value_bytes()
+            ci = key_column(mvb)
+            bound = bound_for(self.reference(("value_counts", ci, mvb))["distinct"])
+            self.add(spec(T.VALUE_COUNTS, ci), ("value_counts", ci, bound, mvb))
+        if "group_counts" in chosen:
+            mvb = max_value_bytes()
+            ck = key_column(mvb)
+            bound = bound_for(self.reference(("value_counts", ck, mvb))["distinct"])
+            # (specs that share the group column and both bounds share one walk: its members)
+            for _ in range(int(rng10.integers(1, 4))):
+                cv = ck if rng10.random() < 0.2 else int(rng10.integers(0, len(self.cols)))
+                self.add(spec(T.GROUP_COUNTS, cv, column2=ck), ("group_counts", cv, ck, bound, mvb))
+        if "group_sums" in chosen:
+            mvb = max_value_bytes()
+            ck = key_column(mvb)
+            bound = bound_for(self.reference(("value_counts", ck, mvb))["distinct"])
+            cv = ck if ck in numeric and rng10.random() < 0.2 else pick(numeric)
+            if self.cols[cv][0] in ("f", "f32"):
+                # (a NaN, an infinity or magnitudes that add up beyond DBL_MAX leave a group to the overflow rule: such
+                #  a column keeps its task half the time, so that the sum bound decides three float tasks in four)
+                with np.errstate(over="ignore", invalid="ignore"):
+                    total = float(np.abs(self.doubles_of(cv)[self.cols[cv][3]]).sum())
+                if not math.isfinite(total) and rng10.random() < 0.5:
+                    cv = pick(numeric)
+            self.add(spec(T.GROUP_SUMS, cv, column2=ck), ("group_sums", cv, ck, bound, mvb))
+        if "pair_counts" in chosen:
+            mvb = max_value_bytes()
+            for attempt in range(3):
+                cx = pick(strings)
+                cy = pick(numeric) if numeric and rng10.random() < 0.6 else pick(strings)
+                if cy in numeric and rng10.random() < 0.5:
+                    cx, cy = cy, cx
+                e = ("pair_counts", cx, cy, 1, mvb, int(pick(self.JOINT_BINS)), bool(rng10.integers(0, 2)))
+                d = self.reference(("pair_counts", cx, cy, mvb, self.pair_binning(e)))["distinct"]
+                if d <= self.BOUND_LIMIT or rng10.random() >= 0.9:  # (pairs with at most BOUND_LIMIT keys preferred)
+                    break
+            self.add(spec(T.PAIR_COUNTS, cx, column2=cy), e[:3] + (bound_for(d),) + e[4:])
+
+    def pair_numeric_side(self, e):
+        """0 / 1: the side of a PAIR_COUNTS expectation that is a numeric column (the spec has two phases); None: none"""
+        sides = [k for k in (0, 1) if self.cols[e[1 + k]][0] != "s"]
+        assert len(sides) < 2, e
+        return sides[0] if sides else None
+
+    def pair_binning(self, e):
+        """the numeric side's (origin, width, bins) for pass two, from the exact reference's range of the whole table
+        (mutual_information.rs:219-233), sometimes with the origin half a width up; None: no numeric side, or no finite
+        row"""
+        side = self.pair_numeric_side(e)
+        if side is None:
+            return None
+        b = EP.binning_of_range(self.reference(("pair_range", e[1 + side], e[2 - side])), e[5])
+        if b is not None and e[6]:
+            b = (b[0] + b[1] / 2, b[1], b[2])
+        return b
+
     @staticmethod
     def columns_of_expect(e):
+        if e[0] in ("pair_counts", "group_counts", "group_sums"):
+            return (e[1],) if e[1] == e[2] else (e[1], e[2])
         if e[0] == "tuple":
             return tuple(e[1])
         if e[0] == "time_gap":
@@ -494,7 +646,8 @@ class Case:
     def describe(self):
         cols = ", ".join("%s%s/nulls=%d" % (c[0], "" if p is None else "as" + (p if isinstance(p, str) else p.__name__),
                                             int((~c[3]).sum())) for c, p in zip(self.cols, self.present))
-        checks = [e[0] if e[0] not in ("histogram", "joint", "temporal", "time_gap") else "%s%r" % (e[0], e[1:]) for e in self.expect]
+        checks = [e[0] if e[0] not in ("histogram", "joint", "temporal", "time_gap") + self.RULES_AND_COUNTS
+                  else "%s%r" % (e[0], e[1:]) for e in self.expect]
         return "seed %d: n=%d cols=[%s] checks=%s pass=%d batching=%s(%d) buffers=%s after=%s env=%s%s" % (
             self.seed, self.n, cols, checks, self.phase, self.mode, len(self.cuts) - 1, self.device,
             self.after + ("" if self.seq == "plain" else "/" + self.seq) + (" kept" if self.retain else "") +
@@ -530,7 +683,9 @@ class Case:
         T.init()
         plan = T.Plan(self.specs)
         self.set_parameters(plan)
+        self.tables = 1  # (the tables that counted rows into the state that is read: slots_held)
         if self.after == "ranks":
+            self.tables = max(1, sum(1 for r in range(self.world) if self.cuts[r + 1] > self.cuts[r]))
             from test_gpu_distributed_sim import _run_ranks
 
             on_device = self.device != "host"
@@ -557,6 +712,10 @@ class Case:
         # with a stored partial state); Spearman states hold their pairs on the device and stay as they are
         blob_at = int(self.rng.integers(0, n_batches + 1)) if self.after == "blob" and not any(
             e[0] == "spearman" for e in self.expect) else -1
+        if self.after == "merge":  # (the states that are given rows)
+            self.tables = max(1, len({b * n_states // max(1, n_batches) for b in order if self.cuts[b + 1] > self.cuts[b]}))
+        elif blob_at >= 0 and 0 < self.cuts[min(blob_at, n_batches)] < self.n:  # (rows before the blob and a table after it)
+            self.tables = 2
         if self.seq == "reuse":  # a first round in the other order, read and thrown away
             for b in reversed(order):
                 on_device = self.device == "device" or (self.device == "mixed" and bool(self.rng.integers(0, 2)))
@@ -598,6 +757,32 @@ class Case:
                 plan.set_temporal(si, **e[4])
             elif e[0] == "time_gap":
                 plan.set_time_gap(si, e[3])
+            elif e[0] == "rule":
+                plan.set_value_rule(si, **e[2])
+            elif e[0] == "value_counts":
+                plan.set_value_counts(si, max_distinct=e[2], max_value_bytes=e[3])
+            elif e[0] == "group_counts":
+                plan.set_group_counts(si, max_groups=e[3], max_value_bytes=e[4])
+            elif e[0] == "group_sums":
+                plan.set_group_sums(si, max_groups=e[3], max_value_bytes=e[4])
+            elif e[0] == "pair_counts":
+                side = self.pair_numeric_side(e)
+                sides = [None, None]
+                if side is not None:
+                    b = self.pass_two.get(si) if self.phase == 2 else None
+                    if b is not None and not self.valid_binning(b):
+                        # a range without a finite positive width: refused, as include/tgx.h promises; the spec stays in
+                        # its range phase and is compared as in pass one
+                        sides[side] = b
+                        try:
+                            plan.set_pair_counts(si, x=sides[0], y=sides[1], max_pairs=e[3], max_value_bytes=e[4])
+                        except T.TgxError as err:
+                            assert "TGX_INVALID_ARGUMENT" in str(err), err
+                        else:
+                            raise AssertionError("%r: set_pair_counts took %r" % (e, b))
+                        b = self.pass_two[si] = None
+                    sides[side] = "range" if b is None else b
+                plan.set_pair_counts(si, x=sides[0], y=sides[1], max_pairs=e[3], max_value_bytes=e[4])
             elif self.phase == 2 and e[0] == "histogram":
                 plan.set_histogram_edges(si, self.pass_two[si])
             elif self.phase == 2 and e[0] == "joint":
@@ -615,11 +800,17 @@ class Case:
                     raise AssertionError("%r: set_joint_binning took %r" % (e, b))
                 self.pass_two[si] = None
 
+    @staticmethod
+    def valid_binning(b):
+        return math.isfinite(b[0]) and math.isfinite(b[1]) and b[1] > 0.0
+
     def has_two_phases(self):
-        return any(e[0] in ("histogram", "joint") for e in self.expect)
+        return any(e[0] in ("histogram", "joint") or (e[0] == "pair_counts" and self.pair_numeric_side(e) is not None)
+                   for e in self.expect)
 
     def enter_pass_two(self):
-        """edges and binnings for every HISTOGRAM / JOINT_BINS spec, from the exact references' ranges of the whole table"""
+        """edges and binnings for every HISTOGRAM / JOINT_BINS / two-phase PAIR_COUNTS spec, from the exact references' ranges
+        of the whole table"""
         for si, e in enumerate(self.expect):
             if e[0] == "histogram":
                 self.pass_two[si] = self.histogram_edges(e)
@@ -630,6 +821,8 @@ class Case:
                 elif e[4]:  # the origin half a width up: the rows of the lowest half bin fall outside
                     b = (b[0] + b[1] / 2, b[1], b[2] + b[3] / 2, b[3], b[4])
                 self.pass_two[si] = b
+            elif e[0] == "pair_counts":  # (None: no numeric side, or no finite row -- the spec stays in its range phase)
+                self.pass_two[si] = self.pair_binning(e)
         self.phase = 2
 
     def histogram_edges(self, e):
@@ -649,6 +842,14 @@ class Case:
             d = d[np.isfinite(d)]
             return sorted(np.random.default_rng(sample_seed).choice(d, size=buckets + 1).tolist())
         return exact
+
+    def string_keys(self, ci):
+        """(index of each row's word, the words as bytes, validity) of a string column, whatever its layout"""
+        key = ("string_keys", ci)
+        if key not in self._cache:
+            extra = self.cols[ci][4]
+            self._cache[key] = (np.asarray(extra[4][:self.n], np.int64), [w.encode("utf-8") for w in extra[3]])
+        return self._cache[key] + (self.cols[ci][3],)
 
     def wide_of(self, ci):
         """the 8-byte values the device widens column ci to (exact_widening.py: nothing converted by a float unit)"""
@@ -680,6 +881,64 @@ class Case:
                 ct, cg = key[1], key[2]
                 self._cache[key] = EG.gaps_np(self.cols[ct][1], self.cols[ct][3], *(
                     (self.cols[cg][1], self.cols[cg][3]) if cg >= 0 else (None, None)))
+            elif what == "value_counts":  # (column, max_value_bytes)
+                ci = key[1]
+                if self.cols[ci][0] != "s":
+                    self._cache[key] = EVC.twin_ints(self.wide_of(ci), self.cols[ci][3])
+                else:  # a bincount of the picks over the words, which are distinct by construction
+                    codes, words, mask = self.string_keys(ci)
+                    per_word = np.bincount(codes[mask], minlength=len(words)).tolist()
+                    held = {w: c for w, c in zip(words, per_word) if c and len(w) <= key[2]}
+                    long_rows = sum(c for w, c in zip(words, per_word) if len(w) > key[2])
+                    self._cache[key] = EVC.summary(self.n, int(mask.sum()), held, long_rows)
+            elif what == "group_counts":  # (value column, key column, max_value_bytes)
+                cv, ck, mvb = key[1:]
+                valid = self.cols[cv][3]
+                if self.cols[ck][0] != "s":
+                    self._cache[key] = EGC.walk_np(valid, self.wide_of(ck), self.cols[ck][3])
+                else:  # the words ranked bytewise stand in for the keys; the rows of long words are a class of their own
+                    codes, words, mask = self.string_keys(ck)
+                    order = sorted(range(len(words)), key=words.__getitem__)
+                    rank = np.empty(len(words), np.int64)
+                    rank[order] = np.arange(len(words))
+                    is_long = mask & np.array([len(w) > mvb for w in words] + [False], bool)[:-1][codes]
+                    s = EGC.walk_np(valid, rank[codes], mask & ~is_long)
+                    s["long_rows"], s["long_non_null"] = int(is_long.sum()), int((is_long & valid).sum())
+                    s["null_group_rows"] -= s["long_rows"]
+                    s["null_group_non_null"] -= s["long_non_null"]
+                    s["entries"] = {words[order[k]]: v for k, v in s["entries"].items()}
+                    self._cache[key] = s
+            elif what == "group_sums":  # (value column, key column, max_value_bytes)
+                cv, ck, mvb = key[1:]
+                values = self.wide_of(cv)
+                if self.cols[ck][0] != "s":
+                    codes, words, mask = self.wide_of(ck), None, self.cols[ck][3]
+                else:
+                    codes, words, mask = self.string_keys(ck)
+                self._cache[key] = EGS.walk_np(values, self.cols[cv][3], codes, mask, words, mvb, rules=True)
+            elif what == "pair_range":  # (numeric column, the other side's column)
+                self._cache[key] = EP.side_range_np(self.doubles_of(key[1]), self.cols[key[1]][3] & self.cols[key[2]][3])
+            elif what == "pair_counts":  # (x column, y column, max_value_bytes, the numeric side's binning or None)
+                cx, cy, mvb, binning = key[1:]
+                sides, args, numeric = [], [], False
+                for ci in (cx, cy):
+                    if self.cols[ci][0] == "s":
+                        codes, words, _ = self.string_keys(ci)
+                        sides.append(None)
+                        args.append((codes, words))
+                    else:
+                        numeric = True
+                        sides.append(binning)
+                        args.append(self.doubles_of(ci))
+                if numeric and (binning is None or not self.valid_binning(binning)):
+                    # (a numeric side without a binning the library takes: the spec never leaves its range phase)
+                    self._cache[key] = dict(distinct=0)
+                else:
+                    self._cache[key] = EP.walk_np(args[0], args[1], self.cols[cx][3] & self.cols[cy][3], sides[0], sides[1], mvb)
+            elif what == "pair_zeros":  # +0.0 AND -0.0 among the finite values of the rows with both sides non-NULL?
+                d = self.doubles_of(key[1])[self.cols[key[1]][3] & self.cols[key[2]][3]]
+                z = d[d == 0.0]
+                self._cache[key] = bool(len(z)) and bool(np.signbit(z).any()) and not bool(np.signbit(z).all())
             elif what == "both_zeros":  # does the column hold +0.0 AND -0.0 among the rows `key[2]` names?
                 d = self.doubles_of(key[1])[self.live_mask(key[2])]
                 z = d[d == 0.0]
@@ -692,12 +951,12 @@ class Case:
             m &= self.cols[ci][3] & np.isfinite(self.doubles_of(ci))
         return m
 
-    def same_extreme(self, e, name, got, want, ci, live_cols):
+    def same_extreme(self, e, name, got, want, ci, live_cols, zeros_key=None):
         """an extreme bit for bit (float.hex: -0.0 is not 0.0).  Only where +0.0 and -0.0 both occur among the rows it
         runs over and it IS zero, either zero stands: they compare equal, and no MIN / MAX is pinned on which it keeps"""
         if want is None:
             assert math.isnan(got), (e, name, got)
-        elif want == 0.0 and got == 0.0 and self.reference(("both_zeros", ci, tuple(live_cols))):
+        elif want == 0.0 and got == 0.0 and self.reference(zeros_key or ("both_zeros", ci, tuple(live_cols))):
             pass
         else:
             assert float(got).hex() == float(want).hex(), (e, name, got, want)
@@ -766,6 +1025,186 @@ class Case:
         seen, _, gaps, violations, _ = want
         assert (r.total, r.non_null, r.matches) == (seen, gaps, gaps - violations), (e, r.total, r.non_null, r.matches, want)
 
+    # ---- VALUE_RULE and the four counting kinds ----
+    def check_rule(self, e, si, r, st):
+        _, ci, rule = e
+        want = EV.counts_np(rule, self.wide_of(ci), self.cols[ci][3])
+        got = tuple(st.value_rule_counts(si))
+        assert got == want, (e, "seen, considered, valid, cast_errors", got, want)
+        assert (r.total, r.non_null, r.matches, r.distinct) == want, (e, "tgx_finalize", r.total, r.non_null, r.matches, r.distinct, want)
+
+    def slots_held(self, bound):
+        """the entries a state can hold at the most: the slots of its table (the smallest power of two >= 2 * bound), once
+        per table that counted rows into it -- one, unless states that were given rows are merged, ranks with rows are
+        reduced, or a blob taken half-way is fed on: tgx_merge, blobs and tgx_allreduce unite the entries of every
+        state (counted_state.h keeps them beside the table), and include/tgx.h promises no limit for the union"""
+        slots = 2
+        while slots < 2 * bound:
+            slots <<= 1
+        return slots * self.tables
+
+    def by_equality(self, e, d, bound, overflow_rows):
+        """is a counting task compared for full equality?  With d <= bound keys include/tgx.h promises no overflow; with
+        more the table may still hold them all, and then nothing is left to invariants either"""
+        if d <= bound:
+            assert overflow_rows == 0, (e, "overflow_rows with", d, "keys under a bound of", bound, overflow_rows)
+        return overflow_rows == 0
+
+    @staticmethod
+    def same_map(e, got, want, what="entries"):
+        """two maps with their order; the message names the first difference, not 65536 entries"""
+        if got != want:
+            missing = [k for k in want if k not in got][:4]
+            extra = [k for k in got if k not in want][:4]
+            other = [(k, got[k], want[k]) for k in want if k in got and got[k] != want[k]][:4]
+            raise AssertionError((e, what, "missing", missing, "not in the table", extra, "(key, device, exact)", other,
+                                  len(got), len(want)))
+        if list(got) != list(want):
+            at = next(k for k, (a, b) in enumerate(zip(got, want)) if a != b)
+            raise AssertionError((e, what, "order differs at", at, list(got)[at:at + 3], list(want)[at:at + 3]))
+
+    def held_entries(self, e, got, want, bound, count=lambda v: v):
+        """a table that overflowed: what it holds are keys of the table, in order, none counted too often"""
+        assert len(got) <= self.slots_held(bound), (e, "entries held", len(got), "slots", self.slots_held(bound))
+        keys = list(got)
+        assert all(a < b for a, b in zip(keys, keys[1:])), (e, "entries out of order")
+        for k, v in got.items():
+            assert k in want, (e, "a key that is not in the table", k, v)
+            assert 0 < count(v) <= count(want[k]), (e, "count of", k, v, want[k])
+
+    def check_value_counts(self, e, si, r, st):
+        _, ci, bound, mvb = e
+        want = self.reference(("value_counts", ci, mvb))
+        summary, counts = st.value_counts(si)
+        assert (r.total, r.non_null, r.distinct, r.matches) == (
+            summary["seen"], summary["non_null"], summary["distinct"], summary["counted"]), (
+            e, "tgx_finalize", r.total, r.non_null, r.distinct, r.matches, summary)
+        if self.by_equality(e, want["distinct"], bound, summary["overflow_rows"]):
+            assert summary == {k: want[k] for k in summary}, (e, summary, {k: want[k] for k in summary})
+            self.same_map(e, counts, want["counts"])
+            return
+        for k in ("seen", "non_null", "long_rows"):
+            assert summary[k] == want[k], (e, k, summary[k], want[k])
+        assert summary["counted"] + summary["overflow_rows"] + summary["long_rows"] == summary["non_null"], (e, summary)
+        assert (summary["distinct"], summary["counted"]) == (len(counts), sum(counts.values())), (e, summary, len(counts))
+        self.held_entries(e, counts, want["counts"], bound)
+
+    def check_group_counts(self, e, si, r, st):
+        _, cv, ck, bound, mvb = e
+        want = self.reference(("group_counts", cv, ck, mvb))
+        count_col = int(self.cols[cv][3].sum())
+        summary, groups = st.group_counts(si)
+        assert (r.total, r.non_null, r.distinct, r.matches) == (summary["seen"], count_col, summary["groups"], summary["counted"]), (
+            e, "tgx_finalize", r.total, r.non_null, r.distinct, r.matches, summary)
+        if self.by_equality(e, want["groups"], bound, summary["overflow_rows"]):
+            assert summary == {k: want[k] for k in summary}, (e, summary, {k: want[k] for k in summary})
+            self.same_map(e, groups, want["entries"])
+            return
+        for k in ("seen", "null_group_rows", "null_group_non_null", "long_rows", "long_non_null"):
+            assert summary[k] == want[k], (e, k, summary[k], want[k])
+        assert sum(summary[k] for k in ("counted", "null_group_rows", "overflow_rows", "long_rows")) == self.n, (e, summary)
+        assert sum(summary[k] for k in ("counted_non_null", "null_group_non_null", "overflow_non_null",
+                                        "long_non_null")) == count_col, (e, summary)
+        assert (summary["groups"], summary["counted"], summary["counted_non_null"]) == (
+            len(groups), sum(g[0] for g in groups.values()), sum(g[1] for g in groups.values())), (e, summary)
+        self.held_entries(e, groups, want["entries"], bound, count=lambda v: v[0])
+        for k, (total, non_null) in groups.items():
+            assert non_null <= min(total, want["entries"][k][1]), (e, "non_null of", k, (total, non_null), want["entries"][k])
+
+    def check_group_sums(self, e, si, r, st):
+        _, cv, ck, bound, mvb = e
+        want = self.reference(("group_sums", cv, ck, mvb))
+        values, valid = self.wide_of(cv), self.cols[cv][3]
+        count_col = int(valid.sum())
+        is_float = values.dtype == np.float64
+        summary, groups = st.group_sums(si)
+        classes = ("counted", "null_group", "overflow", "long_rows")
+        assert summary["is_float"] == want["is_float"], (e, "is_float", summary["is_float"], want["is_float"])
+        assert (r.total, r.non_null, r.distinct, r.matches, bool(r.has_value)) == (
+            summary["seen"], count_col, summary["groups"], summary["counted"][0], count_col > 0), (
+            e, "tgx_finalize", r.total, r.non_null, r.distinct, r.matches, r.has_value, summary)
+        # the identities, overflow or not: every row, every non-NULL value and (integers, wrapping) the sum is in one class
+        assert sum(summary[c][0] for c in classes) == summary["seen"] == self.n, (e, summary)
+        assert sum(summary[c][1] for c in classes) == count_col, (e, summary)
+        assert (summary["groups"], summary["counted"][0], summary["counted"][1]) == (
+            len(groups), sum(g[0] for g in groups.values()), sum(g[1] for g in groups.values())), (e, summary)
+        if is_float and self.n:
+            assert r.sum_i == 0, (e, "sum_i of a float sum", r.sum_i)
+            why = self.float_failure(want, "all", r.sum_f)
+            assert why is None, (e, "tgx_finalize sum_f", why)
+        elif self.n:
+            total = EGS.wrap(int(values[valid].view(np.uint64).sum(dtype=np.uint64)))
+            assert EGS.wrap(sum(summary[c][2] for c in classes)) == total, (e, "the classes' sums", summary, total)
+            assert summary["counted"][2] == EGS.wrap(sum(g[2] for g in groups.values())), (e, "counted sum", summary["counted"])
+            assert (r.sum_i, r.sum_f) == (total, float(total)), (e, "tgx_finalize sum", r.sum_i, r.sum_f, total)
+        equal = self.by_equality(e, want["groups"], bound, summary["overflow"][0])
+        for c in ("null_group", "long_rows") + (("overflow",) if equal else ()):
+            self.same_class(e, c, summary[c], want, c, is_float)
+        if equal:
+            assert summary["groups"] == want["groups"], (e, "groups", summary["groups"], want["groups"])
+            if is_float:
+                self.same_map(e, {k: g[:2] for k, g in groups.items()}, {k: w[:2] for k, w in want["entries"].items()})
+                for k, g in groups.items():
+                    self.same_class(e, k, g, want, k, True)
+                self.same_class(e, "counted", summary["counted"], want, "counted_class", True)
+            else:
+                self.same_map(e, groups, want["entries"])
+                assert summary["counted"] == want["counted"], (e, "counted", summary["counted"], want["counted"])
+            return
+        self.held_entries(e, groups, want["entries"], bound, count=lambda v: v[0])
+        for k, g in groups.items():
+            w = want["entries"][k]
+            assert g[1] <= min(g[0], w[1]), (e, "non_null of", k, g, w)
+            if g[:2] == w[:2]:  # every row of the group is in the entry: so is its sum
+                self.same_class(e, k, g, want, k, is_float)
+
+    def float_failure(self, want, name, got):
+        """EGS.float_failure for the entry or class `name` of a GROUP_SUMS reference"""
+        c = want["entries"][name] if name in want["entries"] else want[name]
+        return EGS.float_failure(got, want["rules"].get(name, ("bound", None)), c[1], c[2], c[3])
+
+    def same_class(self, e, label, got, want, name, is_float):
+        """(rows, non_null, sum) of an entry or a class: the counts and an integer sum for equality, a float sum within
+        float_bound of math.fsum, or by the overflow rule (exact_group_sums.float_rule)"""
+        c = want["entries"][name] if name in want["entries"] else want[name]
+        assert tuple(got[:2]) == tuple(c[:2]), (e, label, "rows, non_null", got, c)
+        if not is_float:
+            assert got[2] == c[2], (e, label, "sum", got, c)
+        else:
+            why = self.float_failure(want, name, got[2])
+            assert why is None, (e, label, "sum", why, got, c)
+
+    def check_pair_counts(self, e, si, r, st):
+        _, cx, cy, bound, mvb, _, _ = e
+        side = self.pair_numeric_side(e)
+        binning = self.pass_two.get(si) if self.phase == 2 else None
+        summary, counts = st.pair_counts(si)
+        assert (r.total, r.non_null, r.distinct, r.matches) == (
+            summary["seen"], summary["both_non_null"], summary["distinct"], summary["counted"]), (
+            e, "tgx_finalize", r.total, r.non_null, r.distinct, r.matches, summary)
+        if side is not None and binning is None:  # the range phase
+            num, other = (cx, cy) if side == 0 else (cy, cx)
+            want = self.reference(("pair_range", num, other))
+            assert summary == dict(dict.fromkeys(summary, 0), seen=want["seen"], both_non_null=want["both_non_null"]), (e, summary, want)
+            assert counts == {}, (e, "entries in the range phase", len(counts))
+            got = st.pair_range(si)
+            for k in ("seen", "both_non_null", "n", "non_finite"):
+                assert got[k] == want[k], (e, k, got[k], want[k])
+            for k in ("min", "max"):
+                self.same_extreme(e, k, got[k], want[k], num, (), zeros_key=("pair_zeros", num, other))
+            return
+        want = self.reference(("pair_counts", cx, cy, mvb, binning))
+        if self.by_equality(e, want["distinct"], bound, summary["overflow_rows"]):
+            assert summary == {k: want[k] for k in summary}, (e, summary, {k: want[k] for k in summary})
+            self.same_map(e, counts, want["counts"], "pairs")
+            return
+        for k in ("seen", "both_non_null", "long_rows", "non_finite", "out_of_range"):
+            assert summary[k] == want[k], (e, k, summary[k], want[k])
+        assert sum(summary[k] for k in ("counted", "overflow_rows", "long_rows", "non_finite",
+                                        "out_of_range")) == summary["both_non_null"], (e, summary)
+        assert (summary["distinct"], summary["counted"]) == (len(counts), sum(counts.values())), (e, summary, len(counts))
+        self.held_entries(e, counts, want["counts"], bound)
+
     # ---- the oracle side + comparison ----
     def key_bits(self, ci):
         """(values as the 64-bit patterns DISTINCT compares, validity) of a numeric column"""
@@ -800,9 +1239,11 @@ class Case:
             if what == "tuple":
                 self.check_tuple(r, e)
                 continue
-            if what in ("histogram", "joint", "temporal", "time_gap"):
+            if what in ("histogram", "joint", "temporal", "time_gap") + self.RULES_AND_COUNTS:
                 {"histogram": self.check_histogram, "joint": self.check_joint, "temporal": self.check_temporal,
-                 "time_gap": self.check_time_gap}[what](e, si, r, st)
+                 "time_gap": self.check_time_gap, "rule": self.check_rule, "value_counts": self.check_value_counts,
+                 "pair_counts": self.check_pair_counts, "group_counts": self.check_group_counts,
+                 "group_sums": self.check_group_sums}[what](e, si, r, st)
                 continue
             kind, vals, vb, mask, extra = self.cols[e[1]]
             wide = (vals if kind in ("i", "f", "s") else W.widen_int(vals, "int32") if kind == "i32"

@@ -151,3 +151,84 @@ def test_nan_and_the_order_of_the_totals():
     got = ex.cross_table_sum({None: 1.0, 2: 1.0, 1: 1e16}, {1: 1e16, 2: 1.0, None: 1.0}, group_by_columns=["g"])
     assert got["total_left_sum"] == (1e16 + 1.0) + 1.0 + 0.0 and got["total_right_sum"] == (1e16 + 1.0) + 0.0 + 1.0
     assert got["total_groups"] == 4 and got["violating_groups"] == 2
+
+
+# ---- the numpy twin against the plain walk; the overflow rule --------------------------------------------------------------
+def test_the_numpy_twin_agrees_with_the_walk():
+    import numpy as np
+
+    rng = np.random.default_rng(20261)
+    words = [b"", b"a", b"ab", b"b", "ÿ".encode(), b"long word!", b"x" * 40] + [b"w%d" % k for k in range(9)]
+    pool = np.array([np.nan, np.inf, -np.inf, -0.0, 1e308, -1e308, 5e-324])
+    met = set()  # (the decisions of the overflow rule that the tables reach)
+    for n, null_rate, max_bytes in ((0, 0.0, 256), (1, 0.0, 256), (400, 0.2, 256), (400, 0.2, 4), (400, 1.0, 4),
+                                    (3000, 0.05, 1), (3000, 0.3, 9)):
+        for is_float in (False, True):
+            if is_float:
+                vals = np.round(rng.standard_normal(n) * 4, 1)
+                hit = rng.random(n) < 0.1
+                vals[hit] = pool[rng.integers(0, len(pool), size=int(hit.sum()))]
+            else:
+                vals = rng.integers(-(2**63), 2**63 - 1, size=n, dtype=np.int64)  # (the sums wrap)
+            valid = rng.random(n) >= null_rate
+            listed = [(float(v) if is_float else int(v)) if m else None for v, m in zip(vals, valid)]
+            key_valid = rng.random(n) >= null_rate
+            int_keys = rng.integers(-3, 40, size=n)
+            codes = rng.integers(0, len(words), size=n)
+            for keys, table in ((int_keys, None), (codes, words)):
+                groups = [(int(k) if table is None else table[k]) if m else None for k, m in zip(keys, key_valid)]
+                want = ex.walk(listed, groups, max_value_bytes=max_bytes, is_float=is_float)
+                got = ex.walk_np(vals, valid, keys, key_valid, words=table, max_value_bytes=max_bytes)
+                assert list(got["entries"]) == list(want["entries"]), (n, is_float, max_bytes)
+                assert repr(sorted(got.items())) == repr(sorted(want.items())), (n, is_float, max_bytes)  # (repr: a NaN sum is a NaN sum)
+                if n == 3000 and max_bytes == 9 and table is not None:
+                    assert want["long_rows"][0] > 0 and want["null_group"][0] > 0 and want["groups"] > 10
+                # rules=True: the two classes it adds and every overflow-rule decision, from the plain lists
+                full = ex.walk_np(vals, valid, keys, key_valid, words=table, max_value_bytes=max_bytes, rules=True)
+                assert repr(sorted((k, v) for k, v in full.items() if k in want)) == repr(sorted(want.items()))
+                if not is_float:
+                    assert "rules" not in full and "all" not in full
+                    continue
+                by_key, nulls, longs = ex.group_by(listed, groups), [], []
+                for key, (_rows, values_of) in by_key.items():
+                    if key is None:
+                        nulls += values_of
+                    elif isinstance(key, bytes) and len(key) > max_bytes:
+                        longs += values_of
+                in_entries = [v for key in want["entries"] for v in by_key[key][1]]
+                lists = dict({key: by_key[key][1] for key in want["entries"]}, null_group=nulls, long_rows=longs,
+                             counted_class=in_entries, all=[v for v in listed if v is not None])
+                assert repr(full["all"]) == repr(ex.float_class(n, lists["all"])), (n, max_bytes)
+                assert repr(full["counted_class"]) == repr(ex.float_class(want["counted"][0], in_entries)), (n, max_bytes)
+                expected = {}
+                for name, values_of in lists.items():
+                    if not math.isfinite(ex.magnitudes_of(values_of)):
+                        expected[name] = ex.float_rule(values_of)
+                assert repr(sorted(full["rules"].items(), key=repr)) == repr(sorted(expected.items(), key=repr)), (n, max_bytes)
+                if n == 3000:  # the rule decides entries and classes here, and every kind of decision is met
+                    assert {"all", "counted_class"} <= set(expected) and len(expected) > 4
+                met |= {how for how, _ in expected.values()}
+    assert met == {"is", "unpinned"}
+
+
+def test_the_overflow_rule():
+    nan, inf, big = math.nan, math.inf, 1e308
+    assert ex.float_rule([1.0, -2.5]) == ("bound", None) and ex.float_rule([]) == ("bound", None)
+    assert ex.float_rule([big]) == ("bound", None)
+    how, value = ex.float_rule([1.0, nan, inf])
+    assert how == "is" and math.isnan(value)
+    assert ex.float_rule([inf, 1.0, inf]) == ("is", inf) and ex.float_rule([-inf, big]) == ("is", -inf)
+    how, value = ex.float_rule([inf, -inf])
+    assert how == "is" and math.isnan(value)
+    assert ex.float_rule([big, big]) == ("unpinned", None)  # 2e308: inf in every order, yet
+    assert ex.float_rule([big, big, -big]) == ("unpinned", None)  # 1e308 in one order and inf in another
+    assert ex.float_rule([inf, big, big]) == ("unpinned", None)  # (-inf from the finite ones would meet +inf as NaN)
+    # the failure texts: a sum within the bound, one off by twice the bound, the rules
+    c = ex.float_class(3, [0.1, 0.2, 0.3])
+    bound = ex.float_bound(c[1], c[2], c[3])
+    assert ex.float_failure(0.1 + 0.2 + 0.3, ("bound", None), *c[1:]) is None
+    assert ex.float_failure(c[2] + 2 * bound, ("bound", None), *c[1:]) is not None
+    assert ex.float_failure(nan, ("bound", None), *c[1:]) is not None
+    assert ex.float_failure(inf, ("is", inf), 1, inf, inf) is None and ex.float_failure(nan, ("is", inf), 1, inf, inf)
+    assert ex.float_failure(nan, ("is", nan), 1, nan, nan) is None and ex.float_failure(0.0, ("is", nan), 1, nan, nan)
+    assert ex.float_failure(-inf, ("unpinned", None), 2, nan, inf) is None

@@ -7,6 +7,10 @@ draws a plan.
 - the TIME_GAP dimension, drawn last and from a stream of its own, leaves those digests and that census as they are (it
   is not one of NEW_KINDS), and the three committed sets together meet a census of its own: every cell for the grouped
   and for the ungrouped route;
+- the VALUE_RULE / VALUE_COUNTS / PAIR_COUNTS / GROUP_COUNTS / GROUP_SUMS dimension, drawn after it from a stream of its
+  own, leaves all of that as it is too; the four committed sets together meet a census of its own, keep the share of
+  tasks that references alone cannot pin (a table that may overflow, a float sum that may) to a quarter, and the
+  dimension is drawn only where its rules allow;
 - check_one passes on the references' own answers and fails on each of a list of single perturbations."""
 import hashlib
 import json
@@ -42,7 +46,7 @@ def case_digest(case):
             d += [_h(extra[0]), bool(extra[1]), extra[2], _h(np.frombuffer("\0".join(extra[3]).encode() or b"\0", np.uint8)),
                   _h(extra[4])]
         cols.append(d)
-    old = [k for k, e in enumerate(case.expect) if e[0] not in NEW_KINDS + ("time_gap",)]
+    old = [k for k, e in enumerate(case.expect) if e[0] not in NEW_KINDS + ("time_gap",) + case.RULES_AND_COUNTS]
     specs = []
     for k in old:
         s = case.specs[k]
@@ -137,12 +141,16 @@ _CASES = {}
 
 
 def committed_cases(third=False):
-    """the cases of the first two committed sets (built once per session), or of the third"""
+    """the cases of the first two committed sets (built once per session), of the third (True) or of the fourth ("fourth")"""
     from fuzz_plans import Case
     from test_gpu_fuzz import SECOND_MAX_ROWS, SECOND_SEEDS, THIRD_SEEDS
 
     if third not in _CASES:
-        if third:
+        if third == "fourth":
+            from test_gpu_fuzz import FOURTH_SEEDS
+
+            _CASES[third] = [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in FOURTH_SEEDS]
+        elif third:
             _CASES[third] = [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in THIRD_SEEDS]
         else:
             _CASES[third] = [Case(seed) for seed in FIRST_SEEDS] + [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in SECOND_SEEDS]
@@ -305,10 +313,217 @@ def test_the_time_gap_dimension_is_drawn_where_it_can_be():
     assert 0.5 <= drawn / eligible <= 0.9, (drawn, eligible)
 
 
+# ---- the census of VALUE_RULE and the four counting kinds: the four committed sets together ---------------------------
+RC_KINDS = ("rule", "value_counts", "pair_counts", "group_counts", "group_sums")
+RC_COUNTING = RC_KINDS[1:]
+RC_MODES = ("one", "cuts", "stream")
+RC_SHARED = {"a DISTINCT or tuple check": ("distinct", "tuple"), "NUMERIC_STATS": ("stats",), "another of the five kinds": RC_KINDS}
+RC_KEYS = ("i", "i32", "a narrow presentation", "s/plain", "s/LargeUtf8", "s/view", "s/dict")
+RULE_MODES = {1: "GE_ZERO", 2: "GT_ZERO", 3: "BETWEEN", 4: "INTEGER"}
+
+
+def rc_key_columns(case, e):
+    """the columns whose values are a counting task's keys: the column, the group column, or both sides of a pair"""
+    return {"value_counts": (e[1],), "pair_counts": (e[1], e[2])}.get(e[0], (e[2],))
+
+
+def rc_keys_and_bound(case, e):
+    """(the exact number of keys d of the whole table, the bound) of a counting task"""
+    if e[0] == "value_counts":
+        return case.reference(("value_counts", e[1], e[3]))["distinct"], e[2]
+    if e[0] == "pair_counts":
+        return case.reference(("pair_counts", e[1], e[2], e[4], case.pair_binning(e)))["distinct"], e[3]
+    return case.reference(("value_counts", e[2], e[4]))["distinct"], e[3]
+
+
+def rc_tasks(case):
+    """per counting kind [may the task be left to invariants: d > bound], and for the float GROUP_SUMS tasks [is any
+    group, class or total decided by the overflow rule]"""
+    tasks = {k: [] for k in RC_COUNTING + ("float group_sums",)}
+    for e in case.expect:
+        if e[0] in RC_COUNTING:
+            d, bound = rc_keys_and_bound(case, e)
+            tasks[e[0]].append(d > bound)
+        if e[0] == "group_sums" and case.cols[e[1]][0] in ("f", "f32"):
+            tasks["float group_sums"].append(bool(case.reference(("group_sums", e[1], e[2], e[4]))["rules"]))
+    return tasks
+
+
+def rc_cells(case):
+    """the cells of the census this case fills"""
+    cells = set()
+    rule_counts = {}
+    for e in case.expect:
+        kind = e[0]
+        if kind not in RC_KINDS:
+            continue
+        cols = case.columns_of_expect(e)
+        mine = {"after=%s" % case.after, "buffers=%s" % case.device, "batching=%s" % case.mode}
+        if case.seq != "plain":
+            mine.add("seq=%s" % case.seq)
+        if case.retain and case.device != "device":
+            mine.add("retained")
+        if case.n == 0 or any(not case.cols[ci][3].any() for ci in cols):
+            mine.add("without rows")
+        for name, kinds in RC_SHARED.items():
+            if any(o is not e and o[0] in kinds and set(cols) & set(case.columns_of_expect(o)) for o in case.expect):
+                mine.add("a column shared with %s" % name)
+        if kind == "rule":
+            rule = e[2]
+            mine.add("mode=%s" % RULE_MODES[rule["mode"]])
+            is_float = case.cols[e[1]][0] in ("f", "f32")
+            if rule["flags"] & 1:
+                mine.add("BOUNDS_AS_DOUBLE")
+            if rule["mode"] == 3:
+                import exact_value_rule as EV
+
+                as_double = is_float or rule["flags"] & 1
+                lo, hi = ((EV.key(EV.bits_of(rule["lo_f"])), EV.key(EV.bits_of(rule["hi_f"]))) if as_double
+                          else (rule["lo_i"], rule["hi_i"]))
+                if lo > hi:
+                    mine.add("lo > hi")
+            if is_float:
+                d = case.doubles_of(e[1])[case.cols[e[1]][3]]
+                if np.isnan(d).any() and np.isinf(d).any() and (d == 0.0).any():
+                    mine.add("a float column with specials")
+            rule_counts[e[1]] = rule_counts.get(e[1], 0) + 1
+            if rule_counts[e[1]] > 8:  # (the rules of one column go to the kernel eight at a time)
+                mine.add("more than eight rules on a column")
+        else:
+            d, bound = rc_keys_and_bound(case, e)
+            mvb = e[3] if kind == "value_counts" else e[4]
+            for ck in rc_key_columns(case, e):
+                k, _, _, mask, extra = case.cols[ck]
+                if k == "s":
+                    mine.add("key s/%s" % (extra[2] if extra[2] != "plain" else "LargeUtf8" if extra[1] else "plain"))
+                    if case.reference(("value_counts", ck, mvb))["long_rows"]:
+                        mine.add("long rows")
+                elif k in ("i", "i32"):
+                    mine.add("key %s" % ("a narrow presentation" if case.present[ck] is not None else k))
+                    if (case.wide_of(ck)[mask] == -1).any():
+                        mine.add("the -1 key")
+                if case.n > 0 and not mask.any():
+                    mine.add("every key NULL")
+            if bound == d:
+                mine.add("bound=d")
+            if bound == d + 1:
+                mine.add("bound=d+1")
+            if d > bound:
+                mine.add("a bound that overflows")
+            if case.after == "merge" and len(case.cuts) == 2:  # (one batch: every state but the first stays empty)
+                mine.add("a merged state that saw no batch")
+        if kind == "group_counts":
+            if sum(1 for o in case.expect if o[0] == kind and o[2:] == e[2:]) > 1:
+                mine.add("more than one member on a walk")
+            if e[1] == e[2]:
+                mine.add("the value column is the key column")
+        elif kind == "group_sums":
+            floats = case.cols[e[1]][0] in ("f", "f32")
+            mine.add("float values" if floats else "integer values")
+            if floats and case.reference(("group_sums", e[1], e[2], e[4]))["rules"]:
+                mine.add("float sums by the overflow rule")
+        elif kind == "pair_counts":
+            side = case.pair_numeric_side(e)
+            mine.add("two string sides" if side is None else "a numeric %s" % "xy"[side])
+            if side is not None:
+                b = case.pair_binning(e)
+                mine.add("range phase after=%s" % case.after)
+                if b is not None and case.valid_binning(b):
+                    mine.add("count phase after=%s" % case.after)
+                    if e[6]:
+                        mine.add("a moved origin")
+        cells |= {"%s %s" % (kind, cell) for cell in mine}
+    return cells
+
+
+RC_REQUIRED = (["%s %s" % (k, c) for k in RC_KINDS for c in (
+    ["after=%s" % a for a in AFTERS] + ["seq=%s" % q for q in SEQS] + ["buffers=%s" % d for d in DEVICES] + ["retained"]
+    + ["batching=%s" % m for m in RC_MODES] + ["without rows"] + ["a column shared with %s" % name for name in RC_SHARED])]
+    + ["%s %s" % (k, c) for k in RC_COUNTING for c in (
+        ["key %s" % key for key in RC_KEYS] + ["bound=d", "bound=d+1", "a bound that overflows", "long rows", "the -1 key",
+                                               "every key NULL", "a merged state that saw no batch"])]
+    + ["rule mode=%s" % m for m in RULE_MODES.values()]
+    + ["rule %s" % c for c in ("BOUNDS_AS_DOUBLE", "lo > hi", "a float column with specials", "more than eight rules on a column")]
+    + ["group_counts more than one member on a walk", "group_counts the value column is the key column",
+       "group_sums integer values", "group_sums float values", "group_sums float sums by the overflow rule",
+       "pair_counts two string sides", "pair_counts a numeric x", "pair_counts a numeric y", "pair_counts a moved origin"]
+    + ["pair_counts %s phase after=%s" % (p, a) for p in ("range", "count") for a in AFTERS])
+
+
+def test_rules_and_counts_census_of_the_four_committed_sets():
+    from test_gpu_fuzz import FOURTH_SEEDS, SECOND_SEEDS, THIRD_SEEDS
+
+    assert len(FOURTH_SEEDS) <= 48 and len(set(FOURTH_SEEDS)) == len(FOURTH_SEEDS)
+    assert not set(FOURTH_SEEDS) & (set(FIRST_SEEDS) | set(SECOND_SEEDS) | set(THIRD_SEEDS))
+    counts, tasks = {}, {}
+    for which in (False, True, "fourth"):
+        for case in committed_cases(which):
+            cells = rc_cells(case)
+            if which == "fourth":  # every seed of the fourth set carries the dimension
+                assert cells, case.seed
+            for cell in cells:
+                counts[cell] = counts.get(cell, 0) + 1
+            for name, flags in rc_tasks(case).items():
+                tasks.setdefault(name, []).extend(flags)
+    for cell in sorted(counts):
+        print("%4d  %s" % (counts[cell], cell))
+    missing = [cell for cell in RC_REQUIRED if not counts.get(cell)]
+    assert not missing, missing
+    # a condition, not a measurement: the references alone pin three tasks in four of every counting kind (d <= bound:
+    # full equality is required), and the sum bound three float GROUP_SUMS tasks in four
+    for name, flags in sorted(tasks.items()):
+        print("%s: %d tasks, %d %s" % (name, len(flags), sum(flags), "with a group, class or total by the overflow rule"
+                                       if name == "float group_sums" else "with more keys than their bound"))
+        assert flags and 4 * sum(flags) <= len(flags), (name, sum(flags), len(flags))
+
+
+def test_the_rules_and_counts_dimension_is_drawn_where_it_can_be():
+    """eligibility is a condition: only cases of at most NEW_KINDS_MAX_ROWS rows, no UInt64 / Boolean presentation in a key
+    or rule role, the types each role takes -- and between a third and two thirds of the eligible cases"""
+    eligible = drawn = 0
+    for which in (False, True, "fourth"):
+        for case in committed_cases(which):
+            mine = [e for e in case.expect if e[0] in RC_KINDS]
+            kinds = [c[0] for c in case.cols]
+            ok = [not case.unsupported_as_key(ci) for ci in range(len(kinds))]
+            numeric = [ci for ci, k in enumerate(kinds) if k in ("i", "i32", "f", "f32") and ok[ci]]
+            keys = [ci for ci, k in enumerate(kinds) if k == "s" or (k in ("i", "i32") and ok[ci])]
+            can = case.n <= case.NEW_KINDS_MAX_ROWS and bool(numeric or keys)
+            assert can or not mine, case.seed
+            if any(e[0] in ("spearman", "time_gap") for e in case.expect):  # (their restriction stands)
+                assert case.after in ("finalize", "ranks") and (case.after == "finalize" or not time_gap_tasks(case)), case.seed
+            for e in mine:
+                if e[0] == "rule":
+                    assert e[1] in numeric, (case.seed, e)
+                elif e[0] == "value_counts":
+                    assert e[1] in keys, (case.seed, e)
+                elif e[0] == "group_counts":
+                    assert e[2] in keys and 0 <= e[1] < len(kinds), (case.seed, e)
+                elif e[0] == "group_sums":
+                    assert e[2] in keys and e[1] in numeric, (case.seed, e)
+                else:
+                    sides = [kinds[e[1]] == "s", kinds[e[2]] == "s"]
+                    assert any(sides) and all(s or c in numeric for s, c in zip(sides, e[1:3])), (case.seed, e)
+                if e[0] in RC_COUNTING:
+                    bound = e[2] if e[0] == "value_counts" else e[3]
+                    assert 1 <= bound <= case.BOUND_LIMIT, (case.seed, e)
+            rules = {}
+            for e in mine:
+                if e[0] == "rule":
+                    rules[e[1]] = rules.get(e[1], 0) + 1
+            assert all(1 <= c <= 3 or c == 9 for c in rules.values()), (case.seed, rules)
+            if which is False:
+                eligible += can
+                drawn += bool(mine)
+    print("the dimension is drawn for %d of the %d eligible cases of the first two sets" % (drawn, eligible))
+    assert 1 / 3 <= drawn / eligible <= 2 / 3, (drawn, eligible)
+
+
 # ---- the comparisons fail when they should ----------------------------------------------------------------------------
 class FakeResult:
-    def __init__(self, total=0, non_null=0, matches=0):
-        self.total, self.non_null, self.matches = total, non_null, matches
+    def __init__(self, total=0, non_null=0, matches=0, distinct=0, sum_i=0, sum_f=0.0, has_value=0):
+        self.total, self.non_null, self.matches, self.distinct = total, non_null, matches, distinct
+        self.sum_i, self.sum_f, self.has_value = sum_i, sum_f, has_value
 
 
 class FakeState:
@@ -317,6 +532,26 @@ class FakeState:
     def __init__(self):
         self.hist_range, self.hist_counts, self.j_range, self.j_counts, self.temporal = {}, {}, {}, {}, {}
         self.time_gap = {}
+        # VALUE_RULE: the four counters; the counting kinds: (summary, entries), as term_amd.State's readers give them
+        self.rule, self.vc, self.pc, self.pr, self.gc, self.gs = {}, {}, {}, {}, {}, {}
+
+    def value_rule_counts(self, si):
+        return tuple(self.rule[si])
+
+    def value_counts(self, si):
+        return dict(self.vc[si][0]), dict(self.vc[si][1])
+
+    def pair_counts(self, si):
+        return dict(self.pc[si][0]), dict(self.pc[si][1])
+
+    def pair_range(self, si):
+        return dict(self.pr[si])
+
+    def group_counts(self, si):
+        return dict(self.gc[si][0]), dict(self.gc[si][1])
+
+    def group_sums(self, si):
+        return dict(self.gs[si][0]), dict(self.gs[si][1])
 
     def histogram_range(self, si):
         return dict(self.hist_range[si])
@@ -342,24 +577,40 @@ X = [0.0, 0.5, 1.0, 2.5, 4.0, float("nan"), 3.0, None, 1.5, 4.0, 0.25, 3.75]
 Y = [3, 1, 4, 1, 5, 9, 2, 6, None, 5, 8, 0]
 # (as a group column: 5, 0 and 4 hold several rows each, and three rows with a timestamp have no group)
 Z = [5, 0, 4, None, 5, 0, None, 4, 3, None, 0, 5]
+# (a string column: NULL rows, the empty string, a word longer than SMALL_MAX_BYTES; "a" holds X's NaN, "bb" only finite values)
+S = ["a", "bb", "a", None, "long word", "a", "bb", "", "a", None, "long word", "bb"]
+S_WORDS = ["a", "bb", "", "long word"]
+SMALL_MAX_BYTES, SMALL_BOUND, PAIR_BINS = 4, 10000, 2
 HIST, JOINT, TEMPORAL, TIME_GAP = 0, 1, 2, 3  # spec indices
+RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS_F, GROUP_SUMS_I = 4, 5, 6, 7, 8, 9
+N_SPECS = 10
 TIME_GAP_MAX = 2  # Y grouped by Z has the gaps 3, 2 | 7, 1 | 2 | 1, 3 (the NULL group): three above, four not
 
 
 def small_case(phase, edges="shifted", moved=True):
-    """a three-column table with one spec of each new kind, built without the generator"""
+    """a four-column table with one spec of each new kind (GROUP_SUMS twice: float and integer values), built without
+    the generator"""
+    import exact_value_rule as EV
     import term_amd as T
     from fuzz_plans import Case
 
     c = Case.__new__(Case)
-    c.seed, c.n, c.specs, c.present, c.phase, c.pass_two, c._cache = -1, len(X), [None] * 4, [None] * 3, 1, {}, {}
+    c.seed, c.n, c.specs, c.present, c.phase, c.pass_two, c._cache = -1, len(X), [None] * N_SPECS, [None] * 4, 1, {}, {}
+    c.tables = 1
     c.cols = []
     for kind, vals, dtype in (("f", X, np.float64), ("i", Y, np.int64), ("i", Z, np.int64)):
         mask = np.array([v is not None for v in vals])
         c.cols.append((kind, np.array([0 if v is None else v for v in vals], dtype), None, mask, None))
+    s_mask = np.array([v is not None for v in S])
+    picks = np.array([S_WORDS.index(v) if v is not None else 0 for v in S])
+    c.cols.append(("s", None, None, s_mask, (None, False, "plain", S_WORDS, picks)))
     c.expect = [("histogram", 0, 4, edges, 7), ("joint", 0, 1, 2, moved),
                 ("temporal", 1, 2, "order", dict(mode=T.TEMPORAL_ORDER, flags=0, delta=1)),
-                ("time_gap", 1, 2, TIME_GAP_MAX)]
+                ("time_gap", 1, 2, TIME_GAP_MAX),
+                ("rule", 0, EV.rule(EV.INTEGER)), ("value_counts", 3, SMALL_BOUND, SMALL_MAX_BYTES),
+                ("pair_counts", 3, 0, SMALL_BOUND, SMALL_MAX_BYTES, PAIR_BINS, moved),
+                ("group_counts", 0, 3, SMALL_BOUND, SMALL_MAX_BYTES), ("group_sums", 0, 3, SMALL_BOUND, SMALL_MAX_BYTES),
+                ("group_sums", 1, 3, SMALL_BOUND, SMALL_MAX_BYTES)]
     if phase == 2:
         c.enter_pass_two()
     return c
@@ -373,7 +624,8 @@ def reference_answer(case):
 
     import exact_time_gap as EG
 
-    res, st = [FakeResult() for _ in range(4)], FakeState()
+    res, st = [FakeResult() for _ in range(N_SPECS)], FakeState()
+    rules_and_counts_answer(case, res, st)
     r = EH.value_range(X)
     res[HIST] = FakeResult(r["total"], r["n"] + r["non_finite"])
     st.hist_range[HIST] = dict(total=r["total"], nulls=r["nulls"], non_finite=r["non_finite"], n=r["n"], min=r["min"],
@@ -393,6 +645,80 @@ def reference_answer(case):
     assert want == (12, 11, 7, 3, 7)  # (worked by hand above: the perturbations below have room on both sides)
     set_time_gap(res, st, want)
     return res, st
+
+
+def s_cells():
+    return [None if v is None else v.encode() for v in S]
+
+
+def set_counted(res, st, si, store, summary, entries):
+    """a device that holds `summary` and `entries` for a VALUE_COUNTS / PAIR_COUNTS / GROUP_COUNTS task, consistently
+    through its getters and tgx_finalize"""
+    getattr(st, store)[si] = (summary, entries)
+    if store == "vc":
+        res[si] = FakeResult(summary["seen"], summary["non_null"], summary["counted"], summary["distinct"])
+    elif store == "pc":
+        res[si] = FakeResult(summary["seen"], summary["both_non_null"], summary["counted"], summary["distinct"])
+    else:
+        res[si] = FakeResult(summary["seen"], sum(v is not None for v in X), summary["counted"], summary["groups"])
+
+
+def set_group_sums(res, st, si, summary, entries, values):
+    """the same for a GROUP_SUMS task over `values`; tgx_finalize carries the sum over all four classes"""
+    import exact_group_sums as EGS
+
+    st.gs[si] = (summary, entries)
+    non_null = [v for v in values if v is not None]
+    total = sum(summary[c][2] for c in ("counted", "null_group", "overflow", "long_rows"))
+    res[si] = FakeResult(summary["seen"], len(non_null), summary["counted"][0], summary["groups"], has_value=int(bool(non_null)))
+    if values is X:  # (float values)
+        res[si].sum_f = total
+    else:
+        res[si].sum_i, res[si].sum_f = EGS.wrap(total), float(EGS.wrap(total))
+
+
+def rules_and_counts_answer(case, res, st):
+    """VALUE_RULE and the four counting kinds, from the plain walks (the tester compares with their numpy twins)"""
+    import exact_group_counts as EGC
+    import exact_group_sums as EGS
+    import exact_pair_counts as EP
+    import exact_value_counts as EVC
+    import exact_value_rule as EV
+
+    bits = [0 if v is None else EV.bits_of(v) for v in X]
+    want = EV.counts(case.expect[RULE][2], bits, [v is not None for v in X], is_float=True)
+    assert want == (12, 11, 5, 1)  # (0, 1, 4, 3 and 4 are whole; the NaN is a cast error)
+    set_rule(res, st, want)
+    w = EVC.walk(s_cells(), SMALL_MAX_BYTES)
+    assert (w["distinct"], w["long_rows"], w["non_null"]) == (3, 2, 10)
+    set_counted(res, st, VALUE_COUNTS, "vc", {k: v for k, v in w.items() if k != "counts"}, w["counts"])
+    # PAIR_COUNTS (S, X): the range of X over the rows that have a word, then the counts under pass two's binning
+    r = EP.side_range(X, S)
+    st.pr[PAIR_COUNTS] = dict(r, min=float("nan") if r["min"] is None else r["min"], max=float("nan") if r["max"] is None else r["max"])
+    blank = dict(seen=len(X), both_non_null=r["both_non_null"], distinct=0, counted=0, overflow_rows=0, long_rows=0,
+                 non_finite=0, out_of_range=0)
+    set_counted(res, st, PAIR_COUNTS, "pc", blank, {})
+    if case.phase == 2:
+        w = EP.walk(S, X, None, case.pass_two[PAIR_COUNTS], SMALL_MAX_BYTES)
+        assert min(w["counted"], w["long_rows"], w["non_finite"]) > 0 and w["distinct"] >= 2
+        set_counted(res, st, PAIR_COUNTS, "pc", {k: v for k, v in w.items() if k != "counts"}, w["counts"])
+    w = EGC.walk(X, s_cells(), SMALL_MAX_BYTES)
+    assert w["groups"] == 3 and min(w["null_group_rows"], w["long_rows"]) > 0
+    set_counted(res, st, GROUP_COUNTS, "gc", {k: v for k, v in w.items() if k != "entries"}, w["entries"])
+    for si, values, is_float in ((GROUP_SUMS_F, X, True), (GROUP_SUMS_I, Y, False)):
+        w = EGS.walk(values, s_cells(), SMALL_MAX_BYTES, is_float)
+        entries = {k: c[:3] for k, c in w["entries"].items()}
+        counted = w["counted"][:2] + (sum(c[2] for c in entries.values()),)  # (the entries' sums in key order)
+        summary = dict(seen=w["seen"], groups=w["groups"], is_float=w["is_float"], counted=counted,
+                       null_group=w["null_group"][:3], overflow=w["overflow"][:3], long_rows=w["long_rows"][:3])
+        set_group_sums(res, st, si, summary, entries, values)
+
+
+def set_rule(res, st, counts):
+    """a device that says `counts`, consistently through tgx_value_rule_get and tgx_finalize"""
+    seen, considered, valid, errors = counts
+    st.rule[RULE] = tuple(counts)
+    res[RULE] = FakeResult(seen, considered, valid, errors)
 
 
 def time_gap_columns():
@@ -552,6 +878,213 @@ def _time_gap_finalize_alone(res, st):
     res[TIME_GAP].matches += 1  # (tgx_finalize disagreeing with tgx_time_gap_get)
 
 
+# ---- VALUE_RULE and the counting kinds: one perturbation at a time ----------------------------------------------------------
+def _rule(change):
+    def perturb(res, st):
+        before = st.rule[RULE]
+        after = tuple(change(*before))
+        assert after != before
+        set_rule(res, st, after)
+    perturb.__qualname__ = "rule: " + change.__name__
+    return perturb
+
+
+def valid_up(seen, considered, valid, errors):
+    return seen, considered, valid + 1, errors
+
+
+def a_cast_error_counted_as_valid(seen, considered, valid, errors):
+    return seen, considered, valid + 1, errors - 1
+
+
+def a_null_row_considered(seen, considered, valid, errors):
+    return seen, considered + 1, valid, errors
+
+
+def _rule_finalize_alone(res, st):
+    res[RULE].matches += 1  # (tgx_finalize disagreeing with tgx_value_rule_get)
+
+
+class Counted:
+    """one counting task of the small case, read and written through the names its kind gives the same things: the
+    summary's fields for the rows in entries, the rows left out as NULL, the overflow and the long rows; an entry's
+    count is the entry itself or its first field"""
+
+    def __init__(self, name, si, store, phase, counted, nulls, nulls_down):
+        self.name, self.si, self.store, self.phase = name, si, store, phase
+        self.counted, self.nulls, self.nulls_down = counted, nulls, nulls_down
+
+    def read(self, st):
+        summary, entries = getattr(st, self.store)[self.si]
+        return dict(summary), dict(entries)
+
+    def write(self, res, st, summary, entries, order=None):
+        n_name = "distinct" if "distinct" in summary else "groups"
+        summary[n_name] = len(entries)
+        if order is not None:
+            entries = {k: entries[k] for k in order}
+        if self.store == "gs":
+            values = X if self.si == GROUP_SUMS_F else Y
+            set_group_sums(res, st, self.si, summary, entries, values)
+        else:
+            set_counted(res, st, self.si, self.store, summary, entries)
+
+    @staticmethod
+    def bump(entries, key, by):
+        v = entries.get(key, 0 if not entries or not isinstance(next(iter(entries.values())), tuple)
+                        else (0,) * len(next(iter(entries.values()))))
+        entries[key] = v + by if not isinstance(v, tuple) else (v[0] + by,) + tuple(v[1:])
+
+    def field(self, summary, name, by):
+        """a row count of the summary up or down (GROUP_SUMS: the rows of the class)"""
+        if self.store == "gs":
+            cls = {"counted": "counted", "overflow_rows": "overflow", "long_rows": "long_rows",
+                   "null_group_rows": "null_group"}[name]
+            summary[cls] = (summary[cls][0] + by,) + tuple(summary[cls][1:])
+        else:
+            summary[name] += by
+
+    def perturbations(self):
+        def two_keys(entries):
+            keys = list(entries)
+            assert len(keys) >= 2
+            return keys[0], keys[1]
+
+        def a_row_from_one_entry_to_another(res, st):
+            summary, entries = self.read(st)
+            a = max(entries, key=lambda k: entries[k][0] if isinstance(entries[k], tuple) else entries[k])
+            b = next(k for k in entries if k != a)
+            self.bump(entries, a, -1)
+            self.bump(entries, b, +1)
+            assert all((v[0] if isinstance(v, tuple) else v) > 0 for v in entries.values())
+            self.write(res, st, summary, entries)
+
+        def an_entry_up_and_the_summary_follows(res, st):
+            summary, entries = self.read(st)
+            self.bump(entries, two_keys(entries)[0], +1)
+            self.field(summary, self.counted, +1)
+            self.write(res, st, summary, entries)
+
+        def a_null_key_row_counted_in_an_entry(res, st):
+            summary, entries = self.read(st)
+            self.bump(entries, two_keys(entries)[0], +1)
+            self.field(summary, self.counted, +1)
+            self.field(summary, self.nulls, -1 if self.nulls_down else +1)
+            self.write(res, st, summary, entries)
+
+        def overflow_rows_under_the_bound(res, st):
+            summary, entries = self.read(st)
+            a = max(entries, key=lambda k: entries[k][0] if isinstance(entries[k], tuple) else entries[k])
+            self.bump(entries, a, -1)
+            self.field(summary, self.counted, -1)
+            self.field(summary, "overflow_rows", +1)
+            self.write(res, st, summary, entries)
+
+        def a_long_row_counted(res, st):
+            summary, entries = self.read(st)
+            long_key = b"long word" if self.store != "pc" else (b"long word", next(iter(entries))[1])
+            self.bump(entries, long_key, +1)
+            self.field(summary, self.counted, +1)
+            self.field(summary, "long_rows", -1)
+            self.write(res, st, summary, entries, order=sorted(entries))
+
+        def two_entries_swapped(res, st):
+            summary, entries = self.read(st)
+            a, b = two_keys(entries)
+            self.write(res, st, summary, entries, order=[b, a] + list(entries)[2:])
+
+        def finalize_alone(res, st):
+            res[self.si].matches += 1  # (tgx_finalize disagreeing with the kind's getter)
+
+        out = []
+        for f in (a_row_from_one_entry_to_another, an_entry_up_and_the_summary_follows, a_null_key_row_counted_in_an_entry,
+                  overflow_rows_under_the_bound, a_long_row_counted, two_entries_swapped, finalize_alone):
+            f.__qualname__ = "%s: %s" % (self.name, f.__name__)
+            out.append((self.phase, f))
+        return out
+
+
+COUNTED = [Counted("value_counts", VALUE_COUNTS, "vc", 1, "counted", "non_null", False),
+           Counted("pair_counts", PAIR_COUNTS, "pc", 2, "counted", "both_non_null", False),
+           Counted("group_counts", GROUP_COUNTS, "gc", 1, "counted", "null_group_rows", True),
+           Counted("group_sums (floats)", GROUP_SUMS_F, "gs", 1, "counted", "null_group_rows", True),
+           Counted("group_sums (integers)", GROUP_SUMS_I, "gs", 1, "counted", "null_group_rows", True)]
+
+
+def _pair_cell_transposed(res, st):
+    """a row of (word, bin i) counted under bin j of the same word"""
+    summary, entries = st.pc[PAIR_COUNTS]
+    entries = dict(entries)
+    (word, i), _ = next(iter(entries.items()))
+    j = 1 - i if i in (0, 1) else 0
+    entries[(word, i)] -= 1
+    entries[(word, j)] = entries.get((word, j), 0) + 1
+    entries = {k: v for k, v in sorted(entries.items()) if v}
+    set_counted(res, st, PAIR_COUNTS, "pc", dict(summary, distinct=len(entries)), entries)
+
+
+def _pair_range_next_double(name):
+    def perturb(res, st):
+        import math
+
+        st.pr[PAIR_COUNTS][name] = math.nextafter(st.pr[PAIR_COUNTS][name], math.inf)
+    perturb.__qualname__ = "pair_counts: range %s moved to the next double" % name
+    return perturb
+
+
+def _pair_range_non_finite(res, st):
+    st.pr[PAIR_COUNTS]["non_finite"] += 1
+    st.pr[PAIR_COUNTS]["n"] -= 1
+
+
+def _pair_entries_in_the_range_phase(res, st):
+    summary, _ = st.pc[PAIR_COUNTS]
+    st.pc[PAIR_COUNTS] = (summary, {(b"a", 0): 1})
+
+
+def _group_sum(si, change, what):
+    def perturb(res, st):
+        summary, entries = st.gs[si]
+        summary, entries = dict(summary), dict(entries)
+        change(summary, entries)
+        set_group_sums(res, st, si, summary, entries, X if si == GROUP_SUMS_F else Y)
+    perturb.__qualname__ = "group_sums: " + what
+    return perturb
+
+
+def _integer_sum_off_by_one(summary, entries):
+    rows, non_null, total = entries[b"bb"]
+    entries[b"bb"] = (rows, non_null, total + 1)
+    summary["counted"] = summary["counted"][:2] + (summary["counted"][2] + 1,)  # (the identities keep holding)
+    summary["null_group"] = summary["null_group"][:2] + (summary["null_group"][2] - 1,)
+
+
+def _float_sum_off_by_twice_its_bound(summary, entries):
+    import exact_group_sums as EGS
+
+    want = EGS.walk(X, s_cells(), SMALL_MAX_BYTES, True)["entries"][b"bb"]
+    assert want[1] > 1 and want[2] == want[2]  # (0.5 + 3.0 + 3.75: a finite group, whose bound is not zero)
+    bound = EGS.float_bound(want[1], want[2], want[3])
+    assert bound > 0 and want[2] + 2 * bound != want[2]
+    entries[b"bb"] = want[:2] + (want[2] + 2 * bound,)
+
+
+def _is_float_flipped(summary, entries):
+    summary["is_float"] = not summary["is_float"]
+
+
+def _a_nan_group_that_is_finite(summary, entries):
+    rows, non_null, total = entries[b"a"]
+    assert total != total  # (the overflow rule: "a" holds X's NaN)
+    entries[b"a"] = (rows, non_null, 2.5)
+
+
+def _null_group_value_lost(summary, entries):
+    rows, non_null, total = summary["null_group"]
+    assert non_null > 0
+    summary["null_group"] = (rows, non_null - 1, total)
+
+
 PERTURBATIONS = [(1, _time_gap(f)) for f in (
     violations_up, violations_down_matches_consistent, largest_gap_up, a_partition_split_in_two, a_null_timestamp_retained,
     a_row_not_seen, null_group_split_row_by_row, the_ungrouped_answer)] + [(1, _time_gap_finalize_alone)]
@@ -560,6 +1093,17 @@ PERTURBATIONS += [(2, _bucket_to_neighbour), (2, _else_row_into_the_last_bucket)
                  (1, _joint_min_next_double), (1, _histogram_negative_zero), (1, _joint_negative_zero),
                  (1, _sum_off_by_twice_its_bound("sum")), (1, _sum_off_by_twice_its_bound("sum_squared")),
                  (2, _joint_cell_transposed), (1, _considered_and_violations_up), (1, _null_row_considered)]
+PERTURBATIONS += [(1, _rule(f)) for f in (valid_up, a_cast_error_counted_as_valid, a_null_row_considered)] + [(1, _rule_finalize_alone)]
+for _kind in COUNTED:
+    PERTURBATIONS += _kind.perturbations()
+PERTURBATIONS += [(2, _pair_cell_transposed), (1, _pair_range_next_double("min")), (1, _pair_range_next_double("max")),
+                  (1, _pair_range_non_finite), (1, _pair_entries_in_the_range_phase),
+                  (1, _group_sum(GROUP_SUMS_I, _integer_sum_off_by_one, "an integer sum off by one")),
+                  (1, _group_sum(GROUP_SUMS_F, _float_sum_off_by_twice_its_bound, "a float sum off by twice its bound")),
+                  (1, _group_sum(GROUP_SUMS_F, _is_float_flipped, "is_float flipped (floats)")),
+                  (1, _group_sum(GROUP_SUMS_I, _is_float_flipped, "is_float flipped (integers)")),
+                  (1, _group_sum(GROUP_SUMS_F, _a_nan_group_that_is_finite, "a finite sum for a group with a NaN")),
+                  (1, _group_sum(GROUP_SUMS_F, _null_group_value_lost, "a value of the NULL group not counted"))]
 
 
 def test_check_one_fails_on_every_single_perturbation():

@@ -1,11 +1,14 @@
-"""-m gpu: three fixed sets of seeds of the differential tester (tests/fuzz_plans.py): random plans x tables x batchings
+"""-m gpu: four fixed sets of seeds of the differential tester (tests/fuzz_plans.py): random plans x tables x batchings
 through the C ABI against the oracle and the exact references.  The first set runs with the default table sizes (up to
 2.6 M rows; the JOINT_BINS / TEMPORAL / HISTOGRAM checks are drawn up to 400 000 rows), the second with at most 400 000
 rows, so that every case of it can carry them; tests/test_fuzz_cases.py holds the two sets together to a census of what
 they must cover.  The third set, sized like the second, holds only cases that carry a TIME_GAP check (drawn for cases
 that are simply finalized): chosen so that the three sets together meet the TIME_GAP census of tests/test_fuzz_cases.py
--- every batching, state sequence, sort route, column role and neighbouring check, grouped and ungrouped.
-tools/fuzz_device.py runs any other range of seeds."""
+-- every batching, state sequence, sort route, column role and neighbouring check, grouped and ungrouped.  The fourth
+set, sized like the second, holds only cases that carry VALUE_RULE or one of the four counting kinds (VALUE_COUNTS,
+PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS; drawn for every way a state ends): chosen so that the four sets together meet the
+census of those kinds in tests/test_fuzz_cases.py -- every key type and layout, bound, state sequence and neighbouring
+check.  tools/fuzz_device.py runs any other range of seeds."""
 import pytest
 
 from fuzz_plans import run_seed
@@ -21,6 +24,11 @@ THIRD_SEEDS = [95, 110, 122, 155, 157, 170, 183, 185, 193, 211, 220, 241, 244, 2
                378, 382, 387, 393, 397, 415, 427, 444, 479, 491, 503, 519, 583, 593, 603, 607, 613, 619, 633, 648, 650, 682, 696]
 
 
+FOURTH_SEEDS = [700, 702, 703, 704, 705, 706, 707, 709, 713, 714, 715, 716, 717, 720, 721, 722, 724, 726, 727, 730, 732, 735, 737,
+                738, 739, 742, 743, 776, 815, 872, 875, 895, 900, 901, 980, 991, 1024, 1036, 1062, 1102, 1104, 1113, 1121, 1344,
+                1490, 1558, 1779, 2243]
+
+
 @pytest.mark.parametrize("seed", range(48))
 def test_seed(seed):
     run_seed(seed)
@@ -33,4 +41,9 @@ def test_seed_up_to_400_000_rows(seed):
 
 @pytest.mark.parametrize("seed", THIRD_SEEDS)
 def test_seed_with_time_gap(seed):
+    run_seed(seed, max_rows=SECOND_MAX_ROWS)
+
+
+@pytest.mark.parametrize("seed", FOURTH_SEEDS)
+def test_seed_with_rules_and_counts(seed):
     run_seed(seed, max_rows=SECOND_MAX_ROWS)
