@@ -1,7 +1,11 @@
 // counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS: the
 // bounded GROUP BY of kernels/count_table.h): the table's size and layout, clearing it, reading it back once between
 // batches, and the two places where sizes come from outside -- a blob's entries and the buffers of the *_entries calls.
+// keyed_state.h builds on this for the three kinds whose keys are the values of one column; PAIR_COUNTS, whose keys are
+// pairs of cells, stands on this file alone.
 #pragma once
+#include <initializer_list>
+
 #include "side_check.h"
 
 namespace tgx {
@@ -28,21 +32,27 @@ struct TGX_HIDDEN CountedTable {
   size_t bytes() const { return extra_at() + (size_t)slots * extra; }
 };
 
-// K gives, beyond what SideState asks:
-//   add_entries(a, b)   the entries of host `b` added to `a` (the counters came with SideState's words)
+// K's Host gives, beyond what SideState asks:
+//   a.add_entries(b)   the entries of host `b` added to `a` (the counters came with SideState's words)
 template <class K>
 struct TGX_HIDDEN CountedState : SideState<K> {
   typedef typename K::Host Host;
 
   std::vector<CountedTable> table;  // per task
+  // per task: the task whose table it counts in -- itself, unless a kind lets tasks share a table; the other tasks of
+  // a shared table have none of their own
+  std::vector<size_t> owner;
   // what the tables held when they were last read back: a read of the state costs the copy once, until the next batch
   // or reset (the *_get calls, the two calls of *_entries and tgx_finalize all gather)
   std::vector<Host> table_cache;
   bool table_cache_ok = false;
 
-  explicit CountedState(const tgx_plan *plan) : SideState<K>(plan), table(this->host.size()) {}
+  explicit CountedState(const tgx_plan *plan) : SideState<K>(plan), table(this->host.size()), owner(table.size()) {
+    for (size_t k = 0; k < owner.size(); k++) owner[k] = k;
+  }
 
-  // slot `s` of task k's table, whose copy is `h`, into `into`: its first key word is taken and its count is `count` > 0
+  // slot `s` of the table task k counts in, whose copy is `h`, into `into` as task k sees it: the slot's first key word
+  // is taken and its count is `count` > 0
   virtual void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, Host &into) const = 0;
 
   tgx_status clear_table(tgx_state *st, size_t k, tgx_error *err) {
@@ -73,9 +83,11 @@ struct TGX_HIDDEN CountedState : SideState<K> {
     return clear_table(st, k, err);
   }
 
-  // the tables' entries into the gathered hosts (the counters are already there)
+  // the tables' entries into the gathered hosts (the counters are already there): a table is copied once and decoded
+  // for every task that counts in it
   tgx_status gather_extra(tgx_state *st, std::vector<Host> *out, tgx_error *err) override {
     std::vector<uint8_t> h;
+    std::vector<size_t> served;
     if (!table_cache_ok) table_cache.assign(table.size(), Host());
     for (size_t k = 0; k < table.size() && !table_cache_ok; k++) {
       const CountedTable &t = table[k];
@@ -83,12 +95,16 @@ struct TGX_HIDDEN CountedState : SideState<K> {
       h.resize(t.bytes());
       HIP_TRY(hipMemcpyAsync(h.data(), t.buf.p, h.size(), hipMemcpyDeviceToHost, st->stream));
       HIP_TRY(hipStreamSynchronize(st->stream));
+      served.clear();
+      for (size_t j = 0; j < owner.size(); j++)
+        if (owner[j] == k) served.push_back(j);
       const uint64_t *keys = (const uint64_t *)h.data(), *counts = (const uint64_t *)(h.data() + t.counts_at());
       for (uint64_t s = 0; s < t.slots; s++)
-        if (keys[s] != kEmptyKey && counts[s] != 0) decode_slot(k, h.data(), s, counts[s], table_cache[k]);
+        if (keys[s] != kEmptyKey && counts[s] != 0)
+          for (size_t j : served) decode_slot(j, h.data(), s, counts[s], table_cache[j]);
     }
     table_cache_ok = true;
-    for (size_t k = 0; k < table.size(); k++) K::add_entries((*out)[k], table_cache[k]);
+    for (size_t k = 0; k < table.size(); k++) (*out)[k].add_entries(table_cache[k]);
     return TGX_OK;
   }
 };
@@ -111,67 +127,65 @@ TGX_HIDDEN inline Utf8ColDesc string_desc(const tgx_column &c, const uint8_t *co
   return d;
 }
 
-// A task's entries in a blob: n x { key, u64 count }, strictly ascending by key, into the empty map `m`; *counted: the
-// sum of their counts.  `least`: the fewest bytes an entry takes.  read_key(key) reads one key and may refuse it.
-// TGX_OK with r.ok cleared: the blob ran out
-template <class Map, class ReadKey>
-TGX_HIDDEN inline tgx_status counted_read_entries(const char *name, size_t k, Reader &r, uint64_t n, size_t least, Map &m,
-                                                  uint64_t *counted, ReadKey read_key, tgx_error *err) {
+// ---- a task's entries in a blob: n x { key, the payload's 64-bit words }, strictly ascending by key -------------------
+// A payload's wire form W gives: kWords, put(payload, words), get(words), and refuse(words): null, or what is wrong with
+// an entry's words, as the refusal says it.  The first word is the entry's count, which is never zero.
+struct CountWire {  // a bare count
+  static constexpr int kWords = 1;
+  void put(uint64_t c, uint64_t *w) const { w[0] = c; }
+  uint64_t get(const uint64_t *w) const { return w[0]; }
+  const char *refuse(const uint64_t *) const { return nullptr; }
+};
+
+// write_key(key) writes one key
+template <class W, class Map, class WriteKey>
+TGX_HIDDEN inline void counted_write_entries(const Map &m, const W &wire, Writer &w, WriteKey write_key) {
+  for (const auto &e : m) {
+    uint64_t words[W::kWords];
+    write_key(e.first);
+    wire.put(e.second, words);
+    w.pod(words);
+  }
+}
+
+// ... read into the empty map `m`; *counted: the sum of their counts.  `key_least`: the fewest bytes a key takes.
+// read_key(key) reads one key and may refuse it.  TGX_OK with r.ok cleared: the blob ran out
+template <class W, class Map, class ReadKey>
+TGX_HIDDEN inline tgx_status counted_read_entries(const char *name, size_t k, Reader &r, uint64_t n, size_t key_least,
+                                                  const W &wire, Map &m, uint64_t *counted, ReadKey read_key,
+                                                  tgx_error *err) {
   size_t bytes = 0;  // (held against the bytes that are left before anything is allocated)
-  if (!r.fits(n, least, &bytes)) return TGX_OK;
+  if (!r.fits(n, key_least + 8 * W::kWords, &bytes)) return TGX_OK;
   *counted = 0;
   for (uint64_t i = 0; i < n; i++) {
     typename Map::key_type key;
     TGX_TRY(read_key(key));
-    const uint64_t c = r.pod<uint64_t>();
+    uint64_t words[W::kWords];
+    r.get(words, sizeof(words));
     if (!r.ok) return TGX_OK;
     if (!m.empty() && !(m.rbegin()->first < key))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu is out of order or repeated)",
                   name, k, (unsigned long long)i);
-    if (c == 0)
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu has a zero count)", name, k,
-                  (unsigned long long)i);
-    if (c > UINT64_MAX - *counted)
+    const char *wrong = words[0] == 0 ? "has a zero count" : wire.refuse(words);
+    if (wrong)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu %s)", name, k,
+                  (unsigned long long)i, wrong);
+    if (words[0] > UINT64_MAX - *counted)
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: counts)", name, k);
-    *counted += c;
-    m.emplace_hint(m.end(), std::move(key), c);
+    *counted += words[0];
+    m.emplace_hint(m.end(), std::move(key), wire.get(words));
   }
   return TGX_OK;
 }
 
-// The sibling for entries with a second counter: n x { key, u64 total, u64 non_null }, non_null <= total, into the map
-// `m` of key -> Counts{total, non_null}; *counted / *counted_non_null: the sums
-template <class Map, class ReadKey>
-TGX_HIDDEN inline tgx_status counted_read_entries2(const char *name, size_t k, Reader &r, uint64_t n, size_t least, Map &m,
-                                                   uint64_t *counted, uint64_t *counted_non_null, ReadKey read_key,
-                                                   tgx_error *err) {
-  size_t bytes = 0;  // (held against the bytes that are left before anything is allocated)
-  if (!r.fits(n, least, &bytes)) return TGX_OK;
-  *counted = *counted_non_null = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    typename Map::key_type key;
-    TGX_TRY(read_key(key));
-    const uint64_t c = r.pod<uint64_t>(), nn = r.pod<uint64_t>();
-    if (!r.ok) return TGX_OK;
-    if (!m.empty() && !(m.rbegin()->first < key))
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu is out of order or repeated)",
-                  name, k, (unsigned long long)i);
-    if (c == 0)
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu has a zero count)", name, k,
-                  (unsigned long long)i);
-    if (nn > c)
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: entry %llu has non_null > total)", name,
-                  k, (unsigned long long)i);
-    if (c > UINT64_MAX - *counted)
-      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (%s task %zu: counts)", name, k);
-    *counted += c;
-    *counted_non_null += nn;
-    typename Map::mapped_type v;
-    v.total = c;
-    v.non_null = nn;
-    m.emplace_hint(m.end(), std::move(key), v);
+// do the terms add up to `whole`?  (No sum can wrap: each term is held against what is left of the whole)
+TGX_HIDDEN inline bool terms_make(uint64_t whole, std::initializer_list<uint64_t> terms) {
+  bool ok = true;
+  for (uint64_t term : terms) {
+    ok = ok && term <= whole;
+    whole -= ok ? term : 0;
   }
-  return TGX_OK;
+  return ok && whole == 0;
 }
 
 // The size query of the *_entries calls: what is needed is reported first, then the buffers are held against it.  A call

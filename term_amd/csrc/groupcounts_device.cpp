@@ -10,11 +10,10 @@
 // of a task is a map from key (int64, or bytes) to (total, non_null) plus the counters: what was merged in or read
 // from a blob, and what the device part is folded into whenever the state is read -- so merges, blobs and the
 // cross-rank step unite by VALUE, never by fingerprint.  Rows seen are counted on the host.
-#include <map>
-#include <string>
-
-#include "api_internal.h"
-#include "counted_state.h"
+//
+// keyed_state.h has what the kind shares with VALUE_COUNTS and GROUP_SUMS; here are its payload (total, non_null), its
+// classes, its walks -- the tasks of a walk count in the leader's table (CountedState::owner) -- and its launches.
+#include "keyed_state.h"
 
 namespace tgx {
 void launch_group_counts_i64(const ComomentColDesc &d, const GroupMembers &mem, const GroupCountsTable &t, int blocks,
@@ -27,30 +26,30 @@ void launch_group_counts_dict(const int32_t *indices, const uint8_t *validity, i
 
 namespace {
 
-enum { kNoKeys = 0, kIntKeys = 1, kByteKeys = 2 };
-
 struct Counts {
   uint64_t total = 0, non_null = 0;
-  void add(const Counts &o) {
+  Counts &operator+=(const Counts &o) {
     total += o.total;
     non_null += o.non_null;
+    return *this;
   }
 };
 
+// in a blob: u64 total, u64 non_null
+struct CountsWire {
+  static constexpr int kWords = 2;
+  void put(const Counts &c, uint64_t *w) const {
+    w[0] = c.total;
+    w[1] = c.non_null;
+  }
+  Counts get(const uint64_t *w) const { return Counts{w[0], w[1]}; }
+  const char *refuse(const uint64_t *w) const { return w[1] > w[0] ? "has non_null > total" : nullptr; }
+};
+
 // one task's state as the host sees it
-struct GroupsHost {
-  int kind = kNoKeys;
+struct GroupsHost : KeyedEntries<Counts> {
   uint64_t seen = 0;
   Counts null_group, overflow, long_keys;
-  std::map<int64_t, Counts> ints;      // ascending int64
-  std::map<std::string, Counts> strs;  // ascending bytewise (std::string compares as unsigned bytes)
-  uint64_t groups() const { return ints.size() + strs.size(); }
-  Counts counted() const {
-    Counts c;
-    for (const auto &e : ints) c.add(e.second);
-    for (const auto &e : strs) c.add(e.second);
-    return c;
-  }
   uint64_t value_non_null() const {
     return counted().non_null + null_group.non_null + overflow.non_null + long_keys.non_null;
   }
@@ -61,17 +60,21 @@ struct NoRange {};
 struct GroupsKind {
   typedef GroupCountsTask Task;
   typedef GroupsHost Host;
+  typedef Counts Payload;
   typedef NoRange Range;
   static constexpr bool kRanged = false;
   static constexpr int kKind = TGX_CHECK_GROUP_COUNTS;
   static constexpr const char *kDiffers = "group column types";
+  static constexpr const char *kNoun = "key";
+  static constexpr const char *kColumn = "the group column";
   static constexpr uint32_t kMagic = 0x544e4347;  // "GCNT"
 
   static const std::vector<GroupCountsTask> &tasks(const tgx_plan *plan) { return plan->group_counts; }
   static size_t words(const GroupCountsTask &) { return kGroupCountsWords; }
+  static uint32_t bound(const GroupCountsTask &t) { return t.params.max_groups; }
   static NoRange range_identity() { return NoRange(); }
   static GroupsHost fresh(const GroupCountsTask &) { return GroupsHost(); }
-  static size_t shape(const GroupsHost &) { return 0; }  // (integer against string keys: GroupsCheck::merge_from)
+  static size_t shape(const GroupsHost &) { return 0; }  // (integer against string keys: KeyedCheck::merge_from)
   // the counters; the table's entries follow in gather_extra.  `w`: the task's words; every task has
   // kGroupCountsWords of them, so the words of its walk's leader, which hold the walk's rows, lie slot - leader tasks
   // in front
@@ -93,17 +96,12 @@ struct GroupsKind {
     }
     return d;
   }
-  static void add_entries(GroupsHost &a, const GroupsHost &b) {
-    if (a.kind == kNoKeys) a.kind = b.kind;
-    for (const auto &e : b.ints) a.ints[e.first].add(e.second);
-    for (const auto &e : b.strs) a.strs[e.first].add(e.second);
-  }
   static void merge_host(GroupsHost &a, const GroupsHost &b) {
     a.seen += b.seen;
-    a.null_group.add(b.null_group);
-    a.overflow.add(b.overflow);
-    a.long_keys.add(b.long_keys);
-    add_entries(a, b);
+    a.null_group += b.null_group;
+    a.overflow += b.overflow;
+    a.long_keys += b.long_keys;
+    a.add_entries(b);
   }
 
   // per task { u32 max_groups, max_value_bytes (the plan's parameters), u32 kind (0 no keys, 1 int64, 2 bytes), u32 0,
@@ -116,19 +114,9 @@ struct GroupsKind {
     w.pod((uint32_t)h.kind);
     w.pod((uint32_t)0);
     const uint64_t counts[8] = {h.seen, h.null_group.total, h.null_group.non_null, h.overflow.total, h.overflow.non_null,
-                                h.long_keys.total, h.long_keys.non_null, h.groups()};
+                                h.long_keys.total, h.long_keys.non_null, h.size()};
     w.pod(counts);
-    for (const auto &e : h.ints) {
-      w.pod(e.first);
-      w.pod(e.second.total);
-      w.pod(e.second.non_null);
-    }
-    for (const auto &e : h.strs) {
-      w.pod((uint32_t)e.first.size());
-      w.put(e.first.data(), e.first.size());
-      w.pod(e.second.total);
-      w.pod(e.second.non_null);
-    }
+    keyed_write_entries(h, CountsWire(), w);
   }
 
   static tgx_status read(const GroupCountsTask &t, GroupsHost &h, Reader &r, size_t k, tgx_error *err) {
@@ -146,36 +134,13 @@ struct GroupsKind {
     const uint64_t n = counts[7];
     if (kind > kByteKeys || pad != 0 || (kind == kNoKeys && n != 0))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (GROUP_COUNTS task %zu: kind)", k);
-    uint64_t counted = 0, counted_nn = 0;
-    if (kind == kIntKeys) {
-      TGX_TRY(counted_read_entries2("GROUP_COUNTS", k, r, n, 24, h.ints, &counted, &counted_nn, [&](int64_t &v) {
-        v = r.pod<int64_t>();
-        return TGX_OK;
-      }, err));
-    } else {
-      TGX_TRY(counted_read_entries2("GROUP_COUNTS", k, r, n, 20, h.strs, &counted, &counted_nn, [&](std::string &v) {
-        const uint32_t len = r.pod<uint32_t>();
-        if (!r.ok) return TGX_OK;
-        if (len > t.params.max_value_bytes)
-          return fail(err, TGX_INVALID_ARGUMENT,
-                      "malformed state blob (GROUP_COUNTS task %zu: a key of %u bytes, max_value_bytes is %u)", k, len,
-                      t.params.max_value_bytes);
-        v.assign(len, '\0');
-        r.get(&v[0], len);
-        return TGX_OK;
-      }, err));
-    }
+    uint64_t counted = 0;
+    TGX_TRY(keyed_read_entries("GROUP_COUNTS", kNoun, k, r, kind, n, t.params.max_value_bytes, CountsWire(), h, &counted,
+                               err));
     if (!r.ok) return TGX_OK;
-    // counted + null_group_rows + overflow_rows + long_rows == seen (no sum can wrap: each term is held against what is
-    // left of seen), and no class has more non-NULL values than rows
-    uint64_t left = counts[0];
-    bool ok = true;
-    const uint64_t terms[4] = {counted, counts[1], counts[3], counts[5]};
-    for (uint64_t term : terms) {
-      ok = ok && term <= left;
-      left -= ok ? term : 0;
-    }
-    if (!ok || left != 0 || counts[2] > counts[1] || counts[4] > counts[3] || counts[6] > counts[5])
+    // counted + null_group_rows + overflow_rows + long_rows == seen, and no class has more non-NULL values than rows
+    if (!terms_make(counts[0], {counted, counts[1], counts[3], counts[5]}) || counts[2] > counts[1] ||
+        counts[4] > counts[3] || counts[6] > counts[5])
       return fail(err, TGX_INVALID_ARGUMENT,
                   "malformed state blob (GROUP_COUNTS task %zu: counted + null_group_rows + overflow_rows + long_rows != "
                   "seen, or a class with non_null > rows)", k);
@@ -191,19 +156,10 @@ struct GroupsKind {
   }
 };
 
-struct GroupsCheck final : CountedState<GroupsKind> {
-  // a walk's device part besides its table (the leader's; made at the first batch, for the kind of key the group
-  // column holds): the per-entry cells of the dictionary route
-  struct Dev {
-    int kind = kNoKeys;
-    DevBuf cells;
-  };
-  std::vector<Dev> dev_part;                 // by leader
-  std::vector<std::vector<int>> walks;       // the tasks of each walk, leader first
-  const std::vector<GroupCountsTask> &tasks;  // (the plan's: their parameters are fixed once a state exists)
+struct GroupsCheck final : KeyedCheck<GroupsKind> {
+  std::vector<std::vector<int>> walks;  // the tasks of each walk, leader first
 
-  explicit GroupsCheck(const tgx_plan *plan)
-      : CountedState(plan), dev_part(plan->group_counts.size()), tasks(plan->group_counts) {
+  explicit GroupsCheck(const tgx_plan *plan) : KeyedCheck(plan) {
     std::vector<int> walk_of(tasks.size(), -1);  // (by leader)
     for (size_t k = 0; k < tasks.size(); k++) {
       const int leader = tasks[k].leader;
@@ -212,48 +168,22 @@ struct GroupsCheck final : CountedState<GroupsKind> {
         walks.emplace_back();
       }
       walks[walk_of[leader]].push_back((int)k);
+      owner[k] = (size_t)leader;
     }
   }
 
-  size_t members(size_t leader) const { return table[leader].extra_counters / 8; }
+  // behind a walk's totals: one array of non_null counters per member
   size_t non_null_at(size_t leader) const { return table[leader].extra_at(); }
-  size_t lens_at(size_t leader) const { return non_null_at(leader) + (size_t)table[leader].slots * 8 * members(leader); }
-  size_t store_at(size_t leader) const { return lens_at(leader) + (size_t)table[leader].slots * 4; }
 
   GroupCountsTable view(const tgx_state *st, size_t leader) const {
-    const Dev &d = dev_part[leader];
-    const uint64_t slots = table[leader].slots;
     uint8_t *base = table[leader].buf.as<uint8_t>();
     GroupCountsTable t;
-    memset(&t, 0, sizeof(t));
-    t.keys = (unsigned long long *)base;
-    t.keys2 = d.kind == kByteKeys ? t.keys + slots : nullptr;
+    fill_view(st, leader, t);
     t.totals = (unsigned long long *)(base + table[leader].counts_at());
     t.non_null = (unsigned long long *)(base + non_null_at(leader));
-    t.lens = d.kind == kByteKeys ? (uint32_t *)(base + lens_at(leader)) : nullptr;
-    t.store = d.kind == kByteKeys ? base + store_at(leader) : nullptr;
     t.words = d_counts.as<unsigned long long>();
     t.shared_word = (uint32_t)word_off[leader];
-    t.mask = slots - 1;
-    t.salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
-    t.max_value_bytes = tasks[leader].params.max_value_bytes;
     return t;
-  }
-
-  tgx_status ensure_table(tgx_state *st, const std::vector<int> &walk, int kind, tgx_error *err) {
-    const size_t leader = (size_t)walk[0];
-    Dev &d = dev_part[leader];
-    if (d.kind == kind) return TGX_OK;
-    if (d.kind != kNoKeys && device_rows[leader] > 0)
-      return fail(err, TGX_INVALID_ARGUMENT,
-                  "GROUP_COUNTS task %zu: the group column changed between integer and string values", leader);
-    const tgx_group_counts_params &p = tasks[leader].params;
-    const bool strings = kind == kByteKeys;
-    const size_t counters = walk.size() * 8;
-    TGX_TRY(open_table(st, leader, p.max_groups, strings ? 2 : 1,
-                       counters + (strings ? 4 + (size_t)p.max_value_bytes : 0), err, counters));
-    d.kind = kind;
-    return TGX_OK;
   }
 
   tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
@@ -264,11 +194,11 @@ struct GroupsCheck final : CountedState<GroupsKind> {
     for (const std::vector<int> &walk : walks) {
       const size_t leader = (size_t)walk[0];
       const tgx_column &g = dev[tasks[leader].group];
-      const bool strings = is_any_string(g.type), dict = g.type == TGX_DICT32_UTF8;
+      const Route route = route_of(g);
       // (an Int64 view: update_validate refuses what is neither a string layout nor widened to one)
-      if ((g.type != TGX_INT64 || !g.values) && !strings && !dict)
+      if (route == kNoRoute || (route == kIntRoute && !g.values))
         return fail(err, TGX_UNSUPPORTED, "GROUP_COUNTS groups by integer and string columns (%d)", g.type);
-      TGX_TRY(ensure_table(st, walk, g.type == TGX_INT64 ? kIntKeys : kByteKeys, err));
+      TGX_TRY(ensure_keys(st, leader, route == kIntRoute ? kIntKeys : kByteKeys, walk.size() * 8, err));
       const GroupCountsTable t = view(st, leader);
       GroupMembers mem;
       memset(&mem, 0, sizeof(mem));
@@ -281,7 +211,7 @@ struct GroupsCheck final : CountedState<GroupsKind> {
         mem.word[m] = (uint32_t)word_off[walk[m]];
         bits += v.validity ? (uint64_t)(nrows + 7) / 8 : 0;
       }
-      if (g.type == TGX_INT64) {
+      if (route == kIntRoute) {
         ComomentColDesc d;
         memset(&d, 0, sizeof(d));
         const uint64_t bytes = side_fill_x(d, g);
@@ -290,24 +220,21 @@ struct GroupsCheck final : CountedState<GroupsKind> {
         TGX_TRY(side_rows_fit("GROUP_COUNTS", nrows, blocks, err));
         ProfScope ps(st, "group_counts", bytes + bits);
         launch_group_counts_i64(d, mem, t, blocks, st->stream);
-      } else if (strings) {
+      } else if (route == kStringRoute) {
         // (per-wave and LDS counters are 32-bit here too: refused as VALUE_COUNTS refuses it)
         TGX_TRY(side_rows_fit("GROUP_COUNTS", nrows, 1024, err));
         ProfScope ps(st, "group_counts", 0);
         launch_group_counts_utf8(string_desc(g, g.variadic, plan->fp_key), mem, t, st->stream);
       } else {
-        const tgx_column *dc = g.dictionary;
-        if (!dc || !is_string(dc->type)) return fail(err, TGX_INVALID_ARGUMENT, "GROUP_COUNTS: malformed dictionary");
+        const tgx_column *dc;
+        TGX_TRY(dictionary_of(g, &dc, err));
         TGX_TRY(side_rows_fit("GROUP_COUNTS", nrows, 1024, err));
-        Dev &d = dev_part[leader];
-        const size_t cell_bytes = std::max<size_t>(8, (size_t)dc->length * 8 * (1 + walk.size()));
-        HIP_TRY(d.cells.reserve_roomy(cell_bytes));
-        HIP_TRY(hipMemsetAsync(d.cells.p, 0, cell_bytes, st->stream));
+        unsigned long long *cells;
+        TGX_TRY(clear_cells(st, leader, std::max<size_t>(8, (size_t)dc->length * 8 * (1 + walk.size())), &cells, err));
         ProfScope ps(st, "group_counts", (uint64_t)g.length * 4 + bits);
         // (without entries every row is a NULL-key row: the count kernel says so, the insert kernel is not launched)
         launch_group_counts_dict((const int32_t *)g.values, g.validity, g.offset, g.length,
-                                 string_desc(*dc, nullptr, plan->fp_key), mem, d.cells.as<unsigned long long>(), t,
-                                 st->stream);
+                                 string_desc(*dc, nullptr, plan->fp_key), mem, cells, t, st->stream);
       }
       HIP_TRY(hipGetLastError());
       for (int k : walk) device_rows[k] += nrows;
@@ -316,66 +243,9 @@ struct GroupsCheck final : CountedState<GroupsKind> {
   }
 
   // slot `s` of the table of task k's walk as task k sees it: the group's rows and its own member's counter
-  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, GroupsHost &o) const override {
-    const size_t leader = (size_t)tasks[k].leader;
-    const Dev &d = dev_part[leader];
-    const uint64_t slots = table[leader].slots;
-    Counts c;
-    c.total = count;
-    c.non_null = ((const uint64_t *)(h + non_null_at(leader)))[(uint64_t)tasks[k].member * slots + s];
-    if (o.kind == kNoKeys) o.kind = d.kind;
-    if (d.kind == kIntKeys) {
-      o.ints[(int64_t)((const uint64_t *)h)[s]].add(c);
-    } else {
-      if (((const uint64_t *)h)[slots + s] == kEmptyKey) return;
-      const uint32_t most = tasks[leader].params.max_value_bytes,
-                     len = std::min(((const uint32_t *)(h + lens_at(leader)))[s], most);
-      o.strs[std::string((const char *)h + store_at(leader) + (size_t)s * most, len)].add(c);
-    }
-  }
-
-  // the walks' tables into the gathered hosts: a table is copied once and decoded for every member of its walk
-  tgx_status gather_extra(tgx_state *st, std::vector<GroupsHost> *out, tgx_error *err) override {
-    std::vector<uint8_t> h;
-    if (!table_cache_ok) table_cache.assign(table.size(), GroupsHost());
-    for (size_t w = 0; w < walks.size() && !table_cache_ok; w++) {
-      const size_t leader = (size_t)walks[w][0];
-      const CountedTable &t = table[leader];
-      if (!t.live || device_rows[leader] == 0) continue;
-      h.resize(t.bytes());
-      HIP_TRY(hipMemcpyAsync(h.data(), t.buf.p, h.size(), hipMemcpyDeviceToHost, st->stream));
-      HIP_TRY(hipStreamSynchronize(st->stream));
-      const uint64_t *keys = (const uint64_t *)h.data(), *counts = (const uint64_t *)(h.data() + t.counts_at());
-      for (uint64_t s = 0; s < t.slots; s++)
-        if (keys[s] != kEmptyKey && counts[s] != 0)
-          for (int k : walks[w]) decode_slot((size_t)k, h.data(), s, counts[s], table_cache[k]);
-    }
-    table_cache_ok = true;
-    for (size_t k = 0; k < table.size(); k++) GroupsKind::add_entries((*out)[k], table_cache[k]);
-    return TGX_OK;
-  }
-
-  // (integer keys and string keys do not unite: SideState's merge knows one shape per kind)
-  tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) override {
-    std::vector<GroupsHost> theirs, mine;
-    TGX_TRY(of(src)->gather(src, &theirs, err));
-    TGX_TRY(gather(st, &mine, err));
-    for (size_t k = 0; k < theirs.size(); k++)
-      if (theirs[k].kind != kNoKeys && mine[k].kind != kNoKeys && theirs[k].kind != mine[k].kind)
-        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", kName, k,
-                    GroupsKind::kDiffers);
-    for (size_t k = 0; k < theirs.size(); k++) GroupsKind::merge_host(host[k], theirs[k]);
-    return TGX_OK;
-  }
-
-  // one task, read; a state that was fed integer keys under one column type and strings under another holds both
-  tgx_status read_task(tgx_state *st, size_t slot, GroupsHost *out, tgx_error *err) {
-    std::vector<GroupsHost> g;
-    TGX_TRY(gather(st, &g, err));
-    if (!g[slot].ints.empty() && !g[slot].strs.empty())
-      return fail(err, TGX_INVALID_ARGUMENT, "GROUP_COUNTS task %zu holds integer and string keys", slot);
-    *out = std::move(g[slot]);
-    return TGX_OK;
+  Counts slot_payload(size_t k, const uint8_t *h, uint64_t s, uint64_t count) const override {
+    const size_t leader = owner[k];
+    return Counts{count, ((const uint64_t *)(h + non_null_at(leader)))[(uint64_t)tasks[k].member * table[leader].slots + s]};
   }
 
   tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) override {
@@ -383,21 +253,11 @@ struct GroupsCheck final : CountedState<GroupsKind> {
     TGX_TRY(read_task(st, (size_t)slot, &h, err));
     r->total = (int64_t)h.seen;
     r->non_null = (int64_t)h.value_non_null();
-    r->distinct = (int64_t)h.groups();
+    r->distinct = (int64_t)h.size();
     r->matches = (int64_t)h.counted().total;
     return TGX_OK;
   }
 };
-
-const char *type_name(int type) {
-  switch (type) {
-    case TGX_FLOAT64: return "Float64";
-    case TGX_FLOAT32: return "Float32";
-    case TGX_UINT64: return "UInt64";
-    case TGX_BOOL: return "Boolean";
-    default: return "this type";
-  }
-}
 
 // the walks of the tasks that have their parameters: a task joins the latest walk on its group column and bounds that
 // has a place left, or opens one
@@ -465,7 +325,7 @@ tgx_status groupcounts_check_column(const tgx_plan *plan, int column, const tgx_
   for (const GroupCountsTask &t : plan->group_counts) groups |= t.group == column;
   if (!groups) return TGX_OK;
   const int type = c.type;
-  if (type == TGX_FLOAT64 || type == TGX_FLOAT32 || type == TGX_UINT64 || type == TGX_BOOL)
+  if (refused_as_key(type))
     return fail(err, TGX_UNSUPPORTED, "column %d: GROUP_COUNTS groups by integer and string columns, not %s (type %d)",
                 column, type_name(type), type);
   if (c.length > 0 && !c.values && (is_numeric(type) || is_widened(type)))
@@ -508,13 +368,11 @@ extern "C" tgx_status tgx_group_counts_get(const tgx_plan *plan, tgx_state *st, 
                                            tgx_group_counts_summary *out, tgx_error *err) try {
   bind_thread();
   if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
-  size_t slot = 0;
-  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_GROUP_COUNTS, "GROUP_COUNTS", &slot, err, "bad arguments"));
   GroupsHost h;
-  TGX_TRY(static_cast<GroupsCheck *>(GroupsCheck::of(st))->read_task(st, slot, &h, err));
+  TGX_TRY(GroupsCheck::read_spec(plan, st, spec_index, &h, err));
   const Counts counted = h.counted();
   out->seen = h.seen;
-  out->groups = h.groups();
+  out->groups = h.size();
   out->counted = counted.total;
   out->counted_non_null = counted.non_null;
   out->null_group_rows = h.null_group.total;
@@ -534,24 +392,12 @@ extern "C" tgx_status tgx_group_counts_entries(const tgx_plan *plan, tgx_state *
                                                tgx_error *err) try {
   bind_thread();
   if (!n_entries || !n_bytes || !is_bytes) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
-  size_t slot = 0;
-  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_GROUP_COUNTS, "GROUP_COUNTS", &slot, err, "bad arguments"));
   GroupsHost h;
-  TGX_TRY(static_cast<GroupsCheck *>(GroupsCheck::of(st))->read_task(st, slot, &h, err));
-  uint64_t need_bytes = 0;
-  for (const auto &e : h.strs) need_bytes += e.first.size();
-  *is_bytes = h.kind == kByteKeys ? 1 : 0;
-  TGX_TRY(counted_entries_sizes(h.groups(), need_bytes, entries, cap, n_entries, bytes, bytes_cap, n_bytes, err));
-  if (!entries) return TGX_OK;
-  size_t i = 0;
-  uint64_t at = 0;
-  for (const auto &e : h.ints) entries[i++] = tgx_group_count_entry{e.first, 0, 0, e.second.total, e.second.non_null};
-  for (const auto &e : h.strs) {
-    if (!e.first.empty()) memcpy(bytes + at, e.first.data(), e.first.size());
-    entries[i++] = tgx_group_count_entry{0, at, (uint64_t)e.first.size(), e.second.total, e.second.non_null};
-    at += e.first.size();
-  }
-  return TGX_OK;
+  TGX_TRY(GroupsCheck::read_spec(plan, st, spec_index, &h, err));
+  return keyed_entries_out(h, entries, cap, n_entries, bytes, bytes_cap, n_bytes, is_bytes,
+                           [](int64_t key, uint64_t at, uint64_t length, const Counts &c) {
+                             return tgx_group_count_entry{key, at, length, c.total, c.non_null};
+                           }, err);
 } catch (...) {
   return tgx::abi_exception(err);
 }

@@ -45,6 +45,9 @@ struct PairsHost {
     for (const auto &e : pairs) c += e.second;
     return c;
   }
+  void add_entries(const PairsHost &b) {
+    for (const auto &e : b.pairs) pairs[e.first] += e.second;
+  }
 };
 
 double key_to_double(long long key) {
@@ -96,9 +99,6 @@ struct PairsKind {
     }
     return d;
   }
-  static void add_entries(PairsHost &a, const PairsHost &b) {
-    for (const auto &e : b.pairs) a.pairs[e.first] += e.second;
-  }
   static void merge_host(PairsHost &a, const PairsHost &b) {
     a.seen += b.seen;
     a.both += b.both;
@@ -109,7 +109,7 @@ struct PairsKind {
     a.n += b.n;
     a.min = std::min(a.min, b.min);
     a.max = std::max(a.max, b.max);
-    add_entries(a, b);
+    a.add_entries(b);
   }
 
   // per task { tgx_pair_counts_params (the plan's: u32 max_pairs, max_value_bytes, per side i32 mode, u32 bins, f64
@@ -124,9 +124,9 @@ struct PairsKind {
     const double ext[2] = {h.min, h.max};
     w.pod(ext);
     w.pod((uint64_t)h.pairs.size());
-    for (const auto &e : h.pairs) {
+    counted_write_entries(h.pairs, CountWire(), w, [&](const PairKey &key) {
       for (int side = 0; side < 2; side++) {
-        const Cell &c = side ? e.first.second : e.first.first;
+        const Cell &c = side ? key.second : key.first;
         if ((side ? t.params.y.mode : t.params.x.mode) == TGX_PAIR_SIDE_VALUE) {
           w.pod((uint32_t)c.second.size());
           w.put(c.second.data(), c.second.size());
@@ -134,8 +134,7 @@ struct PairsKind {
           w.pod(c.first);
         }
       }
-      w.pod(e.second);
-    }
+    });
   }
 
   static tgx_status read(const PairCountsTask &t, PairsHost &h, Reader &r, size_t k, tgx_error *err) {
@@ -167,7 +166,7 @@ struct PairsKind {
       if (counts[6] != 0 || ext[0] != INFINITY || ext[1] != -INFINITY)
         return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (PAIR_COUNTS task %zu: a count phase with a range)", k);
       uint64_t counted = 0;
-      TGX_TRY(counted_read_entries("PAIR_COUNTS", k, r, n, 16, h.pairs, &counted, [&](PairKey &key) {
+      TGX_TRY(counted_read_entries("PAIR_COUNTS", k, r, n, 8, CountWire(), h.pairs, &counted, [&](PairKey &key) {
         for (int side = 0; side < 2; side++) {
           const tgx_pair_side &m = side ? t.params.y : t.params.x;
           Cell &c = side ? key.second : key.first;
@@ -192,16 +191,8 @@ struct PairsKind {
         return TGX_OK;
       }, err));
       if (!r.ok) return TGX_OK;
-      // counted + overflow_rows + long_rows + non_finite + out_of_range == both_non_null <= seen (no sum can wrap: each
-      // term is held against what is left of both_non_null)
-      uint64_t left = both;
-      bool ok = both <= counts[0];
-      const uint64_t terms[5] = {counted, counts[2], counts[3], counts[4], counts[5]};
-      for (uint64_t term : terms) {
-        ok = ok && term <= left;
-        left -= ok ? term : 0;
-      }
-      if (!ok || left != 0)
+      // counted + overflow_rows + long_rows + non_finite + out_of_range == both_non_null <= seen
+      if (both > counts[0] || !terms_make(both, {counted, counts[2], counts[3], counts[4], counts[5]}))
         return fail(err, TGX_INVALID_ARGUMENT,
                     "malformed state blob (PAIR_COUNTS task %zu: counted + overflow_rows + long_rows + non_finite + "
                     "out_of_range != both_non_null)", k);

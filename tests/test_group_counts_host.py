@@ -114,6 +114,9 @@ def test_blob_round_trip_and_merge_by_value():
     blob = groups_blob()
     st = T.State.deserialize(plan, blob)
     assert st.serialize() == blob
+    # a task without keys, with and without rows, beside one with keys
+    for empty in (wire.group_counts_state(4, 8, {}), wire.group_counts_state(4, 8, {}, null_group=(3, 2))):
+        assert T.State.deserialize(plan, groups_blob(first=empty)).serialize() == groups_blob(first=empty)
     other = groups_blob(wire.group_counts_state(4, 8, {7: (1, 1), 9: (5, 2)}),
                         wire.group_counts_state(100, 16, {b"b": (1, 0), b"c": (2, 2)}, null_group=(1, 1)))
     st.merge([T.State.deserialize(plan, other), T.State.deserialize(plan, blob)])
@@ -128,6 +131,29 @@ def test_blob_round_trip_and_merge_by_value():
     assert again.serialize() == st.serialize() and again.group_counts(1) == st.group_counts(1)
     st.reset()
     assert st.group_counts(1) == (ZERO, {})
+
+
+def test_tasks_that_share_a_walk_keep_their_own_counts():
+    # tasks 0 and 1 group by column 3 under the same bounds and ride one walk (one table on the device); task 2 has a
+    # walk of its own
+    plan = T.Plan([spec(T.GROUP_COUNTS, 0, column2=3), spec(T.GROUP_COUNTS, 1, column2=3), spec(T.GROUP_COUNTS, 2, column2=4)])
+    for k in range(3):
+        plan.set_group_counts(k, 8, 16)
+    tasks = [({b"": (4, 4), b"a": (3, 1)}, (2, 2)), ({b"": (4, 0), b"a": (3, 3)}, (2, 0)), ({7: (5, 2), -3: (4, 4)}, (0, 0))]
+    blob = wire.pack(group_counts=[wire.group_counts_state(8, 16, g, null_group=n) for g, n in tasks])
+    st = T.State.deserialize(plan, blob)
+    assert st.serialize() == blob
+    into = T.State(plan)
+    into.merge([st])
+    for state in (st, into):
+        for k, (groups, null_group) in enumerate(tasks):
+            summary, got = state.group_counts(k)
+            assert got == groups
+            assert summary["counted_non_null"] == sum(n for _, n in groups.values())
+            assert (summary["null_group_rows"], summary["null_group_non_null"]) == null_group
+    assert into.serialize() == blob
+    into.merge([st])
+    assert into.group_counts(1)[1] == {b"": (8, 0), b"a": (6, 6)} and into.group_counts(0)[1] == {b"": (8, 8), b"a": (6, 2)}
 
 
 def test_integer_and_string_states_do_not_merge():

@@ -139,6 +139,12 @@ def test_blob_round_trip_and_merge_by_value():
     blob = sums_blob()
     st = T.State.deserialize(plan, blob)
     assert st.serialize() == blob
+    # a task without keys -- without rows, with integer and with float sums -- beside one with keys
+    for empty in (wire.group_sums_state(4, 8, {}), wire.group_sums_state(4, 8, {}, null_group=(3, 2, -5)),
+                  wire.group_sums_state(4, 8, {}, is_float=True, null_group=(3, 2, 0.5))):
+        assert T.State.deserialize(plan, sums_blob(first=empty)).serialize() == sums_blob(first=empty)
+    ints_f = wire.group_sums_state(4, 8, {5: (3, 1, 0.5), -1: (2, 2, -7.25)}, is_float=True)  # float sums by integer keys
+    assert T.State.deserialize(plan, sums_blob(first=ints_f)).serialize() == sums_blob(first=ints_f)
     big = (1 << 63) - 1
     other = sums_blob(wire.group_sums_state(4, 8, {7: (1, 1, big), 9: (5, 2, big)}),
                       wire.group_sums_state(100, 16, {b"b": (1, 0, 0.0), b"c": (2, 2, 0.5)}, is_float=True,

@@ -107,6 +107,9 @@ def test_blob_round_trip_and_merge_by_value():
     blob = counts_blob()
     st = T.State.deserialize(plan, blob)
     assert st.serialize() == blob
+    # a task without values, with and without rows, beside one with values
+    for empty in (wire.value_counts_state(4, 8, 0, {}), wire.value_counts_state(4, 8, 3, {}, nulls=3)):
+        assert T.State.deserialize(plan, counts_blob(first=empty)).serialize() == counts_blob(first=empty)
     other = counts_blob(wire.value_counts_state(4, 8, 6, {7: 1, 9: 5}), wire.value_counts_state(100, 16, 4, {b"b": 1, b"c": 2}, nulls=1))
     st.merge([T.State.deserialize(plan, other), T.State.deserialize(plan, blob)])
     summary, counts = st.value_counts(0)
