@@ -371,7 +371,32 @@ typedef enum tgx_check_kind {
    * Read with tgx_group_sums_get and tgx_group_sums_entries; tgx_result carries total = rows seen, non_null =
    * COUNT(col), distinct = groups held, matches = rows counted in them, sum_i / sum_f = the sum over all classes,
    * has_value = 0 when COUNT(col) is 0. */
-  TGX_CHECK_GROUP_SUMS = 18
+  TGX_CHECK_GROUP_SUMS = 18,
+  /* Is each key of a child column in a parent's key set?  The device side of the reference's ForeignKeyConstraint
+   *                          TG/constraints/foreign_key.rs:152-176
+   *   SELECT COUNT(*), COUNT(DISTINCT child.c) FROM child LEFT JOIN parent ON child.c = parent.p
+   *   WHERE parent.p IS NULL [AND child.c IS NOT NULL]
+   * for integer keys: `column` is the child key column c (column2 must be -1); the bound on the missing keys that are
+   * kept comes with tgx_plan_set_key_probe (below); a spec without it makes tgx_state_create fail.  The parent's key set
+   * belongs to a STATE: tgx_key_probe_set_parent gives it, before the state's first batch; tgx_update on a state whose
+   * task has none is TGX_INVALID_ARGUMENT naming the spec.  tgx_state_reset clears the counters and the missing keys and
+   * keeps the set.
+   * Child columns: the Int64-shaped ones, Int32 / Date32 and Int8 .. UInt32 through the widening staging (the key is the
+   * sign- or zero-extended value, which is what TGX_CHECK_DISTINCT keeps for a parent column of those types: a narrow
+   * parent joins a wide child as SQL's coercion does).  Float32 / Float64, UInt64, Boolean and every string layout are
+   * TGX_UNSUPPORTED from tgx_update, and the state stays usable afterwards.
+   * The counts are exact and nothing is approximated: a NULL row is in null_rows; a non-NULL row is matched (its key is
+   * in the set) or missing, and a missing row is in exactly one of an entry of the missing keys and overflow_rows (its
+   * key found no slot in the table of 2 * max_missing_keys slots, probed as TGX_CHECK_VALUE_COUNTS's is), so
+   *   seen == non_null + null_rows,  non_null == matched + missing_rows,  missing_rows == counted + overflow_rows
+   * always hold, and with overflow_rows == 0 missing_keys is the exact COUNT(DISTINCT) of the violating keys.  The key
+   * whose bits are the table's free-slot marker (int64 -1) is an ordinary key on both sides.
+   * tgx_merge, state blobs and tgx_allreduce add the counters and unite the missing keys by value; states whose parent
+   * sets differ (parent_keys, parent_digest) do not merge.  A deserialized state holds no set: it can be read and merged,
+   * and takes batches again once tgx_key_probe_set_parent has given it a set with the same (parent_keys, parent_digest).
+   * Read with tgx_key_probe_get and tgx_key_probe_entries; tgx_result carries total = rows seen, non_null = non-NULL
+   * rows, matches = matched rows, distinct = missing keys held. */
+  TGX_CHECK_KEY_PROBE = 19
 } tgx_check_kind;
 
 enum {
@@ -669,6 +694,16 @@ typedef struct tgx_group_sums_params {
 } tgx_group_sums_params;
 tgx_status tgx_plan_set_group_sums(tgx_plan *plan, size_t spec_index, const tgx_group_sums_params *params,
                                    tgx_error *err);
+
+/* TGX_CHECK_KEY_PROBE: the bound of spec `spec_index`.  Lifetime and refusals are those of tgx_plan_set_value_counts.
+ * max_missing_keys (1 .. TGX_KEY_PROBE_MAX_MISSING_KEYS) sizes the task's table of missing keys on the device: a power
+ * of two of at least 2 * max_missing_keys slots; `reserved` must be 0. */
+enum { TGX_KEY_PROBE_MAX_MISSING_KEYS = 65536 };
+typedef struct tgx_key_probe_params {
+  uint32_t max_missing_keys;
+  uint32_t reserved;
+} tgx_key_probe_params;
+tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *params, tgx_error *err);
 
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
@@ -978,6 +1013,44 @@ tgx_status tgx_group_sums_entries(const tgx_plan *plan, tgx_state *state, size_t
                                   tgx_group_sum_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
                                   uint64_t bytes_cap, uint64_t *n_bytes, int32_t *is_bytes, tgx_error *err);
 
+/* ---- key probe (TGX_CHECK_KEY_PROBE; TG/constraints/foreign_key.rs:152-176) ----------------------------------------- */
+/* The parent's key set of spec `spec_index` of `state`: n_records 16-byte {uint64 key, uint64 count} records in device
+ * memory -- what tgx_distinct_export(.., world = 1, ..) hands out for a numeric key set, the extra record of the all-ones
+ * key included.  Counts are ignored, duplicate records are allowed, n_records == 0 is a valid, empty set.  The call
+ * builds the state's own probe structure (a bitmap over [MIN, MAX] when MAX - MIN + 1 <= 128 * n_records, else a hash
+ * table of the smallest power of two >= 2 * n_records slots) and has waited for it when it returns: the caller's
+ * records are not kept.  Allowed only on a state that has seen no batch since it was created or reset
+ * (TGX_INVALID_ARGUMENT otherwise); a state that holds counts -- merged in or deserialized -- refuses a set whose
+ * (parent_keys, parent_digest) differ from the ones those counts were taken under. */
+tgx_status tgx_key_probe_set_parent(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                    const void *device_records, uint64_t n_records, tgx_error *err);
+typedef struct tgx_key_probe_summary {
+  uint64_t seen;          /* rows handed to tgx_update */
+  uint64_t non_null;
+  uint64_t null_rows;     /* seen == non_null + null_rows */
+  uint64_t matched;       /* non-NULL rows whose key is in the set */
+  uint64_t missing_rows;  /* ... whose key is not: non_null == matched + missing_rows */
+  uint64_t counted;       /* missing rows counted in the entries: the sum of their counts */
+  uint64_t overflow_rows; /* missing rows whose key found no slot: missing_rows == counted + overflow_rows */
+  uint64_t missing_keys;  /* entries held; may exceed max_missing_keys: the caller compares */
+  uint64_t parent_keys;   /* distinct keys of the set (0 while the state knows of none) */
+  uint64_t parent_digest; /* the wrapping 64-bit sum of mix64(key ^ 0x9e3779b97f4a7c15) over them, mix64 the splitmix64
+                           * finaliser: independent of order, computed by the device during the build */
+  uint32_t route;         /* of the set this state holds: 0 none or empty, 1 bitmap, 2 hash table */
+  uint32_t reserved;
+} tgx_key_probe_summary;
+tgx_status tgx_key_probe_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_key_probe_summary *out,
+                             tgx_error *err);
+/* One missing key and the rows that hold it. */
+typedef struct tgx_key_probe_entry {
+  int64_t value;
+  uint64_t count;
+} tgx_key_probe_entry;
+/* Copies the missing keys, ascending by value.  *n_entries always receives what is needed; `entries` (cap entries) may
+ * be NULL for a size query; a non-NULL buffer that is too small is TGX_INVALID_ARGUMENT with nothing copied. */
+tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                 tgx_key_probe_entry *entries, uint64_t cap, uint64_t *n_entries, tgx_error *err);
+
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
  *   runs of fixed-size records (tgx_distinct_record_bytes) in device memory the state owns (valid until the next call on the
@@ -1067,7 +1140,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

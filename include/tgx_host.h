@@ -181,6 +181,19 @@ tgx_status tgx_host_run_suite_tables_json(const char *suite_json, const tgx_host
 tgx_status tgx_host_cross_table_sum_json(const char *constraint_json, const char *sums_json, char **out_json,
                                          tgx_error *err);
 
+/* The verdict of a "foreign_key" constraint
+ *   {"type": "foreign_key", "child_column": "orders.customer_id", "parent_column": "customers.id", "allow_nulls": false,
+ *    "use_left_join": true, "max_violations_reported": 100, "max_missing_keys": 10000}   (TG/constraints/foreign_key.rs)
+ * on given counts; needs no device.  (Within a suite run over several tables the constraint is evaluated beside the fused
+ * plan: the parent's column under a TGX_CHECK_DISTINCT spec, its key set handed to a TGX_CHECK_KEY_PROBE spec over the
+ * child's column.)  counts_json: {"null_rows": n, "missing_rows": n, "overflow_rows": n, "missing_keys": n,
+ * "entries": [[key, count], ..] ascending by key, "examples": true} as tgx_key_probe_get / tgx_key_probe_entries give
+ * them; "examples": false stands for a child column of a type the reference's example collector does not read.
+ * Returns {"status", "metric", "message", "config": {the constraint as the host layer read it}}.  An unqualified column
+ * and counts that contradict each other are TGX_INVALID_ARGUMENT. */
+tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *counts_json, char **out_json,
+                                     tgx_error *err);
+
 void tgx_host_free(char *s);
 
 #ifdef __cplusplus

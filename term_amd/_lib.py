@@ -27,6 +27,8 @@ PAIR_SIDE_VALUE, PAIR_SIDE_RANGE, PAIR_SIDE_BINNED = 0, 1, 2
 PAIR_COUNTS_MAX_PAIRS, PAIR_COUNTS_MAX_VALUE_BYTES = 65536, 256
 GROUP_COUNTS = 17  # COUNT(*) and COUNT(col) per group of a second column, for a bounded number of groups (Plan.set_group_counts)
 GROUP_COUNTS_MAX_GROUPS, GROUP_COUNTS_MAX_VALUE_BYTES = 65536, 256
+KEY_PROBE = 19  # is each key of a child column in a parent's key set (Plan.set_key_probe, State.key_probe_set_parent)
+KEY_PROBE_MAX_MISSING_KEYS = 65536
 GROUP_SUMS = 18  # COUNT(*), COUNT(col) and SUM(col) per group of a second column, for a bounded number of groups (Plan.set_group_sums)
 GROUP_SUMS_MAX_GROUPS, GROUP_SUMS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
@@ -217,6 +219,24 @@ class GroupSumEntry(C.Structure):
                 ("non_null", C.c_uint64), ("sum_i", C.c_int64), ("sum_f", C.c_double)]
 
 
+class KeyProbeParams(C.Structure):
+    """tgx_key_probe_params (include/tgx.h)"""
+    _fields_ = [("max_missing_keys", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KeyProbeSummary(C.Structure):
+    """tgx_key_probe_summary (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("non_null", C.c_uint64), ("null_rows", C.c_uint64), ("matched", C.c_uint64),
+                ("missing_rows", C.c_uint64), ("counted", C.c_uint64), ("overflow_rows", C.c_uint64),
+                ("missing_keys", C.c_uint64), ("parent_keys", C.c_uint64), ("parent_digest", C.c_uint64),
+                ("route", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KeyProbeEntry(C.Structure):
+    """tgx_key_probe_entry (include/tgx.h)"""
+    _fields_ = [("value", C.c_int64), ("count", C.c_uint64)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -359,6 +379,10 @@ def lib():
                                              C.POINTER(C.c_int32), E]
         L.tgx_group_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
                                                C.POINTER(C.c_int32), E]
+        L.tgx_plan_set_key_probe.argtypes = [vp, sz, C.POINTER(KeyProbeParams), E]
+        L.tgx_key_probe_set_parent.argtypes = [vp, vp, sz, vp, u64, E]
+        L.tgx_key_probe_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeSummary), E]
+        L.tgx_key_probe_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -805,6 +829,12 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_group_sums(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_key_probe(self, spec_index, max_missing_keys=10000, reserved=0):
+        """tgx_plan_set_key_probe: the bound of a KEY_PROBE spec (before the plan's first state)"""
+        p = KeyProbeParams(max_missing_keys, reserved)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def set_pair_counts(self, spec_index, x=None, y=None, max_pairs=10000, max_value_bytes=256):
         """tgx_plan_set_pair_counts: the bounds and the sides of a PAIR_COUNTS spec (before the plan's first state).  A
         side is None or "value" (a string column: PAIR_SIDE_VALUE), "range" (a numeric column: the spec is in its range
@@ -1104,6 +1134,27 @@ class State:
             c = getattr(s, name)
             summary[name] = (c.rows, c.non_null, c.sum_f if is_float else c.sum_i)
         return summary, groups
+
+    # key probe
+    def key_probe_set_parent(self, spec_index, device_ptr, n_records):
+        """tgx_key_probe_set_parent: the parent's key set of a KEY_PROBE spec, n_records {key, count} records in device
+        memory (what distinct_export(spec, 1) of the parent's state hands out), before the state's first batch"""
+        err = _Error()
+        _check(lib().tgx_key_probe_set_parent(self.plan.h, self.h, spec_index, device_ptr, int(n_records), C.byref(err)),
+               err)
+
+    def key_probe(self, spec_index):
+        """tgx_key_probe_get + tgx_key_probe_entries: (summary, missing) -- summary a dict of the fields of
+        tgx_key_probe_summary (reserved left out), missing a dict key -> rows in the library's order (ascending)"""
+        L, err = lib(), _Error()
+        s = KeyProbeSummary()
+        _check(L.tgx_key_probe_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        n = C.c_uint64()
+        _check(L.tgx_key_probe_entries(self.plan.h, self.h, spec_index, None, 0, C.byref(n), C.byref(err)), err)
+        entries = (KeyProbeEntry * max(n.value, 1))()
+        _check(L.tgx_key_probe_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), C.byref(err)), err)
+        summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
+        return summary, {e.value: e.count for e in entries[:n.value]}
 
     def pair_range(self, spec_index):
         """tgx_pair_range_get: dict(seen, both_non_null, n, non_finite, min, max) of a spec in its range phase"""

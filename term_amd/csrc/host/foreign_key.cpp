@@ -1,0 +1,179 @@
+// foreign_key.cpp -- ForeignKeyConstraint (TG/constraints/foreign_key.rs).  The reference runs
+//   SELECT COUNT(*), COUNT(DISTINCT child.c) FROM child LEFT JOIN parent ON child.c = parent.p
+//   WHERE parent.p IS NULL [AND child.c IS NOT NULL]                                                      (:152-176)
+// and a SELECT DISTINCT .. LIMIT n for the examples (:179-207).  Here the parent's column is walked once under a
+// TGX_CHECK_DISTINCT spec, its key set is exported (world 1) into the TGX_CHECK_KEY_PROBE spec of the child's column,
+// and the child is walked once: membership per row on the device, the verdict and the message on the host.  A NULL
+// parent row is no key of the set (NULL = x is not true), a NULL child row matches nothing: it is a violation unless
+// allow_nulls.  Integer keys only: every other column type is the constraint's own error, so the caller can hand the
+// constraint to the stock path.
+#include <string.h>
+
+#include "term_guard.h"
+
+namespace term_guard {
+
+namespace {
+
+[[noreturn]] void evaluation_error(const std::string &msg) {
+  throw TermError{TermError::ConstraintEvaluation, "'foreign_key': " + msg};
+}
+[[noreturn]] void query_failed(const std::string &why) {  // (:320-325)
+  evaluation_error("Foreign key validation query failed: " + why);
+}
+
+struct Handles {
+  tgx_plan *plan = nullptr;
+  tgx_state *state = nullptr;
+  Handles() = default;
+  Handles(const Handles &) = delete;
+  Handles &operator=(const Handles &) = delete;
+  ~Handles() {
+    if (state) tgx_state_destroy(state);
+    if (plan) tgx_plan_destroy(plan);
+  }
+};
+
+const char *off_path_type(int type) {
+  switch (type) {
+    case TGX_FLOAT64: return "Float64";
+    case TGX_FLOAT32: return "Float32";
+    case TGX_UINT64: return "UInt64";
+    case TGX_BOOL: return "Boolean";
+    case TGX_UTF8: return "Utf8";
+    case TGX_LARGE_UTF8: return "LargeUtf8";
+    case TGX_UTF8_VIEW: return "Utf8View";
+    case TGX_DICT32_UTF8: return "Dictionary<Int32, Utf8>";
+    default: return nullptr;
+  }
+}
+
+// the table and the index of the column behind a qualified name, with the reference's planning / schema errors
+const Table *side_of(const Context &ctx, const std::pair<std::string, std::string> &name, int *index) {
+  const Table *table = ctx.table(name.first);
+  if (!table) query_failed("Error during planning: table 'datafusion.public." + name.first + "' not found");
+  *index = -1;
+  for (size_t i = 0; i < table->column_names.size(); i++)
+    if (table->column_names[i] == name.second) *index = (int)i;
+  if (*index < 0) query_failed("Schema error: No field named " + name.second + ".");
+  return table;
+}
+
+// the column's type over the table's batches (0: no batch has the column); integer keys only
+int key_type(const Table &table, int index, const std::string &qualified) {
+  int type = 0;
+  for (const Batch &b : table.batches)
+    if ((size_t)index < b.columns.size()) {
+      const int t = b.columns[index].type;
+      if (const char *name = off_path_type(t))
+        evaluation_error("column '" + qualified + "' is a " + name +
+                         " column: foreign keys of that type are not on the GPU path (TGX_CHECK_KEY_PROBE takes integer "
+                         "keys)");
+      if (type == 0) type = t;
+    }
+  return type;
+}
+
+}  // namespace
+
+ConstraintResult ForeignKeyConstraint::evaluate(const Inputs &) const {
+  throw TermError{TermError::Internal, "foreign_key reads the tables of the context, not the suite's fused plan"};
+}
+
+// :130-149
+std::pair<std::string, std::string> ForeignKeyConstraint::parse_qualified_column(const std::string &qualified) {
+  std::vector<std::string> parts(1);
+  for (char ch : qualified) {
+    if (ch == '.') parts.emplace_back();
+    else parts.back().push_back(ch);
+  }
+  if (parts.size() != 2) evaluation_error("Foreign key column must be qualified (table.column): '" + qualified + "'");
+  if (auto e = validate_identifier(parts[0])) throw *e;
+  if (auto e = validate_identifier(parts[1])) throw *e;
+  return {parts[0], parts[1]};
+}
+
+// :334-410.  total_violations = COUNT(*) over the rows the join left without a parent: the missing rows, and the NULL
+// rows unless allow_nulls filters them; unique_violations = COUNT(DISTINCT child.c), which counts no NULL
+ConstraintResult ForeignKeyConstraint::verdict(const ForeignKeyCounts &c) const {
+  const uint64_t total = c.missing_rows + (allow_nulls_ ? 0 : c.null_rows);
+  if (total == 0) return ConstraintResult::success();
+  const std::string unique = (c.overflow_rows ? "at least " : "") + std::to_string(c.missing_keys);
+  std::string message = "Foreign key constraint violation: " + std::to_string(total) + " values in '" + child_ +
+                        "' do not exist in '" + parent_ + "' (total: " + std::to_string(total) + ", unique: " + unique + ")";
+  // the examples: the max_violations_reported smallest missing keys (the reference's LIMIT has no order; a NULL takes
+  // no slot here); up to 5 are listed (:387-395)
+  const size_t n = c.examples ? std::min(c.keys.size(), max_violations_) : 0;
+  if (n > 0) {
+    std::string list;
+    for (size_t i = 0; i < std::min<size_t>(n, 5); i++) list += (i ? ", " : "") + std::to_string(c.keys[i]);
+    if (n > 5) list += ", ... (" + std::to_string(n - 5) + " more)";
+    message += ". Examples: [" + list + "]";
+  }
+  return ConstraintResult::failure_with_metric((double)total, message);
+}
+
+ConstraintResult ForeignKeyConstraint::evaluate_context(const Context &ctx) const {
+  const auto child = parse_qualified_column(child_), parent = parse_qualified_column(parent_);
+  if (max_missing_keys_ < 1 || max_missing_keys_ > TGX_KEY_PROBE_MAX_MISSING_KEYS)
+    evaluation_error("max_missing_keys must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_MISSING_KEYS) + " (" +
+                     std::to_string(max_missing_keys_) + ")");
+  int ci = -1, pi = -1;
+  const Table *child_table = side_of(ctx, child, &ci);
+  const Table *parent_table = side_of(ctx, parent, &pi);
+  const int child_type = key_type(*child_table, ci, child_);
+  key_type(*parent_table, pi, parent_);
+
+  tgx_error err;
+  memset(&err, 0, sizeof(err));
+  auto check = [&](tgx_status s) {
+    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
+  };
+  check(tgx_init(nullptr, &err));
+
+  // the parent: its distinct non-NULL keys (Int32 / narrow columns as their sign- or zero-extended int64 values)
+  tgx_check_spec spec;
+  memset(&spec, 0, sizeof(spec));
+  spec.kind = TGX_CHECK_DISTINCT;
+  spec.column = pi;
+  spec.column2 = -1;
+  Handles p;
+  check(tgx_plan_create(&spec, 1, &p.plan, &err));
+  check(tgx_state_create(p.plan, nullptr, &p.state, &err));
+  for (const Batch &b : parent_table->batches) check(tgx_update(p.plan, p.state, b.columns.data(), b.columns.size(), &err));
+  const void *records = nullptr;
+  uint64_t n_records = 0;
+  check(tgx_distinct_export(p.plan, p.state, 0, 1, &records, &n_records, &err));
+
+  // the child, against that set (the records stay the parent state's until its next call: it lives to the end)
+  spec.kind = TGX_CHECK_KEY_PROBE;
+  spec.column = ci;
+  Handles c;
+  check(tgx_plan_create(&spec, 1, &c.plan, &err));
+  const tgx_key_probe_params params = {max_missing_keys_, 0};
+  check(tgx_plan_set_key_probe(c.plan, 0, &params, &err));
+  check(tgx_state_create(c.plan, nullptr, &c.state, &err));
+  check(tgx_key_probe_set_parent(c.plan, c.state, 0, records, n_records, &err));
+  for (const Batch &b : child_table->batches) check(tgx_update(c.plan, c.state, b.columns.data(), b.columns.size(), &err));
+  tgx_key_probe_summary s;
+  check(tgx_key_probe_get(c.plan, c.state, 0, &s, &err));
+  uint64_t n = 0;
+  check(tgx_key_probe_entries(c.plan, c.state, 0, nullptr, 0, &n, &err));
+  std::vector<tgx_key_probe_entry> entries((size_t)n + 1);
+  check(tgx_key_probe_entries(c.plan, c.state, 0, entries.data(), n, &n, &err));
+
+  ForeignKeyCounts counts;
+  counts.null_rows = s.null_rows;
+  counts.missing_rows = s.missing_rows;
+  counts.overflow_rows = s.overflow_rows;
+  counts.missing_keys = s.missing_keys;
+  for (uint64_t i = 0; i < n; i++) counts.keys.push_back(entries[i].value);
+  counts.examples = child_type == TGX_INT64 || child_type == TGX_INT32;  // (:265-291)
+  return verdict(counts);
+}
+
+Check::Builder &Check::Builder::foreign_key(std::string child_column, std::string parent_column) {
+  return constraint(std::make_shared<ForeignKeyConstraint>(std::move(child_column), std::move(parent_column)));
+}
+
+}  // namespace term_guard

@@ -732,3 +732,63 @@ extern "C" tgx_status tgx_host_cross_table_sum_json(const char *constraint_json,
     return hfail(err, TGX_INTERNAL, "unknown C++ exception");
   }
 }
+
+extern "C" tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *counts_json, char **out_json,
+                                                tgx_error *err) {
+  if (!constraint_json || !counts_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto c = std::dynamic_pointer_cast<ForeignKeyConstraint>(constraint_from_json_text(constraint_json));
+    if (!c) return hfail(err, TGX_INVALID_ARGUMENT, "not a foreign_key constraint");
+    json::Value v;
+    std::string perr;
+    if (!json::parse(counts_json, &v, &perr) || !v.is(json::Value::Object))
+      return hfail(err, TGX_INVALID_ARGUMENT, "counts JSON: " + (perr.empty() ? std::string("not an object") : perr));
+    (void)ForeignKeyConstraint::parse_qualified_column(c->child_column());
+    (void)ForeignKeyConstraint::parse_qualified_column(c->parent_column());
+    ForeignKeyCounts k;
+    k.null_rows = v.get_u64("null_rows", 0);
+    k.missing_rows = v.get_u64("missing_rows", 0);
+    k.overflow_rows = v.get_u64("overflow_rows", 0);
+    if (v.get("examples")) k.examples = v.get_bool("examples");
+    uint64_t counted = 0;
+    if (const json::Value *es = v.get("entries")) {
+      if (es->type != json::Value::Array) throw TermError{TermError::Internal, "entries must be a JSON array"};
+      for (const json::Value &e : es->arr) {
+        if (e.type != json::Value::Array || e.arr.size() != 2 || e.arr[0].type != json::Value::Number ||
+            e.arr[1].type != json::Value::Number)
+          throw TermError{TermError::Internal, "an entry is [key, count]"};
+        const int64_t key = e.arr[0].as_i64();
+        if (!k.keys.empty() && !(k.keys.back() < key))
+          throw TermError{TermError::Internal, "the entries must be ascending by key"};
+        k.keys.push_back(key);
+        counted += (uint64_t)e.arr[1].as_i64();
+      }
+    }
+    k.missing_keys = v.get_u64("missing_keys", k.keys.size());
+    if (k.missing_keys != k.keys.size() || k.missing_rows != counted + k.overflow_rows)
+      throw TermError{TermError::Internal, "counts JSON: missing_keys is the number of entries and missing_rows the sum "
+                                           "of their counts + overflow_rows"};
+    const ConstraintResult cr = c->verdict(k);
+    const std::string o =
+        std::string("{\"status\": \"") +
+        (cr.status == ConstraintStatus::Success ? "success" : cr.status == ConstraintStatus::Failure ? "failure" : "skipped") +
+        "\", \"metric\": " + (cr.metric ? json_f64(*cr.metric) : "null") + ", \"message\": " +
+        (cr.message ? json::quote(*cr.message) : "null") + ", \"config\": {\"name\": " + json::quote(c->name()) +
+        ", \"child_column\": " + json::quote(c->child_column()) + ", \"parent_column\": " +
+        json::quote(c->parent_column()) + ", \"allow_nulls\": " + (c->nulls_allowed() ? "true" : "false") +
+        ", \"use_left_join\": " + (c->left_join() ? "true" : "false") + ", \"max_violations_reported\": " +
+        std::to_string(c->violations_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) +
+        "}}";
+    *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}

@@ -1789,6 +1789,16 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     x->max_groups((uint32_t)std::min<uint64_t>(c.get_u64("max_groups", CrossTableSumConstraint::kDefaultMaxGroups),
                                                UINT32_MAX));
     b.constraint(std::move(x));
+  } else if (type == "foreign_key") {
+    // {"type": "foreign_key", "child_column": "orders.customer_id", "parent_column": "customers.id", "allow_nulls": false,
+    //  "use_left_join": true, "max_violations_reported": 100, "max_missing_keys": 10000}
+    auto x = std::make_shared<ForeignKeyConstraint>(c.get_str("child_column"), c.get_str("parent_column"));
+    x->allow_nulls(c.get_bool("allow_nulls"));
+    if (c.get("use_left_join")) x->use_left_join(c.get_bool("use_left_join"));
+    x->max_violations_reported((size_t)c.get_u64("max_violations_reported", 100));
+    x->max_missing_keys((uint32_t)std::min<uint64_t>(
+        c.get_u64("max_missing_keys", ForeignKeyConstraint::kDefaultMaxMissingKeys), UINT32_MAX));
+    b.constraint(std::move(x));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
   } else if (type == "histogram") {

@@ -302,6 +302,51 @@ class CrossTableSumConstraint : public Constraint {
   uint32_t max_groups_ = kDefaultMaxGroups;
 };
 
+// ---- constraints/foreign_key.rs: every non-NULL value of child.c is a value of parent.p.  The parent's column is walked
+// once under a TGX_CHECK_DISTINCT spec, its key set handed to a TGX_CHECK_KEY_PROBE spec over the child's column, and the
+// child walked once: integer keys only.  What the verdict is made from, as tgx_key_probe_get / _entries give it
+struct ForeignKeyCounts {
+  uint64_t null_rows = 0, missing_rows = 0, overflow_rows = 0, missing_keys = 0;
+  std::vector<int64_t> keys;  // the missing keys held, ascending
+  bool examples = true;       // the child column is of a type the reference's collector downcasts (:265-291)
+};
+class ForeignKeyConstraint : public Constraint {
+ public:
+  static constexpr uint32_t kDefaultMaxMissingKeys = 10000;
+  ForeignKeyConstraint(std::string child_column, std::string parent_column)  // "table.column" each (:78-91)
+      : child_(std::move(child_column)), parent_(std::move(parent_column)) {}
+  ForeignKeyConstraint &allow_nulls(bool allow) { allow_nulls_ = allow; return *this; }
+  ForeignKeyConstraint &use_left_join(bool on) { use_left_join_ = on; return *this; }  // (accepted; one strategy here)
+  ForeignKeyConstraint &max_violations_reported(size_t n) { max_violations_ = n; return *this; }
+  // this layer's own: the missing keys the child's table on the device is sized for (1 .. 65 536).  Rows beyond it are
+  // counted (overflow): the verdict and the metric stand, `unique` reads "at least n"
+  ForeignKeyConstraint &max_missing_keys(uint32_t n) { max_missing_keys_ = n; return *this; }
+
+  const std::string &child_column() const { return child_; }
+  const std::string &parent_column() const { return parent_; }
+  bool nulls_allowed() const { return allow_nulls_; }
+  bool left_join() const { return use_left_join_; }
+  size_t violations_reported() const { return max_violations_; }
+  uint32_t missing_keys_bound() const { return max_missing_keys_; }
+
+  std::string name() const override { return "foreign_key"; }
+  std::vector<SpecRequest> plan() const override { return {}; }
+  ConstraintResult evaluate(const Inputs &in) const override;  // throws: the constraint reads the Context
+  bool reads_context() const override { return true; }
+  ConstraintResult evaluate_context(const Context &ctx) const override;
+
+  // (table, column) of a qualified name; throws the reference's errors (:130-149)
+  static std::pair<std::string, std::string> parse_qualified_column(const std::string &qualified);
+  // the verdict and the message (:334-410)
+  ConstraintResult verdict(const ForeignKeyCounts &counts) const;
+
+ private:
+  std::string child_, parent_;
+  bool allow_nulls_ = false, use_left_join_ = true;
+  size_t max_violations_ = 100;
+  uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
+};
+
 // ---- core/check.rs
 class Check {
  public:
@@ -422,6 +467,8 @@ class Check::Builder {
   // core/check.rs:2054-2065: pushes CrossTableSumConstraint::new(left, right); a configured object comes through
   // constraint(..)
   Builder &cross_table_sum(std::string left_column, std::string right_column);
+  // pushes ForeignKeyConstraint::new(child, parent); a configured object comes through constraint(..)
+  Builder &foreign_key(std::string child_column, std::string parent_column);
   Check build() { return check_; }
 
  private:

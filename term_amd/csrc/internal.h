@@ -258,8 +258,16 @@ struct GroupSumsTask {
   tgx_group_sums_params params;
 };
 
+// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once tgx_plan_set_key_probe was called.  (The
+// parent's key set belongs to a state, not to the plan: tgx_key_probe_set_parent)
+struct KeyProbeTask {
+  int column, spec_index;
+  bool set;
+  tgx_key_probe_params params;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 8;  // the records of side_check.h's kSideKinds
+constexpr int kNumSide = 9;  // the records of side_check.h's kSideKinds
 
 enum class Source { kScan, kCount };
 
@@ -289,6 +297,7 @@ struct tgx_plan {
   std::vector<tgx::PairCountsTask> pair_counts;
   std::vector<tgx::GroupCountsTask> group_counts;
   std::vector<tgx::GroupSumsTask> group_sums;
+  std::vector<tgx::KeyProbeTask> key_probes;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
@@ -736,7 +745,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS and GROUP_SUMS parameters -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS and KEY_PROBE parameters -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

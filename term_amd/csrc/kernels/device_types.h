@@ -363,6 +363,45 @@ struct GroupSumsTable {
   uint32_t pad;
 };
 
+// Key probe (kernels/keyprobe.hip; TGX_CHECK_KEY_PROBE): is each child key in the parent's key set?  The set is read-only
+// while rows are walked: a bitmap of 32-bit words over [base, base + range) (route 1), or an open-addressing table of
+// `mask + 1` 64-bit keys at load <= 0.5 (route 2: kEmptyKey = free, probed linearly from mix64(key) & mask; the key whose
+// bits are the marker is the flag has_marker).  The keys that are NOT in it are counted in a bounded table laid out as
+// ValueCountsTable's integer half is; the missing key whose bits are the marker has a counter of its own.
+enum { kKpNonNull = 0, kKpMatched = 1, kKpMarker = 2, kKpOverflow = 3, kKeyProbeWords = 4 };
+enum { kKpRouteEmpty = 0, kKpRouteBitmap = 1, kKpRouteHash = 2 };
+constexpr int kKeyProbeBlock = 1024;              // 16 waves share one LDS table of missing keys
+constexpr uint32_t kKeyProbeLdsSlots = 8192;      // 8-byte keys + 4-byte counts: 96 KiB of LDS a workgroup
+constexpr uint32_t kKeyProbeLdsProbes = 8;
+constexpr uint32_t kKeyProbeProbes = 256;         // of the task's global table of missing keys
+constexpr int kMaxKeyProbePerLaunch = 8;
+struct KeyProbeSet {
+  const uint32_t *bits;            // route 1: (range + 31) / 32 words
+  const unsigned long long *keys;  // route 2: mask + 1 slots
+  uint64_t base, range;            // route 1: the bit of key k is k - base, for k - base < range (unsigned)
+  uint64_t mask;                   // route 2
+  uint32_t has_marker;             // route 2: the key whose bits are kEmptyKey is in the set
+  uint32_t pad;
+};
+struct KeyProbeTable {
+  unsigned long long *keys, *counts;  // the missing keys and their rows
+  unsigned long long *words;          // the task's kKeyProbeWords counters
+  uint64_t mask;
+  uint64_t salt;
+};
+struct KeyProbeLaunch {
+  ComomentColDesc cols[kMaxKeyProbePerLaunch];
+  KeyProbeSet sets[kMaxKeyProbePerLaunch];
+  KeyProbeTable tables[kMaxKeyProbePerLaunch];
+};
+// what the build of a set leaves behind: a reduction over the records, then the counts of the distinct inserts
+struct KeyProbeBuild {
+  long long min, max;                  // identities: INT64_MAX / INT64_MIN
+  unsigned long long keys, digest;     // distinct keys and the wrapping sum of mix64(key ^ kKeyProbeDigestSalt) over them
+  unsigned int has_marker, pad;
+};
+constexpr uint64_t kKeyProbeDigestSalt = 0x9e3779b97f4a7c15ULL;
+
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.
 // Range phase: n, rows with a NaN / infinity, the extremes and the raw sums over the non-NULL, finite rows.

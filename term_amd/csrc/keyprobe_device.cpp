@@ -1,0 +1,454 @@
+// keyprobe_device.cpp -- TGX_CHECK_KEY_PROBE: is each key of a child column in a parent's key set?  (The device side of
+// the reference's ForeignKeyConstraint, TG/constraints/foreign_key.rs:152-176; include/tgx.h has the exact semantics.)
+//
+// A task is one spec.  What a state holds for it:
+//   the parent's set   a bitmap or a hash table in device memory, built by tgx_key_probe_set_parent from {key, count}
+//                      records (kernels/keyprobe.hip), with its route, the number of its distinct keys and their digest.
+//                      It is read-only while batches run, survives tgx_state_reset, and travels nowhere: a blob carries
+//                      (parent_keys, parent_digest) only, and a state read from one takes batches again once it has been
+//                      given a set with that identity.
+//   the counters       four 64-bit words on the device (non-NULL rows, matched rows, missing rows whose key's bits are the
+//                      free-slot marker, overflow rows); rows seen are counted on the host.
+//   the missing keys   one open-addressing table of counted keys (counted_state.h), allocated at the first batch.
+// The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
+// under: what was merged in or read from a blob, and what the device part is folded into whenever the state is read.
+#include "keyed_state.h"
+
+namespace tgx {
+void launch_key_probe_reduce(const void *recs, uint64_t n, KeyProbeBuild *b, hipStream_t stream);
+void launch_key_probe_build_bitmap(const void *recs, uint64_t n, uint32_t *bits, uint64_t base, uint64_t range,
+                                   KeyProbeBuild *b, hipStream_t stream);
+void launch_key_probe_build_hash(const void *recs, uint64_t n, unsigned long long *keys, uint64_t mask, KeyProbeBuild *b,
+                                 hipStream_t stream);
+void launch_key_probe(const KeyProbeLaunch &L, int route, int n_tasks, int blocks, hipStream_t stream);
+
+namespace {
+
+constexpr uint64_t kMaxParentRecords = (uint64_t)1 << 40;
+
+// one task's state as the host sees it
+struct ProbeHost : KeyedEntries<uint64_t> {
+  uint64_t seen = 0, non_null = 0, matched = 0, overflow_rows = 0;
+  // the set the counts were taken under (`known`: there is one)
+  bool known = false;
+  uint64_t parent_keys = 0, parent_digest = 0;
+  bool holds_counts() const { return seen != 0 || size() != 0; }
+  bool same_parent(const ProbeHost &o) const { return parent_keys == o.parent_keys && parent_digest == o.parent_digest; }
+};
+
+struct NoRange {};
+
+struct ProbeKind {
+  typedef KeyProbeTask Task;
+  typedef ProbeHost Host;
+  typedef NoRange Range;
+  static constexpr bool kRanged = false;
+  static constexpr int kKind = TGX_CHECK_KEY_PROBE;
+  static constexpr const char *kDiffers = "parent sets";
+  static constexpr uint32_t kMagic = 0x4252504b;  // "KPRB"
+
+  static const std::vector<KeyProbeTask> &tasks(const tgx_plan *plan) { return plan->key_probes; }
+  static size_t words(const KeyProbeTask &) { return kKeyProbeWords; }
+  static NoRange range_identity() { return NoRange(); }
+  static ProbeHost fresh(const KeyProbeTask &) { return ProbeHost(); }
+  static size_t shape(const ProbeHost &) { return 0; }  // (the sets' identities: ProbeCheck::merge_from)
+  // the counters; the table's entries follow in gather_extra
+  static ProbeHost from_device(const KeyProbeTask &, int64_t rows, const NoRange &, const unsigned long long *w) {
+    ProbeHost d;
+    d.seen = (uint64_t)rows;
+    d.non_null = w[kKpNonNull];
+    d.matched = w[kKpMatched];
+    d.overflow_rows = w[kKpOverflow];
+    if (w[kKpMarker]) {
+      d.kind = kIntKeys;
+      d.ints[(int64_t)kEmptyKey] = w[kKpMarker];
+    }
+    return d;
+  }
+  static void merge_host(ProbeHost &a, const ProbeHost &b) {
+    a.seen += b.seen;
+    a.non_null += b.non_null;
+    a.matched += b.matched;
+    a.overflow_rows += b.overflow_rows;
+    a.add_entries(b);
+    if (!a.known && b.known) {
+      a.known = true;
+      a.parent_keys = b.parent_keys;
+      a.parent_digest = b.parent_digest;
+    }
+  }
+
+  // per task { u32 max_missing_keys, u32 0 (the plan's parameters), u32 known (the counts were taken under a set), u32 0,
+  //   u64 parent_keys, parent_digest, u64 seen, non_null, matched, overflow_rows, u64 n_entries,
+  //   n_entries x { i64 key, u64 count }, ascending by key }
+  static void write(const KeyProbeTask &t, const ProbeHost &h, Writer &w) {
+    w.pod(t.params);
+    w.pod((uint32_t)(h.known ? 1 : 0));
+    w.pod((uint32_t)0);
+    const uint64_t words[7] = {h.parent_keys, h.parent_digest, h.seen, h.non_null, h.matched, h.overflow_rows, h.size()};
+    w.pod(words);
+    keyed_write_entries(h, CountWire(), w);
+  }
+
+  static tgx_status read(const KeyProbeTask &t, ProbeHost &h, Reader &r, size_t k, tgx_error *err) {
+    tgx_key_probe_params p;
+    r.get(&p, sizeof(p));
+    const uint32_t known = r.pod<uint32_t>(), pad = r.pod<uint32_t>();
+    uint64_t words[7];
+    r.get(words, sizeof(words));
+    if (!r.ok) return TGX_OK;
+    if (p.max_missing_keys != t.params.max_missing_keys || p.reserved != t.params.reserved)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "KEY_PROBE task %zu: the blob was counted under other parameters (max_missing_keys %u) than the plan's "
+                  "(%u)", k, p.max_missing_keys, t.params.max_missing_keys);
+    const uint64_t seen = words[2], non_null = words[3], n = words[6];
+    if (known > 1 || pad != 0 || (!known && (words[0] != 0 || words[1] != 0 || seen != 0 || n != 0)))
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: parent set)", k);
+    uint64_t counted = 0;
+    TGX_TRY(keyed_read_entries("KEY_PROBE", "key", k, r, kIntKeys, n, 0, CountWire(), h, &counted, err));
+    if (!r.ok) return TGX_OK;
+    // matched + counted + overflow_rows == non_null <= seen
+    if (non_null > seen || !terms_make(non_null, {words[4], counted, words[5]}))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "malformed state blob (KEY_PROBE task %zu: matched + counted + overflow_rows != non_null)", k);
+    h.kind = n ? kIntKeys : kNoKeys;
+    h.known = known != 0;
+    h.parent_keys = words[0];
+    h.parent_digest = words[1];
+    h.seen = seen;
+    h.non_null = non_null;
+    h.matched = words[4];
+    h.overflow_rows = words[5];
+    return TGX_OK;
+  }
+};
+
+// the set of one task on the device
+struct ParentSet {
+  bool has = false;
+  int route = kKpRouteEmpty;
+  DevBuf buf;  // the bitmap's words or the table's keys
+  uint64_t base = 0, range = 0, mask = 0;
+  uint32_t has_marker = 0;
+  uint64_t keys = 0, digest = 0;
+};
+
+struct ProbeCheck final : CountedState<ProbeKind> {
+  const std::vector<KeyProbeTask> &tasks;
+  std::vector<ParentSet> parent;
+  bool fed = false;  // a batch with rows has been handed to tgx_update since the state was created or reset
+
+  explicit ProbeCheck(const tgx_plan *plan) : CountedState(plan), tasks(plan->key_probes), parent(plan->key_probes.size()) {}
+
+  void decode_slot(size_t, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
+    o.kind = kIntKeys;
+    o.ints[(int64_t)((const uint64_t *)h)[s]] += count;
+  }
+
+  // every task, read: host part + device part, under the identity of the set the state holds
+  tgx_status collect(tgx_state *st, std::vector<ProbeHost> *g, tgx_error *err) {
+    TGX_TRY(gather(st, g, err));
+    for (size_t k = 0; k < g->size(); k++) {
+      ProbeHost &h = (*g)[k];
+      if (parent[k].has && !h.known) {
+        h.known = true;
+        h.parent_keys = parent[k].keys;
+        h.parent_digest = parent[k].digest;
+      }
+    }
+    return TGX_OK;
+  }
+
+  tgx_status accepts(tgx_state *, int64_t nrows, tgx_error *err) override {
+    for (size_t k = 0; k < tasks.size(); k++)
+      if (!parent[k].has)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
+                    tasks[k].spec_index);
+    fed |= nrows > 0;
+    return TGX_OK;
+  }
+
+  tgx_status reset(tgx_state *st, tgx_error *err) override {
+    fed = false;
+    return CountedState::reset(st, err);
+  }
+
+  tgx_status set_parent(tgx_state *st, size_t k, const void *recs, uint64_t n, tgx_error *err) {
+    if (fed)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "spec %d: the parent set of a KEY_PROBE check is given before the state's first batch (or after "
+                  "tgx_state_reset)", tasks[k].spec_index);
+    if (n > kMaxParentRecords)
+      return fail(err, TGX_UNSUPPORTED, "spec %d: a parent set of %llu records is too large", tasks[k].spec_index,
+                  (unsigned long long)n);
+    if (n > 0 && !recs) return fail(err, TGX_INVALID_ARGUMENT, "device_records is NULL");
+    TGX_TRY(device_init(st, err));
+    ParentSet s;
+    s.has = true;
+    if (n > 0) {
+      ProfScope ps(st, "key_probe_build", n * 16);
+      DevBuf d_build;
+      HIP_TRY(d_build.reserve(sizeof(KeyProbeBuild)));
+      KeyProbeBuild b = {INT64_MAX, INT64_MIN, 0, 0, 0, 0};
+      HIP_TRY(hipMemcpyAsync(d_build.p, &b, sizeof(b), hipMemcpyHostToDevice, st->stream));
+      launch_key_probe_reduce(recs, n, d_build.as<KeyProbeBuild>(), st->stream);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));
+      // (unsigned: INT64_MIN and INT64_MAX together wrap the range to 0, which is not dense)
+      const uint64_t range = (uint64_t)b.max - (uint64_t)b.min + 1;
+      if (range != 0 && range <= 128 * n) {
+        s.route = kKpRouteBitmap;
+        s.base = (uint64_t)b.min;
+        s.range = range;
+        const size_t bytes = (size_t)((range + 31) / 32) * 4;
+        HIP_TRY(s.buf.reserve(bytes));
+        HIP_TRY(hipMemsetAsync(s.buf.p, 0, bytes, st->stream));
+        launch_key_probe_build_bitmap(recs, n, s.buf.as<uint32_t>(), s.base, s.range, d_build.as<KeyProbeBuild>(),
+                                      st->stream);
+      } else {
+        s.route = kKpRouteHash;
+        uint64_t slots = 2;
+        while (slots < 2 * n) slots <<= 1;
+        s.mask = slots - 1;
+        HIP_TRY(s.buf.reserve((size_t)slots * 8));
+        HIP_TRY(hipMemsetAsync(s.buf.p, 0xFF, (size_t)slots * 8, st->stream));  // (every slot: kEmptyKey)
+        launch_key_probe_build_hash(recs, n, s.buf.as<unsigned long long>(), s.mask, d_build.as<KeyProbeBuild>(),
+                                    st->stream);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));
+      s.has_marker = b.has_marker;
+      s.keys = b.keys;
+      s.digest = b.digest;
+    }
+    ProbeHost &h = host[k];
+    if (h.known && h.holds_counts() && (h.parent_keys != s.keys || h.parent_digest != s.digest))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "spec %d: the state holds counts taken under another parent set (%llu keys, digest %016llx) than the "
+                  "one given (%llu keys, digest %016llx)", tasks[k].spec_index, (unsigned long long)h.parent_keys,
+                  (unsigned long long)h.parent_digest, (unsigned long long)s.keys, (unsigned long long)s.digest);
+    h.known = true;
+    h.parent_keys = s.keys;
+    h.parent_digest = s.digest;
+    parent[k] = std::move(s);
+    return TGX_OK;
+  }
+
+  tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
+    if (nrows <= 0) return TGX_OK;
+    TGX_TRY(device_init(st, err));
+    table_cache_ok = false;
+    for (size_t k = 0; k < tasks.size(); k++) {
+      // (an Int64 view: update_validate refuses what is not widened to one)
+      if (dev[tasks[k].column].type != TGX_INT64)
+        return fail(err, TGX_UNSUPPORTED, "KEY_PROBE takes integer columns (%d)", dev[tasks[k].column].type);
+      if (!parent[k].has)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
+                    tasks[k].spec_index);
+      if (!table[k].live) TGX_TRY(open_table(st, k, tasks[k].params.max_missing_keys, 1, 0, err));
+    }
+    const uint64_t salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
+    for (int route = kKpRouteEmpty; route <= kKpRouteHash; route++) {
+      std::vector<size_t> slots;
+      for (size_t k = 0; k < tasks.size(); k++)
+        if (parent[k].route == route) slots.push_back(k);
+      for (size_t t0 = 0; t0 < slots.size(); t0 += kMaxKeyProbePerLaunch) {
+        const int n = (int)std::min<size_t>(kMaxKeyProbePerLaunch, slots.size() - t0);
+        KeyProbeLaunch L;
+        memset(&L, 0, sizeof(L));
+        uint64_t bytes = 0;
+        for (int i = 0; i < n; i++) {
+          const size_t k = slots[t0 + i];
+          const ParentSet &s = parent[k];
+          bytes += side_fill_x(L.cols[i], dev[tasks[k].column]);
+          KeyProbeSet &ds = L.sets[i];
+          ds.bits = route == kKpRouteBitmap ? s.buf.as<uint32_t>() : nullptr;
+          ds.keys = route == kKpRouteHash ? s.buf.as<unsigned long long>() : nullptr;
+          ds.base = s.base;
+          ds.range = s.range;
+          ds.mask = s.mask;
+          ds.has_marker = s.has_marker;
+          KeyProbeTable &dt = L.tables[i];
+          uint8_t *base = table[k].buf.as<uint8_t>();
+          dt.keys = (unsigned long long *)base;
+          dt.counts = (unsigned long long *)(base + table[k].counts_at());
+          dt.words = d_counts.as<unsigned long long>() + word_off[k];
+          dt.mask = table[k].slots - 1;
+          dt.salt = salt;
+        }
+        // 16 waves a workgroup and 96 KiB of LDS: one workgroup a CU
+        const int blocks = side_blocks(nrows, kKeyProbeBlock, g_ctx.n_cu, 1, n);
+        TGX_TRY(side_rows_fit("KEY_PROBE", nrows, blocks, err));
+        ProfScope ps(st, "key_probe", bytes);
+        launch_key_probe(L, route, n, blocks, st->stream);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    for (size_t k = 0; k < tasks.size(); k++) device_rows[k] += nrows;
+    return TGX_OK;
+  }
+
+  tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) override {
+    std::vector<ProbeHost> theirs, mine;
+    TGX_TRY(static_cast<ProbeCheck *>(of(src))->collect(src, &theirs, err));
+    TGX_TRY(collect(st, &mine, err));
+    for (size_t k = 0; k < theirs.size(); k++)
+      if (theirs[k].known && mine[k].known && !theirs[k].same_parent(mine[k]))
+        return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", kName, k,
+                    ProbeKind::kDiffers);
+    for (size_t k = 0; k < theirs.size(); k++) ProbeKind::merge_host(host[k], theirs[k]);
+    return TGX_OK;
+  }
+
+  tgx_status serialize(tgx_state *st, Writer &w, tgx_error *err) override {
+    std::vector<ProbeHost> g;
+    TGX_TRY(collect(st, &g, err));
+    w.pod(ProbeKind::kMagic);
+    w.pod((uint32_t)tasks.size());
+    for (size_t k = 0; k < g.size(); k++) ProbeKind::write(tasks[k], g[k], w);
+    return TGX_OK;
+  }
+
+  tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) override {
+    std::vector<ProbeHost> g;
+    TGX_TRY(collect(st, &g, err));
+    const ProbeHost &h = g[(size_t)slot];
+    r->total = (int64_t)h.seen;
+    r->non_null = (int64_t)h.non_null;
+    r->distinct = (int64_t)h.size();
+    r->matches = (int64_t)h.matched;
+    return TGX_OK;
+  }
+
+  // the task of spec `spec_index`, read: the head of tgx_key_probe_get and tgx_key_probe_entries
+  static tgx_status read_spec(const tgx_plan *plan, tgx_state *st, size_t spec_index, ProbeHost *out, uint32_t *route,
+                              tgx_error *err) {
+    size_t slot = 0;
+    TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_KEY_PROBE, kName, &slot, err, "bad arguments"));
+    ProbeCheck *c = static_cast<ProbeCheck *>(of(st));
+    std::vector<ProbeHost> g;
+    TGX_TRY(c->collect(st, &g, err));
+    *out = std::move(g[slot]);
+    if (route) *route = c->parent[slot].has ? (uint32_t)c->parent[slot].route : 0;
+    return TGX_OK;
+  }
+};
+
+}  // namespace
+
+tgx_status keyprobe_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err) {
+  const tgx_check_spec &sp = plan->specs[spec_index];
+  if (sp.column2 != -1)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %d: KEY_PROBE reads one column: column2 must be -1 (%d)", spec_index,
+                sp.column2);
+  KeyProbeTask t;
+  memset(&t, 0, sizeof(t));
+  t.column = sp.column;
+  t.spec_index = spec_index;
+  plan->key_probes.push_back(t);
+  *slot = (int)plan->key_probes.size() - 1;
+  return TGX_OK;
+}
+
+tgx_status keyprobe_plan_ready(const tgx_plan *plan, tgx_error *err) {
+  for (const KeyProbeTask &t : plan->key_probes)
+    if (!t.set)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parameters (tgx_plan_set_key_probe)",
+                  t.spec_index);
+  return TGX_OK;
+}
+
+void keyprobe_mark_columns(tgx_plan *plan) {
+  for (const KeyProbeTask &t : plan->key_probes) side_mark(plan, ProbeCheck::kIndex, t.column, true);
+}
+
+tgx_status keyprobe_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+  const int type = c.type;
+  if (refused_as_key(type))
+    return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE takes integer columns, not %s (type %d)", column,
+                type_name(type), type);
+  if (is_any_string(type) || type == TGX_DICT32_UTF8)
+    return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE takes integer columns, not strings (type %d)", column, type);
+  if (c.length > 0 && !c.values)
+    return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE reads the keys: a validity-only column has none", column);
+  return TGX_OK;
+}
+
+SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.empty() ? nullptr : new ProbeCheck(plan); }
+
+}  // namespace tgx
+
+using namespace tgx;
+
+extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                             tgx_error *err) try {
+  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
+  if (plan_has_state(plan))
+    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a KEY_PROBE check are fixed once a state of the plan exists");
+  if (p->max_missing_keys < 1 || p->max_missing_keys > TGX_KEY_PROBE_MAX_MISSING_KEYS)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_missing_keys must be 1 .. %d (%u)", spec_index,
+                (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
+  if (p->reserved != 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: reserved must be 0 (%u)", spec_index, p->reserved);
+  KeyProbeTask &t = plan->key_probes[slot];
+  t.params = *p;
+  t.set = true;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_set_parent(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                               const void *device_records, uint64_t n_records, tgx_error *err) try {
+  bind_thread();
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, "bad arguments"));
+  TGX_TRY(need_device(err));
+  return static_cast<ProbeCheck *>(ProbeCheck::of(st))->set_parent(st, slot, device_records, n_records, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                        tgx_key_probe_summary *out, tgx_error *err) try {
+  bind_thread();
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  uint32_t route = 0;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, &route, err));
+  memset(out, 0, sizeof(*out));
+  out->seen = h.seen;
+  out->non_null = h.non_null;
+  out->null_rows = h.seen - h.non_null;
+  out->matched = h.matched;
+  out->counted = h.counted();
+  out->overflow_rows = h.overflow_rows;
+  out->missing_rows = out->counted + out->overflow_rows;
+  out->missing_keys = h.size();
+  out->parent_keys = h.parent_keys;
+  out->parent_digest = h.parent_digest;
+  out->route = route;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                            tgx_key_probe_entry *entries, uint64_t cap, uint64_t *n_entries,
+                                            tgx_error *err) try {
+  bind_thread();
+  if (!n_entries) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  uint64_t n_bytes = 0;
+  TGX_TRY(counted_entries_sizes(h.size(), 0, entries, cap, n_entries, nullptr, 0, &n_bytes, err));
+  if (!entries) return TGX_OK;
+  size_t i = 0;
+  for (const auto &e : h.ints) entries[i++] = tgx_key_probe_entry{e.first, e.second};
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}

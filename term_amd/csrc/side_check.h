@@ -21,6 +21,9 @@ struct TGX_HIDDEN SideCheck {
   virtual ~SideCheck() {}
   // (the caller has waited for the stream)
   virtual tgx_status reset(tgx_state *st, tgx_error *err) = 0;
+  // may the state take a batch of `nrows` rows at all?  Asked by tgx_update before the batch is noted or run (a kind
+  // whose tasks need more than the plan gives them: KEY_PROBE's parent set)
+  virtual tgx_status accepts(tgx_state *, int64_t, tgx_error *) { return TGX_OK; }
   // one batch (device views of the plan's columns) through the tasks' kernels
   virtual tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) = 0;
   virtual tgx_status fill_result(tgx_state *st, int slot, tgx_result *r, tgx_error *err) = 0;
@@ -59,6 +62,7 @@ TGX_SIDE_KIND(valuecounts)
 TGX_SIDE_KIND(paircounts)
 TGX_SIDE_KIND(groupcounts)
 TGX_SIDE_KIND(groupsums)
+TGX_SIDE_KIND(keyprobe)
 #undef TGX_SIDE_KIND
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
@@ -66,6 +70,7 @@ tgx_status valuecounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupcounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupsums_plan_ready(const tgx_plan *plan, tgx_error *err);
+tgx_status keyprobe_plan_ready(const tgx_plan *plan, tgx_error *err);
 
 // in the order of the blob's sections
 inline constexpr SideKind kSideKinds[kNumSide] = {
@@ -85,6 +90,8 @@ inline constexpr SideKind kSideKinds[kNumSide] = {
      groupcounts_check_column, groupcounts_state_new, true},
     {TGX_CHECK_GROUP_SUMS, "GROUP_SUMS", groupsums_plan_add, groupsums_plan_ready, groupsums_mark_columns,
      groupsums_check_column, groupsums_state_new, true},
+    {TGX_CHECK_KEY_PROBE, "KEY_PROBE", keyprobe_plan_add, keyprobe_plan_ready, keyprobe_mark_columns,
+     keyprobe_check_column, keyprobe_state_new, false},
 };
 
 // where `kind` stands in kSideKinds (and in tgx_state::side, tgx_plan::side_on), or -1: not a kind of this file

@@ -343,6 +343,8 @@ extern "C" tgx_status tgx_update(const tgx_plan *plan, tgx_state *st, const tgx_
   BatchTraits traits;
   traits.retained = any_retained && !any_plain_host;
   TGX_TRY(update_validate(plan, st, columns, n_columns, &nrows, &traits, err));
+  for (auto &side : st->side)
+    if (side) TGX_TRY(side->accepts(st, nrows, err));
   if (nrows == 0) {  // an empty RecordBatch (streams interleave them): nothing to note, nothing to flush for
     st->batches++;
     return TGX_OK;

@@ -273,6 +273,10 @@ class CheckBuilder:
         constraint()"""
         return self.constraint(CrossTableSumConstraint(left_column, right_column))
 
+    def foreign_key(self, child_column, parent_column):
+        """pushes ForeignKeyConstraint::new(child, parent); a configured object goes through constraint()"""
+        return self.constraint(ForeignKeyConstraint(child_column, parent_column))
+
     def has_consistent_data_type(self, column, threshold):
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
@@ -505,6 +509,51 @@ class CrossTableSumConstraint:
             if isinstance(v[k], str):
                 v[k] = float(v[k])
         return v
+
+
+class ForeignKeyConstraint:
+    """constraints/foreign_key.rs:78-117, one method per builder call of the reference: every non-NULL value of
+    `child_column` is a value of `parent_column`, both qualified as "table.column".  The parent's column is walked once
+    under a DISTINCT spec, its key set handed to a KEY_PROBE spec over the child's column, and the child walked once:
+    integer keys only (any other column type is the constraint's own error, which says it is not on the GPU path).  It
+    needs ValidationSuite.run(table, tables={name: table})"""
+
+    def __init__(self, child_column, parent_column):
+        self.spec = {"type": "foreign_key", "child_column": child_column, "parent_column": parent_column,
+                     "allow_nulls": False, "use_left_join": True, "max_violations_reported": 100,
+                     "max_missing_keys": 10000}
+
+    def allow_nulls(self, allow):
+        self.spec["allow_nulls"] = bool(allow)
+        return self
+
+    def use_left_join(self, use_left_join):
+        """accepted as the reference accepts it; there is one strategy here"""
+        self.spec["use_left_join"] = bool(use_left_join)
+        return self
+
+    def max_violations_reported(self, n):
+        self.spec["max_violations_reported"] = int(n)
+        return self
+
+    def max_missing_keys(self, n):
+        """this layer's own: the missing keys the child's table on the device is sized for (1 .. 65 536, default
+        10 000).  Rows beyond it are counted as overflow rows: the verdict and the metric stand, and `unique` reads
+        "at least n" """
+        self.spec["max_missing_keys"] = int(n)
+        return self
+
+    def name(self): return "foreign_key"
+    def child_column(self): return self.spec["child_column"]
+    def parent_column(self): return self.spec["parent_column"]
+
+    def verdict_from_counts(self, counts):
+        """the verdict on given counts (no device): a dict {"null_rows", "missing_rows", "overflow_rows",
+        "missing_keys", "entries": [[key, count], ..] ascending by key, "examples": bool}"""
+        out, err = C.c_char_p(), _Error()
+        _host_check(_host().tgx_host_foreign_key_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
+                                                      C.byref(out), C.byref(err)), err)
+        return json.loads(_take(out))
 
 
 class NumericValidation:
@@ -1188,6 +1237,7 @@ def _host():
         L.tgx_host_run_suite_tables_json.argtypes = [C.c_char_p, C.POINTER(_HostTable), C.c_size_t,
                                                      C.POINTER(C.c_char_p), E]
         L.tgx_host_cross_table_sum_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_foreign_key_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_free.argtypes = [C.c_void_p]
         L.tgx_host_free.restype = None
         _HOST = L

@@ -110,6 +110,7 @@ VALUE_COUNTS_MAGIC = 0x544E4356  # 'VCNT'
 PAIR_COUNTS_MAGIC = 0x544E4350  # 'PCNT'
 GROUP_COUNTS_MAGIC = 0x544E4347  # 'GCNT'
 GROUP_SUMS_MAGIC = 0x4D555347  # 'GSUM'
+KEY_PROBE_MAGIC = 0x4252504B  # 'KPRB'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -309,8 +310,29 @@ def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=N
     return out
 
 
+def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0, overflow_rows=0, parent=None,
+                    ordered=True, non_null=None):
+    """a KEY_PROBE task: the plan's parameter, the identity of the parent set the counts were taken under (`parent`:
+    (parent_keys, parent_digest), or None for a state that knows of none), the counters and the entries of `missing`
+    (key -> rows).  non_null defaults to what the invariant makes it -- matched + sum(missing) + overflow_rows -- and seen
+    to non_null + nulls.  `ordered=False` keeps the entries in the order given (for a blob that is to be refused)."""
+    items = list(missing.items()) if hasattr(missing, "items") else list(missing)
+    if ordered:
+        items.sort(key=lambda kv: kv[0])
+    if non_null is None:
+        non_null = matched + sum(c for _, c in items) + overflow_rows
+    if seen is None:
+        seen = non_null + nulls
+    keys, digest = parent if parent is not None else (0, 0)
+    out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, 0, keys, digest, seen, non_null,
+                      matched, overflow_rows, len(items))
+    for k, c in items:
+        out += struct.pack("<qQ", k, c)
+    return out
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=()):
+         value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=(), key_probes=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
@@ -329,5 +351,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", GROUP_COUNTS_MAGIC, len(group_counts)) + b"".join(group_counts)
     if group_sums:
         tail += struct.pack("<II", GROUP_SUMS_MAGIC, len(group_sums)) + b"".join(group_sums)
+    if key_probes:
+        tail += struct.pack("<II", KEY_PROBE_MAGIC, len(key_probes)) + b"".join(key_probes)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
