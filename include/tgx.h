@@ -395,7 +395,11 @@ typedef enum tgx_check_kind {
    * sets differ (parent_keys, parent_digest) do not merge.  A deserialized state holds no set: it can be read and merged,
    * and takes batches again once tgx_key_probe_set_parent has given it a set with the same (parent_keys, parent_digest).
    * Read with tgx_key_probe_get and tgx_key_probe_entries; tgx_result carries total = rows seen, non_null = non-NULL
-   * rows, matches = matched rows, distinct = missing keys held. */
+   * rows, matches = matched rows, distinct = missing keys held.
+   * Two further modes of a spec, each with a plan call of its own: COUNTED (tgx_plan_set_key_probe_counted: the set keeps
+   * the parent's multiplicities and the state sums them over the matched rows -- the join's matched pairs,
+   * tgx_key_probe_pairs_get) and ROWS (tgx_plan_set_key_probe_rows: the spec gathers its column as {key, 1} records for
+   * such a set instead of probing it, tgx_key_probe_rows_get). */
   TGX_CHECK_KEY_PROBE = 19
 } tgx_check_kind;
 
@@ -704,6 +708,20 @@ typedef struct tgx_key_probe_params {
   uint32_t reserved;
 } tgx_key_probe_params;
 tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *params, tgx_error *err);
+/* The same bound, and the spec becomes COUNTED: its parent set keeps how often each key occurs in the parent (the
+ * records' counts), and the state also sums the multiplicities of the matched rows' keys -- the matched PAIRS, COUNT(*)
+ * of the inner join, which the reference's JoinCoverageConstraint asks for (TG/constraints/join_coverage.rs).  A spec
+ * takes one of the two calls: the other one on the same spec afterwards is TGX_INVALID_ARGUMENT.  See
+ * tgx_key_probe_pairs_get. */
+tgx_status tgx_plan_set_key_probe_counted(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *params,
+                                          tgx_error *err);
+/* The spec GATHERS its column instead of probing it: every non-NULL key of every batch becomes a 16-byte {key, 1}
+ * record in device memory, read with tgx_key_probe_rows_get -- the parent side of a counted probe when the parent's
+ * keys repeat (a TGX_CHECK_DISTINCT export knows a key as seen once or more than once, not how often; duplicate
+ * records of a counted set add up).  Such a spec takes no parent set and no other tgx_plan_set_key_probe* call; its
+ * state costs 16 bytes a row it has seen, tgx_state_reset empties it, and a state that has gathered rows does not merge
+ * or serialize (TGX_UNSUPPORTED).  tgx_key_probe_get gives seen, non_null and null_rows. */
+tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_error *err);
 
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
@@ -1016,7 +1034,8 @@ tgx_status tgx_group_sums_entries(const tgx_plan *plan, tgx_state *state, size_t
 /* ---- key probe (TGX_CHECK_KEY_PROBE; TG/constraints/foreign_key.rs:152-176) ----------------------------------------- */
 /* The parent's key set of spec `spec_index` of `state`: n_records 16-byte {uint64 key, uint64 count} records in device
  * memory -- what tgx_distinct_export(.., world = 1, ..) hands out for a numeric key set, the extra record of the all-ones
- * key included.  Counts are ignored, duplicate records are allowed, n_records == 0 is a valid, empty set.  The call
+ * key included.  Counts are ignored (by a plain spec; a counted one: below), duplicate records are allowed,
+ * n_records == 0 is a valid, empty set.  The call
  * builds the state's own probe structure (a bitmap over [MIN, MAX] when MAX - MIN + 1 <= 128 * n_records, else a hash
  * table of the smallest power of two >= 2 * n_records slots) and has waited for it when it returns: the caller's
  * records are not kept.  Allowed only on a state that has seen no batch since it was created or reset
@@ -1050,6 +1069,32 @@ typedef struct tgx_key_probe_entry {
  * be NULL for a size query; a non-NULL buffer that is too small is TGX_INVALID_ARGUMENT with nothing copied. */
 tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *state, size_t spec_index,
                                  tgx_key_probe_entry *entries, uint64_t cap, uint64_t *n_entries, tgx_error *err);
+/* A COUNTED spec (tgx_plan_set_key_probe_counted).  tgx_key_probe_set_parent uses the records' counts: duplicate records
+ * of one key add up, as a merge of two exports would; a record whose count is 0 is TGX_INVALID_ARGUMENT and a set whose
+ * counts sum to 2^63 or more is TGX_UNSUPPORTED, and the state is then left without a set.  The routes are 3, an array of
+ * 64-bit counts over [MIN, MAX] when MAX - MIN + 1 (unsigned, not 0) <= 4 * n_records, and 4, a hash table of the smallest
+ * power of two >= 2 * n_records 16-byte {key, count} slots.  The three calls above work unchanged (`route` reads 3 or 4,
+ * 0 for none or empty); the set's identity, which blobs carry and merges compare, is (parent_keys, parent_digest,
+ * parent_rows, parent_count_digest).
+ * For L LEFT JOIN R ON L.l = R.r with R's DISTINCT export as the set and L.l as the column, pairs is
+ * SUM(CASE WHEN R.r IS NOT NULL ..) and join_rows is COUNT(*); pairs is the same number from either side.
+ * pairs is exact whenever it is reported: the library keeps the upper bound sum over batches of max_count * rows in
+ * checked arithmetic, and tgx_update refuses (TGX_UNSUPPORTED, nothing noted or run, the state stays usable) the batch
+ * that would carry the bound past 2^64 - 1; merges and blobs add pairs under the same check.
+ * TGX_INVALID_ARGUMENT on a plain spec. */
+typedef struct tgx_key_probe_pairs {
+  uint64_t pairs;               /* the sum over matched rows of the key's multiplicity in the set */
+  uint64_t join_rows;           /* pairs + missing_rows + null_rows: COUNT(*) of the outer join from this side */
+  uint64_t parent_rows;         /* the sum of the set's counts: the parent's non-NULL rows */
+  uint64_t parent_count_digest; /* the wrapping sum of count * mix64(key ^ 0xc2b2ae3d27d4eb4f) over the records */
+  uint64_t max_count;           /* the largest multiplicity of the set */
+} tgx_key_probe_pairs;
+tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_key_probe_pairs *out,
+                                   tgx_error *err);
+/* The records a rows spec (tgx_plan_set_key_probe_rows) has gathered: *n_records {key, 1} records in device memory the
+ * state owns, valid until its next batch or reset; in no particular order.  TGX_INVALID_ARGUMENT on any other spec. */
+tgx_status tgx_key_probe_rows_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, const void **device_records,
+                                  uint64_t *n_records, tgx_error *err);
 
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous
@@ -1140,7 +1185,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -194,6 +194,23 @@ tgx_status tgx_host_cross_table_sum_json(const char *constraint_json, const char
 tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *counts_json, char **out_json,
                                      tgx_error *err);
 
+/* The verdict of a "join_coverage" constraint
+ *   {"type": "join_coverage", "left_table": "orders", "right_table": "customers", "join_keys": [["customer_id", "id"]],
+ *    "expected_match_rate": 1.0, "coverage_type": "left" | "right" | "bidirectional", "distinct_only": false,
+ *    "max_examples_reported": 100, "max_missing_keys": 10000}                       (TG/constraints/join_coverage.rs)
+ * on given counts; needs no device.  (Within a suite run over several tables the far side's column is gathered as
+ * {key, 1} records and handed to a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's column.)
+ * counts_json: {"left": {"pairs": n, "join_rows": n}, "right": {..}, "left_distinct": n, "examples": {"missing_keys": n,
+ * "null_rows": n, "overflow_rows": n}} -- "left": the left column probed against the right side's counted set as
+ * tgx_key_probe_pairs_get gives it, "right": the other way round, "left_distinct": COUNT(DISTINCT left column),
+ * "examples": the left column's missing keys, NULL rows and overflow rows against the right side's set.  A side the
+ * coverage type reads must be there, and "examples" when the check fails with max_examples_reported > 0.
+ * Returns {"status", "metric", "message", "config": {the constraint as the host layer read it}}.  A constraint without
+ * join keys, with more than one key pair, RightCoverage with distinct_only and a join without rows are
+ * TGX_INVALID_ARGUMENT with the constraint's error text. */
+tgx_status tgx_host_join_coverage_json(const char *constraint_json, const char *counts_json, char **out_json,
+                                       tgx_error *err);
+
 void tgx_host_free(char *s);
 
 #ifdef __cplusplus

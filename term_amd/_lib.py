@@ -237,6 +237,12 @@ class KeyProbeEntry(C.Structure):
     _fields_ = [("value", C.c_int64), ("count", C.c_uint64)]
 
 
+class KeyProbePairs(C.Structure):
+    """tgx_key_probe_pairs (include/tgx.h)"""
+    _fields_ = [("pairs", C.c_uint64), ("join_rows", C.c_uint64), ("parent_rows", C.c_uint64),
+                ("parent_count_digest", C.c_uint64), ("max_count", C.c_uint64)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -380,6 +386,10 @@ def lib():
         L.tgx_group_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
                                                C.POINTER(C.c_int32), E]
         L.tgx_plan_set_key_probe.argtypes = [vp, sz, C.POINTER(KeyProbeParams), E]
+        L.tgx_plan_set_key_probe_counted.argtypes = [vp, sz, C.POINTER(KeyProbeParams), E]
+        L.tgx_plan_set_key_probe_rows.argtypes = [vp, sz, E]
+        L.tgx_key_probe_rows_get.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(u64), E]
+        L.tgx_key_probe_pairs_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbePairs), E]
         L.tgx_key_probe_set_parent.argtypes = [vp, vp, sz, vp, u64, E]
         L.tgx_key_probe_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeSummary), E]
         L.tgx_key_probe_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), E]
@@ -835,6 +845,19 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_key_probe(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_key_probe_counted(self, spec_index, max_missing_keys=10000, reserved=0):
+        """tgx_plan_set_key_probe_counted: the same bound, and the spec's parent set keeps the parent's multiplicities
+        (State.key_probe_pairs).  A spec takes one of the two calls"""
+        p = KeyProbeParams(max_missing_keys, reserved)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_counted(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_key_probe_rows(self, spec_index):
+        """tgx_plan_set_key_probe_rows: the spec gathers its column's non-NULL keys as {key, 1} records
+        (State.key_probe_rows): the parent side of a counted probe when the parent's keys repeat"""
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_rows(self.h, spec_index, C.byref(err)), err)
+
     def set_pair_counts(self, spec_index, x=None, y=None, max_pairs=10000, max_value_bytes=256):
         """tgx_plan_set_pair_counts: the bounds and the sides of a PAIR_COUNTS spec (before the plan's first state).  A
         side is None or "value" (a string column: PAIR_SIDE_VALUE), "range" (a numeric column: the spec is in its range
@@ -1155,6 +1178,20 @@ class State:
         _check(L.tgx_key_probe_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), C.byref(err)), err)
         summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
         return summary, {e.value: e.count for e in entries[:n.value]}
+
+    def key_probe_rows(self, spec_index):
+        """tgx_key_probe_rows_get: (device pointer or None, n_records) of a rows spec's {key, 1} records"""
+        ptr, n, err = C.c_void_p(), C.c_uint64(), _Error()
+        _check(lib().tgx_key_probe_rows_get(self.plan.h, self.h, spec_index, C.byref(ptr), C.byref(n), C.byref(err)), err)
+        return ptr.value, n.value
+
+    def key_probe_pairs(self, spec_index):
+        """tgx_key_probe_pairs_get: dict(pairs, join_rows, parent_rows, parent_count_digest, max_count) of a counted
+        KEY_PROBE spec"""
+        out = KeyProbePairs()
+        err = _Error()
+        _check(lib().tgx_key_probe_pairs_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return {name: getattr(out, name) for name, _ in KeyProbePairs._fields_}
 
     def pair_range(self, spec_index):
         """tgx_pair_range_get: dict(seen, both_non_null, n, non_finite, min, max) of a spec in its range phase"""

@@ -733,6 +733,67 @@ extern "C" tgx_status tgx_host_cross_table_sum_json(const char *constraint_json,
   }
 }
 
+extern "C" tgx_status tgx_host_join_coverage_json(const char *constraint_json, const char *counts_json, char **out_json,
+                                                  tgx_error *err) {
+  if (!constraint_json || !counts_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    auto c = std::dynamic_pointer_cast<JoinCoverageConstraint>(constraint_from_json_text(constraint_json));
+    if (!c) return hfail(err, TGX_INVALID_ARGUMENT, "not a join_coverage constraint");
+    json::Value v;
+    std::string perr;
+    if (!json::parse(counts_json, &v, &perr) || !v.is(json::Value::Object))
+      return hfail(err, TGX_INVALID_ARGUMENT, "counts JSON: " + (perr.empty() ? std::string("not an object") : perr));
+    c->validate();
+    JoinCoverageCounts k;
+    auto side = [&](const char *name, JoinCoverageCounts::Side *s) {
+      const json::Value *o = v.get(name);
+      if (!o) return;
+      if (!o->is(json::Value::Object)) throw TermError{TermError::Internal, "counts JSON: a side is an object"};
+      s->known = true;
+      s->pairs = o->get_u64("pairs", 0);
+      s->join_rows = o->get_u64("join_rows", 0);
+      if (s->pairs > s->join_rows)
+        throw TermError{TermError::Internal, "counts JSON: join_rows is pairs + missing_rows + null_rows"};
+    };
+    side("left", &k.left);
+    side("right", &k.right);
+    k.left_distinct = v.get_u64("left_distinct", 0);
+    if (const json::Value *e = v.get("examples")) {
+      if (!e->is(json::Value::Object)) throw TermError{TermError::Internal, "counts JSON: examples is an object"};
+      k.examples_known = true;
+      k.missing_keys = e->get_u64("missing_keys", 0);
+      k.null_rows = e->get_u64("null_rows", 0);
+      k.overflow_rows = e->get_u64("overflow_rows", 0);
+    }
+    const ConstraintResult cr = c->verdict(k);
+    std::string o =
+        std::string("{\"status\": \"") +
+        (cr.status == ConstraintStatus::Success ? "success" : cr.status == ConstraintStatus::Failure ? "failure" : "skipped") +
+        "\", \"metric\": " + (cr.metric ? json_f64(*cr.metric) : "null") + ", \"message\": " +
+        (cr.message ? json::quote(*cr.message) : "null") + ", \"config\": {\"name\": " + json::quote(c->name()) +
+        ", \"left_table\": " + json::quote(c->left_table()) + ", \"right_table\": " + json::quote(c->right_table()) +
+        ", \"join_keys\": [";
+    for (size_t i = 0; i < c->join_keys().size(); i++)
+      o += std::string(i ? ", " : "") + "[" + json::quote(c->join_keys()[i].first) + ", " +
+           json::quote(c->join_keys()[i].second) + "]";
+    o += std::string("], \"expected_match_rate\": ") + json_f64(c->expected_match_rate()) + ", \"coverage_type\": \"" +
+         (c->coverage() == CoverageType::LeftCoverage ? "left" : c->coverage() == CoverageType::RightCoverage ? "right" : "bidirectional") +
+         "\", \"distinct_only\": " + (c->distinct() ? "true" : "false") + ", \"max_examples_reported\": " +
+         std::to_string(c->examples_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) + "}}";
+    *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
 extern "C" tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *counts_json, char **out_json,
                                                 tgx_error *err) {
   if (!constraint_json || !counts_json || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");

@@ -1,0 +1,262 @@
+// join_coverage.cpp -- JoinCoverageConstraint (TG/constraints/join_coverage.rs).  The reference runs one or two outer
+// joins whose rows nobody reads (:181-286):
+//   SELECT COUNT(*) [or COUNT(DISTINCT L.l)] AS total, SUM(CASE WHEN R.r IS NOT NULL THEN 1 ELSE 0 END) AS matched
+//   FROM L LEFT JOIN R ON L.l = R.r
+// and match_rate = matched / total; RightCoverage is the same with the sides swapped, BidirectionalCoverage the LEAST of
+// the two rates.  COUNT(*) over a join counts matched PAIRS: with m_R(k) the rows of R that hold key k,
+//   matched = sum over rows of L of m_R(l) = pairs,   total = pairs + missing rows + NULL rows = join_rows
+// Here the far side is walked once under a TGX_CHECK_KEY_PROBE spec that gathers its non-NULL keys as {key, 1} records
+// (tgx_plan_set_key_probe_rows: a DISTINCT export knows a key as seen once or more than once, not how often), the
+// records go into a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's column, where records of one key add up, and
+// the near side is walked once.  Only the walks the answer needs are run: Left walks R, then L; Right walks L, then R,
+// and for the examples of a failing check R again and a plain probe of L; Bidirectional walks R, then L (the probe, and
+// the gathering for the other direction, in one plan: the column crosses HBM once), then R.  distinct_only adds a
+// DISTINCT spec on L.l to L's plan.
+// One integer key pair only: composite keys and every other column type are the constraint's own error, so the caller
+// can hand the constraint to the stock path.
+#include <stdio.h>
+#include <string.h>
+
+#include "term_guard.h"
+
+namespace term_guard {
+
+namespace {
+
+[[noreturn]] void evaluation_error(const std::string &msg) {
+  throw TermError{TermError::ConstraintEvaluation, "'join_coverage': " + msg};
+}
+[[noreturn]] void query_failed(const std::string &why) {  // (:340-345)
+  evaluation_error("Join coverage query failed: " + why);
+}
+
+struct Handles {
+  tgx_plan *plan = nullptr;
+  tgx_state *state = nullptr;
+  Handles() = default;
+  Handles(const Handles &) = delete;
+  Handles &operator=(const Handles &) = delete;
+  ~Handles() {
+    if (state) tgx_state_destroy(state);
+    if (plan) tgx_plan_destroy(plan);
+  }
+};
+
+const char *off_path_type(int type) {
+  switch (type) {
+    case TGX_FLOAT64: return "Float64";
+    case TGX_FLOAT32: return "Float32";
+    case TGX_UINT64: return "UInt64";
+    case TGX_BOOL: return "Boolean";
+    case TGX_UTF8: return "Utf8";
+    case TGX_LARGE_UTF8: return "LargeUtf8";
+    case TGX_UTF8_VIEW: return "Utf8View";
+    case TGX_DICT32_UTF8: return "Dictionary<Int32, Utf8>";
+    default: return nullptr;
+  }
+}
+
+// one side of the join: its table and key column, with the reference's planning / schema errors; integer keys only
+struct Side {
+  const Table *table = nullptr;
+  int column = -1;
+};
+Side side_of(const Context &ctx, const std::string &table_name, const std::string &column) {
+  Side s;
+  s.table = ctx.table(table_name);
+  if (!s.table) query_failed("Error during planning: table 'datafusion.public." + table_name + "' not found");
+  for (size_t i = 0; i < s.table->column_names.size(); i++)
+    if (s.table->column_names[i] == column) s.column = (int)i;
+  if (s.column < 0) query_failed("Schema error: No field named " + table_name + "." + column + ".");
+  for (const Batch &b : s.table->batches)
+    if ((size_t)s.column < b.columns.size())
+      if (const char *name = off_path_type(b.columns[s.column].type))
+        evaluation_error("column '" + table_name + "." + column + "' is a " + name +
+                         " column: join keys of that type are not on the GPU path (TGX_CHECK_KEY_PROBE takes integer keys)");
+  return s;
+}
+
+std::string percent(double rate) {  // {:.2} of rate * 100.0
+  char buf[64];
+  snprintf(buf, sizeof(buf), "%.2f", rate * 100.0);
+  return buf;
+}
+
+// the device side of one evaluation
+struct Walks {
+  tgx_error err;
+  Walks() { memset(&err, 0, sizeof(err)); }
+  void check(tgx_status s) {
+    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
+  }
+
+  // `side` gathered: one {key, 1} record a non-NULL row.  (The records stay the state's until its next call: `h` lives
+  // as long as they are read)
+  void key_set(const Side &side, Handles &h, const void **records, uint64_t *n_records) {
+    tgx_check_spec spec;
+    memset(&spec, 0, sizeof(spec));
+    spec.kind = TGX_CHECK_KEY_PROBE;
+    spec.column = side.column;
+    spec.column2 = -1;
+    check(tgx_plan_create(&spec, 1, &h.plan, &err));
+    check(tgx_plan_set_key_probe_rows(h.plan, 0, &err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &err));
+    for (const Batch &b : side.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &err));
+    check(tgx_key_probe_rows_get(h.plan, h.state, 0, records, n_records, &err));
+  }
+
+  // `near` walked once against the set of `records`: a counted probe (or a plain one); in the same plan, with
+  // `distinct` a DISTINCT spec on the column, whose count goes there, and with `own_records` a spec that gathers the
+  // column for the other direction
+  void probe(const Side &near, const void *records, uint64_t n_records, bool counted, uint32_t max_missing_keys,
+             Handles &h, tgx_key_probe_summary *summary, tgx_key_probe_pairs *pairs, uint64_t *distinct,
+             const void **own_records, uint64_t *own_n) {
+    tgx_check_spec specs[3];
+    memset(specs, 0, sizeof(specs));
+    size_t n = 1, gathers = 0, counts_distinct = 0;
+    specs[0].kind = TGX_CHECK_KEY_PROBE;
+    if (own_records) specs[gathers = n++].kind = TGX_CHECK_KEY_PROBE;
+    if (distinct) specs[counts_distinct = n++].kind = TGX_CHECK_DISTINCT;
+    for (size_t i = 0; i < n; i++) {
+      specs[i].column = near.column;
+      specs[i].column2 = -1;
+    }
+    check(tgx_plan_create(specs, n, &h.plan, &err));
+    const tgx_key_probe_params params = {max_missing_keys, 0};
+    check(counted ? tgx_plan_set_key_probe_counted(h.plan, 0, &params, &err)
+                  : tgx_plan_set_key_probe(h.plan, 0, &params, &err));
+    if (own_records) check(tgx_plan_set_key_probe_rows(h.plan, gathers, &err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &err));
+    check(tgx_key_probe_set_parent(h.plan, h.state, 0, records, n_records, &err));
+    for (const Batch &b : near.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &err));
+    check(tgx_key_probe_get(h.plan, h.state, 0, summary, &err));
+    if (counted) check(tgx_key_probe_pairs_get(h.plan, h.state, 0, pairs, &err));
+    if (distinct) {
+      tgx_result results[3];
+      memset(results, 0, sizeof(results));
+      check(tgx_finalize(h.plan, h.state, results, n, &err));
+      *distinct = (uint64_t)results[counts_distinct].distinct;
+    }
+    if (own_records) check(tgx_key_probe_rows_get(h.plan, h.state, gathers, own_records, own_n, &err));
+  }
+};
+
+}  // namespace
+
+ConstraintResult JoinCoverageConstraint::evaluate(const Inputs &) const {
+  throw TermError{TermError::Internal, "join_coverage reads the tables of the context, not the suite's fused plan"};
+}
+
+void JoinCoverageConstraint::validate() const {
+  // :165-176, then :181-188
+  if (auto e = validate_identifier(left_)) throw *e;
+  if (auto e = validate_identifier(right_)) throw *e;
+  for (const auto &k : keys_) {
+    if (auto e = validate_identifier(k.first)) throw *e;
+    if (auto e = validate_identifier(k.second)) throw *e;
+  }
+  if (keys_.empty()) evaluation_error("No join keys specified. Use .on() or .on_multiple() to set join keys");
+  if (keys_.size() > 1)
+    evaluation_error("a join on " + std::to_string(keys_.size()) + " key pairs (" + left_ + "." + keys_[0].first + ", " +
+                     left_ + "." + keys_[1].first + ", ..) is not on the GPU path: TGX_CHECK_KEY_PROBE takes one integer "
+                     "key column");
+  if (type_ == CoverageType::RightCoverage && distinct_only_)
+    evaluation_error("distinct_only with RightCoverage counts the keys common to both sides (COUNT(DISTINCT " + left_ + "." +
+                     keys_[0].first + ") over the right join's rows): that is not on the GPU path");
+  if (max_missing_keys_ < 1 || max_missing_keys_ > TGX_KEY_PROBE_MAX_MISSING_KEYS)
+    evaluation_error("max_missing_keys must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_MISSING_KEYS) + " (" +
+                     std::to_string(max_missing_keys_) + ")");
+}
+
+// :327-421
+ConstraintResult JoinCoverageConstraint::verdict(const JoinCoverageCounts &c) const {
+  const bool left = type_ != CoverageType::RightCoverage, right = type_ != CoverageType::LeftCoverage;
+  if ((left && !c.left.known) || (right && !c.right.known))
+    throw TermError{TermError::Internal, "join_coverage: the counts of a side the coverage type reads are missing"};
+  double rate = 0.0;
+  bool first = true;
+  auto take = [&](uint64_t matched, uint64_t total) {
+    // (the reference divides NULL by zero here and then reads a NULL slot's value)
+    if (total == 0) evaluation_error("the join of '" + left_ + "' and '" + right_ + "' has no rows: there is no match rate");
+    const double r = (double)matched / (double)total;
+    rate = first ? r : std::min(rate, r);  // LEAST
+    first = false;
+  };
+  // distinct_only: COUNT(DISTINCT L.l) under the same numerator, so the rate can exceed 1; Bidirectional ignores it
+  if (left) take(c.left.pairs, type_ == CoverageType::LeftCoverage && distinct_only_ ? c.left_distinct : c.left.join_rows);
+  if (right) take(c.right.pairs, c.right.join_rows);
+  if (rate >= expected_) return ConstraintResult::success_with_metric(rate);
+
+  const char *arrow = type_ == CoverageType::LeftCoverage ? " -> " : type_ == CoverageType::RightCoverage ? " <- " : " <-> ";
+  std::string message = "Join coverage constraint failed: " + left_ + arrow + right_ + " coverage is " + percent(rate) +
+                        "% (expected: " + percent(expected_) + "%)";
+  // the examples: SELECT DISTINCT L.l FROM L LEFT JOIN R .. WHERE R.r IS NULL LIMIT n, always from the left side; a NULL
+  // is one distinct value (:289-324, :386-400)
+  if (max_examples_ > 0) {
+    if (!c.examples_known)
+      throw TermError{TermError::Internal, "join_coverage: a failing check with examples needs the left side's missing keys"};
+    const uint64_t found = c.missing_keys + (c.null_rows > 0 ? 1 : 0), n = std::min<uint64_t>(max_examples_, found);
+    if (n > 0)
+      message += std::string(" (") + (c.overflow_rows > 0 && n < max_examples_ ? "at least " : "") + std::to_string(n) +
+                 " unmatched examples found)";
+  }
+  return ConstraintResult::failure_with_metric(rate, message);
+}
+
+ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) const {
+  validate();
+  const Side L = side_of(ctx, left_, keys_[0].first), R = side_of(ctx, right_, keys_[0].second);
+  Walks w;
+  w.check(tgx_init(nullptr, &w.err));
+
+  JoinCoverageCounts counts;
+  tgx_key_probe_summary s;
+  tgx_key_probe_pairs p;
+  memset(&p, 0, sizeof(p));
+  auto note_examples = [&](const tgx_key_probe_summary &of_left) {
+    counts.examples_known = true;
+    counts.missing_keys = of_left.missing_keys;
+    counts.null_rows = of_left.null_rows;
+    counts.overflow_rows = of_left.overflow_rows;
+  };
+  const void *records = nullptr, *left_records = nullptr;
+  uint64_t n_records = 0, n_left = 0;
+  Handles r_set, l_walk, r_walk, l_set, l_plain;
+  if (type_ != CoverageType::RightCoverage) {
+    // R's rows, then L once: the probe, L's DISTINCT where distinct_only reads it, L's rows for the other direction
+    const bool both = type_ == CoverageType::BidirectionalCoverage;
+    w.key_set(R, r_set, &records, &n_records);
+    w.probe(L, records, n_records, true, max_missing_keys_, l_walk, &s, &p,
+            !both && distinct_only_ ? &counts.left_distinct : nullptr, both ? &left_records : nullptr, &n_left);
+    counts.left.known = true;
+    counts.left.pairs = p.pairs;
+    counts.left.join_rows = p.join_rows;
+    note_examples(s);
+    if (both) {
+      w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr);
+      counts.right.known = true;
+      counts.right.pairs = p.pairs;
+      counts.right.join_rows = p.join_rows;
+    }
+    return verdict(counts);
+  }
+  w.key_set(L, l_set, &left_records, &n_left);
+  w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr);
+  counts.right.known = true;
+  counts.right.pairs = p.pairs;
+  counts.right.join_rows = p.join_rows;
+  // a failing check with examples: one plain probe of L against R's set
+  const bool fails = p.join_rows != 0 && !((double)p.pairs / (double)p.join_rows >= expected_);
+  if (fails && wants_examples()) {
+    w.key_set(R, r_set, &records, &n_records);
+    w.probe(L, records, n_records, false, max_missing_keys_, l_plain, &s, &p, nullptr, nullptr, nullptr);
+    note_examples(s);
+  }
+  return verdict(counts);
+}
+
+Check::Builder &Check::Builder::join_coverage(std::string left_table, std::string right_table) {
+  return constraint(std::make_shared<JoinCoverageConstraint>(std::move(left_table), std::move(right_table)));
+}
+
+}  // namespace term_guard

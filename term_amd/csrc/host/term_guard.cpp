@@ -1799,6 +1799,33 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     x->max_missing_keys((uint32_t)std::min<uint64_t>(
         c.get_u64("max_missing_keys", ForeignKeyConstraint::kDefaultMaxMissingKeys), UINT32_MAX));
     b.constraint(std::move(x));
+  } else if (type == "join_coverage") {
+    // {"type": "join_coverage", "left_table": "orders", "right_table": "customers", "join_keys": [["customer_id", "id"]],
+    //  "expected_match_rate": 1.0, "coverage_type": "left" | "right" | "bidirectional", "distinct_only": false,
+    //  "max_examples_reported": 100, "max_missing_keys": 10000}
+    auto x = std::make_shared<JoinCoverageConstraint>(c.get_str("left_table"), c.get_str("right_table"));
+    std::vector<std::pair<std::string, std::string>> keys;
+    if (const json::Value *kv = c.get("join_keys")) {
+      if (!kv->is(json::Value::Array)) throw TermError{TermError::Internal, "join_coverage: join_keys must be an array"};
+      for (const json::Value &e : kv->arr) {
+        if (!e.is(json::Value::Array) || e.arr.size() != 2 || !e.arr[0].is(json::Value::String) ||
+            !e.arr[1].is(json::Value::String))
+          throw TermError{TermError::Internal, "join_coverage: a join key is [left_column, right_column]"};
+        keys.emplace_back(e.arr[0].str, e.arr[1].str);
+      }
+    }
+    x->on_multiple(std::move(keys));
+    x->expect_match_rate(c.get_num("expected_match_rate", 1.0));
+    const std::string kind = c.get("coverage_type") ? c.get_str("coverage_type") : "left";
+    if (kind != "left" && kind != "right" && kind != "bidirectional")
+      throw TermError{TermError::Internal, "join_coverage: coverage_type must be left, right or bidirectional ('" + kind + "')"};
+    x->coverage_type(kind == "left" ? CoverageType::LeftCoverage
+                                    : kind == "right" ? CoverageType::RightCoverage : CoverageType::BidirectionalCoverage);
+    x->distinct_only(c.get_bool("distinct_only"));
+    x->max_examples_reported((size_t)c.get_u64("max_examples_reported", 100));
+    x->max_missing_keys((uint32_t)std::min<uint64_t>(
+        c.get_u64("max_missing_keys", JoinCoverageConstraint::kDefaultMaxMissingKeys), UINT32_MAX));
+    b.constraint(std::move(x));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
   } else if (type == "histogram") {

@@ -347,6 +347,80 @@ class ForeignKeyConstraint : public Constraint {
   uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
 };
 
+// ---- constraints/join_coverage.rs: the match rate of L LEFT / RIGHT JOIN R ON L.l = R.r, SUM(CASE WHEN the far side's key
+// IS NOT NULL ..) / COUNT(*).  COUNT(*) over a join counts matched PAIRS: the far side's non-NULL keys are gathered as
+// {key, 1} records (tgx_plan_set_key_probe_rows) and go into a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's
+// column (tgx_plan_set_key_probe_counted), so matched = pairs and total = join_rows: one integer key pair only.
+enum class CoverageType { LeftCoverage, RightCoverage, BidirectionalCoverage };
+// what the verdict is made from.  left: L probed against R's set, right: R against L's; a side the coverage type does not
+// ask for stays !known
+struct JoinCoverageCounts {
+  struct Side {
+    bool known = false;
+    uint64_t pairs = 0, join_rows = 0;
+  } left, right;
+  uint64_t left_distinct = 0;  // COUNT(DISTINCT L.l): read with distinct_only and LeftCoverage
+  // the examples, always of the left side (:289-324): L's missing keys against R's set, its NULL rows, and the rows
+  // whose key found no slot; read when the check fails and max_examples_reported > 0
+  bool examples_known = false;
+  uint64_t missing_keys = 0, null_rows = 0, overflow_rows = 0;
+};
+class JoinCoverageConstraint : public Constraint {
+ public:
+  static constexpr uint32_t kDefaultMaxMissingKeys = 10000;
+  JoinCoverageConstraint(std::string left_table, std::string right_table)  // (:94-105)
+      : left_(std::move(left_table)), right_(std::move(right_table)) {}
+  JoinCoverageConstraint &on(std::string l, std::string r) {
+    keys_.assign(1, {std::move(l), std::move(r)});
+    return *this;
+  }
+  JoinCoverageConstraint &on_multiple(std::vector<std::pair<std::string, std::string>> keys) {
+    keys_ = std::move(keys);
+    return *this;
+  }
+  JoinCoverageConstraint &expect_match_rate(double r) {  // rate.clamp(0.0, 1.0) (:139-142); a NaN stays one
+    expected_ = r < 0.0 ? 0.0 : r > 1.0 ? 1.0 : r;
+    return *this;
+  }
+  JoinCoverageConstraint &coverage_type(CoverageType t) { type_ = t; return *this; }
+  JoinCoverageConstraint &distinct_only(bool d) { distinct_only_ = d; return *this; }
+  JoinCoverageConstraint &max_examples_reported(size_t n) { max_examples_ = n; return *this; }
+  // this layer's own, as ForeignKeyConstraint's: the missing keys the probe's table on the device is sized for
+  JoinCoverageConstraint &max_missing_keys(uint32_t n) { max_missing_keys_ = n; return *this; }
+
+  const std::string &left_table() const { return left_; }
+  const std::string &right_table() const { return right_; }
+  const std::vector<std::pair<std::string, std::string>> &join_keys() const { return keys_; }
+  double expected_match_rate() const { return expected_; }
+  CoverageType coverage() const { return type_; }
+  bool distinct() const { return distinct_only_; }
+  size_t examples_reported() const { return max_examples_; }
+  uint32_t missing_keys_bound() const { return max_missing_keys_; }
+
+  std::string name() const override { return "join_coverage"; }
+  std::vector<SpecRequest> plan() const override { return {}; }
+  ConstraintResult evaluate(const Inputs &in) const override;  // throws: the constraint reads the Context
+  bool reads_context() const override { return true; }
+  ConstraintResult evaluate_context(const Context &ctx) const override;
+
+  // what evaluation refuses before it looks at a table: no keys, composite keys, identifiers, RightCoverage with
+  // distinct_only, the bound.  Throws
+  void validate() const;
+  // does a failing verdict read the examples' counts?
+  bool wants_examples() const { return max_examples_ > 0; }
+  // the rate, the verdict and the message (:327-421); throws when the join has no rows
+  ConstraintResult verdict(const JoinCoverageCounts &counts) const;
+
+ private:
+  std::string left_, right_;
+  std::vector<std::pair<std::string, std::string>> keys_;
+  double expected_ = 1.0;
+  CoverageType type_ = CoverageType::LeftCoverage;
+  bool distinct_only_ = false;
+  size_t max_examples_ = 100;
+  uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
+};
+
 // ---- core/check.rs
 class Check {
  public:
@@ -469,6 +543,9 @@ class Check::Builder {
   Builder &cross_table_sum(std::string left_column, std::string right_column);
   // pushes ForeignKeyConstraint::new(child, parent); a configured object comes through constraint(..)
   Builder &foreign_key(std::string child_column, std::string parent_column);
+  // Check::join_coverage (core/check.rs:2112): JoinCoverageConstraint::new(left, right) -- without join keys, which is
+  // an evaluation error; a configured constraint goes through constraint()
+  Builder &join_coverage(std::string left_table, std::string right_table);
   Check build() { return check_; }
 
  private:

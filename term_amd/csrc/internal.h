@@ -258,11 +258,13 @@ struct GroupSumsTask {
   tgx_group_sums_params params;
 };
 
-// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once tgx_plan_set_key_probe was called.  (The
+// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once tgx_plan_set_key_probe or
+// tgx_plan_set_key_probe_counted was called, `counted` by the latter: the set keeps the parent's multiplicities.  (The
 // parent's key set belongs to a state, not to the plan: tgx_key_probe_set_parent)
 struct KeyProbeTask {
   int column, spec_index;
-  bool set;
+  bool set, counted;
+  bool rows;  // tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
   tgx_key_probe_params params;
 };
 

@@ -366,21 +366,28 @@ struct GroupSumsTable {
 // Key probe (kernels/keyprobe.hip; TGX_CHECK_KEY_PROBE): is each child key in the parent's key set?  The set is read-only
 // while rows are walked: a bitmap of 32-bit words over [base, base + range) (route 1), or an open-addressing table of
 // `mask + 1` 64-bit keys at load <= 0.5 (route 2: kEmptyKey = free, probed linearly from mix64(key) & mask; the key whose
-// bits are the marker is the flag has_marker).  The keys that are NOT in it are counted in a bounded table laid out as
-// ValueCountsTable's integer half is; the missing key whose bits are the marker has a counter of its own.
-enum { kKpNonNull = 0, kKpMatched = 1, kKpMarker = 2, kKpOverflow = 3, kKeyProbeWords = 4 };
-enum { kKpRouteEmpty = 0, kKpRouteBitmap = 1, kKpRouteHash = 2 };
+// bits are the marker is the flag has_marker).  A COUNTED set keeps how often each key occurs in the parent: an array of
+// 64-bit counts over [base, base + range) (route 3: 0 = not in the set), or a table of `mask + 1` 16-byte {key, count}
+// slots, probed as route 2's is (route 4: the marker key's count is marker_count).  The keys that are NOT in the set are
+// counted in a bounded table laid out as ValueCountsTable's integer half is; the missing key whose bits are the marker
+// has a counter of its own.
+// (kKpNonNull | kKpMatched are flushed as a pair, bin_count.h's tail_flush; kKpPairs: the sum of the multiplicities of
+// the matched rows' keys, which only a counted task adds to)
+enum { kKpNonNull = 0, kKpMatched = 1, kKpMarker = 2, kKpOverflow = 3, kKpPairs = 4, kKeyProbeWords = 5 };
+enum { kKpRouteEmpty = 0, kKpRouteBitmap = 1, kKpRouteHash = 2, kKpRouteCountArray = 3, kKpRouteCountHash = 4 };
 constexpr int kKeyProbeBlock = 1024;              // 16 waves share one LDS table of missing keys
 constexpr uint32_t kKeyProbeLdsSlots = 8192;      // 8-byte keys + 4-byte counts: 96 KiB of LDS a workgroup
 constexpr uint32_t kKeyProbeLdsProbes = 8;
 constexpr uint32_t kKeyProbeProbes = 256;         // of the task's global table of missing keys
 constexpr int kMaxKeyProbePerLaunch = 8;
 struct KeyProbeSet {
-  const uint32_t *bits;            // route 1: (range + 31) / 32 words
-  const unsigned long long *keys;  // route 2: mask + 1 slots
-  uint64_t base, range;            // route 1: the bit of key k is k - base, for k - base < range (unsigned)
-  uint64_t mask;                   // route 2
-  uint32_t has_marker;             // route 2: the key whose bits are kEmptyKey is in the set
+  const uint32_t *bits;              // route 1: (range + 31) / 32 words
+  const unsigned long long *keys;    // route 2: mask + 1 slots
+  const unsigned long long *counts;  // route 3: `range` counts; route 4: mask + 1 slots of {key, count}, 16-byte aligned
+  uint64_t base, range;              // routes 1, 3: the cell of key k is k - base, for k - base < range (unsigned)
+  uint64_t mask;                     // routes 2, 4
+  uint64_t marker_count;             // route 4: how often the key whose bits are kEmptyKey occurs in the parent
+  uint32_t has_marker;               // route 2: the key whose bits are kEmptyKey is in the set
   uint32_t pad;
 };
 struct KeyProbeTable {
@@ -399,8 +406,15 @@ struct KeyProbeBuild {
   long long min, max;                  // identities: INT64_MAX / INT64_MIN
   unsigned long long keys, digest;     // distinct keys and the wrapping sum of mix64(key ^ kKeyProbeDigestSalt) over them
   unsigned int has_marker, pad;
+  // a counted set's reduction: records whose count is 0; the counts' sum in three pieces (bits 0..20, 21..41, 42..63 of
+  // every count, summed apart: no piece's sum can wrap below 2^40 records, so the host has the exact total); the wrapping
+  // sum of count * mix64(key ^ kKeyProbeCountSalt); and, from the build, the largest count a key has come to
+  // and the marker key's count
+  unsigned long long zero_counts, sum_piece[3], count_digest, max_count, marker_count;
 };
 constexpr uint64_t kKeyProbeDigestSalt = 0x9e3779b97f4a7c15ULL;
+constexpr uint64_t kKeyProbeCountSalt = 0xc2b2ae3d27d4eb4fULL;
+constexpr int kKpPieceBits = 21;
 
 // Histogram of one numeric column (kernels/histogram.hip; TGX_CHECK_HISTOGRAM).  The columns of a launch travel as
 // ComomentColDesc (the x side only: the single-column walk of row_walk.h); `acc_index` is the task's slot.

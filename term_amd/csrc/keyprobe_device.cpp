@@ -10,16 +10,31 @@
 //   the counters       four 64-bit words on the device (non-NULL rows, matched rows, missing rows whose key's bits are the
 //                      free-slot marker, overflow rows); rows seen are counted on the host.
 //   the missing keys   one open-addressing table of counted keys (counted_state.h), allocated at the first batch.
+// A COUNTED task (tgx_plan_set_key_probe_counted; the device side of the reference's JoinCoverageConstraint,
+// TG/constraints/join_coverage.rs) keeps the records' counts in its set -- a count array or a table of {key, count}
+// slots -- and one more counter, `pairs`: the sum over the matched rows of their key's multiplicity in the parent, which
+// is COUNT(*) of the inner join.  Its set's identity is (parent_keys, parent_digest, parent_rows, parent_count_digest).
+// A ROWS task (tgx_plan_set_key_probe_rows) probes nothing: it gathers its column's non-NULL keys as {key, 1} records in
+// device memory, the parent side of a counted probe when the parent's keys repeat (a DISTINCT export knows a key as seen
+// once or more than once, not how often).  Its records stay with the state: such a state does not merge or serialize.
+// `pairs` never wraps: the host holds an upper bound, max_count * rows a batch, in checked arithmetic, and refuses the
+// batch, merge or blob that could carry it past 2^64 - 1.
 // The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
 // under: what was merged in or read from a blob, and what the device part is folded into whenever the state is read.
 #include "keyed_state.h"
 
 namespace tgx {
-void launch_key_probe_reduce(const void *recs, uint64_t n, KeyProbeBuild *b, hipStream_t stream);
+void launch_key_probe_reduce(const void *recs, uint64_t n, bool counted, KeyProbeBuild *b, hipStream_t stream);
+void launch_key_probe_build_count_array(const void *recs, uint64_t n, unsigned long long *counts, uint64_t base,
+                                        uint64_t range, KeyProbeBuild *b, hipStream_t stream);
+void launch_key_probe_build_count_hash(const void *recs, uint64_t n, unsigned long long *slots, uint64_t mask,
+                                       KeyProbeBuild *b, hipStream_t stream);
 void launch_key_probe_build_bitmap(const void *recs, uint64_t n, uint32_t *bits, uint64_t base, uint64_t range,
                                    KeyProbeBuild *b, hipStream_t stream);
 void launch_key_probe_build_hash(const void *recs, uint64_t n, unsigned long long *keys, uint64_t mask, KeyProbeBuild *b,
                                  hipStream_t stream);
+void launch_key_probe_rows(const ComomentColDesc &d, unsigned long long *recs, uint64_t cap, unsigned long long *cursor,
+                           int blocks, hipStream_t stream);
 void launch_key_probe(const KeyProbeLaunch &L, int route, int n_tasks, int blocks, hipStream_t stream);
 
 namespace {
@@ -32,9 +47,25 @@ struct ProbeHost : KeyedEntries<uint64_t> {
   // the set the counts were taken under (`known`: there is one)
   bool known = false;
   uint64_t parent_keys = 0, parent_digest = 0;
+  // a counted task: the rest of its set's identity, the set's largest count, and the matched pairs
+  uint64_t parent_rows = 0, parent_count_digest = 0, max_count = 0, pairs = 0;
   bool holds_counts() const { return seen != 0 || size() != 0; }
-  bool same_parent(const ProbeHost &o) const { return parent_keys == o.parent_keys && parent_digest == o.parent_digest; }
+  bool same_parent(const ProbeHost &o) const {
+    return parent_keys == o.parent_keys && parent_digest == o.parent_digest && parent_rows == o.parent_rows &&
+           parent_count_digest == o.parent_count_digest;
+  }
+  void take_parent(const ProbeHost &o) {
+    known = true;
+    parent_keys = o.parent_keys;
+    parent_digest = o.parent_digest;
+    parent_rows = o.parent_rows;
+    parent_count_digest = o.parent_count_digest;
+    max_count = o.max_count;
+  }
 };
+
+// a + b, or false: the sum is past 2^64 - 1
+inline bool add_fits(uint64_t a, uint64_t b, uint64_t *sum) { return !__builtin_add_overflow(a, b, sum); }
 
 struct NoRange {};
 
@@ -59,6 +90,7 @@ struct ProbeKind {
     d.non_null = w[kKpNonNull];
     d.matched = w[kKpMatched];
     d.overflow_rows = w[kKpOverflow];
+    d.pairs = w[kKpPairs];
     if (w[kKpMarker]) {
       d.kind = kIntKeys;
       d.ints[(int64_t)kEmptyKey] = w[kKpMarker];
@@ -70,23 +102,26 @@ struct ProbeKind {
     a.non_null += b.non_null;
     a.matched += b.matched;
     a.overflow_rows += b.overflow_rows;
+    a.pairs += b.pairs;  // (the callers have held the sum against 2^64 - 1: ProbeCheck::pairs_fit)
     a.add_entries(b);
-    if (!a.known && b.known) {
-      a.known = true;
-      a.parent_keys = b.parent_keys;
-      a.parent_digest = b.parent_digest;
-    }
+    if (!a.known && b.known) a.take_parent(b);
   }
 
   // per task { u32 max_missing_keys, u32 0 (the plan's parameters), u32 known (the counts were taken under a set), u32 0,
   //   u64 parent_keys, parent_digest, u64 seen, non_null, matched, overflow_rows, u64 n_entries,
   //   n_entries x { i64 key, u64 count }, ascending by key }
+  // a counted task: the second u32 0 is 1, and { u64 parent_rows, parent_count_digest, max_count, pairs } stand between
+  // n_entries and the entries
   static void write(const KeyProbeTask &t, const ProbeHost &h, Writer &w) {
     w.pod(t.params);
     w.pod((uint32_t)(h.known ? 1 : 0));
-    w.pod((uint32_t)0);
+    w.pod((uint32_t)(t.counted ? 1 : 0));
     const uint64_t words[7] = {h.parent_keys, h.parent_digest, h.seen, h.non_null, h.matched, h.overflow_rows, h.size()};
     w.pod(words);
+    if (t.counted) {
+      const uint64_t more[4] = {h.parent_rows, h.parent_count_digest, h.max_count, h.pairs};
+      w.pod(more);
+    }
     keyed_write_entries(h, CountWire(), w);
   }
 
@@ -94,16 +129,33 @@ struct ProbeKind {
     tgx_key_probe_params p;
     r.get(&p, sizeof(p));
     const uint32_t known = r.pod<uint32_t>(), pad = r.pod<uint32_t>();
-    uint64_t words[7];
+    uint64_t words[7], more[4] = {0, 0, 0, 0};
     r.get(words, sizeof(words));
+    if (!r.ok) return TGX_OK;
+    if (pad != (t.counted ? 1u : 0u))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  pad > 1 ? "malformed state blob (KEY_PROBE task %zu: parent set)"
+                          : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
+                  k);
+    if (t.counted) r.get(more, sizeof(more));
     if (!r.ok) return TGX_OK;
     if (p.max_missing_keys != t.params.max_missing_keys || p.reserved != t.params.reserved)
       return fail(err, TGX_INVALID_ARGUMENT,
                   "KEY_PROBE task %zu: the blob was counted under other parameters (max_missing_keys %u) than the plan's "
                   "(%u)", k, p.max_missing_keys, t.params.max_missing_keys);
     const uint64_t seen = words[2], non_null = words[3], n = words[6];
-    if (known > 1 || pad != 0 || (!known && (words[0] != 0 || words[1] != 0 || seen != 0 || n != 0)))
+    if (known > 1 || (!known && (words[0] != 0 || words[1] != 0 || seen != 0 || n != 0 || more[0] != 0 || more[1] != 0 ||
+                                 more[2] != 0 || more[3] != 0)))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: parent set)", k);
+    // a counted set: keys <= rows < 2^63, the largest count is one of them; matched <= pairs <= matched * max_count
+    if (t.counted) {
+      uint64_t most = 0;
+      const bool set_ok = more[0] >= words[0] && more[0] < ((uint64_t)1 << 63) && more[2] <= more[0] &&
+                          (more[2] != 0) == (words[0] != 0);
+      const bool wraps = __builtin_mul_overflow(words[4], more[2], &most);
+      if (!set_ok || more[3] < words[4] || (!wraps && more[3] > most))
+        return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: counted set and pairs)", k);
+    }
     uint64_t counted = 0;
     TGX_TRY(keyed_read_entries("KEY_PROBE", "key", k, r, kIntKeys, n, 0, CountWire(), h, &counted, err));
     if (!r.ok) return TGX_OK;
@@ -119,6 +171,10 @@ struct ProbeKind {
     h.non_null = non_null;
     h.matched = words[4];
     h.overflow_rows = words[5];
+    h.parent_rows = more[0];
+    h.parent_count_digest = more[1];
+    h.max_count = more[2];
+    h.pairs = more[3];
     return TGX_OK;
   }
 };
@@ -127,18 +183,44 @@ struct ProbeKind {
 struct ParentSet {
   bool has = false;
   int route = kKpRouteEmpty;
-  DevBuf buf;  // the bitmap's words or the table's keys
+  DevBuf buf;  // the bitmap's words, the table's keys, the count array or the table's {key, count} slots
   uint64_t base = 0, range = 0, mask = 0;
   uint32_t has_marker = 0;
   uint64_t keys = 0, digest = 0;
+  uint64_t marker_count = 0, rows = 0, count_digest = 0, max_count = 0;  // a counted set
+  void identify(ProbeHost &h) const {
+    h.known = true;
+    h.parent_keys = keys;
+    h.parent_digest = digest;
+    h.parent_rows = rows;
+    h.parent_count_digest = count_digest;
+    h.max_count = max_count;
+  }
 };
 
 struct ProbeCheck final : CountedState<ProbeKind> {
   const std::vector<KeyProbeTask> &tasks;
   std::vector<ParentSet> parent;
   bool fed = false;  // a batch with rows has been handed to tgx_update since the state was created or reset
+  // per counted task: an upper bound of what the device part's `pairs` can have come to, the sum over the accepted
+  // batches of max_count * rows
+  std::vector<uint64_t> pairs_bound;
+  // per rows task: the gathered records and the records there is room for
+  std::vector<DevBuf> gathered;
+  std::vector<uint64_t> gathered_cap;
 
-  explicit ProbeCheck(const tgx_plan *plan) : CountedState(plan), tasks(plan->key_probes), parent(plan->key_probes.size()) {}
+  explicit ProbeCheck(const tgx_plan *plan)
+      : CountedState(plan), tasks(plan->key_probes), parent(plan->key_probes.size()), pairs_bound(plan->key_probes.size(), 0),
+        gathered(plan->key_probes.size()), gathered_cap(plan->key_probes.size(), 0) {}
+
+  // a state that has gathered rows keeps them to itself
+  tgx_status rows_stay(const char *what, tgx_error *err) const {
+    for (size_t k = 0; k < tasks.size(); k++)
+      if (tasks[k].rows && (device_rows[k] > 0 || host[k].seen > 0))
+        return fail(err, TGX_UNSUPPORTED, "spec %d: a KEY_PROBE check that gathers rows does not %s: its records stay with "
+                    "the state", tasks[k].spec_index, what);
+    return TGX_OK;
+  }
 
   void decode_slot(size_t, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
     o.kind = kIntKeys;
@@ -150,30 +232,53 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     TGX_TRY(gather(st, g, err));
     for (size_t k = 0; k < g->size(); k++) {
       ProbeHost &h = (*g)[k];
-      if (parent[k].has && !h.known) {
-        h.known = true;
-        h.parent_keys = parent[k].keys;
-        h.parent_digest = parent[k].digest;
-      }
+      if (parent[k].has && !h.known) parent[k].identify(h);
     }
     return TGX_OK;
   }
 
   tgx_status accepts(tgx_state *, int64_t nrows, tgx_error *err) override {
     for (size_t k = 0; k < tasks.size(); k++)
-      if (!parent[k].has)
+      if (!parent[k].has && !tasks[k].rows)
         return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
                     tasks[k].spec_index);
+    // a counted task: host part + bound of the device part + this batch's bound stays within 2^64 - 1, for every task
+    // before any bound moves
+    std::vector<uint64_t> next(pairs_bound);
+    for (size_t k = 0; k < tasks.size(); k++) {
+      if (!tasks[k].counted || nrows <= 0) continue;
+      uint64_t batch = 0, all = 0;
+      if (__builtin_mul_overflow(parent[k].max_count, (uint64_t)nrows, &batch) || !add_fits(next[k], batch, &next[k]) ||
+          !add_fits(next[k], host[k].pairs, &all))
+        return fail(err, TGX_UNSUPPORTED,
+                    "spec %d: a batch of %lld rows against a set whose largest count is %llu could carry the matched "
+                    "pairs past 2^64 - 1", tasks[k].spec_index, (long long)nrows, (unsigned long long)parent[k].max_count);
+    }
+    pairs_bound.swap(next);
     fed |= nrows > 0;
     return TGX_OK;
   }
 
   tgx_status reset(tgx_state *st, tgx_error *err) override {
     fed = false;
+    std::fill(pairs_bound.begin(), pairs_bound.end(), 0);
     return CountedState::reset(st, err);
   }
 
+  // may `theirs` be added to what this state holds?  (pairs of a plain task are 0)
+  tgx_status pairs_fit(const std::vector<ProbeHost> &theirs, tgx_error *err) const {
+    for (size_t k = 0; k < theirs.size(); k++) {
+      uint64_t all = 0;
+      if (!add_fits(host[k].pairs, pairs_bound[k], &all) || !add_fits(all, theirs[k].pairs, &all))
+        return fail(err, TGX_UNSUPPORTED, "%s task %zu: the states' matched pairs add up past 2^64 - 1", kName, k);
+    }
+    return TGX_OK;
+  }
+
   tgx_status set_parent(tgx_state *st, size_t k, const void *recs, uint64_t n, tgx_error *err) {
+    if (tasks[k].rows)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check that gathers rows takes no parent set",
+                  tasks[k].spec_index);
     if (fed)
       return fail(err, TGX_INVALID_ARGUMENT,
                   "spec %d: the parent set of a KEY_PROBE check is given before the state's first batch (or after "
@@ -189,15 +294,51 @@ struct ProbeCheck final : CountedState<ProbeKind> {
       ProfScope ps(st, "key_probe_build", n * 16);
       DevBuf d_build;
       HIP_TRY(d_build.reserve(sizeof(KeyProbeBuild)));
-      KeyProbeBuild b = {INT64_MAX, INT64_MIN, 0, 0, 0, 0};
+      const bool counted = tasks[k].counted;
+      KeyProbeBuild b;
+      memset(&b, 0, sizeof(b));
+      b.min = INT64_MAX;
+      b.max = INT64_MIN;
       HIP_TRY(hipMemcpyAsync(d_build.p, &b, sizeof(b), hipMemcpyHostToDevice, st->stream));
-      launch_key_probe_reduce(recs, n, d_build.as<KeyProbeBuild>(), st->stream);
+      launch_key_probe_reduce(recs, n, counted, d_build.as<KeyProbeBuild>(), st->stream);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
       HIP_TRY(hipStreamSynchronize(st->stream));
       // (unsigned: INT64_MIN and INT64_MAX together wrap the range to 0, which is not dense)
       const uint64_t range = (uint64_t)b.max - (uint64_t)b.min + 1;
-      if (range != 0 && range <= 128 * n) {
+      if (counted) {
+        // (a refused set leaves the state without one: the set it had is dropped)
+        if (b.zero_counts) parent[k] = ParentSet();
+        if (b.zero_counts)
+          return fail(err, TGX_INVALID_ARGUMENT, "spec %d: %llu records of the parent set have a count of 0",
+                      tasks[k].spec_index, (unsigned long long)b.zero_counts);
+        const unsigned __int128 total = (unsigned __int128)b.sum_piece[0] +
+                                        ((unsigned __int128)b.sum_piece[1] << kKpPieceBits) +
+                                        ((unsigned __int128)b.sum_piece[2] << (2 * kKpPieceBits));
+        if (total >> 63) parent[k] = ParentSet();
+        if (total >> 63)
+          return fail(err, TGX_UNSUPPORTED, "spec %d: the counts of the parent set sum to 2^63 or more",
+                      tasks[k].spec_index);
+        s.rows = (uint64_t)total;
+        s.count_digest = b.count_digest;
+      }
+      if (counted && range != 0 && range <= 4 * n) {
+        s.route = kKpRouteCountArray;
+        s.base = (uint64_t)b.min;
+        s.range = range;
+        HIP_TRY(s.buf.reserve((size_t)range * 8));
+        HIP_TRY(hipMemsetAsync(s.buf.p, 0, (size_t)range * 8, st->stream));
+        launch_key_probe_build_count_array(recs, n, s.buf.as<unsigned long long>(), s.base, s.range,
+                                           d_build.as<KeyProbeBuild>(), st->stream);
+      } else if (counted) {
+        s.route = kKpRouteCountHash;
+        uint64_t slots = 2;
+        while (slots < 2 * n) slots <<= 1;
+        s.mask = slots - 1;
+        HIP_TRY(s.buf.reserve((size_t)slots * 16));
+        launch_key_probe_build_count_hash(recs, n, s.buf.as<unsigned long long>(), s.mask, d_build.as<KeyProbeBuild>(),
+                                          st->stream);
+      } else if (range != 0 && range <= 128 * n) {
         s.route = kKpRouteBitmap;
         s.base = (uint64_t)b.min;
         s.range = range;
@@ -220,18 +361,20 @@ struct ProbeCheck final : CountedState<ProbeKind> {
       HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
       HIP_TRY(hipStreamSynchronize(st->stream));
       s.has_marker = b.has_marker;
+      s.marker_count = b.marker_count;
+      s.max_count = b.max_count;
       s.keys = b.keys;
       s.digest = b.digest;
     }
     ProbeHost &h = host[k];
-    if (h.known && h.holds_counts() && (h.parent_keys != s.keys || h.parent_digest != s.digest))
+    ProbeHost given;
+    s.identify(given);
+    if (h.known && h.holds_counts() && !h.same_parent(given))
       return fail(err, TGX_INVALID_ARGUMENT,
                   "spec %d: the state holds counts taken under another parent set (%llu keys, digest %016llx) than the "
                   "one given (%llu keys, digest %016llx)", tasks[k].spec_index, (unsigned long long)h.parent_keys,
                   (unsigned long long)h.parent_digest, (unsigned long long)s.keys, (unsigned long long)s.digest);
-    h.known = true;
-    h.parent_keys = s.keys;
-    h.parent_digest = s.digest;
+    s.identify(h);
     parent[k] = std::move(s);
     return TGX_OK;
   }
@@ -244,16 +387,20 @@ struct ProbeCheck final : CountedState<ProbeKind> {
       // (an Int64 view: update_validate refuses what is not widened to one)
       if (dev[tasks[k].column].type != TGX_INT64)
         return fail(err, TGX_UNSUPPORTED, "KEY_PROBE takes integer columns (%d)", dev[tasks[k].column].type);
+      if (tasks[k].rows) {
+        TGX_TRY(gather_rows(st, k, dev[tasks[k].column], nrows, err));
+        continue;
+      }
       if (!parent[k].has)
         return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
                     tasks[k].spec_index);
       if (!table[k].live) TGX_TRY(open_table(st, k, tasks[k].params.max_missing_keys, 1, 0, err));
     }
     const uint64_t salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
-    for (int route = kKpRouteEmpty; route <= kKpRouteHash; route++) {
+    for (int route = kKpRouteEmpty; route <= kKpRouteCountHash; route++) {
       std::vector<size_t> slots;
       for (size_t k = 0; k < tasks.size(); k++)
-        if (parent[k].route == route) slots.push_back(k);
+        if (parent[k].route == route && !tasks[k].rows) slots.push_back(k);
       for (size_t t0 = 0; t0 < slots.size(); t0 += kMaxKeyProbePerLaunch) {
         const int n = (int)std::min<size_t>(kMaxKeyProbePerLaunch, slots.size() - t0);
         KeyProbeLaunch L;
@@ -266,6 +413,8 @@ struct ProbeCheck final : CountedState<ProbeKind> {
           KeyProbeSet &ds = L.sets[i];
           ds.bits = route == kKpRouteBitmap ? s.buf.as<uint32_t>() : nullptr;
           ds.keys = route == kKpRouteHash ? s.buf.as<unsigned long long>() : nullptr;
+          ds.counts = route >= kKpRouteCountArray ? s.buf.as<unsigned long long>() : nullptr;
+          ds.marker_count = s.marker_count;
           ds.base = s.base;
           ds.range = s.range;
           ds.mask = s.mask;
@@ -290,7 +439,47 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
+  // one batch of a rows task: room for every row the state has seen and this batch's, then the batch's non-NULL keys
+  // behind the records that are there
+  tgx_status gather_rows(tgx_state *st, size_t k, const tgx_column &col, int64_t nrows, tgx_error *err) {
+    const uint64_t need = (uint64_t)device_rows[k] + (uint64_t)nrows;
+    if (need > gathered_cap[k]) {
+      const uint64_t cap = std::max<uint64_t>(need, 2 * gathered_cap[k]);
+      DevBuf grown;
+      HIP_TRY(grown.reserve((size_t)cap * 16));
+      if (device_rows[k] > 0) {
+        HIP_TRY(hipMemcpyAsync(grown.p, gathered[k].p, (size_t)device_rows[k] * 16, hipMemcpyDeviceToDevice, st->stream));
+        HIP_TRY(hipStreamSynchronize(st->stream));  // (before the old buffer goes)
+      }
+      gathered[k] = std::move(grown);
+      gathered_cap[k] = cap;
+    }
+    ComomentColDesc d;
+    memset(&d, 0, sizeof(d));
+    const uint64_t bytes = side_fill_x(d, col);
+    ProfScope ps(st, "key_probe_rows", bytes);
+    launch_key_probe_rows(d, gathered[k].as<unsigned long long>(), gathered_cap[k],
+                          d_counts.as<unsigned long long>() + word_off[k] + kKpNonNull,
+                          side_blocks(nrows, 256, g_ctx.n_cu, 4, 1), st->stream);
+    HIP_TRY(hipGetLastError());
+    return TGX_OK;
+  }
+
+  // the records of rows task k (device memory, the state's until its next batch or reset)
+  tgx_status rows_get(tgx_state *st, size_t k, const void **records, uint64_t *n, tgx_error *err) {
+    if (!tasks[k].rows)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %d: the KEY_PROBE check does not gather rows (tgx_plan_set_key_probe_rows)",
+                  tasks[k].spec_index);
+    std::vector<ProbeHost> g;
+    TGX_TRY(collect(st, &g, err));
+    *n = std::min<uint64_t>(g[k].non_null, gathered_cap[k]);
+    *records = *n ? gathered[k].p : nullptr;
+    return TGX_OK;
+  }
+
   tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) override {
+    TGX_TRY(rows_stay("merge", err));
+    TGX_TRY(static_cast<ProbeCheck *>(of(src))->rows_stay("merge", err));
     std::vector<ProbeHost> theirs, mine;
     TGX_TRY(static_cast<ProbeCheck *>(of(src))->collect(src, &theirs, err));
     TGX_TRY(collect(st, &mine, err));
@@ -298,11 +487,13 @@ struct ProbeCheck final : CountedState<ProbeKind> {
       if (theirs[k].known && mine[k].known && !theirs[k].same_parent(mine[k]))
         return fail(err, TGX_INVALID_ARGUMENT, "%s task %zu: the states were counted under different %s", kName, k,
                     ProbeKind::kDiffers);
+    TGX_TRY(pairs_fit(theirs, err));
     for (size_t k = 0; k < theirs.size(); k++) ProbeKind::merge_host(host[k], theirs[k]);
     return TGX_OK;
   }
 
   tgx_status serialize(tgx_state *st, Writer &w, tgx_error *err) override {
+    TGX_TRY(rows_stay("serialize", err));
     std::vector<ProbeHost> g;
     TGX_TRY(collect(st, &g, err));
     w.pod(ProbeKind::kMagic);
@@ -347,6 +538,7 @@ tgx_status keyprobe_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_erro
   memset(&t, 0, sizeof(t));
   t.column = sp.column;
   t.spec_index = spec_index;
+  t.counted = t.rows = false;
   plan->key_probes.push_back(t);
   *slot = (int)plan->key_probes.size() - 1;
   return TGX_OK;
@@ -382,8 +574,8 @@ SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.em
 
 using namespace tgx;
 
-extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
-                                             tgx_error *err) try {
+namespace {
+tgx_status plan_set_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p, bool counted, tgx_error *err) {
   if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
   size_t slot = 0;
   TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
@@ -394,9 +586,59 @@ extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, 
                 (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
   if (p->reserved != 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: reserved must be 0 (%u)", spec_index, p->reserved);
   KeyProbeTask &t = plan->key_probes[slot];
+  // (a spec is plain or counted for good: the second of the two calls is refused)
+  if (t.set && t.rows)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set to gather rows (tgx_plan_set_key_probe_rows)",
+                spec_index);
+  if (t.set && t.counted != counted)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
+                t.counted ? "counted" : "plain", t.counted ? "_counted" : "");
   t.params = *p;
+  t.counted = counted;
   t.set = true;
   return TGX_OK;
+}
+}  // namespace
+
+extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                             tgx_error *err) try {
+  return plan_set_probe(plan, spec_index, p, false, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_counted(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                                     tgx_error *err) try {
+  return plan_set_probe(plan, spec_index, p, true, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
+  if (!plan) return fail(err, TGX_INVALID_ARGUMENT, "plan is NULL");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
+  if (plan_has_state(plan))
+    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a KEY_PROBE check are fixed once a state of the plan exists");
+  KeyProbeTask &t = plan->key_probes[slot];
+  if (t.set && !t.rows)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
+                t.counted ? "counted" : "plain", t.counted ? "_counted" : "");
+  t.params = tgx_key_probe_params{1, 0};
+  t.rows = t.set = true;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_rows_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                             const void **device_records, uint64_t *n_records, tgx_error *err) try {
+  bind_thread();
+  if (!device_records || !n_records) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, st, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, "bad arguments"));
+  TGX_TRY(need_device(err));
+  return static_cast<ProbeCheck *>(ProbeCheck::of(st))->rows_get(st, slot, device_records, n_records, err);
 } catch (...) {
   return tgx::abi_exception(err);
 }
@@ -431,6 +673,29 @@ extern "C" tgx_status tgx_key_probe_get(const tgx_plan *plan, tgx_state *st, siz
   out->parent_keys = h.parent_keys;
   out->parent_digest = h.parent_digest;
   out->route = route;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                              tgx_key_probe_pairs *out, tgx_error *err) try {
+  bind_thread();
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  for (const KeyProbeTask &t : plan->key_probes)
+    if ((size_t)t.spec_index == spec_index && !t.counted)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check is not counted (tgx_plan_set_key_probe_counted)",
+                  spec_index);
+  memset(out, 0, sizeof(*out));
+  out->pairs = h.pairs;
+  // (rows seen are below 2^63; the sum is still held against the word)
+  if (!add_fits(h.pairs, h.seen - h.matched, &out->join_rows))
+    return fail(err, TGX_UNSUPPORTED, "spec %zu: the join has more than 2^64 - 1 rows", spec_index);
+  out->parent_rows = h.parent_rows;
+  out->parent_count_digest = h.parent_count_digest;
+  out->max_count = h.max_count;
   return TGX_OK;
 } catch (...) {
   return tgx::abi_exception(err);

@@ -277,6 +277,11 @@ class CheckBuilder:
         """pushes ForeignKeyConstraint::new(child, parent); a configured object goes through constraint()"""
         return self.constraint(ForeignKeyConstraint(child_column, parent_column))
 
+    def join_coverage(self, left_table, right_table):
+        """core/check.rs:2112-2123: pushes JoinCoverageConstraint::new(left, right) -- without join keys, which is an
+        evaluation error, as in the reference; a configured object goes through constraint()"""
+        return self.constraint(JoinCoverageConstraint(left_table, right_table))
+
     def has_consistent_data_type(self, column, threshold):
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
@@ -553,6 +558,80 @@ class ForeignKeyConstraint:
         out, err = C.c_char_p(), _Error()
         _host_check(_host().tgx_host_foreign_key_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
                                                       C.byref(out), C.byref(err)), err)
+        return json.loads(_take(out))
+
+
+class CoverageType:
+    """constraints/join_coverage.rs:83-91"""
+    Left, Right, Bidirectional = "left", "right", "bidirectional"
+
+
+class JoinCoverageConstraint:
+    """constraints/join_coverage.rs:94-163, one method per builder call of the reference: the match rate of
+    `left_table` LEFT JOIN `right_table` on one key pair, SUM(CASE WHEN the far key IS NOT NULL ..) / COUNT(*), against
+    expect_match_rate.  COUNT(*) over a join counts matched pairs: the far side's non-NULL keys are gathered as {key, 1}
+    records and handed to a counted KEY_PROBE spec over the near side's column (one integer key pair
+    only: composite keys and other column types are the constraint's own error).  It needs
+    ValidationSuite.run(table, tables={name: table})"""
+
+    def __init__(self, left_table, right_table):
+        self.spec = {"type": "join_coverage", "left_table": left_table, "right_table": right_table, "join_keys": [],
+                     "expected_match_rate": 1.0, "coverage_type": CoverageType.Left, "distinct_only": False,
+                     "max_examples_reported": 100, "max_missing_keys": 10000}
+
+    @classmethod
+    def from_spec(cls, spec):
+        """the constraint of its JSON form (a dict as `spec` holds it)"""
+        c = cls(spec["left_table"], spec["right_table"])
+        c.on_multiple(spec.get("join_keys", []))
+        c.expect_match_rate(spec.get("expected_match_rate", 1.0))
+        c.coverage_type(spec.get("coverage_type", CoverageType.Left))
+        c.distinct_only(spec.get("distinct_only", False))
+        c.max_examples_reported(spec.get("max_examples_reported", 100))
+        return c.max_missing_keys(spec.get("max_missing_keys", 10000))
+
+    def on(self, left_column, right_column):
+        self.spec["join_keys"] = [[left_column, right_column]]
+        return self
+
+    def on_multiple(self, keys):
+        self.spec["join_keys"] = [[l, r] for l, r in keys]
+        return self
+
+    def expect_match_rate(self, rate):
+        rate = float(rate)
+        self.spec["expected_match_rate"] = min(1.0, max(0.0, rate))  # rate.clamp(0.0, 1.0) (:139-142)
+        return self
+
+    def coverage_type(self, coverage_type):
+        if coverage_type not in (CoverageType.Left, CoverageType.Right, CoverageType.Bidirectional):
+            raise ValueError("coverage_type is CoverageType.Left, .Right or .Bidirectional")
+        self.spec["coverage_type"] = coverage_type
+        return self
+
+    def distinct_only(self, distinct):
+        """total becomes COUNT(DISTINCT left column) under the same numerator, as the reference's SQL has it: the rate can
+        exceed 1.  Left only: Bidirectional ignores it, with Right it is the constraint's error"""
+        self.spec["distinct_only"] = bool(distinct)
+        return self
+
+    def max_examples_reported(self, n):
+        self.spec["max_examples_reported"] = int(n)
+        return self
+
+    def max_missing_keys(self, n):
+        """this layer's own, as ForeignKeyConstraint's: the missing keys the probe's table on the device is sized for"""
+        self.spec["max_missing_keys"] = int(n)
+        return self
+
+    def name(self): return "join_coverage"
+
+    def verdict_from_counts(self, counts):
+        """the verdict on given counts (no device): a dict {"left": {"pairs", "join_rows"}, "right": {..},
+        "left_distinct", "examples": {"missing_keys", "null_rows", "overflow_rows"}} (include/tgx_host.h)"""
+        out, err = C.c_char_p(), _Error()
+        _host_check(_host().tgx_host_join_coverage_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
+                                                        C.byref(out), C.byref(err)), err)
         return json.loads(_take(out))
 
 
@@ -1238,6 +1317,7 @@ def _host():
                                                      C.POINTER(C.c_char_p), E]
         L.tgx_host_cross_table_sum_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_foreign_key_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_join_coverage_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_free.argtypes = [C.c_void_p]
         L.tgx_host_free.restype = None
         _HOST = L

@@ -311,11 +311,14 @@ def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=N
 
 
 def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0, overflow_rows=0, parent=None,
-                    ordered=True, non_null=None):
+                    ordered=True, non_null=None, counted=None):
     """a KEY_PROBE task: the plan's parameter, the identity of the parent set the counts were taken under (`parent`:
     (parent_keys, parent_digest), or None for a state that knows of none), the counters and the entries of `missing`
     (key -> rows).  non_null defaults to what the invariant makes it -- matched + sum(missing) + overflow_rows -- and seen
-    to non_null + nulls.  `ordered=False` keeps the entries in the order given (for a blob that is to be refused)."""
+    to non_null + nulls.  `ordered=False` keeps the entries in the order given (for a blob that is to be refused).
+    `counted`: (parent_rows, parent_count_digest, max_count, pairs) of a counted task (Plan.set_key_probe_counted) -- the
+    rest of its set's identity, the set's largest count and the matched pairs; the task's second reserved word is then 1
+    and the four words stand before the entries.  None: a plain task, whose bytes are the ones they always were."""
     items = list(missing.items()) if hasattr(missing, "items") else list(missing)
     if ordered:
         items.sort(key=lambda kv: kv[0])
@@ -324,8 +327,10 @@ def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0,
     if seen is None:
         seen = non_null + nulls
     keys, digest = parent if parent is not None else (0, 0)
-    out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, 0, keys, digest, seen, non_null,
-                      matched, overflow_rows, len(items))
+    out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, 1 if counted is not None else 0, keys,
+                      digest, seen, non_null, matched, overflow_rows, len(items))
+    if counted is not None:
+        out += struct.pack("<4Q", *counted)
     for k, c in items:
         out += struct.pack("<qQ", k, c)
     return out
