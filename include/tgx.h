@@ -722,6 +722,21 @@ tgx_status tgx_plan_set_key_probe_counted(tgx_plan *plan, size_t spec_index, con
  * state costs 16 bytes a row it has seen, tgx_state_reset empties it, and a state that has gathered rows does not merge
  * or serialize (TGX_UNSUPPORTED).  tgx_key_probe_get gives seen, non_null and null_rows. */
 tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_error *err);
+/* The spec probes STRING keys: its column is Utf8, LargeUtf8, Utf8View or Dictionary<Int32, Utf8>, and its parent set
+ * holds the parent's values as keyed 128-bit fingerprints (tgx_key_probe_set_parent below).  max_missing_keys
+ * (1 .. TGX_KEY_PROBE_MAX_MISSING_KEYS) sizes the table of missing keys as for a plain spec; a missing key keeps its
+ * bytes when it has at most max_value_bytes (1 .. TGX_KEY_PROBE_MAX_VALUE_BYTES) of them, and is a long row otherwise.
+ * Lifetime and refusals are those of tgx_plan_set_key_probe.  A spec takes exactly one of the four
+ * tgx_plan_set_key_probe* calls: any second one on the same spec is TGX_INVALID_ARGUMENT.  An integer, float, UInt64 or
+ * Boolean column on such a spec is TGX_UNSUPPORTED from tgx_update (the state stays usable), as a string column is on
+ * every other KEY_PROBE spec. */
+enum { TGX_KEY_PROBE_MAX_VALUE_BYTES = 256 };
+typedef struct tgx_key_probe_strings_params {
+  uint32_t max_missing_keys;
+  uint32_t max_value_bytes;
+} tgx_key_probe_strings_params;
+tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec_index, const tgx_key_probe_strings_params *params,
+                                          tgx_error *err);
 
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
@@ -1095,6 +1110,44 @@ tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *state, size_
  * state owns, valid until its next batch or reset; in no particular order.  TGX_INVALID_ARGUMENT on any other spec. */
 tgx_status tgx_key_probe_rows_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, const void **device_records,
                                   uint64_t *n_records, tgx_error *err);
+/* A STRINGS spec (tgx_plan_set_key_probe_strings).  tgx_key_probe_set_parent takes n_records 32-byte
+ * {uint64 hash_a, uint64 hash_b, uint64 count, uint64 0} records in device memory -- what
+ * tgx_distinct_export(.., world = 1, ..) hands out for a string column, with or without TGX_FLAG_EXACT_KEYS on the
+ * parent's spec.  Counts are ignored, duplicate records are allowed, n_records == 0 is the empty set.  The records must
+ * have been made under the fingerprint key that the child's plan carries: copy it with
+ * tgx_plan_get_fingerprint_key(parent plan) into tgx_plan_set_fingerprint_key(child plan) before the child plan's first
+ * state.  THE LIBRARY CANNOT VERIFY THIS: a set made under another key simply matches nothing.  A record whose hash_a or
+ * hash_b is all ones (the free-slot marker, which no fingerprint is) is TGX_INVALID_ARGUMENT, and the state is then left
+ * without a set.  The set is route 5: a hash table of the smallest power of two >= 2 * n_records 16-byte slots; its
+ * identity, which blobs carry and merges compare, is (parent_keys, parent_digest) with parent_digest the wrapping sum
+ * over the distinct fingerprints of mix64(mix64(hash_a ^ 0x9e3779b97f4a7c15) ^ hash_b).
+ * tgx_key_probe_get works unchanged (`route` reads 5, 0 for none or empty) with
+ *   seen == non_null + null_rows,  non_null == matched + missing_rows,  missing_rows == counted + overflow_rows + long_rows
+ * where long_rows (tgx_key_probe_strings_get) are the MISSING rows whose value is longer than max_value_bytes; a long
+ * value that is in the set is matched like any other.  Rows of a dictionary column whose entry is NULL or whose index
+ * lies outside the dictionary are NULL rows.
+ * The guarantee is the one of VALUE_COUNTS and of DISTINCT without TGX_FLAG_EXACT_KEYS: all counts are exact over
+ * FINGERPRINTS.  A child value that is not in the parent is reported as matched only if all 128 bits of its fingerprint
+ * agree with a parent value's, under a key that the data's producer does not know; the missing keys keep their bytes.
+ * A blob that holds such a task with a known, non-empty set is a KEYED blob: its header carries the plan's fingerprint
+ * key, and tgx_state_deserialize under a plan with another key refuses it; a blob that holds such a task and carries no
+ * key is malformed.  States of different identities, of different
+ * max_value_bytes, or of an integer and a strings spec do not merge.
+ * tgx_key_probe_entries, tgx_key_probe_pairs_get and tgx_key_probe_rows_get are TGX_INVALID_ARGUMENT on such a spec, and
+ * the two calls below on every other. */
+typedef struct tgx_key_probe_strings {
+  uint64_t long_rows;       /* missing rows whose value is longer than max_value_bytes */
+  uint32_t max_value_bytes; /* the plan's */
+  uint32_t reserved;
+} tgx_key_probe_strings;
+tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_key_probe_strings *out,
+                                     tgx_error *err);
+/* Copies the missing keys, ascending bytewise: entry i's bytes are bytes[offset .. offset + length), its `value` is 0.
+ * Sizes and buffers as for tgx_value_counts_entries: *n_entries and *n_bytes always receive what is needed; `entries`
+ * may be NULL for a size query; a non-NULL buffer that is too small is TGX_INVALID_ARGUMENT with nothing copied. */
+tgx_status tgx_key_probe_entries_bytes(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                       tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
+                                       uint64_t bytes_cap, uint64_t *n_bytes, tgx_error *err);
 
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous

@@ -159,7 +159,9 @@ tgx_status tgx_host_group_counts_state_json(const char *analyzer_json, const cha
  *    "tolerance": 0.0, "max_violations_reported": 100, "max_groups": 65536}       (TG/constraints/cross_table_sum.rs)
  * is evaluated beside the suite's fused plan, against the registered tables: each side is walked once, as a
  * TGX_CHECK_GROUP_SUMS spec (grouped) or a TGX_CHECK_NUMERIC_STATS spec (ungrouped); the outer join of the sides'
- * groups runs on the host. */
+ * groups runs on the host.  The suite JSON may carry "table_column_types": {table: {column: DataType}}, the Arrow types the
+ * caller holds for columns whose layout does not say them: a column declared "Binary" arrives in a string layout and is
+ * refused as a foreign key.  The table registered under the suite's "table_name" takes the suite's "column_types". */
 typedef struct tgx_host_table {
   const char *name;
   const char *const *column_names; /* n_columns names */
@@ -189,6 +191,10 @@ tgx_status tgx_host_cross_table_sum_json(const char *constraint_json, const char
  * child's column.)  counts_json: {"null_rows": n, "missing_rows": n, "overflow_rows": n, "missing_keys": n,
  * "entries": [[key, count], ..] ascending by key, "examples": true} as tgx_key_probe_get / tgx_key_probe_entries give
  * them; "examples": false stands for a child column of a type the reference's example collector does not read.
+ * String keys (both columns string layouts; the constraint's own "max_value_bytes": 1 .. 256, named in the config only
+ * when it was given): the entries' keys are JSON strings, ascending bytewise, and "long_rows": n counts the missing rows
+ * whose value was too long to keep (missing_rows == sum of the counts + overflow_rows + long_rows), as
+ * tgx_key_probe_strings_get / tgx_key_probe_entries_bytes give them.
  * Returns {"status", "metric", "message", "config": {the constraint as the host layer read it}}.  An unqualified column
  * and counts that contradict each other are TGX_INVALID_ARGUMENT. */
 tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *counts_json, char **out_json,

@@ -29,6 +29,7 @@ GROUP_COUNTS = 17  # COUNT(*) and COUNT(col) per group of a second column, for a
 GROUP_COUNTS_MAX_GROUPS, GROUP_COUNTS_MAX_VALUE_BYTES = 65536, 256
 KEY_PROBE = 19  # is each key of a child column in a parent's key set (Plan.set_key_probe, State.key_probe_set_parent)
 KEY_PROBE_MAX_MISSING_KEYS = 65536
+KEY_PROBE_MAX_VALUE_BYTES = 256  # of a missing key a spec on string keys keeps (Plan.set_key_probe_strings)
 GROUP_SUMS = 18  # COUNT(*), COUNT(col) and SUM(col) per group of a second column, for a bounded number of groups (Plan.set_group_sums)
 GROUP_SUMS_MAX_GROUPS, GROUP_SUMS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
@@ -243,6 +244,16 @@ class KeyProbePairs(C.Structure):
                 ("parent_count_digest", C.c_uint64), ("max_count", C.c_uint64)]
 
 
+class KeyProbeStringsParams(C.Structure):
+    """tgx_key_probe_strings_params (include/tgx.h)"""
+    _fields_ = [("max_missing_keys", C.c_uint32), ("max_value_bytes", C.c_uint32)]
+
+
+class KeyProbeStrings(C.Structure):
+    """tgx_key_probe_strings (include/tgx.h)"""
+    _fields_ = [("long_rows", C.c_uint64), ("max_value_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -393,6 +404,9 @@ def lib():
         L.tgx_key_probe_set_parent.argtypes = [vp, vp, sz, vp, u64, E]
         L.tgx_key_probe_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeSummary), E]
         L.tgx_key_probe_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), E]
+        L.tgx_plan_set_key_probe_strings.argtypes = [vp, sz, C.POINTER(KeyProbeStringsParams), E]
+        L.tgx_key_probe_strings_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeStrings), E]
+        L.tgx_key_probe_entries_bytes.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -852,6 +866,14 @@ class Plan:
         err = _Error()
         _check(lib().tgx_plan_set_key_probe_counted(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
+    def set_key_probe_strings(self, spec_index, max_missing_keys=10000, max_value_bytes=256):
+        """tgx_plan_set_key_probe_strings: the spec probes STRING keys against a set of fingerprints
+        (State.key_probe_strings); a missing key of up to max_value_bytes bytes keeps its bytes.  A spec takes one of
+        the four set_key_probe* calls"""
+        p = KeyProbeStringsParams(max_missing_keys, max_value_bytes)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_strings(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
     def set_key_probe_rows(self, spec_index):
         """tgx_plan_set_key_probe_rows: the spec gathers its column's non-NULL keys as {key, 1} records
         (State.key_probe_rows): the parent side of a counted probe when the parent's keys repeat"""
@@ -1178,6 +1200,19 @@ class State:
         _check(L.tgx_key_probe_entries(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), C.byref(err)), err)
         summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
         return summary, {e.value: e.count for e in entries[:n.value]}
+
+    def key_probe_strings(self, spec_index):
+        """tgx_key_probe_get + tgx_key_probe_strings_get + tgx_key_probe_entries_bytes of a strings spec: (summary,
+        missing) -- summary the fields of tgx_key_probe_summary plus long_rows and max_value_bytes, missing a dict
+        bytes -> rows in the library's order (ascending bytewise)"""
+        L, err = lib(), _Error()
+        s, more = KeyProbeSummary(), KeyProbeStrings()
+        _check(L.tgx_key_probe_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        _check(L.tgx_key_probe_strings_get(self.plan.h, self.h, spec_index, C.byref(more), C.byref(err)), err)
+        entries, raw = self._counted_entries(L.tgx_key_probe_entries_bytes, ValueCountEntry, spec_index)
+        summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
+        summary["long_rows"], summary["max_value_bytes"] = more.long_rows, more.max_value_bytes
+        return summary, {raw[e.offset:e.offset + e.length]: e.count for e in entries}
 
     def key_probe_rows(self, spec_index):
         """tgx_key_probe_rows_get: (device pointer or None, n_records) of a rows spec's {key, 1} records"""

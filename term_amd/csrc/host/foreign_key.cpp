@@ -5,7 +5,10 @@
 // TGX_CHECK_DISTINCT spec, its key set is exported (world 1) into the TGX_CHECK_KEY_PROBE spec of the child's column,
 // and the child is walked once: membership per row on the device, the verdict and the message on the host.  A NULL
 // parent row is no key of the set (NULL = x is not true), a NULL child row matches nothing: it is a violation unless
-// allow_nulls.  Integer keys only: every other column type is the constraint's own error, so the caller can hand the
+// allow_nulls.  Integer keys, or string keys when BOTH columns are string layouts (Utf8, LargeUtf8, Utf8View,
+// Dictionary<Int32, Utf8>): the parent's export is then the values' keyed fingerprints, the child's plan takes the
+// parent plan's fingerprint key, and the probe is a strings spec (tgx_plan_set_key_probe_strings).  Every other column
+// type, and a pair of an integer and a string column, is the constraint's own error, so the caller can hand the
 // constraint to the stock path.
 #include <string.h>
 
@@ -59,6 +62,28 @@ const Table *side_of(const Context &ctx, const std::pair<std::string, std::strin
   return table;
 }
 
+bool string_layout(int type) {
+  return type == TGX_UTF8 || type == TGX_LARGE_UTF8 || type == TGX_UTF8_VIEW || type == TGX_DICT32_UTF8;
+}
+
+// 1: the column is a string layout in every batch that has it; 0: no batch has it (an empty table); -1: another type
+int string_side(const Table &table, int index) {
+  int side = 0;
+  for (const Batch &b : table.batches)
+    if ((size_t)index < b.columns.size()) {
+      if (!string_layout(b.columns[index].type)) return -1;
+      side = 1;
+    }
+  return side;
+}
+
+// the first batch's type of the column (0: no batch has it)
+int first_type(const Table &table, int index) {
+  for (const Batch &b : table.batches)
+    if ((size_t)index < b.columns.size()) return b.columns[index].type;
+  return 0;
+}
+
 // the column's type over the table's batches (0: no batch has the column); integer keys only
 int key_type(const Table &table, int index, const std::string &qualified) {
   int type = 0;
@@ -98,15 +123,17 @@ std::pair<std::string, std::string> ForeignKeyConstraint::parse_qualified_column
 ConstraintResult ForeignKeyConstraint::verdict(const ForeignKeyCounts &c) const {
   const uint64_t total = c.missing_rows + (allow_nulls_ ? 0 : c.null_rows);
   if (total == 0) return ConstraintResult::success();
-  const std::string unique = (c.overflow_rows ? "at least " : "") + std::to_string(c.missing_keys);
+  const std::string unique = (c.overflow_rows || c.long_rows ? "at least " : "") + std::to_string(c.missing_keys);
   std::string message = "Foreign key constraint violation: " + std::to_string(total) + " values in '" + child_ +
                         "' do not exist in '" + parent_ + "' (total: " + std::to_string(total) + ", unique: " + unique + ")";
   // the examples: the max_violations_reported smallest missing keys (the reference's LIMIT has no order; a NULL takes
   // no slot here); up to 5 are listed (:387-395)
-  const size_t n = c.examples ? std::min(c.keys.size(), max_violations_) : 0;
+  // (string keys are printed raw, as the reference's join(", ") prints them)
+  const size_t n = c.examples ? std::min(c.strings ? c.str_keys.size() : c.keys.size(), max_violations_) : 0;
   if (n > 0) {
     std::string list;
-    for (size_t i = 0; i < std::min<size_t>(n, 5); i++) list += (i ? ", " : "") + std::to_string(c.keys[i]);
+    for (size_t i = 0; i < std::min<size_t>(n, 5); i++)
+      list += (i ? ", " : "") + (c.strings ? c.str_keys[i] : std::to_string(c.keys[i]));
     if (n > 5) list += ", ... (" + std::to_string(n - 5) + " more)";
     message += ". Examples: [" + list + "]";
   }
@@ -121,6 +148,16 @@ ConstraintResult ForeignKeyConstraint::evaluate_context(const Context &ctx) cons
   int ci = -1, pi = -1;
   const Table *child_table = side_of(ctx, child, &ci);
   const Table *parent_table = side_of(ctx, parent, &pi);
+  // (a column declared Binary arrives in a string layout; the reference's examples would not print its bytes)
+  for (const auto &side : {std::make_pair(child_table, ci), std::make_pair(parent_table, pi)})
+    if ((size_t)side.second < side.first->arrow_types.size() && side.first->arrow_types[side.second] == "Binary")
+      evaluation_error("column '" + (side.first == child_table && side.second == ci ? child_ : parent_) +
+                       "' is a Binary column: foreign keys of that type are not on the GPU path (TGX_CHECK_KEY_PROBE "
+                       "takes integer and string keys)");
+  // (a side without a batch has no type to object with: it goes the way of the other side)
+  const int cs = string_side(*child_table, ci), ps = string_side(*parent_table, pi);
+  if (cs >= 0 && ps >= 0 && cs + ps > 0)
+    return evaluate_strings(*child_table, ci, *parent_table, pi);
   const int child_type = key_type(*child_table, ci, child_);
   key_type(*parent_table, pi, parent_);
 
@@ -169,6 +206,69 @@ ConstraintResult ForeignKeyConstraint::evaluate_context(const Context &ctx) cons
   counts.missing_keys = s.missing_keys;
   for (uint64_t i = 0; i < n; i++) counts.keys.push_back(entries[i].value);
   counts.examples = child_type == TGX_INT64 || child_type == TGX_INT32;  // (:265-291)
+  return verdict(counts);
+}
+
+// both columns are string layouts: the same two walks over fingerprints
+ConstraintResult ForeignKeyConstraint::evaluate_strings(const Table &child_table, int ci, const Table &parent_table,
+                                                        int pi) const {
+  if (max_value_bytes_ < 1 || max_value_bytes_ > TGX_KEY_PROBE_MAX_VALUE_BYTES)
+    evaluation_error("max_value_bytes must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_VALUE_BYTES) + " (" +
+                     std::to_string(max_value_bytes_) + ")");
+  tgx_error err;
+  memset(&err, 0, sizeof(err));
+  auto check = [&](tgx_status s) {
+    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
+  };
+  check(tgx_init(nullptr, &err));
+
+  // the parent: its distinct non-NULL values as fingerprints under its plan's key
+  tgx_check_spec spec;
+  memset(&spec, 0, sizeof(spec));
+  spec.kind = TGX_CHECK_DISTINCT;
+  spec.column = pi;
+  spec.column2 = -1;
+  Handles p;
+  check(tgx_plan_create(&spec, 1, &p.plan, &err));
+  check(tgx_state_create(p.plan, nullptr, &p.state, &err));
+  for (const Batch &b : parent_table.batches) check(tgx_update(p.plan, p.state, b.columns.data(), b.columns.size(), &err));
+  const void *records = nullptr;
+  uint64_t n_records = 0;
+  check(tgx_distinct_export(p.plan, p.state, 0, 1, &records, &n_records, &err));
+
+  // the child, under the same key, against that set
+  spec.kind = TGX_CHECK_KEY_PROBE;
+  spec.column = ci;
+  Handles c;
+  check(tgx_plan_create(&spec, 1, &c.plan, &err));
+  uint8_t key[16];
+  check(tgx_plan_get_fingerprint_key(p.plan, key));
+  check(tgx_plan_set_fingerprint_key(c.plan, key, &err));
+  const tgx_key_probe_strings_params params = {max_missing_keys_, max_value_bytes_};
+  check(tgx_plan_set_key_probe_strings(c.plan, 0, &params, &err));
+  check(tgx_state_create(c.plan, nullptr, &c.state, &err));
+  check(tgx_key_probe_set_parent(c.plan, c.state, 0, records, n_records, &err));
+  for (const Batch &b : child_table.batches) check(tgx_update(c.plan, c.state, b.columns.data(), b.columns.size(), &err));
+  tgx_key_probe_summary s;
+  check(tgx_key_probe_get(c.plan, c.state, 0, &s, &err));
+  tgx_key_probe_strings more;
+  check(tgx_key_probe_strings_get(c.plan, c.state, 0, &more, &err));
+  uint64_t n = 0, n_bytes = 0;
+  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, nullptr, 0, &n, nullptr, 0, &n_bytes, &err));
+  std::vector<tgx_value_count_entry> entries((size_t)n + 1);
+  std::vector<uint8_t> bytes((size_t)n_bytes + 1);
+  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, entries.data(), n, &n, bytes.data(), n_bytes, &n_bytes, &err));
+
+  ForeignKeyCounts counts;
+  counts.strings = true;
+  counts.null_rows = s.null_rows;
+  counts.missing_rows = s.missing_rows;
+  counts.overflow_rows = s.overflow_rows;
+  counts.long_rows = more.long_rows;
+  counts.missing_keys = s.missing_keys;
+  for (uint64_t i = 0; i < n; i++)
+    counts.str_keys.emplace_back((const char *)bytes.data() + entries[i].offset, (size_t)entries[i].length);
+  counts.examples = first_type(child_table, ci) == TGX_UTF8;  // (the collector downcasts to StringArray only: :265-291)
   return verdict(counts);
 }
 

@@ -633,6 +633,13 @@ extern "C" tgx_status tgx_host_run_suite_tables_json(const char *suite_json, con
   *out_json = nullptr;
   try {
     ValidationSuite suite = suite_from_json(suite_json);
+    // {"table_column_types": {table: {column: DataType}}}: the Arrow types the caller holds for the further tables'
+    // columns, where the layout they arrive in does not say (a Binary column arrives as a string layout)
+    const json::Value doc = parse_json_text(suite_json, "suite");
+    const json::Value *declared = doc.get("table_column_types");
+    // (the suite's own table, registered under "table_name": the "column_types" the suite already carries)
+    const json::Value *own = doc.get("column_types");
+    const std::string own_name = suite.table_name();
     Context ctx;
     for (size_t k = 0; k < n_tables; k++) {
       const tgx_host_table &in = tables[k];
@@ -645,6 +652,10 @@ extern "C" tgx_status tgx_host_run_suite_tables_json(const char *suite_json, con
         batch.columns.assign(in.columns + b * in.n_columns, in.columns + (b + 1) * in.n_columns);
         t.batches.push_back(std::move(batch));
       }
+      const json::Value *types = declared ? declared->get(in.name) : nullptr;
+      if (!types && own && own_name == in.name) types = own;
+      if (types)
+        for (const std::string &column : t.column_names) t.arrow_types.push_back(types->get_str(column));
       ctx.register_table(in.name, std::move(t));
     }
     ValidationResult r = suite.run(ctx);
@@ -811,14 +822,25 @@ extern "C" tgx_status tgx_host_foreign_key_json(const char *constraint_json, con
     k.null_rows = v.get_u64("null_rows", 0);
     k.missing_rows = v.get_u64("missing_rows", 0);
     k.overflow_rows = v.get_u64("overflow_rows", 0);
+    k.long_rows = v.get_u64("long_rows", 0);
     if (v.get("examples")) k.examples = v.get_bool("examples");
     uint64_t counted = 0;
     if (const json::Value *es = v.get("entries")) {
       if (es->type != json::Value::Array) throw TermError{TermError::Internal, "entries must be a JSON array"};
       for (const json::Value &e : es->arr) {
-        if (e.type != json::Value::Array || e.arr.size() != 2 || e.arr[0].type != json::Value::Number ||
+        if (e.type != json::Value::Array || e.arr.size() != 2 ||
+            (e.arr[0].type != json::Value::Number && e.arr[0].type != json::Value::String) ||
             e.arr[1].type != json::Value::Number)
           throw TermError{TermError::Internal, "an entry is [key, count]"};
+        if (e.arr[0].type == json::Value::String) {  // string keys, ascending bytewise
+          if (!k.keys.empty() || (!k.str_keys.empty() && !(k.str_keys.back() < e.arr[0].str)))
+            throw TermError{TermError::Internal, "the entries must be ascending by key"};
+          k.strings = true;
+          k.str_keys.push_back(e.arr[0].str);
+          counted += (uint64_t)e.arr[1].as_i64();
+          continue;
+        }
+        if (k.strings) throw TermError{TermError::Internal, "the entries must be ascending by key"};
         const int64_t key = e.arr[0].as_i64();
         if (!k.keys.empty() && !(k.keys.back() < key))
           throw TermError{TermError::Internal, "the entries must be ascending by key"};
@@ -826,10 +848,11 @@ extern "C" tgx_status tgx_host_foreign_key_json(const char *constraint_json, con
         counted += (uint64_t)e.arr[1].as_i64();
       }
     }
-    k.missing_keys = v.get_u64("missing_keys", k.keys.size());
-    if (k.missing_keys != k.keys.size() || k.missing_rows != counted + k.overflow_rows)
+    const uint64_t held = k.keys.size() + k.str_keys.size();
+    k.missing_keys = v.get_u64("missing_keys", held);
+    if (k.missing_keys != held || k.missing_rows != counted + k.overflow_rows + k.long_rows)
       throw TermError{TermError::Internal, "counts JSON: missing_keys is the number of entries and missing_rows the sum "
-                                           "of their counts + overflow_rows"};
+                                           "of their counts + overflow_rows + long_rows"};
     const ConstraintResult cr = c->verdict(k);
     const std::string o =
         std::string("{\"status\": \"") +
@@ -840,7 +863,7 @@ extern "C" tgx_status tgx_host_foreign_key_json(const char *constraint_json, con
         json::quote(c->parent_column()) + ", \"allow_nulls\": " + (c->nulls_allowed() ? "true" : "false") +
         ", \"use_left_join\": " + (c->left_join() ? "true" : "false") + ", \"max_violations_reported\": " +
         std::to_string(c->violations_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) +
-        "}}";
+        (c->value_bytes_given() ? ", \"max_value_bytes\": " + std::to_string(c->value_bytes_bound()) : std::string()) + "}}";
     *out_json = dup_string(o);
     return TGX_OK;
   } catch (const TermError &e) {

@@ -1791,13 +1791,16 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     b.constraint(std::move(x));
   } else if (type == "foreign_key") {
     // {"type": "foreign_key", "child_column": "orders.customer_id", "parent_column": "customers.id", "allow_nulls": false,
-    //  "use_left_join": true, "max_violations_reported": 100, "max_missing_keys": 10000}
+    //  "use_left_join": true, "max_violations_reported": 100, "max_missing_keys": 10000, "max_value_bytes": 256}
     auto x = std::make_shared<ForeignKeyConstraint>(c.get_str("child_column"), c.get_str("parent_column"));
     x->allow_nulls(c.get_bool("allow_nulls"));
     if (c.get("use_left_join")) x->use_left_join(c.get_bool("use_left_join"));
     x->max_violations_reported((size_t)c.get_u64("max_violations_reported", 100));
     x->max_missing_keys((uint32_t)std::min<uint64_t>(
         c.get_u64("max_missing_keys", ForeignKeyConstraint::kDefaultMaxMissingKeys), UINT32_MAX));
+    if (c.get("max_value_bytes"))
+      x->max_value_bytes((uint32_t)std::min<uint64_t>(
+          c.get_u64("max_value_bytes", ForeignKeyConstraint::kDefaultMaxValueBytes), UINT32_MAX));
     b.constraint(std::move(x));
   } else if (type == "join_coverage") {
     // {"type": "join_coverage", "left_table": "orders", "right_table": "customers", "join_keys": [["customer_id", "id"]],

@@ -199,6 +199,7 @@ struct SpecRequest {
 struct ValueCounts;  // host/value_counts.h
 class Histogram;
 class Context;       // below: the SessionContext stand-in
+struct Table;        // below: a registered table's batches
 
 // ---- core/constraint.rs:187-225.  `evaluate(&SessionContext)` is split in two so scans can be fused:
 // plan() says which aggregates are needed, evaluate() turns them into the verdict.
@@ -304,15 +305,21 @@ class CrossTableSumConstraint : public Constraint {
 
 // ---- constraints/foreign_key.rs: every non-NULL value of child.c is a value of parent.p.  The parent's column is walked
 // once under a TGX_CHECK_DISTINCT spec, its key set handed to a TGX_CHECK_KEY_PROBE spec over the child's column, and the
-// child walked once: integer keys only.  What the verdict is made from, as tgx_key_probe_get / _entries give it
+// child walked once: integer keys, or string keys when both columns are string layouts (the parent's values then travel
+// as keyed fingerprints and the child's plan takes the parent plan's fingerprint key).  What the verdict is made from,
+// as tgx_key_probe_get / _entries (_strings_get / _entries_bytes) give it
 struct ForeignKeyCounts {
   uint64_t null_rows = 0, missing_rows = 0, overflow_rows = 0, missing_keys = 0;
-  std::vector<int64_t> keys;  // the missing keys held, ascending
+  uint64_t long_rows = 0;             // string keys: missing rows whose value is longer than max_value_bytes
+  std::vector<int64_t> keys;          // the missing keys held, ascending
+  std::vector<std::string> str_keys;  // ... of string keys, ascending bytewise
+  bool strings = false;
   bool examples = true;       // the child column is of a type the reference's collector downcasts (:265-291)
 };
 class ForeignKeyConstraint : public Constraint {
  public:
   static constexpr uint32_t kDefaultMaxMissingKeys = 10000;
+  static constexpr uint32_t kDefaultMaxValueBytes = 256;
   ForeignKeyConstraint(std::string child_column, std::string parent_column)  // "table.column" each (:78-91)
       : child_(std::move(child_column)), parent_(std::move(parent_column)) {}
   ForeignKeyConstraint &allow_nulls(bool allow) { allow_nulls_ = allow; return *this; }
@@ -321,6 +328,9 @@ class ForeignKeyConstraint : public Constraint {
   // this layer's own: the missing keys the child's table on the device is sized for (1 .. 65 536).  Rows beyond it are
   // counted (overflow): the verdict and the metric stand, `unique` reads "at least n"
   ForeignKeyConstraint &max_missing_keys(uint32_t n) { max_missing_keys_ = n; return *this; }
+  // this layer's own, string keys only: the bytes a missing key may have to be kept (1 .. 256).  Missing rows with a
+  // longer value are counted (long rows): the verdict and the metric stand, `unique` reads "at least n"
+  ForeignKeyConstraint &max_value_bytes(uint32_t n) { max_value_bytes_ = n; value_bytes_given_ = true; return *this; }
 
   const std::string &child_column() const { return child_; }
   const std::string &parent_column() const { return parent_; }
@@ -328,6 +338,8 @@ class ForeignKeyConstraint : public Constraint {
   bool left_join() const { return use_left_join_; }
   size_t violations_reported() const { return max_violations_; }
   uint32_t missing_keys_bound() const { return max_missing_keys_; }
+  uint32_t value_bytes_bound() const { return max_value_bytes_; }
+  bool value_bytes_given() const { return value_bytes_given_; }  // (the JSON form names the option only then)
 
   std::string name() const override { return "foreign_key"; }
   std::vector<SpecRequest> plan() const override { return {}; }
@@ -341,10 +353,13 @@ class ForeignKeyConstraint : public Constraint {
   ConstraintResult verdict(const ForeignKeyCounts &counts) const;
 
  private:
+  ConstraintResult evaluate_strings(const Table &child_table, int ci, const Table &parent_table, int pi) const;
   std::string child_, parent_;
   bool allow_nulls_ = false, use_left_join_ = true;
   size_t max_violations_ = 100;
   uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
+  uint32_t max_value_bytes_ = kDefaultMaxValueBytes;
+  bool value_bytes_given_ = false;
 };
 
 // ---- constraints/join_coverage.rs: the match rate of L LEFT / RIGHT JOIN R ON L.l = R.r, SUM(CASE WHEN the far side's key

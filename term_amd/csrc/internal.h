@@ -265,6 +265,10 @@ struct KeyProbeTask {
   int column, spec_index;
   bool set, counted;
   bool rows;  // tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
+  // tgx_plan_set_key_probe_strings: the column is a string column, the set holds fingerprints, and a missing key of up
+  // to max_value_bytes bytes keeps its bytes
+  bool strings;
+  uint32_t max_value_bytes;
   tgx_key_probe_params params;
 };
 

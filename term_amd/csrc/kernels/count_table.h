@@ -115,4 +115,53 @@ __device__ __forceinline__ unsigned long long vc_shfl64(unsigned long long v, in
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// ---- what the kinds that count string keys share (valuecounts.hip, keyprobe_strings.hip) ---------------------------------
+// a string key (fa, fb) whose bytes are [p, p + len), with its weight, into a task's global table; a probe sequence
+// that runs out adds the weight to *overflow
+__device__ __forceinline__ void vc_insert_global128(const ValueCountsTable &t, unsigned long long fa,
+                                                    unsigned long long fb, unsigned long long weight, uintptr_t p,
+                                                    uint32_t len, unsigned long long *overflow) {
+  uint64_t h = fa & t.mask;
+  for (uint32_t probe = 0; probe < kValueCountsProbes; probe++) {
+    unsigned long long a = vc_peek(&t.keys[h]);
+    if (a == kEmptyKey) a = atomicCAS(&t.keys[h], (unsigned long long)kEmptyKey, fa);
+    if (a == kEmptyKey || a == fa) {
+      unsigned long long b = vc_peek(&t.keys2[h]);
+      const bool made = b == kEmptyKey && (b = atomicCAS(&t.keys2[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
+      if (made) {  // this lane made the entry: its bytes go to the slot's place in the store
+        global_u8_ptr src = (global_u8_ptr)p;
+        uint8_t *dst = t.store + h * (uint64_t)t.max_value_bytes;
+        for (uint32_t i = 0; i < len; i++) dst[i] = src[i];
+        t.lens[h] = len;
+      }
+      if (made || b == fb) {
+        atomicAdd(&t.counts[h], weight);
+        return;
+      }
+    }
+    h = (h + 1) & t.mask;
+  }
+  atomicAdd(overflow, weight);
+}
+
+// Equal fingerprints combined within the wave, in up to four rounds: a round's leader (the first lane that is still
+// pending) calls insert(weight) with the number of lanes that hold its key; whoever is pending after the rounds calls
+// insert(1) for itself.  Every lane of the wave takes part (`live`: the lane has a key).
+template <class Insert>
+__device__ __forceinline__ void vc_wave_combine128(bool live, unsigned long long fa, unsigned long long fb, int lane,
+                                                   Insert insert) {
+  unsigned long long todo = __ballot(live);
+  bool pending = live;
+  for (int round = 0; round < 4 && todo != 0; round++) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned long long la = vc_shfl64(fa, leader), lb = vc_shfl64(fb, leader);
+    const bool mine = pending && fa == la && fb == lb;
+    const unsigned long long same = __ballot(mine);
+    if (lane == leader) insert((uint32_t)__popcll(same));
+    pending = pending && !mine;
+    todo &= ~same;
+  }
+  if (pending) insert(1u);
+}
+
 }  // namespace tgx

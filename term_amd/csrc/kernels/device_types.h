@@ -412,6 +412,22 @@ struct KeyProbeBuild {
   // and the marker key's count
   unsigned long long zero_counts, sum_piece[3], count_digest, max_count, marker_count;
 };
+// A STRINGS task (kernels/keyprobe_strings.hip): the child column is a string column and the set holds the parent's
+// values as keyed 128-bit fingerprints (route 5: `mask + 1` 16-byte {fa, fb} slots at load <= 0.5, probed linearly from
+// fa & mask; a slot is free while its fa word is kEmptyKey, which fingerprint.h never produces).  The missing keys are
+// counted in a table laid out as ValueCountsTable's string half is (a ValueCountsTable whose `words` are the task's
+// kKeyProbeWords counters).  No string has the marker's bits: the word counts the missing rows whose value is longer
+// than max_value_bytes instead.
+enum { kKpLong = kKpMarker, kKpRouteStrings = 5 };
+struct KeyProbeStringSet {
+  const unsigned long long *slots;  // mask + 1 slots of {fa, fb}, 16-byte aligned; null: the empty set
+  uint64_t mask;
+};
+// what the build of such a set leaves behind: the distinct fingerprints, the wrapping sum of
+// mix64(mix64(fa ^ kKeyProbeDigestSalt) ^ fb) over them, and the records that hold a marker word (refused by the host)
+struct KeyProbeStringsBuild {
+  unsigned long long keys, digest, marker_records;
+};
 constexpr uint64_t kKeyProbeDigestSalt = 0x9e3779b97f4a7c15ULL;
 constexpr uint64_t kKeyProbeCountSalt = 0xc2b2ae3d27d4eb4fULL;
 constexpr int kKpPieceBits = 21;

@@ -24,7 +24,7 @@
 //                     the value (a full table: straight into the global one).  At the end every occupied LDS slot is
 //                     one global insert with its count.  The lane that claims a GLOBAL slot copies the value's bytes
 //                     and length into the slot's place in the value store -- on the device, in the same stream.
-//   dictionary route  value_counts_dict_count_kernel counts the INDICES into one 64-bit cell per dictionary entry (up to
+//   dictionary route  value_counts_dict_count_kernel (dict_count.h) counts the INDICES into one 64-bit cell per dictionary entry (up to
 //                     16384 entries through 32-bit cells in LDS, bin_count.h's idiom; above that with global atomics);
 //                     value_counts_dict_insert_kernel then takes a lane per entry with a non-zero count, fingerprints the
 //                     entry and inserts it with its count (rows of NULL entries are counted nowhere: they are NULLs).
@@ -36,6 +36,7 @@
 #include "bin_count.h"
 #include "count_table.h"
 #include "device_types.h"
+#include "dict_count.h"
 #include "fingerprint.h"
 #include "row_walk.h"
 
@@ -43,40 +44,14 @@ namespace tgx {
 
 namespace {
 
-// ---- the table primitive (vc_peek, vc_claim, the LDS table of 128-bit keys: count_table.h) -----------------------------
+// ---- the table primitive (vc_peek, vc_claim, the LDS table of 128-bit keys, the global insert of one and the wave's
+// combining of equal ones: count_table.h) ---------------------------------------------------------------------------------
 // a numeric key with its weight into the task's global table
 __device__ __forceinline__ void vc_insert_global(const ValueCountsTable &t, unsigned long long key,
                                                  unsigned long long weight) {
   const int64_t s = vc_claim<uint64_t>(t.keys, t.mask, mix64(key ^ t.salt) & t.mask, key, kValueCountsProbes);
   if (s >= 0) atomicAdd(&t.counts[s], weight);
   else atomicAdd(&t.words[kVcOverflow], weight);
-}
-
-// a string key (fa, fb) whose bytes are [p, p + len), with its weight
-__device__ __forceinline__ void vc_insert_global128(const ValueCountsTable &t, unsigned long long fa,
-                                                    unsigned long long fb, unsigned long long weight, uintptr_t p,
-                                                    uint32_t len) {
-  uint64_t h = fa & t.mask;
-  for (uint32_t probe = 0; probe < kValueCountsProbes; probe++) {
-    unsigned long long a = vc_peek(&t.keys[h]);
-    if (a == kEmptyKey) a = atomicCAS(&t.keys[h], (unsigned long long)kEmptyKey, fa);
-    if (a == kEmptyKey || a == fa) {
-      unsigned long long b = vc_peek(&t.keys2[h]);
-      const bool made = b == kEmptyKey && (b = atomicCAS(&t.keys2[h], (unsigned long long)kEmptyKey, fb)) == kEmptyKey;
-      if (made) {  // this lane made the entry: its bytes go to the slot's place in the store
-        global_u8_ptr src = (global_u8_ptr)p;
-        uint8_t *dst = t.store + h * (uint64_t)t.max_value_bytes;
-        for (uint32_t i = 0; i < len; i++) dst[i] = src[i];
-        t.lens[h] = len;
-      }
-      if (made || b == fb) {
-        atomicAdd(&t.counts[h], weight);
-        return;
-      }
-    }
-    h = (h + 1) & t.mask;
-  }
-  atomicAdd(&t.words[kVcOverflow], weight);
 }
 
 }  // namespace
@@ -157,20 +132,10 @@ __global__ __launch_bounds__(256) void value_counts_utf8_kernel(const Utf8ColDes
         live = true;
       }
     }
-    unsigned long long todo = __ballot(live);
-    bool pending = live;
-    for (int round = 0; round < 4 && todo != 0; round++) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const unsigned long long la = vc_shfl64(fa, leader), lb = vc_shfl64(fb, leader);
-      const bool mine = pending && fa == la && fb == lb;
-      const unsigned long long same = __ballot(mine);
-      if (lane == leader && !vc_insert_lds128(lds, fa, fb, (uint32_t)__popcll(same), (unsigned long long)i))
-        vc_insert_global128(t, fa, fb, (unsigned long long)__popcll(same), p, (uint32_t)len);
-      pending = pending && !mine;
-      todo &= ~same;
-    }
-    if (pending && !vc_insert_lds128(lds, fa, fb, 1u, (unsigned long long)i))
-      vc_insert_global128(t, fa, fb, 1ull, p, (uint32_t)len);
+    vc_wave_combine128(live, fa, fb, lane, [&](uint32_t weight) {
+      if (!vc_insert_lds128(lds, fa, fb, weight, (unsigned long long)i))
+        vc_insert_global128(t, fa, fb, (unsigned long long)weight, p, (uint32_t)len, &t.words[kVcOverflow]);
+    });
   }
   __syncthreads();
   // every occupied LDS slot is one global insert with its count; its bytes are those of the row it remembers
@@ -181,7 +146,7 @@ __global__ __launch_bounds__(256) void value_counts_utf8_kernel(const Utf8ColDes
     uintptr_t p;
     uint64_t len;
     utf8_value_of(d, d.offset + (int64_t)lds.row[s], &p, &len);
-    vc_insert_global128(t, fa, fb, (unsigned long long)n, p, (uint32_t)len);
+    vc_insert_global128(t, fa, fb, (unsigned long long)n, p, (uint32_t)len, &t.words[kVcOverflow]);
   }
   // (tail_flush adds to out[0] and out[1], non-zero sums only: both pairs lie within the task's four words)
   tail_flush(non_null, 0u, t.words + kVcNonNull);
@@ -189,46 +154,7 @@ __global__ __launch_bounds__(256) void value_counts_utf8_kernel(const Utf8ColDes
 }
 
 // ---- dictionary route ---------------------------------------------------------------------------------------------------
-// the rows' indices into cells[dict_length]; an index outside the dictionary is a row without a value: it is counted
-// as a NULL row (include/tgx.h says so), never read
-template <bool kLds>
-__global__ __launch_bounds__(256) void value_counts_dict_count_kernel(const int32_t *__restrict__ indices,
-                                                                      const uint8_t *__restrict__ validity,
-                                                                      int64_t offset, int64_t length, int64_t dict_length,
-                                                                      unsigned long long *__restrict__ cells) {
-  global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)validity;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  // up to kValueCountsDictLdsCells entries: the workgroup's cells are 32-bit counters in LDS (bin_count.h), flushed once
-  __shared__ unsigned int lcells[kLds ? kValueCountsDictLdsCells : 1];
-  if (kLds) {
-    for (uint32_t c = threadIdx.x; c < (uint32_t)dict_length; c += 256) lcells[c] = 0;
-    __syncthreads();
-  }
-  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < length; base += stride) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t slot = offset + i;
-    bool live = i < length && (!vbits || TGX_VALID_BIT(vbits, slot));
-    int32_t idx = live ? indices[slot] : 0;
-    live = live && idx >= 0 && (int64_t)idx < dict_length;
-    if (kLds) {
-      bin_add(lcells, live, (uint32_t)idx);
-      continue;
-    }
-    const unsigned long long todo = __ballot(live);
-    if (todo == 0) continue;
-    const int leader = __ffsll((long long)todo) - 1;
-    const int32_t first = __shfl(idx, leader, 64);
-    const unsigned long long same = __ballot(live && idx == first);
-    if (lane == leader) atomicAdd(&cells[first], (unsigned long long)__popcll(same));
-    else if (live && idx != first) atomicAdd(&cells[idx], 1ull);
-  }
-  if (kLds) {
-    __syncthreads();
-    bin_flush<256>(lcells, (uint32_t)dict_length, cells);
-  }
-}
-
+// (the rows' indices into cells[dict_length]: dict_count.h)
 // `d`: the dictionary's values as a string column; a lane per entry with a non-zero count
 __global__ __launch_bounds__(256) void value_counts_dict_insert_kernel(const Utf8ColDesc d,
                                                                        const unsigned long long *__restrict__ cells,
@@ -249,7 +175,7 @@ __global__ __launch_bounds__(256) void value_counts_dict_insert_kernel(const Utf
     }
     uint64_t fa, fb;
     fingerprint(d.key, p, len, &fa, &fb);
-    vc_insert_global128(t, fa, fb, n, p, (uint32_t)len);
+    vc_insert_global128(t, fa, fb, n, p, (uint32_t)len, &t.words[kVcOverflow]);
   }
 }
 
@@ -265,12 +191,7 @@ void launch_value_counts_utf8(const Utf8ColDesc &d, const ValueCountsTable &t, h
 void launch_value_counts_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
                               const Utf8ColDesc &dict, unsigned long long *cells, const ValueCountsTable &t,
                               hipStream_t stream) {
-  if (dict.length <= (int64_t)kValueCountsDictLdsCells)  // (fewer workgroups: each one flushes its cells once)
-    hipLaunchKernelGGL(value_counts_dict_count_kernel<true>, dim3(std::min(grid_for((uint64_t)length), 1024)), dim3(256),
-                       0, stream, indices, validity, offset, length, dict.length, cells);
-  else
-    hipLaunchKernelGGL(value_counts_dict_count_kernel<false>, dim3(grid_for((uint64_t)length)), dim3(256), 0, stream,
-                       indices, validity, offset, length, dict.length, cells);
+  launch_dict_count(indices, validity, offset, length, dict.length, cells, stream);
   hipLaunchKernelGGL(value_counts_dict_insert_kernel, dim3(grid_for((uint64_t)dict.length)), dim3(256), 0, stream, dict,
                      cells, t);
 }

@@ -17,6 +17,11 @@
 // A ROWS task (tgx_plan_set_key_probe_rows) probes nothing: it gathers its column's non-NULL keys as {key, 1} records in
 // device memory, the parent side of a counted probe when the parent's keys repeat (a DISTINCT export knows a key as seen
 // once or more than once, not how often).  Its records stay with the state: such a state does not merge or serialize.
+// A STRINGS task (tgx_plan_set_key_probe_strings; kernels/keyprobe_strings.hip) reads a string column against a set of
+// keyed 128-bit fingerprints (route 5, built from a DISTINCT export's 32-byte records).  Its missing keys keep their bytes:
+// its table is laid out as VALUE_COUNTS's string table is, its entries are KeyedEntries::strs, and it has one more row
+// class, the missing rows whose value is longer than max_value_bytes (long_rows, in the marker's word: no string has the
+// marker's bits).  Merges, blobs and the cross-rank step unite its missing keys by BYTES.
 // `pairs` never wraps: the host holds an upper bound, max_count * rows a batch, in checked arithmetic, and refuses the
 // batch, merge or blob that could carry it past 2^64 - 1.
 // The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
@@ -36,6 +41,13 @@ void launch_key_probe_build_hash(const void *recs, uint64_t n, unsigned long lon
 void launch_key_probe_rows(const ComomentColDesc &d, unsigned long long *recs, uint64_t cap, unsigned long long *cursor,
                            int blocks, hipStream_t stream);
 void launch_key_probe(const KeyProbeLaunch &L, int route, int n_tasks, int blocks, hipStream_t stream);
+void launch_key_probe_build_strings(const void *recs, uint64_t n, unsigned long long *slots, uint64_t mask,
+                                    KeyProbeStringsBuild *b, hipStream_t stream);
+void launch_key_probe_utf8(const Utf8ColDesc &d, const KeyProbeStringSet &set, const ValueCountsTable &t,
+                           hipStream_t stream);
+void launch_key_probe_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
+                           const Utf8ColDesc &dict, unsigned long long *cells, const KeyProbeStringSet &set,
+                           const ValueCountsTable &t, hipStream_t stream);
 
 namespace {
 
@@ -49,6 +61,7 @@ struct ProbeHost : KeyedEntries<uint64_t> {
   uint64_t parent_keys = 0, parent_digest = 0;
   // a counted task: the rest of its set's identity, the set's largest count, and the matched pairs
   uint64_t parent_rows = 0, parent_count_digest = 0, max_count = 0, pairs = 0;
+  uint64_t long_rows = 0;  // a strings task: missing rows whose value is longer than max_value_bytes
   bool holds_counts() const { return seen != 0 || size() != 0; }
   bool same_parent(const ProbeHost &o) const {
     return parent_keys == o.parent_keys && parent_digest == o.parent_digest && parent_rows == o.parent_rows &&
@@ -84,13 +97,17 @@ struct ProbeKind {
   static ProbeHost fresh(const KeyProbeTask &) { return ProbeHost(); }
   static size_t shape(const ProbeHost &) { return 0; }  // (the sets' identities: ProbeCheck::merge_from)
   // the counters; the table's entries follow in gather_extra
-  static ProbeHost from_device(const KeyProbeTask &, int64_t rows, const NoRange &, const unsigned long long *w) {
+  static ProbeHost from_device(const KeyProbeTask &t, int64_t rows, const NoRange &, const unsigned long long *w) {
     ProbeHost d;
     d.seen = (uint64_t)rows;
     d.non_null = w[kKpNonNull];
     d.matched = w[kKpMatched];
     d.overflow_rows = w[kKpOverflow];
     d.pairs = w[kKpPairs];
+    if (t.strings) {  // (no string has the marker's bits)
+      d.long_rows = w[kKpLong];
+      return d;
+    }
     if (w[kKpMarker]) {
       d.kind = kIntKeys;
       d.ints[(int64_t)kEmptyKey] = w[kKpMarker];
@@ -102,6 +119,7 @@ struct ProbeKind {
     a.non_null += b.non_null;
     a.matched += b.matched;
     a.overflow_rows += b.overflow_rows;
+    a.long_rows += b.long_rows;
     a.pairs += b.pairs;  // (the callers have held the sum against 2^64 - 1: ProbeCheck::pairs_fit)
     a.add_entries(b);
     if (!a.known && b.known) a.take_parent(b);
@@ -112,15 +130,23 @@ struct ProbeKind {
   //   n_entries x { i64 key, u64 count }, ascending by key }
   // a counted task: the second u32 0 is 1, and { u64 parent_rows, parent_count_digest, max_count, pairs } stand between
   // n_entries and the entries
+  // a strings task: the second u32 0 is 2, { u32 max_value_bytes, u32 0, u64 long_rows } stand between n_entries and the
+  // entries, and an entry is { u32 length, u8 bytes[length], u64 count }, ascending bytewise
+  static uint32_t mode(const KeyProbeTask &t) { return t.counted ? 1u : t.strings ? 2u : 0u; }
   static void write(const KeyProbeTask &t, const ProbeHost &h, Writer &w) {
     w.pod(t.params);
     w.pod((uint32_t)(h.known ? 1 : 0));
-    w.pod((uint32_t)(t.counted ? 1 : 0));
+    w.pod(mode(t));
     const uint64_t words[7] = {h.parent_keys, h.parent_digest, h.seen, h.non_null, h.matched, h.overflow_rows, h.size()};
     w.pod(words);
     if (t.counted) {
       const uint64_t more[4] = {h.parent_rows, h.parent_count_digest, h.max_count, h.pairs};
       w.pod(more);
+    }
+    if (t.strings) {
+      w.pod(t.max_value_bytes);
+      w.pod((uint32_t)0);
+      w.pod(h.long_rows);
     }
     keyed_write_entries(h, CountWire(), w);
   }
@@ -132,20 +158,35 @@ struct ProbeKind {
     uint64_t words[7], more[4] = {0, 0, 0, 0};
     r.get(words, sizeof(words));
     if (!r.ok) return TGX_OK;
-    if (pad != (t.counted ? 1u : 0u))
+    if (pad != mode(t))
       return fail(err, TGX_INVALID_ARGUMENT,
-                  pad > 1 ? "malformed state blob (KEY_PROBE task %zu: parent set)"
-                          : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
+                  pad > 2 ? "malformed state blob (KEY_PROBE task %zu: parent set)"
+                  : pad == 2 || t.strings
+                      ? "KEY_PROBE task %zu: the blob was counted under the other mode (integer / string keys) than the plan's"
+                      : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
                   k);
     if (t.counted) r.get(more, sizeof(more));
+    uint32_t value_bytes = 0, value_pad = 0;
+    uint64_t long_rows = 0;
+    if (t.strings) {
+      value_bytes = r.pod<uint32_t>();
+      value_pad = r.pod<uint32_t>();
+      long_rows = r.pod<uint64_t>();
+    }
     if (!r.ok) return TGX_OK;
+    if (t.strings && value_pad != 0)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: string keys)", k);
+    if (t.strings && value_bytes != t.max_value_bytes)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "KEY_PROBE task %zu: the blob was counted under other parameters (max_value_bytes %u) than the plan's "
+                  "(%u)", k, value_bytes, t.max_value_bytes);
     if (p.max_missing_keys != t.params.max_missing_keys || p.reserved != t.params.reserved)
       return fail(err, TGX_INVALID_ARGUMENT,
                   "KEY_PROBE task %zu: the blob was counted under other parameters (max_missing_keys %u) than the plan's "
                   "(%u)", k, p.max_missing_keys, t.params.max_missing_keys);
     const uint64_t seen = words[2], non_null = words[3], n = words[6];
     if (known > 1 || (!known && (words[0] != 0 || words[1] != 0 || seen != 0 || n != 0 || more[0] != 0 || more[1] != 0 ||
-                                 more[2] != 0 || more[3] != 0)))
+                                 more[2] != 0 || more[3] != 0 || long_rows != 0)))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: parent set)", k);
     // a counted set: keys <= rows < 2^63, the largest count is one of them; matched <= pairs <= matched * max_count
     if (t.counted) {
@@ -157,13 +198,16 @@ struct ProbeKind {
         return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: counted set and pairs)", k);
     }
     uint64_t counted = 0;
-    TGX_TRY(keyed_read_entries("KEY_PROBE", "key", k, r, kIntKeys, n, 0, CountWire(), h, &counted, err));
+    TGX_TRY(keyed_read_entries("KEY_PROBE", "key", k, r, t.strings ? kByteKeys : kIntKeys, n, t.max_value_bytes,
+                               CountWire(), h, &counted, err));
     if (!r.ok) return TGX_OK;
-    // matched + counted + overflow_rows == non_null <= seen
-    if (non_null > seen || !terms_make(non_null, {words[4], counted, words[5]}))
+    // matched + counted + overflow_rows (+ long_rows) == non_null <= seen
+    if (non_null > seen || !terms_make(non_null, {words[4], counted, words[5], long_rows}))
       return fail(err, TGX_INVALID_ARGUMENT,
-                  "malformed state blob (KEY_PROBE task %zu: matched + counted + overflow_rows != non_null)", k);
-    h.kind = n ? kIntKeys : kNoKeys;
+                  "malformed state blob (KEY_PROBE task %zu: matched + counted + overflow_rows%s != non_null)", k,
+                  t.strings ? " + long_rows" : "");
+    h.kind = !n ? kNoKeys : t.strings ? kByteKeys : kIntKeys;
+    h.long_rows = long_rows;
     h.known = known != 0;
     h.parent_keys = words[0];
     h.parent_digest = words[1];
@@ -183,7 +227,8 @@ struct ProbeKind {
 struct ParentSet {
   bool has = false;
   int route = kKpRouteEmpty;
-  DevBuf buf;  // the bitmap's words, the table's keys, the count array or the table's {key, count} slots
+  // the bitmap's words, the table's keys, the count array, the table's {key, count} slots or (strings) {fa, fb} slots
+  DevBuf buf;
   uint64_t base = 0, range = 0, mask = 0;
   uint32_t has_marker = 0;
   uint64_t keys = 0, digest = 0;
@@ -208,10 +253,15 @@ struct ProbeCheck final : CountedState<ProbeKind> {
   // per rows task: the gathered records and the records there is room for
   std::vector<DevBuf> gathered;
   std::vector<uint64_t> gathered_cap;
+  std::vector<DevBuf> cells;  // per strings task: the dictionary route's per-entry cells
 
   explicit ProbeCheck(const tgx_plan *plan)
       : CountedState(plan), tasks(plan->key_probes), parent(plan->key_probes.size()), pairs_bound(plan->key_probes.size(), 0),
-        gathered(plan->key_probes.size()), gathered_cap(plan->key_probes.size(), 0) {}
+        gathered(plan->key_probes.size()), gathered_cap(plan->key_probes.size(), 0), cells(plan->key_probes.size()) {}
+
+  // a strings task's table: two key words, the counts, the lengths, the bytes (keyed_state.h's string layout)
+  size_t lens_at(size_t k) const { return table[k].extra_at(); }
+  size_t store_at(size_t k) const { return lens_at(k) + (size_t)table[k].slots * 4; }
 
   // a state that has gathered rows keeps them to itself
   tgx_status rows_stay(const char *what, tgx_error *err) const {
@@ -222,7 +272,15 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
-  void decode_slot(size_t, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
+  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
+    if (tasks[k].strings) {
+      const uint64_t *keys = (const uint64_t *)h;
+      if (keys[table[k].slots + s] == kEmptyKey) return;  // (claimed, not settled: nothing was counted into it yet)
+      const uint32_t most = tasks[k].max_value_bytes, len = std::min(((const uint32_t *)(h + lens_at(k)))[s], most);
+      o.kind = kByteKeys;
+      o.strs[std::string((const char *)h + store_at(k) + (size_t)s * most, len)] += count;
+      return;
+    }
     o.kind = kIntKeys;
     o.ints[(int64_t)((const uint64_t *)h)[s]] += count;
   }
@@ -275,6 +333,36 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
+  // route 5: the set of strings task k from `n` 32-byte {hash_a, hash_b, count, 0} records; one wait
+  tgx_status build_strings(tgx_state *st, size_t k, const void *recs, uint64_t n, ParentSet *s, tgx_error *err) {
+    if (n == 0) return TGX_OK;
+    ProfScope ps(st, "key_probe_build", n * 32);
+    DevBuf d_build;
+    HIP_TRY(d_build.reserve(sizeof(KeyProbeStringsBuild)));
+    HIP_TRY(hipMemsetAsync(d_build.p, 0, sizeof(KeyProbeStringsBuild), st->stream));
+    s->route = kKpRouteStrings;
+    uint64_t slots = 2;
+    while (slots < 2 * n) slots <<= 1;
+    s->mask = slots - 1;
+    HIP_TRY(s->buf.reserve((size_t)slots * 16));
+    HIP_TRY(hipMemsetAsync(s->buf.p, 0xFF, (size_t)slots * 16, st->stream));  // (every word: kEmptyKey)
+    launch_key_probe_build_strings(recs, n, s->buf.as<unsigned long long>(), s->mask, d_build.as<KeyProbeStringsBuild>(),
+                                   st->stream);
+    HIP_TRY(hipGetLastError());
+    KeyProbeStringsBuild b;
+    HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    if (b.marker_records) {
+      parent[k] = ParentSet();  // (a refused set leaves the state without one: the set it had is dropped)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "spec %d: %llu records of the parent set hold the free-slot marker (all ones) in hash_a or hash_b, which "
+                  "no fingerprint is", tasks[k].spec_index, (unsigned long long)b.marker_records);
+    }
+    s->keys = b.keys;
+    s->digest = b.digest;
+    return TGX_OK;
+  }
+
   tgx_status set_parent(tgx_state *st, size_t k, const void *recs, uint64_t n, tgx_error *err) {
     if (tasks[k].rows)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check that gathers rows takes no parent set",
@@ -290,7 +378,9 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     TGX_TRY(device_init(st, err));
     ParentSet s;
     s.has = true;
-    if (n > 0) {
+    if (tasks[k].strings) {
+      TGX_TRY(build_strings(st, k, recs, n, &s, err));
+    } else if (n > 0) {
       ProfScope ps(st, "key_probe_build", n * 16);
       DevBuf d_build;
       HIP_TRY(d_build.reserve(sizeof(KeyProbeBuild)));
@@ -384,6 +474,17 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     TGX_TRY(device_init(st, err));
     table_cache_ok = false;
     for (size_t k = 0; k < tasks.size(); k++) {
+      if (tasks[k].strings) {
+        const int type = dev[tasks[k].column].type;
+        if (!is_any_string(type) && type != TGX_DICT32_UTF8)
+          return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on string keys takes string columns (%d)", type);
+        if (!parent[k].has)
+          return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
+                      tasks[k].spec_index);
+        if (!table[k].live)
+          TGX_TRY(open_table(st, k, tasks[k].params.max_missing_keys, 2, 4 + (size_t)tasks[k].max_value_bytes, err));
+        continue;
+      }
       // (an Int64 view: update_validate refuses what is not widened to one)
       if (dev[tasks[k].column].type != TGX_INT64)
         return fail(err, TGX_UNSUPPORTED, "KEY_PROBE takes integer columns (%d)", dev[tasks[k].column].type);
@@ -400,7 +501,7 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     for (int route = kKpRouteEmpty; route <= kKpRouteCountHash; route++) {
       std::vector<size_t> slots;
       for (size_t k = 0; k < tasks.size(); k++)
-        if (parent[k].route == route && !tasks[k].rows) slots.push_back(k);
+        if (parent[k].route == route && !tasks[k].rows && !tasks[k].strings) slots.push_back(k);
       for (size_t t0 = 0; t0 < slots.size(); t0 += kMaxKeyProbePerLaunch) {
         const int n = (int)std::min<size_t>(kMaxKeyProbePerLaunch, slots.size() - t0);
         KeyProbeLaunch L;
@@ -435,7 +536,48 @@ struct ProbeCheck final : CountedState<ProbeKind> {
         HIP_TRY(hipGetLastError());
       }
     }
+    for (size_t k = 0; k < tasks.size(); k++)
+      if (tasks[k].strings) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
     for (size_t k = 0; k < tasks.size(); k++) device_rows[k] += nrows;
+    return TGX_OK;
+  }
+
+  // one batch of strings task k: a row per lane, or the dictionary's two steps (VALUE_COUNTS's routes)
+  tgx_status probe_strings(tgx_state *st, size_t k, const tgx_column &x, int64_t nrows, tgx_error *err) {
+    const tgx_plan *plan = st->plan;
+    const ParentSet &s = parent[k];
+    KeyProbeStringSet set;
+    set.slots = s.route == kKpRouteStrings ? s.buf.as<unsigned long long>() : nullptr;
+    set.mask = s.mask;
+    ValueCountsTable t;
+    memset(&t, 0, sizeof(t));
+    uint8_t *base = table[k].buf.as<uint8_t>();
+    t.keys = (unsigned long long *)base;
+    t.keys2 = t.keys + table[k].slots;
+    t.counts = (unsigned long long *)(base + table[k].counts_at());
+    t.lens = (uint32_t *)(base + lens_at(k));
+    t.store = base + store_at(k);
+    t.words = d_counts.as<unsigned long long>() + word_off[k];  // (the task's kKeyProbeWords counters)
+    t.mask = table[k].slots - 1;
+    t.max_value_bytes = tasks[k].max_value_bytes;
+    // (per-lane and LDS counters are 32-bit: the launchers take up to 2048 workgroups, 1024 for the dictionary's indices)
+    TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
+    if (x.type != TGX_DICT32_UTF8) {
+      ProfScope ps(st, "key_probe", 0);
+      launch_key_probe_utf8(string_desc(x, x.variadic, plan->fp_key), set, t, st->stream);
+    } else {
+      const tgx_column *dc = x.dictionary;
+      if (!dc || !is_string(dc->type)) return fail(err, TGX_INVALID_ARGUMENT, "KEY_PROBE: malformed dictionary");
+      if (dc->length > 0) {  // (without entries every row is a row without a value)
+        const size_t bytes = (size_t)dc->length * 8;
+        HIP_TRY(cells[k].reserve_roomy(bytes));
+        HIP_TRY(hipMemsetAsync(cells[k].p, 0, bytes, st->stream));
+        ProfScope ps(st, "key_probe", (uint64_t)x.length * 4);
+        launch_key_probe_dict((const int32_t *)x.values, x.validity, x.offset, x.length,
+                              string_desc(*dc, nullptr, plan->fp_key), cells[k].as<unsigned long long>(), set, t, st->stream);
+      }
+    }
+    HIP_TRY(hipGetLastError());
     return TGX_OK;
   }
 
@@ -556,8 +698,16 @@ void keyprobe_mark_columns(tgx_plan *plan) {
   for (const KeyProbeTask &t : plan->key_probes) side_mark(plan, ProbeCheck::kIndex, t.column, true);
 }
 
-tgx_status keyprobe_check_column(const tgx_plan *, int column, const tgx_column &c, tgx_error *err) {
+tgx_status keyprobe_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err) {
   const int type = c.type;
+  // a strings task takes the string layouts and nothing else; every other task refuses them (below)
+  bool strings = false, others = false;
+  for (const KeyProbeTask &t : plan->key_probes)
+    if (t.column == column) (t.strings ? strings : others) = true;
+  if (strings && !is_any_string(type) && type != TGX_DICT32_UTF8)
+    return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE on string keys takes string columns, not %s (type %d)", column,
+                refused_as_key(type) ? type_name(type) : "integers", type);
+  if (strings && !others) return TGX_OK;
   if (refused_as_key(type))
     return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE takes integer columns, not %s (type %d)", column,
                 type_name(type), type);
@@ -568,6 +718,15 @@ tgx_status keyprobe_check_column(const tgx_plan *, int column, const tgx_column 
   return TGX_OK;
 }
 
+bool keyprobe_blob_keyed(tgx_state *st) {
+  ProbeCheck *c = static_cast<ProbeCheck *>(ProbeCheck::of(st));
+  if (!c) return false;
+  for (size_t k = 0; k < c->tasks.size(); k++)
+    if (c->tasks[k].strings && ((c->parent[k].has && c->parent[k].keys != 0) || (c->host[k].known && c->host[k].parent_keys != 0)))
+      return true;
+  return false;
+}
+
 SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.empty() ? nullptr : new ProbeCheck(plan); }
 
 }  // namespace tgx
@@ -575,6 +734,12 @@ SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.em
 using namespace tgx;
 
 namespace {
+// how a spec that has had its tgx_plan_set_key_probe* call was set, and that call's suffix
+const char *set_as(const KeyProbeTask &t) {
+  return t.rows ? "to gather rows" : t.strings ? "to probe string keys" : t.counted ? "counted" : "plain";
+}
+const char *set_suffix(const KeyProbeTask &t) { return t.rows ? "_rows" : t.strings ? "_strings" : t.counted ? "_counted" : ""; }
+
 tgx_status plan_set_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p, bool counted, tgx_error *err) {
   if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
   size_t slot = 0;
@@ -587,6 +752,9 @@ tgx_status plan_set_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe
   if (p->reserved != 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: reserved must be 0 (%u)", spec_index, p->reserved);
   KeyProbeTask &t = plan->key_probes[slot];
   // (a spec is plain or counted for good: the second of the two calls is refused)
+  if (t.set && t.strings)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set to probe string keys "
+                "(tgx_plan_set_key_probe_strings)", spec_index);
   if (t.set && t.rows)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set to gather rows (tgx_plan_set_key_probe_rows)",
                 spec_index);
@@ -623,10 +791,82 @@ extern "C" tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_in
   KeyProbeTask &t = plan->key_probes[slot];
   if (t.set && !t.rows)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
-                t.counted ? "counted" : "plain", t.counted ? "_counted" : "");
+                set_as(t), set_suffix(t));
   t.params = tgx_key_probe_params{1, 0};
   t.rows = t.set = true;
   return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec_index,
+                                                     const tgx_key_probe_strings_params *p, tgx_error *err) try {
+  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
+  size_t slot = 0;
+  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
+  if (plan_has_state(plan))
+    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a KEY_PROBE check are fixed once a state of the plan exists");
+  if (p->max_missing_keys < 1 || p->max_missing_keys > TGX_KEY_PROBE_MAX_MISSING_KEYS)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_missing_keys must be 1 .. %d (%u)", spec_index,
+                (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
+  if (p->max_value_bytes < 1 || p->max_value_bytes > TGX_KEY_PROBE_MAX_VALUE_BYTES)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
+                (int)TGX_KEY_PROBE_MAX_VALUE_BYTES, p->max_value_bytes);
+  KeyProbeTask &t = plan->key_probes[slot];
+  if (t.set && !t.strings)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
+                set_as(t), set_suffix(t));
+  t.params = tgx_key_probe_params{p->max_missing_keys, 0};
+  t.max_value_bytes = p->max_value_bytes;
+  t.strings = t.set = true;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+namespace {
+// the task of a spec that spec_slot has accepted
+const KeyProbeTask &task_of(const tgx_plan *plan, size_t spec_index) {
+  for (const KeyProbeTask &t : plan->key_probes)
+    if ((size_t)t.spec_index == spec_index) return t;
+  return plan->key_probes.front();  // (cannot happen)
+}
+}  // namespace
+
+extern "C" tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                                tgx_key_probe_strings *out, tgx_error *err) try {
+  bind_thread();
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  const KeyProbeTask &t = task_of(plan, spec_index);
+  if (!t.strings)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys "
+                "(tgx_plan_set_key_probe_strings)", spec_index);
+  memset(out, 0, sizeof(*out));
+  out->long_rows = h.long_rows;
+  out->max_value_bytes = t.max_value_bytes;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_entries_bytes(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                                  tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries,
+                                                  uint8_t *bytes, uint64_t bytes_cap, uint64_t *n_bytes,
+                                                  tgx_error *err) try {
+  bind_thread();
+  if (!n_entries || !n_bytes) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  if (!task_of(plan, spec_index).strings)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys: its missing keys "
+                "are read with tgx_key_probe_entries", spec_index);
+  int32_t is_bytes = 0;
+  return keyed_entries_out(h, entries, cap, n_entries, bytes, bytes_cap, n_bytes, &is_bytes,
+                           [](int64_t key, uint64_t at, uint64_t length, uint64_t count) {
+                             return tgx_value_count_entry{key, at, length, count};
+                           }, err);
 } catch (...) {
   return tgx::abi_exception(err);
 }
@@ -668,7 +908,7 @@ extern "C" tgx_status tgx_key_probe_get(const tgx_plan *plan, tgx_state *st, siz
   out->matched = h.matched;
   out->counted = h.counted();
   out->overflow_rows = h.overflow_rows;
-  out->missing_rows = out->counted + out->overflow_rows;
+  out->missing_rows = out->counted + out->overflow_rows + h.long_rows;  // (long rows: a strings spec's only)
   out->missing_keys = h.size();
   out->parent_keys = h.parent_keys;
   out->parent_digest = h.parent_digest;
@@ -708,6 +948,9 @@ extern "C" tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *st,
   if (!n_entries) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  if (task_of(plan, spec_index).strings)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check probes string keys: its missing keys are read "
+                "with tgx_key_probe_entries_bytes", spec_index);
   uint64_t n_bytes = 0;
   TGX_TRY(counted_entries_sizes(h.size(), 0, entries, cap, n_entries, nullptr, 0, &n_bytes, err));
   if (!entries) return TGX_OK;

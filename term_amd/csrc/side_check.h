@@ -71,6 +71,9 @@ tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupcounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupsums_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status keyprobe_plan_ready(const tgx_plan *plan, tgx_error *err);
+// does a blob of `st` hold a KEY_PROBE task on string keys with a known, non-empty set?  Its identity is made of
+// fingerprints: such a blob carries the plan's fingerprint key (wire.cpp)
+TGX_HIDDEN bool keyprobe_blob_keyed(tgx_state *st);
 
 // in the order of the blob's sections
 inline constexpr SideKind kSideKinds[kNumSide] = {

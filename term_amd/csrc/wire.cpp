@@ -28,6 +28,7 @@ extern "C" tgx_status tgx_state_serialize(const tgx_plan *plan, tgx_state *st, u
     const DistinctState &ds = st->distinct[k];
     if (has_key_set(ds) && !ds.partitioned && ds.wide) keyed = 1;
   }
+  if (keyprobe_blob_keyed(st)) keyed = 1;  // (a set of fingerprints is known by its digest)
   w.pod(keyed);
   uint32_t key_words[4] = {0, 0, 0, 0};
   if (keyed) memcpy(key_words, plan->fp_key.k, 16);
@@ -99,8 +100,9 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
       n_dist != plan->distinct.size() || n_kll != plan->kll.size() || n_regex != regex_num_tasks(plan) ||
       n_hll != plan->hll.size())
     return fail(err, TGX_INVALID_ARGUMENT, "state blob was produced by a different plan");
+  uint32_t keyed = 0;
   {
-    const uint32_t keyed = r.pod<uint32_t>();
+    keyed = r.pod<uint32_t>();
     uint8_t key[16];
     r.get(key, 16);
     if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
@@ -159,6 +161,11 @@ extern "C" tgx_status tgx_state_deserialize(const tgx_plan *plan, const uint8_t 
     }
     for (auto &side : st->side)
       if (side && r.ok) TGX_TRY(side->deserialize(st.get(), r, err));
+    // (a set of fingerprints is known by its digest: without the key it was made under there is nothing to hold it to)
+    if (r.ok && !keyed && keyprobe_blob_keyed(st.get()))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "malformed state blob (KEY_PROBE: a task on string keys knows a non-empty parent set and the blob "
+                  "carries no fingerprint key)");
   }
   if (!r.ok) return fail(err, TGX_INVALID_ARGUMENT, "truncated state blob");
   *out = st.release();

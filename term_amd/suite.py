@@ -520,7 +520,9 @@ class ForeignKeyConstraint:
     """constraints/foreign_key.rs:78-117, one method per builder call of the reference: every non-NULL value of
     `child_column` is a value of `parent_column`, both qualified as "table.column".  The parent's column is walked once
     under a DISTINCT spec, its key set handed to a KEY_PROBE spec over the child's column, and the child walked once:
-    integer keys only (any other column type is the constraint's own error, which says it is not on the GPU path).  It
+    integer keys, or string keys when both columns are string layouts (Utf8, LargeUtf8, Utf8View, Dictionary<Int32,
+    Utf8>; the parent's values then travel as keyed 128-bit fingerprints).  Any other column type, and a pair of an
+    integer and a string column, is the constraint's own error, which says it is not on the GPU path.  It
     needs ValidationSuite.run(table, tables={name: table})"""
 
     def __init__(self, child_column, parent_column):
@@ -548,13 +550,21 @@ class ForeignKeyConstraint:
         self.spec["max_missing_keys"] = int(n)
         return self
 
+    def max_value_bytes(self, n):
+        """this layer's own, string keys only: the bytes a missing key may have to be kept (1 .. 256, default 256).
+        Missing rows with a longer value are counted as long rows: the verdict and the metric stand, and `unique` reads
+        "at least n" """
+        self.spec["max_value_bytes"] = int(n)
+        return self
+
     def name(self): return "foreign_key"
     def child_column(self): return self.spec["child_column"]
     def parent_column(self): return self.spec["parent_column"]
 
     def verdict_from_counts(self, counts):
         """the verdict on given counts (no device): a dict {"null_rows", "missing_rows", "overflow_rows",
-        "missing_keys", "entries": [[key, count], ..] ascending by key, "examples": bool}"""
+        "missing_keys", "entries": [[key, count], ..] ascending by key, "examples": bool}; string keys: the keys are
+        strings, ascending bytewise, and "long_rows" counts the missing rows whose value was too long to keep"""
         out, err = C.c_char_p(), _Error()
         _host_check(_host().tgx_host_foreign_key_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
                                                       C.byref(out), C.byref(err)), err)
@@ -889,8 +899,15 @@ class ValidationSuite:
                                                         n_batches, C.byref(out), C.byref(err)), err)
             return ValidationResult(_take(out))
         flat = [] if n_cols == 0 else [(spec.get("table_name", "data"), name_arr, n_cols, col_arr, n_batches, _keep)]
+        further = {}
         for name, t in tables.items():
             flat.append((name,) + tuple(_flatten_table(t)))
+            # (what the layout does not say: a Binary column arrives in a string layout)
+            binary = {c: kind for c, kind in _arrow_type_names(t).items() if kind == "Binary"}
+            if binary:
+                further[name] = binary
+        if further:
+            spec = dict(spec, table_column_types=further)
         arr = (_HostTable * max(1, len(flat)))()
         for slot, (name, names, nc, cols, nb, _k) in zip(arr, flat):
             slot.name = name.encode()

@@ -311,36 +311,46 @@ def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=N
 
 
 def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0, overflow_rows=0, parent=None,
-                    ordered=True, non_null=None, counted=None):
+                    ordered=True, non_null=None, counted=None, strings=None):
     """a KEY_PROBE task: the plan's parameter, the identity of the parent set the counts were taken under (`parent`:
     (parent_keys, parent_digest), or None for a state that knows of none), the counters and the entries of `missing`
     (key -> rows).  non_null defaults to what the invariant makes it -- matched + sum(missing) + overflow_rows -- and seen
     to non_null + nulls.  `ordered=False` keeps the entries in the order given (for a blob that is to be refused).
     `counted`: (parent_rows, parent_count_digest, max_count, pairs) of a counted task (Plan.set_key_probe_counted) -- the
     rest of its set's identity, the set's largest count and the matched pairs; the task's second reserved word is then 1
-    and the four words stand before the entries.  None: a plain task, whose bytes are the ones they always were."""
+    and the four words stand before the entries.  None: a plain task, whose bytes are the ones they always were.
+    `strings`: (max_value_bytes, long_rows) of a task on string keys (Plan.set_key_probe_strings): the second reserved
+    word is then 2, { u32 max_value_bytes, u32 0, u64 long_rows } stand before the entries, the keys of `missing` are
+    bytes and an entry is { u32 length, bytes, u64 rows }, ascending bytewise; long_rows count towards non_null.  A blob
+    that holds such a task with a non-empty parent set carries the plan's fingerprint key (pack's fingerprint_key)."""
     items = list(missing.items()) if hasattr(missing, "items") else list(missing)
     if ordered:
         items.sort(key=lambda kv: kv[0])
     if non_null is None:
-        non_null = matched + sum(c for _, c in items) + overflow_rows
+        non_null = matched + sum(c for _, c in items) + overflow_rows + (strings[1] if strings is not None else 0)
     if seen is None:
         seen = non_null + nulls
     keys, digest = parent if parent is not None else (0, 0)
-    out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, 1 if counted is not None else 0, keys,
-                      digest, seen, non_null, matched, overflow_rows, len(items))
+    mode = 1 if counted is not None else 2 if strings is not None else 0
+    out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, mode, keys, digest, seen, non_null,
+                      matched, overflow_rows, len(items))
     if counted is not None:
         out += struct.pack("<4Q", *counted)
+    if strings is not None:
+        out += struct.pack("<IIQ", strings[0], 0, strings[1])
     for k, c in items:
-        out += struct.pack("<qQ", k, c)
+        out += struct.pack("<I", len(k)) + bytes(k) + struct.pack("<Q", c) if strings is not None else struct.pack("<qQ", k, c)
     return out
 
 
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
-         value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=(), key_probes=()):
+         value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=(), key_probes=(),
+         fingerprint_key=None):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
-    head += struct.pack("<I16s", 0, bytes(16))  # (no string keys in a state packed from plain numbers)
+    # (no string keys in a state packed from plain numbers, unless a KEY_PROBE task on string keys knows its parent set:
+    # `fingerprint_key`, the 16 bytes of the plan's key)
+    head += struct.pack("<I16s", 0, bytes(16)) if fingerprint_key is None else struct.pack("<I16s", 1, bytes(fingerprint_key))
     tail = struct.pack("<II", JOINT_MAGIC, len(joint)) + b"".join(joint) if joint else b""
     if temporal:
         tail += struct.pack("<II", TEMPORAL_MAGIC, len(temporal)) + b"".join(temporal)

@@ -32,7 +32,10 @@ def main():
     ap.add_argument("--parents", default="1000000,100000000")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--strings", action="store_true", help="the string-key probe beside VALUE_COUNTS (strings_main)")
     args = ap.parse_args()
+    if args.strings:
+        return strings_main(args)
     import torch
     import term_amd as T
     from term_amd._lib import spec
@@ -127,6 +130,142 @@ def main():
                 del pst, rst, cst, col, keys
             del records
             torch.cuda.empty_cache()
+    print(json.dumps(out))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+STRING_EXPECTATIONS = """expectations, written before the run:
+ (1) a probe step costs what VALUE_COUNTS costs on the same column -- the same row-per-lane walk and the same fingerprint
+     -- plus the lookup.  (The yardstick column has the child's shape and 5000 distinct values: on the child itself, a
+     million distinct values, VALUE_COUNTS's 32 768-slot table overflows and every row walks a probe sequence to its end.)
+ (2) 1 M keys, a 32 MiB table: out of an XCD's L2, inside the Infinity Cache; 100 M keys, a 4 GiB table: one 64-byte line
+     from HBM a row, as on routes 2 and 4, so the step costs what route 4's costs (16-byte slots) plus the string walk.
+ (3) the missing rate moves the time little: 300 missing keys combine in the wave and the LDS table; a miss probes on
+     to a free slot (about 2.5 slots at load 0.5 against 1.5 for a hit).
+ (4) the dictionary child costs its 4 bytes a row: the 10 000 lookups are nothing.
+"""
+
+
+def strings_main(args):
+    """--strings: a Utf8 child of 12-byte values (5 % NULLs, 300 distinct missing keys at 0 %, 1 % and 50 % of the
+    non-NULL rows) probed against parents of --parents string keys (route 5: tables of 16-byte slots, 32 MiB and 4 GiB),
+    beside VALUE_COUNTS in the same process, the plans interleaved step by step -- on a column of the same shape (rows,
+    value length, validity) with 5000 distinct values, which its table holds: the same walker and fingerprint, no set;
+    then a dictionary child of 10 000 entries.  The set is built from the parent column's DISTINCT export under the child plan's
+    fingerprint key; its build is timed by the wall clock around tgx_key_probe_set_parent.  The roofline prices the
+    kind's own bytes -- 12 B of data, a 4-byte offset and one validity bit a row -- at 8 TB/s."""
+    import torch
+    import term_amd as T
+    from term_amd._lib import spec
+
+    T.init(flags=T.OPT_NO_COALESCE)
+    print(STRING_EXPECTATIONS, flush=True)
+    n = args.rows // 64 * 64
+    width = 12
+    gen = torch.Generator(device="cuda").manual_seed(0x7E570020)
+    out = {"rows": n, "cases": {}}
+    own_bytes = n * (width + 4) + n // 8
+    far = 1 << 44  # ids of the missing keys: beyond every parent
+    shifts = (4 * torch.arange(width, device="cuda", dtype=torch.int64))[None, :]
+
+    def render(ids):
+        """ids -> (int32 offsets, bytes): 12 letters a .. p, a nibble each"""
+        data = torch.empty((ids.numel(), width), device="cuda", dtype=torch.uint8)
+        step = 1 << 24
+        for lo in range(0, ids.numel(), step):  # (in pieces: the nibbles as int64 are 96 bytes a row)
+            data[lo:lo + step] = (((ids[lo:lo + step, None] >> shifts) & 15) + 97).to(torch.uint8)
+        offsets = torch.arange(ids.numel() + 1, device="cuda", dtype=torch.int64).mul_(width).to(torch.int32)
+        return offsets, torch.cat([data.reshape(-1), torch.zeros(64, device="cuda", dtype=torch.uint8)])
+
+    bits = (torch.rand(n + 64, device="cuda", generator=gen) >= 0.05).reshape(-1, 8).to(torch.uint8)
+    packed = (bits << torch.arange(8, device="cuda", dtype=torch.uint8)[None, :]).sum(dim=1).to(torch.uint8)
+    non_null = int(bits.reshape(-1)[:n].sum())
+    del bits
+    key = bytes(range(16))
+    yoffs, ydata = render((torch.rand(n, device="cuda", generator=gen) * 5000).to(torch.int64).clamp_(0, 4999))
+    ycol = T.Column(T.UTF8, n, offsets=yoffs, data=ydata, validity=packed, mem=T.MEM_DEVICE)
+
+    def probe_plan():
+        plan = T.Plan([spec(T.KEY_PROBE, 0)])
+        plan.set_fingerprint_key(key)
+        plan.set_key_probe_strings(0, 10000, 256)
+        return plan
+
+    for k in [int(p) for p in args.parents.split(",")]:
+        poffs, pdata = render(torch.arange(k, device="cuda", dtype=torch.int64))
+        dplan = T.Plan([spec(T.DISTINCT, 0)])
+        dplan.set_fingerprint_key(key)
+        parent = T.State(dplan)
+        torch.cuda.synchronize()
+        parent.update([T.Column(T.UTF8, k, offsets=poffs, data=pdata, mem=T.MEM_DEVICE)])
+        ptr, counts = parent.distinct_export(0, 1)
+        assert counts[0] == k, counts
+        slots = 1 << max(1, (2 * k - 1).bit_length())
+        cases = [("missing_%g" % share, share, False) for share in (0.0, 0.01, 0.5)] + [("dictionary_10000", 0.01, True)]
+        for label, share, as_dict in cases:
+            name = "strings_%d_%s" % (k, label)
+            if as_dict:
+                entry_ids = torch.arange(10000, device="cuda", dtype=torch.int64)
+                entry_ids = torch.where(entry_ids % 100 == 0, far + entry_ids // 100, entry_ids % k)
+                eoffs, edata = render(entry_ids)
+                idx = (torch.rand(n, device="cuda", generator=gen) * 10000).to(torch.int32).clamp_(0, 9999)
+                torch.cuda.synchronize()
+                col = T.Column(T.DICT32_UTF8, n, values=idx, validity=packed, mem=T.MEM_DEVICE,
+                               dictionary=T.Column(T.UTF8, 10000, offsets=eoffs, data=edata, mem=T.MEM_DEVICE))
+                case_bytes = n * 4 + n // 8
+            else:
+                ids = (torch.rand(n, device="cuda", generator=gen) * k).to(torch.int64).clamp_(0, k - 1)
+                if share:
+                    miss = torch.rand(n, device="cuda", generator=gen) < share
+                    ids = torch.where(miss, far + (ids % N_MISSING), ids)
+                    del miss
+                offs, data = render(ids)
+                del ids
+                torch.cuda.synchronize()
+                col = T.Column(T.UTF8, n, offsets=offs, data=data, validity=packed, mem=T.MEM_DEVICE)
+                case_bytes = own_bytes
+            pplan = probe_plan()
+            vplan = T.Plan([spec(T.VALUE_COUNTS, 0)])
+            vplan.set_fingerprint_key(key)
+            vplan.set_value_counts(0, 10000, 256)
+            pst, vst = T.State(pplan), T.State(vplan)
+            pst.profile_enable(True)
+            vst.profile_enable(True)
+            builds = []
+            for _ in range(3):  # (a state that has seen no batch takes a set again)
+                t0 = time.perf_counter()
+                pst.key_probe_set_parent(0, ptr, k)
+                builds.append((time.perf_counter() - t0) * 1e3)
+            probe_ms, counts_ms = [], []
+            for it in range(args.steps + 1):
+                for st, kernel, times, batch in ((pst, "key_probe", probe_ms, col), (vst, "value_counts", counts_ms, ycol)):
+                    st.reset()
+                    st.profile_reset()
+                    st.update([batch])
+                    st.finalize()
+                    if it:  # (step 0 warms the shape up)
+                        times.append(st.profile_get(kernel)["total_ms"])
+            s, missing = pst.key_probe_strings(0)
+            assert s["seen"] == n and s["non_null"] == non_null and s["overflow_rows"] == 0 and s["long_rows"] == 0, s
+            assert s["parent_keys"] == k and s["route"] == 5 and s["matched"] + s["missing_rows"] == non_null, s
+            assert s["missing_keys"] == (100 if as_dict else N_MISSING if share else 0), s
+            assert abs(s["missing_rows"] - share * non_null) <= 0.01 * non_null + 1000, s
+            pm, vm = statistics.median(probe_ms), statistics.median(counts_ms)
+            row = {"key_probe_ms": pm, "key_probe_min_ms": min(probe_ms), "key_probe_max_ms": max(probe_ms),
+                   "value_counts_ms": vm, "value_counts_min_ms": min(counts_ms), "value_counts_max_ms": max(counts_ms),
+                   "ratio": pm / vm, "roofline": case_bytes / (pm * 1e-3) / HBM_BYTES_PER_S,
+                   "build_ms": statistics.median(builds), "set_bytes": 16 * slots, "missing_rows": s["missing_rows"]}
+            out["cases"][name] = row
+            print("%d rows, %-36s key_probe %.2f ms (%.2f .. %.2f) | value_counts %.2f ms (%.2f .. %.2f) (x %.2f) | "
+                  "%.0f %% of 8 TB/s | set of %.1f MB built in %.2f ms"
+                  % (n, name, pm, min(probe_ms), max(probe_ms), vm, min(counts_ms), max(counts_ms), row["ratio"],
+                     100 * row["roofline"], row["set_bytes"] / 1e6, row["build_ms"]), flush=True)
+            del pst, vst, col
+            torch.cuda.empty_cache()
+        del parent, poffs, pdata
+        torch.cuda.empty_cache()
     print(json.dumps(out))
     if args.json:
         with open(args.json, "w") as f:
