@@ -1,8 +1,8 @@
 // counted_state.h -- what the kinds share whose tasks count keys in a table on the device (VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS: the
 // bounded GROUP BY of kernels/count_table.h): the table's size and layout, clearing it, reading it back once between
 // batches, and the two places where sizes come from outside -- a blob's entries and the buffers of the *_entries calls.
-// keyed_state.h builds on this for the three kinds whose keys are the values of one column; PAIR_COUNTS, whose keys are
-// pairs of cells, stands on this file alone.
+// keyed_state.h builds on this for the four kinds whose keys are the values of one column (KEY_PROBE counts the keys
+// that are missing from its parent set); PAIR_COUNTS, whose keys are pairs of cells, stands on this file alone.
 #pragma once
 #include <initializer_list>
 
@@ -10,10 +10,10 @@
 
 namespace tgx {
 
-// slots of a table that counts up to `bound` keys: the smallest power of two >= 2 * bound and >= 2
-TGX_HIDDEN inline uint64_t table_slots(uint32_t bound) {
+// slots of a table that counts up to `bound` keys (below 2^62): the smallest power of two >= 2 * bound and >= 2
+TGX_HIDDEN inline uint64_t table_slots(uint64_t bound) {
   uint64_t s = 2;
-  while (s < 2 * (uint64_t)bound) s <<= 1;
+  while (s < 2 * bound) s <<= 1;
   return s;
 }
 

@@ -72,6 +72,7 @@ struct GroupsKind {
   static const std::vector<GroupCountsTask> &tasks(const tgx_plan *plan) { return plan->group_counts; }
   static size_t words(const GroupCountsTask &) { return kGroupCountsWords; }
   static uint32_t bound(const GroupCountsTask &t) { return t.params.max_groups; }
+  static uint32_t max_value_bytes(const GroupCountsTask &t) { return t.params.max_value_bytes; }
   static NoRange range_identity() { return NoRange(); }
   static GroupsHost fresh(const GroupCountsTask &) { return GroupsHost(); }
   static size_t shape(const GroupsHost &) { return 0; }  // (integer against string keys: KeyedCheck::merge_from)

@@ -114,6 +114,7 @@ struct GroupSumsKind {
   static const std::vector<GroupSumsTask> &tasks(const tgx_plan *plan) { return plan->group_sums; }
   static size_t words(const GroupSumsTask &) { return kTaskWords; }
   static uint32_t bound(const GroupSumsTask &t) { return t.params.max_groups; }
+  static uint32_t max_value_bytes(const GroupSumsTask &t) { return t.params.max_value_bytes; }
   static NoRange range_identity() { return NoRange(); }
   static GroupSumsHost fresh(const GroupSumsTask &) { return GroupSumsHost(); }
   static size_t shape(const GroupSumsHost &) { return 0; }  // (the two kinds of a host: KeyedCheck::merge_from)

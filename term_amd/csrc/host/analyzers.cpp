@@ -2,6 +2,7 @@
 // TG/analyzers/basic/{size,completeness,distinctness,mean,min_max,sum}.rs,
 // TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram,entropy}.rs.
 #include "analyzers.h"
+#include "tgx_handles.h"
 
 #include <math.h>
 #include <string.h>
@@ -1245,25 +1246,6 @@ std::shared_ptr<Analyzer> completeness_with_grouping(const std::string &column, 
                                                      bool strict_reference_types, const std::string &group_arrow_type) {
   return std::make_shared<GroupedCompletenessAnalyzer>(column, config, strict_reference_types, group_arrow_type);
 }
-
-namespace {
-
-struct Handles {
-  tgx_plan *plan = nullptr;
-  tgx_state *state = nullptr;
-  Handles() = default;
-  Handles(const Handles &) = delete;
-  Handles &operator=(const Handles &) = delete;
-  void reset() {
-    if (state) tgx_state_destroy(state);
-    if (plan) tgx_plan_destroy(plan);
-    state = nullptr;
-    plan = nullptr;
-  }
-  ~Handles() { reset(); }
-};
-
-}  // namespace
 
 std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
   const std::string t = v.get_str("type");

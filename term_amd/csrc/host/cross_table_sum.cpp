@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "term_guard.h"
+#include "tgx_handles.h"
 
 namespace term_guard {
 
@@ -30,18 +31,6 @@ std::string fixed4(double v) {
   snprintf(buf, sizeof(buf), "%.4f", v);
   return buf;
 }
-
-struct Handles {
-  tgx_plan *plan = nullptr;
-  tgx_state *state = nullptr;
-  Handles() = default;
-  Handles(const Handles &) = delete;
-  Handles &operator=(const Handles &) = delete;
-  ~Handles() {
-    if (state) tgx_state_destroy(state);
-    if (plan) tgx_plan_destroy(plan);
-  }
-};
 
 int column_index(const Table &t, const std::string &name) {
   for (size_t i = 0; i < t.column_names.size(); i++)
@@ -67,11 +56,8 @@ void walk_side(const Context &ctx, const std::string &table_name, const std::str
   spec.column = vi;
   spec.column2 = gi;
   Handles h;
-  tgx_error err;
-  memset(&err, 0, sizeof(err));
-  auto check = [&](tgx_status s) {
-    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
-  };
+  Checker check(query_failed);
+  tgx_error &err = check.err;
   check(tgx_init(nullptr, &err));
   check(tgx_plan_create(&spec, 1, &h.plan, &err));
   if (!group.empty()) {

@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "term_guard.h"
+#include "tgx_handles.h"
 
 namespace term_guard {
 
@@ -23,32 +24,6 @@ namespace {
 }
 [[noreturn]] void query_failed(const std::string &why) {  // (:320-325)
   evaluation_error("Foreign key validation query failed: " + why);
-}
-
-struct Handles {
-  tgx_plan *plan = nullptr;
-  tgx_state *state = nullptr;
-  Handles() = default;
-  Handles(const Handles &) = delete;
-  Handles &operator=(const Handles &) = delete;
-  ~Handles() {
-    if (state) tgx_state_destroy(state);
-    if (plan) tgx_plan_destroy(plan);
-  }
-};
-
-const char *off_path_type(int type) {
-  switch (type) {
-    case TGX_FLOAT64: return "Float64";
-    case TGX_FLOAT32: return "Float32";
-    case TGX_UINT64: return "UInt64";
-    case TGX_BOOL: return "Boolean";
-    case TGX_UTF8: return "Utf8";
-    case TGX_LARGE_UTF8: return "LargeUtf8";
-    case TGX_UTF8_VIEW: return "Utf8View";
-    case TGX_DICT32_UTF8: return "Dictionary<Int32, Utf8>";
-    default: return nullptr;
-  }
 }
 
 // the table and the index of the column behind a qualified name, with the reference's planning / schema errors
@@ -97,6 +72,41 @@ int key_type(const Table &table, int index, const std::string &qualified) {
       if (type == 0) type = t;
     }
   return type;
+}
+
+// The two walks of an evaluation, the same for integer and for string keys.
+// the parent: its column walked under a DISTINCT spec, and the records of its distinct non-NULL keys (Int32 / narrow
+// columns as their sign- or zero-extended int64 values, strings as fingerprints under the plan's key).  The records stay
+// the parent state's until its next call: `p` lives to the end
+void export_parent(Checker &check, const Table &table, int column, Handles &p, const void **records, uint64_t *n_records) {
+  tgx_check_spec spec;
+  memset(&spec, 0, sizeof(spec));
+  spec.kind = TGX_CHECK_DISTINCT;
+  spec.column = column;
+  spec.column2 = -1;
+  check(tgx_plan_create(&spec, 1, &p.plan, &check.err));
+  check(tgx_state_create(p.plan, nullptr, &p.state, &check.err));
+  for (const Batch &b : table.batches) check(tgx_update(p.plan, p.state, b.columns.data(), b.columns.size(), &check.err));
+  check(tgx_distinct_export(p.plan, p.state, 0, 1, records, n_records, &check.err));
+}
+
+// the child: its column walked under a KEY_PROBE spec against that set; `set` makes the plan's tgx_plan_set_key_probe*
+// call (and hands over what its mode needs beside it).  The summary; the entries are read by the caller
+tgx_key_probe_summary probe_child(Checker &check, const Table &table, int column, const void *records, uint64_t n_records,
+                                  Handles &c, const std::function<void(tgx_plan *)> &set) {
+  tgx_check_spec spec;
+  memset(&spec, 0, sizeof(spec));
+  spec.kind = TGX_CHECK_KEY_PROBE;
+  spec.column = column;
+  spec.column2 = -1;
+  check(tgx_plan_create(&spec, 1, &c.plan, &check.err));
+  set(c.plan);
+  check(tgx_state_create(c.plan, nullptr, &c.state, &check.err));
+  check(tgx_key_probe_set_parent(c.plan, c.state, 0, records, n_records, &check.err));
+  for (const Batch &b : table.batches) check(tgx_update(c.plan, c.state, b.columns.data(), b.columns.size(), &check.err));
+  tgx_key_probe_summary s;
+  check(tgx_key_probe_get(c.plan, c.state, 0, &s, &check.err));
+  return s;
 }
 
 }  // namespace
@@ -161,43 +171,20 @@ ConstraintResult ForeignKeyConstraint::evaluate_context(const Context &ctx) cons
   const int child_type = key_type(*child_table, ci, child_);
   key_type(*parent_table, pi, parent_);
 
-  tgx_error err;
-  memset(&err, 0, sizeof(err));
-  auto check = [&](tgx_status s) {
-    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
-  };
-  check(tgx_init(nullptr, &err));
-
-  // the parent: its distinct non-NULL keys (Int32 / narrow columns as their sign- or zero-extended int64 values)
-  tgx_check_spec spec;
-  memset(&spec, 0, sizeof(spec));
-  spec.kind = TGX_CHECK_DISTINCT;
-  spec.column = pi;
-  spec.column2 = -1;
-  Handles p;
-  check(tgx_plan_create(&spec, 1, &p.plan, &err));
-  check(tgx_state_create(p.plan, nullptr, &p.state, &err));
-  for (const Batch &b : parent_table->batches) check(tgx_update(p.plan, p.state, b.columns.data(), b.columns.size(), &err));
+  Checker check(query_failed);
+  check(tgx_init(nullptr, &check.err));
+  Handles p, c;
   const void *records = nullptr;
   uint64_t n_records = 0;
-  check(tgx_distinct_export(p.plan, p.state, 0, 1, &records, &n_records, &err));
-
-  // the child, against that set (the records stay the parent state's until its next call: it lives to the end)
-  spec.kind = TGX_CHECK_KEY_PROBE;
-  spec.column = ci;
-  Handles c;
-  check(tgx_plan_create(&spec, 1, &c.plan, &err));
-  const tgx_key_probe_params params = {max_missing_keys_, 0};
-  check(tgx_plan_set_key_probe(c.plan, 0, &params, &err));
-  check(tgx_state_create(c.plan, nullptr, &c.state, &err));
-  check(tgx_key_probe_set_parent(c.plan, c.state, 0, records, n_records, &err));
-  for (const Batch &b : child_table->batches) check(tgx_update(c.plan, c.state, b.columns.data(), b.columns.size(), &err));
-  tgx_key_probe_summary s;
-  check(tgx_key_probe_get(c.plan, c.state, 0, &s, &err));
+  export_parent(check, *parent_table, pi, p, &records, &n_records);
+  const tgx_key_probe_summary s = probe_child(check, *child_table, ci, records, n_records, c, [&](tgx_plan *plan) {
+    const tgx_key_probe_params params = {max_missing_keys_, 0};
+    check(tgx_plan_set_key_probe(plan, 0, &params, &check.err));
+  });
   uint64_t n = 0;
-  check(tgx_key_probe_entries(c.plan, c.state, 0, nullptr, 0, &n, &err));
+  check(tgx_key_probe_entries(c.plan, c.state, 0, nullptr, 0, &n, &check.err));
   std::vector<tgx_key_probe_entry> entries((size_t)n + 1);
-  check(tgx_key_probe_entries(c.plan, c.state, 0, entries.data(), n, &n, &err));
+  check(tgx_key_probe_entries(c.plan, c.state, 0, entries.data(), n, &n, &check.err));
 
   ForeignKeyCounts counts;
   counts.null_rows = s.null_rows;
@@ -215,49 +202,28 @@ ConstraintResult ForeignKeyConstraint::evaluate_strings(const Table &child_table
   if (max_value_bytes_ < 1 || max_value_bytes_ > TGX_KEY_PROBE_MAX_VALUE_BYTES)
     evaluation_error("max_value_bytes must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_VALUE_BYTES) + " (" +
                      std::to_string(max_value_bytes_) + ")");
-  tgx_error err;
-  memset(&err, 0, sizeof(err));
-  auto check = [&](tgx_status s) {
-    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
-  };
-  check(tgx_init(nullptr, &err));
-
-  // the parent: its distinct non-NULL values as fingerprints under its plan's key
-  tgx_check_spec spec;
-  memset(&spec, 0, sizeof(spec));
-  spec.kind = TGX_CHECK_DISTINCT;
-  spec.column = pi;
-  spec.column2 = -1;
-  Handles p;
-  check(tgx_plan_create(&spec, 1, &p.plan, &err));
-  check(tgx_state_create(p.plan, nullptr, &p.state, &err));
-  for (const Batch &b : parent_table.batches) check(tgx_update(p.plan, p.state, b.columns.data(), b.columns.size(), &err));
+  Checker check(query_failed);
+  check(tgx_init(nullptr, &check.err));
+  Handles p, c;
   const void *records = nullptr;
   uint64_t n_records = 0;
-  check(tgx_distinct_export(p.plan, p.state, 0, 1, &records, &n_records, &err));
-
-  // the child, under the same key, against that set
-  spec.kind = TGX_CHECK_KEY_PROBE;
-  spec.column = ci;
-  Handles c;
-  check(tgx_plan_create(&spec, 1, &c.plan, &err));
-  uint8_t key[16];
-  check(tgx_plan_get_fingerprint_key(p.plan, key));
-  check(tgx_plan_set_fingerprint_key(c.plan, key, &err));
-  const tgx_key_probe_strings_params params = {max_missing_keys_, max_value_bytes_};
-  check(tgx_plan_set_key_probe_strings(c.plan, 0, &params, &err));
-  check(tgx_state_create(c.plan, nullptr, &c.state, &err));
-  check(tgx_key_probe_set_parent(c.plan, c.state, 0, records, n_records, &err));
-  for (const Batch &b : child_table.batches) check(tgx_update(c.plan, c.state, b.columns.data(), b.columns.size(), &err));
-  tgx_key_probe_summary s;
-  check(tgx_key_probe_get(c.plan, c.state, 0, &s, &err));
+  export_parent(check, parent_table, pi, p, &records, &n_records);
+  // (the child's plan fingerprints under the parent plan's key)
+  const tgx_key_probe_summary s = probe_child(check, child_table, ci, records, n_records, c, [&](tgx_plan *plan) {
+    uint8_t key[16];
+    check(tgx_plan_get_fingerprint_key(p.plan, key));
+    check(tgx_plan_set_fingerprint_key(plan, key, &check.err));
+    const tgx_key_probe_strings_params params = {max_missing_keys_, max_value_bytes_};
+    check(tgx_plan_set_key_probe_strings(plan, 0, &params, &check.err));
+  });
   tgx_key_probe_strings more;
-  check(tgx_key_probe_strings_get(c.plan, c.state, 0, &more, &err));
+  check(tgx_key_probe_strings_get(c.plan, c.state, 0, &more, &check.err));
   uint64_t n = 0, n_bytes = 0;
-  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, nullptr, 0, &n, nullptr, 0, &n_bytes, &err));
+  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, nullptr, 0, &n, nullptr, 0, &n_bytes, &check.err));
   std::vector<tgx_value_count_entry> entries((size_t)n + 1);
   std::vector<uint8_t> bytes((size_t)n_bytes + 1);
-  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, entries.data(), n, &n, bytes.data(), n_bytes, &n_bytes, &err));
+  check(tgx_key_probe_entries_bytes(c.plan, c.state, 0, entries.data(), n, &n, bytes.data(), n_bytes, &n_bytes,
+                                    &check.err));
 
   ForeignKeyCounts counts;
   counts.strings = true;

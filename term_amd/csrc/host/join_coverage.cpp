@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "term_guard.h"
+#include "tgx_handles.h"
 
 namespace term_guard {
 
@@ -28,32 +29,6 @@ namespace {
 }
 [[noreturn]] void query_failed(const std::string &why) {  // (:340-345)
   evaluation_error("Join coverage query failed: " + why);
-}
-
-struct Handles {
-  tgx_plan *plan = nullptr;
-  tgx_state *state = nullptr;
-  Handles() = default;
-  Handles(const Handles &) = delete;
-  Handles &operator=(const Handles &) = delete;
-  ~Handles() {
-    if (state) tgx_state_destroy(state);
-    if (plan) tgx_plan_destroy(plan);
-  }
-};
-
-const char *off_path_type(int type) {
-  switch (type) {
-    case TGX_FLOAT64: return "Float64";
-    case TGX_FLOAT32: return "Float32";
-    case TGX_UINT64: return "UInt64";
-    case TGX_BOOL: return "Boolean";
-    case TGX_UTF8: return "Utf8";
-    case TGX_LARGE_UTF8: return "LargeUtf8";
-    case TGX_UTF8_VIEW: return "Utf8View";
-    case TGX_DICT32_UTF8: return "Dictionary<Int32, Utf8>";
-    default: return nullptr;
-  }
 }
 
 // one side of the join: its table and key column, with the reference's planning / schema errors; integer keys only
@@ -84,11 +59,7 @@ std::string percent(double rate) {  // {:.2} of rate * 100.0
 
 // the device side of one evaluation
 struct Walks {
-  tgx_error err;
-  Walks() { memset(&err, 0, sizeof(err)); }
-  void check(tgx_status s) {
-    if (s != TGX_OK) query_failed(std::string(tgx_status_name(s)) + ": " + err.msg);
-  }
+  Checker check{query_failed};
 
   // `side` gathered: one {key, 1} record a non-NULL row.  (The records stay the state's until its next call: `h` lives
   // as long as they are read)
@@ -98,11 +69,11 @@ struct Walks {
     spec.kind = TGX_CHECK_KEY_PROBE;
     spec.column = side.column;
     spec.column2 = -1;
-    check(tgx_plan_create(&spec, 1, &h.plan, &err));
-    check(tgx_plan_set_key_probe_rows(h.plan, 0, &err));
-    check(tgx_state_create(h.plan, nullptr, &h.state, &err));
-    for (const Batch &b : side.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &err));
-    check(tgx_key_probe_rows_get(h.plan, h.state, 0, records, n_records, &err));
+    check(tgx_plan_create(&spec, 1, &h.plan, &check.err));
+    check(tgx_plan_set_key_probe_rows(h.plan, 0, &check.err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
+    for (const Batch &b : side.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
+    check(tgx_key_probe_rows_get(h.plan, h.state, 0, records, n_records, &check.err));
   }
 
   // `near` walked once against the set of `records`: a counted probe (or a plain one); in the same plan, with
@@ -121,23 +92,23 @@ struct Walks {
       specs[i].column = near.column;
       specs[i].column2 = -1;
     }
-    check(tgx_plan_create(specs, n, &h.plan, &err));
+    check(tgx_plan_create(specs, n, &h.plan, &check.err));
     const tgx_key_probe_params params = {max_missing_keys, 0};
-    check(counted ? tgx_plan_set_key_probe_counted(h.plan, 0, &params, &err)
-                  : tgx_plan_set_key_probe(h.plan, 0, &params, &err));
-    if (own_records) check(tgx_plan_set_key_probe_rows(h.plan, gathers, &err));
-    check(tgx_state_create(h.plan, nullptr, &h.state, &err));
-    check(tgx_key_probe_set_parent(h.plan, h.state, 0, records, n_records, &err));
-    for (const Batch &b : near.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &err));
-    check(tgx_key_probe_get(h.plan, h.state, 0, summary, &err));
-    if (counted) check(tgx_key_probe_pairs_get(h.plan, h.state, 0, pairs, &err));
+    check(counted ? tgx_plan_set_key_probe_counted(h.plan, 0, &params, &check.err)
+                  : tgx_plan_set_key_probe(h.plan, 0, &params, &check.err));
+    if (own_records) check(tgx_plan_set_key_probe_rows(h.plan, gathers, &check.err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
+    check(tgx_key_probe_set_parent(h.plan, h.state, 0, records, n_records, &check.err));
+    for (const Batch &b : near.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
+    check(tgx_key_probe_get(h.plan, h.state, 0, summary, &check.err));
+    if (counted) check(tgx_key_probe_pairs_get(h.plan, h.state, 0, pairs, &check.err));
     if (distinct) {
       tgx_result results[3];
       memset(results, 0, sizeof(results));
-      check(tgx_finalize(h.plan, h.state, results, n, &err));
+      check(tgx_finalize(h.plan, h.state, results, n, &check.err));
       *distinct = (uint64_t)results[counts_distinct].distinct;
     }
-    if (own_records) check(tgx_key_probe_rows_get(h.plan, h.state, gathers, own_records, own_n, &err));
+    if (own_records) check(tgx_key_probe_rows_get(h.plan, h.state, gathers, own_records, own_n, &check.err));
   }
 };
 
@@ -207,7 +178,7 @@ ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) co
   validate();
   const Side L = side_of(ctx, left_, keys_[0].first), R = side_of(ctx, right_, keys_[0].second);
   Walks w;
-  w.check(tgx_init(nullptr, &w.err));
+  w.check(tgx_init(nullptr, &w.check.err));
 
   JoinCoverageCounts counts;
   tgx_key_probe_summary s;

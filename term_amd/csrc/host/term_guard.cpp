@@ -15,6 +15,7 @@
 #include "datatype.h"
 #include "value_counts.h"
 #include "temporal.h"
+#include "tgx_handles.h"
 
 namespace term_guard {
 
@@ -1196,20 +1197,6 @@ bool ValidationReport::has_warnings() const {
 
 // ------------------------------------------------------------------------------------------------ suite runner
 namespace {
-struct Handles {
-  tgx_plan *plan = nullptr;
-  tgx_state *state = nullptr;
-  Handles() = default;
-  Handles(const Handles &) = delete;
-  Handles &operator=(const Handles &) = delete;
-  void reset() {
-    if (state) tgx_state_destroy(state);
-    if (plan) tgx_plan_destroy(plan);
-    state = nullptr;
-    plan = nullptr;
-  }
-  ~Handles() { reset(); }
-};
 struct QuantileCtx {
   const tgx_plan *plan;
   tgx_state *state;

@@ -258,17 +258,21 @@ struct GroupSumsTask {
   tgx_group_sums_params params;
 };
 
-// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once tgx_plan_set_key_probe or
-// tgx_plan_set_key_probe_counted was called, `counted` by the latter: the set keeps the parent's multiplicities.  (The
-// parent's key set belongs to a state, not to the plan: tgx_key_probe_set_parent)
+// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once one of the four tgx_plan_set_key_probe* calls
+// was made, which gives the task its mode for good.  (The parent's key set belongs to a state, not to the plan:
+// tgx_key_probe_set_parent)
+//   kKpPlain     tgx_plan_set_key_probe: is each integer key in the set?
+//   kKpCounted   tgx_plan_set_key_probe_counted: the set keeps the parent's multiplicities
+//   kKpStrings   tgx_plan_set_key_probe_strings: the column is a string column, the set holds fingerprints, and a missing
+//                key of up to max_value_bytes bytes keeps its bytes
+//   kKpRows      tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
+// The first three are a blob's mode word; a rows task's state holds nothing by the time it may be serialized.
+enum KeyProbeMode : uint32_t { kKpPlain = 0, kKpCounted = 1, kKpStrings = 2, kKpRows = 3 };
 struct KeyProbeTask {
   int column, spec_index;
-  bool set, counted;
-  bool rows;  // tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
-  // tgx_plan_set_key_probe_strings: the column is a string column, the set holds fingerprints, and a missing key of up
-  // to max_value_bytes bytes keeps its bytes
-  bool strings;
-  uint32_t max_value_bytes;
+  bool set;
+  KeyProbeMode mode;
+  uint32_t max_value_bytes;  // a strings task's; 0 otherwise
   tgx_key_probe_params params;
 };
 

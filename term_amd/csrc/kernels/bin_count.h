@@ -43,6 +43,14 @@ __device__ __forceinline__ void bin_flush(const unsigned int *cells, uint32_t n,
   }
 }
 
+// the sum of the wave's 64 lanes of an integer term (32- or 64-bit, wrapping), in lane 0; every lane takes part
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_down(v, dlt, 64);
+  return v;
+}
+
 // the wave's sums of two per-lane counters into out[0] and out[1]
 __device__ __forceinline__ void tail_flush(uint32_t a, uint32_t b, unsigned long long *__restrict__ out) {
 #pragma unroll

@@ -46,7 +46,9 @@ __device__ __forceinline__ void kp_insert_global(const KeyProbeTable &t, unsigne
   else atomicAdd(&t.words[kKpOverflow], weight);
 }
 
-// the wave's sums of a count and a digest term into the build's counters (non-zero counts only)
+// the wave's sums of a count and a digest term into the build's counters (non-zero counts only).  (Two wave_sums, with
+// their shuffles taken step by step together as tail_flush takes its two: one after the other they come to the same
+// sums, but the build kernels' tails are scheduled differently)
 __device__ __forceinline__ void kp_build_flush(unsigned long long made, unsigned long long digest, KeyProbeBuild *b) {
 #pragma unroll
   for (int dlt = 32; dlt >= 1; dlt >>= 1) {
@@ -57,13 +59,6 @@ __device__ __forceinline__ void kp_build_flush(unsigned long long made, unsigned
     atomicAdd(&b->keys, made);
     atomicAdd(&b->digest, digest);
   }
-}
-
-// the wave's sum of a 64-bit term, in lane 0
-__device__ __forceinline__ unsigned long long kp_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_down(v, dlt, 64);
-  return v;
 }
 
 // a counted build: the largest count a key has come to.  (Counts only grow and their sum is below 2^63: the largest
@@ -144,11 +139,11 @@ __global__ __launch_bounds__(256) void key_probe_reduce_kernel(const unsigned lo
     hi = oh > hi ? oh : hi;
   }
   if (kCounted) {
-    zeros = kp_wave_sum(zeros);
-    p0 = kp_wave_sum(p0);
-    p1 = kp_wave_sum(p1);
-    p2 = kp_wave_sum(p2);
-    cdigest = kp_wave_sum(cdigest);
+    zeros = wave_sum(zeros);
+    p0 = wave_sum(p0);
+    p1 = wave_sum(p1);
+    p2 = wave_sum(p2);
+    cdigest = wave_sum(cdigest);
   }
   if ((threadIdx.x & 63) == 0 && lo <= hi) {
     atomicMin(&b->min, lo);
@@ -345,7 +340,7 @@ __global__ __launch_bounds__(kKeyProbeBlock) void key_probe_kernel(const KeyProb
   tail_flush(non_null, matched, t.words);     // kKpNonNull, kKpMatched
   tail_flush(marker, 0u, t.words + kKpMarker);
   if (kRoute >= kKpRouteCountArray) {
-    pairs = kp_wave_sum(pairs);
+    pairs = wave_sum(pairs);
     if (lane == 0 && pairs) atomicAdd(&t.words[kKpPairs], pairs);
   }
   __syncthreads();

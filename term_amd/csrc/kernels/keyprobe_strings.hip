@@ -47,13 +47,6 @@ __device__ __forceinline__ bool kps_lookup(const KeyProbeStringSet &s, unsigned 
   return false;
 }
 
-// the wave's sum of a 64-bit term, in lane 0
-__device__ __forceinline__ unsigned long long kps_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_down(v, dlt, 64);
-  return v;
-}
-
 }  // namespace
 
 // ---- the build -----------------------------------------------------------------------------------------------------------
@@ -86,9 +79,9 @@ __global__ __launch_bounds__(256) void key_probe_build_strings_kernel(const unsi
       h = (h + 1) & mask;
     }
   }
-  made_n = kps_wave_sum(made_n);
-  digest = kps_wave_sum(digest);
-  markers = kps_wave_sum(markers);
+  made_n = wave_sum(made_n);
+  digest = wave_sum(digest);
+  markers = wave_sum(markers);
   if ((threadIdx.x & 63) == 0) {
     if (made_n) {
       atomicAdd(&b->keys, made_n);
@@ -174,9 +167,9 @@ __global__ __launch_bounds__(256) void key_probe_dict_kernel(const Utf8ColDesc d
     else if (len > t.max_value_bytes) too_long += n;
     else vc_insert_global128(t, fa, fb, n, p, (uint32_t)len, &t.words[kKpOverflow]);
   }
-  non_null = kps_wave_sum(non_null);
-  matched = kps_wave_sum(matched);
-  too_long = kps_wave_sum(too_long);
+  non_null = wave_sum(non_null);
+  matched = wave_sum(matched);
+  too_long = wave_sum(too_long);
   if ((threadIdx.x & 63) == 0) {
     if (non_null) atomicAdd(&t.words[kKpNonNull], non_null);
     if (matched) atomicAdd(&t.words[kKpMatched], matched);

@@ -29,12 +29,6 @@ namespace tgx {
 
 namespace {
 
-__device__ __forceinline__ uint32_t vr_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int dlt = 32; dlt >= 1; dlt >>= 1) v += __shfl_down(v, dlt, 64);
-  return v;
-}
-
 // kRules: rules evaluated per row (those from `n` on match nothing).  kFloat: the column's bits are doubles.  kKeys: a
 // rule reads the totalOrder key (every range rule of a float column does).  kInteger: a rule is kRuleInteger.
 template <int kRules, bool kFloat, bool kKeys, bool kInteger>
@@ -79,12 +73,12 @@ __device__ __forceinline__ void vr_scan(const ComomentColDesc &d, const ValueRul
   });
 
   const bool first = (threadIdx.x & 63) == 0;
-  const uint32_t c = vr_wave_sum(considered);
+  const uint32_t c = wave_sum(considered);
   if (first && c) atomicAdd(&counts[R[0].word + 2], (unsigned long long)c);  // (once per group: in its first rule's slot)
 #pragma unroll
   for (int r = 0; r < kRules; r++) {
-    const uint32_t a = vr_wave_sum(valid[r]);
-    const uint32_t e = kInteger ? vr_wave_sum(cast_errors[r]) : 0u;
+    const uint32_t a = wave_sum(valid[r]);
+    const uint32_t e = kInteger ? wave_sum(cast_errors[r]) : 0u;
     if (first && r < n) {
       unsigned long long *out = counts + R[r].word;
       if (a) atomicAdd(&out[0], (unsigned long long)a);

@@ -1,5 +1,5 @@
 // keyed_state.h -- what the kinds share, on top of counted_state.h, whose tasks count the values of ONE column, an int64
-// or bytes (VALUE_COUNTS, GROUP_COUNTS, GROUP_SUMS): the host's entries, key -> payload, with their blob form and their
+// or bytes (VALUE_COUNTS, GROUP_COUNTS, GROUP_SUMS, and KEY_PROBE for its missing keys): the host's entries, key -> payload, with their blob form and their
 // *_entries call, and the device table's key half -- its layout, its view, decoding a slot's key, and the refusals of a
 // column that changes between integers and strings.  A kind adds a payload (what it keeps per key, with its wire form),
 // its row classes beside the keys, and its launches.
@@ -106,9 +106,10 @@ TGX_HIDDEN inline const char *type_name(int type) {
   }
 }
 
-// K gives, beyond what CountedState asks: Payload; a Host that is a KeyedEntries<Payload>; a Task with
-// params.max_value_bytes; and
-//   bound(task)   the most keys the task counts
+// K gives, beyond what CountedState asks: Payload; a Host that is a KeyedEntries<Payload>; and
+//   bound(task)             the most keys the task counts
+//   max_value_bytes(task)   the most bytes a string key keeps: the task's params.max_value_bytes, unless the kind keeps it
+//                           beside its ABI struct (KEY_PROBE)
 //   kNoun         what the kind calls a key ("value", "key")
 //   kColumn       the key column as the refusal of a changed column names it
 //   kDiffers      what states with integer and with string keys were counted under
@@ -134,6 +135,9 @@ struct TGX_HIDDEN KeyedCheck : CountedState<K> {
 
   explicit KeyedCheck(const tgx_plan *plan) : CountedState<K>(plan), dev_part(K::tasks(plan).size()), tasks(K::tasks(plan)) {}
 
+  // the most bytes a string key of task k keeps
+  uint32_t value_bytes(size_t k) const { return K::max_value_bytes(tasks[k]); }
+
   // behind a table's counts: its further counters (arrays of `slots` 64-bit words), then for strings the lengths and
   // the bytes
   size_t lens_at(size_t k) const { return table[k].extra_at() + (size_t)table[k].slots * table[k].extra_counters; }
@@ -151,7 +155,7 @@ struct TGX_HIDDEN KeyedCheck : CountedState<K> {
     t.store = strings ? base + store_at(k) : nullptr;
     t.mask = table[k].slots - 1;
     t.salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
-    t.max_value_bytes = tasks[k].params.max_value_bytes;
+    t.max_value_bytes = value_bytes(k);
   }
 
   // table k made for keys of `kind`, with `counters` bytes a slot of further counters, unless it is
@@ -163,7 +167,7 @@ struct TGX_HIDDEN KeyedCheck : CountedState<K> {
                   K::kColumn);
     const bool strings = kind == kByteKeys;
     TGX_TRY(this->open_table(st, k, K::bound(tasks[k]), strings ? 2 : 1,
-                             counters + (strings ? 4 + (size_t)tasks[k].params.max_value_bytes : 0), err, counters));
+                             counters + (strings ? 4 + (size_t)value_bytes(k) : 0), err, counters));
     d.kind = kind;
     return TGX_OK;
   }
@@ -200,7 +204,7 @@ struct TGX_HIDDEN KeyedCheck : CountedState<K> {
       o.ints[(int64_t)keys[s]] += slot_payload(k, h, s, count);
     } else {
       if (keys[table[t].slots + s] == kEmptyKey) return;  // (claimed, not settled: nothing was counted into it yet)
-      const uint32_t most = tasks[t].params.max_value_bytes, len = std::min(((const uint32_t *)(h + lens_at(t)))[s], most);
+      const uint32_t most = value_bytes(t), len = std::min(((const uint32_t *)(h + lens_at(t)))[s], most);
       o.strs[std::string((const char *)h + store_at(t) + (size_t)s * most, len)] += slot_payload(k, h, s, count);
     }
   }

@@ -26,6 +26,13 @@
 // batch, merge or blob that could carry it past 2^64 - 1.
 // The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
 // under: what was merged in or read from a blob, and what the device part is folded into whenever the state is read.
+//
+// How the module is put together.  A task has ONE mode (KeyProbeMode, internal.h); kModes says what differs by mode in
+// words, and plan_set_mode is the one body of the four tgx_plan_set_key_probe* calls.  ProbeCheck is a KeyedCheck
+// (keyed_state.h): the table of missing keys, its views, its decoding and the dictionary route's cells are that
+// skeleton's; what KEY_PROBE adds is the parent set with its identity (so merge_from, serialize, collect and read_spec
+// are its own), `pairs` with its bound, and the gathered rows.  tgx_key_probe_set_parent is the checks, choose_route,
+// and one build function per route that fills a ParentSet, whose view() is what the kernels take.
 #include "keyed_state.h"
 
 namespace tgx {
@@ -85,14 +92,19 @@ struct NoRange {};
 struct ProbeKind {
   typedef KeyProbeTask Task;
   typedef ProbeHost Host;
+  typedef uint64_t Payload;
   typedef NoRange Range;
   static constexpr bool kRanged = false;
   static constexpr int kKind = TGX_CHECK_KEY_PROBE;
   static constexpr const char *kDiffers = "parent sets";
+  static constexpr const char *kNoun = "key";
+  static constexpr const char *kColumn = "the column";  // (a task's mode fixes its kind of key: the refusal cannot fire)
   static constexpr uint32_t kMagic = 0x4252504b;  // "KPRB"
 
   static const std::vector<KeyProbeTask> &tasks(const tgx_plan *plan) { return plan->key_probes; }
   static size_t words(const KeyProbeTask &) { return kKeyProbeWords; }
+  static uint32_t bound(const KeyProbeTask &t) { return t.params.max_missing_keys; }
+  static uint32_t max_value_bytes(const KeyProbeTask &t) { return t.max_value_bytes; }
   static NoRange range_identity() { return NoRange(); }
   static ProbeHost fresh(const KeyProbeTask &) { return ProbeHost(); }
   static size_t shape(const ProbeHost &) { return 0; }  // (the sets' identities: ProbeCheck::merge_from)
@@ -104,7 +116,7 @@ struct ProbeKind {
     d.matched = w[kKpMatched];
     d.overflow_rows = w[kKpOverflow];
     d.pairs = w[kKpPairs];
-    if (t.strings) {  // (no string has the marker's bits)
+    if (t.mode == kKpStrings) {  // (no string has the marker's bits)
       d.long_rows = w[kKpLong];
       return d;
     }
@@ -132,18 +144,19 @@ struct ProbeKind {
   // n_entries and the entries
   // a strings task: the second u32 0 is 2, { u32 max_value_bytes, u32 0, u64 long_rows } stand between n_entries and the
   // entries, and an entry is { u32 length, u8 bytes[length], u64 count }, ascending bytewise
-  static uint32_t mode(const KeyProbeTask &t) { return t.counted ? 1u : t.strings ? 2u : 0u; }
+  // (the mode word is the task's mode; a rows task, whose state serializes only while it is empty, writes a plain one's)
+  static uint32_t mode_word(const KeyProbeTask &t) { return t.mode == kKpRows ? (uint32_t)kKpPlain : (uint32_t)t.mode; }
   static void write(const KeyProbeTask &t, const ProbeHost &h, Writer &w) {
     w.pod(t.params);
     w.pod((uint32_t)(h.known ? 1 : 0));
-    w.pod(mode(t));
+    w.pod(mode_word(t));
     const uint64_t words[7] = {h.parent_keys, h.parent_digest, h.seen, h.non_null, h.matched, h.overflow_rows, h.size()};
     w.pod(words);
-    if (t.counted) {
+    if (t.mode == kKpCounted) {
       const uint64_t more[4] = {h.parent_rows, h.parent_count_digest, h.max_count, h.pairs};
       w.pod(more);
     }
-    if (t.strings) {
+    if (t.mode == kKpStrings) {
       w.pod(t.max_value_bytes);
       w.pod((uint32_t)0);
       w.pod(h.long_rows);
@@ -158,25 +171,26 @@ struct ProbeKind {
     uint64_t words[7], more[4] = {0, 0, 0, 0};
     r.get(words, sizeof(words));
     if (!r.ok) return TGX_OK;
-    if (pad != mode(t))
+    const bool counted = t.mode == kKpCounted, strings = t.mode == kKpStrings;
+    if (pad != mode_word(t))
       return fail(err, TGX_INVALID_ARGUMENT,
-                  pad > 2 ? "malformed state blob (KEY_PROBE task %zu: parent set)"
-                  : pad == 2 || t.strings
+                  pad > kKpStrings ? "malformed state blob (KEY_PROBE task %zu: parent set)"
+                  : pad == kKpStrings || strings
                       ? "KEY_PROBE task %zu: the blob was counted under the other mode (integer / string keys) than the plan's"
                       : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
                   k);
-    if (t.counted) r.get(more, sizeof(more));
+    if (counted) r.get(more, sizeof(more));
     uint32_t value_bytes = 0, value_pad = 0;
     uint64_t long_rows = 0;
-    if (t.strings) {
+    if (strings) {
       value_bytes = r.pod<uint32_t>();
       value_pad = r.pod<uint32_t>();
       long_rows = r.pod<uint64_t>();
     }
     if (!r.ok) return TGX_OK;
-    if (t.strings && value_pad != 0)
+    if (strings && value_pad != 0)
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: string keys)", k);
-    if (t.strings && value_bytes != t.max_value_bytes)
+    if (strings && value_bytes != t.max_value_bytes)
       return fail(err, TGX_INVALID_ARGUMENT,
                   "KEY_PROBE task %zu: the blob was counted under other parameters (max_value_bytes %u) than the plan's "
                   "(%u)", k, value_bytes, t.max_value_bytes);
@@ -189,7 +203,7 @@ struct ProbeKind {
                                  more[2] != 0 || more[3] != 0 || long_rows != 0)))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: parent set)", k);
     // a counted set: keys <= rows < 2^63, the largest count is one of them; matched <= pairs <= matched * max_count
-    if (t.counted) {
+    if (counted) {
       uint64_t most = 0;
       const bool set_ok = more[0] >= words[0] && more[0] < ((uint64_t)1 << 63) && more[2] <= more[0] &&
                           (more[2] != 0) == (words[0] != 0);
@@ -197,16 +211,16 @@ struct ProbeKind {
       if (!set_ok || more[3] < words[4] || (!wraps && more[3] > most))
         return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: counted set and pairs)", k);
     }
-    uint64_t counted = 0;
-    TGX_TRY(keyed_read_entries("KEY_PROBE", "key", k, r, t.strings ? kByteKeys : kIntKeys, n, t.max_value_bytes,
-                               CountWire(), h, &counted, err));
+    uint64_t in_entries = 0;
+    TGX_TRY(keyed_read_entries("KEY_PROBE", kNoun, k, r, strings ? kByteKeys : kIntKeys, n, t.max_value_bytes,
+                               CountWire(), h, &in_entries, err));
     if (!r.ok) return TGX_OK;
     // matched + counted + overflow_rows (+ long_rows) == non_null <= seen
-    if (non_null > seen || !terms_make(non_null, {words[4], counted, words[5], long_rows}))
+    if (non_null > seen || !terms_make(non_null, {words[4], in_entries, words[5], long_rows}))
       return fail(err, TGX_INVALID_ARGUMENT,
                   "malformed state blob (KEY_PROBE task %zu: matched + counted + overflow_rows%s != non_null)", k,
-                  t.strings ? " + long_rows" : "");
-    h.kind = !n ? kNoKeys : t.strings ? kByteKeys : kIntKeys;
+                  strings ? " + long_rows" : "");
+    h.kind = !n ? kNoKeys : strings ? kByteKeys : kIntKeys;
     h.long_rows = long_rows;
     h.known = known != 0;
     h.parent_keys = words[0];
@@ -222,6 +236,18 @@ struct ProbeKind {
     return TGX_OK;
   }
 };
+
+// what differs by mode in words: how a refusal names a spec that was set that way, the suffix of its
+// tgx_plan_set_key_probe* call, and the bytes of a record of its parent set (a rows task: of the records it gathers)
+struct ModeInfo {
+  const char *set_as, *suffix;
+  uint32_t record_bytes;
+};
+constexpr ModeInfo kModes[] = {{"plain", "", 16},
+                               {"counted", "_counted", 16},
+                               {"to probe string keys", "_strings", 32},
+                               {"to gather rows", "_rows", 16}};
+static_assert(kKpPlain == 0 && kKpCounted == 1 && kKpStrings == 2 && kKpRows == 3, "kModes is indexed by the mode");
 
 // the set of one task on the device
 struct ParentSet {
@@ -241,10 +267,35 @@ struct ParentSet {
     h.parent_count_digest = count_digest;
     h.max_count = max_count;
   }
+  // the set as the kernels take it: routes 0 .. 4, and route 5 (or the empty set of a strings task)
+  KeyProbeSet view() const {
+    KeyProbeSet v;
+    memset(&v, 0, sizeof(v));
+    v.bits = route == kKpRouteBitmap ? buf.as<uint32_t>() : nullptr;
+    v.keys = route == kKpRouteHash ? buf.as<unsigned long long>() : nullptr;
+    v.counts = route == kKpRouteCountArray || route == kKpRouteCountHash ? buf.as<unsigned long long>() : nullptr;
+    v.base = base;
+    v.range = range;
+    v.mask = mask;
+    v.marker_count = marker_count;
+    v.has_marker = has_marker;
+    return v;
+  }
+  KeyProbeStringSet string_view() const {
+    return KeyProbeStringSet{route == kKpRouteStrings ? buf.as<unsigned long long>() : nullptr, mask};
+  }
 };
 
-struct ProbeCheck final : CountedState<ProbeKind> {
-  const std::vector<KeyProbeTask> &tasks;
+// the route of a set of `n` > 0 records of a task of `mode`, whose keys span `range` (0: all of int64, which is not dense).
+// A dense set is no larger than the table would be: a bit a key up to 128 * n, a count a key up to 4 * n
+int choose_route(KeyProbeMode mode, uint64_t range, uint64_t n) {
+  if (mode == kKpStrings) return kKpRouteStrings;
+  const bool counted = mode == kKpCounted;
+  const bool dense = range != 0 && range <= (counted ? 4 : 128) * n;
+  return counted ? (dense ? kKpRouteCountArray : kKpRouteCountHash) : (dense ? kKpRouteBitmap : kKpRouteHash);
+}
+
+struct ProbeCheck final : KeyedCheck<ProbeKind> {
   std::vector<ParentSet> parent;
   bool fed = false;  // a batch with rows has been handed to tgx_update since the state was created or reset
   // per counted task: an upper bound of what the device part's `pairs` can have come to, the sum over the accepted
@@ -253,36 +304,20 @@ struct ProbeCheck final : CountedState<ProbeKind> {
   // per rows task: the gathered records and the records there is room for
   std::vector<DevBuf> gathered;
   std::vector<uint64_t> gathered_cap;
-  std::vector<DevBuf> cells;  // per strings task: the dictionary route's per-entry cells
 
   explicit ProbeCheck(const tgx_plan *plan)
-      : CountedState(plan), tasks(plan->key_probes), parent(plan->key_probes.size()), pairs_bound(plan->key_probes.size(), 0),
-        gathered(plan->key_probes.size()), gathered_cap(plan->key_probes.size(), 0), cells(plan->key_probes.size()) {}
+      : KeyedCheck(plan), parent(tasks.size()), pairs_bound(tasks.size(), 0), gathered(tasks.size()),
+        gathered_cap(tasks.size(), 0) {}
 
-  // a strings task's table: two key words, the counts, the lengths, the bytes (keyed_state.h's string layout)
-  size_t lens_at(size_t k) const { return table[k].extra_at(); }
-  size_t store_at(size_t k) const { return lens_at(k) + (size_t)table[k].slots * 4; }
+  uint64_t slot_payload(size_t, const uint8_t *, uint64_t, uint64_t count) const override { return count; }
 
   // a state that has gathered rows keeps them to itself
   tgx_status rows_stay(const char *what, tgx_error *err) const {
     for (size_t k = 0; k < tasks.size(); k++)
-      if (tasks[k].rows && (device_rows[k] > 0 || host[k].seen > 0))
+      if (tasks[k].mode == kKpRows && (device_rows[k] > 0 || host[k].seen > 0))
         return fail(err, TGX_UNSUPPORTED, "spec %d: a KEY_PROBE check that gathers rows does not %s: its records stay with "
                     "the state", tasks[k].spec_index, what);
     return TGX_OK;
-  }
-
-  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
-    if (tasks[k].strings) {
-      const uint64_t *keys = (const uint64_t *)h;
-      if (keys[table[k].slots + s] == kEmptyKey) return;  // (claimed, not settled: nothing was counted into it yet)
-      const uint32_t most = tasks[k].max_value_bytes, len = std::min(((const uint32_t *)(h + lens_at(k)))[s], most);
-      o.kind = kByteKeys;
-      o.strs[std::string((const char *)h + store_at(k) + (size_t)s * most, len)] += count;
-      return;
-    }
-    o.kind = kIntKeys;
-    o.ints[(int64_t)((const uint64_t *)h)[s]] += count;
   }
 
   // every task, read: host part + device part, under the identity of the set the state holds
@@ -297,14 +332,14 @@ struct ProbeCheck final : CountedState<ProbeKind> {
 
   tgx_status accepts(tgx_state *, int64_t nrows, tgx_error *err) override {
     for (size_t k = 0; k < tasks.size(); k++)
-      if (!parent[k].has && !tasks[k].rows)
+      if (!parent[k].has && tasks[k].mode != kKpRows)
         return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
                     tasks[k].spec_index);
     // a counted task: host part + bound of the device part + this batch's bound stays within 2^64 - 1, for every task
     // before any bound moves
     std::vector<uint64_t> next(pairs_bound);
     for (size_t k = 0; k < tasks.size(); k++) {
-      if (!tasks[k].counted || nrows <= 0) continue;
+      if (tasks[k].mode != kKpCounted || nrows <= 0) continue;
       uint64_t batch = 0, all = 0;
       if (__builtin_mul_overflow(parent[k].max_count, (uint64_t)nrows, &batch) || !add_fits(next[k], batch, &next[k]) ||
           !add_fits(next[k], host[k].pairs, &all))
@@ -320,7 +355,7 @@ struct ProbeCheck final : CountedState<ProbeKind> {
   tgx_status reset(tgx_state *st, tgx_error *err) override {
     fed = false;
     std::fill(pairs_bound.begin(), pairs_bound.end(), 0);
-    return CountedState::reset(st, err);
+    return KeyedCheck::reset(st, err);
   }
 
   // may `theirs` be added to what this state holds?  (pairs of a plain task are 0)
@@ -333,38 +368,123 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
-  // route 5: the set of strings task k from `n` 32-byte {hash_a, hash_b, count, 0} records; one wait
+  // ---- the parent set: the checks (set_parent), the route (choose_route), one build a route ----
+  // what a build kernel left in the build struct `d`: one wait
+  template <class Build>
+  static tgx_status read_back(tgx_state *st, const DevBuf &d, Build *b, tgx_error *err) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b, d.p, sizeof(*b), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    return TGX_OK;
+  }
+  // a refused set leaves the state without one: the set it had is dropped
+  tgx_status drop_set(size_t k, tgx_status refusal) {
+    parent[k] = ParentSet();
+    return refusal;
+  }
+  // the set's memory, every byte `fill` (0xFF: every word kEmptyKey)
+  static tgx_status set_memory(tgx_state *st, ParentSet *s, size_t bytes, int fill, tgx_error *err) {
+    HIP_TRY(s->buf.reserve(bytes));
+    HIP_TRY(hipMemsetAsync(s->buf.p, fill, bytes, st->stream));
+    return TGX_OK;
+  }
+
+  // routes 1 and 3 span [s->base, s->base + s->range); routes 2, 4 and 5 have s->mask + 1 slots
+  static tgx_status build_bitmap(tgx_state *st, const void *recs, uint64_t n, KeyProbeBuild *b, ParentSet *s, tgx_error *err) {
+    TGX_TRY(set_memory(st, s, (size_t)((s->range + 31) / 32) * 4, 0, err));
+    launch_key_probe_build_bitmap(recs, n, s->buf.as<uint32_t>(), s->base, s->range, b, st->stream);
+    return TGX_OK;
+  }
+  static tgx_status build_hash(tgx_state *st, const void *recs, uint64_t n, KeyProbeBuild *b, ParentSet *s, tgx_error *err) {
+    TGX_TRY(set_memory(st, s, (size_t)(s->mask + 1) * 8, 0xFF, err));
+    launch_key_probe_build_hash(recs, n, s->buf.as<unsigned long long>(), s->mask, b, st->stream);
+    return TGX_OK;
+  }
+  static tgx_status build_count_array(tgx_state *st, const void *recs, uint64_t n, KeyProbeBuild *b, ParentSet *s,
+                                      tgx_error *err) {
+    TGX_TRY(set_memory(st, s, (size_t)s->range * 8, 0, err));
+    launch_key_probe_build_count_array(recs, n, s->buf.as<unsigned long long>(), s->base, s->range, b, st->stream);
+    return TGX_OK;
+  }
+  static tgx_status build_count_hash(tgx_state *st, const void *recs, uint64_t n, KeyProbeBuild *b, ParentSet *s,
+                                     tgx_error *err) {
+    HIP_TRY(s->buf.reserve((size_t)(s->mask + 1) * 16));  // (the launcher clears the slots: {kEmptyKey, 0})
+    launch_key_probe_build_count_hash(recs, n, s->buf.as<unsigned long long>(), s->mask, b, st->stream);
+    return TGX_OK;
+  }
+
+  // routes 1 .. 4: the set of task k from `n` > 0 16-byte {key, count} records; a reduction, the route's build, two waits
+  tgx_status build_integers(tgx_state *st, size_t k, const void *recs, uint64_t n, ParentSet *s, tgx_error *err) {
+    const KeyProbeMode mode = tasks[k].mode;
+    DevBuf d_build;
+    HIP_TRY(d_build.reserve(sizeof(KeyProbeBuild)));
+    KeyProbeBuild b;
+    memset(&b, 0, sizeof(b));
+    b.min = INT64_MAX;
+    b.max = INT64_MIN;
+    HIP_TRY(hipMemcpyAsync(d_build.p, &b, sizeof(b), hipMemcpyHostToDevice, st->stream));
+    launch_key_probe_reduce(recs, n, mode == kKpCounted, d_build.as<KeyProbeBuild>(), st->stream);
+    TGX_TRY(read_back(st, d_build, &b, err));
+    if (mode == kKpCounted) {
+      if (b.zero_counts)
+        return drop_set(k, fail(err, TGX_INVALID_ARGUMENT, "spec %d: %llu records of the parent set have a count of 0",
+                                tasks[k].spec_index, (unsigned long long)b.zero_counts));
+      const unsigned __int128 total = (unsigned __int128)b.sum_piece[0] +
+                                      ((unsigned __int128)b.sum_piece[1] << kKpPieceBits) +
+                                      ((unsigned __int128)b.sum_piece[2] << (2 * kKpPieceBits));
+      if (total >> 63)
+        return drop_set(k, fail(err, TGX_UNSUPPORTED, "spec %d: the counts of the parent set sum to 2^63 or more",
+                                tasks[k].spec_index));
+      s->rows = (uint64_t)total;
+      s->count_digest = b.count_digest;
+    }
+    // (unsigned: INT64_MIN and INT64_MAX together wrap the range to 0, which is not dense)
+    const uint64_t range = (uint64_t)b.max - (uint64_t)b.min + 1;
+    s->route = choose_route(mode, range, n);
+    if (s->route == kKpRouteBitmap || s->route == kKpRouteCountArray) {
+      s->base = (uint64_t)b.min;
+      s->range = range;
+    } else {
+      s->mask = table_slots(n) - 1;
+    }
+    KeyProbeBuild *d = d_build.as<KeyProbeBuild>();
+    TGX_TRY(s->route == kKpRouteBitmap       ? build_bitmap(st, recs, n, d, s, err)
+            : s->route == kKpRouteHash       ? build_hash(st, recs, n, d, s, err)
+            : s->route == kKpRouteCountArray ? build_count_array(st, recs, n, d, s, err)
+                                             : build_count_hash(st, recs, n, d, s, err));
+    TGX_TRY(read_back(st, d_build, &b, err));
+    s->has_marker = b.has_marker;
+    s->marker_count = b.marker_count;
+    s->max_count = b.max_count;
+    s->keys = b.keys;
+    s->digest = b.digest;
+    return TGX_OK;
+  }
+
+  // route 5: the set of strings task k from `n` > 0 32-byte {hash_a, hash_b, count, 0} records; one wait
   tgx_status build_strings(tgx_state *st, size_t k, const void *recs, uint64_t n, ParentSet *s, tgx_error *err) {
-    if (n == 0) return TGX_OK;
-    ProfScope ps(st, "key_probe_build", n * 32);
     DevBuf d_build;
     HIP_TRY(d_build.reserve(sizeof(KeyProbeStringsBuild)));
     HIP_TRY(hipMemsetAsync(d_build.p, 0, sizeof(KeyProbeStringsBuild), st->stream));
-    s->route = kKpRouteStrings;
-    uint64_t slots = 2;
-    while (slots < 2 * n) slots <<= 1;
-    s->mask = slots - 1;
-    HIP_TRY(s->buf.reserve((size_t)slots * 16));
-    HIP_TRY(hipMemsetAsync(s->buf.p, 0xFF, (size_t)slots * 16, st->stream));  // (every word: kEmptyKey)
+    s->route = choose_route(tasks[k].mode, 0, n);
+    s->mask = table_slots(n) - 1;
+    TGX_TRY(set_memory(st, s, (size_t)(s->mask + 1) * 16, 0xFF, err));
     launch_key_probe_build_strings(recs, n, s->buf.as<unsigned long long>(), s->mask, d_build.as<KeyProbeStringsBuild>(),
                                    st->stream);
-    HIP_TRY(hipGetLastError());
     KeyProbeStringsBuild b;
-    HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    if (b.marker_records) {
-      parent[k] = ParentSet();  // (a refused set leaves the state without one: the set it had is dropped)
-      return fail(err, TGX_INVALID_ARGUMENT,
-                  "spec %d: %llu records of the parent set hold the free-slot marker (all ones) in hash_a or hash_b, which "
-                  "no fingerprint is", tasks[k].spec_index, (unsigned long long)b.marker_records);
-    }
+    TGX_TRY(read_back(st, d_build, &b, err));
+    if (b.marker_records)
+      return drop_set(k, fail(err, TGX_INVALID_ARGUMENT,
+                              "spec %d: %llu records of the parent set hold the free-slot marker (all ones) in hash_a or "
+                              "hash_b, which no fingerprint is", tasks[k].spec_index, (unsigned long long)b.marker_records));
     s->keys = b.keys;
     s->digest = b.digest;
     return TGX_OK;
   }
 
   tgx_status set_parent(tgx_state *st, size_t k, const void *recs, uint64_t n, tgx_error *err) {
-    if (tasks[k].rows)
+    const KeyProbeMode mode = tasks[k].mode;
+    if (mode == kKpRows)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check that gathers rows takes no parent set",
                   tasks[k].spec_index);
     if (fed)
@@ -378,83 +498,9 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     TGX_TRY(device_init(st, err));
     ParentSet s;
     s.has = true;
-    if (tasks[k].strings) {
-      TGX_TRY(build_strings(st, k, recs, n, &s, err));
-    } else if (n > 0) {
-      ProfScope ps(st, "key_probe_build", n * 16);
-      DevBuf d_build;
-      HIP_TRY(d_build.reserve(sizeof(KeyProbeBuild)));
-      const bool counted = tasks[k].counted;
-      KeyProbeBuild b;
-      memset(&b, 0, sizeof(b));
-      b.min = INT64_MAX;
-      b.max = INT64_MIN;
-      HIP_TRY(hipMemcpyAsync(d_build.p, &b, sizeof(b), hipMemcpyHostToDevice, st->stream));
-      launch_key_probe_reduce(recs, n, counted, d_build.as<KeyProbeBuild>(), st->stream);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
-      HIP_TRY(hipStreamSynchronize(st->stream));
-      // (unsigned: INT64_MIN and INT64_MAX together wrap the range to 0, which is not dense)
-      const uint64_t range = (uint64_t)b.max - (uint64_t)b.min + 1;
-      if (counted) {
-        // (a refused set leaves the state without one: the set it had is dropped)
-        if (b.zero_counts) parent[k] = ParentSet();
-        if (b.zero_counts)
-          return fail(err, TGX_INVALID_ARGUMENT, "spec %d: %llu records of the parent set have a count of 0",
-                      tasks[k].spec_index, (unsigned long long)b.zero_counts);
-        const unsigned __int128 total = (unsigned __int128)b.sum_piece[0] +
-                                        ((unsigned __int128)b.sum_piece[1] << kKpPieceBits) +
-                                        ((unsigned __int128)b.sum_piece[2] << (2 * kKpPieceBits));
-        if (total >> 63) parent[k] = ParentSet();
-        if (total >> 63)
-          return fail(err, TGX_UNSUPPORTED, "spec %d: the counts of the parent set sum to 2^63 or more",
-                      tasks[k].spec_index);
-        s.rows = (uint64_t)total;
-        s.count_digest = b.count_digest;
-      }
-      if (counted && range != 0 && range <= 4 * n) {
-        s.route = kKpRouteCountArray;
-        s.base = (uint64_t)b.min;
-        s.range = range;
-        HIP_TRY(s.buf.reserve((size_t)range * 8));
-        HIP_TRY(hipMemsetAsync(s.buf.p, 0, (size_t)range * 8, st->stream));
-        launch_key_probe_build_count_array(recs, n, s.buf.as<unsigned long long>(), s.base, s.range,
-                                           d_build.as<KeyProbeBuild>(), st->stream);
-      } else if (counted) {
-        s.route = kKpRouteCountHash;
-        uint64_t slots = 2;
-        while (slots < 2 * n) slots <<= 1;
-        s.mask = slots - 1;
-        HIP_TRY(s.buf.reserve((size_t)slots * 16));
-        launch_key_probe_build_count_hash(recs, n, s.buf.as<unsigned long long>(), s.mask, d_build.as<KeyProbeBuild>(),
-                                          st->stream);
-      } else if (range != 0 && range <= 128 * n) {
-        s.route = kKpRouteBitmap;
-        s.base = (uint64_t)b.min;
-        s.range = range;
-        const size_t bytes = (size_t)((range + 31) / 32) * 4;
-        HIP_TRY(s.buf.reserve(bytes));
-        HIP_TRY(hipMemsetAsync(s.buf.p, 0, bytes, st->stream));
-        launch_key_probe_build_bitmap(recs, n, s.buf.as<uint32_t>(), s.base, s.range, d_build.as<KeyProbeBuild>(),
-                                      st->stream);
-      } else {
-        s.route = kKpRouteHash;
-        uint64_t slots = 2;
-        while (slots < 2 * n) slots <<= 1;
-        s.mask = slots - 1;
-        HIP_TRY(s.buf.reserve((size_t)slots * 8));
-        HIP_TRY(hipMemsetAsync(s.buf.p, 0xFF, (size_t)slots * 8, st->stream));  // (every slot: kEmptyKey)
-        launch_key_probe_build_hash(recs, n, s.buf.as<unsigned long long>(), s.mask, d_build.as<KeyProbeBuild>(),
-                                    st->stream);
-      }
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&b, d_build.p, sizeof(b), hipMemcpyDeviceToHost, st->stream));
-      HIP_TRY(hipStreamSynchronize(st->stream));
-      s.has_marker = b.has_marker;
-      s.marker_count = b.marker_count;
-      s.max_count = b.max_count;
-      s.keys = b.keys;
-      s.digest = b.digest;
+    if (n > 0) {  // (without records: the empty set, route 0)
+      ProfScope ps(st, "key_probe_build", n * kModes[mode].record_bytes);
+      TGX_TRY(mode == kKpStrings ? build_strings(st, k, recs, n, &s, err) : build_integers(st, k, recs, n, &s, err));
     }
     ProbeHost &h = host[k];
     ProbeHost given;
@@ -469,64 +515,52 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
+  // ---- a batch ----
+  // the table of missing integer keys of task k as the kernels take it
+  KeyProbeTable int_view(const tgx_state *st, size_t k) const {
+    uint8_t *base = table[k].buf.as<uint8_t>();
+    KeyProbeTable t;
+    t.keys = (unsigned long long *)base;
+    t.counts = (unsigned long long *)(base + table[k].counts_at());
+    t.words = d_counts.as<unsigned long long>() + word_off[k];
+    t.mask = table[k].slots - 1;
+    t.salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
+    return t;
+  }
+
+  // (accepts has seen to it that every task that probes has its set)
   tgx_status update(tgx_state *st, const tgx_column *dev, int64_t nrows, tgx_error *err) override {
     if (nrows <= 0) return TGX_OK;
     TGX_TRY(device_init(st, err));
     table_cache_ok = false;
     for (size_t k = 0; k < tasks.size(); k++) {
-      if (tasks[k].strings) {
-        const int type = dev[tasks[k].column].type;
-        if (!is_any_string(type) && type != TGX_DICT32_UTF8)
-          return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on string keys takes string columns (%d)", type);
-        if (!parent[k].has)
-          return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
-                      tasks[k].spec_index);
-        if (!table[k].live)
-          TGX_TRY(open_table(st, k, tasks[k].params.max_missing_keys, 2, 4 + (size_t)tasks[k].max_value_bytes, err));
+      const tgx_column &x = dev[tasks[k].column];
+      const Route route = route_of(x);
+      if (tasks[k].mode == kKpStrings) {
+        if (route != kStringRoute && route != kDictRoute)
+          return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on string keys takes string columns (%d)", x.type);
+        TGX_TRY(ensure_keys(st, k, kByteKeys, 0, err));
         continue;
       }
       // (an Int64 view: update_validate refuses what is not widened to one)
-      if (dev[tasks[k].column].type != TGX_INT64)
-        return fail(err, TGX_UNSUPPORTED, "KEY_PROBE takes integer columns (%d)", dev[tasks[k].column].type);
-      if (tasks[k].rows) {
-        TGX_TRY(gather_rows(st, k, dev[tasks[k].column], nrows, err));
-        continue;
-      }
-      if (!parent[k].has)
-        return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
-                    tasks[k].spec_index);
-      if (!table[k].live) TGX_TRY(open_table(st, k, tasks[k].params.max_missing_keys, 1, 0, err));
+      if (route != kIntRoute) return fail(err, TGX_UNSUPPORTED, "KEY_PROBE takes integer columns (%d)", x.type);
+      if (tasks[k].mode == kKpRows) TGX_TRY(gather_rows(st, k, x, nrows, err));
+      else TGX_TRY(ensure_keys(st, k, kIntKeys, 0, err));
     }
-    const uint64_t salt = (uint64_t)st->plan->fp_key.k[0] | ((uint64_t)st->plan->fp_key.k[1] << 32);
     for (int route = kKpRouteEmpty; route <= kKpRouteCountHash; route++) {
-      std::vector<size_t> slots;
-      for (size_t k = 0; k < tasks.size(); k++)
-        if (parent[k].route == route && !tasks[k].rows && !tasks[k].strings) slots.push_back(k);
-      for (size_t t0 = 0; t0 < slots.size(); t0 += kMaxKeyProbePerLaunch) {
-        const int n = (int)std::min<size_t>(kMaxKeyProbePerLaunch, slots.size() - t0);
+      // (side_launches asks about the elements of `tasks` themselves: a task's address gives its index)
+      auto on_route = [&](const KeyProbeTask &t) {
+        return t.mode <= kKpCounted && parent[(size_t)(&t - tasks.data())].route == route;
+      };
+      TGX_TRY(side_launches(tasks, on_route, [&](const int *slots, int n) -> tgx_status {
         KeyProbeLaunch L;
         memset(&L, 0, sizeof(L));
         uint64_t bytes = 0;
         for (int i = 0; i < n; i++) {
-          const size_t k = slots[t0 + i];
-          const ParentSet &s = parent[k];
+          const size_t k = (size_t)slots[i];
           bytes += side_fill_x(L.cols[i], dev[tasks[k].column]);
-          KeyProbeSet &ds = L.sets[i];
-          ds.bits = route == kKpRouteBitmap ? s.buf.as<uint32_t>() : nullptr;
-          ds.keys = route == kKpRouteHash ? s.buf.as<unsigned long long>() : nullptr;
-          ds.counts = route >= kKpRouteCountArray ? s.buf.as<unsigned long long>() : nullptr;
-          ds.marker_count = s.marker_count;
-          ds.base = s.base;
-          ds.range = s.range;
-          ds.mask = s.mask;
-          ds.has_marker = s.has_marker;
-          KeyProbeTable &dt = L.tables[i];
-          uint8_t *base = table[k].buf.as<uint8_t>();
-          dt.keys = (unsigned long long *)base;
-          dt.counts = (unsigned long long *)(base + table[k].counts_at());
-          dt.words = d_counts.as<unsigned long long>() + word_off[k];
-          dt.mask = table[k].slots - 1;
-          dt.salt = salt;
+          L.sets[i] = parent[k].view();
+          L.tables[i] = int_view(st, k);
         }
         // 16 waves a workgroup and 96 KiB of LDS: one workgroup a CU
         const int blocks = side_blocks(nrows, kKeyProbeBlock, g_ctx.n_cu, 1, n);
@@ -534,10 +568,11 @@ struct ProbeCheck final : CountedState<ProbeKind> {
         ProfScope ps(st, "key_probe", bytes);
         launch_key_probe(L, route, n, blocks, st->stream);
         HIP_TRY(hipGetLastError());
-      }
+        return TGX_OK;
+      }));
     }
     for (size_t k = 0; k < tasks.size(); k++)
-      if (tasks[k].strings) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
+      if (tasks[k].mode == kKpStrings) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
     for (size_t k = 0; k < tasks.size(); k++) device_rows[k] += nrows;
     return TGX_OK;
   }
@@ -545,36 +580,25 @@ struct ProbeCheck final : CountedState<ProbeKind> {
   // one batch of strings task k: a row per lane, or the dictionary's two steps (VALUE_COUNTS's routes)
   tgx_status probe_strings(tgx_state *st, size_t k, const tgx_column &x, int64_t nrows, tgx_error *err) {
     const tgx_plan *plan = st->plan;
-    const ParentSet &s = parent[k];
-    KeyProbeStringSet set;
-    set.slots = s.route == kKpRouteStrings ? s.buf.as<unsigned long long>() : nullptr;
-    set.mask = s.mask;
+    const KeyProbeStringSet set = parent[k].string_view();
     ValueCountsTable t;
-    memset(&t, 0, sizeof(t));
-    uint8_t *base = table[k].buf.as<uint8_t>();
-    t.keys = (unsigned long long *)base;
-    t.keys2 = t.keys + table[k].slots;
-    t.counts = (unsigned long long *)(base + table[k].counts_at());
-    t.lens = (uint32_t *)(base + lens_at(k));
-    t.store = base + store_at(k);
+    fill_view(st, k, t);
+    t.counts = (unsigned long long *)(table[k].buf.as<uint8_t>() + table[k].counts_at());
     t.words = d_counts.as<unsigned long long>() + word_off[k];  // (the task's kKeyProbeWords counters)
-    t.mask = table[k].slots - 1;
-    t.max_value_bytes = tasks[k].max_value_bytes;
     // (per-lane and LDS counters are 32-bit: the launchers take up to 2048 workgroups, 1024 for the dictionary's indices)
     TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
     if (x.type != TGX_DICT32_UTF8) {
       ProfScope ps(st, "key_probe", 0);
       launch_key_probe_utf8(string_desc(x, x.variadic, plan->fp_key), set, t, st->stream);
     } else {
-      const tgx_column *dc = x.dictionary;
-      if (!dc || !is_string(dc->type)) return fail(err, TGX_INVALID_ARGUMENT, "KEY_PROBE: malformed dictionary");
+      const tgx_column *dc;
+      TGX_TRY(dictionary_of(x, &dc, err));
       if (dc->length > 0) {  // (without entries every row is a row without a value)
-        const size_t bytes = (size_t)dc->length * 8;
-        HIP_TRY(cells[k].reserve_roomy(bytes));
-        HIP_TRY(hipMemsetAsync(cells[k].p, 0, bytes, st->stream));
+        unsigned long long *cells;
+        TGX_TRY(clear_cells(st, k, (size_t)dc->length * 8, &cells, err));
         ProfScope ps(st, "key_probe", (uint64_t)x.length * 4);
         launch_key_probe_dict((const int32_t *)x.values, x.validity, x.offset, x.length,
-                              string_desc(*dc, nullptr, plan->fp_key), cells[k].as<unsigned long long>(), set, t, st->stream);
+                              string_desc(*dc, nullptr, plan->fp_key), cells, set, t, st->stream);
       }
     }
     HIP_TRY(hipGetLastError());
@@ -609,7 +633,7 @@ struct ProbeCheck final : CountedState<ProbeKind> {
 
   // the records of rows task k (device memory, the state's until its next batch or reset)
   tgx_status rows_get(tgx_state *st, size_t k, const void **records, uint64_t *n, tgx_error *err) {
-    if (!tasks[k].rows)
+    if (tasks[k].mode != kKpRows)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: the KEY_PROBE check does not gather rows (tgx_plan_set_key_probe_rows)",
                   tasks[k].spec_index);
     std::vector<ProbeHost> g;
@@ -619,6 +643,7 @@ struct ProbeCheck final : CountedState<ProbeKind> {
     return TGX_OK;
   }
 
+  // (KeyedCheck's merge, serialize and read_spec know nothing of a set's identity, of rows that stay, or of `pairs`)
   tgx_status merge_from(tgx_state *st, tgx_state *src, tgx_error *err) override {
     TGX_TRY(rows_stay("merge", err));
     TGX_TRY(static_cast<ProbeCheck *>(of(src))->rows_stay("merge", err));
@@ -677,10 +702,9 @@ tgx_status keyprobe_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_erro
     return fail(err, TGX_INVALID_ARGUMENT, "spec %d: KEY_PROBE reads one column: column2 must be -1 (%d)", spec_index,
                 sp.column2);
   KeyProbeTask t;
-  memset(&t, 0, sizeof(t));
+  memset(&t, 0, sizeof(t));  // (not set; its mode is of no account until it is)
   t.column = sp.column;
   t.spec_index = spec_index;
-  t.counted = t.rows = false;
   plan->key_probes.push_back(t);
   *slot = (int)plan->key_probes.size() - 1;
   return TGX_OK;
@@ -703,7 +727,7 @@ tgx_status keyprobe_check_column(const tgx_plan *plan, int column, const tgx_col
   // a strings task takes the string layouts and nothing else; every other task refuses them (below)
   bool strings = false, others = false;
   for (const KeyProbeTask &t : plan->key_probes)
-    if (t.column == column) (t.strings ? strings : others) = true;
+    if (t.column == column) (t.mode == kKpStrings ? strings : others) = true;
   if (strings && !is_any_string(type) && type != TGX_DICT32_UTF8)
     return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE on string keys takes string columns, not %s (type %d)", column,
                 refused_as_key(type) ? type_name(type) : "integers", type);
@@ -722,7 +746,8 @@ bool keyprobe_blob_keyed(tgx_state *st) {
   ProbeCheck *c = static_cast<ProbeCheck *>(ProbeCheck::of(st));
   if (!c) return false;
   for (size_t k = 0; k < c->tasks.size(); k++)
-    if (c->tasks[k].strings && ((c->parent[k].has && c->parent[k].keys != 0) || (c->host[k].known && c->host[k].parent_keys != 0)))
+    if (c->tasks[k].mode == kKpStrings &&
+        ((c->parent[k].has && c->parent[k].keys != 0) || (c->host[k].known && c->host[k].parent_keys != 0)))
       return true;
   return false;
 }
@@ -734,14 +759,11 @@ SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.em
 using namespace tgx;
 
 namespace {
-// how a spec that has had its tgx_plan_set_key_probe* call was set, and that call's suffix
-const char *set_as(const KeyProbeTask &t) {
-  return t.rows ? "to gather rows" : t.strings ? "to probe string keys" : t.counted ? "counted" : "plain";
-}
-const char *set_suffix(const KeyProbeTask &t) { return t.rows ? "_rows" : t.strings ? "_strings" : t.counted ? "_counted" : ""; }
-
-tgx_status plan_set_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p, bool counted, tgx_error *err) {
-  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
+// The four tgx_plan_set_key_probe* calls: `p` is the call's parameters (a rows spec has none to give: its own),
+// `max_value_bytes` a strings spec's.  (A spec keeps the mode of its first call: a call of another mode is refused)
+tgx_status plan_set_mode(tgx_plan *plan, size_t spec_index, KeyProbeMode mode, const tgx_key_probe_params *p,
+                         uint32_t max_value_bytes, tgx_error *err) {
+  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, mode == kKpRows ? "plan is NULL" : "plan/params is NULL");
   size_t slot = 0;
   TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
   if (plan_has_state(plan))
@@ -750,81 +772,20 @@ tgx_status plan_set_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_missing_keys must be 1 .. %d (%u)", spec_index,
                 (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
   if (p->reserved != 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: reserved must be 0 (%u)", spec_index, p->reserved);
+  if (mode == kKpStrings && (max_value_bytes < 1 || max_value_bytes > TGX_KEY_PROBE_MAX_VALUE_BYTES))
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
+                (int)TGX_KEY_PROBE_MAX_VALUE_BYTES, max_value_bytes);
   KeyProbeTask &t = plan->key_probes[slot];
-  // (a spec is plain or counted for good: the second of the two calls is refused)
-  if (t.set && t.strings)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set to probe string keys "
-                "(tgx_plan_set_key_probe_strings)", spec_index);
-  if (t.set && t.rows)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set to gather rows (tgx_plan_set_key_probe_rows)",
-                spec_index);
-  if (t.set && t.counted != counted)
+  if (t.set && t.mode != mode)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
-                t.counted ? "counted" : "plain", t.counted ? "_counted" : "");
+                kModes[t.mode].set_as, kModes[t.mode].suffix);
   t.params = *p;
-  t.counted = counted;
+  t.max_value_bytes = max_value_bytes;
+  t.mode = mode;
   t.set = true;
   return TGX_OK;
 }
-}  // namespace
 
-extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
-                                             tgx_error *err) try {
-  return plan_set_probe(plan, spec_index, p, false, err);
-} catch (...) {
-  return tgx::abi_exception(err);
-}
-
-extern "C" tgx_status tgx_plan_set_key_probe_counted(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
-                                                     tgx_error *err) try {
-  return plan_set_probe(plan, spec_index, p, true, err);
-} catch (...) {
-  return tgx::abi_exception(err);
-}
-
-extern "C" tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
-  if (!plan) return fail(err, TGX_INVALID_ARGUMENT, "plan is NULL");
-  size_t slot = 0;
-  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
-  if (plan_has_state(plan))
-    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a KEY_PROBE check are fixed once a state of the plan exists");
-  KeyProbeTask &t = plan->key_probes[slot];
-  if (t.set && !t.rows)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
-                set_as(t), set_suffix(t));
-  t.params = tgx_key_probe_params{1, 0};
-  t.rows = t.set = true;
-  return TGX_OK;
-} catch (...) {
-  return tgx::abi_exception(err);
-}
-
-extern "C" tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec_index,
-                                                     const tgx_key_probe_strings_params *p, tgx_error *err) try {
-  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, "plan/params is NULL");
-  size_t slot = 0;
-  TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
-  if (plan_has_state(plan))
-    return fail(err, TGX_INVALID_ARGUMENT, "the parameters of a KEY_PROBE check are fixed once a state of the plan exists");
-  if (p->max_missing_keys < 1 || p->max_missing_keys > TGX_KEY_PROBE_MAX_MISSING_KEYS)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_missing_keys must be 1 .. %d (%u)", spec_index,
-                (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
-  if (p->max_value_bytes < 1 || p->max_value_bytes > TGX_KEY_PROBE_MAX_VALUE_BYTES)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
-                (int)TGX_KEY_PROBE_MAX_VALUE_BYTES, p->max_value_bytes);
-  KeyProbeTask &t = plan->key_probes[slot];
-  if (t.set && !t.strings)
-    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
-                set_as(t), set_suffix(t));
-  t.params = tgx_key_probe_params{p->max_missing_keys, 0};
-  t.max_value_bytes = p->max_value_bytes;
-  t.strings = t.set = true;
-  return TGX_OK;
-} catch (...) {
-  return tgx::abi_exception(err);
-}
-
-namespace {
 // the task of a spec that spec_slot has accepted
 const KeyProbeTask &task_of(const tgx_plan *plan, size_t spec_index) {
   for (const KeyProbeTask &t : plan->key_probes)
@@ -833,6 +794,35 @@ const KeyProbeTask &task_of(const tgx_plan *plan, size_t spec_index) {
 }
 }  // namespace
 
+extern "C" tgx_status tgx_plan_set_key_probe(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                             tgx_error *err) try {
+  return plan_set_mode(plan, spec_index, kKpPlain, p, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_counted(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                                     tgx_error *err) try {
+  return plan_set_mode(plan, spec_index, kKpCounted, p, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
+  const tgx_key_probe_params own = {1, 0};
+  return plan_set_mode(plan, spec_index, kKpRows, &own, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec_index,
+                                                     const tgx_key_probe_strings_params *p, tgx_error *err) try {
+  const tgx_key_probe_params q = {p ? p->max_missing_keys : 0, 0};
+  return plan_set_mode(plan, spec_index, kKpStrings, p ? &q : nullptr, p ? p->max_value_bytes : 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
 extern "C" tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
                                                 tgx_key_probe_strings *out, tgx_error *err) try {
   bind_thread();
@@ -840,7 +830,7 @@ extern "C" tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state 
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
   const KeyProbeTask &t = task_of(plan, spec_index);
-  if (!t.strings)
+  if (t.mode != kKpStrings)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys "
                 "(tgx_plan_set_key_probe_strings)", spec_index);
   memset(out, 0, sizeof(*out));
@@ -859,7 +849,7 @@ extern "C" tgx_status tgx_key_probe_entries_bytes(const tgx_plan *plan, tgx_stat
   if (!n_entries || !n_bytes) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  if (!task_of(plan, spec_index).strings)
+  if (task_of(plan, spec_index).mode != kKpStrings)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys: its missing keys "
                 "are read with tgx_key_probe_entries", spec_index);
   int32_t is_bytes = 0;
@@ -924,10 +914,9 @@ extern "C" tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *s
   if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  for (const KeyProbeTask &t : plan->key_probes)
-    if ((size_t)t.spec_index == spec_index && !t.counted)
-      return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check is not counted (tgx_plan_set_key_probe_counted)",
-                  spec_index);
+  if (task_of(plan, spec_index).mode != kKpCounted)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check is not counted (tgx_plan_set_key_probe_counted)",
+                spec_index);
   memset(out, 0, sizeof(*out));
   out->pairs = h.pairs;
   // (rows seen are below 2^63; the sum is still held against the word)
@@ -948,7 +937,7 @@ extern "C" tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *st,
   if (!n_entries) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  if (task_of(plan, spec_index).strings)
+  if (task_of(plan, spec_index).mode == kKpStrings)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check probes string keys: its missing keys are read "
                 "with tgx_key_probe_entries_bytes", spec_index);
   uint64_t n_bytes = 0;

@@ -120,7 +120,8 @@ TGX_HIDDEN inline tgx_status side_plans_ready(const tgx_plan *plan, tgx_error *e
 // ---- what the kinds' updates share -----------------------------------------------------------------------------------
 constexpr int kSidePerLaunch = 8;  // tasks of one launch (grid.y)
 static_assert(kMaxJointPerLaunch == kSidePerLaunch && kMaxTemporalPerLaunch == kSidePerLaunch &&
-                  kMaxHistPerLaunch == kSidePerLaunch && kMaxValueRuleGroupsPerLaunch == kSidePerLaunch,
+                  kMaxHistPerLaunch == kSidePerLaunch && kMaxValueRuleGroupsPerLaunch == kSidePerLaunch &&
+                  kMaxKeyProbePerLaunch == kSidePerLaunch,
               "the kinds' launch descriptors hold kSidePerLaunch tasks");
 
 // the tasks that are `in_phase`, in launches of up to kSidePerLaunch: launch(slots, n)

@@ -45,6 +45,7 @@ struct CountsKind {
   static const std::vector<ValueCountsTask> &tasks(const tgx_plan *plan) { return plan->value_counts; }
   static size_t words(const ValueCountsTask &) { return kValueCountsWords; }
   static uint32_t bound(const ValueCountsTask &t) { return t.params.max_distinct; }
+  static uint32_t max_value_bytes(const ValueCountsTask &t) { return t.params.max_value_bytes; }
   static NoRange range_identity() { return NoRange(); }
   static CountsHost fresh(const ValueCountsTask &) { return CountsHost(); }
   static size_t shape(const CountsHost &) { return 0; }  // (integer against string values: KeyedCheck::merge_from)

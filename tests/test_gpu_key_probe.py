@@ -342,6 +342,77 @@ def test_two_specs_on_one_column_with_different_parent_sets():
     assert [read(st, i)["route"] for i in range(3)] == [ex.ROUTE_HASH, ex.ROUTE_BITMAP, ex.ROUTE_EMPTY]
 
 
+def test_every_mode_in_one_plan_with_a_route_that_spans_two_launches():
+    """nine plain specs on the bitmap route (a launch takes eight tasks: the ninth rides a second launch alone), a plain
+    one on the hash route, a counted one, one that gathers rows and one on string keys, in one plan over an Int64 and a
+    Utf8 column of 65 rows (a wave and a row), each probing spec with five keys of its own"""
+    import torch
+
+    import exact_join_coverage as exj
+    import exact_key_probe_strings as exs
+    import fp_reference as fpr
+
+    rng = np.random.default_rng(15)
+    n, key = 65, bytes(range(1, 17))
+    child = ints(rng.integers(-3, 40, n), mask=rng.random(n) >= 0.15)
+    words = ["k%d" % v for v in rng.integers(0, 12, n)]
+    strings = [None if rng.random() < 0.15 else w for w in words]
+    assert 0 < child.null_count < n and 0 < strings.count(None) < n
+    bitmaps = [np.arange(5) + 3 * j for j in range(9)]
+    spread = np.array([0, 7, 1_000_003, 2_000_006, 30])
+    counted = [(2, 3), (5, 1), (7, 2), (11, 4), (36, 1)]
+    parent_words = ["k1", "k4", "k5", "k9", "zz"]
+    assert all(ex.route_of(p) == ex.ROUTE_BITMAP for p in bitmaps) and ex.route_of(spread) == ex.ROUTE_HASH
+
+    T.init()
+    plan = T.Plan([spec(T.KEY_PROBE, 0) for _ in range(12)] + [spec(T.KEY_PROBE, 1)])
+    plan.set_fingerprint_key(key)
+    for i in range(10):
+        plan.set_key_probe(i, 100)
+    plan.set_key_probe_counted(10, 100)
+    plan.set_key_probe_rows(11)
+    plan.set_key_probe_strings(12, 100, 256)
+    st = T.State(plan)
+    st.profile_enable(True)
+    for i, keys in enumerate(bitmaps + [spread]):
+        set_parent(st, keys, i)
+    recs = to_device(np.array(counted, np.int64).view(np.uint64).reshape(-1))
+    st.key_probe_set_parent(10, recs.data_ptr(), len(counted))
+    fps = [fpr.fingerprint(key, w.encode()) for w in parent_words]
+    frecs = to_device(np.array([(fa, fb, 1, 0) for fa, fb in fps], np.uint64).reshape(-1))
+    st.key_probe_set_parent(12, frecs.data_ptr(), len(fps))
+    scol = T.Column.from_arrow(pa.array(strings, pa.string()))
+    validity, offsets, data = scol._keep[1:4]
+    st.update([column(child), T.Column(scol.c.type, n, validity=padded(validity), offsets=padded(offsets),
+                                       data=padded(data), mem=T.MEM_DEVICE)])
+
+    for i, keys in enumerate(bitmaps + [spread]):
+        assert read(st, i) == exact(child, keys, 100), i
+    values, mask = split(child)
+    want, want_pairs = exj.walk_np(values, mask, counted, 100)
+    assert read(st, 10) == want and st.key_probe_pairs(10) == want_pairs
+    assert want["route"] == exj.ROUTE_COUNT_HASH and want_pairs["pairs"] > want["matched"] > 0
+
+    ptr, count = st.key_probe_rows(11)
+    assert count == n - child.null_count
+
+    class Records:
+        __cuda_array_interface__ = {"shape": (count * 16,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+    gathered = torch.as_tensor(Records(), device="cuda").clone().cpu().numpy().view(np.int64).reshape(count, 2)
+    assert sorted(gathered[:, 0].tolist()) == sorted(values[mask].tolist()) and set(gathered[:, 1].tolist()) == {1}
+
+    want = exs.walk(strings, parent_words, 256, 100)
+    del want["within_bound"]
+    digest = sum(ex.mix64(ex.mix64(fa ^ ex.DIGEST_SALT) ^ fb) for fa, fb in set(fps)) & ex.M64
+    want.update(max_value_bytes=256, parent_digest=digest, route=5)
+    summary, entries = st.key_probe_strings(12)
+    assert dict(summary, entries=entries) == want and list(entries) == list(want["entries"])
+    assert want["matched"] > 0 and want["missing_keys"] > 0
+    # the bitmap route's nine tasks in two launches, then one launch each for the hash route, the counted route and the strings
+    assert st.profile_get("key_probe")["launches"] == 5 and st.profile_get("key_probe_rows")["launches"] == 1
+
+
 # ---- batching and the ways a state travels ------------------------------------------------------------------------------------
 N_BIG = 200_000
 
