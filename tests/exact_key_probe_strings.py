@@ -2,7 +2,9 @@
 ForeignKeyConstraint derives from it (TG/constraints/foreign_key.rs:152-176, 334-410): a plain walk over Python `bytes`
 with a set and a dict.  Nothing here looks at the library, and no fingerprint is involved: the walk compares the values
 themselves, which is what the library's counts are exact over unless two values share all 128 bits of a keyed
-fingerprint.
+fingerprint.  (The one exception is `parent_digest`, the set's identity: that is DEFINED over fingerprints, and is
+restated here with tests/fp_reference.py.)  `walk_np` is a numpy twin of the walk over a column given as (codes, words,
+mask), the form tests/fuzz_plans.py keeps its string columns in.
 
 A table side is a list whose items are `bytes` (or str, taken as UTF-8) or None for a NULL row.  The SQL is a LEFT JOIN on
 child.c = parent.p filtered to parent.p IS NULL: a NULL child row matches nothing (it is a violation unless allow_nulls)
@@ -41,6 +43,36 @@ def walk(child, parent, max_value_bytes=256, max_missing_keys=10000):
             "missing_rows": counted + long_rows, "counted": counted, "overflow_rows": 0, "long_rows": long_rows,
             "missing_keys": len(entries), "parent_keys": len(keys), "entries": entries,
             "within_bound": len(entries) <= max_missing_keys}
+
+
+def walk_np(codes, words, mask, parent, max_value_bytes=256, max_missing_keys=10000):
+    """the walk's state for the column whose row i holds words[codes[i]] (bytes; the words are distinct) where mask[i],
+    a NULL otherwise; `parent` as for walk"""
+    import numpy as np
+
+    codes, mask = np.asarray(codes, np.int64), np.asarray(mask, bool)
+    keys = set(v for v in as_bytes(parent) if v is not None)
+    per_word = np.bincount(codes[mask], minlength=len(words))
+    in_set = np.array([w in keys for w in words] + [False], bool)[:-1]
+    too_long = np.array([len(w) > max_value_bytes for w in words] + [False], bool)[:-1] & ~in_set
+    kept = ~in_set & ~too_long & (per_word > 0)
+    entries = {words[k]: int(per_word[k]) for k in sorted(np.flatnonzero(kept).tolist(), key=words.__getitem__)}
+    counted, long_rows = int(per_word[kept].sum()), int(per_word[too_long].sum())
+    non_null = int(mask.sum())
+    return {"seen": len(codes), "non_null": non_null, "null_rows": len(codes) - non_null,
+            "matched": int(per_word[in_set].sum()), "missing_rows": counted + long_rows, "counted": counted,
+            "overflow_rows": 0, "long_rows": long_rows, "missing_keys": len(entries), "parent_keys": len(keys),
+            "entries": entries, "within_bound": len(entries) <= max_missing_keys}
+
+
+def parent_digest(key, parent):
+    """the identity of a set of string keys under the 16-byte fingerprint key `key` (include/tgx.h): the wrapping sum
+    over the DISTINCT fingerprints (fa, fb) of mix64(mix64(fa ^ salt) ^ fb)"""
+    import exact_key_probe as kp
+    import fp_reference as fpr
+
+    fps = set(fpr.fingerprint(key, v) for v in as_bytes(parent) if v is not None)
+    return sum(kp.mix64(kp.mix64(fa ^ kp.DIGEST_SALT) ^ fb) for fa, fb in fps) & kp.M64
 
 
 def verdict(state, child, parent, allow_nulls=False, max_violations_reported=100, examples=True):

@@ -56,6 +56,50 @@ def test_the_walk_and_its_twin_agree(seed, max_value_bytes):
     assert want["missing_rows"] == want["counted"] + want["overflow_rows"] + want["long_rows"]
 
 
+def as_codes(child):
+    """(codes, words, mask) of a list of bytes / None: the words in order of first appearance"""
+    words, at, codes = [], {}, []
+    for v in ex.as_bytes(child):
+        if v is not None and v not in at:
+            at[v] = len(words)
+            words.append(v)
+        codes.append(0 if v is None else at[v])
+    return np.array(codes, np.int64), words or [b"unused"], np.array([v is not None for v in child], bool)
+
+
+@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("max_value_bytes", [1, 16, 256])
+def test_the_walk_and_its_numpy_twin_agree_on_a_seeded_table_with_long_rows(seed, max_value_bytes):
+    rng = np.random.default_rng(100 + seed)
+    child = random_side(rng, 400, b"ab", [0.0, 0.5, 1.0][seed % 3])
+    parent = random_side(rng, 60, b"ab", 0.2) + [v for v in child if v is not None][:5]
+    want = ex.walk(child, parent, max_value_bytes)
+    got = ex.walk_np(*as_codes(child), parent, max_value_bytes)
+    assert got == want and list(got["entries"]) == list(want["entries"])
+    assert seed % 3 == 2 or max_value_bytes == 256 or want["long_rows"] > 0
+    # a word no row holds (or only NULL rows point at) is no entry
+    codes, words, mask = as_codes(child)
+    assert ex.walk_np(codes, words + [b"never"], mask, parent, max_value_bytes) == want
+
+
+@pytest.mark.parametrize("case", GOLDEN["cases"], ids=[c["name"] for c in GOLDEN["cases"]])
+def test_the_numpy_twin_on_the_golden_cases(case):
+    got, want = ex.walk_np(*as_codes(case["child"]), case["parent"]), ex.walk(case["child"], case["parent"])
+    assert got == want and list(got["entries"]) == list(want["entries"])
+
+
+def test_the_parent_digest_is_over_distinct_fingerprints():
+    import exact_key_probe as kp
+    import fp_reference as fpr
+
+    key = bytes(range(1, 17))
+    assert ex.parent_digest(key, []) == ex.parent_digest(key, [None]) == 0
+    fa, fb = fpr.fingerprint(key, b"a")
+    assert ex.parent_digest(key, ["a", b"a", None]) == kp.mix64(kp.mix64(fa ^ kp.DIGEST_SALT) ^ fb)
+    assert ex.parent_digest(key, ["a", "b"]) == (ex.parent_digest(key, ["a"]) + ex.parent_digest(key, ["b"])) & kp.M64
+    assert ex.parent_digest(bytes(16), ["a"]) != ex.parent_digest(key, ["a"])
+
+
 def test_the_order_is_bytewise_and_a_long_value_in_the_parent_is_matched():
     long_value = b"x" * 300
     s = ex.walk([b"b", b"\xc3\xa9", b"a", b"", b"ab", long_value, long_value + b"y", None], [long_value], 256)

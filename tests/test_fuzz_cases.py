@@ -11,6 +11,11 @@ draws a plan.
   own, leaves all of that as it is too; the four committed sets together meet a census of its own, keep the share of
   tasks that references alone cannot pin (a table that may overflow, a float sum that may) to a quarter, and the
   dimension is drawn only where its rules allow;
+- the KEY_PROBE dimension, drawn last of all from a stream of its own (what is random when a case runs from a second
+  one: run_device_inner draws from the case's stream what it drew before), leaves all of that as it is again; the five
+  committed sets together meet a census of its own for each of its plain, counted and strings modes and for rows specs,
+  the share of tasks whose exact number of missing keys exceeds their bound stays within a quarter per mode, and the
+  dimension is drawn only where its rules allow, for between a third and two thirds of the eligible cases;
 - check_one passes on the references' own answers and fails on each of a list of single perturbations."""
 import hashlib
 import json
@@ -46,7 +51,7 @@ def case_digest(case):
             d += [_h(extra[0]), bool(extra[1]), extra[2], _h(np.frombuffer("\0".join(extra[3]).encode() or b"\0", np.uint8)),
                   _h(extra[4])]
         cols.append(d)
-    old = [k for k, e in enumerate(case.expect) if e[0] not in NEW_KINDS + ("time_gap",) + case.RULES_AND_COUNTS]
+    old = [k for k, e in enumerate(case.expect) if e[0] not in NEW_KINDS + ("time_gap", "key_probe") + case.RULES_AND_COUNTS]
     specs = []
     for k in old:
         s = case.specs[k]
@@ -141,15 +146,16 @@ _CASES = {}
 
 
 def committed_cases(third=False):
-    """the cases of the first two committed sets (built once per session), of the third (True) or of the fourth ("fourth")"""
+    """the cases of the first two committed sets (built once per session), of the third (True), of the fourth ("fourth")
+    or of the fifth ("fifth")"""
     from fuzz_plans import Case
     from test_gpu_fuzz import SECOND_MAX_ROWS, SECOND_SEEDS, THIRD_SEEDS
 
     if third not in _CASES:
-        if third == "fourth":
-            from test_gpu_fuzz import FOURTH_SEEDS
+        if third in ("fourth", "fifth"):
+            from test_gpu_fuzz import FIFTH_SEEDS, FOURTH_SEEDS
 
-            _CASES[third] = [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in FOURTH_SEEDS]
+            _CASES[third] = [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in (FOURTH_SEEDS if third == "fourth" else FIFTH_SEEDS)]
         elif third:
             _CASES[third] = [Case(seed, max_rows=SECOND_MAX_ROWS) for seed in THIRD_SEEDS]
         else:
@@ -519,6 +525,187 @@ def test_the_rules_and_counts_dimension_is_drawn_where_it_can_be():
     assert 1 / 3 <= drawn / eligible <= 2 / 3, (drawn, eligible)
 
 
+# ---- the KEY_PROBE census: the five committed sets together ----------------------------------------------------------------
+KP_PROBING = ("plain", "counted", "strings")
+# (no NUMERIC_STATS check reads a string column: a strings spec shares its column with LENGTH or REGEX_MATCH instead)
+KP_SHARED = {"a DISTINCT or tuple check": ("distinct", "tuple"), "NUMERIC_STATS": ("stats",),
+             "LENGTH or REGEX_MATCH": ("length", "regex"),
+             "one of the five counting kinds": RC_KINDS, "another KEY_PROBE spec": ("key_probe",)}
+KP_NOT_SHARED = {"plain": "LENGTH or REGEX_MATCH", "counted": "LENGTH or REGEX_MATCH", "strings": "NUMERIC_STATS"}
+KP_ROUTES = {"plain": (0, 1, 2), "counted": (0, 3, 4), "strings": (0, 5)}
+KP_SOURCES = {"plain": "ab", "counted": "abc", "strings": "ab"}
+KP_LIMIT = {"plain": 128, "counted": 4}  # exact_key_probe.route_of, exact_join_coverage.route_of
+
+
+def kp_specs(case):
+    return [e for e in case.expect if e[0] == "key_probe"]
+
+
+def kp_want(case, e):
+    """(the reference's state, the route it gives the set) of a probing spec"""
+    want = case.reference(case.kp_reference_key(e))
+    return want, want["route"] if e[2] != "strings" else 5 if want["parent_keys"] else 0
+
+
+def kp_tasks(case):
+    """per probing mode [may the task be left to invariants: d > bound]"""
+    tasks = {m: [] for m in KP_PROBING}
+    for e in kp_specs(case):
+        if e[2] != "rows":
+            tasks[e[2]].append(kp_want(case, e)[0]["missing_keys"] > e[4])
+    return tasks
+
+
+def kp_cells(case):
+    """the cells of the census this case fills"""
+    cells = set()
+    specs = kp_specs(case)
+    for e in specs:
+        _, ci, mode, parent, bound, mvb = e
+        kind, _, _, mask, extra = case.cols[ci]
+        if mode == "rows":
+            cells |= {"rows seq=%s" % case.seq, "rows batching=%s" % case.mode}
+            if mask.any() and not mask.all():
+                cells.add("rows a column with NULLs")
+            continue
+        want, route = kp_want(case, e)
+        d = want["missing_keys"]
+        mine = {"after=%s" % case.after, "buffers=%s" % case.device, "batching=%s" % case.mode,
+                "source (%s)" % parent.source, "route %d" % route}
+        if case.seq != "plain":
+            mine.add("seq=%s" % case.seq)
+        if case.retain and case.device != "device":
+            mine.add("retained")
+        if case.n == 0:
+            mine.add("without rows")
+        for name, kinds in KP_SHARED.items():
+            if any(o is not e and o[0] in kinds and ci in case.columns_of_expect(o) for o in case.expect):
+                mine.add("a column shared with %s" % name)
+        if bound == d:
+            mine.add("bound=d")
+        if bound == d + 1:
+            mine.add("bound=d+1")
+        if d > bound:
+            mine.add("a bound that overflows")
+        if want["non_null"] and not want["missing_rows"]:
+            mine.add("no key missing")
+        if want["non_null"] and not want["matched"]:
+            mine.add("every key missing")
+        if case.n > 0 and not want["non_null"]:
+            mine.add("every child row NULL")
+        if case.kp_refusal_step():
+            mine.add("a mid-table blob with the refusal step")
+        if case.after == "merge" and len(case.cuts) == 2:  # (one batch: every state but the first stays empty)
+            mine.add("a merged state that saw no batch")
+        alike = [o for o in specs if o[1:3] == e[1:3]]
+        if len(alike) >= 9 and len({kp_want(case, o)[1] for o in alike}) == 1:
+            mine.add("nine specs on one column and route")
+        if mode == "strings":
+            mine.add("layout %s" % (extra[2] if extra[2] != "plain" else "LargeUtf8" if extra[1] else "plain"))
+            if want["long_rows"]:
+                mine.add("long rows")
+            live = parent.values[parent.valid]
+            if parent.source == "a" and len(np.unique(live)) < len(live):
+                mine.add("duplicate records")
+            if parent.near:
+                mine.add("records that share one fingerprint word with a missing key")
+        else:
+            keys, counts = parent.records()
+            if parent.on_threshold(KP_LIMIT[mode]):
+                mine.add("a set on a route threshold")
+            if (keys == -1).any():
+                mine.add("the -1 key in the set")
+            if (case.kp_child(ci)[0][mask] == -1).any():
+                mine.add("the -1 key among the child's values")
+            if parent.duplicates():
+                mine.add("duplicate records")
+            if mode == "counted" and len(counts) and int(counts.max()) >= 1 << 40:
+                mine.add("a count of 2^40")
+            mine.add("child %s" % ("a narrow presentation" if case.present[ci] is not None else kind))
+            if parent.width != case.kp_width(ci):
+                mine.add("a parent from a column of another width")
+            if any(o[3] is parent and {o[2], mode} == {"plain", "counted"} for o in specs if o is not e):
+                cells.add("a plain and a counted spec that agree")
+        cells |= {"%s %s" % (mode, cell) for cell in mine}
+    return cells
+
+
+KP_REQUIRED = (["%s %s" % (m, c) for m in KP_PROBING for c in (
+    ["after=%s" % a for a in AFTERS] + ["seq=%s" % q for q in SEQS] + ["buffers=%s" % d for d in DEVICES] + ["retained"]
+    + ["batching=%s" % b for b in RC_MODES] + ["without rows"] + ["a column shared with %s" % name for name in KP_SHARED if name != KP_NOT_SHARED[m]]
+    + ["source (%s)" % x for x in KP_SOURCES[m]] + ["route %d" % x for x in KP_ROUTES[m]]
+    + ["bound=d", "bound=d+1", "a bound that overflows", "no key missing", "every key missing", "every child row NULL",
+       "duplicate records", "a mid-table blob with the refusal step", "a merged state that saw no batch",
+       "nine specs on one column and route"])]
+    + ["%s %s" % (m, c) for m in ("plain", "counted") for c in (
+        ["a set on a route threshold", "the -1 key in the set", "the -1 key among the child's values",
+         "a parent from a column of another width"] + ["child %s" % k for k in ("i", "i32", "a narrow presentation")])]
+    + ["counted a count of 2^40", "strings long rows", "strings records that share one fingerprint word with a missing key", "a plain and a counted spec that agree"]
+    + ["strings layout %s" % x for x in ("plain", "LargeUtf8", "view", "dict")]
+    + ["rows seq=%s" % q for q in ("plain",) + SEQS] + ["rows batching=%s" % b for b in RC_MODES] + ["rows a column with NULLs"])
+ALL_SETS = (False, True, "fourth", "fifth")
+
+
+def test_key_probe_census_of_the_five_committed_sets():
+    from test_gpu_fuzz import FIFTH_SEEDS, FOURTH_SEEDS, SECOND_SEEDS, THIRD_SEEDS
+
+    assert len(FIFTH_SEEDS) <= 48 and len(set(FIFTH_SEEDS)) == len(FIFTH_SEEDS)
+    assert not set(FIFTH_SEEDS) & (set(FIRST_SEEDS) | set(SECOND_SEEDS) | set(THIRD_SEEDS) | set(FOURTH_SEEDS))
+    counts, tasks = {}, {}
+    for which in ALL_SETS:
+        for case in committed_cases(which):
+            cells = kp_cells(case)
+            if which == "fifth":  # every seed of the fifth set carries the kind
+                assert cells, case.seed
+            for cell in cells:
+                counts[cell] = counts.get(cell, 0) + 1
+            for name, flags in kp_tasks(case).items():
+                tasks.setdefault(name, []).extend(flags)
+    for cell in sorted(counts):
+        print("%4d  %s" % (counts[cell], cell))
+    missing = [cell for cell in KP_REQUIRED if not counts.get(cell)]
+    assert not missing, missing
+    # a condition, not a measurement: the references alone pin three tasks in four of every probing mode (d <= bound: full
+    # equality is required) -- from the exact number of missing keys d, on the CPU
+    for name, flags in sorted(tasks.items()):
+        print("%s: %d tasks, %d with more missing keys than their bound" % (name, len(flags), sum(flags)))
+        assert flags and 4 * sum(flags) <= len(flags), (name, sum(flags), len(flags))
+
+
+def test_the_key_probe_dimension_is_drawn_where_it_can_be():
+    """eligibility is a condition: only cases of at most NEW_KINDS_MAX_ROWS rows; integer children Int64, Int32 or a narrow
+    presentation, never UInt64 or Boolean; string children in a strings spec only; a rows spec only in a case that is
+    simply finalized; the bounds the library takes -- and between a third and two thirds of the eligible cases"""
+    import term_amd as T
+    from fuzz_plans import ParentSet
+
+    eligible = drawn = 0
+    for which in ALL_SETS:
+        for case in committed_cases(which):
+            mine = kp_specs(case)
+            kinds = [c[0] for c in case.cols]
+            ints = [ci for ci, k in enumerate(kinds) if k in ("i", "i32") and not case.unsupported_as_key(ci)]
+            can = case.n <= case.NEW_KINDS_MAX_ROWS and (bool(ints) or "s" in kinds)
+            assert can or not mine, case.seed
+            assert len(mine) in (0, 1, 2, 3, 9), (case.seed, len(mine))
+            for _, ci, mode, parent, bound, mvb in mine:
+                assert mode in case.KP_MODES and (ci in ints if mode != "strings" else kinds[ci] == "s"), (case.seed, ci, mode)
+                if mode == "rows":
+                    assert case.after == "finalize" and parent is None, case.seed
+                    continue
+                assert isinstance(parent, ParentSet) and parent.source in KP_SOURCES[mode], (case.seed, mode, parent)
+                assert 1 <= bound <= T.KEY_PROBE_MAX_MISSING_KEYS == case.BOUND_LIMIT, (case.seed, bound)
+                if mode == "strings":
+                    assert 1 <= mvb <= T.KEY_PROBE_MAX_VALUE_BYTES, (case.seed, mvb)
+                else:  # no draw lets rows x the largest multiplicity come near 2^64
+                    assert case.n * max(1, parent.max_count()) < 1 << 62, case.seed
+            if which is False:
+                eligible += can
+                drawn += bool(mine)
+    print("KEY_PROBE is drawn for %d of the %d eligible cases of the first two sets" % (drawn, eligible))
+    assert 1 / 3 <= drawn / eligible <= 2 / 3, (drawn, eligible)
+
+
 # ---- the comparisons fail when they should ----------------------------------------------------------------------------
 class FakeResult:
     def __init__(self, total=0, non_null=0, matches=0, distinct=0, sum_i=0, sum_f=0.0, has_value=0):
@@ -534,6 +721,20 @@ class FakeState:
         self.time_gap = {}
         # VALUE_RULE: the four counters; the counting kinds: (summary, entries), as term_amd.State's readers give them
         self.rule, self.vc, self.pc, self.pr, self.gc, self.gs = {}, {}, {}, {}, {}, {}
+        # KEY_PROBE: (summary, entries) of a plain, counted or strings spec (a rows spec: its three counters, no entry),
+        # the pairs of a counted one, the {key, 1} records of a rows one as a host array
+        self.kp, self.kp_pairs, self.kp_rows = {}, {}, {}
+
+    def key_probe(self, si):
+        return dict(self.kp[si][0]), dict(self.kp[si][1])
+
+    key_probe_strings = key_probe
+
+    def key_probe_pairs(self, si):
+        return dict(self.kp_pairs[si])
+
+    def key_probe_rows(self, si):
+        return self.kp_rows[si].copy(), len(self.kp_rows[si])
 
     def value_rule_counts(self, si):
         return tuple(self.rule[si])
@@ -583,7 +784,18 @@ S_WORDS = ["a", "bb", "", "long word"]
 SMALL_MAX_BYTES, SMALL_BOUND, PAIR_BINS = 4, 10000, 2
 HIST, JOINT, TEMPORAL, TIME_GAP = 0, 1, 2, 3  # spec indices
 RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS_F, GROUP_SUMS_I = 4, 5, 6, 7, 8, 9
-N_SPECS = 10
+KP_PLAIN, KP_COUNTED, KP_STRINGS, KP_ROWS = 10, 11, 12, 13
+N_SPECS = 14
+# KEY_PROBE on the small table.  Plain, Y against hand-made records with a duplicate and a far key (4 records over a range
+# of 1000 > 128 * 4: the hash route): 1, 1, 5, 5 match; 0, 2, 3, 4, 6, 8, 9 are missing once each.  Counted, Z against
+# multiplicities: 5 (three rows) twice and 0 (three rows) once are 9 pairs of 6 matched rows; 4 is missing twice, 3 once.
+# Strings, S under a bound of KP_MAX_BYTES = 2 bytes: "a" matches; "bb" (exactly 2 bytes) and "" are kept, "long word"
+# is two long rows.  Rows: Z's nine non-NULL keys.
+KP_PLAIN_RECORDS = [1, 5, 5, 1000]
+KP_COUNTED_RECORDS = [(5, 2), (0, 1), (7, 3)]
+KP_STRING_PARENT = ["a", "zz", "a"]
+KP_MAX_BYTES = 2
+KP_KEY = bytes(range(1, 17))
 TIME_GAP_MAX = 2  # Y grouped by Z has the gaps 3, 2 | 7, 1 | 2 | 1, 3 (the NULL group): three above, four not
 
 
@@ -592,9 +804,10 @@ def small_case(phase, edges="shifted", moved=True):
     the generator"""
     import exact_value_rule as EV
     import term_amd as T
-    from fuzz_plans import Case
+    from fuzz_plans import Case, ParentSet
 
     c = Case.__new__(Case)
+    c.host_only, c.kp_set_held, c.kp_key = False, True, KP_KEY
     c.seed, c.n, c.specs, c.present, c.phase, c.pass_two, c._cache = -1, len(X), [None] * N_SPECS, [None] * 4, 1, {}, {}
     c.tables = 1
     c.cols = []
@@ -611,6 +824,14 @@ def small_case(phase, edges="shifted", moved=True):
                 ("pair_counts", 3, 0, SMALL_BOUND, SMALL_MAX_BYTES, PAIR_BINS, moved),
                 ("group_counts", 0, 3, SMALL_BOUND, SMALL_MAX_BYTES), ("group_sums", 0, 3, SMALL_BOUND, SMALL_MAX_BYTES),
                 ("group_sums", 1, 3, SMALL_BOUND, SMALL_MAX_BYTES)]
+    ones = np.ones(len(KP_PLAIN_RECORDS), bool)
+    c.expect += [
+        ("key_probe", 1, "plain", ParentSet("a", KP_PLAIN_RECORDS, ones, ones.astype(np.uint64), "by hand"), SMALL_BOUND, 0),
+        ("key_probe", 2, "counted", ParentSet("a", [k for k, _ in KP_COUNTED_RECORDS], ones[:3],
+                                              np.array([n for _, n in KP_COUNTED_RECORDS], np.uint64), "by hand"), SMALL_BOUND, 0),
+        ("key_probe", 3, "strings", ParentSet("b", [0, 1, 0], ones[:3], None, "by hand", words=KP_STRING_PARENT[:2],
+                                              layout=("plain", False)), SMALL_BOUND, KP_MAX_BYTES),
+        ("key_probe", 2, "rows", None, 0, 0)]
     if phase == 2:
         c.enter_pass_two()
     return c
@@ -626,6 +847,7 @@ def reference_answer(case):
 
     res, st = [FakeResult() for _ in range(N_SPECS)], FakeState()
     rules_and_counts_answer(case, res, st)
+    key_probe_answer(res, st)
     r = EH.value_range(X)
     res[HIST] = FakeResult(r["total"], r["n"] + r["non_finite"])
     st.hist_range[HIST] = dict(total=r["total"], nulls=r["nulls"], non_finite=r["non_finite"], n=r["n"], min=r["min"],
@@ -712,6 +934,44 @@ def rules_and_counts_answer(case, res, st):
         summary = dict(seen=w["seen"], groups=w["groups"], is_float=w["is_float"], counted=counted,
                        null_group=w["null_group"][:3], overflow=w["overflow"][:3], long_rows=w["long_rows"][:3])
         set_group_sums(res, st, si, summary, entries, values)
+
+
+def set_key_probe(res, st, si, summary, entries):
+    """a device that holds `summary` and `entries` for a KEY_PROBE spec, consistently through its getter and tgx_finalize"""
+    st.kp[si] = (summary, entries)
+    res[si] = FakeResult(summary["seen"], summary["non_null"], summary["matched"], summary["missing_keys"])
+
+
+def key_probe_answer(res, st):
+    """KEY_PROBE in its four modes, from the plain walks (the tester compares with their numpy twins)"""
+    import exact_join_coverage as EJC
+    import exact_key_probe as EKP
+    import exact_key_probe_strings as EKS
+
+    def side(values):
+        return [0 if v is None else v for v in values], [v is not None for v in values]
+
+    w = EKP.walk(*side(Y), KP_PLAIN_RECORDS, None, SMALL_BOUND, n_records=len(KP_PLAIN_RECORDS))
+    assert (w["matched"], w["missing_keys"], w["parent_keys"], w["route"]) == (4, 7, 3, EKP.ROUTE_HASH)
+    assert EKP.route_of(KP_PLAIN_RECORDS[:3]) == EKP.ROUTE_BITMAP  # (the far key alone makes it a hash table)
+    entries = w.pop("entries")
+    del w["within_bound"]
+    set_key_probe(res, st, KP_PLAIN, w, entries)
+    w, pairs = EJC.walk(*side(Z), KP_COUNTED_RECORDS, SMALL_BOUND)
+    assert (w["matched"], pairs["pairs"], pairs["max_count"], w["entries"]) == (6, 9, 3, {3: 1, 4: 2})
+    entries = w.pop("entries")
+    set_key_probe(res, st, KP_COUNTED, w, entries)
+    st.kp_pairs[KP_COUNTED] = pairs
+    w = EKS.walk(S, KP_STRING_PARENT, KP_MAX_BYTES, SMALL_BOUND)
+    assert (w["matched"], w["long_rows"], w["entries"]) == (4, 2, {b"": 1, b"bb": 3})
+    entries = w.pop("entries")
+    del w["within_bound"]
+    w.update(max_value_bytes=KP_MAX_BYTES, parent_digest=EKS.parent_digest(KP_KEY, KP_STRING_PARENT), route=5)
+    set_key_probe(res, st, KP_STRINGS, w, entries)
+    z, valid = side(Z)
+    blank = dict.fromkeys(st.kp[KP_PLAIN][0], 0)
+    set_key_probe(res, st, KP_ROWS, dict(blank, seen=len(Z), non_null=sum(valid), null_rows=len(Z) - sum(valid)), {})
+    st.kp_rows[KP_ROWS] = np.array([[v, 1] for v, m in zip(z, valid) if m], np.int64).view(np.uint64)[::-1]
 
 
 def set_rule(res, st, counts):
@@ -1085,6 +1345,108 @@ def _null_group_value_lost(summary, entries):
     summary["null_group"] = (rows, non_null - 1, total)
 
 
+# ---- KEY_PROBE: one perturbation at a time ---------------------------------------------------------------------------------
+def _key_probe(si, what, change):
+    """`change` edits (summary, entries) of spec si in place, may return the entries in a new order; tgx_finalize follows"""
+    def perturb(res, st):
+        summary, entries = dict(st.kp[si][0]), dict(st.kp[si][1])
+        before = (dict(summary), list(entries.items()))
+        entries = change(summary, entries) or entries
+        assert (summary, list(entries.items())) != before, what
+        set_key_probe(res, st, si, summary, entries)
+    perturb.__qualname__ = "key_probe: " + what
+    return perturb
+
+
+def _shift(summary, **by):
+    for k, v in by.items():
+        summary[k] += v
+
+
+def _kp_matched_row_missing(summary, entries):
+    entries[3] += 1
+    _shift(summary, matched=-1, missing_rows=+1, counted=+1)
+
+
+def _kp_null_row_non_null(summary, entries):
+    entries[3] += 1
+    _shift(summary, null_rows=-1, non_null=+1, missing_rows=+1, counted=+1)
+
+
+def _kp_count_to_the_neighbour(summary, entries):
+    assert entries == {3: 1, 4: 2}
+    entries.update({3: 2, 4: 1})
+
+
+def _kp_out_of_order(summary, entries):
+    keys = list(entries)
+    return {k: entries[k] for k in [keys[1], keys[0]] + keys[2:]}
+
+
+def _kp_entry_for_a_key_of_the_set(summary, entries):
+    entries[5] = 1
+    _shift(summary, matched=-1, missing_rows=+1, counted=+1, missing_keys=+1)
+    return dict(sorted(entries.items()))
+
+
+def _kp_field(name, by=None, to=None):
+    def change(summary, entries):
+        summary[name] = to if to is not None else summary[name] + by
+    return change
+
+
+def _kp_long_row_kept(summary, entries):
+    entries[b"long word"] = 2
+    _shift(summary, long_rows=-2, counted=+2, missing_keys=+1)
+    return dict(sorted(entries.items()))
+
+
+def _kp_exactly_max_value_bytes_is_long(summary, entries):
+    assert len(b"bb") == KP_MAX_BYTES
+    rows = entries.pop(b"bb")
+    _shift(summary, long_rows=+rows, counted=-rows, missing_keys=-1)
+
+
+def _kp_pairs(what, **fields):
+    def perturb(res, st):
+        assert all(st.kp_pairs[KP_COUNTED][k] != v for k, v in fields.items())
+        st.kp_pairs[KP_COUNTED] = dict(st.kp_pairs[KP_COUNTED], **fields)
+    perturb.__qualname__ = "key_probe: " + what
+    return perturb
+
+
+def _kp_rows_lost_a_record(res, st):
+    st.kp_rows[KP_ROWS] = st.kp_rows[KP_ROWS][1:]
+
+
+def _kp_rows_kept_a_null_row(res, st):
+    st.kp_rows[KP_ROWS] = np.concatenate([st.kp_rows[KP_ROWS], np.array([[0, 1]], np.uint64)])
+
+
+def _kp_finalize_alone(res, st):
+    res[KP_PLAIN].matches += 1  # (tgx_finalize disagreeing with tgx_key_probe_get)
+
+
+KP_PERTURBATIONS = [
+    _key_probe(KP_PLAIN, "a matched row counted as missing, the identities kept", _kp_matched_row_missing),
+    _key_probe(KP_PLAIN, "a NULL row counted as non-NULL", _kp_null_row_non_null),
+    _key_probe(KP_COUNTED, "one entry's count moved to the neighbouring key", _kp_count_to_the_neighbour),
+    _key_probe(KP_PLAIN, "two entries out of order", _kp_out_of_order),
+    _key_probe(KP_STRINGS, "two entries out of order (bytes)", _kp_out_of_order),
+    _key_probe(KP_PLAIN, "an entry for a key that is in the set", _kp_entry_for_a_key_of_the_set),
+    _key_probe(KP_PLAIN, "parent_digest off by one", _kp_field("parent_digest", by=1)),
+    _key_probe(KP_STRINGS, "parent_digest off by one (strings)", _kp_field("parent_digest", by=1)),
+    _key_probe(KP_PLAIN, "parent_keys counting a duplicate record twice", _kp_field("parent_keys", to=len(KP_PLAIN_RECORDS))),
+    _key_probe(KP_PLAIN, "route 1 where the rule gives 2", _kp_field("route", to=1)),
+    _kp_pairs("pairs equal to matched where a multiplicity is 2", pairs=6, join_rows=6 + 3 + 3),
+    _kp_pairs("max_count too small", max_count=2),
+    _key_probe(KP_STRINGS, "a long row kept as an entry", _kp_long_row_kept),
+    _key_probe(KP_STRINGS, "a missing key of exactly max_value_bytes bytes counted as a long row", _kp_exactly_max_value_bytes_is_long),
+    _kp_rows_lost_a_record, _kp_rows_kept_a_null_row, _kp_finalize_alone]
+for _f in KP_PERTURBATIONS[-3:]:
+    _f.__qualname__ = "key_probe: " + _f.__name__[4:].replace("_", " ")
+
+
 PERTURBATIONS = [(1, _time_gap(f)) for f in (
     violations_up, violations_down_matches_consistent, largest_gap_up, a_partition_split_in_two, a_null_timestamp_retained,
     a_row_not_seen, null_group_split_row_by_row, the_ungrouped_answer)] + [(1, _time_gap_finalize_alone)]
@@ -1104,6 +1466,9 @@ PERTURBATIONS += [(2, _pair_cell_transposed), (1, _pair_range_next_double("min")
                   (1, _group_sum(GROUP_SUMS_I, _is_float_flipped, "is_float flipped (integers)")),
                   (1, _group_sum(GROUP_SUMS_F, _a_nan_group_that_is_finite, "a finite sum for a group with a NaN")),
                   (1, _group_sum(GROUP_SUMS_F, _null_group_value_lost, "a value of the NULL group not counted"))]
+
+
+PERTURBATIONS += [(1, f) for f in KP_PERTURBATIONS]
 
 
 def test_check_one_fails_on_every_single_perturbation():

@@ -91,7 +91,9 @@ def test_simulated_ranks_match_one_state(dense, world, device_buffers):
     assert (want[-1].distinct, want[-1].groups_once) == (d.distinct, d.groups_once)
 
 
-def _run_ranks(world, plan, shards_of, device_buffers=True, steps=1):
+def _run_ranks(world, plan, shards_of, device_buffers=True, steps=1, prepare=None):
+    """prepare(state), if given, is called on every rank's fresh state before its first batch (a KEY_PROBE spec's parent
+    set belongs to a state: every rank sets its own copy)"""
     import torch
 
     group = ThreadGroup(world)
@@ -101,6 +103,8 @@ def _run_ranks(world, plan, shards_of, device_buffers=True, steps=1):
         try:
             torch.cuda.set_device(0)
             st = T.State(plan)
+            if prepare is not None:
+                prepare(st)
             comm = thread_comm(group, rank, device_buffers=device_buffers)
             shard = shards_of(rank)
             for _ in range(steps):

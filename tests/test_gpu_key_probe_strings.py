@@ -109,8 +109,7 @@ def set_exported(st, values, i=0, key=KEY, exact=False, layout=pa.string()):
 
 
 def digest_of(values, key=KEY):
-    fps = set(fpr.fingerprint(key, v) for v in ex.as_bytes(values) if v is not None)
-    return sum(exk.mix64(exk.mix64(fa ^ SALT) ^ fb) for fa, fb in fps) & M64
+    return ex.parent_digest(key, values)
 
 
 def plan_of(bounds=((10000, 256),), columns=None, extra=(), key=KEY):
