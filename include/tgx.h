@@ -399,7 +399,9 @@ typedef enum tgx_check_kind {
    * Two further modes of a spec, each with a plan call of its own: COUNTED (tgx_plan_set_key_probe_counted: the set keeps
    * the parent's multiplicities and the state sums them over the matched rows -- the join's matched pairs,
    * tgx_key_probe_pairs_get) and ROWS (tgx_plan_set_key_probe_rows: the spec gathers its column as {key, 1} records for
-   * such a set instead of probing it, tgx_key_probe_rows_get). */
+   * such a set instead of probing it, tgx_key_probe_rows_get).  String keys have the same three: STRINGS
+   * (tgx_plan_set_key_probe_strings), COUNTED STRINGS (tgx_plan_set_key_probe_strings_counted) and ROWS STRINGS
+   * (tgx_plan_set_key_probe_rows_strings). */
   TGX_CHECK_KEY_PROBE = 19
 } tgx_check_kind;
 
@@ -726,7 +728,7 @@ tgx_status tgx_plan_set_key_probe_rows(tgx_plan *plan, size_t spec_index, tgx_er
  * holds the parent's values as keyed 128-bit fingerprints (tgx_key_probe_set_parent below).  max_missing_keys
  * (1 .. TGX_KEY_PROBE_MAX_MISSING_KEYS) sizes the table of missing keys as for a plain spec; a missing key keeps its
  * bytes when it has at most max_value_bytes (1 .. TGX_KEY_PROBE_MAX_VALUE_BYTES) of them, and is a long row otherwise.
- * Lifetime and refusals are those of tgx_plan_set_key_probe.  A spec takes exactly one of the four
+ * Lifetime and refusals are those of tgx_plan_set_key_probe.  A spec takes exactly one of the six
  * tgx_plan_set_key_probe* calls: any second one on the same spec is TGX_INVALID_ARGUMENT.  An integer, float, UInt64 or
  * Boolean column on such a spec is TGX_UNSUPPORTED from tgx_update (the state stays usable), as a string column is on
  * every other KEY_PROBE spec. */
@@ -737,6 +739,22 @@ typedef struct tgx_key_probe_strings_params {
 } tgx_key_probe_strings_params;
 tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec_index, const tgx_key_probe_strings_params *params,
                                           tgx_error *err);
+/* The same, and the spec becomes a COUNTED strings spec: its parent set keeps how often each value occurs in the parent
+ * (the records' counts) and the state sums the multiplicities of the matched rows' values -- JoinCoverageConstraint on
+ * string keys.  Bounds, refusals and column types are those of tgx_plan_set_key_probe_strings.  See
+ * tgx_key_probe_pairs_get and the COUNTED STRINGS paragraph beside tgx_key_probe_strings_get. */
+tgx_status tgx_plan_set_key_probe_strings_counted(tgx_plan *plan, size_t spec_index,
+                                                  const tgx_key_probe_strings_params *params, tgx_error *err);
+/* The spec GATHERS its STRING column (Utf8, LargeUtf8, Utf8View or Dictionary<Int32, Utf8>) instead of probing it, as
+ * 32-byte {uint64 hash_a, uint64 hash_b, uint64 count, uint64 0} records in device memory: the values' fingerprints
+ * under the plan's key, in the record format of a string column's TGX_CHECK_DISTINCT export -- the parent side of a
+ * counted strings probe.  A plain string layout gives one {hash_a, hash_b, 1, 0} record per non-NULL row.  A dictionary
+ * column gives, per batch, one {hash_a, hash_b, n, 0} record for each entry that n > 0 rows of the batch refer to; rows
+ * of NULL entries and of indices outside the dictionary are NULL rows, as in the strings probe.  Lifetime, reset and
+ * the refusals of a parent set, of any other tgx_plan_set_key_probe* call, of merge and of serialize are those of
+ * tgx_plan_set_key_probe_rows.  The state costs 32 bytes a row it has seen (the room it keeps; a dictionary column's
+ * records come to 32 bytes per live entry per batch).  Read with tgx_key_probe_rows_get. */
+tgx_status tgx_plan_set_key_probe_rows_strings(tgx_plan *plan, size_t spec_index, tgx_error *err);
 
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
@@ -1106,8 +1124,10 @@ typedef struct tgx_key_probe_pairs {
 } tgx_key_probe_pairs;
 tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_key_probe_pairs *out,
                                    tgx_error *err);
-/* The records a rows spec (tgx_plan_set_key_probe_rows) has gathered: *n_records {key, 1} records in device memory the
- * state owns, valid until its next batch or reset; in no particular order.  TGX_INVALID_ARGUMENT on any other spec. */
+/* The records a rows spec (tgx_plan_set_key_probe_rows) has gathered: *n_records 16-byte {key, 1} records in device
+ * memory the state owns, valid until its next batch or reset; in no particular order.  A rows strings spec
+ * (tgx_plan_set_key_probe_rows_strings): *n_records 32-byte {hash_a, hash_b, count, 0} records.  TGX_INVALID_ARGUMENT on
+ * any other spec. */
 tgx_status tgx_key_probe_rows_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, const void **device_records,
                                   uint64_t *n_records, tgx_error *err);
 /* A STRINGS spec (tgx_plan_set_key_probe_strings).  tgx_key_probe_set_parent takes n_records 32-byte
@@ -1134,7 +1154,19 @@ tgx_status tgx_key_probe_rows_get(const tgx_plan *plan, tgx_state *state, size_t
  * key is malformed.  States of different identities, of different
  * max_value_bytes, or of an integer and a strings spec do not merge.
  * tgx_key_probe_entries, tgx_key_probe_pairs_get and tgx_key_probe_rows_get are TGX_INVALID_ARGUMENT on such a spec, and
- * the two calls below on every other. */
+ * the two calls below on every spec that is neither such a spec nor a counted strings spec.
+ * A COUNTED STRINGS spec (tgx_plan_set_key_probe_strings_counted) is a strings spec whose set keeps counts.
+ * tgx_key_probe_set_parent takes the same 32-byte records and uses their counts: duplicate records of one fingerprint
+ * add up (within one call's records); a count of 0 and a marker word in hash_a or hash_b are TGX_INVALID_ARGUMENT,
+ * counts that sum to 2^63 or more are TGX_UNSUPPORTED, and the state is then left without a set.  The set is route 6:
+ * route 5's table of 16-byte slots, and beside it one 64-bit count per slot (a miss reads the slot table only, a hit 8
+ * bytes more).  Its identity, which blobs carry and merges compare, is (parent_keys, parent_digest, parent_rows,
+ * parent_count_digest): parent_digest is route 5's, parent_count_digest the wrapping sum over the distinct fingerprints
+ * of count * mix64(mix64(hash_a ^ 0xc2b2ae3d27d4eb4f) ^ hash_b).  tgx_key_probe_get (`route` reads 6), the two calls
+ * below and tgx_key_probe_pairs_get work on it: pairs is the sum over the matched rows of their fingerprint's count,
+ * join_rows = pairs + missing_rows + null_rows (long rows are missing rows), under tgx_key_probe_pairs_get's bound.
+ * Its blob is keyed as a strings spec's is; a counted strings spec, a strings spec and an integer spec never merge
+ * with one another. */
 typedef struct tgx_key_probe_strings {
   uint64_t long_rows;       /* missing rows whose value is longer than max_value_bytes */
   uint32_t max_value_bytes; /* the plan's */

@@ -205,9 +205,11 @@ tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *co
  *    "expected_match_rate": 1.0, "coverage_type": "left" | "right" | "bidirectional", "distinct_only": false,
  *    "max_examples_reported": 100, "max_missing_keys": 10000}                       (TG/constraints/join_coverage.rs)
  * on given counts; needs no device.  (Within a suite run over several tables the far side's column is gathered as
- * {key, 1} records and handed to a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's column.)
+ * {key, 1} records and handed to a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's column; string keys: as
+ * fingerprint records, to a counted strings spec.)  "max_value_bytes": n (1 .. 256, string keys only, optional) is the
+ * bytes a missing key may have to be kept.
  * counts_json: {"left": {"pairs": n, "join_rows": n}, "right": {..}, "left_distinct": n, "examples": {"missing_keys": n,
- * "null_rows": n, "overflow_rows": n}} -- "left": the left column probed against the right side's counted set as
+ * "null_rows": n, "overflow_rows": n, "long_rows": n}} ("long_rows": string keys, optional) -- "left": the left column probed against the right side's counted set as
  * tgx_key_probe_pairs_get gives it, "right": the other way round, "left_distinct": COUNT(DISTINCT left column),
  * "examples": the left column's missing keys, NULL rows and overflow rows against the right side's set.  A side the
  * coverage type reads must be there, and "examples" when the check fails with max_examples_reported > 0.

@@ -405,6 +405,8 @@ def lib():
         L.tgx_key_probe_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeSummary), E]
         L.tgx_key_probe_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_key_probe_strings.argtypes = [vp, sz, C.POINTER(KeyProbeStringsParams), E]
+        L.tgx_plan_set_key_probe_strings_counted.argtypes = [vp, sz, C.POINTER(KeyProbeStringsParams), E]
+        L.tgx_plan_set_key_probe_rows_strings.argtypes = [vp, sz, E]
         L.tgx_key_probe_strings_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeStrings), E]
         L.tgx_key_probe_entries_bytes.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
@@ -869,10 +871,24 @@ class Plan:
     def set_key_probe_strings(self, spec_index, max_missing_keys=10000, max_value_bytes=256):
         """tgx_plan_set_key_probe_strings: the spec probes STRING keys against a set of fingerprints
         (State.key_probe_strings); a missing key of up to max_value_bytes bytes keeps its bytes.  A spec takes one of
-        the four set_key_probe* calls"""
+        the six set_key_probe* calls"""
         p = KeyProbeStringsParams(max_missing_keys, max_value_bytes)
         err = _Error()
         _check(lib().tgx_plan_set_key_probe_strings(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_key_probe_strings_counted(self, spec_index, max_missing_keys=10000, max_value_bytes=256):
+        """tgx_plan_set_key_probe_strings_counted: a strings spec whose set keeps the parent's multiplicities
+        (State.key_probe_strings and State.key_probe_pairs read it)"""
+        p = KeyProbeStringsParams(max_missing_keys, max_value_bytes)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_strings_counted(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_key_probe_rows_strings(self, spec_index):
+        """tgx_plan_set_key_probe_rows_strings: the spec gathers its STRING column as 32-byte {hash_a, hash_b, count,
+        0} records (State.key_probe_rows; State.key_probe_rows_records copies them to the host): the parent side of a
+        counted strings probe"""
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_rows_strings(self.h, spec_index, C.byref(err)), err)
 
     def set_key_probe_rows(self, spec_index):
         """tgx_plan_set_key_probe_rows: the spec gathers its column's non-NULL keys as {key, 1} records
@@ -1215,10 +1231,28 @@ class State:
         return summary, {raw[e.offset:e.offset + e.length]: e.count for e in entries}
 
     def key_probe_rows(self, spec_index):
-        """tgx_key_probe_rows_get: (device pointer or None, n_records) of a rows spec's {key, 1} records"""
+        """tgx_key_probe_rows_get: (device pointer or None, n_records) of a rows spec's 16-byte {key, 1} records, or of
+        a rows strings spec's 32-byte {hash_a, hash_b, count, 0} records"""
         ptr, n, err = C.c_void_p(), C.c_uint64(), _Error()
         _check(lib().tgx_key_probe_rows_get(self.plan.h, self.h, spec_index, C.byref(ptr), C.byref(n), C.byref(err)), err)
         return ptr.value, n.value
+
+    def key_probe_rows_records(self, spec_index, record_bytes):
+        """the gathered records as a host array of uint64 rows, record_bytes // 8 words each (16: a rows spec, 32: a
+        rows strings spec; tests: the records are device memory)"""
+        import numpy as np
+        import torch
+
+        ptr, total = self.key_probe_rows(spec_index)
+        if total == 0:
+            return np.zeros((0, record_bytes // 8), np.uint64)
+
+        class P:
+            __cuda_array_interface__ = {"shape": (total * record_bytes,), "typestr": "|u1", "data": (ptr, False),
+                                        "version": 2}
+
+        raw = torch.as_tensor(P(), device="cuda").clone().cpu().numpy()
+        return raw.view(np.uint64).reshape(total, record_bytes // 8)
 
     def key_probe_pairs(self, spec_index):
         """tgx_key_probe_pairs_get: dict(pairs, join_rows, parent_rows, parent_count_digest, max_count) of a counted

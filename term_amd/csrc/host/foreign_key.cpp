@@ -37,21 +37,6 @@ const Table *side_of(const Context &ctx, const std::pair<std::string, std::strin
   return table;
 }
 
-bool string_layout(int type) {
-  return type == TGX_UTF8 || type == TGX_LARGE_UTF8 || type == TGX_UTF8_VIEW || type == TGX_DICT32_UTF8;
-}
-
-// 1: the column is a string layout in every batch that has it; 0: no batch has it (an empty table); -1: another type
-int string_side(const Table &table, int index) {
-  int side = 0;
-  for (const Batch &b : table.batches)
-    if ((size_t)index < b.columns.size()) {
-      if (!string_layout(b.columns[index].type)) return -1;
-      side = 1;
-    }
-  return side;
-}
-
 // the first batch's type of the column (0: no batch has it)
 int first_type(const Table &table, int index) {
   for (const Batch &b : table.batches)

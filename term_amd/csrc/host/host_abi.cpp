@@ -776,6 +776,7 @@ extern "C" tgx_status tgx_host_join_coverage_json(const char *constraint_json, c
       k.missing_keys = e->get_u64("missing_keys", 0);
       k.null_rows = e->get_u64("null_rows", 0);
       k.overflow_rows = e->get_u64("overflow_rows", 0);
+      k.long_rows = e->get_u64("long_rows", 0);
     }
     const ConstraintResult cr = c->verdict(k);
     std::string o =
@@ -791,7 +792,8 @@ extern "C" tgx_status tgx_host_join_coverage_json(const char *constraint_json, c
     o += std::string("], \"expected_match_rate\": ") + json_f64(c->expected_match_rate()) + ", \"coverage_type\": \"" +
          (c->coverage() == CoverageType::LeftCoverage ? "left" : c->coverage() == CoverageType::RightCoverage ? "right" : "bidirectional") +
          "\", \"distinct_only\": " + (c->distinct() ? "true" : "false") + ", \"max_examples_reported\": " +
-         std::to_string(c->examples_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) + "}}";
+         std::to_string(c->examples_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) +
+         (c->value_bytes_given() ? ", \"max_value_bytes\": " + std::to_string(c->value_bytes_bound()) : std::string()) + "}}";
     *out_json = dup_string(o);
     return TGX_OK;
   } catch (const TermError &e) {

@@ -12,8 +12,16 @@
 // and for the examples of a failing check R again and a plain probe of L; Bidirectional walks R, then L (the probe, and
 // the gathering for the other direction, in one plan: the column crosses HBM once), then R.  distinct_only adds a
 // DISTINCT spec on L.l to L's plan.
-// One integer key pair only: composite keys and every other column type are the constraint's own error, so the caller
-// can hand the constraint to the stock path.
+// String keys -- both columns string layouts in every batch that has them, ForeignKeyConstraint's rule -- take the same
+// walks with the string calls: the far side is gathered as {hash_a, hash_b, n, 0} fingerprint records
+// (tgx_plan_set_key_probe_rows_strings), the near side runs under a counted strings spec
+// (tgx_plan_set_key_probe_strings_counted), RightCoverage's examples under a plain strings spec, and the DISTINCT spec
+// counts by value (TGX_FLAG_EXACT_KEYS, the host layer's default for a string uniqueness count).  Every plan of one
+// evaluation carries ONE fingerprint key, the first plan's: records made under another key would match nothing.  On the
+// Bidirectional walk L's plan holds a counted strings spec and a rows strings spec on one column, which run as two
+// launches: the known second pass.
+// One key pair only: composite keys, every other column type, a pair of an integer and a string column and columns
+// declared Binary are the constraint's own error, so the caller can hand the constraint to the stock path.
 #include <stdio.h>
 #include <string.h>
 
@@ -31,24 +39,33 @@ namespace {
   evaluation_error("Join coverage query failed: " + why);
 }
 
-// one side of the join: its table and key column, with the reference's planning / schema errors; integer keys only
+// one side of the join: its table and key column, with the reference's planning / schema errors
 struct Side {
   const Table *table = nullptr;
   int column = -1;
+  std::string qualified;  // "table.column"
 };
 Side side_of(const Context &ctx, const std::string &table_name, const std::string &column) {
   Side s;
+  s.qualified = table_name + "." + column;
   s.table = ctx.table(table_name);
   if (!s.table) query_failed("Error during planning: table 'datafusion.public." + table_name + "' not found");
   for (size_t i = 0; i < s.table->column_names.size(); i++)
     if (s.table->column_names[i] == column) s.column = (int)i;
   if (s.column < 0) query_failed("Schema error: No field named " + table_name + "." + column + ".");
+  // (a column declared Binary arrives in a string layout; it is no string key)
+  if ((size_t)s.column < s.table->arrow_types.size() && s.table->arrow_types[s.column] == "Binary")
+    evaluation_error("column '" + s.qualified + "' is a Binary column: join keys of that type are not on the GPU path "
+                     "(TGX_CHECK_KEY_PROBE takes integer and string keys)");
+  return s;
+}
+// a side of the integer route: every batch's column is of a type the integer probe takes
+void integer_side(const Side &s) {
   for (const Batch &b : s.table->batches)
     if ((size_t)s.column < b.columns.size())
       if (const char *name = off_path_type(b.columns[s.column].type))
-        evaluation_error("column '" + table_name + "." + column + "' is a " + name +
+        evaluation_error("column '" + s.qualified + "' is a " + name +
                          " column: join keys of that type are not on the GPU path (TGX_CHECK_KEY_PROBE takes integer keys)");
-  return s;
 }
 
 std::string percent(double rate) {  // {:.2} of rate * 100.0
@@ -60,9 +77,23 @@ std::string percent(double rate) {  // {:.2} of rate * 100.0
 // the device side of one evaluation
 struct Walks {
   Checker check{query_failed};
+  // string keys: the calls are the string ones, a missing key keeps up to max_value_bytes bytes, and every plan carries
+  // the fingerprint key of the evaluation's first plan
+  bool strings = false;
+  uint32_t max_value_bytes = 0;
+  bool have_key = false;
+  uint8_t key[16];
 
-  // `side` gathered: one {key, 1} record a non-NULL row.  (The records stay the state's until its next call: `h` lives
-  // as long as they are read)
+  // (before the plan's first state)
+  void keyed(tgx_plan *plan) {
+    if (!strings) return;
+    if (have_key) check(tgx_plan_set_fingerprint_key(plan, key, &check.err));
+    else check(tgx_plan_get_fingerprint_key(plan, key));
+    have_key = true;
+  }
+
+  // `side` gathered: one {key, 1} record a non-NULL row (string keys: {hash_a, hash_b, n, 0} records).  (The records
+  // stay the state's until its next call: `h` lives as long as they are read)
   void key_set(const Side &side, Handles &h, const void **records, uint64_t *n_records) {
     tgx_check_spec spec;
     memset(&spec, 0, sizeof(spec));
@@ -70,7 +101,9 @@ struct Walks {
     spec.column = side.column;
     spec.column2 = -1;
     check(tgx_plan_create(&spec, 1, &h.plan, &check.err));
-    check(tgx_plan_set_key_probe_rows(h.plan, 0, &check.err));
+    keyed(h.plan);
+    check(strings ? tgx_plan_set_key_probe_rows_strings(h.plan, 0, &check.err)
+                  : tgx_plan_set_key_probe_rows(h.plan, 0, &check.err));
     check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
     for (const Batch &b : side.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
     check(tgx_key_probe_rows_get(h.plan, h.state, 0, records, n_records, &check.err));
@@ -78,30 +111,45 @@ struct Walks {
 
   // `near` walked once against the set of `records`: a counted probe (or a plain one); in the same plan, with
   // `distinct` a DISTINCT spec on the column, whose count goes there, and with `own_records` a spec that gathers the
-  // column for the other direction
+  // column for the other direction; string keys: *long_rows are the missing rows whose value was too long to keep
   void probe(const Side &near, const void *records, uint64_t n_records, bool counted, uint32_t max_missing_keys,
              Handles &h, tgx_key_probe_summary *summary, tgx_key_probe_pairs *pairs, uint64_t *distinct,
-             const void **own_records, uint64_t *own_n) {
+             const void **own_records, uint64_t *own_n, uint64_t *long_rows) {
     tgx_check_spec specs[3];
     memset(specs, 0, sizeof(specs));
     size_t n = 1, gathers = 0, counts_distinct = 0;
     specs[0].kind = TGX_CHECK_KEY_PROBE;
     if (own_records) specs[gathers = n++].kind = TGX_CHECK_KEY_PROBE;
     if (distinct) specs[counts_distinct = n++].kind = TGX_CHECK_DISTINCT;
+    if (distinct && strings) specs[counts_distinct].flags = TGX_FLAG_EXACT_KEYS;  // COUNT(DISTINCT) by value
     for (size_t i = 0; i < n; i++) {
       specs[i].column = near.column;
       specs[i].column2 = -1;
     }
     check(tgx_plan_create(specs, n, &h.plan, &check.err));
+    keyed(h.plan);
     const tgx_key_probe_params params = {max_missing_keys, 0};
-    check(counted ? tgx_plan_set_key_probe_counted(h.plan, 0, &params, &check.err)
-                  : tgx_plan_set_key_probe(h.plan, 0, &params, &check.err));
-    if (own_records) check(tgx_plan_set_key_probe_rows(h.plan, gathers, &check.err));
+    const tgx_key_probe_strings_params string_params = {max_missing_keys, max_value_bytes};
+    if (strings)
+      check(counted ? tgx_plan_set_key_probe_strings_counted(h.plan, 0, &string_params, &check.err)
+                    : tgx_plan_set_key_probe_strings(h.plan, 0, &string_params, &check.err));
+    else
+      check(counted ? tgx_plan_set_key_probe_counted(h.plan, 0, &params, &check.err)
+                    : tgx_plan_set_key_probe(h.plan, 0, &params, &check.err));
+    if (own_records)
+      check(strings ? tgx_plan_set_key_probe_rows_strings(h.plan, gathers, &check.err)
+                    : tgx_plan_set_key_probe_rows(h.plan, gathers, &check.err));
     check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
     check(tgx_key_probe_set_parent(h.plan, h.state, 0, records, n_records, &check.err));
     for (const Batch &b : near.table->batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
     check(tgx_key_probe_get(h.plan, h.state, 0, summary, &check.err));
     if (counted) check(tgx_key_probe_pairs_get(h.plan, h.state, 0, pairs, &check.err));
+    *long_rows = 0;
+    if (strings) {
+      tgx_key_probe_strings more;
+      check(tgx_key_probe_strings_get(h.plan, h.state, 0, &more, &check.err));
+      *long_rows = more.long_rows;
+    }
     if (distinct) {
       tgx_result results[3];
       memset(results, 0, sizeof(results));
@@ -137,6 +185,9 @@ void JoinCoverageConstraint::validate() const {
   if (max_missing_keys_ < 1 || max_missing_keys_ > TGX_KEY_PROBE_MAX_MISSING_KEYS)
     evaluation_error("max_missing_keys must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_MISSING_KEYS) + " (" +
                      std::to_string(max_missing_keys_) + ")");
+  if (max_value_bytes_ < 1 || max_value_bytes_ > TGX_KEY_PROBE_MAX_VALUE_BYTES)
+    evaluation_error("max_value_bytes must be 1 .. " + std::to_string((int)TGX_KEY_PROBE_MAX_VALUE_BYTES) + " (" +
+                     std::to_string(max_value_bytes_) + ")");
 }
 
 // :327-421
@@ -162,13 +213,14 @@ ConstraintResult JoinCoverageConstraint::verdict(const JoinCoverageCounts &c) co
   std::string message = "Join coverage constraint failed: " + left_ + arrow + right_ + " coverage is " + percent(rate) +
                         "% (expected: " + percent(expected_) + "%)";
   // the examples: SELECT DISTINCT L.l FROM L LEFT JOIN R .. WHERE R.r IS NULL LIMIT n, always from the left side; a NULL
-  // is one distinct value (:289-324, :386-400)
+  // is one distinct value (:289-324, :386-400).  (A long missing value is a distinct left value the table did not keep:
+  // it makes the number a lower bound as an overflow row does)
   if (max_examples_ > 0) {
     if (!c.examples_known)
       throw TermError{TermError::Internal, "join_coverage: a failing check with examples needs the left side's missing keys"};
     const uint64_t found = c.missing_keys + (c.null_rows > 0 ? 1 : 0), n = std::min<uint64_t>(max_examples_, found);
     if (n > 0)
-      message += std::string(" (") + (c.overflow_rows > 0 && n < max_examples_ ? "at least " : "") + std::to_string(n) +
+      message += std::string(" (") + ((c.overflow_rows > 0 || c.long_rows > 0) && n < max_examples_ ? "at least " : "") + std::to_string(n) +
                  " unmatched examples found)";
   }
   return ConstraintResult::failure_with_metric(rate, message);
@@ -177,18 +229,33 @@ ConstraintResult JoinCoverageConstraint::verdict(const JoinCoverageCounts &c) co
 ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) const {
   validate();
   const Side L = side_of(ctx, left_, keys_[0].first), R = side_of(ctx, right_, keys_[0].second);
+  // (a side without a batch has no type to object with: it goes the way of the other side)
+  const int ls = string_side(*L.table, L.column), rs = string_side(*R.table, R.column);
   Walks w;
+  w.strings = ls >= 0 && rs >= 0 && ls + rs > 0;
+  w.max_value_bytes = max_value_bytes_;
+  if (!w.strings) {
+    if (ls != 1) integer_side(L);
+    if (rs != 1) integer_side(R);
+    if (ls == 1 || rs == 1)
+      evaluation_error("columns '" + L.qualified + "' and '" + R.qualified + "' are " +
+                       (ls == 1 ? "a string and an integer" : "an integer and a string") +
+                       " column: join keys of different kinds are not on the GPU path (TGX_CHECK_KEY_PROBE takes two "
+                       "integer columns or two string columns)");
+  }
   w.check(tgx_init(nullptr, &w.check.err));
 
   JoinCoverageCounts counts;
   tgx_key_probe_summary s;
   tgx_key_probe_pairs p;
   memset(&p, 0, sizeof(p));
+  uint64_t long_rows = 0;
   auto note_examples = [&](const tgx_key_probe_summary &of_left) {
     counts.examples_known = true;
     counts.missing_keys = of_left.missing_keys;
     counts.null_rows = of_left.null_rows;
     counts.overflow_rows = of_left.overflow_rows;
+    counts.long_rows = long_rows;
   };
   const void *records = nullptr, *left_records = nullptr;
   uint64_t n_records = 0, n_left = 0;
@@ -198,13 +265,14 @@ ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) co
     const bool both = type_ == CoverageType::BidirectionalCoverage;
     w.key_set(R, r_set, &records, &n_records);
     w.probe(L, records, n_records, true, max_missing_keys_, l_walk, &s, &p,
-            !both && distinct_only_ ? &counts.left_distinct : nullptr, both ? &left_records : nullptr, &n_left);
+            !both && distinct_only_ ? &counts.left_distinct : nullptr, both ? &left_records : nullptr, &n_left, &long_rows);
     counts.left.known = true;
     counts.left.pairs = p.pairs;
     counts.left.join_rows = p.join_rows;
     note_examples(s);
     if (both) {
-      w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr);
+      uint64_t unread = 0;
+      w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr, &unread);
       counts.right.known = true;
       counts.right.pairs = p.pairs;
       counts.right.join_rows = p.join_rows;
@@ -212,7 +280,7 @@ ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) co
     return verdict(counts);
   }
   w.key_set(L, l_set, &left_records, &n_left);
-  w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr);
+  w.probe(R, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, nullptr, nullptr, nullptr, &long_rows);
   counts.right.known = true;
   counts.right.pairs = p.pairs;
   counts.right.join_rows = p.join_rows;
@@ -220,7 +288,7 @@ ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) co
   const bool fails = p.join_rows != 0 && !((double)p.pairs / (double)p.join_rows >= expected_);
   if (fails && wants_examples()) {
     w.key_set(R, r_set, &records, &n_records);
-    w.probe(L, records, n_records, false, max_missing_keys_, l_plain, &s, &p, nullptr, nullptr, nullptr);
+    w.probe(L, records, n_records, false, max_missing_keys_, l_plain, &s, &p, nullptr, nullptr, nullptr, &long_rows);
     note_examples(s);
   }
   return verdict(counts);

@@ -365,7 +365,10 @@ class ForeignKeyConstraint : public Constraint {
 // ---- constraints/join_coverage.rs: the match rate of L LEFT / RIGHT JOIN R ON L.l = R.r, SUM(CASE WHEN the far side's key
 // IS NOT NULL ..) / COUNT(*).  COUNT(*) over a join counts matched PAIRS: the far side's non-NULL keys are gathered as
 // {key, 1} records (tgx_plan_set_key_probe_rows) and go into a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's
-// column (tgx_plan_set_key_probe_counted), so matched = pairs and total = join_rows: one integer key pair only.
+// column (tgx_plan_set_key_probe_counted), so matched = pairs and total = join_rows.  One key pair only: integer keys,
+// or string keys when both columns are string layouts (ForeignKeyConstraint's rule) -- the far side is then gathered as
+// fingerprint records (tgx_plan_set_key_probe_rows_strings), the near side probed under a counted strings spec
+// (tgx_plan_set_key_probe_strings_counted), and every plan of the evaluation carries one fingerprint key.
 enum class CoverageType { LeftCoverage, RightCoverage, BidirectionalCoverage };
 // what the verdict is made from.  left: L probed against R's set, right: R against L's; a side the coverage type does not
 // ask for stays !known
@@ -379,10 +382,12 @@ struct JoinCoverageCounts {
   // whose key found no slot; read when the check fails and max_examples_reported > 0
   bool examples_known = false;
   uint64_t missing_keys = 0, null_rows = 0, overflow_rows = 0;
+  uint64_t long_rows = 0;  // string keys: L's missing rows whose value is longer than max_value_bytes (not kept)
 };
 class JoinCoverageConstraint : public Constraint {
  public:
   static constexpr uint32_t kDefaultMaxMissingKeys = 10000;
+  static constexpr uint32_t kDefaultMaxValueBytes = ForeignKeyConstraint::kDefaultMaxValueBytes;
   JoinCoverageConstraint(std::string left_table, std::string right_table)  // (:94-105)
       : left_(std::move(left_table)), right_(std::move(right_table)) {}
   JoinCoverageConstraint &on(std::string l, std::string r) {
@@ -402,6 +407,9 @@ class JoinCoverageConstraint : public Constraint {
   JoinCoverageConstraint &max_examples_reported(size_t n) { max_examples_ = n; return *this; }
   // this layer's own, as ForeignKeyConstraint's: the missing keys the probe's table on the device is sized for
   JoinCoverageConstraint &max_missing_keys(uint32_t n) { max_missing_keys_ = n; return *this; }
+  // this layer's own, string keys only, as ForeignKeyConstraint's: the bytes a missing key may have to be kept (1 .. 256).
+  // Missing rows with a longer value are counted (long rows): the rate stands, the examples read "at least n"
+  JoinCoverageConstraint &max_value_bytes(uint32_t n) { max_value_bytes_ = n; value_bytes_given_ = true; return *this; }
 
   const std::string &left_table() const { return left_; }
   const std::string &right_table() const { return right_; }
@@ -411,6 +419,8 @@ class JoinCoverageConstraint : public Constraint {
   bool distinct() const { return distinct_only_; }
   size_t examples_reported() const { return max_examples_; }
   uint32_t missing_keys_bound() const { return max_missing_keys_; }
+  uint32_t value_bytes_bound() const { return max_value_bytes_; }
+  bool value_bytes_given() const { return value_bytes_given_; }  // (the JSON form names the option only then)
 
   std::string name() const override { return "join_coverage"; }
   std::vector<SpecRequest> plan() const override { return {}; }
@@ -434,6 +444,8 @@ class JoinCoverageConstraint : public Constraint {
   bool distinct_only_ = false;
   size_t max_examples_ = 100;
   uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
+  uint32_t max_value_bytes_ = kDefaultMaxValueBytes;
+  bool value_bytes_given_ = false;
 };
 
 // ---- core/check.rs
@@ -579,6 +591,22 @@ struct Table {
   // TGX_INT64 / TGX_INT32 needs its name here for the reference's result-type rule to apply)
   std::vector<std::string> arrow_types;
 };
+// what the constraints that join two tables' key columns ask of a column (foreign_key, join_coverage): both take the
+// strings route when both columns are string layouts in every batch that has them, and a side without a batch goes the
+// way of the other side
+inline bool string_layout(int type) {
+  return type == TGX_UTF8 || type == TGX_LARGE_UTF8 || type == TGX_UTF8_VIEW || type == TGX_DICT32_UTF8;
+}
+// 1: the column is a string layout in every batch that has it; 0: no batch has it (an empty table); -1: another type
+inline int string_side(const Table &table, int index) {
+  int side = 0;
+  for (const Batch &b : table.batches)
+    if ((size_t)index < b.columns.size()) {
+      if (!string_layout(b.columns[index].type)) return -1;
+      side = 1;
+    }
+  return side;
+}
 class Context {
  public:
   void register_table(const std::string &name, Table t) { tables_[name] = std::move(t); }

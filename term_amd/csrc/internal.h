@@ -258,7 +258,7 @@ struct GroupSumsTask {
   tgx_group_sums_params params;
 };
 
-// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once one of the four tgx_plan_set_key_probe* calls
+// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once one of the six tgx_plan_set_key_probe* calls
 // was made, which gives the task its mode for good.  (The parent's key set belongs to a state, not to the plan:
 // tgx_key_probe_set_parent)
 //   kKpPlain     tgx_plan_set_key_probe: is each integer key in the set?
@@ -266,13 +266,23 @@ struct GroupSumsTask {
 //   kKpStrings   tgx_plan_set_key_probe_strings: the column is a string column, the set holds fingerprints, and a missing
 //                key of up to max_value_bytes bytes keeps its bytes
 //   kKpRows      tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
-// The first three are a blob's mode word; a rows task's state holds nothing by the time it may be serialized.
-enum KeyProbeMode : uint32_t { kKpPlain = 0, kKpCounted = 1, kKpStrings = 2, kKpRows = 3 };
+//   kKpStringsCounted  tgx_plan_set_key_probe_strings_counted: a strings task whose set keeps the parent's multiplicities
+//   kKpRowsStrings     tgx_plan_set_key_probe_rows_strings: the task gathers its string column as {fa, fb, n, 0} records
+// Those that probe are a blob's mode word; a task that gathers holds nothing by the time its state may be serialized.
+enum KeyProbeMode : uint32_t {
+  kKpPlain = 0, kKpCounted = 1, kKpStrings = 2, kKpRows = 3, kKpStringsCounted = 4, kKpRowsStrings = 5
+};
+// what the modes have in common: the set is of fingerprints; the set keeps counts (and the task sums `pairs`); the task
+// gathers and probes nothing; the column is a string column
+inline bool kp_string_set(KeyProbeMode m) { return m == kKpStrings || m == kKpStringsCounted; }
+inline bool kp_counts(KeyProbeMode m) { return m == kKpCounted || m == kKpStringsCounted; }
+inline bool kp_gathers(KeyProbeMode m) { return m == kKpRows || m == kKpRowsStrings; }
+inline bool kp_string_column(KeyProbeMode m) { return kp_string_set(m) || m == kKpRowsStrings; }
 struct KeyProbeTask {
   int column, spec_index;
   bool set;
   KeyProbeMode mode;
-  uint32_t max_value_bytes;  // a strings task's; 0 otherwise
+  uint32_t max_value_bytes;  // a strings or counted strings task's; 0 otherwise
   tgx_key_probe_params params;
 };
 

@@ -372,7 +372,8 @@ struct GroupSumsTable {
 // counted in a bounded table laid out as ValueCountsTable's integer half is; the missing key whose bits are the marker
 // has a counter of its own.
 // (kKpNonNull | kKpMatched are flushed as a pair, bin_count.h's tail_flush; kKpPairs: the sum of the multiplicities of
-// the matched rows' keys, which only a counted task adds to)
+// the matched rows' keys, which only a counted task adds to; a task that gathers a STRING column probes nothing and
+// keeps its cursor, the records it has written, in that word: a dictionary batch makes fewer records than it has rows)
 enum { kKpNonNull = 0, kKpMatched = 1, kKpMarker = 2, kKpOverflow = 3, kKpPairs = 4, kKeyProbeWords = 5 };
 enum { kKpRouteEmpty = 0, kKpRouteBitmap = 1, kKpRouteHash = 2, kKpRouteCountArray = 3, kKpRouteCountHash = 4 };
 constexpr int kKeyProbeBlock = 1024;              // 16 waves share one LDS table of missing keys
@@ -427,6 +428,21 @@ struct KeyProbeStringSet {
 // mix64(mix64(fa ^ kKeyProbeDigestSalt) ^ fb) over them, and the records that hold a marker word (refused by the host)
 struct KeyProbeStringsBuild {
   unsigned long long keys, digest, marker_records;
+};
+// A COUNTED strings task: route 6 is route 5's slot table with, beside it, one 64-bit count per slot -- how often the
+// slot's value occurs in the parent.  A miss touches the slot table only; a hit reads its slot's count.  (A type of its
+// own: the kernels take the set as a template parameter, and the plain task's instantiation stays what it was.)
+enum { kKpRouteStringsCounted = 6 };
+struct KeyProbeCountedStringSet {
+  const unsigned long long *slots;   // as KeyProbeStringSet's
+  uint64_t mask;
+  const unsigned long long *counts;  // mask + 1 counts, parallel to the slots
+};
+// what the build of such a set leaves behind: KeyProbeStringsBuild's three, and KeyProbeBuild's counted reduction with
+// count * mix64(mix64(fa ^ kKeyProbeCountSalt) ^ fb) as the count digest's term
+struct KeyProbeCountedStringsBuild {
+  unsigned long long keys, digest, marker_records;
+  unsigned long long zero_counts, sum_piece[3], count_digest, max_count;
 };
 constexpr uint64_t kKeyProbeDigestSalt = 0x9e3779b97f4a7c15ULL;
 constexpr uint64_t kKeyProbeCountSalt = 0xc2b2ae3d27d4eb4fULL;

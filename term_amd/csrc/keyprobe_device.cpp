@@ -22,13 +22,18 @@
 // its table is laid out as VALUE_COUNTS's string table is, its entries are KeyedEntries::strs, and it has one more row
 // class, the missing rows whose value is longer than max_value_bytes (long_rows, in the marker's word: no string has the
 // marker's bits).  Merges, blobs and the cross-rank step unite its missing keys by BYTES.
+// A COUNTED STRINGS task (tgx_plan_set_key_probe_strings_counted) is both: its set is route 6, the fingerprint table of
+// route 5 with one 64-bit count a slot beside it, built from the same 32-byte records with their counts used; its
+// identity is the counted one, its blob carries the counted tail and the strings tail.  A ROWS STRINGS task
+// (tgx_plan_set_key_probe_rows_strings) gathers a string column as 32-byte {fa, fb, n, 0} records, what such a set is
+// built from: a record a non-NULL row, or, a dictionary batch, a record per entry its rows refer to, with their number.
 // `pairs` never wraps: the host holds an upper bound, max_count * rows a batch, in checked arithmetic, and refuses the
 // batch, merge or blob that could carry it past 2^64 - 1.
 // The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
 // under: what was merged in or read from a blob, and what the device part is folded into whenever the state is read.
 //
 // How the module is put together.  A task has ONE mode (KeyProbeMode, internal.h); kModes says what differs by mode in
-// words, and plan_set_mode is the one body of the four tgx_plan_set_key_probe* calls.  ProbeCheck is a KeyedCheck
+// words, and plan_set_mode is the one body of the six tgx_plan_set_key_probe* calls.  ProbeCheck is a KeyedCheck
 // (keyed_state.h): the table of missing keys, its views, its decoding and the dictionary route's cells are that
 // skeleton's; what KEY_PROBE adds is the parent set with its identity (so merge_from, serialize, collect and read_spec
 // are its own), `pairs` with its bound, and the gathered rows.  tgx_key_probe_set_parent is the checks, choose_route,
@@ -55,6 +60,19 @@ void launch_key_probe_utf8(const Utf8ColDesc &d, const KeyProbeStringSet &set, c
 void launch_key_probe_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
                            const Utf8ColDesc &dict, unsigned long long *cells, const KeyProbeStringSet &set,
                            const ValueCountsTable &t, hipStream_t stream);
+void launch_key_probe_build_strings_counted(const void *recs, uint64_t n, unsigned long long *slots,
+                                            unsigned long long *counts, uint64_t mask, KeyProbeCountedStringsBuild *b,
+                                            hipStream_t stream);
+void launch_key_probe_utf8_counted(const Utf8ColDesc &d, const KeyProbeCountedStringSet &set, const ValueCountsTable &t,
+                                   hipStream_t stream);
+void launch_key_probe_dict_counted(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
+                                   const Utf8ColDesc &dict, unsigned long long *cells,
+                                   const KeyProbeCountedStringSet &set, const ValueCountsTable &t, hipStream_t stream);
+void launch_key_probe_rows_utf8(const Utf8ColDesc &d, unsigned long long *recs, uint64_t cap, unsigned long long *words,
+                                hipStream_t stream);
+void launch_key_probe_rows_dict(const int32_t *indices, const uint8_t *validity, int64_t offset, int64_t length,
+                                const Utf8ColDesc &dict, unsigned long long *cells, unsigned long long *recs, uint64_t cap,
+                                unsigned long long *words, hipStream_t stream);
 
 namespace {
 
@@ -69,6 +87,7 @@ struct ProbeHost : KeyedEntries<uint64_t> {
   // a counted task: the rest of its set's identity, the set's largest count, and the matched pairs
   uint64_t parent_rows = 0, parent_count_digest = 0, max_count = 0, pairs = 0;
   uint64_t long_rows = 0;  // a strings task: missing rows whose value is longer than max_value_bytes
+  uint64_t gathered = 0;   // a task that gathers: the records it has written
   bool holds_counts() const { return seen != 0 || size() != 0; }
   bool same_parent(const ProbeHost &o) const {
     return parent_keys == o.parent_keys && parent_digest == o.parent_digest && parent_rows == o.parent_rows &&
@@ -116,7 +135,13 @@ struct ProbeKind {
     d.matched = w[kKpMatched];
     d.overflow_rows = w[kKpOverflow];
     d.pairs = w[kKpPairs];
-    if (t.mode == kKpStrings) {  // (no string has the marker's bits)
+    if (t.mode == kKpRows) d.gathered = d.non_null;
+    if (t.mode == kKpRowsStrings) {  // (its cursor stands in the pairs' word)
+      d.gathered = w[kKpPairs];
+      d.pairs = 0;
+      return d;
+    }
+    if (kp_string_set(t.mode)) {  // (no string has the marker's bits)
       d.long_rows = w[kKpLong];
       return d;
     }
@@ -132,6 +157,7 @@ struct ProbeKind {
     a.matched += b.matched;
     a.overflow_rows += b.overflow_rows;
     a.long_rows += b.long_rows;
+    a.gathered += b.gathered;
     a.pairs += b.pairs;  // (the callers have held the sum against 2^64 - 1: ProbeCheck::pairs_fit)
     a.add_entries(b);
     if (!a.known && b.known) a.take_parent(b);
@@ -144,19 +170,22 @@ struct ProbeKind {
   // n_entries and the entries
   // a strings task: the second u32 0 is 2, { u32 max_value_bytes, u32 0, u64 long_rows } stand between n_entries and the
   // entries, and an entry is { u32 length, u8 bytes[length], u64 count }, ascending bytewise
-  // (the mode word is the task's mode; a rows task, whose state serializes only while it is empty, writes a plain one's)
-  static uint32_t mode_word(const KeyProbeTask &t) { return t.mode == kKpRows ? (uint32_t)kKpPlain : (uint32_t)t.mode; }
+  // a counted strings task: the second u32 0 is 4, and the counted task's four words, then the strings task's
+  // { u32 max_value_bytes, u32 0, u64 long_rows }, stand between n_entries and the entries, which are a strings task's
+  // (the mode word is the task's mode; a task that gathers, whose state serializes only while it is empty, writes a
+  // plain one's)
+  static uint32_t mode_word(const KeyProbeTask &t) { return kp_gathers(t.mode) ? (uint32_t)kKpPlain : (uint32_t)t.mode; }
   static void write(const KeyProbeTask &t, const ProbeHost &h, Writer &w) {
     w.pod(t.params);
     w.pod((uint32_t)(h.known ? 1 : 0));
     w.pod(mode_word(t));
     const uint64_t words[7] = {h.parent_keys, h.parent_digest, h.seen, h.non_null, h.matched, h.overflow_rows, h.size()};
     w.pod(words);
-    if (t.mode == kKpCounted) {
+    if (kp_counts(t.mode)) {
       const uint64_t more[4] = {h.parent_rows, h.parent_count_digest, h.max_count, h.pairs};
       w.pod(more);
     }
-    if (t.mode == kKpStrings) {
+    if (kp_string_set(t.mode)) {
       w.pod(t.max_value_bytes);
       w.pod((uint32_t)0);
       w.pod(h.long_rows);
@@ -171,14 +200,16 @@ struct ProbeKind {
     uint64_t words[7], more[4] = {0, 0, 0, 0};
     r.get(words, sizeof(words));
     if (!r.ok) return TGX_OK;
-    const bool counted = t.mode == kKpCounted, strings = t.mode == kKpStrings;
-    if (pad != mode_word(t))
+    const bool counted = kp_counts(t.mode), strings = kp_string_set(t.mode);
+    if (pad != mode_word(t)) {
+      const bool is_mode = pad <= kKpStrings || pad == kKpStringsCounted;
       return fail(err, TGX_INVALID_ARGUMENT,
-                  pad > kKpStrings ? "malformed state blob (KEY_PROBE task %zu: parent set)"
-                  : pad == kKpStrings || strings
+                  !is_mode ? "malformed state blob (KEY_PROBE task %zu: parent set)"
+                  : (is_mode && kp_string_set((KeyProbeMode)pad)) != strings
                       ? "KEY_PROBE task %zu: the blob was counted under the other mode (integer / string keys) than the plan's"
                       : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
                   k);
+    }
     if (counted) r.get(more, sizeof(more));
     uint32_t value_bytes = 0, value_pad = 0;
     uint64_t long_rows = 0;
@@ -246,14 +277,18 @@ struct ModeInfo {
 constexpr ModeInfo kModes[] = {{"plain", "", 16},
                                {"counted", "_counted", 16},
                                {"to probe string keys", "_strings", 32},
-                               {"to gather rows", "_rows", 16}};
-static_assert(kKpPlain == 0 && kKpCounted == 1 && kKpStrings == 2 && kKpRows == 3, "kModes is indexed by the mode");
+                               {"to gather rows", "_rows", 16},
+                               {"to probe string keys, counted", "_strings_counted", 32},
+                               {"to gather the rows of a string column", "_rows_strings", 32}};
+static_assert(kKpPlain == 0 && kKpCounted == 1 && kKpStrings == 2 && kKpRows == 3 && kKpStringsCounted == 4 &&
+                  kKpRowsStrings == 5, "kModes is indexed by the mode");
 
 // the set of one task on the device
 struct ParentSet {
   bool has = false;
   int route = kKpRouteEmpty;
-  // the bitmap's words, the table's keys, the count array, the table's {key, count} slots or (strings) {fa, fb} slots
+  // the bitmap's words, the table's keys, the count array, the table's {key, count} slots or (strings) {fa, fb} slots;
+  // route 6: the {fa, fb} slots, and behind them a count a slot
   DevBuf buf;
   uint64_t base = 0, range = 0, mask = 0;
   uint32_t has_marker = 0;
@@ -284,12 +319,17 @@ struct ParentSet {
   KeyProbeStringSet string_view() const {
     return KeyProbeStringSet{route == kKpRouteStrings ? buf.as<unsigned long long>() : nullptr, mask};
   }
+  KeyProbeCountedStringSet counted_string_view() const {
+    unsigned long long *slots = route == kKpRouteStringsCounted ? buf.as<unsigned long long>() : nullptr;
+    return KeyProbeCountedStringSet{slots, mask, slots ? slots + 2 * (mask + 1) : nullptr};
+  }
 };
 
 // the route of a set of `n` > 0 records of a task of `mode`, whose keys span `range` (0: all of int64, which is not dense).
 // A dense set is no larger than the table would be: a bit a key up to 128 * n, a count a key up to 4 * n
 int choose_route(KeyProbeMode mode, uint64_t range, uint64_t n) {
   if (mode == kKpStrings) return kKpRouteStrings;
+  if (mode == kKpStringsCounted) return kKpRouteStringsCounted;
   const bool counted = mode == kKpCounted;
   const bool dense = range != 0 && range <= (counted ? 4 : 128) * n;
   return counted ? (dense ? kKpRouteCountArray : kKpRouteCountHash) : (dense ? kKpRouteBitmap : kKpRouteHash);
@@ -301,7 +341,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
   // per counted task: an upper bound of what the device part's `pairs` can have come to, the sum over the accepted
   // batches of max_count * rows
   std::vector<uint64_t> pairs_bound;
-  // per rows task: the gathered records and the records there is room for
+  // per task that gathers: the gathered records and the records there is room for
   std::vector<DevBuf> gathered;
   std::vector<uint64_t> gathered_cap;
 
@@ -314,7 +354,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
   // a state that has gathered rows keeps them to itself
   tgx_status rows_stay(const char *what, tgx_error *err) const {
     for (size_t k = 0; k < tasks.size(); k++)
-      if (tasks[k].mode == kKpRows && (device_rows[k] > 0 || host[k].seen > 0))
+      if (kp_gathers(tasks[k].mode) && (device_rows[k] > 0 || host[k].seen > 0))
         return fail(err, TGX_UNSUPPORTED, "spec %d: a KEY_PROBE check that gathers rows does not %s: its records stay with "
                     "the state", tasks[k].spec_index, what);
     return TGX_OK;
@@ -332,14 +372,14 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
 
   tgx_status accepts(tgx_state *, int64_t nrows, tgx_error *err) override {
     for (size_t k = 0; k < tasks.size(); k++)
-      if (!parent[k].has && tasks[k].mode != kKpRows)
+      if (!parent[k].has && !kp_gathers(tasks[k].mode))
         return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check needs its parent set (tgx_key_probe_set_parent)",
                     tasks[k].spec_index);
     // a counted task: host part + bound of the device part + this batch's bound stays within 2^64 - 1, for every task
     // before any bound moves
     std::vector<uint64_t> next(pairs_bound);
     for (size_t k = 0; k < tasks.size(); k++) {
-      if (tasks[k].mode != kKpCounted || nrows <= 0) continue;
+      if (!kp_counts(tasks[k].mode) || nrows <= 0) continue;
       uint64_t batch = 0, all = 0;
       if (__builtin_mul_overflow(parent[k].max_count, (uint64_t)nrows, &batch) || !add_fits(next[k], batch, &next[k]) ||
           !add_fits(next[k], host[k].pairs, &all))
@@ -413,6 +453,21 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     return TGX_OK;
   }
 
+  // a counted set's reduction, held to its bounds: no zero count, and the sum (three pieces, exact) below 2^63: s->rows
+  tgx_status counts_ok(size_t k, unsigned long long zero_counts, const unsigned long long *piece, ParentSet *s,
+                       tgx_error *err) {
+    if (zero_counts)
+      return drop_set(k, fail(err, TGX_INVALID_ARGUMENT, "spec %d: %llu records of the parent set have a count of 0",
+                              tasks[k].spec_index, zero_counts));
+    const unsigned __int128 total = (unsigned __int128)piece[0] + ((unsigned __int128)piece[1] << kKpPieceBits) +
+                                    ((unsigned __int128)piece[2] << (2 * kKpPieceBits));
+    if (total >> 63)
+      return drop_set(k, fail(err, TGX_UNSUPPORTED, "spec %d: the counts of the parent set sum to 2^63 or more",
+                              tasks[k].spec_index));
+    s->rows = (uint64_t)total;
+    return TGX_OK;
+  }
+
   // routes 1 .. 4: the set of task k from `n` > 0 16-byte {key, count} records; a reduction, the route's build, two waits
   tgx_status build_integers(tgx_state *st, size_t k, const void *recs, uint64_t n, ParentSet *s, tgx_error *err) {
     const KeyProbeMode mode = tasks[k].mode;
@@ -426,16 +481,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     launch_key_probe_reduce(recs, n, mode == kKpCounted, d_build.as<KeyProbeBuild>(), st->stream);
     TGX_TRY(read_back(st, d_build, &b, err));
     if (mode == kKpCounted) {
-      if (b.zero_counts)
-        return drop_set(k, fail(err, TGX_INVALID_ARGUMENT, "spec %d: %llu records of the parent set have a count of 0",
-                                tasks[k].spec_index, (unsigned long long)b.zero_counts));
-      const unsigned __int128 total = (unsigned __int128)b.sum_piece[0] +
-                                      ((unsigned __int128)b.sum_piece[1] << kKpPieceBits) +
-                                      ((unsigned __int128)b.sum_piece[2] << (2 * kKpPieceBits));
-      if (total >> 63)
-        return drop_set(k, fail(err, TGX_UNSUPPORTED, "spec %d: the counts of the parent set sum to 2^63 or more",
-                                tasks[k].spec_index));
-      s->rows = (uint64_t)total;
+      TGX_TRY(counts_ok(k, b.zero_counts, b.sum_piece, s, err));
       s->count_digest = b.count_digest;
     }
     // (unsigned: INT64_MIN and INT64_MAX together wrap the range to 0, which is not dense)
@@ -473,10 +519,39 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
                                    st->stream);
     KeyProbeStringsBuild b;
     TGX_TRY(read_back(st, d_build, &b, err));
-    if (b.marker_records)
-      return drop_set(k, fail(err, TGX_INVALID_ARGUMENT,
-                              "spec %d: %llu records of the parent set hold the free-slot marker (all ones) in hash_a or "
-                              "hash_b, which no fingerprint is", tasks[k].spec_index, (unsigned long long)b.marker_records));
+    if (b.marker_records) return marker_records(k, b.marker_records, err);
+    s->keys = b.keys;
+    s->digest = b.digest;
+    return TGX_OK;
+  }
+
+  // the refusal of records that can be no fingerprints
+  tgx_status marker_records(size_t k, unsigned long long n, tgx_error *err) {
+    return drop_set(k, fail(err, TGX_INVALID_ARGUMENT,
+                            "spec %d: %llu records of the parent set hold the free-slot marker (all ones) in hash_a or "
+                            "hash_b, which no fingerprint is", tasks[k].spec_index, n));
+  }
+
+  // route 6: the set of counted strings task k from `n` > 0 such records, their counts used; one wait
+  tgx_status build_strings_counted(tgx_state *st, size_t k, const void *recs, uint64_t n, ParentSet *s, tgx_error *err) {
+    DevBuf d_build;
+    HIP_TRY(d_build.reserve(sizeof(KeyProbeCountedStringsBuild)));
+    HIP_TRY(hipMemsetAsync(d_build.p, 0, sizeof(KeyProbeCountedStringsBuild), st->stream));
+    s->route = choose_route(tasks[k].mode, 0, n);
+    s->mask = table_slots(n) - 1;
+    const size_t slots = (size_t)(s->mask + 1);
+    HIP_TRY(s->buf.reserve(slots * 24));  // (16-byte slots, every word kEmptyKey; then the counts, 0)
+    HIP_TRY(hipMemsetAsync(s->buf.p, 0xFF, slots * 16, st->stream));
+    HIP_TRY(hipMemsetAsync(s->buf.as<uint8_t>() + slots * 16, 0, slots * 8, st->stream));
+    unsigned long long *table = s->buf.as<unsigned long long>();
+    launch_key_probe_build_strings_counted(recs, n, table, table + 2 * slots, s->mask,
+                                           d_build.as<KeyProbeCountedStringsBuild>(), st->stream);
+    KeyProbeCountedStringsBuild b;
+    TGX_TRY(read_back(st, d_build, &b, err));
+    if (b.marker_records) return marker_records(k, b.marker_records, err);
+    TGX_TRY(counts_ok(k, b.zero_counts, b.sum_piece, s, err));
+    s->count_digest = b.count_digest;
+    s->max_count = b.max_count;
     s->keys = b.keys;
     s->digest = b.digest;
     return TGX_OK;
@@ -484,7 +559,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
 
   tgx_status set_parent(tgx_state *st, size_t k, const void *recs, uint64_t n, tgx_error *err) {
     const KeyProbeMode mode = tasks[k].mode;
-    if (mode == kKpRows)
+    if (kp_gathers(mode))
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: a KEY_PROBE check that gathers rows takes no parent set",
                   tasks[k].spec_index);
     if (fed)
@@ -500,7 +575,9 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     s.has = true;
     if (n > 0) {  // (without records: the empty set, route 0)
       ProfScope ps(st, "key_probe_build", n * kModes[mode].record_bytes);
-      TGX_TRY(mode == kKpStrings ? build_strings(st, k, recs, n, &s, err) : build_integers(st, k, recs, n, &s, err));
+      TGX_TRY(mode == kKpStrings          ? build_strings(st, k, recs, n, &s, err)
+              : mode == kKpStringsCounted ? build_strings_counted(st, k, recs, n, &s, err)
+                                          : build_integers(st, k, recs, n, &s, err));
     }
     ProbeHost &h = host[k];
     ProbeHost given;
@@ -536,10 +613,11 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     for (size_t k = 0; k < tasks.size(); k++) {
       const tgx_column &x = dev[tasks[k].column];
       const Route route = route_of(x);
-      if (tasks[k].mode == kKpStrings) {
+      if (kp_string_column(tasks[k].mode)) {
         if (route != kStringRoute && route != kDictRoute)
           return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on string keys takes string columns (%d)", x.type);
-        TGX_TRY(ensure_keys(st, k, kByteKeys, 0, err));
+        if (tasks[k].mode == kKpRowsStrings) TGX_TRY(gather_strings(st, k, x, nrows, err));
+        else TGX_TRY(ensure_keys(st, k, kByteKeys, 0, err));
         continue;
       }
       // (an Int64 view: update_validate refuses what is not widened to one)
@@ -572,7 +650,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
       }));
     }
     for (size_t k = 0; k < tasks.size(); k++)
-      if (tasks[k].mode == kKpStrings) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
+      if (kp_string_set(tasks[k].mode)) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
     for (size_t k = 0; k < tasks.size(); k++) device_rows[k] += nrows;
     return TGX_OK;
   }
@@ -580,7 +658,9 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
   // one batch of strings task k: a row per lane, or the dictionary's two steps (VALUE_COUNTS's routes)
   tgx_status probe_strings(tgx_state *st, size_t k, const tgx_column &x, int64_t nrows, tgx_error *err) {
     const tgx_plan *plan = st->plan;
+    const bool counted = tasks[k].mode == kKpStringsCounted;
     const KeyProbeStringSet set = parent[k].string_view();
+    const KeyProbeCountedStringSet counted_set = parent[k].counted_string_view();
     ValueCountsTable t;
     fill_view(st, k, t);
     t.counts = (unsigned long long *)(table[k].buf.as<uint8_t>() + table[k].counts_at());
@@ -589,7 +669,9 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
     if (x.type != TGX_DICT32_UTF8) {
       ProfScope ps(st, "key_probe", 0);
-      launch_key_probe_utf8(string_desc(x, x.variadic, plan->fp_key), set, t, st->stream);
+      const Utf8ColDesc d = string_desc(x, x.variadic, plan->fp_key);
+      if (counted) launch_key_probe_utf8_counted(d, counted_set, t, st->stream);
+      else launch_key_probe_utf8(d, set, t, st->stream);
     } else {
       const tgx_column *dc;
       TGX_TRY(dictionary_of(x, &dc, err));
@@ -597,8 +679,12 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
         unsigned long long *cells;
         TGX_TRY(clear_cells(st, k, (size_t)dc->length * 8, &cells, err));
         ProfScope ps(st, "key_probe", (uint64_t)x.length * 4);
-        launch_key_probe_dict((const int32_t *)x.values, x.validity, x.offset, x.length,
-                              string_desc(*dc, nullptr, plan->fp_key), cells, set, t, st->stream);
+        const Utf8ColDesc d = string_desc(*dc, nullptr, plan->fp_key);
+        if (counted)
+          launch_key_probe_dict_counted((const int32_t *)x.values, x.validity, x.offset, x.length, d, cells, counted_set, t,
+                                        st->stream);
+        else
+          launch_key_probe_dict((const int32_t *)x.values, x.validity, x.offset, x.length, d, cells, set, t, st->stream);
       }
     }
     HIP_TRY(hipGetLastError());
@@ -607,19 +693,26 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
 
   // one batch of a rows task: room for every row the state has seen and this batch's, then the batch's non-NULL keys
   // behind the records that are there
-  tgx_status gather_rows(tgx_state *st, size_t k, const tgx_column &col, int64_t nrows, tgx_error *err) {
+  // room in task k's buffer of gathered records for every row the state has seen and `nrows` more (a batch makes at
+  // most a record a row): at least twice the room there was, the records that are there kept
+  tgx_status gather_room(tgx_state *st, size_t k, int64_t nrows, tgx_error *err) {
+    const size_t record = kModes[tasks[k].mode].record_bytes;
     const uint64_t need = (uint64_t)device_rows[k] + (uint64_t)nrows;
-    if (need > gathered_cap[k]) {
-      const uint64_t cap = std::max<uint64_t>(need, 2 * gathered_cap[k]);
-      DevBuf grown;
-      HIP_TRY(grown.reserve((size_t)cap * 16));
-      if (device_rows[k] > 0) {
-        HIP_TRY(hipMemcpyAsync(grown.p, gathered[k].p, (size_t)device_rows[k] * 16, hipMemcpyDeviceToDevice, st->stream));
-        HIP_TRY(hipStreamSynchronize(st->stream));  // (before the old buffer goes)
-      }
-      gathered[k] = std::move(grown);
-      gathered_cap[k] = cap;
+    if (need <= gathered_cap[k]) return TGX_OK;
+    const uint64_t cap = std::max<uint64_t>(need, 2 * gathered_cap[k]);
+    DevBuf grown;
+    HIP_TRY(grown.reserve((size_t)cap * record));
+    if (device_rows[k] > 0) {
+      HIP_TRY(hipMemcpyAsync(grown.p, gathered[k].p, (size_t)device_rows[k] * record, hipMemcpyDeviceToDevice, st->stream));
+      HIP_TRY(hipStreamSynchronize(st->stream));  // (before the old buffer goes)
     }
+    gathered[k] = std::move(grown);
+    gathered_cap[k] = cap;
+    return TGX_OK;
+  }
+
+  tgx_status gather_rows(tgx_state *st, size_t k, const tgx_column &col, int64_t nrows, tgx_error *err) {
+    TGX_TRY(gather_room(st, k, nrows, err));
     ComomentColDesc d;
     memset(&d, 0, sizeof(d));
     const uint64_t bytes = side_fill_x(d, col);
@@ -631,14 +724,39 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     return TGX_OK;
   }
 
+  // one batch of a rows strings task: a {fa, fb, 1, 0} record a non-NULL row, or the dictionary's two steps and a
+  // {fa, fb, n, 0} record an entry that n > 0 rows of the batch refer to
+  tgx_status gather_strings(tgx_state *st, size_t k, const tgx_column &x, int64_t nrows, tgx_error *err) {
+    const tgx_plan *plan = st->plan;
+    TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
+    TGX_TRY(gather_room(st, k, nrows, err));
+    unsigned long long *recs = gathered[k].as<unsigned long long>(), *words = d_counts.as<unsigned long long>() + word_off[k];
+    if (x.type != TGX_DICT32_UTF8) {
+      ProfScope ps(st, "key_probe_rows", 0);
+      launch_key_probe_rows_utf8(string_desc(x, x.variadic, plan->fp_key), recs, gathered_cap[k], words, st->stream);
+    } else {
+      const tgx_column *dc;
+      TGX_TRY(dictionary_of(x, &dc, err));
+      if (dc->length > 0) {  // (without entries every row is a row without a value)
+        unsigned long long *cells;
+        TGX_TRY(clear_cells(st, k, (size_t)dc->length * 8, &cells, err));
+        ProfScope ps(st, "key_probe_rows", (uint64_t)x.length * 4);
+        launch_key_probe_rows_dict((const int32_t *)x.values, x.validity, x.offset, x.length,
+                                   string_desc(*dc, nullptr, plan->fp_key), cells, recs, gathered_cap[k], words, st->stream);
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    return TGX_OK;
+  }
+
   // the records of rows task k (device memory, the state's until its next batch or reset)
   tgx_status rows_get(tgx_state *st, size_t k, const void **records, uint64_t *n, tgx_error *err) {
-    if (tasks[k].mode != kKpRows)
+    if (!kp_gathers(tasks[k].mode))
       return fail(err, TGX_INVALID_ARGUMENT, "spec %d: the KEY_PROBE check does not gather rows (tgx_plan_set_key_probe_rows)",
                   tasks[k].spec_index);
     std::vector<ProbeHost> g;
     TGX_TRY(collect(st, &g, err));
-    *n = std::min<uint64_t>(g[k].non_null, gathered_cap[k]);
+    *n = std::min<uint64_t>(g[k].gathered, gathered_cap[k]);
     *records = *n ? gathered[k].p : nullptr;
     return TGX_OK;
   }
@@ -727,7 +845,7 @@ tgx_status keyprobe_check_column(const tgx_plan *plan, int column, const tgx_col
   // a strings task takes the string layouts and nothing else; every other task refuses them (below)
   bool strings = false, others = false;
   for (const KeyProbeTask &t : plan->key_probes)
-    if (t.column == column) (t.mode == kKpStrings ? strings : others) = true;
+    if (t.column == column) (kp_string_column(t.mode) ? strings : others) = true;
   if (strings && !is_any_string(type) && type != TGX_DICT32_UTF8)
     return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE on string keys takes string columns, not %s (type %d)", column,
                 refused_as_key(type) ? type_name(type) : "integers", type);
@@ -746,7 +864,7 @@ bool keyprobe_blob_keyed(tgx_state *st) {
   ProbeCheck *c = static_cast<ProbeCheck *>(ProbeCheck::of(st));
   if (!c) return false;
   for (size_t k = 0; k < c->tasks.size(); k++)
-    if (c->tasks[k].mode == kKpStrings &&
+    if (kp_string_set(c->tasks[k].mode) &&
         ((c->parent[k].has && c->parent[k].keys != 0) || (c->host[k].known && c->host[k].parent_keys != 0)))
       return true;
   return false;
@@ -759,11 +877,11 @@ SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.em
 using namespace tgx;
 
 namespace {
-// The four tgx_plan_set_key_probe* calls: `p` is the call's parameters (a rows spec has none to give: its own),
-// `max_value_bytes` a strings spec's.  (A spec keeps the mode of its first call: a call of another mode is refused)
+// The six tgx_plan_set_key_probe* calls: `p` is the call's parameters (a spec that gathers has none to give: its own),
+// `max_value_bytes` a strings or counted strings spec's.  (A spec keeps the mode of its first call: a call of another mode is refused)
 tgx_status plan_set_mode(tgx_plan *plan, size_t spec_index, KeyProbeMode mode, const tgx_key_probe_params *p,
                          uint32_t max_value_bytes, tgx_error *err) {
-  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, mode == kKpRows ? "plan is NULL" : "plan/params is NULL");
+  if (!plan || !p) return fail(err, TGX_INVALID_ARGUMENT, kp_gathers(mode) ? "plan is NULL" : "plan/params is NULL");
   size_t slot = 0;
   TGX_TRY(spec_slot(plan, nullptr, spec_index, TGX_CHECK_KEY_PROBE, "KEY_PROBE", &slot, err, nullptr));
   if (plan_has_state(plan))
@@ -772,7 +890,7 @@ tgx_status plan_set_mode(tgx_plan *plan, size_t spec_index, KeyProbeMode mode, c
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_missing_keys must be 1 .. %d (%u)", spec_index,
                 (int)TGX_KEY_PROBE_MAX_MISSING_KEYS, p->max_missing_keys);
   if (p->reserved != 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: reserved must be 0 (%u)", spec_index, p->reserved);
-  if (mode == kKpStrings && (max_value_bytes < 1 || max_value_bytes > TGX_KEY_PROBE_MAX_VALUE_BYTES))
+  if (kp_string_set(mode) && (max_value_bytes < 1 || max_value_bytes > TGX_KEY_PROBE_MAX_VALUE_BYTES))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
                 (int)TGX_KEY_PROBE_MAX_VALUE_BYTES, max_value_bytes);
   KeyProbeTask &t = plan->key_probes[slot];
@@ -823,6 +941,21 @@ extern "C" tgx_status tgx_plan_set_key_probe_strings(tgx_plan *plan, size_t spec
   return tgx::abi_exception(err);
 }
 
+extern "C" tgx_status tgx_plan_set_key_probe_strings_counted(tgx_plan *plan, size_t spec_index,
+                                                             const tgx_key_probe_strings_params *p, tgx_error *err) try {
+  const tgx_key_probe_params q = {p ? p->max_missing_keys : 0, 0};
+  return plan_set_mode(plan, spec_index, kKpStringsCounted, p ? &q : nullptr, p ? p->max_value_bytes : 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_rows_strings(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
+  const tgx_key_probe_params own = {1, 0};
+  return plan_set_mode(plan, spec_index, kKpRowsStrings, &own, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
 extern "C" tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
                                                 tgx_key_probe_strings *out, tgx_error *err) try {
   bind_thread();
@@ -830,7 +963,7 @@ extern "C" tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state 
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
   const KeyProbeTask &t = task_of(plan, spec_index);
-  if (t.mode != kKpStrings)
+  if (!kp_string_set(t.mode))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys "
                 "(tgx_plan_set_key_probe_strings)", spec_index);
   memset(out, 0, sizeof(*out));
@@ -849,7 +982,7 @@ extern "C" tgx_status tgx_key_probe_entries_bytes(const tgx_plan *plan, tgx_stat
   if (!n_entries || !n_bytes) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  if (task_of(plan, spec_index).mode != kKpStrings)
+  if (!kp_string_set(task_of(plan, spec_index).mode))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not probe string keys: its missing keys "
                 "are read with tgx_key_probe_entries", spec_index);
   int32_t is_bytes = 0;
@@ -914,7 +1047,7 @@ extern "C" tgx_status tgx_key_probe_pairs_get(const tgx_plan *plan, tgx_state *s
   if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  if (task_of(plan, spec_index).mode != kKpCounted)
+  if (!kp_counts(task_of(plan, spec_index).mode))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check is not counted (tgx_plan_set_key_probe_counted)",
                 spec_index);
   memset(out, 0, sizeof(*out));
@@ -937,7 +1070,7 @@ extern "C" tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *st,
   if (!n_entries) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
   ProbeHost h;
   TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
-  if (task_of(plan, spec_index).mode == kKpStrings)
+  if (kp_string_set(task_of(plan, spec_index).mode))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check probes string keys: its missing keys are read "
                 "with tgx_key_probe_entries_bytes", spec_index);
   uint64_t n_bytes = 0;

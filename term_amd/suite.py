@@ -580,8 +580,10 @@ class JoinCoverageConstraint:
     """constraints/join_coverage.rs:94-163, one method per builder call of the reference: the match rate of
     `left_table` LEFT JOIN `right_table` on one key pair, SUM(CASE WHEN the far key IS NOT NULL ..) / COUNT(*), against
     expect_match_rate.  COUNT(*) over a join counts matched pairs: the far side's non-NULL keys are gathered as {key, 1}
-    records and handed to a counted KEY_PROBE spec over the near side's column (one integer key pair
-    only: composite keys and other column types are the constraint's own error).  It needs
+    records and handed to a counted KEY_PROBE spec over the near side's column.  One key pair only: integer keys, or
+    string keys when both columns are string layouts (Utf8, LargeUtf8, Utf8View, Dictionary<Int32, Utf8>; the far
+    side's values then travel as keyed 128-bit fingerprints).  Composite keys, other column types and a pair of an
+    integer and a string column are the constraint's own error.  It needs
     ValidationSuite.run(table, tables={name: table})"""
 
     def __init__(self, left_table, right_table):
@@ -598,6 +600,8 @@ class JoinCoverageConstraint:
         c.coverage_type(spec.get("coverage_type", CoverageType.Left))
         c.distinct_only(spec.get("distinct_only", False))
         c.max_examples_reported(spec.get("max_examples_reported", 100))
+        if "max_value_bytes" in spec:
+            c.max_value_bytes(spec["max_value_bytes"])
         return c.max_missing_keys(spec.get("max_missing_keys", 10000))
 
     def on(self, left_column, right_column):
@@ -634,11 +638,18 @@ class JoinCoverageConstraint:
         self.spec["max_missing_keys"] = int(n)
         return self
 
+    def max_value_bytes(self, n):
+        """this layer's own, string keys only, as ForeignKeyConstraint's: the bytes a missing key may have to be kept
+        (1 .. 256, default 256).  Missing rows with a longer value are counted as long rows: the rate stands, and the
+        examples read "at least n" """
+        self.spec["max_value_bytes"] = int(n)
+        return self
+
     def name(self): return "join_coverage"
 
     def verdict_from_counts(self, counts):
         """the verdict on given counts (no device): a dict {"left": {"pairs", "join_rows"}, "right": {..},
-        "left_distinct", "examples": {"missing_keys", "null_rows", "overflow_rows"}} (include/tgx_host.h)"""
+        "left_distinct", "examples": {"missing_keys", "null_rows", "overflow_rows", "long_rows"}} (include/tgx_host.h)"""
         out, err = C.c_char_p(), _Error()
         _host_check(_host().tgx_host_join_coverage_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
                                                         C.byref(out), C.byref(err)), err)

@@ -322,7 +322,9 @@ def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0,
     `strings`: (max_value_bytes, long_rows) of a task on string keys (Plan.set_key_probe_strings): the second reserved
     word is then 2, { u32 max_value_bytes, u32 0, u64 long_rows } stand before the entries, the keys of `missing` are
     bytes and an entry is { u32 length, bytes, u64 rows }, ascending bytewise; long_rows count towards non_null.  A blob
-    that holds such a task with a non-empty parent set carries the plan's fingerprint key (pack's fingerprint_key)."""
+    that holds such a task with a non-empty parent set carries the plan's fingerprint key (pack's fingerprint_key).
+    `counted` and `strings` together: a counted task on string keys (Plan.set_key_probe_strings_counted) -- the second
+    reserved word is 4, the counted task's four words stand first, then the strings task's three, then its entries."""
     items = list(missing.items()) if hasattr(missing, "items") else list(missing)
     if ordered:
         items.sort(key=lambda kv: kv[0])
@@ -331,7 +333,7 @@ def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0,
     if seen is None:
         seen = non_null + nulls
     keys, digest = parent if parent is not None else (0, 0)
-    mode = 1 if counted is not None else 2 if strings is not None else 0
+    mode = (4 if strings is not None else 1) if counted is not None else 2 if strings is not None else 0
     out = struct.pack("<4I7Q", max_missing_keys, 0, 1 if parent is not None else 0, mode, keys, digest, seen, non_null,
                       matched, overflow_rows, len(items))
     if counted is not None:

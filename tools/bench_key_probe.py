@@ -145,6 +145,10 @@ STRING_EXPECTATIONS = """expectations, written before the run:
  (3) the missing rate moves the time little: 300 missing keys combine in the wave and the LDS table; a miss probes on
      to a free slot (about 2.5 slots at load 0.5 against 1.5 for a hit).
  (4) the dictionary child costs its 4 bytes a row: the 10 000 lookups are nothing.
+ (5) the COUNTED strings probe (route 6) reads 8 more bytes per matched row, from a count array beside the slot table:
+     close to the plain probe where every row misses, somewhat above it where every row hits; its build adds an atomicAdd
+     a record to route 5's claims.  The rows strings gather reads what the probe reads and writes 32 bytes a non-NULL
+     row: it should cost about the plain probe against the small set plus 3 GB of stores.
 """
 
 
@@ -155,7 +159,11 @@ def strings_main(args):
     value length, validity) with 5000 distinct values, which its table holds: the same walker and fingerprint, no set;
     then a dictionary child of 10 000 entries.  The set is built from the parent column's DISTINCT export under the child plan's
     fingerprint key; its build is timed by the wall clock around tgx_key_probe_set_parent.  The roofline prices the
-    kind's own bytes -- 12 B of data, a 4-byte offset and one validity bit a row -- at 8 TB/s."""
+    kind's own bytes -- 12 B of data, a 4-byte offset and one validity bit a row -- at 8 TB/s.
+    Beside each plain probe, interleaved with it step by step on the same column: the COUNTED strings probe
+    (tgx_plan_set_key_probe_strings_counted, route 6) against the same records with every count 1 -- so pairs must equal
+    the matched rows -- with its build, and the rows strings gather (tgx_plan_set_key_probe_rows_strings) of the column;
+    each is stated as a ratio to the plain probe of the same case.  A child that misses on every row joins the cases."""
     import torch
     import term_amd as T
     from term_amd._lib import spec
@@ -202,8 +210,15 @@ def strings_main(args):
         parent.update([T.Column(T.UTF8, k, offsets=poffs, data=pdata, mem=T.MEM_DEVICE)])
         ptr, counts = parent.distinct_export(0, 1)
         assert counts[0] == k, counts
+
+        class Exported:  # (the export as a tensor: a copy of the records with every count 1, for the counted set)
+            __cuda_array_interface__ = {"shape": (k, 4), "typestr": "<i8", "data": (ptr, False), "version": 2}
+
+        ones = torch.as_tensor(Exported(), device="cuda").clone()
+        ones[:, 2] = 1
+        torch.cuda.synchronize()
         slots = 1 << max(1, (2 * k - 1).bit_length())
-        cases = [("missing_%g" % share, share, False) for share in (0.0, 0.01, 0.5)] + [("dictionary_10000", 0.01, True)]
+        cases = [("missing_%g" % share, share, False) for share in (0.0, 0.01, 0.5, 1.0)] + [("dictionary_10000", 0.01, True)]
         for label, share, as_dict in cases:
             name = "strings_%d_%s" % (k, label)
             if as_dict:
@@ -230,17 +245,29 @@ def strings_main(args):
             vplan = T.Plan([spec(T.VALUE_COUNTS, 0)])
             vplan.set_fingerprint_key(key)
             vplan.set_value_counts(0, 10000, 256)
-            pst, vst = T.State(pplan), T.State(vplan)
-            pst.profile_enable(True)
-            vst.profile_enable(True)
+            cplan = T.Plan([spec(T.KEY_PROBE, 0)])
+            cplan.set_fingerprint_key(key)
+            cplan.set_key_probe_strings_counted(0, 10000, 256)
+            gplan = T.Plan([spec(T.KEY_PROBE, 0)])
+            gplan.set_fingerprint_key(key)
+            gplan.set_key_probe_rows_strings(0)
+            pst, vst, cst, gst = T.State(pplan), T.State(vplan), T.State(cplan), T.State(gplan)
+            for st in (pst, vst, cst, gst):
+                st.profile_enable(True)
             builds = []
             for _ in range(3):  # (a state that has seen no batch takes a set again)
                 t0 = time.perf_counter()
                 pst.key_probe_set_parent(0, ptr, k)
                 builds.append((time.perf_counter() - t0) * 1e3)
-            probe_ms, counts_ms = [], []
+            cbuilds = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                cst.key_probe_set_parent(0, ones.data_ptr(), k)
+                cbuilds.append((time.perf_counter() - t0) * 1e3)
+            probe_ms, counts_ms, counted_ms, gather_ms = [], [], [], []
             for it in range(args.steps + 1):
-                for st, kernel, times, batch in ((pst, "key_probe", probe_ms, col), (vst, "value_counts", counts_ms, ycol)):
+                for st, kernel, times, batch in ((pst, "key_probe", probe_ms, col), (vst, "value_counts", counts_ms, ycol),
+                                                 (cst, "key_probe", counted_ms, col), (gst, "key_probe_rows", gather_ms, col)):
                     st.reset()
                     st.profile_reset()
                     st.update([batch])
@@ -252,19 +279,38 @@ def strings_main(args):
             assert s["parent_keys"] == k and s["route"] == 5 and s["matched"] + s["missing_rows"] == non_null, s
             assert s["missing_keys"] == (100 if as_dict else N_MISSING if share else 0), s
             assert abs(s["missing_rows"] - share * non_null) <= 0.01 * non_null + 1000, s
+            cs, cmissing = cst.key_probe_strings(0)
+            cp = cst.key_probe_pairs(0)
+            assert cs["route"] == 6 and cmissing == missing, cs
+            assert {f: v for f, v in cs.items() if f != "route"} == {f: v for f, v in s.items() if f != "route"}, cs
+            assert cp["pairs"] == s["matched"] and cp["parent_rows"] == k and cp["max_count"] == 1 and cp["join_rows"] == n, cp
+            _, gathered = gst.key_probe_rows(0)
+            assert gst.finalize()[0].non_null == non_null, gathered
+            assert gathered == (non_null if not as_dict else 10000), gathered
             pm, vm = statistics.median(probe_ms), statistics.median(counts_ms)
+            cm, gm = statistics.median(counted_ms), statistics.median(gather_ms)
+            counted_row = {"counted_ms": cm, "counted_min_ms": min(counted_ms), "counted_max_ms": max(counted_ms),
+                           "counted_ratio": cm / pm, "counted_build_ms": statistics.median(cbuilds),
+                           "counted_set_bytes": 24 * slots, "gather_ms": gm, "gather_min_ms": min(gather_ms),
+                           "gather_max_ms": max(gather_ms), "gather_ratio": gm / pm, "gathered_records": gathered}
             row = {"key_probe_ms": pm, "key_probe_min_ms": min(probe_ms), "key_probe_max_ms": max(probe_ms),
                    "value_counts_ms": vm, "value_counts_min_ms": min(counts_ms), "value_counts_max_ms": max(counts_ms),
                    "ratio": pm / vm, "roofline": case_bytes / (pm * 1e-3) / HBM_BYTES_PER_S,
                    "build_ms": statistics.median(builds), "set_bytes": 16 * slots, "missing_rows": s["missing_rows"]}
+            row.update(counted_row)
             out["cases"][name] = row
             print("%d rows, %-36s key_probe %.2f ms (%.2f .. %.2f) | value_counts %.2f ms (%.2f .. %.2f) (x %.2f) | "
                   "%.0f %% of 8 TB/s | set of %.1f MB built in %.2f ms"
                   % (n, name, pm, min(probe_ms), max(probe_ms), vm, min(counts_ms), max(counts_ms), row["ratio"],
                      100 * row["roofline"], row["set_bytes"] / 1e6, row["build_ms"]), flush=True)
-            del pst, vst, col
+            print("%d rows, %-36s counted   %.2f ms (%.2f .. %.2f) (x %.2f of the plain probe) | set of %.1f MB built in "
+                  "%.2f ms" % (n, name, cm, min(counted_ms), max(counted_ms), row["counted_ratio"],
+                               row["counted_set_bytes"] / 1e6, row["counted_build_ms"]), flush=True)
+            print("%d rows, %-36s gather    %.2f ms (%.2f .. %.2f) (x %.2f of the plain probe) | %d records of 32 B"
+                  % (n, name, gm, min(gather_ms), max(gather_ms), row["gather_ratio"], gathered), flush=True)
+            del pst, vst, cst, gst, col
             torch.cuda.empty_cache()
-        del parent, poffs, pdata
+        del parent, poffs, pdata, ones
         torch.cuda.empty_cache()
     print(json.dumps(out))
     if args.json:
