@@ -401,7 +401,10 @@ typedef enum tgx_check_kind {
    * tgx_key_probe_pairs_get) and ROWS (tgx_plan_set_key_probe_rows: the spec gathers its column as {key, 1} records for
    * such a set instead of probing it, tgx_key_probe_rows_get).  String keys have the same three: STRINGS
    * (tgx_plan_set_key_probe_strings), COUNTED STRINGS (tgx_plan_set_key_probe_strings_counted) and ROWS STRINGS
-   * (tgx_plan_set_key_probe_rows_strings). */
+   * (tgx_plan_set_key_probe_rows_strings).  A spec with a column list (`columns` / `n_columns` of 2 .. 8) reads TUPLE
+   * keys -- a composite join key, JoinCoverageConstraint::on_multiple -- and has the same three again: TUPLES
+   * (tgx_plan_set_key_probe_tuples), COUNTED TUPLES (tgx_plan_set_key_probe_tuples_counted) and ROWS TUPLES
+   * (tgx_plan_set_key_probe_rows_tuples); the row rules stand beside tgx_key_probe_tuples_get. */
   TGX_CHECK_KEY_PROBE = 19
 } tgx_check_kind;
 
@@ -445,7 +448,9 @@ typedef struct tgx_check_spec {
    * layout (Utf8 / LargeUtf8 / Utf8View / Dictionary<Int32, Utf8>: a NULL dictionary entry is a NULL component).
    * Result: total = rows, non_null = rows whose every
    * component is non-NULL (the primary-key NULL check), distinct = tuples, groups_once with MULTIPLICITY.
-   * n_columns == 0 or 1: the single-column check on `column`. */
+   * n_columns == 0 or 1: the single-column check on `column`.
+   * KEY_PROBE over a tuple of 2..8 columns: the spec's key is the tuple (tgx_plan_set_key_probe_tuples).  More than 8
+   * columns or a NULL list is refused by tgx_plan_create; every other kind refuses a column list. */
   const int32_t *columns;
   uint32_t n_columns;
   uint32_t reserved2;
@@ -755,6 +760,19 @@ tgx_status tgx_plan_set_key_probe_strings_counted(tgx_plan *plan, size_t spec_in
  * tgx_plan_set_key_probe_rows.  The state costs 32 bytes a row it has seen (the room it keeps; a dictionary column's
  * records come to 32 bytes per live entry per batch).  Read with tgx_key_probe_rows_get. */
 tgx_status tgx_plan_set_key_probe_rows_strings(tgx_plan *plan, size_t spec_index, tgx_error *err);
+/* The three calls of a spec with a COLUMN LIST (tgx_check_spec::columns, 2 .. 8 columns): its key is the TUPLE of the
+ * row's components.  _tuples: a plain probe against a set of route 5; _tuples_counted: a counted probe against a set of
+ * route 6 (tgx_key_probe_pairs_get works on it under its bound); _rows_tuples: the spec gathers its tuples as 32-byte
+ * {hash_a, hash_b, 1, 0} records (tgx_key_probe_rows_get), one per row whose every component is non-NULL, 32 bytes a
+ * gathered row; such a state does not merge or serialize.  max_missing_keys bounds each of the two classes of entries
+ * (below).  A spec takes exactly one of the nine tgx_plan_set_key_probe* calls: any second one on the same spec is
+ * TGX_INVALID_ARGUMENT, and so is one of these three on a spec without a column list and one of the other six on a spec
+ * with one.  The rules of a row and the reads: tgx_key_probe_tuples_get. */
+tgx_status tgx_plan_set_key_probe_tuples(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *params,
+                                         tgx_error *err);
+tgx_status tgx_plan_set_key_probe_tuples_counted(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *params,
+                                                 tgx_error *err);
+tgx_status tgx_plan_set_key_probe_rows_tuples(tgx_plan *plan, size_t spec_index, tgx_error *err);
 
 /* TGX_CHECK_HISTOGRAM: the `buckets + 1` edges of spec `spec_index`, which puts the spec into its COUNT phase.  Like a
  * JOINT_BINS binning they can be set until the plan's first state exists; afterwards (and for a spec of another kind)
@@ -1180,6 +1198,59 @@ tgx_status tgx_key_probe_strings_get(const tgx_plan *plan, tgx_state *state, siz
 tgx_status tgx_key_probe_entries_bytes(const tgx_plan *plan, tgx_state *state, size_t spec_index,
                                        tgx_value_count_entry *entries, uint64_t cap, uint64_t *n_entries, uint8_t *bytes,
                                        uint64_t bytes_cap, uint64_t *n_bytes, tgx_error *err);
+/* A TUPLES spec (a column list, tgx_plan_set_key_probe_tuples / _tuples_counted): the join key is the tuple
+ * (c0, c1, ..) of the row's components -- JoinCoverageConstraint::on_multiple, TG/constraints/join_coverage.rs:127-138,
+ * the join condition at :192-197.
+ *   components    the sign- or zero-extended int64 of an Int64-shaped, Int32 / Date32 or Int8 .. UInt32 column, or the
+ *                 row's string in any of the four string layouts.  A NULL dictionary entry and an index outside the
+ *                 dictionary are a NULL component.  Float32 / Float64 (SQL's = is not bit equality), UInt64, Boolean and
+ *                 validity-only components are TGX_UNSUPPORTED from tgx_update: nothing is noted, the state stays usable.
+ *   the key       the tuple's keyed 128-bit fingerprint, the one TGX_CHECK_DISTINCT keeps for a tuple of the same
+ *                 components, bit for bit: a narrow column joins a wide one, any string layout joins any other,
+ *                 ("ab","c") != ("a","bc") and (1,2) != (2,1).
+ *   the set       tgx_key_probe_set_parent takes 32-byte {hash_a, hash_b, count, 0} records as a strings spec does, with
+ *                 the same refusals (marker words, zero counts, sums of 2^63 or more) and the same identities; `route`
+ *                 reads 5 (plain) or 6 (counted).  The records must be tuple fingerprints of the SAME ARITY under the
+ *                 plan's fingerprint key -- what a rows tuples spec gathers, or a tuple DISTINCT's export.  THE LIBRARY
+ *                 CANNOT VERIFY THIS: records of another arity, another key or of single values simply match nothing.
+ *   NULLs         SQL's join: a row with at least one NULL component matches nothing -- a parent tuple with a NULL in
+ *                 the same place included, although the two fingerprint alike.  Such a row is never looked up; it is a
+ *                 null_rows row, and non_null counts the rows whose every component is non-NULL.  A rows tuples spec
+ *                 emits no record for it.  The three identities of tgx_key_probe_summary hold verbatim over the all-valid
+ *                 rows; there are no long rows, since the table keeps fingerprints and no bytes.
+ *   two classes   the reference's examples query is SELECT DISTINCT l0, l1 .. WHERE R.r0 IS NULL, where a NULL-bearing
+ *                 tuple is a distinct value of its own: those rows are counted per distinct tuple too, apart from the
+ *                 missing keys (tgx_key_probe_summary's counted, overflow_rows and missing_keys speak of the missing
+ *                 tuples only):  null_rows == null_counted + null_overflow_rows.  max_missing_keys bounds EACH class as it
+ *                 bounds the missing keys of the other modes: each has a table of its own, a power of two of at
+ *                 least 2 * max_missing_keys slots, so neither class can crowd the other out; missing_keys and
+ *                 null_keys may each exceed max_missing_keys, and the caller compares.
+ * tgx_state_reset clears counters and entries and keeps the set.  tgx_merge, blobs and tgx_allreduce behave as for a
+ * strings spec: the blob is keyed and carries the arity, a deserialized state holds no set, and states of different
+ * arity, mode or identity, and a tuples spec with a strings or an integer spec, do not merge.
+ * tgx_key_probe_entries, tgx_key_probe_entries_bytes and tgx_key_probe_strings_get are TGX_INVALID_ARGUMENT on such a
+ * spec, the two calls below on every other spec. */
+typedef struct tgx_key_probe_tuples {
+  uint64_t null_counted;       /* rows with a NULL component that are counted in the entries */
+  uint64_t null_overflow_rows; /* ... whose tuple found no slot */
+  uint64_t null_keys;          /* entries of NULL-bearing tuples held */
+  uint32_t arity;              /* the plan's: columns of the tuple */
+  uint32_t reserved;
+} tgx_key_probe_tuples;
+tgx_status tgx_key_probe_tuples_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_key_probe_tuples *out,
+                                    tgx_error *err);
+/* One tuple that is not in the set, or that holds a NULL, and its rows.  Only its fingerprint is kept. */
+typedef struct tgx_key_probe_tuple_entry {
+  uint64_t hash_a;
+  uint64_t hash_b;
+  uint64_t count;
+  uint32_t has_null; /* 1: a tuple with at least one NULL component; 0: an all-valid tuple missing from the set */
+  uint32_t reserved;
+} tgx_key_probe_tuple_entry;
+/* Copies the entries of both classes together, ascending by (hash_a, hash_b).  Sizes as for tgx_key_probe_entries. */
+tgx_status tgx_key_probe_entries_tuples(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                        tgx_key_probe_tuple_entry *entries, uint64_t cap, uint64_t *n_entries,
+                                        tgx_error *err);
 
 /* ---- exact DISTINCT across ranks: hash-owner key exchange -------------
  * export: partitions this state's key set by owner = mix(key) % world into `world` contiguous

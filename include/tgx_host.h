@@ -207,14 +207,19 @@ tgx_status tgx_host_foreign_key_json(const char *constraint_json, const char *co
  * on given counts; needs no device.  (Within a suite run over several tables the far side's column is gathered as
  * {key, 1} records and handed to a COUNTED TGX_CHECK_KEY_PROBE spec over the near side's column; string keys: as
  * fingerprint records, to a counted strings spec.)  "max_value_bytes": n (1 .. 256, string keys only, optional) is the
- * bytes a missing key may have to be kept.
+ * bytes a missing key may have to be kept.  "composite_keys_on_device": true (optional, an opt-in) lets "join_keys" hold
+ * 2 .. 8 pairs: the join then runs under TGX_CHECK_KEY_PROBE's tuple modes, each pair two integer or two string
+ * columns; a row with a NULL in any key column joins nothing.  Absent or false, more than one key pair is the error it
+ * was.  "examples" then takes two more optional counts, "null_keys" (the left side's distinct tuples with a NULL
+ * component: each a distinct value of the examples query) and "null_overflow_rows" (rows of such tuples that found no
+ * slot: the number reads "at least"); where "null_keys" is absent the NULL rows count as ONE value, as for a single key.
  * counts_json: {"left": {"pairs": n, "join_rows": n}, "right": {..}, "left_distinct": n, "examples": {"missing_keys": n,
  * "null_rows": n, "overflow_rows": n, "long_rows": n}} ("long_rows": string keys, optional) -- "left": the left column probed against the right side's counted set as
  * tgx_key_probe_pairs_get gives it, "right": the other way round, "left_distinct": COUNT(DISTINCT left column),
  * "examples": the left column's missing keys, NULL rows and overflow rows against the right side's set.  A side the
  * coverage type reads must be there, and "examples" when the check fails with max_examples_reported > 0.
  * Returns {"status", "metric", "message", "config": {the constraint as the host layer read it}}.  A constraint without
- * join keys, with more than one key pair, RightCoverage with distinct_only and a join without rows are
+ * join keys, with more than one key pair without the opt-in or more than 8 with it, RightCoverage with distinct_only and a join without rows are
  * TGX_INVALID_ARGUMENT with the constraint's error text. */
 tgx_status tgx_host_join_coverage_json(const char *constraint_json, const char *counts_json, char **out_json,
                                        tgx_error *err);

@@ -254,6 +254,18 @@ class KeyProbeStrings(C.Structure):
     _fields_ = [("long_rows", C.c_uint64), ("max_value_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class KeyProbeTuples(C.Structure):
+    """tgx_key_probe_tuples (include/tgx.h)"""
+    _fields_ = [("null_counted", C.c_uint64), ("null_overflow_rows", C.c_uint64), ("null_keys", C.c_uint64),
+                ("arity", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KeyProbeTupleEntry(C.Structure):
+    """tgx_key_probe_tuple_entry (include/tgx.h)"""
+    _fields_ = [("hash_a", C.c_uint64), ("hash_b", C.c_uint64), ("count", C.c_uint64), ("has_null", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class HistogramRange(C.Structure):
     """tgx_histogram_range (include/tgx.h)"""
     _fields_ = [("total", C.c_uint64), ("nulls", C.c_uint64), ("non_finite", C.c_uint64), ("n", C.c_uint64),
@@ -409,6 +421,11 @@ def lib():
         L.tgx_plan_set_key_probe_rows_strings.argtypes = [vp, sz, E]
         L.tgx_key_probe_strings_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeStrings), E]
         L.tgx_key_probe_entries_bytes.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), E]
+        L.tgx_plan_set_key_probe_tuples.argtypes = [vp, sz, C.POINTER(KeyProbeParams), E]
+        L.tgx_plan_set_key_probe_tuples_counted.argtypes = [vp, sz, C.POINTER(KeyProbeParams), E]
+        L.tgx_plan_set_key_probe_rows_tuples.argtypes = [vp, sz, E]
+        L.tgx_key_probe_tuples_get.argtypes = [vp, vp, sz, C.POINTER(KeyProbeTuples), E]
+        L.tgx_key_probe_entries_tuples.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), E]
         L.tgx_plan_set_histogram_edges.argtypes = [vp, sz, C.POINTER(C.c_double), C.c_uint32, E]
         L.tgx_histogram_range_get.argtypes = [vp, vp, sz, C.POINTER(HistogramRange), E]
         L.tgx_histogram_counts.argtypes = [vp, vp, sz, vp, sz, C.POINTER(u64), C.POINTER(u64), E]
@@ -684,7 +701,8 @@ class Column:
 
 
 def spec(kind, column, column2=-1, flags=0, pattern=None, kll_k=0, columns=None, length_min=0, length_max=None):
-    """columns=[a, b, ...]: DISTINCT over the tuple of those columns (COUNT(DISTINCT (a, b)));
+    """columns=[a, b, ...]: DISTINCT over the tuple of those columns (COUNT(DISTINCT (a, b))), or a KEY_PROBE whose key is
+    that tuple (Plan.set_key_probe_tuples);
     length_min / length_max (None = unbounded): LENGTH bounds in characters"""
     pat = pattern.encode("utf-8") if isinstance(pattern, str) else pattern
     s = CheckSpec(kind, column, column2, flags, pat, len(pat) if pat else 0, kll_k, 0)
@@ -889,6 +907,27 @@ class Plan:
         counted strings probe"""
         err = _Error()
         _check(lib().tgx_plan_set_key_probe_rows_strings(self.h, spec_index, C.byref(err)), err)
+
+    def set_key_probe_tuples(self, spec_index, max_missing_keys=10000, reserved=0):
+        """tgx_plan_set_key_probe_tuples: a spec with a column list (spec(KEY_PROBE, 0, columns=[..])) probes the TUPLE of
+        its columns against a set of tuple fingerprints (State.key_probe_tuples).  A spec takes one of the nine
+        set_key_probe* calls"""
+        p = KeyProbeParams(max_missing_keys, reserved)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_tuples(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_key_probe_tuples_counted(self, spec_index, max_missing_keys=10000, reserved=0):
+        """tgx_plan_set_key_probe_tuples_counted: a tuples spec whose set keeps the parent's multiplicities
+        (State.key_probe_tuples and State.key_probe_pairs read it)"""
+        p = KeyProbeParams(max_missing_keys, reserved)
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_tuples_counted(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_key_probe_rows_tuples(self, spec_index):
+        """tgx_plan_set_key_probe_rows_tuples: the spec gathers the all-valid tuples of its columns as 32-byte
+        {hash_a, hash_b, 1, 0} records (State.key_probe_rows): the parent side of a tuples probe"""
+        err = _Error()
+        _check(lib().tgx_plan_set_key_probe_rows_tuples(self.h, spec_index, C.byref(err)), err)
 
     def set_key_probe_rows(self, spec_index):
         """tgx_plan_set_key_probe_rows: the spec gathers its column's non-NULL keys as {key, 1} records
@@ -1229,6 +1268,23 @@ class State:
         summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
         summary["long_rows"], summary["max_value_bytes"] = more.long_rows, more.max_value_bytes
         return summary, {raw[e.offset:e.offset + e.length]: e.count for e in entries}
+
+    def key_probe_tuples(self, spec_index):
+        """tgx_key_probe_get + tgx_key_probe_tuples_get + tgx_key_probe_entries_tuples of a tuples spec: (summary,
+        entries) -- summary the fields of tgx_key_probe_summary plus null_counted, null_overflow_rows, null_keys and
+        arity; entries a list of (hash_a, hash_b, count, has_null) in the library's order (ascending by the pair)"""
+        L, err = lib(), _Error()
+        s, more = KeyProbeSummary(), KeyProbeTuples()
+        _check(L.tgx_key_probe_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
+        _check(L.tgx_key_probe_tuples_get(self.plan.h, self.h, spec_index, C.byref(more), C.byref(err)), err)
+        n = C.c_uint64(0)
+        _check(L.tgx_key_probe_entries_tuples(self.plan.h, self.h, spec_index, None, 0, C.byref(n), C.byref(err)), err)
+        entries = (KeyProbeTupleEntry * max(n.value, 1))()
+        _check(L.tgx_key_probe_entries_tuples(self.plan.h, self.h, spec_index, entries, n.value, C.byref(n), C.byref(err)),
+               err)
+        summary = {f: getattr(s, f) for f, _ in KeyProbeSummary._fields_ if f != "reserved"}
+        summary.update({f: getattr(more, f) for f, _ in KeyProbeTuples._fields_ if f != "reserved"})
+        return summary, [(e.hash_a, e.hash_b, e.count, e.has_null) for e in entries[:n.value]]
 
     def key_probe_rows(self, spec_index):
         """tgx_key_probe_rows_get: (device pointer or None, n_records) of a rows spec's 16-byte {key, 1} records, or of

@@ -777,6 +777,10 @@ extern "C" tgx_status tgx_host_join_coverage_json(const char *constraint_json, c
       k.null_rows = e->get_u64("null_rows", 0);
       k.overflow_rows = e->get_u64("overflow_rows", 0);
       k.long_rows = e->get_u64("long_rows", 0);
+      // (composite keys; absent: the NULL rows are one distinct value)
+      k.null_keys_known = e->get("null_keys") != nullptr;
+      k.null_keys = e->get_u64("null_keys", 0);
+      k.null_overflow_rows = e->get_u64("null_overflow_rows", 0);
     }
     const ConstraintResult cr = c->verdict(k);
     std::string o =
@@ -793,7 +797,8 @@ extern "C" tgx_status tgx_host_join_coverage_json(const char *constraint_json, c
          (c->coverage() == CoverageType::LeftCoverage ? "left" : c->coverage() == CoverageType::RightCoverage ? "right" : "bidirectional") +
          "\", \"distinct_only\": " + (c->distinct() ? "true" : "false") + ", \"max_examples_reported\": " +
          std::to_string(c->examples_reported()) + ", \"max_missing_keys\": " + std::to_string(c->missing_keys_bound()) +
-         (c->value_bytes_given() ? ", \"max_value_bytes\": " + std::to_string(c->value_bytes_bound()) : std::string()) + "}}";
+         (c->value_bytes_given() ? ", \"max_value_bytes\": " + std::to_string(c->value_bytes_bound()) : std::string()) +
+         (c->composite_keys() ? ", \"composite_keys_on_device\": true" : "") + "}}";
     *out_json = dup_string(o);
     return TGX_OK;
   } catch (const TermError &e) {

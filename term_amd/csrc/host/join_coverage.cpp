@@ -20,7 +20,13 @@
 // evaluation carries ONE fingerprint key, the first plan's: records made under another key would match nothing.  On the
 // Bidirectional walk L's plan holds a counted strings spec and a rows strings spec on one column, which run as two
 // launches: the known second pass.
-// One key pair only: composite keys, every other column type, a pair of an integer and a string column and columns
+// Composite keys are an opt-in (composite_keys_on_device): a join on 2 .. 8 key pairs takes the same three walk patterns
+// with the tuple calls -- the far side gathered as tuple fingerprint records (tgx_plan_set_key_probe_rows_tuples), the
+// near side under a counted tuples spec (tgx_plan_set_key_probe_tuples_counted), the examples under a plain one -- each
+// pair two integer or two string columns, every plan under one fingerprint key.  A row with a NULL in any key column
+// joins nothing; the examples are the missing tuples plus the distinct NULL-bearing tuples, as the reference's
+// SELECT DISTINCT l0, l1 .. counts them.  distinct_only counts COUNT(DISTINCT L.k0), the first left key alone.
+// Without the opt-in, one key pair only: composite keys, every other column type, a pair of an integer and a string column and columns
 // declared Binary are the constraint's own error, so the caller can hand the constraint to the stock path.
 #include <stdio.h>
 #include <string.h>
@@ -85,8 +91,9 @@ struct Walks {
   uint8_t key[16];
 
   // (before the plan's first state)
+  bool tuples = false;  // composite keys: the tuple calls, which are keyed too
   void keyed(tgx_plan *plan) {
-    if (!strings) return;
+    if (!strings && !tuples) return;
     if (have_key) check(tgx_plan_set_fingerprint_key(plan, key, &check.err));
     else check(tgx_plan_get_fingerprint_key(plan, key));
     have_key = true;
@@ -158,6 +165,64 @@ struct Walks {
     }
     if (own_records) check(tgx_key_probe_rows_get(h.plan, h.state, gathers, own_records, own_n, &check.err));
   }
+
+  // ---- composite keys: the same two walks over the key columns of a side as ONE tuple key ----
+  static void tuple_spec(tgx_check_spec *spec, const std::vector<int32_t> &columns) {
+    spec->kind = TGX_CHECK_KEY_PROBE;
+    spec->column = columns[0];
+    spec->column2 = -1;
+    spec->columns = columns.data();
+    spec->n_columns = (uint32_t)columns.size();
+  }
+  void tuple_set(const Table &table, const std::vector<int32_t> &columns, Handles &h, const void **records,
+                 uint64_t *n_records) {
+    tgx_check_spec spec;
+    memset(&spec, 0, sizeof(spec));
+    tuple_spec(&spec, columns);
+    check(tgx_plan_create(&spec, 1, &h.plan, &check.err));
+    keyed(h.plan);
+    check(tgx_plan_set_key_probe_rows_tuples(h.plan, 0, &check.err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
+    for (const Batch &b : table.batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
+    check(tgx_key_probe_rows_get(h.plan, h.state, 0, records, n_records, &check.err));
+  }
+  // `distinct`: COUNT(DISTINCT) of the FIRST key column alone, by value when it is a string column
+  void tuple_probe(const Table &near, const std::vector<int32_t> &columns, const void *records, uint64_t n_records,
+                   bool counted, uint32_t max_missing_keys, Handles &h, tgx_key_probe_summary *summary,
+                   tgx_key_probe_pairs *pairs, tgx_key_probe_tuples *more, uint64_t *distinct, bool distinct_is_string,
+                   const void **own_records, uint64_t *own_n) {
+    tgx_check_spec specs[3];
+    memset(specs, 0, sizeof(specs));
+    size_t n = 1, gathers = 0, counts_distinct = 0;
+    tuple_spec(&specs[0], columns);
+    if (own_records) tuple_spec(&specs[gathers = n++], columns);
+    if (distinct) {
+      counts_distinct = n++;
+      specs[counts_distinct].kind = TGX_CHECK_DISTINCT;
+      specs[counts_distinct].column = columns[0];
+      specs[counts_distinct].column2 = -1;
+      if (distinct_is_string) specs[counts_distinct].flags = TGX_FLAG_EXACT_KEYS;
+    }
+    check(tgx_plan_create(specs, n, &h.plan, &check.err));
+    keyed(h.plan);
+    const tgx_key_probe_params params = {max_missing_keys, 0};
+    check(counted ? tgx_plan_set_key_probe_tuples_counted(h.plan, 0, &params, &check.err)
+                  : tgx_plan_set_key_probe_tuples(h.plan, 0, &params, &check.err));
+    if (own_records) check(tgx_plan_set_key_probe_rows_tuples(h.plan, gathers, &check.err));
+    check(tgx_state_create(h.plan, nullptr, &h.state, &check.err));
+    check(tgx_key_probe_set_parent(h.plan, h.state, 0, records, n_records, &check.err));
+    for (const Batch &b : near.batches) check(tgx_update(h.plan, h.state, b.columns.data(), b.columns.size(), &check.err));
+    check(tgx_key_probe_get(h.plan, h.state, 0, summary, &check.err));
+    check(tgx_key_probe_tuples_get(h.plan, h.state, 0, more, &check.err));
+    if (counted) check(tgx_key_probe_pairs_get(h.plan, h.state, 0, pairs, &check.err));
+    if (distinct) {
+      tgx_result results[3];
+      memset(results, 0, sizeof(results));
+      check(tgx_finalize(h.plan, h.state, results, n, &check.err));
+      *distinct = (uint64_t)results[counts_distinct].distinct;
+    }
+    if (own_records) check(tgx_key_probe_rows_get(h.plan, h.state, gathers, own_records, own_n, &check.err));
+  }
 };
 
 }  // namespace
@@ -175,7 +240,10 @@ void JoinCoverageConstraint::validate() const {
     if (auto e = validate_identifier(k.second)) throw *e;
   }
   if (keys_.empty()) evaluation_error("No join keys specified. Use .on() or .on_multiple() to set join keys");
-  if (keys_.size() > 1)
+  if (keys_.size() > 1 && composite_ && keys_.size() > kMaxKeyPairs)
+    evaluation_error("a join on " + std::to_string(keys_.size()) + " key pairs: composite keys on the device take 2 .. " +
+                     std::to_string(kMaxKeyPairs) + " pairs (TGX_CHECK_KEY_PROBE's tuple keys)");
+  if (keys_.size() > 1 && !composite_)
     evaluation_error("a join on " + std::to_string(keys_.size()) + " key pairs (" + left_ + "." + keys_[0].first + ", " +
                      left_ + "." + keys_[1].first + ", ..) is not on the GPU path: TGX_CHECK_KEY_PROBE takes one integer "
                      "key column");
@@ -218,16 +286,96 @@ ConstraintResult JoinCoverageConstraint::verdict(const JoinCoverageCounts &c) co
   if (max_examples_ > 0) {
     if (!c.examples_known)
       throw TermError{TermError::Internal, "join_coverage: a failing check with examples needs the left side's missing keys"};
-    const uint64_t found = c.missing_keys + (c.null_rows > 0 ? 1 : 0), n = std::min<uint64_t>(max_examples_, found);
+    // (composite keys: every distinct tuple with a NULL component is a value of its own)
+    const uint64_t null_values = c.null_keys_known ? c.null_keys : (c.null_rows > 0 ? 1 : 0);
+    const uint64_t found = c.missing_keys + null_values, n = std::min<uint64_t>(max_examples_, found);
     if (n > 0)
-      message += std::string(" (") + ((c.overflow_rows > 0 || c.long_rows > 0) && n < max_examples_ ? "at least " : "") + std::to_string(n) +
+      message += std::string(" (") + ((c.overflow_rows > 0 || c.long_rows > 0 || c.null_overflow_rows > 0) && n < max_examples_ ? "at least " : "") + std::to_string(n) +
                  " unmatched examples found)";
   }
   return ConstraintResult::failure_with_metric(rate, message);
 }
 
+// 2 .. 8 key pairs under the opt-in: the three walk patterns with the tuple calls
+ConstraintResult JoinCoverageConstraint::evaluate_composite(const Context &ctx) const {
+  std::vector<int32_t> lcols, rcols;
+  const Table *lt = nullptr, *rt = nullptr;
+  bool first_is_string = false;
+  for (size_t k = 0; k < keys_.size(); k++) {
+    const Side L = side_of(ctx, left_, keys_[k].first), R = side_of(ctx, right_, keys_[k].second);
+    lt = L.table;
+    rt = R.table;
+    // (a side without a batch has no type to object with: it goes the way of the other side)
+    const int ls = string_side(*L.table, L.column), rs = string_side(*R.table, R.column);
+    if (ls != 1) integer_side(L);  // (Float, UInt64 and Boolean columns: the wording of before)
+    if (rs != 1) integer_side(R);
+    if ((ls == 1 && rs == -1) || (ls == -1 && rs == 1))
+      evaluation_error("key pair " + std::to_string(k) + ": columns '" + L.qualified + "' and '" + R.qualified + "' are " +
+                       (ls == 1 ? "a string and an integer" : "an integer and a string") +
+                       " column: the two columns of a key pair are two integer columns or two string columns");
+    if (k == 0) first_is_string = ls == 1;
+    lcols.push_back(L.column);
+    rcols.push_back(R.column);
+  }
+  Walks w;
+  w.tuples = true;
+  w.check(tgx_init(nullptr, &w.check.err));
+
+  JoinCoverageCounts counts;
+  tgx_key_probe_summary s;
+  tgx_key_probe_pairs p;
+  tgx_key_probe_tuples more;
+  memset(&p, 0, sizeof(p));
+  auto note_examples = [&](const tgx_key_probe_summary &of_left, const tgx_key_probe_tuples &nulls) {
+    counts.examples_known = true;
+    counts.missing_keys = of_left.missing_keys;
+    counts.null_rows = of_left.null_rows;
+    counts.overflow_rows = of_left.overflow_rows;
+    counts.null_keys_known = true;
+    counts.null_keys = nulls.null_keys;
+    counts.null_overflow_rows = nulls.null_overflow_rows;
+  };
+  const void *records = nullptr, *left_records = nullptr;
+  uint64_t n_records = 0, n_left = 0;
+  Handles r_set, l_walk, r_walk, l_set, l_plain;
+  if (type_ != CoverageType::RightCoverage) {
+    const bool both = type_ == CoverageType::BidirectionalCoverage;
+    w.tuple_set(*rt, rcols, r_set, &records, &n_records);
+    w.tuple_probe(*lt, lcols, records, n_records, true, max_missing_keys_, l_walk, &s, &p, &more,
+                  !both && distinct_only_ ? &counts.left_distinct : nullptr, first_is_string,
+                  both ? &left_records : nullptr, &n_left);
+    counts.left.known = true;
+    counts.left.pairs = p.pairs;
+    counts.left.join_rows = p.join_rows;
+    note_examples(s, more);
+    if (both) {
+      w.tuple_probe(*rt, rcols, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, &more, nullptr, false,
+                    nullptr, nullptr);
+      counts.right.known = true;
+      counts.right.pairs = p.pairs;
+      counts.right.join_rows = p.join_rows;
+    }
+    return verdict(counts);
+  }
+  w.tuple_set(*lt, lcols, l_set, &left_records, &n_left);
+  w.tuple_probe(*rt, rcols, left_records, n_left, true, max_missing_keys_, r_walk, &s, &p, &more, nullptr, false, nullptr,
+                nullptr);
+  counts.right.known = true;
+  counts.right.pairs = p.pairs;
+  counts.right.join_rows = p.join_rows;
+  const bool fails = p.join_rows != 0 && !((double)p.pairs / (double)p.join_rows >= expected_);
+  if (fails && wants_examples()) {
+    w.tuple_set(*rt, rcols, r_set, &records, &n_records);
+    w.tuple_probe(*lt, lcols, records, n_records, false, max_missing_keys_, l_plain, &s, &p, &more, nullptr, false, nullptr,
+                  nullptr);
+    note_examples(s, more);
+  }
+  return verdict(counts);
+}
+
 ConstraintResult JoinCoverageConstraint::evaluate_context(const Context &ctx) const {
   validate();
+  if (keys_.size() > 1) return evaluate_composite(ctx);
   const Side L = side_of(ctx, left_, keys_[0].first), R = side_of(ctx, right_, keys_[0].second);
   // (a side without a batch has no type to object with: it goes the way of the other side)
   const int ls = string_side(*L.table, L.column), rs = string_side(*R.table, R.column);

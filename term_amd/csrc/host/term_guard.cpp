@@ -1792,7 +1792,8 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
   } else if (type == "join_coverage") {
     // {"type": "join_coverage", "left_table": "orders", "right_table": "customers", "join_keys": [["customer_id", "id"]],
     //  "expected_match_rate": 1.0, "coverage_type": "left" | "right" | "bidirectional", "distinct_only": false,
-    //  "max_examples_reported": 100, "max_missing_keys": 10000, "max_value_bytes": 256}
+    //  "max_examples_reported": 100, "max_missing_keys": 10000, "max_value_bytes": 256,
+    //  "composite_keys_on_device": true (optional, an opt-in: 2 .. 8 key pairs on the device)}
     auto x = std::make_shared<JoinCoverageConstraint>(c.get_str("left_table"), c.get_str("right_table"));
     std::vector<std::pair<std::string, std::string>> keys;
     if (const json::Value *kv = c.get("join_keys")) {
@@ -1818,6 +1819,7 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     if (c.get("max_value_bytes"))
       x->max_value_bytes((uint32_t)std::min<uint64_t>(
           c.get_u64("max_value_bytes", JoinCoverageConstraint::kDefaultMaxValueBytes), UINT32_MAX));
+    if (c.get("composite_keys_on_device")) x->composite_keys_on_device(c.get_bool("composite_keys_on_device"));
     b.constraint(std::move(x));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));

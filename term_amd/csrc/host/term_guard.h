@@ -383,6 +383,10 @@ struct JoinCoverageCounts {
   bool examples_known = false;
   uint64_t missing_keys = 0, null_rows = 0, overflow_rows = 0;
   uint64_t long_rows = 0;  // string keys: L's missing rows whose value is longer than max_value_bytes (not kept)
+  // composite keys: L's distinct tuples with a NULL component (each a distinct value of the examples query) and the
+  // rows of such tuples that found no slot; where they are not known the NULL rows count as ONE distinct value
+  bool null_keys_known = false;
+  uint64_t null_keys = 0, null_overflow_rows = 0;
 };
 class JoinCoverageConstraint : public Constraint {
  public:
@@ -410,6 +414,13 @@ class JoinCoverageConstraint : public Constraint {
   // this layer's own, string keys only, as ForeignKeyConstraint's: the bytes a missing key may have to be kept (1 .. 256).
   // Missing rows with a longer value are counted (long rows): the rate stands, the examples read "at least n"
   JoinCoverageConstraint &max_value_bytes(uint32_t n) { max_value_bytes_ = n; value_bytes_given_ = true; return *this; }
+  // this layer's own, an opt-in: a join on 2 .. 8 key pairs (on_multiple) runs on the device, each pair two integer or
+  // two string columns, under TGX_CHECK_KEY_PROBE's tuple modes (tgx_plan_set_key_probe_tuples*).  A row with a NULL in
+  // any key column joins nothing, and the examples are counted over fingerprints.  Off (the default), and with one key
+  // pair, everything is what it was
+  JoinCoverageConstraint &composite_keys_on_device(bool on) { composite_ = on; return *this; }
+  bool composite_keys() const { return composite_; }
+  static constexpr size_t kMaxKeyPairs = 8;
 
   const std::string &left_table() const { return left_; }
   const std::string &right_table() const { return right_; }
@@ -446,6 +457,8 @@ class JoinCoverageConstraint : public Constraint {
   uint32_t max_missing_keys_ = kDefaultMaxMissingKeys;
   uint32_t max_value_bytes_ = kDefaultMaxValueBytes;
   bool value_bytes_given_ = false;
+  bool composite_ = false;
+  ConstraintResult evaluate_composite(const Context &ctx) const;  // (2 .. 8 key pairs, the opt-in given)
 };
 
 // ---- core/check.rs

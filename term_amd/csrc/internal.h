@@ -258,7 +258,7 @@ struct GroupSumsTask {
   tgx_group_sums_params params;
 };
 
-// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once one of the six tgx_plan_set_key_probe* calls
+// TGX_CHECK_KEY_PROBE (keyprobe_device.cpp): one task per spec; `set` once one of the nine tgx_plan_set_key_probe* calls
 // was made, which gives the task its mode for good.  (The parent's key set belongs to a state, not to the plan:
 // tgx_key_probe_set_parent)
 //   kKpPlain     tgx_plan_set_key_probe: is each integer key in the set?
@@ -268,18 +268,30 @@ struct GroupSumsTask {
 //   kKpRows      tgx_plan_set_key_probe_rows: the task gathers its column as {key, 1} records and probes nothing
 //   kKpStringsCounted  tgx_plan_set_key_probe_strings_counted: a strings task whose set keeps the parent's multiplicities
 //   kKpRowsStrings     tgx_plan_set_key_probe_rows_strings: the task gathers its string column as {fa, fb, n, 0} records
+//   kKpTuples          tgx_plan_set_key_probe_tuples: the spec has a column list; a row's key is the tuple of its
+//                      components, the set holds tuple fingerprints, and so do the entries (no bytes are kept)
+//   kKpTuplesCounted   tgx_plan_set_key_probe_tuples_counted: a tuples task whose set keeps the parent's multiplicities
+//   kKpRowsTuples      tgx_plan_set_key_probe_rows_tuples: the task gathers its all-valid tuples as {fa, fb, 1, 0} records
 // Those that probe are a blob's mode word; a task that gathers holds nothing by the time its state may be serialized.
 enum KeyProbeMode : uint32_t {
-  kKpPlain = 0, kKpCounted = 1, kKpStrings = 2, kKpRows = 3, kKpStringsCounted = 4, kKpRowsStrings = 5
+  kKpPlain = 0, kKpCounted = 1, kKpStrings = 2, kKpRows = 3, kKpStringsCounted = 4, kKpRowsStrings = 5,
+  kKpTuples = 6, kKpTuplesCounted = 7, kKpRowsTuples = 8
 };
 // what the modes have in common: the set is of fingerprints; the set keeps counts (and the task sums `pairs`); the task
-// gathers and probes nothing; the column is a string column
+// gathers and probes nothing; the column is a string column; the task reads a column list; the set is built from
+// 32-byte records of fingerprints (routes 5 and 6)
 inline bool kp_string_set(KeyProbeMode m) { return m == kKpStrings || m == kKpStringsCounted; }
-inline bool kp_counts(KeyProbeMode m) { return m == kKpCounted || m == kKpStringsCounted; }
-inline bool kp_gathers(KeyProbeMode m) { return m == kKpRows || m == kKpRowsStrings; }
+inline bool kp_counts(KeyProbeMode m) { return m == kKpCounted || m == kKpStringsCounted || m == kKpTuplesCounted; }
+inline bool kp_gathers(KeyProbeMode m) { return m == kKpRows || m == kKpRowsStrings || m == kKpRowsTuples; }
 inline bool kp_string_column(KeyProbeMode m) { return kp_string_set(m) || m == kKpRowsStrings; }
+inline bool kp_tuples(KeyProbeMode m) { return m == kKpTuples || m == kKpTuplesCounted || m == kKpRowsTuples; }
+inline bool kp_tuple_set(KeyProbeMode m) { return m == kKpTuples || m == kKpTuplesCounted; }
+inline bool kp_fingerprint_set(KeyProbeMode m) { return kp_string_set(m) || kp_tuple_set(m); }
+constexpr int kKeyProbeMaxTuple = 8;  // (kMaxTupleCols: the arities tuple_fingerprint is made for)
 struct KeyProbeTask {
   int column, spec_index;
+  int n_tuple;                   // the spec's column list: 2 .. 8 columns, or 0: the spec reads `column`
+  int tuple[kKeyProbeMaxTuple];  // (tuple[0] == column)
   bool set;
   KeyProbeMode mode;
   uint32_t max_value_bytes;  // a strings or counted strings task's; 0 otherwise

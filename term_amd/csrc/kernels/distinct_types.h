@@ -215,5 +215,11 @@ struct TupleDesc {
   int64_t length;
   FpKey key;
 };
+// a tuple of child columns as the key probe walks it (keyprobe_tuples.hip): per component of kind 4 also the entries of
+// its dictionary -- a row whose index lies outside is a NULL component there, not a read
+struct KeyProbeTupleDesc {
+  TupleDesc d;
+  int64_t dict_length[kMaxTupleCols];
+};
 
 }  // namespace tgx

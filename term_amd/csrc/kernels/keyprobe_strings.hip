@@ -43,40 +43,13 @@
 #include "device_types.h"
 #include "dict_count.h"
 #include "fingerprint.h"
+#include "keyprobe_set.h"
 
 namespace tgx {
 
 namespace {
 
-// the slot of (fa, fb) in the set's table, or -1: it is not in the set.  (Routes 5 and 6)
-template <class Set>
-__device__ __forceinline__ int64_t kps_find(const Set &s, unsigned long long fa, unsigned long long fb) {
-  if (!s.slots) return -1;
-  const ulonglong2 *slots = (const ulonglong2 *)s.slots;
-  uint64_t h = fa & s.mask;
-  for (uint64_t p = 0; p <= s.mask; p++) {
-    const ulonglong2 e = slots[h];  // (one 16-byte load: both words)
-    if (e.x == fa && e.y == fb) return (int64_t)h;
-    if (e.x == kEmptyKey) return -1;
-    h = (h + 1) & s.mask;
-  }
-  return -1;
-}
-
-// how often the value of slot `at` occurs in the parent: a plain set does not say
-__device__ __forceinline__ unsigned long long kps_times(const KeyProbeStringSet &, int64_t) { return 1; }
-__device__ __forceinline__ unsigned long long kps_times(const KeyProbeCountedStringSet &s, int64_t at) {
-  return s.counts[at];
-}
-template <class Set>
-struct KpsCounted {
-  static constexpr bool value = false;
-};
-template <>
-struct KpsCounted<KeyProbeCountedStringSet> {
-  static constexpr bool value = true;
-};
-
+// (kps_find, kps_times and KpsCounted, the lookup in routes 5 and 6: keyprobe_set.h, shared with keyprobe_tuples.hip)
 // the build's claim of (fa, fb), neither word the marker: fa by CAS, then fb by CAS (count_table.h's order).  The slot
 // that holds the fingerprint, or -1 (a table without a free slot: cannot happen at load <= 0.5); *made: this call made
 // the entry.  (Routes 5 and 6)

@@ -27,6 +27,13 @@
 // identity is the counted one, its blob carries the counted tail and the strings tail.  A ROWS STRINGS task
 // (tgx_plan_set_key_probe_rows_strings) gathers a string column as 32-byte {fa, fb, n, 0} records, what such a set is
 // built from: a record a non-NULL row, or, a dictionary batch, a record per entry its rows refer to, with their number.
+// A TUPLES task (tgx_plan_set_key_probe_tuples*; kernels/keyprobe_tuples.hip) reads the 2 .. 8 columns of its spec's list
+// as ONE key, the tuple's keyed fingerprint, against routes 5 and 6; a row with a NULL component matches nothing (SQL's
+// join) and is no non-NULL row.  Its table keeps fingerprints only, in the strings layout with one byte of value a slot
+// whose LENGTH is the flag "a NULL-bearing tuple"; on the host an entry's key is 17 bytes -- hash_a and hash_b big-endian,
+// then the flag -- so KeyedEntries::strs holds the entries ascending by (hash_a, hash_b), and merges, blobs and the
+// cross-rank step unite them as they unite a strings task's.  The NULL-bearing rows that found no slot are counted in
+// kKpLong's word (a tuple has no long rows).
 // `pairs` never wraps: the host holds an upper bound, max_count * rows a batch, in checked arithmetic, and refuses the
 // batch, merge or blob that could carry it past 2^64 - 1.
 // The host part is a map from missing key to count plus the same counters and the identity of the set they were taken
@@ -74,6 +81,13 @@ void launch_key_probe_rows_dict(const int32_t *indices, const uint8_t *validity,
                                 const Utf8ColDesc &dict, unsigned long long *cells, unsigned long long *recs, uint64_t cap,
                                 unsigned long long *words, hipStream_t stream);
 
+void launch_key_probe_tuples(const KeyProbeTupleDesc &L, bool numeric, const KeyProbeStringSet &set,
+                             const ValueCountsTable &t, hipStream_t stream);
+void launch_key_probe_tuples_counted(const KeyProbeTupleDesc &L, bool numeric, const KeyProbeCountedStringSet &set,
+                                     const ValueCountsTable &t, hipStream_t stream);
+void launch_key_probe_rows_tuples(const KeyProbeTupleDesc &L, bool numeric, unsigned long long *recs, uint64_t cap,
+                                  unsigned long long *words, hipStream_t stream);
+
 namespace {
 
 constexpr uint64_t kMaxParentRecords = (uint64_t)1 << 40;
@@ -88,6 +102,7 @@ struct ProbeHost : KeyedEntries<uint64_t> {
   uint64_t parent_rows = 0, parent_count_digest = 0, max_count = 0, pairs = 0;
   uint64_t long_rows = 0;  // a strings task: missing rows whose value is longer than max_value_bytes
   uint64_t gathered = 0;   // a task that gathers: the records it has written
+  uint64_t null_overflow_rows = 0;  // a tuples task: rows with a NULL component whose tuple found no slot
   bool holds_counts() const { return seen != 0 || size() != 0; }
   bool same_parent(const ProbeHost &o) const {
     return parent_keys == o.parent_keys && parent_digest == o.parent_digest && parent_rows == o.parent_rows &&
@@ -102,6 +117,44 @@ struct ProbeHost : KeyedEntries<uint64_t> {
     max_count = o.max_count;
   }
 };
+
+// ---- a tuples task's entries: the key of KeyedEntries::strs is hash_a, hash_b (big-endian: bytewise order is the order
+// of the pair) and one byte, 1 for a tuple with a NULL component ----
+constexpr uint32_t kTupleEntryBytes = 17;
+inline std::string tuple_entry_key(uint64_t fa, uint64_t fb, bool has_null) {
+  std::string k(kTupleEntryBytes, '\0');
+  for (int i = 0; i < 8; i++) {
+    k[i] = (char)(uint8_t)(fa >> (56 - 8 * i));
+    k[8 + i] = (char)(uint8_t)(fb >> (56 - 8 * i));
+  }
+  k[16] = has_null ? 1 : 0;
+  return k;
+}
+inline tgx_key_probe_tuple_entry tuple_entry_of(const std::string &k, uint64_t count) {
+  tgx_key_probe_tuple_entry e;
+  memset(&e, 0, sizeof(e));
+  for (int i = 0; i < 8; i++) {
+    e.hash_a = (e.hash_a << 8) | (uint8_t)k[i];
+    e.hash_b = (e.hash_b << 8) | (uint8_t)k[8 + i];
+  }
+  e.count = count;
+  e.has_null = (uint8_t)k[16];
+  return e;
+}
+// the two classes of a tuples task's entries
+struct TupleClasses {
+  uint64_t missing_keys = 0, missing_counted = 0, null_keys = 0, null_counted = 0;
+};
+template <class Entries>
+inline TupleClasses tuple_classes(const Entries &h) {
+  TupleClasses c;
+  for (const auto &e : h.strs) {
+    const bool has_null = e.first.size() == kTupleEntryBytes && e.first[16] != 0;
+    (has_null ? c.null_keys : c.missing_keys) += 1;
+    (has_null ? c.null_counted : c.missing_counted) += e.second;
+  }
+  return c;
+}
 
 // a + b, or false: the sum is past 2^64 - 1
 inline bool add_fits(uint64_t a, uint64_t b, uint64_t *sum) { return !__builtin_add_overflow(a, b, sum); }
@@ -122,8 +175,11 @@ struct ProbeKind {
 
   static const std::vector<KeyProbeTask> &tasks(const tgx_plan *plan) { return plan->key_probes; }
   static size_t words(const KeyProbeTask &) { return kKeyProbeWords; }
-  static uint32_t bound(const KeyProbeTask &t) { return t.params.max_missing_keys; }
-  static uint32_t max_value_bytes(const KeyProbeTask &t) { return t.max_value_bytes; }
+  // (a tuples task: one allocation whose lower half is the missing tuples' table and whose upper half is the
+  // NULL-bearing tuples': max_missing_keys bounds each class as it bounds the one class of the other modes)
+  static uint32_t bound(const KeyProbeTask &t) { return (kp_tuples(t.mode) ? 2u : 1u) * t.params.max_missing_keys; }
+  // (a tuples task: the one byte a slot whose length is the flag of a NULL-bearing tuple)
+  static uint32_t max_value_bytes(const KeyProbeTask &t) { return kp_tuples(t.mode) ? 1u : t.max_value_bytes; }
   static NoRange range_identity() { return NoRange(); }
   static ProbeHost fresh(const KeyProbeTask &) { return ProbeHost(); }
   static size_t shape(const ProbeHost &) { return 0; }  // (the sets' identities: ProbeCheck::merge_from)
@@ -136,9 +192,13 @@ struct ProbeKind {
     d.overflow_rows = w[kKpOverflow];
     d.pairs = w[kKpPairs];
     if (t.mode == kKpRows) d.gathered = d.non_null;
-    if (t.mode == kKpRowsStrings) {  // (its cursor stands in the pairs' word)
+    if (t.mode == kKpRowsStrings || t.mode == kKpRowsTuples) {  // (its cursor stands in the pairs' word)
       d.gathered = w[kKpPairs];
       d.pairs = 0;
+      return d;
+    }
+    if (kp_tuple_set(t.mode)) {  // (no tuple is long: the word counts the NULL-bearing rows that found no slot)
+      d.null_overflow_rows = w[kKpLong];
       return d;
     }
     if (kp_string_set(t.mode)) {  // (no string has the marker's bits)
@@ -157,6 +217,7 @@ struct ProbeKind {
     a.matched += b.matched;
     a.overflow_rows += b.overflow_rows;
     a.long_rows += b.long_rows;
+    a.null_overflow_rows += b.null_overflow_rows;
     a.gathered += b.gathered;
     a.pairs += b.pairs;  // (the callers have held the sum against 2^64 - 1: ProbeCheck::pairs_fit)
     a.add_entries(b);
@@ -172,6 +233,9 @@ struct ProbeKind {
   // entries, and an entry is { u32 length, u8 bytes[length], u64 count }, ascending bytewise
   // a counted strings task: the second u32 0 is 4, and the counted task's four words, then the strings task's
   // { u32 max_value_bytes, u32 0, u64 long_rows }, stand between n_entries and the entries, which are a strings task's
+  // a tuples task: the second u32 0 is 6 (counted: 7, and the counted task's four words come first);
+  // { u32 arity, u32 0, u64 null_overflow_rows } stand between n_entries and the entries, and an entry is a strings
+  // task's with the 17 bytes { hash_a, hash_b big-endian, u8 has_null }
   // (the mode word is the task's mode; a task that gathers, whose state serializes only while it is empty, writes a
   // plain one's)
   static uint32_t mode_word(const KeyProbeTask &t) { return kp_gathers(t.mode) ? (uint32_t)kKpPlain : (uint32_t)t.mode; }
@@ -190,6 +254,11 @@ struct ProbeKind {
       w.pod((uint32_t)0);
       w.pod(h.long_rows);
     }
+    if (kp_tuple_set(t.mode)) {
+      w.pod((uint32_t)t.n_tuple);
+      w.pod((uint32_t)0);
+      w.pod(h.null_overflow_rows);
+    }
     keyed_write_entries(h, CountWire(), w);
   }
 
@@ -200,11 +269,13 @@ struct ProbeKind {
     uint64_t words[7], more[4] = {0, 0, 0, 0};
     r.get(words, sizeof(words));
     if (!r.ok) return TGX_OK;
-    const bool counted = kp_counts(t.mode), strings = kp_string_set(t.mode);
+    const bool counted = kp_counts(t.mode), strings = kp_string_set(t.mode), tuples = kp_tuple_set(t.mode);
     if (pad != mode_word(t)) {
-      const bool is_mode = pad <= kKpStrings || pad == kKpStringsCounted;
+      const bool is_mode = pad <= kKpStrings || pad == kKpStringsCounted || pad == kKpTuples || pad == kKpTuplesCounted;
       return fail(err, TGX_INVALID_ARGUMENT,
                   !is_mode ? "malformed state blob (KEY_PROBE task %zu: parent set)"
+                  : (is_mode && kp_tuple_set((KeyProbeMode)pad)) != tuples
+                      ? "KEY_PROBE task %zu: the blob was counted under the other mode (single / tuple keys) than the plan's"
                   : (is_mode && kp_string_set((KeyProbeMode)pad)) != strings
                       ? "KEY_PROBE task %zu: the blob was counted under the other mode (integer / string keys) than the plan's"
                       : "KEY_PROBE task %zu: the blob was counted under the other mode (plain / counted) than the plan's",
@@ -218,7 +289,20 @@ struct ProbeKind {
       value_pad = r.pod<uint32_t>();
       long_rows = r.pod<uint64_t>();
     }
+    uint32_t arity = 0;
+    uint64_t null_overflow = 0;
+    if (tuples) {
+      arity = r.pod<uint32_t>();
+      value_pad = r.pod<uint32_t>();
+      null_overflow = r.pod<uint64_t>();
+    }
     if (!r.ok) return TGX_OK;
+    if (tuples && value_pad != 0)
+      return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: tuple keys)", k);
+    if (tuples && arity != (uint32_t)t.n_tuple)
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "KEY_PROBE task %zu: the blob was counted over tuples of %u columns, the plan's have %d", k, arity,
+                  t.n_tuple);
     if (strings && value_pad != 0)
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: string keys)", k);
     if (strings && value_bytes != t.max_value_bytes)
@@ -231,7 +315,7 @@ struct ProbeKind {
                   "(%u)", k, p.max_missing_keys, t.params.max_missing_keys);
     const uint64_t seen = words[2], non_null = words[3], n = words[6];
     if (known > 1 || (!known && (words[0] != 0 || words[1] != 0 || seen != 0 || n != 0 || more[0] != 0 || more[1] != 0 ||
-                                 more[2] != 0 || more[3] != 0 || long_rows != 0)))
+                                 more[2] != 0 || more[3] != 0 || long_rows != 0 || null_overflow != 0)))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: parent set)", k);
     // a counted set: keys <= rows < 2^63, the largest count is one of them; matched <= pairs <= matched * max_count
     if (counted) {
@@ -243,16 +327,28 @@ struct ProbeKind {
         return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: counted set and pairs)", k);
     }
     uint64_t in_entries = 0;
-    TGX_TRY(keyed_read_entries("KEY_PROBE", kNoun, k, r, strings ? kByteKeys : kIntKeys, n, t.max_value_bytes,
-                               CountWire(), h, &in_entries, err));
+    TGX_TRY(keyed_read_entries("KEY_PROBE", kNoun, k, r, strings || tuples ? kByteKeys : kIntKeys, n,
+                               tuples ? kTupleEntryBytes : t.max_value_bytes, CountWire(), h, &in_entries, err));
     if (!r.ok) return TGX_OK;
+    if (tuples) {
+      // an entry is 17 bytes whose last is the flag; null_counted + null_overflow_rows == seen - non_null
+      for (const auto &e : h.strs)
+        if (e.first.size() != kTupleEntryBytes || (uint8_t)e.first[16] > 1)
+          return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (KEY_PROBE task %zu: a tuple entry)", k);
+      const TupleClasses c = tuple_classes(h);
+      if (non_null > seen || !terms_make(seen - non_null, {c.null_counted, null_overflow}))
+        return fail(err, TGX_INVALID_ARGUMENT,
+                    "malformed state blob (KEY_PROBE task %zu: null_counted + null_overflow_rows != null_rows)", k);
+      in_entries = c.missing_counted;
+    }
     // matched + counted + overflow_rows (+ long_rows) == non_null <= seen
     if (non_null > seen || !terms_make(non_null, {words[4], in_entries, words[5], long_rows}))
       return fail(err, TGX_INVALID_ARGUMENT,
                   "malformed state blob (KEY_PROBE task %zu: matched + counted + overflow_rows%s != non_null)", k,
                   strings ? " + long_rows" : "");
-    h.kind = !n ? kNoKeys : strings ? kByteKeys : kIntKeys;
+    h.kind = !n ? kNoKeys : strings || tuples ? kByteKeys : kIntKeys;
     h.long_rows = long_rows;
+    h.null_overflow_rows = null_overflow;
     h.known = known != 0;
     h.parent_keys = words[0];
     h.parent_digest = words[1];
@@ -279,9 +375,13 @@ constexpr ModeInfo kModes[] = {{"plain", "", 16},
                                {"to probe string keys", "_strings", 32},
                                {"to gather rows", "_rows", 16},
                                {"to probe string keys, counted", "_strings_counted", 32},
-                               {"to gather the rows of a string column", "_rows_strings", 32}};
+                               {"to gather the rows of a string column", "_rows_strings", 32},
+                               {"to probe tuple keys", "_tuples", 32},
+                               {"to probe tuple keys, counted", "_tuples_counted", 32},
+                               {"to gather the tuples of its columns", "_rows_tuples", 32}};
 static_assert(kKpPlain == 0 && kKpCounted == 1 && kKpStrings == 2 && kKpRows == 3 && kKpStringsCounted == 4 &&
-                  kKpRowsStrings == 5, "kModes is indexed by the mode");
+                  kKpRowsStrings == 5 && kKpTuples == 6 && kKpTuplesCounted == 7 && kKpRowsTuples == 8,
+              "kModes is indexed by the mode");
 
 // the set of one task on the device
 struct ParentSet {
@@ -328,8 +428,8 @@ struct ParentSet {
 // the route of a set of `n` > 0 records of a task of `mode`, whose keys span `range` (0: all of int64, which is not dense).
 // A dense set is no larger than the table would be: a bit a key up to 128 * n, a count a key up to 4 * n
 int choose_route(KeyProbeMode mode, uint64_t range, uint64_t n) {
-  if (mode == kKpStrings) return kKpRouteStrings;
-  if (mode == kKpStringsCounted) return kKpRouteStringsCounted;
+  if (mode == kKpStrings || mode == kKpTuples) return kKpRouteStrings;
+  if (mode == kKpStringsCounted || mode == kKpTuplesCounted) return kKpRouteStringsCounted;
   const bool counted = mode == kKpCounted;
   const bool dense = range != 0 && range <= (counted ? 4 : 128) * n;
   return counted ? (dense ? kKpRouteCountArray : kKpRouteCountHash) : (dense ? kKpRouteBitmap : kKpRouteHash);
@@ -350,6 +450,16 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
         gathered_cap(tasks.size(), 0) {}
 
   uint64_t slot_payload(size_t, const uint8_t *, uint64_t, uint64_t count) const override { return count; }
+
+  // a tuples task's slot: the fingerprint and the flag are the key, the slot's length is the flag
+  void decode_slot(size_t k, const uint8_t *h, uint64_t s, uint64_t count, ProbeHost &o) const override {
+    if (!kp_tuples(tasks[k].mode)) return KeyedCheck::decode_slot(k, h, s, count, o);
+    const uint64_t *keys = (const uint64_t *)h;
+    const uint64_t fb = keys[table[k].slots + s];
+    if (fb == kEmptyKey) return;  // (claimed, not settled: nothing was counted into it yet)
+    if (o.kind == kNoKeys) o.kind = kByteKeys;
+    o.strs[tuple_entry_key(keys[s], fb, ((const uint32_t *)(h + lens_at(k)))[s] != 0)] += count;
+  }
 
   // a state that has gathered rows keeps them to itself
   tgx_status rows_stay(const char *what, tgx_error *err) const {
@@ -575,9 +685,9 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     s.has = true;
     if (n > 0) {  // (without records: the empty set, route 0)
       ProfScope ps(st, "key_probe_build", n * kModes[mode].record_bytes);
-      TGX_TRY(mode == kKpStrings          ? build_strings(st, k, recs, n, &s, err)
-              : mode == kKpStringsCounted ? build_strings_counted(st, k, recs, n, &s, err)
-                                          : build_integers(st, k, recs, n, &s, err));
+      TGX_TRY(mode == kKpStrings || mode == kKpTuples                 ? build_strings(st, k, recs, n, &s, err)
+              : mode == kKpStringsCounted || mode == kKpTuplesCounted ? build_strings_counted(st, k, recs, n, &s, err)
+                                                                      : build_integers(st, k, recs, n, &s, err));
     }
     ProbeHost &h = host[k];
     ProbeHost given;
@@ -613,6 +723,10 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     for (size_t k = 0; k < tasks.size(); k++) {
       const tgx_column &x = dev[tasks[k].column];
       const Route route = route_of(x);
+      if (kp_tuples(tasks[k].mode)) {  // (its columns: walk_tuples)
+        if (tasks[k].mode != kKpRowsTuples) TGX_TRY(ensure_keys(st, k, kByteKeys, 0, err));
+        continue;
+      }
       if (kp_string_column(tasks[k].mode)) {
         if (route != kStringRoute && route != kDictRoute)
           return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on string keys takes string columns (%d)", x.type);
@@ -651,6 +765,8 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     }
     for (size_t k = 0; k < tasks.size(); k++)
       if (kp_string_set(tasks[k].mode)) TGX_TRY(probe_strings(st, k, dev[tasks[k].column], nrows, err));
+    for (size_t k = 0; k < tasks.size(); k++)
+      if (kp_tuples(tasks[k].mode)) TGX_TRY(walk_tuples(st, k, dev, nrows, err));
     for (size_t k = 0; k < tasks.size(); k++) device_rows[k] += nrows;
     return TGX_OK;
   }
@@ -686,6 +802,88 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
         else
           launch_key_probe_dict((const int32_t *)x.values, x.validity, x.offset, x.length, d, cells, set, t, st->stream);
       }
+    }
+    HIP_TRY(hipGetLastError());
+    return TGX_OK;
+  }
+
+  // the columns of tuples task k as the kernels take them (update_validate has refused floats, UInt64 and Booleans,
+  // and the staging has widened every integer column to 8 bytes); *numeric: every component is an integer column
+  tgx_status tuple_desc(tgx_state *st, size_t k, const tgx_column *dev, KeyProbeTupleDesc *L, bool *numeric,
+                        tgx_error *err) {
+    const KeyProbeTask &task = tasks[k];
+    memset(L, 0, sizeof(*L));
+    L->d.n_cols = task.n_tuple;
+    L->d.length = dev[task.tuple[0]].length;
+    L->d.key = st->plan->fp_key;
+    *numeric = true;
+    for (int c = 0; c < task.n_tuple; c++) {
+      const tgx_column &x = dev[task.tuple[c]];
+      TupleCol &tc = L->d.cols[c];
+      tc.validity = x.validity;
+      tc.offset = x.offset;
+      switch (route_of(x)) {
+        case kIntRoute:
+          tc.kind = 0;
+          tc.values = x.values;
+          break;
+        case kStringRoute:
+          tc.kind = x.type == TGX_UTF8 ? 1 : x.type == TGX_LARGE_UTF8 ? 2 : 3;
+          tc.values = x.type == TGX_UTF8_VIEW ? x.values : nullptr;
+          tc.buffers = x.type == TGX_UTF8_VIEW ? x.variadic : nullptr;
+          tc.offsets = x.offsets;
+          tc.data = x.data;
+          *numeric = false;
+          break;
+        case kDictRoute: {
+          const tgx_column *dc;
+          TGX_TRY(dictionary_of(x, &dc, err));
+          tc.kind = 4;
+          tc.dict_large = dc->type == TGX_LARGE_UTF8 ? 1 : 0;
+          tc.values = x.values;
+          tc.offsets = dc->offsets;
+          tc.data = dc->data;
+          tc.dict_validity = dc->validity;
+          tc.dict_offset = dc->offset;
+          L->dict_length[c] = dc->length;
+          *numeric = false;
+          break;
+        }
+        default:
+          return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on tuple keys takes integer and string columns (%d)", x.type);
+      }
+    }
+    return TGX_OK;
+  }
+
+  // one batch of tuples task k: the probe against its set, or the gather of its all-valid tuples
+  tgx_status walk_tuples(tgx_state *st, size_t k, const tgx_column *dev, int64_t nrows, tgx_error *err) {
+    KeyProbeTupleDesc L;
+    bool numeric = true;
+    TGX_TRY(tuple_desc(st, k, dev, &L, &numeric, err));
+    // (per-lane and LDS counters are 32-bit: the launchers take up to 2048 workgroups)
+    TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
+    unsigned long long *words = d_counts.as<unsigned long long>() + word_off[k];
+    // what the walk reads: 8 bytes a row of an integer component (a string component's bytes are not known here: its
+    // offsets or indices at the least) and a bit of validity where there is a bitmap
+    uint64_t bytes = 0;
+    for (int c = 0; c < L.d.n_cols; c++)
+      bytes += (uint64_t)nrows * (L.d.cols[c].kind == 0 || L.d.cols[c].kind == 2 ? 8 : L.d.cols[c].kind == 3 ? 16 : 4) +
+               (L.d.cols[c].validity ? (uint64_t)(nrows + 7) / 8 : 0);
+    if (tasks[k].mode == kKpRowsTuples) {
+      TGX_TRY(gather_room(st, k, nrows, err));
+      ProfScope ps(st, "key_probe_rows", bytes + (uint64_t)nrows * 32);
+      launch_key_probe_rows_tuples(L, numeric, gathered[k].as<unsigned long long>(), gathered_cap[k], words, st->stream);
+    } else {
+      ValueCountsTable t;
+      fill_view(st, k, t);
+      t.counts = (unsigned long long *)(table[k].buf.as<uint8_t>() + table[k].counts_at());
+      t.words = words;
+      ProfScope ps(st, "key_probe", bytes);
+      if (tasks[k].mode == kKpTuplesCounted)
+        launch_key_probe_tuples_counted(L, numeric, parent[k].counted_string_view(), t, st->stream);
+      else
+        launch_key_probe_tuples(L, numeric, parent[k].string_view(), t, st->stream);
     }
     HIP_TRY(hipGetLastError());
     return TGX_OK;
@@ -793,7 +991,7 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     const ProbeHost &h = g[(size_t)slot];
     r->total = (int64_t)h.seen;
     r->non_null = (int64_t)h.non_null;
-    r->distinct = (int64_t)h.size();
+    r->distinct = (int64_t)(kp_tuples(tasks[(size_t)slot].mode) ? tuple_classes(h).missing_keys : h.size());
     r->matches = (int64_t)h.matched;
     return TGX_OK;
   }
@@ -837,15 +1035,32 @@ tgx_status keyprobe_plan_ready(const tgx_plan *plan, tgx_error *err) {
 }
 
 void keyprobe_mark_columns(tgx_plan *plan) {
-  for (const KeyProbeTask &t : plan->key_probes) side_mark(plan, ProbeCheck::kIndex, t.column, true);
+  for (const KeyProbeTask &t : plan->key_probes) {
+    side_mark(plan, ProbeCheck::kIndex, t.column, true);
+    for (int c = 0; c < t.n_tuple; c++) side_mark(plan, ProbeCheck::kIndex, t.tuple[c], true);
+  }
 }
 
 tgx_status keyprobe_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err) {
   const int type = c.type;
   // a strings task takes the string layouts and nothing else; every other task refuses them (below)
-  bool strings = false, others = false;
-  for (const KeyProbeTask &t : plan->key_probes)
+  // a tuples task takes both, component by component
+  bool strings = false, others = false, in_tuple = false;
+  for (const KeyProbeTask &t : plan->key_probes) {
+    if (t.n_tuple) {
+      for (int c = 0; c < t.n_tuple; c++) in_tuple |= t.tuple[c] == column;
+      continue;
+    }
     if (t.column == column) (kp_string_column(t.mode) ? strings : others) = true;
+  }
+  if (in_tuple) {
+    if (refused_as_key(type))
+      return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE on tuple keys takes integer and string columns, not %s "
+                  "(type %d)", column, type_name(type), type);
+    if (!is_any_string(type) && type != TGX_DICT32_UTF8 && c.length > 0 && !c.values)
+      return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE reads the keys: a validity-only column has none", column);
+    if (!strings && !others) return TGX_OK;
+  }
   if (strings && !is_any_string(type) && type != TGX_DICT32_UTF8)
     return fail(err, TGX_UNSUPPORTED, "column %d: KEY_PROBE on string keys takes string columns, not %s (type %d)", column,
                 refused_as_key(type) ? type_name(type) : "integers", type);
@@ -864,7 +1079,7 @@ bool keyprobe_blob_keyed(tgx_state *st) {
   ProbeCheck *c = static_cast<ProbeCheck *>(ProbeCheck::of(st));
   if (!c) return false;
   for (size_t k = 0; k < c->tasks.size(); k++)
-    if (kp_string_set(c->tasks[k].mode) &&
+    if (kp_fingerprint_set(c->tasks[k].mode) &&
         ((c->parent[k].has && c->parent[k].keys != 0) || (c->host[k].known && c->host[k].parent_keys != 0)))
       return true;
   return false;
@@ -877,7 +1092,7 @@ SideCheck *keyprobe_state_new(const tgx_plan *plan) { return plan->key_probes.em
 using namespace tgx;
 
 namespace {
-// The six tgx_plan_set_key_probe* calls: `p` is the call's parameters (a spec that gathers has none to give: its own),
+// The nine tgx_plan_set_key_probe* calls: `p` is the call's parameters (a spec that gathers has none to give: its own),
 // `max_value_bytes` a strings or counted strings spec's.  (A spec keeps the mode of its first call: a call of another mode is refused)
 tgx_status plan_set_mode(tgx_plan *plan, size_t spec_index, KeyProbeMode mode, const tgx_key_probe_params *p,
                          uint32_t max_value_bytes, tgx_error *err) {
@@ -894,6 +1109,12 @@ tgx_status plan_set_mode(tgx_plan *plan, size_t spec_index, KeyProbeMode mode, c
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: max_value_bytes must be 1 .. %d (%u)", spec_index,
                 (int)TGX_KEY_PROBE_MAX_VALUE_BYTES, max_value_bytes);
   KeyProbeTask &t = plan->key_probes[slot];
+  if (kp_tuples(mode) && !t.n_tuple)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: tgx_plan_set_key_probe%s needs a spec with a column list "
+                "(columns / n_columns of 2 .. %d)", spec_index, kModes[mode].suffix, kKeyProbeMaxTuple);
+  if (!kp_tuples(mode) && t.n_tuple)
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the spec has a column list: it is set with "
+                "tgx_plan_set_key_probe_tuples, _tuples_counted or _rows_tuples", spec_index);
   if (t.set && t.mode != mode)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the check has been set %s (tgx_plan_set_key_probe%s)", spec_index,
                 kModes[t.mode].set_as, kModes[t.mode].suffix);
@@ -952,6 +1173,68 @@ extern "C" tgx_status tgx_plan_set_key_probe_strings_counted(tgx_plan *plan, siz
 extern "C" tgx_status tgx_plan_set_key_probe_rows_strings(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
   const tgx_key_probe_params own = {1, 0};
   return plan_set_mode(plan, spec_index, kKpRowsStrings, &own, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_tuples(tgx_plan *plan, size_t spec_index, const tgx_key_probe_params *p,
+                                                    tgx_error *err) try {
+  return plan_set_mode(plan, spec_index, kKpTuples, p, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_tuples_counted(tgx_plan *plan, size_t spec_index,
+                                                            const tgx_key_probe_params *p, tgx_error *err) try {
+  return plan_set_mode(plan, spec_index, kKpTuplesCounted, p, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_plan_set_key_probe_rows_tuples(tgx_plan *plan, size_t spec_index, tgx_error *err) try {
+  const tgx_key_probe_params own = {1, 0};
+  return plan_set_mode(plan, spec_index, kKpRowsTuples, &own, 0, err);
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_tuples_get(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                               tgx_key_probe_tuples *out, tgx_error *err) try {
+  bind_thread();
+  if (!out) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  const KeyProbeTask &t = task_of(plan, spec_index);
+  if (!kp_tuples(t.mode))
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not read tuple keys "
+                "(tgx_plan_set_key_probe_tuples)", spec_index);
+  const TupleClasses c = tuple_classes(h);
+  memset(out, 0, sizeof(*out));
+  out->null_counted = c.null_counted;
+  out->null_overflow_rows = h.null_overflow_rows;
+  out->null_keys = c.null_keys;
+  out->arity = (uint32_t)t.n_tuple;
+  return TGX_OK;
+} catch (...) {
+  return tgx::abi_exception(err);
+}
+
+extern "C" tgx_status tgx_key_probe_entries_tuples(const tgx_plan *plan, tgx_state *st, size_t spec_index,
+                                                   tgx_key_probe_tuple_entry *entries, uint64_t cap,
+                                                   uint64_t *n_entries, tgx_error *err) try {
+  bind_thread();
+  if (!n_entries) return fail(err, TGX_INVALID_ARGUMENT, "bad arguments");
+  ProbeHost h;
+  TGX_TRY(ProbeCheck::read_spec(plan, st, spec_index, &h, nullptr, err));
+  if (!kp_tuples(task_of(plan, spec_index).mode))
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check does not read tuple keys: its missing keys are "
+                "read with tgx_key_probe_entries or tgx_key_probe_entries_bytes", spec_index);
+  uint64_t n_bytes = 0;
+  TGX_TRY(counted_entries_sizes(h.strs.size(), 0, entries, cap, n_entries, nullptr, 0, &n_bytes, err));
+  if (!entries) return TGX_OK;
+  size_t i = 0;
+  for (const auto &e : h.strs) entries[i++] = tuple_entry_of(e.first, e.second);
+  return TGX_OK;
 } catch (...) {
   return tgx::abi_exception(err);
 }
@@ -1029,10 +1312,13 @@ extern "C" tgx_status tgx_key_probe_get(const tgx_plan *plan, tgx_state *st, siz
   out->non_null = h.non_null;
   out->null_rows = h.seen - h.non_null;
   out->matched = h.matched;
-  out->counted = h.counted();
+  // (a tuples spec: the entries of NULL-bearing tuples are no missing keys -- tgx_key_probe_tuples_get)
+  const bool tuples = kp_tuples(task_of(plan, spec_index).mode);
+  const TupleClasses classes = tuples ? tuple_classes(h) : TupleClasses();
+  out->counted = tuples ? classes.missing_counted : h.counted();
   out->overflow_rows = h.overflow_rows;
   out->missing_rows = out->counted + out->overflow_rows + h.long_rows;  // (long rows: a strings spec's only)
-  out->missing_keys = h.size();
+  out->missing_keys = tuples ? classes.missing_keys : h.size();
   out->parent_keys = h.parent_keys;
   out->parent_digest = h.parent_digest;
   out->route = route;
@@ -1073,6 +1359,9 @@ extern "C" tgx_status tgx_key_probe_entries(const tgx_plan *plan, tgx_state *st,
   if (kp_string_set(task_of(plan, spec_index).mode))
     return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check probes string keys: its missing keys are read "
                 "with tgx_key_probe_entries_bytes", spec_index);
+  if (kp_tuples(task_of(plan, spec_index).mode))
+    return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: the KEY_PROBE check reads tuple keys: its entries are read with "
+                "tgx_key_probe_entries_tuples", spec_index);
   uint64_t n_bytes = 0;
   TGX_TRY(counted_entries_sizes(h.size(), 0, entries, cap, n_entries, nullptr, 0, &n_bytes, err));
   if (!entries) return TGX_OK;

@@ -199,17 +199,18 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
   for (size_t i = 0; i < n_specs; i++) {
     tgx_check_spec &sp = plan->specs[i];
     std::vector<int> tuple;
-    if (sp.kind == TGX_CHECK_DISTINCT && sp.n_columns >= 2) {
+    const bool takes_list = sp.kind == TGX_CHECK_DISTINCT || sp.kind == TGX_CHECK_KEY_PROBE;
+    if (takes_list && sp.n_columns >= 2) {
       if (sp.n_columns > (uint32_t)kMaxTupleCols || !sp.columns)
-        return fail(err, TGX_UNSUPPORTED, "spec %zu: DISTINCT over %u columns (2..%d supported)", i, sp.n_columns,
-                    kMaxTupleCols);
+        return fail(err, TGX_UNSUPPORTED, "spec %zu: %s over %u columns (2..%d supported)", i,
+                    sp.kind == TGX_CHECK_DISTINCT ? "DISTINCT" : "KEY_PROBE", sp.n_columns, kMaxTupleCols);
       for (uint32_t k = 0; k < sp.n_columns; k++) {
         if (sp.columns[k] < 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: negative column index", i);
         tuple.push_back(sp.columns[k]);
         max_col = std::max(max_col, sp.columns[k]);
       }
       sp.column = tuple[0];
-    } else if (sp.kind != TGX_CHECK_DISTINCT && sp.n_columns >= 2) {
+    } else if (!takes_list && sp.n_columns >= 2) {
       return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: only DISTINCT takes a column list", i);
     }
     sp.columns = nullptr;  // the caller's array is not kept: the task holds its own copy
@@ -221,6 +222,11 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     plan->bind[i].count_src = Source::kCount;
     if (const int s = side_index(sp.kind); s >= 0) {  // a kind of side_check.h
       TGX_TRY(kSideKinds[s].plan_add(plan.get(), (int)i, &plan->bind[i].slot, err));
+      if (sp.kind == TGX_CHECK_KEY_PROBE && !tuple.empty()) {  // (the task keeps the list: 2 .. kMaxTupleCols columns)
+        KeyProbeTask &t = plan->key_probes.back();
+        t.n_tuple = (int)tuple.size();
+        std::copy(tuple.begin(), tuple.end(), t.tuple);
+      }
       if (kSideKinds[s].reads_column2) max_col = std::max(max_col, sp.column2);
       continue;
     }

@@ -582,7 +582,8 @@ class JoinCoverageConstraint:
     expect_match_rate.  COUNT(*) over a join counts matched pairs: the far side's non-NULL keys are gathered as {key, 1}
     records and handed to a counted KEY_PROBE spec over the near side's column.  One key pair only: integer keys, or
     string keys when both columns are string layouts (Utf8, LargeUtf8, Utf8View, Dictionary<Int32, Utf8>; the far
-    side's values then travel as keyed 128-bit fingerprints).  Composite keys, other column types and a pair of an
+    side's values then travel as keyed 128-bit fingerprints).  Composite keys (on_multiple with 2 .. 8 pairs) run on
+    the device after composite_keys_on_device(True); without it they, other column types and a pair of an
     integer and a string column are the constraint's own error.  It needs
     ValidationSuite.run(table, tables={name: table})"""
 
@@ -602,6 +603,8 @@ class JoinCoverageConstraint:
         c.max_examples_reported(spec.get("max_examples_reported", 100))
         if "max_value_bytes" in spec:
             c.max_value_bytes(spec["max_value_bytes"])
+        if "composite_keys_on_device" in spec:
+            c.composite_keys_on_device(spec["composite_keys_on_device"])
         return c.max_missing_keys(spec.get("max_missing_keys", 10000))
 
     def on(self, left_column, right_column):
@@ -645,11 +648,21 @@ class JoinCoverageConstraint:
         self.spec["max_value_bytes"] = int(n)
         return self
 
+    def composite_keys_on_device(self, on=True):
+        """this layer's own, an opt-in: a join on 2 .. 8 key pairs (on_multiple) runs on the device under KEY_PROBE's
+        tuple modes, each pair two integer or two string columns.  A row with a NULL in any key column joins nothing;
+        the examples are counted over the tuples' fingerprints, a tuple with a NULL component being a value of its own.
+        The key is written into `spec` only when this is called; without it a composite join stays the constraint's
+        error"""
+        self.spec["composite_keys_on_device"] = bool(on)
+        return self
+
     def name(self): return "join_coverage"
 
     def verdict_from_counts(self, counts):
         """the verdict on given counts (no device): a dict {"left": {"pairs", "join_rows"}, "right": {..},
-        "left_distinct", "examples": {"missing_keys", "null_rows", "overflow_rows", "long_rows"}} (include/tgx_host.h)"""
+        "left_distinct", "examples": {"missing_keys", "null_rows", "overflow_rows", "long_rows", and for composite keys
+        "null_keys", "null_overflow_rows"}} (include/tgx_host.h)"""
         out, err = C.c_char_p(), _Error()
         _host_check(_host().tgx_host_join_coverage_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
                                                         C.byref(out), C.byref(err)), err)

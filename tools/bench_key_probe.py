@@ -11,7 +11,8 @@ figures go into DESIGN.md.  The COUNTED mode (tgx_plan_set_key_probe_counted) ru
 and the same column, its plan interleaved with the other two: the count array (route 3) beside the bitmap (route 1), the
 table of {key, count} slots (route 4) beside the table of keys (route 2); every record's count is 1, so pairs must equal
 the matched rows.
-    python tools/bench_key_probe.py [--rows 100000000] [--parents 1000000,100000000] [--steps 5] [--json out.json]"""
+    python tools/bench_key_probe.py [--rows 100000000] [--parents 1000000,100000000] [--steps 5] [--json out.json]
+    python tools/bench_key_probe.py --tuples ..   (composite keys: tuples_main)"""
 import argparse
 import json
 import os
@@ -33,9 +34,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--strings", action="store_true", help="the string-key probe beside VALUE_COUNTS (strings_main)")
+    ap.add_argument("--tuples", action="store_true", help="the tuple-key probe beside tuple DISTINCT (tuples_main)")
     args = ap.parse_args()
     if args.strings:
         return strings_main(args)
+    if args.tuples:
+        return tuples_main(args)
     import torch
     import term_amd as T
     from term_amd._lib import spec
@@ -150,6 +154,157 @@ STRING_EXPECTATIONS = """expectations, written before the run:
      a record to route 5's claims.  The rows strings gather reads what the probe reads and writes 32 bytes a non-NULL
      row: it should cost about the plain probe against the small set plus 3 GB of stores.
 """
+
+
+def tuples_main(args):
+    """--tuples: a child of (Int64, Int64) and of (Int64, Utf8 of 12 bytes) tuples, 0.01 % NULLs a component's bitmap (every
+    NULL-bearing tuple of such a child is distinct: a higher rate only measures the overflow counter), 1 % of
+    the rows strangers (300 distinct), probed against sets of --parents tuple records (routes 5 and 6; the records are
+    what a rows tuples spec gathers from the parent's columns): the plain probe, the counted probe and the gather of the
+    child, beside the tuple DISTINCT of the same two columns and, for the (Int64, Utf8) shape, the counted STRINGS
+    probe of its string column against a set of the same size -- all plans interleaved step by step in one process,
+    one DEVICE batch, HIP-event kernel times (tgx_profile_get), medians of --steps steps after a warm-up step.  The
+    roofline prices the all-numeric probe's own bytes -- 16 B and two validity bits a row, plus one 16-byte slot load a
+    looked-up row -- at 8 TB/s.  There is no gate: the figures go into DESIGN.md."""
+    import torch
+    import term_amd as T
+    from term_amd._lib import spec
+
+    T.init(flags=T.OPT_NO_COALESCE)
+    n = args.rows // 64 * 64
+    width = 12
+    gen = torch.Generator(device="cuda").manual_seed(0x7E570021)
+    out = {"rows": n, "cases": {}}
+    key = bytes(range(16))
+    far = 1 << 44
+    shifts = (4 * torch.arange(width, device="cuda", dtype=torch.int64))[None, :]
+
+    def render(ids):
+        data = torch.empty((ids.numel(), width), device="cuda", dtype=torch.uint8)
+        step = 1 << 24
+        for lo in range(0, ids.numel(), step):
+            data[lo:lo + step] = (((ids[lo:lo + step, None] >> shifts) & 15) + 97).to(torch.uint8)
+        offsets = torch.arange(ids.numel() + 1, device="cuda", dtype=torch.int64).mul_(width).to(torch.int32)
+        return offsets, torch.cat([data.reshape(-1), torch.zeros(64, device="cuda", dtype=torch.uint8)])
+
+    def bitmap():
+        bits = (torch.rand(n + 64, device="cuda", generator=gen) >= 0.0001).reshape(-1, 8).to(torch.uint8)
+        return (bits << torch.arange(8, device="cuda", dtype=torch.uint8)[None, :]).sum(dim=1).to(torch.uint8), bits.reshape(-1)[:n]
+
+    va, ba = bitmap()
+    vb, bb = bitmap()
+    all_valid = int((ba & bb).sum())
+    b_valid = int(bb.sum())
+    del ba, bb
+
+    def columns(ids, strings, validity=(None, None)):
+        """the tuple (id, 3 * id + 1), or (id, the 12 letters of id)"""
+        a = T.Column.int64(ids, validity[0], length=ids.numel())
+        if not strings:
+            second = ids * 3 + 1
+            return [a, T.Column.int64(second, validity[1], length=ids.numel())], (ids, second)
+        offs, data = render(ids)
+        return [a, T.Column(T.UTF8, ids.numel(), offsets=offs, data=data, validity=validity[1], mem=T.MEM_DEVICE)], (ids, offs, data)
+
+    def plan_of(mode, cols=(0, 1)):
+        plan = T.Plan([spec(T.KEY_PROBE, 0, columns=list(cols))])
+        plan.set_fingerprint_key(key)
+        if mode == "rows":
+            plan.set_key_probe_rows_tuples(0)
+        else:
+            getattr(plan, "set_key_probe_tuples" if mode == "plain" else "set_key_probe_tuples_counted")(0, 65536)
+        return plan
+
+    for strings in (False, True):
+        shape = "int64_utf8" if strings else "int64_int64"
+        for k in [int(p) for p in args.parents.split(",")]:
+            name = "%s_%d" % (shape, k)
+            pcols, pkeep = columns(torch.arange(k, device="cuda", dtype=torch.int64), strings)
+            torch.cuda.synchronize()
+            parent = T.State(plan_of("rows"))
+            parent.update(pcols)
+            ptr, n_records = parent.key_probe_rows(0)
+            assert n_records == k, n_records
+            ids = (torch.rand(n, device="cuda", generator=gen) * k).to(torch.int64).clamp_(0, k - 1)
+            miss = torch.rand(n, device="cuda", generator=gen) < 0.01
+            ids = torch.where(miss, far + (ids % N_MISSING), ids)
+            del miss
+            cols, keep = columns(ids, strings, (va, vb))
+            torch.cuda.synchronize()
+            states = {"plain": T.State(plan_of("plain")), "counted": T.State(plan_of("counted")), "rows": T.State(plan_of("rows"))}
+            dplan = T.Plan([spec(T.DISTINCT, 0, columns=[0, 1])])
+            dplan.set_fingerprint_key(key)
+            states["distinct"] = T.State(dplan)
+            builds = {}
+            for mode in ("plain", "counted"):
+                times = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    states[mode].key_probe_set_parent(0, ptr, n_records)
+                    times.append((time.perf_counter() - t0) * 1e3)
+                builds[mode] = statistics.median(times)
+            if strings:  # the counted strings probe of the string column, against the parent's strings gathered
+                gplan = T.Plan([spec(T.KEY_PROBE, 1)])
+                gplan.set_fingerprint_key(key)
+                gplan.set_key_probe_rows_strings(0)
+                gathered = T.State(gplan)
+                gathered.update(pcols)
+                sptr, sn = gathered.key_probe_rows(0)
+                splan = T.Plan([spec(T.KEY_PROBE, 1)])
+                splan.set_fingerprint_key(key)
+                splan.set_key_probe_strings_counted(0, 10000, 256)
+                states["strings_counted"] = T.State(splan)
+                states["strings_counted"].key_probe_set_parent(0, sptr, sn)
+            kernels = {"plain": "key_probe", "counted": "key_probe", "rows": "key_probe_rows", "distinct": "distinct",
+                       "strings_counted": "key_probe"}
+            ms = {m: [] for m in states}
+            for st in states.values():
+                st.profile_enable(True)
+            for it in range(args.steps + 1):
+                for m, st in states.items():
+                    st.reset()
+                    st.profile_reset()
+                    st.update(cols)
+                    st.finalize()
+                    if it:  # (step 0 warms the shape up)
+                        ms[m].append(st.profile_get(kernels[m])["total_ms"])
+            s, entries = states["plain"].key_probe_tuples(0)
+            cs, _ = states["counted"].key_probe_tuples(0)
+            cp = states["counted"].key_probe_pairs(0)
+            assert s["seen"] == n and s["non_null"] == all_valid and s["overflow_rows"] == 0 and s["route"] == 5, s
+            assert s["parent_keys"] == k and s["missing_keys"] == N_MISSING and s["null_overflow_rows"] == 0, s
+            assert abs(s["missing_rows"] - 0.01 * all_valid) <= 0.002 * all_valid + 1000, s
+            assert cs["route"] == 6 and cp["pairs"] == s["matched"] == cs["matched"] and cp["join_rows"] == n, (cs, cp)
+            assert states["rows"].key_probe_rows(0)[1] == all_valid
+            if strings:
+                ss, _ = states["strings_counted"].key_probe_strings(0)
+                assert ss["non_null"] == b_valid and ss["parent_keys"] == k, ss
+            med = {m: statistics.median(v) for m, v in ms.items()}
+            slots = 1 << max(1, (2 * k - 1).bit_length())
+            own = n * 16 + 2 * (n // 8) + all_valid * 16  # (the all-numeric shape: its columns, bitmaps and slot loads)
+            row = {"%s_ms" % m: med[m] for m in med}
+            row.update({"%s_min_ms" % m: min(ms[m]) for m in ms})
+            row.update({"%s_max_ms" % m: max(ms[m]) for m in ms})
+            row.update(probe_over_distinct=med["plain"] / med["distinct"], counted_ratio=med["counted"] / med["plain"],
+                       gather_ratio=med["rows"] / med["plain"], build_ms=builds["plain"], counted_build_ms=builds["counted"],
+                       set_bytes=16 * slots, counted_set_bytes=24 * slots, matched=s["matched"], missing_rows=s["missing_rows"],
+                       null_rows=s["null_rows"])
+            if not strings:
+                row["roofline"] = own / (med["plain"] * 1e-3) / HBM_BYTES_PER_S
+            out["cases"][name] = row
+            print("%d rows, %-24s plain %.2f ms (%.2f .. %.2f) | counted %.2f ms (x %.2f) | gather %.2f ms (x %.2f) | "
+                  "tuple DISTINCT %.2f ms (probe x %.2f of it)%s%s | sets of %.1f / %.1f MB built in %.2f / %.2f ms"
+                  % (n, name, med["plain"], min(ms["plain"]), max(ms["plain"]), med["counted"], row["counted_ratio"],
+                     med["rows"], row["gather_ratio"], med["distinct"], row["probe_over_distinct"],
+                     " | %.0f %% of 8 TB/s" % (100 * row["roofline"]) if not strings else "",
+                     " | counted strings probe of the Utf8 column %.2f ms" % med["strings_counted"] if strings else "",
+                     row["set_bytes"] / 1e6, row["counted_set_bytes"] / 1e6, builds["plain"], builds["counted"]), flush=True)
+            del states, parent, cols, keep, pcols, pkeep, ids
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
 
 
 def strings_main(args):
