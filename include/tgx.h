@@ -405,7 +405,17 @@ typedef enum tgx_check_kind {
    * keys -- a composite join key, JoinCoverageConstraint::on_multiple -- and has the same three again: TUPLES
    * (tgx_plan_set_key_probe_tuples), COUNTED TUPLES (tgx_plan_set_key_probe_tuples_counted) and ROWS TUPLES
    * (tgx_plan_set_key_probe_rows_tuples); the row rules stand beside tgx_key_probe_tuples_get. */
-  TGX_CHECK_KEY_PROBE = 19
+  TGX_CHECK_KEY_PROBE = 19,
+  /* A row predicate over 1 .. 8 columns: the rows on which a closed boolean expression is TRUE, and those on which it is
+   * UNKNOWN -- the device side of the reference's Check::satisfies (TG/constraints/custom_sql.rs:192-282) and of its
+   * ComplianceAnalyzer (TG/analyzers/advanced/compliance.rs:136-204), both one
+   *     SELECT COUNT(CASE WHEN <expr> THEN 1 END), COUNT(*) FROM t
+   * The spec names its columns through `columns` / `n_columns` (1 .. 8; `column2` must be -1); the predicate -- leaves,
+   * a postfix program over them and a pool of literal bytes -- comes with tgx_plan_set_row_predicate (below, which also
+   * holds the exact semantics); a spec without it makes tgx_state_create fail.  Read with tgx_row_predicate_get;
+   * tgx_result carries total = rows seen, matches = satisfied rows, non_null = seen - unknown.  The state is additive
+   * counters: tgx_merge, blobs and tgx_allreduce add them; a blob counted under another predicate is refused. */
+  TGX_CHECK_ROW_PREDICATE = 20
 } tgx_check_kind;
 
 enum {
@@ -450,7 +460,9 @@ typedef struct tgx_check_spec {
    * component is non-NULL (the primary-key NULL check), distinct = tuples, groups_once with MULTIPLICITY.
    * n_columns == 0 or 1: the single-column check on `column`.
    * KEY_PROBE over a tuple of 2..8 columns: the spec's key is the tuple (tgx_plan_set_key_probe_tuples).  More than 8
-   * columns or a NULL list is refused by tgx_plan_create; every other kind refuses a column list. */
+   * columns or a NULL list is refused by tgx_plan_create.
+   * ROW_PREDICATE: the 1 .. 8 columns its leaves name by position in this list (a list of length 1 too).
+   * Every other kind refuses a column list. */
   const int32_t *columns;
   uint32_t n_columns;
   uint32_t reserved2;
@@ -644,6 +656,72 @@ typedef struct tgx_value_rule_params {
 } tgx_value_rule_params;
 tgx_status tgx_plan_set_value_rule(tgx_plan *plan, size_t spec_index, const tgx_value_rule_params *params,
                                    tgx_error *err);
+
+/* TGX_CHECK_ROW_PREDICATE: the predicate of spec `spec_index`.  Like the VALUE_RULE parameters it can be set until the
+ * plan's first state exists; afterwards, and for a spec of another kind, the call is refused with TGX_INVALID_ARGUMENT.
+ * This is a closed predicate subset, not SQL: what is written here is all there is, and it is what the exact reference
+ * of the tests is held to.
+ *
+ * LEAVES (1 .. TGX_PRED_MAX_LEAVES).  Each leaf is TRUE, FALSE or UNKNOWN for a row.  `col` / `col2` are positions in the
+ * spec's column list.  A row's value is an int64 or a double as for VALUE_RULE (above); a string column's value is the
+ * row's bytes whatever the layout (Utf8, LargeUtf8, Utf8View, Dictionary<Int32, Utf8>), and a row whose dictionary
+ * entry is NULL, or whose index lies outside the dictionary, is a NULL row (the rule of VALUE_COUNTS).
+ *   TGX_PRED_IS_NULL      col IS NULL: TRUE on a NULL row, FALSE otherwise; never UNKNOWN.  Takes every column type.
+ *   TGX_PRED_CMP_LITERAL  col <op> literal, op one of TGX_PRED_EQ / LT / LE / GT / GE.  UNKNOWN when col is NULL.  The
+ *                         literal is carried as int64 (lit_i) and as double (lit_f); TGX_PRED_LITERAL_IS_DOUBLE says it was
+ *                         written with a point or an exponent.  What is compared follows the column's type in the batch:
+ *                           integer column, integer literal:   v <op> lit_i as int64;
+ *                           integer column, double literal:    key((double)v) <op> key(lit_f), the conversion
+ *                                                              round-to-nearest-even as CAST(col AS DOUBLE) does;
+ *                           float column:                      key(x) <op> key(lit_f) (the caller gives an integer
+ *                                                              literal's lit_f = (double)lit_i).
+ *                         key is the IEEE totalOrder key of VALUE_RULE (above), for `=` as well: -0.0 < +0.0 and a NaN
+ *                         equals the NaN with the same bits.  (This rests on arrow-ord's documented ordering, as for
+ *                         VALUE_RULE; INTEGRATION.md lists it as unverified.)
+ *   TGX_PRED_CMP_COLUMNS  col <op> col2.  UNKNOWN when either side is NULL.  Both integer: int64 compare.  Any float:
+ *                         both sides as double keys (an integer side converted as above).  Two string columns:
+ *                         TGX_PRED_EQ only, by bytes.
+ *   TGX_PRED_STR_EQ       col = the literal bytes [lit_offset, lit_offset + lit_len) of the pool, by bytes; the empty
+ *                         string is a value.  UNKNOWN when col is NULL.
+ * A leaf that does not fit the type its column arrives in -- a string leaf on a numeric column, a numeric leaf on a
+ * string column, a string column against a numeric one, UInt64 / Boolean / validity-only columns under anything but
+ * IS_NULL -- makes tgx_update fail with TGX_UNSUPPORTED; the batch is not counted and the state stays usable.
+ *
+ * PROGRAM (1 .. TGX_PRED_MAX_OPS ops, postfix).  An op is `code | arg << 8`: TGX_PRED_PUSH (arg: the leaf), TGX_PRED_AND,
+ * TGX_PRED_OR, TGX_PRED_NOT (arg 0).  The logic is Kleene's: AND is FALSE if either side is FALSE, else UNKNOWN if either
+ * is UNKNOWN, else TRUE; OR is the dual; NOT UNKNOWN is UNKNOWN.  The program must leave exactly one value, never pop
+ * an empty stack and never hold more than TGX_PRED_MAX_DEPTH values.  `<>`, BETWEEN and IN are not device notions: the
+ * caller lowers them by SQL's own definitions (NOT(x = l); x >= a AND x <= b; an OR of equalities).
+ *
+ * The setter refuses with TGX_INVALID_ARGUMENT: counts out of range, an unknown leaf kind / comparison / flag / op, a
+ * column position outside the spec's list, a literal range outside the pool, a PUSH of a leaf that does not exist,
+ * underflow, a depth above 32, and a program that leaves more or fewer than one value.  What a leaf does not read is
+ * kept as zero bits (the blob compares the predicate byte by byte). */
+enum { TGX_PRED_MAX_COLUMNS = 8, TGX_PRED_MAX_LEAVES = 32, TGX_PRED_MAX_OPS = 64, TGX_PRED_MAX_DEPTH = 32,
+       TGX_PRED_MAX_LITERAL_BYTES = 256 };
+enum { TGX_PRED_IS_NULL = 1, TGX_PRED_CMP_LITERAL = 2, TGX_PRED_CMP_COLUMNS = 3, TGX_PRED_STR_EQ = 4 };
+enum { TGX_PRED_EQ = 1, TGX_PRED_LT = 2, TGX_PRED_LE = 3, TGX_PRED_GT = 4, TGX_PRED_GE = 5 };
+enum { TGX_PRED_LITERAL_IS_DOUBLE = 1u << 0 };
+enum { TGX_PRED_PUSH = 1, TGX_PRED_AND = 2, TGX_PRED_OR = 3, TGX_PRED_NOT = 4 };
+typedef struct tgx_row_predicate_leaf {
+  int32_t kind;        /* TGX_PRED_IS_NULL .. TGX_PRED_STR_EQ */
+  int32_t op;          /* CMP_LITERAL / CMP_COLUMNS: TGX_PRED_EQ .. TGX_PRED_GE; otherwise 0 */
+  int32_t col, col2;   /* positions in the spec's column list; col2: CMP_COLUMNS only, otherwise 0 */
+  uint32_t flags;      /* CMP_LITERAL: TGX_PRED_LITERAL_IS_DOUBLE */
+  uint32_t lit_offset; /* STR_EQ: the literal's bytes in the pool */
+  uint32_t lit_len;
+  uint32_t reserved;   /* 0 */
+  int64_t lit_i;       /* CMP_LITERAL */
+  double lit_f;
+} tgx_row_predicate_leaf;
+typedef struct tgx_row_predicate_params {
+  uint32_t n_leaves, n_ops, n_literal_bytes, reserved;
+  tgx_row_predicate_leaf leaves[TGX_PRED_MAX_LEAVES];
+  uint16_t program[TGX_PRED_MAX_OPS];
+  uint8_t literals[TGX_PRED_MAX_LITERAL_BYTES];
+} tgx_row_predicate_params;
+tgx_status tgx_plan_set_row_predicate(tgx_plan *plan, size_t spec_index, const tgx_row_predicate_params *params,
+                                      tgx_error *err);
 
 /* TGX_CHECK_VALUE_COUNTS: the bounds of spec `spec_index`.  Like the VALUE_RULE parameters they can be set until the
  * plan's first state exists; afterwards, and for a spec of another kind, the call is refused with TGX_INVALID_ARGUMENT.
@@ -945,6 +1023,16 @@ typedef struct tgx_value_rule_counts {
 } tgx_value_rule_counts;
 tgx_status tgx_value_rule_get(const tgx_plan *plan, tgx_state *state, size_t spec_index, tgx_value_rule_counts *out,
                               tgx_error *err);
+
+/* ---- row predicates (TGX_CHECK_ROW_PREDICATE; TG/constraints/custom_sql.rs:192-282) -------------------------------- */
+typedef struct tgx_row_predicate_counts {
+  uint64_t seen;      /* rows handed to tgx_update: the SQL's COUNT(*) */
+  uint64_t satisfied; /* rows on which the predicate is TRUE: the SQL's COUNT(CASE WHEN <expr> THEN 1 END) */
+  uint64_t unknown;   /* rows on which it is UNKNOWN */
+  uint64_t failed;    /* rows on which it is FALSE: seen - satisfied - unknown */
+} tgx_row_predicate_counts;
+tgx_status tgx_row_predicate_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                 tgx_row_predicate_counts *out, tgx_error *err);
 
 /* ---- value counts (TGX_CHECK_VALUE_COUNTS; TG/constraints/histogram.rs:205-391) ----------------------------------- */
 typedef struct tgx_value_counts_summary {
@@ -1341,7 +1429,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "row_predicate", "hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -76,6 +76,14 @@ tgx_status tgx_host_temporal_params_json(const char *constraint_json, const char
  * Needs no device. */
 tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **out_json, tgx_error *err);
 
+/* What the predicate compiler of Check::satisfies / ComplianceAnalyzer makes of `expression` (host/custom_sql.h has the
+ * grammar): {"columns": the columns in order of first appearance, "leaves": [{"kind", "op", "col", "col2", "flags",
+ * "lit_offset", "lit_len", "lit_i", "lit_f", "lit_f_bits"}] (the fields of tgx_row_predicate_leaf; lit_f_bits: the
+ * double's bits as an unsigned integer, which keeps the sign of -0.0), "program": [[code, arg], ..],
+ * "literals_hex": the literal pool}.  An expression outside the subset is TGX_UNSUPPORTED with
+ * "the expression is not on the GPU path: <the first thing outside the subset>".  Needs no device. */
+tgx_status tgx_host_row_predicate_json(const char *expression, char **out_json, tgx_error *err);
+
 /* `Constraint::evaluate`'s verdict half on given aggregates: results_json is an array of objects with
  * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}, a
  * VALUE_COUNTS entry {"total", "non_null", "value_counts": {"entries": {value text: count}, "overflow_rows",
@@ -86,7 +94,8 @@ tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **o
  * must hold; it plans one TGX_CHECK_VALUE_COUNTS request ({"kind": 15, "value_counts": {"max_distinct",
  * "max_value_bytes"}}).
  * Returns {"status": "success|failure|skipped", "metric": x|null, "message": s|null}.  Needs no device.
- * The constraint JSON may carry "column_type" (the column's Arrow DataType) and "strict_reference_types" as above. */
+ * The constraint JSON may carry "column_type" (the column's Arrow DataType) and "strict_reference_types" as above,
+ * and "column_types" (an array: the Arrow DataTypes of a ROW_PREDICATE request's column list, in the list's order). */
 tgx_status tgx_host_constraint_verdict_json(const char *constraint_json, const char *results_json, char **out_json,
                                             tgx_error *err);
 

@@ -30,6 +30,12 @@ GROUP_COUNTS_MAX_GROUPS, GROUP_COUNTS_MAX_VALUE_BYTES = 65536, 256
 KEY_PROBE = 19  # is each key of a child column in a parent's key set (Plan.set_key_probe, State.key_probe_set_parent)
 KEY_PROBE_MAX_MISSING_KEYS = 65536
 KEY_PROBE_MAX_VALUE_BYTES = 256  # of a missing key a spec on string keys keeps (Plan.set_key_probe_strings)
+ROW_PREDICATE = 20  # the rows on which a closed boolean predicate over 1 .. 8 columns is TRUE / UNKNOWN (Plan.set_row_predicate)
+PRED_MAX_COLUMNS, PRED_MAX_LEAVES, PRED_MAX_OPS, PRED_MAX_DEPTH, PRED_MAX_LITERAL_BYTES = 8, 32, 64, 32, 256
+PRED_IS_NULL, PRED_CMP_LITERAL, PRED_CMP_COLUMNS, PRED_STR_EQ = 1, 2, 3, 4
+PRED_EQ, PRED_LT, PRED_LE, PRED_GT, PRED_GE = 1, 2, 3, 4, 5
+PRED_LITERAL_IS_DOUBLE = 1
+PRED_PUSH, PRED_AND, PRED_OR, PRED_NOT = 1, 2, 3, 4
 GROUP_SUMS = 18  # COUNT(*), COUNT(col) and SUM(col) per group of a second column, for a bounded number of groups (Plan.set_group_sums)
 GROUP_SUMS_MAX_GROUPS, GROUP_SUMS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
@@ -132,6 +138,25 @@ class ValueRuleParams(C.Structure):
 class ValueRuleCounts(C.Structure):
     """tgx_value_rule_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("considered", C.c_uint64), ("valid", C.c_uint64), ("cast_errors", C.c_uint64)]
+
+
+class RowPredicateLeaf(C.Structure):
+    """tgx_row_predicate_leaf (include/tgx.h)"""
+    _fields_ = [("kind", C.c_int32), ("op", C.c_int32), ("col", C.c_int32), ("col2", C.c_int32), ("flags", C.c_uint32),
+                ("lit_offset", C.c_uint32), ("lit_len", C.c_uint32), ("reserved", C.c_uint32), ("lit_i", C.c_int64),
+                ("lit_f", C.c_double)]
+
+
+class RowPredicateParams(C.Structure):
+    """tgx_row_predicate_params (include/tgx.h)"""
+    _fields_ = [("n_leaves", C.c_uint32), ("n_ops", C.c_uint32), ("n_literal_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("leaves", RowPredicateLeaf * PRED_MAX_LEAVES), ("program", C.c_uint16 * PRED_MAX_OPS),
+                ("literals", C.c_uint8 * PRED_MAX_LITERAL_BYTES)]
+
+
+class RowPredicateCounts(C.Structure):
+    """tgx_row_predicate_counts (include/tgx.h)"""
+    _fields_ = [("seen", C.c_uint64), ("satisfied", C.c_uint64), ("unknown", C.c_uint64), ("failed", C.c_uint64)]
 
 
 class ValueCountsParams(C.Structure):
@@ -392,6 +417,8 @@ def lib():
         L.tgx_time_gap_get.argtypes = [vp, vp, sz, C.POINTER(TimeGapCounts), E]
         L.tgx_plan_set_value_rule.argtypes = [vp, sz, C.POINTER(ValueRuleParams), E]
         L.tgx_value_rule_get.argtypes = [vp, vp, sz, C.POINTER(ValueRuleCounts), E]
+        L.tgx_plan_set_row_predicate.argtypes = [vp, sz, C.POINTER(RowPredicateParams), E]
+        L.tgx_row_predicate_get.argtypes = [vp, vp, sz, C.POINTER(RowPredicateCounts), E]
         L.tgx_plan_set_value_counts.argtypes = [vp, sz, C.POINTER(ValueCountsParams), E]
         L.tgx_value_counts_get.argtypes = [vp, vp, sz, C.POINTER(ValueCountsSummary), E]
         L.tgx_value_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
@@ -702,13 +729,13 @@ class Column:
 
 def spec(kind, column, column2=-1, flags=0, pattern=None, kll_k=0, columns=None, length_min=0, length_max=None):
     """columns=[a, b, ...]: DISTINCT over the tuple of those columns (COUNT(DISTINCT (a, b))), or a KEY_PROBE whose key is
-    that tuple (Plan.set_key_probe_tuples);
+    that tuple (Plan.set_key_probe_tuples), or the 1 .. 8 columns a ROW_PREDICATE's leaves name by position;
     length_min / length_max (None = unbounded): LENGTH bounds in characters"""
     pat = pattern.encode("utf-8") if isinstance(pattern, str) else pattern
     s = CheckSpec(kind, column, column2, flags, pat, len(pat) if pat else 0, kll_k, 0)
     s.length_min = length_min
     s.length_max = (1 << 64) - 1 if length_max is None else length_max
-    if columns is not None and len(columns) >= 2:
+    if columns is not None and (len(columns) >= 2 or (kind == ROW_PREDICATE and columns)):
         arr = (C.c_int32 * len(columns))(*columns)
         s.columns = C.cast(arr, C.POINTER(C.c_int32))
         s.n_columns = len(columns)
@@ -854,6 +881,26 @@ class Plan:
         p = ValueRuleParams(mode, flags, lo_i, hi_i, lo_f, hi_f)
         err = _Error()
         _check(lib().tgx_plan_set_value_rule(self.h, spec_index, C.byref(p), C.byref(err)), err)
+
+    def set_row_predicate(self, spec_index, leaves, program, literals=b"", n_leaves=None, n_ops=None,
+                          n_literal_bytes=None):
+        """tgx_plan_set_row_predicate: the predicate of a ROW_PREDICATE spec (before the plan's first state).  `leaves`:
+        dicts with the fields of tgx_row_predicate_leaf (those left out are 0); `program`: (code, arg) pairs or packed
+        ints; `literals`: the pool's bytes.  The n_* arguments override the counts (for a call that is to be refused)."""
+        p = RowPredicateParams()
+        for j, leaf in enumerate(list(leaves)[:PRED_MAX_LEAVES]):
+            for k, v in leaf.items():
+                setattr(p.leaves[j], k, v)
+        for k, op in enumerate(list(program)[:PRED_MAX_OPS]):
+            p.program[k] = op if isinstance(op, int) else (op[0] | (op[1] << 8))
+        literals = bytes(literals)
+        for k, b in enumerate(literals[:PRED_MAX_LITERAL_BYTES]):
+            p.literals[k] = b
+        p.n_leaves = len(leaves) if n_leaves is None else n_leaves
+        p.n_ops = len(program) if n_ops is None else n_ops
+        p.n_literal_bytes = len(literals) if n_literal_bytes is None else n_literal_bytes
+        err = _Error()
+        _check(lib().tgx_plan_set_row_predicate(self.h, spec_index, C.byref(p), C.byref(err)), err)
 
     def set_value_counts(self, spec_index, max_distinct=10000, max_value_bytes=256):
         """tgx_plan_set_value_counts: the bounds of a VALUE_COUNTS spec (before the plan's first state)"""
@@ -1147,6 +1194,13 @@ class State:
         err = _Error()
         _check(lib().tgx_value_rule_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.considered, out.valid, out.cast_errors
+
+    def row_predicate_counts(self, spec_index):
+        """tgx_row_predicate_get: (seen, satisfied, unknown, failed)"""
+        out = RowPredicateCounts()
+        err = _Error()
+        _check(lib().tgx_row_predicate_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return out.seen, out.satisfied, out.unknown, out.failed
 
     def _counted_entries(self, call, entry_type, spec_index, *more):
         """the two calls of a *_entries function: ask for the sizes, allocate, fetch; (the entries, the bytes their

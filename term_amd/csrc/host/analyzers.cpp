@@ -2,6 +2,7 @@
 // TG/analyzers/basic/{size,completeness,distinctness,mean,min_max,sum}.rs,
 // TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram,entropy}.rs.
 #include "analyzers.h"
+#include "custom_sql.h"
 #include "tgx_handles.h"
 
 #include <math.h>
@@ -153,6 +154,53 @@ class SizeAnalyzer : public Analyzer {  // basic/size.rs
     return jobj({{"count", jcount(c)}});
   }
   MetricValue metric_from_state(const json::Value &s) const override { return MetricValue::of_long((int64_t)u(s, "count")); }
+};
+
+// advanced/compliance.rs: the fraction of rows on which a predicate is TRUE,
+//   SELECT COUNT(CASE WHEN (<predicate>) THEN 1 END), COUNT(*) FROM t
+// as one TGX_CHECK_ROW_PREDICATE request; the predicate is compiled by host/custom_sql.h's closed subset
+class ComplianceAnalyzer : public Analyzer {
+ public:
+  ComplianceAnalyzer(std::string name, std::string predicate) : name_(std::move(name)), predicate_(std::move(predicate)) {}
+  std::string name() const override { return "compliance"; }  // (metric_key: the trait's default, the name)
+  const std::string &check_name() const { return name_; }
+  const std::string &predicate() const { return predicate_; }
+  std::vector<std::string> columns() const override {
+    try {
+      return compile_row_predicate(predicate_).columns;
+    } catch (const PredicateRefusal &) {
+      return {};
+    }
+  }
+  std::vector<SpecRequest> plan() const override {
+    // validate_predicate (:88-108): a substring test on the lower-cased text, in the list's order
+    if (auto word = compliance_forbidden_keyword(predicate_))
+      throw AnalyzerError::custom("Invalid configuration: Predicate contains forbidden keyword: " + *word);
+    try {
+      return {row_predicate_request(compile_row_predicate(predicate_))};
+    } catch (const PredicateRefusal &r) {
+      throw AnalyzerError::custom("Invalid configuration: Invalid predicate '" + predicate_ +
+                                  "': not on the GPU path: " + r.what);
+    }
+  }
+  json::Value state_from_results(const std::vector<const tgx_result *> &r, const std::vector<int> &) const override {
+    return jobj({{"compliant_count", jcount(r[0]->matches)}, {"total_count", jcount(r[0]->total)}});
+  }
+  json::Value merge_states(const std::vector<json::Value> &states) const override {  // :66-75
+    uint64_t c = 0, t = 0;
+    for (auto &s : states) {
+      c += u(s, "compliant_count");
+      t += u(s, "total_count");
+    }
+    return jobj({{"compliant_count", jcount(c)}, {"total_count", jcount(t)}});
+  }
+  MetricValue metric_from_state(const json::Value &s) const override {  // :52-58: an empty dataset is compliant
+    const uint64_t t = u(s, "total_count");
+    return MetricValue::of_double(t == 0 ? 1.0 : (double)u(s, "compliant_count") / (double)t);
+  }
+
+ private:
+  std::string name_, predicate_;
 };
 
 class ColumnAnalyzer : public Analyzer {
@@ -1301,6 +1349,7 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
     cfg.include_overall = v.get_bool("include_overall", true);
     return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"));
   }
+  if (t == "compliance") return std::make_shared<ComplianceAnalyzer>(v.get_str("name"), v.get_str("predicate"));
   // ("entropy" stays an unknown type: the tag of EntropyAnalyzer is "value_entropy")
   if (t == "value_entropy")
     return std::make_shared<EntropyAnalyzer>(col(), v.get_u64("max_unique_values", 10000), v.get_str("arrow_type"));
@@ -1355,6 +1404,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
         if (column_index(*c) < 0 && !p.error)
           p.error = AnalyzerError::query("Schema error: No field named " + *c + ".").text;
       }
+      for (const std::string &c : r.columns)
+        if (column_index(c) < 0 && !p.error) p.error = AnalyzerError::query("Schema error: No field named " + c + ".").text;
       if (p.error) break;
       p.reqs.push_back(r);
     }
@@ -1365,9 +1416,11 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
   }
   // one pass over the table for every analyzer that is still in the run: their requests fused and de-duplicated
   std::vector<tgx_check_spec> specs;
+  std::deque<std::vector<int32_t>> list_columns;  // owns the column lists of the specs that have one
   auto fuse = [&]() {
     requests.clear();
     specs.clear();
+    list_columns.clear();
     for (Planned &p : planned) {
       p.spec_index.clear();
       if (p.error) continue;
@@ -1375,7 +1428,7 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
         size_t found = requests.size();
         for (size_t i = 0; i < requests.size(); i++)
           if (requests[i].kind == r.kind && requests[i].column == r.column && requests[i].column2 == r.column2 &&
-              requests[i].flags == r.flags && requests[i].same_parameters(r))
+              requests[i].columns == r.columns && requests[i].flags == r.flags && requests[i].same_parameters(r))
             found = i;
         if (found == requests.size()) requests.push_back(r);
         p.spec_index.push_back(found);
@@ -1389,6 +1442,12 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       s.column2 = r.column2.empty() ? -1 : column_index(r.column2);
       s.flags = r.flags;
       if (r.kind == TGX_CHECK_DISTINCT) s.flags |= TGX_FLAG_EXACT_KEYS;  // DistinctnessAnalyzer counts by value
+      if (r.kind == TGX_CHECK_ROW_PREDICATE) {  // (the one kind of this runner that names its columns through a list)
+        list_columns.emplace_back();
+        for (const std::string &c : r.columns) list_columns.back().push_back(column_index(c));
+        s.columns = list_columns.back().data();
+        s.n_columns = (uint32_t)list_columns.back().size();
+      }
       specs.push_back(s);
     }
   };
@@ -1414,6 +1473,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       if (requests[i].pair_counts) s = tgx_plan_set_pair_counts(hh.plan, i, &*requests[i].pair_counts, &err);
       if (s == TGX_OK && requests[i].group_counts)
         s = tgx_plan_set_group_counts(hh.plan, i, &*requests[i].group_counts, &err);
+      if (s == TGX_OK && requests[i].row_predicate)
+        s = tgx_plan_set_row_predicate(hh.plan, i, &*requests[i].row_predicate, &err);
     }
     if (s == TGX_OK) s = tgx_state_create(hh.plan, nullptr, &hh.state, &err);
     std::vector<tgx_column> cut;

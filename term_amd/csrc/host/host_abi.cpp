@@ -7,6 +7,7 @@
 #include "../../../include/tgx_host.h"
 #include "json.h"
 #include "analyzers.h"
+#include "custom_sql.h"
 #include "datatype.h"
 #include "value_counts.h"
 #include "temporal.h"
@@ -120,6 +121,12 @@ extern "C" tgx_status tgx_host_constraint_plan_json(const char *constraint_json,
       if (r.value_counts)
         o += ", \"value_counts\": {\"max_distinct\": " + std::to_string(r.value_counts->max_distinct) +
              ", \"max_value_bytes\": " + std::to_string(r.value_counts->max_value_bytes) + "}";
+      if (r.row_predicate) {
+        RowPredicate p;
+        p.columns = r.columns;
+        p.params = *r.row_predicate;
+        o += ", \"row_predicate\": " + row_predicate_json(p);
+      }
       o += "}";
     }
     o += "]}";
@@ -240,6 +247,12 @@ extern "C" tgx_status tgx_host_constraint_verdict_json(const char *constraint_js
       std::string cerr;
       if (json::parse(constraint_json, &cv, &cerr) && cv.is(json::Value::Object)) {
         if (cv.get("column_type")) in.arrow_types.assign(results.size(), cv.get_str("column_type"));
+        if (const json::Value *ct = cv.get("column_types"))  // ... of a request's column list, in the list's order
+          if (ct->is(json::Value::Array)) {
+            std::vector<std::string> types;
+            for (const json::Value &e : ct->arr) types.push_back(e.is(json::Value::String) ? e.str : std::string());
+            in.list_arrow_types.assign(results.size(), types);
+          }
         in.strict_reference_types = cv.get_bool("strict_reference_types", true);
       }
     }
@@ -321,6 +334,23 @@ extern "C" tgx_status tgx_host_value_rule_params_json(const char *constraint_jso
     return TGX_OK;
   } catch (const TermError &e) {
     return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_row_predicate_json(const char *expression, char **out_json, tgx_error *err) {
+  if (!expression || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    *out_json = dup_string(row_predicate_json(compile_row_predicate(expression)));
+    return TGX_OK;
+  } catch (const PredicateRefusal &r) {
+    return hfail(err, TGX_UNSUPPORTED, "the expression is not on the GPU path: " + r.what);
   } catch (const std::bad_alloc &) {
     return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
   } catch (const std::exception &e) {

@@ -12,6 +12,7 @@
 #include <chrono>
 
 #include "json.h"
+#include "custom_sql.h"
 #include "datatype.h"
 #include "value_counts.h"
 #include "temporal.h"
@@ -35,6 +36,7 @@ std::string TermError::display() const {
     case NotSupported: return "Operation not supported: " + message;
     case Configuration: return "Configuration error: " + message;
     case ConstraintEvaluation: return "Constraint evaluation failed for " + message;  // error.rs:28
+    case ValidationFailed: return "Validation failed: " + message;  // error.rs (validation_failed)
     case TypeMismatch: return "Type mismatch: " + message;  // error.rs:81 ("expected {expected}, found {found}")
     default: return "Internal error: " + message;
   }
@@ -1373,7 +1375,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       s.kll_k = r.kll_k;
       s.length_min = r.length_min;
       s.length_max = r.length_max;
-      if (r.columns.size() >= 2) {
+      if (r.columns.size() >= 2 || (r.kind == TGX_CHECK_ROW_PREDICATE && !r.columns.empty())) {
         tuple_columns.emplace_back();
         for (const std::string &c2 : r.columns) tuple_columns.back().push_back(column_index(c2));
         s.columns = tuple_columns.back().data();
@@ -1396,6 +1398,7 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       const SpecRequest &r = spec_requests[i];
       if (r.value_rule) s = tgx_plan_set_value_rule(hh.plan, i, &*r.value_rule, &err);
       if (r.value_counts && s == TGX_OK) s = tgx_plan_set_value_counts(hh.plan, i, &*r.value_counts, &err);
+      if (r.row_predicate && s == TGX_OK) s = tgx_plan_set_row_predicate(hh.plan, i, &*r.row_predicate, &err);
       if (!r.temporal) continue;
       if (r.kind == TGX_CHECK_TIME_GAP) {
         const tgx_time_gap_params gp = time_gap_params(*r.temporal, arrow_type_of(r.column), arrow_type_of(r.column2));
@@ -1484,7 +1487,11 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
       Constraint::Inputs in;
       QuantileCtx qctx{h.plan, h.state, p.spec_index};
       for (size_t si : p.spec_index) in.results.push_back(&results[si]);
-      for (const SpecRequest &r : p.requests) in.arrow_types.push_back(arrow_type_of(r.column));
+      for (const SpecRequest &r : p.requests) {
+        in.arrow_types.push_back(arrow_type_of(r.column));
+        in.list_arrow_types.emplace_back();
+        for (const std::string &c2 : r.columns) in.list_arrow_types.back().push_back(arrow_type_of(c2));
+      }
       in.strict_reference_types = strict_types_;
       in.ctx = &qctx;
       in.quantile = quantile_cb;
@@ -1493,6 +1500,12 @@ ValidationResult ValidationSuite::run(const Context &ctx) const {
         cr = p.constraint->evaluate(in);
       } catch (const TermError &e) {
         error = e.display();
+      }
+    }
+    if (error) {
+      if (std::optional<ConstraintResult> verdict = p.constraint->failure_from_error(*error)) {
+        cr = *verdict;  // (the reference's evaluate() answers Ok(failure(..)) here, not Err)
+        error.reset();
       }
     }
     if (error) {
@@ -1823,6 +1836,11 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     b.constraint(std::move(x));
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
+  } else if (type == "custom_sql") {
+    // {"type": "custom_sql", "expression", "hint"?}
+    const json::Value *hint = c.get("hint");
+    b.satisfies(c.get_str("expression"),
+                hint && hint->is(json::Value::String) ? std::optional<std::string>(hint->str) : std::nullopt);
   } else if (type == "histogram") {
     // {"type": "histogram", "column", "measures": [{"measure", "assertion", "n"?, "value"?}, ..], "description"?,
     //  "max_distinct"? (default 10000)}: every measure must hold

@@ -49,7 +49,8 @@ struct ConstraintResult {
 // TermError (error.rs:14-145): only the variants this path produces
 struct TermError {
   // ConstraintEvaluation: `message` starts with the quoted constraint name ("'temporal_ordering': ..", error.rs:28)
-  enum Kind { Internal, SecurityError, DataFusion, NotSupported, Configuration, TypeMismatch, ConstraintEvaluation } kind = Internal;
+  enum Kind { Internal, SecurityError, DataFusion, NotSupported, Configuration, TypeMismatch, ConstraintEvaluation,
+              ValidationFailed } kind = Internal;
   std::string message;
   std::string display() const;  // thiserror Display strings, e.g. "Security error: ..."
 };
@@ -182,6 +183,9 @@ struct SpecRequest {
   std::optional<tgx_value_counts_params> value_counts;  // VALUE_COUNTS: the bounds (host/value_counts.h)
   std::optional<tgx_pair_counts_params> pair_counts;    // PAIR_COUNTS: the bounds and the sides (host/analyzers.cpp)
   std::optional<tgx_group_counts_params> group_counts;  // GROUP_COUNTS (`column2`: the group column): the bounds
+  // ROW_PREDICATE (`columns`: the spec's column list, of any length from 1): the predicate as the device takes it
+  // (host/custom_sql.h); what a leaf does not read is zero, so equal predicates are equal bytes
+  std::optional<tgx_row_predicate_params> row_predicate;
   // do two requests ask the device for the same thing (what the runners' fusing compares beside kind and columns)?
   bool same_parameters(const SpecRequest &o) const {
     return value_rule.has_value() == o.value_rule.has_value() &&
@@ -193,7 +197,9 @@ struct SpecRequest {
            (!pair_counts || memcmp(&*pair_counts, &*o.pair_counts, sizeof(tgx_pair_counts_params)) == 0) &&
            group_counts.has_value() == o.group_counts.has_value() &&
            (!group_counts || (group_counts->max_groups == o.group_counts->max_groups &&
-                              group_counts->max_value_bytes == o.group_counts->max_value_bytes));
+                              group_counts->max_value_bytes == o.group_counts->max_value_bytes)) &&
+           row_predicate.has_value() == o.row_predicate.has_value() &&
+           (!row_predicate || memcmp(&*row_predicate, &*o.row_predicate, sizeof(tgx_row_predicate_params)) == 0);
   }
 };
 struct ValueCounts;  // host/value_counts.h
@@ -221,9 +227,15 @@ class Constraint {
     // "Timestamp", "Float32", "UInt16", ...; empty = unknown, taken for Int64 / Float64), and whether the verdict
     // follows the reference's own extraction rule for it (reference_extracts below)
     std::vector<std::string> arrow_types;
+    // ... and of the columns of request i's column list, in the list's order (empty for a request without a list)
+    std::vector<std::vector<std::string>> list_arrow_types;
     bool strict_reference_types = true;
   };
   virtual ConstraintResult evaluate(const Inputs &in) const = 0;
+  // A constraint whose reference turns a query's error into a verdict (CustomSqlConstraint: a Failure that carries the
+  // error's text) says so here: `error` is what the run would otherwise report as this constraint's error -- a column
+  // the table lacks, a batch the device refuses.  nullopt: the error stands
+  virtual std::optional<ConstraintResult> failure_from_error(const std::string & /*error*/) const { return std::nullopt; }
   // A constraint that reads tables of its own (CrossTableSumConstraint) is no part of the suite's fused plan: plan() is
   // empty and ValidationSuite::run evaluates it beside the plan, against the Context.  Throws TermError as plan() does.
   virtual bool reads_context() const { return false; }
@@ -573,6 +585,9 @@ class Check::Builder {
   // reference's constructor returns Err and the builder panics on it (a threshold outside [0, 1]: Configuration).  The other validations come
   // as configured objects through constraint(..) (host/datatype.h)
   Builder &has_consistent_data_type(std::string column, double threshold);
+  // core/check.rs:685-694: pushes CustomSqlConstraint::new(expression, hint); throws TermError (ValidationFailed) where
+  // the reference's builder panics on the constructor's Err (host/custom_sql.h)
+  Builder &satisfies(std::string sql_expression, std::optional<std::string> hint = std::nullopt);
   // core/check.rs has_histogram / has_histogram_with_description: pushes HistogramConstraint::new[_with_description]
   // (host/value_counts.h; max_distinct bounds the values the device counts, default 10000)
   Builder &has_histogram(std::string column, std::function<bool(const Histogram &)> assertion);

@@ -298,8 +298,20 @@ struct KeyProbeTask {
   tgx_key_probe_params params;
 };
 
+// TGX_CHECK_ROW_PREDICATE (rowpredicate_device.cpp): one task per spec; `set` once tgx_plan_set_row_predicate was called.
+// `columns`: the spec's column list (1 .. 8), which the leaves name by position; `params`: the predicate as it was set,
+// what a leaf does not read zeroed
+constexpr int kRowPredicateMaxCols = 8;
+struct RowPredicateTask {
+  int spec_index;
+  int n_columns;
+  int columns[kRowPredicateMaxCols];
+  bool set;
+  tgx_row_predicate_params params;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 9;  // the records of side_check.h's kSideKinds
+constexpr int kNumSide = 10;  // the records of side_check.h's kSideKinds
 
 enum class Source { kScan, kCount };
 
@@ -330,6 +342,7 @@ struct tgx_plan {
   std::vector<tgx::GroupCountsTask> group_counts;
   std::vector<tgx::GroupSumsTask> group_sums;
   std::vector<tgx::KeyProbeTask> key_probes;
+  std::vector<tgx::RowPredicateTask> row_predicates;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;
@@ -777,7 +790,7 @@ struct tgx_state {
 namespace tgx {
 tgx_status fail(tgx_error *err, tgx_status code, const char *fmt, ...);
 // has a state of the plan been created (or deserialized)?  From then on what the plan's states are built from -- the
-// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS and KEY_PROBE parameters -- is fixed.  (The flag keeps the name of its first user.)
+// fingerprint key, a JOINT_BINS binning, TEMPORAL parameters, HISTOGRAM edges, VALUE_RULE, VALUE_COUNTS, PAIR_COUNTS, GROUP_COUNTS, GROUP_SUMS, KEY_PROBE and ROW_PREDICATE parameters -- is fixed.  (The flag keeps the name of its first user.)
 inline bool plan_has_state(const tgx_plan *plan) { return plan->fp_key_locked.load(); }
 // the task (`*slot`, an index into the plan's tasks of that kind) behind spec `spec_index`, which must be a check of
 // `kind` ("spec 3 is not a <kind_name> check").  `foreign`: what to say when `st` is not a state of `plan`; nullptr: the

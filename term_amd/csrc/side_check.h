@@ -63,6 +63,7 @@ TGX_SIDE_KIND(paircounts)
 TGX_SIDE_KIND(groupcounts)
 TGX_SIDE_KIND(groupsums)
 TGX_SIDE_KIND(keyprobe)
+TGX_SIDE_KIND(rowpredicate)
 #undef TGX_SIDE_KIND
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
@@ -71,6 +72,7 @@ tgx_status paircounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupcounts_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status groupsums_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status keyprobe_plan_ready(const tgx_plan *plan, tgx_error *err);
+tgx_status rowpredicate_plan_ready(const tgx_plan *plan, tgx_error *err);
 // does a blob of `st` hold a KEY_PROBE task on string keys with a known, non-empty set?  Its identity is made of
 // fingerprints: such a blob carries the plan's fingerprint key (wire.cpp)
 TGX_HIDDEN bool keyprobe_blob_keyed(tgx_state *st);
@@ -95,6 +97,8 @@ inline constexpr SideKind kSideKinds[kNumSide] = {
      groupsums_check_column, groupsums_state_new, true},
     {TGX_CHECK_KEY_PROBE, "KEY_PROBE", keyprobe_plan_add, keyprobe_plan_ready, keyprobe_mark_columns,
      keyprobe_check_column, keyprobe_state_new, false},
+    {TGX_CHECK_ROW_PREDICATE, "ROW_PREDICATE", rowpredicate_plan_add, rowpredicate_plan_ready,
+     rowpredicate_mark_columns, rowpredicate_check_column, rowpredicate_state_new, false},
 };
 
 // where `kind` stands in kSideKinds (and in tgx_state::side, tgx_plan::side_on), or -1: not a kind of this file

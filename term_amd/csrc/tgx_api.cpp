@@ -199,8 +199,14 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
   for (size_t i = 0; i < n_specs; i++) {
     tgx_check_spec &sp = plan->specs[i];
     std::vector<int> tuple;
-    const bool takes_list = sp.kind == TGX_CHECK_DISTINCT || sp.kind == TGX_CHECK_KEY_PROBE;
-    if (takes_list && sp.n_columns >= 2) {
+    const bool takes_list =
+        sp.kind == TGX_CHECK_DISTINCT || sp.kind == TGX_CHECK_KEY_PROBE || sp.kind == TGX_CHECK_ROW_PREDICATE;
+    // (a ROW_PREDICATE spec names its columns through the list whatever their number: its leaves refer to positions)
+    if (sp.kind == TGX_CHECK_ROW_PREDICATE && (sp.n_columns < 1 || sp.n_columns > (uint32_t)kRowPredicateMaxCols || !sp.columns))
+      return fail(err, sp.n_columns > (uint32_t)kRowPredicateMaxCols ? TGX_UNSUPPORTED : TGX_INVALID_ARGUMENT,
+                  "spec %zu: ROW_PREDICATE names its columns through a column list of 1..%d (%u)", i, kRowPredicateMaxCols,
+                  sp.n_columns);
+    if (takes_list && (sp.n_columns >= 2 || sp.kind == TGX_CHECK_ROW_PREDICATE)) {
       if (sp.n_columns > (uint32_t)kMaxTupleCols || !sp.columns)
         return fail(err, TGX_UNSUPPORTED, "spec %zu: %s over %u columns (2..%d supported)", i,
                     sp.kind == TGX_CHECK_DISTINCT ? "DISTINCT" : "KEY_PROBE", sp.n_columns, kMaxTupleCols);
@@ -226,6 +232,11 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         KeyProbeTask &t = plan->key_probes.back();
         t.n_tuple = (int)tuple.size();
         std::copy(tuple.begin(), tuple.end(), t.tuple);
+      }
+      if (sp.kind == TGX_CHECK_ROW_PREDICATE) {
+        RowPredicateTask &t = plan->row_predicates.back();
+        t.n_columns = (int)tuple.size();
+        std::copy(tuple.begin(), tuple.end(), t.columns);
       }
       if (kSideKinds[s].reads_column2) max_col = std::max(max_col, sp.column2);
       continue;

@@ -13,6 +13,7 @@ core/builder_extensions.rs); a suite is serialised to the JSON of include/tgx_ho
 """
 import ctypes as C
 import json
+import re
 
 from . import _lib
 from ._lib import MEM_HOST, MEM_HOST_RETAINED, Column, TgxError, _Column, _Error
@@ -285,6 +286,11 @@ class CheckBuilder:
     def has_consistent_data_type(self, column, threshold):
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
+
+    def satisfies(self, sql_expression, hint=None):
+        """core/check.rs:685-694: CustomSqlConstraint::new(sql_expression, hint); raises where the reference's builder
+        panics on the constructor's Err"""
+        return self.constraint(CustomSqlConstraint(sql_expression, hint))
 
     def has_histogram(self, column, measures, max_distinct=10000):
         """Check::has_histogram: HistogramConstraint.new(column, measures) -- `measures` is what stands for the
@@ -741,6 +747,66 @@ class DataTypeConstraint:
         return DataTypeConstraint(column, DataTypeValidation.SpecificType(data_type))
 
 
+class CustomSqlConstraint:
+    """constraints/custom_sql.rs:24-93, 192-303: every row satisfies a boolean expression.  The expression is compiled by
+    the library's closed predicate subset (row_predicate(); include/tgx.h TGX_CHECK_ROW_PREDICATE) and counted on the
+    device; one outside the subset evaluates to the constraint's own error ("... not on the GPU path: <what>").  The
+    constructor raises what CustomSqlConstraint::new returns as Err (validate_sql_expression, :100-190): of several
+    forbidden words the first in the list's written order is named"""
+
+    FORBIDDEN = ("DROP", "DELETE", "INSERT", "UPDATE", "CREATE", "ALTER", "TRUNCATE", "GRANT", "REVOKE", "EXECUTE", "EXEC",
+                 "CALL", "MERGE", "REPLACE", "RENAME", "MODIFY", "SET", "COMMIT", "ROLLBACK", "SAVEPOINT", "BEGIN", "START",
+                 "TRANSACTION", "LOCK", "UNLOCK")
+
+    def __init__(self, expression, hint=None):
+        refusal = self.refusal(expression)
+        if refusal:
+            raise TgxError(1, "Validation failed: " + refusal)
+        self.expression, self.hint = expression, hint
+        self.spec = {"type": "custom_sql", "expression": expression}
+        if hint is not None:
+            self.spec["hint"] = hint
+
+    try_new = classmethod(lambda cls, expression, hint=None: cls(expression, hint))
+
+    @classmethod
+    def refusal(cls, sql):
+        """validate_sql_expression: the reference's message, or None for an expression it accepts"""
+        upper = "".join(chr(ord(c) - 32) if "a" <= c <= "z" else c for c in sql)  # (ASCII, as the words are)
+        for word in cls.FORBIDDEN:
+            if re.search(r"(?<![A-Za-z0-9_])%s(?![A-Za-z0-9_])" % word, upper):
+                return "SQL expression contains forbidden operation: " + word
+        if ";" in sql:
+            return "SQL expression cannot contain semicolons"
+        if "--" in sql or "/*" in sql or "*/" in sql:
+            return "SQL expression cannot contain comments"
+        return None
+
+    def name(self):
+        return "custom_sql"
+
+    def metadata(self):
+        """custom_sql.rs:288-302"""
+        m = {"description": "Checks that all rows satisfy the SQL expression: " + self.expression,
+             "expression": self.expression, "constraint_type": "custom"}
+        if self.hint is not None:
+            m["hint"] = self.hint
+        return m
+
+    def verdict(self, satisfied, total):
+        """custom_sql.rs:234-281 on given counts: (status, metric, message)"""
+        if total == 0:
+            return "skipped", None, "No data to validate"
+        ratio = float(satisfied) / float(total)
+        if ratio == 1.0:
+            return "success", ratio, None
+        failed = int(float(total) - float(satisfied))
+        if self.hint is not None:
+            return "failure", ratio, "%s (%d rows failed the condition)" % (self.hint, failed)
+        return "failure", ratio, ("Custom SQL condition not satisfied for %d rows. Expression: '%s'"
+                                  % (failed, self.expression))
+
+
 class HistogramMeasure:
     """One named measure of a column's value histogram held to an Assertion (constraints/histogram.rs:37-127): the form a
     histogram assertion takes where no function can travel (JSON, Python)"""
@@ -1104,7 +1170,7 @@ class _Analyzer:
 
     def metric_key(self):
         t = self.name()
-        if t in ("size", "standard_deviation", "histogram"):  # (these analyzers do not override metric_key)
+        if t in ("size", "standard_deviation", "histogram", "compliance"):  # (these analyzers do not override metric_key)
             return t
         if t == "correlation":
             return "correlation_%s_%s_%s" % (self.spec.get("method", "pearson"), self.spec["column1"], self.spec["column2"])
@@ -1253,6 +1319,25 @@ def HistogramAnalyzer(column, num_buckets=10, strict_reference_types=True):
     return _Analyzer(spec)
 
 
+COMPLIANCE_FORBIDDEN = ("drop", "delete", "insert", "update", "create", "alter", "grant", "revoke", "exec", "execute",
+                        "union", "select", "--", "/*", "*/")
+
+
+def compliance_forbidden_keyword(predicate):
+    """ComplianceAnalyzer::validate_predicate (advanced/compliance.rs:88-108): the first forbidden keyword, in the list's
+    order, that the lower-cased predicate CONTAINS (a substring test: `created_at` holds `create`), or None"""
+    lower = predicate.lower()
+    return next((w for w in COMPLIANCE_FORBIDDEN if w in lower), None)
+
+
+def ComplianceAnalyzer(name, predicate):
+    """advanced/compliance.rs:37-204: the fraction of rows on which `predicate` is TRUE, counted on the device under the
+    library's closed predicate subset (TGX_CHECK_ROW_PREDICATE).  State {"compliant_count", "total_count"}; the metric is
+    a Double, 1.0 on an empty table; metric_key is "compliance".  A forbidden keyword or a predicate outside the subset
+    is the analyzer's error when it runs, as the reference validates in compute_state_from_data"""
+    return _Analyzer({"type": "compliance", "name": name, "predicate": predicate})
+
+
 def EntropyAnalyzer(column, max_unique_values=10000, arrow_type=None):
     """TG/analyzers/advanced/entropy.rs over TGX_CHECK_VALUE_COUNTS: entropy (bits), normalized entropy, Gini impurity,
     effective and unique values, the ten most frequent values; the state is {value_counts, total_count, truncated}.
@@ -1345,6 +1430,7 @@ def _host():
         L.tgx_host_constraint_verdict_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_temporal_params_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_value_rule_params_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_row_predicate_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_validate_identifier.argtypes = [C.c_char_p, E]
         L.tgx_host_assertion_json.argtypes = [C.c_char_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), E]
         L.tgx_host_run_analysis_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_Column),
@@ -1412,6 +1498,16 @@ def value_rule_params(constraint):
     out = C.c_char_p()
     err = _Error()
     _host_check(_host().tgx_host_value_rule_params_json(json.dumps(constraint).encode(), C.byref(out), C.byref(err)), err)
+    return json.loads(_take(out))
+
+
+def row_predicate(expression):
+    """what the predicate compiler of Check.satisfies / ComplianceAnalyzer makes of `expression`
+    (tgx_host_row_predicate_json): {"columns", "leaves", "program", "literals_hex"}; TgxError (TGX_UNSUPPORTED) naming
+    the first thing outside the subset otherwise.  Needs no device"""
+    out = C.c_char_p()
+    err = _Error()
+    _host_check(_host().tgx_host_row_predicate_json(expression.encode(), C.byref(out), C.byref(err)), err)
     return json.loads(_take(out))
 
 

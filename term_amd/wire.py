@@ -95,6 +95,15 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                                rows > 0, every non_null <= its rows, a sum of 0 where non_null is 0, every length <=
                                max_value_bytes, no key twice, values 0 only with seen 0 and no keys, and
                                sum(rows) + null_group_rows + overflow_rows + long_rows == seen.
+    and ONLY for plans with ROW_PREDICATE checks, behind every other section:
+    u32 magic 'RRPD', u32 n_tasks
+    n_tasks     x { u32 n_leaves, n_ops, n_literal_bytes, 0            (the plan's predicate as it was set: a blob counted
+                    n_leaves x { i32 kind, op, col, col2; u32 flags,    under another program, other leaves or other literal
+                                 lit_offset, lit_len, 0; i64 lit_i;     bytes is refused; what a leaf does not read is zero)
+                                 f64 lit_f }
+                    n_ops x u16 (code | arg << 8); u8 literals[n_literal_bytes]
+                    u64 seen, satisfied, unknown }
+                               satisfied + unknown <= seen; the failed rows are the rest.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -111,6 +120,7 @@ PAIR_COUNTS_MAGIC = 0x544E4350  # 'PCNT'
 GROUP_COUNTS_MAGIC = 0x544E4347  # 'GCNT'
 GROUP_SUMS_MAGIC = 0x4D555347  # 'GSUM'
 KEY_PROBE_MAGIC = 0x4252504B  # 'KPRB'
+ROW_PREDICATE_MAGIC = 0x44505252  # 'RRPD'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -345,9 +355,22 @@ def key_probe_state(max_missing_keys, missing=(), seen=None, nulls=0, matched=0,
     return out
 
 
+def row_predicate_state(leaves, program, literals, seen, satisfied, unknown=0):
+    """a ROW_PREDICATE task: the plan's predicate as it was set (`leaves`: dicts with the fields of
+    tgx_row_predicate_leaf, those left out 0; `program`: (code, arg) pairs or packed ints; `literals`: the pool's
+    bytes) and its three counters"""
+    out = struct.pack("<4I", len(leaves), len(program), len(literals), 0)
+    for leaf in leaves:
+        g = leaf.get
+        out += struct.pack("<4i4Iqd", g("kind", 0), g("op", 0), g("col", 0), g("col2", 0), g("flags", 0),
+                           g("lit_offset", 0), g("lit_len", 0), 0, g("lit_i", 0), g("lit_f", 0.0))
+    out += b"".join(struct.pack("<H", op if isinstance(op, int) else (op[0] | (op[1] << 8))) for op in program)
+    return out + bytes(literals) + struct.pack("<3Q", seen, satisfied, unknown)
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
          value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=(), key_probes=(),
-         fingerprint_key=None):
+         fingerprint_key=None, row_predicates=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     # (no string keys in a state packed from plain numbers, unless a KEY_PROBE task on string keys knows its parent set:
@@ -370,5 +393,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", GROUP_SUMS_MAGIC, len(group_sums)) + b"".join(group_sums)
     if key_probes:
         tail += struct.pack("<II", KEY_PROBE_MAGIC, len(key_probes)) + b"".join(key_probes)
+    if row_predicates:
+        tail += struct.pack("<II", ROW_PREDICATE_MAGIC, len(row_predicates)) + b"".join(row_predicates)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
