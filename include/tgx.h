@@ -415,7 +415,19 @@ typedef enum tgx_check_kind {
    * holds the exact semantics); a spec without it makes tgx_state_create fail.  Read with tgx_row_predicate_get;
    * tgx_result carries total = rows seen, matches = satisfied rows, non_null = seen - unknown.  The state is additive
    * counters: tgx_merge, blobs and tgx_allreduce add them; a blob counted under another predicate is refused. */
-  TGX_CHECK_ROW_PREDICATE = 20
+  TGX_CHECK_ROW_PREDICATE = 20,
+  /* The type classes of one STRING column: every non-NULL value is read once and put into exactly one of seven classes
+   * -- the device side of the reference's DataTypeAnalyzer (TG/analyzers/advanced/data_type.rs:129-150), one
+   *     SELECT CASE WHEN <boolean> .. WHEN <integer> .. WHEN <double> .. WHEN <date> .. WHEN <timestamp> .. ELSE 'string'
+   *            END, COUNT(*) FROM t WHERE c IS NOT NULL GROUP BY 1
+   * One column (`column`; `column2` must be -1; no column list), no parameters.  Specs on the same column share one
+   * task and one walk.  Read with tgx_type_classes_get (below, which holds the classes' exact grammar); tgx_result
+   * carries total = rows seen and non_null.  Utf8, LargeUtf8, Utf8View and Dictionary<Int32, Utf8> columns are taken (a
+   * NULL dictionary entry and an index outside the dictionary are NULL rows, as for VALUE_COUNTS); every other type is
+   * TGX_UNSUPPORTED from tgx_update, before anything runs, and the state stays usable.  The state is nine additive
+   * counters: tgx_merge, blobs (a section of its own, behind all others, only for plans with such specs) and
+   * tgx_allreduce add them. */
+  TGX_CHECK_TYPE_CLASSES = 21
 } tgx_check_kind;
 
 enum {
@@ -1034,6 +1046,52 @@ typedef struct tgx_row_predicate_counts {
 tgx_status tgx_row_predicate_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
                                  tgx_row_predicate_counts *out, tgx_error *err);
 
+/* ---- type classes (TGX_CHECK_TYPE_CLASSES; TG/analyzers/advanced/data_type.rs:129-150) ----------------------------- *
+ * The classes are SYNTACTIC: defined on the value's bytes, closed, and tried in the order below -- the first that fits
+ * wins.  D is an ASCII digit.  The letters of BOOLEAN, of the DOUBLE specials and the exponent's e are compared under
+ * ASCII case folding only; the T and the Z of DATETIME are upper case.  No whitespace is trimmed.  A byte at or above
+ * 0x80 fits no grammar.
+ *   BOOLEAN    exactly 0 or 1, or true / false in any ASCII case.
+ *   INTEGER    0 | -?[1-9]D*  with the value in [-2^31, 2^31 - 1]: the canonical text of an Int32 (so that
+ *              CAST(TRY_CAST(c AS INT) AS VARCHAR) = c holds however lenient a parser is).  +5, 007, -0 and 2147483648
+ *              are not INTEGER and go on to DOUBLE.
+ *   DOUBLE     [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)?  or  [+-]?(nan|inf|infinity), of any length; no value is out of
+ *              range (overflow is +-inf, not a failure).
+ *   DATE       at most 10 bytes, DDDD-D{1,2}-D{1,2}, a valid day of the proleptic Gregorian calendar in the years
+ *              0000 .. 9999 (year 0 is a leap year).
+ *   DATETIME   more than 10 bytes: DDDD-DD-DD as a valid date; then T or one space; then hh:mm:ss with hh <= 23,
+ *              mm <= 59, ss <= 59; optionally . and 1 .. 9 digits; optionally Z or [+-]hh:mm with hh <= 23, mm <= 59.
+ *   UNDECIDED  none of the above, and the value begins DDDD- or [+-]D{4,}- : everything a date or timestamp parser
+ *              could conceivably take in a form this contract does not spell out (single-digit fields in odd places, t,
+ *              hh:mm without seconds, offsets without a colon, named zones, leap seconds, signed extended years, invalid
+ *              calendar dates).  Reported, never guessed.
+ *   STRING     everything else, the empty string included.
+ * Identities:  seen == non_null + NULL rows;
+ *              non_null == boolean_rows + integer_rows + double_rows + date_rows + datetime_rows + string_rows +
+ *                          undecided_rows. */
+enum {
+  TGX_TYPE_CLASS_BOOLEAN = 0,
+  TGX_TYPE_CLASS_INTEGER = 1,
+  TGX_TYPE_CLASS_DOUBLE = 2,
+  TGX_TYPE_CLASS_DATE = 3,
+  TGX_TYPE_CLASS_DATETIME = 4,
+  TGX_TYPE_CLASS_STRING = 5,
+  TGX_TYPE_CLASS_UNDECIDED = 6
+};
+typedef struct tgx_type_classes_counts {
+  uint64_t seen;     /* rows handed to tgx_update */
+  uint64_t non_null; /* the SQL's WHERE c IS NOT NULL */
+  uint64_t boolean_rows;
+  uint64_t integer_rows;
+  uint64_t double_rows;
+  uint64_t date_rows;
+  uint64_t datetime_rows;
+  uint64_t string_rows;
+  uint64_t undecided_rows;
+} tgx_type_classes_counts;
+tgx_status tgx_type_classes_get(const tgx_plan *plan, tgx_state *state, size_t spec_index,
+                                tgx_type_classes_counts *out, tgx_error *err);
+
 /* ---- value counts (TGX_CHECK_VALUE_COUNTS; TG/constraints/histogram.rs:205-391) ----------------------------------- */
 typedef struct tgx_value_counts_summary {
   uint64_t seen;          /* rows handed to tgx_update */
@@ -1429,7 +1487,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "row_predicate", "hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "row_predicate", "type_classes","hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -113,7 +113,8 @@ tgx_status tgx_host_assertion_json(const char *assertion_json, double value, int
  *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10, "max_pairs": N (optional),
  *      "max_value_bytes": 256 (optional), "arrow_types": ["Utf8", "Int64"] (optional)},
  *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true},
- *     {"type": "value_entropy", "column": "c", "max_unique_values": 10000, "arrow_type": "Int64" (optional)}]}
+ *     {"type": "value_entropy", "column": "c", "max_unique_values": 10000, "arrow_type": "Int64" (optional)},
+ *     {"type": "data_type", "column": "c", "arrow_type": "Int32" (optional)}]}
  * "value_entropy" is the tag of EntropyAnalyzer (TG/analyzers/advanced/entropy.rs; name() "entropy", metric key
  * "entropy.<column>"): the tag "entropy" is not taken, it stays an unknown analyzer type.
  * AnalysisRunner::run: every analyzer's aggregates planned into ONE tgx_plan, one pass over the table; the
@@ -143,7 +144,8 @@ tgx_status tgx_host_metric_from_state_json(const char *analyzer_json, const char
 /* What an analyzer plans for columns of the given tgx_types (column_types_json: an array of tgx_type numbers parallel to
  * the analyzer's columns; 0 = unknown): {"requests": [{"kind", "column", "column2", "pair_counts": {"max_pairs",
  * "max_value_bytes", "x_mode", "y_mode"} (TGX_CHECK_PAIR_COUNTS only), "group_counts": {"max_groups", "max_value_bytes"}
- * (TGX_CHECK_GROUP_COUNTS only)}]}.  Needs no device. */
+ * (TGX_CHECK_GROUP_COUNTS only), "value_rule": {"mode", "flags", "lo_i", "hi_i", "lo_f", "hi_f"} (TGX_CHECK_VALUE_RULE
+ * only)}]}.  Needs no device. */
 tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *column_types_json, char **out_json,
                                        tgx_error *err);
 
@@ -160,6 +162,19 @@ tgx_status tgx_host_pair_counts_state_json(const char *analyzer_json, const char
  * AnalyzerError is returned as TGX_INVALID_ARGUMENT with its text in err->msg. */
 tgx_status tgx_host_group_counts_state_json(const char *analyzer_json, const char *group_counts_json,
                                             char **out_state_json, tgx_error *err);
+
+/* The class (TGX_TYPE_CLASS_*, include/tgx.h) the lexer of TGX_CHECK_TYPE_CLASSES gives the value bytes[0 .. len): the
+ * same function the kernels compile (kernels/typeclass_lex.h).  `bytes` may be NULL when len is 0.  Needs no device. */
+int32_t tgx_host_type_class(const uint8_t *bytes, uint64_t len);
+
+/* The state a "data_type" analyzer ({"type": "data_type", "column": "c", "arrow_type": "Int32" (optional: the column's
+ * Arrow DataType where the table does not say it)}; TG/analyzers/advanced/data_type.rs) builds from given counts; needs
+ * no device.  counts_json is either the nine counters of tgx_type_classes_counts by their field names (a string column;
+ * absent ones are 0), or {"results": [{"total", "non_null", "matches"}, ..]}: the tgx_results that answer the requests
+ * the analyzer plans for an integer column (two VALUE_RULE requests) or a float column (one COUNT).  Returns
+ * {"type_counts": {label: n}, "total_count": n}; undecided_rows > 0 is TGX_INVALID_ARGUMENT with the analyzer's error. */
+tgx_status tgx_host_data_type_state_json(const char *analyzer_json, const char *counts_json, char **out_state_json,
+                                         tgx_error *err);
 
 /* ValidationSuite::run over SEVERAL registered tables: what tgx_host_run_suite_json does, with every table of `tables`
  * registered under its own name (the suite's table among them, under the suite's table_name; a suite whose table is not

@@ -36,6 +36,11 @@ PRED_IS_NULL, PRED_CMP_LITERAL, PRED_CMP_COLUMNS, PRED_STR_EQ = 1, 2, 3, 4
 PRED_EQ, PRED_LT, PRED_LE, PRED_GT, PRED_GE = 1, 2, 3, 4, 5
 PRED_LITERAL_IS_DOUBLE = 1
 PRED_PUSH, PRED_AND, PRED_OR, PRED_NOT = 1, 2, 3, 4
+TYPE_CLASSES = 21  # the syntactic class of every non-NULL value of a string column (State.type_classes)
+# the classes in the order they are tried (TGX_TYPE_CLASS_*: what host_type_class answers)
+(TYPE_CLASS_BOOLEAN, TYPE_CLASS_INTEGER, TYPE_CLASS_DOUBLE, TYPE_CLASS_DATE, TYPE_CLASS_DATETIME, TYPE_CLASS_STRING,
+ TYPE_CLASS_UNDECIDED) = range(7)
+TYPE_CLASS_NAMES = ("boolean", "integer", "double", "date", "datetime", "string", "undecided")
 GROUP_SUMS = 18  # COUNT(*), COUNT(col) and SUM(col) per group of a second column, for a bounded number of groups (Plan.set_group_sums)
 GROUP_SUMS_MAX_GROUPS, GROUP_SUMS_MAX_VALUE_BYTES = 65536, 256
 FLAG_VARIANCE, FLAG_MULTIPLICITY, FLAG_TRIM, FLAG_CASE_INSENSITIVE, FLAG_NULL_IS_VALID = 1, 2, 4, 8, 16
@@ -157,6 +162,12 @@ class RowPredicateParams(C.Structure):
 class RowPredicateCounts(C.Structure):
     """tgx_row_predicate_counts (include/tgx.h)"""
     _fields_ = [("seen", C.c_uint64), ("satisfied", C.c_uint64), ("unknown", C.c_uint64), ("failed", C.c_uint64)]
+
+
+class TypeClassesCounts(C.Structure):
+    """tgx_type_classes_counts (include/tgx.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("seen", "non_null", "boolean_rows", "integer_rows", "double_rows", "date_rows",
+                                          "datetime_rows", "string_rows", "undecided_rows")]
 
 
 class ValueCountsParams(C.Structure):
@@ -419,6 +430,9 @@ def lib():
         L.tgx_value_rule_get.argtypes = [vp, vp, sz, C.POINTER(ValueRuleCounts), E]
         L.tgx_plan_set_row_predicate.argtypes = [vp, sz, C.POINTER(RowPredicateParams), E]
         L.tgx_row_predicate_get.argtypes = [vp, vp, sz, C.POINTER(RowPredicateCounts), E]
+        L.tgx_type_classes_get.argtypes = [vp, vp, sz, C.POINTER(TypeClassesCounts), E]
+        L.tgx_host_type_class.argtypes = [C.c_char_p, u64]
+        L.tgx_host_type_class.restype = C.c_int32
         L.tgx_plan_set_value_counts.argtypes = [vp, sz, C.POINTER(ValueCountsParams), E]
         L.tgx_value_counts_get.argtypes = [vp, vp, sz, C.POINTER(ValueCountsSummary), E]
         L.tgx_value_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
@@ -502,6 +516,13 @@ def init(device_id=-1, distinct_capacity_hint=0, flags=0):
     opts = _Options(device_id, flags, distinct_capacity_hint)
     _check(lib().tgx_init(C.byref(opts), C.byref(err)), err)
     _INITED = True
+
+
+def host_type_class(value):
+    """tgx_host_type_class: the class (TYPE_CLASS_*) the lexer of TYPE_CLASSES gives the bytes of `value` (bytes, or a
+    str taken as UTF-8) -- the function the kernels compile, run on the host; needs no device"""
+    b = value.encode("utf-8") if isinstance(value, str) else bytes(value)
+    return lib().tgx_host_type_class(b, len(b))
 
 
 def _ptr_of(buf):
@@ -1201,6 +1222,14 @@ class State:
         err = _Error()
         _check(lib().tgx_row_predicate_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
         return out.seen, out.satisfied, out.unknown, out.failed
+
+    def type_classes(self, spec_index):
+        """tgx_type_classes_get: {"seen", "non_null", "boolean_rows", "integer_rows", "double_rows", "date_rows",
+        "datetime_rows", "string_rows", "undecided_rows"}"""
+        out = TypeClassesCounts()
+        err = _Error()
+        _check(lib().tgx_type_classes_get(self.plan.h, self.h, spec_index, C.byref(out), C.byref(err)), err)
+        return {name: getattr(out, name) for name, _ in TypeClassesCounts._fields_}
 
     def _counted_entries(self, call, entry_type, spec_index, *more):
         """the two calls of a *_entries function: ask for the sizes, allocate, fetch; (the entries, the bytes their

@@ -976,6 +976,136 @@ class EntropyAnalyzer : public ColumnAnalyzer {
   std::string arrow_type_;
 };
 
+// advanced/data_type.rs: the CASE over TRY_CASTs, counted per inferred type (:129-150).  What is planned depends on the
+// column (plan_for):
+//   a string column          one TGX_CHECK_TYPE_CLASSES request; the device's syntactic classes become the reference's
+//                            labels in state_from_type_classes
+//   a declared integer type  (Int8 .. Int64, UInt8 .. UInt32) two VALUE_RULE BETWEEN requests that share one walk:
+//                            [0, 1] and the Int32 range.  CAST(c AS VARCHAR) of an integer is its canonical text, so
+//                            boolean = valid[0, 1], integer = valid[Int32] - boolean, double = non_null - valid[Int32]
+//                            (TRY_CAST AS DOUBLE of an Int64 never fails)
+//   Float32 / Float64        a COUNT: every non-NULL row is 'double' (CAST(1.0 AS VARCHAR) is "1.0", never an integer's
+//                            text, and a float is no boolean's text)
+//   declared temporal, decimal, boolean, binary, UInt64: the analyzer's own error
+// State {"type_counts": {label: u64}, "total_count": u64}; a class without rows is absent, as the GROUP BY has no row
+// for it.
+constexpr const char *kDatetimeLabel = "date";  // UNVERIFIED: arrow-cast's Date32 parser is believed to
+                                                // take a text longer than 10 bytes through the timestamp parser and keep
+                                                // the date, so the CASE stops at 'date' and 'timestamp' is unreachable
+                                                // from a string column
+class DataTypeAnalyzer : public ColumnAnalyzer {
+ public:
+  DataTypeAnalyzer(std::string c, std::string arrow_type) : ColumnAnalyzer(std::move(c)), arrow_type_(std::move(arrow_type)) {}
+  std::string name() const override { return "data_type"; }
+  enum Route { kStrings, kIntegers, kFloats };
+  Route route_for(int type, const std::string &declared) const {
+    const std::string &given = !arrow_type_.empty() ? arrow_type_ : declared;
+    std::string t;
+    for (char ch : given) t += (char)tolower((unsigned char)ch);
+    auto starts = [&](const char *p) { return t.compare(0, strlen(p), p) == 0; };
+    if (!t.empty()) {
+      if (starts("utf8") || starts("largeutf8") || starts("dictionary") || starts("string") || starts("large_string"))
+        return kStrings;
+      if ((starts("int") && !starts("interval")) || (starts("uint") && !starts("uint64"))) return kIntegers;
+      if (starts("float32") || starts("float64")) return kFloats;
+      throw AnalyzerError::invalid_data("column '" + column_ + "' (" + given +
+                                        ") is not on the GPU path: data_type takes string, integer (other than UInt64) "
+                                        "and Float32 / Float64 columns");
+    }
+    switch (type) {
+      case TGX_FLOAT64: case TGX_FLOAT32: return kFloats;
+      case TGX_UINT64: case TGX_BOOL:
+        throw AnalyzerError::invalid_data("column '" + column_ + "' (" + (type == TGX_BOOL ? "Boolean" : "UInt64") +
+                                          ") is not on the GPU path: data_type takes string, integer (other than UInt64) "
+                                          "and Float32 / Float64 columns");
+      case 0: case TGX_UTF8: case TGX_LARGE_UTF8: case TGX_UTF8_VIEW: case TGX_DICT32_UTF8: return kStrings;
+      default: return kIntegers;
+    }
+  }
+  std::vector<SpecRequest> plan() const override { return {req(TGX_CHECK_TYPE_CLASSES, column_)}; }
+  std::vector<SpecRequest> plan_for(const std::vector<int> &types, const std::vector<std::string> &declared) const override {
+    const Route route = route_for(types.empty() ? 0 : types[0], declared.empty() ? std::string() : declared[0]);
+    if (route == kStrings) return plan();
+    if (route == kFloats) return {req(TGX_CHECK_COUNT, column_)};
+    std::vector<SpecRequest> out;
+    for (int k = 0; k < 2; k++) {
+      SpecRequest r = req(TGX_CHECK_VALUE_RULE, column_);
+      tgx_value_rule_params p;
+      memset(&p, 0, sizeof(p));
+      p.mode = TGX_RULE_BETWEEN;
+      p.lo_i = k == 0 ? 0 : INT32_MIN;
+      p.hi_i = k == 0 ? 1 : INT32_MAX;
+      p.lo_f = (double)p.lo_i;
+      p.hi_f = (double)p.hi_i;
+      r.value_rule = p;
+      out.push_back(r);
+    }
+    return out;
+  }
+  static json::Value state_of(const std::vector<std::pair<const char *, uint64_t>> &counts) {
+    std::vector<std::pair<std::string, json::Value>> types;
+    uint64_t total = 0;
+    for (const auto &c : counts) {
+      total += c.second;
+      if (c.second == 0) continue;
+      bool merged = false;
+      for (auto &t : types)
+        if (t.first == c.first) {
+          t.second = jcount(t.second.as_u64() + c.second);
+          merged = true;
+        }
+      if (!merged) types.push_back({c.first, jcount(c.second)});
+    }
+    return jobj({{"type_counts", jobj(types)}, {"total_count", jcount(total)}});
+  }
+  // the integer route (two VALUE_RULE results) and the float route (one COUNT)
+  json::Value state_from_results(const std::vector<const tgx_result *> &r, const std::vector<int> &) const override {
+    if (r.size() == 2) {
+      const uint64_t non_null = (uint64_t)r[1]->non_null, small = (uint64_t)r[0]->matches, fits = (uint64_t)r[1]->matches;
+      return state_of({{"boolean", small}, {"integer", fits - small}, {"double", non_null - fits}});
+    }
+    return state_of({{"double", (uint64_t)r[0]->non_null}});
+  }
+  json::Value state_from_type_classes(const tgx_type_classes_counts &c) const override {
+    if (c.undecided_rows > 0)
+      throw AnalyzerError::invalid_data("column '" + column_ + "' is not on the GPU path: " +
+                                        std::to_string((unsigned long long)c.undecided_rows) +
+                                        " values look like dates in a form this path does not decide");
+    return state_of({{"boolean", c.boolean_rows}, {"integer", c.integer_rows}, {"double", c.double_rows},
+                     {"date", c.date_rows}, {kDatetimeLabel, c.datetime_rows}, {"string", c.string_rows}});
+  }
+  json::Value merge_states(const std::vector<json::Value> &states) const override {  // :94-109
+    std::vector<std::pair<std::string, json::Value>> types;
+    uint64_t total = 0;
+    for (const json::Value &s : states) {
+      total += u(s, "total_count");
+      const json::Value *tc = s.get("type_counts");
+      if (!tc || !tc->is(json::Value::Object)) continue;
+      for (const auto &kv : tc->obj) {
+        bool merged = false;
+        for (auto &t : types)
+          if (t.first == kv.first) {
+            t.second = jcount(t.second.as_u64() + kv.second.as_u64());
+            merged = true;
+          }
+        if (!merged) types.push_back({kv.first, jcount(kv.second.as_u64())});
+      }
+    }
+    return jobj({{"type_counts", jobj(types)}, {"total_count", jcount(total)}});
+  }
+  MetricValue metric_from_state(const json::Value &s) const override {  // :193-202: a Map of Long
+    MetricValue m;
+    m.kind = MetricValue::Map;
+    if (const json::Value *tc = s.get("type_counts"))
+      if (tc->is(json::Value::Object))
+        for (const auto &kv : tc->obj) m.map.push_back({kv.first, MetricValue::of_long((int64_t)kv.second.as_u64())});
+    return m;
+  }
+
+ private:
+  std::string arrow_type_;  // the column's Arrow DataType name where the table does not say
+};
+
 // basic/grouped_completeness.rs + grouped.rs: CompletenessAnalyzer::with_grouping, "completeness per segment",
 //   SELECT g, COUNT(*) AS total_count, COUNT(col) AS non_null_count FROM t GROUP BY g
 //   ORDER BY COUNT(col) * 1.0 / COUNT(*) DESC LIMIT max_groups + 1                    (grouped_completeness.rs:119-150)
@@ -1350,6 +1480,7 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
     return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"));
   }
   if (t == "compliance") return std::make_shared<ComplianceAnalyzer>(v.get_str("name"), v.get_str("predicate"));
+  if (t == "data_type") return std::make_shared<DataTypeAnalyzer>(col(), v.get_str("arrow_type"));
   // ("entropy" stays an unknown type: the tag of EntropyAnalyzer is "value_entropy")
   if (t == "value_entropy")
     return std::make_shared<EntropyAnalyzer>(col(), v.get_u64("max_unique_values", 10000), v.get_str("arrow_type"));
@@ -1469,7 +1600,9 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
                                                    : tgx_plan_set_joint_binning(hh.plan, i, &fu.binning, &err);
     }
     for (size_t i = 0; s == TGX_OK && !follow_ups && i < requests.size(); i++) {
-      if (requests[i].value_counts) s = tgx_plan_set_value_counts(hh.plan, i, &*requests[i].value_counts, &err);
+      if (requests[i].value_rule) s = tgx_plan_set_value_rule(hh.plan, i, &*requests[i].value_rule, &err);
+      if (s == TGX_OK && requests[i].value_counts)
+        s = tgx_plan_set_value_counts(hh.plan, i, &*requests[i].value_counts, &err);
       if (requests[i].pair_counts) s = tgx_plan_set_pair_counts(hh.plan, i, &*requests[i].pair_counts, &err);
       if (s == TGX_OK && requests[i].group_counts)
         s = tgx_plan_set_group_counts(hh.plan, i, &*requests[i].group_counts, &err);
@@ -1641,6 +1774,13 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
           }
         } else if (an.reads_group_counts()) {
           st = an.state_from_group_counts(read_group_counts(h.plan, h.state, planned[a].spec_index[0]));
+        } else if (!planned[a].reqs.empty() && planned[a].reqs[0].kind == TGX_CHECK_TYPE_CLASSES) {
+          tgx_type_classes_counts counts;
+          tgx_error err;
+          memset(&err, 0, sizeof(err));
+          const tgx_status s = tgx_type_classes_get(h.plan, h.state, planned[a].spec_index[0], &counts, &err);
+          if (s != TGX_OK) throw AnalyzerError::query(std::string(tgx_status_name(s)) + ": " + err.msg);
+          st = an.state_from_type_classes(counts);
         } else {
           st = an.two_pass()
                    ? an.state_from_follow_up(followed[a].first, followed[a].counted ? &followed[a].second : nullptr)

@@ -184,6 +184,9 @@ class Analyzer {
   // from the groups the device counted
   virtual bool reads_group_counts() const { return false; }
   virtual json::Value state_from_group_counts(const GroupCounts &) const { return json::Value(); }
+  // An analyzer whose planned request is a TGX_CHECK_TYPE_CLASSES one (DataTypeAnalyzer on a string column) builds its
+  // state from the nine counters of tgx_type_classes_get
+  virtual json::Value state_from_type_classes(const tgx_type_classes_counts &) const { return json::Value(); }
   virtual bool two_pass() const { return false; }
   virtual std::optional<FollowUp> follow_up(const FirstPass &) const { return std::nullopt; }
   virtual json::Value state_from_follow_up(const FirstPass &, const SecondPass *) const { return json::Value(); }

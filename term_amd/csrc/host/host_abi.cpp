@@ -9,6 +9,7 @@
 #include "analyzers.h"
 #include "custom_sql.h"
 #include "datatype.h"
+#include "../kernels/typeclass_lex.h"
 #include "value_counts.h"
 #include "temporal.h"
 #include "term_guard.h"
@@ -523,10 +524,64 @@ extern "C" tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, con
       if (r.group_counts)
         o += ", \"group_counts\": {\"max_groups\": " + std::to_string(r.group_counts->max_groups) +
              ", \"max_value_bytes\": " + std::to_string(r.group_counts->max_value_bytes) + "}";
+      if (r.value_rule) o += ", \"value_rule\": " + value_rule_json(*r.value_rule);
       o += "}";
     }
     o += "]}";
     *out_json = dup_string(o);
+    return TGX_OK;
+  } catch (const AnalyzerError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.text);
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" int32_t tgx_host_type_class(const uint8_t *bytes, uint64_t len) {
+  tgx::TcByteFetch f{bytes};
+  return (int32_t)tgx::type_class_of(f, bytes ? len : 0);
+}
+
+extern "C" tgx_status tgx_host_data_type_state_json(const char *analyzer_json, const char *counts_json,
+                                                    char **out_state_json, tgx_error *err) {
+  if (!analyzer_json || !counts_json || !out_state_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_state_json = nullptr;
+  try {
+    auto a = analyzer_from_json(parse_json_text(analyzer_json, "analyzer"));
+    json::Value v = parse_json_text(counts_json, "counts");
+    if (!v.is(json::Value::Object)) return hfail(err, TGX_INVALID_ARGUMENT, "counts must be a JSON object");
+    if (const json::Value *rs = v.get("results")) {
+      if (!rs->is(json::Value::Array)) return hfail(err, TGX_INVALID_ARGUMENT, "results must be a JSON array");
+      std::vector<tgx_result> results(rs->arr.size());
+      std::vector<const tgx_result *> r;
+      for (size_t i = 0; i < rs->arr.size(); i++) {
+        memset(&results[i], 0, sizeof(tgx_result));
+        results[i].total = (int64_t)rs->arr[i].get_u64("total", 0);
+        results[i].non_null = (int64_t)rs->arr[i].get_u64("non_null", 0);
+        results[i].matches = (int64_t)rs->arr[i].get_u64("matches", 0);
+        r.push_back(&results[i]);
+      }
+      if (r.empty() || r.size() > 2) return hfail(err, TGX_INVALID_ARGUMENT, "results holds one or two tgx_results");
+      *out_state_json = dup_string(json_dump(a->state_from_results(r, std::vector<int>())));
+      return TGX_OK;
+    }
+    tgx_type_classes_counts c;
+    c.seen = v.get_u64("seen", 0);
+    c.non_null = v.get_u64("non_null", 0);
+    c.boolean_rows = v.get_u64("boolean_rows", 0);
+    c.integer_rows = v.get_u64("integer_rows", 0);
+    c.double_rows = v.get_u64("double_rows", 0);
+    c.date_rows = v.get_u64("date_rows", 0);
+    c.datetime_rows = v.get_u64("datetime_rows", 0);
+    c.string_rows = v.get_u64("string_rows", 0);
+    c.undecided_rows = v.get_u64("undecided_rows", 0);
+    *out_state_json = dup_string(json_dump(a->state_from_type_classes(c)));
     return TGX_OK;
   } catch (const AnalyzerError &e) {
     return hfail(err, TGX_INVALID_ARGUMENT, e.text);

@@ -310,8 +310,14 @@ struct RowPredicateTask {
   tgx_row_predicate_params params;
 };
 
+// TGX_CHECK_TYPE_CLASSES (typeclass_device.cpp): one task per COLUMN -- the specs of one column share its task and its
+// walk; `spec_index`: the first of them.  The kind has no parameters
+struct TypeClassesTask {
+  int column, spec_index;
+};
+
 struct SideCheck;            // side_check.h: the state of one kind's tasks
-constexpr int kNumSide = 10;  // the records of side_check.h's kSideKinds
+constexpr int kNumSide = 11;  // the records of side_check.h's kSideKinds
 
 enum class Source { kScan, kCount };
 
@@ -343,6 +349,7 @@ struct tgx_plan {
   std::vector<tgx::GroupSumsTask> group_sums;
   std::vector<tgx::KeyProbeTask> key_probes;
   std::vector<tgx::RowPredicateTask> row_predicates;
+  std::vector<tgx::TypeClassesTask> type_classes;
   int n_columns_needed = 0;  // 1 + max column index
   // per plan column, fixed at tgx_plan_create (tgx_update runs once per 8192-row batch: nothing is allocated there)
   std::vector<char> used, reads_values, needs_wide;

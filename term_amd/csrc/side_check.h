@@ -64,6 +64,7 @@ TGX_SIDE_KIND(groupcounts)
 TGX_SIDE_KIND(groupsums)
 TGX_SIDE_KIND(keyprobe)
 TGX_SIDE_KIND(rowpredicate)
+TGX_SIDE_KIND(typeclasses)
 #undef TGX_SIDE_KIND
 tgx_status temporal_plan_ready(const tgx_plan *plan, tgx_error *err);
 tgx_status valuerule_plan_ready(const tgx_plan *plan, tgx_error *err);
@@ -99,6 +100,8 @@ inline constexpr SideKind kSideKinds[kNumSide] = {
      keyprobe_check_column, keyprobe_state_new, false},
     {TGX_CHECK_ROW_PREDICATE, "ROW_PREDICATE", rowpredicate_plan_add, rowpredicate_plan_ready,
      rowpredicate_mark_columns, rowpredicate_check_column, rowpredicate_state_new, false},
+    {TGX_CHECK_TYPE_CLASSES, "TYPE_CLASSES", typeclasses_plan_add, nullptr, typeclasses_mark_columns,
+     typeclasses_check_column, typeclasses_state_new, false},
 };
 
 // where `kind` stands in kSideKinds (and in tgx_state::side, tgx_plan::side_on), or -1: not a kind of this file

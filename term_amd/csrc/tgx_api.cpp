@@ -206,6 +206,9 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
       return fail(err, sp.n_columns > (uint32_t)kRowPredicateMaxCols ? TGX_UNSUPPORTED : TGX_INVALID_ARGUMENT,
                   "spec %zu: ROW_PREDICATE names its columns through a column list of 1..%d (%u)", i, kRowPredicateMaxCols,
                   sp.n_columns);
+    if (sp.kind == TGX_CHECK_TYPE_CLASSES && sp.n_columns != 0)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: TYPE_CLASSES reads one column: it takes no column list (%u)", i,
+                  sp.n_columns);
     if (takes_list && (sp.n_columns >= 2 || sp.kind == TGX_CHECK_ROW_PREDICATE)) {
       if (sp.n_columns > (uint32_t)kMaxTupleCols || !sp.columns)
         return fail(err, TGX_UNSUPPORTED, "spec %zu: %s over %u columns (2..%d supported)", i,

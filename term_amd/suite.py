@@ -1238,6 +1238,16 @@ class _Analyzer:
                                                             C.byref(out), C.byref(err)), err)
         return _take(out)
 
+    def state_text_from_type_classes(self, counts):
+        """the state (the bytes the library wrote) a data_type analyzer builds from given counts: the dict of
+        State.type_classes (a string column), or {"results": [{"total", "non_null", "matches"}, ..]}, the results that
+        answer what the analyzer plans for an integer or a float column"""
+        out = C.c_char_p()
+        err = _Error()
+        _host_check(_host().tgx_host_data_type_state_json(json.dumps(self.spec).encode(), json.dumps(counts).encode(),
+                                                          C.byref(out), C.byref(err)), err)
+        return _take(out)
+
     def compute_metric_from_state(self, state):
         """-> MetricValue as {"type": "Double"|"Long"|"Map", "value": ...}; raises TgxError with the
         reference's AnalyzerError text (e.g. 'No data available for analysis')"""
@@ -1351,6 +1361,36 @@ def EntropyAnalyzer(column, max_unique_values=10000, arrow_type=None):
     return _Analyzer(spec)
 
 
+def DataTypeAnalyzer(column, arrow_type=None):
+    """TG/analyzers/advanced/data_type.rs: how many non-NULL values of `column` read as boolean, integer, double, date
+    or string.  A string column is classified on the device (TGX_CHECK_TYPE_CLASSES: syntactic classes, include/tgx.h;
+    DATETIME values count as "date"); a declared integer column takes two VALUE_RULE range counts, a float column a
+    COUNT.  State {"type_counts": {label: n}, "total_count": n}, a label without rows absent; the metric is a Map of
+    Long; metric_key is "data_type.<column>".  Values that look like dates in a form the device does not decide, and a
+    declared temporal, decimal, boolean, binary or UInt64 column, are the analyzer's own error.  `arrow_type`: the
+    column's Arrow DataType where the table is not a pyarrow one"""
+    spec = {"type": "data_type", "column": column}
+    if arrow_type:
+        spec["arrow_type"] = arrow_type
+    return _Analyzer(spec)
+
+
+def data_type_dominant_type(state):
+    """DataTypeState::dominant_type (data_type.rs:71-79): (label, fraction) of the most common type, or None"""
+    if not state["type_counts"]:
+        return None
+    label, count = max(state["type_counts"].items(), key=lambda kv: kv[1])
+    return label, count / state["total_count"]
+
+
+def data_type_consistency(state):
+    """DataTypeState::type_consistency (data_type.rs:82-90): 1.0 without rows, else the dominant type's fraction"""
+    if state["total_count"] == 0:
+        return 1.0
+    top = data_type_dominant_type(state)
+    return top[1] if top else 0.0
+
+
 class AnalyzerContext:
     """TG/analyzers/context.rs: metrics by key, errors; plus the analyzers' states (for merges across shards)"""
 
@@ -1393,7 +1433,7 @@ class AnalysisRunner:
     def run(self, table):
         declared = _arrow_type_names(table)  # (analyzers that read a column's values as text need its Arrow type)
         specs = [dict(a.spec, arrow_type=declared[a.spec["column"]])
-                 if a.spec["type"] == "value_entropy" and "arrow_type" not in a.spec and a.spec["column"] in declared
+                 if a.spec["type"] in ("value_entropy", "data_type") and "arrow_type" not in a.spec and a.spec["column"] in declared
                  else dict(a.spec, arrow_types=[declared.get(a.spec["column1"], ""), declared.get(a.spec["column2"], "")])
                  if a.spec["type"] == "mutual_information" and "max_pairs" in a.spec and "arrow_types" not in a.spec
                  else dict(a.spec, group_arrow_type=declared[a.spec["group_by"][0]])
@@ -1440,6 +1480,7 @@ def _host():
         L.tgx_host_analyzer_plan_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_pair_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_group_counts_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_data_type_state_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_run_suite_tables_json.argtypes = [C.c_char_p, C.POINTER(_HostTable), C.c_size_t,
                                                      C.POINTER(C.c_char_p), E]
         L.tgx_host_cross_table_sum_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
@@ -1589,7 +1630,7 @@ def _state_is_empty(analyzer, state):
     t = analyzer.spec["type"]
     if t in ("size", "mean", "standard_deviation"):
         return state.get("count", 0) == 0
-    if t in ("completeness", "distinctness", "approx_count_distinct"):
+    if t in ("completeness", "distinctness", "approx_count_distinct", "data_type"):
         return state.get("total_count", 0) == 0
     if t in ("min", "max"):
         return state.get("min") is None and state.get("max") is None

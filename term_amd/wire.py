@@ -95,7 +95,7 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                                rows > 0, every non_null <= its rows, a sum of 0 where non_null is 0, every length <=
                                max_value_bytes, no key twice, values 0 only with seen 0 and no keys, and
                                sum(rows) + null_group_rows + overflow_rows + long_rows == seen.
-    and ONLY for plans with ROW_PREDICATE checks, behind every other section:
+    and ONLY for plans with ROW_PREDICATE checks, behind the sections above:
     u32 magic 'RRPD', u32 n_tasks
     n_tasks     x { u32 n_leaves, n_ops, n_literal_bytes, 0            (the plan's predicate as it was set: a blob counted
                     n_leaves x { i32 kind, op, col, col2; u32 flags,    under another program, other leaves or other literal
@@ -104,6 +104,10 @@ counterpart of the serde_json analyzer states of the reference's IncrementalAnal
                     n_ops x u16 (code | arg << 8); u8 literals[n_literal_bytes]
                     u64 seen, satisfied, unknown }
                                satisfied + unknown <= seen; the failed rows are the rest.
+    and ONLY for plans with TYPE_CLASSES checks, behind every other section (the ROW_PREDICATE one included):
+    u32 magic 'TCLS', u32 n_tasks                                 (a task is a COLUMN: its specs share it)
+    n_tasks     x { u64 seen, non_null, boolean, integer, double, date, datetime, string, undecided }
+                               non_null <= seen, and the seven classes add up to non_null.
 
 min_key / max_key are the Int64 values themselves, or the IEEE totalOrder keys of Float64 values
 (bits ^ ((bits >> 63) >>> 1)).  This module packs partial states from plain numbers; libtgx does the parsing.
@@ -121,6 +125,7 @@ GROUP_COUNTS_MAGIC = 0x544E4347  # 'GCNT'
 GROUP_SUMS_MAGIC = 0x4D555347  # 'GSUM'
 KEY_PROBE_MAGIC = 0x4252504B  # 'KPRB'
 ROW_PREDICATE_MAGIC = 0x44505252  # 'RRPD'
+TYPE_CLASSES_MAGIC = 0x534C4354  # 'TCLS'
 I64_MAX, I64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
@@ -368,9 +373,14 @@ def row_predicate_state(leaves, program, literals, seen, satisfied, unknown=0):
     return out + bytes(literals) + struct.pack("<3Q", seen, satisfied, unknown)
 
 
+def type_classes_state(seen, non_null, boolean=0, integer=0, double=0, date=0, datetime=0, string=0, undecided=0):
+    """a TYPE_CLASSES task (one column): rows seen, the non-NULL rows and the seven classes they fall into"""
+    return struct.pack("<9Q", seen, non_null, boolean, integer, double, date, datetime, string, undecided)
+
+
 def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(), joint=(), temporal=(), hist=(),
          value_rules=(), value_counts=(), pair_counts=(), group_counts=(), group_sums=(), key_probes=(),
-         fingerprint_key=None, row_predicates=()):
+         fingerprint_key=None, row_predicates=(), type_classes=()):
     head = struct.pack("<9I", MAGIC, VERSION, len(scan), len(count), len(comoments), len(distinct), len(kll), len(regex),
                        len(hll))
     # (no string keys in a state packed from plain numbers, unless a KEY_PROBE task on string keys knows its parent set:
@@ -395,5 +405,7 @@ def pack(scan=(), count=(), comoments=(), distinct=(), kll=(), regex=(), hll=(),
         tail += struct.pack("<II", KEY_PROBE_MAGIC, len(key_probes)) + b"".join(key_probes)
     if row_predicates:
         tail += struct.pack("<II", ROW_PREDICATE_MAGIC, len(row_predicates)) + b"".join(row_predicates)
+    if type_classes:
+        tail += struct.pack("<II", TYPE_CLASSES_MAGIC, len(type_classes)) + b"".join(type_classes)
     return (head + b"".join(scan) + b"".join(count) + b"".join(comoments) + b"".join(distinct) + b"".join(kll) +
             b"".join(regex) + b"".join(hll) + tail)
