@@ -341,7 +341,37 @@ typedef enum tgx_check_kind {
    * are grouped by their 128-bit keyed fingerprint and every entry keeps its bytes; across states, blobs and ranks
    * entries are united by their bytes.  tgx_merge, state blobs and tgx_allreduce unite by value and add every counter.
    * Read with tgx_group_counts_get and tgx_group_counts_entries; tgx_result carries total = rows seen, non_null =
-   * COUNT(col), distinct = groups held (the NULL group not among them), matches = rows counted in them. */
+   * COUNT(col), distinct = groups held (the NULL group not among them), matches = rows counted in them.
+   *
+   * GROUP BY SEVERAL COLUMNS.  A spec with column2 == -1 and a column list (columns / n_columns, 2 .. 8) groups by the
+   * TUPLE of the listed columns, in the list's order; `column` stays the value column (the list does not overwrite it,
+   * as it does for the other kinds that take a list).  A list together with column2 >= 0, a list of one column, more
+   * than 8 columns, a NULL list and a negative index are refused by tgx_plan_create; the bounds, the reads and the
+   * summary are the ones above.
+   *   Components   are read as TGX_CHECK_KEY_PROBE's tuples read them: integers widened to int64 (the Int64-shaped
+   *                types, Int32 / Date32, Int8 .. UInt32), strings of any of the four layouts; a dictionary component
+   *                whose index is negative or outside the dictionary, or whose entry is NULL, is a NULL component and
+   *                is never read; each component sits under its own Arrow offset.  Float32 / Float64, UInt64, Boolean
+   *                and validity-only group columns are TGX_UNSUPPORTED from tgx_update, refused before anything runs.
+   *   NULL         is a value, as in SQL's GROUP BY: (NULL, 'a'), ('', 'a') and (NULL, NULL) are three groups and are
+   *                entries like any other; null_group_rows and null_group_non_null are always 0.
+   *   An entry's key is the concatenation of its components' canonical bytes:
+   *                NULL      0x00
+   *                integer   0x01, then the 8 big-endian bytes of value ^ 2^63
+   *                string    0x02, then the length as 2 big-endian bytes, then the bytes
+   *                The form is prefix-free per component, so injective for a given arity; a narrow column and a wide one
+   *                give the same bytes; bytewise ascending order -- the order of the entries, which come with
+   *                *is_bytes = 1 -- is lexicographic by component, NULL before integers before strings, integers in
+   *                numeric order, strings by length and then bytewise.  A row whose encoded key is longer than max_value_bytes is a long row (long_rows); a
+   *                string component of 65 536 bytes or more makes one by construction.
+   *   Grouping     on the device rows are grouped by the tuple's keyed 128-bit fingerprint -- the function, bit for bit,
+   *                that TGX_CHECK_DISTINCT and TGX_CHECK_KEY_PROBE give a tuple -- and the entry keeps the encoded
+   *                bytes: grouped by fingerprint within a state, united by bytes across states, blobs and ranks.
+   *   Walks        tuple specs that name the same list in the same order, with the same bounds, share one walk (up to
+   *                eight value columns).
+   * The identities above hold unchanged.  In a state blob the task's record carries its arity (0 for a single group
+   * column); a blob whose arity differs from the plan's task is refused, as is one whose keys are not encoded tuples of
+   * that arity. */
   TGX_CHECK_GROUP_COUNTS = 17,
   /* A sum per group: each side of the reference's CrossTableSumConstraint
    *                          TG/constraints/cross_table_sum.rs:251-262
@@ -370,7 +400,11 @@ typedef enum tgx_check_kind {
    * integers and one that summed floats do not merge, nor do integer-key and string-key states.
    * Read with tgx_group_sums_get and tgx_group_sums_entries; tgx_result carries total = rows seen, non_null =
    * COUNT(col), distinct = groups held, matches = rows counted in them, sum_i / sum_f = the sum over all classes,
-   * has_value = 0 when COUNT(col) is 0. */
+   * has_value = 0 when COUNT(col) is 0.
+   * GROUP BY SEVERAL COLUMNS: a spec with column2 == -1 and a column list of 2 .. 8 columns groups by the tuple of the
+   * listed columns, with the row rules, the canonical key bytes, the grouping guarantee and the blob rule written down
+   * for TGX_CHECK_GROUP_COUNTS; `column` stays the value column (it may be one of the listed columns), the null_group
+   * class is always empty, and the identities hold unchanged. */
   TGX_CHECK_GROUP_SUMS = 18,
   /* Is each key of a child column in a parent's key set?  The device side of the reference's ForeignKeyConstraint
    *                          TG/constraints/foreign_key.rs:152-176
@@ -1487,7 +1521,7 @@ tgx_status tgx_allreduce(const tgx_plan *plan, tgx_state *state, tgx_comm *comm,
 
 /* ---- measurement ----------------------------------------------------------------------------
  * Per-kernel HIP-event timing on the state's stream (what bench.py's `roofline` uses).
- * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_sums", "key_probe", "key_probe_build", "key_probe_rows", "row_predicate", "type_classes","hist_range",
+ * Kernel names: "scan", "count", "distinct", "regex", "kll", "comoments", "joint_range", "joint_bins", "temporal", "value_rule", "value_counts", "pair_range", "pair_counts", "group_counts", "group_counts_tuples", "group_sums", "group_sums_tuples", "key_probe", "key_probe_build", "key_probe_rows", "row_predicate", "type_classes","hist_range",
  * "hist_counts"; "distinct_lists" is the share of
  * "distinct" spent on big Utf8 batches that were deduplicated through partitioned fingerprint lists. */
 tgx_status tgx_profile_enable(tgx_state *state, int32_t on);

@@ -113,6 +113,11 @@ tgx_status tgx_host_assertion_json(const char *assertion_json, double value, int
  *     {"type": "mutual_information", "column1": "a", "column2": "b", "bins": 10, "max_pairs": N (optional),
  *      "max_value_bytes": 256 (optional), "arrow_types": ["Utf8", "Int64"] (optional)},
  *     {"type": "histogram", "column": "c", "num_buckets": 10, "strict_reference_types": true},
+ *     {"type": "grouped_completeness", "column": "c", "group_by": ["g"], "max_groups": 10000 | null, "include_overall": true,
+ *      "strict_reference_types": true, "group_arrow_type": "Utf8" (optional: the Arrow DataType of the ONE group column
+ *      where the table does not say it), "composite_groups_on_device": true (optional, an opt-in: 2 .. 8 "group_by"
+ *      columns are one TGX_CHECK_GROUP_COUNTS walk on the tuple of the columns), "group_arrow_types": ["Utf8", "Int64"]
+ *      (optional, with several group columns: their Arrow DataTypes, parallel to "group_by"; "" = the table says)},
  *     {"type": "value_entropy", "column": "c", "max_unique_values": 10000, "arrow_type": "Int64" (optional)},
  *     {"type": "data_type", "column": "c", "arrow_type": "Int32" (optional)}]}
  * "value_entropy" is the tag of EntropyAnalyzer (TG/analyzers/advanced/entropy.rs; name() "entropy", metric key
@@ -144,7 +149,8 @@ tgx_status tgx_host_metric_from_state_json(const char *analyzer_json, const char
 /* What an analyzer plans for columns of the given tgx_types (column_types_json: an array of tgx_type numbers parallel to
  * the analyzer's columns; 0 = unknown): {"requests": [{"kind", "column", "column2", "pair_counts": {"max_pairs",
  * "max_value_bytes", "x_mode", "y_mode"} (TGX_CHECK_PAIR_COUNTS only), "group_counts": {"max_groups", "max_value_bytes"}
- * (TGX_CHECK_GROUP_COUNTS only), "value_rule": {"mode", "flags", "lo_i", "hi_i", "lo_f", "hi_f"} (TGX_CHECK_VALUE_RULE
+ * (TGX_CHECK_GROUP_COUNTS only; a request that groups by several columns -- a "grouped_completeness" analyzer with
+ * "composite_groups_on_device": true and 2 .. 8 "group_by" columns -- has "column2": "" and "columns": [..]), "value_rule": {"mode", "flags", "lo_i", "hi_i", "lo_f", "hi_f"} (TGX_CHECK_VALUE_RULE
  * only)}]}.  Needs no device. */
 tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, const char *column_types_json, char **out_json,
                                        tgx_error *err);
@@ -181,6 +187,8 @@ tgx_status tgx_host_data_type_state_json(const char *analyzer_json, const char *
  * registered answers as the reference does for a missing table).  A "cross_table_sum" constraint
  *   {"type": "cross_table_sum", "left_column": "orders.total", "right_column": "payments.amount", "group_by": ["g"],
  *    "tolerance": 0.0, "max_violations_reported": 100, "max_groups": 65536}       (TG/constraints/cross_table_sum.rs)
+ * (optional: "composite_groups_on_device": true, an opt-in -- 2 .. 8 "group_by" columns are one GROUP_SUMS walk a side on
+ * the tuple of the columns; without it several columns are the constraint's error)
  * is evaluated beside the suite's fused plan, against the registered tables: each side is walked once, as a
  * TGX_CHECK_GROUP_SUMS spec (grouped) or a TGX_CHECK_NUMERIC_STATS spec (ungrouped); the outer join of the sides'
  * groups runs on the host.  The suite JSON may carry "table_column_types": {table: {column: DataType}}, the Arrow types the

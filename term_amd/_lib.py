@@ -750,7 +750,9 @@ class Column:
 
 def spec(kind, column, column2=-1, flags=0, pattern=None, kll_k=0, columns=None, length_min=0, length_max=None):
     """columns=[a, b, ...]: DISTINCT over the tuple of those columns (COUNT(DISTINCT (a, b))), or a KEY_PROBE whose key is
-    that tuple (Plan.set_key_probe_tuples), or the 1 .. 8 columns a ROW_PREDICATE's leaves name by position;
+    that tuple (Plan.set_key_probe_tuples), or the 1 .. 8 columns a ROW_PREDICATE's leaves name by position, or -- with
+    column2 left at -1 -- the 2 .. 8 columns a GROUP_COUNTS / GROUP_SUMS spec groups by, `column` staying its value column
+    (the entries' keys are then term_amd.group_key's encoded tuples);
     length_min / length_max (None = unbounded): LENGTH bounds in characters"""
     pat = pattern.encode("utf-8") if isinstance(pattern, str) else pattern
     s = CheckSpec(kind, column, column2, flags, pat, len(pat) if pat else 0, kll_k, 0)
@@ -761,7 +763,8 @@ def spec(kind, column, column2=-1, flags=0, pattern=None, kll_k=0, columns=None,
         s.columns = C.cast(arr, C.POINTER(C.c_int32))
         s.n_columns = len(columns)
         s._keep_columns = arr
-        s.column = columns[0]
+        if not (kind in (GROUP_COUNTS, GROUP_SUMS) and column2 < 0):
+            s.column = columns[0]
     return s
 
 
@@ -1283,7 +1286,9 @@ class State:
         """tgx_group_counts_get + tgx_group_counts_entries: (summary, groups) -- summary a dict of the ten counters (seen,
         groups, counted, counted_non_null, null_group_rows, null_group_non_null, overflow_rows, overflow_non_null,
         long_rows, long_non_null), groups a dict key -> (total, non_null) in the library's order (ascending by key); its
-        keys are ints for an integer group column and bytes for a string one.  The NULL group is in the summary"""
+        keys are ints for an integer group column and bytes for a string one; a spec that groups by several columns
+        (spec(GROUP_COUNTS, value, columns=[..])) has bytes keys that are encoded tuples: term_amd.group_key.decode.  The
+        NULL group is in the summary"""
         L, err = lib(), _Error()
         s = GroupCountsSummary()
         _check(L.tgx_group_counts_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)
@@ -1301,7 +1306,8 @@ class State:
         the four classes counted, null_group, overflow, long_rows, each a tuple (rows, non_null, sum); groups a dict
         key -> (rows, non_null, sum) in the library's order (ascending by key), its keys ints for an integer group column
         and bytes for a string one.  A sum is an int (the wrapping Int64 sum, sum_i) for an integer value column and a
-        float (sum_f) for a float one.  The NULL group is in the summary"""
+        float (sum_f) for a float one.  A spec that groups by several columns has bytes keys that are encoded tuples
+        (term_amd.group_key.decode).  The NULL group is in the summary"""
         L, err = lib(), _Error()
         s = GroupSumsSummary()
         _check(L.tgx_group_sums_get(self.plan.h, self.h, spec_index, C.byref(s), C.byref(err)), err)

@@ -11,11 +11,17 @@
 // from a blob, and what the device part is folded into whenever the state is read -- so merges, blobs and the
 // cross-rank step unite by VALUE, never by fingerprint.  Rows seen are counted on the host.
 //
+// A TUPLE task (a spec with a column list and no column2) groups by the tuple of its 2 .. 8 columns: its table always
+// holds byte keys, an entry's bytes are the tuple's canonical form (group_key.h), NULL is a value of a component -- there
+// is no NULL group -- and the tasks that name the same list in the same order, with the same bounds, ride one walk.
+//
 // keyed_state.h has what the kind shares with VALUE_COUNTS and GROUP_SUMS; here are its payload (total, non_null), its
 // classes, its walks -- the tasks of a walk count in the leader's table (CountedState::owner) -- and its launches.
 #include "keyed_state.h"
 
 namespace tgx {
+void launch_group_counts_tuples(const KeyProbeTupleDesc &L, bool numeric, const GroupMembers &mem,
+                                const GroupCountsTable &t, hipStream_t stream);
 void launch_group_counts_i64(const ComomentColDesc &d, const GroupMembers &mem, const GroupCountsTable &t, int blocks,
                              hipStream_t stream);
 void launch_group_counts_utf8(const Utf8ColDesc &d, const GroupMembers &mem, const GroupCountsTable &t,
@@ -105,7 +111,8 @@ struct GroupsKind {
     a.add_entries(b);
   }
 
-  // per task { u32 max_groups, max_value_bytes (the plan's parameters), u32 kind (0 no keys, 1 int64, 2 bytes), u32 0,
+  // per task { u32 max_groups, max_value_bytes (the plan's parameters), u32 kind (0 no keys, 1 int64, 2 bytes),
+  //   u32 arity (0: the task groups by one column; 2 .. 8: by a tuple, whose entries are canonical tuple keys),
   //   u64 seen, null_group_rows, null_group_non_null, overflow_rows, overflow_non_null, long_rows, long_non_null,
   //   u64 n_entries,
   //   n_entries x { i64 key, u64 total, u64 non_null }  or  { u32 length, u8 bytes[length], u64 total, u64 non_null },
@@ -113,7 +120,7 @@ struct GroupsKind {
   static void write(const GroupCountsTask &t, const GroupsHost &h, Writer &w) {
     w.pod(t.params);
     w.pod((uint32_t)h.kind);
-    w.pod((uint32_t)0);
+    w.pod((uint32_t)t.n_tuple);
     const uint64_t counts[8] = {h.seen, h.null_group.total, h.null_group.non_null, h.overflow.total, h.overflow.non_null,
                                 h.long_keys.total, h.long_keys.non_null, h.size()};
     w.pod(counts);
@@ -123,7 +130,7 @@ struct GroupsKind {
   static tgx_status read(const GroupCountsTask &t, GroupsHost &h, Reader &r, size_t k, tgx_error *err) {
     tgx_group_counts_params p;
     r.get(&p, sizeof(p));
-    const uint32_t kind = r.pod<uint32_t>(), pad = r.pod<uint32_t>();
+    const uint32_t kind = r.pod<uint32_t>(), arity = r.pod<uint32_t>();
     uint64_t counts[8];
     r.get(counts, sizeof(counts));
     if (!r.ok) return TGX_OK;
@@ -133,12 +140,18 @@ struct GroupsKind {
                   "%u) than the plan's (%u, %u)",
                   k, p.max_groups, p.max_value_bytes, t.params.max_groups, t.params.max_value_bytes);
     const uint64_t n = counts[7];
-    if (kind > kByteKeys || pad != 0 || (kind == kNoKeys && n != 0))
+    if (arity != (uint32_t)t.n_tuple && (arity == 0 || (arity >= 2 && arity <= (uint32_t)kGroupMaxTuple)))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "GROUP_COUNTS task %zu: the blob groups by %u columns, the plan's task by %d (0: a single group column)",
+                  k, arity, t.n_tuple);
+    if (kind > kByteKeys || arity != (uint32_t)t.n_tuple || (kind == kNoKeys && n != 0) ||
+        (arity != 0 && kind == kIntKeys))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (GROUP_COUNTS task %zu: kind)", k);
     uint64_t counted = 0;
     TGX_TRY(keyed_read_entries("GROUP_COUNTS", kNoun, k, r, kind, n, t.params.max_value_bytes, CountsWire(), h, &counted,
                                err));
     if (!r.ok) return TGX_OK;
+    TGX_TRY(tuple_keys_ok("GROUP_COUNTS", k, t.n_tuple, h, err));
     // counted + null_group_rows + overflow_rows + long_rows == seen, and no class has more non-NULL values than rows
     if (!terms_make(counts[0], {counted, counts[1], counts[3], counts[5]}) || counts[2] > counts[1] ||
         counts[4] > counts[3] || counts[6] > counts[5])
@@ -195,11 +208,17 @@ struct GroupsCheck final : KeyedCheck<GroupsKind> {
     for (const std::vector<int> &walk : walks) {
       const size_t leader = (size_t)walk[0];
       const tgx_column &g = dev[tasks[leader].group];
+      const bool tuples = tasks[leader].n_tuple != 0;
       const Route route = route_of(g);
       // (an Int64 view: update_validate refuses what is neither a string layout nor widened to one)
-      if (route == kNoRoute || (route == kIntRoute && !g.values))
+      if (!tuples && (route == kNoRoute || (route == kIntRoute && !g.values)))
         return fail(err, TGX_UNSUPPORTED, "GROUP_COUNTS groups by integer and string columns (%d)", g.type);
-      TGX_TRY(ensure_keys(st, leader, route == kIntRoute ? kIntKeys : kByteKeys, walk.size() * 8, err));
+      KeyProbeTupleDesc L;
+      bool numeric = true;
+      uint64_t tuple_bytes = 0;
+      if (tuples)
+        TGX_TRY(tuple_desc(plan, tasks[leader].tuple, tasks[leader].n_tuple, dev, &L, &numeric, &tuple_bytes, err));
+      TGX_TRY(ensure_keys(st, leader, !tuples && route == kIntRoute ? kIntKeys : kByteKeys, walk.size() * 8, err));
       const GroupCountsTable t = view(st, leader);
       GroupMembers mem;
       memset(&mem, 0, sizeof(mem));
@@ -212,7 +231,12 @@ struct GroupsCheck final : KeyedCheck<GroupsKind> {
         mem.word[m] = (uint32_t)word_off[walk[m]];
         bits += v.validity ? (uint64_t)(nrows + 7) / 8 : 0;
       }
-      if (route == kIntRoute) {
+      if (tuples) {
+        // (per-wave and LDS counters are 32-bit here too)
+        TGX_TRY(side_rows_fit("GROUP_COUNTS", nrows, 1024, err));
+        ProfScope ps(st, "group_counts_tuples", tuple_bytes + bits);
+        launch_group_counts_tuples(L, numeric, mem, t, st->stream);
+      } else if (route == kIntRoute) {
         ComomentColDesc d;
         memset(&d, 0, sizeof(d));
         const uint64_t bytes = side_fill_x(d, g);
@@ -272,7 +296,8 @@ void assign_walks(std::vector<GroupCountsTask> &tasks) {
     for (size_t j = 0; j < k; j++) {
       const GroupCountsTask &o = tasks[j];
       if (!o.set || o.group != t.group || o.params.max_groups != t.params.max_groups ||
-          o.params.max_value_bytes != t.params.max_value_bytes)
+          o.params.max_value_bytes != t.params.max_value_bytes || o.n_tuple != t.n_tuple ||
+          !std::equal(t.tuple, t.tuple + t.n_tuple, o.tuple))  // (tuple tasks: the same list in the same order)
         continue;
       if (o.leader == o.slot) {
         leader = o.slot;
@@ -292,7 +317,7 @@ void assign_walks(std::vector<GroupCountsTask> &tasks) {
 
 tgx_status groupcounts_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err) {
   const tgx_check_spec &sp = plan->specs[spec_index];
-  if (sp.column2 < 0)
+  if (sp.column2 < 0 && sp.n_columns < 2)  // (a column list instead: tgx_plan_create hands it to the task)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %d: GROUP_COUNTS needs column2, the group column", spec_index);
   GroupCountsTask t;
   memset(&t, 0, sizeof(t));
@@ -317,13 +342,17 @@ tgx_status groupcounts_plan_ready(const tgx_plan *plan, tgx_error *err) {
 void groupcounts_mark_columns(tgx_plan *plan) {
   for (const GroupCountsTask &t : plan->group_counts) {
     side_mark(plan, GroupsCheck::kIndex, t.group, true);
+    for (int c = 0; c < t.n_tuple; c++) side_mark(plan, GroupsCheck::kIndex, t.tuple[c], true);
     plan->used[t.column] = plan->side_on[GroupsCheck::kIndex][t.column] = 1;
   }
 }
 
 tgx_status groupcounts_check_column(const tgx_plan *plan, int column, const tgx_column &c, tgx_error *err) {
   bool groups = false;  // (a value column may be of any type)
-  for (const GroupCountsTask &t : plan->group_counts) groups |= t.group == column;
+  for (const GroupCountsTask &t : plan->group_counts) {
+    groups |= t.group == column;
+    for (int g = 0; g < t.n_tuple; g++) groups |= t.tuple[g] == column;
+  }
   if (!groups) return TGX_OK;
   const int type = c.type;
   if (refused_as_key(type))

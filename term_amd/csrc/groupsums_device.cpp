@@ -11,11 +11,16 @@
 // device part is folded into whenever the state is read -- so merges, blobs and the cross-rank step unite by VALUE.
 // Rows seen are counted on the host.
 //
+// A TUPLE task (a spec with a column list and no column2) groups by the tuple of its 2 .. 8 columns, as GROUP_COUNTS's
+// tuple tasks do: byte keys always, an entry's bytes the tuple's canonical form (group_key.h), no NULL group.
+//
 // keyed_state.h has what the kind shares with VALUE_COUNTS and GROUP_COUNTS; here are its payload (rows, non_null, sum),
 // its classes, the kind of its sums -- a second thing two batches or two states can differ in -- and its launches.
 #include "keyed_state.h"
 
 namespace tgx {
+void launch_group_sums_tuples(const KeyProbeTupleDesc &L, bool numeric, const GroupSumsValue &val,
+                              const GroupSumsTable &t, bool is_float, hipStream_t stream);
 void launch_group_sums_i64(const ComomentColDesc &d, const GroupSumsTable &t, bool is_float, int blocks,
                            hipStream_t stream);
 void launch_group_sums_utf8(const Utf8ColDesc &d, const GroupSumsValue &val, const GroupSumsTable &t, bool is_float,
@@ -143,7 +148,9 @@ struct GroupSumsKind {
     a.add_entries(b);
   }
 
-  // per task { u32 max_groups, max_value_bytes (the plan's parameters), u32 key kind (0 no keys, 1 int64, 2 bytes),
+  // per task { u32 max_groups, max_value_bytes (the plan's parameters),
+  //   u32 key kind (0 no keys, 1 int64, 2 bytes) | arity << 16 (0: the task groups by one column; 2 .. 8: by a tuple,
+  //   whose entries are canonical tuple keys -- GROUP_COUNTS's arity word; this record has no spare word for it),
   //   u32 value kind (0 no rows, 1 integer sums, 2 double sums),
   //   u64 seen, then rows, non_null, sum of the NULL group, of overflow, of the long rows, u64 n_entries,
   //   n_entries x { i64 key | u32 length, u8 bytes[length] ; u64 rows, u64 non_null, u64 sum }, ascending by key }
@@ -151,7 +158,7 @@ struct GroupSumsKind {
   static void write(const GroupSumsTask &t, const GroupSumsHost &h, Writer &w) {
     const SumsWire wire{h.is_float()};
     w.pod(t.params);
-    w.pod((uint32_t)h.kind);
+    w.pod((uint32_t)h.kind | (uint32_t)t.n_tuple << 16);
     w.pod((uint32_t)h.values);
     uint64_t counts[11] = {h.seen};
     wire.put(h.null_group, counts + 1);
@@ -165,7 +172,8 @@ struct GroupSumsKind {
   static tgx_status read(const GroupSumsTask &t, GroupSumsHost &h, Reader &r, size_t k, tgx_error *err) {
     tgx_group_sums_params p;
     r.get(&p, sizeof(p));
-    const uint32_t kind = r.pod<uint32_t>(), values = r.pod<uint32_t>();
+    const uint32_t kind_word = r.pod<uint32_t>(), values = r.pod<uint32_t>();
+    const uint32_t kind = kind_word & 0xffffu, arity = kind_word >> 16;
     uint64_t counts[11];
     r.get(counts, sizeof(counts));
     if (!r.ok) return TGX_OK;
@@ -175,13 +183,18 @@ struct GroupSumsKind {
                   "%u) than the plan's (%u, %u)",
                   k, p.max_groups, p.max_value_bytes, t.params.max_groups, t.params.max_value_bytes);
     const uint64_t n = counts[10];
-    if (kind > kByteKeys || values > kFloatSums || (kind == kNoKeys && n != 0) ||
+    if (arity != (uint32_t)t.n_tuple && (arity == 0 || (arity >= 2 && arity <= (uint32_t)kGroupMaxTuple)))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "GROUP_SUMS task %zu: the blob groups by %u columns, the plan's task by %d (0: a single group column)", k,
+                  arity, t.n_tuple);
+    if (kind > kByteKeys || arity != (uint32_t)t.n_tuple || (arity != 0 && kind == kIntKeys) || values > kFloatSums || (kind == kNoKeys && n != 0) ||
         (values == kNoSums && (counts[0] != 0 || kind != kNoKeys)))
       return fail(err, TGX_INVALID_ARGUMENT, "malformed state blob (GROUP_SUMS task %zu: kind)", k);
     const SumsWire wire{values == kFloatSums};
     uint64_t counted = 0;
     TGX_TRY(keyed_read_entries("GROUP_SUMS", kNoun, k, r, kind, n, t.params.max_value_bytes, wire, h, &counted, err));
     if (!r.ok) return TGX_OK;
+    TGX_TRY(tuple_keys_ok("GROUP_SUMS", k, t.n_tuple, h, err));
     // counted + null_group_rows + overflow_rows + long_rows == seen, no class has more non-NULL values than rows, and
     // none a sum without a value
     bool ok = terms_make(counts[0], {counted, counts[1], counts[4], counts[7]});
@@ -244,21 +257,32 @@ struct GroupSumsCheck final : KeyedCheck<GroupSumsKind> {
     table_cache_ok = false;
     for (size_t k = 0; k < tasks.size(); k++) {
       const tgx_column &g = dev[tasks[k].group], &v = dev[tasks[k].column];
+      const bool tuples = tasks[k].n_tuple != 0;
       const Route route = route_of(g);
       // (Int64 / Float64 views: update_validate refuses what is neither those nor widened to them)
-      if (route == kNoRoute || (route == kIntRoute && !g.values))
+      if (!tuples && (route == kNoRoute || (route == kIntRoute && !g.values)))
         return fail(err, TGX_UNSUPPORTED, "GROUP_SUMS groups by integer and string columns (%d)", g.type);
+      KeyProbeTupleDesc L;
+      bool numeric = true;
+      uint64_t tuple_bytes = 0;
+      if (tuples) TGX_TRY(tuple_desc(plan, tasks[k].tuple, tasks[k].n_tuple, dev, &L, &numeric, &tuple_bytes, err));
       if (!is_numeric(v.type) || !v.values)
         return fail(err, TGX_UNSUPPORTED, "GROUP_SUMS sums integer and float columns (%d)", v.type);
       const bool is_float = v.type == TGX_FLOAT64;
-      TGX_TRY(ensure_table(st, k, route == kIntRoute ? kIntKeys : kByteKeys, is_float ? kFloatSums : kIntSums, err));
+      TGX_TRY(ensure_table(st, k, !tuples && route == kIntRoute ? kIntKeys : kByteKeys, is_float ? kFloatSums : kIntSums,
+                           err));
       const GroupSumsTable t = view(st, k);
       GroupSumsValue val;
       val.values = v.values;
       val.validity = v.validity;
       val.offset = v.offset;
       const uint64_t value_bytes = (uint64_t)nrows * 8 + (v.validity ? (uint64_t)(nrows + 7) / 8 : 0);
-      if (route == kIntRoute) {
+      if (tuples) {
+        // (per-wave and LDS counters are 32-bit here too)
+        TGX_TRY(side_rows_fit("GROUP_SUMS", nrows, 1024, err));
+        ProfScope ps(st, "group_sums_tuples", tuple_bytes + value_bytes);
+        launch_group_sums_tuples(L, numeric, val, t, is_float, st->stream);
+      } else if (route == kIntRoute) {
         ComomentColDesc d;
         memset(&d, 0, sizeof(d));
         const uint64_t bytes = side_fill_x(d, g) + side_fill_y(d, v);
@@ -321,7 +345,7 @@ struct GroupSumsCheck final : KeyedCheck<GroupSumsKind> {
 
 tgx_status groupsums_plan_add(tgx_plan *plan, int spec_index, int *slot, tgx_error *err) {
   const tgx_check_spec &sp = plan->specs[spec_index];
-  if (sp.column2 < 0)
+  if (sp.column2 < 0 && sp.n_columns < 2)  // (a column list instead: tgx_plan_create hands it to the task)
     return fail(err, TGX_INVALID_ARGUMENT, "spec %d: GROUP_SUMS needs column2, the group column", spec_index);
   GroupSumsTask t;
   memset(&t, 0, sizeof(t));
@@ -344,6 +368,7 @@ tgx_status groupsums_plan_ready(const tgx_plan *plan, tgx_error *err) {
 void groupsums_mark_columns(tgx_plan *plan) {
   for (const GroupSumsTask &t : plan->group_sums) {
     side_mark(plan, GroupSumsCheck::kIndex, t.group, true);
+    for (int c = 0; c < t.n_tuple; c++) side_mark(plan, GroupSumsCheck::kIndex, t.tuple[c], true);
     side_mark(plan, GroupSumsCheck::kIndex, t.column, true);
   }
 }
@@ -352,6 +377,7 @@ tgx_status groupsums_check_column(const tgx_plan *plan, int column, const tgx_co
   bool groups = false, values = false;
   for (const GroupSumsTask &t : plan->group_sums) {
     groups |= t.group == column;
+    for (int g = 0; g < t.n_tuple; g++) groups |= t.tuple[g] == column;
     values |= t.column == column;
   }
   const int type = c.type;

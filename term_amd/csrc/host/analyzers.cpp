@@ -2,6 +2,7 @@
 // TG/analyzers/basic/{size,completeness,distinctness,mean,min_max,sum}.rs,
 // TG/analyzers/advanced/{standard_deviation,correlation,mutual_information,histogram,entropy}.rs.
 #include "analyzers.h"
+#include "../group_key.h"
 #include "custom_sql.h"
 #include "tgx_handles.h"
 
@@ -10,8 +11,16 @@
 
 #include <algorithm>
 #include <deque>
+#include <map>
+#include <set>
 
 namespace term_guard {
+using tgx::GroupKeyCell;
+using tgx::group_key_decode;
+using tgx::kGroupKeyInt;
+using tgx::kGroupKeyMaxArity;
+using tgx::kGroupKeyNull;
+using tgx::kGroupKeyString;
 
 // ---------------------------------------------------------------- JSON helpers
 static json::Value jnum(double v) {
@@ -1127,9 +1136,10 @@ class DataTypeAnalyzer : public ColumnAnalyzer {
 // "overall": {..}|null, "metadata": GroupedMetadata}.  Beyond the device's bounds the analyzer fails with the numbers.
 class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
  public:
-  GroupedCompletenessAnalyzer(std::string c, GroupingConfig config, bool strict, std::string group_arrow_type)
+  GroupedCompletenessAnalyzer(std::string c, GroupingConfig config, bool strict, std::string group_arrow_type,
+                              std::vector<std::string> group_arrow_types = {})
       : ColumnAnalyzer(std::move(c)), config_(std::move(config)), strict_(strict),
-        group_arrow_type_(std::move(group_arrow_type)) {}
+        group_arrow_type_(std::move(group_arrow_type)), group_arrow_types_(std::move(group_arrow_types)) {}
   std::string name() const override { return "completeness"; }
   std::string metric_key() const override {
     std::string joined;
@@ -1146,7 +1156,17 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
     const uint64_t most = TGX_GROUP_COUNTS_MAX_GROUPS;
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(config_.max_groups.value_or(most), 1), most);
   }
+  // 2 .. 8 group columns with the opt-in: one request on the tuple of the columns
+  bool tuples() const {
+    return config_.composite_on_device && config_.columns.size() >= 2 && config_.columns.size() <= (size_t)kGroupKeyMaxArity;
+  }
   std::vector<SpecRequest> plan() const override {
+    if (tuples()) {
+      SpecRequest r = req(TGX_CHECK_GROUP_COUNTS, column_);
+      r.columns = config_.columns;
+      r.group_counts = tgx_group_counts_params{device_bound(), TGX_GROUP_COUNTS_MAX_VALUE_BYTES};
+      return {r};
+    }
     if (config_.columns.size() != 1)
       throw AnalyzerError::invalid_data("grouped completeness groups by exactly one column on the GPU path (" +
                                         std::to_string(config_.columns.size()) + " given)");
@@ -1158,16 +1178,21 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
   std::vector<SpecRequest> plan_for(const std::vector<int> &types, const std::vector<std::string> &declared) const override {
     std::vector<SpecRequest> reqs = plan();
     if (!strict_) return reqs;
-    const int type = types.size() > 1 ? types[1] : 0;
-    std::string t = !group_arrow_type_.empty() ? group_arrow_type_ : declared.size() > 1 ? declared[1] : std::string();
-    if (t.empty())
-      t = type == TGX_UTF8 ? "Utf8" : type == TGX_LARGE_UTF8 ? "LargeUtf8" : type == TGX_UTF8_VIEW ? "Utf8View"
-          : type == TGX_DICT32_UTF8 ? "Dictionary(Int32, Utf8)" : type == 0 ? "" : "tgx type " + std::to_string(type);
-    if (!t.empty() && t != "Utf8")
-      throw AnalyzerError::invalid_data(
-          "group column '" + config_.columns[0] + "' is " + t + ": the reference reads only a Utf8 group column by value "
-          "and pushes the {:?} of the whole key array for every row of any other (grouped_completeness.rs:263-268); "
-          "strict_reference_types=false groups strings of every layout by value and prints integers as decimal text");
+    // every group column must be declared Utf8: the error names the first that is not
+    for (size_t g = 0; g < config_.columns.size(); g++) {
+      const int type = types.size() > 1 + g ? types[1 + g] : 0;
+      std::string t = g == 0 && !group_arrow_type_.empty() ? group_arrow_type_
+                      : g < group_arrow_types_.size() && !group_arrow_types_[g].empty() ? group_arrow_types_[g]
+                      : declared.size() > 1 + g ? declared[1 + g] : std::string();
+      if (t.empty())
+        t = type == TGX_UTF8 ? "Utf8" : type == TGX_LARGE_UTF8 ? "LargeUtf8" : type == TGX_UTF8_VIEW ? "Utf8View"
+            : type == TGX_DICT32_UTF8 ? "Dictionary(Int32, Utf8)" : type == 0 ? "" : "tgx type " + std::to_string(type);
+      if (!t.empty() && t != "Utf8")
+        throw AnalyzerError::invalid_data(
+            "group column '" + config_.columns[g] + "' is " + t + ": the reference reads only a Utf8 group column by value "
+            "and pushes the {:?} of the whole key array for every row of any other (grouped_completeness.rs:263-268); "
+            "strict_reference_types=false groups strings of every layout by value and prints integers as decimal text");
+    }
     return reqs;
   }
   bool reads_group_counts() const override { return true; }
@@ -1209,8 +1234,143 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
     return jobj({{"groups", arr}, {"null_group", null_group}, {"overall", overall}, {"metadata", meta}});
   }
 
+  // ---- several group columns: the entries' keys are encoded tuples (group_key.h) ----
+  // a key as the state holds it: per group column NULL, or the cell's text (an integer as decimal text)
+  typedef std::vector<std::pair<bool, std::string>> KeyVec;  // (is NULL, text)
+  // key ascending, a NULL cell after any value; values by their text's bytes
+  static bool key_less(const KeyVec &a, const KeyVec &b) {
+    for (size_t i = 0; i < a.size() && i < b.size(); i++) {
+      if (a[i].first != b[i].first) return b[i].first;
+      if (a[i].second != b[i].second) return a[i].second < b[i].second;
+    }
+    return a.size() < b.size();
+  }
+  static std::vector<std::string> texts_of(const KeyVec &k) {  // (a NULL reads as "")
+    std::vector<std::string> t;
+    for (const auto &c : k) t.push_back(c.first ? std::string() : c.second);
+    return t;
+  }
+  struct TupleRow {
+    std::vector<GroupKeyCell> cells;
+    KeyVec key;
+    uint64_t total = 0, non_null = 0;
+  };
+  // ... as the query orders it: integers numerically, strings bytewise, a NULL cell after any value
+  static bool cells_less(const std::vector<GroupKeyCell> &a, const std::vector<GroupKeyCell> &b) {
+    for (size_t i = 0; i < a.size() && i < b.size(); i++) {
+      const bool an = a[i].tag == kGroupKeyNull, bn = b[i].tag == kGroupKeyNull;
+      if (an != bn) return bn;
+      if (a[i].tag != b[i].tag) return a[i].tag < b[i].tag;
+      if (a[i].tag == kGroupKeyInt && a[i].value != b[i].value) return a[i].value < b[i].value;
+      if (a[i].tag == kGroupKeyString && a[i].bytes != b[i].bytes) return a[i].bytes < b[i].bytes;
+    }
+    return a.size() < b.size();
+  }
+  json::Value tuple_state_of(std::vector<std::pair<KeyVec, std::pair<uint64_t, uint64_t>>> groups, const json::Value &overall,
+                             const json::Value &meta) const {
+    std::sort(groups.begin(), groups.end(), [](const auto &a, const auto &b) { return key_less(a.first, b.first); });
+    json::Value arr;
+    arr.type = json::Value::Array;
+    for (const auto &g : groups) {
+      json::Value key;
+      key.type = json::Value::Array;
+      for (const auto &c : g.first) key.arr.push_back(c.first ? jnull() : jstr(c.second));
+      arr.arr.push_back(jobj({{"key", key}, {"total_count", jcount(g.second.first)}, {"non_null_count", jcount(g.second.second)}}));
+    }
+    return jobj({{"groups", arr}, {"null_group", jnull()}, {"overall", overall}, {"metadata", meta}});
+  }
+  static uint64_t distinct_texts(const std::vector<std::pair<KeyVec, std::pair<uint64_t, uint64_t>>> &groups) {
+    std::set<std::vector<std::string>> seen;
+    for (const auto &g : groups) seen.insert(texts_of(g.first));
+    return seen.size();
+  }
+  std::string joined_columns() const {
+    std::string joined;
+    for (size_t i = 0; i < config_.columns.size(); i++) joined += (i ? ", " : "") + config_.columns[i];
+    return joined;
+  }
+  json::Value tuple_state_from_group_counts(const GroupCounts &gc) const {
+    std::vector<TupleRow> rows;
+    for (const GroupCounts::Entry &e : gc.entries) {
+      TupleRow r;
+      if (!gc.is_bytes || !group_key_decode((const uint8_t *)e.bytes.data(), e.bytes.size(), &r.cells) ||
+          r.cells.size() != config_.columns.size())
+        throw AnalyzerError::invalid_data("a group key of columns [" + joined_columns() + "] is not the encoded form of a "
+                                          "tuple of " + std::to_string(config_.columns.size()) + " columns");
+      for (const GroupKeyCell &c : r.cells)
+        r.key.push_back({c.tag == kGroupKeyNull, c.tag == kGroupKeyInt ? std::to_string((long long)c.value) : c.bytes});
+      r.total = e.total;
+      r.non_null = e.non_null;
+      rows.push_back(std::move(r));
+    }
+    // ORDER BY completeness DESC; ties by key ascending, a NULL cell after any value
+    std::stable_sort(rows.begin(), rows.end(), [](const TupleRow &a, const TupleRow &b) {
+      const double ca = completeness(a.total, a.non_null), cb = completeness(b.total, b.non_null);
+      if (ca != cb) return ca > cb;
+      return cells_less(a.cells, b.cells);
+    });
+    const uint64_t limit = config_.max_groups ? *config_.max_groups : UINT64_MAX;
+    const uint64_t total_groups = std::min<uint64_t>(rows.size(), limit == UINT64_MAX ? limit : limit + 1);  // LIMIT max_groups + 1
+    const size_t kept = (size_t)std::min<uint64_t>(rows.size(), limit);
+    std::vector<std::pair<KeyVec, std::pair<uint64_t, uint64_t>>> groups;
+    uint64_t all = 0, all_non_null = 0;
+    for (size_t i = 0; i < kept; i++) {
+      all += rows[i].total;
+      all_non_null += rows[i].non_null;
+      groups.push_back({rows[i].key, {rows[i].total, rows[i].non_null}});
+    }
+    // (NULL reads as "": two kept rows with equal text vectors are one key of the reference's map)
+    const uint64_t included = distinct_texts(groups);
+    return tuple_state_of(std::move(groups), config_.include_overall ? counts(all, all_non_null) : jnull(),
+                          metadata(total_groups, included));
+  }
+  static KeyVec key_of_json(const json::Value *key) {
+    KeyVec k;
+    if (key && key->type == json::Value::Array)
+      for (const json::Value &c : key->arr) k.push_back({c.type != json::Value::String, c.type == json::Value::String ? c.str : std::string()});
+    return k;
+  }
+  // merge_states over the whole key vector (a NULL cell is a cell of its own, apart from "")
+  json::Value tuple_merge_states(const std::vector<json::Value> &states) const {
+    std::map<KeyVec, std::pair<uint64_t, uint64_t>> by_key;
+    bool has_overall = false;
+    uint64_t all_t = 0, all_n = 0, total_groups = 0;
+    for (const json::Value &st : states) {
+      if (const json::Value *gs = st.get("groups"))
+        if (gs->type == json::Value::Array)
+          for (const json::Value &g : gs->arr) {
+            std::pair<uint64_t, uint64_t> &c = by_key[key_of_json(g.get("key"))];
+            c.first += u(g, "total_count");
+            c.second += u(g, "non_null_count");
+          }
+      if (const json::Value *ov = st.get("overall"))
+        if (ov->type == json::Value::Object) {
+          has_overall = true;
+          all_t += u(*ov, "total_count");
+          all_n += u(*ov, "non_null_count");
+        }
+      if (const json::Value *md = st.get("metadata")) total_groups = std::max(total_groups, u(*md, "total_groups"));
+    }
+    std::vector<std::pair<KeyVec, std::pair<uint64_t, uint64_t>>> groups(by_key.begin(), by_key.end());
+    json::Value meta = metadata(0, 0);
+    if (const json::Value *md = states[0].get("metadata"))
+      if (const json::Value *gc = md->get("group_columns")) meta.obj[0].second = *gc;
+    const uint64_t included = distinct_texts(groups);
+    meta.obj[1].second = jcount(total_groups);
+    meta.obj[2].second = jcount(included);
+    meta.obj[3].second = jbool(total_groups > included);
+    return tuple_state_of(std::move(groups), has_overall ? counts(all_t, all_n) : jnull(), meta);
+  }
+
   json::Value state_from_group_counts(const GroupCounts &gc) const override {
     const tgx_group_counts_summary &s = gc.summary;
+    if (tuples() && (s.overflow_rows || s.long_rows))
+      throw AnalyzerError::invalid_data(
+          "columns [" + joined_columns() + "] have more groups than the table for max_groups " +
+          std::to_string(device_bound()) + " holds, or encoded keys longer than " +
+          std::to_string((int)TGX_GROUP_COUNTS_MAX_VALUE_BYTES) + " bytes: " + std::to_string(s.groups) + " groups held, " +
+          std::to_string(s.overflow_rows) + " overflow rows, " + std::to_string(s.long_rows) + " long rows");
+    if (tuples()) return tuple_state_from_group_counts(gc);
     if (s.overflow_rows || s.long_rows)
       throw AnalyzerError::invalid_data(
           "column '" + config_.columns[0] + "' has more groups than the table for max_groups " +
@@ -1268,6 +1428,7 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
   // metadata with total_groups the maximum, included_groups the merged map's size, truncated = total > included
   json::Value merge_states(const std::vector<json::Value> &states) const override {
     if (states.empty()) throw AnalyzerError::custom("Invalid configuration: Cannot merge empty states");
+    if (tuples()) return tuple_merge_states(states);
     std::vector<std::pair<std::string, std::pair<uint64_t, uint64_t>>> groups;
     bool has_null = false, has_overall = false, empty_text = false;
     uint64_t null_t = 0, null_n = 0, all_t = 0, all_n = 0, total_groups = 0;
@@ -1326,18 +1487,24 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
     const bool has_null = ng && ng->type == json::Value::Object;
     const double null_c = has_null ? completeness(u(*ng, "total_count"), u(*ng, "non_null_count")) : 0.0;
     bool null_done = false;
+    std::map<std::string, double> group_keys;  // (the keys that groups have put so far, with what they put)
     if (const json::Value *gs = st.get("groups"))
       if (gs->type == json::Value::Array)
         for (const json::Value &g : gs->arr) {
           std::string joined;
           if (const json::Value *key = g.get("key"))
             for (size_t i = 0; key->type == json::Value::Array && i < key->arr.size(); i++)
-              joined += (i ? "_" : "") + key->arr[i].str;
+              joined += (i ? "_" : "") + (key->arr[i].type == json::Value::String ? key->arr[i].str : std::string());
           double c = completeness(u(g, "total_count"), u(g, "non_null_count"));
+          // two groups under one joined key (a NULL cell reads as ""): the later in the query's order stays, which is
+          // the less complete of the two
+          const auto earlier = group_keys.find(joined);
+          if (earlier != group_keys.end() && earlier->second < c) c = earlier->second;
           if (joined.empty() && has_null) {  // the "" row and the NULL row: the later in the query's order stays
             if (null_c <= c) c = null_c;
             null_done = true;
           }
+          group_keys[joined] = c;
           put(joined, MetricValue::of_double(c));
         }
     if (has_null && !null_done) put("", MetricValue::of_double(null_c));
@@ -1361,6 +1528,7 @@ class GroupedCompletenessAnalyzer : public ColumnAnalyzer {
   GroupingConfig config_;
   bool strict_;
   std::string group_arrow_type_;
+  std::vector<std::string> group_arrow_types_;  // several group columns: their Arrow DataType names where the table does not say
 };
 
 }  // namespace
@@ -1421,8 +1589,10 @@ GroupCounts read_group_counts(const tgx_plan *plan, tgx_state *state, size_t spe
 }
 
 std::shared_ptr<Analyzer> completeness_with_grouping(const std::string &column, const GroupingConfig &config,
-                                                     bool strict_reference_types, const std::string &group_arrow_type) {
-  return std::make_shared<GroupedCompletenessAnalyzer>(column, config, strict_reference_types, group_arrow_type);
+                                                     bool strict_reference_types, const std::string &group_arrow_type,
+                                                     const std::vector<std::string> &group_arrow_types) {
+  return std::make_shared<GroupedCompletenessAnalyzer>(column, config, strict_reference_types, group_arrow_type,
+                                                       group_arrow_types);
 }
 
 std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
@@ -1477,7 +1647,13 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
       else cfg.max_groups = mg->as_u64();
     }
     cfg.include_overall = v.get_bool("include_overall", true);
-    return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"));
+    cfg.composite_on_device = v.get_bool("composite_groups_on_device", false);
+    std::vector<std::string> group_arrow_types;
+    if (const json::Value *at = v.get("group_arrow_types"))
+      if (at->type == json::Value::Array)
+        for (const json::Value &e : at->arr) group_arrow_types.push_back(e.type == json::Value::String ? e.str : std::string());
+    return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"),
+                                      group_arrow_types);
   }
   if (t == "compliance") return std::make_shared<ComplianceAnalyzer>(v.get_str("name"), v.get_str("predicate"));
   if (t == "data_type") return std::make_shared<DataTypeAnalyzer>(col(), v.get_str("arrow_type"));
@@ -1573,7 +1749,8 @@ AnalyzerContext AnalysisRunner::run(const Context &ctx) const {
       s.column2 = r.column2.empty() ? -1 : column_index(r.column2);
       s.flags = r.flags;
       if (r.kind == TGX_CHECK_DISTINCT) s.flags |= TGX_FLAG_EXACT_KEYS;  // DistinctnessAnalyzer counts by value
-      if (r.kind == TGX_CHECK_ROW_PREDICATE) {  // (the one kind of this runner that names its columns through a list)
+      // (the kinds of this runner that name columns through a list: a predicate's, and a GROUP BY over several)
+      if (r.kind == TGX_CHECK_ROW_PREDICATE || (r.kind == TGX_CHECK_GROUP_COUNTS && !r.columns.empty())) {
         list_columns.emplace_back();
         for (const std::string &c : r.columns) list_columns.back().push_back(column_index(c));
         s.columns = list_columns.back().data();

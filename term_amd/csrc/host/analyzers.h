@@ -119,13 +119,21 @@ struct GroupingConfig {
   std::optional<uint64_t> max_groups = 10000;
   bool include_overall = true;
   OverflowStrategy overflow_strategy = OverflowStrategy::TopK;
+  // an opt-in: 2 .. 8 group columns are one TGX_CHECK_GROUP_COUNTS request on the tuple of the columns (off: more than
+  // one group column is the analyzer's error, as it always was)
+  bool composite_on_device = false;
+  GroupingConfig &composite_groups_on_device(bool on) {
+    composite_on_device = on;
+    return *this;
+  }
 };
 class Analyzer;
 // CompletenessAnalyzer::with_grouping (grouped.rs:200-210, basic/grouped_completeness.rs): the one grouped analyzer.
 // strict_reference_types: only a group column declared Utf8 is taken (see the class in analyzers.cpp)
 std::shared_ptr<Analyzer> completeness_with_grouping(const std::string &column, const GroupingConfig &config,
                                                      bool strict_reference_types = true,
-                                                     const std::string &group_arrow_type = std::string());
+                                                     const std::string &group_arrow_type = std::string(),
+                                                     const std::vector<std::string> &group_arrow_types = {});
 
 struct FirstPass {  // what the request's range phase found
   int kind = 0;                   // the kind of plan()[0]

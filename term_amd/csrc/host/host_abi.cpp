@@ -521,6 +521,11 @@ extern "C" tgx_status tgx_host_analyzer_plan_json(const char *analyzer_json, con
         o += ", \"pair_counts\": {\"max_pairs\": " + std::to_string(r.pair_counts->max_pairs) + ", \"max_value_bytes\": " +
              std::to_string(r.pair_counts->max_value_bytes) + ", \"x_mode\": " + std::to_string(r.pair_counts->x.mode) +
              ", \"y_mode\": " + std::to_string(r.pair_counts->y.mode) + "}";
+      if (r.kind == TGX_CHECK_GROUP_COUNTS && !r.columns.empty()) {  // (a tuple of group columns: the spec's list)
+        o += ", \"columns\": [";
+        for (size_t c = 0; c < r.columns.size(); c++) o += (c ? ", " : "") + json::quote(r.columns[c]);
+        o += "]";
+      }
       if (r.group_counts)
         o += ", \"group_counts\": {\"max_groups\": " + std::to_string(r.group_counts->max_groups) +
              ", \"max_value_bytes\": " + std::to_string(r.group_counts->max_value_bytes) + "}";
@@ -769,10 +774,13 @@ static SideSums side_sums_from(const json::Value &v) {
       if (j.type == json::Value::String) {
         s.is_bytes = true;
         g.bytes = j.str;
+      } else if (j.type == json::Value::Array) {  // (bytes that are no text: an encoded tuple key)
+        s.is_bytes = true;
+        for (const json::Value &b : j.arr) g.bytes += (char)(unsigned char)b.as_u64();
       } else if (j.type == json::Value::Number) {
         g.value = j.as_i64();
       } else {
-        throw TermError{TermError::Internal, "a key is a string or an integer"};
+        throw TermError{TermError::Internal, "a key is a string, an array of bytes or an integer"};
       }
       g.sum = e.arr[1].num;
       s.groups.push_back(std::move(g));
@@ -782,6 +790,7 @@ static SideSums side_sums_from(const json::Value &v) {
     if (n->type == json::Value::Number) s.null_group = n->num;
   s.overflow_rows = v.get_u64("overflow_rows", 0);
   s.long_rows = v.get_u64("long_rows", 0);
+  s.arity = (int)v.get_u64("arity", 0);
   return s;
 }
 
@@ -815,7 +824,8 @@ extern "C" tgx_status tgx_host_cross_table_sum_json(const char *constraint_json,
                     json::quote(c->left_column()) + ", \"right_column\": " + json::quote(c->right_column()) + ", \"group_by\": [";
     for (size_t i = 0; i < c->group_by_columns().size(); i++) o += (i ? ", " : "") + json::quote(c->group_by_columns()[i]);
     o += "], \"tolerance\": " + json_f64(c->tolerance_value()) + ", \"max_violations_reported\": " +
-         std::to_string(c->violations_reported()) + ", \"max_groups\": " + std::to_string(c->groups_bound()) + "}}";
+         std::to_string(c->violations_reported()) + ", \"max_groups\": " + std::to_string(c->groups_bound()) +
+         (c->composite_groups() ? ", \"composite_groups_on_device\": true" : "") + "}}";
     *out_json = dup_string(o);
     return TGX_OK;
   } catch (const TermError &e) {

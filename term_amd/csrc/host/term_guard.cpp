@@ -1788,6 +1788,7 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
     x->max_violations_reported((size_t)c.get_u64("max_violations_reported", 100));
     x->max_groups((uint32_t)std::min<uint64_t>(c.get_u64("max_groups", CrossTableSumConstraint::kDefaultMaxGroups),
                                                UINT32_MAX));
+    if (c.get("composite_groups_on_device")) x->composite_groups_on_device(c.get_bool("composite_groups_on_device"));
     b.constraint(std::move(x));
   } else if (type == "foreign_key") {
     // {"type": "foreign_key", "child_column": "orders.customer_id", "parent_column": "customers.id", "allow_nulls": false,

@@ -172,7 +172,8 @@ struct TemporalRequest {
 struct SpecRequest {
   int kind = 0;  // tgx_check_kind
   std::string column, column2;
-  std::vector<std::string> columns;  // DISTINCT over a tuple of columns (then `column` is columns[0])
+  std::vector<std::string> columns;  // DISTINCT over a tuple of columns (then `column` is columns[0]); GROUP_COUNTS by
+                                     // the tuple of these columns (`column` stays the value column, `column2` is empty)
   uint32_t flags = 0;
   std::string pattern;
   uint32_t kll_k = 0;
@@ -261,6 +262,9 @@ bool reference_extracts_quantile(const std::string &arrow_type);
 // One side's groups as the join takes them: COALESCE(SUM(col), 0.0) as a double per key, ascending by key
 struct SideSums {
   bool is_bytes = false;                             // string keys (`bytes`), else integer keys (`value`)
+  int arity = 0;                                     // 2 .. 8: GROUP BY a tuple of columns, `bytes` an encoded tuple key
+                                                     // (group_key.h); 0: one group column.  The tuple join refuses a
+                                                     // side whose arity is not the constraint's
   struct Group {
     int64_t value = 0;
     std::string bytes;
@@ -285,6 +289,12 @@ class CrossTableSumConstraint : public Constraint {
   // this layer's own: the groups a side's table on the device is sized for (1 .. 65 536).  A side with rows beyond it
   // (overflow) or with keys longer than 256 bytes makes the constraint an error that names the bound
   CrossTableSumConstraint &max_groups(uint32_t n) { max_groups_ = n; return *this; }
+  // an opt-in: 2 .. 8 group_by columns are one TGX_CHECK_GROUP_SUMS walk a side on the tuple of the columns, and the
+  // outer join merges the two sides' entries by their encoded key bytes (off: several columns are an error, as ever)
+  CrossTableSumConstraint &composite_groups_on_device(bool on) { composite_ = on; return *this; }
+  bool composite_groups() const { return composite_; }
+  // the opt-in given and 2 .. 8 group_by columns: the sides are tuple walks and join() merges encoded tuple keys
+  bool groups_by_tuple() const { return composite_ && group_by_.size() >= 2 && group_by_.size() <= 8; }
 
   const std::string &left_column() const { return left_; }
   const std::string &right_column() const { return right_; }
@@ -313,6 +323,8 @@ class CrossTableSumConstraint : public Constraint {
   double tolerance_ = 0.0;
   size_t max_violations_ = 100;
   uint32_t max_groups_ = kDefaultMaxGroups;
+  bool composite_ = false;
+  CrossTableSumRow join_tuples(const SideSums &left, const SideSums &right) const;  // (2 .. 8 group columns)
 };
 
 // ---- constraints/foreign_key.rs: every non-NULL value of child.c is a value of parent.p.  The parent's column is walked

@@ -243,17 +243,24 @@ struct PairCountsTask {
 // TGX_CHECK_GROUP_COUNTS (groupcounts_device.cpp): one task per spec; `set` once tgx_plan_set_group_counts was called.
 // The set tasks that share the group column and both bounds ride one walk of the group column, up to
 // kGroupCountsMembers of them, in plan order: `leader` is the first task of this one's walk (`slot`: the task's own
-// index), whose table and shared counters hold the walk's; `member`: the task's place in the walk
+// index), whose table and shared counters hold the walk's; `member`: the task's place in the walk.
+// A spec with a column list groups by the TUPLE of its columns: `n_tuple` of them (2 .. 8, or 0: the spec groups by
+// `group`), and `group` is then tuple[0].  Tuple tasks share a walk when their lists are the same, in the same order
+constexpr int kGroupMaxTuple = 8;  // (kMaxTupleCols: the arities tuple_fingerprint is made for)
 struct GroupCountsTask {
   int column, group, spec_index, slot, leader, member;
+  int n_tuple;
+  int tuple[kGroupMaxTuple];
   bool set;
   tgx_group_counts_params params;
 };
 
 // TGX_CHECK_GROUP_SUMS (groupsums_device.cpp): one task per spec, each with a walk and a table of its own; `set` once
-// tgx_plan_set_group_sums was called
+// tgx_plan_set_group_sums was called.  `n_tuple` / `tuple`: the spec's column list, as GroupCountsTask has it
 struct GroupSumsTask {
   int column, group, spec_index;
+  int n_tuple;
+  int tuple[kGroupMaxTuple];
   bool set;
   tgx_group_sums_params params;
 };

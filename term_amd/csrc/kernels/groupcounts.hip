@@ -28,6 +28,11 @@
 //                     (1 + members) * entries fit kGroupCountsDictLdsCells, in global memory otherwise);
 //                     group_counts_dict_insert_kernel takes a lane per used entry, fingerprints it and inserts it with
 //                     all its counters.  Rows of NULL entries, and indices outside the dictionary, are NULL-key rows.
+//   tuple route       group_counts_tuple_kernel<ARITY, NUMERIC>: GROUP BY the tuple of 2 .. 8 columns (a spec with a
+//                     column list).  The string route's walk with tuple_key.h's fingerprint for the key -- the one
+//                     DISTINCT and KEY_PROBE give the tuple -- and tuple_group.h's canonical bytes for the entry: the
+//                     lane that makes a global slot encodes the row it holds, or the row the LDS slot remembers.  NULL
+//                     is a value here: there are no NULL-key rows, (NULL, 'a') is a group like any other.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +42,7 @@
 #include "device_types.h"
 #include "fingerprint.h"
 #include "row_walk.h"
+#include "tuple_group.h"
 
 namespace tgx {
 
@@ -369,6 +375,122 @@ __global__ __launch_bounds__(256) void group_counts_utf8_kernel(const Utf8ColDes
   }
 }
 
+// ---- tuple route --------------------------------------------------------------------------------------------------------
+namespace {
+// a tuple key (fa, fb) with its counters; `row` holds the key: the lane that makes the entry encodes it into the slot's
+// place in the store
+template <int ARITY, bool NUMERIC>
+__device__ __forceinline__ void gc_insert_global_tuple(const GroupCountsTable &t, const GroupMembers &mem,
+                                                       const KeyProbeTupleDesc &L, unsigned long long fa,
+                                                       unsigned long long fb, unsigned long long w,
+                                                       const unsigned long long (&nn)[kM], int64_t row) {
+  bool made;
+  const int64_t s = vc_claim128<uint64_t>(t.keys, t.keys2, t.mask, fa & t.mask, fa, fb, kValueCountsProbes, &made);
+  if (s < 0) {
+    gc_add_words(t, mem, kGcOverflowRows, w, nn);
+    return;
+  }
+  if (made) {
+    const uint32_t nulls = kpt_nulls<ARITY, NUMERIC>(L, row);
+    const uint64_t len = tuple_encoded_length<ARITY, NUMERIC>(L, row, nulls);
+    if (len <= t.max_value_bytes) {  // (always: a longer row is a long row and comes to no slot)
+      tuple_encode<ARITY, NUMERIC>(L, row, nulls, t.store + (uint64_t)s * (uint64_t)t.max_value_bytes);
+      t.lens[s] = (uint32_t)len;
+    }
+  }
+  gc_add_slot(t, mem, (uint64_t)s, w, nn);
+}
+}  // namespace
+
+template <int ARITY, bool NUMERIC>
+__global__ __launch_bounds__(256) void group_counts_tuple_kernel(const KeyProbeTupleDesc L, const GroupMembers mem,
+                                                                 const GroupCountsTable t) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  __shared__ GcLdsStrings lds;
+  for (uint32_t s = threadIdx.x; s < kValueCountsStrLdsSlots; s += 256) {
+    lds.fa[s] = lds.fb[s] = kEmptyKey;
+    lds.total[s] = 0;
+#pragma unroll
+    for (int m = 0; m < kM; m++) lds.nn[m][s] = 0;
+  }
+  __syncthreads();
+  GcWaveWords longs;
+  gc_wave_clear(longs);
+  // the key (fa, fb) of row `row` with its counters: the workgroup's table, or the global one where that is full
+  // around the key's place
+  auto insert = [&](unsigned long long fa, unsigned long long fb, unsigned long long w,
+                    const unsigned long long (&nn)[kM], int64_t row) {
+    bool made;
+    const int64_t s = vc_claim128<uint32_t>(lds.fa, lds.fb, kValueCountsStrLdsSlots - 1,
+                                            (uint32_t)fa & (kValueCountsStrLdsSlots - 1), fa, fb, kValueCountsLdsProbes,
+                                            &made);
+    if (s < 0) {
+      gc_insert_global_tuple<ARITY, NUMERIC>(t, mem, L, fa, fb, w, nn, row);
+      return;
+    }
+    if (made) lds.row[s] = (unsigned long long)row;  // (read after the workgroup's barrier)
+    atomicAdd(&lds.total[s], (unsigned int)w);
+#pragma unroll
+    for (int m = 0; m < kM; m++)
+      if (m < mem.n && nn[m]) atomicAdd(&lds.nn[m][s], (unsigned int)nn[m]);
+  };
+  // (the loop is uniform within the wave: a wave's lanes hold 64 consecutive rows and take part in every ballot)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < L.d.length; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const bool in = i < L.d.length;
+    unsigned long long vm[kM];
+    gc_windows(mem, mem.n, i, in, vm);
+    unsigned long long fa = 0, fb = 0;
+    bool live = false, too_long = false;
+    if (in) {
+      const uint32_t nulls = kpt_nulls<ARITY, NUMERIC>(L, i);  // (before any value is read)
+      if (tuple_encoded_length<ARITY, NUMERIC>(L, i, nulls) > (uint64_t)t.max_value_bytes) {
+        too_long = true;
+      } else {
+        uint64_t a, b;
+        kpt_fingerprint<ARITY, NUMERIC>(L, i, nulls, &a, &b);
+        fa = a;
+        fb = b;
+        live = true;
+      }
+    }
+    gc_wave_count(longs, __ballot(too_long), vm);
+    unsigned long long todo = __ballot(live);
+    bool pending = live;
+    for (int round = 0; round < 4 && todo != 0; round++) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const unsigned long long la = vc_shfl64(fa, leader), lb = vc_shfl64(fb, leader);
+      const bool mine = pending && fa == la && fb == lb;
+      const unsigned long long same = __ballot(mine);
+      if (lane == leader) {
+        unsigned long long w, nn[kM];
+        gc_lane_counts(true, same, lane, vm, &w, nn);
+        insert(fa, fb, w, nn, i);
+      }
+      pending = pending && !mine;
+      todo &= ~same;
+    }
+    if (pending) {
+      unsigned long long w, nn[kM];
+      gc_lane_counts(false, 0ull, lane, vm, &w, nn);
+      insert(fa, fb, w, nn, i);
+    }
+  }
+  gc_wave_flush(t, mem, kGcLongRows, longs);
+  __syncthreads();
+  // every occupied LDS slot is one global insert with its counters; its bytes are those of the row it remembers
+  for (uint32_t s = threadIdx.x; s < kValueCountsStrLdsSlots; s += 256) {
+    const unsigned long long fa = lds.fa[s], fb = lds.fb[s];
+    const unsigned int n = lds.total[s];
+    if (fa == kEmptyKey || fb == kEmptyKey || n == 0) continue;
+    unsigned long long nn[kM];
+#pragma unroll
+    for (int m = 0; m < kM; m++) nn[m] = lds.nn[m][s];
+    gc_insert_global_tuple<ARITY, NUMERIC>(t, mem, L, fa, fb, (unsigned long long)n, nn, (int64_t)lds.row[s]);
+  }
+}
+
 // ---- dictionary route ---------------------------------------------------------------------------------------------------
 // the rows' indices into cells[(1 + members) * dict_length]: cell c of entry e is cells[c * dict_length + e], c = 0 the
 // rows, c = 1 + m member m's non-NULL rows.  A NULL index, and an index outside the dictionary (never read), make the
@@ -496,6 +618,16 @@ void launch_group_counts_dict(const int32_t *indices, const uint8_t *validity, i
   if (dict.length > 0)
     hipLaunchKernelGGL(group_counts_dict_insert_kernel, dim3(grid_for((uint64_t)dict.length)), dim3(256), 0, stream,
                        dict, mem, cells, t);
+}
+
+// `numeric`: every component is an 8-byte integer column (TupleCol::kind 0)
+void launch_group_counts_tuples(const KeyProbeTupleDesc &L, bool numeric, const GroupMembers &mem,
+                                const GroupCountsTable &t, hipStream_t stream) {
+  const dim3 grid(grid_for((uint64_t)L.d.length)), block(256);
+#define TGX_GCT_CASE(N, NUMERIC) \
+  hipLaunchKernelGGL((group_counts_tuple_kernel<N, NUMERIC>), grid, block, 0, stream, L, mem, t);
+  TGX_TUPLE_GROUP_DISPATCH(L.d.n_cols, numeric, TGX_GCT_CASE)
+#undef TGX_GCT_CASE
 }
 
 }  // namespace tgx

@@ -26,6 +26,9 @@
 //   dictionary route  group_sums_dict_count_kernel sums per INDEX into cells of (rows, non_null, sum) -- in LDS while
 //                     the dictionary has at most kGroupSumsDictLdsEntries entries, in global memory otherwise;
 //                     group_sums_dict_insert_kernel takes a lane per used entry, fingerprints it and inserts it.
+//   tuple route       group_sums_tuple_kernel<kFloat, ARITY, NUMERIC>: GROUP BY the tuple of 2 .. 8 columns; the string
+//                     route's walk with tuple_key.h's fingerprint for the key and tuple_group.h's canonical bytes for the
+//                     entry, as group_counts_tuple_kernel has them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +38,7 @@
 #include "device_types.h"
 #include "fingerprint.h"
 #include "row_walk.h"
+#include "tuple_group.h"
 
 namespace tgx {
 
@@ -353,6 +357,115 @@ __global__ __launch_bounds__(256) void group_sums_utf8_kernel(const Utf8ColDesc 
   }
 }
 
+// ---- tuple route --------------------------------------------------------------------------------------------------------
+namespace {
+// a tuple key (fa, fb) with its counters; `row` holds the key: the lane that makes the entry encodes it into the slot's
+// place in the store
+template <bool kFloat, int ARITY, bool NUMERIC>
+__device__ __forceinline__ void gs_insert_global_tuple(const GroupSumsTable &t, const KeyProbeTupleDesc &L,
+                                                       unsigned long long fa, unsigned long long fb,
+                                                       unsigned long long w, unsigned long long nn,
+                                                       unsigned long long sum, int64_t row) {
+  bool made;
+  const int64_t s = vc_claim128<uint64_t>(t.keys, t.keys2, t.mask, fa & t.mask, fa, fb, kValueCountsProbes, &made);
+  if (s < 0) {
+    gs_add_words<kFloat>(t, kGsOverflow, w, nn, sum);
+    return;
+  }
+  if (made) {
+    const uint32_t nulls = kpt_nulls<ARITY, NUMERIC>(L, row);
+    const uint64_t len = tuple_encoded_length<ARITY, NUMERIC>(L, row, nulls);
+    if (len <= t.max_value_bytes) {  // (always: a longer row is a long row and comes to no slot)
+      tuple_encode<ARITY, NUMERIC>(L, row, nulls, t.store + (uint64_t)s * (uint64_t)t.max_value_bytes);
+      t.lens[s] = (uint32_t)len;
+    }
+  }
+  gs_add_slot<kFloat>(t, (uint64_t)s, w, nn, sum);
+}
+}  // namespace
+
+// L: the group columns; val: the value column (with its own validity and Arrow offset).  NULL is a value of a
+// component: there are no NULL-key rows
+template <bool kFloat, int ARITY, bool NUMERIC>
+__global__ __launch_bounds__(256) void group_sums_tuple_kernel(const KeyProbeTupleDesc L, const GroupSumsValue val,
+                                                               const GroupSumsTable t) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  __shared__ GsLdsStrings lds;
+  for (uint32_t s = threadIdx.x; s < kGroupSumsStrLdsSlots; s += 256) {
+    lds.fa[s] = lds.fb[s] = kEmptyKey;
+    lds.sum[s] = 0;
+    lds.rows[s] = lds.nn[s] = 0;
+  }
+  __syncthreads();
+  GsWaveClass longs;
+  gs_class_clear(longs);
+  auto insert = [&](unsigned long long fa, unsigned long long fb, unsigned int w, unsigned int nn,
+                    unsigned long long sum, int64_t row) {
+    bool made;
+    const int64_t s = vc_claim128<uint32_t>(lds.fa, lds.fb, kGroupSumsStrLdsSlots - 1,
+                                            (uint32_t)fa & (kGroupSumsStrLdsSlots - 1), fa, fb, kValueCountsLdsProbes,
+                                            &made);
+    if (s < 0) {
+      gs_insert_global_tuple<kFloat, ARITY, NUMERIC>(t, L, fa, fb, w, nn, sum, row);
+      return;
+    }
+    if (made) lds.row[s] = (unsigned long long)row;  // (read after the workgroup's barrier)
+    atomicAdd(&lds.rows[s], w);
+    if (nn) {
+      atomicAdd(&lds.nn[s], nn);
+      gs_atomic_add<kFloat>(&lds.sum[s], sum);
+    }
+  };
+  // (the loop is uniform within the wave: a wave's lanes hold 64 consecutive rows and take part in every ballot)
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < L.d.length; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const bool in = i < L.d.length;
+    bool vok;
+    const unsigned long long v = gs_value(val, i, in, &vok);
+    const unsigned long long vm = __ballot(vok);
+    unsigned long long fa = 0, fb = 0;
+    bool live = false, too_long = false;
+    if (in) {
+      const uint32_t nulls = kpt_nulls<ARITY, NUMERIC>(L, i);  // (before any value is read)
+      if (tuple_encoded_length<ARITY, NUMERIC>(L, i, nulls) > (uint64_t)t.max_value_bytes) {
+        too_long = true;
+      } else {
+        uint64_t a, b;
+        kpt_fingerprint<ARITY, NUMERIC>(L, i, nulls, &a, &b);
+        fa = a;
+        fb = b;
+        live = true;
+      }
+    }
+    gs_class_count<kFloat>(longs, __ballot(too_long), too_long, vm, v);
+    unsigned long long todo = __ballot(live);
+    bool pending = live;
+    for (int round = 0; round < 4 && todo != 0; round++) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const unsigned long long la = vc_shfl64(fa, leader), lb = vc_shfl64(fb, leader);
+      const bool mine = pending && fa == la && fb == lb;
+      const unsigned long long same = __ballot(mine);
+      const unsigned long long led = gs_same_sum<kFloat>(same, mine, v);
+      if (lane == leader)
+        insert(fa, fb, (unsigned int)__popcll(same), (unsigned int)__popcll(same & vm), led, i);
+      pending = pending && !mine;
+      todo &= ~same;
+    }
+    if (pending) insert(fa, fb, 1u, (unsigned int)((vm >> lane) & 1ull), v, i);
+  }
+  gs_class_flush<kFloat>(t, kGsLong, longs);
+  __syncthreads();
+  // every occupied LDS slot is one global insert with its counters; its bytes are those of the row it remembers
+  for (uint32_t s = threadIdx.x; s < kGroupSumsStrLdsSlots; s += 256) {
+    const unsigned long long fa = lds.fa[s], fb = lds.fb[s];
+    const unsigned int n = lds.rows[s];
+    if (fa == kEmptyKey || fb == kEmptyKey || n == 0) continue;
+    gs_insert_global_tuple<kFloat, ARITY, NUMERIC>(t, L, fa, fb, (unsigned long long)n, lds.nn[s], lds.sum[s],
+                                                   (int64_t)lds.row[s]);
+  }
+}
+
 // ---- dictionary route ---------------------------------------------------------------------------------------------------
 // the rows' indices into cells[3 * dict_length]: entry e has its rows at cells[e], its non-NULL values at
 // cells[dict_length + e], their sum at cells[2 * dict_length + e].  A NULL index, and an index outside the dictionary
@@ -500,6 +613,25 @@ void launch_group_sums_dict(const int32_t *indices, const uint8_t *validity, int
                             const GroupSumsTable &t, bool is_float, hipStream_t stream) {
   if (is_float) dict_launches<true>(indices, validity, offset, length, dict, val, cells, t, stream);
   else dict_launches<false>(indices, validity, offset, length, dict, val, cells, t, stream);
+}
+
+namespace {
+template <bool kFloat>
+void tuple_launches(const KeyProbeTupleDesc &L, bool numeric, const GroupSumsValue &val, const GroupSumsTable &t,
+                    hipStream_t stream) {
+  const dim3 grid(grid_for((uint64_t)L.d.length)), block(256);
+#define TGX_GST_CASE(N, NUMERIC) \
+  hipLaunchKernelGGL((group_sums_tuple_kernel<kFloat, N, NUMERIC>), grid, block, 0, stream, L, val, t);
+  TGX_TUPLE_GROUP_DISPATCH(L.d.n_cols, numeric, TGX_GST_CASE)
+#undef TGX_GST_CASE
+}
+}  // namespace
+
+// `numeric`: every component is an 8-byte integer column (TupleCol::kind 0)
+void launch_group_sums_tuples(const KeyProbeTupleDesc &L, bool numeric, const GroupSumsValue &val,
+                              const GroupSumsTable &t, bool is_float, hipStream_t stream) {
+  if (is_float) tuple_launches<true>(L, numeric, val, t, stream);
+  else tuple_launches<false>(L, numeric, val, t, stream);
 }
 
 }  // namespace tgx

@@ -41,65 +41,7 @@
 
 namespace tgx {
 
-namespace {
-
-// is component c of row i a value?  (NUMERIC: every component is kind 0)
-template <bool NUMERIC>
-__device__ __forceinline__ bool kpt_valid(const KeyProbeTupleDesc &L, int c, int64_t i) {
-  const TupleCol &col = L.d.cols[c];
-  const int64_t slot = col.offset + i;
-  global_u8_ptr vbits = (global_u8_ptr)(uintptr_t)col.validity;
-  if (vbits && !TGX_VALID_BIT(vbits, slot)) return false;
-  if (!NUMERIC && col.kind == 4) {
-    const int64_t idx = (int64_t)((global_i32_ptr)(uintptr_t)col.values)[slot];
-    if ((uint64_t)idx >= (uint64_t)L.dict_length[c]) return false;  // (a negative index too)
-    global_u8_ptr dbits = (global_u8_ptr)(uintptr_t)col.dict_validity;
-    if (dbits && !TGX_VALID_BIT(dbits, col.dict_offset + idx)) return false;
-  }
-  return true;
-}
-
-// bit c: component c of row i is NULL
-template <int ARITY, bool NUMERIC>
-__device__ __forceinline__ uint32_t kpt_nulls(const KeyProbeTupleDesc &L, int64_t i) {
-  uint32_t nulls = 0;
-#pragma unroll
-  for (int c = 0; c < ARITY; c++) nulls |= kpt_valid<NUMERIC>(L, c, i) ? 0u : 1u << c;
-  return nulls;
-}
-
-// tuple_fingerprint's message for row i, whose NULL components are `nulls`: a component that is NULL is not read (an
-// index outside its dictionary leads nowhere)
-template <int ARITY, bool NUMERIC>
-__device__ __forceinline__ void kpt_fingerprint(const KeyProbeTupleDesc &L, int64_t i, uint32_t nulls, uint64_t *out_a,
-                                                uint64_t *out_b) {
-  Fp s;
-  fp_init(s, L.d.key);
-#pragma unroll
-  for (int c = 0; c < ARITY; c++) {
-    const TupleCol &col = L.d.cols[c];
-    uint64_t ca = 0x4e554c4c4e554c4cULL, cb = 0;  // the NULL marker
-    if (!((nulls >> c) & 1)) {
-      if (NUMERIC || col.kind == 0) {
-        ca = (uint64_t)((global_i64_ptr)(uintptr_t)col.values)[col.offset + i];
-        cb = 1;
-      } else {
-        const TupleComp comp = tuple_component(L.d, c, i);
-        if (comp.kind == 2) {  // (nothing else: the component is a value and no number)
-          fingerprint(L.d.key, comp.p, comp.len, &ca, &cb);
-          cb |= 2;
-        }
-      }
-    }
-    if (c + 1 < ARITY)
-      fp_block(s, ca, cb);
-    else
-      fp_last_padded(s, ca, cb, true, L.d.key);
-  }
-  fp_out(s, out_a, out_b);
-}
-
-}  // namespace
+// (kpt_valid, kpt_nulls and kpt_fingerprint: tuple_key.h, shared with the tuple GROUP BY of tuple_group.h)
 
 // ---- the probe -----------------------------------------------------------------------------------------------------------
 // `Set`: KeyProbeStringSet, or KeyProbeCountedStringSet for a counted task, whose hits also sum their slots' counts.

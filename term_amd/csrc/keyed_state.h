@@ -9,6 +9,7 @@
 
 #include "api_internal.h"
 #include "counted_state.h"
+#include "group_key.h"
 
 namespace tgx {
 
@@ -70,6 +71,20 @@ TGX_HIDDEN inline tgx_status keyed_read_entries(const char *name, const char *no
     r.get(&v[0], len);
     return TGX_OK;
   }, err);
+}
+
+// the entries a blob brings a task that groups by a tuple of `arity` columns (0: it does not, and nothing is asked):
+// every key is the canonical form of such a tuple (group_key.h)
+template <class P>
+TGX_HIDDEN inline tgx_status tuple_keys_ok(const char *name, size_t k, int arity, const KeyedEntries<P> &e,
+                                           tgx_error *err) {
+  if (arity == 0) return TGX_OK;
+  for (const auto &s : e.strs)
+    if (!group_key_valid((const uint8_t *)s.first.data(), s.first.size(), arity))
+      return fail(err, TGX_INVALID_ARGUMENT,
+                  "malformed state blob (%s task %zu: a key that is not the encoded form of a tuple of %d columns)", name,
+                  k, arity);
+  return TGX_OK;
 }
 
 // A *_entries call: the sizes, then the entries -- the integers, then the strings with their bytes laid end to end.
@@ -184,6 +199,59 @@ struct TGX_HIDDEN KeyedCheck : CountedState<K> {
     if (!*dict || !is_string((*dict)->type)) return fail(err, TGX_INVALID_ARGUMENT, "%s: malformed dictionary", kName);
     return TGX_OK;
   }
+  // The `n` columns `tuple` of a task on tuple keys as the kernels take them (update_validate has refused floats, UInt64
+  // and Booleans, and the staging has widened every integer column to 8 bytes); *numeric: every component is an integer
+  // column.  *bytes: what a walk reads at the least -- 8 bytes a row of an integer component (a string component's
+  // bytes are not known here: its offsets, views or indices) and a bit of validity where there is a bitmap
+  static tgx_status tuple_desc(const tgx_plan *plan, const int *tuple, int n, const tgx_column *dev,
+                               KeyProbeTupleDesc *L, bool *numeric, uint64_t *bytes, tgx_error *err) {
+    memset(L, 0, sizeof(*L));
+    L->d.n_cols = n;
+    L->d.length = dev[tuple[0]].length;
+    L->d.key = plan->fp_key;
+    *numeric = true;
+    *bytes = 0;
+    for (int c = 0; c < n; c++) {
+      const tgx_column &x = dev[tuple[c]];
+      TupleCol &tc = L->d.cols[c];
+      tc.validity = x.validity;
+      tc.offset = x.offset;
+      switch (route_of(x)) {
+        case kIntRoute:
+          tc.kind = 0;
+          tc.values = x.values;
+          break;
+        case kStringRoute:
+          tc.kind = x.type == TGX_UTF8 ? 1 : x.type == TGX_LARGE_UTF8 ? 2 : 3;
+          tc.values = x.type == TGX_UTF8_VIEW ? x.values : nullptr;
+          tc.buffers = x.type == TGX_UTF8_VIEW ? x.variadic : nullptr;
+          tc.offsets = x.offsets;
+          tc.data = x.data;
+          *numeric = false;
+          break;
+        case kDictRoute: {
+          const tgx_column *dc;
+          TGX_TRY(dictionary_of(x, &dc, err));
+          tc.kind = 4;
+          tc.dict_large = dc->type == TGX_LARGE_UTF8 ? 1 : 0;
+          tc.values = x.values;
+          tc.offsets = dc->offsets;
+          tc.data = dc->data;
+          tc.dict_validity = dc->validity;
+          tc.dict_offset = dc->offset;
+          L->dict_length[c] = dc->length;
+          *numeric = false;
+          break;
+        }
+        default:
+          return fail(err, TGX_UNSUPPORTED, "%s on tuple keys takes integer and string columns (%d)", kName, x.type);
+      }
+      *bytes += (uint64_t)x.length * (tc.kind == 0 || tc.kind == 2 ? 8 : tc.kind == 3 ? 16 : 4) +
+                (x.validity ? (uint64_t)(x.length + 7) / 8 : 0);
+    }
+    return TGX_OK;
+  }
+
   // the dictionary route's cells of table k: `bytes` of them, zero
   tgx_status clear_cells(tgx_state *st, size_t k, size_t bytes, unsigned long long **cells, tgx_error *err) {
     DevBuf &c = dev_part[k].cells;

@@ -807,69 +807,16 @@ struct ProbeCheck final : KeyedCheck<ProbeKind> {
     return TGX_OK;
   }
 
-  // the columns of tuples task k as the kernels take them (update_validate has refused floats, UInt64 and Booleans,
-  // and the staging has widened every integer column to 8 bytes); *numeric: every component is an integer column
-  tgx_status tuple_desc(tgx_state *st, size_t k, const tgx_column *dev, KeyProbeTupleDesc *L, bool *numeric,
-                        tgx_error *err) {
-    const KeyProbeTask &task = tasks[k];
-    memset(L, 0, sizeof(*L));
-    L->d.n_cols = task.n_tuple;
-    L->d.length = dev[task.tuple[0]].length;
-    L->d.key = st->plan->fp_key;
-    *numeric = true;
-    for (int c = 0; c < task.n_tuple; c++) {
-      const tgx_column &x = dev[task.tuple[c]];
-      TupleCol &tc = L->d.cols[c];
-      tc.validity = x.validity;
-      tc.offset = x.offset;
-      switch (route_of(x)) {
-        case kIntRoute:
-          tc.kind = 0;
-          tc.values = x.values;
-          break;
-        case kStringRoute:
-          tc.kind = x.type == TGX_UTF8 ? 1 : x.type == TGX_LARGE_UTF8 ? 2 : 3;
-          tc.values = x.type == TGX_UTF8_VIEW ? x.values : nullptr;
-          tc.buffers = x.type == TGX_UTF8_VIEW ? x.variadic : nullptr;
-          tc.offsets = x.offsets;
-          tc.data = x.data;
-          *numeric = false;
-          break;
-        case kDictRoute: {
-          const tgx_column *dc;
-          TGX_TRY(dictionary_of(x, &dc, err));
-          tc.kind = 4;
-          tc.dict_large = dc->type == TGX_LARGE_UTF8 ? 1 : 0;
-          tc.values = x.values;
-          tc.offsets = dc->offsets;
-          tc.data = dc->data;
-          tc.dict_validity = dc->validity;
-          tc.dict_offset = dc->offset;
-          L->dict_length[c] = dc->length;
-          *numeric = false;
-          break;
-        }
-        default:
-          return fail(err, TGX_UNSUPPORTED, "KEY_PROBE on tuple keys takes integer and string columns (%d)", x.type);
-      }
-    }
-    return TGX_OK;
-  }
-
   // one batch of tuples task k: the probe against its set, or the gather of its all-valid tuples
   tgx_status walk_tuples(tgx_state *st, size_t k, const tgx_column *dev, int64_t nrows, tgx_error *err) {
     KeyProbeTupleDesc L;
     bool numeric = true;
-    TGX_TRY(tuple_desc(st, k, dev, &L, &numeric, err));
+    // what the walk reads: KeyedCheck::tuple_desc's figure
+    uint64_t bytes = 0;
+    TGX_TRY(tuple_desc(st->plan, tasks[k].tuple, tasks[k].n_tuple, dev, &L, &numeric, &bytes, err));
     // (per-lane and LDS counters are 32-bit: the launchers take up to 2048 workgroups)
     TGX_TRY(side_rows_fit("KEY_PROBE", nrows, 1024, err));
     unsigned long long *words = d_counts.as<unsigned long long>() + word_off[k];
-    // what the walk reads: 8 bytes a row of an integer component (a string component's bytes are not known here: its
-    // offsets or indices at the least) and a bit of validity where there is a bitmap
-    uint64_t bytes = 0;
-    for (int c = 0; c < L.d.n_cols; c++)
-      bytes += (uint64_t)nrows * (L.d.cols[c].kind == 0 || L.d.cols[c].kind == 2 ? 8 : L.d.cols[c].kind == 3 ? 16 : 4) +
-               (L.d.cols[c].validity ? (uint64_t)(nrows + 7) / 8 : 0);
     if (tasks[k].mode == kKpRowsTuples) {
       TGX_TRY(gather_room(st, k, nrows, err));
       ProfScope ps(st, "key_probe_rows", bytes + (uint64_t)nrows * 32);

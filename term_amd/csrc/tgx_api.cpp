@@ -199,8 +199,11 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
   for (size_t i = 0; i < n_specs; i++) {
     tgx_check_spec &sp = plan->specs[i];
     std::vector<int> tuple;
-    const bool takes_list =
-        sp.kind == TGX_CHECK_DISTINCT || sp.kind == TGX_CHECK_KEY_PROBE || sp.kind == TGX_CHECK_ROW_PREDICATE;
+    // (a GROUP_COUNTS / GROUP_SUMS spec without column2 groups by the tuple of its list: `column` stays its value column)
+    const bool groups_by_list =
+        (sp.kind == TGX_CHECK_GROUP_COUNTS || sp.kind == TGX_CHECK_GROUP_SUMS) && sp.column2 < 0;
+    const bool takes_list = sp.kind == TGX_CHECK_DISTINCT || sp.kind == TGX_CHECK_KEY_PROBE ||
+                            sp.kind == TGX_CHECK_ROW_PREDICATE || groups_by_list;
     // (a ROW_PREDICATE spec names its columns through the list whatever their number: its leaves refer to positions)
     if (sp.kind == TGX_CHECK_ROW_PREDICATE && (sp.n_columns < 1 || sp.n_columns > (uint32_t)kRowPredicateMaxCols || !sp.columns))
       return fail(err, sp.n_columns > (uint32_t)kRowPredicateMaxCols ? TGX_UNSUPPORTED : TGX_INVALID_ARGUMENT,
@@ -212,13 +215,17 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
     if (takes_list && (sp.n_columns >= 2 || sp.kind == TGX_CHECK_ROW_PREDICATE)) {
       if (sp.n_columns > (uint32_t)kMaxTupleCols || !sp.columns)
         return fail(err, TGX_UNSUPPORTED, "spec %zu: %s over %u columns (2..%d supported)", i,
-                    sp.kind == TGX_CHECK_DISTINCT ? "DISTINCT" : "KEY_PROBE", sp.n_columns, kMaxTupleCols);
+                    sp.kind == TGX_CHECK_DISTINCT       ? "DISTINCT"
+                    : sp.kind == TGX_CHECK_GROUP_COUNTS ? "GROUP_COUNTS"
+                    : sp.kind == TGX_CHECK_GROUP_SUMS   ? "GROUP_SUMS"
+                                                        : "KEY_PROBE",
+                    sp.n_columns, kMaxTupleCols);
       for (uint32_t k = 0; k < sp.n_columns; k++) {
         if (sp.columns[k] < 0) return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: negative column index", i);
         tuple.push_back(sp.columns[k]);
         max_col = std::max(max_col, sp.columns[k]);
       }
-      sp.column = tuple[0];
+      if (!groups_by_list) sp.column = tuple[0];
     } else if (!takes_list && sp.n_columns >= 2) {
       return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: only DISTINCT takes a column list", i);
     }
@@ -235,6 +242,19 @@ extern "C" tgx_status tgx_plan_create(const tgx_check_spec *specs, size_t n_spec
         KeyProbeTask &t = plan->key_probes.back();
         t.n_tuple = (int)tuple.size();
         std::copy(tuple.begin(), tuple.end(), t.tuple);
+      }
+      if (groups_by_list && !tuple.empty()) {  // (the task keeps the list; its `group` is the list's first column)
+        if (sp.kind == TGX_CHECK_GROUP_COUNTS) {
+          GroupCountsTask &t = plan->group_counts.back();
+          t.n_tuple = (int)tuple.size();
+          std::copy(tuple.begin(), tuple.end(), t.tuple);
+          t.group = tuple[0];
+        } else {
+          GroupSumsTask &t = plan->group_sums.back();
+          t.n_tuple = (int)tuple.size();
+          std::copy(tuple.begin(), tuple.end(), t.tuple);
+          t.group = tuple[0];
+        }
       }
       if (sp.kind == TGX_CHECK_ROW_PREDICATE) {
         RowPredicateTask &t = plan->row_predicates.back();

@@ -503,6 +503,15 @@ class CrossTableSumConstraint:
         self.spec["max_groups"] = int(n)
         return self
 
+    def composite_groups_on_device(self, on=True):
+        """an opt-in: 2 .. 8 group_by columns are one GROUP_SUMS walk a side on the tuple of the columns, joined on the
+        host by their encoded keys; a key with a NULL component never joins.  Off, several columns are an error"""
+        if on:
+            self.spec["composite_groups_on_device"] = True
+        else:
+            self.spec.pop("composite_groups_on_device", None)
+        return self
+
     def name(self): return "cross_table_sum"
     def left_column(self): return self.spec["left_column"]
     def right_column(self): return self.spec["right_column"]
@@ -1190,6 +1199,8 @@ class _Analyzer:
                 "max_groups": config.max_groups, "include_overall": bool(config.include_overall)}
         if not config.strict_reference_types:
             spec["strict_reference_types"] = False
+        if config.composite_on_device:
+            spec["composite_groups_on_device"] = True
         return _Analyzer(spec)
 
     def state_text_from_group_counts(self, summary, entries):
@@ -1263,13 +1274,20 @@ class GroupingConfig:
     groups by the metric, descending, are kept; also the bound of the table on the device, capped at
     GROUP_COUNTS_MAX_GROUPS), include_overall (default true) and the overflow strategy, which the reference carries and
     never reads.  strict_reference_types (default true): only a group column declared Utf8 is taken, the one type the
-    reference reads by value; off, strings of every layout group by value and integers print as decimal text"""
+    reference reads by value; off, strings of every layout group by value and integers print as decimal text.
+    composite_groups_on_device (default false, an opt-in): 2 .. 8 group columns are one GROUP_COUNTS walk on the tuple
+    of the columns; off, more than one group column is the analyzer's error"""
 
     def __init__(self, columns, max_groups=10000, include_overall=True, overflow_strategy="TopK",
-                 strict_reference_types=True):
+                 strict_reference_types=True, composite_groups_on_device=False):
         self.columns = [columns] if isinstance(columns, str) else list(columns)
         self.max_groups, self.include_overall = max_groups, include_overall
         self.overflow_strategy, self.strict_reference_types = overflow_strategy, strict_reference_types
+        self.composite_on_device = bool(composite_groups_on_device)
+
+    def composite_groups_on_device(self, on=True):
+        self.composite_on_device = bool(on)
+        return self
 
     def with_max_groups(self, n):
         self.max_groups = int(n)
@@ -1439,6 +1457,9 @@ class AnalysisRunner:
                  else dict(a.spec, group_arrow_type=declared[a.spec["group_by"][0]])
                  if a.spec["type"] == "grouped_completeness" and len(a.spec["group_by"]) == 1 and
                  a.spec["group_by"][0] in declared and "group_arrow_type" not in a.spec
+                 else dict(a.spec, group_arrow_types=[declared.get(g, "") for g in a.spec["group_by"]])
+                 if a.spec["type"] == "grouped_completeness" and len(a.spec["group_by"]) > 1 and
+                 "group_arrow_types" not in a.spec
                  else a.spec for a in self._analyzers]
         spec = {"table_name": self._table, "continue_on_error": self._continue, "analyzers": specs}
         name_arr, n_cols, col_arr, n_batches, _keep = _flatten_table(table)

@@ -281,18 +281,19 @@ def pair_counts_state(max_pairs, max_value_bytes, x_side, y_side, seen, counts=(
 
 
 def group_counts_state(max_groups, max_value_bytes, groups, seen=None, null_group=(0, 0), overflow=(0, 0), long=(0, 0),
-                       ordered=True):
+                       ordered=True, arity=0):
     """a GROUP_COUNTS task: the plan's parameters, the counters and the entries of `groups` (key -> (total, non_null);
     every key an int, or every key bytes).  null_group / overflow / long: (rows, non-NULL values among them).  seen
     defaults to what the invariant makes it.  `ordered=False` keeps the entries in the order given (for a blob that is to
-    be refused)."""
+    be refused).  arity: 2 .. 8 for a task that groups by a tuple of columns, whose keys are term_amd.group_key's encoded
+    tuples; 0 for a task with one group column."""
     items = list(groups.items()) if hasattr(groups, "items") else list(groups)
     is_bytes = bool(items) and isinstance(items[0][0], (bytes, bytearray))
     if ordered:
         items.sort(key=lambda kv: kv[0])
     if seen is None:
         seen = sum(t for _, (t, _n) in items) + null_group[0] + overflow[0] + long[0]
-    out = struct.pack("<4I8Q", max_groups, max_value_bytes, (2 if is_bytes else 1) if items else 0, 0, seen, *null_group,
+    out = struct.pack("<4I8Q", max_groups, max_value_bytes, (2 if is_bytes else 1) if items else 0, arity, seen, *null_group,
                       *overflow, *long, len(items))
     for k, (t, n) in items:
         out += (struct.pack("<I", len(k)) + bytes(k) if is_bytes else struct.pack("<q", k)) + struct.pack("<QQ", t, n)
@@ -300,12 +301,13 @@ def group_counts_state(max_groups, max_value_bytes, groups, seen=None, null_grou
 
 
 def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=None, null_group=(0, 0, 0),
-                     overflow=(0, 0, 0), long=(0, 0, 0), ordered=True, values=None):
+                     overflow=(0, 0, 0), long=(0, 0, 0), ordered=True, values=None, arity=0):
     """a GROUP_SUMS task: the plan's parameters, the classes and the entries of `groups` (key -> (rows, non_null, sum);
     every key an int, or every key bytes).  null_group / overflow / long: (rows, non-NULL values among them, their sum).
     A sum is an int (taken modulo 2^64) or, with is_float, a float.  seen defaults to what the invariant makes it, values
     (the blob's value kind) to what is_float says, 0 for a state without rows.  `ordered=False` keeps the entries in the
-    order given (for a blob that is to be refused)."""
+    order given (for a blob that is to be refused).  arity: as in group_counts_state; it rides the upper half of the key
+    kind word."""
     items = list(groups.items()) if hasattr(groups, "items") else list(groups)
     is_bytes = bool(items) and isinstance(items[0][0], (bytes, bytearray))
     if ordered:
@@ -318,7 +320,8 @@ def group_sums_state(max_groups, max_value_bytes, groups, is_float=False, seen=N
     def cls(c):
         return struct.pack("<QQ", c[0], c[1]) + (struct.pack("<d", c[2]) if is_float else
                                                   struct.pack("<Q", c[2] & ((1 << 64) - 1)))
-    out = struct.pack("<4IQ", max_groups, max_value_bytes, (2 if is_bytes else 1) if items else 0, values, seen)
+    out = struct.pack("<4IQ", max_groups, max_value_bytes, ((2 if is_bytes else 1) if items else 0) | arity << 16, values,
+                      seen)
     out += cls(null_group) + cls(overflow) + cls(long) + struct.pack("<Q", len(items))
     for k, v in items:
         out += (struct.pack("<I", len(k)) + bytes(k) if is_bytes else struct.pack("<q", k)) + cls(v)
