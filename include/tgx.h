@@ -729,6 +729,22 @@ tgx_status tgx_plan_set_value_rule(tgx_plan *plan, size_t spec_index, const tgx_
  *                         TGX_PRED_EQ only, by bytes.
  *   TGX_PRED_STR_EQ       col = the literal bytes [lit_offset, lit_offset + lit_len) of the pool, by bytes; the empty
  *                         string is a value.  UNKNOWN when col is NULL.
+ * Four more kinds read a string value's bytes; each is UNKNOWN when col is NULL.  KIND 5 IS UNASSIGNED and stays an
+ * unknown leaf kind.  A byte of the form 10xxxxxx is called a continuation byte below; nothing asks the value or the
+ * literal to be UTF-8.
+ *   TGX_PRED_STR_CMP      col <op> the literal bytes, op one of TGX_PRED_LT / LE / GT / GE (TGX_PRED_EQ is refused: use
+ *                         STR_EQ, so that a predicate has one spelling).  Bytewise lexicographic: the first differing
+ *                         byte decides, as unsigned; a proper prefix is smaller.  (What arrow-ord does on Utf8.)
+ *   TGX_PRED_STR_LENGTH   len(col) <op> lit_i as int64, any of the five ops.  len is the number of bytes that are no
+ *                         continuation bytes -- on valid UTF-8 the code points, DataFusion's LENGTH = character_length
+ *                         -- or, under the flag TGX_PRED_LENGTH_IN_BYTES, the number of bytes (OCTET_LENGTH).
+ *   TGX_PRED_STR_LIKE     col LIKE the pattern bytes [lit_offset, lit_offset + lit_len) of the pool.  `%` matches any
+ *                         run of bytes, the empty one included.  `_` matches exactly one unit: one byte that is no
+ *                         continuation byte plus all continuation bytes directly after it; at offset 0 the first byte
+ *                         opens a unit whatever it is.  Every other byte matches itself.  The match is anchored at both
+ *                         ends and case-sensitive; `_` and `%` match a line feed.  The empty pattern matches the empty
+ *                         string only.  There is no escape: a pattern that holds the byte 0x5C is refused.
+ *   TGX_PRED_STR_BLANK    TRUE iff every byte of the value is 0x20, the empty string included: TRIM(col) = ''.
  * A leaf that does not fit the type its column arrives in -- a string leaf on a numeric column, a numeric leaf on a
  * string column, a string column against a numeric one, UInt64 / Boolean / validity-only columns under anything but
  * IS_NULL -- makes tgx_update fail with TGX_UNSUPPORTED; the batch is not counted and the state stays usable.
@@ -741,23 +757,27 @@ tgx_status tgx_plan_set_value_rule(tgx_plan *plan, size_t spec_index, const tgx_
  *
  * The setter refuses with TGX_INVALID_ARGUMENT: counts out of range, an unknown leaf kind / comparison / flag / op, a
  * column position outside the spec's list, a literal range outside the pool, a PUSH of a leaf that does not exist,
- * underflow, a depth above 32, and a program that leaves more or fewer than one value.  What a leaf does not read is
- * kept as zero bits (the blob compares the predicate byte by byte). */
+ * underflow, a depth above 32, and a program that leaves more or fewer than one value; of the kinds 6 .. 9 also a
+ * comparison outside the kind's ops (STR_CMP: LT .. GE; STR_LENGTH: EQ .. GE), a flag other than
+ * TGX_PRED_LENGTH_IN_BYTES on STR_LENGTH and any flag on the other three, and a 0x5C in a LIKE pattern.  What a leaf
+ * does not read is kept as zero bits (the blob compares the predicate byte by byte). */
 enum { TGX_PRED_MAX_COLUMNS = 8, TGX_PRED_MAX_LEAVES = 32, TGX_PRED_MAX_OPS = 64, TGX_PRED_MAX_DEPTH = 32,
        TGX_PRED_MAX_LITERAL_BYTES = 256 };
-enum { TGX_PRED_IS_NULL = 1, TGX_PRED_CMP_LITERAL = 2, TGX_PRED_CMP_COLUMNS = 3, TGX_PRED_STR_EQ = 4 };
+enum { TGX_PRED_IS_NULL = 1, TGX_PRED_CMP_LITERAL = 2, TGX_PRED_CMP_COLUMNS = 3, TGX_PRED_STR_EQ = 4,
+       /* 5: unassigned */
+       TGX_PRED_STR_CMP = 6, TGX_PRED_STR_LENGTH = 7, TGX_PRED_STR_LIKE = 8, TGX_PRED_STR_BLANK = 9 };
 enum { TGX_PRED_EQ = 1, TGX_PRED_LT = 2, TGX_PRED_LE = 3, TGX_PRED_GT = 4, TGX_PRED_GE = 5 };
-enum { TGX_PRED_LITERAL_IS_DOUBLE = 1u << 0 };
+enum { TGX_PRED_LITERAL_IS_DOUBLE = 1u << 0, TGX_PRED_LENGTH_IN_BYTES = 1u << 1 };
 enum { TGX_PRED_PUSH = 1, TGX_PRED_AND = 2, TGX_PRED_OR = 3, TGX_PRED_NOT = 4 };
 typedef struct tgx_row_predicate_leaf {
-  int32_t kind;        /* TGX_PRED_IS_NULL .. TGX_PRED_STR_EQ */
-  int32_t op;          /* CMP_LITERAL / CMP_COLUMNS: TGX_PRED_EQ .. TGX_PRED_GE; otherwise 0 */
+  int32_t kind;        /* TGX_PRED_IS_NULL .. TGX_PRED_STR_BLANK */
+  int32_t op;          /* CMP_LITERAL / CMP_COLUMNS / STR_CMP / STR_LENGTH: TGX_PRED_EQ .. TGX_PRED_GE; otherwise 0 */
   int32_t col, col2;   /* positions in the spec's column list; col2: CMP_COLUMNS only, otherwise 0 */
-  uint32_t flags;      /* CMP_LITERAL: TGX_PRED_LITERAL_IS_DOUBLE */
-  uint32_t lit_offset; /* STR_EQ: the literal's bytes in the pool */
+  uint32_t flags;      /* CMP_LITERAL: TGX_PRED_LITERAL_IS_DOUBLE; STR_LENGTH: TGX_PRED_LENGTH_IN_BYTES */
+  uint32_t lit_offset; /* STR_EQ / STR_CMP / STR_LIKE: the literal's bytes in the pool */
   uint32_t lit_len;
   uint32_t reserved;   /* 0 */
-  int64_t lit_i;       /* CMP_LITERAL */
+  int64_t lit_i;       /* CMP_LITERAL; STR_LENGTH: the length compared with */
   double lit_f;
 } tgx_row_predicate_leaf;
 typedef struct tgx_row_predicate_params {

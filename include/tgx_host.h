@@ -83,6 +83,20 @@ tgx_status tgx_host_value_rule_params_json(const char *constraint_json, char **o
  * "literals_hex": the literal pool}.  An expression outside the subset is TGX_UNSUPPORTED with
  * "the expression is not on the GPU path: <the first thing outside the subset>".  Needs no device. */
 tgx_status tgx_host_row_predicate_json(const char *expression, char **out_json, tgx_error *err);
+/* The same under options: options_json is NULL or {"string_functions": true|false (default false)} -- the compiler's
+ * dialect of that name (LIKE, LENGTH / CHAR_LENGTH / CHARACTER_LENGTH / OCTET_LENGTH, TRIM(c) = '', string order; the
+ * leaves TGX_PRED_STR_CMP .. TGX_PRED_STR_BLANK).  Without the option the answer is tgx_host_row_predicate_json's. */
+tgx_status tgx_host_row_predicate_json_ex(const char *expression, const char *options_json, char **out_json,
+                                          tgx_error *err);
+
+/* One string leaf of TGX_CHECK_ROW_PREDICATE (kind TGX_PRED_STR_CMP .. TGX_PRED_STR_BLANK; op, flags, lit_i as in
+ * tgx_row_predicate_leaf; `pattern`: the literal of STR_CMP / the pattern of STR_LIKE) on ONE non-NULL value, through the
+ * functions the kernel compiles (kernels/string_leaf.h): *out = 1 for TRUE, 0 for FALSE.  The value is read in aligned
+ * words as the kernel reads it, `value`'s own address giving the alignment.  What tgx_plan_set_row_predicate refuses of
+ * a leaf (another kind, a comparison outside the kind's ops, a flag, a 0x5C in a pattern) is TGX_INVALID_ARGUMENT.
+ * Needs no device. */
+tgx_status tgx_host_string_leaf(int32_t kind, int32_t op, uint32_t flags, int64_t lit_i, const uint8_t *pattern,
+                                uint32_t pattern_len, const uint8_t *value, uint64_t value_len, int *out);
 
 /* `Constraint::evaluate`'s verdict half on given aggregates: results_json is an array of objects with
  * tgx_result's field names (answering the plan in order; a KLL entry may carry {"quantiles": {"0.5": v}}, a

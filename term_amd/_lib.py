@@ -33,8 +33,10 @@ KEY_PROBE_MAX_VALUE_BYTES = 256  # of a missing key a spec on string keys keeps 
 ROW_PREDICATE = 20  # the rows on which a closed boolean predicate over 1 .. 8 columns is TRUE / UNKNOWN (Plan.set_row_predicate)
 PRED_MAX_COLUMNS, PRED_MAX_LEAVES, PRED_MAX_OPS, PRED_MAX_DEPTH, PRED_MAX_LITERAL_BYTES = 8, 32, 64, 32, 256
 PRED_IS_NULL, PRED_CMP_LITERAL, PRED_CMP_COLUMNS, PRED_STR_EQ = 1, 2, 3, 4
+PRED_STR_CMP, PRED_STR_LENGTH, PRED_STR_LIKE, PRED_STR_BLANK = 6, 7, 8, 9  # (5 is no kind)
 PRED_EQ, PRED_LT, PRED_LE, PRED_GT, PRED_GE = 1, 2, 3, 4, 5
 PRED_LITERAL_IS_DOUBLE = 1
+PRED_LENGTH_IN_BYTES = 2
 PRED_PUSH, PRED_AND, PRED_OR, PRED_NOT = 1, 2, 3, 4
 TYPE_CLASSES = 21  # the syntactic class of every non-NULL value of a string column (State.type_classes)
 # the classes in the order they are tried (TGX_TYPE_CLASS_*: what host_type_class answers)
@@ -433,6 +435,8 @@ def lib():
         L.tgx_type_classes_get.argtypes = [vp, vp, sz, C.POINTER(TypeClassesCounts), E]
         L.tgx_host_type_class.argtypes = [C.c_char_p, u64]
         L.tgx_host_type_class.restype = C.c_int32
+        L.tgx_host_string_leaf.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           u64, C.POINTER(C.c_int)]
         L.tgx_plan_set_value_counts.argtypes = [vp, sz, C.POINTER(ValueCountsParams), E]
         L.tgx_value_counts_get.argtypes = [vp, vp, sz, C.POINTER(ValueCountsSummary), E]
         L.tgx_value_counts_entries.argtypes = [vp, vp, sz, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64),
@@ -523,6 +527,24 @@ def host_type_class(value):
     str taken as UTF-8) -- the function the kernels compile, run on the host; needs no device"""
     b = value.encode("utf-8") if isinstance(value, str) else bytes(value)
     return lib().tgx_host_type_class(b, len(b))
+
+
+def host_string_leaf(kind, value, op=0, flags=0, lit_i=0, pattern=b"", align=0):
+    """tgx_host_string_leaf: one string leaf of ROW_PREDICATE (PRED_STR_CMP .. PRED_STR_BLANK) on one non-NULL value
+    (bytes, or a str taken as UTF-8), through the functions the kernel compiles, run on the host: True or False.
+    `pattern`: STR_CMP's literal / STR_LIKE's pattern; `align` (0 .. 3): where the value's first byte lies in its 32-bit
+    word.  TgxError (TGX_INVALID_ARGUMENT) for a leaf the setter refuses.  Needs no device"""
+    v = value.encode("utf-8") if isinstance(value, str) else bytes(value)
+    pat = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+    raw = C.create_string_buffer(len(v) + 8)
+    base = C.addressof(raw)
+    at = base + ((align - base) & 3)
+    C.memmove(at, v, len(v))
+    out = C.c_int(0)
+    rc = lib().tgx_host_string_leaf(kind, op, flags, lit_i, pat, len(pat), at, len(v), C.byref(out))
+    if rc != 0:
+        raise TgxError(rc, "tgx_host_string_leaf refuses the leaf (kind %d, op %d, flags 0x%x)" % (kind, op, flags))
+    return bool(out.value)
 
 
 def _ptr_of(buf):

@@ -170,13 +170,17 @@ class SizeAnalyzer : public Analyzer {  // basic/size.rs
 // as one TGX_CHECK_ROW_PREDICATE request; the predicate is compiled by host/custom_sql.h's closed subset
 class ComplianceAnalyzer : public Analyzer {
  public:
-  ComplianceAnalyzer(std::string name, std::string predicate) : name_(std::move(name)), predicate_(std::move(predicate)) {}
+  // string_functions: the opt-in "string_functions_on_device" (host/custom_sql.h's dialect of that name)
+  ComplianceAnalyzer(std::string name, std::string predicate, bool string_functions = false)
+      : name_(std::move(name)), predicate_(std::move(predicate)) {
+    dialect_.string_functions = string_functions;
+  }
   std::string name() const override { return "compliance"; }  // (metric_key: the trait's default, the name)
   const std::string &check_name() const { return name_; }
   const std::string &predicate() const { return predicate_; }
   std::vector<std::string> columns() const override {
     try {
-      return compile_row_predicate(predicate_).columns;
+      return compile_row_predicate(predicate_, dialect_).columns;
     } catch (const PredicateRefusal &) {
       return {};
     }
@@ -186,7 +190,7 @@ class ComplianceAnalyzer : public Analyzer {
     if (auto word = compliance_forbidden_keyword(predicate_))
       throw AnalyzerError::custom("Invalid configuration: Predicate contains forbidden keyword: " + *word);
     try {
-      return {row_predicate_request(compile_row_predicate(predicate_))};
+      return {row_predicate_request(compile_row_predicate(predicate_, dialect_))};
     } catch (const PredicateRefusal &r) {
       throw AnalyzerError::custom("Invalid configuration: Invalid predicate '" + predicate_ +
                                   "': not on the GPU path: " + r.what);
@@ -210,6 +214,7 @@ class ComplianceAnalyzer : public Analyzer {
 
  private:
   std::string name_, predicate_;
+  PredicateDialect dialect_;
 };
 
 class ColumnAnalyzer : public Analyzer {
@@ -1655,7 +1660,9 @@ std::shared_ptr<Analyzer> analyzer_from_json(const json::Value &v) {
     return completeness_with_grouping(col(), cfg, v.get_bool("strict_reference_types", true), v.get_str("group_arrow_type"),
                                       group_arrow_types);
   }
-  if (t == "compliance") return std::make_shared<ComplianceAnalyzer>(v.get_str("name"), v.get_str("predicate"));
+  if (t == "compliance")
+    return std::make_shared<ComplianceAnalyzer>(v.get_str("name"), v.get_str("predicate"),
+                                                v.get("string_functions_on_device") && v.get_bool("string_functions_on_device"));
   if (t == "data_type") return std::make_shared<DataTypeAnalyzer>(col(), v.get_str("arrow_type"));
   // ("entropy" stays an unknown type: the tag of EntropyAnalyzer is "value_entropy")
   if (t == "value_entropy")

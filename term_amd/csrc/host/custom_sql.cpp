@@ -103,8 +103,9 @@ struct Lexer {
 
 // ---- the parser: straight into leaves and postfix ops ------------------------------------------------------------------
 struct Operand {
-  enum Kind { Column, Number, Text } kind = Column;
+  enum Kind { Column, Number, Text, Length, Trim } kind = Column;  // Length / Trim: lenfn(col) / TRIM(col)
   int col = 0;
+  bool in_bytes = false;  // Length: OCTET_LENGTH
   bool is_double = false;
   int64_t i = 0;
   double f = 0;
@@ -115,9 +116,10 @@ struct Compiler {
   Lexer lex;
   Token tok;
   RowPredicate out;
+  PredicateDialect dialect;
   int depth = 0, max_depth = 0, nesting = 0;
 
-  explicit Compiler(const std::string &s) : lex(s) {
+  Compiler(const std::string &s, const PredicateDialect &d) : lex(s), dialect(d) {
     memset(&out.params, 0, sizeof(out.params));
     advance();
   }
@@ -178,8 +180,10 @@ struct Compiler {
   // col <op> literal, op one of TGX_PRED_EQ .. TGX_PRED_GE, onto the stack
   void compare_literal(int col, int op, const Operand &lit) {
     if (lit.kind == Operand::Text) {
-      if (op != TGX_PRED_EQ) refuse("a string order comparison (only = and <> compare strings)");
-      tgx_row_predicate_leaf l = blank(TGX_PRED_STR_EQ, col);
+      if (op != TGX_PRED_EQ && !dialect.string_functions)
+        refuse("a string order comparison (only = and <> compare strings)");
+      tgx_row_predicate_leaf l = blank(op == TGX_PRED_EQ ? TGX_PRED_STR_EQ : TGX_PRED_STR_CMP, col);
+      if (op != TGX_PRED_EQ) l.op = op;
       l.lit_len = (uint32_t)lit.text.size();
       l.lit_offset = pool(lit.text);
       push_leaf(l);
@@ -243,6 +247,27 @@ struct Compiler {
       for (char ch : tok.text) name += (char)tolower((unsigned char)ch);
       const std::string written = tok.text, upper = tok.upper;
       advance();
+      if (symbol("(") && dialect.string_functions) {
+        if (upper == "LTRIM" || upper == "RTRIM" || upper == "BTRIM") refuse(upper + " (only TRIM(col) = '' is taken)");
+        const bool chars = upper == "LENGTH" || upper == "CHAR_LENGTH" || upper == "CHARACTER_LENGTH";
+        if (chars || upper == "OCTET_LENGTH" || upper == "TRIM") {
+          advance();
+          if (upper == "TRIM" && (keyword("BOTH") || keyword("LEADING") || keyword("TRAILING"))) refuse("TRIM(.. FROM ..)");
+          if (++nesting > 64) refuse("nesting deeper than 64");
+          const Operand arg = operand();
+          nesting--;
+          if (upper == "TRIM" && keyword("FROM")) refuse("TRIM(.. FROM ..)");
+          if (arg.kind == Operand::Length || arg.kind == Operand::Trim) refuse("a nested function call (" + upper + "(..(..)))");
+          if (arg.kind != Operand::Column) refuse(upper + " of a literal");
+          if (symbol(",")) refuse("a function call with several arguments (" + upper + "(.., ..))");
+          if (!symbol(")")) refuse(here() + " where " + upper + "'s ')' should stand");
+          advance();
+          o.kind = upper == "TRIM" ? Operand::Trim : Operand::Length;
+          o.col = arg.col;
+          o.in_bytes = upper == "OCTET_LENGTH";
+          return after_operand(o);
+        }
+      }
       if (symbol("(")) refuse("a function call (" + shown(written) + "(..))");
       for (const char *k : refused)
         if (upper == k) refuse(upper == "NULL" ? std::string("a NULL literal") : upper);
@@ -253,6 +278,10 @@ struct Compiler {
     } else {
       refuse(here() + " where a column or a literal should stand");
     }
+    return after_operand(o);
+  }
+
+  Operand after_operand(const Operand &o) {
     // what may follow an operand is a comparison, a keyword, ')' or ',': an operator is arithmetic
     if (tok.kind == Token::Symbol) {
       static const char *const arithmetic[] = {"+", "-", "*", "/", "%", "||"};
@@ -265,6 +294,7 @@ struct Compiler {
 
   Operand literal() {
     Operand o = operand();
+    if (o.kind == Operand::Length || o.kind == Operand::Trim) refuse("a function call where a literal should stand");
     if (o.kind == Operand::Column) refuse("a column where a literal should stand (" + shown(out.columns[o.col]) + ")");
     return o;
   }
@@ -285,8 +315,80 @@ struct Compiler {
   }
 
   // -- the grammar
+  // -- the atoms of the dialect string_functions
+  // lenfn(col) <op> literal, op one of TGX_PRED_EQ .. TGX_PRED_GE, onto the stack
+  void compare_length(const Operand &call, int op, const Operand &lit) {
+    if (lit.kind == Operand::Column) refuse("a length compared with a column");
+    if (lit.kind == Operand::Length || lit.kind == Operand::Trim) refuse("a length compared with a function call");
+    if (lit.kind == Operand::Text) refuse("a length compared with a string literal");
+    if (lit.is_double) refuse("a length compared with a float literal");
+    tgx_row_predicate_leaf l = blank(TGX_PRED_STR_LENGTH, call.col);
+    l.op = op;
+    l.flags = call.in_bytes ? TGX_PRED_LENGTH_IN_BYTES : 0;
+    l.lit_i = lit.i;
+    push_leaf(l);
+  }
+  // TRIM(col) = / <> / != '': `op` as comparison() gives it
+  void compare_trim(const Operand &call, int op, const Operand &lit) {
+    if (op != TGX_PRED_EQ && op != 6) refuse("TRIM(col) under an order comparison (only = '' and <> '')");
+    if (lit.kind != Operand::Text || !lit.text.empty()) refuse("TRIM(col) compared with anything but ''");
+    push_leaf(blank(TGX_PRED_STR_BLANK, call.col));
+    if (op == 6) emit(TGX_PRED_NOT);
+  }
+  // what follows lenfn(col) / TRIM(col)
+  void call_atom(const Operand &a) {
+    const std::string what = a.kind == Operand::Trim ? "TRIM(col)" : "a length";
+    bool negated = false;
+    if (keyword("IS")) refuse("IS [NOT] NULL of a function call");
+    if (keyword("NOT")) {
+      negated = true;
+      advance();
+      if (keyword("IN")) refuse("IN on " + what);
+      if (!keyword("BETWEEN") || a.kind == Operand::Trim) refuse("NOT " + here() + " after " + what);
+    }
+    if (keyword("IN")) refuse("IN on " + what);
+    if (keyword("LIKE") || keyword("ILIKE") || keyword("SIMILAR")) refuse(tok.upper + " on " + what);
+    if (keyword("BETWEEN")) {
+      if (a.kind == Operand::Trim) refuse("TRIM(col) compared with anything but ''");
+      advance();
+      const Operand lo = literal();
+      if (!keyword("AND")) refuse(here() + " where BETWEEN's AND should stand");
+      advance();
+      const Operand hi = literal();
+      compare_length(a, TGX_PRED_GE, lo);
+      compare_length(a, TGX_PRED_LE, hi);
+      emit(TGX_PRED_AND);
+      if (negated) emit(TGX_PRED_NOT);
+      return;
+    }
+    const int op = comparison(tok);
+    if (!op) refuse(here() + " where a comparison should stand");
+    advance();
+    const Operand b = operand();
+    if (a.kind == Operand::Trim) return compare_trim(a, op, b);
+    compare_length(a, op == 6 ? TGX_PRED_EQ : op, b);
+    if (op == 6) emit(TGX_PRED_NOT);
+  }
+  // col [NOT] LIKE 'pattern'; the token is LIKE
+  void like_atom(const Operand &a, bool negated) {
+    if (a.kind != Operand::Column) refuse("LIKE of a literal");
+    advance();
+    if (tok.kind != Token::String) refuse(here() + " where LIKE's pattern should stand (a string literal)");
+    const std::string pattern = tok.text;
+    advance();
+    if (keyword("ESCAPE")) refuse("an ESCAPE clause");
+    if (pattern.find('\\') != std::string::npos) refuse("a LIKE pattern with a backslash");
+    if (tok.kind == Token::Symbol && tok.text == "||") refuse("arithmetic ('||')");
+    tgx_row_predicate_leaf l = blank(TGX_PRED_STR_LIKE, a.col);
+    l.lit_len = (uint32_t)pattern.size();
+    l.lit_offset = pool(pattern);
+    push_leaf(l);
+    if (negated) emit(TGX_PRED_NOT);
+  }
+
   void atom() {
     const Operand a = operand();
+    if (a.kind == Operand::Length || a.kind == Operand::Trim) return call_atom(a);
     bool negated = false;
     if (keyword("IS")) {
       if (a.kind != Operand::Column) refuse("IS [NOT] NULL of a literal");
@@ -304,7 +406,7 @@ struct Compiler {
     if (keyword("NOT")) {
       negated = true;
       advance();
-      if (!keyword("BETWEEN") && !keyword("IN"))
+      if (!keyword("BETWEEN") && !keyword("IN") && !(dialect.string_functions && keyword("LIKE")))
         refuse(keyword("LIKE") || keyword("ILIKE") ? tok.upper : "NOT " + here() + " (only NOT BETWEEN and NOT IN)");
     }
     if (keyword("BETWEEN")) {
@@ -314,8 +416,9 @@ struct Compiler {
       if (!keyword("AND")) refuse(here() + " where BETWEEN's AND should stand");
       advance();
       const Operand hi = literal();
-      if (lo.kind == Operand::Text || hi.kind == Operand::Text)
+      if ((lo.kind == Operand::Text || hi.kind == Operand::Text) && !dialect.string_functions)
         refuse("a string order comparison (BETWEEN on a string literal)");
+      if (lo.kind != hi.kind) refuse("a BETWEEN that mixes strings and numbers");
       compare_literal(a.col, TGX_PRED_GE, lo);
       compare_literal(a.col, TGX_PRED_LE, hi);
       emit(TGX_PRED_AND);
@@ -347,11 +450,18 @@ struct Compiler {
       if (negated) emit(TGX_PRED_NOT);
       return;
     }
+    if (dialect.string_functions && keyword("LIKE")) return like_atom(a, negated);
     if (keyword("LIKE") || keyword("ILIKE") || keyword("SIMILAR")) refuse(tok.upper);
     const int op = comparison(tok);
     if (!op) refuse(here() + " where a comparison should stand");
     advance();
     const Operand b = operand();
+    if (b.kind == Operand::Length || b.kind == Operand::Trim) {  // lit op call: turned round
+      if (b.kind == Operand::Trim) return compare_trim(b, op, a);
+      compare_length(b, op == 6 ? TGX_PRED_EQ : turned(op), a);
+      if (op == 6) emit(TGX_PRED_NOT);
+      return;
+    }
     const int plain = op == 6 ? TGX_PRED_EQ : op;
     if (a.kind != Operand::Column && b.kind != Operand::Column) refuse("a comparison of two literals");
     if (a.kind == Operand::Column && b.kind == Operand::Column) {
@@ -430,8 +540,8 @@ std::string json_f64(double v) {
 
 }  // namespace
 
-RowPredicate compile_row_predicate(const std::string &expression) {
-  Compiler c(expression);
+RowPredicate compile_row_predicate(const std::string &expression, const PredicateDialect &dialect) {
+  Compiler c(expression, dialect);
   c.pred();
   if (c.tok.kind != Token::End) refuse(c.here() + " after the end of the predicate");
   return std::move(c.out);
@@ -507,7 +617,7 @@ CustomSqlConstraint::CustomSqlConstraint(std::string expression, std::optional<s
 
 std::vector<SpecRequest> CustomSqlConstraint::plan() const {
   try {
-    return {row_predicate_request(compile_row_predicate(expression_))};
+    return {row_predicate_request(compile_row_predicate(expression_, dialect()))};
   } catch (const PredicateRefusal &r) {
     throw TermError{TermError::ConstraintEvaluation,
                     "'custom_sql': the expression is not on the GPU path: " + r.what + ". Expression: '" + expression_ + "'"};
@@ -528,7 +638,7 @@ ConstraintResult CustomSqlConstraint::evaluate(const Inputs &in) const {
   if (!in.list_arrow_types.empty()) {
     RowPredicate p;
     try {
-      p = compile_row_predicate(expression_);
+      p = compile_row_predicate(expression_, dialect());
     } catch (const PredicateRefusal &) {
       return plan(), ConstraintResult::success();  // (plan() throws the refusal)
     }
@@ -563,8 +673,11 @@ std::vector<std::pair<std::string, std::string>> CustomSqlConstraint::metadata()
   return m;
 }
 
-Check::Builder &Check::Builder::satisfies(std::string sql_expression, std::optional<std::string> hint) {
-  return constraint(std::make_shared<CustomSqlConstraint>(std::move(sql_expression), std::move(hint)));
+Check::Builder &Check::Builder::satisfies(std::string sql_expression, std::optional<std::string> hint,
+                                          bool string_functions_on_device) {
+  auto c = std::make_shared<CustomSqlConstraint>(std::move(sql_expression), std::move(hint));
+  c->string_functions_on_device(string_functions_on_device);
+  return constraint(std::move(c));
 }
 #endif  // TGX_PREDICATE_COMPILER_ONLY
 

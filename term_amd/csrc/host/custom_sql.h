@@ -17,6 +17,18 @@
 // include/tgx.h.  Everything else -- arithmetic, function calls, LIKE, CASE, casts, TRUE / FALSE, string order
 // comparisons, literal-against-literal comparisons, IN lists that mix strings and numbers, more than 8 columns, 32
 // leaves, 64 ops or 256 literal bytes -- is refused with a message that names the first thing outside the subset.
+//
+// The dialect `string_functions` (an opt-in; without it the above is all there is, byte for byte) adds the atoms
+//     col [NOT] LIKE 'pattern'                                 STR_LIKE, under NOT where written
+//     lenfn '(' col ')' cmp int | lenfn '(' col ')' [NOT] BETWEEN int AND int
+//                                                              STR_LENGTH; lenfn := LENGTH | CHAR_LENGTH |
+//                                                              CHARACTER_LENGTH (characters) | OCTET_LENGTH (bytes)
+//     TRIM '(' col ')' (= | <> | !=) ''                        STR_BLANK, under NOT for the two inequalities
+//     col (< | <= | > | >=) 'lit' | col [NOT] BETWEEN 'a' AND 'b'     STR_CMP
+// lowered as above (`lit op call` is turned round too).  It is a superset: what the base dialect accepts compiles to the
+// identical leaves, program and pool.  Refused by name: ILIKE, SIMILAR TO, an ESCAPE clause, a pattern with a backslash;
+// a length against a float literal, a string, a column or another call, a nested call, IN on a length; TRIM against
+// any literal but '', LTRIM / RTRIM / BTRIM, TRIM(.. FROM ..); every other function.
 #pragma once
 #include <optional>
 #include <string>
@@ -37,7 +49,11 @@ struct RowPredicate {
   // per column: a CMP_LITERAL leaf reads it (what a declared temporal / decimal / boolean / binary type refuses)
   std::vector<char> literal_compared;
 };
-RowPredicate compile_row_predicate(const std::string &expression);  // throws PredicateRefusal
+struct PredicateDialect {
+  bool string_functions = false;
+};
+// throws PredicateRefusal
+RowPredicate compile_row_predicate(const std::string &expression, const PredicateDialect &dialect = PredicateDialect());
 std::string row_predicate_json(const RowPredicate &p);
 // the request of a compiled predicate: kind TGX_CHECK_ROW_PREDICATE, `columns`, `row_predicate`
 SpecRequest row_predicate_request(const RowPredicate &p);
@@ -57,6 +73,10 @@ class CustomSqlConstraint : public Constraint {
   }
   const std::string &expression() const { return expression_; }
   const std::optional<std::string> &hint() const { return hint_; }
+  // an opt-in: the expression is compiled under the dialect `string_functions` (LIKE, LENGTH, TRIM(c) = '', string
+  // order).  Without it such an expression is what it was: "not on the GPU path"
+  CustomSqlConstraint &string_functions_on_device(bool on) { string_functions_ = on; return *this; }
+  bool string_functions() const { return string_functions_; }
 
   std::string name() const override { return "custom_sql"; }
   // throws TermError ("... not on the GPU path: <what>") for an expression outside the subset
@@ -70,6 +90,12 @@ class CustomSqlConstraint : public Constraint {
  private:
   std::string expression_;
   std::optional<std::string> hint_;
+  bool string_functions_ = false;
+  PredicateDialect dialect() const {
+    PredicateDialect d;
+    d.string_functions = string_functions_;
+    return d;
+  }
 };
 
 }  // namespace term_guard

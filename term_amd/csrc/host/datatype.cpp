@@ -1,6 +1,8 @@
 // datatype.cpp -- DataTypeConstraint (TG/constraints/datatype.rs), placeholders included.
 #include "datatype.h"
 
+#include "custom_sql.h"
+
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -118,6 +120,32 @@ std::string DataTypeConstraint::description() const {
   return "Validates " + validation_.description() + " for column '" + column_ + "'";
 }
 
+// ---- datatype.rs:161-175
+std::string DataTypeConstraint::string_predicate() const {
+  std::string col = "\"";
+  for (char ch : column_) col += ch == '"' ? std::string("\"\"") : std::string(1, ch);
+  col += "\"";
+  switch (validation_.string.kind) {
+    case StringTypeValidation::NotEmpty: return "LENGTH(" + col + ") > 0";
+    case StringTypeValidation::ValidUtf8: return col + " IS NOT NULL";
+    case StringTypeValidation::NotBlank: return "TRIM(" + col + ") != ''";
+    case StringTypeValidation::MaxBytes: return "OCTET_LENGTH(" + col + ") <= " + std::to_string(validation_.string.max_bytes);
+  }
+  return std::string();
+}
+
+namespace {
+
+// the verdict of the validations that count (:406-438): `valid` of `considered` rows
+ConstraintResult rate_verdict(double valid, double considered, const std::string &description) {
+  const double rate = valid / considered;  // (0 / 0: NaN, a Failure)
+  const std::string msg = pct1(rate * 100.0) + "% of values satisfy " + description;
+  if (rate >= 1.0) return {ConstraintStatus::Success, rate, msg};
+  return ConstraintResult::failure_with_metric(rate, msg);
+}
+
+}  // namespace
+
 tgx_value_rule_params value_rule_params(const NumericValidation &v) {
   tgx_value_rule_params p;
   memset(&p, 0, sizeof(p));
@@ -160,7 +188,17 @@ std::vector<SpecRequest> DataTypeConstraint::plan() const {
       r.value_rule = value_rule_params(validation_.numeric);
       break;
     case DataTypeValidation::String:
-      evaluation_error(validation_.description() + " validation reads a string column (not on the GPU path)");
+      if (!string_functions_)
+        evaluation_error(validation_.description() + " validation reads a string column (not on the GPU path)");
+      if (validation_.string.max_bytes > (uint64_t)INT64_MAX)
+        evaluation_error("a byte limit beyond int64 is no SQL integer literal (not on the GPU path)");
+      try {
+        PredicateDialect dialect;
+        dialect.string_functions = true;
+        return {row_predicate_request(compile_row_predicate(string_predicate(), dialect))};
+      } catch (const PredicateRefusal &refusal) {
+        evaluation_error(validation_.description() + " validation is not on the GPU path: " + refusal.what);
+      }
     case DataTypeValidation::Temporal:
       evaluation_error(validation_.description() + " validation compares with CURRENT_DATE or date texts "
                        "(not on the GPU path)");
@@ -194,10 +232,22 @@ ConstraintResult DataTypeConstraint::evaluate(const Inputs &in) const {
       if (r.distinct > 0)
         evaluation_error(std::to_string(r.distinct) + " rows do not fit Int32: the reference's query fails on "
                          "CAST(" + column_ + " AS INT), which is not TRY_CAST");
-      const double rate = (double)r.matches / (double)r.non_null;  // (0 / 0: NaN, a Failure)
-      const std::string msg = pct1(rate * 100.0) + "% of values satisfy " + validation_.description();
-      if (rate >= 1.0) return {ConstraintStatus::Success, rate, msg};
-      return ConstraintResult::failure_with_metric(rate, msg);
+      return rate_verdict((double)r.matches, (double)r.non_null, validation_.description());
+    }
+    case DataTypeValidation::String: {  // :383-439: COUNT(*) and the valid rows, WHERE col IS NOT NULL
+      if (!string_functions_) return plan(), ConstraintResult::success();  // (plan() throws the validation's error)
+      if (!in.list_arrow_types.empty() && !in.list_arrow_types[0].empty() && !in.list_arrow_types[0][0].empty()) {
+        const std::string &t = in.list_arrow_types[0][0];
+        const bool dict_of_strings = t.compare(0, 10, "Dictionary") == 0 && t.find("Utf8") != std::string::npos;
+        if (t != "Utf8" && t != "LargeUtf8" && t != "Utf8View" && !dict_of_strings)
+          evaluation_error(validation_.description() + " validation reads a string column: column '" + column_ +
+                           "' is declared " + t);
+      }
+      // total = rows seen, matches = satisfied, non_null = rows on which the predicate is not UNKNOWN -- the non-NULL
+      // rows, but for `col IS NOT NULL`, which is never UNKNOWN and TRUE on exactly the non-NULL rows
+      const tgx_result &r = *in.results.at(0);
+      const int64_t considered = validation_.string.kind == StringTypeValidation::ValidUtf8 ? r.matches : r.non_null;
+      return rate_verdict((double)r.matches, (double)considered, validation_.description());
     }
     default:
       return plan(), ConstraintResult::success();  // (plan() throws the validation's error)
@@ -207,7 +257,8 @@ ConstraintResult DataTypeConstraint::evaluate(const Inputs &in) const {
 // {"type": "datatype", "column": c, "validation": "specific_type" ("data_type") | "consistency" ("threshold") |
 //  "numeric" ("numeric": non_negative | positive | integer | range ("min", "max": numbers, or "inf" / "-inf" / "NaN") |
 //  finite) | "string" ("string": not_empty | valid_utf8 | not_blank | max_bytes ("max_bytes")) | "temporal"
-//  ("temporal": past_date | future_date | date_range ("start", "end") | valid_timezone) | "custom" ("sql_predicate")}
+//  ("temporal": past_date | future_date | date_range ("start", "end") | valid_timezone) | "custom" ("sql_predicate"),
+//  "string_functions_on_device"? (an opt-in: the String validations on the device)}
 std::shared_ptr<Constraint> datatype_from_json(const json::Value &c) {
   const std::string v = c.get_str("validation");
   DataTypeValidation d;
@@ -239,7 +290,9 @@ std::shared_ptr<Constraint> datatype_from_json(const json::Value &c) {
   } else {
     throw TermError{TermError::Internal, "unknown datatype validation '" + v + "'"};
   }
-  return std::make_shared<DataTypeConstraint>(c.get_str("column"), std::move(d));
+  auto out = std::make_shared<DataTypeConstraint>(c.get_str("column"), std::move(d));
+  if (c.get("string_functions_on_device")) out->string_functions_on_device(c.get_bool("string_functions_on_device"));
+  return out;
 }
 
 Check::Builder &Check::Builder::has_consistent_data_type(std::string column, double threshold) {

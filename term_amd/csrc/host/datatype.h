@@ -1,8 +1,10 @@
 // datatype.h -- DataTypeConstraint (TG/constraints/datatype.rs) over TGX_CHECK_VALUE_RULE: the numeric NonNegative,
 // Positive, Integer and Range validations are one scan on the device; SpecificType and Consistency need no scan beyond
 // the one that says the column exists; Finite and every String, Temporal and Custom validation are the constraint's own
-// error (the caller hands such a constraint to the stock path).  Included by term_guard.h's users through
-// term_guard.cpp and host_abi.cpp.
+// error (the caller hands such a constraint to the stock path).  The four String validations run on the device after
+// string_functions_on_device(true), an opt-in: one TGX_CHECK_ROW_PREDICATE request on [column], built from the SQL of
+// datatype.rs:161-175 by host/custom_sql.h's compiler under its dialect string_functions.  Included by term_guard.h's
+// users through term_guard.cpp and host_abi.cpp.
 #pragma once
 #include "json.h"
 #include "term_guard.h"
@@ -86,11 +88,18 @@ class DataTypeConstraint : public Constraint {
   std::vector<SpecRequest> plan() const override;
   ConstraintResult evaluate(const Inputs &in) const override;
   const DataTypeValidation &validation() const { return validation_; }
+  // an opt-in: a String validation plans a ROW_PREDICATE request instead of being the constraint's error.  Every other
+  // validation answers as without it
+  DataTypeConstraint &string_functions_on_device(bool on) { string_functions_ = on; return *this; }
+  bool string_functions() const { return string_functions_; }
+  // the predicate of a String validation, as datatype.rs:161-175 writes it (the column quoted)
+  std::string string_predicate() const;
   std::string description() const;  // metadata(): "Validates {description} for column '{column}'"
 
  private:
   std::string column_;
   DataTypeValidation validation_;
+  bool string_functions_ = false;
 };
 
 // a numeric validation -> the device's rule.  Range {min, max}: the reference prints the bounds with Rust's `{}` and

@@ -9,6 +9,7 @@
 #include "analyzers.h"
 #include "custom_sql.h"
 #include "datatype.h"
+#include "../kernels/string_leaf.h"
 #include "../kernels/typeclass_lex.h"
 #include "value_counts.h"
 #include "temporal.h"
@@ -358,6 +359,62 @@ extern "C" tgx_status tgx_host_row_predicate_json(const char *expression, char *
     return hfail(err, TGX_INTERNAL, e.what());
   } catch (...) {
     return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_row_predicate_json_ex(const char *expression, const char *options_json, char **out_json,
+                                                     tgx_error *err) {
+  if (!expression || !out_json) return hfail(err, TGX_INVALID_ARGUMENT, "NULL argument");
+  *out_json = nullptr;
+  try {
+    PredicateDialect dialect;
+    if (options_json) {
+      json::Value o;
+      std::string perr;
+      if (!json::parse(options_json, &o, &perr)) return hfail(err, TGX_INVALID_ARGUMENT, "options JSON: " + perr);
+      if (!o.is(json::Value::Object)) return hfail(err, TGX_INVALID_ARGUMENT, "options must be a JSON object");
+      dialect.string_functions = o.get("string_functions") && o.get_bool("string_functions");
+    }
+    *out_json = dup_string(row_predicate_json(compile_row_predicate(expression, dialect)));
+    return TGX_OK;
+  } catch (const PredicateRefusal &r) {
+    return hfail(err, TGX_UNSUPPORTED, "the expression is not on the GPU path: " + r.what);
+  } catch (const TermError &e) {
+    return hfail(err, TGX_INVALID_ARGUMENT, e.display());
+  } catch (const std::bad_alloc &) {
+    return hfail(err, TGX_OUT_OF_MEMORY, "host allocation failed (std::bad_alloc)");
+  } catch (const std::exception &e) {
+    return hfail(err, TGX_INTERNAL, e.what());
+  } catch (...) {
+    return hfail(err, TGX_INTERNAL, "unknown C++ exception");
+  }
+}
+
+extern "C" tgx_status tgx_host_string_leaf(int32_t kind, int32_t op, uint32_t flags, int64_t lit_i, const uint8_t *pattern,
+                                           uint32_t pattern_len, const uint8_t *value, uint64_t value_len, int *out) {
+  if (!out || (!pattern && pattern_len) || (!value && value_len)) return TGX_INVALID_ARGUMENT;
+  // (the value's words as the kernel would see them were its first byte where `value` points)
+  tgx::SlHostFetch f{value, value_len, (uint32_t)((uintptr_t)value & 3)};
+  const bool ordered = op >= TGX_PRED_LT && op <= TGX_PRED_GE;
+  switch (kind) {
+    case TGX_PRED_STR_CMP:
+      if (!ordered || flags) return TGX_INVALID_ARGUMENT;
+      *out = tgx::sl::order(f, value_len, (uint32_t)op, pattern, pattern_len);
+      return TGX_OK;
+    case TGX_PRED_STR_LENGTH:
+      if (!(ordered || op == TGX_PRED_EQ) || (flags & ~(uint32_t)TGX_PRED_LENGTH_IN_BYTES)) return TGX_INVALID_ARGUMENT;
+      *out = tgx::sl::length(f, value_len, (uint32_t)op, lit_i, (flags & TGX_PRED_LENGTH_IN_BYTES) != 0);
+      return TGX_OK;
+    case TGX_PRED_STR_LIKE:
+      if (flags || (pattern_len && memchr(pattern, 0x5C, pattern_len))) return TGX_INVALID_ARGUMENT;
+      *out = tgx::sl::like(f, value_len, pattern, pattern_len, tgx::sl::like_min_len(pattern, pattern_len));
+      return TGX_OK;
+    case TGX_PRED_STR_BLANK:
+      if (flags) return TGX_INVALID_ARGUMENT;
+      *out = tgx::sl::blank(f, value_len);
+      return TGX_OK;
+    default:
+      return TGX_INVALID_ARGUMENT;
   }
 }
 

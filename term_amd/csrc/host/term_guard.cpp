@@ -1838,10 +1838,12 @@ void add_constraint_from_json(Check::Builder &b, const json::Value &c) {
   } else if (type == "datatype") {
     b.constraint(datatype_from_json(c));
   } else if (type == "custom_sql") {
-    // {"type": "custom_sql", "expression", "hint"?}
+    // {"type": "custom_sql", "expression", "hint"?, "string_functions_on_device"? (an opt-in: LIKE, LENGTH, TRIM(c) = ''
+    //  and string order on the device)}
     const json::Value *hint = c.get("hint");
     b.satisfies(c.get_str("expression"),
-                hint && hint->is(json::Value::String) ? std::optional<std::string>(hint->str) : std::nullopt);
+                hint && hint->is(json::Value::String) ? std::optional<std::string>(hint->str) : std::nullopt,
+                c.get("string_functions_on_device") && c.get_bool("string_functions_on_device"));
   } else if (type == "histogram") {
     // {"type": "histogram", "column", "measures": [{"measure", "assertion", "n"?, "value"?}, ..], "description"?,
     //  "max_distinct"? (default 10000)}: every measure must hold

@@ -599,7 +599,9 @@ class Check::Builder {
   Builder &has_consistent_data_type(std::string column, double threshold);
   // core/check.rs:685-694: pushes CustomSqlConstraint::new(expression, hint); throws TermError (ValidationFailed) where
   // the reference's builder panics on the constructor's Err (host/custom_sql.h)
-  Builder &satisfies(std::string sql_expression, std::optional<std::string> hint = std::nullopt);
+  // string_functions_on_device: the constraint's opt-in of that name
+  Builder &satisfies(std::string sql_expression, std::optional<std::string> hint = std::nullopt,
+                     bool string_functions_on_device = false);
   // core/check.rs has_histogram / has_histogram_with_description: pushes HistogramConstraint::new[_with_description]
   // (host/value_counts.h; max_distinct bounds the values the device counts, default 10000)
   Builder &has_histogram(std::string column, std::function<bool(const Histogram &)> assertion);

@@ -24,13 +24,19 @@
 //   general     row_predicate_general_kernel: any column is a string layout.  A row per lane; a row's components are
 //               read once through tuple_key.h's tuple_component (shared, not copied; a dictionary column is followed to
 //               its entry, an index outside the dictionary is a NULL row).  STR_EQ compares the length first, then the
-//               bytes against the literal pool of the descriptor.
+//               bytes against the literal pool of the descriptor.  STR_CMP, STR_LENGTH, STR_LIKE and STR_BLANK are the
+//               functions of string_leaf.h over word_fetch.h's TcWordFetch (aligned 32-bit words, nothing outside the
+//               words that hold a byte of the value); a workgroup copies the task's literal pool into LDS once, and
+//               STR_CMP and STR_LIKE read their literal from there -- a LIKE pattern is indexed per lane.  IS_NULL,
+//               STR_LENGTH in bytes and LIKE's length test read no byte of a value.
 #include <hip/hip_runtime.h>
 
 #include "bin_count.h"
 #include "device_types.h"
 #include "rowpredicate_types.h"
+#include "string_leaf.h"
 #include "tuple_key.h"
+#include "word_fetch.h"
 
 namespace tgx {
 
@@ -247,11 +253,15 @@ __global__ __launch_bounds__(kRowPredBlock) void row_predicate_numeric_kernel(co
   else rp_dispatch<8>(task, counts);
 }
 
-__global__ __launch_bounds__(kRowPredBlock) void row_predicate_general_kernel(const RowPredTask *__restrict__ tasks,
-                                                                              unsigned long long *__restrict__ counts) {
+// (5 waves a SIMD, what the kernel had before the string leaves of string_leaf.h: the bound holds it at 96 VGPRs)
+__global__ __launch_bounds__(kRowPredBlock, 5) void row_predicate_general_kernel(const RowPredTask *__restrict__ tasks,
+                                                                                 unsigned long long *__restrict__ counts) {
   const RowPredTask &task = tasks[blockIdx.y];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int n_cols = task.d.n_cols, n_leaves = (int)task.n_leaves;
+  __shared__ uint8_t pool[kRowPredMaxLiteralBytes];
+  for (int k = (int)threadIdx.x; k < kRowPredMaxLiteralBytes; k += (int)blockDim.x) pool[k] = task.literals[k];
+  __syncthreads();
   uint32_t satisfied = 0, unknown = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < task.d.length; i += stride) {
     TupleComp comps[kMaxTupleCols];
@@ -285,6 +295,15 @@ __global__ __launch_bounds__(kRowPredBlock) void row_predicate_general_kernel(co
         } else if (kind == kRpCmpColumns && L.strings) {
           known = known && B.kind != 0;
           if (known && A.len == B.len) res = rp_bytes_equal(A.p, B.p, A.len);
+        } else if (kind >= kRpStrCmp) {  // (lit_offset + lit_len <= the pool's size: the setter)
+          if (known) {
+            TcWordFetch fetch;
+            fetch.p = A.p;
+            if (kind == kRpStrLength) res = sl::length(fetch, A.len, L.op, L.lit, L.strings != 0);
+            else if (kind == kRpStrBlank) res = sl::blank(fetch, A.len);
+            else if (kind == kRpStrCmp) res = sl::order(fetch, A.len, L.op, pool + L.lit_offset, L.lit_len);
+            else res = sl::like(fetch, A.len, pool + L.lit_offset, L.lit_len, (uint32_t)L.lit);
+          }
         } else {
           const bool columns = kind == kRpCmpColumns;
           known = known && !(columns && B.kind == 0);

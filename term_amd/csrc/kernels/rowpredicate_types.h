@@ -12,6 +12,7 @@
 namespace tgx {
 
 enum { kRpIsNull = 1, kRpCmpLiteral = 2, kRpCmpColumns = 3, kRpStrEq = 4 };  // TGX_PRED_IS_NULL ..
+enum { kRpStrCmp = 6, kRpStrLength = 7, kRpStrLike = 8, kRpStrBlank = 9 };   // TGX_PRED_STR_CMP .. (5 is no kind)
 enum { kRpEq = 1, kRpLt = 2, kRpLe = 3, kRpGt = 4, kRpGe = 5 };              // TGX_PRED_EQ ..
 enum { kRpPush = 1, kRpAnd = 2, kRpOr = 3, kRpNot = 4 };                     // TGX_PRED_PUSH ..
 
@@ -25,9 +26,11 @@ struct RowPredLeaf {
   uint8_t kind, op, col, col2;
   uint8_t keyed;             // the sides are compared as totalOrder keys (a float column, or a double literal)
   uint8_t a_float, b_float;  // keyed: col's / col2's bits are doubles already (otherwise int64, converted)
-  uint8_t strings;           // CMP_COLUMNS of two string columns: bytes
+  uint8_t strings;           // CMP_COLUMNS of two string columns: bytes.  STR_LENGTH: the length is in bytes
   uint32_t lit_offset, lit_len;
-  int64_t lit;  // CMP_LITERAL: the int64 literal, or the key of the double literal when keyed
+  // CMP_LITERAL: the int64 literal, or the key of the double literal when keyed.  STR_LENGTH: the length compared
+  // with.  STR_LIKE: the pattern's bytes that are not '%' (string_leaf.h's like_min_len)
+  int64_t lit;
 };
 
 struct RowPredTask {

@@ -15,9 +15,10 @@
 //                     and adds its count to the class with 64-bit adds.  Rows of NULL entries and of indices outside the
 //                     dictionary are counted nowhere: they are NULL rows.
 //
-// The bytes of a value are fetched through TcWordFetch: the naturally aligned 32-bit word that holds the byte, kept
-// until the lexer leaves it.  Such a word always holds at least one byte of the value, so it lies in the value's
-// allocation (allocations start and end on word boundaries); nothing else outside [p, p + len) is read.
+// The bytes of a value are fetched through TcWordFetch (word_fetch.h, shared with the string leaves of
+// rowpredicate.hip): the naturally aligned 32-bit word that holds the byte, kept until the lexer leaves it.  Such a word
+// always holds at least one byte of the value, so it lies in the value's allocation (allocations start and end on word
+// boundaries); nothing else outside [p, p + len) is read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,26 +28,11 @@
 #include "device_types.h"
 #include "dict_count.h"
 #include "typeclass_types.h"
+#include "word_fetch.h"
 
 namespace tgx {
 
 namespace {
-
-typedef const uint32_t __attribute__((address_space(1))) *global_u32_ptr;
-
-struct TcWordFetch {
-  uintptr_t p;       // the value's first byte
-  uintptr_t at = 1;  // the address of the word in `w` (1: none yet; a word's address is a multiple of 4)
-  uint32_t w = 0;
-  __device__ __forceinline__ uint8_t operator()(uint64_t i) {
-    const uintptr_t a = p + (uintptr_t)i, wa = a & ~(uintptr_t)3;
-    if (wa != at) {
-      w = *(global_u32_ptr)wa;
-      at = wa;
-    }
-    return (uint8_t)(w >> (8u * (uint32_t)(a & 3)));
-  }
-};
 
 __device__ __forceinline__ int tc_classify(uintptr_t p, uint64_t len) {
   TcWordFetch f;

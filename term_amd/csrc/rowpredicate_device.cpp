@@ -12,6 +12,7 @@
 
 #include "api_internal.h"
 #include "kernels/rowpredicate_types.h"
+#include "kernels/string_leaf.h"
 
 namespace tgx {
 void launch_row_predicate(const RowPredTask *tasks, int n_tasks, bool numeric, int blocks_per_task,
@@ -24,7 +25,10 @@ static_assert(kRowPredMaxLeaves == TGX_PRED_MAX_LEAVES && kRowPredMaxOps == TGX_
                   kMaxTupleCols == TGX_PRED_MAX_COLUMNS,
               "the device's limits are the ABI's");
 static_assert(kRpIsNull == TGX_PRED_IS_NULL && kRpStrEq == TGX_PRED_STR_EQ && kRpEq == TGX_PRED_EQ &&
-                  kRpGe == TGX_PRED_GE && kRpPush == TGX_PRED_PUSH && kRpNot == TGX_PRED_NOT,
+                  kRpGe == TGX_PRED_GE && kRpPush == TGX_PRED_PUSH && kRpNot == TGX_PRED_NOT &&
+                  kRpStrCmp == TGX_PRED_STR_CMP && kRpStrLength == TGX_PRED_STR_LENGTH &&
+                  kRpStrLike == TGX_PRED_STR_LIKE && kRpStrBlank == TGX_PRED_STR_BLANK && (int)sl::kEq == TGX_PRED_EQ &&
+                  (int)sl::kGe == TGX_PRED_GE,
               "the device's codes are the ABI's");
 
 struct PredHost {
@@ -47,6 +51,8 @@ TypeClass class_of(int type) {
 }
 
 bool reads_values(const tgx_row_predicate_leaf &l) { return l.kind != TGX_PRED_IS_NULL; }
+// a leaf that fits string layouts only (kind 5 is no kind)
+bool string_leaf(int kind) { return kind == TGX_PRED_STR_EQ || (kind >= TGX_PRED_STR_CMP && kind <= TGX_PRED_STR_BLANK); }
 
 struct NoRange {};
 
@@ -249,6 +255,15 @@ struct PredCheck final : SideState<PredKind> {
             L.keyed = L.a_float || L.b_float;
           }
           break;
+        case TGX_PRED_STR_LENGTH:
+          fits = a == kClassString;
+          L.strings = (l.flags & TGX_PRED_LENGTH_IN_BYTES) != 0;
+          L.lit = l.lit_i;
+          break;
+        case TGX_PRED_STR_LIKE:
+          fits = a == kClassString;
+          L.lit = (int64_t)sl::like_min_len(p.literals + l.lit_offset, l.lit_len);
+          break;
         default:
           fits = a == kClassString;
           break;
@@ -371,7 +386,7 @@ tgx_status rowpredicate_check_column(const tgx_plan *plan, int column, const tgx
       if (cls == kClassOther)
         return fail(err, TGX_UNSUPPORTED, "column %d: ROW_PREDICATE takes %s columns under IS NULL only (spec %d, leaf %u)",
                     column, c.type == TGX_BOOL ? "Boolean" : "UInt64", t.spec_index, j);
-      if (l.kind == TGX_PRED_STR_EQ && cls != kClassString)
+      if (string_leaf(l.kind) && cls != kClassString)
         return fail(err, TGX_UNSUPPORTED, "column %d: a string leaf of the ROW_PREDICATE on a numeric column (spec %d, leaf %u)",
                     column, t.spec_index, j);
       if (l.kind == TGX_PRED_CMP_LITERAL && cls == kClassString)
@@ -419,7 +434,7 @@ extern "C" tgx_status tgx_plan_set_row_predicate(tgx_plan *plan, size_t spec_ind
   for (uint32_t j = 0; j < p->n_leaves; j++) {
     const tgx_row_predicate_leaf &l = p->leaves[j];
     tgx_row_predicate_leaf &o = q.leaves[j];
-    if (l.kind < TGX_PRED_IS_NULL || l.kind > TGX_PRED_STR_EQ)
+    if (l.kind < TGX_PRED_IS_NULL || l.kind > TGX_PRED_STR_BLANK || l.kind == 5)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: unknown leaf kind %d", spec_index, j, l.kind);
     if (l.col < 0 || l.col >= t.n_columns)
       return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u names column slot %d of a list of %d", spec_index, j, l.col,
@@ -445,12 +460,33 @@ extern "C" tgx_status tgx_plan_set_row_predicate(tgx_plan *plan, size_t spec_ind
       o.lit_i = l.lit_i;
       o.lit_f = l.lit_f;
     }
-    if (l.kind == TGX_PRED_STR_EQ) {
+    if (l.kind == TGX_PRED_STR_CMP) {
+      if (l.op == TGX_PRED_EQ)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: STR_CMP orders (LT .. GE): use STR_EQ for =", spec_index, j);
+      if (l.op < TGX_PRED_LT || l.op > TGX_PRED_GE)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: unknown comparison %d", spec_index, j, l.op);
+      o.op = l.op;
+    }
+    if (l.kind == TGX_PRED_STR_LENGTH) {
+      if (l.op < TGX_PRED_EQ || l.op > TGX_PRED_GE)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: unknown comparison %d", spec_index, j, l.op);
+      if (l.flags & ~(uint32_t)TGX_PRED_LENGTH_IN_BYTES)
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: unknown flags 0x%x", spec_index, j, l.flags);
+      o.op = l.op;
+      o.flags = l.flags;
+      o.lit_i = l.lit_i;
+    }
+    if ((l.kind == TGX_PRED_STR_CMP || l.kind == TGX_PRED_STR_LIKE || l.kind == TGX_PRED_STR_BLANK) && l.flags)
+      return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: unknown flags 0x%x", spec_index, j, l.flags);
+    if (l.kind == TGX_PRED_STR_EQ || l.kind == TGX_PRED_STR_CMP || l.kind == TGX_PRED_STR_LIKE) {
       if (l.lit_offset > p->n_literal_bytes || l.lit_len > p->n_literal_bytes - l.lit_offset)
         return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u names literal bytes [%u, %u + %u) of a pool of %u", spec_index,
                     j, l.lit_offset, l.lit_offset, l.lit_len, p->n_literal_bytes);
       o.lit_offset = l.lit_offset;
       o.lit_len = l.lit_len;
+      if (l.kind == TGX_PRED_STR_LIKE && memchr(p->literals + l.lit_offset, 0x5C, l.lit_len))
+        return fail(err, TGX_INVALID_ARGUMENT, "spec %zu: leaf %u: a LIKE pattern may not hold a backslash (0x5C): there is no escape",
+                    spec_index, j);
     }
   }
   int depth = 0;

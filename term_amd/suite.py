@@ -287,10 +287,13 @@ class CheckBuilder:
         """core/check.rs:651-657: DataTypeConstraint::type_consistency(column, threshold)"""
         return self.constraint(DataTypeConstraint.type_consistency(column, threshold))
 
-    def satisfies(self, sql_expression, hint=None):
+    def satisfies(self, sql_expression, hint=None, string_functions_on_device=False):
         """core/check.rs:685-694: CustomSqlConstraint::new(sql_expression, hint); raises where the reference's builder
-        panics on the constructor's Err"""
-        return self.constraint(CustomSqlConstraint(sql_expression, hint))
+        panics on the constructor's Err.  string_functions_on_device: the constraint's opt-in of that name"""
+        c = CustomSqlConstraint(sql_expression, hint)
+        if string_functions_on_device:
+            c.string_functions_on_device(True)
+        return self.constraint(c)
 
     def has_histogram(self, column, measures, max_distinct=10000):
         """Check::has_histogram: HistogramConstraint.new(column, measures) -- `measures` is what stands for the
@@ -735,13 +738,24 @@ class DataTypeConstraint:
     device (TGX_CHECK_VALUE_RULE); SpecificType reads the column's Arrow type, Consistency is the reference's placeholder;
     Finite and every String, Temporal and Custom validation evaluate to the constraint's own error.  The constructor
     raises what DataTypeConstraint::new returns as Err: a column name that is no identifier, a consistency threshold
-    outside [0, 1]"""
+    outside [0, 1].
+
+    string_functions_on_device(True) is an opt-in for the four String validations: NotEmpty (LENGTH(c) > 0), ValidUtf8
+    (c IS NOT NULL), NotBlank (TRIM(c) != '') and MaxBytes (OCTET_LENGTH(c) <= n) then plan one TGX_CHECK_ROW_PREDICATE
+    request on [column], count the valid rows among the non-NULL ones and answer with the reference's
+    "{:.1}% of values satisfy .." verdict; a column declared non-string is the constraint's error.  Without it, and for
+    every other validation with or without it, the constraint answers as it did"""
 
     def __init__(self, column, validation):
         validate_identifier(column)
         if validation.get("validation") == "consistency" and not 0.0 <= validation["threshold"] <= 1.0:
             raise TgxError(1, "Configuration error: Threshold must be between 0.0 and 1.0")
         self.spec = dict(validation, type="datatype", column=column)
+
+    def string_functions_on_device(self, on=True):
+        """the opt-in of the class's docstring; the key is written into the constraint's JSON only when this is called"""
+        self.spec["string_functions_on_device"] = bool(on)
+        return self
 
     @staticmethod
     def non_negative(column):
@@ -761,7 +775,13 @@ class CustomSqlConstraint:
     the library's closed predicate subset (row_predicate(); include/tgx.h TGX_CHECK_ROW_PREDICATE) and counted on the
     device; one outside the subset evaluates to the constraint's own error ("... not on the GPU path: <what>").  The
     constructor raises what CustomSqlConstraint::new returns as Err (validate_sql_expression, :100-190): of several
-    forbidden words the first in the list's written order is named"""
+    forbidden words the first in the list's written order is named.
+
+    string_functions_on_device(True) is an opt-in: the expression is then compiled under the dialect that also takes
+    `col [NOT] LIKE 'pattern'` (no escapes: a backslash is refused), LENGTH / CHAR_LENGTH / CHARACTER_LENGTH /
+    OCTET_LENGTH of a column against an integer, TRIM(col) = '' / <> '' and order comparisons of a string column with a
+    string literal, by bytes (row_predicate(expression, string_functions=True)).  Without it such an expression is "not
+    on the GPU path", as it was"""
 
     FORBIDDEN = ("DROP", "DELETE", "INSERT", "UPDATE", "CREATE", "ALTER", "TRUNCATE", "GRANT", "REVOKE", "EXECUTE", "EXEC",
                  "CALL", "MERGE", "REPLACE", "RENAME", "MODIFY", "SET", "COMMIT", "ROLLBACK", "SAVEPOINT", "BEGIN", "START",
@@ -777,6 +797,11 @@ class CustomSqlConstraint:
             self.spec["hint"] = hint
 
     try_new = classmethod(lambda cls, expression, hint=None: cls(expression, hint))
+
+    def string_functions_on_device(self, on=True):
+        """the opt-in of the class's docstring; the key is written into the constraint's JSON only when this is called"""
+        self.spec["string_functions_on_device"] = bool(on)
+        return self
 
     @classmethod
     def refusal(cls, sql):
@@ -1358,12 +1383,16 @@ def compliance_forbidden_keyword(predicate):
     return next((w for w in COMPLIANCE_FORBIDDEN if w in lower), None)
 
 
-def ComplianceAnalyzer(name, predicate):
+def ComplianceAnalyzer(name, predicate, string_functions_on_device=False):
     """advanced/compliance.rs:37-204: the fraction of rows on which `predicate` is TRUE, counted on the device under the
     library's closed predicate subset (TGX_CHECK_ROW_PREDICATE).  State {"compliant_count", "total_count"}; the metric is
     a Double, 1.0 on an empty table; metric_key is "compliance".  A forbidden keyword or a predicate outside the subset
-    is the analyzer's error when it runs, as the reference validates in compute_state_from_data"""
-    return _Analyzer({"type": "compliance", "name": name, "predicate": predicate})
+    is the analyzer's error when it runs, as the reference validates in compute_state_from_data.
+    string_functions_on_device: CustomSqlConstraint's opt-in of that name (LIKE, LENGTH, TRIM(c) = '', string order)"""
+    spec = {"type": "compliance", "name": name, "predicate": predicate}
+    if string_functions_on_device:
+        spec["string_functions_on_device"] = True
+    return _Analyzer(spec)
 
 
 def EntropyAnalyzer(column, max_unique_values=10000, arrow_type=None):
@@ -1492,6 +1521,7 @@ def _host():
         L.tgx_host_temporal_params_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_value_rule_params_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_row_predicate_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), E]
+        L.tgx_host_row_predicate_json_ex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), E]
         L.tgx_host_validate_identifier.argtypes = [C.c_char_p, E]
         L.tgx_host_assertion_json.argtypes = [C.c_char_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), E]
         L.tgx_host_run_analysis_json.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_Column),
@@ -1563,13 +1593,18 @@ def value_rule_params(constraint):
     return json.loads(_take(out))
 
 
-def row_predicate(expression):
+def row_predicate(expression, string_functions=False):
     """what the predicate compiler of Check.satisfies / ComplianceAnalyzer makes of `expression`
     (tgx_host_row_predicate_json): {"columns", "leaves", "program", "literals_hex"}; TgxError (TGX_UNSUPPORTED) naming
-    the first thing outside the subset otherwise.  Needs no device"""
+    the first thing outside the subset otherwise.  string_functions: compile under the dialect of that name
+    (tgx_host_row_predicate_json_ex), what string_functions_on_device opts into.  Needs no device"""
     out = C.c_char_p()
     err = _Error()
-    _host_check(_host().tgx_host_row_predicate_json(expression.encode(), C.byref(out), C.byref(err)), err)
+    if string_functions:
+        options = json.dumps({"string_functions": True}).encode()
+        _host_check(_host().tgx_host_row_predicate_json_ex(expression.encode(), options, C.byref(out), C.byref(err)), err)
+    else:
+        _host_check(_host().tgx_host_row_predicate_json(expression.encode(), C.byref(out), C.byref(err)), err)
     return json.loads(_take(out))
 
 
